@@ -9,11 +9,19 @@ poison_rate 0.1, BOX_14 trigger, fp32, synthetic data.  One "step" = poison-blen
         bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line on rank 0.  Inputs (uint8 images, noise, timesteps) are resident in HBM before the timed
-region, which carries no instrumentation.  `roofline` is measured live with hipEvent pairs around every GEMM-class
-launch (bd_prof_*) of extra untimed steps behind it, `cpu_baseline` is the CPU oracle (pure PyTorch fp32 restatement
-of the reference path) timed on this box's host cores.  The line also carries `sampling` (DDIM-50 x 2048, DDPM-1000 x
-256), `celeba` (the 256x256 DDPM-CELEBA-HQ-256 step at B = 4) -- each with its own `roofline` and `cpu_baseline` --
-`sustained`, and `dp_path_at_world_1` (trainer.py's data-parallel branch under RCCL on a 1-rank group).
+region, which carries no instrumentation.  A plain run sets up, warms up, times exactly --steps steps, writes the
+last timed step's outputs when --dump-outputs DIR is given, and prints the line; nothing else runs.
+
+--full adds the side measurements behind the timed region (each can still be switched off by its --no-* option):
+`roofline`, measured live with hipEvent pairs around every GEMM-class launch (bd_prof_*) of extra untimed steps,
+`cpu_baseline`, the CPU oracle (pure PyTorch fp32 restatement of the reference path) timed on the host cores,
+`sampling` (DDIM-50 x 2048, DDPM-1000 x 256), `celeba` (the 256x256 DDPM-CELEBA-HQ-256 step at B = 4) -- each with
+its own `roofline` and `cpu_baseline` -- `fid_features`, `sustained`, `dp_path_at_world_1` (trainer.py's
+data-parallel branch under RCCL on a 1-rank group) and, at N > 1, the data-parallel sweeps (`distributed.measured`).
+
+--dump-outputs DIR writes, after the timed steps and before anything else runs, what the last timed step handed
+its caller (see dump_train_outputs) as DIR/<name>.npy; the inputs are seeded, so the same arguments give the same
+inputs on every run and two builds can be compared output for output.
 """
 import argparse
 import ctypes
@@ -575,6 +583,33 @@ def timed_steps(step, first, n, barrier, dev, world, prof=None):
     return dt, loss, per
 
 
+DUMP_SAMPLE = 1 << 21         # elements per sampled array (8 MB of float32 each)
+DUMP_SEED = 20240601
+
+
+def dump_train_outputs(out_dir, model, eng, loss):
+    """--dump-outputs: what TrainEngine.train_step handed its caller after the LAST timed step, as .npy files in `out_dir`:
+    loss.npy (the step's loss, float32 scalar), grad_norm.npy (its pre-clip gradient norm, float32 scalar), and a fixed, seeded
+    sample of DUMP_SAMPLE elements (the same indices on every run) of weights.npy (the weights after the step's clip + Adam update)
+    and grads.npy (the step's gradient).  Both samples index the parameters in the logical state-dict layout, keys sorted, so that
+    builds with different storage layouts of the flat buffer compare element for element.  Called before any untimed step runs."""
+    torch.cuda.synchronize()
+    w, g = model.state_dict(), model.logical_grads(eng.grads)
+    keys = sorted(w)
+    wf = torch.cat([w[k].reshape(-1) for k in keys])
+    gf = torch.cat([g[k].reshape(-1) for k in keys])
+    n = wf.numel()
+    idx = torch.randint(0, n, (min(DUMP_SAMPLE, n),), generator=torch.Generator().manual_seed(DUMP_SEED)).sort().values.to(wf.device)
+    arrays = {"loss": loss.detach().reshape(()).float().cpu().numpy(),
+              "grad_norm": eng.grad_norm.detach().reshape(()).float().cpu().numpy(),
+              "weights": wf[idx].float().cpu().numpy(),
+              "grads": gf[idx].float().cpu().numpy()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def measure_dp(eng, model, step, lib, barrier, dev, world, args, log, first):
     """N > 1, behind the contract region (every rank runs the same sequence, so collectives stay matched): (1) per-bucket collective time from
     events on the communication stream; (2) EXPOSED communication = the step with the collectives minus the same step with every part of the
@@ -673,7 +708,7 @@ def headline_line(out, detail_file=None):
     """The ONE JSON line of the contract, bounded (< HEADLINE_MAX_BYTES): the contract's keys, `roofline` and `cpu_baseline` of the timed
     workload, and for the riders (`sampling.*`, `celeba`, `fid_features`) value / ms_per_step / roofline.frac / roofline.traffic /
     cpu_baseline.value only.  Everything else -- per-class kernel tables, sweeps, per-bucket times, the notes saying how each figure was
-    taken -- is the DETAIL object `out`, written to `detail_file` (gpurun_out/bench_detail.json) and copied under profiles/ per round."""
+    taken -- is the DETAIL object `out`, written to `detail_file` (--detail-file) and copied under profiles/ per round."""
     h = {k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                                       "vs_baseline", "dtype", "data") if k in out}
     h["config"] = dict(out["config"])
@@ -762,17 +797,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default 128 for cifar, 4 for celeba)")
     ap.add_argument("--workload", default="cifar", choices=["cifar", "celeba", "ddim50", "ddpm1000", "pndm50", "anp", "fid"],
-                    help="cifar = BASELINE configs[1] (the metric; its line also carries the sampling loops and the 256x256 step as "
+                    help="cifar = BASELINE configs[1] (the metric; with --full its line also carries the sampling loops and the 256x256 step as "
                          "`sampling` / `celeba` objects); celeba = the 256x256 DDPM-CELEBA-HQ-256 topology alone; "
                          "ddim50 / ddpm1000 / pndm50 = one CIFAR sampling loop alone (samples/s, --batch samples per GPU, --steps ignored); "
                          "anp = one batch of the ANP defense loop on the CIFAR network (SURVEY f-4)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-prof", action="store_true")
-    ap.add_argument("--no-sampling", action="store_true", help="skip the DDIM-50 x 2048 and DDPM-1000 x 256 loops of the default line")
+    ap.add_argument("--no-sampling", action="store_true", help="skip the DDIM-50 x 2048 and DDPM-1000 x 256 loops of a --full line")
     ap.add_argument("--sampling-n", default="2048,256", help="samples per GPU of the DDIM-50 and DDPM-1000 loops (BASELINE configs[4]'s "
                                                              "eval_max_batch 2048; the reference's default eval batch 256)")
-    ap.add_argument("--no-fid", action="store_true", help="skip the FID feature-extractor measurement of the default line")
-    ap.add_argument("--no-celeba", action="store_true", help="skip the 256x256 batch-4 train step of the default line")
+    ap.add_argument("--no-fid", action="store_true", help="skip the FID feature-extractor measurement of a --full line")
+    ap.add_argument("--no-celeba", action="store_true", help="skip the 256x256 batch-4 train step of a --full line")
     ap.add_argument("--no-dp-probe", action="store_true", help="skip the N = 1 measurement of the data-parallel communication path "
                                                                "(TrainEngine(force_dp=True): RCCL on a 1-rank group)")
     ap.add_argument("--no-dp-sweep", action="store_true", help="N > 1: skip the bucket-size / weight-gradient-slot sweep and the exposed-communication "
@@ -790,14 +825,32 @@ def main():
                     help="1: replay the train step as one hipGraph (TrainEngine(use_graph=True)); sampled roofline steps stay eager")
     ap.add_argument("--mode", default=os.environ.get("BD_COMPUTE_MODE", "bf16x3"), choices=["f32", "bf16x3"],
                     help="contraction arithmetic: exact fp32 MFMA, or split-bf16 (hi+lo, 3 MFMAs, ~2^-16 rel. error)")
-    ap.add_argument("--detail-file", default=os.environ.get("BD_BENCH_DETAIL", os.path.join(ROOT, "gpurun_out", "bench_detail.json")),
+    ap.add_argument("--detail-file", default=os.environ.get("BD_BENCH_DETAIL"),
                     help="where the DETAIL object goes (per-class kernel tables, sweeps, per-bucket times, notes); the stdout line stays < 8 KB "
-                         "and names this file as `detail_file`; '' = do not write")
+                         "and names this file as `detail_file`; '' = do not write.  Default: $BD_BENCH_DETAIL, else bench_out/bench_detail.json "
+                         "with --full and no file without it")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements behind the timed region: roofline profile steps, sustained run, MFMA probe, data-parallel "
+                         "probe / sweeps, sampling loops, FID features, the 256x256 step and the CPU baselines (their --no-* options still apply)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="train workloads: write what the last timed step computed (loss, gradient norm, seeded samples of the updated weights and "
+                         "of the gradient) as DIR/<name>.npy, before any untimed step runs")
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-baseline-kind", default="train", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.cpu_baseline_worker:
         return _cpu_baseline_worker(args.cpu_baseline_kind)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.workload not in ("cifar", "celeba"):
+        ap.error(f"--dump-outputs covers the train workloads (cifar, celeba), not --workload {args.workload}")
+    if args.detail_file is None:
+        args.detail_file = os.path.join(ROOT, "bench_out", "bench_detail.json") if args.full else ""
+    if not args.full:
+        # a plain run times the headline step and nothing else: every side measurement stays off
+        args.no_cpu_baseline = args.no_prof = args.no_sampling = args.no_fid = args.no_celeba = True
+        args.no_dp_probe = args.no_dp_sweep = True
+        args.sustain = 0.0
 
     # ONE JSON line on stdout: native libraries print there too (RCCL: "Librccl path : ..."), so file descriptor 1 is pointed
     # at stderr for the life of the process and the line goes to a private duplicate of the original stdout
@@ -833,7 +886,7 @@ def main():
         return bench_sampling(args, world, rank, dev)
     if args.workload == "anp":
         return bench_anp(args, world, rank, dev)
-    if args.workload == "fid":         # the measure path's feature extractor alone (side measurement; also rides in the default line)
+    if args.workload == "fid":         # the measure path's feature extractor alone (side measurement; also rides in a --full line)
         res = run_fid_features(dev, batch=args.batch if args.batch > 0 else None)
         if rank == 0:
             emit({"metric": "FID InceptionV3 pool3 features, images/s (2048 CIFAR-size images)", "value": res["cifar32"]["images_per_s"],
@@ -866,6 +919,10 @@ def main():
     dt, loss, per_step = timed_steps(step, args.warmup, args.steps, barrier, dev, world)
     final_loss = float(loss)
     log(f"timed region done: {dt / args.steps * 1e3:.2f} ms/step")
+    dumped = None
+    if args.dump_outputs and rank == 0:      # before any untimed step moves the weights on
+        dumped = dump_train_outputs(args.dump_outputs, model, eng, loss)
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
     # roofline: hipEvent pairs around every GEMM-class launch (bd_prof_*) of PROF_STEPS extra, UNTIMED steps of the same
     # two-stream schedule, then of two more with the side stream off (stand-alone launch durations)
     PROF_STEPS = 3
@@ -882,7 +939,7 @@ def main():
         log(f"sustained: {n_sus} steps in {sdt:.1f} s = {sdt / n_sus * 1e3:.2f} ms/step")
 
     dp_meas = None
-    if world > 1 and not celeba:
+    if world > 1 and not celeba and args.full:
         try:
             dp_meas = measure_dp(eng, model, step, lib, barrier, dev, world, args, log, args.warmup + 4 * args.steps + 100000)
             log(f"dp: {dp_meas['ms_per_step']:.2f} ms/step, without collectives {dp_meas['ms_per_step_without_collectives']:.2f}")
@@ -952,7 +1009,7 @@ def main():
             dp_probe = {"error": f"{type(e).__name__}: {e}"}
 
     probe = None
-    if args.mode != "f32":
+    if args.mode != "f32" and args.full:
         # what the matrix pipe alone sustains on this board right now (register-operand MFMA loop, random bf16 operands)
         tf_r, tf_c = ctypes.c_double(), ctypes.c_double()
         L.check(lib.bd_mfma_probe(1, 40000, 12, ctypes.byref(tf_r), L.stream()), "bd_mfma_probe")
@@ -1059,6 +1116,8 @@ def main():
                                "note": "backward segments are fused into buckets of >= BD_DP_BUCKET_MB (32); when a bucket's last segment has run, "
                                        "its ranges of the flat fp32 gradient are all-reduced (sum; loss gradient pre-scaled by 1/world) from the "
                                        "communication stream while the next segments compute"}}
+        if dumped:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
         if sustained:
             out["sustained"] = sustained
         if not args.no_prof and classes:

@@ -1,7 +1,12 @@
-"""bench.py JSON line on stdin -> one row per kernel class (with BD_PROF_SHAPES=1: one per GEMM shape).
-usage: BD_PROF_SHAPES=1 python bench.py ... | python scripts/classes.py [kernel_classes|kernel_classes_standalone]"""
+"""bench.py detail object on stdin -> one row per kernel class (with BD_PROF_SHAPES=1: one per GEMM shape).
+usage: BD_PROF_SHAPES=1 python bench.py --full --detail-file d.json ...; python scripts/classes.py [kernel_classes|kernel_classes_standalone] < d.json"""
 import sys,json
-d=json.loads(sys.stdin.read().strip().splitlines()[-1])
+s=sys.stdin.read().strip()
+try:
+    d=json.loads(s)                       # the detail file (multi-line JSON)
+except ValueError:
+    d=json.loads(s.splitlines()[-1])      # a single JSON line
+
 print(d['ms_per_step'])
 tot=0
 for c in sorted(d[sys.argv[1] if len(sys.argv) > 1 else 'kernel_classes'], key=lambda c:-c['ms']):

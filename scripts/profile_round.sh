@@ -2,6 +2,7 @@
 # Round profile artifacts (run on the GPU box through gpurun): rocprofv3 kernel-trace summaries + bench JSON lines, then the
 # PMC traffic passes.  usage: scripts/profile_round.sh <tag>   -> gpurun_out/<tag>_*   (copy what is to be judged into profiles/)
 tag=${1:-r06}
+repo=$(cd "$(dirname "$0")/.." && pwd)      # the repository root
 out=$GRAFT_REPO_ROOT/gpurun_out
 TRAIN="--no-cpu-baseline --no-sampling --no-celeba --no-fid --no-dp-probe --sustain 0"     # the headline train step alone (what the kernel tables describe)
 cd /tmp && export TMPDIR=/tmp
@@ -10,12 +11,12 @@ rm -rf /tmp/rp
 rocprofv3 --kernel-trace --stats -d /tmp/rp -o r -- python $GRAFT_REPO_ROOT/bench.py --steps 8 --warmup 2 --no-prof $TRAIN > /tmp/rp.log 2>&1
 grep "^{\"metric\"" /tmp/rp.log | tail -1 > $out/${tag}_bench_under_rocprof.json
 python $GRAFT_REPO_ROOT/scripts/rocprof_summary.py $(find /tmp/rp -name "*.db" | head -1) 10 > $out/${tag}_train_step_b128_kernel_stats.txt
-# 2. the driver's command, unprofiled: the whole default line (train + sustained + sampling + celeba + CPU baselines)
+# 2. the benchmark unprofiled, with its side measurements: the whole --full line (train + sustained + sampling + celeba + CPU baselines)
 # (round 6: stdout carries the bounded headline, the full object goes to --detail-file)
-cd $GRAFT_REPO_ROOT && python bench.py --steps 20 --warmup 5 --detail-file $out/${tag}_bench_detail.json 2>/dev/null | tail -1 > $out/${tag}_bench.json
-cd $GRAFT_REPO_ROOT && python bench.py --steps 20 --warmup 5 --mode f32 $TRAIN --detail-file $out/${tag}_bench_f32.json 2>/dev/null | tail -1 > /dev/null
-cd $GRAFT_REPO_ROOT && python bench.py --workload celeba --steps 5 --warmup 2 --no-cpu-baseline --sustain 0 --detail-file $out/${tag}_bench_celeba256.json 2>/dev/null | tail -1 > /dev/null
-cd $GRAFT_REPO_ROOT && python bench.py --workload pndm50 --batch 2048 --no-cpu-baseline --detail-file $out/${tag}_bench_pndm50.json 2>/dev/null | tail -1 > /dev/null
+cd "$repo" && python bench.py --full --steps 20 --warmup 5 --detail-file $out/${tag}_bench_detail.json 2>/dev/null | tail -1 > $out/${tag}_bench.json
+cd "$repo" && python bench.py --full --steps 20 --warmup 5 --mode f32 $TRAIN --detail-file $out/${tag}_bench_f32.json 2>/dev/null | tail -1 > /dev/null
+cd "$repo" && python bench.py --full --workload celeba --steps 5 --warmup 2 --no-cpu-baseline --sustain 0 --detail-file $out/${tag}_bench_celeba256.json 2>/dev/null | tail -1 > /dev/null
+cd "$repo" && python bench.py --full --workload pndm50 --batch 2048 --no-cpu-baseline --detail-file $out/${tag}_bench_pndm50.json 2>/dev/null | tail -1 > /dev/null
 # 3. HBM traffic per kernel (FETCH_SIZE / WRITE_SIZE in separate --pmc passes)
 $GRAFT_REPO_ROOT/scripts/pmc_bench.sh bf16x3 > /dev/null 2>&1
 cp $out/pmc_bench_bf16x3.json $out/${tag}_pmc_bench_bf16x3.json

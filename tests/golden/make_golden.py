@@ -18,7 +18,7 @@ Fixtures:
   full_size.npz G10 BASELINE configs[1] at its real size (DDPM-CIFAR10-32 topology, B=128 train step) and the real
                     DDPM-CELEBA-HQ-256 network at 256x256, B=1 (forward + backward): what the reference computes, so the
                     full-size GPU tests compare with the reference and not with the product's other arithmetic mode
-  attn_planes.npz G11 AttentionBlock forward + backward at 16 x 16 (256 tokens, head dim 256; one and two heads): the shapes the
+  attn_planes.npz (+ attn_planes_512_y.npz, attn_planes_512_dx.npz) G11 AttentionBlock forward + backward at 16 x 16 (256 tokens, head dim 256; one and two heads): the shapes the
                     split-plane attention path takes (modules.npz has 8 x 8 / 4 x 4 blocks, which stay on the unfused path)
   full_size_b4.npz G12 the same 256x256 network at B = 4, the per-GPU batch of BASELINE configs[3] (four timesteps, per-sample output
                     slices + checksums, every gradient tensor's norm + leading elements)
@@ -222,6 +222,9 @@ def g11():
         y = m(x); y.backward(dy)
         out[f"{name}_y"] = y; out[f"{name}_dx"] = x.grad
         out.update(grads_summary(m, name + "_"))
+    for part in ("y", "dx"):      # ~1 MB each compressed: one file each, so that no committed fixture exceeds 1 MiB
+        k = f"attn_512_n256_hd256_{part}"
+        save(f"attn_planes_512_{part}.npz", **{k: out.pop(k)})
     save("attn_planes.npz", **out)
 
 

@@ -10,7 +10,7 @@ torchvision 0.15 does for a PIL input).  So the fixture pins everything the REFE
 conversion order, the resize target of an int / [H, W] size, the padding arithmetic incl. the negative-offset branch,
 `trig >= 0.999 -> vmin`, bg2grey -- and is only as good as the stand-in for the resampling itself (PIL BILINEAR, which is
 what torchvision hands a PIL image to).  tests/test_host.py::test_image_file_triggers_match_reference_fixture compares
-baddiffusion_amd.dataset.Backdoor with these vectors whenever the assets are reachable (skipped on the GPU box).
+baddiffusion_amd.dataset.Backdoor with these vectors on copies of the four assets kept in tests/golden/static/.
 Outputs only: tests/golden/img_triggers.npz.
 """
 import os, sys, types

@@ -185,7 +185,7 @@ def test_attention_block_on_split_planes_vs_reference(ops, golden, name):
     (unet_plan.cpp node_attention, use_sp): GroupNorm -> planes, bd_gemm_sp (QKV projection, planes out), bd_attn_sp_fwd, bd_gemm_sp (output
     projection + bias + residual); backward: planes of dy, bd_gemm_sp weight / data gradients, bd_attn_sp_bwd, GroupNorm backward --
     against what the reference's own module computed (tests/golden/attn_planes.npz, G11): y, dx, every parameter gradient."""
-    g = golden("attn_planes")
+    g = {**golden("attn_planes"), **golden("attn_planes_512_y"), **golden("attn_planes_512_dx")}     # G11, split so that each file stays < 1 MiB
     Cc, hw, hd = C.ATTN_SP_CASES[name]
     heads = 1 if hd is None else Cc // hd
     N = hw * hw

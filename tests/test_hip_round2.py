@@ -423,7 +423,7 @@ def test_bench_two_ranks_end_to_end(gpu, tmp_path):
     both ranks can share the test box's single GPU: one JSON line from rank 0 with the whole-job aggregate -- BOUNDED (the driver captures a
     bounded tail of stdout; round 5's 20 KB line did not parse) -- and the detail object in the file the line names."""
     detail = str(tmp_path / "bench_detail.json")
-    r = _torchrun(["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2", "--no-cpu-baseline", "--sampling-n", "4,2",
+    r = _torchrun(["bench.py", "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2", "--no-cpu-baseline", "--sampling-n", "4,2",
                    "--no-celeba", "--no-fid", "--sustain", "0.05", "--dp-sweep-buckets", "0,32", "--dp-sweep-slots", "128,192", "--total", "16",
                    "--detail-file", detail], {}, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -471,7 +471,7 @@ def test_bench_eight_ranks_end_to_end(gpu, tmp_path):
     weight-gradient slot sweep, exposed-communication measurement with its sync_state(), per-bucket timing, the sharded DDIM-50 job of
     configs[4] at its real size (2048 chains = 256 rows per rank) and the bounded headline all execute once before real hardware does."""
     detail = str(tmp_path / "bench_detail8.json")
-    r = _torchrun(["bench.py", "--gpus", "8", "--steps", "2", "--warmup", "1", "--batch", "2", "--no-cpu-baseline", "--sampling-n", "8,1",
+    r = _torchrun(["bench.py", "--full", "--gpus", "8", "--steps", "2", "--warmup", "1", "--batch", "2", "--no-cpu-baseline", "--sampling-n", "8,1",
                    "--no-celeba", "--no-fid", "--sustain", "0.05", "--dp-sweep-buckets", "0,32", "--dp-sweep-slots", "128,192", "--total", "2048",
                    "--detail-file", detail], {"OMP_NUM_THREADS": "1"}, timeout=1500, nproc=8)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -505,6 +505,37 @@ def test_bench_two_gpus_rccl(gpu):
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["n_gpus"] == 2 and d["distributed"]["backend"] == "nccl" and d["distributed"]["world"] == 2
     assert np.isfinite(d["final_loss"]) and d["config"]["global_batch"] == 256
+
+
+def test_bench_plain_run_dumps_last_step_outputs(gpu, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times exactly K steps and runs no side measurement; --dump-outputs writes what the last
+    timed step computed (loss, pre-clip gradient norm, seeded samples of the updated weights and of the gradient) as float32 .npy files of at
+    most 64 MB in all, and two runs with the same arguments start from the same inputs, so they agree output for output."""
+    outs = []
+    for run in range(2):
+        d = str(tmp_path / f"out{run}")
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8",
+                            "--dump-outputs", d], capture_output=True, text=True, cwd=ROOT, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        h = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup"):
+            assert k in h, k
+        assert h["steps"] == 3 and h["warmup"] == 1 and abs(h["value"] - 8 * 1000 / h["ms_per_step"]) < 1e-6 * h["value"]
+        for k in ("roofline", "cpu_baseline", "sampling", "celeba", "fid_features", "sustained", "dp_path_at_world_1", "detail_file"):
+            assert k not in h, k
+        files = sorted(os.listdir(d))
+        assert files == ["grad_norm.npy", "grads.npy", "loss.npy", "weights.npy"], files
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in files) <= 64 << 20
+        a = {f[:-4]: np.load(os.path.join(d, f)) for f in files}
+        assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+        assert a["loss"].shape == () and abs(float(a["loss"]) - h["final_loss"]) <= 1e-4 * abs(h["final_loss"])   # the line keeps 5 digits
+        assert a["weights"].shape == a["grads"].shape and a["weights"].size > 10 ** 6 and float(a["grad_norm"]) > 0
+        outs.append(a)
+    assert abs(float(outs[0]["loss"]) - float(outs[1]["loss"])) <= 1e-5 * abs(float(outs[0]["loss"]))
+    assert relerr(torch.from_numpy(outs[1]["weights"]), torch.from_numpy(outs[0]["weights"])) < 1e-5
+    assert relerr(torch.from_numpy(outs[1]["grads"]), torch.from_numpy(outs[0]["grads"])) < 1e-3
 
 
 def test_cli_train_loop_two_ranks(gpu, tmp_path):

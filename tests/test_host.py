@@ -230,16 +230,18 @@ def test_reference_checkpoint_layout(tmp_path):
     assert all(torch.equal(sd2[k], P[k]) for k in P)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/static/fedora-hat.png"),
-                    reason="the reference's static/ image assets are not redistributed (build container only)")
 def test_image_file_triggers_match_reference_fixture():
     """GLASSES / STOP_SIGN triggers and HAT / CAT targets (dataset.py:428-497, 576-597, 643-655): the product's
-    Backdoor, reading the reference's assets in place, against tests/golden/img_triggers.npz -- outputs of the reference's
-    own Backdoor class (generator: tests/golden/make_trigger_fixture.py; its header states what the torchvision stand-in
-    does and does not pin).  BASELINE configs[1]'s HAT target and configs[3]'s GLASSES -> CAT pair are among them."""
+    Backdoor, reading the reference's four image assets (stored as fixtures in tests/golden/static/), against
+    tests/golden/img_triggers.npz -- outputs of the reference's own Backdoor class on the same files (generator:
+    tests/golden/make_trigger_fixture.py; its header states what the torchvision stand-in does and does not pin).
+    BASELINE configs[1]'s HAT target and configs[3]'s GLASSES -> CAT pair are among them."""
     from baddiffusion_amd.dataset import Backdoor
-    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "img_triggers.npz"))
-    bd = Backdoor(root="/root/reference")
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    g = np.load(os.path.join(golden, "img_triggers.npz"))
+    bd = Backdoor(root=golden)
+    for rel in (bd.GLASSES_IMG, bd.STOP_SIGN_IMG, bd.HAT_IMG, bd.CAT_IMG):       # the fixtures themselves, not a file found elsewhere
+        assert bd._asset(rel) == os.path.join(golden, rel), rel
     n = 0
     for key in g.files:
         kind, name = key.split("_", 1)
@@ -400,6 +402,22 @@ def test_bench_headline_is_bounded_and_parses():
     bad = dict(out, celeba={"error": "x" * 5000}, fid_features={"error": "y" * 5000})
     hb = json.loads(b.headline_line(bad, None))
     assert len(hb["celeba"]["error"]) <= 120 and len(hb["fid_features"]["error"]) <= 120
+
+
+def test_bench_options_are_checked_before_any_device_work(tmp_path):
+    """bench.py offers --full (the side measurements) and --dump-outputs DIR (train workloads); arguments it cannot honour are refused by the
+    argument parser, before any device is touched: zero timed steps, or outputs asked of a workload that has no train step."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    run = lambda *a: subprocess.run([sys.executable, os.path.join(root, "bench.py"), *a], capture_output=True, text=True, cwd=str(tmp_path),
+                                    timeout=300)
+    r = run("--help")
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    for bad in (["--steps", "0"], ["--workload", "anp", "--dump-outputs", str(tmp_path / "o")]):
+        r = run(*bad)
+        assert r.returncode == 2 and "error:" in r.stderr, (bad, r.stderr[-500:])
+    assert os.listdir(tmp_path) == []
 
 
 def test_sharded_generator_reproduces_the_single_stream():

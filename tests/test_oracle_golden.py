@@ -187,7 +187,7 @@ def test_modules_vs_reference(golden):
 def test_oracle_attention_at_16x16_vs_reference(golden):
     """G11: the AttentionBlock shapes the split-plane GPU path takes (256 tokens, head dim 256; one and two heads) -- the oracle's block
     against the reference's module, so the GPU test's comparison target is pinned on the CPU side too"""
-    g = golden("attn_planes")
+    g = {**golden("attn_planes"), **golden("attn_planes_512_y"), **golden("attn_planes_512_dx")}     # G11, split so that each file stays < 1 MiB
     for name, (Cc, hw, hd) in C.ATTN_SP_CASES.items():
         P = {k: v.requires_grad_(True) for k, v in C.module_params(name).items()}
         x, dy = C.attn_inputs(name); x.requires_grad_(True)
