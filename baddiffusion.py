@@ -101,7 +101,7 @@ class TrainingConfig:
     learning_rate_32_scratch: float = 2e-4
     learning_rate_256_scratch: float = 2e-5
     lr_warmup_steps: int = 500
-    mixed_precision: str = "no"      # this engine trains in fp32 (the reference hard-codes fp16 AMP, :116)
+    mixed_precision: str = "no"      # this engine trains in fp32 (the reference hard-codes fp16 AMP, :116); BD_COMPUTE_MODE=bf16 is its autocast counterpart
     seed: int = 0
     dataset_path: str = "datasets"
     ckpt_dir: str = "ckpt"

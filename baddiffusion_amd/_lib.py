@@ -103,35 +103,38 @@ class ConvPsDesc(C.Structure):
     _fields_ = [("B", i32), ("H", i32), ("W", i32), ("K", i32), ("N", i32), ("direction", i32),
                 ("x_split", vp), ("ldx", i64), ("w_split", vp), ("bias", vp), ("rowbias", vp), ("ld_rowbias", i64),
                 ("residual", vp), ("ldr", i64), ("out_scale", f32), ("y", vp), ("ldy", i64), ("accumulate", i32),
-                ("workspace", vp), ("workspace_bytes", sz), ("gn_part", vp), ("gn_groups", i32)]
+                ("workspace", vp), ("workspace_bytes", sz), ("gn_part", vp), ("gn_groups", i32), ("mode", i32)]
 
 
 class ConvPsWgradDesc(C.Structure):
     _fields_ = [("B", i32), ("H", i32), ("W", i32), ("Cin", i32), ("Cout", i32), ("x_split", vp), ("ldx", i64),
-                ("dy_split", vp), ("lddy", i64), ("dw", vp), ("db", vp), ("workspace", vp), ("workspace_bytes", sz)]
+                ("dy_split", vp), ("lddy", i64), ("dw", vp), ("db", vp), ("workspace", vp), ("workspace_bytes", sz),
+                ("mode", i32)]
 
 
 class UpsampleConvDesc(C.Structure):
     _fields_ = [("B", i32), ("H", i32), ("W", i32), ("Cin", i32), ("Cout", i32), ("x_split", vp), ("ldx", i64), ("dy_split", vp),
                 ("lddy", i64), ("e_split", vp), ("et_split", vp), ("bias", vp), ("y", vp), ("ldy", i64), ("dx", vp), ("lddx", i64),
-                ("accumulate", i32), ("dw", vp), ("db", vp), ("workspace", vp), ("workspace_bytes", sz)]
+                ("accumulate", i32), ("dw", vp), ("db", vp), ("workspace", vp), ("workspace_bytes", sz), ("mode", i32)]
 
 
 class ConvS2DgradDesc(C.Structure):
     _fields_ = [("B", i32), ("Ho", i32), ("Wo", i32), ("Cin", i32), ("Cout", i32), ("pad", i32), ("dy_split", vp), ("lddy", i64),
-                ("wT_split", vp), ("dx", vp), ("lddx", i64), ("accumulate", i32)]
+                ("wT_split", vp), ("dx", vp), ("lddx", i64), ("accumulate", i32), ("mode", i32)]
 
 
 class GemmSpDesc(C.Structure):
     _fields_ = [("M", i32), ("N", i32), ("K", i32), ("batch", i32), ("a", vp), ("lda", i64), ("a_bs", i64), ("a_kmajor", i32),
                 ("b", vp), ("ldb", i64), ("b_bs", i64), ("b_kmajor", i32), ("c", vp), ("ldc", i64), ("c_bs", i64),
                 ("c_split", vp), ("ldcs", i64), ("cs_bs", i64), ("bias", vp), ("residual", vp), ("ldr", i64), ("r_bs", i64),
-                ("alpha", f32), ("out_scale", f32), ("accumulate", i32), ("a_colsum", vp), ("workspace", vp), ("workspace_bytes", sz)]
+                ("alpha", f32), ("out_scale", f32), ("accumulate", i32), ("a_colsum", vp), ("workspace", vp), ("workspace_bytes", sz),
+                ("mode", i32)]
 
 
 class AttnSpDesc(C.Structure):
     _fields_ = [("B", i32), ("heads", i32), ("N", i32), ("dh", i32), ("qkv_split", vp), ("ld", i64), ("scale", f32), ("o_split", vp),
-                ("ldo", i64), ("pt_split", vp), ("do_split", vp), ("lddo", i64), ("dst_split", vp), ("dqkv_split", vp), ("lddqkv", i64)]
+                ("ldo", i64), ("pt_split", vp), ("do_split", vp), ("lddo", i64), ("dst_split", vp), ("dqkv_split", vp), ("lddqkv", i64),
+                ("mode", i32)]
 
 
 class Conv2dDesc(C.Structure):

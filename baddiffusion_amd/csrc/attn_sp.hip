@@ -8,7 +8,9 @@
 // replacing, per attention block, Q K^T + softmax + P V (3 launches, 71 us at B = 128) and dP + dV + softmax backward + dQ + dK (5
 // launches, 118 us).  Operands are split planes (bd_split_rows layout, DMA'd global -> LDS without touching registers) and so are
 // the results; same arithmetic as the GEMM engines (x = hi + lo, lo*hi + hi*lo + hi*hi on v_mfma_f32_32x32x16_bf16, fp32 accumulate,
-// fp32 softmax with the row maximum subtracted).
+// fp32 softmax with the row maximum subtracted).  Single pass (SP, BD_MODE_BF16): only the hi planes / registers enter the MFMAs, one
+// product each -- P (and dS) are rounded to bf16 once, the hi the three-product form also uses; the P^T / dS^T / output planes are still
+// written with both halves.
 //
 // One workgroup = 4 waves; a wave OWNS 32 rows (queries, or keys in backward B) and all 256 columns of the [N, N] matrix, so the row
 // statistics of the softmax (and of its backward) are in-lane reductions plus one lane ^ 32 exchange: the waves only share the LDS
@@ -130,7 +132,7 @@ __device__ __forceinline__ void as_tie(AsGroup& g) {
                  "+v"(g.a[3][1]));
 }
 __device__ __forceinline__ void as_tie2(as_short8& a, as_short8& b) { asm volatile("" : "+v"(a), "+v"(b)); }
-template <class W>
+template <bool SP, class W>   // SP (BD_MODE_BF16): hi fragments only, one MFMA per product
 __device__ __forceinline__ void as_phase_s(const char* a_base, long long lda, const char* own_base, long long ldo, int nch, char* smem,
                                            const AsLane& L, as_floatx16 (&acc)[8], W&& work) {
     // uniform chunk pointers + 32-bit lane offsets (saddr + voffset addressing: 12 address registers instead of 24)
@@ -169,14 +171,14 @@ __device__ __forceinline__ void as_phase_s(const char* a_base, long long lda, co
     auto reads_q = [&](unsigned sb, auto S) {
         constexpr int s = decltype(S)::value;
         q[s][0] = as_read128<0>(sb + L.kq[s][0]);
-        q[s][1] = as_read128<0>(sb + L.kq[s][1]);
+        if constexpr (!SP) q[s][1] = as_read128<0>(sb + L.kq[s][1]);
     };
     auto reads = [&](unsigned sb, auto S, auto GI, AsGroup& g) {
         constexpr int s = decltype(S)::value, gi = decltype(GI)::value;
         as_for<0, 4>([&](auto T) {
             constexpr int t = decltype(T)::value;
             g.a[t][0] = as_read128<(gi * 4 + t) * 4096>(sb + L.kc[s][0]);
-            g.a[t][1] = as_read128<(gi * 4 + t) * 4096>(sb + L.kc[s][1]);
+            if constexpr (!SP) g.a[t][1] = as_read128<(gi * 4 + t) * 4096>(sb + L.kc[s][1]);
         });
     };
     auto wait = [&](AsGroup& g, auto S) {
@@ -189,9 +191,9 @@ __device__ __forceinline__ void as_phase_s(const char* a_base, long long lda, co
         constexpr int s = decltype(S)::value, gi = decltype(GI)::value;
         const as_bf16x8 qh = as_bf(q[s][0]), ql = as_bf(q[s][1]);
 #pragma unroll
-        for (int t = 0; t < 4; ++t) acc[gi * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(g.a[t][1]), qh, acc[gi * 4 + t], 0, 0, 0);
+        for (int t = 0; t < 4; ++t) if constexpr (!SP) acc[gi * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(g.a[t][1]), qh, acc[gi * 4 + t], 0, 0, 0);
 #pragma unroll
-        for (int t = 0; t < 4; ++t) acc[gi * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(g.a[t][0]), ql, acc[gi * 4 + t], 0, 0, 0);
+        for (int t = 0; t < 4; ++t) if constexpr (!SP) acc[gi * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(g.a[t][0]), ql, acc[gi * 4 + t], 0, 0, 0);
 #pragma unroll
         for (int t = 0; t < 4; ++t) acc[gi * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(g.a[t][0]), qh, acc[gi * 4 + t], 0, 0, 0);
     };
@@ -281,7 +283,7 @@ __device__ __forceinline__ void as_tie(AsOFrag& f) {
 // vmcnt counts stores as well as loads and the two complete out of order, so a counted wait is exact only while no store is in flight:
 // the last DMA is issued while unit 9 runs, the barrier that opens unit 12 waits for everything, and only work(u >= 12) may store.
 constexpr int AS_O_STORE_FROM = 12;
-template <bool PERM, class W>
+template <bool PERM, bool SP, class W>   // SP (BD_MODE_BF16): the hi planes of both operands only, one MFMA per product
 __device__ __forceinline__ void as_o_run(const AsStream& s, char* smem, const AsLane& L, const as_uint4 (&ah)[8][2], const as_uint4 (&al)[8][2],
                                          as_floatx16 (&oacc)[8], W&& work) {
     using I0 = std::integral_constant<int, 0>;
@@ -302,7 +304,7 @@ __device__ __forceinline__ void as_o_run(const AsStream& s, char* smem, const As
         as_for<0, 4>([&](auto T) {
             constexpr int t = decltype(T)::value;
 #pragma unroll
-            for (int pl = 0; pl < 2; ++pl) {
+            for (int pl = 0; pl < (SP ? 1 : 2); ++pl) {
                 const unsigned a = ub + (PERM ? L.kmp[t & 1][pl] : L.km[t & 1][pl]);
                 f.v0[t][pl] = as_read_tr<sp * 16 * 512 + (t >> 1) * 256>(a);
                 f.v1[t][pl] = as_read_tr<sp * 16 * 512 + (t >> 1) * 256 + second>(a);
@@ -328,9 +330,9 @@ __device__ __forceinline__ void as_o_run(const AsStream& s, char* smem, const As
             constexpr int sp = decltype(S)::value;
             const as_bf16x8 mh = __builtin_bit_cast(as_bf16x8, ah[kc][sp]), ml = __builtin_bit_cast(as_bf16x8, al[kc][sp]);
 #pragma unroll
-            for (int t = 0; t < 4; ++t) oacc[half * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ml, as_bf(f.v0[t][0], f.v1[t][0]), oacc[half * 4 + t], 0, 0, 0);
+            for (int t = 0; t < 4; ++t) if constexpr (!SP) oacc[half * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ml, as_bf(f.v0[t][0], f.v1[t][0]), oacc[half * 4 + t], 0, 0, 0);
 #pragma unroll
-            for (int t = 0; t < 4; ++t) oacc[half * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(mh, as_bf(f.v0[t][1], f.v1[t][1]), oacc[half * 4 + t], 0, 0, 0);
+            for (int t = 0; t < 4; ++t) if constexpr (!SP) oacc[half * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(mh, as_bf(f.v0[t][1], f.v1[t][1]), oacc[half * 4 + t], 0, 0, 0);
 #pragma unroll
             for (int t = 0; t < 4; ++t) oacc[half * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(mh, as_bf(f.v0[t][0], f.v1[t][0]), oacc[half * 4 + t], 0, 0, 0);
         };
@@ -430,7 +432,7 @@ __device__ __forceinline__ void as_coord(int& bh, int& blk) {
     bh = j >> 1; blk = j & 1;
 }
 
-template <bool WRITE_P>
+template <bool WRITE_P, bool SP>
 __global__ __launch_bounds__(AS_NT, 1) void attn_sp_fwd_kernel(AsParams p) {
     __shared__ __attribute__((aligned(128))) char smem[AS_LDS];
     const AsLane L = as_lane(smem, p.ablate, p.dbg);
@@ -447,7 +449,7 @@ __global__ __launch_bounds__(AS_NT, 1) void attn_sp_fwd_kernel(AsParams p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[kt][r] = 0.f;
     AS_STAMP(0);
-    as_phase_s(base + (long long)p.C * 4, p.ld, base + own0 * p.ld, p.ld, p.dh >> 5, smem, L, acc, [](auto) {});
+    as_phase_s<SP>(base + (long long)p.C * 4, p.ld, base + own0 * p.ld, p.ld, p.dh >> 5, smem, L, acc, [](auto) {});
     AS_STAMP(1);
     __builtin_amdgcn_s_barrier();
     const AsStream vs = as_o_open(base + (long long)p.C * 8, p.ld, L);
@@ -481,7 +483,7 @@ __global__ __launch_bounds__(AS_NT, 1) void attn_sp_fwd_kernel(AsParams p) {
     const AsPair po = as_pair(L, p.ldo), pp = as_pair(L, AS_N * 4);
     char* orow = p.o + ((long long)b * AS_N + own0) * p.ldo + colq;                                   // uniform
     char* ptb = WRITE_P ? p.pt + (long long)bh * AS_N * AS_N * 4 + (qb * 4 + L.wave) * 128 : nullptr;  // uniform
-    as_o_run<true>(vs, smem, L, ah, al, oacc, [&](auto UU) {
+    as_o_run<true, SP>(vs, smem, L, ah, al, oacc, [&](auto UU) {
         constexpr int u = decltype(UU)::value;
         if constexpr (u < 7) as_pack_tile(acc[u + 1], inv, ah[u + 1], al[u + 1]);
         if constexpr (u >= AS_O_STORE_FROM) {
@@ -499,6 +501,7 @@ __global__ __launch_bounds__(AS_NT, 1) void attn_sp_fwd_kernel(AsParams p) {
     AS_STAMP(4);
 }
 
+template <bool SP>
 __global__ __launch_bounds__(AS_NT, 1) void attn_sp_bwd_a_kernel(AsParams p) {
     __shared__ __attribute__((aligned(128))) char smem[AS_LDS];
     const AsLane L = as_lane(smem, p.ablate, p.dbg);
@@ -527,7 +530,7 @@ __global__ __launch_bounds__(AS_NT, 1) void attn_sp_bwd_a_kernel(AsParams p) {
         for (int r = 0; r < 16; ++r) acc[kt][r] = 0.f;
     // dP^T = V dO^T; under the MFMAs of chunk c, tile c of P goes from its plane words back to fp32 (hi + lo, exact)
     const unsigned sel_hi = pp.odd ? 0x07060c0cu : 0x01000c0cu, sel_lo = pp.odd ? 0x03020c0cu : 0x05040c0cu;   // v_perm(nb, own): 0x0c = zero byte
-    as_phase_s(base + (long long)p.C * 8, p.ld, p.dO + ((long long)b * AS_N + own0) * p.lddo + colq, p.lddo, p.dh >> 5, smem, L, acc, [&](auto CC) {
+    as_phase_s<SP>(base + (long long)p.C * 8, p.ld, p.dO + ((long long)b * AS_N + own0) * p.lddo + colq, p.lddo, p.dh >> 5, smem, L, acc, [&](auto CC) {
         constexpr int c = decltype(CC)::value;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -561,7 +564,7 @@ __global__ __launch_bounds__(AS_NT, 1) void attn_sp_bwd_a_kernel(AsParams p) {
         for (int r = 0; r < 16; ++r) oacc[dt][r] = 0.f;
     char* qrow = p.dqkv + ((long long)b * AS_N + own0) * p.lddqkv + colq;                              // uniform
     char* dsb = p.dst + (long long)bh * AS_N * AS_N * 4 + (qb * 4 + L.wave) * 128;                      // uniform
-    as_o_run<true>(ks, smem, L, ah, al, oacc, [&](auto UU) {   // dQ = dS K
+    as_o_run<true, SP>(ks, smem, L, ah, al, oacc, [&](auto UU) {   // dQ = dS K
         constexpr int u = decltype(UU)::value;
         if constexpr (u < 7) { ds_tile(u + 1); as_pack_tile(acc[u + 1], 1.f, ah[u + 1], al[u + 1]); }
         if constexpr (u >= AS_O_STORE_FROM) {
@@ -575,6 +578,7 @@ __global__ __launch_bounds__(AS_NT, 1) void attn_sp_bwd_a_kernel(AsParams p) {
     for (int dt = 4; dt < 8; ++dt) as_store_tile(qrow + dt * 128, p.lddqkv, pq, oacc[dt]);
 }
 
+template <bool SP>
 __global__ __launch_bounds__(AS_NT, 1) void attn_sp_bwd_b_kernel(AsParams p) {
     __shared__ __attribute__((aligned(128))) char smem[AS_LDS];
     const AsLane L = as_lane(smem, p.ablate, p.dbg);
@@ -605,7 +609,7 @@ __global__ __launch_bounds__(AS_NT, 1) void attn_sp_bwd_b_kernel(AsParams p) {
         for (int dt = 0; dt < 8; ++dt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) oacc[dt][r] = 0.f;
-        as_o_run<false>(st, smem, L, ah, al, oacc, [&](auto UU) {
+        as_o_run<false, SP>(st, smem, L, ah, al, oacc, [&](auto UU) {
             constexpr int u = decltype(UU)::value;
             if constexpr (u >= AS_O_STORE_FROM) as_store_tile(out + (u - AS_O_STORE_FROM) * 128, p.lddqkv, pq, oacc[u - AS_O_STORE_FROM]);
         });
@@ -667,6 +671,7 @@ static int attn_sp_common(const bd_attn_sp_desc& d, const char* who, AsParams& p
     const int C = d.heads * d.dh;
     BD_CHECK(d.qkv_split && d.ld >= 3 * C && d.ld % 32 == 0 && ((uintptr_t)d.qkv_split & 127) == 0, BD_ERR_INVALID,
              "%s: qkv planes must be 128-byte aligned with a row stride >= 3C, multiple of 32", who);
+    BD_CHECK(sp_mode_valid(d.mode), BD_ERR_INVALID, "%s: unknown compute mode %d", who, d.mode);
     p = {};
     p.qkv = reinterpret_cast<const char*>(d.qkv_split); p.ld = d.ld * 4;
     p.C = C; p.dh = d.dh; p.heads = d.heads; p.scale = d.scale;
@@ -688,9 +693,12 @@ int attn_sp_fwd(const bd_attn_sp_desc& d, hipStream_t st) {
 #endif
     // bench.py roofline: S = Q K^T and O = P V (4 B N^2 dh flop per head); bytes = q, k, v in, o (+ P^T for training) out
     const double bh = (double)d.B * d.heads, nn = (double)d.N * d.N, nd = (double)d.N * d.dh;
-    const int rec = prof_on() ? prof_begin("attn_sp_fwd", 4.0 * bh * nn * d.dh, 4.0 * bh * (4.0 * nd + (d.pt_split ? nn : 0.0)), st) : -1;
-    if (d.pt_split) hipLaunchKernelGGL(attn_sp_fwd_kernel<true>, grid, dim3(AS_NT), 0, st, p);
-    else hipLaunchKernelGGL(attn_sp_fwd_kernel<false>, grid, dim3(AS_NT), 0, st, p);
+    const bool sp = d.mode == BD_MODE_BF16;
+    const int rec = prof_on() ? prof_begin(sp ? "attn_sp_fwd_bf16" : "attn_sp_fwd", 4.0 * bh * nn * d.dh, 4.0 * bh * (4.0 * nd + (d.pt_split ? nn : 0.0)), st) : -1;
+    if (d.pt_split && sp) hipLaunchKernelGGL((attn_sp_fwd_kernel<true, true>), grid, dim3(AS_NT), 0, st, p);
+    else if (d.pt_split) hipLaunchKernelGGL((attn_sp_fwd_kernel<true, false>), grid, dim3(AS_NT), 0, st, p);
+    else if (sp) hipLaunchKernelGGL((attn_sp_fwd_kernel<false, true>), grid, dim3(AS_NT), 0, st, p);
+    else hipLaunchKernelGGL((attn_sp_fwd_kernel<false, false>), grid, dim3(AS_NT), 0, st, p);
     BD_LAUNCH_CHECK("attn_sp_fwd");
     prof_end(rec, st);
 #ifdef BD_AS_ABLATION
@@ -714,14 +722,17 @@ int attn_sp_bwd(const bd_attn_sp_desc& d, hipStream_t st) {
     // bench.py roofline.  A: dP = dO V^T, dQ = dS K (4 B N^2 dh flop per head; reads k, v, dO, P^T; writes dq, dS^T).
     // B: dV = P^T dO, dK = dS^T Q (same flops; reads P^T, dS^T, dO, q; writes dk, dv).
     const double bh = (double)d.B * d.heads, nn = (double)d.N * d.N, nd = (double)d.N * d.dh;
-    int rec = prof_on() ? prof_begin("attn_sp_bwd_a", 4.0 * bh * nn * d.dh, 4.0 * bh * (4.0 * nd + 2.0 * nn), st) : -1;
-    hipLaunchKernelGGL(attn_sp_bwd_a_kernel, grid, dim3(AS_NT), 0, st, p);
+    const bool sp = d.mode == BD_MODE_BF16;
+    int rec = prof_on() ? prof_begin(sp ? "attn_sp_bwd_a_bf16" : "attn_sp_bwd_a", 4.0 * bh * nn * d.dh, 4.0 * bh * (4.0 * nd + 2.0 * nn), st) : -1;
+    if (sp) hipLaunchKernelGGL(attn_sp_bwd_a_kernel<true>, grid, dim3(AS_NT), 0, st, p);
+    else hipLaunchKernelGGL(attn_sp_bwd_a_kernel<false>, grid, dim3(AS_NT), 0, st, p);
     prof_end(rec, st);
 #ifdef BD_AS_ABLATION
     p.dbg = as_dbg_buf();
 #endif
-    rec = prof_on() ? prof_begin("attn_sp_bwd_b", 4.0 * bh * nn * d.dh, 4.0 * bh * (4.0 * nd + 2.0 * nn), st) : -1;
-    hipLaunchKernelGGL(attn_sp_bwd_b_kernel, grid, dim3(AS_NT), 0, st, p);
+    rec = prof_on() ? prof_begin(sp ? "attn_sp_bwd_b_bf16" : "attn_sp_bwd_b", 4.0 * bh * nn * d.dh, 4.0 * bh * (4.0 * nd + 2.0 * nn), st) : -1;
+    if (sp) hipLaunchKernelGGL(attn_sp_bwd_b_kernel<true>, grid, dim3(AS_NT), 0, st, p);
+    else hipLaunchKernelGGL(attn_sp_bwd_b_kernel<false>, grid, dim3(AS_NT), 0, st, p);
     prof_end(rec, st);
     BD_LAUNCH_CHECK("attn_sp_bwd");
 #ifdef BD_AS_ABLATION

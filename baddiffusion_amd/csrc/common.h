@@ -44,6 +44,11 @@ void set_error(const char* fmt, ...);
 
 static inline hipStream_t S(bd_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// BD_MODE_BF16X3 and BD_MODE_BF16 run the same bf16 MFMA kernels and plans (three products vs one)
+static inline bool mode_bf16(int m) { return m == BD_MODE_BF16X3 || m == BD_MODE_BF16; }
+static inline bool mode_valid(int m) { return m == BD_MODE_F32 || mode_bf16(m); }
+// the split-plane kernels' descriptor field: 0 (zero-initialised) or BD_MODE_BF16X3 = three products, BD_MODE_BF16 = one
+static inline bool sp_mode_valid(int m) { return m == 0 || mode_bf16(m); }
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 

@@ -17,7 +17,9 @@
 // parity of the input pixel only 4 / 2 / 2 / 1 of the 9 taps can contribute, so four classes on the OUTPUT grid replace a 9-tap
 // gather in which 3 of 4 products are structurally zero.
 // Same arithmetic as conv_ps.hip (x = hi + lo, lo*hi + hi*lo + hi*hi on v_mfma_f32_32x32x16_bf16, fp32 accumulate); the only
-// numerical difference to the literal form is that weights are summed (in fp32) before the split, ~1e-7 relative.
+// numerical difference to the literal form is that weights are summed (in fp32) before the split, ~1e-7 relative.  In the single-pass
+// mode (BD_MODE_BF16: hi*hi only) the rounded operand is the summed weight E, so the forward / data gradient differ from a product of the
+// rounded 3x3 weights by up to 2^-9 relative per E entry -- the same order as the mode's rounding itself.
 #include "common.h"
 
 #include <cstdlib>
@@ -112,6 +114,7 @@ __device__ __forceinline__ void ph_epilogue(const PhParams& p, const ph_floatx16
 // 256 x 128 tile, 8 waves of 64 x 64, three LDS stages, one barrier per K chunk (one tap x 32 channels): conv_ps_kernel's
 // main loop with (i) a tap TABLE per class instead of the 3 x 3 cursor, (ii) the A rows optionally taken from the fine grid at
 // stride 2, (iii) the output rows optionally scattered to one pixel class of the fine grid, (iv) any chunk count.
+template <bool SP>   // single pass (BD_MODE_BF16): hi fragments only, one MFMA per product
 __global__ __launch_bounds__(PH_NT, 2) void conv_ph_kernel(PhParams p) {
     __shared__ __attribute__((aligned(128))) char smem[PH_LDS_BYTES];
     const int tid = threadIdx.x;
@@ -208,18 +211,18 @@ __global__ __launch_bounds__(PH_NT, 2) void conv_ph_kernel(PhParams p) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 ah[i] = *reinterpret_cast<const ph_bf16x8*>(stage + abase + i * 4096 + foff[s][0]);
-                al[i] = *reinterpret_cast<const ph_bf16x8*>(stage + abase + i * 4096 + foff[s][1]);
+                if constexpr (!SP) al[i] = *reinterpret_cast<const ph_bf16x8*>(stage + abase + i * 4096 + foff[s][1]);
                 bh[i] = *reinterpret_cast<const ph_bf16x8*>(stage + bbase + i * 4096 + foff[s][0]);
-                bl[i] = *reinterpret_cast<const ph_bf16x8*>(stage + bbase + i * 4096 + foff[s][1]);
+                if constexpr (!SP) bl[i] = *reinterpret_cast<const ph_bf16x8*>(stage + bbase + i * 4096 + foff[s][1]);
             }
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int q = 0; q < 2; ++q) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[q], acc[i][q], 0, 0, 0);
+                for (int q = 0; q < 2; ++q) if constexpr (!SP) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[q], acc[i][q], 0, 0, 0);
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int q = 0; q < 2; ++q) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[q], acc[i][q], 0, 0, 0);
+                for (int q = 0; q < 2; ++q) if constexpr (!SP) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[q], acc[i][q], 0, 0, 0);
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -360,10 +363,11 @@ bool upsample_conv_ps_supported(int B, int H, int W, int Cin, int Cout) {
     return !off && B > 0 && ph_ilog2(H) >= 0 && ph_ilog2(W) >= 0 && Cin % 128 == 0 && Cout % 128 == 0;
 }
 
-static int ph_launch(PhParams& p, hipStream_t st, const char* what) {
+static int ph_launch(PhParams& p, bool sp, hipStream_t st, const char* what) {
     p.tiles_m = (int)cdiv((long long)p.M, PH_BM); p.tiles_n = p.N / PH_BN;
     const dim3 grid((unsigned)(p.tiles_m * p.tiles_n), (unsigned)(p.tsplit > 1 ? p.tsplit : p.ncls)), block(PH_NT);
-    hipLaunchKernelGGL(conv_ph_kernel, grid, block, 0, st, p);
+    if (sp) hipLaunchKernelGGL(conv_ph_kernel<true>, grid, block, 0, st, p);
+    else hipLaunchKernelGGL(conv_ph_kernel<false>, grid, block, 0, st, p);
     BD_LAUNCH_CHECK(what);
     if (p.tsplit > 1) {
         const long long mn = (long long)p.M * p.N;
@@ -388,8 +392,9 @@ size_t upsample_conv_dgrad_workspace_bytes(const bd_upsample_conv_desc& d) {
 }
 
 static int ph_common(PhParams& p, int B, int H, int W, int C, int N, const void* a, long long lda, const void* w, float* y, long long ldy,
-                     const char* who) {
+                     int mode, const char* who) {
     BD_CHECK(a && w && y, BD_ERR_INVALID, "%s: null pointer", who);
+    BD_CHECK(sp_mode_valid(mode), BD_ERR_INVALID, "%s: unknown compute mode %d", who, mode);
     BD_CHECK(B > 0 && ph_ilog2(H) >= 0 && ph_ilog2(W) >= 0, BD_ERR_UNSUPPORTED, "%s: H, W must be powers of two", who);
     BD_CHECK(C > 0 && C % 32 == 0 && N > 0 && N % PH_BN == 0, BD_ERR_UNSUPPORTED, "%s: K channels %% 32 and N channels %% %d must be 0 (got %d, %d)",
              who, PH_BN, C, N);
@@ -413,7 +418,7 @@ int upsample_weights(const float* w, int Cin, int Cout, uint16_t* e_split, uint1
 // y [B, 2H, 2W, Cout] = conv3x3(nearest_up2(x)) + bias, x given as split planes on the SOURCE grid
 int upsample_conv_fwd(const bd_upsample_conv_desc& d, hipStream_t st) {
     PhParams p = {};
-    BD_TRY(ph_common(p, d.B, d.H, d.W, d.Cin, d.Cout, d.x_split, d.ldx, d.e_split, d.y, d.ldy, "bd_upsample_conv_fwd"));
+    BD_TRY(ph_common(p, d.B, d.H, d.W, d.Cin, d.Cout, d.x_split, d.ldx, d.e_split, d.y, d.ldy, d.mode, "bd_upsample_conv_fwd"));
     p.bias = d.bias; p.WT = 16; p.a_fine = 0; p.y_fine = 1; p.accumulate = 0; p.ncls = 4;
     for (int c = 0; c < 4; ++c) {
         PhClass& k = p.cls[c];
@@ -424,9 +429,9 @@ int upsample_conv_fwd(const bd_upsample_conv_desc& d, hipStream_t st) {
             k.wt[t] = (ph_o_of(k.p, dy) + 1) * 4 + (ph_o_of(k.q, dx) + 1);
         }
     }
-    const int rec = prof_on() ? prof_begin("conv_ph_ups_fwd", 2.0 * d.B * 4.0 * d.H * d.W * d.Cout * 9.0 * d.Cin,
+    const int rec = prof_on() ? prof_begin(d.mode == BD_MODE_BF16 ? "conv_ph_ups_fwd_bf16" : "conv_ph_ups_fwd", 2.0 * d.B * 4.0 * d.H * d.W * d.Cout * 9.0 * d.Cin,
                                            4.0 * d.B * d.H * d.W * (d.Cin + 4.0 * d.Cout) + 36.0 * d.Cin * d.Cout, st) : -1;
-    const int rc = ph_launch(p, st, "conv_ph (upsample forward)");
+    const int rc = ph_launch(p, d.mode == BD_MODE_BF16, st, "conv_ph (upsample forward)");
     prof_end(rec, st);
     return rc;
 }
@@ -434,7 +439,7 @@ int upsample_conv_fwd(const bd_upsample_conv_desc& d, hipStream_t st) {
 // dx [B, H, W, Cin] (+)= the data gradient of the same layer from dY [B, 2H, 2W, Cout] given as split planes on the FINE grid
 int upsample_conv_dgrad(const bd_upsample_conv_desc& d, hipStream_t st) {
     PhParams p = {};
-    BD_TRY(ph_common(p, d.B, d.H, d.W, d.Cout, d.Cin, d.dy_split, d.lddy, d.et_split, d.dx, d.lddx, "bd_upsample_conv_dgrad"));
+    BD_TRY(ph_common(p, d.B, d.H, d.W, d.Cout, d.Cin, d.dy_split, d.lddy, d.et_split, d.dx, d.lddx, d.mode, "bd_upsample_conv_dgrad"));
     p.bias = nullptr; p.WT = 16; p.a_fine = 1; p.y_fine = 0; p.accumulate = d.accumulate; p.ncls = 1;
     PhClass& k = p.cls[0];
     k.p = k.q = 0; k.ntaps = 16;
@@ -444,9 +449,9 @@ int upsample_conv_dgrad(const bd_upsample_conv_desc& d, hipStream_t st) {
         BD_CHECK(d.workspace && d.workspace_bytes >= need, BD_ERR_WORKSPACE, "bd_upsample_conv_dgrad: workspace %zu < %zu", d.workspace_bytes, need);
         p.tsplit = 4; p.partial = reinterpret_cast<float*>(d.workspace);
     }
-    const int rec = prof_on() ? prof_begin("conv_ph_ups_dgrad", 2.0 * d.B * 4.0 * d.H * d.W * d.Cout * 9.0 * d.Cin,
+    const int rec = prof_on() ? prof_begin(d.mode == BD_MODE_BF16 ? "conv_ph_ups_dgrad_bf16" : "conv_ph_ups_dgrad", 2.0 * d.B * 4.0 * d.H * d.W * d.Cout * 9.0 * d.Cin,
                                            4.0 * d.B * d.H * d.W * (d.Cin + 4.0 * d.Cout) + 36.0 * d.Cin * d.Cout, st) : -1;
-    const int rc = ph_launch(p, st, "conv_ph (upsample dgrad)");
+    const int rc = ph_launch(p, d.mode == BD_MODE_BF16, st, "conv_ph (upsample dgrad)");
     prof_end(rec, st);
     return rc;
 }
@@ -455,7 +460,7 @@ int upsample_conv_dgrad(const bd_upsample_conv_desc& d, hipStream_t st) {
 // asymmetric F.pad(0,1,0,1) + padding 0) from dy [B, Ho, Wo, Cout] split planes and the transposed weight planes Wt[ci][9][co]
 int conv3x3_s2_dgrad_ps(const bd_conv3x3_s2_dgrad_desc& d, hipStream_t st) {
     PhParams p = {};
-    BD_TRY(ph_common(p, d.B, d.Ho, d.Wo, d.Cout, d.Cin, d.dy_split, d.lddy, d.wT_split, d.dx, d.lddx, "bd_conv3x3_s2_dgrad_ps"));
+    BD_TRY(ph_common(p, d.B, d.Ho, d.Wo, d.Cout, d.Cin, d.dy_split, d.lddy, d.wT_split, d.dx, d.lddx, d.mode, "bd_conv3x3_s2_dgrad_ps"));
     BD_CHECK(d.pad == 0 || d.pad == 1, BD_ERR_UNSUPPORTED, "bd_conv3x3_s2_dgrad_ps: pad must be 0 or 1");
     p.bias = nullptr; p.WT = 9; p.a_fine = 0; p.y_fine = 1; p.accumulate = d.accumulate; p.ncls = 4;
     for (int c = 0; c < 4; ++c) {
@@ -469,9 +474,9 @@ int conv3x3_s2_dgrad_ps(const bd_conv3x3_s2_dgrad_desc& d, hipStream_t st) {
                 ++k.ntaps;
             }
     }
-    const int rec = prof_on() ? prof_begin("conv_ph_s2_dgrad", 2.0 * d.B * d.Ho * d.Wo * d.Cout * 9.0 * d.Cin,
+    const int rec = prof_on() ? prof_begin(d.mode == BD_MODE_BF16 ? "conv_ph_s2_dgrad_bf16" : "conv_ph_s2_dgrad", 2.0 * d.B * d.Ho * d.Wo * d.Cout * 9.0 * d.Cin,
                                            4.0 * d.B * d.Ho * d.Wo * (4.0 * d.Cin + d.Cout) + 36.0 * d.Cin * d.Cout, st) : -1;
-    const int rc = ph_launch(p, st, "conv_ph (stride-2 dgrad)");
+    const int rc = ph_launch(p, d.mode == BD_MODE_BF16, st, "conv_ph (stride-2 dgrad)");
     prof_end(rec, st);
     return rc;
 }

@@ -12,6 +12,10 @@
 // c+2 is issued right after the barrier that retires chunk c-1's stage and is waited for with a counted vmcnt two
 // chunks later (cdna_hip_programming.md section 5, "Pipelining across barriers": raw s_barrier, never vmcnt(0) in the loop).
 // Zero padding: lanes whose tap falls outside the image read a 16-byte zero page instead (branch-free).
+// Single pass (SP template parameter, BD_MODE_BF16): the same DMA of whole 128-byte lines, but only the hi fragments are read from
+// LDS and each product is the one MFMA hi*hi.  The weight-gradient kernels' bias gradient (ones-MFMA) keeps hi + lo of dY: the
+// lo plane is still in LDS, and only the waves that own the bias row read it.  The lo halves of every line are still DMA'd; a
+// hi-only DMA (half the operand bytes into LDS) is the next step for this mode.
 //
 // data gradient of the same convolution: dx[p][ci] = sum_{tap,co} dy[p - tap][co] * W[co][tap][ci] is the same kernel
 // with the gather direction negated (sign = -1) over the TRANSPOSED weight planes Wt[ci][tap][co] (bd_split_wt).
@@ -185,7 +189,7 @@ __device__ __forceinline__ void ps3_gn_partials(const PsParams& p, float (&st)[2
 // All eight waves run in lock step, one barrier per chunk.  (A ping-pong schedule -- the two waves of a SIMD one phase
 // apart, four barriers per chunk -- and a wave-specialised form with four extra DMA-only loader waves were built and
 // measured: bit-identical, and within +-2 % of this form on every layer)
-template <int EPI>
+template <int EPI, bool SP>
 __global__ __launch_bounds__(PS_NT, 2) void conv_ps_kernel(PsParams p) {
     __shared__ __attribute__((aligned(128))) char smem[PS_LDS_BYTES];   // ONE LDS object (guide section 5, trap (a))
 
@@ -294,9 +298,9 @@ __global__ __launch_bounds__(PS_NT, 2) void conv_ps_kernel(PsParams p) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 ah[i] = *reinterpret_cast<const bf16x8*>(stage + abase + i * 4096 + foff[s][0]);
-                al[i] = *reinterpret_cast<const bf16x8*>(stage + abase + i * 4096 + foff[s][1]);
+                if constexpr (!SP) al[i] = *reinterpret_cast<const bf16x8*>(stage + abase + i * 4096 + foff[s][1]);
                 bh[i] = *reinterpret_cast<const bf16x8*>(stage + bbase + i * 4096 + foff[s][0]);
-                bl[i] = *reinterpret_cast<const bf16x8*>(stage + bbase + i * 4096 + foff[s][1]);
+                if constexpr (!SP) bl[i] = *reinterpret_cast<const bf16x8*>(stage + bbase + i * 4096 + foff[s][1]);
             }
             }
 #ifdef BD_PS_ABLATION
@@ -309,11 +313,11 @@ __global__ __launch_bounds__(PS_NT, 2) void conv_ps_kernel(PsParams p) {
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int q = 0; q < 2; ++q) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[q], acc[i][q], 0, 0, 0);
+                for (int q = 0; q < 2; ++q) if constexpr (!SP) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[q], acc[i][q], 0, 0, 0);
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int q = 0; q < 2; ++q) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[q], acc[i][q], 0, 0, 0);
+                for (int q = 0; q < 2; ++q) if constexpr (!SP) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[q], acc[i][q], 0, 0, 0);
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -359,7 +363,7 @@ __global__ __launch_bounds__(PS_NT, 2) void conv_ps_kernel(PsParams p) {
 constexpr int PS3_WIN_ROWS = 320, PS3_A_BYTES = PS3_WIN_ROWS * 128, PS3_B_BYTES = 128 * 128;
 constexpr int PS3_LDS_BYTES = 2 * PS3_A_BYTES + 3 * PS3_B_BYTES;
 
-template <int EPI>
+template <int EPI, bool SP>
 __global__ __launch_bounds__(PS_NT, 2) void conv_ps3_kernel(PsParams p) {
     __shared__ __attribute__((aligned(128))) char smem[PS3_LDS_BYTES];
     const int tid = threadIdx.x;
@@ -455,18 +459,18 @@ __global__ __launch_bounds__(PS_NT, 2) void conv_ps3_kernel(PsParams p) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 ah[i] = *reinterpret_cast<const bf16x8*>(a0 + i * 4096 + foff[s][0]);
-                al[i] = *reinterpret_cast<const bf16x8*>(a0 + i * 4096 + foff[s][1]);
+                if constexpr (!SP) al[i] = *reinterpret_cast<const bf16x8*>(a0 + i * 4096 + foff[s][1]);
                 bh[i] = *reinterpret_cast<const bf16x8*>(b0 + i * 4096 + foff[s][0]);
-                bl[i] = *reinterpret_cast<const bf16x8*>(b0 + i * 4096 + foff[s][1]);
+                if constexpr (!SP) bl[i] = *reinterpret_cast<const bf16x8*>(b0 + i * 4096 + foff[s][1]);
             }
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int q = 0; q < 2; ++q) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[q], acc[i][q], 0, 0, 0);
+                for (int q = 0; q < 2; ++q) if constexpr (!SP) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[q], acc[i][q], 0, 0, 0);
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int q = 0; q < 2; ++q) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[q], acc[i][q], 0, 0, 0);
+                for (int q = 0; q < 2; ++q) if constexpr (!SP) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[q], acc[i][q], 0, 0, 0);
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -535,7 +539,7 @@ struct PsSmallParams {
 // STAGES = 4 (round 6): 128 KB, one workgroup per CU, THREE chunks in flight ahead of the one being computed -- for the short K slices of
 // the 4 x 4 level (4 - 9 chunks per workgroup), where a workgroup's life is a handful of DMA round trips and the two-stage form exposes one
 // L2 -> LDS latency per chunk.
-template <int EPI, int STAGES = 2>
+template <int EPI, bool SP, int STAGES = 2>
 __global__ __launch_bounds__(512, STAGES == 2 ? 4 : 2) void conv_ps128_kernel(PsSmallParams pp) {
     const PsParams& p = pp.q;
     constexpr int A_BYTES = 128 * 128, STAGE = 2 * A_BYTES;
@@ -619,17 +623,17 @@ __global__ __launch_bounds__(512, STAGES == 2 ? 4 : 2) void conv_ps128_kernel(Ps
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             const bf16x8 ah = *reinterpret_cast<const bf16x8*>(stage + abase + foff[s][0]);
-            const bf16x8 al = *reinterpret_cast<const bf16x8*>(stage + abase + foff[s][1]);
+            const bf16x8 al = SP ? bf16x8{} : *reinterpret_cast<const bf16x8*>(stage + abase + foff[s][1]);
             bf16x8 bh[2], bl[2];
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 bh[i] = *reinterpret_cast<const bf16x8*>(stage + bbase + i * 4096 + foff[s][0]);
-                bl[i] = *reinterpret_cast<const bf16x8*>(stage + bbase + i * 4096 + foff[s][1]);
+                if constexpr (!SP) bl[i] = *reinterpret_cast<const bf16x8*>(stage + bbase + i * 4096 + foff[s][1]);
             }
 #pragma unroll
-            for (int q = 0; q < 2; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[q], acc[q], 0, 0, 0);
+            for (int q = 0; q < 2; ++q) if constexpr (!SP) acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[q], acc[q], 0, 0, 0);
 #pragma unroll
-            for (int q = 0; q < 2; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[q], acc[q], 0, 0, 0);
+            for (int q = 0; q < 2; ++q) if constexpr (!SP) acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[q], acc[q], 0, 0, 0);
 #pragma unroll
             for (int q = 0; q < 2; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[q], acc[q], 0, 0, 0);
         }
@@ -783,7 +787,7 @@ __device__ __forceinline__ bf16x8 ps_tr_join(ps_short4 v0, ps_short4 v1) {
 // to the source-grid shift (dy, dx) with oy -> (p, dy): -1 -> (1, +1), 0 -> (0, 0), 1 -> (1, 0), 2 -> (0, -1):
 //     dE[e][co][ci] = sum_{source pixels (a, b)} dY[2a+p, 2b+q][co] * X[a+dy, b+dx][ci].
 // The bias gradient (sum of ALL dY) rides in the four (dy, dx) = (0, 0) entries, one bias row per class and K split.
-template <int STAGES, int NW, bool PH = false>
+template <int STAGES, int NW, bool SP, bool PH = false>
 __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 2) void conv_ps_wgrad_kernel(PsWgParams p) {
     constexpr int TMW = 8 / NW;        // 32-row co tiles per wave
     constexpr int NDMA = 16 / NW;      // pixel pairs per wave, operand and chunk
@@ -918,6 +922,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 2) void conv_ps_wgrad_kernel
         for (int i = 0; i < TMW; ++i)
 #pragma unroll
             for (int pl = 0; pl < 2; ++pl) {
+                if (SP && pl == 1 && !do_db) continue;   // single pass: dY's lo plane feeds the bias gradient only
                 f.a0[i][pl] = ps_tr_read<KOFF>(sbase + aoff[i][pl]);
                 f.a1[i][pl] = ps_tr_read<KOFF + 4 * 512>(sbase + aoff[i][pl]);
             }
@@ -925,6 +930,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 2) void conv_ps_wgrad_kernel
         for (int q = 0; q < 2; ++q)
 #pragma unroll
             for (int pl = 0; pl < 2; ++pl) {
+                if (SP && pl == 1) continue;
                 f.b0[q][pl] = ps_tr_read<KOFF>(sbase + boff[q][pl]);
                 f.b1[q][pl] = ps_tr_read<KOFF + 4 * 512>(sbase + boff[q][pl]);
             }
@@ -959,11 +965,11 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 2) void conv_ps_wgrad_kernel
 #pragma unroll
         for (int i = 0; i < TMW; ++i)
 #pragma unroll
-            for (int q = 0; q < 2; ++q) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[q], acc[i][q], 0, 0, 0);
+            for (int q = 0; q < 2; ++q) if constexpr (!SP) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[q], acc[i][q], 0, 0, 0);
 #pragma unroll
         for (int i = 0; i < TMW; ++i)
 #pragma unroll
-            for (int q = 0; q < 2; ++q) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[q], acc[i][q], 0, 0, 0);
+            for (int q = 0; q < 2; ++q) if constexpr (!SP) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[q], acc[i][q], 0, 0, 0);
 #pragma unroll
         for (int i = 0; i < TMW; ++i)
 #pragma unroll
@@ -1072,6 +1078,7 @@ constexpr int WG3_LDS_BYTES = 2 * WG_OP_BYTES + WG3_RING_UNITS * WG3_UNIT_BYTES;
 #endif
 constexpr int WG3_ABL = BD_WG3_ABL;
 
+template <bool SP>
 __global__ __launch_bounds__(512, 2) void conv_ps_wgrad3_kernel(PsWgParams p) {
     __shared__ __attribute__((aligned(128))) char smem[WG3_LDS_BYTES];
     const int tid = threadIdx.x;
@@ -1175,6 +1182,7 @@ __global__ __launch_bounds__(512, 2) void conv_ps_wgrad3_kernel(PsWgParams p) {
         }
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl) {
+            if (SP && pl == 1) continue;   // single pass: X's lo plane is never read
             f.b0[pl] = ps_tr_read<0>(xbase + boff[pl]);
             f.b1[pl] = ps_tr_read<4 * 512>(xbase + boff[pl]);
         }
@@ -1186,6 +1194,7 @@ __global__ __launch_bounds__(512, 2) void conv_ps_wgrad3_kernel(PsWgParams p) {
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int pl = 0; pl < 2; ++pl) {
+                if (SP && pl == 1 && !do_db) continue;   // single pass: dY's lo plane feeds the bias gradient only
                 f.a0[i][pl] = S ? ps_tr_read<16 * 512>(dbase + aoff[i][pl]) : ps_tr_read<0>(dbase + aoff[i][pl]);
                 f.a1[i][pl] = S ? ps_tr_read<16 * 512 + 4 * 512>(dbase + aoff[i][pl]) : ps_tr_read<4 * 512>(dbase + aoff[i][pl]);
             }
@@ -1198,9 +1207,9 @@ __global__ __launch_bounds__(512, 2) void conv_ps_wgrad3_kernel(PsWgParams p) {
     auto tap_mfmas = [&](floatx16 (&a)[2], const bf16x8 (&ah)[2], const bf16x8 (&al)[2], const BFrag& f) {
         const bf16x8 bh = ps_tr_join(f.b0[0], f.b1[0]), bl = ps_tr_join(f.b0[1], f.b1[1]);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) a[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh, a[i], 0, 0, 0);
+        for (int i = 0; i < 2; ++i) if constexpr (!SP) a[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh, a[i], 0, 0, 0);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) a[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl, a[i], 0, 0, 0);
+        for (int i = 0; i < 2; ++i) if constexpr (!SP) a[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl, a[i], 0, 0, 0);
 #pragma unroll
         for (int i = 0; i < 2; ++i) a[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh, a[i], 0, 0, 0);
     };
@@ -1496,6 +1505,8 @@ int conv3x3_ps(const bd_conv3x3_ps_desc& d, hipStream_t st) {
     BD_CHECK(d.ldx % 32 == 0 && ((uintptr_t)d.x_split & 127) == 0 && ((uintptr_t)d.w_split & 127) == 0, BD_ERR_UNSUPPORTED,
              "conv3x3_ps: split planes need ld %% 32 == 0 and 128-byte aligned bases");
     BD_CHECK(d.direction == 1 || d.direction == -1, BD_ERR_INVALID, "conv3x3_ps: direction must be +1 or -1");
+    BD_CHECK(sp_mode_valid(d.mode), BD_ERR_INVALID, "conv3x3_ps: unknown compute mode %d", d.mode);
+    const bool sp = d.mode == BD_MODE_BF16;   // single pass: hi*hi only
     // the epilogues and the split-K second pass move float4: every fp32 operand needs 16-byte rows
     BD_CHECK(d.ldy % 4 == 0 && ((uintptr_t)d.y & 15) == 0, BD_ERR_UNSUPPORTED, "conv3x3_ps: y needs ldy %% 4 == 0 and a 16-byte aligned base");
     BD_CHECK(!d.residual || (d.ldr % 4 == 0 && ((uintptr_t)d.residual & 15) == 0), BD_ERR_UNSUPPORTED,
@@ -1516,7 +1527,9 @@ int conv3x3_ps(const bd_conv3x3_ps_desc& d, hipStream_t st) {
     const bool large = ps_large(M, d.N);
     int rec = -1;
     if (prof_on()) {
-        rec = prof_begin(d.direction > 0 ? (large ? "conv_ps_fwd" : "conv_ps128_fwd") : (large ? "conv_ps_dgrad" : "conv_ps128_dgrad"),
+        static const char* kName[2][2][2] = {{{"conv_ps128_dgrad", "conv_ps_dgrad"}, {"conv_ps128_fwd", "conv_ps_fwd"}},
+                                             {{"conv_ps128_dgrad_bf16", "conv_ps_dgrad_bf16"}, {"conv_ps128_fwd_bf16", "conv_ps_fwd_bf16"}}};
+        rec = prof_begin(kName[sp][d.direction > 0][large],
                          2.0 * (double)M * d.N * 9.0 * d.K, ((double)M * d.K + 9.0 * d.K * d.N + (double)M * d.N) * 4.0, st);
     }
     const int epi = (d.residual ? 1 : 0) | (d.rowbias ? 2 : 0) | (d.accumulate ? 4 : 0);
@@ -1535,8 +1548,10 @@ int conv3x3_ps(const bd_conv3x3_ps_desc& d, hipStream_t st) {
                      "conv3x3_ps: gn_part needs a forward call with exactly one of rowbias / residual and bd_conv3x3_ps_gn_splits() > 0");
             p.gn_part = d.gn_part; p.gn_G = d.gn_groups; p.gn_lcpg = ilog2x(d.N / d.gn_groups);
         }
-#define PS_LAUNCH(E) do { if (v3) hipLaunchKernelGGL((conv_ps3_kernel<E>), grid, block, 0, st, p); \
-                          else hipLaunchKernelGGL((conv_ps_kernel<E>), grid, block, 0, st, p); } while (0)
+#define PS_LAUNCH(E) do { if (v3) { if (sp) hipLaunchKernelGGL((conv_ps3_kernel<E, true>), grid, block, 0, st, p); \
+                                    else hipLaunchKernelGGL((conv_ps3_kernel<E, false>), grid, block, 0, st, p); } \
+                          else if (sp) hipLaunchKernelGGL((conv_ps_kernel<E, true>), grid, block, 0, st, p); \
+                          else hipLaunchKernelGGL((conv_ps_kernel<E, false>), grid, block, 0, st, p); } while (0)
         switch (epi) {          // every combination has its own instantiation: the epilogue's addends are compile-time
             case 0: PS_LAUNCH(0); break;
             case 1: PS_LAUNCH(1); break;
@@ -1564,19 +1579,22 @@ int conv3x3_ps(const bd_conv3x3_ps_desc& d, hipStream_t st) {
         const dim3 grid((unsigned)(p.tiles_m * p.tiles_n * pp.ksplit)), block(512);
         // round 6: short K slices (the 4 x 4 level) take the four-stage form (three chunks in flight, one workgroup per CU)
         static const int deep_maxcps = getenv("BD_PS128_DEEP_MAXCPS") ? atoi(getenv("BD_PS128_DEEP_MAXCPS")) : 9;       // (A/B knob: 0 = off)
+#define PS128_LAUNCH(E, ...) do { if (sp) hipLaunchKernelGGL((conv_ps128_kernel<E, true, ##__VA_ARGS__>), grid, block, 0, st, pp); \
+                                      else hipLaunchKernelGGL((conv_ps128_kernel<E, false, ##__VA_ARGS__>), grid, block, 0, st, pp); } while (0)
         if (pp.ksplit > 1 && pp.cps <= deep_maxcps) {
-            hipLaunchKernelGGL((conv_ps128_kernel<0, 4>), grid, block, 0, st, pp);
+            PS128_LAUNCH(0, 4);
         } else
         switch (pp.ksplit > 1 ? 0 : epi) {
-            case 0: hipLaunchKernelGGL(conv_ps128_kernel<0>, grid, block, 0, st, pp); break;
-            case 1: hipLaunchKernelGGL(conv_ps128_kernel<1>, grid, block, 0, st, pp); break;
-            case 2: hipLaunchKernelGGL(conv_ps128_kernel<2>, grid, block, 0, st, pp); break;
-            case 3: hipLaunchKernelGGL(conv_ps128_kernel<3>, grid, block, 0, st, pp); break;
-            case 4: hipLaunchKernelGGL(conv_ps128_kernel<4>, grid, block, 0, st, pp); break;
-            case 5: hipLaunchKernelGGL(conv_ps128_kernel<5>, grid, block, 0, st, pp); break;
-            case 6: hipLaunchKernelGGL(conv_ps128_kernel<6>, grid, block, 0, st, pp); break;
-            default: hipLaunchKernelGGL(conv_ps128_kernel<7>, grid, block, 0, st, pp); break;
+            case 0: PS128_LAUNCH(0); break;
+            case 1: PS128_LAUNCH(1); break;
+            case 2: PS128_LAUNCH(2); break;
+            case 3: PS128_LAUNCH(3); break;
+            case 4: PS128_LAUNCH(4); break;
+            case 5: PS128_LAUNCH(5); break;
+            case 6: PS128_LAUNCH(6); break;
+            default: PS128_LAUNCH(7); break;
         }
+#undef PS128_LAUNCH
         BD_LAUNCH_CHECK("conv_ps128");
         if (pp.ksplit > 1) {
             hipLaunchKernelGGL(conv_ps128_reduce, dim3((unsigned)cdiv(M * (d.N / 4), 256)), dim3(256), 0, st, pp);
@@ -1635,6 +1653,8 @@ int conv3x3_ps_wgrad(const bd_conv3x3_ps_wgrad_desc& d, hipStream_t st) {
              "conv3x3_ps_wgrad: needs power-of-two H, W, Cin and Cout multiples of 128");
     BD_CHECK(d.ldx % 32 == 0 && d.lddy % 32 == 0 && ((uintptr_t)d.x_split & 127) == 0 && ((uintptr_t)d.dy_split & 127) == 0,
              BD_ERR_UNSUPPORTED, "conv3x3_ps_wgrad: split planes need ld %% 32 == 0 and 128-byte aligned bases");
+    BD_CHECK(sp_mode_valid(d.mode), BD_ERR_INVALID, "conv3x3_ps_wgrad: unknown compute mode %d", d.mode);
+    const bool sp = d.mode == BD_MODE_BF16;
     PsWgParams p = {};
     p.dy = reinterpret_cast<const char*>(d.dy_split); p.x = reinterpret_cast<const char*>(d.x_split);
     p.lddy = d.lddy; p.ldx = d.ldx; p.Cin = d.Cin; p.Cout = d.Cout; p.H = d.H; p.W = d.W; p.lw = ilog2x(d.W);
@@ -1654,7 +1674,7 @@ int conv3x3_ps_wgrad(const bd_conv3x3_ps_wgrad_desc& d, hipStream_t st) {
     }
     int rec = -1;
     if (prof_on())
-        rec = prof_begin(v3 ? "conv_ps_wgrad3" : "conv_ps_wgrad", 2.0 * (double)p.P * d.Cout * 9.0 * d.Cin,   // (round 6: the large layers' kernel is its own class)
+        rec = prof_begin(v3 ? (sp ? "conv_ps_wgrad3_bf16" : "conv_ps_wgrad3") : (sp ? "conv_ps_wgrad_bf16" : "conv_ps_wgrad"), 2.0 * (double)p.P * d.Cout * 9.0 * d.Cin,   // (round 6: the large layers' kernel is its own class)
                          ((double)p.P * (d.Cin + d.Cout) + 9.0 * d.Cin * d.Cout) * 4.0, st);
 #ifdef BD_PS_ABLATION
     p.ablate = getenv("BD_PS_ABLATE") ? atoi(getenv("BD_PS_ABLATE")) : 0;
@@ -1664,13 +1684,18 @@ int conv3x3_ps_wgrad(const bd_conv3x3_ps_wgrad_desc& d, hipStream_t st) {
     // (NW = 4 -- 2 x 2 waves of 64 x 64 -- measured within +-2 % of NW = 8 on every layer; one form is kept)
 #ifdef BD_PS_ABLATION
     static const int nw = getenv("BD_PS_WG_NW") ? atoi(getenv("BD_PS_WG_NW")) : 8;
-    if (nw == 4 && stages == 2) hipLaunchKernelGGL((conv_ps_wgrad_kernel<2, 4>), grid, dim3(256), 0, st, p);
-    else if (nw == 4) hipLaunchKernelGGL((conv_ps_wgrad_kernel<3, 4>), grid, dim3(256), 0, st, p);
+    if (nw == 4 && stages == 2) { if (sp) hipLaunchKernelGGL((conv_ps_wgrad_kernel<2, 4, true>), grid, dim3(256), 0, st, p);
+                                  else hipLaunchKernelGGL((conv_ps_wgrad_kernel<2, 4, false>), grid, dim3(256), 0, st, p); }
+    else if (nw == 4) { if (sp) hipLaunchKernelGGL((conv_ps_wgrad_kernel<3, 4, true>), grid, dim3(256), 0, st, p);
+                        else hipLaunchKernelGGL((conv_ps_wgrad_kernel<3, 4, false>), grid, dim3(256), 0, st, p); }
     else
 #endif
-    if (v3) hipLaunchKernelGGL(conv_ps_wgrad3_kernel, grid, dim3(512), 0, st, p);
-    else if (stages == 2) hipLaunchKernelGGL((conv_ps_wgrad_kernel<2, 8>), grid, dim3(512), 0, st, p);
-    else hipLaunchKernelGGL((conv_ps_wgrad_kernel<3, 8>), grid, dim3(512), 0, st, p);
+    if (v3 && sp) hipLaunchKernelGGL(conv_ps_wgrad3_kernel<true>, grid, dim3(512), 0, st, p);
+    else if (v3) hipLaunchKernelGGL(conv_ps_wgrad3_kernel<false>, grid, dim3(512), 0, st, p);
+    else if (stages == 2) { if (sp) hipLaunchKernelGGL((conv_ps_wgrad_kernel<2, 8, true>), grid, dim3(512), 0, st, p);
+                            else hipLaunchKernelGGL((conv_ps_wgrad_kernel<2, 8, false>), grid, dim3(512), 0, st, p); }
+    else if (sp) hipLaunchKernelGGL((conv_ps_wgrad_kernel<3, 8, true>), grid, dim3(512), 0, st, p);
+    else hipLaunchKernelGGL((conv_ps_wgrad_kernel<3, 8, false>), grid, dim3(512), 0, st, p);
     BD_LAUNCH_CHECK("conv_ps_wgrad");
     if (p.ksplit > 1) {
         const long long total = mn / 4 + (d.db ? d.Cout : 0);
@@ -1712,6 +1737,7 @@ int upsample_conv_wgrad(const bd_upsample_conv_desc& d, hipStream_t st) {
     BD_CHECK(d.ldx % 32 == 0 && d.lddy % 32 == 0 && ((uintptr_t)d.x_split & 127) == 0 && ((uintptr_t)d.dy_split & 127) == 0,
              BD_ERR_UNSUPPORTED, "bd_upsample_conv_wgrad: split planes need ld %% 32 == 0 and 128-byte aligned bases");
     BD_CHECK((long long)d.B * d.H * d.W * 4 < (1ll << 31), BD_ERR_UNSUPPORTED, "bd_upsample_conv_wgrad: pixel count overflows int32");
+    BD_CHECK(sp_mode_valid(d.mode), BD_ERR_INVALID, "bd_upsample_conv_wgrad: unknown compute mode %d", d.mode);
     const size_t need = upsample_conv_wgrad_workspace_bytes(d);
     BD_CHECK(d.workspace && d.workspace_bytes >= need, BD_ERR_WORKSPACE, "bd_upsample_conv_wgrad: workspace %zu < %zu", d.workspace_bytes, need);
     PsWgParams p = {};
@@ -1726,10 +1752,11 @@ int upsample_conv_wgrad(const bd_upsample_conv_desc& d, hipStream_t st) {
     float* de = p.out + (size_t)p.ksplit * ((size_t)mn + 4 * (size_t)d.Cout);
     int rec = -1;
     if (prof_on())
-        rec = prof_begin("conv_ph_ups_wgrad", 2.0 * (double)p.P * 4.0 * d.Cout * 9.0 * d.Cin,
+        rec = prof_begin(d.mode == BD_MODE_BF16 ? "conv_ph_ups_wgrad_bf16" : "conv_ph_ups_wgrad", 2.0 * (double)p.P * 4.0 * d.Cout * 9.0 * d.Cin,
                          ((double)p.P * (d.Cin + 4.0 * d.Cout) + 9.0 * d.Cin * d.Cout) * 4.0, st);
     const dim3 grid((unsigned)(p.tiles_m * p.tiles_n * p.ksplit));
-    hipLaunchKernelGGL((conv_ps_wgrad_kernel<2, 8, true>), grid, dim3(512), 0, st, p);
+    if (d.mode == BD_MODE_BF16) hipLaunchKernelGGL((conv_ps_wgrad_kernel<2, 8, true, true>), grid, dim3(512), 0, st, p);
+    else hipLaunchKernelGGL((conv_ps_wgrad_kernel<2, 8, false, true>), grid, dim3(512), 0, st, p);
     BD_LAUNCH_CHECK("conv_ps_wgrad (phase)");
     const long long total = mn / 4 + (d.db ? d.Cout : 0);
     hipLaunchKernelGGL(conv_ps_wgrad_reduce<false>, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, st, p.out, p.ksplit, mn, d.Cout, de, d.db, 4 * p.ksplit);

@@ -258,7 +258,7 @@ __global__ __launch_bounds__(256) void thin_expand_kernel(const float* __restric
     }
 }
 
-// Round 4: the expand direction on the matrix pipe (BD_MODE_BF16X3 only).  thin_expand_kernel is bound by plain v_fma_f32 issue (3 456 FMAs per pixel
+// Round 4: the expand direction on the matrix pipe (BD_MODE_BF16X3; BD_MODE_BF16 takes the same three-product kernel).  thin_expand_kernel is bound by plain v_fma_f32 issue (3 456 FMAs per pixel
 // for 128 output channels: 92 us for a 27 us stream of bytes at 256 x 256).  As a GEMM the layer is [pixels x 27] x [27 x C]: K = 27 pads to 32 = two
 // v_mfma_f32_32x32x16_bf16 steps, and the im2col operand needs no LDS: a lane of the A fragment IS one pixel and one octet of K, so it loads its
 // own 16 tap values (the 3-channel tensor is tiny: every read hits L1 / L2), splits them into bf16 hi | lo in registers (the same RNE / RNE
@@ -548,8 +548,9 @@ static int thin_expand_launch(int J, const float* in, long long ldi, const float
     const long long pixels = (long long)B * H * W;
     const long long runs = cdiv(pixels, 32);
     static const bool mfma_off = getenv("BD_THIN_MFMA") && atoi(getenv("BD_THIN_MFMA")) == 0;      // (A/B knob)
-    if (!mfma_off && mode == BD_MODE_BF16X3 && J == 3 && W % 32 == 0 && pixels % 32 == 0) {
-        // split-bf16 products like every other convolution of this mode; the exact-fp32 mode keeps the FMA kernel below
+    if (!mfma_off && mode_bf16(mode) && J == 3 && W % 32 == 0 && pixels % 32 == 0) {
+        // split-bf16 products like every other convolution of this mode; the exact-fp32 mode keeps the FMA kernel below.  BD_MODE_BF16 runs
+        // the same three-product kernel here (the 3-channel layers are bound by their fp32 loads, not by the MFMAs)
         int iters = 8;
         while (iters > 1 && runs / (4 * iters) < 512) iters >>= 1;        // >= 512 workgroups where the layer has them
         const dim3 grid((unsigned)cdiv(runs, 4 * iters), (unsigned)(N / 128)), block(256);
@@ -611,7 +612,7 @@ bool conv3x3_wgrad_is_thin(const bd_conv3x3_wgrad_desc& d) {
 }
 
 // returns 1 when it handled the call, 0 when the shape belongs to the igemm path, < 0 on error
-// Round 4: the two weight gradients on the matrix pipe (BD_MODE_BF16X3, W % 32 == 0).  Both are out[c][k] = sum_p wide[p][c] * col[p][k] with a
+// Round 4: the two weight gradients on the matrix pipe (BD_MODE_BF16X3 or BD_MODE_BF16 -- three products in both --, W % 32 == 0).  Both are out[c][k] = sum_p wide[p][c] * col[p][k] with a
 // 128-channel-wide tensor and a <= 32-column im2col of the 3-channel one (k = tap * 3 + channel; conv_in: col[p][k] = x[p + d(t)][j] and column 27 = 1
 // carries the bias gradient; conv_out: col[q][k] = dy[q - d(t)][o]).  The contraction runs over pixels, so the MFMA A operand is wide^T: lane = channel,
 // 8 consecutive pixels per K octet -- each of the 8 loads of a step is a coalesced 128-byte row piece per half-wave -- and the B operand is the lane's
@@ -707,7 +708,7 @@ int conv3x3_wgrad_thin(const bd_conv3x3_wgrad_desc& d, hipStream_t st) {
              need);
     float* part = reinterpret_cast<float*>(d.workspace);
     static const bool mfma_off = getenv("BD_THIN_MFMA") && atoi(getenv("BD_THIN_MFMA")) == 0;      // (A/B knob)
-    if (!mfma_off && d.mode == BD_MODE_BF16X3 && d.Ws % 32 == 0 && d.pad_t == 1 && d.pad_l == 1 && (thin_in ? d.Cin == 3 : d.Cout == 3)) {
+    if (!mfma_off && mode_bf16(d.mode) && d.Ws % 32 == 0 && d.pad_t == 1 && d.pad_l == 1 && (thin_in ? d.Cin == 3 : d.Cout == 3)) {
         const long long nsteps = g.pixels / 16;
         const int spw = (int)cdiv(nsteps, 512);                  // <= 512 partial rows (7 MB for the second pass to fold)
         const int rows = (int)cdiv(nsteps, spw);

@@ -18,6 +18,8 @@
 // 64 KB and <= 256 registers per wave leave room for TWO workgroups per CU, which de-phase -- one runs its epilogue / prologue while
 // the other is in its main loop; with 8 K chunks per tile that overlap is worth more than a deeper ring in one workgroup.
 // Long-K products (the weight gradients: K = all tokens) split K over workgroups with a fixed-order second pass (deterministic).
+// Single pass (SP, BD_MODE_BF16): only the hi fragments are read and each product is hi*hi; the a_colsum bias gradient keeps hi + lo
+// (its waves alone read A's lo plane).  The split-plane output is still written with both planes.
 #include "common.h"
 
 #include <cstdlib>
@@ -94,7 +96,7 @@ __device__ __forceinline__ void sp_tie(SpFrag<true>& f) {
 // y -> (bf16 hi = RNE, bf16 lo = RNE of the remainder): the split of bd_split_rows (common.h), packed hi | lo << 16
 __device__ __forceinline__ unsigned sp_split1(float v) { return bd_split1(v); }
 
-template <bool AKM, bool BKM>
+template <bool AKM, bool BKM, bool SP>
 __global__ __launch_bounds__(SP_NT, 2) void gemm_sp_kernel(SpParams p) {
     __shared__ __attribute__((aligned(128))) char smem[SP_LDS_BYTES];
     const int tid = threadIdx.x;
@@ -192,6 +194,7 @@ __global__ __launch_bounds__(SP_NT, 2) void gemm_sp_kernel(SpParams p) {
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int pl = 0; pl < 2; ++pl) {
+                if (SP && pl == 1 && !do_sum) continue;   // single pass: A's lo plane feeds the column sum only
                 if constexpr (AKM) {
                     fa.v0[i][pl] = sp_read_tr<SB + s * 16 * 512>(aoff[i][pl]);
                     fa.v1[i][pl] = sp_read_tr<SB + s * 16 * 512 + 4 * 512>(aoff[i][pl]);
@@ -203,6 +206,7 @@ __global__ __launch_bounds__(SP_NT, 2) void gemm_sp_kernel(SpParams p) {
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int pl = 0; pl < 2; ++pl) {
+                if (SP && pl == 1) continue;              // single pass: B's lo plane is never read
                 if constexpr (BKM) {
                     fb.v0[i][pl] = sp_read_tr<SB + s * 16 * 512>(boff[i][pl]);
                     fb.v1[i][pl] = sp_read_tr<SB + s * 16 * 512 + 4 * 512>(boff[i][pl]);
@@ -222,11 +226,11 @@ __global__ __launch_bounds__(SP_NT, 2) void gemm_sp_kernel(SpParams p) {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int q = 0; q < 2; ++q) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[q], acc[i][q], 0, 0, 0);
+            for (int q = 0; q < 2; ++q) if constexpr (!SP) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[q], acc[i][q], 0, 0, 0);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int q = 0; q < 2; ++q) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[q], acc[i][q], 0, 0, 0);
+            for (int q = 0; q < 2; ++q) if constexpr (!SP) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[q], acc[i][q], 0, 0, 0);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -438,6 +442,8 @@ size_t gemm_sp_workspace_bytes(const bd_gemm_sp_desc& d) {
 
 int gemm_sp(const bd_gemm_sp_desc& d, hipStream_t st) {
     BD_CHECK(d.a && d.b && (d.c || d.c_split), BD_ERR_INVALID, "bd_gemm_sp: null pointer");
+    BD_CHECK(sp_mode_valid(d.mode), BD_ERR_INVALID, "bd_gemm_sp: unknown compute mode %d", d.mode);
+    const bool sp = d.mode == BD_MODE_BF16;   // single pass: hi*hi only
     BD_CHECK(d.M > 0 && d.N > 0 && d.K > 0 && d.M % SP_T == 0 && d.N % SP_T == 0 && d.K % 32 == 0, BD_ERR_UNSUPPORTED,
              "bd_gemm_sp: needs M, N %% 128 == 0 and K %% 32 == 0 (M=%d N=%d K=%d)", d.M, d.N, d.K);
     const int batch = d.batch > 0 ? d.batch : 1;
@@ -474,13 +480,22 @@ int gemm_sp(const bd_gemm_sp_desc& d, hipStream_t st) {
     if (prof_on()) {   // bench.py roofline: algorithmic flops, unique operand + output bytes (planes are 4 B per element like fp32)
         const double nb = batch;
         const double outs = (d.c ? 1.0 : 0.0) + (d.c_split ? 1.0 : 0.0) + (d.residual ? 1.0 : 0.0) + (d.accumulate ? 1.0 : 0.0);
-        rec = prof_begin(d.a_kmajor && d.b_kmajor ? "gemm_sp_tn" : (d.b_kmajor ? "gemm_sp_nn" : (d.a_kmajor ? "gemm_sp_tn_a" : "gemm_sp_nt")),
+        static const char* kName[2][4] = {{"gemm_sp_nt", "gemm_sp_nn", "gemm_sp_tn_a", "gemm_sp_tn"},
+                                          {"gemm_sp_nt_bf16", "gemm_sp_nn_bf16", "gemm_sp_tn_a_bf16", "gemm_sp_tn_bf16"}};
+        rec = prof_begin(kName[sp][(d.a_kmajor ? 2 : 0) + (d.b_kmajor ? 1 : 0)],
                          2.0 * d.M * d.N * (double)d.K * nb, 4.0 * nb * ((double)d.M * d.K + (double)d.N * d.K + outs * d.M * d.N), st);
     }
-    if (d.a_kmajor && d.b_kmajor) hipLaunchKernelGGL((gemm_sp_kernel<true, true>), g, b, 0, st, p);
-    else if (d.a_kmajor) hipLaunchKernelGGL((gemm_sp_kernel<true, false>), g, b, 0, st, p);
-    else if (d.b_kmajor) hipLaunchKernelGGL((gemm_sp_kernel<false, true>), g, b, 0, st, p);
-    else hipLaunchKernelGGL((gemm_sp_kernel<false, false>), g, b, 0, st, p);
+    if (sp) {
+        if (d.a_kmajor && d.b_kmajor) hipLaunchKernelGGL((gemm_sp_kernel<true, true, true>), g, b, 0, st, p);
+        else if (d.a_kmajor) hipLaunchKernelGGL((gemm_sp_kernel<true, false, true>), g, b, 0, st, p);
+        else if (d.b_kmajor) hipLaunchKernelGGL((gemm_sp_kernel<false, true, true>), g, b, 0, st, p);
+        else hipLaunchKernelGGL((gemm_sp_kernel<false, false, true>), g, b, 0, st, p);
+    } else {
+        if (d.a_kmajor && d.b_kmajor) hipLaunchKernelGGL((gemm_sp_kernel<true, true, false>), g, b, 0, st, p);
+        else if (d.a_kmajor) hipLaunchKernelGGL((gemm_sp_kernel<true, false, false>), g, b, 0, st, p);
+        else if (d.b_kmajor) hipLaunchKernelGGL((gemm_sp_kernel<false, true, false>), g, b, 0, st, p);
+        else hipLaunchKernelGGL((gemm_sp_kernel<false, false, false>), g, b, 0, st, p);
+    }
     BD_LAUNCH_CHECK("gemm_sp");
     if (p.ksplit > 1) {
         const long long work = (long long)d.M * (d.N / 8);

@@ -124,6 +124,7 @@ struct KCStore {
 #pragma unroll
         for (int i = 0; i < NI; ++i) *reinterpret_cast<float4*>(s + (krow(tid) + (NT / 8) * i) * LDK + k4) = v[i];
     }
+    template <bool SP>
     __device__ __forceinline__ static void store_split(unsigned short* sh, unsigned short* sl, int tid, const float4 (&v)[NI]);
 };
 // RC thread map: every thread owns the float4 of rows r4..r4+3 at NI values of k, k_i = kfirst + KSTEP*i.
@@ -150,14 +151,16 @@ struct RCStore {
         for (int i = 0; i < NI; ++i) *reinterpret_cast<float4*>(s + (k0 + RCMap<R, NT>::KSTEP * i) * (R + 4) + r4) = v[i];
     }
     // split-bf16 planes, row-contiguous image [k][R + 32] bf16 (the global loads stay fully coalesced); the MFMA
-    // fragments are gathered from it with ds_read_b64_tr_b16 (hardware 4x4 transpose), see rc_frag()
+    // fragments are gathered from it with ds_read_b64_tr_b16 (hardware 4x4 transpose), see rc_frag().  SP (single pass,
+    // BD_MODE_BF16): the hi plane only, no lo is computed
+    template <bool SP>
     __device__ __forceinline__ static void store_split(unsigned short* sh, unsigned short* sl, int tid, const float4 (&v)[NI]) {
         const int r4 = RCMap<R, NT>::r4(tid), k0 = RCMap<R, NT>::kfirst(tid);
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
             const int o = (k0 + RCMap<R, NT>::KSTEP * i) * (R + 32) + r4;
             *reinterpret_cast<uint2*>(sh + o) = make_uint2(pack_hi(v[i].x, v[i].y), pack_hi(v[i].z, v[i].w));
-            *reinterpret_cast<uint2*>(sl + o) = make_uint2(pack_lo(v[i].x, v[i].y), pack_lo(v[i].z, v[i].w));
+            if constexpr (!SP) *reinterpret_cast<uint2*>(sl + o) = make_uint2(pack_lo(v[i].x, v[i].y), pack_lo(v[i].z, v[i].w));
         }
     }
 };
@@ -181,13 +184,14 @@ __device__ __forceinline__ bf16x8 rc_frag(const unsigned short* plane, int rowti
 }
 
 template <int R, int NT>
+template <bool SP>
 __device__ __forceinline__ void KCStore<R, NT>::store_split(unsigned short* sh, unsigned short* sl, int tid, const float4 (&v)[NI]) {
     const int k4 = (tid & 7) * 4;
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
         const int o = (krow(tid) + (NT / 8) * i) * LDH + k4;
         *reinterpret_cast<uint2*>(sh + o) = make_uint2(pack_hi(v[i].x, v[i].y), pack_hi(v[i].z, v[i].w));
-        *reinterpret_cast<uint2*>(sl + o) = make_uint2(pack_lo(v[i].x, v[i].y), pack_lo(v[i].z, v[i].w));
+        if constexpr (!SP) *reinterpret_cast<uint2*>(sl + o) = make_uint2(pack_lo(v[i].x, v[i].y), pack_lo(v[i].z, v[i].w));
     }
 }
 
@@ -436,7 +440,9 @@ struct WgtKCs {
     __device__ __forceinline__ void advance(const Opnd&) {
         if (++tap == 9) { tap = 0; c0 += BK; }
     }
+    template <bool SP>
     __device__ __forceinline__ static void store_split(unsigned short* sh, unsigned short* sl, int tid, const float4 (&v)[NI]) {
+        if (SP && plane_of(tid)) return;   // single pass: the lo plane is never read
         unsigned short* pl = plane_of(tid) ? sl : sh;
         const int k8 = (tid & 3) * 8;
 #pragma unroll
@@ -480,7 +486,9 @@ struct WgtRCs {
     __device__ __forceinline__ void advance(const Opnd&) {
         if (++tap == 9) { tap = 0; c0 += BK; }
     }
+    template <bool SP>
     __device__ __forceinline__ static void store_split(unsigned short* sh, unsigned short* sl, int tid, const float4 (&v)[NI]) {
+        if (SP && plane_of(tid)) return;   // single pass: the lo plane is never read
         unsigned short* pl = plane_of(tid) ? sl : sh;
         const int k0 = tid / LPK;
 #pragma unroll
@@ -941,7 +949,8 @@ __global__ __launch_bounds__(256) void igemm_kernel(IGemmParams p) {
 // split-bf16 kernel: same tiling / staging, but the register -> LDS store splits every fp32 value ONCE into
 // hi + lo bf16 planes ([rows][32 + 8] bf16 each, RC operands transposed in registers on the way), and the
 // K loop issues hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16 (fp32 accumulate) from ds_read_b128 fragments.
-template <int BM, int BN, class LA, class LB, int NT, int DEPTH>
+// SP (single pass, BD_MODE_BF16): the store computes and writes the hi plane only and the K loop issues hi*hi alone.
+template <int BM, int BN, class LA, class LB, int NT, int DEPTH, bool SP>
 __global__ __launch_bounds__(NT, NT / 128) void igemm_bf16x3_kernel(IGemmParams p) {   // (threads, min waves per SIMD)
     // waves: (NT/128) x 2 over the tile; 256 threads -> 64x64 per wave (2 workgroups = 2 waves per SIMD), 512 threads ->
     // 32x64 per wave: half the accumulators and half the staging registers per thread, 4 waves per SIMD
@@ -1008,8 +1017,8 @@ __global__ __launch_bounds__(NT, NT / 128) void igemm_bf16x3_kernel(IGemmParams 
 #pragma unroll
             for (int i = 0; i < LA::NI; ++i) add4(cs, ua[i]);
         }
-        LA::store_split(sAh, sAl, tid, ua);
-        LB::store_split(sBh, sBl, tid, ub);
+        LA::template store_split<SP>(sAh, sAl, tid, ua);
+        LB::template store_split<SP>(sBh, sBl, tid, ub);
         __syncthreads();
         la.advance(A);
         lb.advance(B);
@@ -1023,10 +1032,10 @@ __global__ __launch_bounds__(NT, NT / 128) void igemm_bf16x3_kernel(IGemmParams 
                 if (A_KC) {
                     const int o = (wm * WM + i * 32 + li) * LDH + 16 * s + 8 * h;
                     ah[i] = *reinterpret_cast<const bf16x8*>(sAh + o);
-                    al[i] = *reinterpret_cast<const bf16x8*>(sAl + o);
+                    if constexpr (!SP) al[i] = *reinterpret_cast<const bf16x8*>(sAl + o);
                 } else {
                     ah[i] = rc_frag<BM + 32>(sAh, wm * WM + i * 32, 16 * s, lane);
-                    al[i] = rc_frag<BM + 32>(sAl, wm * WM + i * 32, 16 * s, lane);
+                    if constexpr (!SP) al[i] = rc_frag<BM + 32>(sAl, wm * WM + i * 32, 16 * s, lane);
                 }
             }
 #pragma unroll
@@ -1034,20 +1043,22 @@ __global__ __launch_bounds__(NT, NT / 128) void igemm_bf16x3_kernel(IGemmParams 
                 if (B_KC) {
                     const int o = (wn * WN + i * 32 + li) * LDH + 16 * s + 8 * h;
                     bh[i] = *reinterpret_cast<const bf16x8*>(sBh + o);
-                    bl[i] = *reinterpret_cast<const bf16x8*>(sBl + o);
+                    if constexpr (!SP) bl[i] = *reinterpret_cast<const bf16x8*>(sBl + o);
                 } else {
                     bh[i] = rc_frag<BN + 32>(sBh, wn * WN + i * 32, 16 * s, lane);
-                    bl[i] = rc_frag<BN + 32>(sBl, wn * WN + i * 32, 16 * s, lane);
+                    if constexpr (!SP) bl[i] = rc_frag<BN + 32>(sBl, wn * WN + i * 32, 16 * s, lane);
                 }
             }
+            if constexpr (!SP) {
 #pragma unroll
-            for (int i = 0; i < TM; ++i)
+                for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int q = 0; q < TN; ++q) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[q], acc[i][q], 0, 0, 0);
+                    for (int q = 0; q < TN; ++q) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[q], acc[i][q], 0, 0, 0);
 #pragma unroll
-            for (int i = 0; i < TM; ++i)
+                for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int q = 0; q < TN; ++q) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[q], acc[i][q], 0, 0, 0);
+                    for (int q = 0; q < TN; ++q) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[q], acc[i][q], 0, 0, 0);
+            }
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -1290,7 +1301,7 @@ static bool presplit_ok(const bd_igemm_desc& d) {
     const bd_operand& o = d.B;
     // whole 32-element blocks: block-aligned base (the caller passes split + 2*e for a base element e % 32 == 0),
     // ld % 32 == 0 (rows start on blocks), channel count % 32 == 0, N % 32 == 0 (RC rows come in blocks)
-    return d.mode == BD_MODE_BF16X3 && o.split && ((uintptr_t)o.split & 127) == 0 && (o.ld & 31) == 0 && (o.C & 31) == 0 &&
+    return mode_bf16(d.mode) && o.split && ((uintptr_t)o.split & 127) == 0 && (o.ld & 31) == 0 && (o.C & 31) == 0 &&
            (d.N & 31) == 0 && d.batch_outer * d.batch_inner == 1;
 }
 
@@ -1316,35 +1327,35 @@ static Cls classify(const bd_igemm_desc& d, bool fast) {
 }
 
 // TR = true selects the split-bf16 kernel (RC operands keep the coalesced thread map; transposition happens in the
-// ds_read_b64_tr_b16 fragment reads)
-template <int T, bool TR, class LA, class LB, int NT = 256, int DEPTH = 2>
+// ds_read_b64_tr_b16 fragment reads); SP its single-pass instantiation (BD_MODE_BF16)
+template <int T, bool TR, bool SP, class LA, class LB, int NT = 256, int DEPTH = 2>
 static void launch1(const IGemmParams& p, dim3 grid, hipStream_t st) {
-    if constexpr (TR) hipLaunchKernelGGL((igemm_bf16x3_kernel<T, T, LA, LB, NT, DEPTH>), grid, dim3(NT), 0, st, p);
+    if constexpr (TR) hipLaunchKernelGGL((igemm_bf16x3_kernel<T, T, LA, LB, NT, DEPTH, SP>), grid, dim3(NT), 0, st, p);
     else hipLaunchKernelGGL((igemm_kernel<T, T, LA, LB>), grid, dim3(256), 0, st, p);
 }
 
 // fast classes; NT = threads per workgroup (512 only for the split-bf16 128x128 tiles: 8 waves of 32x64)
-template <int T, bool TR, int NT>
+template <int T, bool TR, bool SP, int NT>
 static bool launch_fast(const IGemmParams& p, Cls cls, dim3 grid, hipStream_t st) {
     switch (cls) {
-        case CLS_CONV_FWD: launch1<T, TR, ConvKC<T, NT>, WgtKC<T, NT>, NT>(p, grid, st); return true;
-        case CLS_GEMM_NT: launch1<T, TR, DenseKC<T, NT>, DenseKC<T, NT>, NT>(p, grid, st); return true;
-        case CLS_CONV_DGRAD: launch1<T, TR, TConvKC<T, NT>, WgtRC<T, NT>, NT>(p, grid, st); return true;
-        case CLS_GEMM_NN: launch1<T, TR, DenseKC<T, NT>, DenseRC<T, NT>, NT, (NT == 512 ? 1 : 2)>(p, grid, st); return true;
-        case CLS_CONV_WGRAD: launch1<T, TR, DenseRC<T, NT>, ConvRC<T, NT>, NT, (NT == 512 ? 1 : 2)>(p, grid, st); return true;
-        case CLS_CONV_WGRAD_SAME: launch1<T, TR, DenseRC<T, NT>, ConvRCs<T, NT>, NT, (NT == 512 ? 1 : 2)>(p, grid, st); return true;
-        case CLS_GEMM_TN: launch1<T, TR, DenseRC<T, NT>, DenseRC<T, NT>, NT, (NT == 512 ? 1 : 2)>(p, grid, st); return true;
+        case CLS_CONV_FWD: launch1<T, TR, SP, ConvKC<T, NT>, WgtKC<T, NT>, NT>(p, grid, st); return true;
+        case CLS_GEMM_NT: launch1<T, TR, SP, DenseKC<T, NT>, DenseKC<T, NT>, NT>(p, grid, st); return true;
+        case CLS_CONV_DGRAD: launch1<T, TR, SP, TConvKC<T, NT>, WgtRC<T, NT>, NT>(p, grid, st); return true;
+        case CLS_GEMM_NN: launch1<T, TR, SP, DenseKC<T, NT>, DenseRC<T, NT>, NT, (NT == 512 ? 1 : 2)>(p, grid, st); return true;
+        case CLS_CONV_WGRAD: launch1<T, TR, SP, DenseRC<T, NT>, ConvRC<T, NT>, NT, (NT == 512 ? 1 : 2)>(p, grid, st); return true;
+        case CLS_CONV_WGRAD_SAME: launch1<T, TR, SP, DenseRC<T, NT>, ConvRCs<T, NT>, NT, (NT == 512 ? 1 : 2)>(p, grid, st); return true;
+        case CLS_GEMM_TN: launch1<T, TR, SP, DenseRC<T, NT>, DenseRC<T, NT>, NT, (NT == 512 ? 1 : 2)>(p, grid, st); return true;
         case CLS_CONV_FWD_WS:
-            if constexpr (TR) { launch1<T, true, ConvKC<T, NT>, WgtKCs<T, NT>, NT>(p, grid, st); return true; }
+            if constexpr (TR) { launch1<T, true, SP, ConvKC<T, NT>, WgtKCs<T, NT>, NT>(p, grid, st); return true; }
             return false;
         case CLS_CONV_DGRAD_WS:
-            if constexpr (TR) { launch1<T, true, TConvKC<T, NT>, WgtRCs<T, NT>, NT>(p, grid, st); return true; }
+            if constexpr (TR) { launch1<T, true, SP, TConvKC<T, NT>, WgtRCs<T, NT>, NT>(p, grid, st); return true; }
             return false;
         default: return false;
     }
 }
 
-template <int T, bool TR>
+template <int T, bool TR, bool SP>
 static void launch_tile(const IGemmParams& p, const bd_igemm_desc& d, Cls cls, dim3 grid, hipStream_t st) {
     // split-bf16 128x128 tiles run with 512 threads (8 waves of 32x64, 4 waves per SIMD): half the accumulators and
     // staging registers per thread buys the occupancy that hides the split / staging work (conv fwd +7 %, dgrad +9 %,
@@ -1352,14 +1363,14 @@ static void launch_tile(const IGemmParams& p, const bd_igemm_desc& d, Cls cls, d
     // only with a single prefetch register set (DEPTH 1).  BD_IGEMM_NT=256 forces the narrow form everywhere.
     static const bool narrow = getenv("BD_IGEMM_NT") && atoi(getenv("BD_IGEMM_NT")) == 256;
     if constexpr (TR && T == 128) {
-        if (!narrow && launch_fast<T, TR, 512>(p, cls, grid, st)) return;
+        if (!narrow && launch_fast<T, TR, SP, 512>(p, cls, grid, st)) return;
     }
-    if (launch_fast<T, TR, 256>(p, cls, grid, st)) return;
+    if (launch_fast<T, TR, SP, 256>(p, cls, grid, st)) return;
     const bool akc = d.A.kc != 0, bkc = d.B.kc != 0;
-    if (akc && bkc) launch1<T, TR, GenericKC<T>, GenericKC<T>>(p, grid, st);
-    else if (akc && !bkc) launch1<T, TR, GenericKC<T>, GenericRC<T, 256>>(p, grid, st);
-    else if (!akc && !bkc) launch1<T, TR, GenericRC<T, 256>, GenericRC<T, 256>>(p, grid, st);
-    else launch1<T, TR, GenericRC<T, 256>, GenericKC<T>>(p, grid, st);
+    if (akc && bkc) launch1<T, TR, SP, GenericKC<T>, GenericKC<T>>(p, grid, st);
+    else if (akc && !bkc) launch1<T, TR, SP, GenericKC<T>, GenericRC<T, 256>>(p, grid, st);
+    else if (!akc && !bkc) launch1<T, TR, SP, GenericRC<T, 256>, GenericRC<T, 256>>(p, grid, st);
+    else launch1<T, TR, SP, GenericRC<T, 256>, GenericKC<T>>(p, grid, st);
 }
 
 int igemm_launch(const bd_igemm_desc& d, hipStream_t stream) {
@@ -1367,7 +1378,7 @@ int igemm_launch(const bd_igemm_desc& d, hipStream_t stream) {
     BD_CHECK(d.batch_outer >= 1 && d.batch_inner >= 1, BD_ERR_INVALID, "igemm: batch counts must be >= 1");
     BD_CHECK(d.C != nullptr, BD_ERR_INVALID, "igemm: C is null");
     BD_CHECK(d.tile == 0 || d.tile == 64 || d.tile == 128, BD_ERR_INVALID, "igemm: tile must be 0, 64 or 128");
-    BD_CHECK(d.mode == BD_MODE_F32 || d.mode == BD_MODE_BF16X3, BD_ERR_INVALID, "igemm: unknown compute mode %d", d.mode);
+    BD_CHECK(mode_valid(d.mode), BD_ERR_INVALID, "igemm: unknown compute mode %d", d.mode);
     BD_TRY(validate_operand(d.A, "A"));
     BD_TRY(validate_operand(d.B, "B"));
     BD_CHECK(!(d.rowbias && d.rows_per_group <= 0), BD_ERR_INVALID, "igemm: rowbias needs rows_per_group > 0");
@@ -1410,22 +1421,26 @@ int igemm_launch(const bd_igemm_desc& d, hipStream_t stream) {
             return (double)rows * d.K * 4.0;
         };
         char name[128];
+        const char* msuf = d.mode == BD_MODE_BF16X3 ? "_bf16x3" : d.mode == BD_MODE_BF16 ? "_bf16" : "";
         static const bool shapes = getenv("BD_PROF_SHAPES") != nullptr;   // one class per shape (tuning aid)
         if (shapes)
             snprintf(name, sizeof(name), "igemm_%s_%d%s M%d N%d K%d b%d ks%d e%d%d%d%d", kClsName[cls], c.tile,
-                     d.mode == BD_MODE_BF16X3 ? "_bf16x3" : "", d.M, d.N, d.K, nb, c.ksplit, d.bias ? 1 : 0, d.rowbias ? 1 : 0,
+                     msuf, d.M, d.N, d.K, nb, c.ksplit, d.bias ? 1 : 0, d.rowbias ? 1 : 0,
                      d.residual ? 1 : 0, d.accumulate ? 1 : 0);
         else
-            snprintf(name, sizeof(name), "igemm_%s_%d%s", kClsName[cls], c.tile, d.mode == BD_MODE_BF16X3 ? "_bf16x3" : "");
+            snprintf(name, sizeof(name), "igemm_%s_%d%s", kClsName[cls], c.tile, msuf);
         rec = prof_begin(name, 2.0 * d.M * d.N * (double)d.K * nb,
                          (op_bytes(d.A, d.M) + op_bytes(d.B, d.N) + (double)d.M * d.N * 4.0) * nb, stream);
     }
     if (d.mode == BD_MODE_BF16X3) {
-        if (c.tile == 128) launch_tile<128, true>(p, d, cls, grid, stream);
-        else launch_tile<64, true>(p, d, cls, grid, stream);
+        if (c.tile == 128) launch_tile<128, true, false>(p, d, cls, grid, stream);
+        else launch_tile<64, true, false>(p, d, cls, grid, stream);
+    } else if (d.mode == BD_MODE_BF16) {
+        if (c.tile == 128) launch_tile<128, true, true>(p, d, cls, grid, stream);
+        else launch_tile<64, true, true>(p, d, cls, grid, stream);
     } else {
-        if (c.tile == 128) launch_tile<128, false>(p, d, cls, grid, stream);
-        else launch_tile<64, false>(p, d, cls, grid, stream);
+        if (c.tile == 128) launch_tile<128, false, false>(p, d, cls, grid, stream);
+        else launch_tile<64, false, false>(p, d, cls, grid, stream);
     }
     BD_LAUNCH_CHECK("igemm");
     if (c.ksplit > 1) {

@@ -93,7 +93,7 @@ struct Ctx {
     // before node k+2 reuses their arena (and at the end of every backward call).  Null = everything on `st`.
     hipStream_t st2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};
     char* opws2 = nullptr; int par = 0; bool launched = false, pend[2] = {false, false};
-    const uint16_t* w_split = nullptr;   // pre-split weights (BF16X3, bd_split_bf16 layout): element e of params <-> 2*e here
+    const uint16_t* w_split = nullptr;   // pre-split weights (the bf16 modes, bd_split_bf16 layout): element e of params <-> 2*e here
     const uint16_t* wT_split = nullptr;  // transposed split planes Wt[ci][tap][co] of the 3x3 conv weights, same element offsets
     std::vector<char> ginit;
     // GroupNorm weight / bias gradients: the layers leave their per-sample partials in `gnpart` and ONE launch per
@@ -282,7 +282,7 @@ struct bd_unet {
     }
     // GEMM on split planes (gemm_sp.hip); aux: a weight gradient, on the side stream
     int gemm_s(Ctx& c, bd_gemm_sp_desc& g, bool aux = false) const {
-        g.workspace_bytes = c.opws_bytes;
+        g.workspace_bytes = c.opws_bytes; g.mode = cfg.compute_mode;
         if (c.dry) {
             const size_t n = gemm_sp_workspace_bytes(g);
             if (n > c.opws_need) c.opws_need = n;
@@ -394,14 +394,14 @@ struct bd_unet {
         return on_aux(c, [&](hipStream_t st, char* ws) { d.workspace = ws; return conv3x3_wgrad(d, st); });
     }
     // pre-split / LDS-DMA convolution (conv_ps.hip) for the stride-1 3x3 convs whose operands the producers can emit as
-    // split planes: BF16X3 mode only (same arithmetic, bit-identical), shapes per conv3x3_ps_supported
+    // split planes: the bf16 modes only (same arithmetic as igemm, bit-identical), shapes per conv3x3_ps_supported
     // One decision per convolution, for its forward, data gradient and weight gradient alike (they share the split
     // operands), taken on the batch the workspace is laid out for (c.LB: the forward's half-batch pipelines and the
     // backward must agree).
     bool ps_ok(const Ctx& c, int H, int W, int Cin, int Cout) const {
         static const bool off = getenv("BD_CONV_PS") && atoi(getenv("BD_CONV_PS")) == 0;
         const int B = c.LB > 0 ? c.LB : c.B;
-        return !off && cfg.compute_mode == BD_MODE_BF16X3 && (c.dry || c.w_split) && conv3x3_ps_supported(B, H, W, Cin, Cout) &&
+        return !off && mode_bf16(cfg.compute_mode) && (c.dry || c.w_split) && conv3x3_ps_supported(B, H, W, Cin, Cout) &&
                conv3x3_ps_supported(B, H, W, Cout, Cin) && conv3x3_ps_wgrad_supported(B, H, W, Cin, Cout);
     }
     // phase-decomposed forms (conv_ph.hip): the upsample convolution on its SOURCE grid, the stride-2 data gradient by parity class
@@ -410,10 +410,10 @@ struct bd_unet {
     bool phase_ok(const Ctx& c, int H, int W, int Cin, int Cout, int classes = 4, int min_wgs = 128) const {
         const int B = c.LB > 0 ? c.LB : c.B;
         const long long wgs = (long long)classes * (((long long)B * H * W + 255) / 256) * (Cout / 128);
-        return cfg.compute_mode == BD_MODE_BF16X3 && (c.dry || c.w_split) && upsample_conv_ps_supported(B, H, W, Cin, Cout) && wgs >= min_wgs;
+        return mode_bf16(cfg.compute_mode) && (c.dry || c.w_split) && upsample_conv_ps_supported(B, H, W, Cin, Cout) && wgs >= min_wgs;
     }
     int conv_pw(Ctx& c, bd_conv3x3_ps_wgrad_desc& d) const {
-        d.workspace_bytes = c.opws_bytes;
+        d.workspace_bytes = c.opws_bytes; d.mode = cfg.compute_mode;
         if (c.dry) {
             note_conv(c);
             const size_t n = conv3x3_ps_wgrad_workspace_bytes(d);      // K-split slabs of this layer (grow with the tile of the shared-tap form)
@@ -431,7 +431,7 @@ struct bd_unet {
     }
     static uint16_t* U16(float* p) { return reinterpret_cast<uint16_t*>(p); }
     int conv_p(Ctx& c, bd_conv3x3_ps_desc& d) const {
-        d.workspace = c.opws; d.workspace_bytes = c.opws_bytes;
+        d.workspace = c.opws; d.workspace_bytes = c.opws_bytes; d.mode = cfg.compute_mode;
         if (c.dry) { note_conv(c); return BD_OK; }
         return conv3x3_ps(d, c.st);
     }
@@ -765,7 +765,7 @@ void bd_unet::node_attention(const std::string& pre, const View& x, const View& 
     // weights' planes are the per-step bd_split_bf16 copy (K-contiguous rows: the layout a [N][K] weight wants forward, and the K-major
     // operand of its data gradient as it stands).  N = 256 tokens, head dim 256 (attn_sp_supported); the mid block (4 x 4) stays below.
     auto use_sp = [=](const Ctx& c) {
-        return cfg.compute_mode == BD_MODE_BF16X3 && (c.dry || c.w_split) && attn_sp_supported(N, dh) &&
+        return mode_bf16(cfg.compute_mode) && (c.dry || c.w_split) && attn_sp_supported(N, dh) &&
                gemm_sp_supported((int)((int64_t)(c.LB > 0 ? c.LB : c.B) * N), C, C) && gemm_sp_supported(3 * C, C, 32);
     };
     const int gs_in = claim_gsplit(x, true);
@@ -793,7 +793,7 @@ void bd_unet::node_attention(const std::string& pre, const View& x, const View& 
             if (!c.dry) {
                 bd_attn_sp_desc a = {};
                 a.B = c.B; a.heads = heads; a.N = N; a.dh = dh; a.qkv_split = U16(BP(c, b_qkv)); a.ld = 3 * C; a.scale = sm_scale;
-                a.o_split = U16(BP(c, b_o)); a.ldo = C; a.pt_split = c.training ? U16(BP(c, b_p)) : nullptr;
+                a.o_split = U16(BP(c, b_o)); a.ldo = C; a.pt_split = c.training ? U16(BP(c, b_p)) : nullptr; a.mode = cfg.compute_mode;
                 BD_TRY(attn_sp_fwd(a, c.st));
             }
             bd_gemm_sp_desc o = {};      // y = (o Wp^T + b + x) / scale
@@ -853,7 +853,7 @@ void bd_unet::node_attention(const std::string& pre, const View& x, const View& 
                 bd_attn_sp_desc a = {};
                 a.B = c.B; a.heads = heads; a.N = N; a.dh = dh; a.qkv_split = U16(BP(c, b_qkv)); a.ld = 3 * C; a.scale = sm_scale;
                 a.pt_split = U16(BP(c, b_p)); a.do_split = U16(BP(c, b_do)); a.lddo = C; a.dst_split = U16(BP(c, b_dp));
-                a.dqkv_split = U16(BP(c, b_dqkv)); a.lddqkv = 3 * C;
+                a.dqkv_split = U16(BP(c, b_dqkv)); a.lddqkv = 3 * C; a.mode = cfg.compute_mode;
                 BD_TRY(attn_sp_bwd(a, c.st));
             }
             bd_gemm_sp_desc wq = {};     // dWqkv = dqkv^T n, dbqkv = column sums of dqkv  (side stream)
@@ -948,7 +948,7 @@ void bd_unet::node_downsample(const std::string& pre, const View& x, const View&
             bd_conv3x3_s2_dgrad_desc g = {};
             g.B = c.B; g.Ho = Ho; g.Wo = Wo; g.Cin = C; g.Cout = C; g.pad = pad;
             g.dy_split = U16(dyS); g.lddy = C; g.wT_split = c.wT_split + 2 * pw;
-            g.dx = GP(c, x); g.lddx = x.ld; g.accumulate = acc;
+            g.dx = GP(c, x); g.lddx = x.ld; g.accumulate = acc; g.mode = cfg.compute_mode;
             return conv3x3_s2_dgrad_ps(g, c.st);
         }
         bd_conv3x3_dgrad_desc g = {};
@@ -986,6 +986,7 @@ void bd_unet::node_upsample(const std::string& pre, const View& x, const View& y
             BD_TRY(split_rows(c, VP(c, x), x.ld, (int64_t)c.B * H * W, C, BP(c, b_xS)));
             if (c.dry) return (int)BD_OK;
             bd_upsample_conv_desc d = {};
+            d.mode = cfg.compute_mode;
             d.B = c.B; d.H = H; d.W = W; d.Cin = C; d.Cout = C;
             d.x_split = U16(BP(c, b_xS)); d.ldx = C; d.e_split = U16(BP(c, b_e)); d.bias = c.params + pb;
             d.y = VP(c, y); d.ldy = y.ld;
@@ -1014,6 +1015,7 @@ void bd_unet::node_upsample(const std::string& pre, const View& x, const View& y
         if (phase_ok(c, H, W, C, C)) {
             if (!ready) BD_TRY(split_rows(c, dy, y.ld, (int64_t)c.B * 4 * H * W, C, dyS));
             bd_upsample_conv_desc d = {};
+            d.mode = cfg.compute_mode;
             d.B = c.B; d.H = H; d.W = W; d.Cin = C; d.Cout = C;
             d.x_split = U16(BP(c, b_xS)); d.ldx = C; d.dy_split = U16(dyS); d.lddy = C;
             d.et_split = U16(BP(c, b_et)); d.dx = GP(c, x); d.lddx = x.ld; d.accumulate = acc;
@@ -1299,7 +1301,7 @@ extern "C" int bd_unet_create(const bd_unet_config* cfg, bd_unet** out) {
                      "bd_unet_create: attention_head_dim %d must divide %d and be a multiple of 4", cfg->attention_head_dim, C);
     }
     BD_CHECK(cfg->mid_block_scale_factor != 0.f, BD_ERR_INVALID, "bd_unet_create: mid_block_scale_factor == 0");
-    BD_CHECK(cfg->compute_mode == BD_MODE_F32 || cfg->compute_mode == BD_MODE_BF16X3, BD_ERR_INVALID, "bd_unet_create: compute_mode %d", cfg->compute_mode);
+    BD_CHECK(mode_valid(cfg->compute_mode), BD_ERR_INVALID, "bd_unet_create: compute_mode %d", cfg->compute_mode);
     bd_unet* u = new (std::nothrow) bd_unet();
     BD_CHECK(u, BD_ERR_INVALID, "bd_unet_create: out of host memory");
     u->cfg = *cfg;
@@ -1342,7 +1344,7 @@ extern "C" int bd_unet_set_static_weights(bd_unet* u, int enabled) {
     return BD_OK;
 }
 extern "C" int bd_unet_set_compute_mode(bd_unet* u, int mode) {
-    BD_CHECK(u && (mode == BD_MODE_F32 || mode == BD_MODE_BF16X3), BD_ERR_INVALID, "bd_unet_set_compute_mode: bad arguments");
+    BD_CHECK(u && mode_valid(mode), BD_ERR_INVALID, "bd_unet_set_compute_mode: bad arguments (mode %d)", mode);
     if (u->cfg.compute_mode != mode) {
         u->lay_B = -1;   // the op-workspace bound depends on which kernels the mode selects: lay out again
         u->prep_params = nullptr; u->prep_ws = nullptr; u->prep_B = -1;   // ... and the prepared weight planes belong to the old mode
@@ -1391,7 +1393,7 @@ static int unet_ctx(bd_unet* u, Ctx& c, int B, int training, void* workspace, si
     const size_t fl = (size_t)(u->value_floats + u->grad_floats + u->scratch_floats) * sizeof(float);
     c.opws = reinterpret_cast<char*>(workspace) + align_up(fl, 256);
     c.opws_bytes = u->opws_bytes;
-    if (u->cfg.compute_mode == BD_MODE_BF16X3) {
+    if (mode_bf16(u->cfg.compute_mode)) {
         c.w_split = reinterpret_cast<const uint16_t*>(c.opws + align_up(u->opws_bytes, 256));
     }
     c.opws2 = c.opws + align_up(u->opws_bytes, 256) + 2 * wsplit_bytes(u);

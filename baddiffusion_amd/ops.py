@@ -275,8 +275,9 @@ def split_wT(w):
 
 
 def conv3x3_ps(x_split, w_split, B, H, W, K, N, direction=1, bias=None, rowbias=None, residual=None, out_scale=1.0,
-               out=None, accumulate=False, gn_groups=0):
+               out=None, accumulate=False, gn_groups=0, mode=0):
     """stride-1 pad-1 3x3 convolution (direction +1) / data gradient (-1) on pre-split operands -> fp32 [B,H,W,N].
+    mode (every split-plane wrapper): 0 / 1 = BD_MODE_BF16X3 (hi*hi + hi*lo + lo*hi), 2 = BD_MODE_BF16 (hi*hi, single pass).
     gn_groups > 0: also the GroupNorm partials of y from the epilogue -> (y, partials [B, S, gn_groups, 2] fp64), S =
     bd_conv3x3_ps_gn_splits() (raises when the call cannot produce them)."""
     lib = L.load(); _need_cuda(x_split, w_split, bias, rowbias, residual)
@@ -290,7 +291,7 @@ def conv3x3_ps(x_split, w_split, B, H, W, K, N, direction=1, bias=None, rowbias=
     d = L.ConvPsDesc(B=B, H=H, W=W, K=K, N=N, direction=direction, x_split=L.ptr(x_split), ldx=K, w_split=L.ptr(w_split),
                      bias=L.ptr(bias), rowbias=L.ptr(rowbias), ld_rowbias=rowbias.stride(0) if rowbias is not None else 0,
                      residual=L.ptr(residual), ldr=_ld(residual) if residual is not None else 0, out_scale=out_scale,
-                     y=L.ptr(y), ldy=_ld(y), accumulate=int(accumulate))
+                     y=L.ptr(y), ldy=_ld(y), accumulate=int(accumulate), mode=mode)
     ws = workspace(lib.bd_conv3x3_ps_workspace_bytes(C.byref(d)), x_split.device, "ps")
     d.workspace = L.ptr(ws); d.workspace_bytes = ws.numel()
     if part is not None:
@@ -299,13 +300,13 @@ def conv3x3_ps(x_split, w_split, B, H, W, K, N, direction=1, bias=None, rowbias=
     return y if part is None else (y, part)
 
 
-def conv3x3_ps_wgrad(x_split, dy_split, B, H, W, Cin, Cout, with_db=False):
+def conv3x3_ps_wgrad(x_split, dy_split, B, H, W, Cin, Cout, with_db=False, mode=0):
     """dw [Cout,3,3,Cin] (and db [Cout]) of the stride-1 pad-1 conv from split-plane operands."""
     lib = L.load(); _need_cuda(x_split, dy_split)
     dw = torch.empty(Cout, 3, 3, Cin, device=x_split.device)
     db = torch.empty(Cout, device=x_split.device) if with_db else None
     d = L.ConvPsWgradDesc(B=B, H=H, W=W, Cin=Cin, Cout=Cout, x_split=L.ptr(x_split), ldx=Cin, dy_split=L.ptr(dy_split),
-                          lddy=Cout, dw=L.ptr(dw), db=L.ptr(db))
+                          lddy=Cout, dw=L.ptr(dw), db=L.ptr(db), mode=mode)
     ws = workspace(lib.bd_conv3x3_ps_wgrad_workspace_bytes(C.byref(d)), x_split.device, "ps_wgrad")
     d.workspace = L.ptr(ws); d.workspace_bytes = ws.numel()
     L.check(lib.bd_conv3x3_ps_wgrad(C.byref(d), L.stream()), "bd_conv3x3_ps_wgrad")
@@ -323,48 +324,48 @@ def upsample_weights(w):
     return e, et
 
 
-def upsample_conv_fwd(x_split, e_split, B, H, W, Cin, Cout, bias=None):
+def upsample_conv_fwd(x_split, e_split, B, H, W, Cin, Cout, bias=None, mode=0):
     """y [B,2H,2W,Cout] = conv3x3(nearest_up2(x)) + bias from the SOURCE-grid split planes of x and the E planes."""
     lib = L.load(); _need_cuda(x_split, e_split, bias)
     y = torch.empty(B, 2 * H, 2 * W, Cout, device=x_split.device)
     d = L.UpsampleConvDesc(B=B, H=H, W=W, Cin=Cin, Cout=Cout, x_split=L.ptr(x_split), ldx=Cin, e_split=L.ptr(e_split), bias=L.ptr(bias),
-                           y=L.ptr(y), ldy=Cout)
+                           y=L.ptr(y), ldy=Cout, mode=mode)
     L.check(lib.bd_upsample_conv_fwd(C.byref(d), L.stream()), "bd_upsample_conv_fwd")
     return y
 
 
-def upsample_conv_dgrad(dy_split, et_split, B, H, W, Cin, Cout, out=None, accumulate=False):
+def upsample_conv_dgrad(dy_split, et_split, B, H, W, Cin, Cout, out=None, accumulate=False, mode=0):
     """dx [B,H,W,Cin] of the same layer from the fine-grid split planes of dY [B,2H,2W,Cout] and the E^T planes."""
     lib = L.load(); _need_cuda(dy_split, et_split)
     dx = torch.empty(B, H, W, Cin, device=dy_split.device) if out is None else out
     d = L.UpsampleConvDesc(B=B, H=H, W=W, Cin=Cin, Cout=Cout, dy_split=L.ptr(dy_split), lddy=Cout, et_split=L.ptr(et_split),
-                           dx=L.ptr(dx), lddx=_ld(dx), accumulate=int(accumulate))
+                           dx=L.ptr(dx), lddx=_ld(dx), accumulate=int(accumulate), mode=mode)
     ws = workspace(lib.bd_upsample_conv_dgrad_workspace_bytes(C.byref(d)), dy_split.device, "ups_dgrad")
     d.workspace = L.ptr(ws); d.workspace_bytes = ws.numel()
     L.check(lib.bd_upsample_conv_dgrad(C.byref(d), L.stream()), "bd_upsample_conv_dgrad")
     return dx
 
 
-def upsample_conv_wgrad(x_split, dy_split, B, H, W, Cin, Cout, with_db=False):
+def upsample_conv_wgrad(x_split, dy_split, B, H, W, Cin, Cout, with_db=False, mode=0):
     """dw [Cout,3,3,Cin] (and db) of the same layer from x (source grid) and dY (fine grid), both split planes."""
     lib = L.load(); _need_cuda(x_split, dy_split)
     dw = torch.empty(Cout, 3, 3, Cin, device=x_split.device)
     db = torch.empty(Cout, device=x_split.device) if with_db else None
     d = L.UpsampleConvDesc(B=B, H=H, W=W, Cin=Cin, Cout=Cout, x_split=L.ptr(x_split), ldx=Cin, dy_split=L.ptr(dy_split), lddy=Cout,
-                           dw=L.ptr(dw), db=L.ptr(db))
+                           dw=L.ptr(dw), db=L.ptr(db), mode=mode)
     ws = workspace(lib.bd_upsample_conv_wgrad_workspace_bytes(C.byref(d)), x_split.device, "ups_wgrad")
     d.workspace = L.ptr(ws); d.workspace_bytes = ws.numel()
     L.check(lib.bd_upsample_conv_wgrad(C.byref(d), L.stream()), "bd_upsample_conv_wgrad")
     return (dw, db) if with_db else dw
 
 
-def conv3x3_s2_dgrad_ps(dy_split, wT_split, B, Ho, Wo, Cin, Cout, pad=0, out=None, accumulate=False):
+def conv3x3_s2_dgrad_ps(dy_split, wT_split, B, Ho, Wo, Cin, Cout, pad=0, out=None, accumulate=False, mode=0):
     """dx [B,2Ho,2Wo,Cin] of a stride-2 3x3 convolution (pad 0 = F.pad(0,1,0,1) + padding 0; 1 = padding 1) from the split planes
     of dy [B,Ho,Wo,Cout] and the transposed weight planes (split_wT)."""
     lib = L.load(); _need_cuda(dy_split, wT_split)
     dx = torch.empty(B, 2 * Ho, 2 * Wo, Cin, device=dy_split.device) if out is None else out
     d = L.ConvS2DgradDesc(B=B, Ho=Ho, Wo=Wo, Cin=Cin, Cout=Cout, pad=pad, dy_split=L.ptr(dy_split), lddy=Cout, wT_split=L.ptr(wT_split),
-                          dx=L.ptr(dx), lddx=_ld(dx), accumulate=int(accumulate))
+                          dx=L.ptr(dx), lddx=_ld(dx), accumulate=int(accumulate), mode=mode)
     L.check(lib.bd_conv3x3_s2_dgrad_ps(C.byref(d), L.stream()), "bd_conv3x3_s2_dgrad_ps")
     return dx
 
@@ -441,14 +442,14 @@ def unsplit_rows(s):
 
 
 def gemm_sp(a_split, b_split, M, N, K, a_kmajor=False, b_kmajor=False, batch=1, bias=None, residual=None, alpha=1.0, out_scale=1.0,
-            want_f32=True, want_split=False, out=None, accumulate=False, want_colsum=False):
+            want_f32=True, want_split=False, out=None, accumulate=False, want_colsum=False, mode=0):
     """C = out_scale * (alpha * A B^T + bias + residual) on split planes (include/bd_hip.h bd_gemm_sp).  a_split: planes of A [batch, M, K]
     (or [batch, K, M] when a_kmajor); b_split: planes of B [batch, N, K] (or [batch, K, N] when b_kmajor), or un-batched (shared by the
     batch).  Returns (c fp32 or None, c_split or None[, colsum])."""
     lib = L.load(); _need_cuda(a_split, b_split, bias, residual)
     dev = a_split.device
     d = L.GemmSpDesc()
-    d.M, d.N, d.K, d.batch = M, N, K, batch
+    d.M, d.N, d.K, d.batch, d.mode = M, N, K, batch, mode
     ar, ac = (K, M) if a_kmajor else (M, K)
     br, bc = (K, N) if b_kmajor else (N, K)
     d.a = L.ptr(a_split); d.lda = ac; d.a_bs = ar * ac if a_split.numel() * 2 == batch * ar * ac * 4 else 0; d.a_kmajor = int(a_kmajor)
@@ -489,7 +490,7 @@ def sum2x2(du):
     return dx
 
 
-def attn_sp_fwd(qkv_split, B, heads, scale, want_pt=True, C_=None):
+def attn_sp_fwd(qkv_split, B, heads, scale, want_pt=True, C_=None, mode=0):
     """Attention core forward on the planes of the QKV projection's output [B*N, 3C/32, 2, 32] (include/bd_hip.h bd_attn_sp_fwd):
     returns (o_split [B*N, C/32, 2, 32], pt_split [B*heads, N, N/32, 2, 32] or None)."""
     lib = L.load(); _need_cuda(qkv_split)
@@ -499,12 +500,12 @@ def attn_sp_fwd(qkv_split, B, heads, scale, want_pt=True, C_=None):
     o = torch.empty(rows, Cc // 32, 2, 32, dtype=torch.int16, device=qkv_split.device)
     pt = torch.empty(B * heads, N, N // 32, 2, 32, dtype=torch.int16, device=qkv_split.device) if want_pt else None
     d = L.AttnSpDesc(B=B, heads=heads, N=N, dh=Cc // heads, qkv_split=L.ptr(qkv_split), ld=blocks * 32, scale=scale, o_split=L.ptr(o), ldo=Cc,
-                     pt_split=L.ptr(pt))
+                     pt_split=L.ptr(pt), mode=mode)
     L.check(lib.bd_attn_sp_fwd(C.byref(d), L.stream()), "bd_attn_sp_fwd")
     return o, pt
 
 
-def attn_sp_bwd(qkv_split, pt_split, do_split, B, heads, scale):
+def attn_sp_bwd(qkv_split, pt_split, do_split, B, heads, scale, mode=0):
     """Attention core backward: returns (dqkv_split [B*N, 3C/32, 2, 32], dst_split = planes of scale * dS^T)."""
     lib = L.load(); _need_cuda(qkv_split, pt_split, do_split)
     rows, blocks = qkv_split.shape[0], qkv_split.shape[1]
@@ -513,7 +514,7 @@ def attn_sp_bwd(qkv_split, pt_split, do_split, B, heads, scale):
     dqkv = torch.empty_like(qkv_split)
     dst = torch.empty_like(pt_split)
     d = L.AttnSpDesc(B=B, heads=heads, N=N, dh=Cc // heads, qkv_split=L.ptr(qkv_split), ld=3 * Cc, scale=scale, pt_split=L.ptr(pt_split),
-                     do_split=L.ptr(do_split), lddo=Cc, dst_split=L.ptr(dst), dqkv_split=L.ptr(dqkv), lddqkv=3 * Cc)
+                     do_split=L.ptr(do_split), lddo=Cc, dst_split=L.ptr(dst), dqkv_split=L.ptr(dqkv), lddqkv=3 * Cc, mode=mode)
     L.check(lib.bd_attn_sp_bwd(C.byref(d), L.stream()), "bd_attn_sp_bwd")
     return dqkv, dst
 

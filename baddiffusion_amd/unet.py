@@ -45,7 +45,7 @@ class UNet2DOutput:
         self.sample = sample
 
 
-COMPUTE_MODES = {"f32": 0, "bf16x3": 1}   # include/bd_hip.h: bd_compute_mode
+COMPUTE_MODES = {"f32": 0, "bf16x3": 1, "bf16": 2}   # include/bd_hip.h: bd_compute_mode
 
 _SUPPORTED_DOWN = ("DownBlock2D", "AttnDownBlock2D")
 _SUPPORTED_UP = ("UpBlock2D", "AttnUpBlock2D")
@@ -152,7 +152,7 @@ class UNet2DModel(nn.Module):
         c.norm_num_groups = int(norm_num_groups)
         c.attention_head_dim = int(attention_head_dim or 0)
         c.mid_block_scale_factor = float(mid_block_scale_factor)
-        if compute_mode is None:   # matrix-product arithmetic: split-bf16 (default) or bit-exact fp32 (include/bd_hip.h)
+        if compute_mode is None:   # matrix-product arithmetic: split-bf16 (default), single-pass bf16 or bit-exact fp32 (include/bd_hip.h)
             compute_mode = os.environ.get("BD_COMPUTE_MODE", "bf16x3")
         if compute_mode not in COMPUTE_MODES:
             raise ValueError(f"compute_mode must be one of {sorted(COMPUTE_MODES)}, got {compute_mode!r}")
@@ -198,7 +198,9 @@ class UNet2DModel(nn.Module):
             pass
 
     def set_compute_mode(self, mode):
-        """'f32' (exact fp32 MFMA) or 'bf16x3' (split-bf16, ~2^-16 relative per product, 3 MFMAs on the bf16 pipe)."""
+        """'f32' (exact fp32 MFMA), 'bf16x3' (split-bf16, ~2^-16 relative per product, 3 MFMAs on the bf16 pipe) or 'bf16'
+        (single pass: every matrix-product operand rounded once to bf16, one MFMA per product, fp32 accumulation; everything
+        else -- activations, GroupNorm, softmax, loss, optimizer -- stays fp32: the counterpart of the reference's autocast)."""
         L.check(self._lib.bd_unet_set_compute_mode(self._plan, COMPUTE_MODES[mode]), "bd_unet_set_compute_mode")
         if getattr(self, "compute_mode", mode) != mode:
             self._ws_pool = {}        # the workspace bound depends on which kernels the mode selects: pooled buffers may be too small

@@ -217,8 +217,14 @@ int bd_gn_bwd_params(const bd_gn_param_item* items, int n, int B, bd_stream_t st
  *   BD_MODE_F32     v_mfma_f32_32x32x2_f32, exact fp32 products and accumulation (157 TFLOP/s roof)
  *   BD_MODE_BF16X3  every fp32 operand is split on the fly into hi + lo bf16 (x = hi + lo + O(2^-17 x)) and the
  *                   product is hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16 with fp32 accumulation:
- *                   ~2^-16 relative error per product, 3 MFMAs on the 2.5 PFLOP/s pipe                      */
-enum bd_compute_mode { BD_MODE_F32 = 0, BD_MODE_BF16X3 = 1 };
+ *                   ~2^-16 relative error per product, 3 MFMAs on the 2.5 PFLOP/s pipe
+ *   BD_MODE_BF16    single pass: every operand of every matrix product (convolution, GEMM, attention q k^T and P v) is
+ *                   rounded once to bf16 RNE -- the hi plane above -- and the product is ONE v_mfma_f32_32x32x16_bf16
+ *                   with fp32 accumulation (~2^-9 relative error per operand).  Everything else keeps fp32 arithmetic
+ *                   and storage: activations, GroupNorm, SiLU, softmax, loss, clip, Adam, master weights, scheduler
+ *                   steps.  Autocast with fp32 activation storage; bf16 has fp32's exponent range, so training needs
+ *                   no loss scaling.  Same kernels, workspace and split-plane formats as BD_MODE_BF16X3, lo unread.   */
+enum bd_compute_mode { BD_MODE_F32 = 0, BD_MODE_BF16X3 = 1, BD_MODE_BF16 = 2 };
 
 enum bd_operand_kind {
     BD_OPK_DENSE = 0, /* KC: p[row*ld + k]            RC: p[k*ld + row]                          */
@@ -233,7 +239,7 @@ typedef struct {
     const float* p; int64_t ld;
     int64_t bs_outer, bs_inner;   /* batch strides (elements)                                   */
     int C, Hs, Ws, Ho, Wo, stride, pad_t, pad_l, ups;   /* conv geometry (CONV/TCONV/WGT)       */
-    const uint16_t* split;   /* optional, BD_MODE_BF16X3 only: the same buffer already split into bf16 hi/lo by
+    const uint16_t* split;   /* optional, BD_MODE_BF16X3 / BD_MODE_BF16 only: the same buffer already split into bf16 hi/lo by
                                 bd_split_bf16 (blocked layout below; element e of p <-> e of split); used where the
                                 engine has a loader for it (weights of conv fwd / dgrad), ignored otherwise -- p must
                                 always be valid                                                               */
@@ -343,6 +349,8 @@ typedef struct {
                                        [B][S][gn_groups][2] fp64 partial (sum, sum of squares) per sample and 256-pixel tile, S =
                                        bd_conv3x3_ps_gn_splits() > 0; forward calls with exactly one of rowbias / residual, no accumulate.
                                        Hand them to bd_gn_fwd as stats / stats_splits.                                              */
+    int mode;                       /* bd_compute_mode of the products: BD_MODE_BF16X3 (or 0, the zero-initialised default: these
+                                       kernels have no f32 form) = hi*hi + hi*lo + lo*hi, BD_MODE_BF16 = hi*hi; other values BD_ERR_INVALID */
 } bd_conv3x3_ps_desc;
 size_t bd_conv3x3_ps_workspace_bytes(const bd_conv3x3_ps_desc* d);
 int bd_conv3x3_ps_gn_splits(int B, int H, int W, int K, int N, int groups);   /* 0: this call cannot write GroupNorm partials */
@@ -357,6 +365,7 @@ typedef struct {
     const uint16_t* dy_split; int64_t lddy;   /* output grad [B*H*W, lddy] */
     float* dw; float* db;
     void* workspace; size_t workspace_bytes;
+    int mode;                                   /* BD_MODE_BF16X3 (or 0) / BD_MODE_BF16, as bd_conv3x3_ps_desc.mode */
 } bd_conv3x3_ps_wgrad_desc;
 /* Run-time tuning knob for measurement sweeps (bench.py --gpus N sweeps the weight-gradient slot count inside ONE process, because a
  * multi-GPU node is leased once): key "ps_wg3_slots" = K-split slots of conv_ps_wgrad3_kernel (0 restores BD_PS_WG3_SLOTS / the default:
@@ -544,6 +553,7 @@ typedef struct {
     float* dx; int64_t lddx; int accumulate;    /* dgrad out [B*HW, Cin], += when accumulate                       */
     float* dw; float* db;                       /* wgrad out [Cout,3,3,Cin] and (optional) [Cout]                  */
     void* workspace; size_t workspace_bytes;    /* wgrad / dgrad: bd_upsample_conv_{wgrad,dgrad}_workspace_bytes   */
+    int mode;                                   /* BD_MODE_BF16X3 (or 0) / BD_MODE_BF16, as bd_conv3x3_ps_desc.mode */
 } bd_upsample_conv_desc;
 int bd_upsample_weights(const float* w /* [Cout,3,3,Cin] */, int Cin, int Cout, uint16_t* e_split, uint16_t* et_split /* may be null: forward only */,
                         bd_stream_t stream);
@@ -558,6 +568,7 @@ typedef struct {
     const uint16_t* dy_split; int64_t lddy;     /* [B*Ho*Wo, Cout] */
     const uint16_t* wT_split;                   /* transposed weight planes Wt[ci][9][co] (bd_split_wt) */
     float* dx; int64_t lddx; int accumulate;    /* [B*4HoWo, Cin] */
+    int mode;                                   /* BD_MODE_BF16X3 (or 0) / BD_MODE_BF16, as bd_conv3x3_ps_desc.mode */
 } bd_conv3x3_s2_dgrad_desc;
 int bd_conv3x3_s2_dgrad_ps(const bd_conv3x3_s2_dgrad_desc* d, bd_stream_t stream);
 
@@ -583,6 +594,7 @@ typedef struct {
     int accumulate;                              /* c += ...  (needs c)                                            */
     float* a_colsum;                             /* [M] or NULL                                                    */
     void* workspace; size_t workspace_bytes;
+    int mode;                                    /* BD_MODE_BF16X3 (or 0) / BD_MODE_BF16, as bd_conv3x3_ps_desc.mode */
 } bd_gemm_sp_desc;
 size_t bd_gemm_sp_workspace_bytes(const bd_gemm_sp_desc* d);
 int bd_gemm_sp(const bd_gemm_sp_desc* d, bd_stream_t stream);
@@ -603,6 +615,8 @@ typedef struct {
     const uint16_t* do_split; int64_t lddo;    /* backward in */
     uint16_t* dst_split;                       /* backward scratch [B*heads, N, N] planes */
     uint16_t* dqkv_split; int64_t lddqkv;      /* backward out */
+    int mode;                                  /* BD_MODE_BF16X3 (or 0) / BD_MODE_BF16, as bd_conv3x3_ps_desc.mode; BD_MODE_BF16 rounds
+                                                  P (and dS) to bf16 once, the hi plane the three-product form also uses */
 } bd_attn_sp_desc;
 int bd_attn_sp_supported(int N, int dh);
 int bd_attn_sp_fwd(const bd_attn_sp_desc* d, bd_stream_t stream);

@@ -57,7 +57,7 @@ def main():
     ap.add_argument("--eval-at", default="0,250,500,1000,2000,3000")
     ap.add_argument("--eval-n", type=int, default=64)
     ap.add_argument("--sample-steps", type=int, default=1000)
-    ap.add_argument("--mode", default="bf16x3", choices=["f32", "bf16x3"])
+    ap.add_argument("--mode", default="bf16x3", choices=["f32", "bf16x3", "bf16"])
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "r05_backdoor_run.json"))
     args = ap.parse_args()
 

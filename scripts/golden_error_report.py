@@ -1,6 +1,6 @@
 """How far is each compute mode from the reference's golden vectors at BASELINE configs[1]'s real size?  (G10: tests/golden/full_size.npz, vectors the imported
 reference produced for the DDPM-CIFAR10-32 topology at batch 128.)  Prints one JSON object: relative L2 error of the prediction rows, relative loss error,
-relative clip-norm error per mode.  usage (GPU): python scripts/golden_error_report.py > gpurun_out/r06_golden_error.json"""
+relative clip-norm error per mode.  usage (GPU): python scripts/golden_error_report.py [mode ...] > golden_error.json"""
 import json
 import os
 import sys
@@ -21,7 +21,7 @@ tag = "cifar128"
 cfg = U.CIFAR10_32
 _, a, ac = sched_ref.make_tables()
 out = {}
-for mode in ("f32", "bf16x3"):
+for mode in sys.argv[1:] or ("f32", "bf16x3", "bf16"):   # modes to report (default: all three)
     m = unet.unet_from_config(cfg).cuda()
     m.load_state_dict(U.gen_params(cfg, 0))
     m.set_compute_mode(mode)
