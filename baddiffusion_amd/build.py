@@ -20,10 +20,10 @@ SOURCES = [  # (file, extra flags)
     ("elementwise.hip", ["-ffp-contract=off"]),
     ("groupnorm.hip", []),
     ("igemm.hip", []),
-    ("conv_ps.hip", ["-DBD_PS_ABLATION"] if os.environ.get("BD_BUILD_ABLATION") == "1" else []),
+    ("conv_ps.hip", []),
     ("conv_ph.hip", []),
     ("gemm_sp.hip", []),
-    ("attn_sp.hip", ["-DBD_AS_ABLATION"] if os.environ.get("BD_BUILD_ABLATION") == "1" else []),
+    ("attn_sp.hip", []),
     ("metrics.hip", ["-ffp-contract=off"]),
     ("inception.hip", ["-ffp-contract=off"]),
     ("conv.cpp", ["-x", "hip"]),

@@ -83,27 +83,16 @@ __device__ __forceinline__ unsigned as_xor1(unsigned w) {   // the value of lane
     return (unsigned)__builtin_amdgcn_mov_dpp((int)w, 0xB1, 0xF, 0xF, true);
 }
 
-#ifdef BD_AS_ABLATION
-__device__ int g_as_ablate_dummy;
-#define AS_ABL(L, bit) ((L).ablate & (bit))
-#define AS_STAMP(i) do { if (p.dbg && threadIdx.x == 0) p.dbg[blockIdx.x * 32 + (i)] = __builtin_readcyclecounter(); } while (0)
-#else
-#define AS_STAMP(i) do {} while (0)
-#define AS_ABL(L, bit) false
-#endif
 struct AsLane {
     int lane, wave, li, h;
-    unsigned long long* dbg;
-    int ablate;               // -DBD_AS_ABLATION builds only (BD_AS_ABLATE): 1 = no DMA, 2 = no global stores
     unsigned smem;            // LDS byte address of the workgroup's buffer
     unsigned kc[2][2];        // K-contiguous fragment offset [k16 step][plane] of row li of a 32-row tile (tile = immediate)
     unsigned kq[2][2];        // the same inside this wave's own-row region of a phase-S slot
     unsigned km[2][2];        // K-major fragment offset [tile parity][plane] (natural contraction order)
     unsigned kmp[2][2];       // ... in the permuted order of a phase-S accumulator: k-slots j of lane half h = rows 4h + (j&3) + 8(j>>2) (+16 per step)
 };
-__device__ __forceinline__ AsLane as_lane(const char* smem, int ablate = 0, unsigned long long* dbg = nullptr) {
+__device__ __forceinline__ AsLane as_lane(const char* smem) {
     AsLane L;
-    L.ablate = ablate; L.dbg = dbg;
     const int tid = threadIdx.x;
     L.lane = tid & 63;
     L.wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -149,7 +138,6 @@ __device__ __forceinline__ void as_phase_s(const char* a_base, long long lda, co
     }
     const char* a_cur = a_base; const char* b_cur = own_base;
     auto issue = [&](int slot) {
-        if (AS_ABL(L, 1)) return;
         char* st = smem + slot * AS_SLOT;
 #pragma unroll
         for (int j = 0; j < 8; ++j) as_dma16(a_cur + aoff[j], st + (L.wave + 4 * j) * 1024);
@@ -261,7 +249,6 @@ __device__ __forceinline__ AsStream as_o_open(const char* b_base, long long ldb,
 template <int U>
 __device__ __forceinline__ void as_o_issue(const AsStream& s, char* smem, const AsLane& L) {
     constexpr int kc = U & 7, half = U >> 3;
-    if (AS_ABL(L, 1)) return;
     const char* ub = s.base + (long long)kc * 32 * s.ldb + half * 512;   // uniform
 #pragma unroll
     for (int j = 0; j < 4; ++j) as_dma16(ub + s.off[j], smem + kc * AS_UNIT + (L.wave + 4 * j) * 1024);
@@ -292,15 +279,6 @@ __device__ __forceinline__ void as_o_run(const AsStream& s, char* smem, const As
     auto reads = [&](unsigned ub, auto S, AsOFrag& f) {
         constexpr int sp = decltype(S)::value;
         constexpr int second = PERM ? 8 * 512 : 4 * 512;
-#ifdef BD_AS_ABLATION
-        if (AS_ABL(L, 4)) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int pl = 0; pl < 2; ++pl) f.v0[t][pl] = f.v1[t][pl] = as_short4{0x3f80, 0x3f80, (short)sp, 0x3f80};
-            return;
-        }
-#endif
         as_for<0, 4>([&](auto T) {
             constexpr int t = decltype(T)::value;
 #pragma unroll
@@ -322,9 +300,6 @@ __device__ __forceinline__ void as_o_run(const AsStream& s, char* smem, const As
     wait(f0);
     as_for<0, 16>([&](auto UU) {
         constexpr int u = decltype(UU)::value, kc = u & 7, half = u >> 3, nkc = (u + 1) & 7;
-#ifdef BD_AS_ABLATION
-        if (L.dbg && threadIdx.x == 0) L.dbg[blockIdx.x * 32 + 8 + u] = __builtin_readcyclecounter();
-#endif
         const unsigned ub = L.smem + kc * AS_UNIT, nub = L.smem + nkc * AS_UNIT;
         auto mfmas = [&](auto S, const AsOFrag& f) {
             constexpr int sp = decltype(S)::value;
@@ -372,19 +347,15 @@ __device__ __forceinline__ void as_o_run(const AsStream& s, char* smem, const As
 // a 32 x 32 accumulator tile (rows (r&3) + 8(r>>2) + 4h, column li of a 32-column block) as split planes: lane pairs trade halves so that
 // every lane stores ONE dword per row -- even lanes the hi pair (li, li+1), odd lanes the lo pair (li-1, li).  `ubase` (uniform) = first
 // row of the tile + 128 * column block; `lane_off` = 4h * ld + the lane's dword inside the 128-byte line.
-struct AsPair { unsigned off, sel; bool odd; bool nostore; };
+struct AsPair { unsigned off, sel; bool odd; };
 __device__ __forceinline__ AsPair as_pair(const AsLane& L, long long ld) {
     AsPair q;
     q.odd = L.li & 1;
-    q.nostore = AS_ABL(L, 2);
     q.off = (unsigned)(4 * L.h * (int)ld + (q.odd ? 64 + (L.li - 1) * 2 : L.li * 2));
     q.sel = q.odd ? 0x03020706u : 0x05040100u;   // v_perm_b32(neighbour, own): odd (nb >> 16) | (own & 0xFFFF0000), even (own & 0xFFFF) | (nb << 16)
     return q;
 }
 __device__ __forceinline__ void as_store_word(char* urow, const AsPair& q, unsigned w) {
-#ifdef BD_AS_ABLATION
-    if (q.nostore) { asm volatile("" ::"v"(__builtin_amdgcn_perm(as_xor1(w), w, q.sel))); return; }
-#endif
     *reinterpret_cast<unsigned*>(urow + q.off) = __builtin_amdgcn_perm(as_xor1(w), w, q.sel);
 }
 __device__ __forceinline__ void as_store_tile(char* ubase, long long ld, const AsPair& q, const as_floatx16& v) {
@@ -421,8 +392,6 @@ struct AsParams {
     char* dqkv; long long lddqkv;           // backward: dq | dk | dv planes (layout of qkv)
     int C, dh, heads;
     float scale;
-    int ablate;
-    unsigned long long* dbg;   // -DBD_AS_ABLATION builds: [workgroup][8] s_memtime stamps of wave 0
 };
 
 // workgroup -> (sample * heads + head, 128-row block); the two blocks of a sample are neighbours in one XCD's run (shared K / V in L2)
@@ -435,7 +404,7 @@ __device__ __forceinline__ void as_coord(int& bh, int& blk) {
 template <bool WRITE_P, bool SP>
 __global__ __launch_bounds__(AS_NT, 1) void attn_sp_fwd_kernel(AsParams p) {
     __shared__ __attribute__((aligned(128))) char smem[AS_LDS];
-    const AsLane L = as_lane(smem, p.ablate, p.dbg);
+    const AsLane L = as_lane(smem);
     int bh, qb;
     as_coord(bh, qb);
     const int b = bh / p.heads, hd = bh - b * p.heads;
@@ -448,9 +417,7 @@ __global__ __launch_bounds__(AS_NT, 1) void attn_sp_fwd_kernel(AsParams p) {
     for (int kt = 0; kt < 8; ++kt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[kt][r] = 0.f;
-    AS_STAMP(0);
     as_phase_s<SP>(base + (long long)p.C * 4, p.ld, base + own0 * p.ld, p.ld, p.dh >> 5, smem, L, acc, [](auto) {});
-    AS_STAMP(1);
     __builtin_amdgcn_s_barrier();
     const AsStream vs = as_o_open(base + (long long)p.C * 8, p.ld, L);
     as_o_prologue(vs, smem, L);
@@ -479,7 +446,6 @@ __global__ __launch_bounds__(AS_NT, 1) void attn_sp_fwd_kernel(AsParams p) {
     for (int dt = 0; dt < 8; ++dt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) oacc[dt][r] = 0.f;
-    AS_STAMP(2);
     const AsPair po = as_pair(L, p.ldo), pp = as_pair(L, AS_N * 4);
     char* orow = p.o + ((long long)b * AS_N + own0) * p.ldo + colq;                                   // uniform
     char* ptb = WRITE_P ? p.pt + (long long)bh * AS_N * AS_N * 4 + (qb * 4 + L.wave) * 128 : nullptr;  // uniform
@@ -495,16 +461,14 @@ __global__ __launch_bounds__(AS_NT, 1) void attn_sp_fwd_kernel(AsParams p) {
             as_store_tile(orow + i * 128, p.ldo, po, oacc[i]);
         }
     });
-    AS_STAMP(3);
 #pragma unroll
     for (int dt = 4; dt < 8; ++dt) as_store_tile(orow + dt * 128, p.ldo, po, oacc[dt]);
-    AS_STAMP(4);
 }
 
 template <bool SP>
 __global__ __launch_bounds__(AS_NT, 1) void attn_sp_bwd_a_kernel(AsParams p) {
     __shared__ __attribute__((aligned(128))) char smem[AS_LDS];
-    const AsLane L = as_lane(smem, p.ablate, p.dbg);
+    const AsLane L = as_lane(smem);
     int bh, qb;
     as_coord(bh, qb);
     const int b = bh / p.heads, hd = bh - b * p.heads;
@@ -581,7 +545,7 @@ __global__ __launch_bounds__(AS_NT, 1) void attn_sp_bwd_a_kernel(AsParams p) {
 template <bool SP>
 __global__ __launch_bounds__(AS_NT, 1) void attn_sp_bwd_b_kernel(AsParams p) {
     __shared__ __attribute__((aligned(128))) char smem[AS_LDS];
-    const AsLane L = as_lane(smem, p.ablate, p.dbg);
+    const AsLane L = as_lane(smem);
     int bh, kb;
     as_coord(bh, kb);
     const int b = bh / p.heads, hd = bh - b * p.heads;
@@ -617,20 +581,15 @@ __global__ __launch_bounds__(AS_NT, 1) void attn_sp_bwd_b_kernel(AsParams p) {
         for (int dt = 4; dt < 8; ++dt) as_store_tile(out + dt * 128, p.lddqkv, pq, oacc[dt]);
     };
     // dV = P^T dO
-    AS_STAMP(0);
     load_slab(p.pt, ah, al);
     const AsStream ds = as_o_open(p.dO + (long long)b * AS_N * p.lddo + colq, p.lddo, L);
     as_o_prologue(ds, smem, L);
-    AS_STAMP(1);
     run(ds, orow + (long long)p.C * 8);
-    AS_STAMP(2);
     // dK = dS^T Q  (dS already carries the softmax scale)
     load_slab(p.dst, ah, al);
     const AsStream qs = as_o_open(p.qkv + (long long)b * AS_N * p.ld + colq, p.ld, L);
     as_o_prologue(qs, smem, L);
-    AS_STAMP(3);
     run(qs, orow + (long long)p.C * 4);
-    AS_STAMP(4);
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
@@ -639,32 +598,6 @@ bool attn_sp_supported(int N, int dh) {
     return !off && N == AS_N && dh == 256;
 }
 
-#ifdef BD_AS_ABLATION
-static unsigned long long* as_dbg_buf() {
-    static unsigned long long* d = nullptr;
-    if (!d && getenv("BD_AS_STAMPS")) { (void)hipMalloc(&d, 4096 * 32 * 8); (void)hipMemset(d, 0, 4096 * 32 * 8); }
-    return d;
-}
-static void as_dbg_print(const char* who, int wgs, hipStream_t st) {
-    unsigned long long* d = as_dbg_buf();
-    if (!d) return;
-    (void)hipStreamSynchronize(st);
-    static unsigned long long h[4096 * 32];
-    (void)hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
-    double seg[5] = {0, 0, 0, 0, 0};
-    for (int w = 0; w < wgs; ++w)
-        for (int i = 0; i < 4; ++i) seg[i] += (double)(h[w * 32 + i + 1] - h[w * 32 + i]);
-    fprintf(stderr, "[stamps] %s: segments (cycles, mean over %d workgroups):", who, wgs);
-    for (int i = 0; i < 4; ++i) fprintf(stderr, " %.0f", seg[i] / wgs);
-    fprintf(stderr, "\n[stamps]   last O run, cycles per unit:");
-    for (int u = 0; u < 15; ++u) {
-        double t = 0;
-        for (int w = 0; w < wgs; ++w) t += (double)(h[w * 32 + 8 + u + 1] - h[w * 32 + 8 + u]);
-        fprintf(stderr, " %.0f", t / wgs);
-    }
-    fprintf(stderr, "\n");
-}
-#endif
 static int attn_sp_common(const bd_attn_sp_desc& d, const char* who, AsParams& p) {
     BD_CHECK(d.B > 0 && d.heads > 0 && attn_sp_supported(d.N, d.dh), BD_ERR_UNSUPPORTED, "%s: needs N == 256 and head dim 256 (got N %d, dh %d)", who,
              d.N, d.dh);
@@ -675,9 +608,6 @@ static int attn_sp_common(const bd_attn_sp_desc& d, const char* who, AsParams& p
     p = {};
     p.qkv = reinterpret_cast<const char*>(d.qkv_split); p.ld = d.ld * 4;
     p.C = C; p.dh = d.dh; p.heads = d.heads; p.scale = d.scale;
-#ifdef BD_AS_ABLATION
-    p.ablate = getenv("BD_AS_ABLATE") ? atoi(getenv("BD_AS_ABLATE")) : 0;
-#endif
     return BD_OK;
 }
 
@@ -688,9 +618,6 @@ int attn_sp_fwd(const bd_attn_sp_desc& d, hipStream_t st) {
     BD_CHECK(((uintptr_t)d.pt_split & 127) == 0, BD_ERR_INVALID, "bd_attn_sp_fwd: P^T planes must be 128-byte aligned");
     p.o = reinterpret_cast<char*>(d.o_split); p.ldo = d.ldo * 4; p.pt = reinterpret_cast<char*>(d.pt_split);
     const dim3 grid((unsigned)(d.B * d.heads * 2));
-#ifdef BD_AS_ABLATION
-    p.dbg = as_dbg_buf();
-#endif
     // bench.py roofline: S = Q K^T and O = P V (4 B N^2 dh flop per head); bytes = q, k, v in, o (+ P^T for training) out
     const double bh = (double)d.B * d.heads, nn = (double)d.N * d.N, nd = (double)d.N * d.dh;
     const bool sp = d.mode == BD_MODE_BF16;
@@ -701,9 +628,6 @@ int attn_sp_fwd(const bd_attn_sp_desc& d, hipStream_t st) {
     else hipLaunchKernelGGL((attn_sp_fwd_kernel<false, false>), grid, dim3(AS_NT), 0, st, p);
     BD_LAUNCH_CHECK("attn_sp_fwd");
     prof_end(rec, st);
-#ifdef BD_AS_ABLATION
-    as_dbg_print("fwd  S | softmax | O run | tail stores", (int)grid.x, st);
-#endif
     return BD_OK;
 }
 
@@ -727,17 +651,11 @@ int attn_sp_bwd(const bd_attn_sp_desc& d, hipStream_t st) {
     if (sp) hipLaunchKernelGGL(attn_sp_bwd_a_kernel<true>, grid, dim3(AS_NT), 0, st, p);
     else hipLaunchKernelGGL(attn_sp_bwd_a_kernel<false>, grid, dim3(AS_NT), 0, st, p);
     prof_end(rec, st);
-#ifdef BD_AS_ABLATION
-    p.dbg = as_dbg_buf();
-#endif
     rec = prof_on() ? prof_begin(sp ? "attn_sp_bwd_b_bf16" : "attn_sp_bwd_b", 4.0 * bh * nn * d.dh, 4.0 * bh * (4.0 * nd + 2.0 * nn), st) : -1;
     if (sp) hipLaunchKernelGGL(attn_sp_bwd_b_kernel<true>, grid, dim3(AS_NT), 0, st, p);
     else hipLaunchKernelGGL(attn_sp_bwd_b_kernel<false>, grid, dim3(AS_NT), 0, st, p);
     prof_end(rec, st);
     BD_LAUNCH_CHECK("attn_sp_bwd");
-#ifdef BD_AS_ABLATION
-    as_dbg_print("bwdB slab1 | run1 | slab2+prologue | run2", (int)grid.x, st);
-#endif
     return BD_OK;
 }
 

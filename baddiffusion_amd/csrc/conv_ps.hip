@@ -51,7 +51,6 @@ struct PsParams {
     float out_scale;
     int accumulate;
     unsigned short* y_split; long long ldys;   // optional second output: y in split planes (same row count, ld)
-    int ablate;            // -DBD_PS_ABLATION builds only (BD_PS_ABLATE): 1 = no steady-state DMA, 2 = no MFMA, 4 = no fragment reads
     int lvw;               // conv_ps3_kernel: log2 of the VIRTUAL image width min(W, 32), see ps_v2r
     double* gn_part;       // conv_ps3_kernel, optional: [B][H*W/256][gn_G][2] partial (sum, sum of squares) of y per pixel tile and group
     int gn_G, gn_lcpg;     //   groups of the GroupNorm that reads y next; log2(channels per group), 2 .. 5
@@ -243,12 +242,7 @@ __global__ __launch_bounds__(PS_NT, 2) void conv_ps_kernel(PsParams p) {
     // cursor of the NEXT chunk to issue, all wave-uniform: tap = 3*kh + kw, byte offsets of the tap / channel block
     int q_kh = 0, q_kw = 0, q_bit = 1;
     int q_aoff = -p.sign * (p.W + 1) * pix_bytes, q_woff = 0;   // tap (0,0) of block 0
-    int issued = 0;
     auto issue = [&](char* stage) {
-#ifdef BD_PS_ABLATION
-        if ((p.ablate & 1) && issued >= 2) return;
-#endif
-        ++issued;
 #pragma unroll
         for (int j = 0; j < 4; ++j) ps_dma16((vm[j] & q_bit) ? ap[j] + q_aoff : reinterpret_cast<const char*>(kPsZero), stage + (wave + 8 * j) * 1024);
 #pragma unroll
@@ -288,13 +282,6 @@ __global__ __launch_bounds__(PS_NT, 2) void conv_ps_kernel(PsParams p) {
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             bf16x8 ah[2], al[2], bh[2], bl[2];
-#ifdef BD_PS_ABLATION
-            if (p.ablate & 4) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i) { ah[i] = al[i] = bh[i] = bl[i] = __builtin_bit_cast(bf16x8, make_float4(1.f, 1.f, (float)s, 1.f)); }
-            } else
-#endif
-            {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 ah[i] = *reinterpret_cast<const bf16x8*>(stage + abase + i * 4096 + foff[s][0]);
@@ -302,14 +289,6 @@ __global__ __launch_bounds__(PS_NT, 2) void conv_ps_kernel(PsParams p) {
                 bh[i] = *reinterpret_cast<const bf16x8*>(stage + bbase + i * 4096 + foff[s][0]);
                 if constexpr (!SP) bl[i] = *reinterpret_cast<const bf16x8*>(stage + bbase + i * 4096 + foff[s][1]);
             }
-            }
-#ifdef BD_PS_ABLATION
-            if (p.ablate & 2) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i) asm volatile("" ::"v"(ah[i]), "v"(al[i]), "v"(bh[i]), "v"(bl[i]));
-                continue;
-            }
-#endif
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -749,7 +728,6 @@ struct PsWgParams {
     int P;                             // pixels = K
     int tiles_m, tiles_n, ksplit, cps; // chunks (of 32 pixels) per split
     int want_db;
-    int ablate;                        // -DBD_PS_ABLATION builds only, as in PsParams
     int ntaps;                         // taps per output row: 9, or 16 in the PHASE form (conv_ph.hip: upsample convolution)
     int lh, lvw;                       // conv_ps_wgrad3_kernel: log2(H), log2 of the virtual image width min(W, 32) (ps_v2r)
 };
@@ -780,15 +758,17 @@ __device__ __forceinline__ bf16x8 ps_tr_join(ps_short4 v0, ps_short4 v1) {
     return __builtin_bit_cast(bf16x8, v);
 }
 
-// NW = 8: waves 4 x 2, 32 x 64 each.  NW = 4: waves 2 x 2, 64 x 64 each (a third fewer LDS fragment reads per MFMA, twice
-// the MFMAs between barriers, half the waves per SIMD).
+// STAGES = 2 and NW = 8 only: two LDS stages, the chunk c+1 is fetched while chunk c computes; waves 4 x 2, 32 x 64 each.  (NW = 4 --
+// waves 2 x 2 of 64 x 64, a third fewer LDS fragment reads per MFMA -- measured within +-2 % of NW = 8 on every layer; one form is kept.)
+// Both stay template parameters: the kernel's name, which profiles match on.
 // PH = true: the PHASE form for the upsample convolution (conv_ph.hip).  H x W is the SOURCE grid, X lives on it, dY on the 2H x 2W
 // grid; the 16 "taps" e = (oy+1)*4 + (ox+1) are the entries of E: entry (oy, ox) belongs to pixel class (p, q) of the fine grid and
 // to the source-grid shift (dy, dx) with oy -> (p, dy): -1 -> (1, +1), 0 -> (0, 0), 1 -> (1, 0), 2 -> (0, -1):
 //     dE[e][co][ci] = sum_{source pixels (a, b)} dY[2a+p, 2b+q][co] * X[a+dy, b+dx][ci].
 // The bias gradient (sum of ALL dY) rides in the four (dy, dx) = (0, 0) entries, one bias row per class and K split.
 template <int STAGES, int NW, bool SP, bool PH = false>
-__global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 2) void conv_ps_wgrad_kernel(PsWgParams p) {
+__global__ __launch_bounds__(NW * 64, 2) void conv_ps_wgrad_kernel(PsWgParams p) {
+    static_assert(STAGES == 2 && NW == 8, "conv_ps_wgrad_kernel: one form (two stages, eight waves)");
     constexpr int TMW = 8 / NW;        // 32-row co tiles per wave
     constexpr int NDMA = 16 / NW;      // pixel pairs per wave, operand and chunk
     __shared__ __attribute__((aligned(128))) char smem[STAGES * WG_STAGE_BYTES];
@@ -839,9 +819,6 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 2) void conv_ps_wgrad_kernel
     }
     const long long a_adv = 32 * p.lddy * 4, b_adv = 32 * p.ldx * 4;
     int q_pix = c_begin * 32;   // first pixel of the next chunk to issue
-#ifdef BD_PS_ABLATION
-    int issued = 0;
-#endif
     auto issue_j = [&](char* stage, int j) {
         const int pp = q_pix + kpix[j];
         const int x = pp & (p.W - 1), y = (pp >> p.lw) & (p.H - 1);
@@ -854,17 +831,10 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 2) void conv_ps_wgrad_kernel
             ps_dma16(in ? asrc[j] : reinterpret_cast<const char*>(kPsZero), stage + (wave + NW * j) * 1024);
             asrc[j] += a_adv;
         }
-#ifdef BD_PS_ABLATION
-        if (!(p.ablate & 8) || ((pp >> 5) % 3) == 0)     // 8: the X operand fetched for one chunk in three (timing model of vertical-tap sharing)
-#endif
         ps_dma16(ok ? bsrc[j] : reinterpret_cast<const char*>(kPsZero), stage + WG_OP_BYTES + (wave + NW * j) * 1024);
         bsrc[j] += b_adv;
     };
     auto issue = [&](char* stage) {
-#ifdef BD_PS_ABLATION
-        if ((p.ablate & 1) && issued >= 2) return;
-        ++issued;
-#endif
 #pragma unroll
         for (int j = 0; j < NDMA; ++j) issue_j(stage, j);
         q_pix += 32;
@@ -905,19 +875,6 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 2) void conv_ps_wgrad_kernel
     struct Frag { ps_short4 a0[TMW][2], a1[TMW][2], b0[2][2], b1[2][2]; };
     auto reads = [&](auto S, unsigned sbase, Frag& f) {
         constexpr int KOFF = decltype(S)::value * 16 * 512;
-#ifdef BD_PS_ABLATION
-        if (p.ablate & 4) {
-#pragma unroll
-            for (int i = 0; i < TMW; ++i)
-#pragma unroll
-                for (int pl = 0; pl < 2; ++pl) f.a0[i][pl] = f.a1[i][pl] = ps_short4{0x3f80, 0x3f80, 0x3f80, 0x3f80};
-#pragma unroll
-            for (int q = 0; q < 2; ++q)
-#pragma unroll
-                for (int pl = 0; pl < 2; ++pl) f.b0[q][pl] = f.b1[q][pl] = ps_short4{0x3f80, 0x3f80, 0x3f80, 0x3f80};
-            return;
-        }
-#endif
 #pragma unroll
         for (int i = 0; i < TMW; ++i)
 #pragma unroll
@@ -937,15 +894,9 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 2) void conv_ps_wgrad_kernel
     };
     // all LDS reads of this wave have returned; the fragment registers pass through the asm so no MFMA can move above it
     auto wait = [&](Frag& f) {
-        if constexpr (TMW == 1)
-            asm volatile("s_waitcnt lgkmcnt(0)"
-                         : "+v"(f.a0[0][0]), "+v"(f.a1[0][0]), "+v"(f.a0[0][1]), "+v"(f.a1[0][1]), "+v"(f.b0[0][0]), "+v"(f.b1[0][0]),
-                           "+v"(f.b0[0][1]), "+v"(f.b1[0][1]), "+v"(f.b0[1][0]), "+v"(f.b1[1][0]), "+v"(f.b0[1][1]), "+v"(f.b1[1][1]));
-        else
-            asm volatile("s_waitcnt lgkmcnt(0)"
-                         : "+v"(f.a0[0][0]), "+v"(f.a1[0][0]), "+v"(f.a0[0][1]), "+v"(f.a1[0][1]), "+v"(f.a0[TMW - 1][0]),
-                           "+v"(f.a1[TMW - 1][0]), "+v"(f.a0[TMW - 1][1]), "+v"(f.a1[TMW - 1][1]), "+v"(f.b0[0][0]), "+v"(f.b1[0][0]),
-                           "+v"(f.b0[0][1]), "+v"(f.b1[0][1]), "+v"(f.b0[1][0]), "+v"(f.b1[1][0]), "+v"(f.b0[1][1]), "+v"(f.b1[1][1]));
+        asm volatile("s_waitcnt lgkmcnt(0)"
+                     : "+v"(f.a0[0][0]), "+v"(f.a1[0][0]), "+v"(f.a0[0][1]), "+v"(f.a1[0][1]), "+v"(f.b0[0][0]), "+v"(f.b1[0][0]),
+                       "+v"(f.b0[0][1]), "+v"(f.b1[0][1]), "+v"(f.b0[1][0]), "+v"(f.b1[1][0]), "+v"(f.b0[1][1]), "+v"(f.b1[1][1]));
     };
     auto mfmas = [&](const Frag& f) {
         bf16x8 ah[TMW], al[TMW], bh[2], bl[2];
@@ -953,15 +904,6 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 2) void conv_ps_wgrad_kernel
         for (int i = 0; i < TMW; ++i) { ah[i] = ps_tr_join(f.a0[i][0], f.a1[i][0]); al[i] = ps_tr_join(f.a0[i][1], f.a1[i][1]); }
 #pragma unroll
         for (int q = 0; q < 2; ++q) { bh[q] = ps_tr_join(f.b0[q][0], f.b1[q][0]); bl[q] = ps_tr_join(f.b0[q][1], f.b1[q][1]); }
-#ifdef BD_PS_ABLATION
-        if (p.ablate & 2) {
-#pragma unroll
-            for (int i = 0; i < TMW; ++i) asm volatile("" ::"v"(ah[i]), "v"(al[i]));
-#pragma unroll
-            for (int q = 0; q < 2; ++q) asm volatile("" ::"v"(bh[q]), "v"(bl[q]));
-            return;
-        }
-#endif
 #pragma unroll
         for (int i = 0; i < TMW; ++i)
 #pragma unroll
@@ -988,10 +930,6 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 2) void conv_ps_wgrad_kernel
         const unsigned sbase = smem_addr + (unsigned)(stage - smem);
         Frag f0, f1;
         reads(std::integral_constant<int, 0>{}, sbase, f0);
-#ifdef BD_PS_ABLATION
-        if ((p.ablate & 1) && issued >= 2) next = nullptr;
-        if (next) ++issued;
-#endif
         if (next) issue_j(next, 0);
         wait(f0);
         reads(std::integral_constant<int, 1>{}, sbase, f1);
@@ -1008,27 +946,11 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 2) void conv_ps_wgrad_kernel
     };
 
     const int n = c_end - c_begin;
-    if constexpr (STAGES == 3) {
-        // ring of three: chunk c+2 is issued behind the barrier that frees chunk c-1's stage
-        if (n > 0) issue(smem);
-        if (n > 1) issue(smem + WG_STAGE_BYTES);
-        for (int c = 0; c < n; ++c) {
-            if (c + 1 < n) {
-                if constexpr (NW == 8) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
-            } else {
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            }
-            __builtin_amdgcn_s_barrier();
-            chunk(smem + (c % 3) * WG_STAGE_BYTES, c + 2 < n ? smem + ((c + 2) % 3) * WG_STAGE_BYTES : nullptr);
-        }
-    } else {
-        if (n > 0) issue(smem);
-        for (int c = 0; c < n; ++c) {
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            chunk(smem + (c & 1) * WG_STAGE_BYTES, c + 1 < n ? smem + ((c + 1) & 1) * WG_STAGE_BYTES : nullptr);
-        }
+    if (n > 0) issue(smem);
+    for (int c = 0; c < n; ++c) {
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        chunk(smem + (c & 1) * WG_STAGE_BYTES, c + 1 < n ? smem + ((c + 1) & 1) * WG_STAGE_BYTES : nullptr);
     }
 
     // ---- epilogue: lane holds column n = li of rows (r&3) + 8*(r>>2) + 4*h
@@ -1070,13 +992,6 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 2) void conv_ps_wgrad_kernel
 // LDS: two dY stages (2 x 16 KB) + the X ring (64 KB) = 96 KB, one workgroup per CU.
 constexpr int WG3_RING_UNITS = 8, WG3_UNIT_BYTES = 16 * 512;
 constexpr int WG3_LDS_BYTES = 2 * WG_OP_BYTES + WG3_RING_UNITS * WG3_UNIT_BYTES;
-// Compile-time ablation of conv_ps_wgrad3_kernel (timing experiments, scripts/abl_wg3.sh; results are wrong by design): 1 no steady-state DMA,
-// 2 no MFMA, 4 no X fragment reads, 16 no barrier, 32 no epilogue stores, 64 no main loop.  Compile-time because the run-time form of these
-// switches (-DBD_PS_ABLATION, p.ablate) made this kernel 5x slower by itself; DESIGN.md section 3 has the decomposition they gave.
-#ifndef BD_WG3_ABL
-#define BD_WG3_ABL 0
-#endif
-constexpr int WG3_ABL = BD_WG3_ABL;
 
 template <bool SP>
 __global__ __launch_bounds__(512, 2) void conv_ps_wgrad3_kernel(PsWgParams p) {
@@ -1103,7 +1018,6 @@ __global__ __launch_bounds__(512, 2) void conv_ps_wgrad3_kernel(PsWgParams p) {
     const int c_begin = zz * p.cps;
     int c_end = c_begin + p.cps;
     if (c_end > nchunks) c_end = nchunks;
-    if constexpr ((WG3_ABL & 64) != 0) c_end = c_begin;
 
     // ---- DMA: wave w moves pixel pairs w and w + 8 of a 32-pixel chunk; lane: pixel k = 2*pair + lane/32, 16-byte slot lane%32
     const int ps = lane & 31;
@@ -1175,11 +1089,6 @@ __global__ __launch_bounds__(512, 2) void conv_ps_wgrad3_kernel(PsWgParams p) {
     // one 16-pixel step of one tap: X fragments (one 32-channel tile x hi / lo x two pixel halves)
     struct BFrag { ps_short4 b0[2], b1[2]; };
     auto readB = [&](BFrag& f, unsigned xbase) {
-        if constexpr ((WG3_ABL & 4) != 0) {
-#pragma unroll
-            for (int pl = 0; pl < 2; ++pl) f.b0[pl] = f.b1[pl] = ps_short4{0x3f80, 0x3f80, 0x3f80, 0x3f80};
-            return;
-        }
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl) {
             if (SP && pl == 1) continue;   // single pass: X's lo plane is never read
@@ -1242,7 +1151,6 @@ __global__ __launch_bounds__(512, 2) void conv_ps_wgrad3_kernel(PsWgParams p) {
             __builtin_amdgcn_sched_barrier(0);
             const bf16x8 ah[2] = {ps_tr_join(fa[S].a0[0][0], fa[S].a1[0][0]), ps_tr_join(fa[S].a0[1][0], fa[S].a1[1][0])};
             const bf16x8 al[2] = {ps_tr_join(fa[S].a0[0][1], fa[S].a1[0][1]), ps_tr_join(fa[S].a0[1][1], fa[S].a1[1][1])};
-            if constexpr ((WG3_ABL & 2) != 0) { asm volatile("" ::"v"(ah[0]), "v"(al[0]), "v"(ah[1]), "v"(al[1]), "v"(fb[i & 1].b0[0]), "v"(fb[i & 1].b1[1])); } else
             if (ok[i]) tap_mfmas(acc[ky], ah, al, fb[i & 1]);
             if (do_db && ky == 0) {
 #pragma unroll
@@ -1264,8 +1172,8 @@ __global__ __launch_bounds__(512, 2) void conv_ps_wgrad3_kernel(PsWgParams p) {
         issue_dy(c_begin); issue_x(c_begin);
         for (int c = c_begin; c < c_end; ++c) {
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            if constexpr ((WG3_ABL & 16) == 0) __builtin_amdgcn_s_barrier();
-            if (c + 1 < c_end && !((WG3_ABL & 1) && c > c_begin)) { issue_dy(c + 1); issue_x(c + 1); }
+            __builtin_amdgcn_s_barrier();
+            if (c + 1 < c_end) { issue_dy(c + 1); issue_x(c + 1); }
             compute(c);
         }
     }
@@ -1274,13 +1182,6 @@ __global__ __launch_bounds__(512, 2) void conv_ps_wgrad3_kernel(PsWgParams p) {
     const int li = lane & 31;
     const int M = p.Cout, N = 9 * p.Cin;
     float* out = p.out + (p.ksplit > 1 ? (long long)zz * M * N : 0);
-    if constexpr ((WG3_ABL & 32) != 0) {     // every accumulator stays live, nothing is stored
-        float t = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) t += accb[0][r] + accb[1][r] + acc[0][0][r] + acc[0][1][r] + acc[1][0][r] + acc[1][1][r] + acc[2][0][r] + acc[2][1][r];
-        if (p.P < 0) out[lane] = t;
-        return;
-    }
 #pragma unroll
     for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
@@ -1448,22 +1349,16 @@ static int ilog2x(int v) {
 bool conv3x3_ps_supported(int B, int H, int W, int K_channels, int N_channels) {
     return B > 0 && ilog2x(H) >= 0 && ilog2x(W) >= 0 && K_channels % 32 == 0 && N_channels % PS_BN == 0 && K_channels >= 32;
 }
-static bool ps_large(long long M, int N) {
-    static const int force = getenv("BD_PS_TILE") ? atoi(getenv("BD_PS_TILE")) : 0;   // 128 / 256 force a variant (A/B)
-    if (force == 128) return false;
-    if (force == 256) return true;
-    return cdiv(M, PS_BM) * (N / PS_BN) >= 96;
-}
+static bool ps_large(long long M, int N) { return cdiv(M, PS_BM) * (N / PS_BN) >= 96; }
 static void ps_small_split(long long M, int N, int K, int& ksplit, int& cps) {
     const long long tiles = cdiv(M, 128) * (N / 128);
     const int nchunks = 9 * (K / 32);
     static const int slots = [] {
         int dev = 0, cus = 256;
         if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        const char* e = getenv("BD_PS_SMALL_SLOTS");
-        return e ? atoi(e) : cus;   // (2 x CUs measured 0.1-0.2 ms/step slower: twice the slab traffic for the 4x4 / 8x8 layers)
+        return cus;   // (2 x CUs measured 0.1-0.2 ms/step slower: twice the slab traffic for the 4x4 / 8x8 layers)
     }();
-    static const int mincps = getenv("BD_PS_SMALL_MINCPS") ? atoi(getenv("BD_PS_SMALL_MINCPS")) : 4;
+    constexpr int mincps = 4;   // chunks per split at least
     int ks = (int)(slots / tiles);
     if (ks < 1) ks = 1;
     if (ks > nchunks / mincps) ks = nchunks / mincps;
@@ -1490,8 +1385,7 @@ static bool ps_takes_v3(int B, int H, int W, int N) {
 }
 // Round 4: pixel splits of the GroupNorm partials a forward call can write from its epilogue (0: it cannot).  One split per 256-pixel tile.
 int conv3x3_ps_gn_splits(int B, int H, int W, int K, int N, int groups) {
-    static const bool off = getenv("BD_GN_EPI_STATS") && atoi(getenv("BD_GN_EPI_STATS")) == 0;       // (A/B knob)
-    if (off || B <= 0 || ilog2x(H) < 0 || ilog2x(W) < 0 || K <= 0 || K % 32 || N <= 0 || N % PS_BN || groups <= 0 || N % groups) return 0;
+    if (B <= 0 || ilog2x(H) < 0 || ilog2x(W) < 0 || K <= 0 || K % 32 || N <= 0 || N % PS_BN || groups <= 0 || N % groups) return 0;
     const int lc = ilog2x(N / groups);
     if (lc < 2 || lc > 5 || (H * W) % PS_BM) return 0;
     return ps_takes_v3(B, H, W, N) ? H * W / PS_BM : 0;
@@ -1536,9 +1430,6 @@ int conv3x3_ps(const bd_conv3x3_ps_desc& d, hipStream_t st) {
     if (large) {
         p.tiles_m = (int)cdiv(M, PS_BM); p.tiles_n = d.N / PS_BN;
         const dim3 grid((unsigned)(p.tiles_m * p.tiles_n)), block(PS_NT);
-#ifdef BD_PS_ABLATION
-        p.ablate = getenv("BD_PS_ABLATE") ? atoi(getenv("BD_PS_ABLATE")) : 0;
-#endif
         // vertical-tap sharing variant (conv_ps3_kernel): image rows of 16 or 32 pixels, whole images per tile row block
         const int vw = d.W < 32 ? d.W : 32;
         const bool v3 = ps_takes_v3(d.B, d.H, d.W, d.N);
@@ -1577,8 +1468,9 @@ int conv3x3_ps(const bd_conv3x3_ps_desc& d, hipStream_t st) {
             pp.partial = reinterpret_cast<float*>(d.workspace);
         }
         const dim3 grid((unsigned)(p.tiles_m * p.tiles_n * pp.ksplit)), block(512);
-        // round 6: short K slices (the 4 x 4 level) take the four-stage form (three chunks in flight, one workgroup per CU)
-        static const int deep_maxcps = getenv("BD_PS128_DEEP_MAXCPS") ? atoi(getenv("BD_PS128_DEEP_MAXCPS")) : 9;       // (A/B knob: 0 = off)
+        // round 6: short K slices (the 4 x 4 level) take the four-stage form (three chunks in flight, one workgroup per CU).  9: the 4 x 4
+        // level only, -0.05 ms per step; two stages everywhere or the 8 x 8 level too measured slower (profiles/r06_ab_ps128_deep.txt)
+        constexpr int deep_maxcps = 9;
 #define PS128_LAUNCH(E, ...) do { if (sp) hipLaunchKernelGGL((conv_ps128_kernel<E, true, ##__VA_ARGS__>), grid, block, 0, st, pp); \
                                       else hipLaunchKernelGGL((conv_ps128_kernel<E, false, ##__VA_ARGS__>), grid, block, 0, st, pp); } while (0)
         if (pp.ksplit > 1 && pp.cps <= deep_maxcps) {
@@ -1623,8 +1515,7 @@ static void ps_wgrad_split(const bd_conv3x3_ps_wgrad_desc& d, int& ksplit, int& 
     static const int slots = [] {
         int dev = 0, cus = 256;
         if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        const char* e = getenv("BD_PS_WG_SLOTS");
-        return e ? atoi(e) : 2 * cus;   // two 64-KB workgroups per CU (two LDS stages each): the pair de-phases, 141 vs 189 us
+        return 2 * cus;   // two 64-KB workgroups per CU (two LDS stages each): the pair de-phases, 141 vs 189 us
     }();
     // 96 KB of LDS: one workgroup per CU -- and three quarters of the CUs (round 4, late: 192 of 256).  The kernel never runs alone: the data-gradient
     // chain shares the chip with it, so the CUs it leaves are not idle, and a quarter fewer slabs are a quarter less slab traffic: CIFAR step
@@ -1635,7 +1526,7 @@ static void ps_wgrad_split(const bd_conv3x3_ps_wgrad_desc& d, int& ksplit, int& 
     static const int slots3_getenv = getenv("BD_PS_WG3_SLOTS") ? atoi(getenv("BD_PS_WG3_SLOTS")) : 0;
     const int slots3_env = g_wg3_slots_override > 0 ? g_wg3_slots_override : slots3_getenv;      // bd_tune_set("ps_wg3_slots", n) wins over the environment
     const int slots3 = slots3_env > 0 ? slots3_env : (d.W > 32 ? slots / 4 : slots * 3 / 8);
-    static const int mincps = getenv("BD_PS_WG_MINCPS") ? atoi(getenv("BD_PS_WG_MINCPS")) : 8;   // chunks per split at least (4x4 layers: 8 slabs instead of 14; 4 / 16 measured +0.2 / +0.1 ms)
+    constexpr int mincps = 8;   // chunks per split at least (4x4 layers: 8 slabs instead of 14; 4 / 16 measured +0.2 / +0.1 ms)
     int ks = (int)((v3 ? slots3 : slots) / tiles);
     if (ks < 1) ks = 1;
     if (ks > nchunks / mincps) ks = nchunks / mincps > 0 ? nchunks / mincps : 1;
@@ -1676,26 +1567,11 @@ int conv3x3_ps_wgrad(const bd_conv3x3_ps_wgrad_desc& d, hipStream_t st) {
     if (prof_on())
         rec = prof_begin(v3 ? (sp ? "conv_ps_wgrad3_bf16" : "conv_ps_wgrad3") : (sp ? "conv_ps_wgrad_bf16" : "conv_ps_wgrad"), 2.0 * (double)p.P * d.Cout * 9.0 * d.Cin,   // (round 6: the large layers' kernel is its own class)
                          ((double)p.P * (d.Cin + d.Cout) + 9.0 * d.Cin * d.Cout) * 4.0, st);
-#ifdef BD_PS_ABLATION
-    p.ablate = getenv("BD_PS_ABLATE") ? atoi(getenv("BD_PS_ABLATE")) : 0;
-#endif
-    static const int stages = getenv("BD_PS_WG_STAGES") ? atoi(getenv("BD_PS_WG_STAGES")) : 2;
     const dim3 grid((unsigned)(p.tiles_m * p.tiles_n * p.ksplit));
-    // (NW = 4 -- 2 x 2 waves of 64 x 64 -- measured within +-2 % of NW = 8 on every layer; one form is kept)
-#ifdef BD_PS_ABLATION
-    static const int nw = getenv("BD_PS_WG_NW") ? atoi(getenv("BD_PS_WG_NW")) : 8;
-    if (nw == 4 && stages == 2) { if (sp) hipLaunchKernelGGL((conv_ps_wgrad_kernel<2, 4, true>), grid, dim3(256), 0, st, p);
-                                  else hipLaunchKernelGGL((conv_ps_wgrad_kernel<2, 4, false>), grid, dim3(256), 0, st, p); }
-    else if (nw == 4) { if (sp) hipLaunchKernelGGL((conv_ps_wgrad_kernel<3, 4, true>), grid, dim3(256), 0, st, p);
-                        else hipLaunchKernelGGL((conv_ps_wgrad_kernel<3, 4, false>), grid, dim3(256), 0, st, p); }
-    else
-#endif
     if (v3 && sp) hipLaunchKernelGGL(conv_ps_wgrad3_kernel<true>, grid, dim3(512), 0, st, p);
     else if (v3) hipLaunchKernelGGL(conv_ps_wgrad3_kernel<false>, grid, dim3(512), 0, st, p);
-    else if (stages == 2) { if (sp) hipLaunchKernelGGL((conv_ps_wgrad_kernel<2, 8, true>), grid, dim3(512), 0, st, p);
-                            else hipLaunchKernelGGL((conv_ps_wgrad_kernel<2, 8, false>), grid, dim3(512), 0, st, p); }
-    else if (sp) hipLaunchKernelGGL((conv_ps_wgrad_kernel<3, 8, true>), grid, dim3(512), 0, st, p);
-    else hipLaunchKernelGGL((conv_ps_wgrad_kernel<3, 8, false>), grid, dim3(512), 0, st, p);
+    else if (sp) hipLaunchKernelGGL((conv_ps_wgrad_kernel<2, 8, true>), grid, dim3(512), 0, st, p);
+    else hipLaunchKernelGGL((conv_ps_wgrad_kernel<2, 8, false>), grid, dim3(512), 0, st, p);
     BD_LAUNCH_CHECK("conv_ps_wgrad");
     if (p.ksplit > 1) {
         const long long total = mn / 4 + (d.db ? d.Cout : 0);

@@ -499,8 +499,8 @@ static bool gn_resident_plan(int B, int HW, int C, int G, GnRes& o, bool wide_ok
         // round 4 (late): a slab whose row pieces are not whole 64-byte halves of a line (12 channels per group at 32 x 32: 24 channels = 96 B rows,
         // 48-byte half planes) writes 1.3 - 1.4x its bytes (PMC, profiles/r04_gn_pmc_by_shape.txt) and runs at 2.8 TB/s: the two-pass kernels,
         // whose rows are whole, are faster there although they read x twice
-        static const int row_align = getenv("BD_GN_RES_ALIGN") ? atoi(getenv("BD_GN_RES_ALIGN")) : 64;      // (A/B knob: 0 = round 3's rule)
-        if (row_align > 0 && (best * 4) % row_align != 0 && best < C) continue;
+        constexpr int row_align = 64;
+        if ((best * 4) % row_align != 0 && best < C) continue;
         while ((long long)B * (C / best) < 512) {
             const int half = best / 2;
             if (half < 16 || half % unit || C % half) break;
@@ -909,9 +909,7 @@ extern "C" int bd_gn_fwd_takes_stats(int B, int HW, int C, int G) {
 
 extern "C" int bd_gn_bwd_defers(int B, int HW, int C, int G) {
     // round 4: both the resident and the large-image path leave per-sample partials to the caller
-    static const bool split_too = !(getenv("BD_GN_DEFER_SPLIT") && atoi(getenv("BD_GN_DEFER_SPLIT")) == 0);      // (A/B knob)
-    GnRes rp;
-    return B > 0 && HW > 0 && C > 0 && G > 0 && C % G == 0 && (C & 3) == 0 && (split_too || gn_resident_plan(B, HW, C, G, rp, true)) ? 1 : 0;
+    return B > 0 && HW > 0 && C > 0 && G > 0 && C % G == 0 && (C & 3) == 0 ? 1 : 0;
 }
 
 extern "C" int bd_gn_bwd_params(const bd_gn_param_item* items, int n, int B, bd_stream_t stream) {

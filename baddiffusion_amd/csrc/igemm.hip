@@ -1360,10 +1360,9 @@ static void launch_tile(const IGemmParams& p, const bd_igemm_desc& d, Cls cls, d
     // split-bf16 128x128 tiles run with 512 threads (8 waves of 32x64, 4 waves per SIMD): half the accumulators and
     // staging registers per thread buys the occupancy that hides the split / staging work (conv fwd +7 %, dgrad +9 %,
     // K=256 GEMMs +20..30 %).  The conv wgrad (both operands row-contiguous, the largest address state) fits 128 VGPRs
-    // only with a single prefetch register set (DEPTH 1).  BD_IGEMM_NT=256 forces the narrow form everywhere.
-    static const bool narrow = getenv("BD_IGEMM_NT") && atoi(getenv("BD_IGEMM_NT")) == 256;
+    // only with a single prefetch register set (DEPTH 1).
     if constexpr (TR && T == 128) {
-        if (!narrow && launch_fast<T, TR, SP, 512>(p, cls, grid, st)) return;
+        if (launch_fast<T, TR, SP, 512>(p, cls, grid, st)) return;
     }
     if (launch_fast<T, TR, SP, 256>(p, cls, grid, st)) return;
     const bool akc = d.A.kc != 0, bkc = d.B.kc != 0;

@@ -288,8 +288,8 @@ struct bd_unet {
             if (n > c.opws_need) c.opws_need = n;
             return BD_OK;
         }
-        static const bool aux_on = !(getenv("BD_SP_WG_AUX") && atoi(getenv("BD_SP_WG_AUX")) == 0);   // (A/B knob: weight gradients on the main stream)
-        if (aux && aux_on) return on_aux(c, [&](hipStream_t st, char* ws) { g.workspace = ws; return gemm_sp(g, st); });
+        // (the attention block's weight gradients on the main stream measured +0.35 ms per step)
+        if (aux) return on_aux(c, [&](hipStream_t st, char* ws) { g.workspace = ws; return gemm_sp(g, st); });
         g.workspace = c.opws;
         return gemm_sp(g, c.st);
     }
@@ -420,13 +420,8 @@ struct bd_unet {
             if (n > c.opws_need) c.opws_need = n;
             return BD_OK;
         }
-        // BD_AUX_MAXPIX (A/B knob): weight gradients over more pixels than this stay on the main stream -- they fill the chip
-        // on their own, and beside the dgrad chain they mostly trade clock for overlap
-        static const long long maxpix = getenv("BD_AUX_MAXPIX") ? atoll(getenv("BD_AUX_MAXPIX")) : (1ll << 62);
-        // BD_AUX_MINPIX (A/B knob): weight gradients over fewer pixels than this stay on the main stream too -- at 4 x 4 / 8 x 8 a launch is
-        // 10-30 us and the fork / join events cost as much as the overlap returns
-        static const long long minpix = getenv("BD_AUX_MINPIX") ? atoll(getenv("BD_AUX_MINPIX")) : 0;
-        if ((long long)d.B * d.H * d.W > maxpix || (long long)d.B * d.H * d.W < minpix) { d.workspace = c.opws; return conv3x3_ps_wgrad(d, c.st); }
+        // every weight gradient runs on the side stream: keeping the large layers' (they fill the chip on their own) or the 4 x 4 / 8 x 8
+        // layers' (10-30 us launches, as long as the fork / join) on the main stream measured 0.2 - 0.7 ms per step slower
         return on_aux(c, [&](hipStream_t st, char* ws) { d.workspace = ws; return conv3x3_ps_wgrad(d, st); });
     }
     static uint16_t* U16(float* p) { return reinterpret_cast<uint16_t*>(p); }
@@ -1409,8 +1404,7 @@ static int unet_aux_init(bd_unet* u) {
     if (u->aux_stream) return BD_OK;
     int lo = 0, hi = 0;
     BD_HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));   // lowest priority: in backward the dgrad chain is the critical path
-    const int prio = getenv("BD_AUX_PRIO") ? atoi(getenv("BD_AUX_PRIO")) : lo;     // (A/B knob; `lo` = lowest)
-    BD_HIP_TRY(hipStreamCreateWithPriority(&u->aux_stream, hipStreamNonBlocking, prio));
+    BD_HIP_TRY(hipStreamCreateWithPriority(&u->aux_stream, hipStreamNonBlocking, lo));
     BD_HIP_TRY(hipEventCreateWithFlags(&u->aux_ev_fork, hipEventDisableTiming));
     BD_HIP_TRY(hipEventCreateWithFlags(&u->aux_ev_join[0], hipEventDisableTiming));
     BD_HIP_TRY(hipEventCreateWithFlags(&u->aux_ev_join[1], hipEventDisableTiming));
@@ -1446,11 +1440,10 @@ extern "C" int bd_unet_forward(bd_unet* u, int B, int training, const float* par
         return split_wt_batched(params, const_cast<uint16_t*>(c.wT_split), u->wt_off.data(), u->wt_cin.data(), u->wt_cout.data(),
                                 (int)u->wt_off.size(), st);
     };
-    static const int fwd_pipes = getenv("BD_FWD_PIPES") ? atoi(getenv("BD_FWD_PIPES")) : 2;   // 1 = forward on one stream (A/B)
     // two pipelines need enough work per half to pay for twice the host enqueue: >= 32 K input pixels in the batch (B = 32 at 32 x 32 as
     // before; round 4: B = 4 at 256 x 256 qualifies too -- 29.05 -> 28.13 ms per 256 x 256 train step, small layers fill the chip in pairs)
     static const long long pipes_min_px = getenv("BD_FWD_PIPES_MINPX") ? atoll(getenv("BD_FWD_PIPES_MINPX")) : 32768;      // (A/B knob)
-    if (!u->aux_enabled || B < 2 || (long long)B * u->cfg.sample_size * u->cfg.sample_size < pipes_min_px || fwd_pipes < 2) {
+    if (!u->aux_enabled || B < 2 || (long long)B * u->cfg.sample_size * u->cfg.sample_size < pipes_min_px) {
         BD_TRY(transpose_weights(c.st));
         for (auto& f : u->fwd) BD_TRY(f(c));
         return BD_OK;
