@@ -235,6 +235,7 @@ SIGNATURES = {
     "bd_unet_workspace_bytes": (sz, [vp, i32, i32]),
     "bd_unet_forward": (i32, [vp, i32, i32, vp, vp, i64, vp, i32, vp, i64, vp, sz, vp]),
     "bd_unet_backward": (i32, [vp, i32, vp, vp, i64, vp, i64, vp, vp, sz, vp]),
+    "bd_unet_backward_input": (i32, [vp, i32, vp, vp, i64, vp, i64, vp, vp, i64, vp, sz, vp]),
     "bd_unet_num_segments": (i32, [vp]),
     "bd_unet_set_aux_stream": (i32, [vp, i32]),
     "bd_unet_set_static_weights": (i32, [vp, i32]),

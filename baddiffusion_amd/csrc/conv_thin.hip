@@ -434,6 +434,82 @@ __global__ __launch_bounds__(256, 3) void thin_contract_kernel(const float* __re
     }
 }
 
+// conv_in DATA GRADIENT (C -> J = Cin in {1, 3}): the contract direction with flipped taps and the coefficient index transposed,
+//   dx[p][j] = sum_{t, co} dy[p + d(t)][co] * w[co][8 - t][j],   w = [Cout][3][3][J]   (the network's input gradient).
+// Same form as thin_contract_kernel: wave = 32 adjacent pixels of one image row, lane = 2 channels of dy, sliding 3 x 10 window, one
+// butterfly per output value.  The lane's 2 x 9 x J coefficients are 27 floats apart per channel in w, so a workgroup stages the
+// 128-channel chunk of w in LDS (coalesced read, transposed to [j][flipped tap][channel]: 14 KB for J = 3) and every lane reads its pair
+// per tap from there (9 reads feed the 8 pixels of a group); a wave walks `segs_per_wave` segments per staging.  Cout > 128 runs chunk by
+// chunk: the lane that stored a pixel's partial sum adds the next chunk to it (same thread, fixed order: deterministic).  Plain fp32 FMAs
+// in every compute mode, the lane's two channels as one packed FMA; the layer is bound by its dy read.
+typedef float thin_f32x2 __attribute__((ext_vector_type(2)));
+template <int J>
+__global__ __launch_bounds__(256, 3) void thin_contract_dgrad_kernel(const float* __restrict__ dy, long long lddy, const float* __restrict__ w,
+                                                                int Cout, float* __restrict__ dx, long long lddx, int H, int W, long long nseg,
+                                                                int segs_per_wave) {
+    constexpr int WLD = 130;       // row of 128 channels + 2: the transposing store below spreads over the banks, rows stay 8-byte aligned
+    __shared__ __attribute__((aligned(8))) float wsh[9 * J * WLD];      // [j][flipped tap][channel of the chunk]
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int HW = H * W;
+    const unsigned ld32 = (unsigned)lddy;
+    for (int ch = 0; ch < Cout / 128; ++ch) {             // workgroup-uniform: the barriers below are reached by every thread
+        if (ch) __syncthreads();
+        for (int i = threadIdx.x; i < 128 * 9 * J; i += 256) {      // coalesced read of w as stored: i = (co, tap, j)
+            const int co = i / (9 * J), r = i - co * 9 * J, tt = r / J, j = r - tt * J;
+            wsh[(j * 9 + 8 - tt) * WLD + co] = w[(long long)ch * 128 * 9 * J + i];
+        }
+        __syncthreads();
+        for (int s = 0; s < segs_per_wave; ++s) {
+            const long long seg = ((long long)blockIdx.x * 4 + wave) * segs_per_wave + s;   // wave-uniform
+            if (seg >= nseg) break;
+            const long long p0 = seg * 32;                 // W % 32 == 0: a segment is 32 pixels of one image row
+            const int b = (int)(p0 / HW), r = (int)(p0 - (long long)b * HW);
+            const int y = r / W, x0 = r - y * W;
+            const float* base = dy + (long long)b * HW * lddy + ch * 128 + lane * 2;
+            // out-of-image taps: clamped (valid) pixel of the same image x 0 (no select around the load, see thin_contract_kernel)
+            auto ld = [&](int ys, int xs) -> thin_f32x2 {
+                const float m = ((unsigned)ys < (unsigned)H && (unsigned)xs < (unsigned)W) ? 1.f : 0.f;
+                const int yc = min(max(ys, 0), H - 1), xc = min(max(xs, 0), W - 1);
+                const thin_f32x2 v = *reinterpret_cast<const thin_f32x2*>(base + (unsigned)(yc * W + xc) * ld32);      // H W lddy < 2^31 (launch check)
+                return v * m;
+            };
+            constexpr int GP = 8;
+#pragma unroll 1
+            for (int g = 0; g < 32 / GP; ++g) {
+                thin_f32x2 win[3][GP + 2];
+#pragma unroll
+                for (int dr = 0; dr < 3; ++dr)
+#pragma unroll
+                    for (int dc = 0; dc < GP + 2; ++dc) win[dr][dc] = ld(y - 1 + dr, x0 + g * GP + dc - 1);
+#pragma unroll
+                for (int j = 0; j < J; ++j) {
+                    // this lane's two channels: one conflict-free 8-byte LDS read per tap, reused by the 8 pixels.  The empty asm keeps the
+                    // reads here: hoisted out of the loops (they are invariant) the 27 pairs cost 54 registers and the kernel spills
+                    int lo = 2 * lane;
+                    asm volatile("" : "+v"(lo));
+                    thin_f32x2 cf[9];
+#pragma unroll
+                    for (int t = 0; t < 9; ++t) cf[t] = *reinterpret_cast<const thin_f32x2*>(wsh + (j * 9 + t) * WLD + lo);
+                    float part[GP];
+#pragma unroll
+                    for (int px = 0; px < GP; ++px) {
+                        thin_f32x2 a = {0.f, 0.f};      // the lane's two channels side by side: window pair x coefficient pair = one v_pk_fma_f32
+#pragma unroll
+                        for (int t = 0; t < 9; ++t) a = __builtin_elementwise_fma(win[t / 3][px + t % 3], cf[t], a);
+                        part[px] = a.x + a.y;
+                    }
+                    const float v = thin_fold<GP>(part, lane);
+                    if ((lane & (64 / GP - 1)) == 0) {
+                        float* o = dx + (p0 + g * GP + lane / (64 / GP)) * lddx + j;
+                        *o = ch ? *o + v : v;
+                    }
+                }
+            }
+        }
+    }
+}
+
 // Weight gradients of the two layers, wave-per-row form (W % 32 == 0): a wave walks 32-pixel row segments, lane = 2 channels of
 // the wide tensor (one coalesced 512-byte load per pixel), the narrow tensor's 3 x 3 x J neighbourhood is wave-uniform (scalar
 // loads, sliding window), 9*J float2 accumulators per lane.  Four waves fold through LDS in a fixed order, every workgroup
@@ -595,6 +671,20 @@ int conv3x3_fwd_thin(const bd_conv3x3_fwd_desc& d, hipStream_t st) {
 int conv3x3_dgrad_thin(const bd_conv3x3_dgrad_desc& d, hipStream_t st) {
     static const bool off = getenv("BD_THIN_DIRECT") && atoi(getenv("BD_THIN_DIRECT")) == 0;
     if (off || d.accumulate || !thin_same_grid(d.stride, d.ups, d.pad_t, d.pad_l, d.Hs, d.Ws, d.Ho, d.Wo)) return 0;
+    if ((d.Cin == 3 || d.Cin == 1) && d.Cout % 128 == 0 && d.Ws % 32 == 0 && d.lddy % 2 == 0 && ((uintptr_t)d.dy & 7) == 0 &&
+        (long long)d.Hs * d.Ws * d.lddy < (1ll << 31)) {
+        // conv_in: the input gradient of the network (its own class: the expand direction below is conv_out's)
+        const int rec = prof_on() ? prof_begin("conv_thin_dgrad_in", 2.0 * d.B * d.Hs * d.Ws * 9.0 * d.Cin * d.Cout, 4.0 * d.B * d.Hs * d.Ws * (d.Cin + d.Cout), st) : -1;
+        const long long nseg = (long long)d.B * d.Hs * d.Ws / 32;
+        int spw = 1;
+        while (spw < 8 && nseg / (8 * spw) >= 2048) spw *= 2;      // amortise the coefficient staging only where >= 2048 workgroups remain
+        const dim3 grid((unsigned)cdiv(nseg, 4 * spw)), block(256);
+        if (d.Cin == 3) hipLaunchKernelGGL(thin_contract_dgrad_kernel<3>, grid, block, 0, st, d.dy, (long long)d.lddy, d.w, d.Cout, d.dx, (long long)d.lddx, d.Hs, d.Ws, nseg, spw);
+        else hipLaunchKernelGGL(thin_contract_dgrad_kernel<1>, grid, block, 0, st, d.dy, (long long)d.lddy, d.w, d.Cout, d.dx, (long long)d.lddx, d.Hs, d.Ws, nseg, spw);
+        BD_LAUNCH_CHECK("conv3x3 thin contract dgrad");
+        prof_end(rec, st);
+        return 1;
+    }
     if (!((d.Cout == 3 || d.Cout == 1) && d.Cin % 128 == 0 && d.Ws % 4 == 0 && d.lddx % 4 == 0 && aligned16(d.dx))) return 0;
     const int rec = prof_on() ? prof_begin("conv_thin_dgrad", 2.0 * d.B * d.Hs * d.Ws * 9.0 * d.Cin * d.Cout, 4.0 * d.B * d.Hs * d.Ws * (d.Cin + d.Cout), st) : -1;
     // dx[p][c] = sum_{t', o} dy[p + d(t')][o] * w[o][8 - t'][c]   (w = [Cout][3][3][Cin])

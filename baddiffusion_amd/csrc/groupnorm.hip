@@ -740,9 +740,11 @@ __global__ __launch_bounds__(NT) void gn_bwd_res_kernel(const float* __restrict_
                 a += o[0]; e += o[1]; h += o[2];
             }
             ch[3 * c] = a; ch[3 * c + 1] = e; ch[3 * c + 2] = h;
-            float* o = part + (long long)b * 2 * C + c0 + c;
-            o[0] = e;   // plane 0: sum dz * xhat -> dgamma
-            o[C] = a;   // plane 1: sum dz        -> dbeta
+            if (part) {   // null: a data-gradient-only backward (no parameter gradients wanted)
+                float* o = part + (long long)b * 2 * C + c0 + c;
+                o[0] = e;   // plane 0: sum dz * xhat -> dgamma
+                o[C] = a;   // plane 1: sum dz        -> dbeta
+            }
         }
     } else {
         for (int c = t >> 6; c < cb; c += NT / 64) {   // one wave per channel, lanes stride over the pixel rows
@@ -754,9 +756,11 @@ __global__ __launch_bounds__(NT) void gn_bwd_res_kernel(const float* __restrict_
             for (int off = 1; off < 64; off <<= 1) { a += __shfl_xor(a, off); e += __shfl_xor(e, off); h += __shfl_xor(h, off); }
             if ((t & 63) == 0) {
                 ch[3 * c] = a; ch[3 * c + 1] = e; ch[3 * c + 2] = h;
-                float* o = part + (long long)b * 2 * C + c0 + c;
-                o[0] = e;
-                o[C] = a;
+                if (part) {
+                    float* o = part + (long long)b * 2 * C + c0 + c;
+                    o[0] = e;
+                    o[C] = a;
+                }
             }
         }
     }
@@ -934,8 +938,11 @@ extern "C" int bd_gn_bwd_params(const bd_gn_param_item* items, int n, int B, bd_
 extern "C" int bd_gn_bwd(const bd_gn_bwd_desc* d, bd_stream_t stream) {
     BD_CHECK(d, BD_ERR_INVALID, "bd_gn_bwd: null descriptor");
     BD_TRY(gn_common_checks("bd_gn_bwd", d->B, d->HW, d->C, d->G, d->x, d->ldx));
-    BD_CHECK(d->gamma && d->beta && d->mean && d->rstd && d->dy && (d->dx || d->dx_split) && d->dgamma && d->dbeta && d->workspace,
+    BD_CHECK(d->gamma && d->beta && d->mean && d->rstd && d->dy && (d->dx || d->dx_split) && d->workspace,
              BD_ERR_INVALID, "bd_gn_bwd: null pointer");
+    // dgamma == dbeta == param_partials == NULL: no parameter gradient is computed or written (the data gradient is the same launch, bit for bit)
+    const bool no_params = !d->dgamma && !d->dbeta && !d->param_partials;
+    BD_CHECK(no_params || (d->dgamma && d->dbeta), BD_ERR_INVALID, "bd_gn_bwd: dgamma and dbeta go together (both null with null param_partials = no parameter gradients)");
     BD_CHECK(!d->dx_split || (d->C % 32 == 0 && d->lddxs % 32 == 0 && ((uintptr_t)d->dx_split & 127) == 0), BD_ERR_UNSUPPORTED,
              "bd_gn_bwd: dx_split needs C %% 32 == 0, lddxs %% 32 == 0 and a 128-byte aligned base");
     const int xs0 = d->dx_split_c1 > d->dx_split_c0 ? d->dx_split_c0 : 0, xs1 = d->dx_split_c1 > d->dx_split_c0 ? d->dx_split_c1 : d->C;
@@ -948,9 +955,9 @@ extern "C" int bd_gn_bwd(const bd_gn_bwd_desc* d, bd_stream_t stream) {
     BD_CHECK(!d->dx_add || (d->dx && (d->ld_add & 3) == 0 && aligned16(d->dx_add)), BD_ERR_INVALID, "bd_gn_bwd: dx_add needs dx, a 16B-aligned pointer and ld_add %% 4 == 0");
     GnRes rp;
     if (gn_resident_plan(d->B, d->HW, d->C, d->G, rp, true)) {
-        const size_t need_r = d->param_partials ? 0 : (size_t)d->B * d->C * 2 * sizeof(float);
+        const size_t need_r = d->param_partials || no_params ? 0 : (size_t)d->B * d->C * 2 * sizeof(float);
         BD_CHECK(d->workspace_bytes >= need_r, BD_ERR_WORKSPACE, "bd_gn_bwd: workspace %zu < %zu", d->workspace_bytes, need_r);
-        float* part_r = d->param_partials ? d->param_partials : reinterpret_cast<float*>(d->workspace);
+        float* part_r = d->param_partials ? d->param_partials : (no_params ? nullptr : reinterpret_cast<float*>(d->workspace));
         const dim3 grid((unsigned)rp.nblk * (unsigned)d->B);
         int rec = -1;       // REQUIRED bytes of this call: x and dy in (+ the dx it accumulates into, + the added gradient), dx and / or its planes out
         if (prof_on())
@@ -968,7 +975,7 @@ extern "C" int bd_gn_bwd(const bd_gn_bwd_desc* d, bd_stream_t stream) {
 #undef BD_GN_BWD_RES
         BD_LAUNCH_CHECK("gn_bwd_res");
         prof_end(rec, S(stream));
-        if (d->param_partials) return BD_OK;   // the caller folds them (bd_gn_bwd_params)
+        if (d->param_partials || no_params) return BD_OK;   // the caller folds them (bd_gn_bwd_params) / nobody wants them
         hipLaunchKernelGGL(gn_bwd_param_kernel, dim3((unsigned)cdiv(2 * d->C, 64)), dim3(1024), 0, S(stream), part_r, d->B, 2 * d->C,
                            d->C, d->dgamma, d->dbeta);
         BD_LAUNCH_CHECK("gn_bwd_param");
@@ -986,7 +993,7 @@ extern "C" int bd_gn_bwd(const bd_gn_bwd_desc* d, bd_stream_t stream) {
                        (long long)d->ldx, d->dy, (long long)d->lddy, d->HW, d->C, d->G, r, S_, d->gamma, d->beta, d->mean,
                        d->rstd, d->silu, part);
     BD_LAUNCH_CHECK("gn_bwd_stats");
-    if (!d->param_partials) {
+    if (!d->param_partials && !no_params) {
         hipLaunchKernelGGL(gn_bwd_param_kernel, dim3((unsigned)cdiv(2 * d->C, 64)), dim3(1024), 0, S(stream), part, d->B * S_, 3 * d->C,
                            d->C, d->dgamma, d->dbeta);
         BD_LAUNCH_CHECK("gn_bwd_param");

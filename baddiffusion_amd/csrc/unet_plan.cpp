@@ -86,6 +86,11 @@ struct Ctx {
     const int64_t* t = nullptr; int t_stride = 0;
     float* out = nullptr; int64_t ldo = 0;
     const float* dout = nullptr; int64_t lddo = 0;
+    // backward only.  wg = false: the data-gradient-only schedule (bd_unet_backward_input with grads == NULL) -- every launch that produces
+    // a parameter gradient is skipped by the helper it goes through, nothing is forked to the side stream.  dx: where conv_in's backward
+    // leaves the gradient of the network input (null: not wanted)
+    bool wg = true;
+    float* dx = nullptr; int64_t lddx = 0;
     char* opws = nullptr; size_t opws_bytes = 0; size_t opws_need = 0;
     // weight-gradient side stream (backward only): wgrad GEMMs feed nothing but the optimizer, so they run on a second
     // stream next to the dgrad / GroupNorm chain that the rest of backward waits for.  Forked per launch; the scratch
@@ -102,7 +107,7 @@ struct Ctx {
     std::vector<bd_gn_param_item> gn_items;
     // hands a GroupNorm backward its slot (or nothing: the layer then reduces its own parameters as before)
     float* gn_slot(int B, int HW, int C, int G, float* dgamma, float* dbeta) {
-        if (!bd_gn_bwd_defers(B, HW, C, G)) return nullptr;
+        if (!wg || !bd_gn_bwd_defers(B, HW, C, G)) return nullptr;
         const size_t n = ((size_t)B * 2 * C + 63) / 64 * 64;
         if (dry) { gnpart_need += n; return nullptr; }
         if (!gnpart || gnpart_used + n > gnpart_floats) return nullptr;
@@ -282,6 +287,7 @@ struct bd_unet {
     }
     // GEMM on split planes (gemm_sp.hip); aux: a weight gradient, on the side stream
     int gemm_s(Ctx& c, bd_gemm_sp_desc& g, bool aux = false) const {
+        if (aux && !c.wg) return BD_OK;
         g.workspace_bytes = c.opws_bytes; g.mode = cfg.compute_mode;
         if (c.dry) {
             const size_t n = gemm_sp_workspace_bytes(g);
@@ -319,6 +325,7 @@ struct bd_unet {
     // dW[N,K] = dY[M,N]^T * X[M,K]; db[N] = column sums of dY, fused into the same launch (N % 4 == 0)
     int linear_wgrad(Ctx& c, const float* dY, int64_t lddy, const float* X, int64_t ldx, float* dW, int M, int N, int K,
                      float* db = nullptr) const {
+        if (!c.wg) return BD_OK;
         bd_igemm_desc g = {};
         g.A = dense(dY, lddy, 0); g.B = dense(X, ldx, 0);
         g.M = N; g.N = K; g.K = M; g.batch_outer = g.batch_inner = 1;
@@ -333,6 +340,7 @@ struct bd_unet {
     }
     // bias gradient: per-sample column sums (scratch [B,N]) then a sum over the batch (fixed order)
     int bias_grad(Ctx& c, const float* dY, int64_t ld, int HW, int N, int scratch_buf, float* db, float* db2 = nullptr) const {
+        if (!c.wg) return BD_OK;
         float* s = BP(c, scratch_buf);
         BD_TRY(colsum(c, dY, ld, (int64_t)c.B * HW, N, HW, s, N));
         BD_TRY(colsum(c, s, N, c.B, N, c.B, db, N));
@@ -366,7 +374,7 @@ struct bd_unet {
         d.dy = dy; d.lddy = lddy; d.dx = GP(c, x); d.lddx = x.ld;
         d.accumulate_dx = c.ginit[x.buf];
         c.ginit[x.buf] = 1;
-        d.dgamma = c.grads + pg; d.dbeta = c.grads + pb;
+        if (c.wg) { d.dgamma = c.grads + pg; d.dbeta = c.grads + pb; }      // (else: bd_gn_bwd leaves the parameter sums out)
         d.workspace = c.opws; d.workspace_bytes = c.opws_bytes;
         d.param_partials = c.gn_slot(d.B, d.HW, d.C, d.G, d.dgamma, d.dbeta);
         if (c.dry) return BD_OK;
@@ -389,6 +397,7 @@ struct bd_unet {
         return conv3x3_dgrad(d, c.st);
     }
     int conv_w(Ctx& c, bd_conv3x3_wgrad_desc& d) const {
+        if (!c.wg) return BD_OK;
         d.workspace = c.opws; d.workspace_bytes = c.opws_bytes; d.mode = cfg.compute_mode;
         if (c.dry) { note_conv(c); return BD_OK; }
         return on_aux(c, [&](hipStream_t st, char* ws) { d.workspace = ws; return conv3x3_wgrad(d, st); });
@@ -413,6 +422,7 @@ struct bd_unet {
         return mode_bf16(cfg.compute_mode) && (c.dry || c.w_split) && upsample_conv_ps_supported(B, H, W, Cin, Cout) && wgs >= min_wgs;
     }
     int conv_pw(Ctx& c, bd_conv3x3_ps_wgrad_desc& d) const {
+        if (!c.wg) return BD_OK;
         d.workspace_bytes = c.opws_bytes; d.mode = cfg.compute_mode;
         if (c.dry) {
             note_conv(c);
@@ -482,6 +492,7 @@ void bd_unet::node_time_embed() {
         return (int)BD_OK;
     });
     Bk([=](Ctx& c) {
+        if (!c.wg) return (int)BD_OK;      // the timestep is not differentiable: this branch feeds weight gradients only
         float* dtp = BP(c, b_dtproj);
         // (the weight / bias gradient of the batched projection is produced resnet by resnet, see node_resnet)
         BD_TRY(linear_dgrad(c, dtp, sumC, c.params + p_tw, BP(c, b_dembs), T, c.B, sumC, T, 0));
@@ -511,7 +522,13 @@ void bd_unet::node_conv_in(const View& y) {
         bd_conv3x3_wgrad_desc d = {};
         d.B = c.B; d.Hs = S_; d.Ws = S_; d.Cin = Cin; d.Cout = Cout; d.stride = 1; d.pad_t = 1; d.pad_l = 1; d.Ho = S_; d.Wo = S_;
         d.x = c.x; d.ldx = c.ldx; d.dy = dy; d.lddy = y.ld; d.dw = c.grads + pw; d.db = c.grads + pb;
-        return conv_w(c, d);
+        BD_TRY(conv_w(c, d));
+        if (!c.dx && !c.dry) return (int)BD_OK;
+        // the last link of the data-gradient chain: dL/dx of the network input (bd_unet_backward_input), on the main stream
+        bd_conv3x3_dgrad_desc g = {};
+        g.B = c.B; g.Hs = S_; g.Ws = S_; g.Cin = Cin; g.Cout = Cout; g.stride = 1; g.pad_t = 1; g.pad_l = 1; g.Ho = S_; g.Wo = S_;
+        g.dy = dy; g.lddy = y.ld; g.w = c.params + pw; g.dx = c.dx; g.lddx = c.lddx;
+        return conv_d(c, g);
     });
 }
 
@@ -671,10 +688,12 @@ void bd_unet::node_resnet(const std::string& pre, const View& x, const View& y, 
             d.x = BP(c, b_h1); d.ldx = Cout; d.gamma = c.params + pn2w; d.beta = c.params + pn2b;
             d.mean = MEANP(c, b_st2, G); d.rstd = RSTDP(c, b_st2, G);
             d.dy = BP(c, b_da2); d.lddy = Cout; d.dx = ps1 ? nullptr : BP(c, b_dh1); d.lddx = Cout; d.accumulate_dx = 0;
-            d.dgamma = c.grads + pn2w; d.dbeta = c.grads + pn2b;
             d.workspace = c.opws; d.workspace_bytes = c.opws_bytes;
-            // time-embedding gradient = per-sample column sums of dh1, out of the same launch
-            d.dx_colsum = BP(c, b_dtproj) + toff; d.ld_colsum = sumC_;
+            if (c.wg) {
+                d.dgamma = c.grads + pn2w; d.dbeta = c.grads + pn2b;
+                // time-embedding gradient = per-sample column sums of dh1, out of the same launch
+                d.dx_colsum = BP(c, b_dtproj) + toff; d.ld_colsum = sumC_;
+            }
             if (ps1) { d.dx_split = U16(BP(c, b_dh1S)); d.lddxs = Cout; }
             d.param_partials = c.gn_slot(d.B, d.HW, d.C, d.G, d.dgamma, d.dbeta);
             if (!c.dry) BD_TRY(bd_gn_bwd(&d, (bd_stream_t)c.st));
@@ -1026,7 +1045,7 @@ void bd_unet::node_upsample(const std::string& pre, const View& x, const View& y
                 return (int)BD_OK;
             }
             d.workspace_bytes = c.opws_bytes;
-            BD_TRY(on_aux(c, [&](hipStream_t st, char* ws) { d.workspace = ws; return upsample_conv_wgrad(d, st); }));
+            if (c.wg) BD_TRY(on_aux(c, [&](hipStream_t st, char* ws) { d.workspace = ws; return upsample_conv_wgrad(d, st); }));
             if (ph_d) {      // 16 taps on dY sampled at stride 2: replaces the fine-grid dgrad + 2x2 sum
                 d.workspace = c.opws;
                 return upsample_conv_dgrad(d, c.st);
@@ -1492,26 +1511,35 @@ extern "C" int bd_unet_segment_range(const bd_unet* u, int seg, int64_t* lo, int
     return BD_OK;
 }
 
-extern "C" int bd_unet_backward_segment(bd_unet* u, int seg, int B, const float* params, const float* x, int64_t ldx,
-                                        const float* dout, int64_t lddo, float* grads, void* workspace, size_t workspace_bytes,
-                                        bd_stream_t stream, int64_t* ready_lo, int64_t* ready_hi) {
+// the backward behind bd_unet_backward[_segment] (need_grads, dx == NULL) and bd_unet_backward_input (dx != NULL; grads == NULL selects the
+// data-gradient-only schedule, Ctx::wg)
+static int unet_backward_run(bd_unet* u, int seg, int B, const float* params, const float* x, int64_t ldx, const float* dout, int64_t lddo,
+                             float* grads, bool need_grads, float* dx, int64_t lddx, void* workspace, size_t workspace_bytes,
+                             bd_stream_t stream, int64_t* ready_lo, int64_t* ready_hi) {
     Ctx c;
     // a tuning-knob change re-lays out the workspace lazily: never under the saved activations of a forward that already ran
     BD_CHECK(!u || u->fwd_ws != workspace || u->fwd_B != B || u->fwd_gen == bd::g_tune_gen, BD_ERR_INVALID,
              "bd_unet_backward: bd_tune_set was called between the training forward and its backward (the saved activations would move)");
     BD_TRY(unet_ctx(u, c, B, 1, workspace, workspace_bytes));
-    BD_CHECK(params && x && dout && grads, BD_ERR_INVALID, "bd_unet_backward: null pointer");
+    BD_CHECK(params && x && dout && (grads || !need_grads), BD_ERR_INVALID, "bd_unet_backward: null pointer");
     BD_CHECK(aligned16(params) && aligned16(grads), BD_ERR_INVALID, "bd_unet_backward: params/grads must be 16-byte aligned");
     BD_CHECK(seg >= -1 && seg < (int)u->segs.size(), BD_ERR_INVALID, "bd_unet_backward: segment %d out of range", seg);
     c.params = params; c.grads = grads; c.dout = dout; c.lddo = lddo; c.st = S(stream);
     c.x = x; c.ldx = ldx;   // conv_in wgrad re-reads the forward input
+    c.wg = grads != nullptr; c.dx = dx; c.lddx = lddx;
+    const bool aux_on = u->aux_enabled && c.wg;      // without weight gradients there is nothing for the side stream
     // Deferred join (bd_unet_set_deferred_join, used by the data-parallel trainer): the weight gradients a segment puts on the side
     // stream may still be running when the call returns and while the NEXT segment's data-gradient chain runs; the caller orders
     // whatever consumes this segment's gradient ranges behind them with bd_unet_stream_wait_aux(plan, consumer_stream).  The
     // scratch-arena hazard is covered across calls by carrying the per-parity "pending" marks in the plan.  The last segment (and
     // a whole backward, seg == -1) always joins, so the caller's stream ends ordered after everything.
-    const bool defer = u->aux_enabled && u->aux_defer && seg >= 0 && seg + 1 < (int)u->segs.size();
-    if (u->aux_enabled) {
+    const bool defer = aux_on && u->aux_defer && seg >= 0 && seg + 1 < (int)u->segs.size();
+    if (!aux_on && !c.wg && u->aux_stream && (u->aux_pend[0] || u->aux_pend[1])) {
+        // (same hazard as below, for a pass that forks nothing itself)
+        BD_HIP_TRY(hipStreamWaitEvent(c.st, u->aux_ev_seg, 0));
+        u->aux_pend[0] = u->aux_pend[1] = false;
+    }
+    if (aux_on) {
         BD_TRY(unet_aux_init(u));
         c.st2 = u->aux_stream; c.ev_fork = u->aux_ev_fork; c.ev_join[0] = u->aux_ev_join[0]; c.ev_join[1] = u->aux_ev_join[1];
         if (seg > 0 && u->aux_defer) { c.pend[0] = u->aux_pend[0]; c.pend[1] = u->aux_pend[1]; }
@@ -1566,6 +1594,25 @@ extern "C" int bd_unet_backward_segment(bd_unet* u, int seg, int B, const float*
         if (ready_hi) *ready_hi = u->segs[seg].hi;
     }
     return BD_OK;
+}
+
+extern "C" int bd_unet_backward_segment(bd_unet* u, int seg, int B, const float* params, const float* x, int64_t ldx,
+                                        const float* dout, int64_t lddo, float* grads, void* workspace, size_t workspace_bytes,
+                                        bd_stream_t stream, int64_t* ready_lo, int64_t* ready_hi) {
+    return unet_backward_run(u, seg, B, params, x, ldx, dout, lddo, grads, true, nullptr, 0, workspace, workspace_bytes, stream, ready_lo,
+                             ready_hi);
+}
+
+extern "C" int bd_unet_backward_input(bd_unet* u, int B, const float* params, const float* x, int64_t ldx, const float* dout,
+                                      int64_t lddo, float* grads, float* dx, int64_t lddx, void* workspace, size_t workspace_bytes,
+                                      bd_stream_t stream) {
+    BD_CHECK(u, BD_ERR_INVALID, "bd_unet_backward_input: null plan");
+    BD_CHECK(dx, BD_ERR_INVALID, "bd_unet_backward_input: dx is null (bd_unet_backward is the call without an input gradient)");
+    BD_CHECK(lddx >= u->cfg.in_channels, BD_ERR_INVALID, "bd_unet_backward_input: lddx %lld < in_channels %d", (long long)lddx,
+             u->cfg.in_channels);
+    BD_CHECK(params && aligned16(params), BD_ERR_INVALID, "bd_unet_backward_input: params must be non-null and 16-byte aligned");
+    return unet_backward_run(u, -1, B, params, x, ldx, dout, lddo, grads, false, dx, lddx, workspace, workspace_bytes, stream, nullptr,
+                             nullptr);
 }
 
 extern "C" int bd_unet_backward(bd_unet* u, int B, const float* params, const float* x, int64_t ldx, const float* dout,

@@ -52,7 +52,9 @@ _SUPPORTED_UP = ("UpBlock2D", "AttnUpBlock2D")
 
 
 class _UNetFn(torch.autograd.Function):
-    """Whole-network autograd node: forward = bd_unet_forward(training), backward = bd_unet_backward."""
+    """Whole-network autograd node: forward = bd_unet_forward(training); backward follows ctx.needs_input_grad: weights only ->
+    bd_unet_backward (unchanged), input only -> bd_unet_backward_input's data-gradient-only schedule (no weight gradient is
+    computed), both -> bd_unet_backward_input with both outputs."""
 
     @staticmethod
     def forward(ctx, flat, x_nhwc, t, model):
@@ -66,10 +68,15 @@ class _UNetFn(torch.autograd.Function):
     def backward(ctx, dout):
         flat, x_nhwc = ctx.saved_tensors
         model = ctx.model
-        grads = model._run_backward(flat, x_nhwc, dout.contiguous(), ctx.ws)
+        need_w, need_x = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dx = None
+        if need_x:
+            grads, dx = model._run_backward_input(flat, x_nhwc, dout.contiguous(), ctx.ws, with_grads=need_w)
+        else:
+            grads = model._run_backward(flat, x_nhwc, dout.contiguous(), ctx.ws)
         model._release_ws(ctx.ws)
         ctx.ws = None
-        return grads, None, None, None
+        return grads, dx, None, None
 
 
 _LIVE = weakref.WeakSet()     # every model with a plan: ops.tune_set drops their pooled workspaces (sizes follow the knobs)
@@ -382,6 +389,21 @@ class UNet2DModel(nn.Module):
                                            L.stream()), "bd_unet_backward")
         return grads
 
+    def _run_backward_input(self, flat, x_nhwc, dout, ws, with_grads):
+        """(grads or None, dx [B,S,S,in_channels] NHWC).  with_grads=False is the data-gradient-only schedule."""
+        B = x_nhwc.shape[0]
+        grads = None
+        if with_grads:
+            grads = torch.empty(self.num_flat, device=flat.device)
+            for lo, hi in self._pads:
+                grads[lo:hi].zero_()
+        dx = torch.empty(tuple(x_nhwc.shape), device=flat.device)
+        L.check(self._lib.bd_unet_backward_input(self._plan, B, flat.data_ptr(), x_nhwc.data_ptr(), x_nhwc.shape[-1],
+                                                 dout.data_ptr(), dout.shape[-1], grads.data_ptr() if with_grads else None,
+                                                 dx.data_ptr(), dx.shape[-1], ws.data_ptr(), ws.numel(), L.stream()),
+                "bd_unet_backward_input")
+        return grads, dx
+
     def segments(self):
         """[(lo, hi)] flat-gradient ranges, in the order backward finalises them (for DP bucketing)."""
         if self._segments is None:
@@ -399,7 +421,12 @@ class UNet2DModel(nn.Module):
             raise ValueError("sample must be [B,C,H,W]")
         # logical NCHW -> physical NHWC.  A channels_last tensor (or a permuted NHWC buffer) is already NHWC.
         perm = sample.permute(0, 2, 3, 1)
-        x_nhwc = perm if perm.is_contiguous() else ops.nchw_to_nhwc(sample.float())
+        if perm.is_contiguous():
+            x_nhwc = perm
+        elif sample.requires_grad and torch.is_grad_enabled():
+            x_nhwc = perm.float().contiguous()      # torch ops: the input gradient flows back to the caller's NCHW tensor
+        else:
+            x_nhwc = ops.nchw_to_nhwc(sample.float())
         if x_nhwc.dtype != torch.float32:
             x_nhwc = x_nhwc.float()
         if not torch.is_tensor(timestep):
@@ -417,8 +444,6 @@ class UNet2DModel(nn.Module):
         B = x_nhwc.shape[0]
         need_grad = torch.is_grad_enabled() and (self.flat.requires_grad or x_nhwc.requires_grad)
         if need_grad:
-            if x_nhwc.requires_grad:
-                raise NotImplementedError("gradient w.r.t. the UNet input is not provided (the reference never needs it)")
             out = _UNetFn.apply(self.flat, x_nhwc, t, self)
         else:
             out = self._forward_chunked(x_nhwc, t, self.effective_chunk(B))

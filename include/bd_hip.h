@@ -176,7 +176,9 @@ typedef struct {
     const float* mean; const float* rstd;
     const float* dy; int64_t lddy;          /* grad wrt the (activated) output                 */
     float* dx; int64_t lddx; int accumulate_dx;  /* dx (+)= ...                                */
-    float* dgamma; float* dbeta;            /* [C], written (not accumulated)                  */
+    float* dgamma; float* dbeta;            /* [C], written (not accumulated); both NULL together with a NULL
+                                               param_partials: no parameter gradient is computed or written
+                                               (dx is the same launch, bit for bit)               */
     void* workspace; size_t workspace_bytes;
     float* dx_colsum; int64_t ld_colsum;    /* optional [B, C] (row stride ld_colsum): per-sample sum
                                                over pixels of the written dx (needs accumulate_dx=0);
@@ -488,6 +490,17 @@ int bd_unet_forward(bd_unet* u, int B, int training, const float* params, const 
 int bd_unet_backward(bd_unet* u, int B, const float* params, const float* x, int64_t ldx,
                      const float* dout, int64_t lddo, float* grads, void* workspace, size_t workspace_bytes,
                      bd_stream_t stream);
+/* bd_unet_backward that also writes the gradient with respect to the network input x: dx [B, S, S, in_channels] NHWC with row
+ * stride lddx >= in_channels (every element written, never accumulated).
+ *   grads != NULL: the ordinary backward plus dx; grads is bit-identical to bd_unet_backward's for the same inputs.
+ *   grads == NULL: the DATA-GRADIENT-ONLY schedule (frozen weights: trigger inversion, adversarial probes, guidance).  No weight, bias
+ *                  or GroupNorm-parameter gradient is computed or written, nothing is put on the plan's side stream, and the
+ *                  time-embedding backward (the timestep is not differentiable: that branch feeds weights only) is skipped.
+ * dx is bit-identical between the two schedules (same kernels in the same order on the caller's stream).  Same workspace contract as
+ * bd_unet_backward: bd_unet_workspace_bytes(u, B, 1), after a training forward with that workspace and the same x. */
+int bd_unet_backward_input(bd_unet* u, int B, const float* params, const float* x, int64_t ldx,
+                           const float* dout, int64_t lddo, float* grads, float* dx, int64_t lddx,
+                           void* workspace, size_t workspace_bytes, bd_stream_t stream);
 /* backward split in `bd_unet_num_segments` contiguous-in-time segments so the caller can overlap a
  * gradient all-reduce with the rest of backward: after segment s, grads in
  * [seg_lo[s], seg_hi[s]) (elements) are final. */
