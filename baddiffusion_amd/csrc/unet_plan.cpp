@@ -12,6 +12,10 @@
 //    contiguous => one GEMM; Adam + clip are single launches; DP all-reduce buckets are plain ranges);
 //  * every parameter receives exactly one gradient contribution => grads are written, never accumulated;
 //  * forward and backward are fixed launch sequences on one stream: hipGraph-capturable, no host sync.
+//
+// Layout of this file: node builders (node_*) name parameters, buffers and the order of launches; what follows from a kernel-path choice
+// (descriptor type, operand format, weight copy, workspace, stream, dry-run accounting) lives in the run-time helpers of struct bd_unet
+// (conv3_fwd / conv3_dgrad / conv3_wgrad over a Conv3 record, gn_fwd / gn_bwd, grad_planes, need, take_ginit) and is written once.
 #include "common.h"
 
 #include <functional>
@@ -119,6 +123,23 @@ struct Ctx {
     }
 };
 
+// one 3x3 convolution of the plan, built with its node (bd_unet::conv3_fwd / conv3_dgrad / conv3_wgrad)
+struct Conv3 {
+    int64_t pw, pb;               // weight [Cout][3][3][Cin] and bias in the flat parameter / gradient buffers
+    int Cin, Cout, Hs, Ws;        // source grid
+    int stride, pad, ups;         // ups: the source is nearest-upsampled x2 first (Upsample2D)
+    int Ho, Wo;
+};
+static Conv3 conv3_same(int64_t pw, int64_t pb, int Cin, int Cout, int H, int W) { return Conv3{pw, pb, Cin, Cout, H, W, 1, 1, 0, H, W}; }
+// an activation or gradient operand: fp32 [rows, ld] for the literal family, split planes [rows, ld] (ld = channels) for the plane family
+struct Opnd { const float* p; int64_t ld; };
+struct Conv3Epi {       // forward epilogue terms: y = out_scale * (conv + bias + rowbias + residual)
+    const float* rowbias = nullptr; int64_t ld_rowbias = 0;     // [B, Cout] per sample (time embedding)
+    const float* residual = nullptr; int64_t ldr = 0;
+    float out_scale = 1.f;
+    int gn_splits = 0;  // plane family: > 0 leaves the partial statistics of the GroupNorm that reads y next in the op workspace
+};
+
 typedef std::function<int(Ctx&)> Step;
 
 }  // namespace bd
@@ -158,9 +179,10 @@ struct bd_unet {
     // to dL/dT in backward, and if that node ends with a GroupNorm backward (resnet norm1, attention group_norm, conv_norm_out) the kernel
     // writes the planes of the final value next to the fp32 store (bd_gn_bwd_desc.dx_split + channel range): the producer's bd_split_rows
     // launch and its 4 B / element read disappear.  Consumers that end otherwise (down- / upsample data gradients) leave the fallback.
-    struct GSplit { int buf, coff, C, H, W; int b_pl; std::function<bool(const Ctx&)> want; bool claimed = false, emitted = false; };
+    // `want`: the producer's path predicate for a batch size (shape part; a context adds planes(c))
+    struct GSplit { int buf, coff, C, H, W; int b_pl; std::function<bool(int)> want; bool claimed = false, emitted = false; };
     std::vector<GSplit> gsplits;
-    int reg_gsplit(const View& y, std::function<bool(const Ctx&)> want) {
+    int reg_gsplit(const View& y, std::function<bool(int)> want) {
         static const bool off = getenv("BD_GSPLIT") && atoi(getenv("BD_GSPLIT")) == 0;      // (A/B knob)
         if (off || y.buf < 0 || y.C % 32 != 0) return -1;
         GSplit e; e.buf = y.buf; e.coff = y.coff; e.C = y.C; e.H = y.H; e.W = y.W; e.want = std::move(want);
@@ -169,10 +191,7 @@ struct bd_unet {
         cur_group = keep;
         gsplits.push_back(std::move(e));
         const int idx = (int)gsplits.size() - 1;
-        bufs[gsplits[idx].b_pl].live = [this, idx](int B, int training) {
-            Ctx q; q.dry = true; q.B = q.LB = B;
-            return training && gsplits[idx].emitted && gsplits[idx].want(q);
-        };
+        bufs[gsplits[idx].b_pl].live = [this, idx](int B, int training) { return training && gsplits[idx].emitted && gsplits[idx].want(B); };
         return idx;
     }
     // called by every node for its input view, in forward order: the first consumer of a registered tensor; `emits`: it can write the planes
@@ -276,24 +295,32 @@ struct bd_unet {
         c.pend[p] = true; c.launched = false;
         return BD_OK;
     }
+    // the op workspace is sized by the dry run: the maximum over every launch of the plan
+    static void need(Ctx& c, size_t bytes) { if (bytes > c.opws_need) c.opws_need = bytes; }
+    static void note_conv(Ctx& c) { need(c, bd_conv3x3_workspace_bytes(0, 0, 0, 0, 0, 0, 0, 0)); }
+    // the first gradient contribution to a value buffer is written, every later one accumulates: returns the flag and sets it
+    static int take_ginit(Ctx& c, int buf) {
+        const int acc = c.ginit[buf];
+        c.ginit[buf] = 1;
+        return acc;
+    }
+    // the batch the workspace is laid out for (the forward's half-batch pipelines and the backward must agree on every path choice)
+    static int lay_batch(const Ctx& c) { return c.LB > 0 ? c.LB : c.B; }
+    // the split-plane kernels need the per-step plane copy of the weights (the dry run only sizes the workspace)
+    static bool planes(const Ctx& c) { return c.dry || c.w_split; }
+    static uint16_t* U16(float* p) { return reinterpret_cast<uint16_t*>(p); }
+    static const uint16_t* U16(const float* p) { return reinterpret_cast<const uint16_t*>(p); }
+
     int igemm(Ctx& c, bd_igemm_desc& g) const {
         g.workspace = c.opws; g.workspace_bytes = c.opws_bytes; g.mode = cfg.compute_mode;
-        if (c.dry) {
-            size_t n = igemm_workspace_bytes(g);
-            if (n > c.opws_need) c.opws_need = n;
-            return BD_OK;
-        }
+        if (c.dry) { need(c, igemm_workspace_bytes(g)); return BD_OK; }
         return igemm_launch(g, c.st);
     }
     // GEMM on split planes (gemm_sp.hip); aux: a weight gradient, on the side stream
     int gemm_s(Ctx& c, bd_gemm_sp_desc& g, bool aux = false) const {
         if (aux && !c.wg) return BD_OK;
         g.workspace_bytes = c.opws_bytes; g.mode = cfg.compute_mode;
-        if (c.dry) {
-            const size_t n = gemm_sp_workspace_bytes(g);
-            if (n > c.opws_need) c.opws_need = n;
-            return BD_OK;
-        }
+        if (c.dry) { need(c, gemm_sp_workspace_bytes(g)); return BD_OK; }
         // (the attention block's weight gradients on the main stream measured +0.35 ms per step)
         if (aux) return on_aux(c, [&](hipStream_t st, char* ws) { g.workspace = ws; return gemm_sp(g, st); });
         g.workspace = c.opws;
@@ -347,111 +374,168 @@ struct bd_unet {
         if (db2) BD_TRY(colsum(c, s, N, c.B, N, c.B, db2, N));
         return BD_OK;
     }
-    int gn_fwd(Ctx& c, const View& x, int64_t pg, int64_t pb, float* y, int64_t ldy, int stats_buf, int silu) const {
-        bd_gn_fwd_desc d = {};
-        d.B = c.B; d.HW = x.H * x.W; d.C = x.C; d.G = cfg.norm_num_groups; d.eps = cfg.norm_eps; d.silu = silu;
-        d.x = VP(c, x); d.ldx = x.ld; d.gamma = c.params + pg; d.beta = c.params + pb; d.y = y; d.ldy = ldy;
-        d.mean = MEANP(c, stats_buf, d.G); d.rstd = RSTDP(c, stats_buf, d.G);
-        d.workspace = c.opws; d.workspace_bytes = c.opws_bytes;
-        if (c.dry) {
-            size_t n = bd_gn_workspace_bytes(c.B, x.C);
-            if (n > c.opws_need) c.opws_need = n;
-            return BD_OK;
-        }
-        return bd_gn_fwd(&d, (bd_stream_t)c.st);
-    }
-    int gn_bwd(Ctx& c, const View& x, int64_t pg, int64_t pb, int stats_buf, const float* dy, int64_t lddy, int silu,
-               const float* dx_add = nullptr, int64_t ld_add = 0, int gs = -1) {
-        bd_gn_bwd_desc d = {};
-        d.dx_add = dx_add; d.ld_add = ld_add;
-        if (gs >= 0 && gsplits[gs].want(c)) {      // this launch makes dL/dx final: hand its producer the planes of its channel range
-            const GSplit& e = gsplits[gs];
-            d.dx_split = U16(BP(c, e.b_pl)); d.lddxs = e.C; d.dx_split_c0 = e.coff - x.coff; d.dx_split_c1 = d.dx_split_c0 + e.C;
-        }
-        d.B = c.B; d.HW = x.H * x.W; d.C = x.C; d.G = cfg.norm_num_groups; d.silu = silu;
-        d.x = VP(c, x); d.ldx = x.ld; d.gamma = c.params + pg; d.beta = c.params + pb;
-        d.mean = MEANP(c, stats_buf, d.G); d.rstd = RSTDP(c, stats_buf, d.G);
-        d.dy = dy; d.lddy = lddy; d.dx = GP(c, x); d.lddx = x.ld;
-        d.accumulate_dx = c.ginit[x.buf];
-        c.ginit[x.buf] = 1;
-        if (c.wg) { d.dgamma = c.grads + pg; d.dbeta = c.grads + pb; }      // (else: bd_gn_bwd leaves the parameter sums out)
-        d.workspace = c.opws; d.workspace_bytes = c.opws_bytes;
-        d.param_partials = c.gn_slot(d.B, d.HW, d.C, d.G, d.dgamma, d.dbeta);
-        if (c.dry) return BD_OK;
-        return bd_gn_bwd(&d, (bd_stream_t)c.st);
-    }
     int add(Ctx& c, const float* src, int64_t lds, float* dst, int64_t ldd, int64_t nrows, int C, float scale, int acc) const {
         if (c.dry) return BD_OK;
         return add_launch(src, lds, dst, ldd, nrows, C, scale, acc, c.st);
-    }
-    int conv_f(Ctx& c, bd_conv3x3_fwd_desc& d) const {
-        d.workspace = c.opws; d.workspace_bytes = c.opws_bytes; d.mode = cfg.compute_mode;
-        if (c.w_split && !c.dry) d.w_split = c.w_split + 2 * (d.w - c.params);
-        if (c.dry) { note_conv(c); return BD_OK; }
-        return conv3x3_fwd(d, c.st);
-    }
-    int conv_d(Ctx& c, bd_conv3x3_dgrad_desc& d) const {
-        d.workspace = c.opws; d.workspace_bytes = c.opws_bytes; d.mode = cfg.compute_mode;
-        if (c.w_split && !c.dry) d.w_split = c.w_split + 2 * (d.w - c.params);
-        if (c.dry) { note_conv(c); return BD_OK; }
-        return conv3x3_dgrad(d, c.st);
-    }
-    int conv_w(Ctx& c, bd_conv3x3_wgrad_desc& d) const {
-        if (!c.wg) return BD_OK;
-        d.workspace = c.opws; d.workspace_bytes = c.opws_bytes; d.mode = cfg.compute_mode;
-        if (c.dry) { note_conv(c); return BD_OK; }
-        return on_aux(c, [&](hipStream_t st, char* ws) { d.workspace = ws; return conv3x3_wgrad(d, st); });
-    }
-    // pre-split / LDS-DMA convolution (conv_ps.hip) for the stride-1 3x3 convs whose operands the producers can emit as
-    // split planes: the bf16 modes only (same arithmetic as igemm, bit-identical), shapes per conv3x3_ps_supported
-    // One decision per convolution, for its forward, data gradient and weight gradient alike (they share the split
-    // operands), taken on the batch the workspace is laid out for (c.LB: the forward's half-batch pipelines and the
-    // backward must agree).
-    bool ps_ok(const Ctx& c, int H, int W, int Cin, int Cout) const {
-        static const bool off = getenv("BD_CONV_PS") && atoi(getenv("BD_CONV_PS")) == 0;
-        const int B = c.LB > 0 ? c.LB : c.B;
-        return !off && mode_bf16(cfg.compute_mode) && (c.dry || c.w_split) && conv3x3_ps_supported(B, H, W, Cin, Cout) &&
-               conv3x3_ps_supported(B, H, W, Cout, Cin) && conv3x3_ps_wgrad_supported(B, H, W, Cin, Cout);
-    }
-    // phase-decomposed forms (conv_ph.hip): the upsample convolution on its SOURCE grid, the stride-2 data gradient by parity class
-    // `min_wgs`: the launch must offer at least that many 256 x 128 workgroups (classes x tiles on the batch the workspace is laid
-    // out for) -- a one-class 16-tap data gradient of an 8 x 8 source grid is 64 long workgroups on 256 CUs and loses to the literal form
-    bool phase_ok(const Ctx& c, int H, int W, int Cin, int Cout, int classes = 4, int min_wgs = 128) const {
-        const int B = c.LB > 0 ? c.LB : c.B;
-        const long long wgs = (long long)classes * (((long long)B * H * W + 255) / 256) * (Cout / 128);
-        return mode_bf16(cfg.compute_mode) && (c.dry || c.w_split) && upsample_conv_ps_supported(B, H, W, Cin, Cout) && wgs >= min_wgs;
-    }
-    int conv_pw(Ctx& c, bd_conv3x3_ps_wgrad_desc& d) const {
-        if (!c.wg) return BD_OK;
-        d.workspace_bytes = c.opws_bytes; d.mode = cfg.compute_mode;
-        if (c.dry) {
-            note_conv(c);
-            const size_t n = conv3x3_ps_wgrad_workspace_bytes(d);      // K-split slabs of this layer (grow with the tile of the shared-tap form)
-            if (n > c.opws_need) c.opws_need = n;
-            return BD_OK;
-        }
-        // every weight gradient runs on the side stream: keeping the large layers' (they fill the chip on their own) or the 4 x 4 / 8 x 8
-        // layers' (10-30 us launches, as long as the fork / join) on the main stream measured 0.2 - 0.7 ms per step slower
-        return on_aux(c, [&](hipStream_t st, char* ws) { d.workspace = ws; return conv3x3_ps_wgrad(d, st); });
-    }
-    static uint16_t* U16(float* p) { return reinterpret_cast<uint16_t*>(p); }
-    int conv_p(Ctx& c, bd_conv3x3_ps_desc& d) const {
-        d.workspace = c.opws; d.workspace_bytes = c.opws_bytes; d.mode = cfg.compute_mode;
-        if (c.dry) { note_conv(c); return BD_OK; }
-        return conv3x3_ps(d, c.st);
     }
     int split_rows(Ctx& c, const float* src, int64_t ld, int64_t nrows, int C, float* dst) const {
         if (c.dry) return BD_OK;
         return bd_split_rows(src, ld, nrows, C, U16(dst), C, (bd_stream_t)c.st);
     }
-    static void note_conv(Ctx& c) {
-        size_t n = bd_conv3x3_workspace_bytes(0, 0, 0, 0, 0, 0, 0, 0);
-        if (n > c.opws_need) c.opws_need = n;
+
+    // ---- GroupNorm (+SiLU).  x is a View (forward / backward into its gradient buffer) or, for a tensor without a persistent gradient
+    // buffer (the resnet's h1), the View of its value and a destination the caller names
+    // planes: y receives split planes [rows, x.C] ONLY (the operand of the plane kernels that read it next) instead of fp32 [rows, ldy]
+    // stats_splits > 0: the producing convolution left the statistics' partials in the op workspace (Conv3Epi::gn_splits): no pass over x
+    int gn_fwd(Ctx& c, const View& x, int64_t pg, int64_t pb, float* y, int64_t ldy, int stats_buf, int silu, bool planes = false,
+               int stats_splits = 0) const {
+        bd_gn_fwd_desc d = {};
+        d.B = c.B; d.HW = x.H * x.W; d.C = x.C; d.G = cfg.norm_num_groups; d.eps = cfg.norm_eps; d.silu = silu;
+        d.x = VP(c, x); d.ldx = x.ld; d.gamma = c.params + pg; d.beta = c.params + pb;
+        if (planes) { d.y = nullptr; d.ldy = x.C; d.y_split = U16(y); d.ldys = x.C; }
+        else { d.y = y; d.ldy = ldy; }
+        d.mean = MEANP(c, stats_buf, d.G); d.rstd = RSTDP(c, stats_buf, d.G);
+        d.workspace = c.opws; d.workspace_bytes = c.opws_bytes;
+        if (stats_splits > 0) { d.stats = reinterpret_cast<const double*>(c.opws); d.stats_splits = stats_splits; }
+        if (c.dry) { need(c, bd_gn_workspace_bytes(c.B, x.C)); return BD_OK; }
+        return bd_gn_fwd(&d, (bd_stream_t)c.st);
+    }
+    // `d` arrives with the destination filled in: dx / lddx / accumulate_dx and, optionally, dx_split, dx_add, dx_colsum
+    // (dx_colsum feeds a weight gradient only: dropped with the parameter sums in the data-gradient-only schedule)
+    int gn_bwd(Ctx& c, bd_gn_bwd_desc& d, const View& x, int64_t pg, int64_t pb, int stats_buf, const float* dy, int64_t lddy, int silu) const {
+        d.B = c.B; d.HW = x.H * x.W; d.C = x.C; d.G = cfg.norm_num_groups; d.silu = silu;
+        d.x = VP(c, x); d.ldx = x.ld; d.gamma = c.params + pg; d.beta = c.params + pb;
+        d.mean = MEANP(c, stats_buf, d.G); d.rstd = RSTDP(c, stats_buf, d.G);
+        d.dy = dy; d.lddy = lddy;
+        if (c.wg) { d.dgamma = c.grads + pg; d.dbeta = c.grads + pb; }      // (else: bd_gn_bwd leaves the parameter sums out)
+        else { d.dx_colsum = nullptr; d.ld_colsum = 0; }
+        d.workspace = c.opws; d.workspace_bytes = c.opws_bytes;
+        d.param_partials = c.gn_slot(d.B, d.HW, d.C, d.G, d.dgamma, d.dbeta);
+        if (c.dry) return BD_OK;
+        return bd_gn_bwd(&d, (bd_stream_t)c.st);
+    }
+    // ... into x's gradient buffer (+ dx_add, a second gradient of x folded into the store); gs: the GSplit entry this launch can serve
+    int gn_bwd(Ctx& c, const View& x, int64_t pg, int64_t pb, int stats_buf, const float* dy, int64_t lddy, int silu,
+               const float* dx_add = nullptr, int64_t ld_add = 0, int gs = -1) const {
+        bd_gn_bwd_desc d = {};
+        d.dx_add = dx_add; d.ld_add = ld_add;
+        if (gs >= 0 && planes(c) && gsplits[gs].want(lay_batch(c))) {      // this launch makes dL/dx final: hand its producer the planes of its channel range
+            const GSplit& e = gsplits[gs];
+            d.dx_split = U16(BP(c, e.b_pl)); d.lddxs = e.C; d.dx_split_c0 = e.coff - x.coff; d.dx_split_c1 = d.dx_split_c0 + e.C;
+        }
+        d.dx = GP(c, x); d.lddx = x.ld; d.accumulate_dx = take_ginit(c, x.buf);
+        return gn_bwd(c, d, x, pg, pb, stats_buf, dy, lddy, silu);
+    }
+
+    // ---- 3x3 convolutions.  Two kernel families: the literal implicit GEMM on fp32 operands (conv.cpp; any stride / padding / folded
+    // nearest-upsampling) and the split-plane LDS-DMA kernels of conv_ps.hip (stride 1, pad 1, on the OUTPUT grid; the bf16 modes only, same
+    // arithmetic as igemm, bit-identical).  A node takes ONE decision per convolution and step (ps_ok), for its forward, data gradient and
+    // weight gradient alike -- they share the split operands -- and hands it to the three helpers below with operands in that family's
+    // format; everything that follows from the decision (descriptor, weight copy, workspace, stream, dry-run accounting) lives in them.
+    template <class D>
+    static void conv3_geometry(D& d, const Ctx& c, const Conv3& k) {
+        d.B = c.B; d.Hs = k.Hs; d.Ws = k.Ws; d.Cin = k.Cin; d.Cout = k.Cout; d.stride = k.stride; d.pad_t = k.pad; d.pad_l = k.pad; d.ups = k.ups;
+        d.Ho = k.Ho; d.Wo = k.Wo;
+    }
+    // One decision per convolution, for its forward, data gradient and weight gradient alike, taken on the batch the workspace is laid
+    // out for; shapes per conv3x3_ps_supported
+    bool ps_shape(int B, int H, int W, int Cin, int Cout) const {
+        static const bool off = getenv("BD_CONV_PS") && atoi(getenv("BD_CONV_PS")) == 0;
+        return !off && mode_bf16(cfg.compute_mode) && conv3x3_ps_supported(B, H, W, Cin, Cout) && conv3x3_ps_supported(B, H, W, Cout, Cin) &&
+               conv3x3_ps_wgrad_supported(B, H, W, Cin, Cout);
+    }
+    bool ps_ok(const Ctx& c, int H, int W, int Cin, int Cout) const { return planes(c) && ps_shape(lay_batch(c), H, W, Cin, Cout); }
+    // phase-decomposed forms (conv_ph.hip): the upsample convolution on its SOURCE grid, the stride-2 data gradient by parity class
+    // `min_wgs`: the launch must offer at least that many 256 x 128 workgroups (classes x tiles on the batch the workspace is laid
+    // out for) -- a one-class 16-tap data gradient of an 8 x 8 source grid is 64 long workgroups on 256 CUs and loses to the literal form
+    bool phase_shape(int B, int H, int W, int Cin, int Cout, int classes = 4, int min_wgs = 128) const {
+        const long long wgs = (long long)classes * (((long long)B * H * W + 255) / 256) * (Cout / 128);
+        return mode_bf16(cfg.compute_mode) && upsample_conv_ps_supported(B, H, W, Cin, Cout) && wgs >= min_wgs;
+    }
+    bool phase_ok(const Ctx& c, int H, int W, int Cin, int Cout, int classes = 4, int min_wgs = 128) const {
+        return planes(c) && phase_shape(lay_batch(c), H, W, Cin, Cout, classes, min_wgs);
+    }
+    // the plane kernel in either direction: +1 forward (W planes of the per-step split copy), -1 data gradient (transposed planes)
+    int conv3_planes(Ctx& c, const Conv3& k, int direction, const Opnd& x, float* y, int64_t ldy, int acc, const Conv3Epi& e) const {
+        bd_conv3x3_ps_desc d = {};
+        d.B = c.B; d.H = k.Ho; d.W = k.Wo; d.direction = direction;
+        d.K = direction > 0 ? k.Cin : k.Cout; d.N = direction > 0 ? k.Cout : k.Cin;
+        d.x_split = U16(x.p); d.ldx = x.ld; d.w_split = (direction > 0 ? c.w_split : c.wT_split) + 2 * k.pw;
+        if (direction > 0) d.bias = c.params + k.pb;
+        d.rowbias = e.rowbias; d.ld_rowbias = e.ld_rowbias; d.residual = e.residual; d.ldr = e.ldr; d.out_scale = e.out_scale;
+        d.y = y; d.ldy = ldy; d.accumulate = acc;
+        d.workspace = c.opws; d.workspace_bytes = c.opws_bytes; d.mode = cfg.compute_mode;
+        if (e.gn_splits > 0) {
+            d.gn_part = reinterpret_cast<double*>(c.opws); d.gn_groups = cfg.norm_num_groups;
+            if (c.dry) need(c, (size_t)c.B * e.gn_splits * d.gn_groups * 2 * sizeof(double));
+        }
+        if (c.dry) { note_conv(c); return BD_OK; }
+        return conv3x3_ps(d, c.st);
+    }
+    int conv3_fwd(Ctx& c, const Conv3& k, bool ps, const Opnd& x, float* y, int64_t ldy, const Conv3Epi& e = Conv3Epi()) const {
+        if (ps) return conv3_planes(c, k, 1, x, y, ldy, 0, e);
+        bd_conv3x3_fwd_desc d = {};
+        conv3_geometry(d, c, k);
+        d.x = x.p; d.ldx = x.ld; d.w = c.params + k.pw; d.bias = c.params + k.pb;
+        d.rowbias = e.rowbias; d.ld_rowbias = e.ld_rowbias; d.residual = e.residual; d.ldr = e.ldr; d.out_scale = e.out_scale;
+        d.y = y; d.ldy = ldy;
+        d.workspace = c.opws; d.workspace_bytes = c.opws_bytes; d.mode = cfg.compute_mode;
+        if (c.dry) { note_conv(c); return BD_OK; }
+        if (c.w_split) d.w_split = c.w_split + 2 * k.pw;
+        return conv3x3_fwd(d, c.st);
+    }
+    // dx (+)= data gradient, over the convolution's own (virtual, upsampled) input grid
+    int conv3_dgrad(Ctx& c, const Conv3& k, bool ps, const Opnd& dy, float* dx, int64_t lddx, int acc) const {
+        if (ps) return conv3_planes(c, k, -1, dy, dx, lddx, acc, Conv3Epi());
+        bd_conv3x3_dgrad_desc d = {};
+        conv3_geometry(d, c, k);
+        d.dy = dy.p; d.lddy = dy.ld; d.w = c.params + k.pw; d.dx = dx; d.lddx = lddx; d.accumulate = acc;
+        d.workspace = c.opws; d.workspace_bytes = c.opws_bytes; d.mode = cfg.compute_mode;
+        if (c.dry) { note_conv(c); return BD_OK; }
+        if (c.w_split) d.w_split = c.w_split + 2 * k.pw;
+        return conv3x3_dgrad(d, c.st);
+    }
+    // weight and bias gradient.  Every weight gradient runs on the side stream: keeping the large layers' (they fill the chip on their own)
+    // or the 4 x 4 / 8 x 8 layers' (10-30 us launches, as long as the fork / join) on the main stream measured 0.2 - 0.7 ms per step slower
+    // bias_scratch >= 0: a [B, Cout] scratch for a Cout the igemm row-sum fusion cannot take (conv_out, Cout = 3): the bias gradient is
+    // then column sums on the main stream, unless the direct thin kernel runs, which sums dy on the way
+    int conv3_wgrad(Ctx& c, const Conv3& k, bool ps, const Opnd& x, const Opnd& dy, int bias_scratch = -1) const {
+        if (!c.wg) return BD_OK;
+        if (ps) {
+            bd_conv3x3_ps_wgrad_desc d = {};
+            d.B = c.B; d.H = k.Ho; d.W = k.Wo; d.Cin = k.Cin; d.Cout = k.Cout;
+            d.x_split = U16(x.p); d.ldx = x.ld; d.dy_split = U16(dy.p); d.lddy = dy.ld;
+            d.dw = c.grads + k.pw; d.db = c.grads + k.pb;
+            d.workspace_bytes = c.opws_bytes; d.mode = cfg.compute_mode;
+            if (c.dry) {
+                note_conv(c);
+                need(c, conv3x3_ps_wgrad_workspace_bytes(d));      // K-split slabs of this layer (grow with the tile of the shared-tap form)
+                return BD_OK;
+            }
+            return on_aux(c, [&](hipStream_t st, char* ws) { d.workspace = ws; return conv3x3_ps_wgrad(d, st); });
+        }
+        bd_conv3x3_wgrad_desc d = {};
+        conv3_geometry(d, c, k);
+        d.x = x.p; d.ldx = x.ld; d.dy = dy.p; d.lddy = dy.ld; d.dw = c.grads + k.pw; d.db = c.grads + k.pb;
+        if (bias_scratch >= 0 && !conv3x3_wgrad_is_thin(d)) {
+            d.db = nullptr;
+            BD_TRY(bias_grad(c, dy.p, dy.ld, k.Ho * k.Wo, k.Cout, bias_scratch, c.grads + k.pb));
+        }
+        d.workspace = c.opws; d.workspace_bytes = c.opws_bytes; d.mode = cfg.compute_mode;
+        if (c.dry) { note_conv(c); return BD_OK; }
+        return on_aux(c, [&](hipStream_t st, char* ws) { d.workspace = ws; return conv3x3_wgrad(d, st); });
+    }
+    // dL/dy of a node's output [nrows, C] as split planes (GSplit): the ones y's first consumer left when it made the gradient final (run-time
+    // fact: `emitted` is set after the producer node was built), else bd_split_rows of the fp32 gradient into the node's own scratch
+    int grad_planes(Ctx& c, int gs, const float* dy, int64_t lddy, int64_t nrows, int C, int b_scratch, Opnd& out) const {
+        const bool ready = gs >= 0 && gsplits[gs].emitted;
+        float* pl = BP(c, ready ? gsplits[gs].b_pl : b_scratch);
+        if (!ready) BD_TRY(split_rows(c, dy, lddy, nrows, C, pl));
+        out = Opnd{pl, C};
+        return BD_OK;
     }
 
     // ---------------------------------------------------------------- nodes
-    struct ConvSpec { int Cin, Cout, stride, pad_t, pad_l, ups; };
-
     void build();
     void node_time_embed();
     void node_conv_in(const View& y);
@@ -506,29 +590,17 @@ void bd_unet::node_time_embed() {
 }
 
 void bd_unet::node_conv_in(const View& y) {
-    const int Cin = cfg.in_channels, Cout = y.C, S_ = cfg.sample_size;
-    const int64_t pw = add_param("conv_in.weight", {Cout, Cin, 3, 3}, 1);
-    const int64_t pb = add_param("conv_in.bias", {Cout});
-    const int b_bs = scratch(Cout);
-    F([=](Ctx& c) {
-        bd_conv3x3_fwd_desc d = {};
-        d.B = c.B; d.Hs = S_; d.Ws = S_; d.Cin = Cin; d.Cout = Cout; d.stride = 1; d.pad_t = 1; d.pad_l = 1; d.Ho = S_; d.Wo = S_;
-        d.x = c.x; d.ldx = c.ldx; d.w = c.params + pw; d.bias = c.params + pb; d.out_scale = 1.f;
-        d.y = VP(c, y); d.ldy = y.ld;
-        return conv_f(c, d);
-    });
+    const int S_ = cfg.sample_size;
+    const int64_t pw = add_param("conv_in.weight", {y.C, cfg.in_channels, 3, 3}, 1);
+    const int64_t pb = add_param("conv_in.bias", {y.C});
+    const Conv3 k = conv3_same(pw, pb, cfg.in_channels, y.C, S_, S_);
+    F([=](Ctx& c) { return conv3_fwd(c, k, false, {c.x, c.ldx}, VP(c, y), y.ld); });
     Bk([=](Ctx& c) {
-        const float* dy = GP(c, y);
-        bd_conv3x3_wgrad_desc d = {};
-        d.B = c.B; d.Hs = S_; d.Ws = S_; d.Cin = Cin; d.Cout = Cout; d.stride = 1; d.pad_t = 1; d.pad_l = 1; d.Ho = S_; d.Wo = S_;
-        d.x = c.x; d.ldx = c.ldx; d.dy = dy; d.lddy = y.ld; d.dw = c.grads + pw; d.db = c.grads + pb;
-        BD_TRY(conv_w(c, d));
+        const Opnd dy = {GP(c, y), y.ld};
+        BD_TRY(conv3_wgrad(c, k, false, {c.x, c.ldx}, dy));
         if (!c.dx && !c.dry) return (int)BD_OK;
         // the last link of the data-gradient chain: dL/dx of the network input (bd_unet_backward_input), on the main stream
-        bd_conv3x3_dgrad_desc g = {};
-        g.B = c.B; g.Hs = S_; g.Ws = S_; g.Cin = Cin; g.Cout = Cout; g.stride = 1; g.pad_t = 1; g.pad_l = 1; g.Ho = S_; g.Wo = S_;
-        g.dy = dy; g.lddy = y.ld; g.w = c.params + pw; g.dx = c.dx; g.lddx = c.lddx;
-        return conv_d(c, g);
+        return conv3_dgrad(c, k, false, dy, c.dx, c.lddx, 0);
     });
 }
 
@@ -551,9 +623,9 @@ void bd_unet::node_resnet(const std::string& pre, const View& x, const View& y, 
         }
     }
     const int b_embs_ = b_embs, T_ = T;
-    const int64_t p_tw_ = p_tw, p_tb_ = p_tb;
     const int64_t pn2w = add_param(pre + "norm2.weight", {Cout}), pn2b = add_param(pre + "norm2.bias", {Cout});
     const int64_t pc2w = add_param(pre + "conv2.weight", {Cout, Cout, 3, 3}, 1), pc2b = add_param(pre + "conv2.bias", {Cout});
+    const Conv3 k1 = conv3_same(pc1w, pc1b, Cin, Cout, H, W), k2 = conv3_same(pc2w, pc2b, Cout, Cout, H, W);
     int64_t psw = -1, psb = -1;
     if (shortcut) {
         psw = add_param(pre + "conv_shortcut.weight", {Cout, Cin, 1, 1}, 1);
@@ -572,7 +644,7 @@ void bd_unet::node_resnet(const std::string& pre, const View& x, const View& y, 
     View h1v; h1v.buf = b_h1; h1v.coff = 0; h1v.C = Cout; h1v.ld = Cout; h1v.H = H; h1v.W = W;
     bufs[b_h1].gbuf = -1;
     const int b_dys = scale != 1.f ? scratch((int64_t)HW * Cout) : -1;
-    const int b_bs = scratch(Cout), b_da2 = scratch((int64_t)HW * Cout), b_dh1 = scratch((int64_t)HW * Cout);
+    const int b_da2 = scratch((int64_t)HW * Cout), b_dh1 = scratch((int64_t)HW * Cout);
     const int b_da1 = scratch((int64_t)HW * Cin);
     // backward operands of the LDS-DMA data gradients: dy / dh1 as split planes, transposed weight planes
     const int b_dyS = scratch((int64_t)HW * Cout), b_dh1S = scratch((int64_t)HW * Cout);
@@ -581,169 +653,75 @@ void bd_unet::node_resnet(const std::string& pre, const View& x, const View& y, 
     // dL/dx becomes final in this node's norm1 backward (first consumer of x in forward order); dL/dy arrives ready-split when y's first
     // consumer can do the same for us (GSplit)
     const int gs_in = claim_gsplit(x, true);
-    const int gs_out = b_dys < 0 ? reg_gsplit(y, [this, H, W, Cout](const Ctx& c) { return ps_ok(c, H, W, Cout, Cout); }) : -1;
+    const int gs_out = b_dys < 0 ? reg_gsplit(y, [this, H, W, Cout](int B) { return ps_shape(B, H, W, Cout, Cout); }) : -1;
 
     F([=](Ctx& c) {
         const bool ps1 = ps_ok(c, H, W, Cin, Cout), ps2 = ps_ok(c, H, W, Cout, Cout);
-        int st2 = 0;          // pixel splits of the norm2 partials conv1's epilogue leaves in the op workspace (0: none)
-        if (ps1) {
-            bd_gn_fwd_desc g = {};
-            g.B = c.B; g.HW = HW; g.C = Cin; g.G = G; g.eps = cfg.norm_eps; g.silu = 1;
-            g.x = VP(c, x); g.ldx = x.ld; g.gamma = c.params + pn1w; g.beta = c.params + pn1b;
-            g.y = nullptr; g.ldy = Cin;     // split planes only: conv1 fwd and (a1s is a value buffer) its weight gradient read them
-            g.y_split = U16(BP(c, b_a1s)); g.ldys = Cin;
-            g.mean = MEANP(c, b_st1, G); g.rstd = RSTDP(c, b_st1, G);
-            g.workspace = c.opws; g.workspace_bytes = c.opws_bytes;
-            if (!c.dry) BD_TRY(bd_gn_fwd(&g, (bd_stream_t)c.st));
-            bd_conv3x3_ps_desc d = {};
-            d.B = c.B; d.H = H; d.W = W; d.K = Cin; d.N = Cout; d.direction = 1;
-            d.x_split = U16(BP(c, b_a1s)); d.ldx = Cin; d.w_split = c.w_split + 2 * pc1w;
-            d.bias = c.params + pc1b; d.rowbias = BP(c, b_tproj) + toff; d.ld_rowbias = sumC_; d.out_scale = 1.f;
-            d.y = BP(c, b_h1); d.ldy = Cout;
-            // round 4: norm2's statistics from this epilogue when norm2 would otherwise make a pass over h1 for them (large images)
-            st2 = ps2 && bd_gn_fwd_takes_stats(c.B, HW, Cout, G) ? bd_conv3x3_ps_gn_splits(c.B, H, W, Cin, Cout, G) : 0;
-            if (st2 > 0) {
-                d.gn_part = reinterpret_cast<double*>(c.opws); d.gn_groups = G;
-                const size_t n = (size_t)c.B * st2 * G * 2 * sizeof(double);
-                if (c.dry && n > c.opws_need) c.opws_need = n;
-            }
-            BD_TRY(conv_p(c, d));
-        } else {
-            BD_TRY(gn_fwd(c, x, pn1w, pn1b, BP(c, b_a1), Cin, b_st1, 1));
-            bd_conv3x3_fwd_desc d = {};
-            d.B = c.B; d.Hs = H; d.Ws = W; d.Cin = Cin; d.Cout = Cout; d.stride = 1; d.pad_t = 1; d.pad_l = 1; d.Ho = H; d.Wo = W;
-            d.x = BP(c, b_a1); d.ldx = Cin; d.w = c.params + pc1w; d.bias = c.params + pc1b;
-            d.rowbias = BP(c, b_tproj) + toff; d.ld_rowbias = sumC_; d.out_scale = 1.f;
-            d.y = BP(c, b_h1); d.ldy = Cout;
-            BD_TRY(conv_f(c, d));
-        }
-        if (ps2) {
-            bd_gn_fwd_desc g = {};
-            g.B = c.B; g.HW = HW; g.C = Cout; g.G = G; g.eps = cfg.norm_eps; g.silu = 1;
-            g.x = BP(c, b_h1); g.ldx = Cout; g.gamma = c.params + pn2w; g.beta = c.params + pn2b;
-            g.y = nullptr; g.ldy = Cout;
-            g.y_split = U16(BP(c, b_a2s)); g.ldys = Cout;
-            g.mean = MEANP(c, b_st2, G); g.rstd = RSTDP(c, b_st2, G);
-            g.workspace = c.opws; g.workspace_bytes = c.opws_bytes;
-            if (st2 > 0) { g.stats = reinterpret_cast<const double*>(c.opws); g.stats_splits = st2; }
-            if (!c.dry) BD_TRY(bd_gn_fwd(&g, (bd_stream_t)c.st));
-        } else {
-            BD_TRY(gn_fwd(c, h1v, pn2w, pn2b, BP(c, b_a2), Cout, b_st2, 1));
-        }
-        const float* res = VP(c, x); int64_t ldr = x.ld;
+        // a1 / a2 in the format their convolution reads (planes: conv1 / conv2 forward and, they are value buffers, the weight gradients)
+        float* a1 = BP(c, ps1 ? b_a1s : b_a1);
+        float* a2 = BP(c, ps2 ? b_a2s : b_a2);
+        BD_TRY(gn_fwd(c, x, pn1w, pn1b, a1, Cin, b_st1, 1, ps1));
+        Conv3Epi e1;
+        e1.rowbias = BP(c, b_tproj) + toff; e1.ld_rowbias = sumC_;
+        // round 4: norm2's statistics from conv1's epilogue when norm2 would otherwise make a pass over h1 for them (large images)
+        if (ps1 && ps2 && bd_gn_fwd_takes_stats(c.B, HW, Cout, G)) e1.gn_splits = bd_conv3x3_ps_gn_splits(c.B, H, W, Cin, Cout, G);
+        BD_TRY(conv3_fwd(c, k1, ps1, {a1, Cin}, BP(c, b_h1), Cout, e1));
+        BD_TRY(gn_fwd(c, h1v, pn2w, pn2b, a2, Cout, b_st2, 1, ps2, e1.gn_splits));
+        Conv3Epi e2;
+        e2.residual = VP(c, x); e2.ldr = x.ld; e2.out_scale = inv;
         if (shortcut) {
             BD_TRY(linear_fwd(c, VP(c, x), x.ld, c.params + psw, c.params + psb, VP(c, y), y.ld, (int)rows(c, x), Cout, Cin));
-            res = VP(c, y); ldr = y.ld;
+            e2.residual = VP(c, y); e2.ldr = y.ld;
         }
-        if (ps2) {
-            bd_conv3x3_ps_desc e = {};
-            e.B = c.B; e.H = H; e.W = W; e.K = Cout; e.N = Cout; e.direction = 1;
-            e.x_split = U16(BP(c, b_a2s)); e.ldx = Cout; e.w_split = c.w_split + 2 * pc2w;
-            e.bias = c.params + pc2b; e.residual = res; e.ldr = ldr; e.out_scale = inv;
-            e.y = VP(c, y); e.ldy = y.ld;
-            return conv_p(c, e);
-        }
-        bd_conv3x3_fwd_desc e = {};
-        e.B = c.B; e.Hs = H; e.Ws = W; e.Cin = Cout; e.Cout = Cout; e.stride = 1; e.pad_t = 1; e.pad_l = 1; e.Ho = H; e.Wo = W;
-        e.x = BP(c, b_a2); e.ldx = Cout; e.w = c.params + pc2w; e.bias = c.params + pc2b;
-        e.residual = res; e.ldr = ldr; e.out_scale = inv;
-        e.y = VP(c, y); e.ldy = y.ld;
-        return conv_f(c, e);
+        return conv3_fwd(c, k2, ps2, {a2, Cout}, VP(c, y), y.ld, e2);
     });
     Bk([=](Ctx& c) {
         const int M = (int)rows(c, x);
-        const float* dy = GP(c, y); int64_t lddy = y.ld;
+        Opnd dy = {GP(c, y), y.ld};
         if (b_dys >= 0) {
-            BD_TRY(add(c, dy, lddy, BP(c, b_dys), Cout, M, Cout, inv, 0));
-            dy = BP(c, b_dys); lddy = Cout;
+            BD_TRY(add(c, dy.p, dy.ld, BP(c, b_dys), Cout, M, Cout, inv, 0));
+            dy = {BP(c, b_dys), Cout};
         }
         const bool ps1 = ps_ok(c, H, W, Cin, Cout), ps2 = ps_ok(c, H, W, Cout, Cout);
-        if (ps2) {
-            const bool ready = gs_out >= 0 && gsplits[gs_out].emitted;      // y's consumer left the planes of dL/dy (run-time: set after this node was built)
-            float* dyS = ready ? BP(c, gsplits[gs_out].b_pl) : BP(c, b_dyS);
-            if (!ready) BD_TRY(split_rows(c, dy, lddy, M, Cout, dyS));
-            bd_conv3x3_ps_wgrad_desc w2 = {};
-            w2.B = c.B; w2.H = H; w2.W = W; w2.Cin = Cout; w2.Cout = Cout;
-            w2.x_split = U16(BP(c, b_a2s)); w2.ldx = Cout; w2.dy_split = U16(dyS); w2.lddy = Cout;
-            w2.dw = c.grads + pc2w; w2.db = c.grads + pc2b;
-            BD_TRY(conv_pw(c, w2));
-            bd_conv3x3_ps_desc g2 = {};
-            g2.B = c.B; g2.H = H; g2.W = W; g2.K = Cout; g2.N = Cout; g2.direction = -1;
-            g2.x_split = U16(dyS); g2.ldx = Cout; g2.w_split = c.wT_split + 2 * pc2w; g2.out_scale = 1.f;
-            g2.y = BP(c, b_da2); g2.ldy = Cout;
-            BD_TRY(conv_p(c, g2));
-        } else {
-            bd_conv3x3_wgrad_desc w2 = {};
-            w2.B = c.B; w2.Hs = H; w2.Ws = W; w2.Cin = Cout; w2.Cout = Cout; w2.stride = 1; w2.pad_t = 1; w2.pad_l = 1; w2.Ho = H; w2.Wo = W;
-            w2.x = BP(c, b_a2); w2.ldx = Cout; w2.dy = dy; w2.lddy = lddy; w2.dw = c.grads + pc2w; w2.db = c.grads + pc2b;
-            BD_TRY(conv_w(c, w2));
-            bd_conv3x3_dgrad_desc g2 = {};
-            g2.B = c.B; g2.Hs = H; g2.Ws = W; g2.Cin = Cout; g2.Cout = Cout; g2.stride = 1; g2.pad_t = 1; g2.pad_l = 1; g2.Ho = H; g2.Wo = W;
-            g2.dy = dy; g2.lddy = lddy; g2.w = c.params + pc2w; g2.dx = BP(c, b_da2); g2.lddx = Cout;
-            BD_TRY(conv_d(c, g2));
-        }
-        {   // norm2 backward: dh1 = gn_silu_bwd(h1, da2)   (h1 has no persistent grad buffer: write to scratch)
+        Opnd dy2 = dy;      // dL/dy as conv2's family reads it
+        if (ps2) BD_TRY(grad_planes(c, gs_out, dy.p, dy.ld, M, Cout, b_dyS, dy2));
+        BD_TRY(conv3_wgrad(c, k2, ps2, {BP(c, ps2 ? b_a2s : b_a2), Cout}, dy2));
+        BD_TRY(conv3_dgrad(c, k2, ps2, dy2, BP(c, b_da2), Cout, 0));
+        float* dh1 = BP(c, ps1 ? b_dh1S : b_dh1);
+        {   // norm2 backward: dh1 = gn_silu_bwd(h1, da2), in conv1's family   (h1 has no persistent grad buffer: write to scratch)
             bd_gn_bwd_desc d = {};
-            d.B = c.B; d.HW = HW; d.C = Cout; d.G = G; d.silu = 1;
-            d.x = BP(c, b_h1); d.ldx = Cout; d.gamma = c.params + pn2w; d.beta = c.params + pn2b;
-            d.mean = MEANP(c, b_st2, G); d.rstd = RSTDP(c, b_st2, G);
-            d.dy = BP(c, b_da2); d.lddy = Cout; d.dx = ps1 ? nullptr : BP(c, b_dh1); d.lddx = Cout; d.accumulate_dx = 0;
-            d.workspace = c.opws; d.workspace_bytes = c.opws_bytes;
-            if (c.wg) {
-                d.dgamma = c.grads + pn2w; d.dbeta = c.grads + pn2b;
-                // time-embedding gradient = per-sample column sums of dh1, out of the same launch
-                d.dx_colsum = BP(c, b_dtproj) + toff; d.ld_colsum = sumC_;
-            }
-            if (ps1) { d.dx_split = U16(BP(c, b_dh1S)); d.lddxs = Cout; }
-            d.param_partials = c.gn_slot(d.B, d.HW, d.C, d.G, d.dgamma, d.dbeta);
-            if (!c.dry) BD_TRY(bd_gn_bwd(&d, (bd_stream_t)c.st));
+            d.lddx = Cout;
+            if (ps1) { d.dx_split = U16(dh1); d.lddxs = Cout; }
+            else d.dx = dh1;
+            // time-embedding gradient = per-sample column sums of dh1, out of the same launch
+            d.dx_colsum = BP(c, b_dtproj) + toff; d.ld_colsum = sumC_;
+            BD_TRY(gn_bwd(c, d, h1v, pn2w, pn2b, b_st2, BP(c, b_da2), Cout, 1));
         }
         // (this resnet's rows of the batched time_emb_proj weight / bias gradient, dW = dtproj[:, rows]^T embs (resnet.py:571),
         //  are produced by ONE launch per backward segment over all of the segment's resnets: temb_wgrad below)
         if (c.dry) BD_TRY(linear_wgrad(c, BP(c, b_dtproj), sumC_, BP(c, b_embs_), T_, c.grads, c.B, sumC_, T_, c.grads));   // workspace bound
-        if (ps1) {
-            bd_conv3x3_ps_wgrad_desc w1 = {};
-            w1.B = c.B; w1.H = H; w1.W = W; w1.Cin = Cin; w1.Cout = Cout;
-            w1.x_split = U16(BP(c, b_a1s)); w1.ldx = Cin; w1.dy_split = U16(BP(c, b_dh1S)); w1.lddy = Cout;
-            w1.dw = c.grads + pc1w; w1.db = c.grads + pc1b;
-            BD_TRY(conv_pw(c, w1));
-            bd_conv3x3_ps_desc g1 = {};
-            g1.B = c.B; g1.H = H; g1.W = W; g1.K = Cout; g1.N = Cin; g1.direction = -1;
-            g1.x_split = U16(BP(c, b_dh1S)); g1.ldx = Cout; g1.w_split = c.wT_split + 2 * pc1w; g1.out_scale = 1.f;
-            g1.y = BP(c, b_da1); g1.ldy = Cin;
-            BD_TRY(conv_p(c, g1));
-        } else {
-            bd_conv3x3_wgrad_desc w1 = {};
-            w1.B = c.B; w1.Hs = H; w1.Ws = W; w1.Cin = Cin; w1.Cout = Cout; w1.stride = 1; w1.pad_t = 1; w1.pad_l = 1; w1.Ho = H; w1.Wo = W;
-            w1.x = BP(c, b_a1); w1.ldx = Cin; w1.dy = BP(c, b_dh1); w1.lddy = Cout; w1.dw = c.grads + pc1w; w1.db = c.grads + pc1b;
-            BD_TRY(conv_w(c, w1));
-            bd_conv3x3_dgrad_desc g1 = {};
-            g1.B = c.B; g1.Hs = H; g1.Ws = W; g1.Cin = Cin; g1.Cout = Cout; g1.stride = 1; g1.pad_t = 1; g1.pad_l = 1; g1.Ho = H; g1.Wo = W;
-            g1.dy = BP(c, b_dh1); g1.lddy = Cout; g1.w = c.params + pc1w; g1.dx = BP(c, b_da1); g1.lddx = Cin;
-            BD_TRY(conv_d(c, g1));
-        }
+        BD_TRY(conv3_wgrad(c, k1, ps1, {BP(c, ps1 ? b_a1s : b_a1), Cin}, {dh1, Cout}));
+        BD_TRY(conv3_dgrad(c, k1, ps1, {dh1, Cout}, BP(c, b_da1), Cin, 0));
         if (shortcut) {   // 1x1 shortcut convolution: its data gradient goes in FIRST, so that the norm1 backward below is the store that makes
             // dL/dx final (and can hand x's producer the split planes of it)
-            BD_TRY(linear_wgrad(c, dy, lddy, VP(c, x), x.ld, c.grads + psw, M, Cout, Cin, c.grads + psb));
-            const int acc = c.ginit[x.buf];
-            c.ginit[x.buf] = 1;
+            BD_TRY(linear_wgrad(c, dy.p, dy.ld, VP(c, x), x.ld, c.grads + psw, M, Cout, Cin, c.grads + psb));
+            const int acc = take_ginit(c, x.buf);
             // dL/dy exists as split planes whenever conv2 took the plane kernels: the shortcut's data gradient then runs DMA-fed on them
             // (bd_gemm_sp, the weight's per-step plane copy taken K-major) instead of splitting both fp32 operands in the igemm loaders
             static const bool sc_sp = !(getenv("BD_SHORTCUT_SP") && atoi(getenv("BD_SHORTCUT_SP")) == 0);      // (A/B knob)
             if (sc_sp && ps2 && gemm_sp_supported(M, Cin, Cout) && x.ld % 4 == 0) {
-                const bool ready = gs_out >= 0 && gsplits[gs_out].emitted;
                 bd_gemm_sp_desc g = {};
                 g.M = M; g.N = Cin; g.K = Cout; g.batch = 1;
-                g.a = U16(ready ? BP(c, gsplits[gs_out].b_pl) : BP(c, b_dyS)); g.lda = Cout;
+                g.a = U16(dy2.p); g.lda = Cout;
                 g.b = c.w_split + 2 * psw; g.ldb = Cin; g.b_kmajor = 1;
                 g.c = GP(c, x); g.ldc = x.ld; g.accumulate = acc; g.alpha = 1.f; g.out_scale = 1.f;
                 BD_TRY(gemm_s(c, g));
             } else {
-                BD_TRY(linear_dgrad(c, dy, lddy, c.params + psw, GP(c, x), x.ld, M, Cout, Cin, acc));
+                BD_TRY(linear_dgrad(c, dy.p, dy.ld, c.params + psw, GP(c, x), x.ld, M, Cout, Cin, acc));
             }
         }
         // norm1 backward; the identity shortcut's gradient (dy itself) is added in the same store
-        return gn_bwd(c, x, pn1w, pn1b, b_st1, BP(c, b_da1), Cin, 1, shortcut ? nullptr : dy, lddy, gs_in);
+        return gn_bwd(c, x, pn1w, pn1b, b_st1, BP(c, b_da1), Cin, 1, shortcut ? nullptr : dy.p, dy.ld, gs_in);
     });
 }
 
@@ -765,7 +743,7 @@ void bd_unet::node_attention(const std::string& pre, const View& x, const View& 
     const int b_p = new_buf((int64_t)heads * N * N, 0, R_VALUE), b_o = new_buf((int64_t)N * C, 0, R_VALUE);
     const int b_st = new_buf(2 * G, 0, R_VALUE);
     const int b_dys = scale != 1.f ? scratch((int64_t)N * C) : -1;
-    const int b_bs = scratch(3 * C), b_do = scratch((int64_t)N * C), b_dp = scratch((int64_t)heads * N * N);
+    const int b_do = scratch((int64_t)N * C), b_dp = scratch((int64_t)heads * N * N);
     const int b_dqkv = scratch((int64_t)N * 3 * C), b_dn = scratch((int64_t)N * C);
     const int b_dyS = scratch((int64_t)N * C);
     const float inv = 1.f / scale;
@@ -778,27 +756,18 @@ void bd_unet::node_attention(const std::string& pre, const View& x, const View& 
     // hands planes to the output projection; the backward mirrors it.  The same buffers hold planes instead of fp32 (same bytes); the
     // weights' planes are the per-step bd_split_bf16 copy (K-contiguous rows: the layout a [N][K] weight wants forward, and the K-major
     // operand of its data gradient as it stands).  N = 256 tokens, head dim 256 (attn_sp_supported); the mid block (4 x 4) stays below.
-    auto use_sp = [=](const Ctx& c) {
-        return mode_bf16(cfg.compute_mode) && (c.dry || c.w_split) && attn_sp_supported(N, dh) &&
-               gemm_sp_supported((int)((int64_t)(c.LB > 0 ? c.LB : c.B) * N), C, C) && gemm_sp_supported(3 * C, C, 32);
+    auto sp_shape = [=](int B) {
+        return mode_bf16(cfg.compute_mode) && attn_sp_supported(N, dh) && gemm_sp_supported((int)((int64_t)B * N), C, C) &&
+               gemm_sp_supported(3 * C, C, 32);
     };
+    auto use_sp = [=](const Ctx& c) { return planes(c) && sp_shape(lay_batch(c)); };
     const int gs_in = claim_gsplit(x, true);
-    const int gs_out = b_dys < 0 ? reg_gsplit(y, [use_sp](const Ctx& c) { return use_sp(c); }) : -1;
+    const int gs_out = b_dys < 0 ? reg_gsplit(y, sp_shape) : -1;
     F([=](Ctx& c) {
         const int M = (int)rows(c, x);
-        if (use_sp(c)) {
-            bd_gn_fwd_desc g = {};
-            g.B = c.B; g.HW = N; g.C = C; g.G = G; g.eps = cfg.norm_eps; g.silu = 0;
-            g.x = VP(c, x); g.ldx = x.ld; g.gamma = c.params + pgw; g.beta = c.params + pgb;
-            g.y = nullptr; g.ldy = C; g.y_split = U16(BP(c, b_n)); g.ldys = C;
-            g.mean = MEANP(c, b_st, G); g.rstd = RSTDP(c, b_st, G);
-            g.workspace = c.opws; g.workspace_bytes = c.opws_bytes;
-            if (c.dry) {
-                const size_t n = bd_gn_workspace_bytes(c.B, C);
-                if (n > c.opws_need) c.opws_need = n;
-            } else {
-                BD_TRY(bd_gn_fwd(&g, (bd_stream_t)c.st));
-            }
+        const bool sp = use_sp(c);
+        BD_TRY(gn_fwd(c, x, pgw, pgb, BP(c, b_n), C, b_st, 0, sp));
+        if (sp) {
             bd_gemm_sp_desc q = {};      // qkv = n Wqkv^T + b  -> planes
             q.M = M; q.N = 3 * C; q.K = C; q.batch = 1;
             q.a = U16(BP(c, b_n)); q.lda = C; q.b = c.w_split + 2 * pqw; q.ldb = C;
@@ -816,7 +785,6 @@ void bd_unet::node_attention(const std::string& pre, const View& x, const View& 
             o.c = VP(c, y); o.ldc = y.ld; o.bias = c.params + ppb; o.residual = VP(c, x); o.ldr = x.ld; o.alpha = 1.f; o.out_scale = inv;
             return gemm_s(c, o);
         }
-        BD_TRY(gn_fwd(c, x, pgw, pgb, BP(c, b_n), C, b_st, 0));
         BD_TRY(linear_fwd(c, BP(c, b_n), C, c.params + pqw, c.params + pqb, BP(c, b_qkv), 3 * C, M, 3 * C, C));
         float* qkv = BP(c, b_qkv);
         {
@@ -850,17 +818,16 @@ void bd_unet::node_attention(const std::string& pre, const View& x, const View& 
             dy = BP(c, b_dys); lddy = C;
         }
         if (use_sp(c)) {
-            const bool ready = gs_out >= 0 && gsplits[gs_out].emitted;
-            float* dyS = ready ? BP(c, gsplits[gs_out].b_pl) : BP(c, b_dyS);
-            if (!ready) BD_TRY(split_rows(c, dy, lddy, M, C, dyS));
+            Opnd dyS;
+            BD_TRY(grad_planes(c, gs_out, dy, lddy, M, C, b_dyS, dyS));
             bd_gemm_sp_desc w = {};      // dWp = dy^T o, dbp = column sums of dy  (side stream)
             w.M = C; w.N = C; w.K = M; w.batch = 1;
-            w.a = U16(dyS); w.lda = C; w.a_kmajor = 1; w.b = U16(BP(c, b_o)); w.ldb = C; w.b_kmajor = 1;
+            w.a = U16(dyS.p); w.lda = C; w.a_kmajor = 1; w.b = U16(BP(c, b_o)); w.ldb = C; w.b_kmajor = 1;
             w.c = c.grads + ppw; w.ldc = C; w.a_colsum = c.grads + ppb; w.alpha = 1.f; w.out_scale = 1.f;
             BD_TRY(gemm_s(c, w, true));
             bd_gemm_sp_desc g = {};      // dO = dy Wp -> planes
             g.M = M; g.N = C; g.K = C; g.batch = 1;
-            g.a = U16(dyS); g.lda = C; g.b = c.w_split + 2 * ppw; g.ldb = C; g.b_kmajor = 1;
+            g.a = U16(dyS.p); g.lda = C; g.b = c.w_split + 2 * ppw; g.ldb = C; g.b_kmajor = 1;
             g.c_split = U16(BP(c, b_do)); g.ldcs = C; g.alpha = 1.f; g.out_scale = 1.f;
             BD_TRY(gemm_s(c, g));
             if (!c.dry) {
@@ -935,40 +902,27 @@ void bd_unet::node_downsample(const std::string& pre, const View& x, const View&
     const int pad = cfg.downsample_padding ? 1 : 0;
     const int64_t pw = add_param(pre + "conv.weight", {C, C, 3, 3}, 1), pb = add_param(pre + "conv.bias", {C});
     if (C % 32 == 0) { wt_off.push_back(pw); wt_cin.push_back(C); wt_cout.push_back(C); }   // transposed planes for the phase data gradient
-    const int b_bs = scratch(C), b_dyS = scratch((int64_t)Ho * Wo * C);
+    Conv3 k = conv3_same(pw, pb, C, C, H, W);
+    k.stride = 2; k.pad = pad; k.Ho = Ho; k.Wo = Wo;
+    const int b_dyS = scratch((int64_t)Ho * Wo * C);
     claim_gsplit(x, false);        // (this node's data gradient is a convolution: it cannot leave dL/dx as planes)
-    const int gs_out = reg_gsplit(y, [this, H, W, Ho, Wo, C](const Ctx& c) { return H == 2 * Ho && W == 2 * Wo && phase_ok(c, Ho, Wo, C, C); });
-    F([=](Ctx& c) {
-        bd_conv3x3_fwd_desc d = {};
-        d.B = c.B; d.Hs = H; d.Ws = W; d.Cin = C; d.Cout = C; d.stride = 2; d.pad_t = pad; d.pad_l = pad; d.Ho = Ho; d.Wo = Wo;
-        d.x = VP(c, x); d.ldx = x.ld; d.w = c.params + pw; d.bias = c.params + pb; d.out_scale = 1.f;
-        d.y = VP(c, y); d.ldy = y.ld;
-        return conv_f(c, d);
-    });
+    // by the parity of the input pixel only 4 / 2 / 2 / 1 of the nine taps contribute to the data gradient: four classes on the output grid
+    const bool even = H == 2 * Ho && W == 2 * Wo;
+    const int gs_out = reg_gsplit(y, [=](int B) { return even && phase_shape(B, Ho, Wo, C, C); });
+    F([=](Ctx& c) { return conv3_fwd(c, k, false, {VP(c, x), x.ld}, VP(c, y), y.ld); });
     Bk([=](Ctx& c) {
-        const float* dy = GP(c, y);
-        bd_conv3x3_wgrad_desc w = {};
-        w.B = c.B; w.Hs = H; w.Ws = W; w.Cin = C; w.Cout = C; w.stride = 2; w.pad_t = pad; w.pad_l = pad; w.Ho = Ho; w.Wo = Wo;
-        w.x = VP(c, x); w.ldx = x.ld; w.dy = dy; w.lddy = y.ld; w.dw = c.grads + pw; w.db = c.grads + pb;
-        BD_TRY(conv_w(c, w));
-        const int acc = c.ginit[x.buf];
-        c.ginit[x.buf] = 1;
-        if (H == 2 * Ho && W == 2 * Wo && phase_ok(c, Ho, Wo, C, C)) {
-            // by the parity of the input pixel only 4 / 2 / 2 / 1 of the nine taps contribute: four classes on the output grid
-            const bool ready = gs_out >= 0 && gsplits[gs_out].emitted;
-            float* dyS = ready ? BP(c, gsplits[gs_out].b_pl) : BP(c, b_dyS);
-            if (!ready) BD_TRY(split_rows(c, dy, y.ld, (int64_t)c.B * Ho * Wo, C, dyS));
-            if (c.dry) return (int)BD_OK;
-            bd_conv3x3_s2_dgrad_desc g = {};
-            g.B = c.B; g.Ho = Ho; g.Wo = Wo; g.Cin = C; g.Cout = C; g.pad = pad;
-            g.dy_split = U16(dyS); g.lddy = C; g.wT_split = c.wT_split + 2 * pw;
-            g.dx = GP(c, x); g.lddx = x.ld; g.accumulate = acc; g.mode = cfg.compute_mode;
-            return conv3x3_s2_dgrad_ps(g, c.st);
-        }
-        bd_conv3x3_dgrad_desc g = {};
-        g.B = c.B; g.Hs = H; g.Ws = W; g.Cin = C; g.Cout = C; g.stride = 2; g.pad_t = pad; g.pad_l = pad; g.Ho = Ho; g.Wo = Wo;
-        g.dy = dy; g.lddy = y.ld; g.w = c.params + pw; g.dx = GP(c, x); g.lddx = x.ld; g.accumulate = acc;
-        return conv_d(c, g);
+        const Opnd dy = {GP(c, y), y.ld};
+        BD_TRY(conv3_wgrad(c, k, false, {VP(c, x), x.ld}, dy));
+        const int acc = take_ginit(c, x.buf);
+        if (!(even && phase_ok(c, Ho, Wo, C, C))) return conv3_dgrad(c, k, false, dy, GP(c, x), x.ld, acc);
+        Opnd dyS;
+        BD_TRY(grad_planes(c, gs_out, dy.p, dy.ld, (int64_t)c.B * Ho * Wo, C, b_dyS, dyS));
+        if (c.dry) return (int)BD_OK;
+        bd_conv3x3_s2_dgrad_desc g = {};
+        g.B = c.B; g.Ho = Ho; g.Wo = Wo; g.Cin = C; g.Cout = C; g.pad = pad;
+        g.dy_split = U16(dyS.p); g.lddy = C; g.wT_split = c.wT_split + 2 * pw;
+        g.dx = GP(c, x); g.lddx = x.ld; g.accumulate = acc; g.mode = cfg.compute_mode;
+        return conv3x3_s2_dgrad_ps(g, c.st);
     });
 }
 
@@ -976,7 +930,9 @@ void bd_unet::node_upsample(const std::string& pre, const View& x, const View& y
     const int C = x.C, H = x.H, W = x.W;
     const int64_t pw = add_param(pre + "conv.weight", {C, C, 3, 3}, 1), pb = add_param(pre + "conv.bias", {C});
     if (C % 32 == 0) { wt_off.push_back(pw); wt_cin.push_back(C); wt_cout.push_back(C); }
-    const int b_bs = scratch(C), b_du = scratch((int64_t)4 * H * W * C);
+    Conv3 k = conv3_same(pw, pb, C, C, H, W);
+    k.ups = 1; k.Ho = 2 * H; k.Wo = 2 * W;
+    const int b_du = scratch((int64_t)4 * H * W * C);
     // LDS-DMA path: the nearest-upsampled input is materialised ONCE as split planes (4 B per element of the 2H x 2W
     // grid) and feeds the stride-1 "same" kernels of conv_ps.hip: forward, weight gradient and (through b_du + 2x2 sums)
     // the data gradient.  Otherwise the upsampling stays folded into the igemm gather.
@@ -986,15 +942,14 @@ void bd_unet::node_upsample(const std::string& pre, const View& x, const View& y
     const int b_e = new_buf(0, (int64_t)16 * C * C, R_VALUE), b_et = new_buf(0, (int64_t)16 * C * C, R_VALUE);
     if (C % 128 == 0) upsw.push_back({pw, C, H, W, b_e, b_et});
     claim_gsplit(x, false);
-    const int gs_out = reg_gsplit(y, [this, H, W, C](const Ctx& c) { return phase_ok(c, H, W, C, C) || ps_ok(c, 2 * H, 2 * W, C, C); });
-    {   // which of the two operand sets exists is the plan's path choice for the batch the workspace is laid out for
-        auto phase_at = [=](int B) { Ctx q; q.dry = true; q.B = q.LB = B; return phase_ok(q, H, W, C, C); };
-        auto ps_at = [=](int B) { Ctx q; q.dry = true; q.B = q.LB = B; return ps_ok(q, 2 * H, 2 * W, C, C); };
-        bufs[b_xuS].live = [=](int B, int) { return !phase_at(B) && ps_at(B); };
-        bufs[b_xS].live = [=](int B, int) { return phase_at(B); };
-        bufs[b_e].live = [=](int B, int) { return phase_at(B); };
-        bufs[b_et].live = [=](int B, int training) { return training && phase_at(B); };
-    }
+    auto phase_at = [=](int B) { return phase_shape(B, H, W, C, C); };
+    auto ps_at = [=](int B) { return ps_shape(B, 2 * H, 2 * W, C, C); };
+    const int gs_out = reg_gsplit(y, [=](int B) { return phase_at(B) || ps_at(B); });
+    // which of the two operand sets exists is the plan's path choice for the batch the workspace is laid out for
+    bufs[b_xuS].live = [=](int B, int) { return !phase_at(B) && ps_at(B); };
+    bufs[b_xS].live = [=](int B, int) { return phase_at(B); };
+    bufs[b_e].live = [=](int B, int) { return phase_at(B); };
+    bufs[b_et].live = [=](int B, int training) { return training && phase_at(B); };
     F([=](Ctx& c) {
         if (phase_ok(c, H, W, C, C)) {
             BD_TRY(split_rows(c, VP(c, x), x.ld, (int64_t)c.B * H * W, C, BP(c, b_xS)));
@@ -1006,79 +961,42 @@ void bd_unet::node_upsample(const std::string& pre, const View& x, const View& y
             d.y = VP(c, y); d.ldy = y.ld;
             return upsample_conv_fwd(d, c.st);
         }
-        if (ps_ok(c, 2 * H, 2 * W, C, C)) {
-            if (!c.dry) BD_TRY(bd_split_rows_ups2(VP(c, x), x.ld, c.B, H, W, C, U16(BP(c, b_xuS)), C, (bd_stream_t)c.st));
-            bd_conv3x3_ps_desc d = {};
-            d.B = c.B; d.H = 2 * H; d.W = 2 * W; d.K = C; d.N = C; d.direction = 1;
-            d.x_split = U16(BP(c, b_xuS)); d.ldx = C; d.w_split = c.w_split + 2 * pw; d.bias = c.params + pb; d.out_scale = 1.f;
-            d.y = VP(c, y); d.ldy = y.ld;
-            return conv_p(c, d);
-        }
-        bd_conv3x3_fwd_desc d = {};
-        d.B = c.B; d.Hs = H; d.Ws = W; d.Cin = C; d.Cout = C; d.stride = 1; d.pad_t = 1; d.pad_l = 1; d.ups = 1; d.Ho = 2 * H; d.Wo = 2 * W;
-        d.x = VP(c, x); d.ldx = x.ld; d.w = c.params + pw; d.bias = c.params + pb; d.out_scale = 1.f;
-        d.y = VP(c, y); d.ldy = y.ld;
-        return conv_f(c, d);
+        const bool ps = ps_ok(c, 2 * H, 2 * W, C, C);
+        if (ps && !c.dry) BD_TRY(bd_split_rows_ups2(VP(c, x), x.ld, c.B, H, W, C, U16(BP(c, b_xuS)), C, (bd_stream_t)c.st));
+        return conv3_fwd(c, k, ps, ps ? Opnd{BP(c, b_xuS), C} : Opnd{VP(c, x), x.ld}, VP(c, y), y.ld);
     });
     Bk([=](Ctx& c) {
-        const float* dy = GP(c, y);
-        const int acc = c.ginit[x.buf];
-        c.ginit[x.buf] = 1;
-        const bool ready = gs_out >= 0 && gsplits[gs_out].emitted;
-        float* dyS = ready ? BP(c, gsplits[gs_out].b_pl) : BP(c, b_dyS);
-        if (phase_ok(c, H, W, C, C)) {
-            if (!ready) BD_TRY(split_rows(c, dy, y.ld, (int64_t)c.B * 4 * H * W, C, dyS));
+        Opnd dy = {GP(c, y), y.ld};
+        const int acc = take_ginit(c, x.buf);
+        const bool ph = phase_ok(c, H, W, C, C);
+        const bool ps = ph || ps_ok(c, 2 * H, 2 * W, C, C);      // family of the fine-grid data gradient
+        if (ps) BD_TRY(grad_planes(c, gs_out, dy.p, dy.ld, (int64_t)c.B * 4 * H * W, C, b_dyS, dy));
+        if (ph) {
             bd_upsample_conv_desc d = {};
             d.mode = cfg.compute_mode;
             d.B = c.B; d.H = H; d.W = W; d.Cin = C; d.Cout = C;
-            d.x_split = U16(BP(c, b_xS)); d.ldx = C; d.dy_split = U16(dyS); d.lddy = C;
+            d.x_split = U16(BP(c, b_xS)); d.ldx = C; d.dy_split = U16(dy.p); d.lddy = C;
             d.et_split = U16(BP(c, b_et)); d.dx = GP(c, x); d.lddx = x.ld; d.accumulate = acc;
             d.dw = c.grads + pw; d.db = c.grads + pb;
             // ONE class of 16 taps: >= 128 tiles of its own, or (taps dealt to four workgroups per tile) >= 32
             const bool ph_d = phase_ok(c, H, W, C, C, upsample_conv_dgrad_workspace_bytes(d) ? 4 : 1);
             if (c.dry) {
-                size_t n = upsample_conv_wgrad_workspace_bytes(d);
-                if (n > c.opws_need) c.opws_need = n;
-                n = upsample_conv_dgrad_workspace_bytes(d);
-                if (n > c.opws_need) c.opws_need = n;
-                if (!ph_d) note_conv(c);
-                return (int)BD_OK;
+                need(c, upsample_conv_wgrad_workspace_bytes(d));
+                need(c, upsample_conv_dgrad_workspace_bytes(d));
+            } else {
+                d.workspace_bytes = c.opws_bytes;
+                if (c.wg) BD_TRY(on_aux(c, [&](hipStream_t st, char* ws) { d.workspace = ws; return upsample_conv_wgrad(d, st); }));
             }
-            d.workspace_bytes = c.opws_bytes;
-            if (c.wg) BD_TRY(on_aux(c, [&](hipStream_t st, char* ws) { d.workspace = ws; return upsample_conv_wgrad(d, st); }));
             if (ph_d) {      // 16 taps on dY sampled at stride 2: replaces the fine-grid dgrad + 2x2 sum
+                if (c.dry) return (int)BD_OK;
                 d.workspace = c.opws;
                 return upsample_conv_dgrad(d, c.st);
             }
-            bd_conv3x3_ps_desc g = {};                           // literal data gradient on the fine grid + 2x2 sums
-            g.B = c.B; g.H = 2 * H; g.W = 2 * W; g.K = C; g.N = C; g.direction = -1;
-            g.x_split = U16(dyS); g.ldx = C; g.w_split = c.wT_split + 2 * pw; g.out_scale = 1.f;
-            g.y = BP(c, b_du); g.ldy = C;
-            BD_TRY(conv_p(c, g));
-            return bd_sum2x2(BP(c, b_du), C, GP(c, x), x.ld, c.B, H, W, C, acc, (bd_stream_t)c.st);
-        }
-        if (ps_ok(c, 2 * H, 2 * W, C, C)) {
-            if (!ready) BD_TRY(split_rows(c, dy, y.ld, (int64_t)c.B * 4 * H * W, C, dyS));
-            bd_conv3x3_ps_wgrad_desc w = {};
-            w.B = c.B; w.H = 2 * H; w.W = 2 * W; w.Cin = C; w.Cout = C;
-            w.x_split = U16(BP(c, b_xuS)); w.ldx = C; w.dy_split = U16(dyS); w.lddy = C;
-            w.dw = c.grads + pw; w.db = c.grads + pb;
-            BD_TRY(conv_pw(c, w));
-            bd_conv3x3_ps_desc g = {};
-            g.B = c.B; g.H = 2 * H; g.W = 2 * W; g.K = C; g.N = C; g.direction = -1;
-            g.x_split = U16(dyS); g.ldx = C; g.w_split = c.wT_split + 2 * pw; g.out_scale = 1.f;
-            g.y = BP(c, b_du); g.ldy = C;
-            BD_TRY(conv_p(c, g));
         } else {
-            bd_conv3x3_wgrad_desc w = {};
-            w.B = c.B; w.Hs = H; w.Ws = W; w.Cin = C; w.Cout = C; w.stride = 1; w.pad_t = 1; w.pad_l = 1; w.ups = 1; w.Ho = 2 * H; w.Wo = 2 * W;
-            w.x = VP(c, x); w.ldx = x.ld; w.dy = dy; w.lddy = y.ld; w.dw = c.grads + pw; w.db = c.grads + pb;
-            BD_TRY(conv_w(c, w));
-            bd_conv3x3_dgrad_desc g = {};
-            g.B = c.B; g.Hs = H; g.Ws = W; g.Cin = C; g.Cout = C; g.stride = 1; g.pad_t = 1; g.pad_l = 1; g.ups = 1; g.Ho = 2 * H; g.Wo = 2 * W;
-            g.dy = dy; g.lddy = y.ld; g.w = c.params + pw; g.dx = BP(c, b_du); g.lddx = C;
-            BD_TRY(conv_d(c, g));
+            BD_TRY(conv3_wgrad(c, k, ps, ps ? Opnd{BP(c, b_xuS), C} : Opnd{VP(c, x), x.ld}, dy));
         }
+        // literal data gradient on the fine grid + 2x2 sums
+        BD_TRY(conv3_dgrad(c, k, ps, dy, BP(c, b_du), C, 0));
         if (c.dry) return (int)BD_OK;
         return bd_sum2x2(BP(c, b_du), C, GP(c, x), x.ld, c.B, H, W, C, acc, (bd_stream_t)c.st);
     });
@@ -1088,29 +1006,19 @@ void bd_unet::node_conv_out(const View& x) {
     const int C = x.C, H = x.H, W = x.W, Co = cfg.out_channels;
     const int64_t pnw = add_param("conv_norm_out.weight", {C}), pnb = add_param("conv_norm_out.bias", {C});
     const int64_t pw = add_param("conv_out.weight", {Co, C, 3, 3}, 1), pb = add_param("conv_out.bias", {Co});
+    const Conv3 k = conv3_same(pw, pb, C, Co, H, W);
     const int G = cfg.norm_num_groups;
     const int b_a = new_buf((int64_t)H * W * C, 0, R_VALUE), b_st = new_buf(2 * G, 0, R_VALUE);
     const int b_bs = scratch(Co), b_da = scratch((int64_t)H * W * C);
     const int gs_in = claim_gsplit(x, true);
     F([=](Ctx& c) {
         BD_TRY(gn_fwd(c, x, pnw, pnb, BP(c, b_a), C, b_st, 1));
-        bd_conv3x3_fwd_desc d = {};
-        d.B = c.B; d.Hs = H; d.Ws = W; d.Cin = C; d.Cout = Co; d.stride = 1; d.pad_t = 1; d.pad_l = 1; d.Ho = H; d.Wo = W;
-        d.x = BP(c, b_a); d.ldx = C; d.w = c.params + pw; d.bias = c.params + pb; d.out_scale = 1.f;
-        d.y = c.out; d.ldy = c.ldo;
-        return conv_f(c, d);
+        return conv3_fwd(c, k, false, {BP(c, b_a), C}, c.out, c.ldo);
     });
     Bk([=](Ctx& c) {
-        bd_conv3x3_wgrad_desc w = {};
-        w.B = c.B; w.Hs = H; w.Ws = W; w.Cin = C; w.Cout = Co; w.stride = 1; w.pad_t = 1; w.pad_l = 1; w.Ho = H; w.Wo = W;
-        w.x = BP(c, b_a); w.ldx = C; w.dy = c.dout; w.lddy = c.lddo; w.dw = c.grads + pw;
-        if (conv3x3_wgrad_is_thin(w)) w.db = c.grads + pb;                    // the direct kernel sums dy on the way
-        else BD_TRY(bias_grad(c, c.dout, c.lddo, H * W, Co, b_bs, c.grads + pb));   // Cout = 3: no igemm row-sum fusion
-        BD_TRY(conv_w(c, w));
-        bd_conv3x3_dgrad_desc g = {};
-        g.B = c.B; g.Hs = H; g.Ws = W; g.Cin = C; g.Cout = Co; g.stride = 1; g.pad_t = 1; g.pad_l = 1; g.Ho = H; g.Wo = W;
-        g.dy = c.dout; g.lddy = c.lddo; g.w = c.params + pw; g.dx = BP(c, b_da); g.lddx = C;
-        BD_TRY(conv_d(c, g));
+        const Opnd dy = {c.dout, c.lddo};
+        BD_TRY(conv3_wgrad(c, k, false, {BP(c, b_a), C}, dy, b_bs));
+        BD_TRY(conv3_dgrad(c, k, false, dy, BP(c, b_da), C, 0));
         return gn_bwd(c, x, pnw, pnb, b_st, BP(c, b_da), C, 1, nullptr, 0, gs_in);
     });
 }
@@ -1156,7 +1064,7 @@ void bd_unet::build() {
     // segments in BACKWARD order: 0 = out, 1..n = up blocks n-1..0, n+1 = mid, n+2..2n+1 = down n-1..0, 2n+2 = conv_in, 2n+3 = time
     const int nseg = 2 * n + 4;
     segs.assign(nseg, Seg{-1, -1});
-    auto seg_out = 0;
+    const int seg_out = 0;
     auto seg_up = [&](int i) { return 1 + (n - 1 - i); };
     const int seg_mid = n + 1;
     auto seg_down = [&](int i) { return n + 2 + (n - 1 - i); };
@@ -1259,7 +1167,6 @@ void bd_unet::build() {
     }
     cur_seg = seg_out; cur_group = group++;
     node_conv_out(last);
-    (void)seg_out;
     nparams = (nparams + 3) / 4 * 4;
 }
 
