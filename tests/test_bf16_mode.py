@@ -110,7 +110,10 @@ def test_igemm_gemm_against_rounded_operands(ops):
 
 @pytest.mark.parametrize("B,S,Cin,Cout", [(3, 8, 256, 128), (48, 16, 128, 256), (16, 32, 128, 128)])
 def test_conv_ps_family_against_rounded_operands(ops, B, S, Cin, Cout):
-    """bd_conv3x3_ps (+1 / -1: the 256x128 kernel, conv_ps3, conv_ps128 by shape) and bd_conv3x3_ps_wgrad (wgrad / wgrad3 by shape)"""
+    """bd_conv3x3_ps (+1 / -1) and bd_conv3x3_ps_wgrad (wgrad / wgrad3 by shape).  At 256 CUs the three shapes reach conv_ps128 in its four-stage
+    split form (3 x 8 x 8, both directions), conv_ps3 (48 x 16 x 16 forward; its data gradient is conv_ps128, two stages) and conv_ps128 in its
+    two-stage split form (16 x 32 x 32) -- not the general 256 x 128 kernel (conv_ps_kernel), which tests/test_conv_ps_dispatch.py covers
+    together with the other branches these shapes miss."""
     g = torch.Generator().manual_seed(B * 1000 + S)
     x = torch.randn(B, S, S, Cin, generator=g).cuda(); dy = torch.randn(B, S, S, Cout, generator=g).cuda()
     w = (torch.randn(Cout, 3, 3, Cin, generator=g) * 0.05).cuda(); bias = torch.randn(Cout, generator=g).cuda()

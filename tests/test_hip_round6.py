@@ -42,15 +42,18 @@ def _inputs(n, seed):
 
 @pytest.mark.parametrize("mode", ["bf16x3", "f32"])
 def test_rows_of_any_batch_equal_the_batch_of_one(model, mode):
-    """B = 1, 3 (ragged 128-row tiles at 4 x 4: 48 rows), 33 (two pipelines of 16 + 17), 129 (64 + 65), 128: every row against its own B = 1
-    evaluation.  Tolerance 2e-5 relative: the products are the same, the K-split / tile choice (fp32 summation order) follows the batch."""
+    """B = 1, 3 (ragged 128-row tiles at 4 x 4: 48 rows), 33 (two pipelines of 16 + 17), 129 (64 + 65), 128, 379 (189 + 190: the 8 x 8 level is
+    a "large" layer there and runs the general 256 x 128 kernel, conv_ps_kernel, with a ragged last tile -- rows 188 / 189 sit either side of
+    the pipeline boundary, 378 is the last row): every row against its own B = 1 evaluation.  Tolerance 2e-5 relative: the products are the
+    same, the K-split / tile choice (fp32 summation order) follows the batch."""
     m = model
     m.set_compute_mode(mode)
     try:
-        x, t, _ = _inputs(129, 1)
+        x, t, _ = _inputs(379, 1)
         with torch.no_grad():
-            ones = {j: m._run_forward(m.flat.data, x[j: j + 1].contiguous(), t[j: j + 1].contiguous(), False)[0].clone() for j in (0, 1, 2, 16, 32, 64, 127, 128)}
-            for B in (3, 33, 128, 129):
+            ones = {j: m._run_forward(m.flat.data, x[j: j + 1].contiguous(), t[j: j + 1].contiguous(), False)[0].clone()
+                    for j in (0, 1, 2, 16, 32, 64, 127, 128, 188, 189, 378)}
+            for B in (3, 33, 128, 129, 379):
                 out = m._run_forward(m.flat.data, x[:B].contiguous(), t[:B].contiguous(), False)[0]
                 assert bool(torch.isfinite(out).all())
                 for j, o in ones.items():

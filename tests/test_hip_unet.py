@@ -274,6 +274,32 @@ def test_cifar_full_batch_modes_and_schedules_agree(bd):
             assert relerr(alone, res[("bf16x3", True)][0][i:i + 1]) < 5e-5
 
 
+def test_cifar_batch_201_modes_agree(bd):
+    """one forward + backward of DDPM-CIFAR10-32 at B = 201, a batch at which the bf16x3 backward takes branches B = 128 does not: the 8 x 8
+    data gradients are "large" layers with 12 864 pixels (the general 256 x 128 kernel, conv_ps_kernel, with a ragged last tile) and the
+    4 x 4 weight gradients have a ragged last 32-pixel chunk inside a K split (3 216 pixels).  The exact-fp32 mode takes none of the
+    split-plane kernels and is the reference; bounds as test_cifar_full_batch_modes_and_schedules_agree carries them for this pair of modes.
+    The same branches with known answers: tests/test_conv_ps_dispatch.py."""
+    unet, ops = bd
+    m = make_model(unet, U.CIFAR10_32, 0)
+    B = 201
+    x = torch.randn(B, 3, 32, 32, generator=torch.Generator().manual_seed(13)).cuda()
+    t = torch.randint(0, 1000, (B,), generator=torch.Generator().manual_seed(14)).cuda()
+    dout = torch.randn(B, 3, 32, 32, generator=torch.Generator().manual_seed(15)).cuda() / (B * 3072)
+    res = {}
+    for mode in ("f32", "bf16x3"):
+        m.set_compute_mode(mode)
+        m.flat.grad = None
+        out = m(x, t, return_dict=False)[0]
+        out.backward(dout)
+        assert torch.isfinite(out).all() and torch.isfinite(m.flat.grad).all()
+        res[mode] = (out.detach().clone(), m.flat.grad.detach().clone())
+    e_out, e_grad = relerr(res["bf16x3"][0], res["f32"][0]), relerr(res["bf16x3"][1], res["f32"][1])
+    print(f"MEASURE cifar_b201 bf16x3 vs f32: out {e_out:.3e} grad {e_grad:.3e}")
+    assert e_out < 1e-4, e_out
+    assert e_grad < 1e-3, e_grad
+
+
 def test_celeba_full_resolution_modes_agree(bd):
     """the real 256x256 DDPM-CELEBA-HQ-256 network (113.7 M parameters), batch 1: forward + backward run, are finite,
     and the split-bf16 contraction agrees with the exact-fp32 one (size-independent self-consistency; the oracle
