@@ -27,21 +27,12 @@
 // N = 256 (16 x 16 feature maps), head dim 256; other shapes keep the unfused path.
 // Measured: 43 / 48 / 49 us at B = 128 against 71 + 118 for the unfused launches; each kernel moves exactly its
 // algorithmic bytes behind the L2 at 3.8-4.1 TB/s, and that -- not the CU side -- is what it waits for.
-#include "common.h"
+#include "splitplane.h"
 
 #include <cstdlib>
 #include <type_traits>
 
 namespace bd {
-
-typedef float as_floatx16 __attribute__((ext_vector_type(16)));
-typedef __bf16 as_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 as_bf16x2 __attribute__((ext_vector_type(2)));
-typedef short as_short4 __attribute__((ext_vector_type(4)));
-typedef short as_short8 __attribute__((ext_vector_type(8)));
-typedef unsigned as_uint4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* as_lds_ptr;
-typedef const __attribute__((address_space(1))) void* as_gbl_ptr;
 
 constexpr int AS_NT = 256, AS_N = 256;
 constexpr int AS_OWN = 32768, AS_SLOT = 49152, AS_LDS = 3 * AS_SLOT;   // phase S slot: streamed chunk 32 KB | 4 waves x 4 KB own rows
@@ -55,30 +46,6 @@ __device__ __forceinline__ void as_for(F&& f) {
     }
 }
 
-__device__ __forceinline__ int as_swz(int row) { return (row >> 1) & 7; }
-__device__ __forceinline__ void as_dma16(const char* src, char* lds_dst) {
-    __builtin_amdgcn_global_load_lds((as_gbl_ptr)src, (as_lds_ptr)lds_dst, 16, 0, 0);
-}
-template <int OFF>
-__device__ __forceinline__ as_short4 as_read_tr(unsigned addr) {
-    as_short4 v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-    return v;
-}
-template <int OFF>
-__device__ __forceinline__ as_short8 as_read128(unsigned addr) {
-    as_short8 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-    return v;
-}
-__device__ __forceinline__ as_bf16x8 as_bf(as_short8 v) { return __builtin_bit_cast(as_bf16x8, v); }
-__device__ __forceinline__ as_bf16x8 as_bf(as_short4 v0, as_short4 v1) {
-    const as_short8 v = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(as_bf16x8, v);
-}
-__device__ __forceinline__ unsigned as_pack_hi(float a, float b) { return bd_pack_hi(a, b); }   // common.h: the library's split
-__device__ __forceinline__ unsigned as_pack_lo(float a, float b) { return bd_pack_lo(a, b); }
-__device__ __forceinline__ unsigned as_split1(float v) { return bd_split1(v); }   // hi | lo << 16
 __device__ __forceinline__ unsigned as_xor1(unsigned w) {   // the value of lane ^ 1 (DPP quad_perm [1,0,3,2])
     return (unsigned)__builtin_amdgcn_mov_dpp((int)w, 0xB1, 0xF, 0xF, true);
 }
@@ -97,13 +64,13 @@ __device__ __forceinline__ AsLane as_lane(const char* smem) {
     L.lane = tid & 63;
     L.wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     L.li = L.lane & 31; L.h = L.lane >> 5;
-    L.smem = (unsigned)(uintptr_t)(as_lds_ptr)smem;
+    L.smem = (unsigned)(uintptr_t)(sp_lds_ptr)smem;
     const int sl = L.lane & 15, hb = (L.lane >> 4) & 1, kq = sl >> 2, rq = sl & 3;
 #pragma unroll
     for (int x = 0; x < 2; ++x)
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl) {
-            L.kc[x][pl] = (unsigned)(L.li * 128 + (((pl * 4 + x * 2 + L.h) ^ as_swz(L.li)) << 4));
+            L.kc[x][pl] = (unsigned)(L.li * 128 + (((pl * 4 + x * 2 + L.h) ^ sp_swz(L.li)) << 4));
             L.kq[x][pl] = L.kc[x][pl] + AS_OWN + L.wave * 4096;
             const unsigned win = (unsigned)((((x * 2 + pl) ^ kq) << 6) + hb * 32 + rq * 8);
             L.km[x][pl] = (unsigned)((8 * L.h + kq) * 512) + win;
@@ -115,34 +82,34 @@ __device__ __forceinline__ AsLane as_lane(const char* smem) {
 // ---- phase S ---------------------------------------------------------------------------------------------------------------------
 // acc[kt][r] += sum_d streamed[kt*32 + (r&3) + 8(r>>2) + 4h][d] * own[li][d]   (d = 0 .. 32 nch - 1)
 // streamed: 256 rows from `a_base` (stride lda bytes); own: this wave's 32 rows from `own_base` (stride ldo bytes); both split planes.
-struct AsGroup { as_short8 a[4][2]; };
+struct AsGroup { sp_short8 a[4][2]; };
 __device__ __forceinline__ void as_tie(AsGroup& g) {
     asm volatile("" : "+v"(g.a[0][0]), "+v"(g.a[0][1]), "+v"(g.a[1][0]), "+v"(g.a[1][1]), "+v"(g.a[2][0]), "+v"(g.a[2][1]), "+v"(g.a[3][0]),
                  "+v"(g.a[3][1]));
 }
-__device__ __forceinline__ void as_tie2(as_short8& a, as_short8& b) { asm volatile("" : "+v"(a), "+v"(b)); }
+__device__ __forceinline__ void as_tie2(sp_short8& a, sp_short8& b) { asm volatile("" : "+v"(a), "+v"(b)); }
 template <bool SP, class W>   // SP (BD_MODE_BF16): hi fragments only, one MFMA per product
 __device__ __forceinline__ void as_phase_s(const char* a_base, long long lda, const char* own_base, long long ldo, int nch, char* smem,
-                                           const AsLane& L, as_floatx16 (&acc)[8], W&& work) {
+                                           const AsLane& L, sp_floatx16 (&acc)[8], W&& work) {
     // uniform chunk pointers + 32-bit lane offsets (saddr + voffset addressing: 12 address registers instead of 24)
     unsigned aoff[8], boff[4];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int r = (L.wave + 4 * j) * 8 + (L.lane >> 3);
-        aoff[j] = (unsigned)(r * (int)lda + (((L.lane & 7) ^ as_swz(r)) << 4));
+        aoff[j] = (unsigned)(r * (int)lda + (((L.lane & 7) ^ sp_swz(r)) << 4));
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int r = j * 8 + (L.lane >> 3);
-        boff[j] = (unsigned)(r * (int)ldo + (((L.lane & 7) ^ as_swz(r)) << 4));
+        boff[j] = (unsigned)(r * (int)ldo + (((L.lane & 7) ^ sp_swz(r)) << 4));
     }
     const char* a_cur = a_base; const char* b_cur = own_base;
     auto issue = [&](int slot) {
         char* st = smem + slot * AS_SLOT;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) as_dma16(a_cur + aoff[j], st + (L.wave + 4 * j) * 1024);
+        for (int j = 0; j < 8; ++j) sp_dma16(a_cur + aoff[j], st + (L.wave + 4 * j) * 1024);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) as_dma16(b_cur + boff[j], st + AS_OWN + L.wave * 4096 + j * 1024);
+        for (int j = 0; j < 4; ++j) sp_dma16(b_cur + boff[j], st + AS_OWN + L.wave * 4096 + j * 1024);
         a_cur += 128; b_cur += 128;
     };
     // eight chunks (dh = 256), statically unrolled, four fragment groups (k16 step, half of the key tiles) per chunk.  work(c) is VALU
@@ -152,21 +119,21 @@ __device__ __forceinline__ void as_phase_s(const char* a_base, long long lda, co
     (void)nch;
     issue(0);
     issue(1);
-    as_short8 q[2][2];
+    sp_short8 q[2][2];
     AsGroup g0, g1;
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
     auto reads_q = [&](unsigned sb, auto S) {
         constexpr int s = decltype(S)::value;
-        q[s][0] = as_read128<0>(sb + L.kq[s][0]);
-        if constexpr (!SP) q[s][1] = as_read128<0>(sb + L.kq[s][1]);
+        q[s][0] = sp_read128<0>(sb + L.kq[s][0]);
+        if constexpr (!SP) q[s][1] = sp_read128<0>(sb + L.kq[s][1]);
     };
     auto reads = [&](unsigned sb, auto S, auto GI, AsGroup& g) {
         constexpr int s = decltype(S)::value, gi = decltype(GI)::value;
         as_for<0, 4>([&](auto T) {
             constexpr int t = decltype(T)::value;
-            g.a[t][0] = as_read128<(gi * 4 + t) * 4096>(sb + L.kc[s][0]);
-            if constexpr (!SP) g.a[t][1] = as_read128<(gi * 4 + t) * 4096>(sb + L.kc[s][1]);
+            g.a[t][0] = sp_read128<(gi * 4 + t) * 4096>(sb + L.kc[s][0]);
+            if constexpr (!SP) g.a[t][1] = sp_read128<(gi * 4 + t) * 4096>(sb + L.kc[s][1]);
         });
     };
     auto wait = [&](AsGroup& g, auto S) {
@@ -177,16 +144,15 @@ __device__ __forceinline__ void as_phase_s(const char* a_base, long long lda, co
     };
     auto mfmas = [&](auto S, auto GI, const AsGroup& g) {
         constexpr int s = decltype(S)::value, gi = decltype(GI)::value;
-        const as_bf16x8 qh = as_bf(q[s][0]), ql = as_bf(q[s][1]);
+        const sp_bf16x8 qh = sp_join(q[s][0]), ql = sp_join(q[s][1]);
 #pragma unroll
-        for (int t = 0; t < 4; ++t) if constexpr (!SP) acc[gi * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(g.a[t][1]), qh, acc[gi * 4 + t], 0, 0, 0);
+        for (int t = 0; t < 4; ++t) if constexpr (!SP) acc[gi * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sp_join(g.a[t][1]), qh, acc[gi * 4 + t], 0, 0, 0);
 #pragma unroll
-        for (int t = 0; t < 4; ++t) if constexpr (!SP) acc[gi * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(g.a[t][0]), ql, acc[gi * 4 + t], 0, 0, 0);
+        for (int t = 0; t < 4; ++t) if constexpr (!SP) acc[gi * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sp_join(g.a[t][0]), ql, acc[gi * 4 + t], 0, 0, 0);
 #pragma unroll
-        for (int t = 0; t < 4; ++t) acc[gi * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(g.a[t][0]), qh, acc[gi * 4 + t], 0, 0, 0);
+        for (int t = 0; t < 4; ++t) acc[gi * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sp_join(g.a[t][0]), qh, acc[gi * 4 + t], 0, 0, 0);
     };
-    asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    sp_sync<12>();
     issue(2);
     reads_q(L.smem, I0{}); reads(L.smem, I0{}, I0{}, g0); wait(g0, I0{});
     as_for<0, 8>([&](auto CC) {
@@ -214,8 +180,8 @@ __device__ __forceinline__ void as_phase_s(const char* a_base, long long lda, co
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (c + 1 < 8) {
             // chunk c+1 has landed everywhere, every read of chunk c has returned: its slot takes chunk c+3
-            if constexpr (c + 2 < 8) asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            if constexpr (c + 2 < 8) sp_wait<12>();
+            else sp_wait<0>();
             __builtin_amdgcn_s_barrier();
             if constexpr (c + 3 < 8) issue(slot);
             as_tie(g1); as_tie2(q[1][0], q[1][1]);
@@ -251,13 +217,13 @@ __device__ __forceinline__ void as_o_issue(const AsStream& s, char* smem, const 
     constexpr int kc = U & 7, half = U >> 3;
     const char* ub = s.base + (long long)kc * 32 * s.ldb + half * 512;   // uniform
 #pragma unroll
-    for (int j = 0; j < 4; ++j) as_dma16(ub + s.off[j], smem + kc * AS_UNIT + (L.wave + 4 * j) * 1024);
+    for (int j = 0; j < 4; ++j) sp_dma16(ub + s.off[j], smem + kc * AS_UNIT + (L.wave + 4 * j) * 1024);
 }
 // units 0..5 in flight; the caller has passed a barrier behind the last read of the ring
 __device__ __forceinline__ void as_o_prologue(const AsStream& s, char* smem, const AsLane& L) {
     as_for<0, 6>([&](auto U) { as_o_issue<decltype(U)::value>(s, smem, L); });
 }
-struct AsOFrag { as_short4 v0[4][2], v1[4][2]; };
+struct AsOFrag { sp_short4 v0[4][2], v1[4][2]; };
 __device__ __forceinline__ void as_tie(AsOFrag& f) {
     asm volatile("" : "+v"(f.v0[0][0]), "+v"(f.v0[0][1]), "+v"(f.v0[1][0]), "+v"(f.v0[1][1]), "+v"(f.v0[2][0]), "+v"(f.v0[2][1]), "+v"(f.v0[3][0]),
                  "+v"(f.v0[3][1]));
@@ -271,8 +237,8 @@ __device__ __forceinline__ void as_tie(AsOFrag& f) {
 // the last DMA is issued while unit 9 runs, the barrier that opens unit 12 waits for everything, and only work(u >= 12) may store.
 constexpr int AS_O_STORE_FROM = 12;
 template <bool PERM, bool SP, class W>   // SP (BD_MODE_BF16): the hi planes of both operands only, one MFMA per product
-__device__ __forceinline__ void as_o_run(const AsStream& s, char* smem, const AsLane& L, const as_uint4 (&ah)[8][2], const as_uint4 (&al)[8][2],
-                                         as_floatx16 (&oacc)[8], W&& work) {
+__device__ __forceinline__ void as_o_run(const AsStream& s, char* smem, const AsLane& L, const sp_uint4 (&ah)[8][2], const sp_uint4 (&al)[8][2],
+                                         sp_floatx16 (&oacc)[8], W&& work) {
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
     AsOFrag f0, f1;
@@ -284,8 +250,8 @@ __device__ __forceinline__ void as_o_run(const AsStream& s, char* smem, const As
 #pragma unroll
             for (int pl = 0; pl < (SP ? 1 : 2); ++pl) {
                 const unsigned a = ub + (PERM ? L.kmp[t & 1][pl] : L.km[t & 1][pl]);
-                f.v0[t][pl] = as_read_tr<sp * 16 * 512 + (t >> 1) * 256>(a);
-                f.v1[t][pl] = as_read_tr<sp * 16 * 512 + (t >> 1) * 256 + second>(a);
+                f.v0[t][pl] = sp_read_tr<sp * 16 * 512 + (t >> 1) * 256>(a);
+                f.v1[t][pl] = sp_read_tr<sp * 16 * 512 + (t >> 1) * 256 + second>(a);
             }
         });
     };
@@ -293,8 +259,7 @@ __device__ __forceinline__ void as_o_run(const AsStream& s, char* smem, const As
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         as_tie(f);
     };
-    asm volatile("s_waitcnt vmcnt(20) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    sp_sync<20>();
     as_o_issue<6>(s, smem, L);
     reads(L.smem, I0{}, f0);
     wait(f0);
@@ -303,13 +268,13 @@ __device__ __forceinline__ void as_o_run(const AsStream& s, char* smem, const As
         const unsigned ub = L.smem + kc * AS_UNIT, nub = L.smem + nkc * AS_UNIT;
         auto mfmas = [&](auto S, const AsOFrag& f) {
             constexpr int sp = decltype(S)::value;
-            const as_bf16x8 mh = __builtin_bit_cast(as_bf16x8, ah[kc][sp]), ml = __builtin_bit_cast(as_bf16x8, al[kc][sp]);
+            const sp_bf16x8 mh = __builtin_bit_cast(sp_bf16x8, ah[kc][sp]), ml = __builtin_bit_cast(sp_bf16x8, al[kc][sp]);
 #pragma unroll
-            for (int t = 0; t < 4; ++t) if constexpr (!SP) oacc[half * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ml, as_bf(f.v0[t][0], f.v1[t][0]), oacc[half * 4 + t], 0, 0, 0);
+            for (int t = 0; t < 4; ++t) if constexpr (!SP) oacc[half * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ml, sp_join(f.v0[t][0], f.v1[t][0]), oacc[half * 4 + t], 0, 0, 0);
 #pragma unroll
-            for (int t = 0; t < 4; ++t) if constexpr (!SP) oacc[half * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(mh, as_bf(f.v0[t][1], f.v1[t][1]), oacc[half * 4 + t], 0, 0, 0);
+            for (int t = 0; t < 4; ++t) if constexpr (!SP) oacc[half * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(mh, sp_join(f.v0[t][1], f.v1[t][1]), oacc[half * 4 + t], 0, 0, 0);
 #pragma unroll
-            for (int t = 0; t < 4; ++t) oacc[half * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(mh, as_bf(f.v0[t][0], f.v1[t][0]), oacc[half * 4 + t], 0, 0, 0);
+            for (int t = 0; t < 4; ++t) oacc[half * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(mh, sp_join(f.v0[t][0], f.v1[t][0]), oacc[half * 4 + t], 0, 0, 0);
         };
         reads(ub, I1{}, f1);
         __builtin_amdgcn_sched_barrier(0);
@@ -324,9 +289,9 @@ __device__ __forceinline__ void as_o_run(const AsStream& s, char* smem, const As
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (u + 1 < 16) {
             // unit u+1 has landed everywhere and every read of unit u has returned
-            if constexpr (u + 1 <= 10) asm volatile("s_waitcnt vmcnt(20) lgkmcnt(0)" ::: "memory");
-            else if constexpr (u + 1 == 11) asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory");
-            else if constexpr (u + 1 == 12) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            if constexpr (u + 1 <= 10) sp_wait<20>();
+            else if constexpr (u + 1 == 11) sp_wait<16>();
+            else if constexpr (u + 1 == 12) sp_wait<0>();
             else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             if constexpr (u + 7 < 16) as_o_issue<u + 7>(s, smem, L);
@@ -358,12 +323,12 @@ __device__ __forceinline__ AsPair as_pair(const AsLane& L, long long ld) {
 __device__ __forceinline__ void as_store_word(char* urow, const AsPair& q, unsigned w) {
     *reinterpret_cast<unsigned*>(urow + q.off) = __builtin_amdgcn_perm(as_xor1(w), w, q.sel);
 }
-__device__ __forceinline__ void as_store_tile(char* ubase, long long ld, const AsPair& q, const as_floatx16& v) {
+__device__ __forceinline__ void as_store_tile(char* ubase, long long ld, const AsPair& q, const sp_floatx16& v) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) as_store_word(ubase + (long long)((r & 3) + 8 * (r >> 2)) * ld, q, as_split1(v[r]));
+    for (int r = 0; r < 16; ++r) as_store_word(ubase + (long long)((r & 3) + 8 * (r >> 2)) * ld, q, bd_split1(v[r]));
 }
 // tile kt of the packed A operands back out as planes of the TRANSPOSED matrix [k][own row]: value r = element r&7 of step r>>3
-__device__ __forceinline__ void as_store_packed_tile(char* ubase, long long ld, const AsPair& q, const as_uint4 (&ah)[2], const as_uint4 (&al)[2]) {
+__device__ __forceinline__ void as_store_packed_tile(char* ubase, long long ld, const AsPair& q, const sp_uint4 (&ah)[2], const sp_uint4 (&al)[2]) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const unsigned hw = ah[r >> 3][(r & 7) >> 1], lw = al[r >> 3][(r & 7) >> 1];
@@ -372,14 +337,14 @@ __device__ __forceinline__ void as_store_packed_tile(char* ubase, long long ld, 
     }
 }
 // fp32 values of one tile (accumulator layout), times `mul`, -> packed A operands
-__device__ __forceinline__ void as_pack_tile(const as_floatx16& v, float mul, as_uint4 (&ah)[2], as_uint4 (&al)[2]) {
+__device__ __forceinline__ void as_pack_tile(const sp_floatx16& v, float mul, sp_uint4 (&ah)[2], sp_uint4 (&al)[2]) {
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const float a = __fmul_rn(v[8 * s + 2 * j], mul), b = __fmul_rn(v[8 * s + 2 * j + 1], mul);
-            ah[s][j] = as_pack_hi(a, b);
-            al[s][j] = as_pack_lo(a, b);
+            ah[s][j] = bd_pack_hi(a, b);
+            al[s][j] = bd_pack_lo(a, b);
         }
 }
 
@@ -396,8 +361,7 @@ struct AsParams {
 
 // workgroup -> (sample * heads + head, 128-row block); the two blocks of a sample are neighbours in one XCD's run (shared K / V in L2)
 __device__ __forceinline__ void as_coord(int& bh, int& blk) {
-    const unsigned L = blockIdx.x, T = gridDim.x, q = T >> 3;
-    const unsigned j = L < (q << 3) ? (L & 7) * q + (L >> 3) : L;
+    const unsigned j = xcd_tile_order();
     bh = j >> 1; blk = j & 1;
 }
 
@@ -412,7 +376,7 @@ __global__ __launch_bounds__(AS_NT, 1) void attn_sp_fwd_kernel(AsParams p) {
     const char* base = p.qkv + (long long)b * AS_N * p.ld + colq;
     const long long own0 = (long long)qb * 128 + L.wave * 32;
 
-    as_floatx16 acc[8];
+    sp_floatx16 acc[8];
 #pragma unroll
     for (int kt = 0; kt < 8; ++kt)
 #pragma unroll
@@ -439,9 +403,9 @@ __global__ __launch_bounds__(AS_NT, 1) void attn_sp_fwd_kernel(AsParams p) {
     const float inv = 1.0f / sum;
 
     // P as packed A operands, one key tile per unit of the first sweep (tile 0 now); P^T and the first half of O leave in the last units
-    as_uint4 ah[8][2], al[8][2];
+    sp_uint4 ah[8][2], al[8][2];
     as_pack_tile(acc[0], inv, ah[0], al[0]);
-    as_floatx16 oacc[8];
+    sp_floatx16 oacc[8];
 #pragma unroll
     for (int dt = 0; dt < 8; ++dt)
 #pragma unroll
@@ -487,7 +451,7 @@ __global__ __launch_bounds__(AS_NT, 1) void attn_sp_bwd_a_kernel(AsParams p) {
             for (int r = 0; r < 16; ++r)
                 pw[kt][r] = *reinterpret_cast<const unsigned*>(pt + (long long)(kt * 32 + (r & 3) + 8 * (r >> 2)) * (AS_N * 4) + pp.off);
     }
-    as_floatx16 acc[8];
+    sp_floatx16 acc[8];
 #pragma unroll
     for (int kt = 0; kt < 8; ++kt)
 #pragma unroll
@@ -518,10 +482,10 @@ __global__ __launch_bounds__(AS_NT, 1) void attn_sp_bwd_a_kernel(AsParams p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[kt][r] = p.scale * __builtin_bit_cast(float, pw[kt][r]) * (acc[kt][r] - delta);
     };
-    as_uint4 ah[8][2], al[8][2];
+    sp_uint4 ah[8][2], al[8][2];
     ds_tile(0);
     as_pack_tile(acc[0], 1.f, ah[0], al[0]);
-    as_floatx16 oacc[8];
+    sp_floatx16 oacc[8];
 #pragma unroll
     for (int dt = 0; dt < 8; ++dt)
 #pragma unroll
@@ -554,19 +518,19 @@ __global__ __launch_bounds__(AS_NT, 1) void attn_sp_bwd_b_kernel(AsParams p) {
     const AsPair pq = as_pair(L, p.lddqkv);
 
     // own 32 rows (keys) of a [N keys][N queries] plane matrix as A operands: chunk c, step s = 16 bytes of hi and of lo
-    auto load_slab = [&](const char* m, as_uint4 (&ah)[8][2], as_uint4 (&al)[8][2]) {
+    auto load_slab = [&](const char* m, sp_uint4 (&ah)[8][2], sp_uint4 (&al)[8][2]) {
         const char* row = m + (long long)bh * AS_N * AS_N * 4 + own0 * (AS_N * 4);   // uniform
         const unsigned off = (unsigned)(L.li * (AS_N * 4) + L.h * 16);
 #pragma unroll
         for (int c = 0; c < 8; ++c)
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
-                ah[c][s] = *reinterpret_cast<const as_uint4*>(row + c * 128 + s * 32 + off);
-                al[c][s] = *reinterpret_cast<const as_uint4*>(row + c * 128 + 64 + s * 32 + off);
+                ah[c][s] = *reinterpret_cast<const sp_uint4*>(row + c * 128 + s * 32 + off);
+                al[c][s] = *reinterpret_cast<const sp_uint4*>(row + c * 128 + 64 + s * 32 + off);
             }
     };
-    as_uint4 ah[8][2], al[8][2];
-    as_floatx16 oacc[8];
+    sp_uint4 ah[8][2], al[8][2];
+    sp_floatx16 oacc[8];
     char* orow = p.dqkv + ((long long)b * AS_N + own0) * p.lddqkv + colq;   // uniform; dk at + C*4, dv at + C*8
     auto run = [&](const AsStream& st, char* out) {
 #pragma unroll

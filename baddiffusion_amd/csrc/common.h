@@ -51,6 +51,40 @@ static inline bool mode_valid(int m) { return m == BD_MODE_F32 || mode_bf16(m); 
 static inline bool sp_mode_valid(int m) { return m == 0 || mode_bf16(m); }
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// log2 of a power of two, -1 for anything else
+static inline int ilog2_exact(int v) {
+    if (v <= 0 || (v & (v - 1))) return -1;
+    int l = 0;
+    while ((1 << l) < v) ++l;
+    return l;
+}
+// CU count of the current device (256 if the query fails), looked up once per process: the project drives one GPU per process, so the
+// first answer holds for every later call.
+static inline int device_cus() {
+    static const int cus = [] {
+        int dev = 0, n = 256;
+        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+        return n > 0 ? n : 256;
+    }();
+    return cus;
+}
+// K split of `nchunks` chunks over `tiles` output tiles on `slots` workgroup slots: as many splits as fill the slots (rounded down),
+// each at least `mincps` chunks long, and no empty split.
+static inline void split_k(int slots, long long tiles, int nchunks, int mincps, int& ksplit, int& cps) {
+    int ks = (int)(slots / tiles);
+    if (ks > nchunks / mincps) ks = nchunks / mincps;
+    if (ks < 1) ks = 1;
+    cps = (int)cdiv(nchunks, ks);
+    ksplit = (int)cdiv(nchunks, cps);
+}
+
+// XCD-contiguous order of a 1-D grid: workgroup L runs on XCD L % 8 and each XCD has its own L2, so every XCD is handed one contiguous
+// run of the logical order j and the tiles that share an operand panel meet in one L2.  Speed only; callers decompose j themselves.
+// (groupnorm.hip's gn_res_coord keeps its own `if` form of this line: its kernels take up to 30 more VGPRs behind the select.)
+__device__ __forceinline__ unsigned xcd_tile_order() {
+    const unsigned L = blockIdx.x, T = gridDim.x, q = T >> 3;
+    return L < (q << 3) ? (L & 7) * q + (L >> 3) : L;
+}
 
 // ---- wave64 reductions (DPP/shuffle, no LDS) --------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {

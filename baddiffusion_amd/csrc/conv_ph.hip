@@ -20,17 +20,11 @@
 // numerical difference to the literal form is that weights are summed (in fp32) before the split, ~1e-7 relative.  In the single-pass
 // mode (BD_MODE_BF16: hi*hi only) the rounded operand is the summed weight E, so the forward / data gradient differ from a product of the
 // rounded 3x3 weights by up to 2^-9 relative per E entry -- the same order as the mode's rounding itself.
-#include "common.h"
+#include "splitplane.h"
 
 #include <cstdlib>
 
 namespace bd {
-
-typedef float ph_floatx16 __attribute__((ext_vector_type(16)));
-typedef __bf16 ph_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 ph_bf16x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void* ph_lds_ptr;
-typedef const __attribute__((address_space(1))) void* ph_gbl_ptr;
 
 constexpr int PH_BM = 256, PH_BN = 128, PH_NT = 512, PH_STAGES = 3;
 constexpr int PH_A_BYTES = PH_BM * 128, PH_B_BYTES = PH_BN * 128, PH_STAGE_BYTES = PH_A_BYTES + PH_B_BYTES;
@@ -57,23 +51,11 @@ struct PhParams {
     PhClass cls[4];
 };
 
-__device__ __forceinline__ int ph_swz(int row) { return (row >> 1) & 7; }
-__device__ __attribute__((aligned(16))) const float kPhZero[4] = {0.f, 0.f, 0.f, 0.f};
-__device__ __forceinline__ void ph_dma16(const char* src, char* lds_dst) {
-    __builtin_amdgcn_global_load_lds((ph_gbl_ptr)src, (ph_lds_ptr)lds_dst, 16, 0, 0);
-}
-template <int N>
-__device__ __forceinline__ void ph_sync() {
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-}
-
 // y = out_scale * (acc + bias) (+ y) for a wave's 2 x 2 grid of 32x32 tiles; rows optionally scattered to one pixel class of the fine
 // grid.  FULL removes the per-element predicate (behind an exec-masked branch hipcc serialises the stores with s_waitcnt vmcnt(0),
 // DESIGN.md "a compiler trap"); the old values of an accumulating store are loaded first, all in flight.
 template <bool FULL>
-__device__ __forceinline__ void ph_epilogue(const PhParams& p, const ph_floatx16 (&acc)[2][2], int mw, int nw, int li, int h, int yoff) {
+__device__ __forceinline__ void ph_epilogue(const PhParams& p, const sp_floatx16 (&acc)[2][2], int mw, int nw, int li, int h, int yoff) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         long long rowoff[16];
@@ -95,7 +77,7 @@ __device__ __forceinline__ void ph_epilogue(const PhParams& p, const ph_floatx16
             if (p.accumulate) {
                 float old[16];
 #pragma unroll
-                for (int r = 0; r < 16; ++r) old[r] = *((FULL || rowoff[r] >= 0) ? p.y + rowoff[r] + n : kPhZero);   // branch-free
+                for (int r = 0; r < 16; ++r) old[r] = *((FULL || rowoff[r] >= 0) ? p.y + rowoff[r] + n : kSpZero);   // branch-free
 #pragma unroll
                 for (int r = 0; r < 16; ++r) v[r] += old[r];
             }
@@ -130,8 +112,7 @@ __global__ __launch_bounds__(PH_NT, 2) void conv_ph_kernel(PhParams p) {
 
     int tm, tn;
     {
-        const unsigned L = blockIdx.x, T = gridDim.x, q = T >> 3;
-        const unsigned j = L < (q << 3) ? (L & 7) * q + (L >> 3) : L;
+        const unsigned j = xcd_tile_order();
         tm = j / p.tiles_n;
         tn = j - tm * p.tiles_n;
     }
@@ -155,7 +136,7 @@ __global__ __launch_bounds__(PH_NT, 2) void conv_ph_kernel(PhParams p) {
         }
         vm[j] = m < p.M ? mask : 0;
         const long long row = ((long long)img * Hv + gy) * Wf + gx;
-        ap[j] = p.a + row * p.lda * 4 + ((ps ^ ph_swz(r)) << 4);
+        ap[j] = p.a + row * p.lda * 4 + ((ps ^ sp_swz(r)) << 4);
     }
     const char* wp[2];
 #pragma unroll
@@ -163,7 +144,7 @@ __global__ __launch_bounds__(PH_NT, 2) void conv_ph_kernel(PhParams p) {
         const int r = (wave + 8 * j) * 8 + dr;
         int n = n0 + r;
         if (n >= p.N) n = p.N - 1;
-        wp[j] = p.w + (long long)n * p.WT * p.C * 4 + ((ps ^ ph_swz(r)) << 4);
+        wp[j] = p.w + (long long)n * p.WT * p.C * 4 + ((ps ^ sp_swz(r)) << 4);
     }
     const int pix_bytes = (int)p.lda * 4;
     const int nchunks = ntaps * (p.C >> 5);
@@ -183,59 +164,26 @@ __global__ __launch_bounds__(PH_NT, 2) void conv_ph_kernel(PhParams p) {
         const int woff = __builtin_amdgcn_readlane(v_woff, tbase + q_t) + q_cb * 128;
         const int bit = 1 << q_t;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) ph_dma16((vm[j] & bit) ? ap[j] + aoff : reinterpret_cast<const char*>(kPhZero), stage + (wave + 8 * j) * 1024);
+        for (int j = 0; j < 4; ++j) sp_dma16((vm[j] & bit) ? ap[j] + aoff : reinterpret_cast<const char*>(kSpZero), stage + (wave + 8 * j) * 1024);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) ph_dma16(wp[j] + woff, stage + PH_A_BYTES + (wave + 8 * j) * 1024);
+        for (int j = 0; j < 2; ++j) sp_dma16(wp[j] + woff, stage + PH_A_BYTES + (wave + 8 * j) * 1024);
         if (++q_t == ntaps) { q_t = 0; ++q_cb; }
     };
 
     int foff[2][2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl) foff[s][pl] = li * 128 + (((pl * 4 + s * 2 + h) ^ ph_swz(li)) << 4);
+    sp_frag_offsets(foff, li, h);
     const int abase = wm * 64 * 128, bbase = PH_A_BYTES + wn * 64 * 128;
 
-    ph_floatx16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    sp_floatx16 acc[2][2] = {};
 
-    auto compute = [&](const char* stage) {
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            ph_bf16x8 ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                ah[i] = *reinterpret_cast<const ph_bf16x8*>(stage + abase + i * 4096 + foff[s][0]);
-                if constexpr (!SP) al[i] = *reinterpret_cast<const ph_bf16x8*>(stage + abase + i * 4096 + foff[s][1]);
-                bh[i] = *reinterpret_cast<const ph_bf16x8*>(stage + bbase + i * 4096 + foff[s][0]);
-                if constexpr (!SP) bl[i] = *reinterpret_cast<const ph_bf16x8*>(stage + bbase + i * 4096 + foff[s][1]);
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) if constexpr (!SP) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[q], acc[i][q], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) if constexpr (!SP) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[q], acc[i][q], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[q], acc[i][q], 0, 0, 0);
-        }
-    };
+    auto compute = [&](const char* stage) { sp_mma_chunk<SP>(stage + abase, stage + bbase, foff, acc); };
 
     // ring of three stages, any chunk count >= 1: chunk c+2 is issued behind the barrier that retires chunk c-1's stage
     // (three chunks per trip with the stage addresses as compile-time offsets: a rotating pointer triple makes every fragment
     //  address a run-time VALU add)
     char* const s0 = smem; char* const s1 = smem + PH_STAGE_BYTES; char* const s2 = smem + 2 * PH_STAGE_BYTES;
     auto step = [&](const char* cur, char* nxt, int c) {
-        if (c + 1 < nchunks) ph_sync<6>(); else ph_sync<0>();
+        if (c + 1 < nchunks) sp_sync<6>(); else sp_sync<0>();
         if (c + 2 < nchunks) issue(nxt);
         compute(cur);
     };
@@ -286,8 +234,6 @@ __global__ __launch_bounds__(256) void ph_tsplit_reduce(const float* __restrict_
 }
 
 // ---- weights of the upsample convolution ----------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned ph_pack_hi(float a, float b) { return bd_pack_hi(a, b); }   // common.h: the library's split
-__device__ __forceinline__ unsigned ph_pack_lo(float a, float b) { return bd_pack_lo(a, b); }
 // S(o) as a bit set over ky: o = -1 -> {2}, 0 -> {1,2}, 1 -> {0,1}, 2 -> {0}
 __device__ __host__ __forceinline__ int ph_set(int o) { return o == -1 ? 4 : (o == 0 ? 6 : (o == 1 ? 3 : 1)); }
 
@@ -315,14 +261,14 @@ __global__ __launch_bounds__(256) void ups_weff_kernel(const float* __restrict__
     {   // E: row co = cob*32 + r, 4 consecutive ci
         const float v0 = t[r][c4], v1 = t[r][c4 + 1], v2 = t[r][c4 + 2], v3 = t[r][c4 + 3];
         unsigned short* o = e_out + 2 * (((long long)(cob * 32 + r) * 16 + e) * Cin + cib * 32) + c4;
-        *reinterpret_cast<uint2*>(o) = make_uint2(ph_pack_hi(v0, v1), ph_pack_hi(v2, v3));
-        *reinterpret_cast<uint2*>(o + 32) = make_uint2(ph_pack_lo(v0, v1), ph_pack_lo(v2, v3));
+        *reinterpret_cast<uint2*>(o) = make_uint2(bd_pack_hi(v0, v1), bd_pack_hi(v2, v3));
+        *reinterpret_cast<uint2*>(o + 32) = make_uint2(bd_pack_lo(v0, v1), bd_pack_lo(v2, v3));
     }
     if (et_out) {   // E^T: row ci = cib*32 + r, 4 consecutive co  (the data gradient's operand: null for inference)
         const float v0 = t[c4][r], v1 = t[c4 + 1][r], v2 = t[c4 + 2][r], v3 = t[c4 + 3][r];
         unsigned short* o = et_out + 2 * (((long long)(cib * 32 + r) * 16 + e) * Cout + cob * 32) + c4;
-        *reinterpret_cast<uint2*>(o) = make_uint2(ph_pack_hi(v0, v1), ph_pack_hi(v2, v3));
-        *reinterpret_cast<uint2*>(o + 32) = make_uint2(ph_pack_lo(v0, v1), ph_pack_lo(v2, v3));
+        *reinterpret_cast<uint2*>(o) = make_uint2(bd_pack_hi(v0, v1), bd_pack_hi(v2, v3));
+        *reinterpret_cast<uint2*>(o + 32) = make_uint2(bd_pack_lo(v0, v1), bd_pack_lo(v2, v3));
     }
 }
 
@@ -349,18 +295,12 @@ __global__ __launch_bounds__(256) void ups_dweff_combine_kernel(const float* __r
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
-static int ph_ilog2(int v) {
-    if (v <= 0 || (v & (v - 1))) return -1;
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return l;
-}
 // (p, d) -> o for the forward classes: p = 0: d in {-1, 0} -> o in {2, 0};  p = 1: d in {0, 1} -> o in {1, -1}
 static int ph_o_of(int p, int d) { return p == 0 ? (d == -1 ? 2 : 0) : (d == 0 ? 1 : -1); }
 
 bool upsample_conv_ps_supported(int B, int H, int W, int Cin, int Cout) {
     static const bool off = getenv("BD_CONV_PHASE") && atoi(getenv("BD_CONV_PHASE")) == 0;
-    return !off && B > 0 && ph_ilog2(H) >= 0 && ph_ilog2(W) >= 0 && Cin % 128 == 0 && Cout % 128 == 0;
+    return !off && B > 0 && ilog2_exact(H) >= 0 && ilog2_exact(W) >= 0 && Cin % 128 == 0 && Cout % 128 == 0;
 }
 
 static int ph_launch(PhParams& p, bool sp, hipStream_t st, const char* what) {
@@ -379,12 +319,7 @@ static int ph_launch(PhParams& p, bool sp, hipStream_t st, const char* what) {
 }
 // tiles of a one-class launch on this device's CUs: below half a wave of workgroups the 16 taps are dealt to 4 groups
 static int ph_tap_groups(long long M, int N) {
-    static const int cus = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n;
-    }();
-    return cdiv(M, PH_BM) * (N / PH_BN) * 2 <= cus ? 4 : 1;
+    return cdiv(M, PH_BM) * (N / PH_BN) * 2 <= device_cus() ? 4 : 1;
 }
 size_t upsample_conv_dgrad_workspace_bytes(const bd_upsample_conv_desc& d) {
     const long long M = (long long)d.B * d.H * d.W;
@@ -395,14 +330,14 @@ static int ph_common(PhParams& p, int B, int H, int W, int C, int N, const void*
                      int mode, const char* who) {
     BD_CHECK(a && w && y, BD_ERR_INVALID, "%s: null pointer", who);
     BD_CHECK(sp_mode_valid(mode), BD_ERR_INVALID, "%s: unknown compute mode %d", who, mode);
-    BD_CHECK(B > 0 && ph_ilog2(H) >= 0 && ph_ilog2(W) >= 0, BD_ERR_UNSUPPORTED, "%s: H, W must be powers of two", who);
+    BD_CHECK(B > 0 && ilog2_exact(H) >= 0 && ilog2_exact(W) >= 0, BD_ERR_UNSUPPORTED, "%s: H, W must be powers of two", who);
     BD_CHECK(C > 0 && C % 32 == 0 && N > 0 && N % PH_BN == 0, BD_ERR_UNSUPPORTED, "%s: K channels %% 32 and N channels %% %d must be 0 (got %d, %d)",
              who, PH_BN, C, N);
     BD_CHECK(lda % 32 == 0 && ((uintptr_t)a & 127) == 0 && ((uintptr_t)w & 127) == 0, BD_ERR_UNSUPPORTED,
              "%s: split planes need ld %% 32 == 0 and 128-byte aligned bases", who);
     BD_CHECK((long long)B * H * W * 4 < (1ll << 31) && (long long)(4 * W + 4) * lda * 4 < (1ll << 31), BD_ERR_UNSUPPORTED, "%s: grid too large", who);
     p.a = reinterpret_cast<const char*>(a); p.w = reinterpret_cast<const char*>(w); p.y = y;
-    p.lda = lda; p.ldy = ldy; p.C = C; p.H = H; p.W = W; p.lw = ph_ilog2(W); p.lhw = ph_ilog2(W) + ph_ilog2(H);
+    p.lda = lda; p.ldy = ldy; p.C = C; p.H = H; p.W = W; p.lw = ilog2_exact(W); p.lhw = ilog2_exact(W) + ilog2_exact(H);
     p.M = B * H * W; p.N = N; p.out_scale = 1.f;
     return BD_OK;
 }

@@ -20,19 +20,13 @@
 // data gradient of the same convolution: dx[p][ci] = sum_{tap,co} dy[p - tap][co] * W[co][tap][ci] is the same kernel
 // with the gather direction negated (sign = -1) over the TRANSPOSED weight planes Wt[ci][tap][co] (bd_split_wt).
 // Replaces aten::convolution / convolution_backward(input) of resnet.py:493,514 for the stride-1 convolutions.
-#include "common.h"
+#include "splitplane.h"
 #include <string.h>
 
 #include <type_traits>
 #include <cstdlib>
 
 namespace bd {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void* lds_ptr;
-typedef const __attribute__((address_space(1))) void* gbl_ptr;
 
 constexpr int BD_WT_MAX = 64;   // weights per batched transpose launch (table passed by value)
 constexpr int PS_BM = 256, PS_BN = 128, PS_NT = 512, PS_STAGES = 3;
@@ -70,29 +64,6 @@ __device__ __forceinline__ int ps_v2r(int v, int lw, int lh, int lvw) {
     return (v - r) + (((r >> lvw) & ((1 << lh) - 1)) << lw) + ((r >> (lh + lvw)) << lvw) + (r & ((1 << lvw) - 1));
 }
 
-// bank swizzle of the 16-byte slots of a 128-byte LDS row (row stride 128 B = half a 256-byte bank row): rows r and
-// r^1 share a bank row, f spreads 16 consecutive rows over the 8 slots x 2 halves -> every ds_read_b128 lane group
-// (16 lanes = 16 different rows, same logical slot) touches each bank once.
-__device__ __forceinline__ int ps_swz(int row) { return (row >> 1) & 7; }
-
-// 16 zero bytes in the code object: the DMA source of lanes whose filter tap falls outside the image
-__device__ __attribute__((aligned(16))) const float kPsZero[4] = {0.f, 0.f, 0.f, 0.f};
-
-__device__ __forceinline__ void ps_dma16(const char* src, char* lds_dst) {
-    __builtin_amdgcn_global_load_lds((gbl_ptr)src, (lds_ptr)lds_dst, 16, 0, 0);
-}
-
-// wait until at most N of this wave's DMAs are outstanding AND all of its LDS reads have returned, then the workgroup
-// barrier: behind it the chunk is visible to every wave and the stage read last may be refilled.  Raw s_barrier: a
-// __syncthreads() would drain the DMAs in flight (vmcnt(0)).
-template <int N>
-__device__ __forceinline__ void ps_sync() {
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
-    else static_assert(N == 0, "unsupported vmcnt");
-    __builtin_amdgcn_s_barrier();
-}
-
 // Epilogue of a wave's TM x 2 grid of 32x32 accumulator tiles: y = out_scale * (acc + bias + rowbias + residual) (+ y).
 // The addends of a tile are loaded FIRST (16 independent loads each, all in flight), then combined and stored.  FULL
 // (wave-uniform: every row of the sub-tile is < M) removes the per-element predicate: behind an exec-masked branch per
@@ -103,7 +74,7 @@ __device__ __forceinline__ void ps_sync() {
 // STATS (round 4, conv_ps3_kernel only): st[q][0 / 1] += the lane's column sums of y and y * y over its 16 rows of every tile -- the
 // statistics of the GroupNorm that reads y next come out of this epilogue instead of a pass over y (ps3_gn_partials)
 template <int EPI, int TM, bool FULL, bool STATS = false>
-__device__ __forceinline__ void ps_epilogue(const PsParams& p, floatx16 (&acc)[TM][2], const int (&mb)[TM], int nw, int li, int h,
+__device__ __forceinline__ void ps_epilogue(const PsParams& p, sp_floatx16 (&acc)[TM][2], const int (&mb)[TM], int nw, int li, int h,
                                             float (*st)[2] = nullptr) {
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -198,11 +169,10 @@ __global__ __launch_bounds__(PS_NT, 2) void conv_ps_kernel(PsParams p) {
     const int wm = wave >> 1, wn = wave & 1;
     const int li = lane & 31, h = lane >> 5;
 
-    // XCD-contiguous tile order (n fastest): tiles sharing an A panel meet in one L2 (igemm.hip wg_coord)
+    // XCD-contiguous tile order (n fastest): tiles sharing an A panel meet in one L2 (common.h xcd_tile_order)
     int tm, tn;
     {
-        const unsigned L = blockIdx.x, T = gridDim.x, q = T >> 3;
-        const unsigned j = L < (q << 3) ? (L & 7) * q + (L >> 3) : L;
+        const unsigned j = xcd_tile_order();
         tm = j / p.tiles_n;
         tn = j - tm * p.tiles_n;
     }
@@ -225,7 +195,7 @@ __global__ __launch_bounds__(PS_NT, 2) void conv_ps_kernel(PsParams p) {
             if ((unsigned)yy < (unsigned)p.H && (unsigned)xx < (unsigned)p.W) mask |= 1 << t;
         }
         vm[j] = m < p.M ? mask : 0;
-        ap[j] = p.a + (long long)m * p.lda * 4 + ((ps ^ ps_swz(r)) << 4);
+        ap[j] = p.a + (long long)m * p.lda * 4 + ((ps ^ sp_swz(r)) << 4);
     }
     const char* wp[2];
 #pragma unroll
@@ -233,7 +203,7 @@ __global__ __launch_bounds__(PS_NT, 2) void conv_ps_kernel(PsParams p) {
         const int r = (wave + 8 * j) * 8 + dr;
         int n = n0 + r;
         if (n >= p.N) n = p.N - 1;
-        wp[j] = p.w + (long long)n * 36 * p.C + ((ps ^ ps_swz(r)) << 4);
+        wp[j] = p.w + (long long)n * 36 * p.C + ((ps ^ sp_swz(r)) << 4);
     }
     const int pix_bytes = (int)p.lda * 4;   // bytes between pixels (host checks (W + 1) * pix_bytes < 2^31)
     const int nchunks = 9 * (p.C >> 5);
@@ -244,9 +214,9 @@ __global__ __launch_bounds__(PS_NT, 2) void conv_ps_kernel(PsParams p) {
     int q_aoff = -p.sign * (p.W + 1) * pix_bytes, q_woff = 0;   // tap (0,0) of block 0
     auto issue = [&](char* stage) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) ps_dma16((vm[j] & q_bit) ? ap[j] + q_aoff : reinterpret_cast<const char*>(kPsZero), stage + (wave + 8 * j) * 1024);
+        for (int j = 0; j < 4; ++j) sp_dma16((vm[j] & q_bit) ? ap[j] + q_aoff : reinterpret_cast<const char*>(kSpZero), stage + (wave + 8 * j) * 1024);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) ps_dma16(wp[j] + q_woff, stage + PS_A_BYTES + (wave + 8 * j) * 1024);
+        for (int j = 0; j < 2; ++j) sp_dma16(wp[j] + q_woff, stage + PS_A_BYTES + (wave + 8 * j) * 1024);
         // advance: kw fastest; a full window moves on to the next 32-channel block
         q_bit <<= 1;
         q_woff += p.C * 4;
@@ -264,45 +234,12 @@ __global__ __launch_bounds__(PS_NT, 2) void conv_ps_kernel(PsParams p) {
 
     // ---- fragment addresses: lane -> row li of a 32-row tile, k octet h; logical slot = plane*4 + step*2 + h
     int foff[2][2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl) foff[s][pl] = li * 128 + (((pl * 4 + s * 2 + h) ^ ps_swz(li)) << 4);
+    sp_frag_offsets(foff, li, h);
     const int abase = wm * 64 * 128, bbase = PS_A_BYTES + wn * 64 * 128;
 
-    floatx16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    sp_floatx16 acc[2][2] = {};
 
-    auto compute = [&](const char* stage) {
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            bf16x8 ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                ah[i] = *reinterpret_cast<const bf16x8*>(stage + abase + i * 4096 + foff[s][0]);
-                if constexpr (!SP) al[i] = *reinterpret_cast<const bf16x8*>(stage + abase + i * 4096 + foff[s][1]);
-                bh[i] = *reinterpret_cast<const bf16x8*>(stage + bbase + i * 4096 + foff[s][0]);
-                if constexpr (!SP) bl[i] = *reinterpret_cast<const bf16x8*>(stage + bbase + i * 4096 + foff[s][1]);
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) if constexpr (!SP) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[q], acc[i][q], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) if constexpr (!SP) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[q], acc[i][q], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[q], acc[i][q], 0, 0, 0);
-        }
-    };
+    auto compute = [&](const char* stage) { sp_mma_chunk<SP>(stage + abase, stage + bbase, foff, acc); };
 
     char* const st0 = smem;
     char* const st1 = smem + PS_STAGE_BYTES;
@@ -315,13 +252,13 @@ __global__ __launch_bounds__(PS_NT, 2) void conv_ps_kernel(PsParams p) {
     // chunk c+1 in flight), barrier (chunk c visible to everyone, chunk c-1's stage free), refill that stage with chunk c+2
     const int trips = nchunks / 3;
     for (int t = 0; t + 1 < trips; ++t) {
-        ps_sync<6>(); issue(st2); compute(st0);
-        ps_sync<6>(); issue(st0); compute(st1);
-        ps_sync<6>(); issue(st1); compute(st2);
+        sp_sync<6>(); issue(st2); compute(st0);
+        sp_sync<6>(); issue(st0); compute(st1);
+        sp_sync<6>(); issue(st1); compute(st2);
     }
-    ps_sync<6>(); issue(st2); compute(st0);
-    ps_sync<6>(); compute(st1);
-    ps_sync<0>(); compute(st2);
+    sp_sync<6>(); issue(st2); compute(st0);
+    sp_sync<6>(); compute(st1);
+    sp_sync<0>(); compute(st2);
 
     // ---- epilogue: lane holds column n = li of rows (r&3) + 8*(r>>2) + 4*h of every 32x32 tile
     const int mw = m0 + wm * 64, nw = n0 + wn * 64;
@@ -352,8 +289,7 @@ __global__ __launch_bounds__(PS_NT, 2) void conv_ps3_kernel(PsParams p) {
     const int li = lane & 31, h = lane >> 5;
     int tm, tn;
     {
-        const unsigned L = blockIdx.x, T = gridDim.x, q = T >> 3;
-        const unsigned j = L < (q << 3) ? (L & 7) * q + (L >> 3) : L;
+        const unsigned j = xcd_tile_order();
         tm = j / p.tiles_n;
         tn = j - tm * p.tiles_n;
     }
@@ -381,7 +317,7 @@ __global__ __launch_bounds__(PS_NT, 2) void conv_ps3_kernel(PsParams p) {
                 if ((unsigned)(x + p.sign * (kx - 1)) < (unsigned)p.W) mask |= 1 << kx;
         }
         vm[j] = mask;
-        ap[j] = p.a + (long long)m * p.lda * 4 + ((ps ^ ps_swz(wr)) << 4);
+        ap[j] = p.a + (long long)m * p.lda * 4 + ((ps ^ sp_swz(wr)) << 4);
     }
     const char* wp[2];
 #pragma unroll
@@ -389,7 +325,7 @@ __global__ __launch_bounds__(PS_NT, 2) void conv_ps3_kernel(PsParams p) {
         const int r = (wave + 8 * j) * 8 + dr;
         int n = n0 + r;
         if (n >= p.N) n = p.N - 1;
-        wp[j] = p.w + (long long)n * 36 * p.C + ((ps ^ ps_swz(r)) << 4);
+        wp[j] = p.w + (long long)n * 36 * p.C + ((ps ^ sp_swz(r)) << 4);
     }
     const int pix_bytes = (int)p.lda * 4;
     const int ngroups = 3 * (p.C >> 5);          // (channel block, kx)
@@ -401,60 +337,28 @@ __global__ __launch_bounds__(PS_NT, 2) void conv_ps3_kernel(PsParams p) {
         const int aoff = p.sign * (ga_kx - 1) * pix_bytes + ga_cb * 128;
         const int bit = 1 << ga_kx;
 #pragma unroll
-        for (int j = 0; j < 5; ++j) ps_dma16((vm[j] & bit) ? ap[j] + aoff : reinterpret_cast<const char*>(kPsZero), win + (wave + 8 * j) * 1024);
+        for (int j = 0; j < 5; ++j) sp_dma16((vm[j] & bit) ? ap[j] + aoff : reinterpret_cast<const char*>(kSpZero), win + (wave + 8 * j) * 1024);
         if (++ga_kx == 3) { ga_kx = 0; ++ga_cb; }
     };
     int gb_ky = 0, gb_kx = 0, gb_cb = 0;
     auto issue_b = [&](char* slot) {
         const int woff = ((gb_ky * 3 + gb_kx) * p.C + gb_cb * 32) * 4;
 #pragma unroll
-        for (int j = 0; j < 2; ++j) ps_dma16(wp[j] + woff, slot + (wave + 8 * j) * 1024);
+        for (int j = 0; j < 2; ++j) sp_dma16(wp[j] + woff, slot + (wave + 8 * j) * 1024);
         if (++gb_ky == 3) { gb_ky = 0; if (++gb_kx == 3) { gb_kx = 0; ++gb_cb; } }
     };
 
     int foff[2][2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl) foff[s][pl] = li * 128 + (((pl * 4 + s * 2 + h) ^ ps_swz(li)) << 4);
+    sp_frag_offsets(foff, li, h);
     const int abase = wm * 64 * 128, bbase = wn * 64 * 128;
     // vertical tap ky of the forward gather reads window rows r + ky*VW; the data-gradient gather (sign -1) mirrors it
     const int wrow_bytes = VW * 128;
 
-    floatx16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    sp_floatx16 acc[2][2] = {};
 
     auto compute = [&](const char* win, const char* bslot, int ky) {
         const char* a0 = win + abase + (p.sign > 0 ? ky : 2 - ky) * wrow_bytes;
-        const char* b0 = bslot + bbase;
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            bf16x8 ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                ah[i] = *reinterpret_cast<const bf16x8*>(a0 + i * 4096 + foff[s][0]);
-                if constexpr (!SP) al[i] = *reinterpret_cast<const bf16x8*>(a0 + i * 4096 + foff[s][1]);
-                bh[i] = *reinterpret_cast<const bf16x8*>(b0 + i * 4096 + foff[s][0]);
-                if constexpr (!SP) bl[i] = *reinterpret_cast<const bf16x8*>(b0 + i * 4096 + foff[s][1]);
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) if constexpr (!SP) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[q], acc[i][q], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) if constexpr (!SP) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[q], acc[i][q], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[q], acc[i][q], 0, 0, 0);
-        }
+        sp_mma_chunk<SP>(a0, bslot + bbase, foff, acc);
     };
 
     char* const A0 = smem; char* const A1 = smem + PS3_A_BYTES;
@@ -467,24 +371,21 @@ __global__ __launch_bounds__(PS_NT, 2) void conv_ps3_kernel(PsParams p) {
     issue_a(A0);
     issue_b(B0);
     issue_b(B1);
-    auto sync2 = [&]() { asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); };
-    auto sync7 = [&]() { asm volatile("s_waitcnt vmcnt(7) lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); };
-    auto sync0 = [&]() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); };
     // two groups (six chunks) per trip so that the A windows and the three weight slots are compile-time addresses
     for (int g = 0; g < ngroups; g += 2) {
         const bool more1 = g + 1 < ngroups, more2 = g + 2 < ngroups;
         // group g on A0: chunks 3g .. 3g+2 on slots (3g) % 3 = 0, 1, 2 (3g is a multiple of 3)
-        sync2(); if (more1) issue_a(A1); issue_b(B2); compute(A0, B0, 0);
-        if (more1) sync7(); else sync2();
+        sp_sync<2>(); if (more1) issue_a(A1); issue_b(B2); compute(A0, B0, 0);
+        if (more1) sp_sync<7>(); else sp_sync<2>();
         if (more1) issue_b(B0); compute(A0, B1, 1);
-        if (more1) sync2(); else sync0();
+        if (more1) sp_sync<2>(); else sp_sync<0>();
         if (more1) issue_b(B1); compute(A0, B2, 2);
         if (!more1) break;
         // group g + 1 on A1
-        sync2(); if (more2) issue_a(A0); issue_b(B2); compute(A1, B0, 0);
-        if (more2) sync7(); else sync2();
+        sp_sync<2>(); if (more2) issue_a(A0); issue_b(B2); compute(A1, B0, 0);
+        if (more2) sp_sync<7>(); else sp_sync<2>();
         if (more2) issue_b(B0); compute(A1, B1, 1);
-        if (more2) sync2(); else sync0();
+        if (more2) sp_sync<2>(); else sp_sync<0>();
         if (more2) issue_b(B1); compute(A1, B2, 2);
     }
     (void)nchunks;
@@ -530,8 +431,7 @@ __global__ __launch_bounds__(512, STAGES == 2 ? 4 : 2) void conv_ps128_kernel(Ps
     const int li = lane & 31, h = lane >> 5;
     int tm, tn, zz;
     {
-        const unsigned L = blockIdx.x, T = gridDim.x, q = T >> 3;
-        const unsigned j = L < (q << 3) ? (L & 7) * q + (L >> 3) : L;
+        const unsigned j = xcd_tile_order();
         const unsigned ntiles = p.tiles_m * p.tiles_n;
         zz = j / ntiles;
         const unsigned tile = j - zz * ntiles;
@@ -559,10 +459,10 @@ __global__ __launch_bounds__(512, STAGES == 2 ? 4 : 2) void conv_ps128_kernel(Ps
             if ((unsigned)yy < (unsigned)p.H && (unsigned)xx < (unsigned)p.W) mask |= 1 << t;
         }
         vm[j] = m < p.M ? mask : 0;
-        ap[j] = p.a + (long long)m * p.lda * 4 + ((ps ^ ps_swz(r)) << 4);
+        ap[j] = p.a + (long long)m * p.lda * 4 + ((ps ^ sp_swz(r)) << 4);
         int n = n0 + r;
         if (n >= p.N) n = p.N - 1;
-        wp[j] = p.w + (long long)n * 36 * p.C + ((ps ^ ps_swz(r)) << 4);
+        wp[j] = p.w + (long long)n * 36 * p.C + ((ps ^ sp_swz(r)) << 4);
     }
     const int pix_bytes = (int)p.lda * 4;
     int q_cb = c_begin / 9;
@@ -573,8 +473,8 @@ __global__ __launch_bounds__(512, STAGES == 2 ? 4 : 2) void conv_ps128_kernel(Ps
     auto issue = [&](char* stage) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            ps_dma16((vm[j] & q_bit) ? ap[j] + q_aoff : reinterpret_cast<const char*>(kPsZero), stage + (wave + 8 * j) * 1024);
-            ps_dma16(wp[j] + q_woff, stage + A_BYTES + (wave + 8 * j) * 1024);
+            sp_dma16((vm[j] & q_bit) ? ap[j] + q_aoff : reinterpret_cast<const char*>(kSpZero), stage + (wave + 8 * j) * 1024);
+            sp_dma16(wp[j] + q_woff, stage + A_BYTES + (wave + 8 * j) * 1024);
         }
         q_bit <<= 1;
         q_woff += p.C * 4;
@@ -590,39 +490,15 @@ __global__ __launch_bounds__(512, STAGES == 2 ? 4 : 2) void conv_ps128_kernel(Ps
         }
     };
     int foff[2][2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl) foff[s][pl] = li * 128 + (((pl * 4 + s * 2 + h) ^ ps_swz(li)) << 4);
+    sp_frag_offsets(foff, li, h);
     const int abase = wm * 32 * 128, bbase = A_BYTES + wn * 64 * 128;
-    floatx16 acc[2];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { acc[0][r] = 0.f; acc[1][r] = 0.f; }
-    auto compute = [&](const char* stage) {
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const bf16x8 ah = *reinterpret_cast<const bf16x8*>(stage + abase + foff[s][0]);
-            const bf16x8 al = SP ? bf16x8{} : *reinterpret_cast<const bf16x8*>(stage + abase + foff[s][1]);
-            bf16x8 bh[2], bl[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                bh[i] = *reinterpret_cast<const bf16x8*>(stage + bbase + i * 4096 + foff[s][0]);
-                if constexpr (!SP) bl[i] = *reinterpret_cast<const bf16x8*>(stage + bbase + i * 4096 + foff[s][1]);
-            }
-#pragma unroll
-            for (int q = 0; q < 2; ++q) if constexpr (!SP) acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[q], acc[q], 0, 0, 0);
-#pragma unroll
-            for (int q = 0; q < 2; ++q) if constexpr (!SP) acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[q], acc[q], 0, 0, 0);
-#pragma unroll
-            for (int q = 0; q < 2; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[q], acc[q], 0, 0, 0);
-        }
-    };
+    sp_floatx16 acc[1][2] = {};
+    auto compute = [&](const char* stage) { sp_mma_chunk<SP>(stage + abase, stage + bbase, foff, acc); };
     const int n = c_end - c_begin;
     if constexpr (STAGES == 2) {
         if (n > 0) issue(smem);
         for (int c = 0; c < n; ++c) {
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
+            sp_sync<0>();
             if (c + 1 < n) issue(smem + ((c + 1) & 1) * STAGE);
             compute(smem + (c & 1) * STAGE);
         }
@@ -634,9 +510,9 @@ __global__ __launch_bounds__(512, STAGES == 2 ? 4 : 2) void conv_ps128_kernel(Ps
             if (k < n) issue(smem + k * STAGE);
         for (int c = 0; c < n; ++c) {
             const int later = (n < c + STAGES - 1 ? n : c + STAGES - 1) - (c + 1);      // chunks issued after chunk c (wave-uniform)
-            if (later >= 2) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
-            else if (later == 1) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            if (later >= 2) sp_wait<8>();
+            else if (later == 1) sp_wait<4>();
+            else sp_wait<0>();
             __builtin_amdgcn_s_barrier();
             if (c + STAGES - 1 < n) issue(smem + ((c + STAGES - 1) % STAGES) * STAGE);
             compute(smem + (c % STAGES) * STAGE);
@@ -651,21 +527,20 @@ __global__ __launch_bounds__(512, STAGES == 2 ? 4 : 2) void conv_ps128_kernel(Ps
             const int nn = nw + q * 32 + li;
             if (full) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) out[(long long)(mw + (r & 3) + 8 * (r >> 2) + 4 * h) * p.N + nn] = acc[q][r];
+                for (int r = 0; r < 16; ++r) out[(long long)(mw + (r & 3) + 8 * (r >> 2) + 4 * h) * p.N + nn] = acc[0][q][r];
             } else {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int m = mw + (r & 3) + 8 * (r >> 2) + 4 * h;
-                    if (m < p.M) out[(long long)m * p.N + nn] = acc[q][r];
+                    if (m < p.M) out[(long long)m * p.N + nn] = acc[0][q][r];
                 }
             }
         }
         return;
     }
-    floatx16 a2[1][2] = {{acc[0], acc[1]}};
     const int mb[1] = {mw};
-    if (full) ps_epilogue<EPI, 1, true>(p, a2, mb, nw, li, h);
-    else ps_epilogue<EPI, 1, false>(p, a2, mb, nw, li, h);
+    if (full) ps_epilogue<EPI, 1, true>(p, acc, mb, nw, li, h);
+    else ps_epilogue<EPI, 1, false>(p, acc, mb, nw, li, h);
 }
 
 // second pass of the K split: fixed-order sum of the slabs + the epilogue, float4 per thread (N % 4 == 0)
@@ -732,32 +607,6 @@ struct PsWgParams {
     int lh, lvw;                       // conv_ps_wgrad3_kernel: log2(H), log2 of the virtual image width min(W, 32) (ps_v2r)
 };
 
-typedef short ps_short4 __attribute__((ext_vector_type(4)));
-typedef short ps_short8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) ps_short4 ps_lds_short4;
-
-__device__ __forceinline__ bf16x8 ps_tr_frag(const char* lds, int off) {
-    const ps_short4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ps_lds_short4*)(lds + off));
-    const ps_short4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ps_lds_short4*)(lds + off + 4 * 512));
-    const ps_short8 v = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8, v);
-}
-
-// The same read as inline asm, address = LDS byte offset.  hipcc puts `s_waitcnt vmcnt(0)` in front of the intrinsic form
-// whenever LDS-DMA loads are in flight (it cannot tell the stage being read from the stage being filled), so every chunk
-// waited for the NEXT chunk's DMA before its first fragment read.  The asm form is opaque to that pass; the matching
-// s_waitcnt lgkmcnt(0) is tied to the fragment registers so that no consumer can be scheduled above it.
-template <int OFF>
-__device__ __forceinline__ ps_short4 ps_tr_read(unsigned addr) {
-    ps_short4 v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-    return v;
-}
-__device__ __forceinline__ bf16x8 ps_tr_join(ps_short4 v0, ps_short4 v1) {
-    const ps_short8 v = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8, v);
-}
-
 // STAGES = 2 and NW = 8 only: two LDS stages, the chunk c+1 is fetched while chunk c computes; waves 4 x 2, 32 x 64 each.  (NW = 4 --
 // waves 2 x 2 of 64 x 64, a third fewer LDS fragment reads per MFMA -- measured within +-2 % of NW = 8 on every layer; one form is kept.)
 // Both stay template parameters: the kernel's name, which profiles match on.
@@ -780,8 +629,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_ps_wgrad_kernel(PsWgParams p)
     // logical order: n fastest, then m, then the K split; one contiguous run per XCD (same k-slice -> same L2)
     int tm, tn, zz;
     {
-        const unsigned L = blockIdx.x, T = gridDim.x, q = T >> 3;
-        const unsigned j = L < (q << 3) ? (L & 7) * q + (L >> 3) : L;
+        const unsigned j = xcd_tile_order();
         const unsigned ntiles = p.tiles_m * p.tiles_n;
         zz = j / ntiles;
         const unsigned tile = j - zz * ntiles;
@@ -826,12 +674,12 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_ps_wgrad_kernel(PsWgParams p)
         const bool ok = in && (unsigned)(y + dyt) < (unsigned)p.H && (unsigned)(x + dxt) < (unsigned)p.W;
         if constexpr (PH) {
             const long long fr = 4ll * pp - 2 * x + fine_off;       // pixel (2a+p, 2b+q) of the fine grid, x = pp & (W-1)
-            ps_dma16(in ? asrc[j] + fr * p.lddy * 4 : reinterpret_cast<const char*>(kPsZero), stage + (wave + NW * j) * 1024);
+            sp_dma16(in ? asrc[j] + fr * p.lddy * 4 : reinterpret_cast<const char*>(kSpZero), stage + (wave + NW * j) * 1024);
         } else {
-            ps_dma16(in ? asrc[j] : reinterpret_cast<const char*>(kPsZero), stage + (wave + NW * j) * 1024);
+            sp_dma16(in ? asrc[j] : reinterpret_cast<const char*>(kSpZero), stage + (wave + NW * j) * 1024);
             asrc[j] += a_adv;
         }
-        ps_dma16(ok ? bsrc[j] : reinterpret_cast<const char*>(kPsZero), stage + WG_OP_BYTES + (wave + NW * j) * 1024);
+        sp_dma16(ok ? bsrc[j] : reinterpret_cast<const char*>(kSpZero), stage + WG_OP_BYTES + (wave + NW * j) * 1024);
         bsrc[j] += b_adv;
     };
     auto issue = [&](char* stage) {
@@ -849,14 +697,14 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_ps_wgrad_kernel(PsWgParams p)
     for (int v = 0; v < 4; ++v) xw[v] = (v ^ kq) << 6;
     auto foff = [&](int t, int plane, int kk) { return lane_base + xw[(t & 1) * 2 + plane] + (t >> 1) * 256 + kk * 512; };
 
-    floatx16 acc[TMW][2], accb[TMW];
+    sp_floatx16 acc[TMW][2], accb[TMW];
 #pragma unroll
     for (int i = 0; i < TMW; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) { acc[i][0][r] = 0.f; acc[i][1][r] = 0.f; accb[i][r] = 0.f; }
     // wave-uniform.  PH: the (dy, dx) = (0, 0) entry of each pixel class (taps 5, 6, 9, 10), first channel block
     const bool do_db = p.want_db && wn == 0 && (PH ? (dyt == 0 && dxt == 0 && ci0 == 0) : tn == 0);
-    bf16x8 ones;
+    sp_bf16x8 ones;
 #pragma unroll
     for (int j = 0; j < 8; ++j) ones[j] = (__bf16)1.0f;
 
@@ -870,9 +718,9 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_ps_wgrad_kernel(PsWgParams p)
     for (int q = 0; q < 2; ++q)
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl) boff[q][pl] = (unsigned)foff(wn * 2 + q, pl, 0) + WG_OP_BYTES;
-    const unsigned smem_addr = (unsigned)(uintptr_t)(lds_ptr)smem;
+    const unsigned smem_addr = (unsigned)(uintptr_t)(sp_lds_ptr)smem;
 
-    struct Frag { ps_short4 a0[TMW][2], a1[TMW][2], b0[2][2], b1[2][2]; };
+    struct Frag { sp_short4 a0[TMW][2], a1[TMW][2], b0[2][2], b1[2][2]; };
     auto reads = [&](auto S, unsigned sbase, Frag& f) {
         constexpr int KOFF = decltype(S)::value * 16 * 512;
 #pragma unroll
@@ -880,16 +728,16 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_ps_wgrad_kernel(PsWgParams p)
 #pragma unroll
             for (int pl = 0; pl < 2; ++pl) {
                 if (SP && pl == 1 && !do_db) continue;   // single pass: dY's lo plane feeds the bias gradient only
-                f.a0[i][pl] = ps_tr_read<KOFF>(sbase + aoff[i][pl]);
-                f.a1[i][pl] = ps_tr_read<KOFF + 4 * 512>(sbase + aoff[i][pl]);
+                f.a0[i][pl] = sp_read_tr<KOFF>(sbase + aoff[i][pl]);
+                f.a1[i][pl] = sp_read_tr<KOFF + 4 * 512>(sbase + aoff[i][pl]);
             }
 #pragma unroll
         for (int q = 0; q < 2; ++q)
 #pragma unroll
             for (int pl = 0; pl < 2; ++pl) {
                 if (SP && pl == 1) continue;
-                f.b0[q][pl] = ps_tr_read<KOFF>(sbase + boff[q][pl]);
-                f.b1[q][pl] = ps_tr_read<KOFF + 4 * 512>(sbase + boff[q][pl]);
+                f.b0[q][pl] = sp_read_tr<KOFF>(sbase + boff[q][pl]);
+                f.b1[q][pl] = sp_read_tr<KOFF + 4 * 512>(sbase + boff[q][pl]);
             }
     };
     // all LDS reads of this wave have returned; the fragment registers pass through the asm so no MFMA can move above it
@@ -899,11 +747,11 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_ps_wgrad_kernel(PsWgParams p)
                        "+v"(f.b0[0][1]), "+v"(f.b1[0][1]), "+v"(f.b0[1][0]), "+v"(f.b1[1][0]), "+v"(f.b0[1][1]), "+v"(f.b1[1][1]));
     };
     auto mfmas = [&](const Frag& f) {
-        bf16x8 ah[TMW], al[TMW], bh[2], bl[2];
+        sp_bf16x8 ah[TMW], al[TMW], bh[2], bl[2];
 #pragma unroll
-        for (int i = 0; i < TMW; ++i) { ah[i] = ps_tr_join(f.a0[i][0], f.a1[i][0]); al[i] = ps_tr_join(f.a0[i][1], f.a1[i][1]); }
+        for (int i = 0; i < TMW; ++i) { ah[i] = sp_join(f.a0[i][0], f.a1[i][0]); al[i] = sp_join(f.a0[i][1], f.a1[i][1]); }
 #pragma unroll
-        for (int q = 0; q < 2; ++q) { bh[q] = ps_tr_join(f.b0[q][0], f.b1[q][0]); bl[q] = ps_tr_join(f.b0[q][1], f.b1[q][1]); }
+        for (int q = 0; q < 2; ++q) { bh[q] = sp_join(f.b0[q][0], f.b1[q][0]); bl[q] = sp_join(f.b0[q][1], f.b1[q][1]); }
 #pragma unroll
         for (int i = 0; i < TMW; ++i)
 #pragma unroll
@@ -948,8 +796,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_ps_wgrad_kernel(PsWgParams p)
     const int n = c_end - c_begin;
     if (n > 0) issue(smem);
     for (int c = 0; c < n; ++c) {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
+        sp_sync<0>();
         chunk(smem + (c & 1) * WG_STAGE_BYTES, c + 1 < n ? smem + ((c + 1) & 1) * WG_STAGE_BYTES : nullptr);
     }
 
@@ -1002,8 +849,7 @@ __global__ __launch_bounds__(512, 2) void conv_ps_wgrad3_kernel(PsWgParams p) {
     const int wm = wave >> 2, wn = wave & 3;       // wave tile = 64 co (two 32-row blocks) x 3 taps x 32 ci: 20 fragment reads per 18 MFMAs (32 x 64: 28)
     int tm, tn, zz;
     {
-        const unsigned L = blockIdx.x, T = gridDim.x, q = T >> 3;
-        const unsigned j = L < (q << 3) ? (L & 7) * q + (L >> 3) : L;
+        const unsigned j = xcd_tile_order();
         const unsigned ntiles = p.tiles_m * p.tiles_n;
         zz = j / ntiles;
         const unsigned tile = j - zz * ntiles;
@@ -1037,7 +883,7 @@ __global__ __launch_bounds__(512, 2) void conv_ps_wgrad3_kernel(PsWgParams p) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const long long pp = ps_v2r(c * 32 + kpix[j], p.lw, p.lh, p.lvw);       // chunk c = 32 VIRTUAL pixels (one strip row when W > 32)
-            ps_dma16(abase_g[j] + pp * p.lddy * 4, stage + (wave + 8 * j) * 1024);
+            sp_dma16(abase_g[j] + pp * p.lddy * 4, stage + (wave + 8 * j) * 1024);
         }
     };
     const int VW = 1 << p.lvw;
@@ -1051,7 +897,7 @@ __global__ __launch_bounds__(512, 2) void conv_ps_wgrad3_kernel(PsWgParams p) {
             const int x = sr & (p.W - 1);
             const bool ok = s >= 0 && s < p.P && (unsigned)(x + dxt) < (unsigned)p.W;
             const int unit = ((s0 + 4096) >> 4) & (WG3_RING_UNITS - 1);
-            ps_dma16(ok ? bbase_g[j] + (long long)(sr + dxt) * p.ldx * 4 : reinterpret_cast<const char*>(kPsZero),
+            sp_dma16(ok ? bbase_g[j] + (long long)(sr + dxt) * p.ldx * 4 : reinterpret_cast<const char*>(kSpZero),
                      ring + unit * WG3_UNIT_BYTES + (s0 & 15) * 512);
         }
     };
@@ -1071,10 +917,10 @@ __global__ __launch_bounds__(512, 2) void conv_ps_wgrad3_kernel(PsWgParams p) {
         for (int pl = 0; pl < 2; ++pl) aoff[i][pl] = (unsigned)foff(wm * 2 + i, pl);
 #pragma unroll
     for (int pl = 0; pl < 2; ++pl) boff[pl] = (unsigned)foff(wn, pl);
-    const unsigned smem_addr = (unsigned)(uintptr_t)(lds_ptr)smem;
+    const unsigned smem_addr = (unsigned)(uintptr_t)(sp_lds_ptr)smem;
     const unsigned ring_addr = smem_addr + 2 * WG_OP_BYTES;
 
-    floatx16 acc[3][2], accb[2];          // acc[tap][co block]
+    sp_floatx16 acc[3][2], accb[2];          // acc[tap][co block]
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         accb[0][r] = 0.f; accb[1][r] = 0.f;
@@ -1082,30 +928,30 @@ __global__ __launch_bounds__(512, 2) void conv_ps_wgrad3_kernel(PsWgParams p) {
         for (int t = 0; t < 3; ++t) { acc[t][0][r] = 0.f; acc[t][1][r] = 0.f; }
     }
     const bool do_db = p.want_db && tn == 0 && wn == 0;   // wave-uniform
-    bf16x8 ones;
+    sp_bf16x8 ones;
 #pragma unroll
     for (int j = 0; j < 8; ++j) ones[j] = (__bf16)1.0f;
 
     // one 16-pixel step of one tap: X fragments (one 32-channel tile x hi / lo x two pixel halves)
-    struct BFrag { ps_short4 b0[2], b1[2]; };
+    struct BFrag { sp_short4 b0[2], b1[2]; };
     auto readB = [&](BFrag& f, unsigned xbase) {
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl) {
             if (SP && pl == 1) continue;   // single pass: X's lo plane is never read
-            f.b0[pl] = ps_tr_read<0>(xbase + boff[pl]);
-            f.b1[pl] = ps_tr_read<4 * 512>(xbase + boff[pl]);
+            f.b0[pl] = sp_read_tr<0>(xbase + boff[pl]);
+            f.b1[pl] = sp_read_tr<4 * 512>(xbase + boff[pl]);
         }
     };
     auto waitB = [&](BFrag& f) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f.b0[0]), "+v"(f.b1[0]), "+v"(f.b0[1]), "+v"(f.b1[1])); };
-    struct AFrag { ps_short4 a0[2][2], a1[2][2]; };      // [co block][plane]
+    struct AFrag { sp_short4 a0[2][2], a1[2][2]; };      // [co block][plane]
     auto readA = [&](AFrag& f, unsigned dbase, int S) {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int pl = 0; pl < 2; ++pl) {
                 if (SP && pl == 1 && !do_db) continue;   // single pass: dY's lo plane feeds the bias gradient only
-                f.a0[i][pl] = S ? ps_tr_read<16 * 512>(dbase + aoff[i][pl]) : ps_tr_read<0>(dbase + aoff[i][pl]);
-                f.a1[i][pl] = S ? ps_tr_read<16 * 512 + 4 * 512>(dbase + aoff[i][pl]) : ps_tr_read<4 * 512>(dbase + aoff[i][pl]);
+                f.a0[i][pl] = S ? sp_read_tr<16 * 512>(dbase + aoff[i][pl]) : sp_read_tr<0>(dbase + aoff[i][pl]);
+                f.a1[i][pl] = S ? sp_read_tr<16 * 512 + 4 * 512>(dbase + aoff[i][pl]) : sp_read_tr<4 * 512>(dbase + aoff[i][pl]);
             }
     };
     auto waitA = [&](AFrag& f) {
@@ -1113,8 +959,8 @@ __global__ __launch_bounds__(512, 2) void conv_ps_wgrad3_kernel(PsWgParams p) {
                      : "+v"(f.a0[0][0]), "+v"(f.a1[0][0]), "+v"(f.a0[0][1]), "+v"(f.a1[0][1]), "+v"(f.a0[1][0]), "+v"(f.a1[1][0]), "+v"(f.a0[1][1]),
                        "+v"(f.a1[1][1]));
     };
-    auto tap_mfmas = [&](floatx16 (&a)[2], const bf16x8 (&ah)[2], const bf16x8 (&al)[2], const BFrag& f) {
-        const bf16x8 bh = ps_tr_join(f.b0[0], f.b1[0]), bl = ps_tr_join(f.b0[1], f.b1[1]);
+    auto tap_mfmas = [&](sp_floatx16 (&a)[2], const sp_bf16x8 (&ah)[2], const sp_bf16x8 (&al)[2], const BFrag& f) {
+        const sp_bf16x8 bh = sp_join(f.b0[0], f.b1[0]), bl = sp_join(f.b0[1], f.b1[1]);
 #pragma unroll
         for (int i = 0; i < 2; ++i) if constexpr (!SP) a[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh, a[i], 0, 0, 0);
 #pragma unroll
@@ -1149,8 +995,8 @@ __global__ __launch_bounds__(512, 2) void conv_ps_wgrad3_kernel(PsWgParams p) {
             if (i + 1 < 6) readB(fb[(i + 1) & 1], xb[i + 1]);
             if (i == 1) readA(fa[1], dbase, 1);
             __builtin_amdgcn_sched_barrier(0);
-            const bf16x8 ah[2] = {ps_tr_join(fa[S].a0[0][0], fa[S].a1[0][0]), ps_tr_join(fa[S].a0[1][0], fa[S].a1[1][0])};
-            const bf16x8 al[2] = {ps_tr_join(fa[S].a0[0][1], fa[S].a1[0][1]), ps_tr_join(fa[S].a0[1][1], fa[S].a1[1][1])};
+            const sp_bf16x8 ah[2] = {sp_join(fa[S].a0[0][0], fa[S].a1[0][0]), sp_join(fa[S].a0[1][0], fa[S].a1[1][0])};
+            const sp_bf16x8 al[2] = {sp_join(fa[S].a0[0][1], fa[S].a1[0][1]), sp_join(fa[S].a0[1][1], fa[S].a1[1][1])};
             if (ok[i]) tap_mfmas(acc[ky], ah, al, fb[i & 1]);
             if (do_db && ky == 0) {
 #pragma unroll
@@ -1171,8 +1017,7 @@ __global__ __launch_bounds__(512, 2) void conv_ps_wgrad3_kernel(PsWgParams p) {
         for (int v = c_begin - (VW >> 4); v < c_begin; ++v) issue_x(v);      // halo: X rows [32 c_begin - VW, 32 c_begin + VW)
         issue_dy(c_begin); issue_x(c_begin);
         for (int c = c_begin; c < c_end; ++c) {
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
+            sp_sync<0>();
             if (c + 1 < c_end) { issue_dy(c + 1); issue_x(c + 1); }
             compute(c);
         }
@@ -1226,9 +1071,6 @@ __global__ __launch_bounds__(256) void conv_ps_wgrad_reduce(const float* __restr
 }
 
 // ---- producers of split planes -------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned ps_pack_hi(float a, float b) { return bd_pack_hi(a, b); }   // common.h: the library's split
-__device__ __forceinline__ unsigned ps_pack_lo(float a, float b) { return bd_pack_lo(a, b); }
-
 // rows x C fp32 (row stride lds) -> split planes (row stride ldd elements = 4*ldd bytes); C % 32 == 0.  8 values per thread.
 __global__ __launch_bounds__(256) void split_rows_kernel(const float* __restrict__ src, long long lds, long long rows, int C,
                                                           unsigned short* __restrict__ dst, long long ldd) {
@@ -1240,8 +1082,8 @@ __global__ __launch_bounds__(256) void split_rows_kernel(const float* __restrict
         const float4 a = *reinterpret_cast<const float4*>(src + r * lds + j * 8);
         const float4 b = *reinterpret_cast<const float4*>(src + r * lds + j * 8 + 4);
         unsigned short* o = dst + 2 * r * ldd + (j >> 2) * 64 + (j & 3) * 8;
-        *reinterpret_cast<uint4*>(o) = make_uint4(ps_pack_hi(a.x, a.y), ps_pack_hi(a.z, a.w), ps_pack_hi(b.x, b.y), ps_pack_hi(b.z, b.w));
-        *reinterpret_cast<uint4*>(o + 32) = make_uint4(ps_pack_lo(a.x, a.y), ps_pack_lo(a.z, a.w), ps_pack_lo(b.x, b.y), ps_pack_lo(b.z, b.w));
+        *reinterpret_cast<uint4*>(o) = make_uint4(bd_pack_hi(a.x, a.y), bd_pack_hi(a.z, a.w), bd_pack_hi(b.x, b.y), bd_pack_hi(b.z, b.w));
+        *reinterpret_cast<uint4*>(o + 32) = make_uint4(bd_pack_lo(a.x, a.y), bd_pack_lo(a.z, a.w), bd_pack_lo(b.x, b.y), bd_pack_lo(b.z, b.w));
     }
 }
 
@@ -1262,8 +1104,8 @@ __global__ __launch_bounds__(256) void split_rows_ups2_kernel(const float* __res
         const float4 a = *reinterpret_cast<const float4*>(src + rs * lds + j * 8);
         const float4 bb = *reinterpret_cast<const float4*>(src + rs * lds + j * 8 + 4);
         unsigned short* o = dst + 2 * r * ldd + (j >> 2) * 64 + (j & 3) * 8;
-        *reinterpret_cast<uint4*>(o) = make_uint4(ps_pack_hi(a.x, a.y), ps_pack_hi(a.z, a.w), ps_pack_hi(bb.x, bb.y), ps_pack_hi(bb.z, bb.w));
-        *reinterpret_cast<uint4*>(o + 32) = make_uint4(ps_pack_lo(a.x, a.y), ps_pack_lo(a.z, a.w), ps_pack_lo(bb.x, bb.y), ps_pack_lo(bb.z, bb.w));
+        *reinterpret_cast<uint4*>(o) = make_uint4(bd_pack_hi(a.x, a.y), bd_pack_hi(a.z, a.w), bd_pack_hi(bb.x, bb.y), bd_pack_hi(bb.z, bb.w));
+        *reinterpret_cast<uint4*>(o + 32) = make_uint4(bd_pack_lo(a.x, a.y), bd_pack_lo(a.z, a.w), bd_pack_lo(bb.x, bb.y), bd_pack_lo(bb.z, bb.w));
     }
 }
 
@@ -1283,8 +1125,8 @@ __global__ __launch_bounds__(256) void split_wT_kernel(const float* __restrict__
     const int r = threadIdx.x >> 3, c4 = (threadIdx.x & 7) * 4;
     const float v0 = t[c4][r], v1 = t[c4 + 1][r], v2 = t[c4 + 2][r], v3 = t[c4 + 3][r];
     unsigned short* o = out + 2 * (((long long)(cib * 32 + r) * 9 + tap) * Cout + cob * 32) + c4;
-    *reinterpret_cast<uint2*>(o) = make_uint2(ps_pack_hi(v0, v1), ps_pack_hi(v2, v3));
-    *reinterpret_cast<uint2*>(o + 32) = make_uint2(ps_pack_lo(v0, v1), ps_pack_lo(v2, v3));
+    *reinterpret_cast<uint2*>(o) = make_uint2(bd_pack_hi(v0, v1), bd_pack_hi(v2, v3));
+    *reinterpret_cast<uint2*>(o + 32) = make_uint2(bd_pack_lo(v0, v1), bd_pack_lo(v2, v3));
 }
 
 // all 3x3 conv weights of a network in ONE launch: the table (by value in the kernel arguments) lists, per weight,
@@ -1316,8 +1158,8 @@ __global__ __launch_bounds__(256) void split_wT_batched_kernel(const float* __re
     const int r = threadIdx.x >> 3, c4 = (threadIdx.x & 7) * 4;
     const float v0 = tl[c4][r], v1 = tl[c4 + 1][r], v2 = tl[c4 + 2][r], v3 = tl[c4 + 3][r];
     unsigned short* o = o_base + 2 * (((long long)(cib * 32 + r) * 9 + tap) * Cout + cob * 32) + c4;
-    *reinterpret_cast<uint2*>(o) = make_uint2(ps_pack_hi(v0, v1), ps_pack_hi(v2, v3));
-    *reinterpret_cast<uint2*>(o + 32) = make_uint2(ps_pack_lo(v0, v1), ps_pack_lo(v2, v3));
+    *reinterpret_cast<uint2*>(o) = make_uint2(bd_pack_hi(v0, v1), bd_pack_hi(v2, v3));
+    *reinterpret_cast<uint2*>(o + 32) = make_uint2(bd_pack_lo(v0, v1), bd_pack_lo(v2, v3));
 }
 
 int split_wt_batched(const float* params, uint16_t* out, const long long* off, const int* cin, const int* cout, int n, hipStream_t st) {
@@ -1336,35 +1178,18 @@ int split_wt_batched(const float* params, uint16_t* out, const long long* off, c
     return BD_OK;
 }
 
-static int ilog2x(int v) {
-    if (v <= 0 || (v & (v - 1))) return -1;
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return l;
-}
-
 // shapes the LDS-DMA convolution handles: power-of-two images, whole 32-channel blocks, 128-wide output tiles.
 // Large layers (>= 96 tiles of 256 x 128) run the three-stage 256 x 128 kernel, one workgroup per CU and no K split;
 // small ones (8x8 / 4x4 images at CIFAR batch sizes) the 128 x 128 split-K variant.
 bool conv3x3_ps_supported(int B, int H, int W, int K_channels, int N_channels) {
-    return B > 0 && ilog2x(H) >= 0 && ilog2x(W) >= 0 && K_channels % 32 == 0 && N_channels % PS_BN == 0 && K_channels >= 32;
+    return B > 0 && ilog2_exact(H) >= 0 && ilog2_exact(W) >= 0 && K_channels % 32 == 0 && N_channels % PS_BN == 0 && K_channels >= 32;
 }
 static bool ps_large(long long M, int N) { return cdiv(M, PS_BM) * (N / PS_BN) >= 96; }
 static void ps_small_split(long long M, int N, int K, int& ksplit, int& cps) {
     const long long tiles = cdiv(M, 128) * (N / 128);
     const int nchunks = 9 * (K / 32);
-    static const int slots = [] {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        return cus;   // (2 x CUs measured 0.1-0.2 ms/step slower: twice the slab traffic for the 4x4 / 8x8 layers)
-    }();
-    constexpr int mincps = 4;   // chunks per split at least
-    int ks = (int)(slots / tiles);
-    if (ks < 1) ks = 1;
-    if (ks > nchunks / mincps) ks = nchunks / mincps;
-    if (ks < 1) ks = 1;
-    cps = (int)cdiv(nchunks, ks);
-    ksplit = (int)cdiv(nchunks, cps);
+    // one slot per CU (2 x CUs measured 0.1-0.2 ms/step slower: twice the slab traffic for the 4x4 / 8x8 layers), >= 4 chunks per split
+    split_k(device_cus(), tiles, nchunks, 4, ksplit, cps);
 }
 size_t conv3x3_ps_workspace_bytes(const bd_conv3x3_ps_desc& d) {
     const long long M = (long long)d.B * d.H * d.W;
@@ -1385,15 +1210,15 @@ static bool ps_takes_v3(int B, int H, int W, int N) {
 }
 // Round 4: pixel splits of the GroupNorm partials a forward call can write from its epilogue (0: it cannot).  One split per 256-pixel tile.
 int conv3x3_ps_gn_splits(int B, int H, int W, int K, int N, int groups) {
-    if (B <= 0 || ilog2x(H) < 0 || ilog2x(W) < 0 || K <= 0 || K % 32 || N <= 0 || N % PS_BN || groups <= 0 || N % groups) return 0;
-    const int lc = ilog2x(N / groups);
+    if (B <= 0 || ilog2_exact(H) < 0 || ilog2_exact(W) < 0 || K <= 0 || K % 32 || N <= 0 || N % PS_BN || groups <= 0 || N % groups) return 0;
+    const int lc = ilog2_exact(N / groups);
     if (lc < 2 || lc > 5 || (H * W) % PS_BM) return 0;
     return ps_takes_v3(B, H, W, N) ? H * W / PS_BM : 0;
 }
 
 int conv3x3_ps(const bd_conv3x3_ps_desc& d, hipStream_t st) {
     BD_CHECK(d.x_split && d.w_split && d.y, BD_ERR_INVALID, "conv3x3_ps: null pointer");
-    BD_CHECK(d.B > 0 && ilog2x(d.H) >= 0 && ilog2x(d.W) >= 0, BD_ERR_UNSUPPORTED, "conv3x3_ps: H, W must be powers of two");
+    BD_CHECK(d.B > 0 && ilog2_exact(d.H) >= 0 && ilog2_exact(d.W) >= 0, BD_ERR_UNSUPPORTED, "conv3x3_ps: H, W must be powers of two");
     BD_CHECK(d.K > 0 && d.K % 32 == 0 && d.N > 0 && d.N % PS_BN == 0, BD_ERR_UNSUPPORTED,
              "conv3x3_ps: K channels %% 32 and N channels %% %d must be 0 (got %d, %d)", PS_BN, d.K, d.N);
     BD_CHECK(d.ldx % 32 == 0 && ((uintptr_t)d.x_split & 127) == 0 && ((uintptr_t)d.w_split & 127) == 0, BD_ERR_UNSUPPORTED,
@@ -1415,7 +1240,7 @@ int conv3x3_ps(const bd_conv3x3_ps_desc& d, hipStream_t st) {
     p.a = reinterpret_cast<const char*>(d.x_split); p.w = reinterpret_cast<const char*>(d.w_split);
     p.y = d.y; p.bias = d.bias; p.rowbias = d.rowbias; p.residual = d.residual;
     p.lda = d.ldx; p.ldy = d.ldy; p.ldr = d.ldr; p.ld_rowbias = d.ld_rowbias;
-    p.C = d.K; p.H = d.H; p.W = d.W; p.lw = ilog2x(d.W); p.lhw = ilog2x(d.W) + ilog2x(d.H);
+    p.C = d.K; p.H = d.H; p.W = d.W; p.lw = ilog2_exact(d.W); p.lhw = ilog2_exact(d.W) + ilog2_exact(d.H);
     p.sign = d.direction; p.M = (int)M; p.N = d.N;
     p.out_scale = d.out_scale == 0.f ? 1.f : d.out_scale; p.accumulate = d.accumulate;
     const bool large = ps_large(M, d.N);
@@ -1433,11 +1258,11 @@ int conv3x3_ps(const bd_conv3x3_ps_desc& d, hipStream_t st) {
         // vertical-tap sharing variant (conv_ps3_kernel): image rows of 16 or 32 pixels, whole images per tile row block
         const int vw = d.W < 32 ? d.W : 32;
         const bool v3 = ps_takes_v3(d.B, d.H, d.W, d.N);
-        p.lvw = ilog2x(vw);
+        p.lvw = ilog2_exact(vw);
         if (d.gn_part) {
             BD_CHECK(d.direction == 1 && (epi == 1 || epi == 2) && conv3x3_ps_gn_splits(d.B, d.H, d.W, d.K, d.N, d.gn_groups) > 0, BD_ERR_UNSUPPORTED,
                      "conv3x3_ps: gn_part needs a forward call with exactly one of rowbias / residual and bd_conv3x3_ps_gn_splits() > 0");
-            p.gn_part = d.gn_part; p.gn_G = d.gn_groups; p.gn_lcpg = ilog2x(d.N / d.gn_groups);
+            p.gn_part = d.gn_part; p.gn_G = d.gn_groups; p.gn_lcpg = ilog2_exact(d.N / d.gn_groups);
         }
 #define PS_LAUNCH(E) do { if (v3) { if (sp) hipLaunchKernelGGL((conv_ps3_kernel<E, true>), grid, block, 0, st, p); \
                                     else hipLaunchKernelGGL((conv_ps3_kernel<E, false>), grid, block, 0, st, p); } \
@@ -1498,7 +1323,7 @@ int conv3x3_ps(const bd_conv3x3_ps_desc& d, hipStream_t st) {
 }
 
 bool conv3x3_ps_wgrad_supported(int B, int H, int W, int Cin, int Cout) {
-    return B > 0 && ilog2x(H) >= 0 && ilog2x(W) >= 0 && Cin % WG_BN == 0 && Cout % WG_BM == 0;
+    return B > 0 && ilog2_exact(H) >= 0 && ilog2_exact(W) >= 0 && Cin % WG_BN == 0 && Cout % WG_BM == 0;
 }
 // vertical-tap sharing form (conv_ps_wgrad3_kernel): image rows of 16 or 32 pixels, whole 32-pixel chunks
 static bool ps_wgrad_v3(const bd_conv3x3_ps_wgrad_desc& d) {
@@ -1512,11 +1337,7 @@ static void ps_wgrad_split(const bd_conv3x3_ps_wgrad_desc& d, int& ksplit, int& 
     const bool v3 = ps_wgrad_v3(d);
     const long long tiles = (long long)(d.Cout / WG_BM) * ((v3 ? 3 : 9) * d.Cin / WG_BN);
     const int nchunks = (int)cdiv((long long)d.B * d.H * d.W, 32);
-    static const int slots = [] {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        return 2 * cus;   // two 64-KB workgroups per CU (two LDS stages each): the pair de-phases, 141 vs 189 us
-    }();
+    const int slots = 2 * device_cus();   // two 64-KB workgroups per CU (two LDS stages each): the pair de-phases, 141 vs 189 us
     // 96 KB of LDS: one workgroup per CU -- and three quarters of the CUs (round 4, late: 192 of 256).  The kernel never runs alone: the data-gradient
     // chain shares the chip with it, so the CUs it leaves are not idle, and a quarter fewer slabs are a quarter less slab traffic: CIFAR step
     // 17.71 -> 17.53 ms and 18.01 -> 17.89 on two boxes (160 / 176 / 208 / 224 / 256 slots: 17.70 / 17.59 / 17.67 / 17.72 / 17.71), 256 x 256 28.06 -> 27.93.
@@ -1526,12 +1347,8 @@ static void ps_wgrad_split(const bd_conv3x3_ps_wgrad_desc& d, int& ksplit, int& 
     static const int slots3_getenv = getenv("BD_PS_WG3_SLOTS") ? atoi(getenv("BD_PS_WG3_SLOTS")) : 0;
     const int slots3_env = g_wg3_slots_override > 0 ? g_wg3_slots_override : slots3_getenv;      // bd_tune_set("ps_wg3_slots", n) wins over the environment
     const int slots3 = slots3_env > 0 ? slots3_env : (d.W > 32 ? slots / 4 : slots * 3 / 8);
-    constexpr int mincps = 8;   // chunks per split at least (4x4 layers: 8 slabs instead of 14; 4 / 16 measured +0.2 / +0.1 ms)
-    int ks = (int)((v3 ? slots3 : slots) / tiles);
-    if (ks < 1) ks = 1;
-    if (ks > nchunks / mincps) ks = nchunks / mincps > 0 ? nchunks / mincps : 1;
-    cps = (int)cdiv(nchunks, ks);
-    ksplit = (int)cdiv(nchunks, cps);
+    // chunks per split at least 8 (4x4 layers: 8 slabs instead of 14; 4 / 16 measured +0.2 / +0.1 ms)
+    split_k(v3 ? slots3 : slots, tiles, nchunks, 8, ksplit, cps);
 }
 size_t conv3x3_ps_wgrad_workspace_bytes(const bd_conv3x3_ps_wgrad_desc& d) {
     int ks, cps;
@@ -1548,8 +1365,8 @@ int conv3x3_ps_wgrad(const bd_conv3x3_ps_wgrad_desc& d, hipStream_t st) {
     const bool sp = d.mode == BD_MODE_BF16;
     PsWgParams p = {};
     p.dy = reinterpret_cast<const char*>(d.dy_split); p.x = reinterpret_cast<const char*>(d.x_split);
-    p.lddy = d.lddy; p.ldx = d.ldx; p.Cin = d.Cin; p.Cout = d.Cout; p.H = d.H; p.W = d.W; p.lw = ilog2x(d.W);
-    p.lh = ilog2x(d.H); p.lvw = ilog2x(d.W < 32 ? d.W : 32);
+    p.lddy = d.lddy; p.ldx = d.ldx; p.Cin = d.Cin; p.Cout = d.Cout; p.H = d.H; p.W = d.W; p.lw = ilog2_exact(d.W);
+    p.lh = ilog2_exact(d.H); p.lvw = ilog2_exact(d.W < 32 ? d.W : 32);
     p.P = d.B * d.H * d.W;
     const bool v3 = ps_wgrad_v3(d);
     p.tiles_m = d.Cout / WG_BM; p.tiles_n = (v3 ? 3 : 9) * d.Cin / WG_BN; p.ntaps = 9;
@@ -1587,17 +1404,9 @@ int conv3x3_ps_wgrad(const bd_conv3x3_ps_wgrad_desc& d, hipStream_t st) {
 int ups_dweff_combine(const float* de, int Cin, int Cout, float* dw, hipStream_t st);   // conv_ph.hip
 
 static void ups_wgrad_split(const bd_upsample_conv_desc& d, int& ksplit, int& cps) {
-    bd_conv3x3_ps_wgrad_desc q = {};
-    q.B = d.B; q.H = d.H; q.W = d.W; q.Cin = d.Cin; q.Cout = d.Cout;
     const long long tiles = (long long)(d.Cout / WG_BM) * (16 * d.Cin / WG_BN);
     const int nchunks = (int)cdiv((long long)d.B * d.H * d.W, 32);
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    int ks = (int)(2 * cus / tiles);
-    if (ks < 1) ks = 1;
-    if (ks > nchunks / 8) ks = nchunks / 8 > 0 ? nchunks / 8 : 1;
-    cps = (int)cdiv(nchunks, ks);
-    ksplit = (int)cdiv(nchunks, cps);
+    split_k(2 * device_cus(), tiles, nchunks, 8, ksplit, cps);
 }
 size_t upsample_conv_wgrad_workspace_bytes(const bd_upsample_conv_desc& d) {
     int ks, cps;
@@ -1618,7 +1427,7 @@ int upsample_conv_wgrad(const bd_upsample_conv_desc& d, hipStream_t st) {
     BD_CHECK(d.workspace && d.workspace_bytes >= need, BD_ERR_WORKSPACE, "bd_upsample_conv_wgrad: workspace %zu < %zu", d.workspace_bytes, need);
     PsWgParams p = {};
     p.dy = reinterpret_cast<const char*>(d.dy_split); p.x = reinterpret_cast<const char*>(d.x_split);
-    p.lddy = d.lddy; p.ldx = d.ldx; p.Cin = d.Cin; p.Cout = d.Cout; p.H = d.H; p.W = d.W; p.lw = ilog2x(d.W);
+    p.lddy = d.lddy; p.ldx = d.ldx; p.Cin = d.Cin; p.Cout = d.Cout; p.H = d.H; p.W = d.W; p.lw = ilog2_exact(d.W);
     p.P = d.B * d.H * d.W;
     p.tiles_m = d.Cout / WG_BM; p.tiles_n = 16 * d.Cin / WG_BN; p.ntaps = 16;
     ups_wgrad_split(d, p.ksplit, p.cps);

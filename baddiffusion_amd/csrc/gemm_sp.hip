@@ -20,20 +20,12 @@
 // Long-K products (the weight gradients: K = all tokens) split K over workgroups with a fixed-order second pass (deterministic).
 // Single pass (SP, BD_MODE_BF16): only the hi fragments are read and each product is hi*hi; the a_colsum bias gradient keeps hi + lo
 // (its waves alone read A's lo plane).  The split-plane output is still written with both planes.
-#include "common.h"
+#include "splitplane.h"
 
 #include <cstdlib>
 #include <type_traits>
 
 namespace bd {
-
-typedef float sp_floatx16 __attribute__((ext_vector_type(16)));
-typedef __bf16 sp_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 sp_bf16x2 __attribute__((ext_vector_type(2)));
-typedef short sp_short4 __attribute__((ext_vector_type(4)));
-typedef short sp_short8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void* sp_lds_ptr;
-typedef const __attribute__((address_space(1))) void* sp_gbl_ptr;
 
 constexpr int SP_T = 128, SP_NT = 256;
 constexpr int SP_OP_BYTES = 128 * 128, SP_STAGE_BYTES = 2 * SP_OP_BYTES, SP_LDS_BYTES = 2 * SP_STAGE_BYTES;
@@ -53,36 +45,16 @@ struct SpParams {
     float* colsum; int want_colsum;            // both operands K-major: colsum[m] = sum_k A[k][m] (a linear layer's bias gradient)
 };
 
-__device__ __forceinline__ int sp_swz(int row) { return (row >> 1) & 7; }
-__device__ __forceinline__ void sp_dma16(const char* src, char* lds_dst) {
-    __builtin_amdgcn_global_load_lds((sp_gbl_ptr)src, (sp_lds_ptr)lds_dst, 16, 0, 0);
-}
-// asm reads (address = LDS byte offset): opaque to hipcc's "LDS-DMA in flight -> s_waitcnt vmcnt(0) before any LDS read" pass
-// (conv_ps.hip ps_tr_read); the matching s_waitcnt lgkmcnt(0) is tied to the fragment registers in sp_wait().
-template <int OFF>
-__device__ __forceinline__ sp_short4 sp_read_tr(unsigned addr) {
-    sp_short4 v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-    return v;
-}
-template <int OFF>
-__device__ __forceinline__ sp_short8 sp_read128(unsigned addr) {
-    sp_short8 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-    return v;
-}
-
 // fragments of one 16-wide K step of a wave's two 32-row tiles, planes hi / lo
 template <bool KM> struct SpFrag;
 template <> struct SpFrag<false> {
     sp_short8 v[2][2];
-    __device__ __forceinline__ sp_bf16x8 get(int i, int pl) const { return __builtin_bit_cast(sp_bf16x8, v[i][pl]); }
+    __device__ __forceinline__ sp_bf16x8 get(int i, int pl) const { return sp_join(v[i][pl]); }
 };
 template <> struct SpFrag<true> {
     sp_short4 v0[2][2], v1[2][2];
     __device__ __forceinline__ sp_bf16x8 get(int i, int pl) const {
-        const sp_short8 v = __builtin_shufflevector(v0[i][pl], v1[i][pl], 0, 1, 2, 3, 4, 5, 6, 7);
-        return __builtin_bit_cast(sp_bf16x8, v);
+        return sp_join(v0[i][pl], v1[i][pl]);
     }
 };
 __device__ __forceinline__ void sp_tie(SpFrag<false>& f) {
@@ -92,9 +64,6 @@ __device__ __forceinline__ void sp_tie(SpFrag<true>& f) {
     asm volatile("" : "+v"(f.v0[0][0]), "+v"(f.v0[0][1]), "+v"(f.v0[1][0]), "+v"(f.v0[1][1]), "+v"(f.v1[0][0]), "+v"(f.v1[0][1]),
                  "+v"(f.v1[1][0]), "+v"(f.v1[1][1]));
 }
-
-// y -> (bf16 hi = RNE, bf16 lo = RNE of the remainder): the split of bd_split_rows (common.h), packed hi | lo << 16
-__device__ __forceinline__ unsigned sp_split1(float v) { return bd_split1(v); }
 
 template <bool AKM, bool BKM, bool SP>
 __global__ __launch_bounds__(SP_NT, 2) void gemm_sp_kernel(SpParams p) {
@@ -108,8 +77,7 @@ __global__ __launch_bounds__(SP_NT, 2) void gemm_sp_kernel(SpParams p) {
     // logical order: n fastest, m, batch, K split; one contiguous run per XCD (tiles sharing an operand panel meet in one L2)
     int tm, tn, bz, zz;
     {
-        const unsigned L = blockIdx.x, T = gridDim.x, q = T >> 3;
-        unsigned j = L < (q << 3) ? (L & 7) * q + (L >> 3) : L;
+        unsigned j = xcd_tile_order();
         const unsigned ntiles = p.tiles_m * p.tiles_n;
         const unsigned per_split = ntiles * p.batch;
         zz = j / per_split; j -= zz * per_split;
@@ -261,13 +229,11 @@ __global__ __launch_bounds__(SP_NT, 2) void gemm_sp_kernel(SpParams p) {
     // two stages: chunk c+1 is fetched while chunk c is multiplied; the second resident workgroup covers the rest of the latency
     if (n > 0) issue(smem);
     for (int c = 0; c < n; c += 2) {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
+        sp_sync<0>();
         if (c + 1 < n) issue(smem + SP_STAGE_BYTES);
         chunk(std::integral_constant<int, 0>{});
         if (c + 1 < n) {
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
+            sp_sync<0>();
             if (c + 2 < n) issue(smem);
             chunk(std::integral_constant<int, 1>{});
         }
@@ -329,7 +295,7 @@ __global__ __launch_bounds__(SP_NT, 2) void gemm_sp_kernel(SpParams p) {
                 float v = (p.alpha * acc[i][q][r] + bn + rs[r]) * p.out_scale + pc[r];
                 if (c) c[m * p.ldc + nn] = v;
                 if (cs) {
-                    const unsigned w = sp_split1(v);
+                    const unsigned w = bd_split1(v);
                     const unsigned nb = (unsigned)__builtin_amdgcn_mov_dpp((int)w, 0xB1, 0xF, 0xF, true);   // quad_perm [1,0,3,2]: lane ^ 1
                     const unsigned o = odd ? ((nb >> 16) | (w & 0xFFFF0000u)) : ((w & 0xFFFFu) | (nb << 16));
                     *reinterpret_cast<unsigned*>(cs + m * p.ldcs + cs_col) = o;
@@ -377,7 +343,7 @@ __global__ __launch_bounds__(256) void gemm_sp_reduce(SpParams p) {
         unsigned hi[4], lo[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const unsigned w0 = sp_split1(v[2 * j]), w1 = sp_split1(v[2 * j + 1]);
+            const unsigned w0 = bd_split1(v[2 * j]), w1 = bd_split1(v[2 * j + 1]);
             hi[j] = (w0 & 0xFFFFu) | (w1 << 16);
             lo[j] = (w0 >> 16) | (w1 & 0xFFFF0000u);
         }
@@ -404,20 +370,12 @@ __global__ __launch_bounds__(64) void gemm_sp_colsum_reduce(const float* __restr
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------
-static int sp_cus() {
-    static int cus = [] {
-        int dev = 0; hipDeviceProp_t pr;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return 256;
-        return pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
-    }();
-    return cus;
-}
 static void sp_split(const bd_gemm_sp_desc& d, int& ksplit, int& cps) {
     const int nch = d.K / 32;
     const long long tiles = (long long)(d.M / SP_T) * (d.N / SP_T) * (d.batch > 0 ? d.batch : 1);
     ksplit = 1;
-    if (d.batch <= 1 && tiles < sp_cus() && nch >= 32) {   // one workgroup per CU: the slabs are written and read once more each
-        ksplit = (int)cdiv(sp_cus(), tiles);
+    if (d.batch <= 1 && tiles < device_cus() && nch >= 32) {   // one workgroup per CU: the slabs are written and read once more each
+        ksplit = (int)cdiv(device_cus(), tiles);
         if (ksplit > nch / 8) ksplit = nch / 8;
     }
     if (ksplit < 1) ksplit = 1;

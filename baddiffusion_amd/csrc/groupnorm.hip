@@ -80,14 +80,11 @@ __device__ __forceinline__ float silu_grad_fast(float z) {
 
 // ---- split-plane output (bd_hip.h "split planes"): 4 consecutive channels c..c+3 of one row -> 8 B of bf16 hi and 8 B of
 // bf16 lo (common.h: hi = RNE, lo = RNE of the remainder: bit-identical to the on-the-fly split of the bf16x3 engine)
-typedef __bf16 gn_bf16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned gn_pack_hi(float a, float b) { return bd_pack_hi(a, b); }
-__device__ __forceinline__ unsigned gn_pack_lo(float a, float b) { return bd_pack_lo(a, b); }
 // row = start of the row's planes (uint16 units), c = channel of o[0] (c % 4 == 0)
 __device__ __forceinline__ void gn_store_split4(unsigned short* row, int c, const float (&o)[4]) {
     unsigned short* q = row + (c >> 5) * 64 + (c & 31);
-    *reinterpret_cast<uint2*>(q) = make_uint2(gn_pack_hi(o[0], o[1]), gn_pack_hi(o[2], o[3]));
-    *reinterpret_cast<uint2*>(q + 32) = make_uint2(gn_pack_lo(o[0], o[1]), gn_pack_lo(o[2], o[3]));
+    *reinterpret_cast<uint2*>(q) = make_uint2(bd_pack_hi(o[0], o[1]), bd_pack_hi(o[2], o[3]));
+    *reinterpret_cast<uint2*>(q + 32) = make_uint2(bd_pack_lo(o[0], o[1]), bd_pack_lo(o[2], o[3]));
 }
 
 // predicated 16-byte load without control flow: masked-off lanes read 16 zero bytes that live in the code object (the
@@ -525,7 +522,7 @@ struct GnCoord {
 __device__ __forceinline__ GnCoord gn_res_coord(int nblk) {
     const unsigned L = blockIdx.x, T = gridDim.x, qq = T >> 3;
     unsigned j = (L & 7) * qq + (L >> 3);
-    if (L >= (qq << 3)) j = L;   // (an if, not a select: the ternary form trips a gfx950 backend assertion in this kernel)
+    if (L >= (qq << 3)) j = L;   // (an if, not the select of xcd_tile_order(): behind the select these kernels take up to 30 more VGPRs)
     GnCoord c;
     c.b = (int)(j / (unsigned)nblk);
     c.bx = (int)(j - (unsigned)c.b * (unsigned)nblk);

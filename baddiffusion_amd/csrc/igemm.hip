@@ -139,8 +139,6 @@ struct RCMap {
 
 constexpr int LDH = BK + 8;  // bf16 row stride of the split-bf16 LDS planes: 80 B (conflict-free b128 reads, b64 writes)
 
-__device__ __forceinline__ unsigned pack_hi(float a, float b) { return bd_pack_hi(a, b); }   // common.h: RNE hi planes
-__device__ __forceinline__ unsigned pack_lo(float a, float b) { return bd_pack_lo(a, b); }
 
 template <int R, int NT>
 struct RCStore {
@@ -159,8 +157,8 @@ struct RCStore {
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
             const int o = (k0 + RCMap<R, NT>::KSTEP * i) * (R + 32) + r4;
-            *reinterpret_cast<uint2*>(sh + o) = make_uint2(pack_hi(v[i].x, v[i].y), pack_hi(v[i].z, v[i].w));
-            if constexpr (!SP) *reinterpret_cast<uint2*>(sl + o) = make_uint2(pack_lo(v[i].x, v[i].y), pack_lo(v[i].z, v[i].w));
+            *reinterpret_cast<uint2*>(sh + o) = make_uint2(bd_pack_hi(v[i].x, v[i].y), bd_pack_hi(v[i].z, v[i].w));
+            if constexpr (!SP) *reinterpret_cast<uint2*>(sl + o) = make_uint2(bd_pack_lo(v[i].x, v[i].y), bd_pack_lo(v[i].z, v[i].w));
         }
     }
 };
@@ -190,8 +188,8 @@ __device__ __forceinline__ void KCStore<R, NT>::store_split(unsigned short* sh, 
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
         const int o = (krow(tid) + (NT / 8) * i) * LDH + k4;
-        *reinterpret_cast<uint2*>(sh + o) = make_uint2(pack_hi(v[i].x, v[i].y), pack_hi(v[i].z, v[i].w));
-        if constexpr (!SP) *reinterpret_cast<uint2*>(sl + o) = make_uint2(pack_lo(v[i].x, v[i].y), pack_lo(v[i].z, v[i].w));
+        *reinterpret_cast<uint2*>(sh + o) = make_uint2(bd_pack_hi(v[i].x, v[i].y), bd_pack_hi(v[i].z, v[i].w));
+        if constexpr (!SP) *reinterpret_cast<uint2*>(sl + o) = make_uint2(bd_pack_lo(v[i].x, v[i].y), bd_pack_lo(v[i].z, v[i].w));
     }
 }
 
@@ -738,8 +736,7 @@ struct WgCoord {
     int tm, tn, zz;
 };
 __device__ __forceinline__ WgCoord wg_coord(const IGemmParams& p) {
-    const unsigned L = blockIdx.x, T = gridDim.x, q = T >> 3;
-    const unsigned j = L < (q << 3) ? (L & 7) * q + (L >> 3) : L;
+    const unsigned j = xcd_tile_order();
     const unsigned ntiles = p.tiles_m * p.tiles_n;
     const unsigned zz = j / ntiles, tile = j - zz * ntiles;
     WgCoord w;
@@ -1086,8 +1083,8 @@ __global__ __launch_bounds__(256) void split_bf16_kernel(const float* __restrict
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long long)gridDim.x * 256) {
         const float4 a = ld4(src + 8 * i), b = ld4(src + 8 * i + 4);
         unsigned short* o = out + (i >> 2) * 64 + (i & 3) * 8;
-        *reinterpret_cast<uint4*>(o) = make_uint4(pack_hi(a.x, a.y), pack_hi(a.z, a.w), pack_hi(b.x, b.y), pack_hi(b.z, b.w));
-        *reinterpret_cast<uint4*>(o + 32) = make_uint4(pack_lo(a.x, a.y), pack_lo(a.z, a.w), pack_lo(b.x, b.y), pack_lo(b.z, b.w));
+        *reinterpret_cast<uint4*>(o) = make_uint4(bd_pack_hi(a.x, a.y), bd_pack_hi(a.z, a.w), bd_pack_hi(b.x, b.y), bd_pack_hi(b.z, b.w));
+        *reinterpret_cast<uint4*>(o + 32) = make_uint4(bd_pack_lo(a.x, a.y), bd_pack_lo(a.z, a.w), bd_pack_lo(b.x, b.y), bd_pack_lo(b.z, b.w));
     }
 }
 
@@ -1227,13 +1224,6 @@ static int validate_operand(const bd_operand& o, const char* which) {
     return BD_OK;
 }
 
-static int ilog2_exact(int v) {
-    if (v <= 0 || (v & (v - 1))) return -1;
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return l;
-}
-
 static Opnd make_opnd(const bd_operand& o, int rows, int K) {
     Opnd r;
     r.p = o.p; r.split = o.split; r.ld = o.ld; r.kind = o.kind; r.vec = operand_vec_ok(o, rows, K) ? 1 : 0;
@@ -1265,11 +1255,7 @@ static Choice choose(const bd_igemm_desc& d) {
             // workgroups into a second, nearly empty round).  Sweep of the budget 384 / 448 / 512 / 640 on the CIFAR
             // step: 25.07 / 25.15 / 25.16 / 25.55 ms -- beyond ~1.5 per CU the extra partial tiles cost more than the
             // fuller chip gains (the second stream fills idle CUs anyway).
-            static const int slots = [] {
-                int dev = 0, cus = 256;
-                if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-                return 3 * cus / 2;
-            }();
+            const int slots = 3 * device_cus() / 2;
             ks = (int)(slots / t);
             if (ks < 1) ks = 1;
             int maxks = nchunks / 8;

@@ -93,9 +93,7 @@ using namespace bd;
 extern "C" int bd_mfma_probe(int random_operands, int iters, int launches, double* tflops, bd_stream_t stream) {
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     BD_CHECK(tflops && iters > 0 && launches > 0, BD_ERR_INVALID, "bd_mfma_probe: tflops must be non-null, iters and launches positive");
-    int dev = 0, cus = 256;
-    BD_HIP_TRY(hipGetDevice(&dev));
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = device_cus();
     float* sink = nullptr;
     BD_HIP_TRY(hipMalloc(&sink, 64));
     hipEvent_t a, b;
