@@ -173,6 +173,9 @@ SIGNATURES = {
     "bd_anp_grad": (i32, [vp, vp, vp, i32, i64, vp, vp, vp, vp, vp]),
     "bd_ssim_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "bd_ssim": (i32, [vp, vp, i32, i32, i32, i32, i64, i64, i64, i64, f32, vp, vp, sz, vp]),
+    "bd_pairwise_sqdist_workspace_bytes": (sz, [i32, i32]),
+    "bd_pairwise_sqdist": (i32, [vp, i64, i32, i32, vp, i64, vp, sz, vp]),
+    "bd_total_variation": (i32, [vp, i32, i32, i32, i32, i64, i64, i64, i64, vp, vp]),
     "bd_conv2d_nhwc": (i32, [C.POINTER(Conv2dDesc), vp]),
     "bd_pool2d_nhwc": (i32, [vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "bd_resize_bilinear_nhwc": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, i32, f32, f32, vp]),

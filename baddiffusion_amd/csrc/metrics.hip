@@ -93,9 +93,240 @@ __global__ __launch_bounds__(256) void ssim_final_kernel(const double* __restric
     if (threadIdx.x == 0) out[0] = (float)(red[0] * inv_count);
 }
 
+// ---- backdoor detection statistics (defense.py; DESIGN.md section 3, "Detection statistics") ---------------------------------------------------------
+// Pairwise squared distances of N rows: one workgroup = one 64 x 64 tile of pairs (ti <= tj: the upper triangle of tiles), the 64 + 64
+// rows staged through LDS in chunks of 32 values (row pitch 36 floats: the 128-bit reads of 8 consecutive rows cover all 32 banks), each
+// thread a 4 x 4 micro-tile of pairs with rows ty + 16 r and tx + 16 c.  Two values of k go through one v_pk_add_f32 (the difference)
+// and one v_pk_fma_f32 (the square and the add round once), so a pair keeps one sum over the even and one over the odd k, added at the
+// end: 122 VGPRs, 4 workgroups per CU.  The next chunk is fetched into registers while the current one is consumed.
+// grid.z > 1: the workgroup covers chunks [z * cps, (z + 1) * cps) and stores its tile into the workspace; pairwise_fold_kernel adds
+// the splits in order.  Both go through pd_store_tile, which writes d2[i][j] directly and d2[j][i] through an LDS transpose.
+typedef float pd_f2 __attribute__((ext_vector_type(2)));
+constexpr int PD_T = 64, PD_KC = 32, PD_LD = PD_KC + 4, PD_MINCPS = 8;   // tile edge, chunk, LDS row pitch, fewest chunks per split
+
+__device__ __forceinline__ long long pd_tile_index(int ti, int tj, int nt) {   // row-major over the upper triangle, ti <= tj
+    return (long long)ti * nt - (long long)ti * (ti - 1) / 2 + (tj - ti);
+}
+
+// 4 values x[row][k .. k + 3] (zeros beyond row N or column kend)
+template <bool VEC>
+__device__ __forceinline__ float4 pd_fetch(const float* __restrict__ x, long long ldx, int N, int row, long long k, long long kend) {
+    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (row < N) {
+        const float* p = x + (long long)row * ldx + k;
+        if (VEC && k + 4 <= kend) {
+            r = *reinterpret_cast<const float4*>(p);
+        } else {
+            if (k < kend) r.x = p[0];
+            if (k + 1 < kend) r.y = p[1];
+            if (k + 2 < kend) r.z = p[2];
+            if (k + 3 < kend) r.w = p[3];
+        }
+    }
+    return r;
+}
+
+// acc[r][c] = value of the pair (rows ty + 16 (r0 + r) of tile ti, tx + 16 c of tile tj).  T: 64 * (16 R + 1) floats of LDS nobody reads
+// any more.  A diagonal tile holds every pair twice: the copy with i < j is stored at both places, i == j is written as 0.
+template <int R>
+__device__ __forceinline__ void pd_store_tile(const float (&acc)[R][4], int r0, int ti, int tj, int N, float* __restrict__ d2, long long ldd,
+                                              float* T, int tid) {
+    constexpr int TP = 16 * R + 1;
+    const int tx = tid & 15, ty = tid >> 4;
+    const bool diag = ti == tj;
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int jl = tx + 16 * c, gi = ti * PD_T + ty + 16 * (r0 + r), gj = tj * PD_T + jl;
+            T[jl * TP + ty + 16 * r] = acc[r][c];
+            if (gi < N && gj < N) {
+                if (!diag || gi < gj) d2[(long long)gi * ldd + gj] = acc[r][c];
+                else if (gi == gj) d2[(long long)gi * ldd + gj] = 0.f;
+            }
+        }
+    __syncthreads();
+    for (int idx = tid; idx < PD_T * 16 * R; idx += 256) {
+        const int jl = idx / (16 * R), is = idx - jl * (16 * R);
+        const int gi = ti * PD_T + 16 * r0 + is, gj = tj * PD_T + jl;
+        if (gi < N && gj < N && (!diag || gi < gj)) d2[(long long)gj * ldd + gi] = T[jl * TP + is];
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void pairwise_sqdist_kernel(const float* __restrict__ x, long long ldx, int N, int D, int cps,
+                                                              float* __restrict__ d2, long long ldd, float* __restrict__ part) {
+    const int tj = blockIdx.x, ti = blockIdx.y;
+    if (tj < ti) return;
+    __shared__ __attribute__((aligned(16))) float sm[2 * PD_T * PD_LD];   // A rows | B rows; afterwards the transposed tile (64 x 65)
+    static_assert(2 * PD_T * PD_LD >= PD_T * (PD_T + 1), "the epilogue's transpose reuses the staging buffer");
+    float* As = sm;
+    float* Bs = sm + PD_T * PD_LD;
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int lr = tid >> 3, lq = (tid & 7) * 4;                          // loader: rows lr and lr + 32, values lq .. lq + 3 of the chunk
+    const long long kbeg = (long long)blockIdx.z * cps * PD_KC;
+    const long long kend = kbeg + (long long)cps * PD_KC < D ? kbeg + (long long)cps * PD_KC : D;
+    pd_f2 acc2[4][4] = {};                                                // per pair: the sums over even and over odd k
+    float4 pa[2], pb[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        pa[s] = pd_fetch<VEC>(x, ldx, N, ti * PD_T + lr + 32 * s, kbeg + lq, kend);
+        pb[s] = pd_fetch<VEC>(x, ldx, N, tj * PD_T + lr + 32 * s, kbeg + lq, kend);
+    }
+    for (long long k0 = kbeg; k0 < kend; k0 += PD_KC) {
+        __syncthreads();                                                  // the previous chunk has been consumed
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            *reinterpret_cast<float4*>(&As[(lr + 32 * s) * PD_LD + lq]) = pa[s];
+            *reinterpret_cast<float4*>(&Bs[(lr + 32 * s) * PD_LD + lq]) = pb[s];
+        }
+        __syncthreads();
+        if (k0 + PD_KC < kend) {
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                pa[s] = pd_fetch<VEC>(x, ldx, N, ti * PD_T + lr + 32 * s, k0 + PD_KC + lq, kend);
+                pb[s] = pd_fetch<VEC>(x, ldx, N, tj * PD_T + lr + 32 * s, k0 + PD_KC + lq, kend);
+            }
+        }
+#pragma unroll 2
+        for (int k4 = 0; k4 < PD_KC; k4 += 4) {
+            float4 a[4], b[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) a[r] = *reinterpret_cast<const float4*>(&As[(ty + 16 * r) * PD_LD + k4]);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) b[c] = *reinterpret_cast<const float4*>(&Bs[(tx + 16 * c) * PD_LD + k4]);
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {                             // two values of k per v_pk_add_f32 / v_pk_fma_f32
+                    pd_f2 d = pd_f2{a[r].x, a[r].y} - pd_f2{b[c].x, b[c].y};
+                    acc2[r][c] = __builtin_elementwise_fma(d, d, acc2[r][c]);
+                    d = pd_f2{a[r].z, a[r].w} - pd_f2{b[c].z, b[c].w};
+                    acc2[r][c] = __builtin_elementwise_fma(d, d, acc2[r][c]);
+                }
+        }
+    }
+    float acc[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[r][c] = acc2[r][c].x + acc2[r][c].y;
+    if (part) {                                                           // split D: this split's tile, [split][tile][64 x 64]
+        const long long ntiles = (long long)gridDim.x * (gridDim.x + 1) / 2;
+        float* o = part + ((long long)blockIdx.z * ntiles + pd_tile_index(ti, tj, gridDim.x)) * (PD_T * PD_T);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) o[(ty + 16 * r) * PD_T + tx + 16 * c] = acc[r][c];
+        return;
+    }
+    __syncthreads();                                                      // everyone is done reading As / Bs
+    pd_store_tile<4>(acc, 0, ti, tj, N, d2, ldd, sm, tid);
+}
+
+// grid (nt, nt, 4): 16 rows of one tile per workgroup, the splits added in split order
+__global__ __launch_bounds__(256) void pairwise_fold_kernel(const float* __restrict__ part, int ksplit, int N, float* __restrict__ d2,
+                                                            long long ldd) {
+    const int tj = blockIdx.x, ti = blockIdx.y, r0 = blockIdx.z;
+    if (tj < ti) return;
+    __shared__ float T[PD_T * 17];
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const long long ntiles = (long long)gridDim.x * (gridDim.x + 1) / 2;
+    const float* p = part + pd_tile_index(ti, tj, gridDim.x) * (PD_T * PD_T) + (ty + 16 * r0) * PD_T + tx;
+    float acc[1][4] = {};
+    for (int s = 0; s < ksplit; ++s, p += ntiles * (PD_T * PD_T))
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[0][c] += p[16 * c];
+    pd_store_tile<1>(acc, r0, ti, tj, N, d2, ldd, T, tid);
+}
+
+// Total variation: one workgroup per image; thread-strided over the logical index (c, h, w), |differences| in fp32 summed in fp64 per
+// thread, then the tree of ssim_final_kernel.  The order depends on the logical index only, never on the strides.
+__global__ __launch_bounds__(256) void total_variation_kernel(const float* __restrict__ x, int C, int H, int W, long long sn, long long sc,
+                                                              long long sh, long long sw, float* __restrict__ tv) {
+    __shared__ double red[256];
+    const float* img = x + (long long)blockIdx.x * sn;
+    const unsigned total = (unsigned)C * H * W;
+    double acc = 0.0;
+    for (unsigned i = threadIdx.x; i < total; i += 256) {
+        const unsigned q = i / W, w = i - q * W, c = q / H, h = q - c * H;
+        const float* p = img + c * sc + h * sh + w * sw;
+        const float v = p[0];
+        if (h + 1 < (unsigned)H) acc += (double)fabsf(p[sh] - v);
+        if (w + 1 < (unsigned)W) acc += (double)fabsf(p[sw] - v);
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) tv[blockIdx.x] = (float)red[0];
+}
+
+// Split of D for N rows: tiles, the largest split count any D' <= D can get (the workspace bound, monotone in D), the split used
+struct PdPlan { int nt; long long ntiles; int cap, ksplit, cps; };
+static PdPlan pd_plan(int N, int D) {
+    PdPlan p;
+    p.nt = (int)cdiv(N, PD_T);
+    p.ntiles = (long long)p.nt * (p.nt + 1) / 2;
+    // 8 workgroups per CU, twice what is resident: the 528 tiles of 2048 rows alone would leave 240 CUs with two and 16 with three
+    const int nchunks = (int)cdiv(D, PD_KC), slots = 8 * device_cus();
+    long long cap = slots / p.ntiles;
+    if (cap > nchunks / PD_MINCPS) cap = nchunks / PD_MINCPS;
+    p.cap = cap < 1 ? 1 : (int)cap;
+    split_k(slots, p.ntiles, nchunks, PD_MINCPS, p.ksplit, p.cps);
+    return p;
+}
+
 }  // namespace bd
 
 using namespace bd;
+
+extern "C" size_t bd_pairwise_sqdist_workspace_bytes(int N, int D) {
+    if (N <= 0 || D <= 0) return 0;
+    const PdPlan p = pd_plan(N, D);
+    return p.cap > 1 ? (size_t)p.cap * p.ntiles * PD_T * PD_T * sizeof(float) : 0;
+}
+
+extern "C" int bd_pairwise_sqdist(const float* x, int64_t ldx, int N, int D, float* d2, int64_t ldd, void* workspace, size_t workspace_bytes,
+                                  bd_stream_t stream) {
+    BD_CHECK(x && d2, BD_ERR_INVALID, "bd_pairwise_sqdist: null pointer");
+    BD_CHECK(N >= 1 && D >= 1, BD_ERR_INVALID, "bd_pairwise_sqdist: N=%d D=%d must be positive", N, D);
+    BD_CHECK(ldx >= D, BD_ERR_INVALID, "bd_pairwise_sqdist: ldx=%lld < D=%d", (long long)ldx, D);
+    BD_CHECK(ldd >= N, BD_ERR_INVALID, "bd_pairwise_sqdist: ldd=%lld < N=%d", (long long)ldd, N);
+    BD_CHECK((reinterpret_cast<uintptr_t>(x) & 3) == 0 && (reinterpret_cast<uintptr_t>(d2) & 3) == 0, BD_ERR_INVALID,
+             "bd_pairwise_sqdist: x and d2 must be 4-byte aligned");
+    const PdPlan p = pd_plan(N, D);
+    BD_CHECK(p.nt <= 65535, BD_ERR_UNSUPPORTED, "bd_pairwise_sqdist: N=%d too large for one launch", N);
+    const size_t need = bd_pairwise_sqdist_workspace_bytes(N, D);
+    BD_CHECK(workspace_bytes >= need && (workspace || !need), BD_ERR_WORKSPACE, "bd_pairwise_sqdist: workspace %zu < %zu",
+             workspace ? workspace_bytes : (size_t)0, need);
+    float* part = p.ksplit > 1 ? reinterpret_cast<float*>(workspace) : nullptr;
+    const dim3 grid((unsigned)p.nt, (unsigned)p.nt, (unsigned)p.ksplit);
+    if (aligned16(x) && ldx % 4 == 0)
+        hipLaunchKernelGGL(pairwise_sqdist_kernel<true>, grid, dim3(256), 0, S(stream), x, (long long)ldx, N, D, p.cps, d2, (long long)ldd, part);
+    else
+        hipLaunchKernelGGL(pairwise_sqdist_kernel<false>, grid, dim3(256), 0, S(stream), x, (long long)ldx, N, D, p.cps, d2, (long long)ldd, part);
+    BD_LAUNCH_CHECK("pairwise_sqdist");
+    if (part) {
+        hipLaunchKernelGGL(pairwise_fold_kernel, dim3((unsigned)p.nt, (unsigned)p.nt, 4), dim3(256), 0, S(stream), part, p.ksplit, N, d2,
+                           (long long)ldd);
+        BD_LAUNCH_CHECK("pairwise_fold");
+    }
+    return BD_OK;
+}
+
+extern "C" int bd_total_variation(const float* x, int N, int C, int H, int W, int64_t stride_n, int64_t stride_c, int64_t stride_h,
+                                  int64_t stride_w, float* tv, bd_stream_t stream) {
+    BD_CHECK(x && tv, BD_ERR_INVALID, "bd_total_variation: null pointer");
+    BD_CHECK(N > 0 && C > 0 && H > 0 && W > 0, BD_ERR_INVALID, "bd_total_variation: N=%d C=%d H=%d W=%d must be positive", N, C, H, W);
+    BD_CHECK((long long)C * H * W < (1ll << 31), BD_ERR_UNSUPPORTED, "bd_total_variation: C*H*W=%lld does not fit 31 bits", (long long)C * H * W);
+    hipLaunchKernelGGL(total_variation_kernel, dim3((unsigned)N), dim3(256), 0, S(stream), x, C, H, W, (long long)stride_n, (long long)stride_c,
+                       (long long)stride_h, (long long)stride_w, tv);
+    BD_LAUNCH_CHECK("total_variation");
+    return BD_OK;
+}
 
 extern "C" size_t bd_ssim_workspace_bytes(int N, int C, int H, int W) {
     if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;

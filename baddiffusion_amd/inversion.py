@@ -3,7 +3,7 @@
 A BadDiffusion backdoor makes the network's noise prediction follow a shift of the initial noise.  `invert_trigger` optimises such a
 shift `tau` through the FROZEN network: it needs nothing but d loss / d x, which `UNet2DModel` provides with its data-gradient-only
 backward (bd_unet_backward_input with grads == NULL: no weight gradient is computed in any of the passes).  Detection scores and
-backdoor removal built on the inverted trigger are follow-ups; this module states the optimisation below and nothing more.
+backdoor removal built on the inverted trigger are in defense.py; this module states the optimisation below and nothing more.
 """
 import torch
 

@@ -43,6 +43,43 @@ def ssim(preds, target, data_range=1.0):
     return float(ops.ssim(preds.float(), target.float(), data_range))
 
 
+def pairwise_sqdist(images):
+    """[N, N] device tensor of squared Euclidean distances between the flattened images of an [N, ...] float batch: the HIP kernel
+    bd_pairwise_sqdist, which subtracts in fp32 before it squares (never |a|^2 + |b|^2 - 2ab: that cancels on the near-identical
+    images a backdoored model produces).  Symmetric bit for bit, exact zeros on the diagonal and between duplicates."""
+    if not images.is_cuda:
+        raise RuntimeError("metrics.pairwise_sqdist: device tensors required (bd_pairwise_sqdist is a HIP kernel; no CPU fallback)")
+    if images.dim() < 1 or images.shape[0] < 1 or images.numel() == 0:
+        raise ValueError(f"pairwise_sqdist: expected a non-empty [N, ...] batch, got {tuple(images.shape)}")
+    from . import ops
+    return ops.pairwise_sqdist(images.float().contiguous().reshape(images.shape[0], -1))
+
+
+def uniformity(images):
+    """Mean pairwise Euclidean distance of a batch: mean over the unordered pairs i < j of sqrt(d2[i][j]), the square root and the mean
+    taken in fp64 on the device.  Small when the batch has collapsed onto one image (the backdoor target)."""
+    n = images.shape[0] if images.dim() >= 1 else 0
+    if n < 2:
+        raise ValueError(f"uniformity: needs at least two images, got {n}")
+    if not images.is_cuda:
+        raise RuntimeError("metrics.uniformity: device tensors required (the measure path runs on the GPU; no CPU fallback)")
+    d2 = pairwise_sqdist(images)
+    i, j = torch.triu_indices(n, n, offset=1, device=d2.device)
+    return float(d2[i, j].double().sqrt().mean())
+
+
+def total_variation(images):
+    """Mean over the batch of tv[n] / (C*H*W), tv[n] = the sum over channels of the absolute vertical and horizontal neighbour
+    differences of image n (HIP kernel bd_total_variation: fp32 differences, fp64 sums).  [N,C,H,W] in either memory format."""
+    if not images.is_cuda:
+        raise RuntimeError("metrics.total_variation: device tensors required (bd_total_variation is a HIP kernel; no CPU fallback)")
+    if images.dim() != 4 or images.numel() == 0:
+        raise ValueError(f"total_variation: expected a non-empty [N,C,H,W] tensor, got {tuple(images.shape)}")
+    from . import ops
+    tv = ops.total_variation(images.float())
+    return float(tv.double().mean() / (images.shape[1] * images.shape[2] * images.shape[3]))
+
+
 class ActivationStats:
     """Running mean / covariance of feature rows, accumulated in fp64 on the features' device
     (fid_score.py:207-230: mu = mean(act, 0), sigma = np.cov(act, rowvar=False))."""

@@ -639,6 +639,37 @@ def ssim(preds, target, data_range=1.0):
     return (total / N).float()
 
 
+def pairwise_sqdist(x, out=None):
+    """d2[i][j] = sum_k (x[i][k] - x[j][k])^2 of the rows of a float32 [N, D] GPU tensor whose last dim is contiguous (any row
+    stride): bd_pairwise_sqdist, difference first, square after.  `out`: a float32 [N, >= N] view to write into (last dim
+    contiguous); otherwise a new [N, N] tensor.  Returns out[:, :N]."""
+    lib = L.load(); _need_cuda(x, out)
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise TypeError(f"pairwise_sqdist: a float32 [N, D] tensor is required, got {x.dtype} {tuple(x.shape)}")
+    N, D = x.shape
+    if out is None:
+        out = torch.empty(N, N, device=x.device)
+    if out.dim() != 2 or out.dtype != torch.float32 or out.shape[0] != N or out.shape[1] < N:
+        raise TypeError(f"pairwise_sqdist: out must be float32 [{N}, >= {N}], got {out.dtype} {tuple(out.shape)}")
+    nbytes = lib.bd_pairwise_sqdist_workspace_bytes(N, D)
+    ws = workspace(nbytes, x.device, "pairwise") if nbytes else None
+    L.check(lib.bd_pairwise_sqdist(L.ptr(x), _ld(x), N, D, L.ptr(out), _ld(out), L.ptr(ws), nbytes, L.stream()), "bd_pairwise_sqdist")
+    return out[:, :N]
+
+
+def total_variation(images):
+    """tv[n] = sum of |vertical| + |horizontal| neighbour differences over all channels of a float32 [N,C,H,W] GPU tensor with any
+    strides (NCHW, channels_last, a permuted NHWC buffer): bd_total_variation.  Returns a float32 [N] device tensor."""
+    lib = L.load(); _need_cuda(images)
+    if images.dim() != 4 or images.dtype != torch.float32:
+        raise TypeError(f"total_variation: a float32 [N,C,H,W] tensor is required, got {images.dtype} {tuple(images.shape)}")
+    N, Cc, H, W = images.shape
+    tv = torch.empty(N, device=images.device)
+    sn, sc, sh, sw = images.stride()
+    L.check(lib.bd_total_variation(L.ptr(images), N, Cc, H, W, sn, sc, sh, sw, L.ptr(tv), L.stream()), "bd_total_variation")
+    return tv
+
+
 def sumsq(g, out=None):
     lib = L.load(); _need_cuda(g)
     if out is None:

@@ -1,0 +1,148 @@
+"""Elijah-style defense on the MI355X path: invert the trigger, score the checkpoint, remove the backdoor, score it again.
+
+    python elijah_defense.py --ckpt <checkpoint dir> [--inv_steps 100] [--inv_batch 64] [--inv_lr 0.1] [--lam 0.5]
+                             [--detect_n 256] [--sched DDIM-SCHED|DDPM-SCHED] [--infer_steps 50] [--max_ratio R]
+                             [--remove_steps 200] [--batch 64] [--learning_rate 2e-5] [--output_dir DIR] [--tag T] [--seed 0] [--gpu 0]
+
+The sibling of anp_defense.py.  Stages (baddiffusion_amd/inversion.py, baddiffusion_amd/defense.py):
+  1. invert_trigger: the shift tau the frozen network follows;
+  2. backdoor_scores of the checkpoint on noise / noise + tau, and -- only when --max_ratio is given -- the verdict;
+  3. remove_backdoor (skipped with --remove_steps 0);
+  4. backdoor_scores of the repaired model on the same noise.
+Outputs in <output_dir>/<name>: config.json, score.json ({"before", "after", "detected", "removal"}), tau.pt and the repaired model in the
+diffusers layout (unet/, scheduler/), which DiffuserModelSched.get_trained loads.  `--ckpt` must be a local diffusers-layout directory.
+"""
+import argparse
+import json
+import os
+from dataclasses import dataclass
+from typing import Union
+
+import torch
+
+from baddiffusion_amd import defense
+from baddiffusion_amd.inversion import invert_trigger
+from baddiffusion_amd.model import DiffuserModelSched, save_scheduler, save_unet
+from baddiffusion_amd.pipelines import DDIMPipeline, DDPMPipeline
+
+
+@dataclass
+class Config:
+    project: str = "elijah_test"
+    ckpt: Union[str, os.PathLike] = None
+    inv_steps: int = 100
+    inv_batch: int = 64
+    inv_lr: float = 0.1
+    lam: float = 0.5
+    detect_n: int = 256
+    sched: str = DiffuserModelSched.DDIM_SCHED
+    infer_steps: int = 50
+    max_ratio: float = None
+    remove_steps: int = 200
+    clip: bool = True
+    batch: int = 64
+    learning_rate: float = 2e-5
+    eval_max_batch: int = 256
+    gpu: str = "0"
+    tag: str = None
+    output_dir: Union[str, os.PathLike] = ""
+    score_file: Union[str, os.PathLike] = "score.json"
+    seed: int = 0
+
+
+def naming_fn(config):
+    add_on = f"_{config.tag}" if config.tag is not None else ""
+    return (f"res_elijah_inv{config.inv_steps}_lam{config.lam}_rm{config.remove_steps}_lr{config.learning_rate}{add_on}_"
+            f"{os.path.basename(str(config.ckpt).rstrip('/'))}")
+
+
+def get_config(argv=None):
+    config = Config()
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--project", "-pj", type=str)
+    p.add_argument("--ckpt", "-c", type=str, required=True)
+    p.add_argument("--inv_steps", type=int, default=config.inv_steps)
+    p.add_argument("--inv_batch", type=int, default=config.inv_batch)
+    p.add_argument("--inv_lr", type=float, default=config.inv_lr)
+    p.add_argument("--lam", type=float, default=config.lam)
+    p.add_argument("--detect_n", type=int, default=config.detect_n)
+    p.add_argument("--sched", "-sc", type=str, default=config.sched, choices=[DiffuserModelSched.DDIM_SCHED, DiffuserModelSched.DDPM_SCHED])
+    p.add_argument("--infer_steps", "-is", type=int, default=config.infer_steps)
+    p.add_argument("--max_ratio", type=float)
+    p.add_argument("--remove_steps", type=int, default=config.remove_steps)
+    p.add_argument("--batch", "-b", type=int, default=config.batch)
+    p.add_argument("--learning_rate", "-lr", type=float, default=config.learning_rate)
+    p.add_argument("--output_dir", "-od", type=str)
+    p.add_argument("--tag", "-t", type=str)
+    p.add_argument("--seed", type=int, default=config.seed)
+    p.add_argument("--gpu", "-g", type=str, default=config.gpu)
+    for k, v in vars(p.parse_args(argv)).items():
+        if v is not None:
+            setattr(config, k, v)
+    config.output_dir = os.path.join(config.output_dir or "", naming_fn(config))
+    os.makedirs(config.output_dir, exist_ok=True)
+    with open(os.path.join(config.output_dir, "config.json"), "w") as f:
+        json.dump({k: v for k, v in config.__dict__.items()}, f, indent=2, default=str)
+    return config
+
+
+def make_pipeline(config, model, noise_sched):
+    return (DDIMPipeline if config.sched == DiffuserModelSched.DDIM_SCHED else DDPMPipeline)(unet=model, scheduler=noise_sched)
+
+
+def invert(config, model, noise_sched, log=print):
+    g = torch.Generator(device=model.device); g.manual_seed(config.seed)
+    tau, losses = invert_trigger(model, steps=config.inv_steps, batch=config.inv_batch, lr=config.inv_lr, lam=config.lam,
+                                 timestep=noise_sched.num_train_timesteps - 1, generator=g)
+    log(f"inversion: loss {losses[0]:.6g} -> {losses[-1]:.6g}, |tau| {float(tau.norm()):.6g}")
+    torch.save(tau.cpu(), os.path.join(config.output_dir, "tau.pt"))
+    return tau
+
+
+def detection_noise(config, model):
+    """the one noise batch both score passes start from"""
+    s = model.sample_size
+    return torch.randn((config.detect_n, model.in_channels, s, s), generator=torch.manual_seed(config.seed))
+
+
+def score(config, model, noise_sched, tau, noise, log=print, tag="before"):
+    sc = defense.backdoor_scores(make_pipeline(config, model, noise_sched), tau, n=config.detect_n, init=noise.to(model.device),
+                                 max_batch_n=config.eval_max_batch, num_inference_steps=config.infer_steps)
+    log(f"[{tag}] " + json.dumps(sc))
+    return sc
+
+
+def remove(config, model, noise_sched, tau, log=print):
+    g = torch.Generator(device=model.device); g.manual_seed(config.seed + 1)
+    history = defense.remove_backdoor(model, noise_sched, tau, steps=config.remove_steps, batch=config.batch, lr=config.learning_rate, generator=g)
+    log(f"removal: loss {history[0]['loss']:.6g} -> {history[-1]['loss']:.6g}")
+    return history
+
+
+def save_model(config, model, noise_sched):
+    save_unet(model, os.path.join(config.output_dir, "unet"))
+    save_scheduler(noise_sched, os.path.join(config.output_dir, "scheduler"))
+
+
+def main(argv=None):
+    config = get_config(argv)
+    # the checkpoint's own scheduler carries the training tables and is saved back; --sched only picks the sampling pipeline
+    model, noise_sched, _ = DiffuserModelSched.get_pretrained(ckpt=config.ckpt, clip_sample=config.clip)
+    model = model.cuda()
+    tau = invert(config, model, noise_sched)
+    noise = detection_noise(config, model)
+    result = {"before": score(config, model, noise_sched, tau, noise, tag="before"), "after": None, "detected": None, "removal": []}
+    if config.max_ratio is not None:
+        result["detected"] = bool(defense.detect_backdoor(result["before"], max_ratio=config.max_ratio))
+        print(f"backdoor detected: {result['detected']} (uniformity_ratio {result['before']['uniformity_ratio']:.6g} vs {config.max_ratio})")
+    if config.remove_steps > 0:
+        result["removal"] = remove(config, model, noise_sched, tau)
+    result["after"] = score(config, model, noise_sched, tau, noise, tag="after")
+    with open(os.path.join(config.output_dir, config.score_file), "w") as f:
+        json.dump(result, f, indent=2)
+    save_model(config, model, noise_sched)
+    return result
+
+
+if __name__ == "__main__":
+    main()

@@ -409,6 +409,27 @@ int bd_ssim(const float* preds, const float* target, int N, int C, int H, int W,
             int64_t stride_h, int64_t stride_w, float data_range, float* out, void* workspace, size_t workspace_bytes,
             bd_stream_t stream);
 
+/* Backdoor detection statistics of a batch of generated images (baddiffusion_amd/defense.py, DESIGN.md section 3, "Detection statistics").
+ *
+ * bd_pairwise_sqdist: d2[i][j] = sum_k (x[i][k] - x[j][k])^2 for the N rows of x (fp32 [N, D], row stride ldx >= D floats;
+ * any 4-byte aligned x and any ldx, 16-byte aligned rows take vector loads).  The difference is taken in fp32 BEFORE it is
+ * squared: no Gram identity |a|^2 + |b|^2 - 2ab (which cancels on the close pairs a collapsed batch consists of) and no
+ * pre-centring.  Every unordered pair is computed once and the same value is stored at d2[i][j] and d2[j][i]; the diagonal is
+ * written as 0.0f; all N * N entries of d2 (fp32, row stride ldd >= N) are written, columns >= N of a row are not touched.
+ * When the 64 x 64 tiles of pairs alone do not fill the chip, D is split over workgroups into workspace partials that a
+ * second launch adds in split order (no atomics): the result is bit-identical from call to call.
+ * workspace >= bd_pairwise_sqdist_workspace_bytes(N, D) (0 when D is not split: workspace may then be NULL).
+ *
+ * bd_total_variation: tv[n] = sum_c ( sum_{h<H-1,w} |x[h+1][w] - x[h][w]| + sum_{h,w<W-1} |x[h][w+1] - x[h][w]| ) of an
+ * [N,C,H,W] batch given by element strides as in bd_ssim; differences in fp32, accumulated in fp64 in a fixed order that
+ * depends on the logical index only (NCHW and NHWC storage give the same bits).  tv: fp32 [N], written.  H = 1 / W = 1 are
+ * valid (that direction contributes 0).  Needs C*H*W < 2^31. */
+size_t bd_pairwise_sqdist_workspace_bytes(int N, int D);
+int bd_pairwise_sqdist(const float* x, int64_t ldx, int N, int D, float* d2, int64_t ldd, void* workspace,
+                       size_t workspace_bytes, bd_stream_t stream);
+int bd_total_variation(const float* x, int N, int C, int H, int W, int64_t stride_n, int64_t stride_c, int64_t stride_h,
+                       int64_t stride_w, float* tv, bd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * FID feature extractor (measure path, SURVEY f-3): the layer kernels of pytorch_fid's InceptionV3 up to pool3
  * (/root/reference/fid_score.py:53 `from pytorch_fid.inception import InceptionV3`, :91-148 get_activations, :255
