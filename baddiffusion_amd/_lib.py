@@ -143,6 +143,13 @@ class Conv2dDesc(C.Structure):
                 ("w_kc", i32)]
 
 
+LOSS_MAX_GROUPS = 4
+
+
+class LossGroupsDesc(C.Structure):
+    _fields_ = [("n_groups", i32), ("group_rows", i64 * LOSS_MAX_GROUPS), ("group_weight", f32 * LOSS_MAX_GROUPS)]
+
+
 class UnetConfig(C.Structure):
     _fields_ = [("sample_size", i32), ("in_channels", i32), ("out_channels", i32), ("num_blocks", i32),
                 ("block_out_channels", i32 * 8), ("down_attn", i32 * 8), ("up_attn", i32 * 8),
@@ -217,6 +224,8 @@ SIGNATURES = {
     "bd_silu_bwd": (i32, [vp, vp, vp, i64, i32, vp]),
     "bd_reduce_workspace_bytes": (sz, []),
     "bd_loss_fwd_bwd": (i32, [vp, i64, vp, i64, i64, i32, i32, f32, vp, vp, i64, vp, vp]),
+    "bd_loss_groups_workspace_bytes": (sz, [i32]),
+    "bd_loss_groups_fwd_bwd": (i32, [vp, i64, vp, i64, i64, i32, i32, f32, C.POINTER(LossGroupsDesc), vp, vp, i64, vp, sz, vp]),
     "bd_sumsq": (i32, [vp, i64, vp, vp, vp]),
     "bd_adam_clip": (i32, [vp, vp, vp, vp, i64, vp, f64, f64, f64, f64, f64, i32, vp, vp]),
     "bd_prof_enable": (i32, [i32]),

@@ -4,6 +4,7 @@
 // order is copied (q_sample, scheduler steps).
 #include "common.h"
 
+#include <cmath>
 #include <mutex>
 #include <string>
 
@@ -325,6 +326,13 @@ __device__ __forceinline__ double block_sum(double v, double* sh) {
     return r;  // valid on thread 0
 }
 
+// per-element loss l and derivative g of loss(target, pred) at df = pred - target
+__device__ __forceinline__ void loss_elem(int type, float df, float& l, float& g) {
+    if (type == 0) { l = df * df; g = 2.0f * df; }
+    else if (type == 1) { l = fabsf(df); g = df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f); }
+    else { float ad = fabsf(df); if (ad < 1.0f) { l = 0.5f * df * df; g = df; } else { l = ad - 0.5f; g = df > 0.f ? 1.f : -1.f; } }
+}
+
 __global__ __launch_bounds__(TPB) void loss_kernel(const float* pred, int64_t ldp, const float* tgt, int64_t ldt, int64_t rows,
                                                  int C, int type, float gscale, float* dpred, int64_t lddp, double* part) {
     __shared__ double sh[TPB / 64];
@@ -336,9 +344,7 @@ __global__ __launch_bounds__(TPB) void loss_kernel(const float* pred, int64_t ld
         const float p = pred[m * ldp + c], t = tgt[m * ldt + c];
         const float df = p - t;   // d/dpred of loss(target, pred)
         float l, g;
-        if (type == 0) { l = df * df; g = 2.0f * df; }
-        else if (type == 1) { l = fabsf(df); g = df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f); }
-        else { float ad = fabsf(df); if (ad < 1.0f) { l = 0.5f * df * df; g = df; } else { l = ad - 0.5f; g = df > 0.f ? 1.f : -1.f; } }
+        loss_elem(type, df, l, g);
         acc += (double)l;
         if (dpred) dpred[m * lddp + c] = g / (float)n * gscale;
     }
@@ -355,6 +361,47 @@ __device__ __forceinline__ double final_sum(const double* part, int nb) {
 __global__ __launch_bounds__(64) void loss_final_kernel(const double* part, int nb, int64_t n, float* loss) {
     const double s = final_sum(part, nb);
     if (threadIdx.x == 0) *loss = (float)(s / (double)n);
+}
+
+// Grouped form of the two kernels above: the rows are n_groups consecutive groups and blockIdx.y picks one.  Group g is walked by
+// its own nb[g] blocks with the block / stride pattern loss_kernel uses for a whole array of rows[g] rows, so one group of weight 1
+// reproduces loss_kernel's partials, loss and dpred bit for bit.  Partials of group g live at part[g * RED_BLOCKS ..].
+struct LossGroups {
+    int n_groups;
+    int nb[BD_LOSS_MAX_GROUPS];
+    int64_t row0[BD_LOSS_MAX_GROUPS], rows[BD_LOSS_MAX_GROUPS];
+    float weight[BD_LOSS_MAX_GROUPS];
+};
+__global__ __launch_bounds__(TPB) void loss_groups_kernel(const float* pred, int64_t ldp, const float* tgt, int64_t ldt, int C, int type,
+                                                        float gscale, float* dpred, int64_t lddp, double* part, LossGroups G) {
+    __shared__ double sh[TPB / 64];
+    const int grp = blockIdx.y, nb = G.nb[grp];
+    if ((int)blockIdx.x >= nb) return;          // (uniform per block: before any barrier)
+    const int64_t n = G.rows[grp] * C, row0 = G.row0[grp];
+    const float w = G.weight[grp];
+    double acc = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)nb * TPB) {
+        const int64_t m = row0 + i / C;
+        const int c = (int)(i % C);
+        const float df = pred[m * ldp + c] - tgt[m * ldt + c];
+        float l, g;
+        loss_elem(type, df, l, g);
+        acc += (double)l;
+        if (dpred) dpred[m * lddp + c] = g / (float)n * gscale * w;
+    }
+    double r = block_sum(acc, sh);
+    if (threadIdx.x == 0) part[(int64_t)grp * RED_BLOCKS + blockIdx.x] = r;
+}
+// losses[g] = S_g / n_g per group, losses[n_groups] = sum_g w_g S_g / n_g (fp64, groups in order)
+__global__ __launch_bounds__(64) void loss_groups_final_kernel(const double* part, int C, float* losses, LossGroups G) {
+    double total = 0.0;
+    for (int grp = 0; grp < G.n_groups; ++grp) {
+        const double s = final_sum(part + (int64_t)grp * RED_BLOCKS, G.nb[grp]);
+        const double n = (double)(G.rows[grp] * C);
+        if (threadIdx.x == 0) losses[grp] = (float)(s / n);
+        total += (double)G.weight[grp] * s / n;
+    }
+    if (threadIdx.x == 0) losses[G.n_groups] = (float)total;
 }
 
 __global__ __launch_bounds__(TPB) void sumsq_kernel(const float* g, int64_t n, double* part) {
@@ -655,6 +702,43 @@ extern "C" int bd_loss_fwd_bwd(const float* pred, int64_t ldp, const float* targ
     BD_LAUNCH_CHECK("loss");
     hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(64), 0, S(stream), (const double*)workspace, nb, rows * C, loss);
     BD_LAUNCH_CHECK("loss_final");
+    return BD_OK;
+}
+extern "C" size_t bd_loss_groups_workspace_bytes(int n_groups) {
+    if (n_groups < 1 || n_groups > BD_LOSS_MAX_GROUPS) return 0;
+    return (size_t)n_groups * RED_BLOCKS * sizeof(double);
+}
+extern "C" int bd_loss_groups_fwd_bwd(const float* pred, int64_t ldp, const float* target, int64_t ldt, int64_t rows, int C,
+                                      int loss_type, float grad_scale, const bd_loss_groups_desc* groups, float* losses,
+                                      float* dpred, int64_t lddp, void* workspace, size_t workspace_bytes, bd_stream_t stream) {
+    BD_CHECK(pred && target && groups && losses && workspace && rows > 0 && C > 0, BD_ERR_INVALID, "bd_loss_groups_fwd_bwd: bad args");
+    BD_CHECK(loss_type >= 0 && loss_type <= 2, BD_ERR_UNSUPPORTED, "bd_loss_groups_fwd_bwd: loss_type %d (l2=0,l1=1,huber=2)", loss_type);
+    BD_CHECK(groups->n_groups >= 1 && groups->n_groups <= BD_LOSS_MAX_GROUPS, BD_ERR_INVALID,
+             "bd_loss_groups_fwd_bwd: n_groups %d outside 1..%d", groups->n_groups, BD_LOSS_MAX_GROUPS);
+    LossGroups G = {};
+    G.n_groups = groups->n_groups;
+    int64_t row0 = 0;
+    unsigned nb_max = 1;
+    for (int g = 0; g < G.n_groups; ++g) {
+        const int64_t r = groups->group_rows[g];
+        const float w = groups->group_weight[g];
+        BD_CHECK(r > 0 && r <= rows - row0, BD_ERR_INVALID, "bd_loss_groups_fwd_bwd: group_rows[%d] = %lld (must be > 0 and sum to rows = %lld)",
+                 g, (long long)r, (long long)rows);
+        BD_CHECK(w >= 0.f && std::isfinite(w), BD_ERR_INVALID, "bd_loss_groups_fwd_bwd: group_weight[%d] = %g (must be finite and >= 0)", g,
+                 (double)w);
+        const unsigned nb = nblocks(r * C, TPB, RED_BLOCKS);
+        G.nb[g] = (int)nb; G.row0[g] = row0; G.rows[g] = r; G.weight[g] = w;
+        if (nb > nb_max) nb_max = nb;
+        row0 += r;
+    }
+    BD_CHECK(row0 == rows, BD_ERR_INVALID, "bd_loss_groups_fwd_bwd: group_rows sum to %lld, rows = %lld", (long long)row0, (long long)rows);
+    BD_CHECK(workspace_bytes >= bd_loss_groups_workspace_bytes(G.n_groups), BD_ERR_WORKSPACE,
+             "bd_loss_groups_fwd_bwd: workspace %zu < %zu bytes", workspace_bytes, bd_loss_groups_workspace_bytes(G.n_groups));
+    hipLaunchKernelGGL(loss_groups_kernel, dim3(nb_max, G.n_groups), dim3(TPB), 0, S(stream), pred, ldp, target, ldt, C, loss_type,
+                       grad_scale, dpred, lddp, (double*)workspace, G);
+    BD_LAUNCH_CHECK("loss_groups");
+    hipLaunchKernelGGL(loss_groups_final_kernel, dim3(1), dim3(64), 0, S(stream), (const double*)workspace, C, losses, G);
+    BD_LAUNCH_CHECK("loss_groups_final");
     return BD_OK;
 }
 extern "C" int bd_sumsq(const float* g, int64_t n, double* sumsq, void* workspace, bd_stream_t stream) {

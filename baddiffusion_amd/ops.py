@@ -570,6 +570,33 @@ def loss_fwd_bwd(pred, target, loss_type="l2", grad_scale=1.0, want_grad=True):
     return loss, dp
 
 
+def loss_groups_fwd_bwd(pred, target, groups, loss_type="l2", grad_scale=1.0, want_grad=True):
+    """The loss of loss_fwd_bwd over consecutive groups of rows (bd_loss_groups_fwd_bwd).  pred / target as in loss_fwd_bwd; `groups` is a
+    sequence of (row_count, weight) in rows of the [rows, C] view, 1 .. 4 of them, counts > 0 summing to rows, weights finite and >= 0.
+    Returns (losses float [n_groups + 1]: each group's own mean, then sum_g weight_g * mean_g; dpred contiguous [rows, C] or None),
+    dpred = d(weighted total)/dpred * grad_scale."""
+    lib = L.load(); _need_cuda(pred, target)
+    if loss_type not in LOSS_TYPES:
+        raise NotImplementedError()
+    groups = [(int(r), float(w)) for r, w in groups]
+    if not 1 <= len(groups) <= L.LOSS_MAX_GROUPS:
+        raise ValueError(f"loss_groups_fwd_bwd: 1..{L.LOSS_MAX_GROUPS} groups, got {len(groups)}")
+    Cc = pred.shape[-1]
+    rows = pred.numel() // Cc
+    p2 = pred.reshape(rows, Cc) if pred.is_contiguous() else pred
+    t2 = target.reshape(rows, Cc) if target.is_contiguous() else target
+    d = L.LossGroupsDesc(n_groups=len(groups))
+    for g, (r, w) in enumerate(groups):
+        d.group_rows[g], d.group_weight[g] = r, w
+    losses = torch.empty(len(groups) + 1, device=pred.device)
+    dp = torch.empty(rows, Cc, device=pred.device) if want_grad else None
+    nbytes = lib.bd_loss_groups_workspace_bytes(len(groups))
+    ws = workspace(nbytes, pred.device, "reduce")
+    L.check(lib.bd_loss_groups_fwd_bwd(L.ptr(p2), _ld(p2), L.ptr(t2), _ld(t2), rows, Cc, LOSS_TYPES[loss_type], grad_scale, C.byref(d),
+                                       L.ptr(losses), L.ptr(dp), Cc, L.ptr(ws), ws.numel(), L.stream()), "bd_loss_groups_fwd_bwd")
+    return losses, dp
+
+
 def lincomb(terms, coeffs, clip=None, out=None):
     """out = clamp?(sum_j coeffs[j] * terms[j]) (bd_lincomb): up to 6 dense float32 GPU tensors of one shape and layout."""
     lib = L.load(); _need_cuda(*terms)

@@ -189,6 +189,7 @@ class TrainEngine:
         self.v = torch.zeros(n, device=dev)
         self.sumsq = torch.zeros((), dtype=torch.float64, device=dev)
         self.grad_norm = torch.zeros((), device=dev)
+        self.group_losses = None       # per-group means of the last step taken with groups= (forward_backward)
         self.opt_step = 0      # optimizer steps taken
         self.micro = 0
         self._lib = L.load()
@@ -365,13 +366,23 @@ class TrainEngine:
         return self.lr * cosine_schedule_with_warmup(self.opt_step, self.warmup, self.total_steps)
 
     # ---- pieces ---------------------------------------------------------------------------------------
-    def forward_backward(self, xn, tg, t):
-        """xn / tg NHWC [B,H,W,C] ; fills self.grads (already all-reduced when world > 1); returns loss."""
+    def forward_backward(self, xn, tg, t, groups=None):
+        """xn / tg NHWC [B,H,W,C] ; fills self.grads (already all-reduced when world > 1); returns loss.
+        groups: ((batch_rows, weight), ...) splits the batch into consecutive groups, each with its own mean; the loss returned is
+        sum_g weight_g * mean_g and self.group_losses holds the per-group means (device float [n_groups]) of this call."""
         model = self.model
         flat = model.flat.data
-        pred, ws = model._run_forward(flat, xn, t, training=True)
-        loss, dpred = ops.loss_fwd_bwd(pred, tg, self.loss_type, grad_scale=1.0 / (self.world * self.accum))
         B = xn.shape[0]
+        if groups is not None and sum(int(r) for r, _ in groups) != B:
+            raise ValueError(f"forward_backward: groups {tuple(groups)} do not cover the batch of {B}")
+        pred, ws = model._run_forward(flat, xn, t, training=True)
+        if groups is None:
+            loss, dpred = ops.loss_fwd_bwd(pred, tg, self.loss_type, grad_scale=1.0 / (self.world * self.accum))
+        else:
+            hw = xn.shape[1] * xn.shape[2]
+            losses, dpred = ops.loss_groups_fwd_bwd(pred, tg, [(int(r) * hw, w) for r, w in groups], self.loss_type,
+                                                    grad_scale=1.0 / (self.world * self.accum))
+            loss, self.group_losses = losses[-1], losses[:-1]
         if self._dp_shadow is not None:
             self.grads.fill_(float("nan"))
             for plo, phi in model._pads:
@@ -505,9 +516,10 @@ class TrainEngine:
         xn, tg = ops.qsample(x_start, R, noise, timesteps, self.alphas, self.alphas_cumprod)
         return self.step_from_noisy(xn, tg, timesteps)
 
-    def step_from_noisy(self, xn, tg, timesteps):
+    def step_from_noisy(self, xn, tg, timesteps, groups=None):
+        """One eager step on an already noised NHWC batch.  `groups` as in forward_backward (not available in the graph-captured step)."""
         t = timesteps.to(torch.int64).contiguous()
-        loss = self.forward_backward(xn, tg, t)
+        loss = self.forward_backward(xn, tg, t) if groups is None else self.forward_backward(xn, tg, t, groups=groups)
         self.micro += 1
         if self.accum > 1:
             lib = self._lib

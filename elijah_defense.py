@@ -3,13 +3,17 @@
     python elijah_defense.py --ckpt <checkpoint dir> [--inv_steps 100] [--inv_batch 64] [--inv_lr 0.1] [--lam 0.5]
                              [--detect_n 256] [--sched DDIM-SCHED|DDPM-SCHED] [--infer_steps 50] [--max_ratio R]
                              [--remove_steps 200] [--batch 64] [--learning_rate 2e-5] [--output_dir DIR] [--tag T] [--seed 0] [--gpu 0]
+                             [--clean_source none|synthetic|dataset] [--clean_n 256] [--clean_batch 64] [--clean_weight 1.0]
+                             [--clean_target frozen|noise] [--dataset CIFAR10] [--dataset_path datasets]
 
 The sibling of anp_defense.py.  Stages (baddiffusion_amd/inversion.py, baddiffusion_amd/defense.py):
   1. invert_trigger: the shift tau the frozen network follows;
   2. backdoor_scores of the checkpoint on noise / noise + tau, and -- only when --max_ratio is given -- the verdict;
-  3. remove_backdoor (skipped with --remove_steps 0);
+  3. remove_backdoor (skipped with --remove_steps 0); with --clean_source synthetic (the checkpoint's own samples, synthesize_clean) or
+     dataset (DatasetLoader's resident uint8 images) it adds the clean-data term, and prediction_drift of the repaired model against the
+     frozen copy taken before the removal, on the same clean images, is written as score.json["drift"];
   4. backdoor_scores of the repaired model on the same noise.
-Outputs in <output_dir>/<name>: config.json, score.json ({"before", "after", "detected", "removal"}), tau.pt and the repaired model in the
+Outputs in <output_dir>/<name>: config.json, score.json ({"before", "after", "detected", "removal"[, "drift"]}), tau.pt and the repaired model in the
 diffusers layout (unet/, scheduler/), which DiffuserModelSched.get_trained loads.  `--ckpt` must be a local diffusers-layout directory.
 """
 import argparse
@@ -48,6 +52,13 @@ class Config:
     output_dir: Union[str, os.PathLike] = ""
     score_file: Union[str, os.PathLike] = "score.json"
     seed: int = 0
+    clean_source: str = "none"
+    clean_n: int = 256
+    clean_batch: int = 64
+    clean_weight: float = 1.0
+    clean_target: str = "frozen"
+    dataset: str = None
+    dataset_path: Union[str, os.PathLike] = "datasets"
 
 
 def naming_fn(config):
@@ -76,9 +87,18 @@ def get_config(argv=None):
     p.add_argument("--tag", "-t", type=str)
     p.add_argument("--seed", type=int, default=config.seed)
     p.add_argument("--gpu", "-g", type=str, default=config.gpu)
+    p.add_argument("--clean_source", type=str, default=config.clean_source, choices=["none", "synthetic", "dataset"])
+    p.add_argument("--clean_n", type=int, default=config.clean_n)
+    p.add_argument("--clean_batch", type=int, default=config.clean_batch)
+    p.add_argument("--clean_weight", type=float, default=config.clean_weight)
+    p.add_argument("--clean_target", type=str, default=config.clean_target, choices=list(defense.CLEAN_TARGETS))
+    p.add_argument("--dataset", "-ds", type=str)
+    p.add_argument("--dataset_path", "-dp", type=str, default=config.dataset_path)
     for k, v in vars(p.parse_args(argv)).items():
         if v is not None:
             setattr(config, k, v)
+    if config.clean_source == "dataset" and config.dataset is None:
+        p.error("--clean_source dataset needs --dataset")
     config.output_dir = os.path.join(config.output_dir or "", naming_fn(config))
     os.makedirs(config.output_dir, exist_ok=True)
     with open(os.path.join(config.output_dir, "config.json"), "w") as f:
@@ -112,11 +132,40 @@ def score(config, model, noise_sched, tau, noise, log=print, tag="before"):
     return sc
 
 
-def remove(config, model, noise_sched, tau, log=print):
+def clean_images(config, model, noise_sched, log=print):
+    """uint8 [N, H, W, C] device images for the clean-data term: the checkpoint's own samples, or the first --clean_n rows of the dataset"""
+    if config.clean_source == "synthetic":
+        g = torch.Generator(device=model.device); g.manual_seed(config.seed + 2)
+        clean = defense.synthesize_clean(make_pipeline(config, model, noise_sched), config.clean_n, generator=g, max_batch_n=config.eval_max_batch,
+                                         num_inference_steps=config.infer_steps)
+    else:
+        from baddiffusion_amd.dataset import DatasetLoader
+        root = config.dataset_path if config.dataset_path and os.path.isdir(str(config.dataset_path)) else None
+        dsl = DatasetLoader(root=root, name=config.dataset, channel=model.in_channels, image_size=model.sample_size, seed=config.seed,
+                            device=model.device, num_images=config.clean_n)
+        clean = dsl.device_images[: config.clean_n]
+        log(f"clean data: {dsl.source}")
+    log(f"clean data: {config.clean_source}, {tuple(clean.shape)}")
+    return clean
+
+
+def remove(config, model, noise_sched, tau, log=print, clean=None, frozen=None):
     g = torch.Generator(device=model.device); g.manual_seed(config.seed + 1)
-    history = defense.remove_backdoor(model, noise_sched, tau, steps=config.remove_steps, batch=config.batch, lr=config.learning_rate, generator=g)
+    if clean is None:
+        history = defense.remove_backdoor(model, noise_sched, tau, steps=config.remove_steps, batch=config.batch, lr=config.learning_rate, generator=g)
+    else:
+        history = defense.remove_backdoor(model, noise_sched, tau, steps=config.remove_steps, batch=config.batch, lr=config.learning_rate, generator=g,
+                                          clean=clean, clean_batch=config.clean_batch, clean_weight=config.clean_weight,
+                                          clean_target=config.clean_target, frozen=frozen)
     log(f"removal: loss {history[0]['loss']:.6g} -> {history[-1]['loss']:.6g}")
     return history
+
+
+def drift(config, model, frozen, clean, noise_sched, log=print):
+    g = torch.Generator(device=model.device); g.manual_seed(config.seed + 3)
+    d = defense.prediction_drift(model, frozen, clean, noise_sched, n=clean.shape[0], generator=g, max_batch_n=config.eval_max_batch)
+    log(f"prediction drift on the clean data: {d:.6g}")
+    return d
 
 
 def save_model(config, model, noise_sched):
@@ -135,7 +184,14 @@ def main(argv=None):
     if config.max_ratio is not None:
         result["detected"] = bool(defense.detect_backdoor(result["before"], max_ratio=config.max_ratio))
         print(f"backdoor detected: {result['detected']} (uniformity_ratio {result['before']['uniformity_ratio']:.6g} vs {config.max_ratio})")
-    if config.remove_steps > 0:
+    if config.clean_source != "none":
+        # one frozen copy serves the removal (its targets) and the drift (the predictions before the repair)
+        clean, frozen = clean_images(config, model, noise_sched), defense.frozen_copy(model)
+        if config.remove_steps > 0:
+            result["removal"] = remove(config, model, noise_sched, tau, clean=clean, frozen=frozen)
+        result["drift"] = drift(config, model, frozen, clean, noise_sched)
+        del frozen
+    elif config.remove_steps > 0:
         result["removal"] = remove(config, model, noise_sched, tau)
     result["after"] = score(config, model, noise_sched, tau, noise, tag="after")
     with open(os.path.join(config.output_dir, config.score_file), "w") as f:

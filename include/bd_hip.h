@@ -400,6 +400,25 @@ int bd_loss_fwd_bwd(const float* pred, int64_t ldp, const float* target, int64_t
                     int loss_type, float grad_scale, float* loss, float* dpred, int64_t lddp,
                     void* workspace, bd_stream_t stream);
 
+/* The same loss over n_groups consecutive groups of rows, each with its own mean and weight (the clean-data and shift terms of
+ * baddiffusion_amd/defense.py remove_backdoor, DESIGN.md section 3, "Grouped loss").  With n_g = group_rows[g] * C and S_g the fp64 sum
+ * of group g's per-element fp32 losses (fixed order, no atomics: two calls give the same bits):
+ *   losses[g] = (float)(S_g / n_g),  losses[n_groups] = (float)(sum_g (double)group_weight[g] * S_g / n_g)   (device float[n_groups + 1],
+ *   written), dpred[m][c] = ((g' / (float)n_g) * grad_scale) * group_weight[g] in fp32 (may be null; columns >= C of a row are not touched).
+ * Every group is reduced with the block / stride pattern bd_loss_fwd_bwd uses for a whole array, so one group of weight 1 gives
+ * losses[0], losses[1] and dpred bit-identical to it.  group_rows[g] > 0 and sum to rows; group_weight[g] finite and >= 0 (host
+ * values, checked before any launch).  workspace >= bd_loss_groups_workspace_bytes(n_groups) (0 for n_groups out of range). */
+#define BD_LOSS_MAX_GROUPS 4
+typedef struct {
+    int n_groups;                                   /* 1 .. BD_LOSS_MAX_GROUPS */
+    int64_t group_rows[BD_LOSS_MAX_GROUPS];
+    float group_weight[BD_LOSS_MAX_GROUPS];
+} bd_loss_groups_desc;
+size_t bd_loss_groups_workspace_bytes(int n_groups);
+int bd_loss_groups_fwd_bwd(const float* pred, int64_t ldp, const float* target, int64_t ldt, int64_t rows, int C,
+                           int loss_type, float grad_scale, const bd_loss_groups_desc* groups, float* losses,
+                           float* dpred, int64_t lddp, void* workspace, size_t workspace_bytes, bd_stream_t stream);
+
 /* f-3: mean structural similarity of two [N,C,H,W] image batches in [0, data_range] given by element strides (NCHW or
  * NHWC storage alike): StructuralSimilarityIndexMeasure(data_range=1.0) of baddiffusion.py:536-547 with the torchmetrics
  * defaults (11x11 Gaussian, sigma 1.5, k1 0.01, k2 0.03, reflect padding, cropped border, mean over C,H,W then batch).
