@@ -103,19 +103,28 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
-__device__ __forceinline__ float silu_f(float z) { return z / (1.0f + expf(-z)); }
-// d/dz [z * sigmoid(z)] = s * (1 + z * (1 - s))
-__device__ __forceinline__ float silu_grad_f(float z) {
-    float s = 1.0f / (1.0f + expf(-z));
-    return s * (1.0f + z * (1.0f - s));
+// ---- predicated loads without control flow and without a dependent select: masked-off lanes read zero bytes that live in the code
+// object.  Branch-free loads keep the s_waitcnt vmcnt() counting exact, and nothing touches the loaded registers until their first
+// use, which the register prefetch of the igemm kernels depends on (a skipped load would force vmcnt(0) at the join, a select would
+// wait for the load right behind its issue).  The zero page is also the LDS-DMA source of lanes whose filter tap falls outside the
+// image (splitplane.h).  One object per translation unit: the library is built without relocatable device code.
+[[maybe_unused]] static __device__ __attribute__((aligned(16))) const float bd_zero16[4] = {0.f, 0.f, 0.f, 0.f};
+typedef float bd_f32x4_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 bd_ld4_if(const float* p, bool ok) {      // global address space: global_load, not flat_load
+    const bd_f32x4_t t = *(const bd_f32x4_t __attribute__((address_space(1)))*)(ok ? p : bd_zero16);
+    return make_float4(t.x, t.y, t.z, t.w);
+}
+__device__ __forceinline__ float bd_ld1_if(const float* p, bool ok) {
+    return *(const float __attribute__((address_space(1)))*)(ok ? p : bd_zero16);
 }
 
 // ---- THE split of this library (round 6): x = hi + lo with hi = RNE_bf16(x), lo = RNE_bf16(x - hi).  x - hi is exact in fp32 (at most 16
 // significant bits), so hi + lo reproduces x to 2^-18 |x| and the dropped lo * lo product is <= 2^-18 of the term -- rounds 1 - 5 truncated
 // hi (the upper 16 bits of x), which costs one bit on both (per-convolution error vs fp64 8.8e-6 -> 4e-6, scripts/wino/numerics.py).  Every
-// producer of split planes and every on-the-fly split goes through these three functions: the MFMA engines stay bit-identical to one
+// producer of split planes and every on-the-fly split goes through these four functions: the MFMA engines stay bit-identical to one
 // another because they split identically.  (__bf16)float is v_cvt_pk_bf16_f32 on gfx950: round to nearest even.
 typedef __bf16 bd_bf16x2_t __attribute__((ext_vector_type(2)));
+typedef __bf16 bd_bf16x8_t __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ unsigned bd_pack_hi(float a, float b) {          // bf16 RNE(a) | bf16 RNE(b) << 16
     bd_bf16x2_t t;
     t[0] = (__bf16)a; t[1] = (__bf16)b;
@@ -135,17 +144,52 @@ __device__ __forceinline__ unsigned bd_split1(float v) {                    // h
     const __bf16 l = (__bf16)(v - __builtin_bit_cast(float, hb << 16));
     return hb | ((unsigned)__builtin_bit_cast(unsigned short, l) << 16);
 }
+__device__ __forceinline__ void bd_split8(const float (&x)[8], bd_bf16x8_t& hi, bd_bf16x8_t& lo) {   // eight values into MFMA fragments
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        hi[j] = (__bf16)x[j];
+        lo[j] = (__bf16)(x[j] - (float)hi[j]);      // (float)hi: the exact widening the functions above write as bits << 16
+    }
+}
 
 // ---- run-time tuning knobs (bd_tune_set): a generation counter that makes every plan lay its workspace out again -----------------
 extern int g_tune_gen;
 
-// ---- internal (non-ABI) launchers shared between files -------------------------------------------
-int igemm_launch(const bd_igemm_desc& d, hipStream_t stream);
+// ---- internal (non-ABI) launchers shared between files: every one is declared here and nowhere else ---------------------------
+int igemm_launch(const bd_igemm_desc& d, hipStream_t stream);                       // igemm.hip
 size_t igemm_workspace_bytes(const bd_igemm_desc& d);
-bool prof_on();
+bool prof_on();                                                                     // prof.cpp
 int prof_begin(const char* name, double flops, double bytes, hipStream_t st);
 void prof_end(int rec, hipStream_t st);
-int add_launch(const float* src, int64_t lds, float* dst, int64_t ldd, int64_t rows, int C, float scale, int acc,
+int add_launch(const float* src, int64_t lds, float* dst, int64_t ldd, int64_t rows, int C, float scale, int acc,   // elementwise.hip
                hipStream_t st);
+int conv3x3_fwd(const bd_conv3x3_fwd_desc& d, hipStream_t st);                      // conv.cpp
+int conv3x3_dgrad(const bd_conv3x3_dgrad_desc& d, hipStream_t st);
+int conv3x3_wgrad(const bd_conv3x3_wgrad_desc& d, hipStream_t st);
+int conv3x3_fwd_thin(const bd_conv3x3_fwd_desc& d, hipStream_t st);                 // conv_thin.hip
+int conv3x3_dgrad_thin(const bd_conv3x3_dgrad_desc& d, hipStream_t st);
+int conv3x3_wgrad_thin(const bd_conv3x3_wgrad_desc& d, hipStream_t st);
+bool conv3x3_wgrad_is_thin(const bd_conv3x3_wgrad_desc& d);
+int conv3x3_ps(const bd_conv3x3_ps_desc& d, hipStream_t st);                        // conv_ps.hip
+bool conv3x3_ps_supported(int B, int H, int W, int K_channels, int N_channels);
+int conv3x3_ps_wgrad(const bd_conv3x3_ps_wgrad_desc& d, hipStream_t st);
+size_t conv3x3_ps_wgrad_workspace_bytes(const bd_conv3x3_ps_wgrad_desc& d);
+bool conv3x3_ps_wgrad_supported(int B, int H, int W, int Cin, int Cout);
+int upsample_conv_wgrad(const bd_upsample_conv_desc& d, hipStream_t st);            // (PHASE form of the weight gradient)
+size_t upsample_conv_wgrad_workspace_bytes(const bd_upsample_conv_desc& d);
+int split_wt_batched(const float* params, uint16_t* out, const long long* off, const int* cin, const int* cout, int n, hipStream_t st);
+int upsample_weights(const float* w, int Cin, int Cout, uint16_t* e_split, uint16_t* et_split, hipStream_t st);   // conv_ph.hip
+int upsample_conv_fwd(const bd_upsample_conv_desc& d, hipStream_t st);
+int upsample_conv_dgrad(const bd_upsample_conv_desc& d, hipStream_t st);
+size_t upsample_conv_dgrad_workspace_bytes(const bd_upsample_conv_desc& d);
+bool upsample_conv_ps_supported(int B, int H, int W, int Cin, int Cout);
+int conv3x3_s2_dgrad_ps(const bd_conv3x3_s2_dgrad_desc& d, hipStream_t st);
+int ups_dweff_combine(const float* de, int Cin, int Cout, float* dw, hipStream_t st);
+int gemm_sp(const bd_gemm_sp_desc& d, hipStream_t st);                              // gemm_sp.hip
+size_t gemm_sp_workspace_bytes(const bd_gemm_sp_desc& d);
+bool gemm_sp_supported(int M, int N, int K);
+int attn_sp_fwd(const bd_attn_sp_desc& d, hipStream_t st);                          // attn_sp.hip
+int attn_sp_bwd(const bd_attn_sp_desc& d, hipStream_t st);
+bool attn_sp_supported(int N, int dh);
 
 }  // namespace bd

@@ -19,9 +19,6 @@ static int conv_geom_check(const char* who, int B, int Hs, int Ws, int Cin, int 
     return BD_OK;
 }
 
-int conv3x3_fwd_thin(const bd_conv3x3_fwd_desc& d, hipStream_t st);       // conv_thin.hip
-int conv3x3_dgrad_thin(const bd_conv3x3_dgrad_desc& d, hipStream_t st);
-
 int conv3x3_fwd(const bd_conv3x3_fwd_desc& d, hipStream_t st) {
     BD_TRY(conv_geom_check("conv3x3_fwd", d.B, d.Hs, d.Ws, d.Cin, d.Cout, d.stride, d.ups, d.Ho, d.Wo));
     BD_CHECK(d.x && d.w && d.y, BD_ERR_INVALID, "conv3x3_fwd: null pointer");
@@ -65,8 +62,6 @@ int conv3x3_dgrad(const bd_conv3x3_dgrad_desc& d, hipStream_t st) {
     g.workspace = d.workspace; g.workspace_bytes = d.workspace_bytes; g.mode = d.mode;
     return igemm_launch(g, st);
 }
-
-int conv3x3_wgrad_thin(const bd_conv3x3_wgrad_desc& d, hipStream_t st);   // conv_thin.hip
 
 int conv3x3_wgrad(const bd_conv3x3_wgrad_desc& d, hipStream_t st) {
     BD_TRY(conv_geom_check("conv3x3_wgrad", d.B, d.Hs, d.Ws, d.Cin, d.Cout, d.stride, d.ups, d.Ho, d.Wo));

@@ -77,7 +77,7 @@ __device__ __forceinline__ void ph_epilogue(const PhParams& p, const sp_floatx16
             if (p.accumulate) {
                 float old[16];
 #pragma unroll
-                for (int r = 0; r < 16; ++r) old[r] = *((FULL || rowoff[r] >= 0) ? p.y + rowoff[r] + n : kSpZero);   // branch-free
+                for (int r = 0; r < 16; ++r) old[r] = *((FULL || rowoff[r] >= 0) ? p.y + rowoff[r] + n : bd_zero16);   // branch-free
 #pragma unroll
                 for (int r = 0; r < 16; ++r) v[r] += old[r];
             }
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(PH_NT, 2) void conv_ph_kernel(PhParams p) {
         const int woff = __builtin_amdgcn_readlane(v_woff, tbase + q_t) + q_cb * 128;
         const int bit = 1 << q_t;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) sp_dma16((vm[j] & bit) ? ap[j] + aoff : reinterpret_cast<const char*>(kSpZero), stage + (wave + 8 * j) * 1024);
+        for (int j = 0; j < 4; ++j) sp_dma16((vm[j] & bit) ? ap[j] + aoff : reinterpret_cast<const char*>(bd_zero16), stage + (wave + 8 * j) * 1024);
 #pragma unroll
         for (int j = 0; j < 2; ++j) sp_dma16(wp[j] + woff, stage + PH_A_BYTES + (wave + 8 * j) * 1024);
         if (++q_t == ntaps) { q_t = 0; ++q_cb; }

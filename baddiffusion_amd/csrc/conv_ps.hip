@@ -214,7 +214,7 @@ __global__ __launch_bounds__(PS_NT, 2) void conv_ps_kernel(PsParams p) {
     int q_aoff = -p.sign * (p.W + 1) * pix_bytes, q_woff = 0;   // tap (0,0) of block 0
     auto issue = [&](char* stage) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) sp_dma16((vm[j] & q_bit) ? ap[j] + q_aoff : reinterpret_cast<const char*>(kSpZero), stage + (wave + 8 * j) * 1024);
+        for (int j = 0; j < 4; ++j) sp_dma16((vm[j] & q_bit) ? ap[j] + q_aoff : reinterpret_cast<const char*>(bd_zero16), stage + (wave + 8 * j) * 1024);
 #pragma unroll
         for (int j = 0; j < 2; ++j) sp_dma16(wp[j] + q_woff, stage + PS_A_BYTES + (wave + 8 * j) * 1024);
         // advance: kw fastest; a full window moves on to the next 32-channel block
@@ -337,7 +337,7 @@ __global__ __launch_bounds__(PS_NT, 2) void conv_ps3_kernel(PsParams p) {
         const int aoff = p.sign * (ga_kx - 1) * pix_bytes + ga_cb * 128;
         const int bit = 1 << ga_kx;
 #pragma unroll
-        for (int j = 0; j < 5; ++j) sp_dma16((vm[j] & bit) ? ap[j] + aoff : reinterpret_cast<const char*>(kSpZero), win + (wave + 8 * j) * 1024);
+        for (int j = 0; j < 5; ++j) sp_dma16((vm[j] & bit) ? ap[j] + aoff : reinterpret_cast<const char*>(bd_zero16), win + (wave + 8 * j) * 1024);
         if (++ga_kx == 3) { ga_kx = 0; ++ga_cb; }
     };
     int gb_ky = 0, gb_kx = 0, gb_cb = 0;
@@ -473,7 +473,7 @@ __global__ __launch_bounds__(512, STAGES == 2 ? 4 : 2) void conv_ps128_kernel(Ps
     auto issue = [&](char* stage) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            sp_dma16((vm[j] & q_bit) ? ap[j] + q_aoff : reinterpret_cast<const char*>(kSpZero), stage + (wave + 8 * j) * 1024);
+            sp_dma16((vm[j] & q_bit) ? ap[j] + q_aoff : reinterpret_cast<const char*>(bd_zero16), stage + (wave + 8 * j) * 1024);
             sp_dma16(wp[j] + q_woff, stage + A_BYTES + (wave + 8 * j) * 1024);
         }
         q_bit <<= 1;
@@ -674,12 +674,12 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_ps_wgrad_kernel(PsWgParams p)
         const bool ok = in && (unsigned)(y + dyt) < (unsigned)p.H && (unsigned)(x + dxt) < (unsigned)p.W;
         if constexpr (PH) {
             const long long fr = 4ll * pp - 2 * x + fine_off;       // pixel (2a+p, 2b+q) of the fine grid, x = pp & (W-1)
-            sp_dma16(in ? asrc[j] + fr * p.lddy * 4 : reinterpret_cast<const char*>(kSpZero), stage + (wave + NW * j) * 1024);
+            sp_dma16(in ? asrc[j] + fr * p.lddy * 4 : reinterpret_cast<const char*>(bd_zero16), stage + (wave + NW * j) * 1024);
         } else {
-            sp_dma16(in ? asrc[j] : reinterpret_cast<const char*>(kSpZero), stage + (wave + NW * j) * 1024);
+            sp_dma16(in ? asrc[j] : reinterpret_cast<const char*>(bd_zero16), stage + (wave + NW * j) * 1024);
             asrc[j] += a_adv;
         }
-        sp_dma16(ok ? bsrc[j] : reinterpret_cast<const char*>(kSpZero), stage + WG_OP_BYTES + (wave + NW * j) * 1024);
+        sp_dma16(ok ? bsrc[j] : reinterpret_cast<const char*>(bd_zero16), stage + WG_OP_BYTES + (wave + NW * j) * 1024);
         bsrc[j] += b_adv;
     };
     auto issue = [&](char* stage) {
@@ -897,7 +897,7 @@ __global__ __launch_bounds__(512, 2) void conv_ps_wgrad3_kernel(PsWgParams p) {
             const int x = sr & (p.W - 1);
             const bool ok = s >= 0 && s < p.P && (unsigned)(x + dxt) < (unsigned)p.W;
             const int unit = ((s0 + 4096) >> 4) & (WG3_RING_UNITS - 1);
-            sp_dma16(ok ? bbase_g[j] + (long long)(sr + dxt) * p.ldx * 4 : reinterpret_cast<const char*>(kSpZero),
+            sp_dma16(ok ? bbase_g[j] + (long long)(sr + dxt) * p.ldx * 4 : reinterpret_cast<const char*>(bd_zero16),
                      ring + unit * WG3_UNIT_BYTES + (s0 & 15) * 512);
         }
     };
@@ -1185,19 +1185,21 @@ bool conv3x3_ps_supported(int B, int H, int W, int K_channels, int N_channels) {
     return B > 0 && ilog2_exact(H) >= 0 && ilog2_exact(W) >= 0 && K_channels % 32 == 0 && N_channels % PS_BN == 0 && K_channels >= 32;
 }
 static bool ps_large(long long M, int N) { return cdiv(M, PS_BM) * (N / PS_BN) >= 96; }
-static void ps_small_split(long long M, int N, int K, int& ksplit, int& cps) {
-    const long long tiles = cdiv(M, 128) * (N / 128);
-    const int nchunks = 9 * (K / 32);
-    // one slot per CU (2 x CUs measured 0.1-0.2 ms/step slower: twice the slab traffic for the 4x4 / 8x8 layers), >= 4 chunks per split
-    split_k(device_cus(), tiles, nchunks, 4, ksplit, cps);
-}
-size_t conv3x3_ps_workspace_bytes(const bd_conv3x3_ps_desc& d) {
+// K split and slab bytes of one call: what bd_conv3x3_ps_workspace_bytes answers and what the launcher checks and hands the kernel.
+// Large layers (and shapes the launcher refuses) take no workspace.
+struct PsWs { int ksplit, cps; size_t bytes; };
+static PsWs ps_ws(const bd_conv3x3_ps_desc& d) {
+    PsWs s = {1, 0, 0};
     const long long M = (long long)d.B * d.H * d.W;
-    if (d.N % PS_BN || ps_large(M, d.N)) return 0;
-    int ks, cps;
-    ps_small_split(M, d.N, d.K, ks, cps);
-    return ks > 1 ? (size_t)ks * (size_t)M * d.N * sizeof(float) : 0;
+    if (d.N % PS_BN || ps_large(M, d.N)) return s;
+    const long long tiles = cdiv(M, 128) * (d.N / 128);
+    const int nchunks = 9 * (d.K / 32);
+    // one slot per CU (2 x CUs measured 0.1-0.2 ms/step slower: twice the slab traffic for the 4x4 / 8x8 layers), >= 4 chunks per split
+    split_k(device_cus(), tiles, nchunks, 4, s.ksplit, s.cps);
+    if (s.ksplit > 1) s.bytes = (size_t)s.ksplit * (size_t)M * d.N * sizeof(float);
+    return s;
 }
+size_t conv3x3_ps_workspace_bytes(const bd_conv3x3_ps_desc& d) { return ps_ws(d).bytes; }
 
 // does this call run on conv_ps3_kernel (256 x 128 tiles, whole tiles only)?
 static bool ps_takes_v3(int B, int H, int W, int N) {
@@ -1285,10 +1287,10 @@ int conv3x3_ps(const bd_conv3x3_ps_desc& d, hipStream_t st) {
         PsSmallParams pp = {};
         p.tiles_m = (int)cdiv(M, 128); p.tiles_n = d.N / 128;
         pp.q = p;
-        ps_small_split(M, d.N, d.K, pp.ksplit, pp.cps);
+        const PsWs ws = ps_ws(d);
+        pp.ksplit = ws.ksplit; pp.cps = ws.cps;
         if (pp.ksplit > 1) {
-            const size_t need = (size_t)pp.ksplit * (size_t)M * d.N * sizeof(float);
-            BD_CHECK(d.workspace && d.workspace_bytes >= need, BD_ERR_WORKSPACE, "conv3x3_ps: split-K needs %zu workspace bytes, got %zu", need,
+            BD_CHECK(d.workspace && d.workspace_bytes >= ws.bytes, BD_ERR_WORKSPACE, "conv3x3_ps: split-K needs %zu workspace bytes, got %zu", ws.bytes,
                      d.workspace_bytes);
             pp.partial = reinterpret_cast<float*>(d.workspace);
         }
@@ -1333,7 +1335,11 @@ static bool ps_wgrad_v3(const bd_conv3x3_ps_wgrad_desc& d) {
     return !off && d.W >= 16 && d.W <= maxw && ((long long)d.B * d.H * d.W) % 32 == 0;
 }
 static int g_wg3_slots_override = 0;     // 0: environment / default (set by bd_tune_set)
-static void ps_wgrad_split(const bd_conv3x3_ps_wgrad_desc& d, int& ksplit, int& cps) {
+// K split and slab bytes (Cout * 9 * Cin gradient + Cout bias-gradient floats per split) of one call: what
+// bd_conv3x3_ps_wgrad_workspace_bytes answers and what the launcher checks and hands the kernel
+struct PsWgWs { int ksplit, cps; size_t bytes; };
+static PsWgWs ps_wgrad_ws(const bd_conv3x3_ps_wgrad_desc& d) {
+    PsWgWs s = {1, 0, 0};
     const bool v3 = ps_wgrad_v3(d);
     const long long tiles = (long long)(d.Cout / WG_BM) * ((v3 ? 3 : 9) * d.Cin / WG_BN);
     const int nchunks = (int)cdiv((long long)d.B * d.H * d.W, 32);
@@ -1348,13 +1354,11 @@ static void ps_wgrad_split(const bd_conv3x3_ps_wgrad_desc& d, int& ksplit, int& 
     const int slots3_env = g_wg3_slots_override > 0 ? g_wg3_slots_override : slots3_getenv;      // bd_tune_set("ps_wg3_slots", n) wins over the environment
     const int slots3 = slots3_env > 0 ? slots3_env : (d.W > 32 ? slots / 4 : slots * 3 / 8);
     // chunks per split at least 8 (4x4 layers: 8 slabs instead of 14; 4 / 16 measured +0.2 / +0.1 ms)
-    split_k(v3 ? slots3 : slots, tiles, nchunks, 8, ksplit, cps);
+    split_k(v3 ? slots3 : slots, tiles, nchunks, 8, s.ksplit, s.cps);
+    if (s.ksplit > 1) s.bytes = (size_t)s.ksplit * ((size_t)d.Cout * 9 * d.Cin + d.Cout) * sizeof(float);
+    return s;
 }
-size_t conv3x3_ps_wgrad_workspace_bytes(const bd_conv3x3_ps_wgrad_desc& d) {
-    int ks, cps;
-    ps_wgrad_split(d, ks, cps);
-    return ks > 1 ? (size_t)ks * ((size_t)d.Cout * 9 * d.Cin + d.Cout) * sizeof(float) : 0;
-}
+size_t conv3x3_ps_wgrad_workspace_bytes(const bd_conv3x3_ps_wgrad_desc& d) { return ps_wgrad_ws(d).bytes; }
 int conv3x3_ps_wgrad(const bd_conv3x3_ps_wgrad_desc& d, hipStream_t st) {
     BD_CHECK(d.x_split && d.dy_split && d.dw, BD_ERR_INVALID, "conv3x3_ps_wgrad: null pointer");
     BD_CHECK(d.B > 0 && conv3x3_ps_wgrad_supported(d.B, d.H, d.W, d.Cin, d.Cout), BD_ERR_UNSUPPORTED,
@@ -1370,12 +1374,12 @@ int conv3x3_ps_wgrad(const bd_conv3x3_ps_wgrad_desc& d, hipStream_t st) {
     p.P = d.B * d.H * d.W;
     const bool v3 = ps_wgrad_v3(d);
     p.tiles_m = d.Cout / WG_BM; p.tiles_n = (v3 ? 3 : 9) * d.Cin / WG_BN; p.ntaps = 9;
-    ps_wgrad_split(d, p.ksplit, p.cps);
+    const PsWgWs ws = ps_wgrad_ws(d);
+    p.ksplit = ws.ksplit; p.cps = ws.cps;
     p.want_db = d.db != nullptr;
     const long long mn = (long long)d.Cout * 9 * d.Cin;
     if (p.ksplit > 1) {
-        const size_t need = (size_t)p.ksplit * ((size_t)mn + d.Cout) * sizeof(float);
-        BD_CHECK(d.workspace && d.workspace_bytes >= need, BD_ERR_WORKSPACE, "conv3x3_ps_wgrad: workspace %zu < %zu", d.workspace_bytes, need);
+        BD_CHECK(d.workspace && d.workspace_bytes >= ws.bytes, BD_ERR_WORKSPACE, "conv3x3_ps_wgrad: workspace %zu < %zu", d.workspace_bytes, ws.bytes);
         p.out = reinterpret_cast<float*>(d.workspace);
     } else {
         p.out = d.dw; p.db = d.db;
@@ -1401,8 +1405,6 @@ int conv3x3_ps_wgrad(const bd_conv3x3_ps_wgrad_desc& d, hipStream_t st) {
 }
 
 // ---- PHASE form of the weight gradient: the upsample convolution (conv_ph.hip) ---------------------------------------------------
-int ups_dweff_combine(const float* de, int Cin, int Cout, float* dw, hipStream_t st);   // conv_ph.hip
-
 static void ups_wgrad_split(const bd_upsample_conv_desc& d, int& ksplit, int& cps) {
     const long long tiles = (long long)(d.Cout / WG_BM) * (16 * d.Cin / WG_BN);
     const int nchunks = (int)cdiv((long long)d.B * d.H * d.W, 32);

@@ -11,7 +11,6 @@
 namespace bd {
 
 constexpr int THIN_TP = 64;   // pixels staged per LDS tile
-__device__ const float kThinZero = 0.f;
 
 struct ThinGeom {
     int B, H, W, pad_t, pad_l;          // stride-1 conv: output grid == input grid (H, W)
@@ -120,7 +119,7 @@ __global__ __launch_bounds__(256) void wgrad_thin_cout_kernel(const float* __res
                 for (int t = 0; t < 9; ++t) {
                     const int ys = y - g.pad_t + t / 3, xs_ = xx - g.pad_l + t % 3;
                     const bool ok = (unsigned)ys < (unsigned)g.H && (unsigned)xs_ < (unsigned)g.W;
-                    a[u][t] = *(ok ? xb + ((long long)ys * g.W + xs_) * ldx : &kThinZero);
+                    a[u][t] = *(ok ? xb + ((long long)ys * g.W + xs_) * ldx : bd_zero16);   // not bd_ld1_if: the global-address form costs these kernels 2 VGPRs
                 }
             }
 #pragma unroll
@@ -191,8 +190,6 @@ __global__ __launch_bounds__(1024) void thin_reduce_kernel(const float* __restri
 //            a 3 x 3 window of float2 slides along the row (3 coalesced 512-byte loads per pixel), the per-lane partial sums
 //            of the 32 pixels are folded across the wave by a halving butterfly (one shuffle per value, not six).
 // Both compute modes take these kernels: plain fp32 FMAs are exact products, i.e. at least as accurate as either MFMA path.
-__device__ __attribute__((aligned(16))) const float kThinZero4[4] = {0.f, 0.f, 0.f, 0.f};
-
 struct ThinCoef { long long base, sn, st, sj; };   // coefficient of (out channel n, tap t, in channel j) = w[base + n*sn + t*st + j*sj]
 
 template <int J>
@@ -264,15 +261,7 @@ __global__ __launch_bounds__(256) void thin_expand_kernel(const float* __restric
 // own 16 tap values (the 3-channel tensor is tiny: every read hits L1 / L2), splits them into bf16 hi | lo in registers (the same RNE / RNE
 // split as everywhere else) and multiplies against weight fragments built once per wave.  24 MFMAs (3 passes x 4 channel tiles x 2 K steps) + 16
 // loads + 64 coalesced 128-byte stores per 32 pixels and 128 channels: the kernel writes at the rate of its output.
-typedef __bf16 thin_bf16x8 __attribute__((ext_vector_type(8)));
 typedef float thin_f32x16 __attribute__((ext_vector_type(16)));
-__device__ __forceinline__ void thin_split8(const float (&v)[8], thin_bf16x8& hi, thin_bf16x8& lo) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        hi[j] = (__bf16)v[j];                       // common.h: hi = RNE_bf16(x), lo = RNE_bf16(x - hi)
-        lo[j] = (__bf16)(v[j] - (float)hi[j]);
-    }
-}
 
 template <int J>
 __global__ __launch_bounds__(256) void thin_expand_mfma_kernel(const float* __restrict__ in, long long ldi, const float* __restrict__ w, ThinCoef cm,
@@ -291,7 +280,7 @@ __global__ __launch_bounds__(256) void thin_expand_mfma_kernel(const float* __re
         kch[i] = k < 9 * J ? k % J : 0;
     }
     // weight fragments: lane = output channel li of tile q, its 16 k values, hi | lo
-    thin_bf16x8 bh[4][2], bl[4][2];
+    bd_bf16x8_t bh[4][2], bl[4][2];
     float bn[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -306,7 +295,7 @@ __global__ __launch_bounds__(256) void thin_expand_mfma_kernel(const float* __re
                 const float v = w[cm.base + (long long)n * cm.sn + (ktap[i] < 0 ? 0 : ktap[i]) * cm.st + kch[i] * cm.sj];
                 c[j] = ktap[i] < 0 ? 0.f : v;
             }
-            thin_split8(c, bh[q][s], bl[q][s]);
+            bd_split8(c, bh[q][s], bl[q][s]);
         }
     }
     const int HW = H * W;
@@ -326,13 +315,13 @@ __global__ __launch_bounds__(256) void thin_expand_mfma_kernel(const float* __re
             const int yc = min(max(ys, 0), H - 1), xc = min(max(xs, 0), W - 1);
             a[i] = in[((long long)b * HW + (long long)yc * W + xc) * ldi + kch[i]] * m;
         }
-        thin_bf16x8 ah[2], al[2];
+        bd_bf16x8_t ah[2], al[2];
         {
             float lo8[8], hi8[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) { lo8[j] = a[j]; hi8[j] = a[8 + j]; }
-            thin_split8(lo8, ah[0], al[0]);
-            thin_split8(hi8, ah[1], al[1]);
+            bd_split8(lo8, ah[0], al[0]);
+            bd_split8(hi8, ah[1], al[1]);
         }
         thin_f32x16 acc[4];
 #pragma unroll
@@ -754,9 +743,9 @@ __global__ __launch_bounds__(256) void wgrad_thin_mfma_kernel(const float* __res
 #pragma unroll
             for (int j = 0; j < 8; ++j) csum += bv[j];     // centre-tap columns: sum_p dy[p][o] = the bias gradient of conv_out
         }
-        thin_bf16x8 ah, al, bh, bl;
-        thin_split8(av, ah, al);
-        thin_split8(bv, bh, bl);
+        bd_bf16x8_t ah, al, bh, bl;
+        bd_split8(av, ah, al);
+        bd_split8(bv, bh, bl);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);

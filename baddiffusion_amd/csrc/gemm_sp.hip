@@ -370,17 +370,25 @@ __global__ __launch_bounds__(64) void gemm_sp_colsum_reduce(const float* __restr
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------
-static void sp_split(const bd_gemm_sp_desc& d, int& ksplit, int& cps) {
+// K split and workspace of one supported call (gemm_sp_supported): what bd_gemm_sp_workspace_bytes answers and what the launcher checks
+// and hands the kernels.  ksplit slabs of M x N floats, then at colsum_off the ksplit partial rows of the a_colsum bias gradient
+struct SpWs { int ksplit, cps; size_t bytes, colsum_off; };
+static SpWs sp_ws(const bd_gemm_sp_desc& d) {
+    SpWs s = {1, 0, 0, 0};
     const int nch = d.K / 32;
     const long long tiles = (long long)(d.M / SP_T) * (d.N / SP_T) * (d.batch > 0 ? d.batch : 1);
-    ksplit = 1;
     if (d.batch <= 1 && tiles < device_cus() && nch >= 32) {   // one workgroup per CU: the slabs are written and read once more each
-        ksplit = (int)cdiv(device_cus(), tiles);
-        if (ksplit > nch / 8) ksplit = nch / 8;
+        s.ksplit = (int)cdiv(device_cus(), tiles);
+        if (s.ksplit > nch / 8) s.ksplit = nch / 8;
     }
-    if (ksplit < 1) ksplit = 1;
-    cps = (int)cdiv(nch, ksplit);
-    ksplit = (int)cdiv(nch, cps);
+    if (s.ksplit < 1) s.ksplit = 1;
+    s.cps = (int)cdiv(nch, s.ksplit);
+    s.ksplit = (int)cdiv(nch, s.cps);
+    if (s.ksplit > 1) {
+        s.colsum_off = (size_t)s.ksplit * ((size_t)d.M * d.N) * sizeof(float);
+        s.bytes = s.colsum_off + (size_t)s.ksplit * d.M * sizeof(float);
+    }
+    return s;
 }
 
 bool gemm_sp_supported(int M, int N, int K) {
@@ -388,12 +396,7 @@ bool gemm_sp_supported(int M, int N, int K) {
     return !off && M > 0 && N > 0 && K > 0 && M % SP_T == 0 && N % SP_T == 0 && K % 32 == 0;
 }
 
-size_t gemm_sp_workspace_bytes(const bd_gemm_sp_desc& d) {
-    if (!gemm_sp_supported(d.M, d.N, d.K)) return 0;
-    int ksplit, cps;
-    sp_split(d, ksplit, cps);
-    return ksplit > 1 ? (size_t)ksplit * ((size_t)d.M * d.N + d.M) * sizeof(float) : 0;
-}
+size_t gemm_sp_workspace_bytes(const bd_gemm_sp_desc& d) { return gemm_sp_supported(d.M, d.N, d.K) ? sp_ws(d).bytes : 0; }
 
 int gemm_sp(const bd_gemm_sp_desc& d, hipStream_t st) {
     BD_CHECK(d.a && d.b && (d.c || d.c_split), BD_ERR_INVALID, "bd_gemm_sp: null pointer");
@@ -422,10 +425,10 @@ int gemm_sp(const bd_gemm_sp_desc& d, hipStream_t st) {
     p.alpha = d.alpha; p.out_scale = d.out_scale; p.accumulate = d.accumulate;
     p.M = d.M; p.N = d.N; p.K = d.K; p.tiles_m = d.M / SP_T; p.tiles_n = d.N / SP_T; p.batch = batch;
     p.colsum = d.a_colsum; p.want_colsum = d.a_colsum != nullptr;
-    sp_split(d, p.ksplit, p.cps);
+    const SpWs ws = sp_ws(d);
+    p.ksplit = ws.ksplit; p.cps = ws.cps;
     if (p.ksplit > 1) {
-        const size_t need = (size_t)p.ksplit * ((size_t)d.M * d.N + d.M) * sizeof(float);
-        BD_CHECK(d.workspace && d.workspace_bytes >= need, BD_ERR_WORKSPACE, "bd_gemm_sp: workspace %zu < %zu", d.workspace_bytes, need);
+        BD_CHECK(d.workspace && d.workspace_bytes >= ws.bytes, BD_ERR_WORKSPACE, "bd_gemm_sp: workspace %zu < %zu", d.workspace_bytes, ws.bytes);
         p.partial = reinterpret_cast<float*>(d.workspace);
     }
     const long long grid = (long long)p.tiles_m * p.tiles_n * batch * p.ksplit;
@@ -457,7 +460,7 @@ int gemm_sp(const bd_gemm_sp_desc& d, hipStream_t st) {
         hipLaunchKernelGGL(gemm_sp_reduce, dim3((unsigned)cdiv(work, 256)), dim3(256), 0, st, p);
         if (p.want_colsum)
             hipLaunchKernelGGL(gemm_sp_colsum_reduce, dim3((unsigned)cdiv(d.M, 64)), dim3(64), 0, st,
-                               p.partial + (long long)p.ksplit * d.M * d.N, p.ksplit, d.M, d.a_colsum);
+                               p.partial + ws.colsum_off / sizeof(float), p.ksplit, d.M, d.a_colsum);
         BD_LAUNCH_CHECK("gemm_sp_reduce");
     }
     prof_end(rec, st);

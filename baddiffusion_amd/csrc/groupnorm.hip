@@ -46,11 +46,6 @@ static int gn_apply_rows(int HW, int r) {
     return (int)per;
 }
 
-__device__ __forceinline__ float silu_dev(float z) { return z / (1.0f + expf(-z)); }
-__device__ __forceinline__ float silu_grad_dev(float z) {
-    const float s = 1.0f / (1.0f + expf(-z));
-    return s * (1.0f + z * (1.0f - s));
-}
 // Round 4: the sigmoid from the hardware transcendentals -- v_exp_f32 (2^x, 1 ulp) of -z * log2(e) and v_rcp_f32 (1 ulp): 4 VALU instructions instead of
 // the ~25 of expf() + an IEEE division, <= 3 ulp of fp32 (tests: 1e-5 against fp64 torch).  An instruction census of the CIFAR step
 // (scripts/valu_census.sh, SQ_INSTS_VALU per kernel) puts a THIRD of all VALU wave-instructions in the GroupNorm kernels, which share the chip with
@@ -87,16 +82,9 @@ __device__ __forceinline__ void gn_store_split4(unsigned short* row, int c, cons
     *reinterpret_cast<uint2*>(q + 32) = make_uint2(bd_pack_lo(o[0], o[1]), bd_pack_lo(o[2], o[3]));
 }
 
-// predicated 16-byte load without control flow: masked-off lanes read 16 zero bytes that live in the code object (the
-// igemm.hip idiom).  A `cond ? *p : 0` in an unrolled loop makes hipcc branch around every load and wait vmcnt(0) behind
-// it (cdna_hip_programming.md section 5, trap (c)): 16 serialised memory round trips per thread instead of 16 loads in flight.
-__device__ __attribute__((aligned(16))) const float kGnZero16[4] = {0.f, 0.f, 0.f, 0.f};
-typedef float gn_v4f __attribute__((ext_vector_type(4)));
-typedef const gn_v4f __attribute__((address_space(1))) * gn_gptr4;
-__device__ __forceinline__ float4 gn_ld4_if(const float* p, bool ok) {
-    const gn_v4f t = *(gn_gptr4)(ok ? p : kGnZero16);
-    return make_float4(t.x, t.y, t.z, t.w);
-}
+// The kernels below load their rows with common.h's bd_ld4_if.  A `cond ? *p : 0` in an unrolled loop makes hipcc branch around every
+// load and wait vmcnt(0) behind it (cdna_hip_programming.md section 5, trap (c)): 16 serialised memory round trips per thread instead
+// of 16 loads in flight.
 
 // ---- forward stats: per (b, split) partial (sum, sumsq) per group, in double -----------------------
 __global__ void gn_stats_kernel(const float* __restrict__ x, long long ldx, int HW, int C, int G, int r, int S,
@@ -115,7 +103,7 @@ __global__ void gn_stats_kernel(const float* __restrict__ x, long long ldx, int 
     for (int p = p0 + prow; p < p1; p += 4 * r) {   // four rows in flight (branch-free: rows past the end read zeros)
         float4 v[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = gn_ld4_if(xb + (long long)(p + u * r) * ldx, p + u * r < p1);
+        for (int u = 0; u < 4; ++u) v[u] = bd_ld4_if(xb + (long long)(p + u * r) * ldx, p + u * r < p1);
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             sm[0] += v[u].x; sm[1] += v[u].y; sm[2] += v[u].z; sm[3] += v[u].w;
@@ -201,7 +189,7 @@ __global__ void gn_apply_kernel(const float* __restrict__ x, long long ldx, floa
     for (int p = p0 + prow; p < p1; p += 4 * r) {
         float4 v[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = gn_ld4_if(xb + (long long)(p + u * r) * ldx, p + u * r < p1);
+        for (int u = 0; u < 4; ++u) v[u] = bd_ld4_if(xb + (long long)(p + u * r) * ldx, p + u * r < p1);
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const float in[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
@@ -259,8 +247,8 @@ __global__ void gn_bwd_stats_kernel(const float* __restrict__ x, long long ldx, 
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const bool ok = p + u * r < p1;
-            v[u] = gn_ld4_if(xb + (long long)(p + u * r) * ldx, ok);
-            d[u] = gn_ld4_if(db + (long long)(p + u * r) * lddy, ok);
+            v[u] = bd_ld4_if(xb + (long long)(p + u * r) * ldx, ok);
+            d[u] = bd_ld4_if(db + (long long)(p + u * r) * lddy, ok);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -437,10 +425,10 @@ __global__ void gn_bwd_apply_kernel(const float* __restrict__ x, long long ldx, 
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const bool ok = p + u * r < p1;
-            v[u] = gn_ld4_if(xb + (long long)(p + u * r) * ldx, ok);
-            d[u] = gn_ld4_if(db + (long long)(p + u * r) * lddy, ok);
-            e[u] = gn_ld4_if(ob + (long long)(p + u * r) * lddx, ok && do_acc);
-            a2[u] = gn_ld4_if(ab + (long long)(p + u * r) * ldadd, ok && addp != nullptr);
+            v[u] = bd_ld4_if(xb + (long long)(p + u * r) * ldx, ok);
+            d[u] = bd_ld4_if(db + (long long)(p + u * r) * lddy, ok);
+            e[u] = bd_ld4_if(ob + (long long)(p + u * r) * lddx, ok && do_acc);
+            a2[u] = bd_ld4_if(ab + (long long)(p + u * r) * ldadd, ok && addp != nullptr);
         }
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -561,7 +549,7 @@ __global__ __launch_bounds__(NT, NT == 256 ? 4 : 2) void gn_fwd_res_kernel(const
     for (int i = 0; i < EMAX; ++i) {
         const int p = prow + R * i;
         const bool ok = active && i < E && p < HW;
-        v[i] = gn_ld4_if(xb + (long long)p * ldx, ok);
+        v[i] = bd_ld4_if(xb + (long long)p * ldx, ok);
         sm[0] += v[i].x; sm[1] += v[i].y; sm[2] += v[i].z; sm[3] += v[i].w;
         sq[0] += v[i].x * v[i].x; sq[1] += v[i].y * v[i].y; sq[2] += v[i].z * v[i].z; sq[3] += v[i].w * v[i].w;
     }
@@ -690,8 +678,8 @@ __global__ __launch_bounds__(NT) void gn_bwd_res_kernel(const float* __restrict_
     for (int i = 0; i < EMAX; ++i) {
         const int p = prow + R * i;
         const bool ok = active && i < E && p < HW;
-        xh[i] = gn_ld4_if(xb + (long long)p * ldx, ok);
-        dz[i] = gn_ld4_if(db + (long long)p * lddy, ok);
+        xh[i] = bd_ld4_if(xb + (long long)p * ldx, ok);
+        dz[i] = bd_ld4_if(db + (long long)p * lddy, ok);
     }
 #pragma unroll
     for (int i = 0; i < EMAX; ++i) {
@@ -799,7 +787,7 @@ __global__ __launch_bounds__(NT) void gn_bwd_res_kernel(const float* __restrict_
 #pragma unroll
         for (int i = 0; i < EMAX; ++i) {
             const int p = prow + R * i;
-            xh[i] = gn_ld4_if(ob + (long long)p * lddx, i < E && p < HW);
+            xh[i] = bd_ld4_if(ob + (long long)p * lddx, i < E && p < HW);
         }
 #pragma unroll
         for (int i = 0; i < EMAX; ++i) { dz[i].x += xh[i].x; dz[i].y += xh[i].y; dz[i].z += xh[i].z; dz[i].w += xh[i].w; }
@@ -809,7 +797,7 @@ __global__ __launch_bounds__(NT) void gn_bwd_res_kernel(const float* __restrict_
 #pragma unroll
         for (int i = 0; i < EMAX; ++i) {
             const int p = prow + R * i;
-            xh[i] = gn_ld4_if(ab + (long long)p * ldadd, i < E && p < HW);
+            xh[i] = bd_ld4_if(ab + (long long)p * ldadd, i < E && p < HW);
         }
 #pragma unroll
         for (int i = 0; i < EMAX; ++i) { dz[i].x += xh[i].x; dz[i].y += xh[i].y; dz[i].z += xh[i].z; dz[i].w += xh[i].w; }

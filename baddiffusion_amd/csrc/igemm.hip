@@ -31,15 +31,6 @@ typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
-// split 8 fp32 values into hi + lo bf16 planes (common.h: hi = RNE_bf16(x), lo = RNE_bf16(x - hi)); x = hi + lo + O(2^-18 |x|).
-__device__ __forceinline__ void split8(const float (&x)[8], bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        hi[j] = (__bf16)x[j];
-        lo[j] = (__bf16)(x[j] - (float)hi[j]);
-    }
-}
-
 constexpr int BK = 32;
 constexpr int LDK = BK + 4;  // KC row stride (floats): 16B-aligned rows, conflict-free b128 reads
 
@@ -84,17 +75,6 @@ __device__ __forceinline__ int krow(int tid) {
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-// predicated 16-byte load without control flow and without a dependent select: masked-off lanes read 16 zero bytes
-// that live in the code object.  Branch-free loads keep the s_waitcnt vmcnt() counting exact, and nothing touches the
-// loaded registers until the split, which the two-chunk-deep register prefetch of the kernels depends on (a skipped
-// load would force vmcnt(0) at the join, a select would wait for the load right behind its issue).
-__device__ __attribute__((aligned(16))) const float kZero16[4] = {0.f, 0.f, 0.f, 0.f};
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef const v4f __attribute__((address_space(1))) * gptr4;   // global address space: global_load, not flat_load
-__device__ __forceinline__ float4 ld4_if(const float* p, bool ok, const float*) {
-    const v4f t = *(gptr4)(ok ? p : kZero16);
-    return make_float4(t.x, t.y, t.z, t.w);
-}
 
 // pixel index -> (b, y, x) over an (Ho, Wo) grid
 __device__ __forceinline__ void decode_pixel(const Opnd& o, int pix, int& b, int& y, int& x) {
@@ -212,7 +192,7 @@ struct DenseKC : KCStore<R, NT> {
     }
     __device__ __forceinline__ void load(const Opnd& o, float4 (&v)[NI]) const {
 #pragma unroll
-        for (int i = 0; i < NI; ++i) v[i] = ld4_if(ptr[i], ok[i] && krem > 0, o.p);
+        for (int i = 0; i < NI; ++i) v[i] = bd_ld4_if(ptr[i], ok[i] && krem > 0);
     }
     __device__ __forceinline__ void advance(const Opnd&) {
         krem -= BK;
@@ -253,7 +233,7 @@ struct ConvKC : KCStore<R, NT> {
             const int ys = y0[i] + kh, xs = x0[i] + kw;
             const bool okk = (unsigned)ys < (unsigned)He && (unsigned)xs < (unsigned)We && c0 < o.C;
             const int off = ((ys >> o.ups) * o.Ws + (xs >> o.ups)) * (int)o.ld + c0;
-            v[i] = ld4_if(base[i] + off, okk, o.p);
+            v[i] = bd_ld4_if(base[i] + off, okk);
         }
     }
     __device__ __forceinline__ void advance(const Opnd&) {
@@ -287,7 +267,7 @@ struct WgtKC : KCStore<R, NT> {
     __device__ __forceinline__ void load(const Opnd& o, float4 (&v)[NI]) const {
         const int off = tap * o.C + c0;
 #pragma unroll
-        for (int i = 0; i < NI; ++i) v[i] = ld4_if(ptr[i] + off, ok[i] && c0 < o.C, o.p);
+        for (int i = 0; i < NI; ++i) v[i] = bd_ld4_if(ptr[i] + off, ok[i] && c0 < o.C);
     }
     __device__ __forceinline__ void advance(const Opnd&) {
         if (++tap == 9) { tap = 0; c0 += BK; }
@@ -327,7 +307,7 @@ struct TConvKC : KCStore<R, NT> {
             const int ys = yn >> sh, xs = xn >> sh;
             const bool okk = yn >= 0 && xn >= 0 && ((yn | xn) & sh) == 0 && ys < o.Hs && xs < o.Ws && c0 < o.C;
             const int off = (ys * o.Ws + xs) * (int)o.ld + c0;
-            v[i] = ld4_if(base[i] + off, okk, o.p);
+            v[i] = bd_ld4_if(base[i] + off, okk);
         }
     }
     __device__ __forceinline__ void advance(const Opnd&) {
@@ -356,7 +336,7 @@ struct DenseRC : RCStore<R, NT> {
     }
     __device__ __forceinline__ void load(const Opnd& o, float4 (&v)[NI]) const {
 #pragma unroll
-        for (int i = 0; i < NI; ++i) v[i] = ld4_if(ptr + step * i, ok && krem > KS * i, o.p);
+        for (int i = 0; i < NI; ++i) v[i] = bd_ld4_if(ptr + step * i, ok && krem > KS * i);
     }
     __device__ __forceinline__ void advance(const Opnd& o) {
         ptr += (long long)BK * o.ld;
@@ -386,7 +366,7 @@ struct WgtRC : RCStore<R, NT> {
     __device__ __forceinline__ void load(const Opnd& o, float4 (&v)[NI]) const {
         const float* q = ptr + ((long long)c0 * 9 + tap) * o.ld;
 #pragma unroll
-        for (int i = 0; i < NI; ++i) v[i] = ld4_if(q + step * i, ok && c0 < o.C, o.p);
+        for (int i = 0; i < NI; ++i) v[i] = bd_ld4_if(q + step * i, ok && c0 < o.C);
     }
     __device__ __forceinline__ void advance(const Opnd&) {
         if (++tap == 9) { tap = 0; c0 += BK; }
@@ -399,8 +379,7 @@ struct WgtRC : RCStore<R, NT> {
 // full-line global reads like the fp32 source, and the lane -> (row, plane) maps below make every 16-lane group of a
 // ds_write_b128 sweep all 64 banks once.
 __device__ __forceinline__ float4 ldb8_if(const unsigned short* p, bool ok) {   // 8 bf16 as raw bits in a float4
-    const v4f t = *(gptr4)(ok ? (const void*)p : (const void*)kZero16);
-    return make_float4(t.x, t.y, t.z, t.w);
+    return bd_ld4_if(reinterpret_cast<const float*>(p), ok);
 }
 
 // forward-conv weights, rows = co, K order of ConvKC (channel block outer, tap inner).  Per wave instruction: 8 rows x
@@ -529,7 +508,7 @@ struct ConvRC : RCStore<R, NT> {
                 int b, y, x;
                 decode_pixel(o, p, b, y, x);
                 const bool okk = ok && p < Kp && (unsigned)(y + kh - o.pad_t) < (unsigned)o.Hs && (unsigned)(x + kw - o.pad_l) < (unsigned)o.Ws;
-                v[i] = ld4_if(ptr + step * i, okk, o.p);
+                v[i] = bd_ld4_if(ptr + step * i, okk);
             }
             return;
         }
@@ -542,7 +521,7 @@ struct ConvRC : RCStore<R, NT> {
             const int ys = y * o.stride - o.pad_t + kh, xs = x * o.stride - o.pad_l + kw;
             const bool okk = ok && p < Kp && (unsigned)ys < (unsigned)He && (unsigned)xs < (unsigned)We;
             const long long off = ((long long)b * o.Hs * o.Ws + (ys >> o.ups) * o.Ws + (xs >> o.ups)) * o.ld + ci;
-            v[i] = ld4_if(o.p + off, okk, o.p);
+            v[i] = bd_ld4_if(o.p + off, okk);
         }
     }
     __device__ __forceinline__ void advance(const Opnd&) { pix += BK; ptr += adv; }
@@ -578,7 +557,7 @@ struct ConvRCs : RCStore<R, NT> {
             int b, y, x;
             decode_pixel(o, p, b, y, x);
             const bool okk = ok && p < o.rows_k && (unsigned)(y + dy) < (unsigned)o.Hs && (unsigned)(x + dx) < (unsigned)o.Ws;
-            v[i] = ld4_if(ptr + step * i, okk, o.p);
+            v[i] = bd_ld4_if(ptr + step * i, okk);
         }
     }
     __device__ __forceinline__ void advance(const Opnd& o) { pix += BK; ptr += (long long)BK * o.ld; }
@@ -747,9 +726,6 @@ __device__ __forceinline__ WgCoord wg_coord(const IGemmParams& p) {
 }
 
 // ---- epilogue: lane holds column (n) li of rows (r&3) + 8*(r>>2) + 4*h of every 32x32 tile ---------------------
-// predicated scalar load without control flow (see ld4_if): masked-off lanes read a zero from the code object
-typedef const float __attribute__((address_space(1))) * gptr1;
-__device__ __forceinline__ float ld1_if(const float* p, bool ok) { return *(gptr1)(ok ? p : kZero16); }
 
 // All optional addends (row bias, residual, previous C) of a 32x32 tile are LOADED FIRST -- 16 branch-free loads each, all in
 // flight together -- and only then combined and stored.  The straightforward form (per element: `if (residual) v += *r;
@@ -777,7 +753,7 @@ __device__ __forceinline__ void epilogue_impl(const IGemmParams& p, floatx16 (&a
                 }
                 continue;
             }
-            const float bn = p.bias ? ld1_if(p.bias + n, nok) : 0.f;
+            const float bn = p.bias ? bd_ld1_if(p.bias + n, nok) : 0.f;
             float rb[16], rs[16], pc[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) { rb[r] = 0.f; rs[r] = 0.f; pc[r] = 0.f; }
@@ -785,21 +761,21 @@ __device__ __forceinline__ void epilogue_impl(const IGemmParams& p, floatx16 (&a
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int m = m_base + (r & 3) + 8 * (r >> 2);
-                    rb[r] = ld1_if(p.rowbias + (long long)(m / p.rows_per_group) * p.ld_rowbias + n, FULL || (nok && m < p.M));
+                    rb[r] = bd_ld1_if(p.rowbias + (long long)(m / p.rows_per_group) * p.ld_rowbias + n, FULL || (nok && m < p.M));
                 }
             }
             if (p.residual) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int m = m_base + (r & 3) + 8 * (r >> 2);
-                    rs[r] = ld1_if(p.residual + coff + (long long)m * p.ldr + n, FULL || (nok && m < p.M));
+                    rs[r] = bd_ld1_if(p.residual + coff + (long long)m * p.ldr + n, FULL || (nok && m < p.M));
                 }
             }
             if (p.accumulate) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int m = m_base + (r & 3) + 8 * (r >> 2);
-                    pc[r] = ld1_if(p.C + coff + (long long)m * p.ldc + n, FULL || (nok && m < p.M));
+                    pc[r] = bd_ld1_if(p.C + coff + (long long)m * p.ldc + n, FULL || (nok && m < p.M));
                 }
             }
 #pragma unroll
@@ -994,7 +970,7 @@ __global__ __launch_bounds__(NT, NT / 128) void igemm_bf16x3_kernel(IGemmParams 
 
     // Register prefetch two chunks deep: ra0/rb0 hold chunk c, ra1/rb1 chunk c+1; after a pair has been split into LDS it
     // is refilled with chunk c+2, whose loads then have two MFMA sections to land.  The loads are unconditional
-    // (predicated by address, ld4_if) and there is no branch in the loop body, so the compiler waits with exact
+    // (predicated by address, bd_ld4_if) and there is no branch in the loop body, so the compiler waits with exact
     // vmcnt(N) instead of vmcnt(0).  Chunks past c_end are loaded and never used (in-range addresses or masked off).
     // (DEPTH == 1: a single register set, refilled with chunk c+1 -- for the operand pairs whose address state does not
     // leave room for two sets under the 128-VGPR budget of the 512-thread form.)
@@ -1235,8 +1211,12 @@ static Opnd make_opnd(const bd_operand& o, int rows, int K) {
     return r;
 }
 
+// tile, K split and split-K workspace of one call: what bd_igemm_workspace_bytes answers and what the launcher checks.  The slabs
+// (ksplit per batch entry, M x N floats each) come first; the a_colsum partial rows (ksplit x M floats) lie behind them at colsum_off,
+// which is where colsum_tail and the reduce kernels look for them: partial[ksplit * M * N + ...]
 struct Choice {
     int tile, ksplit, cps;
+    size_t bytes, colsum_off;   // 0, 0 without a K split
 };
 
 static Choice choose(const bd_igemm_desc& d) {
@@ -1268,14 +1248,16 @@ static Choice choose(const bd_igemm_desc& d) {
     if (ks < 1) ks = 1;
     c.cps = (int)cdiv(nchunks, ks);
     c.ksplit = (int)cdiv(nchunks, c.cps);  // no empty splits
+    c.bytes = c.colsum_off = 0;
+    if (c.ksplit > 1) {
+        const size_t slabs = (size_t)d.batch_outer * d.batch_inner * c.ksplit;
+        c.colsum_off = slabs * ((size_t)d.M * d.N) * sizeof(float);
+        c.bytes = c.colsum_off + (d.a_colsum ? slabs * (size_t)d.M * sizeof(float) : 0);
+    }
     return c;
 }
 
-size_t igemm_workspace_bytes(const bd_igemm_desc& d) {
-    Choice c = choose(d);
-    if (c.ksplit <= 1) return 0;
-    return (size_t)d.batch_outer * d.batch_inner * c.ksplit * ((size_t)d.M * d.N + (d.a_colsum ? (size_t)d.M : 0)) * sizeof(float);
-}
+size_t igemm_workspace_bytes(const bd_igemm_desc& d) { return choose(d).bytes; }
 
 enum Cls { CLS_GENERIC = 0, CLS_CONV_FWD, CLS_CONV_DGRAD, CLS_CONV_WGRAD, CLS_GEMM_NT, CLS_GEMM_NN, CLS_GEMM_TN,
            CLS_CONV_FWD_WS, CLS_CONV_DGRAD_WS,     // _WS: weights (B) taken from pre-split bf16 planes
@@ -1387,9 +1369,8 @@ int igemm_launch(const bd_igemm_desc& d, hipStream_t stream) {
     BD_CHECK(!d.a_colsum || (nb == 1 && d.A.kc == 0 && d.A.kind == BD_OPK_DENSE && (d.M & 3) == 0), BD_ERR_UNSUPPORTED,
              "igemm: a_colsum needs a row-contiguous DENSE A operand, M %% 4 == 0 and batch 1");
     if (c.ksplit > 1) {
-        size_t need = (size_t)nb * c.ksplit * ((size_t)d.M * d.N + (d.a_colsum ? (size_t)d.M : 0)) * sizeof(float);
-        BD_CHECK(d.workspace && d.workspace_bytes >= need, BD_ERR_WORKSPACE,
-                 "igemm: split-K needs %zu workspace bytes, got %zu", need, d.workspace_bytes);
+        BD_CHECK(d.workspace && d.workspace_bytes >= c.bytes, BD_ERR_WORKSPACE,
+                 "igemm: split-K needs %zu workspace bytes, got %zu", c.bytes, d.workspace_bytes);
         p.partial = reinterpret_cast<float*>(d.workspace);
     }
     dim3 grid((unsigned)(p.tiles_m * p.tiles_n * nb * c.ksplit), 1, 1);

@@ -20,10 +20,7 @@ typedef const __attribute__((address_space(1))) void* sp_gbl_ptr;
 // (16 lanes = 16 different rows, same logical slot) touches each bank once.
 __device__ __forceinline__ int sp_swz(int row) { return (row >> 1) & 7; }
 
-// 16 zero bytes in the code object: the DMA source of lanes whose filter tap falls outside the image.  One object per translation
-// unit (the library is built without relocatable device code).
-[[maybe_unused]] static __device__ __attribute__((aligned(16))) const float kSpZero[4] = {0.f, 0.f, 0.f, 0.f};
-
+// (the DMA source of lanes whose filter tap falls outside the image is common.h's zero page, bd_zero16)
 __device__ __forceinline__ void sp_dma16(const char* src, char* lds_dst) {
     __builtin_amdgcn_global_load_lds((sp_gbl_ptr)src, (sp_lds_ptr)lds_dst, 16, 0, 0);
 }

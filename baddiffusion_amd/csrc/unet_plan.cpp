@@ -26,31 +26,6 @@
 
 namespace bd {
 
-int conv3x3_fwd(const bd_conv3x3_fwd_desc& d, hipStream_t st);
-int conv3x3_dgrad(const bd_conv3x3_dgrad_desc& d, hipStream_t st);
-int conv3x3_wgrad(const bd_conv3x3_wgrad_desc& d, hipStream_t st);
-bool conv3x3_wgrad_is_thin(const bd_conv3x3_wgrad_desc& d);
-int conv3x3_ps(const bd_conv3x3_ps_desc& d, hipStream_t st);                         // conv_ps.hip
-bool conv3x3_ps_supported(int B, int H, int W, int K_channels, int N_channels);
-int conv3x3_ps_wgrad(const bd_conv3x3_ps_wgrad_desc& d, hipStream_t st);
-size_t conv3x3_ps_wgrad_workspace_bytes(const bd_conv3x3_ps_wgrad_desc& d);
-bool conv3x3_ps_wgrad_supported(int B, int H, int W, int Cin, int Cout);
-int upsample_weights(const float* w, int Cin, int Cout, uint16_t* e_split, uint16_t* et_split, hipStream_t st);   // conv_ph.hip
-int upsample_conv_fwd(const bd_upsample_conv_desc& d, hipStream_t st);
-int upsample_conv_dgrad(const bd_upsample_conv_desc& d, hipStream_t st);
-int upsample_conv_wgrad(const bd_upsample_conv_desc& d, hipStream_t st);             // conv_ps.hip (PHASE form of the weight gradient)
-size_t upsample_conv_wgrad_workspace_bytes(const bd_upsample_conv_desc& d);
-size_t upsample_conv_dgrad_workspace_bytes(const bd_upsample_conv_desc& d);
-bool upsample_conv_ps_supported(int B, int H, int W, int Cin, int Cout);
-int conv3x3_s2_dgrad_ps(const bd_conv3x3_s2_dgrad_desc& d, hipStream_t st);
-int gemm_sp(const bd_gemm_sp_desc& d, hipStream_t st);                              // gemm_sp.hip
-size_t gemm_sp_workspace_bytes(const bd_gemm_sp_desc& d);
-bool gemm_sp_supported(int M, int N, int K);
-int attn_sp_fwd(const bd_attn_sp_desc& d, hipStream_t st);                          // attn_sp.hip
-int attn_sp_bwd(const bd_attn_sp_desc& d, hipStream_t st);
-bool attn_sp_supported(int N, int dh);
-int split_wt_batched(const float* params, uint16_t* out, const long long* off, const int* cin, const int* cout, int n, hipStream_t st);
-
 struct View {
     int buf = -1;   // value buffer id
     int coff = 0;   // channel offset inside the buffer
@@ -1295,12 +1270,27 @@ extern "C" int bd_unet_param_info(const bd_unet* u, int i, const char** name, in
 static size_t wsplit_elems(const bd_unet* u) { return (size_t)(u->nparams / 32 * 32); }
 static size_t wsplit_bytes(const bd_unet* u) { return align_up(wsplit_elems(u) * 2 * sizeof(uint16_t), 256); }
 
+// The arena of one call, after layout(B, training): byte offsets of the regions behind the activation floats (which start at 0) and
+// the size bd_unet_workspace_bytes reports.  The one place that knows the order of the regions.
+struct Arena { size_t opws, w_split, wT_split, opws2, gnpart, total; };
+static Arena unet_arena(const bd_unet* u) {
+    const size_t fl = (size_t)(u->value_floats + u->grad_floats + u->scratch_floats) * sizeof(float);
+    const size_t op = align_up(u->opws_bytes, 256);
+    Arena a;
+    a.opws = align_up(fl, 256);                // the main stream's op workspace
+    a.w_split = a.opws + op;                   // pre-split copy of the weights (the bf16 modes)
+    a.wT_split = a.w_split + wsplit_bytes(u);  // transposed conv-weight planes
+    a.opws2 = a.wT_split + wsplit_bytes(u);    // the side stream's op workspace
+    a.gnpart = a.opws2 + op;                   // GroupNorm parameter partials of one backward
+    // the end of the last region plus up to 256 bytes of slack: fl is counted unrounded + 256 (layout() makes opws_bytes a multiple of 256)
+    a.total = fl + u->opws_bytes + 256 + 2 * wsplit_bytes(u) + op + align_up(u->gnpart_floats * sizeof(float), 256);
+    return a;
+}
+
 extern "C" size_t bd_unet_workspace_bytes(bd_unet* u, int B, int training) {
     if (!u || B <= 0) return 0;
     u->layout(B, training);
-    return (size_t)(u->value_floats + u->grad_floats + u->scratch_floats) * sizeof(float) + u->opws_bytes + 256 +
-           2 * wsplit_bytes(u) + align_up(u->opws_bytes, 256) +   // + transposed conv-weight planes + the side stream's op workspace
-           align_up(u->gnpart_floats * sizeof(float), 256);      // + GroupNorm parameter partials of one backward
+    return unet_arena(u).total;
 }
 
 static int unet_ctx(bd_unet* u, Ctx& c, int B, int training, void* workspace, size_t workspace_bytes) {
@@ -1311,16 +1301,17 @@ static int unet_ctx(bd_unet* u, Ctx& c, int B, int training, void* workspace, si
     BD_CHECK(aligned16(workspace), BD_ERR_INVALID, "bd_unet: workspace must be 16-byte aligned");
     c.B = B; c.LB = B;
     c.ws = reinterpret_cast<float*>(workspace);
-    const size_t fl = (size_t)(u->value_floats + u->grad_floats + u->scratch_floats) * sizeof(float);
-    c.opws = reinterpret_cast<char*>(workspace) + align_up(fl, 256);
+    const Arena a = unet_arena(u);   // laid out by the size query above
+    char* const base = reinterpret_cast<char*>(workspace);
+    c.opws = base + a.opws;
     c.opws_bytes = u->opws_bytes;
     if (mode_bf16(u->cfg.compute_mode)) {
-        c.w_split = reinterpret_cast<const uint16_t*>(c.opws + align_up(u->opws_bytes, 256));
+        c.w_split = reinterpret_cast<const uint16_t*>(base + a.w_split);
+        c.wT_split = reinterpret_cast<const uint16_t*>(base + a.wT_split);
     }
-    c.opws2 = c.opws + align_up(u->opws_bytes, 256) + 2 * wsplit_bytes(u);
-    c.gnpart = u->gnpart_floats ? reinterpret_cast<float*>(c.opws2 + align_up(u->opws_bytes, 256)) : nullptr;
+    c.opws2 = base + a.opws2;
+    c.gnpart = u->gnpart_floats ? reinterpret_cast<float*>(base + a.gnpart) : nullptr;
     c.gnpart_floats = u->gnpart_floats; c.gnpart_used = 0;
-    if (c.w_split) c.wT_split = reinterpret_cast<const uint16_t*>(c.opws + align_up(u->opws_bytes, 256) + wsplit_bytes(u));
     c.ginit.assign(u->bufs.size(), 0);
     return BD_OK;
 }
