@@ -15,7 +15,12 @@
 //
 // Layout of this file: node builders (node_*) name parameters, buffers and the order of launches; what follows from a kernel-path choice
 // (descriptor type, operand format, weight copy, workspace, stream, dry-run accounting) lives in the run-time helpers of struct bd_unet
-// (conv3_fwd / conv3_dgrad / conv3_wgrad over a Conv3 record, gn_fwd / gn_bwd, grad_planes, need, take_ginit) and is written once.
+// and is written once: conv3_fwd / conv3_dgrad / conv3_wgrad (+ conv3_dgrad_input, conv3_gn_splits) and the phase-decomposed phase_ups_fwd /
+// phase_ups_wgrad / phase_ups_dgrad / phase_s2_dgrad over a Conv3 record; lin_fwd / lin_dgrad / lin_wgrad over a Lin record, temb_wgrad for the
+// batched time_emb_proj rows; attn_fwd / attn_bwd over an Attn record (head_gemm: the per-head products of the fp32 family); gn_fwd / gn_bwd,
+// grad_planes, silu_fwd / silu_bwd, add, colsum, split_rows, split_rows_ups2, sum2x2, timestep_embedding; need, take_ginit.  A node states each
+// path choice ONCE as a Path -- a function of the batch the workspace is laid out for -- and its buffers' `live`, reg_gsplit's `want` and both
+// closures ask that one function through takes(c, path).
 #include "common.h"
 
 #include <functional>
@@ -25,6 +30,17 @@
 #include <cstdlib>
 
 namespace bd {
+
+// the A/B knobs of this file, read once per process
+struct Knobs {
+    bool gsplit, conv_ps, shortcut_sp;      // BD_GSPLIT, BD_CONV_PS, BD_SHORTCUT_SP: on unless set to 0
+    long long fwd_pipes_minpx;              // BD_FWD_PIPES_MINPX: input pixels per batch from which the forward runs as two pipelines
+    static long long env(const char* name, long long dflt) { const char* v = getenv(name); return v ? atoll(v) : dflt; }
+    static const Knobs& get() {
+        static const Knobs k = {env("BD_GSPLIT", 1) != 0, env("BD_CONV_PS", 1) != 0, env("BD_SHORTCUT_SP", 1) != 0, env("BD_FWD_PIPES_MINPX", 32768)};
+        return k;
+    }
+};
 
 struct View {
     int buf = -1;   // value buffer id
@@ -115,7 +131,16 @@ struct Conv3Epi {       // forward epilogue terms: y = out_scale * (conv + bias 
     int gn_splits = 0;  // plane family: > 0 leaves the partial statistics of the GroupNorm that reads y next in the op workspace
 };
 
+// one Linear layer / 1x1 convolution of the plan: y[M, N] = x[M, K] W[N, K]^T + b (bd_unet::lin_fwd / lin_dgrad / lin_wgrad)
+struct Lin { int64_t pw, pb; int N, K; };
+struct LinEpi { const float* residual = nullptr; int64_t ldr = 0; float out_scale = 1.f; };     // y = out_scale * (x W^T + b + residual)
+// the core of one attention block (bd_unet::attn_fwd / attn_bwd): buffers of qkv [B*N, 3C], the scores P [B, heads, N, N], o [B*N, C] and
+// of their gradients; fp32 or split planes by the family of the call (same bytes)
+struct Attn { int heads, N, dh, C; float scale; int b_qkv, b_p, b_o, b_do, b_dp, b_dqkv; };
+
 typedef std::function<int(Ctx&)> Step;
+// a node's kernel-path choice as a function of the batch the workspace is laid out for (bd_unet::takes adds the context's part)
+typedef std::function<bool(int)> Path;
 
 }  // namespace bd
 
@@ -137,7 +162,8 @@ struct bd_unet {
     // gradient ranges that are final when a backward segment has run: the segment's own parameters [lo, hi) plus, for the
     // blocks that hold resnets, their rows of the batched time_emb_proj weight / bias (which live in the time-embedding
     // segment's range of the flat buffer but get their gradient inside the resnet's backward)
-    struct Seg { int64_t lo, hi; int64_t tw_lo = -1, tw_hi = -1, tb_lo = -1, tb_hi = -1; };
+    struct Range { int64_t lo = -1, hi = -1; void cover(int64_t l, int64_t h) { if (lo < 0 || l < lo) lo = l; if (h > hi) hi = h; } };
+    struct Seg { Range own, tw, tb; };
     std::vector<Seg> segs;   // indexed by segment id (backward order)
     int cur_seg = 0, cur_group = 0;
     // layout cache
@@ -155,11 +181,10 @@ struct bd_unet {
     // writes the planes of the final value next to the fp32 store (bd_gn_bwd_desc.dx_split + channel range): the producer's bd_split_rows
     // launch and its 4 B / element read disappear.  Consumers that end otherwise (down- / upsample data gradients) leave the fallback.
     // `want`: the producer's path predicate for a batch size (shape part; a context adds planes(c))
-    struct GSplit { int buf, coff, C, H, W; int b_pl; std::function<bool(int)> want; bool claimed = false, emitted = false; };
+    struct GSplit { int buf, coff, C, H, W; int b_pl; Path want; bool claimed = false, emitted = false; };
     std::vector<GSplit> gsplits;
-    int reg_gsplit(const View& y, std::function<bool(int)> want) {
-        static const bool off = getenv("BD_GSPLIT") && atoi(getenv("BD_GSPLIT")) == 0;      // (A/B knob)
-        if (off || y.buf < 0 || y.C % 32 != 0) return -1;
+    int reg_gsplit(const View& y, Path want) {
+        if (!Knobs::get().gsplit || y.buf < 0 || y.C % 32 != 0) return -1;
         GSplit e; e.buf = y.buf; e.coff = y.coff; e.C = y.C; e.H = y.H; e.W = y.W; e.want = std::move(want);
         const int keep = cur_group;
         e.b_pl = new_buf((int64_t)y.H * y.W * y.C, 0, R_GRAD);
@@ -180,11 +205,12 @@ struct bd_unet {
         }
         return got;
     }
-    struct UpsW { int64_t pw; int C, H, W; int b_e, b_et; };           // upsample convolutions on the phase path: E (/ E^T when training) planes
+    struct UpsW { int64_t pw; int C; Path phase; int b_e, b_et; };     // upsample convolutions on the phase path: E (/ E^T when training) planes
     // weight preprocessing (split copy, E planes) is skipped while the caller promises constant weights (bd_unet_set_static_weights):
     // a sampling loop runs 50-1000 forwards over the same parameters
     int static_weights = 0; const void* prep_params = nullptr; const void* prep_ws = nullptr; int prep_B = -1;
     std::vector<UpsW> upsw;
+    void forget_prepared() { prep_params = nullptr; prep_ws = nullptr; prep_B = -1; }
 
     // ---------------------------------------------------------------- construction helpers
     int new_buf(int64_t per_sample, int64_t fixed, int region) {
@@ -216,11 +242,7 @@ struct bd_unet {
         p.off = nparams;
         nparams += n;
         params.push_back(p);
-        if (!segs.empty()) {
-            Seg& s = segs[cur_seg];
-            if (s.lo < 0 || p.off < s.lo) s.lo = p.off;
-            if (p.off + n > s.hi) s.hi = p.off + n;
-        }
+        if (!segs.empty()) segs[cur_seg].own.cover(p.off, p.off + n);
         return p.off;
     }
     void alias_param(const std::string& name, int64_t off, std::initializer_list<int64_t> shape) {
@@ -283,79 +305,172 @@ struct bd_unet {
     static int lay_batch(const Ctx& c) { return c.LB > 0 ? c.LB : c.B; }
     // the split-plane kernels need the per-step plane copy of the weights (the dry run only sizes the workspace)
     static bool planes(const Ctx& c) { return c.dry || c.w_split; }
+    // THE place that applies a context to a node's path choice
+    static bool takes(const Ctx& c, const Path& path) { return planes(c) && path(lay_batch(c)); }
     static uint16_t* U16(float* p) { return reinterpret_cast<uint16_t*>(p); }
     static const uint16_t* U16(const float* p) { return reinterpret_cast<const uint16_t*>(p); }
 
-    int igemm(Ctx& c, bd_igemm_desc& g) const {
-        g.workspace = c.opws; g.workspace_bytes = c.opws_bytes; g.mode = cfg.compute_mode;
-        if (c.dry) { need(c, igemm_workspace_bytes(g)); return BD_OK; }
-        return igemm_launch(g, c.st);
-    }
-    // GEMM on split planes (gemm_sp.hip); aux: a weight gradient, on the side stream
-    int gemm_s(Ctx& c, bd_gemm_sp_desc& g, bool aux = false) const {
+    // a GEMM of either family; aux: a weight gradient, on the side stream (the attention block's on the main stream measured +0.35 ms per step)
+    template <class D, class Bytes, class Launch>
+    int gemm_run(Ctx& c, D& g, bool aux, Bytes bytes, Launch launch) const {
         if (aux && !c.wg) return BD_OK;
-        g.workspace_bytes = c.opws_bytes; g.mode = cfg.compute_mode;
-        if (c.dry) { need(c, gemm_sp_workspace_bytes(g)); return BD_OK; }
-        // (the attention block's weight gradients on the main stream measured +0.35 ms per step)
-        if (aux) return on_aux(c, [&](hipStream_t st, char* ws) { g.workspace = ws; return gemm_sp(g, st); });
-        g.workspace = c.opws;
-        return gemm_sp(g, c.st);
+        g.workspace = c.opws; g.workspace_bytes = c.opws_bytes; g.mode = cfg.compute_mode;
+        if (c.dry) { need(c, bytes(g)); return BD_OK; }
+        if (aux) return on_aux(c, [&](hipStream_t st, char* ws) { g.workspace = ws; return launch(g, st); });
+        return launch(g, c.st);
     }
+    int igemm(Ctx& c, bd_igemm_desc& g, bool aux = false) const { return gemm_run(c, g, aux, igemm_workspace_bytes, igemm_launch); }
+    int gemm_s(Ctx& c, bd_gemm_sp_desc& g, bool aux = false) const { return gemm_run(c, g, aux, gemm_sp_workspace_bytes, gemm_sp); }
     static bd_operand dense(const float* p, int64_t ld, int kc) {
         bd_operand o = {};
         o.kind = BD_OPK_DENSE; o.kc = kc; o.p = p; o.ld = ld;
         return o;
     }
-    // C[M,N] = alpha * A[M,K] * W[N,K]^T (+bias) (+residual)*out_scale        (Linear / 1x1 conv forward)
-    int linear_fwd(Ctx& c, const float* A, int64_t lda, const float* W, const float* bias, float* C, int64_t ldc, int M, int N,
-                   int K, const float* residual = nullptr, int64_t ldr = 0, float out_scale = 1.f) const {
+    // C[M, N] = op(A) op(B), one problem: fp32 operands (kc: the operand's rows run along K) / split planes (km: K-major)
+    static bd_igemm_desc gemm_f32(const float* A, int64_t lda, int kca, const float* B, int64_t ldb, int kcb, int M, int N, int K, float* C,
+                                  int64_t ldc) {
         bd_igemm_desc g = {};
-        g.A = dense(A, lda, 1); g.B = dense(W, K, 1);
+        g.A = dense(A, lda, kca); g.B = dense(B, ldb, kcb);
         g.M = M; g.N = N; g.K = K; g.batch_outer = g.batch_inner = 1;
-        g.C = C; g.ldc = ldc; g.alpha = 1.f; g.out_scale = out_scale; g.bias = bias; g.residual = residual; g.ldr = ldr;
+        g.C = C; g.ldc = ldc; g.alpha = 1.f; g.out_scale = 1.f;
+        return g;
+    }
+    static bd_gemm_sp_desc gemm_planes(const uint16_t* a, int64_t lda, int akm, const uint16_t* b, int64_t ldb, int bkm, int M, int N, int K) {
+        bd_gemm_sp_desc g = {};
+        g.M = M; g.N = N; g.K = K; g.batch = 1;
+        g.a = a; g.lda = lda; g.a_kmajor = akm; g.b = b; g.ldb = ldb; g.b_kmajor = bkm;
+        g.alpha = 1.f; g.out_scale = 1.f;
+        return g;
+    }
+    // ---- Linear layers / 1x1 convolutions.  Two families like the 3x3 convolutions: igemm on fp32 operands, and bd_gemm_sp on split planes
+    // with the per-step plane copy of the weight (K-contiguous rows: the layout a [N][K] weight wants forward, and the K-major operand of its
+    // data gradient as it stands).  The family is a flag per CALL (the shortcut's data gradient takes planes while its forward and weight
+    // gradient stay on igemm); the gates (gemm_sp_supported, ld % 4, BD_SHORTCUT_SP) stay where the node decides its path.
+    // y = out_scale * (x W^T + b + residual);  y_planes (plane family): y receives split planes [M, ldy] instead of fp32
+    int lin_fwd(Ctx& c, const Lin& l, bool sp, const Opnd& x, float* y, int64_t ldy, int M, bool y_planes = false, const LinEpi& e = LinEpi()) const {
+        if (!sp) {
+            bd_igemm_desc g = gemm_f32(x.p, x.ld, 1, c.params + l.pw, l.K, 1, M, l.N, l.K, y, ldy);
+            g.bias = c.params + l.pb; g.residual = e.residual; g.ldr = e.ldr; g.out_scale = e.out_scale;
+            return igemm(c, g);
+        }
+        bd_gemm_sp_desc g = gemm_planes(U16(x.p), x.ld, 0, c.w_split + 2 * l.pw, l.K, 0, M, l.N, l.K);
+        if (y_planes) { g.c_split = U16(y); g.ldcs = ldy; }
+        else { g.c = y; g.ldc = ldy; }
+        g.bias = c.params + l.pb; g.residual = e.residual; g.ldr = e.ldr; g.out_scale = e.out_scale;
+        return gemm_s(c, g);
+    }
+    // dx[M, K] (+)= dy[M, N] W;  dx_planes (plane family): dx receives split planes, written
+    int lin_dgrad(Ctx& c, const Lin& l, bool sp, const Opnd& dy, float* dx, int64_t lddx, int M, int acc, bool dx_planes = false) const {
+        if (!sp) {
+            bd_igemm_desc g = gemm_f32(dy.p, dy.ld, 1, c.params + l.pw, l.K, 0, M, l.K, l.N, dx, lddx);
+            g.accumulate = acc;
+            return igemm(c, g);
+        }
+        bd_gemm_sp_desc g = gemm_planes(U16(dy.p), dy.ld, 0, c.w_split + 2 * l.pw, l.K, 1, M, l.K, l.N);
+        if (dx_planes) { g.c_split = U16(dx); g.ldcs = lddx; }
+        else { g.c = dx; g.ldc = lddx; g.accumulate = acc; }
+        return gemm_s(c, g);
+    }
+    // dW[N, K] = dy[M, N]^T x[M, K], db[N] = column sums of dy out of the same launch; on the side stream in either family
+    int lin_wgrad(Ctx& c, const Lin& l, bool sp, const Opnd& dy, const Opnd& x, int M) const {
+        if (!sp) {
+            bd_igemm_desc g = gemm_f32(dy.p, dy.ld, 0, x.p, x.ld, 0, l.N, l.K, M, c.grads + l.pw, l.K);
+            g.a_colsum = c.grads + l.pb;
+            return igemm(c, g, true);
+        }
+        bd_gemm_sp_desc g = gemm_planes(U16(dy.p), dy.ld, 1, U16(x.p), x.ld, 1, l.N, l.K, M);
+        g.c = c.grads + l.pw; g.ldc = l.K; g.a_colsum = c.grads + l.pb;
+        return gemm_s(c, g, true);
+    }
+    // rows [lo, hi) of the batched time_emb_proj weight / bias gradient, dW = dtproj[:, rows]^T embs (resnet.py:571): the rows of a backward
+    // segment are adjacent in the [sumC, T] projection, so one GEMM per segment (one for a whole backward) replaces one tiny launch per resnet
+    int temb_wgrad(Ctx& c, int64_t lo, int64_t hi) const {
+        const Lin rows = {p_tw + lo * T, p_tb + lo, (int)(hi - lo), T};
+        return lin_wgrad(c, rows, false, {BP(c, b_dtproj) + lo, sumC}, {BP(c, b_embs), T}, c.B);
+    }
+
+    // ---- the attention core: P = softmax(scale Q K^T), O = P V per head, and its backward.  Plane family (attn_sp.hip): one launch forward,
+    // two backward, the [N, N] matrices stay on chip (P^T is kept for the backward when training); fp32 family: per-head batched igemm products
+    // around the softmax kernels, operands being [B*N, ld] token matrices whose head h owns columns [h*dh, (h+1)*dh), or the scores
+    struct HeadMat { float* p; int64_t ld, bs_outer, bs_inner; int cols; };
+    static HeadMat tokens(const Attn& a, float* p, int64_t ld) { return {p, ld, (int64_t)a.N * ld, a.dh, a.dh}; }
+    static HeadMat scores(const Attn& a, float* p) { return {p, a.N, (int64_t)a.heads * a.N * a.N, (int64_t)a.N * a.N, a.N}; }
+    // C = alpha * op(A) op(B) for every (sample, head); ta: A is read transposed ([K, M] rows), bt: B holds [N, K] rows
+    int head_gemm(Ctx& c, const Attn& a, const HeadMat& A, bool ta, const HeadMat& B, bool bt, const HeadMat& C, float alpha) const {
+        bd_igemm_desc g = gemm_f32(A.p, A.ld, ta ? 0 : 1, B.p, B.ld, bt ? 1 : 0, a.N, C.cols, ta ? a.N : A.cols, C.p, C.ld);
+        g.A.bs_outer = A.bs_outer; g.A.bs_inner = A.bs_inner; g.B.bs_outer = B.bs_outer; g.B.bs_inner = B.bs_inner;
+        g.c_bs_outer = C.bs_outer; g.c_bs_inner = C.bs_inner; g.batch_outer = c.B; g.batch_inner = a.heads; g.alpha = alpha;
         return igemm(c, g);
     }
-    // dX[M,K] (+)= dY[M,N] * W[N,K]
-    int linear_dgrad(Ctx& c, const float* dY, int64_t lddy, const float* W, float* dX, int64_t lddx, int M, int N, int K,
-                     int acc) const {
-        bd_igemm_desc g = {};
-        g.A = dense(dY, lddy, 1); g.B = dense(W, K, 0);
-        g.M = M; g.N = K; g.K = N; g.batch_outer = g.batch_inner = 1;
-        g.C = dX; g.ldc = lddx; g.alpha = 1.f; g.out_scale = 1.f; g.accumulate = acc;
-        return igemm(c, g);
+    bd_attn_sp_desc attn_planes(Ctx& c, const Attn& a) const {
+        bd_attn_sp_desc d = {};
+        d.B = c.B; d.heads = a.heads; d.N = a.N; d.dh = a.dh; d.qkv_split = U16(BP(c, a.b_qkv)); d.ld = 3 * a.C; d.scale = a.scale;
+        d.mode = cfg.compute_mode;
+        return d;
     }
-    // dW[N,K] = dY[M,N]^T * X[M,K]; db[N] = column sums of dY, fused into the same launch (N % 4 == 0)
-    int linear_wgrad(Ctx& c, const float* dY, int64_t lddy, const float* X, int64_t ldx, float* dW, int M, int N, int K,
-                     float* db = nullptr) const {
-        if (!c.wg) return BD_OK;
-        bd_igemm_desc g = {};
-        g.A = dense(dY, lddy, 0); g.B = dense(X, ldx, 0);
-        g.M = N; g.N = K; g.K = M; g.batch_outer = g.batch_inner = 1;
-        g.C = dW; g.ldc = K; g.alpha = 1.f; g.out_scale = 1.f; g.a_colsum = db;
-        if (c.dry) return igemm(c, g);
-        g.workspace_bytes = c.opws_bytes; g.mode = cfg.compute_mode;
-        return on_aux(c, [&](hipStream_t st, char* ws) { g.workspace = ws; return igemm_launch(g, st); });
+    int attn_fwd(Ctx& c, const Attn& a, bool sp) const {
+        if (sp) {
+            if (c.dry) return BD_OK;
+            bd_attn_sp_desc d = attn_planes(c, a);
+            d.o_split = U16(BP(c, a.b_o)); d.ldo = a.C; d.pt_split = c.training ? U16(BP(c, a.b_p)) : nullptr;
+            return attn_sp_fwd(d, c.st);
+        }
+        float* qkv = BP(c, a.b_qkv); float* P = BP(c, a.b_p);
+        const int C = a.C;
+        BD_TRY(head_gemm(c, a, tokens(a, qkv, 3 * C), false, tokens(a, qkv + C, 3 * C), true, scores(a, P), a.scale));       // S = scale * Q K^T
+        if (!c.dry) BD_TRY(bd_softmax_fwd(P, P, (int64_t)c.B * a.heads * a.N, a.N, (bd_stream_t)c.st));
+        return head_gemm(c, a, scores(a, P), false, tokens(a, qkv + 2 * C, 3 * C), false, tokens(a, BP(c, a.b_o), C), 1.f);      // O = P V
     }
+    // dqkv from dO (b_do), in the family's format
+    int attn_bwd(Ctx& c, const Attn& a, bool sp) const {
+        if (sp) {
+            if (c.dry) return BD_OK;
+            bd_attn_sp_desc d = attn_planes(c, a);
+            d.pt_split = U16(BP(c, a.b_p)); d.do_split = U16(BP(c, a.b_do)); d.lddo = a.C; d.dst_split = U16(BP(c, a.b_dp));
+            d.dqkv_split = U16(BP(c, a.b_dqkv)); d.lddqkv = 3 * a.C;
+            return attn_sp_bwd(d, c.st);
+        }
+        float* qkv = BP(c, a.b_qkv); float* dqkv = BP(c, a.b_dqkv); float* P = BP(c, a.b_p); float* dP = BP(c, a.b_dp);
+        const int C = a.C;
+        const HeadMat dO = tokens(a, BP(c, a.b_do), C);
+        BD_TRY(head_gemm(c, a, dO, false, tokens(a, qkv + 2 * C, 3 * C), true, scores(a, dP), 1.f));                        // dP = dO V^T
+        BD_TRY(head_gemm(c, a, scores(a, P), true, dO, false, tokens(a, dqkv + 2 * C, 3 * C), 1.f));                        // dV = P^T dO
+        if (!c.dry) BD_TRY(bd_softmax_bwd(P, dP, dP, (int64_t)c.B * a.heads * a.N, a.N, (bd_stream_t)c.st));
+        BD_TRY(head_gemm(c, a, scores(a, dP), false, tokens(a, qkv + C, 3 * C), false, tokens(a, dqkv, 3 * C), a.scale));   // dQ = scale * dS K
+        return head_gemm(c, a, scores(a, dP), true, tokens(a, qkv, 3 * C), false, tokens(a, dqkv + C, 3 * C), a.scale);     // dK = scale * dS^T Q
+    }
+
+    // launches without a workspace, on the main stream: the dry run has nothing to account for
     int colsum(Ctx& c, const float* x, int64_t ldx, int64_t nrows, int N, int64_t rpg, float* out, int64_t ldo) const {
-        if (c.dry) return BD_OK;
-        return bd_colsum(x, ldx, nrows, N, rpg, out, ldo, 0, c.st);
+        return c.dry ? BD_OK : bd_colsum(x, ldx, nrows, N, rpg, out, ldo, 0, c.st);
+    }
+    int add(Ctx& c, const float* src, int64_t lds, float* dst, int64_t ldd, int64_t nrows, int C, float scale, int acc) const {
+        return c.dry ? BD_OK : add_launch(src, lds, dst, ldd, nrows, C, scale, acc, c.st);
+    }
+    int split_rows(Ctx& c, const float* src, int64_t ld, int64_t nrows, int C, float* dst) const {
+        return c.dry ? BD_OK : bd_split_rows(src, ld, nrows, C, U16(dst), C, (bd_stream_t)c.st);
+    }
+    // ... of the nearest-upsampled x2 image: planes [B, 2H, 2W, C]
+    int split_rows_ups2(Ctx& c, const float* src, int64_t ld, int H, int W, int C, float* dst) const {
+        return c.dry ? BD_OK : bd_split_rows_ups2(src, ld, c.B, H, W, C, U16(dst), C, (bd_stream_t)c.st);
+    }
+    // dst [B, H, W, C] (+)= sums over the 2x2 blocks of src [B, 2H, 2W, C]: the adjoint of the nearest upsampling
+    int sum2x2(Ctx& c, const float* src, int64_t lds, float* dst, int64_t ldd, int H, int W, int C, int acc) const {
+        return c.dry ? BD_OK : bd_sum2x2(src, lds, dst, ldd, c.B, H, W, C, acc, (bd_stream_t)c.st);
+    }
+    int silu_fwd(Ctx& c, const float* x, float* y, int64_t n) const { return c.dry ? BD_OK : bd_silu_fwd(x, y, n, (bd_stream_t)c.st); }
+    int silu_bwd(Ctx& c, const float* x, const float* dy, float* dx, int64_t n) const {
+        return c.dry ? BD_OK : bd_silu_bwd(x, dy, dx, n, 0, (bd_stream_t)c.st);
+    }
+    int timestep_embedding(Ctx& c, int dim, float* out) const {
+        return c.dry ? BD_OK : bd_timestep_embedding(c.t, c.t_stride, c.B, dim, cfg.flip_sin_to_cos, cfg.freq_shift, out, (bd_stream_t)c.st);
     }
     // bias gradient: per-sample column sums (scratch [B,N]) then a sum over the batch (fixed order)
-    int bias_grad(Ctx& c, const float* dY, int64_t ld, int HW, int N, int scratch_buf, float* db, float* db2 = nullptr) const {
+    int bias_grad(Ctx& c, const float* dY, int64_t ld, int HW, int N, int scratch_buf, float* db) const {
         if (!c.wg) return BD_OK;
         float* s = BP(c, scratch_buf);
         BD_TRY(colsum(c, dY, ld, (int64_t)c.B * HW, N, HW, s, N));
-        BD_TRY(colsum(c, s, N, c.B, N, c.B, db, N));
-        if (db2) BD_TRY(colsum(c, s, N, c.B, N, c.B, db2, N));
-        return BD_OK;
-    }
-    int add(Ctx& c, const float* src, int64_t lds, float* dst, int64_t ldd, int64_t nrows, int C, float scale, int acc) const {
-        if (c.dry) return BD_OK;
-        return add_launch(src, lds, dst, ldd, nrows, C, scale, acc, c.st);
-    }
-    int split_rows(Ctx& c, const float* src, int64_t ld, int64_t nrows, int C, float* dst) const {
-        if (c.dry) return BD_OK;
-        return bd_split_rows(src, ld, nrows, C, U16(dst), C, (bd_stream_t)c.st);
+        return colsum(c, s, N, c.B, N, c.B, db, N);
     }
 
     // ---- GroupNorm (+SiLU).  x is a View (forward / backward into its gradient buffer) or, for a tensor without a persistent gradient
@@ -394,7 +509,7 @@ struct bd_unet {
                const float* dx_add = nullptr, int64_t ld_add = 0, int gs = -1) const {
         bd_gn_bwd_desc d = {};
         d.dx_add = dx_add; d.ld_add = ld_add;
-        if (gs >= 0 && planes(c) && gsplits[gs].want(lay_batch(c))) {      // this launch makes dL/dx final: hand its producer the planes of its channel range
+        if (gs >= 0 && takes(c, gsplits[gs].want)) {      // this launch makes dL/dx final: hand its producer the planes of its channel range
             const GSplit& e = gsplits[gs];
             d.dx_split = U16(BP(c, e.b_pl)); d.lddxs = e.C; d.dx_split_c0 = e.coff - x.coff; d.dx_split_c1 = d.dx_split_c0 + e.C;
         }
@@ -404,8 +519,8 @@ struct bd_unet {
 
     // ---- 3x3 convolutions.  Two kernel families: the literal implicit GEMM on fp32 operands (conv.cpp; any stride / padding / folded
     // nearest-upsampling) and the split-plane LDS-DMA kernels of conv_ps.hip (stride 1, pad 1, on the OUTPUT grid; the bf16 modes only, same
-    // arithmetic as igemm, bit-identical).  A node takes ONE decision per convolution and step (ps_ok), for its forward, data gradient and
-    // weight gradient alike -- they share the split operands -- and hands it to the three helpers below with operands in that family's
+    // arithmetic as igemm, bit-identical).  A node takes ONE decision per convolution and step (a Path over ps_shape), for its forward, data
+    // gradient and weight gradient alike -- they share the split operands -- and hands it to the three helpers below with operands in that family's
     // format; everything that follows from the decision (descriptor, weight copy, workspace, stream, dry-run accounting) lives in them.
     template <class D>
     static void conv3_geometry(D& d, const Ctx& c, const Conv3& k) {
@@ -415,11 +530,9 @@ struct bd_unet {
     // One decision per convolution, for its forward, data gradient and weight gradient alike, taken on the batch the workspace is laid
     // out for; shapes per conv3x3_ps_supported
     bool ps_shape(int B, int H, int W, int Cin, int Cout) const {
-        static const bool off = getenv("BD_CONV_PS") && atoi(getenv("BD_CONV_PS")) == 0;
-        return !off && mode_bf16(cfg.compute_mode) && conv3x3_ps_supported(B, H, W, Cin, Cout) && conv3x3_ps_supported(B, H, W, Cout, Cin) &&
-               conv3x3_ps_wgrad_supported(B, H, W, Cin, Cout);
+        return Knobs::get().conv_ps && mode_bf16(cfg.compute_mode) && conv3x3_ps_supported(B, H, W, Cin, Cout) &&
+               conv3x3_ps_supported(B, H, W, Cout, Cin) && conv3x3_ps_wgrad_supported(B, H, W, Cin, Cout);
     }
-    bool ps_ok(const Ctx& c, int H, int W, int Cin, int Cout) const { return planes(c) && ps_shape(lay_batch(c), H, W, Cin, Cout); }
     // phase-decomposed forms (conv_ph.hip): the upsample convolution on its SOURCE grid, the stride-2 data gradient by parity class
     // `min_wgs`: the launch must offer at least that many 256 x 128 workgroups (classes x tiles on the batch the workspace is laid
     // out for) -- a one-class 16-tap data gradient of an 8 x 8 source grid is 64 long workgroups on 256 CUs and loses to the literal form
@@ -427,8 +540,13 @@ struct bd_unet {
         const long long wgs = (long long)classes * (((long long)B * H * W + 255) / 256) * (Cout / 128);
         return mode_bf16(cfg.compute_mode) && upsample_conv_ps_supported(B, H, W, Cin, Cout) && wgs >= min_wgs;
     }
-    bool phase_ok(const Ctx& c, int H, int W, int Cin, int Cout, int classes = 4, int min_wgs = 128) const {
-        return planes(c) && phase_shape(lay_batch(c), H, W, Cin, Cout, classes, min_wgs);
+    // the upsample convolution's data gradient as ONE class of 16 taps on dY sampled at stride 2 (else: the fine-grid form + 2x2 sums): with
+    // >= 128 tiles of its own, or >= 32 where the launch deals the taps of a tile to four workgroups, as it does while the tiles fill at most half
+    // the chip.  KEEP IN STEP with ph_tap_groups of conv_ph.hip (256 x 128 = its PH_BM x PH_BN tile): that function takes the launcher's
+    // decision, this line restates it as the plan's path choice.  (phase_ups_dgrad sizes the workspace by the launcher's own function.)
+    bool phase_dgrad_shape(int B, int H, int W, int C) const {
+        const bool deals_taps = cdiv((int64_t)B * H * W, 256) * (C / 128) * 2 <= device_cus();
+        return phase_shape(B, H, W, C, C, deals_taps ? 4 : 1);
     }
     // the plane kernel in either direction: +1 forward (W planes of the per-step split copy), -1 data gradient (transposed planes)
     int conv3_planes(Ctx& c, const Conv3& k, int direction, const Opnd& x, float* y, int64_t ldy, int acc, const Conv3Epi& e) const {
@@ -470,6 +588,16 @@ struct bd_unet {
         if (c.w_split) d.w_split = c.w_split + 2 * k.pw;
         return conv3x3_dgrad(d, c.st);
     }
+    // the last link of the data-gradient chain: dL/dx of the network input (bd_unet_backward_input; c.dx null: not wanted), on the main stream
+    int conv3_dgrad_input(Ctx& c, const Conv3& k, const Opnd& dy) const {
+        if (!c.dx && !c.dry) return BD_OK;
+        return conv3_dgrad(c, k, false, dy, c.dx, c.lddx, 0);
+    }
+    // Conv3Epi::gn_splits of a plane-family forward: > 0 where the GroupNorm that reads its output would otherwise make a pass for its statistics
+    int conv3_gn_splits(const Ctx& c, const Conv3& k) const {
+        const int G = cfg.norm_num_groups;
+        return bd_gn_fwd_takes_stats(c.B, k.Ho * k.Wo, k.Cout, G) ? bd_conv3x3_ps_gn_splits(c.B, k.Ho, k.Wo, k.Cin, k.Cout, G) : 0;
+    }
     // weight and bias gradient.  Every weight gradient runs on the side stream: keeping the large layers' (they fill the chip on their own)
     // or the 4 x 4 / 8 x 8 layers' (10-30 us launches, as long as the fork / join) on the main stream measured 0.2 - 0.7 ms per step slower
     // bias_scratch >= 0: a [B, Cout] scratch for a Cout the igemm row-sum fusion cannot take (conv_out, Cout = 3): the bias gradient is
@@ -500,6 +628,45 @@ struct bd_unet {
         if (c.dry) { note_conv(c); return BD_OK; }
         return on_aux(c, [&](hipStream_t st, char* ws) { d.workspace = ws; return conv3x3_wgrad(d, st); });
     }
+    // ---- phase-decomposed forms (conv_ph.hip) of the upsample convolution k (ups = 1), on its SOURCE grid: x as split planes there, dy as
+    // split planes on the fine grid, the pre-summed tap planes E / E^T of the layer (prepared with the weights' plane copy)
+    bd_upsample_conv_desc phase_ups(const Ctx& c, const Conv3& k) const {
+        bd_upsample_conv_desc d = {};
+        d.mode = cfg.compute_mode; d.B = c.B; d.H = k.Hs; d.W = k.Ws; d.Cin = k.Cin; d.Cout = k.Cout;
+        return d;
+    }
+    int phase_ups_fwd(Ctx& c, const Conv3& k, const Opnd& x, const float* e_planes, float* y, int64_t ldy) const {
+        if (c.dry) return BD_OK;
+        bd_upsample_conv_desc d = phase_ups(c, k);
+        d.x_split = U16(x.p); d.ldx = x.ld; d.e_split = U16(e_planes); d.bias = c.params + k.pb; d.y = y; d.ldy = ldy;
+        return upsample_conv_fwd(d, c.st);
+    }
+    int phase_ups_wgrad(Ctx& c, const Conv3& k, const Opnd& x, const Opnd& dy) const {
+        if (!c.wg) return BD_OK;
+        bd_upsample_conv_desc d = phase_ups(c, k);
+        d.x_split = U16(x.p); d.ldx = x.ld; d.dy_split = U16(dy.p); d.lddy = dy.ld; d.dw = c.grads + k.pw; d.db = c.grads + k.pb;
+        d.workspace_bytes = c.opws_bytes;
+        if (c.dry) { need(c, upsample_conv_wgrad_workspace_bytes(d)); return BD_OK; }
+        return on_aux(c, [&](hipStream_t st, char* ws) { d.workspace = ws; return upsample_conv_wgrad(d, st); });
+    }
+    // the one-class form (phase_dgrad_shape): dx (+)= 16 taps on dY sampled at stride 2
+    int phase_ups_dgrad(Ctx& c, const Conv3& k, const Opnd& dy, const float* et_planes, float* dx, int64_t lddx, int acc) const {
+        bd_upsample_conv_desc d = phase_ups(c, k);
+        d.dy_split = U16(dy.p); d.lddy = dy.ld; d.et_split = U16(et_planes); d.dx = dx; d.lddx = lddx; d.accumulate = acc;
+        d.workspace = c.opws; d.workspace_bytes = c.opws_bytes;
+        if (c.dry) { need(c, upsample_conv_dgrad_workspace_bytes(d)); return BD_OK; }
+        return upsample_conv_dgrad(d, c.st);
+    }
+    // data gradient of the stride-2 convolution k by the parity class of the input pixel (4 / 2 / 2 / 1 of the nine taps), from dy as split
+    // planes on the output grid and the transposed weight planes
+    int phase_s2_dgrad(Ctx& c, const Conv3& k, const Opnd& dy, float* dx, int64_t lddx, int acc) const {
+        if (c.dry) return BD_OK;
+        bd_conv3x3_s2_dgrad_desc g = {};
+        g.B = c.B; g.Ho = k.Ho; g.Wo = k.Wo; g.Cin = k.Cin; g.Cout = k.Cout; g.pad = k.pad;
+        g.dy_split = U16(dy.p); g.lddy = dy.ld; g.wT_split = c.wT_split + 2 * k.pw;
+        g.dx = dx; g.lddx = lddx; g.accumulate = acc; g.mode = cfg.compute_mode;
+        return conv3x3_s2_dgrad_ps(g, c.st);
+    }
     // dL/dy of a node's output [nrows, C] as split planes (GSplit): the ones y's first consumer left when it made the gradient final (run-time
     // fact: `emitted` is set after the producer node was built), else bd_split_rows of the fp32 gradient into the node's own scratch
     int grad_planes(Ctx& c, int gs, const float* dy, int64_t lddy, int64_t nrows, int C, int b_scratch, Opnd& out) const {
@@ -525,15 +692,14 @@ struct bd_unet {
 // ----------------------------------------------------------------------------------------------------
 void bd_unet::node_time_embed() {
     const int c0 = cfg.block_out_channels[0];
-    const int64_t pw1 = add_param("time_embedding.linear_1.weight", {T, c0});
-    const int64_t pb1 = add_param("time_embedding.linear_1.bias", {T});
-    const int64_t pw2 = add_param("time_embedding.linear_2.weight", {T, T});
-    const int64_t pb2 = add_param("time_embedding.linear_2.bias", {T});
+    const Lin l1 = {add_param("time_embedding.linear_1.weight", {T, c0}), add_param("time_embedding.linear_1.bias", {T}), T, c0};
+    const Lin l2 = {add_param("time_embedding.linear_2.weight", {T, T}), add_param("time_embedding.linear_2.bias", {T}), T, T};
     // batched time_emb_proj of every resnet: one [sumC, T] weight, one [sumC] bias (aliases registered per resnet)
-    segs[cur_seg].hi = nparams;          // the time segment proper: linear_1 / linear_2 (the batched projection below is
+    segs[cur_seg].own.hi = nparams;      // the time segment proper: linear_1 / linear_2 (the batched projection below is
     nparams = (nparams + 31) / 32 * 32;   // reduced row range by row range with the blocks that own the resnets)
     p_tw = nparams; nparams += (int64_t)sumC * T;
     p_tb = nparams; nparams += sumC;
+    const Lin lp = {p_tw, p_tb, sumC, T};
     const int b_tsin = new_buf(c0, 0, R_VALUE), b_e1 = new_buf(T, 0, R_VALUE), b_e1s = new_buf(T, 0, R_VALUE);
     const int b_emb = new_buf(T, 0, R_VALUE);
     b_embs = new_buf(T, 0, R_VALUE);
@@ -541,26 +707,22 @@ void bd_unet::node_time_embed() {
     b_dtproj = new_buf(sumC, 0, R_GRAD);
     const int b_dembs = scratch(T), b_demb = scratch(T), b_de1s = scratch(T), b_de1 = scratch(T);
     F([=](Ctx& c) {
-        if (!c.dry)
-            BD_TRY(bd_timestep_embedding(c.t, c.t_stride, c.B, c0, cfg.flip_sin_to_cos, cfg.freq_shift, BP(c, b_tsin), (bd_stream_t)c.st));
-        BD_TRY(linear_fwd(c, BP(c, b_tsin), c0, c.params + pw1, c.params + pb1, BP(c, b_e1), T, c.B, T, c0));
-        if (!c.dry) BD_TRY(bd_silu_fwd(BP(c, b_e1), BP(c, b_e1s), (int64_t)c.B * T, (bd_stream_t)c.st));
-        BD_TRY(linear_fwd(c, BP(c, b_e1s), T, c.params + pw2, c.params + pb2, BP(c, b_emb), T, c.B, T, T));
-        if (!c.dry) BD_TRY(bd_silu_fwd(BP(c, b_emb), BP(c, b_embs), (int64_t)c.B * T, (bd_stream_t)c.st));
-        BD_TRY(linear_fwd(c, BP(c, b_embs), T, c.params + p_tw, c.params + p_tb, BP(c, b_tproj), sumC, c.B, sumC, T));
-        return (int)BD_OK;
+        BD_TRY(timestep_embedding(c, c0, BP(c, b_tsin)));
+        BD_TRY(lin_fwd(c, l1, false, {BP(c, b_tsin), c0}, BP(c, b_e1), T, c.B));
+        BD_TRY(silu_fwd(c, BP(c, b_e1), BP(c, b_e1s), (int64_t)c.B * T));
+        BD_TRY(lin_fwd(c, l2, false, {BP(c, b_e1s), T}, BP(c, b_emb), T, c.B));
+        BD_TRY(silu_fwd(c, BP(c, b_emb), BP(c, b_embs), (int64_t)c.B * T));
+        return lin_fwd(c, lp, false, {BP(c, b_embs), T}, BP(c, b_tproj), lp.N, c.B);
     });
     Bk([=](Ctx& c) {
         if (!c.wg) return (int)BD_OK;      // the timestep is not differentiable: this branch feeds weight gradients only
-        float* dtp = BP(c, b_dtproj);
-        // (the weight / bias gradient of the batched projection is produced resnet by resnet, see node_resnet)
-        BD_TRY(linear_dgrad(c, dtp, sumC, c.params + p_tw, BP(c, b_dembs), T, c.B, sumC, T, 0));
-        if (!c.dry) BD_TRY(bd_silu_bwd(BP(c, b_emb), BP(c, b_dembs), BP(c, b_demb), (int64_t)c.B * T, 0, (bd_stream_t)c.st));
-        BD_TRY(linear_wgrad(c, BP(c, b_demb), T, BP(c, b_e1s), T, c.grads + pw2, c.B, T, T, c.grads + pb2));
-        BD_TRY(linear_dgrad(c, BP(c, b_demb), T, c.params + pw2, BP(c, b_de1s), T, c.B, T, T, 0));
-        if (!c.dry) BD_TRY(bd_silu_bwd(BP(c, b_e1), BP(c, b_de1s), BP(c, b_de1), (int64_t)c.B * T, 0, (bd_stream_t)c.st));
-        BD_TRY(linear_wgrad(c, BP(c, b_de1), T, BP(c, b_tsin), c0, c.grads + pw1, c.B, T, c0, c.grads + pb1));
-        return (int)BD_OK;
+        // (the weight / bias gradient of the batched projection is produced segment by segment: temb_wgrad)
+        BD_TRY(lin_dgrad(c, lp, false, {BP(c, b_dtproj), lp.N}, BP(c, b_dembs), T, c.B, 0));
+        BD_TRY(silu_bwd(c, BP(c, b_emb), BP(c, b_dembs), BP(c, b_demb), (int64_t)c.B * T));
+        BD_TRY(lin_wgrad(c, l2, false, {BP(c, b_demb), T}, {BP(c, b_e1s), T}, c.B));
+        BD_TRY(lin_dgrad(c, l2, false, {BP(c, b_demb), T}, BP(c, b_de1s), T, c.B, 0));
+        BD_TRY(silu_bwd(c, BP(c, b_e1), BP(c, b_de1s), BP(c, b_de1), (int64_t)c.B * T));
+        return lin_wgrad(c, l1, false, {BP(c, b_de1), T}, {BP(c, b_tsin), c0}, c.B);
     });
 }
 
@@ -573,9 +735,7 @@ void bd_unet::node_conv_in(const View& y) {
     Bk([=](Ctx& c) {
         const Opnd dy = {GP(c, y), y.ld};
         BD_TRY(conv3_wgrad(c, k, false, {c.x, c.ldx}, dy));
-        if (!c.dx && !c.dry) return (int)BD_OK;
-        // the last link of the data-gradient chain: dL/dx of the network input (bd_unet_backward_input), on the main stream
-        return conv3_dgrad(c, k, false, dy, c.dx, c.lddx, 0);
+        return conv3_dgrad_input(c, k, dy);
     });
 }
 
@@ -587,24 +747,17 @@ void bd_unet::node_resnet(const std::string& pre, const View& x, const View& y, 
     alias_param(pre + "time_emb_proj.weight", p_tw + (int64_t)toff * T, {Cout, T});
     alias_param(pre + "time_emb_proj.bias", p_tb + toff, {Cout});
     {   // this block's rows of the batched projection become final with this segment (resnets of a block are consecutive)
-        Seg& sg = segs[cur_seg];
-        const int64_t wlo = p_tw + (int64_t)toff * T, whi = wlo + (int64_t)Cout * T, blo = p_tb + toff, bhi = blo + Cout;
-        if (sg.tw_lo < 0) { sg.tw_lo = wlo; sg.tw_hi = whi; sg.tb_lo = blo; sg.tb_hi = bhi; }
-        else {
-            if (wlo < sg.tw_lo) sg.tw_lo = wlo;
-            if (whi > sg.tw_hi) sg.tw_hi = whi;
-            if (blo < sg.tb_lo) sg.tb_lo = blo;
-            if (bhi > sg.tb_hi) sg.tb_hi = bhi;
-        }
+        const int64_t wlo = p_tw + (int64_t)toff * T, blo = p_tb + toff;
+        segs[cur_seg].tw.cover(wlo, wlo + (int64_t)Cout * T);
+        segs[cur_seg].tb.cover(blo, blo + Cout);
     }
-    const int b_embs_ = b_embs, T_ = T;
     const int64_t pn2w = add_param(pre + "norm2.weight", {Cout}), pn2b = add_param(pre + "norm2.bias", {Cout});
     const int64_t pc2w = add_param(pre + "conv2.weight", {Cout, Cout, 3, 3}, 1), pc2b = add_param(pre + "conv2.bias", {Cout});
     const Conv3 k1 = conv3_same(pc1w, pc1b, Cin, Cout, H, W), k2 = conv3_same(pc2w, pc2b, Cout, Cout, H, W);
-    int64_t psw = -1, psb = -1;
+    Lin sc = {-1, -1, Cout, Cin};
     if (shortcut) {
-        psw = add_param(pre + "conv_shortcut.weight", {Cout, Cin, 1, 1}, 1);
-        psb = add_param(pre + "conv_shortcut.bias", {Cout});
+        sc.pw = add_param(pre + "conv_shortcut.weight", {Cout, Cin, 1, 1}, 1);
+        sc.pb = add_param(pre + "conv_shortcut.bias", {Cout});
     }
     if (Cin % 32 == 0 && Cout % 32 == 0) {
         wt_off.push_back(pc1w); wt_cin.push_back(Cin); wt_cout.push_back(Cout);
@@ -625,30 +778,36 @@ void bd_unet::node_resnet(const std::string& pre, const View& x, const View& y, 
     const int b_dyS = scratch((int64_t)HW * Cout), b_dh1S = scratch((int64_t)HW * Cout);
     const float inv = 1.f / scale;
     const int sumC_ = sumC;
+    // the family of conv1 / conv2, and of the shortcut's data gradient: dL/dy exists as split planes whenever conv2 took the plane kernels, and
+    // the 1x1 then runs DMA-fed on them instead of splitting both fp32 operands in the igemm loaders
+    const Path ps1 = [=](int B) { return ps_shape(B, H, W, Cin, Cout); }, ps2 = [=](int B) { return ps_shape(B, H, W, Cout, Cout); };
+    const Path sc_sp = [=](int B) {
+        return Knobs::get().shortcut_sp && ps2(B) && gemm_sp_supported((int)((int64_t)B * HW), Cin, Cout) && x.ld % 4 == 0;
+    };
     // dL/dx becomes final in this node's norm1 backward (first consumer of x in forward order); dL/dy arrives ready-split when y's first
     // consumer can do the same for us (GSplit)
     const int gs_in = claim_gsplit(x, true);
-    const int gs_out = b_dys < 0 ? reg_gsplit(y, [this, H, W, Cout](int B) { return ps_shape(B, H, W, Cout, Cout); }) : -1;
+    const int gs_out = b_dys < 0 ? reg_gsplit(y, ps2) : -1;
 
     F([=](Ctx& c) {
-        const bool ps1 = ps_ok(c, H, W, Cin, Cout), ps2 = ps_ok(c, H, W, Cout, Cout);
+        const bool p1 = takes(c, ps1), p2 = takes(c, ps2);
         // a1 / a2 in the format their convolution reads (planes: conv1 / conv2 forward and, they are value buffers, the weight gradients)
-        float* a1 = BP(c, ps1 ? b_a1s : b_a1);
-        float* a2 = BP(c, ps2 ? b_a2s : b_a2);
-        BD_TRY(gn_fwd(c, x, pn1w, pn1b, a1, Cin, b_st1, 1, ps1));
+        float* a1 = BP(c, p1 ? b_a1s : b_a1);
+        float* a2 = BP(c, p2 ? b_a2s : b_a2);
+        BD_TRY(gn_fwd(c, x, pn1w, pn1b, a1, Cin, b_st1, 1, p1));
         Conv3Epi e1;
         e1.rowbias = BP(c, b_tproj) + toff; e1.ld_rowbias = sumC_;
         // round 4: norm2's statistics from conv1's epilogue when norm2 would otherwise make a pass over h1 for them (large images)
-        if (ps1 && ps2 && bd_gn_fwd_takes_stats(c.B, HW, Cout, G)) e1.gn_splits = bd_conv3x3_ps_gn_splits(c.B, H, W, Cin, Cout, G);
-        BD_TRY(conv3_fwd(c, k1, ps1, {a1, Cin}, BP(c, b_h1), Cout, e1));
-        BD_TRY(gn_fwd(c, h1v, pn2w, pn2b, a2, Cout, b_st2, 1, ps2, e1.gn_splits));
+        if (p1 && p2) e1.gn_splits = conv3_gn_splits(c, k1);
+        BD_TRY(conv3_fwd(c, k1, p1, {a1, Cin}, BP(c, b_h1), Cout, e1));
+        BD_TRY(gn_fwd(c, h1v, pn2w, pn2b, a2, Cout, b_st2, 1, p2, e1.gn_splits));
         Conv3Epi e2;
         e2.residual = VP(c, x); e2.ldr = x.ld; e2.out_scale = inv;
         if (shortcut) {
-            BD_TRY(linear_fwd(c, VP(c, x), x.ld, c.params + psw, c.params + psb, VP(c, y), y.ld, (int)rows(c, x), Cout, Cin));
+            BD_TRY(lin_fwd(c, sc, false, {VP(c, x), x.ld}, VP(c, y), y.ld, (int)rows(c, x)));
             e2.residual = VP(c, y); e2.ldr = y.ld;
         }
-        return conv3_fwd(c, k2, ps2, {a2, Cout}, VP(c, y), y.ld, e2);
+        return conv3_fwd(c, k2, p2, {a2, Cout}, VP(c, y), y.ld, e2);
     });
     Bk([=](Ctx& c) {
         const int M = (int)rows(c, x);
@@ -657,43 +816,28 @@ void bd_unet::node_resnet(const std::string& pre, const View& x, const View& y, 
             BD_TRY(add(c, dy.p, dy.ld, BP(c, b_dys), Cout, M, Cout, inv, 0));
             dy = {BP(c, b_dys), Cout};
         }
-        const bool ps1 = ps_ok(c, H, W, Cin, Cout), ps2 = ps_ok(c, H, W, Cout, Cout);
+        const bool p1 = takes(c, ps1), p2 = takes(c, ps2);
         Opnd dy2 = dy;      // dL/dy as conv2's family reads it
-        if (ps2) BD_TRY(grad_planes(c, gs_out, dy.p, dy.ld, M, Cout, b_dyS, dy2));
-        BD_TRY(conv3_wgrad(c, k2, ps2, {BP(c, ps2 ? b_a2s : b_a2), Cout}, dy2));
-        BD_TRY(conv3_dgrad(c, k2, ps2, dy2, BP(c, b_da2), Cout, 0));
-        float* dh1 = BP(c, ps1 ? b_dh1S : b_dh1);
+        if (p2) BD_TRY(grad_planes(c, gs_out, dy.p, dy.ld, M, Cout, b_dyS, dy2));
+        BD_TRY(conv3_wgrad(c, k2, p2, {BP(c, p2 ? b_a2s : b_a2), Cout}, dy2));
+        BD_TRY(conv3_dgrad(c, k2, p2, dy2, BP(c, b_da2), Cout, 0));
+        float* dh1 = BP(c, p1 ? b_dh1S : b_dh1);
         {   // norm2 backward: dh1 = gn_silu_bwd(h1, da2), in conv1's family   (h1 has no persistent grad buffer: write to scratch)
             bd_gn_bwd_desc d = {};
             d.lddx = Cout;
-            if (ps1) { d.dx_split = U16(dh1); d.lddxs = Cout; }
+            if (p1) { d.dx_split = U16(dh1); d.lddxs = Cout; }
             else d.dx = dh1;
-            // time-embedding gradient = per-sample column sums of dh1, out of the same launch
+            // time-embedding gradient = per-sample column sums of dh1, out of the same launch (its weight gradient: temb_wgrad, per segment)
             d.dx_colsum = BP(c, b_dtproj) + toff; d.ld_colsum = sumC_;
             BD_TRY(gn_bwd(c, d, h1v, pn2w, pn2b, b_st2, BP(c, b_da2), Cout, 1));
         }
-        // (this resnet's rows of the batched time_emb_proj weight / bias gradient, dW = dtproj[:, rows]^T embs (resnet.py:571),
-        //  are produced by ONE launch per backward segment over all of the segment's resnets: temb_wgrad below)
-        if (c.dry) BD_TRY(linear_wgrad(c, BP(c, b_dtproj), sumC_, BP(c, b_embs_), T_, c.grads, c.B, sumC_, T_, c.grads));   // workspace bound
-        BD_TRY(conv3_wgrad(c, k1, ps1, {BP(c, ps1 ? b_a1s : b_a1), Cin}, {dh1, Cout}));
-        BD_TRY(conv3_dgrad(c, k1, ps1, {dh1, Cout}, BP(c, b_da1), Cin, 0));
+        BD_TRY(conv3_wgrad(c, k1, p1, {BP(c, p1 ? b_a1s : b_a1), Cin}, {dh1, Cout}));
+        BD_TRY(conv3_dgrad(c, k1, p1, {dh1, Cout}, BP(c, b_da1), Cin, 0));
         if (shortcut) {   // 1x1 shortcut convolution: its data gradient goes in FIRST, so that the norm1 backward below is the store that makes
             // dL/dx final (and can hand x's producer the split planes of it)
-            BD_TRY(linear_wgrad(c, dy.p, dy.ld, VP(c, x), x.ld, c.grads + psw, M, Cout, Cin, c.grads + psb));
-            const int acc = take_ginit(c, x.buf);
-            // dL/dy exists as split planes whenever conv2 took the plane kernels: the shortcut's data gradient then runs DMA-fed on them
-            // (bd_gemm_sp, the weight's per-step plane copy taken K-major) instead of splitting both fp32 operands in the igemm loaders
-            static const bool sc_sp = !(getenv("BD_SHORTCUT_SP") && atoi(getenv("BD_SHORTCUT_SP")) == 0);      // (A/B knob)
-            if (sc_sp && ps2 && gemm_sp_supported(M, Cin, Cout) && x.ld % 4 == 0) {
-                bd_gemm_sp_desc g = {};
-                g.M = M; g.N = Cin; g.K = Cout; g.batch = 1;
-                g.a = U16(dy2.p); g.lda = Cout;
-                g.b = c.w_split + 2 * psw; g.ldb = Cin; g.b_kmajor = 1;
-                g.c = GP(c, x); g.ldc = x.ld; g.accumulate = acc; g.alpha = 1.f; g.out_scale = 1.f;
-                BD_TRY(gemm_s(c, g));
-            } else {
-                BD_TRY(linear_dgrad(c, dy.p, dy.ld, c.params + psw, GP(c, x), x.ld, M, Cout, Cin, acc));
-            }
+            BD_TRY(lin_wgrad(c, sc, false, dy, {VP(c, x), x.ld}, M));
+            const bool sp = takes(c, sc_sp);
+            BD_TRY(lin_dgrad(c, sc, sp, sp ? dy2 : dy, GP(c, x), x.ld, M, take_ginit(c, x.buf)));
         }
         // norm1 backward; the identity shortcut's gradient (dy itself) is added in the same store
         return gn_bwd(c, x, pn1w, pn1b, b_st1, BP(c, b_da1), Cin, 1, shortcut ? nullptr : dy.p, dy.ld, gs_in);
@@ -704,15 +848,16 @@ void bd_unet::node_attention(const std::string& pre, const View& x, const View& 
     const int C = x.C, H = x.H, W = x.W, N = H * W;
     const int heads = cfg.attention_head_dim > 0 ? C / cfg.attention_head_dim : 1;
     const int dh = C / heads;
-    const float sm_scale = 1.0f / std::sqrt((float)C / (float)heads);
     const int64_t pgw = add_param(pre + "group_norm.weight", {C}), pgb = add_param(pre + "group_norm.bias", {C});
+    // query / key / value are one [3C, C] projection: their weights, then their biases, are adjacent in the flat buffer
     const int64_t pqw = add_param(pre + "query.weight", {C, C});
     add_param(pre + "key.weight", {C, C});
     add_param(pre + "value.weight", {C, C});
     const int64_t pqb = add_param(pre + "query.bias", {C});
     add_param(pre + "key.bias", {C});
     add_param(pre + "value.bias", {C});
-    const int64_t ppw = add_param(pre + "proj_attn.weight", {C, C}), ppb = add_param(pre + "proj_attn.bias", {C});
+    const Lin qkv = {pqw, pqb, 3 * C, C};
+    const Lin proj = {add_param(pre + "proj_attn.weight", {C, C}), add_param(pre + "proj_attn.bias", {C}), C, C};
     const int G = cfg.norm_num_groups;
     const int b_n = new_buf((int64_t)N * C, 0, R_VALUE), b_qkv = new_buf((int64_t)N * 3 * C, 0, R_VALUE);
     const int b_p = new_buf((int64_t)heads * N * N, 0, R_VALUE), b_o = new_buf((int64_t)N * C, 0, R_VALUE);
@@ -722,153 +867,45 @@ void bd_unet::node_attention(const std::string& pre, const View& x, const View& 
     const int b_dqkv = scratch((int64_t)N * 3 * C), b_dn = scratch((int64_t)N * C);
     const int b_dyS = scratch((int64_t)N * C);
     const float inv = 1.f / scale;
-
-    auto batched = [=](bd_igemm_desc& g, int B) {
-        g.batch_outer = B; g.batch_inner = heads;
-    };
+    const Attn at = {heads, N, dh, C, 1.0f / std::sqrt((float)C / (float)heads), b_qkv, b_p, b_o, b_do, b_dp, b_dqkv};
     // Round 3: the whole block on SPLIT PLANES (gemm_sp.hip + attn_sp.hip): GroupNorm writes planes, the QKV projection reads and writes
-    // planes, the attention core (scores, softmax, value product: one launch forward, two backward) keeps the [N, N] matrices on chip and
-    // hands planes to the output projection; the backward mirrors it.  The same buffers hold planes instead of fp32 (same bytes); the
-    // weights' planes are the per-step bd_split_bf16 copy (K-contiguous rows: the layout a [N][K] weight wants forward, and the K-major
-    // operand of its data gradient as it stands).  N = 256 tokens, head dim 256 (attn_sp_supported); the mid block (4 x 4) stays below.
-    auto sp_shape = [=](int B) {
+    // planes, the attention core keeps the [N, N] matrices on chip and hands planes to the output projection; the backward mirrors it.  The
+    // same buffers hold planes instead of fp32 (same bytes).  N = 256 tokens, head dim 256 (attn_sp_supported); the mid block (4 x 4) and
+    // head dim 512 stay on the fp32 family.
+    const Path sp_at = [=](int B) {
         return mode_bf16(cfg.compute_mode) && attn_sp_supported(N, dh) && gemm_sp_supported((int)((int64_t)B * N), C, C) &&
                gemm_sp_supported(3 * C, C, 32);
     };
-    auto use_sp = [=](const Ctx& c) { return planes(c) && sp_shape(lay_batch(c)); };
     const int gs_in = claim_gsplit(x, true);
-    const int gs_out = b_dys < 0 ? reg_gsplit(y, sp_shape) : -1;
+    const int gs_out = b_dys < 0 ? reg_gsplit(y, sp_at) : -1;
     F([=](Ctx& c) {
         const int M = (int)rows(c, x);
-        const bool sp = use_sp(c);
+        const bool sp = takes(c, sp_at);
         BD_TRY(gn_fwd(c, x, pgw, pgb, BP(c, b_n), C, b_st, 0, sp));
-        if (sp) {
-            bd_gemm_sp_desc q = {};      // qkv = n Wqkv^T + b  -> planes
-            q.M = M; q.N = 3 * C; q.K = C; q.batch = 1;
-            q.a = U16(BP(c, b_n)); q.lda = C; q.b = c.w_split + 2 * pqw; q.ldb = C;
-            q.c_split = U16(BP(c, b_qkv)); q.ldcs = 3 * C; q.bias = c.params + pqb; q.alpha = 1.f; q.out_scale = 1.f;
-            BD_TRY(gemm_s(c, q));
-            if (!c.dry) {
-                bd_attn_sp_desc a = {};
-                a.B = c.B; a.heads = heads; a.N = N; a.dh = dh; a.qkv_split = U16(BP(c, b_qkv)); a.ld = 3 * C; a.scale = sm_scale;
-                a.o_split = U16(BP(c, b_o)); a.ldo = C; a.pt_split = c.training ? U16(BP(c, b_p)) : nullptr; a.mode = cfg.compute_mode;
-                BD_TRY(attn_sp_fwd(a, c.st));
-            }
-            bd_gemm_sp_desc o = {};      // y = (o Wp^T + b + x) / scale
-            o.M = M; o.N = C; o.K = C; o.batch = 1;
-            o.a = U16(BP(c, b_o)); o.lda = C; o.b = c.w_split + 2 * ppw; o.ldb = C;
-            o.c = VP(c, y); o.ldc = y.ld; o.bias = c.params + ppb; o.residual = VP(c, x); o.ldr = x.ld; o.alpha = 1.f; o.out_scale = inv;
-            return gemm_s(c, o);
-        }
-        BD_TRY(linear_fwd(c, BP(c, b_n), C, c.params + pqw, c.params + pqb, BP(c, b_qkv), 3 * C, M, 3 * C, C));
-        float* qkv = BP(c, b_qkv);
-        {
-            {   // S = scale * Q K^T
-                bd_igemm_desc g = {};
-                g.A = dense(qkv, 3 * C, 1); g.A.bs_outer = (int64_t)N * 3 * C; g.A.bs_inner = dh;
-                g.B = dense(qkv + C, 3 * C, 1); g.B.bs_outer = (int64_t)N * 3 * C; g.B.bs_inner = dh;
-                g.M = N; g.N = N; g.K = dh; batched(g, c.B);
-                g.C = BP(c, b_p); g.ldc = N; g.c_bs_outer = (int64_t)heads * N * N; g.c_bs_inner = (int64_t)N * N;
-                g.alpha = sm_scale; g.out_scale = 1.f;
-                BD_TRY(igemm(c, g));
-            }
-            if (!c.dry) BD_TRY(bd_softmax_fwd(BP(c, b_p), BP(c, b_p), (int64_t)c.B * heads * N, N, (bd_stream_t)c.st));
-            {   // O = P V
-                bd_igemm_desc g = {};
-                g.A = dense(BP(c, b_p), N, 1); g.A.bs_outer = (int64_t)heads * N * N; g.A.bs_inner = (int64_t)N * N;
-                g.B = dense(qkv + 2 * C, 3 * C, 0); g.B.bs_outer = (int64_t)N * 3 * C; g.B.bs_inner = dh;
-                g.M = N; g.N = dh; g.K = N; batched(g, c.B);
-                g.C = BP(c, b_o); g.ldc = C; g.c_bs_outer = (int64_t)N * C; g.c_bs_inner = dh;
-                g.alpha = 1.f; g.out_scale = 1.f;
-                BD_TRY(igemm(c, g));
-            }
-        }
-        return linear_fwd(c, BP(c, b_o), C, c.params + ppw, c.params + ppb, VP(c, y), y.ld, M, C, C, VP(c, x), x.ld, inv);
+        BD_TRY(lin_fwd(c, qkv, sp, {BP(c, b_n), C}, BP(c, b_qkv), 3 * C, M, sp));
+        BD_TRY(attn_fwd(c, at, sp));
+        LinEpi e;      // y = (o Wp^T + b + x) / scale
+        e.residual = VP(c, x); e.ldr = x.ld; e.out_scale = inv;
+        return lin_fwd(c, proj, sp, {BP(c, b_o), C}, VP(c, y), y.ld, M, false, e);
     });
     Bk([=](Ctx& c) {
         const int M = (int)rows(c, x);
-        const float* dy = GP(c, y); int64_t lddy = y.ld;
+        const bool sp = takes(c, sp_at);
+        Opnd dy = {GP(c, y), y.ld};
         if (b_dys >= 0) {
-            BD_TRY(add(c, dy, lddy, BP(c, b_dys), C, M, C, inv, 0));
-            dy = BP(c, b_dys); lddy = C;
+            BD_TRY(add(c, dy.p, dy.ld, BP(c, b_dys), C, M, C, inv, 0));
+            dy = {BP(c, b_dys), C};
         }
-        if (use_sp(c)) {
-            Opnd dyS;
-            BD_TRY(grad_planes(c, gs_out, dy, lddy, M, C, b_dyS, dyS));
-            bd_gemm_sp_desc w = {};      // dWp = dy^T o, dbp = column sums of dy  (side stream)
-            w.M = C; w.N = C; w.K = M; w.batch = 1;
-            w.a = U16(dyS.p); w.lda = C; w.a_kmajor = 1; w.b = U16(BP(c, b_o)); w.ldb = C; w.b_kmajor = 1;
-            w.c = c.grads + ppw; w.ldc = C; w.a_colsum = c.grads + ppb; w.alpha = 1.f; w.out_scale = 1.f;
-            BD_TRY(gemm_s(c, w, true));
-            bd_gemm_sp_desc g = {};      // dO = dy Wp -> planes
-            g.M = M; g.N = C; g.K = C; g.batch = 1;
-            g.a = U16(dyS.p); g.lda = C; g.b = c.w_split + 2 * ppw; g.ldb = C; g.b_kmajor = 1;
-            g.c_split = U16(BP(c, b_do)); g.ldcs = C; g.alpha = 1.f; g.out_scale = 1.f;
-            BD_TRY(gemm_s(c, g));
-            if (!c.dry) {
-                bd_attn_sp_desc a = {};
-                a.B = c.B; a.heads = heads; a.N = N; a.dh = dh; a.qkv_split = U16(BP(c, b_qkv)); a.ld = 3 * C; a.scale = sm_scale;
-                a.pt_split = U16(BP(c, b_p)); a.do_split = U16(BP(c, b_do)); a.lddo = C; a.dst_split = U16(BP(c, b_dp));
-                a.dqkv_split = U16(BP(c, b_dqkv)); a.lddqkv = 3 * C; a.mode = cfg.compute_mode;
-                BD_TRY(attn_sp_bwd(a, c.st));
-            }
-            bd_gemm_sp_desc wq = {};     // dWqkv = dqkv^T n, dbqkv = column sums of dqkv  (side stream)
-            wq.M = 3 * C; wq.N = C; wq.K = M; wq.batch = 1;
-            wq.a = U16(BP(c, b_dqkv)); wq.lda = 3 * C; wq.a_kmajor = 1; wq.b = U16(BP(c, b_n)); wq.ldb = C; wq.b_kmajor = 1;
-            wq.c = c.grads + pqw; wq.ldc = C; wq.a_colsum = c.grads + pqb; wq.alpha = 1.f; wq.out_scale = 1.f;
-            BD_TRY(gemm_s(c, wq, true));
-            bd_gemm_sp_desc dn = {};     // dn = dqkv Wqkv
-            dn.M = M; dn.N = C; dn.K = 3 * C; dn.batch = 1;
-            dn.a = U16(BP(c, b_dqkv)); dn.lda = 3 * C; dn.b = c.w_split + 2 * pqw; dn.ldb = C; dn.b_kmajor = 1;
-            dn.c = BP(c, b_dn); dn.ldc = C; dn.alpha = 1.f; dn.out_scale = 1.f;
-            BD_TRY(gemm_s(c, dn));
-            return gn_bwd(c, x, pgw, pgb, b_st, BP(c, b_dn), C, 0, dy, lddy, gs_in);
-        }
-        float* qkv = BP(c, b_qkv); float* dqkv = BP(c, b_dqkv); float* P = BP(c, b_p); float* dP = BP(c, b_dp);
-        float* dO = BP(c, b_do);
-        BD_TRY(linear_wgrad(c, dy, lddy, BP(c, b_o), C, c.grads + ppw, M, C, C, c.grads + ppb));
-        BD_TRY(linear_dgrad(c, dy, lddy, c.params + ppw, dO, C, M, C, C, 0));
-        {   // dP = dO V^T
-            bd_igemm_desc g = {};
-            g.A = dense(dO, C, 1); g.A.bs_outer = (int64_t)N * C; g.A.bs_inner = dh;
-            g.B = dense(qkv + 2 * C, 3 * C, 1); g.B.bs_outer = (int64_t)N * 3 * C; g.B.bs_inner = dh;
-            g.M = N; g.N = N; g.K = dh; batched(g, c.B);
-            g.C = dP; g.ldc = N; g.c_bs_outer = (int64_t)heads * N * N; g.c_bs_inner = (int64_t)N * N;
-            g.alpha = 1.f; g.out_scale = 1.f;
-            BD_TRY(igemm(c, g));
-        }
-        {   // dV = P^T dO
-            bd_igemm_desc g = {};
-            g.A = dense(P, N, 0); g.A.bs_outer = (int64_t)heads * N * N; g.A.bs_inner = (int64_t)N * N;
-            g.B = dense(dO, C, 0); g.B.bs_outer = (int64_t)N * C; g.B.bs_inner = dh;
-            g.M = N; g.N = dh; g.K = N; batched(g, c.B);
-            g.C = dqkv + 2 * C; g.ldc = 3 * C; g.c_bs_outer = (int64_t)N * 3 * C; g.c_bs_inner = dh;
-            g.alpha = 1.f; g.out_scale = 1.f;
-            BD_TRY(igemm(c, g));
-        }
-        if (!c.dry) BD_TRY(bd_softmax_bwd(P, dP, dP, (int64_t)c.B * heads * N, N, (bd_stream_t)c.st));
-        {   // dQ = scale * dS K
-            bd_igemm_desc g = {};
-            g.A = dense(dP, N, 1); g.A.bs_outer = (int64_t)heads * N * N; g.A.bs_inner = (int64_t)N * N;
-            g.B = dense(qkv + C, 3 * C, 0); g.B.bs_outer = (int64_t)N * 3 * C; g.B.bs_inner = dh;
-            g.M = N; g.N = dh; g.K = N; batched(g, c.B);
-            g.C = dqkv; g.ldc = 3 * C; g.c_bs_outer = (int64_t)N * 3 * C; g.c_bs_inner = dh;
-            g.alpha = sm_scale; g.out_scale = 1.f;
-            BD_TRY(igemm(c, g));
-        }
-        {   // dK = scale * dS^T Q
-            bd_igemm_desc g = {};
-            g.A = dense(dP, N, 0); g.A.bs_outer = (int64_t)heads * N * N; g.A.bs_inner = (int64_t)N * N;
-            g.B = dense(qkv, 3 * C, 0); g.B.bs_outer = (int64_t)N * 3 * C; g.B.bs_inner = dh;
-            g.M = N; g.N = dh; g.K = N; batched(g, c.B);
-            g.C = dqkv + C; g.ldc = 3 * C; g.c_bs_outer = (int64_t)N * 3 * C; g.c_bs_inner = dh;
-            g.alpha = sm_scale; g.out_scale = 1.f;
-            BD_TRY(igemm(c, g));
-        }
-        BD_TRY(linear_wgrad(c, dqkv, 3 * C, BP(c, b_n), C, c.grads + pqw, M, 3 * C, C, c.grads + pqb));
-        BD_TRY(linear_dgrad(c, dqkv, 3 * C, c.params + pqw, BP(c, b_dn), C, M, 3 * C, C, 0));
-        // group-norm backward; the residual connection's gradient (dy itself) is added in the same store
-        return gn_bwd(c, x, pgw, pgb, b_st, BP(c, b_dn), C, 0, dy, lddy, gs_in);
+        Opnd dyf = dy;      // dL/dy as the family reads it
+        if (sp) BD_TRY(grad_planes(c, gs_out, dy.p, dy.ld, M, C, b_dyS, dyf));
+        BD_TRY(lin_wgrad(c, proj, sp, dyf, {BP(c, b_o), C}, M));
+        BD_TRY(lin_dgrad(c, proj, sp, dyf, BP(c, b_do), C, M, 0, sp));
+        BD_TRY(attn_bwd(c, at, sp));
+        const Opnd dqkv = {BP(c, b_dqkv), 3 * C};
+        BD_TRY(lin_wgrad(c, qkv, sp, dqkv, {BP(c, b_n), C}, M));
+        BD_TRY(lin_dgrad(c, qkv, sp, dqkv, BP(c, b_dn), C, M, 0));
+        // group-norm backward; the residual connection's gradient (dy itself, fp32) is added in the same store
+        return gn_bwd(c, x, pgw, pgb, b_st, BP(c, b_dn), C, 0, dy.p, dy.ld, gs_in);
     });
 }
 
@@ -882,22 +919,17 @@ void bd_unet::node_downsample(const std::string& pre, const View& x, const View&
     const int b_dyS = scratch((int64_t)Ho * Wo * C);
     claim_gsplit(x, false);        // (this node's data gradient is a convolution: it cannot leave dL/dx as planes)
     // by the parity of the input pixel only 4 / 2 / 2 / 1 of the nine taps contribute to the data gradient: four classes on the output grid
-    const bool even = H == 2 * Ho && W == 2 * Wo;
-    const int gs_out = reg_gsplit(y, [=](int B) { return even && phase_shape(B, Ho, Wo, C, C); });
+    const Path phase = [=](int B) { return H == 2 * Ho && W == 2 * Wo && phase_shape(B, Ho, Wo, C, C); };
+    const int gs_out = reg_gsplit(y, phase);
     F([=](Ctx& c) { return conv3_fwd(c, k, false, {VP(c, x), x.ld}, VP(c, y), y.ld); });
     Bk([=](Ctx& c) {
         const Opnd dy = {GP(c, y), y.ld};
         BD_TRY(conv3_wgrad(c, k, false, {VP(c, x), x.ld}, dy));
         const int acc = take_ginit(c, x.buf);
-        if (!(even && phase_ok(c, Ho, Wo, C, C))) return conv3_dgrad(c, k, false, dy, GP(c, x), x.ld, acc);
+        if (!takes(c, phase)) return conv3_dgrad(c, k, false, dy, GP(c, x), x.ld, acc);
         Opnd dyS;
         BD_TRY(grad_planes(c, gs_out, dy.p, dy.ld, (int64_t)c.B * Ho * Wo, C, b_dyS, dyS));
-        if (c.dry) return (int)BD_OK;
-        bd_conv3x3_s2_dgrad_desc g = {};
-        g.B = c.B; g.Ho = Ho; g.Wo = Wo; g.Cin = C; g.Cout = C; g.pad = pad;
-        g.dy_split = U16(dyS.p); g.lddy = C; g.wT_split = c.wT_split + 2 * pw;
-        g.dx = GP(c, x); g.lddx = x.ld; g.accumulate = acc; g.mode = cfg.compute_mode;
-        return conv3x3_s2_dgrad_ps(g, c.st);
+        return phase_s2_dgrad(c, k, dyS, GP(c, x), x.ld, acc);
     });
 }
 
@@ -915,65 +947,40 @@ void bd_unet::node_upsample(const std::string& pre, const View& x, const View& y
     // phase-decomposed path (round 3): x as split planes on the SOURCE grid + the pre-summed tap planes E / E^T of this layer
     const int b_xS = new_buf((int64_t)H * W * C, 0, R_VALUE);
     const int b_e = new_buf(0, (int64_t)16 * C * C, R_VALUE), b_et = new_buf(0, (int64_t)16 * C * C, R_VALUE);
-    if (C % 128 == 0) upsw.push_back({pw, C, H, W, b_e, b_et});
+    // the plan's path choice: phase form; else the plane kernels on the materialised fine grid; else the literal form.  The phase form's data
+    // gradient is one class on the source grid where that pays (phase_dgrad_shape), else the fine-grid data gradient + 2x2 sums on planes
+    const Path phase = [=](int B) { return phase_shape(B, H, W, C, C); };
+    const Path fine_ps = [=](int B) { return !phase(B) && ps_shape(B, 2 * H, 2 * W, C, C); };
+    const Path phase_d = [=](int B) { return phase(B) && phase_dgrad_shape(B, H, W, C); };
+    if (C % 128 == 0) upsw.push_back({pw, C, phase, b_e, b_et});
     claim_gsplit(x, false);
-    auto phase_at = [=](int B) { return phase_shape(B, H, W, C, C); };
-    auto ps_at = [=](int B) { return ps_shape(B, 2 * H, 2 * W, C, C); };
-    const int gs_out = reg_gsplit(y, [=](int B) { return phase_at(B) || ps_at(B); });
-    // which of the two operand sets exists is the plan's path choice for the batch the workspace is laid out for
-    bufs[b_xuS].live = [=](int B, int) { return !phase_at(B) && ps_at(B); };
-    bufs[b_xS].live = [=](int B, int) { return phase_at(B); };
-    bufs[b_e].live = [=](int B, int) { return phase_at(B); };
-    bufs[b_et].live = [=](int B, int training) { return training && phase_at(B); };
+    const int gs_out = reg_gsplit(y, [=](int B) { return phase(B) || fine_ps(B); });
+    // which of the two operand sets exists
+    bufs[b_xuS].live = [=](int B, int) { return fine_ps(B); };
+    bufs[b_xS].live = [=](int B, int) { return phase(B); };
+    bufs[b_e].live = [=](int B, int) { return phase(B); };
+    bufs[b_et].live = [=](int B, int training) { return training && phase(B); };
     F([=](Ctx& c) {
-        if (phase_ok(c, H, W, C, C)) {
+        if (takes(c, phase)) {
             BD_TRY(split_rows(c, VP(c, x), x.ld, (int64_t)c.B * H * W, C, BP(c, b_xS)));
-            if (c.dry) return (int)BD_OK;
-            bd_upsample_conv_desc d = {};
-            d.mode = cfg.compute_mode;
-            d.B = c.B; d.H = H; d.W = W; d.Cin = C; d.Cout = C;
-            d.x_split = U16(BP(c, b_xS)); d.ldx = C; d.e_split = U16(BP(c, b_e)); d.bias = c.params + pb;
-            d.y = VP(c, y); d.ldy = y.ld;
-            return upsample_conv_fwd(d, c.st);
+            return phase_ups_fwd(c, k, {BP(c, b_xS), C}, BP(c, b_e), VP(c, y), y.ld);
         }
-        const bool ps = ps_ok(c, 2 * H, 2 * W, C, C);
-        if (ps && !c.dry) BD_TRY(bd_split_rows_ups2(VP(c, x), x.ld, c.B, H, W, C, U16(BP(c, b_xuS)), C, (bd_stream_t)c.st));
+        const bool ps = takes(c, fine_ps);
+        if (ps) BD_TRY(split_rows_ups2(c, VP(c, x), x.ld, H, W, C, BP(c, b_xuS)));
         return conv3_fwd(c, k, ps, ps ? Opnd{BP(c, b_xuS), C} : Opnd{VP(c, x), x.ld}, VP(c, y), y.ld);
     });
     Bk([=](Ctx& c) {
         Opnd dy = {GP(c, y), y.ld};
         const int acc = take_ginit(c, x.buf);
-        const bool ph = phase_ok(c, H, W, C, C);
-        const bool ps = ph || ps_ok(c, 2 * H, 2 * W, C, C);      // family of the fine-grid data gradient
+        const bool ph = takes(c, phase);
+        const bool ps = ph || takes(c, fine_ps);      // family of the fine-grid data gradient
         if (ps) BD_TRY(grad_planes(c, gs_out, dy.p, dy.ld, (int64_t)c.B * 4 * H * W, C, b_dyS, dy));
-        if (ph) {
-            bd_upsample_conv_desc d = {};
-            d.mode = cfg.compute_mode;
-            d.B = c.B; d.H = H; d.W = W; d.Cin = C; d.Cout = C;
-            d.x_split = U16(BP(c, b_xS)); d.ldx = C; d.dy_split = U16(dy.p); d.lddy = C;
-            d.et_split = U16(BP(c, b_et)); d.dx = GP(c, x); d.lddx = x.ld; d.accumulate = acc;
-            d.dw = c.grads + pw; d.db = c.grads + pb;
-            // ONE class of 16 taps: >= 128 tiles of its own, or (taps dealt to four workgroups per tile) >= 32
-            const bool ph_d = phase_ok(c, H, W, C, C, upsample_conv_dgrad_workspace_bytes(d) ? 4 : 1);
-            if (c.dry) {
-                need(c, upsample_conv_wgrad_workspace_bytes(d));
-                need(c, upsample_conv_dgrad_workspace_bytes(d));
-            } else {
-                d.workspace_bytes = c.opws_bytes;
-                if (c.wg) BD_TRY(on_aux(c, [&](hipStream_t st, char* ws) { d.workspace = ws; return upsample_conv_wgrad(d, st); }));
-            }
-            if (ph_d) {      // 16 taps on dY sampled at stride 2: replaces the fine-grid dgrad + 2x2 sum
-                if (c.dry) return (int)BD_OK;
-                d.workspace = c.opws;
-                return upsample_conv_dgrad(d, c.st);
-            }
-        } else {
-            BD_TRY(conv3_wgrad(c, k, ps, ps ? Opnd{BP(c, b_xuS), C} : Opnd{VP(c, x), x.ld}, dy));
-        }
-        // literal data gradient on the fine grid + 2x2 sums
+        if (ph) BD_TRY(phase_ups_wgrad(c, k, {BP(c, b_xS), C}, dy));
+        else BD_TRY(conv3_wgrad(c, k, ps, ps ? Opnd{BP(c, b_xuS), C} : Opnd{VP(c, x), x.ld}, dy));
+        if (takes(c, phase_d)) return phase_ups_dgrad(c, k, dy, BP(c, b_et), GP(c, x), x.ld, acc);
+        // data gradient on the fine grid + 2x2 sums
         BD_TRY(conv3_dgrad(c, k, ps, dy, BP(c, b_du), C, 0));
-        if (c.dry) return (int)BD_OK;
-        return bd_sum2x2(BP(c, b_du), C, GP(c, x), x.ld, c.B, H, W, C, acc, (bd_stream_t)c.st);
+        return sum2x2(c, BP(c, b_du), C, GP(c, x), x.ld, H, W, C, acc);
     });
 }
 
@@ -1038,7 +1045,7 @@ void bd_unet::build() {
 
     // segments in BACKWARD order: 0 = out, 1..n = up blocks n-1..0, n+1 = mid, n+2..2n+1 = down n-1..0, 2n+2 = conv_in, 2n+3 = time
     const int nseg = 2 * n + 4;
-    segs.assign(nseg, Seg{-1, -1});
+    segs.assign(nseg, Seg());
     const int seg_out = 0;
     auto seg_up = [&](int i) { return 1 + (n - 1 - i); };
     const int seg_mid = n + 1;
@@ -1065,7 +1072,7 @@ void bd_unet::build() {
 
     // ---- pass 2: nodes in forward order ---------------------------------------------------------------
     cur_group = 0;
-    cur_seg = seg_time; segs[seg_time].lo = 0;
+    cur_seg = seg_time; segs[seg_time].own.lo = 0;
     node_time_embed();
     int toff = 0, group = 1;
     cur_seg = seg_in; cur_group = group++;
@@ -1171,11 +1178,14 @@ void bd_unet::layout(int B, int training) {
     c.dry = true; c.B = B; c.ws = nullptr; c.ginit.assign(bufs.size(), 0);
     c.opws_bytes = (size_t)1 << 62;
     for (auto& f : fwd) f(c);
-    if (training) for (auto it = bwd.rbegin(); it != bwd.rend(); ++it) it->fn(c);
+    if (training) {
+        for (auto it = bwd.rbegin(); it != bwd.rend(); ++it) it->fn(c);
+        temb_wgrad(c, 0, sumC);      // (unet_backward_run launches it outside any step: at most all rows at once)
+    }
     opws_bytes = align_up(c.opws_need, 256);
     gnpart_floats = training ? c.gnpart_need : 0;
     lay_B = B; lay_train = training; lay_gen = bd::g_tune_gen;
-    prep_params = nullptr; prep_ws = nullptr; prep_B = -1;   // a new layout moves the prepared planes inside the workspace
+    forget_prepared();   // a new layout moves the prepared planes inside the workspace
 }
 
 // ----------------------------------------------------------------------------------------------------
@@ -1236,21 +1246,21 @@ extern "C" int bd_unet_stream_wait_aux(bd_unet* u, bd_stream_t stream) {
 extern "C" int bd_unet_set_static_weights(bd_unet* u, int enabled) {
     BD_CHECK(u, BD_ERR_INVALID, "bd_unet_set_static_weights: null plan");
     u->static_weights = enabled ? 1 : 0;
-    u->prep_params = nullptr; u->prep_ws = nullptr; u->prep_B = -1;     // turning it on or off always re-reads the weights once
+    u->forget_prepared();     // turning it on or off always re-reads the weights once
     return BD_OK;
 }
 extern "C" int bd_unet_set_compute_mode(bd_unet* u, int mode) {
     BD_CHECK(u && mode_valid(mode), BD_ERR_INVALID, "bd_unet_set_compute_mode: bad arguments (mode %d)", mode);
     if (u->cfg.compute_mode != mode) {
         u->lay_B = -1;   // the op-workspace bound depends on which kernels the mode selects: lay out again
-        u->prep_params = nullptr; u->prep_ws = nullptr; u->prep_B = -1;   // ... and the prepared weight planes belong to the old mode
+        u->forget_prepared();   // ... and the prepared weight planes belong to the old mode
     }
     u->cfg.compute_mode = mode;
     return BD_OK;
 }
 extern "C" int bd_unet_reset_static_cache(bd_unet* u) {
     BD_CHECK(u, BD_ERR_INVALID, "bd_unet_reset_static_cache: null plan");
-    u->prep_params = nullptr; u->prep_ws = nullptr; u->prep_B = -1;
+    u->forget_prepared();
     return BD_OK;
 }
 extern "C" int64_t bd_unet_num_params(const bd_unet* u) { return u ? u->nparams : 0; }
@@ -1346,7 +1356,7 @@ extern "C" int bd_unet_forward(bd_unet* u, int B, int training, const float* par
         // pre-summed tap planes of the upsample convolutions that take the phase path (both forward pipelines read them: before
         // the fork); the transposed set E^T is the data gradient's operand: training only
         for (const auto& uw : u->upsw)
-            if (u->phase_ok(c, uw.H, uw.W, uw.C, uw.C))
+            if (u->takes(c, uw.phase))
                 BD_TRY(upsample_weights(params + uw.pw, uw.C, uw.C, bd_unet::U16(u->BP(c, uw.b_e)),
                                         training ? bd_unet::U16(u->BP(c, uw.b_et)) : nullptr, c.st));
         u->prep_params = u->static_weights && !training ? (const void*)params : nullptr; u->prep_ws = workspace; u->prep_B = B;
@@ -1359,8 +1369,7 @@ extern "C" int bd_unet_forward(bd_unet* u, int B, int training, const float* par
     };
     // two pipelines need enough work per half to pay for twice the host enqueue: >= 32 K input pixels in the batch (B = 32 at 32 x 32 as
     // before; round 4: B = 4 at 256 x 256 qualifies too -- 29.05 -> 28.13 ms per 256 x 256 train step, small layers fill the chip in pairs)
-    static const long long pipes_min_px = getenv("BD_FWD_PIPES_MINPX") ? atoll(getenv("BD_FWD_PIPES_MINPX")) : 32768;      // (A/B knob)
-    if (!u->aux_enabled || B < 2 || (long long)B * u->cfg.sample_size * u->cfg.sample_size < pipes_min_px) {
+    if (!u->aux_enabled || B < 2 || (long long)B * u->cfg.sample_size * u->cfg.sample_size < Knobs::get().fwd_pipes_minpx) {
         BD_TRY(transpose_weights(c.st));
         for (auto& f : u->fwd) BD_TRY(f(c));
         return BD_OK;
@@ -1391,22 +1400,20 @@ extern "C" int bd_unet_forward(bd_unet* u, int B, int training, const float* par
 extern "C" int bd_unet_num_segments(const bd_unet* u) { return u ? (int)u->segs.size() : 0; }
 extern "C" int bd_unet_segment_num_ranges(const bd_unet* u, int seg) {
     if (!u || seg < 0 || seg >= (int)u->segs.size()) return 0;
-    return u->segs[seg].tw_lo >= 0 ? 3 : 1;
+    return u->segs[seg].tw.lo >= 0 ? 3 : 1;
 }
 extern "C" int bd_unet_segment_range_k(const bd_unet* u, int seg, int k, int64_t* lo, int64_t* hi) {
     BD_CHECK(u && seg >= 0 && seg < (int)u->segs.size() && k >= 0 && k < bd_unet_segment_num_ranges(u, seg), BD_ERR_INVALID,
              "bd_unet_segment_range_k: segment / range out of range");
     const bd_unet::Seg& s = u->segs[seg];
-    const int64_t l = k == 0 ? s.lo : (k == 1 ? s.tw_lo : s.tb_lo), h = k == 0 ? s.hi : (k == 1 ? s.tw_hi : s.tb_hi);
-    if (lo) *lo = l;
-    if (hi) *hi = h;
+    const bd_unet::Range& r = k == 0 ? s.own : (k == 1 ? s.tw : s.tb);
+    if (lo) *lo = r.lo;
+    if (hi) *hi = r.hi;
     return BD_OK;
 }
 extern "C" int bd_unet_segment_range(const bd_unet* u, int seg, int64_t* lo, int64_t* hi) {
     BD_CHECK(u && seg >= 0 && seg < (int)u->segs.size(), BD_ERR_INVALID, "bd_unet_segment_range: segment out of range");
-    if (lo) *lo = u->segs[seg].lo;
-    if (hi) *hi = u->segs[seg].hi;
-    return BD_OK;
+    return bd_unet_segment_range_k(u, seg, 0, lo, hi);
 }
 
 // the backward behind bd_unet_backward[_segment] (need_grads, dx == NULL) and bd_unet_backward_input (dx != NULL; grads == NULL selects the
@@ -1462,19 +1469,14 @@ static int unet_backward_run(bd_unet* u, int seg, int B, const float* params, co
         if (run) BD_TRY(bd_unet::aux_mark(c, par));
     }
     if (!c.gn_items.empty()) BD_TRY(bd_gn_bwd_params(c.gn_items.data(), (int)c.gn_items.size(), c.B, (bd_stream_t)c.st));
-    {   // time_emb_proj weight / bias gradient rows of the resnets that just ran: the rows of a segment are adjacent in the batched
-        // [sumC, T] projection, so one GEMM per segment (one for a whole backward) replaces one tiny launch per resnet
-        int64_t lo = -1, hi = -1;
+    {   // time_emb_proj weight / bias gradient rows of the resnets that just ran
+        bd_unet::Range r;
         for (int sg = 0; sg < (int)u->segs.size(); ++sg) {
-            if (seg >= 0 && sg != seg) continue;
-            const bd_unet::Seg& q = u->segs[sg];
-            if (q.tb_lo < 0) continue;
-            if (lo < 0 || q.tb_lo - u->p_tb < lo) lo = q.tb_lo - u->p_tb;
-            if (q.tb_hi - u->p_tb > hi) hi = q.tb_hi - u->p_tb;
+            const bd_unet::Range& tb = u->segs[sg].tb;
+            if ((seg < 0 || sg == seg) && tb.lo >= 0) r.cover(tb.lo - u->p_tb, tb.hi - u->p_tb);
         }
-        if (lo >= 0) {
-            BD_TRY(u->linear_wgrad(c, u->BP(c, u->b_dtproj) + lo, u->sumC, u->BP(c, u->b_embs), u->T, c.grads + u->p_tw + lo * u->T, c.B,
-                                   (int)(hi - lo), u->T, c.grads + u->p_tb + lo));
+        if (r.lo >= 0) {
+            BD_TRY(u->temb_wgrad(c, r.lo, r.hi));
             BD_TRY(bd_unet::aux_mark(c, 0));
         }
     }
@@ -1487,11 +1489,7 @@ static int unet_backward_run(bd_unet* u, int seg, int B, const float* params, co
         u->aux_pend[0] = u->aux_pend[1] = false;
         if (c.st2) BD_HIP_TRY(hipEventRecord(u->aux_ev_seg, c.st2));
     }
-    if (seg >= 0) {
-        if (ready_lo) *ready_lo = u->segs[seg].lo;
-        if (ready_hi) *ready_hi = u->segs[seg].hi;
-    }
-    return BD_OK;
+    return seg >= 0 ? bd_unet_segment_range(u, seg, ready_lo, ready_hi) : (int)BD_OK;
 }
 
 extern "C" int bd_unet_backward_segment(bd_unet* u, int seg, int B, const float* params, const float* x, int64_t ldx,

@@ -18,7 +18,7 @@ The outputs are written into a NaN-filled buffer with a guard band behind the la
 store past M lands in the band.
 
 The branch tables hold for 256 CUs; on another device the GPU tests skip rather than assert a stale table.  Whoever retunes ps_large,
-ps_small_split or ps_wgrad_split moves the cases with it ("Dispatch branches of the split-plane convolutions").
+ps_ws or ps_wgrad_ws moves the cases with it ("Dispatch branches of the split-plane convolutions").
 
 Observed on MI355X (256 CUs): equality holds on the anchor cases the older tests already cover (P10, W6) and on every other case, both modes,
 both operand sets, every epilogue -- the bf16 MFMA's fp32 accumulation is exact when every partial sum is representable, so the tests assert

@@ -182,7 +182,7 @@ def test_attention_block_vs_reference(ops, golden, name, mode):
 @pytest.mark.parametrize("name", list(C.ATTN_SP_CASES))
 def test_attention_block_on_split_planes_vs_reference(ops, golden, name):
     """AttentionBlock (attention.py:121-174) forward + backward at 16 x 16 through the split-plane path exactly as the plan wires it
-    (unet_plan.cpp node_attention, use_sp): GroupNorm -> planes, bd_gemm_sp (QKV projection, planes out), bd_attn_sp_fwd, bd_gemm_sp (output
+    (unet_plan.cpp node_attention, sp_at): GroupNorm -> planes, bd_gemm_sp (QKV projection, planes out), bd_attn_sp_fwd, bd_gemm_sp (output
     projection + bias + residual); backward: planes of dy, bd_gemm_sp weight / data gradients, bd_attn_sp_bwd, GroupNorm backward --
     against what the reference's own module computed (tests/golden/attn_planes.npz, G11): y, dx, every parameter gradient."""
     g = {**golden("attn_planes"), **golden("attn_planes_512_y"), **golden("attn_planes_512_dx")}     # G11, split so that each file stays < 1 MiB
