@@ -35,8 +35,9 @@ DEFAULT_LEARNING_RATE_32, DEFAULT_LEARNING_RATE_256 = 2e-4, 8e-5
 NOT_MODE_TRAIN_OPTS = ["sample_ep"]
 NOT_MODE_TRAIN_MEASURE_OPTS = ["sample_ep"]
 MODE_RESUME_OPTS = ["project", "mode", "gpu", "ckpt"]
-MODE_SAMPLING_OPTS = ["project", "mode", "eval_max_batch", "gpu", "fclip", "ckpt", "sample_ep", "sched"]
-MODE_MEASURE_OPTS = ["project", "mode", "eval_max_batch", "gpu", "fclip", "ckpt", "sample_ep", "sched"]
+MODE_SAMPLING_OPTS = ["project", "mode", "eval_max_batch", "gpu", "fclip", "ckpt", "sample_ep", "sched", "use_ema"]
+MODE_MEASURE_OPTS = ["project", "mode", "eval_max_batch", "gpu", "fclip", "ckpt", "sample_ep", "sched", "use_ema"]
+EMA_DIR, EMA_STATE = "unet_ema", "ema.bin"     # averaged weights in diffusers layout under output_dir; EMA scalars + shadow under ckpt/
 IGNORE_ARGS = ["overwrite", "is_save_all_model_epochs"]
 SCHED_CHOICES = ["DDPM-SCHED", "DDIM-SCHED", "DPM_SOLVER_PP_O1-SCHED", "DPM_SOLVER_O1-SCHED", "DPM_SOLVER_PP_O2-SCHED",
                  "DPM_SOLVER_O2-SCHED", "DPM_SOLVER_PP_O3-SCHED", "DPM_SOLVER_O3-SCHED", "UNIPC-SCHED", "PNDM-SCHED", "DEIS-SCHED",
@@ -68,6 +69,11 @@ def parse_args(argv=None):
     p.add_argument("--is_save_all_model_epochs", "-isame", action="store_true")
     p.add_argument("--sample_ep", "-se", type=int)
     p.add_argument("--result", "-res", type=str)
+    # exponential moving average of the weights, named as in diffusers' train_unconditional.py:176-182 (use_ema_warmup=True as there)
+    p.add_argument("--use_ema", action="store_true", help="keep an EMA of the weights; sample / measure from it")
+    p.add_argument("--ema_inv_gamma", type=float, help="inverse gamma of the EMA warm-up (1.0)")
+    p.add_argument("--ema_power", type=float, help="power of the EMA warm-up (0.75)")
+    p.add_argument("--ema_max_decay", type=float, help="largest EMA decay (0.9999)")
     return p.parse_args(argv)
 
 
@@ -93,6 +99,10 @@ class TrainingConfig:
     is_save_all_model_epochs: bool = False
     sample_ep: int = None
     result: str = "."
+    use_ema: bool = False
+    ema_inv_gamma: float = 1.0
+    ema_power: float = 3 / 4
+    ema_max_decay: float = 0.9999
     eval_sample_n: int = 16
     measure_sample_n: int = 2048
     batch_32: int = 128
@@ -135,6 +145,8 @@ def setup(argv=None, write=True):
                 if v is not None:
                     setattr(config, k, v)
         config.output_dir = args.ckpt
+        if args.mode != MODE_RESUME:      # which weights to sample / measure is this command's choice, not the training run's
+            config.use_ema = bool(args.use_ema)
     allowed = {MODE_RESUME: MODE_RESUME_OPTS, MODE_SAMPLING: MODE_SAMPLING_OPTS, MODE_MEASURE: MODE_MEASURE_OPTS}
     for key, value in vars(args).items():
         if value is None or value is False:
@@ -240,7 +252,18 @@ def get_model_sched(config, device):
         model, noise_sched, get_pipeline = DiffuserModelSched.get_model_sched(image_size=config.image_size, channels=config.channel,
                                                                              model_type=DiffuserModelSched.MODEL_DEFAULT,
                                                                              noise_sched_type=config.sched, clip_sample=config.clip)
+    if getattr(config, "use_ema", False) and config.mode in (MODE_SAMPLING, MODE_MEASURE):
+        load_ema_weights(model, base)      # beside the `unet` directory the raw weights came from
     return model.to(device), noise_sched, get_pipeline
+
+
+def load_ema_weights(model, pipeline_dir):
+    """the averaged weights of <pipeline_dir>/unet_ema into `model`, in place"""
+    from baddiffusion_amd.model import load_unet
+    d = os.path.join(pipeline_dir, EMA_DIR)
+    if not os.path.isdir(d):
+        raise FileNotFoundError(f"--use_ema: {d} is missing (the run was not trained with --use_ema)")
+    model.load_state_dict(load_unet(d).state_dict())
 
 
 def make_grid(images, rows, cols):
@@ -395,17 +418,46 @@ def measure(config, dsl, folder_name, pipeline, rank=0, world=1):
                              extra={"inference_chunk": used[0] if len(used) == 1 else (used or None)})
 
 
+def make_ema(config, model):
+    """the EMAModel of --use_ema (train_unconditional.py:465-473), or None"""
+    if not getattr(config, "use_ema", False):
+        return None
+    from baddiffusion_amd.ema import EMAModel
+    return EMAModel(model, decay=config.ema_max_decay, use_ema_warmup=True, inv_gamma=config.ema_inv_gamma, power=config.ema_power)
+
+
+def save_ema(config, ema, model, dirs):
+    """the averaged weights in diffusers layout (<dir>/unet_ema for every pipeline directory in `dirs`: what --mode sampling|measure
+    --use_ema load) and the EMA's scalars + flat shadow (<ckpt>/ema.bin: what --mode resume continues from).  <dir>/unet stays the RAW
+    weights."""
+    from baddiffusion_amd.model import CONFIG_NAME, WEIGHTS_NAME
+    cfg = {k: (list(v) if isinstance(v, tuple) else v) for k, v in model.config_dict().items()}
+    sd = {k: v.cpu() for k, v in ema.averaged_state_dict(model).items()}
+    for d in (os.path.join(d, EMA_DIR) for d in dirs):
+        os.makedirs(d, exist_ok=True)
+        with open(os.path.join(d, CONFIG_NAME), "w") as f:
+            json.dump(cfg, f, indent=2, sort_keys=True)
+        torch.save(sd, os.path.join(d, WEIGHTS_NAME))
+    st = ema.state_dict()
+    st["shadow_params"] = st["shadow_params"].cpu()
+    torch.save(st, os.path.join(config.ckpt_path, EMA_STATE))
+
+
 def checkpoint(config, engine, pipeline, cur_epoch, cur_step):
-    """baddiffusion.py:558-570: optimizer state + {epoch, step} + the diffusers-layout pipeline."""
+    """baddiffusion.py:558-570: optimizer state + {epoch, step} + the diffusers-layout pipeline; with an EMA on the engine, save_ema()."""
     os.makedirs(config.ckpt_path, exist_ok=True)
     torch.save({"m": engine.m.cpu(), "v": engine.v.cpu(), "opt_step": engine.opt_step, "micro": engine.micro},
                os.path.join(config.ckpt_path, "optimizer.bin"))
     # + the random-number state, so that a resumed run draws the noise / timesteps the uninterrupted run would have drawn
     torch.save({"epoch": cur_epoch, "step": cur_step, "world": _world_size(), "cpu_rng": torch.get_rng_state(),
                 "cuda_rng": torch.cuda.get_rng_state() if torch.cuda.is_available() else None}, config.data_ckpt_path)
-    pipeline.save_pretrained(config.output_dir)
+    dirs = [config.output_dir]
     if config.is_save_all_model_epochs:
-        pipeline.save_pretrained(os.path.join(config.output_dir, config.ep_model_dir, f"ep{cur_epoch}"))
+        dirs.append(os.path.join(config.output_dir, config.ep_model_dir, f"ep{cur_epoch}"))
+    for d in dirs:
+        pipeline.save_pretrained(d)
+    if getattr(engine, "ema", None) is not None:
+        save_ema(config, engine.ema, engine.model, dirs)
 
 
 def _world_size():
@@ -439,6 +491,11 @@ def restore_training_state(config, engine, rank=0):
     if os.path.exists(opt_file):
         st = torch.load(opt_file, map_location="cpu")
         engine.m.copy_(st["m"]); engine.v.copy_(st["v"]); engine.opt_step = st["opt_step"]; engine.micro = st["micro"]
+        ema_file = os.path.join(config.ckpt_path, EMA_STATE)
+        if getattr(engine, "ema", None) is not None:
+            if not os.path.exists(ema_file):
+                raise FileNotFoundError(f"{ema_file} is missing: the run was not checkpointed with --use_ema, its average cannot be resumed")
+            engine.ema.load_state_dict(torch.load(ema_file, map_location="cpu"))
         engine.sync_state()
     epoch = step = 0
     if os.path.exists(config.data_ckpt_path):
@@ -470,7 +527,8 @@ def train_loop(config, model, noise_sched, get_pipeline, dsl, device, world, ran
     num_batch = (len(dsl) + config.batch * world - 1) // (config.batch * world)
     engine = TrainEngine(model, noise_sched, lr=config.learning_rate, lr_warmup_steps=config.lr_warmup_steps,
                          num_training_steps=num_batch * config.epoch // config.gradient_accumulation_steps,
-                         grad_accum_steps=config.gradient_accumulation_steps)
+                         grad_accum_steps=config.gradient_accumulation_steps, ema=make_ema(config, model))
+    ema = engine.ema
     if config.mode == MODE_RESUME:
         restore_training_state(config, engine, rank)
     dsl.to_device(device)
@@ -490,6 +548,8 @@ def train_loop(config, model, noise_sched, get_pipeline, dsl, device, world, ran
                 cur_step += 1
                 if log is not None and step % 50 == 0:
                     rec = {"loss": float(loss), "lr": engine.current_lr(), "epoch": epoch, "step": cur_step}
+                    if ema is not None:
+                        rec["ema_decay"] = ema.cur_decay_value
                     log.write(json.dumps(rec) + "\n"); log.flush()
             ckpt_now = (epoch + 1) % config.save_model_epochs == 0 or epoch == config.epoch - 1
             rng_now = capture_rank_rng(epoch, cur_step) if (rank > 0 and ckpt_now) else None
@@ -497,7 +557,14 @@ def train_loop(config, model, noise_sched, get_pipeline, dsl, device, world, ran
                 print(f"epoch {epoch}: {time.time() - t0:.1f} s, loss {float(loss):.5f}")
                 pipeline = get_pipeline(unet=model, scheduler=noise_sched)
                 if (epoch + 1) % config.save_image_epochs == 0 or epoch == config.epoch - 1:
-                    sampling(config, epoch, pipeline, dsl)
+                    if ema is not None:       # sample from the averaged weights (train_unconditional.py:629-648)
+                        ema.store(model)
+                        ema.copy_to(model)
+                    try:
+                        sampling(config, epoch, pipeline, dsl)
+                    finally:
+                        if ema is not None:
+                            ema.restore(model)
                 if ckpt_now:
                     checkpoint(config, engine, pipeline, epoch, cur_step)
             if ckpt_now and world > 1:
@@ -543,6 +610,8 @@ def main(argv=None):
             start_epoch, start_step = st["epoch"], st["step"]
         pipeline = train_loop(config, model, noise_sched, get_pipeline, dsl, device, world, rank, start_epoch, start_step)
         if config.mode == MODE_TRAIN_MEASURE:
+            if getattr(config, "use_ema", False):      # score what --mode measure --use_ema would load: the averaged weights of the last checkpoint
+                load_ema_weights(model, config.output_dir)
             measure(config, dsl, "measure", pipeline, rank, world)
     elif config.mode == MODE_SAMPLING:
         pipeline = get_pipeline(unet=model, scheduler=noise_sched)

@@ -236,6 +236,9 @@ SIGNATURES = {
     "bd_mfma_probe": (i32, [i32, i32, i32, C.POINTER(f64), vp]),
     "bd_axpy": (i32, [vp, vp, i64, f32, i32, vp]),
     "bd_adam_clip_dev": (i32, [vp, vp, vp, vp, i64, vp, f64, vp, f64, f64, f64, vp, vp]),
+    "bd_adam_clip_ema": (i32, [vp, vp, vp, vp, vp, i64, vp, f64, f64, f64, f64, f64, i32, f32, vp, vp]),
+    "bd_adam_clip_ema_dev": (i32, [vp, vp, vp, vp, vp, i64, vp, f64, vp, f64, f64, f64, vp, vp]),
+    "bd_ema_update": (i32, [vp, vp, i64, f32, vp]),
     "bd_unet_create": (i32, [C.POINTER(UnetConfig), C.POINTER(vp)]),
     "bd_unet_destroy": (None, [vp]),
     "bd_unet_set_compute_mode": (i32, [vp, i32]),

@@ -31,7 +31,8 @@ SOURCES = [  # (file, extra flags)
     ("unet_plan.cpp", ["-x", "hip"]),
     ("prof.cpp", ["-x", "hip"]),
 ]
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "splitplane.h"), os.path.join(os.path.dirname(HERE), "include", "bd_hip.h")]
+HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "splitplane.h"), os.path.join(CSRC, "ema_check.h"),
+           os.path.join(os.path.dirname(HERE), "include", "bd_hip.h")]
 
 
 def _hipcc():

@@ -3,6 +3,7 @@
 // ops (separate mul / add kernels, no FMA contraction) is reproduced exactly where the formula
 // order is copied (q_sample, scheduler steps).
 #include "common.h"
+#include "ema_check.h"
 
 #include <cmath>
 #include <mutex>
@@ -421,12 +422,18 @@ __global__ __launch_bounds__(64) void sumsq_final_kernel(const double* part, int
     if (threadIdx.x == 0) *out = s;
 }
 
-// clip_grad_norm_(max_norm) + torch.optim.Adam (single-tensor formulas), flat buffers
+// clip_grad_norm_(max_norm) + torch.optim.Adam (single-tensor formulas), flat buffers.
+// EMA = true: the shadow update of diffusers' EMAModel.step (training_utils.py:200-202) rides along, from the p[i] just stored:
+// s.sub_(omd * (s - p)) is three separately rounded fp32 operations (sub, mul, sub) -- a contracted fma(-omd, s - p, s) is another
+// number, so the roundings are spelled out.  hyper[2] = omd in the device-scalar form.  EMA = false is the kernel as it always was.
+__device__ __forceinline__ float ema_shadow(float s, float p, float omd) { return __fsub_rn(s, __fmul_rn(omd, __fsub_rn(s, p))); }
+
+template <bool EMA>
 __global__ __launch_bounds__(TPB) void adam_clip_kernel(float* p, const float* g, float* m, float* v, int64_t n,
                                                       const double* sumsq, float max_norm, float step_size, float omb1,
                                                       float b2, float omb2, float eps, float bc2_sqrt, float* gn_out,
-                                                      const float* hyper) {
-    if (hyper) { step_size = hyper[0]; bc2_sqrt = hyper[1]; }
+                                                      const float* hyper, float* ema, float omd) {
+    if (hyper) { step_size = hyper[0]; bc2_sqrt = hyper[1]; if (EMA) omd = hyper[2]; }
     const float norm = (float)sqrt(*sumsq);
     float coef = max_norm / (norm + 1e-6f);
     coef = fminf(coef, 1.0f);
@@ -437,10 +444,17 @@ __global__ __launch_bounds__(TPB) void adam_clip_kernel(float* p, const float* g
         mi = mi + (gi - mi) * omb1;                       // exp_avg.lerp_(grad, 1 - beta1)
         vi = vi * b2 + omb2 * gi * gi;                     // mul_(beta2).addcmul_(grad, grad, 1 - beta2)
         const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        p[i] = p[i] - step_size * (mi / denom);            // addcdiv_(exp_avg, denom, -step_size)
+        const float pi = p[i] - step_size * (mi / denom); // addcdiv_(exp_avg, denom, -step_size)
+        p[i] = pi;
         m[i] = mi;
         v[i] = vi;
+        if (EMA) ema[i] = ema_shadow(ema[i], pi, omd);
     }
+}
+
+// EMAModel.step outside an optimizer step: the same three roundings over the same grid
+__global__ __launch_bounds__(TPB) void ema_update_kernel(float* ema, const float* p, int64_t n, float omd) {
+    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) ema[i] = ema_shadow(ema[i], p[i], omd);
 }
 
 
@@ -755,18 +769,55 @@ extern "C" int bd_adam_clip(float* p, const float* g, float* m, float* v, int64_
     BD_CHECK(p && g && m && v && sumsq && n > 0 && step >= 1, BD_ERR_INVALID, "bd_adam_clip: bad args");
     const double bc1 = 1.0 - pow(b1, step), bc2 = 1.0 - pow(b2, step);
     const float step_size = (float)(lr / bc1), bc2_sqrt = (float)sqrt(bc2);
-    hipLaunchKernelGGL(adam_clip_kernel, dim3(nblocks(n, TPB, 8192)), dim3(TPB), 0, S(stream), p, g, m, v, n, sumsq, (float)max_norm,
-                       step_size, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)eps, bc2_sqrt, grad_norm_out,
-                       (const float*)nullptr);
+    hipLaunchKernelGGL(adam_clip_kernel<false>, dim3(nblocks(n, TPB, 8192)), dim3(TPB), 0, S(stream), p, g, m, v, n, sumsq,
+                       (float)max_norm, step_size, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)eps, bc2_sqrt, grad_norm_out,
+                       (const float*)nullptr, (float*)nullptr, 0.f);
     BD_LAUNCH_CHECK("adam_clip");
     return BD_OK;
 }
 extern "C" int bd_adam_clip_dev(float* p, const float* g, float* m, float* v, int64_t n, const double* sumsq, double max_norm,
                                 const float* hyper, double b1, double b2, double eps, float* grad_norm_out, bd_stream_t stream) {
     BD_CHECK(p && g && m && v && sumsq && hyper && n > 0, BD_ERR_INVALID, "bd_adam_clip_dev: bad args");
-    hipLaunchKernelGGL(adam_clip_kernel, dim3(nblocks(n, TPB, 8192)), dim3(TPB), 0, S(stream), p, g, m, v, n, sumsq, (float)max_norm,
-                       0.f, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)eps, 1.f, grad_norm_out, hyper);
+    hipLaunchKernelGGL(adam_clip_kernel<false>, dim3(nblocks(n, TPB, 8192)), dim3(TPB), 0, S(stream), p, g, m, v, n, sumsq,
+                       (float)max_norm, 0.f, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)eps, 1.f, grad_norm_out, hyper,
+                       (float*)nullptr, 0.f);
     BD_LAUNCH_CHECK("adam_clip_dev");
+    return BD_OK;
+}
+extern "C" int bd_adam_clip_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const double* sumsq, double max_norm,
+                                double lr, double b1, double b2, double eps, int step, float one_minus_decay, float* grad_norm_out,
+                                bd_stream_t stream) {
+    BD_CHECK(p && g && m && v && ema && sumsq && n > 0 && step >= 1, BD_ERR_INVALID, "bd_adam_clip_ema: bad args (null pointer, n <= 0 or step < 1)");
+    const float* others[4] = {p, m, v, g};
+    const int bad = ema_args_bad(ema, others, 4, n, one_minus_decay);
+    BD_CHECK(bad != 1, BD_ERR_INVALID, "bd_adam_clip_ema: one_minus_decay = %g (must be finite and in [0, 1])", (double)one_minus_decay);
+    BD_CHECK(bad == 0, BD_ERR_INVALID, "bd_adam_clip_ema: ema overlaps p, m, v or g over n = %lld floats", (long long)n);
+    const double bc1 = 1.0 - pow(b1, step), bc2 = 1.0 - pow(b2, step);
+    const float step_size = (float)(lr / bc1), bc2_sqrt = (float)sqrt(bc2);
+    hipLaunchKernelGGL(adam_clip_kernel<true>, dim3(nblocks(n, TPB, 8192)), dim3(TPB), 0, S(stream), p, g, m, v, n, sumsq,
+                       (float)max_norm, step_size, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)eps, bc2_sqrt, grad_norm_out,
+                       (const float*)nullptr, ema, one_minus_decay);
+    BD_LAUNCH_CHECK("adam_clip_ema");
+    return BD_OK;
+}
+extern "C" int bd_adam_clip_ema_dev(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const double* sumsq,
+                                    double max_norm, const float* hyper, double b1, double b2, double eps, float* grad_norm_out,
+                                    bd_stream_t stream) {
+    BD_CHECK(p && g && m && v && ema && sumsq && hyper && n > 0, BD_ERR_INVALID, "bd_adam_clip_ema_dev: bad args (null pointer or n <= 0)");
+    hipLaunchKernelGGL(adam_clip_kernel<true>, dim3(nblocks(n, TPB, 8192)), dim3(TPB), 0, S(stream), p, g, m, v, n, sumsq,
+                       (float)max_norm, 0.f, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)eps, 1.f, grad_norm_out, hyper, ema,
+                       0.f);
+    BD_LAUNCH_CHECK("adam_clip_ema_dev");
+    return BD_OK;
+}
+extern "C" int bd_ema_update(float* ema, const float* p, int64_t n, float one_minus_decay, bd_stream_t stream) {
+    BD_CHECK(ema && p && n > 0, BD_ERR_INVALID, "bd_ema_update: bad args (null pointer or n <= 0)");
+    const float* others[1] = {p};
+    const int bad = ema_args_bad(ema, others, 1, n, one_minus_decay);
+    BD_CHECK(bad != 1, BD_ERR_INVALID, "bd_ema_update: one_minus_decay = %g (must be finite and in [0, 1])", (double)one_minus_decay);
+    BD_CHECK(bad == 0, BD_ERR_INVALID, "bd_ema_update: ema overlaps p over n = %lld floats", (long long)n);
+    hipLaunchKernelGGL(ema_update_kernel, dim3(nblocks(n, TPB, 8192)), dim3(TPB), 0, S(stream), ema, p, n, one_minus_decay);
+    BD_LAUNCH_CHECK("ema_update");
     return BD_OK;
 }
 __global__ __launch_bounds__(256) void axpy_kernel(const float* src, float* dst, int64_t n, float scale, int acc) {

@@ -706,11 +706,37 @@ def sumsq(g, out=None):
     return out
 
 
-def adam_clip(p, g, m, v, sumsq_t, step, lr, max_norm=1.0, betas=(0.9, 0.999), eps=1e-8, grad_norm_out=None):
+def adam_clip(p, g, m, v, sumsq_t, step, lr, max_norm=1.0, betas=(0.9, 0.999), eps=1e-8, grad_norm_out=None, ema=None, one_minus_decay=None):
+    """clip + Adam on flat buffers; with `ema` (a flat fp32 shadow of p) and `one_minus_decay`, the EMA update of the shadow rides in the same launch"""
     lib = L.load(); _need_cuda(p, g, m, v, sumsq_t)
-    L.check(lib.bd_adam_clip(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(), L.ptr(sumsq_t), float(max_norm), float(lr),
-                             float(betas[0]), float(betas[1]), float(eps), int(step), L.ptr(grad_norm_out), L.stream()),
-            "bd_adam_clip")
+    if ema is None:
+        if one_minus_decay is not None:
+            raise ValueError("adam_clip: one_minus_decay without ema")
+        L.check(lib.bd_adam_clip(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(), L.ptr(sumsq_t), float(max_norm), float(lr),
+                                 float(betas[0]), float(betas[1]), float(eps), int(step), L.ptr(grad_norm_out), L.stream()),
+                "bd_adam_clip")
+        return
+    if one_minus_decay is None:
+        raise ValueError("adam_clip: ema needs one_minus_decay")
+    _need_cuda(ema)
+    _need_flat_f32("adam_clip", ema, p)
+    L.check(lib.bd_adam_clip_ema(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), L.ptr(ema), p.numel(), L.ptr(sumsq_t), float(max_norm), float(lr),
+                                 float(betas[0]), float(betas[1]), float(eps), int(step), float(one_minus_decay), L.ptr(grad_norm_out),
+                                 L.stream()), "bd_adam_clip_ema")
+
+
+def _need_flat_f32(what, ema, p):
+    if ema.dtype != torch.float32 or p.dtype != torch.float32 or not ema.is_contiguous() or not p.is_contiguous() or ema.numel() != p.numel():
+        raise TypeError(f"{what}: ema and p must be contiguous float32 tensors of one size, got {ema.dtype} {tuple(ema.shape)} / "
+                        f"{p.dtype} {tuple(p.shape)}")
+
+
+def ema_update(ema, p, one_minus_decay):
+    """ema <- ema - fl(omd * fl(ema - p)) in place (EMAModel.step, diffusers/training_utils.py:200-202): three fp32 roundings, one launch"""
+    lib = L.load(); _need_cuda(ema, p)
+    _need_flat_f32("ema_update", ema, p)
+    L.check(lib.bd_ema_update(L.ptr(ema), L.ptr(p), p.numel(), float(one_minus_decay), L.stream()), "bd_ema_update")
+    return ema
 
 
 def tune_set(name, value, check=True):

@@ -159,9 +159,16 @@ def plan_segment_ranges(model):
 class TrainEngine:
     def __init__(self, model, noise_sched, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0,
                  lr_warmup_steps=500, num_training_steps=None, loss_type="l2", process_group=None,
-                 grad_accum_steps=1, use_graph=None, force_dp=None, dp_check=False):
+                 grad_accum_steps=1, use_graph=None, force_dp=None, dp_check=False, ema=None):
         if not model.flat.is_cuda:
             raise RuntimeError("TrainEngine needs the model on a GPU")
+        # ema: an ema.EMAModel built on this model.  Its flat shadow is updated inside the clip + Adam launch of every OPTIMIZER step
+        # (bd_adam_clip_ema), from the weights that launch has just written; None: the step is the launches it always was.
+        if ema is not None and (ema.shadow.shape != model.flat.shape or ema.shadow.device != model.flat.device):
+            raise ValueError("TrainEngine: ema must be an EMAModel built on the same model (same flat size and device)")
+        self.ema = ema
+        if ema is not None:
+            ema.attached = True      # the shadow's address is handed to launches (and captured graphs): EMAModel.to() may not move it
         self.model, self.sched = model, noise_sched
         self.lr, self.betas, self.eps, self.max_grad_norm = lr, betas, eps, max_grad_norm
         self.warmup, self.total_steps = lr_warmup_steps, num_training_steps
@@ -353,7 +360,7 @@ class TrainEngine:
         without this, ranks that initialised or resumed differently would apply the averaged gradient at different
         points and drift apart).  Call again after loading optimizer state on a resume."""
         if self.world > 1:
-            for t in (self.model.flat.data, self.m, self.v):
+            for t in (self.model.flat.data, self.m, self.v) + (() if self.ema is None else (self.ema.shadow,)):
                 if self._rccl is not None and self._rccl != "none":
                     self._rccl.broadcast_(t, 0, torch.cuda.current_stream())
                 else:
@@ -429,8 +436,10 @@ class TrainEngine:
         lr = self.current_lr() if self.total_steps is None else \
             self.lr * cosine_schedule_with_warmup(self.opt_step - 1, self.warmup, self.total_steps)
         ops.sumsq(grads, out=self.sumsq)
+        ema = self.ema
         ops.adam_clip(self.model.flat.data, grads, self.m, self.v, self.sumsq, self.opt_step, lr, self.max_grad_norm,
-                      self.betas, self.eps, grad_norm_out=self.grad_norm)
+                      self.betas, self.eps, grad_norm_out=self.grad_norm, ema=None if ema is None else ema.shadow,
+                      one_minus_decay=None if ema is None else ema.advance())
 
     # ---- hipGraph replay of the step ----------------------------------------------------------------------
     def _adam_hyper(self, step, lr):
@@ -440,9 +449,11 @@ class TrainEngine:
     def _graph_step(self, images, is_poison, trigger, target_img, noise, timesteps, row_index, flip):
         """Same launches as the eager step, captured once per input signature and replayed.  Everything that changes
         from step to step enters through static device buffers: the batch (or its row numbers into the resident
-        dataset), noise, timesteps and the two Adam scalars {lr / (1 - b1^t), sqrt(1 - b2^t)} (bd_adam_clip_dev)."""
+        dataset), noise, timesteps and the two Adam scalars {lr / (1 - b1^t), sqrt(1 - b2^t)} (bd_adam_clip_dev); with an EMA, its
+        one_minus_decay as a third (bd_adam_clip_ema_dev)."""
         key = (tuple(images.shape), images.dtype, images.data_ptr() if row_index is not None else 0, row_index is not None,
                flip is not None, tuple(noise.shape))
+        nh = 2 if self.ema is None else 3
         ent = self._graphs.get(key)
         if ent is None:
             dev = noise.device
@@ -451,8 +462,8 @@ class TrainEngine:
                   "images": images if row_index is not None else torch.empty_like(images),
                   "rows": torch.empty_like(row_index) if row_index is not None else None,
                   "flip": torch.empty_like(flip) if flip is not None else None,
-                  "hyper": torch.zeros(2, device=dev), "loss": torch.zeros((), device=dev)}
-            ring = torch.zeros(64, 2).pin_memory()
+                  "hyper": torch.zeros(nh, device=dev), "loss": torch.zeros((), device=dev)}
+            ring = torch.zeros(64, nh).pin_memory()
 
             def body():
                 xn, tg = ops.poison_qsample(st["images"], st["is_poison"], st["trigger"], st["target"], st["noise"], st["t"],
@@ -460,10 +471,17 @@ class TrainEngine:
                 loss = self.forward_backward(xn, tg, st["t"])
                 ops.sumsq(self.grads, out=self.sumsq)
                 b1, b2 = self.betas
-                L.check(self._lib.bd_adam_clip_dev(self.model.flat.data.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(),
-                                                   self.v.data_ptr(), self.grads.numel(), self.sumsq.data_ptr(), float(self.max_grad_norm),
-                                                   st["hyper"].data_ptr(), float(b1), float(b2), float(self.eps),
-                                                   self.grad_norm.data_ptr(), L.stream()), "bd_adam_clip_dev")
+                if self.ema is None:
+                    L.check(self._lib.bd_adam_clip_dev(self.model.flat.data.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(),
+                                                       self.v.data_ptr(), self.grads.numel(), self.sumsq.data_ptr(), float(self.max_grad_norm),
+                                                       st["hyper"].data_ptr(), float(b1), float(b2), float(self.eps),
+                                                       self.grad_norm.data_ptr(), L.stream()), "bd_adam_clip_dev")
+                else:
+                    L.check(self._lib.bd_adam_clip_ema_dev(self.model.flat.data.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(),
+                                                           self.v.data_ptr(), self.ema.shadow.data_ptr(), self.grads.numel(),
+                                                           self.sumsq.data_ptr(), float(self.max_grad_norm), st["hyper"].data_ptr(),
+                                                           float(b1), float(b2), float(self.eps), self.grad_norm.data_ptr(), L.stream()),
+                                "bd_adam_clip_ema_dev")
                 st["loss"].copy_(loss)
             ent = {"st": st, "ring": ring, "graph": None, "body": body, "n": 0}
             self._graphs[key] = ent
@@ -480,6 +498,8 @@ class TrainEngine:
         lr = self.lr if self.total_steps is None else self.lr * cosine_schedule_with_warmup(self.opt_step - 1, self.warmup, self.total_steps)
         slot = ent["ring"][ent["n"] % 64]
         slot[0], slot[1] = self._adam_hyper(self.opt_step, lr)
+        if self.ema is not None:
+            slot[2] = self.ema.advance()
         st["hyper"].copy_(slot, non_blocking=True)
         ent["n"] += 1
         if ent["graph"] is None and ent["n"] >= 2:        # step 1 runs eagerly (lazy allocations, side stream creation)

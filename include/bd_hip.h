@@ -691,6 +691,25 @@ int bd_adam_clip_dev(float* p, const float* g, float* m, float* v, int64_t n, co
                      double max_norm, const float* hyper, double b1, double b2, double eps,
                      float* grad_norm_out, bd_stream_t stream);
 
+/* a-8 + EMA: the exponential moving average of the weights (diffusers/training_utils.py:176-204, EMAModel.step) over ONE
+ * flat fp32 shadow buffer `ema` of the same n floats as p:
+ *   s_param.sub_(one_minus_decay * (s_param - param))   ==   s <- s - fl(omd * fl(s - p)),  omd = (float)(1 - decay),
+ * three separately rounded fp32 operations (never a contracted fma), so the shadow carries the bits torch computes.
+ * decay 0 gives s - (s - p), which is not always p; the reference has the same property.
+ * bd_adam_clip_ema: bd_adam_clip plus the shadow update in the SAME launch, from the p[i] it has just stored; p, m, v and
+ *   *grad_norm_out are bit-identical to bd_adam_clip on the same inputs.  Scalar accesses: any 4-byte aligned `ema` is valid.
+ * bd_adam_clip_ema_dev: the hipGraph form, hyper = { lr / (1 - b1^step), sqrt(1 - b2^step), one_minus_decay } in DEVICE memory.
+ * bd_ema_update: the stand-alone update (EMAModel.step outside a training engine), same formula, same bits.
+ * Host checks before any launch (BD_ERR_INVALID): null pointers, n <= 0; one_minus_decay not finite or outside [0, 1]; `ema`
+ * overlapping p, m, v or g as ranges of n floats.  The _dev form checks pointers only. */
+int bd_adam_clip_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const double* sumsq,
+                     double max_norm, double lr, double b1, double b2, double eps, int step, float one_minus_decay,
+                     float* grad_norm_out, bd_stream_t stream);
+int bd_adam_clip_ema_dev(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const double* sumsq,
+                         double max_norm, const float* hyper, double b1, double b2, double eps,
+                         float* grad_norm_out, bd_stream_t stream);
+int bd_ema_update(float* ema, const float* p, int64_t n, float one_minus_decay, bd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
