@@ -60,6 +60,11 @@ class GnParamItem(C.Structure):
     _fields_ = [("partials", vp), ("C", i32), ("dgamma", vp), ("dbeta", vp)]
 
 
+class GnPlanInfo(C.Structure):
+    _fields_ = [("resident", i32), ("nt", i32), ("cb", i32), ("q", i32), ("R", i32), ("E", i32), ("emax", i32),
+                ("S", i32), ("threads", i32), ("r", i32), ("per", i32)]
+
+
 class Operand(C.Structure):
     _fields_ = [("kind", i32), ("kc", i32), ("p", vp), ("ld", i64), ("bs_outer", i64), ("bs_inner", i64),
                 ("C", i32), ("Hs", i32), ("Ws", i32), ("Ho", i32), ("Wo", i32), ("stride", i32),
@@ -189,6 +194,7 @@ SIGNATURES = {
     "bd_global_avgpool_nhwc": (i32, [vp, i64, vp, i32, i32, i32, vp]),
     "bd_gn_bwd_defers": (i32, [i32, i32, i32, i32]),
     "bd_gn_bwd_params": (i32, [C.POINTER(GnParamItem), i32, i32, vp]),
+    "bd_gn_plan": (i32, [i32, i32, i32, i32, i32, C.POINTER(GnPlanInfo)]),
     "bd_igemm_workspace_bytes": (sz, [C.POINTER(IgemmDesc)]),
     "bd_igemm": (i32, [C.POINTER(IgemmDesc), vp]),
     "bd_split_bf16": (i32, [vp, i64, vp, vp]),

@@ -500,6 +500,11 @@ static bool gn_resident_plan(int B, int HW, int C, int G, GnRes& o, bool wide_ok
     }
     return false;
 }
+// the instantiation <EMAX, NT> of gn_fwd_res_kernel / gn_bwd_res_kernel that a resident plan launches: the smallest register array that holds E
+static void gn_res_template(const GnRes& rp, int& emax, int& nt) {
+    nt = rp.nt == 512 ? 512 : 256;
+    emax = nt == 512 ? (rp.E <= 8 ? 8 : GN_RES_EMAX) : (rp.E <= 4 ? 4 : GN_RES_EMAX);
+}
 
 // 1-D grid over (sample, channel block), remapped so that each XCD (workgroup id % 8) owns a contiguous run with the
 // channel blocks of a sample adjacent: the 64-byte row pieces of neighbouring channel blocks share 128-byte lines, and
@@ -855,9 +860,11 @@ extern "C" int bd_gn_fwd(const bd_gn_fwd_desc* d, bd_stream_t stream) {
     hipLaunchKernelGGL((gn_fwd_res_kernel<EM, NT>), grid, dim3(NT), 0, S(stream), d->x, (long long)d->ldx, d->y,             \
                        (long long)d->ldy, d->HW, d->C, d->G, rp.cb, rp.q, rp.R, rp.E, d->eps, d->gamma, d->beta, d->mean,       \
                        d->rstd, d->silu, d->y_split, (long long)d->ldys)
-        if (rp.nt == 512 && rp.E <= 8) BD_GN_FWD_RES(8, 512);
-        else if (rp.nt == 512) BD_GN_FWD_RES(GN_RES_EMAX, 512);
-        else if (rp.E <= 4) BD_GN_FWD_RES(4, 256);
+        int em, nt;
+        gn_res_template(rp, em, nt);
+        if (nt == 512 && em == 8) BD_GN_FWD_RES(8, 512);
+        else if (nt == 512) BD_GN_FWD_RES(GN_RES_EMAX, 512);
+        else if (em == 4) BD_GN_FWD_RES(4, 256);
         else BD_GN_FWD_RES(GN_RES_EMAX, 256);
 #undef BD_GN_FWD_RES
         BD_LAUNCH_CHECK("gn_fwd_res");
@@ -899,6 +906,25 @@ extern "C" int bd_gn_fwd_takes_stats(int B, int HW, int C, int G) {
 extern "C" int bd_gn_bwd_defers(int B, int HW, int C, int G) {
     // round 4: both the resident and the large-image path leave per-sample partials to the caller
     return B > 0 && HW > 0 && C > 0 && G > 0 && C % G == 0 && (C & 3) == 0 ? 1 : 0;
+}
+
+extern "C" int bd_gn_plan(int B, int HW, int C, int G, int backward, bd_gn_plan_info* out) {
+    // host only: the functions bd_gn_fwd / bd_gn_bwd call to choose their kernels, nothing else
+    BD_CHECK(out, BD_ERR_INVALID, "bd_gn_plan: null output");
+    BD_CHECK(B > 0 && HW > 0 && C > 0 && G > 0 && C % G == 0 && (C & 3) == 0 && C / 4 <= 1024 && B <= 65535, BD_ERR_INVALID,
+             "bd_gn_plan: not a shape bd_gn_fwd / bd_gn_bwd take (B=%d HW=%d C=%d G=%d)", B, HW, C, G);
+    *out = bd_gn_plan_info{};
+    GnRes rp;
+    if (gn_resident_plan(B, HW, C, G, rp, backward != 0)) {
+        out->resident = 1;
+        out->cb = rp.cb; out->q = rp.q; out->R = rp.R; out->E = rp.E;
+        gn_res_template(rp, out->emax, out->nt);
+        return BD_OK;
+    }
+    out->S = gn_splits(B, HW);
+    gn_block(C, out->threads, out->r);
+    out->per = gn_apply_rows(HW, out->r);
+    return BD_OK;
 }
 
 extern "C" int bd_gn_bwd_params(const bd_gn_param_item* items, int n, int B, bd_stream_t stream) {
@@ -953,9 +979,11 @@ extern "C" int bd_gn_bwd(const bd_gn_bwd_desc* d, bd_stream_t stream) {
                        (long long)d->lddy, d->dx, (long long)d->lddx, d->HW, d->C, d->G, rp.cb, rp.q, rp.R, rp.E, d->gamma,     \
                        d->beta, d->mean, d->rstd, d->silu, d->accumulate_dx, part_r, d->dx_colsum, (long long)d->ld_colsum, \
                        d->dx_split, (long long)d->lddxs, d->dx_add, (long long)d->ld_add, xs0, xs1)
-        if (rp.nt == 512 && rp.E <= 8) BD_GN_BWD_RES(8, 512);
-        else if (rp.nt == 512) BD_GN_BWD_RES(GN_RES_EMAX, 512);
-        else if (rp.E <= 4) BD_GN_BWD_RES(4, 256);
+        int em, nt;
+        gn_res_template(rp, em, nt);
+        if (nt == 512 && em == 8) BD_GN_BWD_RES(8, 512);
+        else if (nt == 512) BD_GN_BWD_RES(GN_RES_EMAX, 512);
+        else if (em == 4) BD_GN_BWD_RES(4, 256);
         else BD_GN_BWD_RES(GN_RES_EMAX, 256);
 #undef BD_GN_BWD_RES
         BD_LAUNCH_CHECK("gn_bwd_res");

@@ -207,6 +207,17 @@ typedef struct {
 /* dgamma[c] / dbeta[c] = sum over the B samples of the partials, fixed order, for n layers in one launch
  * (the reduction over the batch of aten::native_group_norm_backward's weight / bias gradients, resnet.py:559,591) */
 int bd_gn_bwd_params(const bd_gn_param_item* items, int n, int B, bd_stream_t stream);
+/* Which kernels bd_gn_fwd (backward == 0) / bd_gn_bwd (backward != 0) launch for a shape: host code only, computed by the functions the
+ * launchers themselves call.  For tests and tools that must know which branch a shape takes (DESIGN.md "GroupNorm dispatch"). */
+typedef struct {
+    int resident;                   /* 1: one workgroup per (sample, channel block) holds its slab in registers; 0: the two-stage kernels */
+    int nt, cb, q, R, E, emax;      /* resident: threads per workgroup, channels per block, float4 per pixel row (cb / 4), pixel rows in
+                                       flight (nt / q), float4 per thread and tensor (ceil(HW / R)), and the EMAX of the <EMAX, nt>
+                                       instantiation launched (4, 8 or 16); 0 otherwise */
+    int S, threads, r, per;         /* two-stage: pixel splits of the statistics pass, threads per workgroup ((C / 4) * r), pixel rows in
+                                       flight, pixel rows per block of the apply kernels; 0 otherwise */
+} bd_gn_plan_info;
+int bd_gn_plan(int B, int HW, int C, int G, int backward, bd_gn_plan_info* out);
 
 /* ------------------------------------------------------------------------------------------------
  * Implicit-GEMM engine on f32 MFMA (v_mfma_f32_32x32x2_f32: exact fp32 products/accumulate).
