@@ -62,7 +62,7 @@ class GnParamItem(C.Structure):
 
 class GnPlanInfo(C.Structure):
     _fields_ = [("resident", i32), ("nt", i32), ("cb", i32), ("q", i32), ("R", i32), ("E", i32), ("emax", i32),
-                ("S", i32), ("threads", i32), ("r", i32), ("per", i32)]
+                ("S", i32), ("threads", i32), ("r", i32), ("per", i32), ("workspace_bytes", sz)]
 
 
 class Operand(C.Structure):

@@ -51,6 +51,9 @@ static inline bool mode_valid(int m) { return m == BD_MODE_F32 || mode_bf16(m); 
 static inline bool sp_mode_valid(int m) { return m == 0 || mode_bf16(m); }
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// GroupNorm statistics partials [B][S][G][2] fp64 (sum, sum of squares per sample, pixel split and group): written by gn_stats_kernel or by
+// the epilogue of the producing convolution (bd_conv3x3_ps gn_part), read by gn_fwd_finalize_kernel
+static inline size_t gn_stats_partial_bytes(int B, int S, int G) { return (size_t)B * (size_t)S * (size_t)G * 2 * sizeof(double); }
 // log2 of a power of two, -1 for anything else
 static inline int ilog2_exact(int v) {
     if (v <= 0 || (v & (v - 1))) return -1;

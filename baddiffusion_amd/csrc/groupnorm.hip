@@ -14,37 +14,14 @@
 //
 // Replaces aten::native_group_norm / native_group_norm_backward / silu / silu_backward
 // (resnet.py:559,591; attention.py:125; unet_2d.py:312-313).
+//
+// Layout: the device helpers the kernels share (GnChan, gn_affine, gn_dz, gn_dx_term, gn_mean_rstd, GnSpan), the two-stage kernels, the
+// resident kernels, then the host side: gn_plan() decides once what the launchers decide from a shape, gn_fwd_workspace() /
+// gn_bwd_workspace() lay the workspace out, and bd_gn_fwd, bd_gn_bwd, bd_gn_plan, bd_gn_fwd_takes_stats and bd_gn_bwd_defers read those.
+#include <type_traits>
 #include "common.h"
 
 namespace bd {
-
-constexpr int GN_MAX_SPLITS = 128;   // small batches of large images (B = 4 at 256x256) need the pixel splits to fill the chip
-
-static int gn_max_splits(int B) {
-    int s = 512 / (B > 0 ? B : 1);
-    return s < 1 ? 1 : (s > GN_MAX_SPLITS ? GN_MAX_SPLITS : s);
-}
-static int gn_splits(int B, int HW) {
-    int s = 512 / (B > 0 ? B : 1);
-    if (s < 1) s = 1;
-    if (s > GN_MAX_SPLITS) s = GN_MAX_SPLITS;
-    while (s > 1 && HW / s < 32) s >>= 1;
-    return s;
-}
-// threads = (C/4) * r, r pixel rows in flight
-static void gn_block(int C, int& threads, int& r) {
-    const int q = C / 4;
-    r = 256 / q;
-    if (r < 1) r = 1;
-    threads = q * r;
-}
-
-// pixel rows per block of the apply kernels: 16 rows per thread (four / eight trips of the unrolled loop), at most 65535 blocks
-static int gn_apply_rows(int HW, int r) {
-    long long per = 16LL * r;
-    while (cdiv(HW, per) > 65535) per *= 2;
-    return (int)per;
-}
 
 // Round 4: the sigmoid from the hardware transcendentals -- v_exp_f32 (2^x, 1 ulp) of -z * log2(e) and v_rcp_f32 (1 ulp): 4 VALU instructions instead of
 // the ~25 of expf() + an IEEE division, <= 3 ulp of fp32 (tests: 1e-5 against fp64 torch).  An instruction census of the CIFAR step
@@ -75,29 +52,73 @@ __device__ __forceinline__ float silu_grad_fast(float z) {
 
 // ---- split-plane output (bd_hip.h "split planes"): 4 consecutive channels c..c+3 of one row -> 8 B of bf16 hi and 8 B of
 // bf16 lo (common.h: hi = RNE, lo = RNE of the remainder: bit-identical to the on-the-fly split of the bf16x3 engine)
-// row = start of the row's planes (uint16 units), c = channel of o[0] (c % 4 == 0)
-__device__ __forceinline__ void gn_store_split4(unsigned short* row, int c, const float (&o)[4]) {
+// row = start of the row's planes (uint16 units), c = channel of o.x (c % 4 == 0)
+__device__ __forceinline__ void gn_store_split4(unsigned short* row, int c, const float4& o) {
     unsigned short* q = row + (c >> 5) * 64 + (c & 31);
-    *reinterpret_cast<uint2*>(q) = make_uint2(bd_pack_hi(o[0], o[1]), bd_pack_hi(o[2], o[3]));
-    *reinterpret_cast<uint2*>(q + 32) = make_uint2(bd_pack_lo(o[0], o[1]), bd_pack_lo(o[2], o[3]));
+    *reinterpret_cast<uint2*>(q) = make_uint2(bd_pack_hi(o.x, o.y), bd_pack_hi(o.z, o.w));
+    *reinterpret_cast<uint2*>(q + 32) = make_uint2(bd_pack_lo(o.x, o.y), bd_pack_lo(o.z, o.w));
 }
 
 // The kernels below load their rows with common.h's bd_ld4_if.  A `cond ? *p : 0` in an unrolled loop makes hipcc branch around every
 // load and wait vmcnt(0) behind it (cdna_hip_programming.md section 5, trap (c)): 16 serialised memory round trips per thread instead
 // of 16 loads in flight.
 
+// ---- the arithmetic the kernels share, written once ---------------------------------------------------
+// the constants of a thread's four channels c0 .. c0 + 3 of sample b
+struct GnChan {
+    float mu[4], rs[4], gg[4], bb[4];
+    GnChan() = default;      // (filled by the kernel's own loop: see there why)
+    __device__ __forceinline__ GnChan(const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ gamma,
+                                      const float* __restrict__ beta, int b, int G, int cpg, int c0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = c0 + j, g = c / cpg;
+            mu[j] = mean[b * G + g]; rs[j] = rstd[b * G + g];
+            gg[j] = gamma[c]; bb[j] = beta[c];
+        }
+    }
+};
+__device__ __forceinline__ float gn_xhat(const GnChan& k, int j, float x) { return (x - k.mu[j]) * k.rs[j]; }
+__device__ __forceinline__ float gn_z(const GnChan& k, int j, float xhat) { return xhat * k.gg[j] + k.bb[j]; }   // what the SiLU sees
+__device__ __forceinline__ float gn_affine(const GnChan& k, int j, float x) { return gn_z(k, j, gn_xhat(k, j, x)); }
+// dz: dy through the SiLU's gradient
+__device__ __forceinline__ float gn_dz(const GnChan& k, int j, float xhat, float dy, int silu) {
+    return silu ? dy * silu_grad_fast(gn_z(k, j, xhat)) : dy;
+}
+// dx = rstd * (dz*gamma - (s1 + xhat*s2)/n), s1 = sum gamma*dz and s2 = sum gamma*dz*xhat over the group
+__device__ __forceinline__ float gn_dx_term(const GnChan& k, int j, float xhat, float dz, float s1, float s2, float inv_n) {
+    return k.rs[j] * (dz * k.gg[j] - (s1 + xhat * s2) * inv_n);
+}
+// (mean, rstd) of a group from its sum a and sum of squares c2 over n elements
+__device__ __forceinline__ void gn_mean_rstd(double a, double c2, double n, float eps, float* mean, float* rstd) {
+    const double mu = a / n;
+    double var = c2 / n - mu * mu;
+    if (var < 0.0) var = 0.0;
+    *mean = (float)mu;
+    *rstd = (float)(1.0 / sqrt(var + (double)eps));
+}
+// a thread of the two-stage kernels (grid = (pixel ranges, B), block = q x r threads): float4 column cq of the pixel rows prow, prow + r, ...
+// of [p0, p1) in sample b.  splits: n is the number of ranges (statistics kernels), else the rows of one (apply kernels).  (A constructor:
+// hipcc optimises a function that returns the struct on its own before inlining it, and the statistics kernels' schedule changes.)
+struct GnSpan {
+    int cq, prow, b, p0, p1;
+    __device__ __forceinline__ GnSpan(int q, int HW, int n, bool splits) {
+        const int t = threadIdx.x;
+        cq = t % q; prow = t / q;
+        b = blockIdx.y;
+        const int bx = blockIdx.x, per = splits ? (HW + n - 1) / n : n;
+        p0 = bx * per;
+        p1 = p0 + per;
+        if (p1 > HW) p1 = HW;
+    }
+};
+
 // ---- forward stats: per (b, split) partial (sum, sumsq) per group, in double -----------------------
 __global__ void gn_stats_kernel(const float* __restrict__ x, long long ldx, int HW, int C, int G, int r, int S,
                                 double* __restrict__ part /* [B][S][G][2] */) {
     extern __shared__ float sh[];  // [r][C][2]
-    const int q = C / 4;
-    const int t = threadIdx.x;
-    const int cq = t % q, prow = t / q;
-    const int b = blockIdx.y, s = blockIdx.x;
-    const int per = (HW + S - 1) / S;
-    const int p0 = s * per;
-    int p1 = p0 + per;
-    if (p1 > HW) p1 = HW;
+    const auto [cq, prow, b, p0, p1] = GnSpan(C / 4, HW, S, true);
+    const int t = threadIdx.x, s = blockIdx.x;
     float sm[4] = {0.f, 0.f, 0.f, 0.f}, sq[4] = {0.f, 0.f, 0.f, 0.f};
     const float* xb = x + (long long)b * HW * ldx + cq * 4;
     for (int p = p0 + prow; p < p1; p += 4 * r) {   // four rows in flight (branch-free: rows past the end read zeros)
@@ -151,11 +172,9 @@ __global__ __launch_bounds__(256) void gn_fwd_finalize_kernel(const double* __re
         if (ph == 0 && g < G) {
             a = 0.0; c2 = 0.0;
             for (int k = 0; k < 8; ++k) { a += red[threadIdx.x + k][0]; c2 += red[threadIdx.x + k][1]; }
-            const double mu = a / n;
-            double var = c2 / n - mu * mu;
-            if (var < 0.0) var = 0.0;
-            mean[b * G + g] = (float)mu;
-            rstd[b * G + g] = (float)(1.0 / sqrt(var + (double)eps));
+            float m, r;
+            gn_mean_rstd(a, c2, n, eps, &m, &r);
+            mean[b * G + g] = m; rstd[b * G + g] = r;
         }
         __syncthreads();
     }
@@ -170,20 +189,8 @@ __global__ void gn_apply_kernel(const float* __restrict__ x, long long ldx, floa
                                 int G, int r, int per, const float* __restrict__ gamma, const float* __restrict__ beta,
                                 const float* __restrict__ mean, const float* __restrict__ rstd, int silu,
                                 unsigned short* __restrict__ ys, long long ldys) {
-    const int q = C / 4, cpg = C / G;
-    const int t = threadIdx.x;
-    const int cq = t % q, prow = t / q;
-    const int b = blockIdx.y;
-    const int p0 = blockIdx.x * per;
-    int p1 = p0 + per;
-    if (p1 > HW) p1 = HW;
-    float mu[4], rs[4], gg[4], bb[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int c = cq * 4 + j;
-        mu[j] = mean[b * G + c / cpg]; rs[j] = rstd[b * G + c / cpg];
-        gg[j] = gamma[c]; bb[j] = beta[c];
-    }
+    const auto [cq, prow, b, p0, p1] = GnSpan(C / 4, HW, per, false);
+    const GnChan k(mean, rstd, gamma, beta, b, G, C / G, cq * 4);
     const float* xb = x + (long long)b * HW * ldx + cq * 4;
     float* yb = y + (long long)b * HW * ldy + cq * 4;
     for (int p = p0 + prow; p < p1; p += 4 * r) {
@@ -196,7 +203,7 @@ __global__ void gn_apply_kernel(const float* __restrict__ x, long long ldx, floa
             float o[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const float z = (in[j] - mu[j]) * rs[j] * gg[j] + bb[j];
+                const float z = gn_affine(k, j, in[j]);
                 o[j] = silu ? silu_fast(z) : z;
             }
             v[u] = make_float4(o[0], o[1], o[2], o[3]);
@@ -206,10 +213,7 @@ __global__ void gn_apply_kernel(const float* __restrict__ x, long long ldx, floa
             const int pu = p + u * r;
             if (pu < p1) {
                 if (y) *reinterpret_cast<float4*>(yb + (long long)pu * ldy) = v[u];
-                if (ys) {
-                    const float o[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-                    gn_store_split4(ys + 2 * ((long long)b * HW + pu) * ldys, cq * 4, o);
-                }
+                if (ys) gn_store_split4(ys + 2 * ((long long)b * HW + pu) * ldys, cq * 4, v[u]);
             }
         }
     }
@@ -222,23 +226,9 @@ __global__ void gn_bwd_stats_kernel(const float* __restrict__ x, long long ldx, 
                                     const float* __restrict__ rstd, int silu, float* __restrict__ part /* [B][S][3][C] */) {
     extern __shared__ float sh[];  // [r][C][3]
     const int q = C / 4, cpg = C / G;
-    const int t = threadIdx.x;
-    const int cq = t % q, prow = t / q;
-    const int b = blockIdx.y, s = blockIdx.x;
-    const int per = (HW + S - 1) / S;
-    const int p0 = s * per;
-    int p1 = p0 + per;
-    if (p1 > HW) p1 = HW;
-    float mu[4], rs[4], gg[4], bb[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int c = cq * 4 + j;
-        const int g = c / cpg;
-        mu[j] = mean[b * G + g];
-        rs[j] = rstd[b * G + g];
-        gg[j] = gamma[c];
-        bb[j] = beta[c];
-    }
+    const auto [cq, prow, b, p0, p1] = GnSpan(q, HW, S, true);
+    const int t = threadIdx.x, s = blockIdx.x;
+    const GnChan k(mean, rstd, gamma, beta, b, G, cpg, cq * 4);
     float s0[4] = {0.f, 0.f, 0.f, 0.f}, s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
     const float* xb = x + (long long)b * HW * ldx + cq * 4;
     const float* db = dy + (long long)b * HW * lddy + cq * 4;
@@ -256,9 +246,8 @@ __global__ void gn_bwd_stats_kernel(const float* __restrict__ x, long long ldx, 
             const float in[4] = {v[u].x, v[u].y, v[u].z, v[u].w}, dd[4] = {d[u].x, d[u].y, d[u].z, d[u].w};
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const float xh = ok ? (in[j] - mu[j]) * rs[j] : 0.f;
-                float dz = dd[j];
-                if (silu) dz *= silu_grad_fast(xh * gg[j] + bb[j]);
+                const float xh = ok ? gn_xhat(k, j, in[j]) : 0.f;
+                const float dz = gn_dz(k, j, xh, dd[j], silu);
                 s0[j] += dz;
                 s1[j] += dz * xh;
                 s2[j] += xh;
@@ -287,31 +276,14 @@ __global__ void gn_bwd_stats_kernel(const float* __restrict__ x, long long ldx, 
 }
 
 // ---- backward finalize -----------------------------------------------------------------------------
-// (a) dgamma/dbeta[c] = sum over the B*S partial rows: 64 columns x 4 row phases per block, fixed order
-__global__ __launch_bounds__(1024) void gn_bwd_param_kernel(const float* __restrict__ part, int rows, int row_stride, int C,
-                                                          float* __restrict__ dgamma, float* __restrict__ dbeta) {
-    __shared__ double red[16][64];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;   // 64 columns x 16 row phases
-    const int n = blockIdx.x * 64 + tx;   // column in [0, 2C): plane 0 = dgamma, plane 1 = dbeta
-    double s = 0.0;
-    if (n < 2 * C)
-        for (int r = ty; r < rows; r += 16) s += (double)part[(long long)r * row_stride + n];
-    red[ty][tx] = s;
-    __syncthreads();
-    if (ty == 0 && n < 2 * C) {
-        double t = 0.0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) t += red[k][tx];
-        const float v = (float)t;
-        if (n < C) dgamma[n] = v; else dbeta[n - C] = v;
-    }
-}
-// (a') the same fold for up to GN_PARAM_MAX layers whose per-sample partials [B][2][C] were left to the caller
-// (bd_gn_bwd_desc.param_partials): one launch per backward segment instead of one per GroupNorm
+// (a) dgamma/dbeta[c] = sum over the partial rows, for up to GN_PARAM_MAX layers in one launch: 64 columns x 16 row phases per block, fixed
+// order.  A layer's rows are the first two planes (0 = dgamma, 1 = dbeta) of either the per-sample partials [B][2][C] (row stride 2C: the
+// resident kernel's, or what bd_gn_bwd_desc.param_partials left to the caller -- one launch per backward segment instead of one per
+// GroupNorm) or the two-stage statistics rows [B*S][3][C] (row stride 3C).
 constexpr int GN_PARAM_MAX = 32;
 struct GnParamTable {
     const float* part[GN_PARAM_MAX]; float* dg[GN_PARAM_MAX]; float* db[GN_PARAM_MAX];
-    int C[GN_PARAM_MAX]; int blk0[GN_PARAM_MAX + 1]; int n;
+    int C[GN_PARAM_MAX]; int stride[GN_PARAM_MAX]; int blk0[GN_PARAM_MAX + 1]; int n;
 };
 __global__ __launch_bounds__(1024) void gn_bwd_param_batched_kernel(GnParamTable t, int rows) {
     __shared__ double red[16][64];
@@ -319,11 +291,11 @@ __global__ __launch_bounds__(1024) void gn_bwd_param_batched_kernel(GnParamTable
     while (i + 1 < t.n && (int)blockIdx.x >= t.blk0[i + 1]) ++i;
     const int C = t.C[i];
     const float* part = t.part[i];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const int n = ((int)blockIdx.x - t.blk0[i]) * 64 + tx;
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;   // 64 columns x 16 row phases
+    const int n = ((int)blockIdx.x - t.blk0[i]) * 64 + tx;    // column in [0, 2C)
     double s = 0.0;
     if (n < 2 * C)
-        for (int r = ty; r < rows; r += 16) s += (double)part[(long long)r * 2 * C + n];
+        for (int r = ty; r < rows; r += 16) s += (double)part[(long long)r * t.stride[i] + n];
     red[ty][tx] = s;
     __syncthreads();
     if (ty == 0 && n < 2 * C) {
@@ -401,19 +373,15 @@ __global__ void gn_bwd_apply_kernel(const float* __restrict__ x, long long ldx, 
                                     unsigned short* __restrict__ dxs, long long lddxs, const float* __restrict__ addp,
                                     long long ldadd, int dxs_c0, int dxs_c1) {
     const int q = C / 4, cpg = C / G;
-    const int t = threadIdx.x;
-    const int cq = t % q, prow = t / q;
-    const int b = blockIdx.y;
-    const int p0 = blockIdx.x * per;
-    int p1 = p0 + per;
-    if (p1 > HW) p1 = HW;
-    float mu[4], rs[4], gg[4], bb[4], g1[4], g2[4];
+    const auto [cq, prow, b, p0, p1] = GnSpan(q, HW, per, false);
+    GnChan k;      // (its own loop: the group sums between the loads of the constructor; behind them hipcc schedules one s_nop fewer)
+    float g1[4], g2[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int c = cq * 4 + j, g = c / cpg;
-        mu[j] = mean[b * G + g]; rs[j] = rstd[b * G + g];
+        k.mu[j] = mean[b * G + g]; k.rs[j] = rstd[b * G + g];
         g1[j] = ds[((long long)b * G + g) * 2]; g2[j] = ds[((long long)b * G + g) * 2 + 1];
-        gg[j] = gamma[c]; bb[j] = beta[c];
+        k.gg[j] = gamma[c]; k.bb[j] = beta[c];
     }
     const float* xb = x + (long long)b * HW * ldx + cq * 4;
     const float* db = dy + (long long)b * HW * lddy + cq * 4;
@@ -437,10 +405,8 @@ __global__ void gn_bwd_apply_kernel(const float* __restrict__ x, long long ldx, 
             float o[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const float xh = (in[j] - mu[j]) * rs[j];
-                float dz = dd[j];
-                if (silu) dz *= silu_grad_fast(xh * gg[j] + bb[j]);
-                o[j] = (rs[j] * (dz * gg[j] - (g1[j] + xh * g2[j]) * inv_n) + ee[j]) + aa[j];
+                const float xh = gn_xhat(k, j, in[j]);
+                o[j] = (gn_dx_term(k, j, xh, gn_dz(k, j, xh, dd[j], silu), g1[j], g2[j], inv_n) + ee[j]) + aa[j];
             }
             v[u] = make_float4(o[0], o[1], o[2], o[3]);
         }
@@ -449,10 +415,7 @@ __global__ void gn_bwd_apply_kernel(const float* __restrict__ x, long long ldx, 
             const int pu = p + u * r;
             if (pu < p1) {
                 if (dx) *reinterpret_cast<float4*>(ob + (long long)pu * lddx) = v[u];
-                if (dxs && cq * 4 >= dxs_c0 && cq * 4 < dxs_c1) {
-                    const float o[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-                    gn_store_split4(dxs + 2 * ((long long)b * HW + pu) * lddxs, cq * 4 - dxs_c0, o);
-                }
+                if (dxs && cq * 4 >= dxs_c0 && cq * 4 < dxs_c1) gn_store_split4(dxs + 2 * ((long long)b * HW + pu) * lddxs, cq * 4 - dxs_c0, v[u]);
             }
         }
     }
@@ -500,11 +463,6 @@ static bool gn_resident_plan(int B, int HW, int C, int G, GnRes& o, bool wide_ok
     }
     return false;
 }
-// the instantiation <EMAX, NT> of gn_fwd_res_kernel / gn_bwd_res_kernel that a resident plan launches: the smallest register array that holds E
-static void gn_res_template(const GnRes& rp, int& emax, int& nt) {
-    nt = rp.nt == 512 ? 512 : 256;
-    emax = nt == 512 ? (rp.E <= 8 ? 8 : GN_RES_EMAX) : (rp.E <= 4 ? 4 : GN_RES_EMAX);
-}
 
 // 1-D grid over (sample, channel block), remapped so that each XCD (workgroup id % 8) owns a contiguous run with the
 // channel blocks of a sample adjacent: the 64-byte row pieces of neighbouring channel blocks share 128-byte lines, and
@@ -522,11 +480,10 @@ __device__ __forceinline__ GnCoord gn_res_coord(int nblk) {
     return c;
 }
 
+// a group's statistics to LDS (st, for the apply phase) and to mean / rstd (saved for the backward)
 __device__ __forceinline__ void gn_fwd_group_stats(double a, double c2, double n, float eps, float* st, float* mean, float* rstd) {
-    const double mu = a / n;
-    double var = c2 / n - mu * mu;
-    if (var < 0.0) var = 0.0;
-    const float m = (float)mu, r = (float)(1.0 / sqrt(var + (double)eps));
+    float m, r;
+    gn_mean_rstd(a, c2, n, eps, &m, &r);
     st[0] = m; st[1] = r;
     *mean = m; *rstd = r;
 }
@@ -611,12 +568,12 @@ __global__ __launch_bounds__(NT, NT == 256 ? 4 : 2) void gn_fwd_res_kernel(const
     }
     __syncthreads();
     if (!active) return;
-    float mu[4], rs[4], gg[4], bb[4];
+    GnChan k;      // (not gn_chan: the statistics are this block's own, in LDS)
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int lc = cq * 4 + j;
-        mu[j] = st[2 * (lc / cpg)]; rs[j] = st[2 * (lc / cpg) + 1];
-        gg[j] = gamma[c0 + lc]; bb[j] = beta[c0 + lc];
+        k.mu[j] = st[2 * (lc / cpg)]; k.rs[j] = st[2 * (lc / cpg) + 1];
+        k.gg[j] = gamma[c0 + lc]; k.bb[j] = beta[c0 + lc];
     }
     float* yb = y + (long long)b * HW * ldy + c0 + cq * 4;
     // all outputs first (registers only), then the stores: with the arithmetic inside the per-element store branch hipcc
@@ -627,7 +584,7 @@ __global__ __launch_bounds__(NT, NT == 256 ? 4 : 2) void gn_fwd_res_kernel(const
         float o[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float z = (in[j] - mu[j]) * rs[j] * gg[j] + bb[j];
+            const float z = gn_affine(k, j, in[j]);
             o[j] = silu ? silu_fast_pinned(z) : z;
         }
         v[i] = make_float4(o[0], o[1], o[2], o[3]);
@@ -637,16 +594,13 @@ __global__ __launch_bounds__(NT, NT == 256 ? 4 : 2) void gn_fwd_res_kernel(const
         const int p = prow + R * i;
         if (i < E && p < HW) {
             if (y) *reinterpret_cast<float4*>(yb + (long long)p * ldy) = v[i];
-            if (ys) {
-                const float o[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
-                gn_store_split4(ys + 2 * ((long long)b * HW + p) * ldys, c0 + cq * 4, o);
-            }
+            if (ys) gn_store_split4(ys + 2 * ((long long)b * HW + p) * ldys, c0 + cq * 4, v[i]);
         }
     }
 }
 
 // backward: dx (+)= rstd * (dz*gamma - (s1 + xhat*s2)/n); per-sample per-channel (sum dz*xhat, sum dz) rows go to
-// `part` ([B][2][C], reduced over B by gn_bwd_param_kernel); optional dx_colsum[b][c] = sum over pixels of this
+// `part` ([B][2][C], reduced over B by gn_bwd_param_batched_kernel); optional dx_colsum[b][c] = sum over pixels of this
 // launch's dx term in closed form: rstd * (gamma*sum dz - (HW*s1 + s2*sum xhat)/n)   (time-embedding gradient)
 template <int EMAX, int NT>
 __global__ __launch_bounds__(NT) void gn_bwd_res_kernel(const float* __restrict__ x, long long ldx,
@@ -668,12 +622,12 @@ __global__ __launch_bounds__(NT) void gn_bwd_res_kernel(const float* __restrict_
     const int b = wgc.b, c0 = wgc.bx * cb;
     const int cpg = C / G, ng = cb / cpg;
     const float inv_n = 1.0f / ((float)HW * cpg);
-    float mu[4], rs[4], gg[4], bb[4];
+    GnChan k;      // (not gn_chan: an inactive thread reads channel c0 four times; with c0 + j hipcc merges the loads and the code changes)
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int c = c0 + (active ? cq * 4 + j : 0);
-        mu[j] = mean[b * G + c / cpg]; rs[j] = rstd[b * G + c / cpg];
-        gg[j] = gamma[c]; bb[j] = beta[c];
+        k.mu[j] = mean[b * G + c / cpg]; k.rs[j] = rstd[b * G + c / cpg];
+        k.gg[j] = gamma[c]; k.bb[j] = beta[c];
     }
     const float* xb = x + (long long)b * HW * ldx + c0 + cq * 4;
     const float* db = dy + (long long)b * HW * lddy + c0 + cq * 4;
@@ -693,9 +647,8 @@ __global__ __launch_bounds__(NT) void gn_bwd_res_kernel(const float* __restrict_
         float in[4] = {xh[i].x, xh[i].y, xh[i].z, xh[i].w}, dd[4] = {dz[i].x, dz[i].y, dz[i].z, dz[i].w};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float h = ok ? (in[j] - mu[j]) * rs[j] : 0.f;
-            float d = dd[j];
-            if (silu) d *= silu_grad_fast(h * gg[j] + bb[j]);
+            const float h = ok ? gn_xhat(k, j, in[j]) : 0.f;
+            const float d = gn_dz(k, j, h, dd[j], silu);
             in[j] = h; dd[j] = d;
             s0[j] += d; s1[j] += d * h; s2[j] += h;
         }
@@ -785,7 +738,7 @@ __global__ __launch_bounds__(NT) void gn_bwd_res_kernel(const float* __restrict_
         const float h[4] = {xh[i].x, xh[i].y, xh[i].z, xh[i].w}, d[4] = {dz[i].x, dz[i].y, dz[i].z, dz[i].w};
         float o[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = rs[j] * (d[j] * gg[j] - (g1[j] + h[j] * g2[j]) * inv_n);
+        for (int j = 0; j < 4; ++j) o[j] = gn_dx_term(k, j, h[j], d[j], g1[j], g2[j], inv_n);
         dz[i] = make_float4(o[0], o[1], o[2], o[3]);
     }
     if (dx && acc) {                      // accumulate: the existing dx values, all loads in flight at once
@@ -812,33 +765,103 @@ __global__ __launch_bounds__(NT) void gn_bwd_res_kernel(const float* __restrict_
         const int p = prow + R * i;
         if (i < E && p < HW) {
             if (dx) *reinterpret_cast<float4*>(ob + (long long)p * lddx) = dz[i];
-            if (dxs && c0 + cq * 4 >= dxs_c0 && c0 + cq * 4 < dxs_c1) {      // planes of the FINAL value, channels [dxs_c0, dxs_c1) only
-                const float o[4] = {dz[i].x, dz[i].y, dz[i].z, dz[i].w};
-                gn_store_split4(dxs + 2 * ((long long)b * HW + p) * lddxs, c0 + cq * 4 - dxs_c0, o);
-            }
+            // planes of the FINAL value, channels [dxs_c0, dxs_c1) only
+            if (dxs && c0 + cq * 4 >= dxs_c0 && c0 + cq * 4 < dxs_c1) gn_store_split4(dxs + 2 * ((long long)b * HW + p) * lddxs, c0 + cq * 4 - dxs_c0, dz[i]);
         }
     }
 }
 
+// =====================================================================================================================
+// Host: the shape predicate, the plan, the workspace layout
+// =====================================================================================================================
+// The shape predicate, in two levels: a shape these kernels are written for (what bd_gn_fwd_takes_stats / bd_gn_bwd_defers answer for), and
+// on top of it the launch limits (block <= 1024 threads, grid.y <= 65535) that the launchers and bd_gn_plan add.
+static bool gn_shape_ok(int B, int HW, int C, int G) { return B > 0 && HW > 0 && C > 0 && G > 0 && C % G == 0 && (C & 3) == 0; }
+static bool gn_launch_ok(int B, int C) { return C / 4 <= 1024 && B <= 65535; }
+// both levels for the launchers: the message names the part that failed
 static int gn_common_checks(const char* who, int B, int HW, int C, int G, const void* x, long long ldx) {
-    BD_CHECK(B > 0 && HW > 0 && C > 0 && G > 0, BD_ERR_INVALID, "%s: bad shape", who);
-    BD_CHECK(C % G == 0, BD_ERR_INVALID, "%s: C=%d not divisible by G=%d", who, C, G);
-    BD_CHECK((C & 3) == 0 && (ldx & 3) == 0 && aligned16(x), BD_ERR_UNSUPPORTED,
+    if (!gn_shape_ok(B, HW, C, G)) {
+        BD_CHECK(B > 0 && HW > 0 && C > 0 && G > 0, BD_ERR_INVALID, "%s: bad shape", who);
+        BD_CHECK(C % G == 0, BD_ERR_INVALID, "%s: C=%d not divisible by G=%d", who, C, G);
+    }
+    BD_CHECK(gn_shape_ok(B, HW, C, G) && (ldx & 3) == 0 && aligned16(x), BD_ERR_UNSUPPORTED,
              "%s: needs C and ld multiples of 4 and a 16B-aligned pointer (C=%d ld=%lld)", who, C, ldx);
-    BD_CHECK(C / 4 <= 1024, BD_ERR_UNSUPPORTED, "%s: C=%d too large", who, C);
-    BD_CHECK(B <= 65535, BD_ERR_UNSUPPORTED, "%s: B=%d too large", who, B);
+    if (!gn_launch_ok(B, C)) {
+        BD_CHECK(C / 4 <= 1024, BD_ERR_UNSUPPORTED, "%s: C=%d too large", who, C);
+        BD_CHECK(B <= 65535, BD_ERR_UNSUPPORTED, "%s: B=%d too large", who, B);
+    }
     return BD_OK;
+}
+
+constexpr int GN_MAX_SPLITS = 128;   // small batches of large images (B = 4 at 256x256) need the pixel splits to fill the chip
+static int gn_max_splits(int B) {
+    const int s = 512 / (B > 0 ? B : 1);
+    return s < 1 ? 1 : (s > GN_MAX_SPLITS ? GN_MAX_SPLITS : s);
+}
+static int gn_splits(int B, int HW) {
+    int s = gn_max_splits(B);
+    while (s > 1 && HW / s < 32) s >>= 1;
+    return s;
+}
+
+// Everything the launchers decide from a level-1 shape, decided once (DESIGN.md "GroupNorm dispatch"): bd_gn_fwd, bd_gn_bwd and the three
+// queries read it, and bd_gn_plan reports it.
+struct GnPlan {
+    int B, HW, C, G;
+    bool resident;
+    GnRes res; int emax, nt;    // resident: the slab and the <EMAX, NT> of gn_fwd_res_kernel / gn_bwd_res_kernel, the smallest register array that holds E
+    int S, threads, r, per;     // two-stage: pixel splits; threads = (C/4) * r, r pixel rows in flight; pixel rows per block of the apply kernels
+};
+static GnPlan gn_plan(int B, int HW, int C, int G, bool backward) {
+    GnPlan p = {};
+    p.B = B; p.HW = HW; p.C = C; p.G = G;
+    p.resident = gn_resident_plan(B, HW, C, G, p.res, backward);
+    if (p.resident) {
+        p.nt = p.res.nt == 512 ? 512 : 256;
+        p.emax = p.nt == 512 ? (p.res.E <= 8 ? 8 : GN_RES_EMAX) : (p.res.E <= 4 ? 4 : GN_RES_EMAX);
+        return p;
+    }
+    p.S = gn_splits(B, HW);
+    const int q = C / 4;
+    p.r = 256 / q < 1 ? 1 : 256 / q;
+    p.threads = q * p.r;
+    long long per = 16LL * p.r;     // 16 rows per thread (four / eight trips of the unrolled loop), at most 65535 blocks
+    while (cdiv(HW, per) > 65535) per *= 2;
+    p.per = (int)per;
+    return p;
+}
+// f(integral_constant EMAX, integral_constant NT) for the plan's instantiation, one of <4,256> <16,256> <8,512> <16,512>
+template <class F>
+static void gn_res_dispatch(const GnPlan& p, F&& f) {
+    using std::integral_constant;
+    if (p.nt == 512 && p.emax == 8) f(integral_constant<int, 8>{}, integral_constant<int, 512>{});
+    else if (p.nt == 512) f(integral_constant<int, GN_RES_EMAX>{}, integral_constant<int, 512>{});
+    else if (p.emax == 4) f(integral_constant<int, 4>{}, integral_constant<int, 256>{});
+    else f(integral_constant<int, GN_RES_EMAX>{}, integral_constant<int, 256>{});
+}
+
+// ---- workspace: one layout per direction; the launcher's check, its message and its pointers read these, and so does bd_gn_plan
+// forward: the two-stage statistics [B][S][G][2] fp64; resident: nothing
+static size_t gn_fwd_workspace(const GnPlan& p) { return p.resident ? 0 : gn_stats_partial_bytes(p.B, p.S, p.G); }
+// backward two-stage: the statistics rows `part` [B][S][3][C] fp32 (256-aligned), then `ds` [B][G][2] fp32; resident: the per-sample
+// parameter partials `part` [B][2][C] fp32, only when the launcher owns the parameter sums (no param_partials, dgamma / dbeta wanted)
+struct GnBwdWs { size_t ds, bytes; };   // offset of ds, total
+static GnBwdWs gn_bwd_workspace(const GnPlan& p, bool owns_params) {
+    if (p.resident) return {0, owns_params ? (size_t)p.B * p.C * 2 * sizeof(float) : 0};
+    const size_t ds = align_up((size_t)p.B * p.S * p.C * 3 * sizeof(float), 256);
+    return {ds, ds + (size_t)p.B * p.G * 2 * sizeof(float)};
 }
 
 }  // namespace bd
 
 using namespace bd;
 
+// A bound, not a need: >= gn_fwd_workspace / gn_bwd_workspace of every (HW, G) the launchers take at this (B, C), from S <= gn_max_splits(B)
+// and G <= C (tests/test_workspace_host.py).  The UNet plan's dry run sizes its op workspace with it.
 extern "C" size_t bd_gn_workspace_bytes(int B, int C) {
-    // fwd: [B][S][G<=C][2] doubles ; bwd: [B][S][3][C] floats + [B][G][2] floats
     const size_t ms = (size_t)gn_max_splits(B);
-    size_t fwd = (size_t)B * ms * (size_t)C * 2 * sizeof(double);
-    size_t bwd = (size_t)B * ms * (size_t)C * 3 * sizeof(float) + (size_t)B * C * 2 * sizeof(float) + 256;
+    const size_t fwd = gn_stats_partial_bytes(B, (int)ms, C);
+    const size_t bwd = (size_t)B * ms * (size_t)C * 3 * sizeof(float) + 256 + (size_t)B * C * 2 * sizeof(float);
     return fwd > bwd ? fwd : bwd;
 }
 
@@ -850,85 +873,68 @@ extern "C" int bd_gn_fwd(const bd_gn_fwd_desc* d, bd_stream_t stream) {
              "bd_gn_fwd: y/gamma/beta must be 16B aligned, ldy multiple of 4");
     BD_CHECK(!d->y_split || (d->C % 32 == 0 && d->ldys % 32 == 0 && ((uintptr_t)d->y_split & 127) == 0), BD_ERR_UNSUPPORTED,
              "bd_gn_fwd: y_split needs C %% 32 == 0, ldys %% 32 == 0 and a 128-byte aligned base");
-    GnRes rp;
-    if (gn_resident_plan(d->B, d->HW, d->C, d->G, rp)) {
-        const dim3 grid((unsigned)rp.nblk * (unsigned)d->B);
+    const GnPlan p = gn_plan(d->B, d->HW, d->C, d->G, false);
+    const size_t need = gn_fwd_workspace(p);
+    BD_CHECK(d->workspace_bytes >= need, BD_ERR_WORKSPACE, "bd_gn_fwd: workspace %zu < %zu", d->workspace_bytes, need);
+    if (p.resident) {
+        const dim3 grid((unsigned)p.res.nblk * (unsigned)d->B);
         int rec = -1;       // round 6: the resident GroupNorm launches are profiled classes too (REQUIRED bytes: x in, y and / or planes out)
         if (prof_on())
             rec = prof_begin("gn_fwd_res", 0.0, (double)d->B * d->HW * d->C * 4.0 * (1.0 + (d->y ? 1.0 : 0.0) + (d->y_split ? 1.0 : 0.0)), S(stream));
-#define BD_GN_FWD_RES(EM, NT)                                                                                              \
-    hipLaunchKernelGGL((gn_fwd_res_kernel<EM, NT>), grid, dim3(NT), 0, S(stream), d->x, (long long)d->ldx, d->y,             \
-                       (long long)d->ldy, d->HW, d->C, d->G, rp.cb, rp.q, rp.R, rp.E, d->eps, d->gamma, d->beta, d->mean,       \
-                       d->rstd, d->silu, d->y_split, (long long)d->ldys)
-        int em, nt;
-        gn_res_template(rp, em, nt);
-        if (nt == 512 && em == 8) BD_GN_FWD_RES(8, 512);
-        else if (nt == 512) BD_GN_FWD_RES(GN_RES_EMAX, 512);
-        else if (em == 4) BD_GN_FWD_RES(4, 256);
-        else BD_GN_FWD_RES(GN_RES_EMAX, 256);
-#undef BD_GN_FWD_RES
+        gn_res_dispatch(p, [&](auto em, auto nt) {
+            constexpr int EM = decltype(em)::value, NT = decltype(nt)::value;
+            hipLaunchKernelGGL((gn_fwd_res_kernel<EM, NT>), grid, dim3(NT), 0, S(stream), d->x, (long long)d->ldx, d->y, (long long)d->ldy,
+                               d->HW, d->C, d->G, p.res.cb, p.res.q, p.res.R, p.res.E, d->eps, d->gamma, d->beta, d->mean, d->rstd, d->silu,
+                               d->y_split, (long long)d->ldys);
+        });
         BD_LAUNCH_CHECK("gn_fwd_res");
         prof_end(rec, S(stream));
         return BD_OK;
     }
-    const int S_ = gn_splits(d->B, d->HW);
-    const size_t need = (size_t)d->B * S_ * d->G * 2 * sizeof(double);
-    BD_CHECK(d->workspace_bytes >= need, BD_ERR_WORKSPACE, "bd_gn_fwd: workspace %zu < %zu", d->workspace_bytes, need);
-    int threads, r;
-    gn_block(d->C, threads, r);
     const double* part = reinterpret_cast<double*>(d->workspace);
-    int Sf = S_;
+    int Sf = p.S;
     if (d->stats) {           // round 4: the producer of x left the partials (bd_conv3x3_ps gn_part): no pass over x
         BD_CHECK(d->stats_splits > 0, BD_ERR_INVALID, "bd_gn_fwd: stats without stats_splits");
         part = d->stats; Sf = d->stats_splits;
     } else {
-        hipLaunchKernelGGL(gn_stats_kernel, dim3(S_, d->B), dim3(threads), (size_t)r * d->C * 2 * sizeof(float), S(stream), d->x,
-                           (long long)d->ldx, d->HW, d->C, d->G, r, S_, reinterpret_cast<double*>(d->workspace));
+        hipLaunchKernelGGL(gn_stats_kernel, dim3(p.S, d->B), dim3(p.threads), (size_t)p.r * d->C * 2 * sizeof(float), S(stream), d->x,
+                           (long long)d->ldx, d->HW, d->C, d->G, p.r, p.S, reinterpret_cast<double*>(d->workspace));
         BD_LAUNCH_CHECK("gn_stats");
     }
-    {
-        const int per = gn_apply_rows(d->HW, r);
-        hipLaunchKernelGGL(gn_fwd_finalize_kernel, dim3(d->B), dim3(256), 0, S(stream), part, d->G, Sf,
-                           (double)d->HW * (d->C / d->G), d->eps, d->mean, d->rstd);
-        hipLaunchKernelGGL(gn_apply_kernel, dim3((unsigned)cdiv(d->HW, per), d->B), dim3(threads), 0, S(stream), d->x,
-                           (long long)d->ldx, d->y, (long long)d->ldy, d->HW, d->C, d->G, r, per, d->gamma, d->beta, d->mean,
-                           d->rstd, d->silu, d->y_split, (long long)d->ldys);
-    }
+    hipLaunchKernelGGL(gn_fwd_finalize_kernel, dim3(d->B), dim3(256), 0, S(stream), part, d->G, Sf, (double)d->HW * (d->C / d->G), d->eps,
+                       d->mean, d->rstd);
+    hipLaunchKernelGGL(gn_apply_kernel, dim3((unsigned)cdiv(d->HW, p.per), d->B), dim3(p.threads), 0, S(stream), d->x, (long long)d->ldx,
+                       d->y, (long long)d->ldy, d->HW, d->C, d->G, p.r, p.per, d->gamma, d->beta, d->mean, d->rstd, d->silu, d->y_split,
+                       (long long)d->ldys);
     BD_LAUNCH_CHECK("gn_apply");
     return BD_OK;
 }
 
 extern "C" int bd_gn_fwd_takes_stats(int B, int HW, int C, int G) {
-    GnRes rp;
-    return B > 0 && HW > 0 && C > 0 && G > 0 && C % G == 0 && (C & 3) == 0 && !gn_resident_plan(B, HW, C, G, rp) ? 1 : 0;
+    return gn_shape_ok(B, HW, C, G) && !gn_plan(B, HW, C, G, false).resident ? 1 : 0;
 }
 
 extern "C" int bd_gn_bwd_defers(int B, int HW, int C, int G) {
     // round 4: both the resident and the large-image path leave per-sample partials to the caller
-    return B > 0 && HW > 0 && C > 0 && G > 0 && C % G == 0 && (C & 3) == 0 ? 1 : 0;
+    return gn_shape_ok(B, HW, C, G) ? 1 : 0;
 }
 
 extern "C" int bd_gn_plan(int B, int HW, int C, int G, int backward, bd_gn_plan_info* out) {
-    // host only: the functions bd_gn_fwd / bd_gn_bwd call to choose their kernels, nothing else
+    // host only: what bd_gn_fwd / bd_gn_bwd themselves read to choose their kernels and lay their workspace out, nothing else
     BD_CHECK(out, BD_ERR_INVALID, "bd_gn_plan: null output");
-    BD_CHECK(B > 0 && HW > 0 && C > 0 && G > 0 && C % G == 0 && (C & 3) == 0 && C / 4 <= 1024 && B <= 65535, BD_ERR_INVALID,
+    BD_CHECK(gn_shape_ok(B, HW, C, G) && gn_launch_ok(B, C), BD_ERR_INVALID,
              "bd_gn_plan: not a shape bd_gn_fwd / bd_gn_bwd take (B=%d HW=%d C=%d G=%d)", B, HW, C, G);
+    const GnPlan p = gn_plan(B, HW, C, G, backward != 0);
     *out = bd_gn_plan_info{};
-    GnRes rp;
-    if (gn_resident_plan(B, HW, C, G, rp, backward != 0)) {
-        out->resident = 1;
-        out->cb = rp.cb; out->q = rp.q; out->R = rp.R; out->E = rp.E;
-        gn_res_template(rp, out->emax, out->nt);
-        return BD_OK;
-    }
-    out->S = gn_splits(B, HW);
-    gn_block(C, out->threads, out->r);
-    out->per = gn_apply_rows(HW, out->r);
+    out->resident = p.resident;
+    out->nt = p.nt; out->cb = p.res.cb; out->q = p.res.q; out->R = p.res.R; out->E = p.res.E; out->emax = p.emax;
+    out->S = p.S; out->threads = p.threads; out->r = p.r; out->per = p.per;
+    out->workspace_bytes = backward ? gn_bwd_workspace(p, true).bytes : gn_fwd_workspace(p);
     return BD_OK;
 }
 
-extern "C" int bd_gn_bwd_params(const bd_gn_param_item* items, int n, int B, bd_stream_t stream) {
-    BD_CHECK(items && n > 0 && B > 0, BD_ERR_INVALID, "bd_gn_bwd_params: bad arguments");
+// dgamma / dbeta of n layers from `rows` partial rows each (row stride planes * C floats), GN_PARAM_MAX layers per launch
+static int gn_fold_params(const bd_gn_param_item* items, int n, int rows, int planes, hipStream_t st) {
     for (int i0 = 0; i0 < n; i0 += GN_PARAM_MAX) {
         GnParamTable t;
         t.n = n - i0 < GN_PARAM_MAX ? n - i0 : GN_PARAM_MAX;
@@ -936,14 +942,19 @@ extern "C" int bd_gn_bwd_params(const bd_gn_param_item* items, int n, int B, bd_
         for (int i = 0; i < t.n; ++i) {
             const bd_gn_param_item& it = items[i0 + i];
             BD_CHECK(it.partials && it.dgamma && it.dbeta && it.C > 0, BD_ERR_INVALID, "bd_gn_bwd_params: item %d", i0 + i);
-            t.part[i] = it.partials; t.dg[i] = it.dgamma; t.db[i] = it.dbeta; t.C[i] = it.C; t.blk0[i] = blk;
+            t.part[i] = it.partials; t.dg[i] = it.dgamma; t.db[i] = it.dbeta; t.C[i] = it.C; t.stride[i] = planes * it.C; t.blk0[i] = blk;
             blk += (int)cdiv(2 * it.C, 64);
         }
         t.blk0[t.n] = blk;
-        hipLaunchKernelGGL(gn_bwd_param_batched_kernel, dim3((unsigned)blk), dim3(1024), 0, S(stream), t, B);
+        hipLaunchKernelGGL(gn_bwd_param_batched_kernel, dim3((unsigned)blk), dim3(1024), 0, st, t, rows);
         BD_LAUNCH_CHECK("gn_bwd_param_batched");
     }
     return BD_OK;
+}
+
+extern "C" int bd_gn_bwd_params(const bd_gn_param_item* items, int n, int B, bd_stream_t stream) {
+    BD_CHECK(items && n > 0 && B > 0, BD_ERR_INVALID, "bd_gn_bwd_params: bad arguments");
+    return gn_fold_params(items, n, B, 2, S(stream));
 }
 
 extern "C" int bd_gn_bwd(const bd_gn_bwd_desc* d, bd_stream_t stream) {
@@ -964,64 +975,43 @@ extern "C" int bd_gn_bwd(const bd_gn_bwd_desc* d, bd_stream_t stream) {
                  aligned16(d->beta), BD_ERR_UNSUPPORTED, "bd_gn_bwd: pointers must be 16B aligned, ld multiples of 4");
     BD_CHECK(!(d->dx_colsum && (d->accumulate_dx || d->dx_add)), BD_ERR_INVALID, "bd_gn_bwd: dx_colsum is the column sum of this launch's dx term alone");
     BD_CHECK(!d->dx_add || (d->dx && (d->ld_add & 3) == 0 && aligned16(d->dx_add)), BD_ERR_INVALID, "bd_gn_bwd: dx_add needs dx, a 16B-aligned pointer and ld_add %% 4 == 0");
-    GnRes rp;
-    if (gn_resident_plan(d->B, d->HW, d->C, d->G, rp, true)) {
-        const size_t need_r = d->param_partials || no_params ? 0 : (size_t)d->B * d->C * 2 * sizeof(float);
-        BD_CHECK(d->workspace_bytes >= need_r, BD_ERR_WORKSPACE, "bd_gn_bwd: workspace %zu < %zu", d->workspace_bytes, need_r);
-        float* part_r = d->param_partials ? d->param_partials : (no_params ? nullptr : reinterpret_cast<float*>(d->workspace));
-        const dim3 grid((unsigned)rp.nblk * (unsigned)d->B);
+    const GnPlan p = gn_plan(d->B, d->HW, d->C, d->G, true);
+    const bool owns_params = !d->param_partials && !no_params;   // else the caller folds them (bd_gn_bwd_params) / nobody wants them
+    const GnBwdWs ws = gn_bwd_workspace(p, owns_params);
+    BD_CHECK(d->workspace_bytes >= ws.bytes, BD_ERR_WORKSPACE, "bd_gn_bwd: workspace %zu < %zu", d->workspace_bytes, ws.bytes);
+    float* part = reinterpret_cast<float*>(d->workspace);
+    float* ds = reinterpret_cast<float*>(reinterpret_cast<char*>(d->workspace) + ws.ds);
+    const bd_gn_param_item own = {part, d->C, d->dgamma, d->dbeta};
+    if (p.resident) {
+        float* part_r = d->param_partials ? d->param_partials : (no_params ? nullptr : part);
+        const dim3 grid((unsigned)p.res.nblk * (unsigned)d->B);
         int rec = -1;       // REQUIRED bytes of this call: x and dy in (+ the dx it accumulates into, + the added gradient), dx and / or its planes out
         if (prof_on())
             rec = prof_begin("gn_bwd_res", 0.0, (double)d->B * d->HW * 4.0 * ((double)d->C * (2.0 + (d->accumulate_dx ? 1.0 : 0.0) + (d->dx_add ? 1.0 : 0.0) +
                              (d->dx ? 1.0 : 0.0)) + (d->dx_split ? (double)(xs1 - xs0) : 0.0)), S(stream));
-#define BD_GN_BWD_RES(EM, NT)                                                                                              \
-    hipLaunchKernelGGL((gn_bwd_res_kernel<EM, NT>), grid, dim3(NT), 0, S(stream), d->x, (long long)d->ldx, d->dy,            \
-                       (long long)d->lddy, d->dx, (long long)d->lddx, d->HW, d->C, d->G, rp.cb, rp.q, rp.R, rp.E, d->gamma,     \
-                       d->beta, d->mean, d->rstd, d->silu, d->accumulate_dx, part_r, d->dx_colsum, (long long)d->ld_colsum, \
-                       d->dx_split, (long long)d->lddxs, d->dx_add, (long long)d->ld_add, xs0, xs1)
-        int em, nt;
-        gn_res_template(rp, em, nt);
-        if (nt == 512 && em == 8) BD_GN_BWD_RES(8, 512);
-        else if (nt == 512) BD_GN_BWD_RES(GN_RES_EMAX, 512);
-        else if (em == 4) BD_GN_BWD_RES(4, 256);
-        else BD_GN_BWD_RES(GN_RES_EMAX, 256);
-#undef BD_GN_BWD_RES
+        gn_res_dispatch(p, [&](auto em, auto nt) {
+            constexpr int EM = decltype(em)::value, NT = decltype(nt)::value;
+            hipLaunchKernelGGL((gn_bwd_res_kernel<EM, NT>), grid, dim3(NT), 0, S(stream), d->x, (long long)d->ldx, d->dy, (long long)d->lddy,
+                               d->dx, (long long)d->lddx, d->HW, d->C, d->G, p.res.cb, p.res.q, p.res.R, p.res.E, d->gamma, d->beta, d->mean,
+                               d->rstd, d->silu, d->accumulate_dx, part_r, d->dx_colsum, (long long)d->ld_colsum, d->dx_split,
+                               (long long)d->lddxs, d->dx_add, (long long)d->ld_add, xs0, xs1);
+        });
         BD_LAUNCH_CHECK("gn_bwd_res");
         prof_end(rec, S(stream));
-        if (d->param_partials || no_params) return BD_OK;   // the caller folds them (bd_gn_bwd_params) / nobody wants them
-        hipLaunchKernelGGL(gn_bwd_param_kernel, dim3((unsigned)cdiv(2 * d->C, 64)), dim3(1024), 0, S(stream), part_r, d->B, 2 * d->C,
-                           d->C, d->dgamma, d->dbeta);
-        BD_LAUNCH_CHECK("gn_bwd_param");
-        return BD_OK;
+        return owns_params ? gn_fold_params(&own, 1, d->B, 2, S(stream)) : BD_OK;       // rows [B][2][C]
     }
-    const int S_ = gn_splits(d->B, d->HW);
-    const size_t part_bytes = align_up((size_t)d->B * S_ * d->C * 3 * sizeof(float), 256);
-    const size_t need = part_bytes + (size_t)d->B * d->G * 2 * sizeof(float);
-    BD_CHECK(d->workspace_bytes >= need, BD_ERR_WORKSPACE, "bd_gn_bwd: workspace %zu < %zu", d->workspace_bytes, need);
-    float* part = reinterpret_cast<float*>(d->workspace);
-    float* ds = reinterpret_cast<float*>(reinterpret_cast<char*>(d->workspace) + part_bytes);
-    int threads, r;
-    gn_block(d->C, threads, r);
-    hipLaunchKernelGGL(gn_bwd_stats_kernel, dim3(S_, d->B), dim3(threads), (size_t)r * d->C * 3 * sizeof(float), S(stream), d->x,
-                       (long long)d->ldx, d->dy, (long long)d->lddy, d->HW, d->C, d->G, r, S_, d->gamma, d->beta, d->mean,
-                       d->rstd, d->silu, part);
+    hipLaunchKernelGGL(gn_bwd_stats_kernel, dim3(p.S, d->B), dim3(p.threads), (size_t)p.r * d->C * 3 * sizeof(float), S(stream), d->x,
+                       (long long)d->ldx, d->dy, (long long)d->lddy, d->HW, d->C, d->G, p.r, p.S, d->gamma, d->beta, d->mean, d->rstd,
+                       d->silu, part);
     BD_LAUNCH_CHECK("gn_bwd_stats");
-    if (!d->param_partials && !no_params) {
-        hipLaunchKernelGGL(gn_bwd_param_kernel, dim3((unsigned)cdiv(2 * d->C, 64)), dim3(1024), 0, S(stream), part, d->B * S_, 3 * d->C,
-                           d->C, d->dgamma, d->dbeta);
-        BD_LAUNCH_CHECK("gn_bwd_param");
-    }
-    {
-        const int per = gn_apply_rows(d->HW, r);
-        const float inv_n = 1.0f / ((float)d->HW * (d->C / d->G));
-        hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(d->B, (unsigned)d->G), dim3(256), (size_t)(256 + 3 * (d->C / d->G) + 2) * sizeof(double),
-                           S(stream), part, d->HW, d->C, d->G, S_, d->gamma, d->rstd, inv_n, ds, d->dx_colsum, (long long)d->ld_colsum,
-                           d->param_partials);
-        hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3((unsigned)cdiv(d->HW, per), d->B), dim3(threads), 0, S(stream), d->x,
-                           (long long)d->ldx, d->dy, (long long)d->lddy, d->dx, (long long)d->lddx, d->HW, d->C, d->G, r, per, ds,
-                           d->gamma, d->beta, d->mean, d->rstd, inv_n, d->silu, d->accumulate_dx, d->dx_split,
-                           (long long)d->lddxs, d->dx_add, (long long)d->ld_add, xs0, xs1);
-    }
+    if (owns_params) BD_TRY(gn_fold_params(&own, 1, d->B * p.S, 3, S(stream)));          // rows [B*S][3][C]
+    const float inv_n = 1.0f / ((float)d->HW * (d->C / d->G));
+    hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(d->B, (unsigned)d->G), dim3(256), (size_t)(256 + 3 * (d->C / d->G) + 2) * sizeof(double),
+                       S(stream), part, d->HW, d->C, d->G, p.S, d->gamma, d->rstd, inv_n, ds, d->dx_colsum, (long long)d->ld_colsum,
+                       d->param_partials);
+    hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3((unsigned)cdiv(d->HW, p.per), d->B), dim3(p.threads), 0, S(stream), d->x, (long long)d->ldx,
+                       d->dy, (long long)d->lddy, d->dx, (long long)d->lddx, d->HW, d->C, d->G, p.r, p.per, ds, d->gamma, d->beta, d->mean,
+                       d->rstd, inv_n, d->silu, d->accumulate_dx, d->dx_split, (long long)d->lddxs, d->dx_add, (long long)d->ld_add, xs0, xs1);
     BD_LAUNCH_CHECK("gn_bwd_apply");
     return BD_OK;
 }

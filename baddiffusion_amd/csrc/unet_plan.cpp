@@ -560,7 +560,7 @@ struct bd_unet {
         d.workspace = c.opws; d.workspace_bytes = c.opws_bytes; d.mode = cfg.compute_mode;
         if (e.gn_splits > 0) {
             d.gn_part = reinterpret_cast<double*>(c.opws); d.gn_groups = cfg.norm_num_groups;
-            if (c.dry) need(c, (size_t)c.B * e.gn_splits * d.gn_groups * 2 * sizeof(double));
+            if (c.dry) need(c, gn_stats_partial_bytes(c.B, e.gn_splits, d.gn_groups));
         }
         if (c.dry) { note_conv(c); return BD_OK; }
         return conv3x3_ps(d, c.st);

@@ -150,7 +150,9 @@ int bd_timestep_embedding(const int64_t* t, int t_stride, int B, int dim, int fl
 /* ------------------------------------------------------------------------------------------------
  * GroupNorm (+ optional SiLU) over NHWC(ld).  Replaces nn.GroupNorm + F.silu at resnet.py:559,591,
  * attention.py:125, unet_2d.py:312-313 and their autograd backward.
- * Workspace: bd_gn_workspace_bytes(B, C).  mean/rstd are [B, G] fp32 outputs saved for backward.
+ * Workspace: bd_gn_workspace_bytes(B, C), a bound: at least what bd_gn_fwd and bd_gn_bwd need for any (HW, G) they take at that
+ * (B, C); the exact need of one shape and direction is bd_gn_plan(...).workspace_bytes.  mean/rstd are [B, G] fp32 outputs saved
+ * for backward.
  * ------------------------------------------------------------------------------------------------ */
 typedef struct {
     int B, HW, C, G; float eps; int silu;
@@ -207,8 +209,9 @@ typedef struct {
 /* dgamma[c] / dbeta[c] = sum over the B samples of the partials, fixed order, for n layers in one launch
  * (the reduction over the batch of aten::native_group_norm_backward's weight / bias gradients, resnet.py:559,591) */
 int bd_gn_bwd_params(const bd_gn_param_item* items, int n, int B, bd_stream_t stream);
-/* Which kernels bd_gn_fwd (backward == 0) / bd_gn_bwd (backward != 0) launch for a shape: host code only, computed by the functions the
- * launchers themselves call.  For tests and tools that must know which branch a shape takes (DESIGN.md "GroupNorm dispatch"). */
+/* Which kernels bd_gn_fwd (backward == 0) / bd_gn_bwd (backward != 0) launch for a shape and the workspace they need: host code only, a
+ * copy of the plan and the workspace layout the launchers themselves read.  For tests and tools that must know which branch a shape takes
+ * (DESIGN.md "GroupNorm dispatch").  BD_ERR_INVALID for a shape the launchers do not take. */
 typedef struct {
     int resident;                   /* 1: one workgroup per (sample, channel block) holds its slab in registers; 0: the two-stage kernels */
     int nt, cb, q, R, E, emax;      /* resident: threads per workgroup, channels per block, float4 per pixel row (cb / 4), pixel rows in
@@ -216,6 +219,10 @@ typedef struct {
                                        instantiation launched (4, 8 or 16); 0 otherwise */
     int S, threads, r, per;         /* two-stage: pixel splits of the statistics pass, threads per workgroup ((C / 4) * r), pixel rows in
                                        flight, pixel rows per block of the apply kernels; 0 otherwise */
+    size_t workspace_bytes;         /* what the launcher asks of desc.workspace_bytes: forward two-stage [B][S][G][2] fp64 (0 resident); backward
+                                       two-stage [B][S][3][C] fp32 rounded up to 256 + [B][G][2] fp32; backward resident [B][2][C] fp32 when the
+                                       launcher owns the parameter sums (dgamma / dbeta set, no param_partials), which is what is reported here: the
+                                       largest of the descriptor's variants (0 with param_partials or without dgamma / dbeta) */
 } bd_gn_plan_info;
 int bd_gn_plan(int B, int HW, int C, int G, int backward, bd_gn_plan_info* out);
 

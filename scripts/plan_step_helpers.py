@@ -6,7 +6,9 @@ Every sub-command works on the tree in the CURRENT DIRECTORY (its baddiffusion_a
                         bd_unet_num_params, every bd_unet_param_info row and every bd_unet_segment_range_k
   dump OUTDIR           on the GPU: prediction, loss, flat gradient and dx of seeded forwards + backwards (whole, input-gradient with and
                         without weight gradients, segment by segment under the deferred join) as tensors, plus the launch census
-  compare A B OUT.json  A, B: two `plans` files (exact equality) or two `dump` folders (torch.equal tensor by tensor, census class by class)
+  gnplans OUT.json      no device needed: bd_gn_plan (both directions), bd_gn_fwd_takes_stats, bd_gn_bwd_defers and bd_gn_workspace_bytes on a
+                        grid of shapes that holds every dispatch branch and the shapes the launchers turn away
+  compare A B OUT.json  A, B: two `plans` or `gnplans` files (exact equality) or two `dump` folders (torch.equal tensor by tensor, census class by class)
   symbols LIB_A LIB_B OUT.json   the exported bd_* symbols of two builds (nm -D)
   speed PARENT OUT.json [N]      on the GPU: N (default 3) alternating windows parent / this tree of the bench.py CIFAR step, each in a child
                                  process of its own under a time limit; stops at the first failing window
@@ -57,6 +59,32 @@ def plans(out):
     knobs = {k: os.environ[k] for k in ("BD_GSPLIT", "BD_SHORTCUT_SP", "BD_CONV_PS", "BD_FWD_PIPES_MINPX") if k in os.environ}
     json.dump({"knobs": knobs, "plans": rows}, open(out, "w"))
     print(f"{len(rows)} plans -> {out}")
+
+
+GN_B = (1, 2, 3, 4, 5, 40, 128, 170, 171, 256, 257, 513, 515, 2048, 65535, 65536)
+GN_HW = (16, 64, 256, 900, 1024, 2000, 4096, 4100, 65536)
+GN_CG = ((24, 6), (64, 32), (96, 8), (128, 32), (256, 2), (256, 32), (384, 32), (512, 32), (768, 32), (1024, 32), (4096, 32), (4100, 4), (130, 32),
+         (126, 6))
+GN_FIELDS = ("resident", "nt", "cb", "q", "R", "E", "emax", "S", "threads", "r", "per")     # (workspace_bytes came later: not compared)
+
+
+def gnplans(out):
+    """host-only: the GroupNorm queries, return codes of the rejected shapes included"""
+    from baddiffusion_amd import _lib as L
+    lib = L.load()
+    rows = {}
+    for B in GN_B:
+        for HW in GN_HW:
+            for Cc, G in GN_CG:
+                row = {"takes_stats": lib.bd_gn_fwd_takes_stats(B, HW, Cc, G), "defers": lib.bd_gn_bwd_defers(B, HW, Cc, G),
+                       "workspace_bound": lib.bd_gn_workspace_bytes(B, Cc)}
+                for backward in (0, 1):
+                    p = L.GnPlanInfo()
+                    rc = lib.bd_gn_plan(B, HW, Cc, G, backward, C.byref(p))
+                    row[f"plan{backward}"] = [rc] + [getattr(p, f) for f in GN_FIELDS]
+                rows[f"B{B}|HW{HW}|C{Cc}|G{G}"] = row
+    json.dump({"knobs": {}, "plans": rows}, open(out, "w"))
+    print(f"{len(rows)} shapes -> {out}")
 
 
 # (topology, mode, B): what each one reaches is listed in profiles/plan_step_helpers.json
@@ -152,7 +180,8 @@ def compare(a, b, out):
         bad = [k for k in keys if A["plans"].get(k) != B["plans"].get(k)]
         same_knobs = A["knobs"] == B["knobs"]      # two sweeps under different knobs do not compare: counts as a mismatch
         rep = {"knobs": A["knobs"], "same_knobs": same_knobs, "plans": len(keys), "mismatches": len(bad) + (0 if same_knobs else 1), "mismatching": bad[:20],
-               "param_rows": sum(len(v["params"]) for v in A["plans"].values()), "segment_ranges": sum(len(v["segments"]) for v in A["plans"].values())}
+               "param_rows": sum(len(v.get("params", ())) for v in A["plans"].values()),
+               "segment_ranges": sum(len(v.get("segments", ())) for v in A["plans"].values())}
     else:
         import torch
         rep = {"rows": {}, "census": {}}
@@ -245,4 +274,4 @@ def speed(parent, out, rounds=3):
 
 if __name__ == "__main__":
     cmd = sys.argv[1]
-    sys.exit({"plans": plans, "dump": dump, "compare": compare, "symbols": symbols, "speed": speed}[cmd](*sys.argv[2:]) or 0)
+    sys.exit({"plans": plans, "gnplans": gnplans, "dump": dump, "compare": compare, "symbols": symbols, "speed": speed}[cmd](*sys.argv[2:]) or 0)

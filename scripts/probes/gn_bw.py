@@ -50,8 +50,10 @@ def run(B, HW, Cc, G=32, planes=True, reps=20):
     tf = timed(lambda: L.check(lib.bd_gn_fwd(C.byref(f), st), "fwd"))
     tb = timed(lambda: L.check(lib.bd_gn_bwd(C.byref(b), st), "bwd"))
     n = B * HW * Cc * 4
-    resident = bool(lib.bd_gn_resident(B, HW, Cc, G)) if hasattr(lib, "bd_gn_resident") else None
-    return tf, tb, n, resident
+    plan = [L.GnPlanInfo(), L.GnPlanInfo()]        # forward, backward
+    for backward in (0, 1):
+        L.check(lib.bd_gn_plan(B, HW, Cc, G, backward, C.byref(plan[backward])), "plan")
+    return tf, tb, n, "/".join("resident" if p.resident else "two-stage" for p in plan)
 
 
 SHAPES = {
@@ -68,10 +70,10 @@ SHAPES = {
 
 if __name__ == "__main__":
     which = sys.argv[1:] or ["cifar", "sample", "celeba"]
-    print(f"{'set':8s} {'B':>4s} {'HW':>6s} {'C':>5s} {'MB':>7s} | {'fwd us':>8s} {'GB/s(2x)':>9s} {'GB/s(3x)':>9s} | {'bwd us':>8s} {'GB/s(4x)':>9s} {'GB/s(6x)':>9s}")
+    print(f"{'set':8s} {'B':>4s} {'HW':>6s} {'C':>5s} {'MB':>7s} | {'fwd us':>8s} {'GB/s(2x)':>9s} {'GB/s(3x)':>9s} | {'bwd us':>8s} {'GB/s(4x)':>9s} {'GB/s(6x)':>9s} | fwd/bwd path")
     for w in which:
         for (B, HW, Cc) in SHAPES[w]:
             tf, tb, n, res = run(B, HW, Cc, reps=2 if w == "pmc" else 20)
             # forward: 2x = x once + planes; 3x = x twice + planes (large-image path).  backward: 4x = x, dy, dx, planes; 6x = x, dy twice
             print(f"{w:8s} {B:4d} {HW:6d} {Cc:5d} {n / 1e6:7.1f} | {tf:8.1f} {2 * n / tf / 1e3:9.0f} {3 * n / tf / 1e3:9.0f} | "
-                  f"{tb:8.1f} {4 * n / tb / 1e3:9.0f} {6 * n / tb / 1e3:9.0f}", flush=True)
+                  f"{tb:8.1f} {4 * n / tb / 1e3:9.0f} {6 * n / tb / 1e3:9.0f} | {res}", flush=True)

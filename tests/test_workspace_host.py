@@ -1,7 +1,8 @@
 """CPU: the four K-split launchers (bd_conv3x3_ps, bd_conv3x3_ps_wgrad, bd_igemm, bd_gemm_sp) size their workspace exactly as their
-bd_*_workspace_bytes functions report it.  Each case hands the launcher one byte less than the reported size: the call must be turned
-away with BD_ERR_WORKSPACE, and the need it prints must be the reported size.  The check comes before any launch, so no GPU is involved;
-no call here is ever made with a sufficient workspace (the pointers are fake)."""
+bd_*_workspace_bytes functions report it, and the GroupNorm launchers (bd_gn_fwd, bd_gn_bwd) as bd_gn_plan reports it.  Each case hands
+the launcher one byte less than the reported size: the call must be turned away with BD_ERR_WORKSPACE, and the need it prints must be
+the reported size.  The check comes before any launch, so no GPU is involved; no call here is ever made with a sufficient workspace (the
+pointers are fake).  bd_gn_workspace_bytes(B, C) is a bound over (HW, G), and is tested as one."""
 import ctypes
 import re
 
@@ -88,3 +89,81 @@ def test_a_colsum_rows_lie_behind_the_igemm_slabs(lib):
     plain = lib.bd_igemm_workspace_bytes(ctypes.byref(igemm(L, 4, 4, 512, False)))
     with_rows = lib.bd_igemm_workspace_bytes(ctypes.byref(igemm(L, 4, 4, 512, True)))
     assert plain == 2 * 4 * 4 * 4 and with_rows == plain + 2 * 4 * 4
+
+
+# ---- GroupNorm: the launchers read the layout that bd_gn_plan reports (groupnorm.hip gn_fwd_workspace / gn_bwd_workspace) ----------------
+def gn_plan(L, lib, B, HW, Cc, G, backward):
+    p = L.GnPlanInfo()
+    assert lib.bd_gn_plan(B, HW, Cc, G, backward, ctypes.byref(p)) == 0, lib.bd_last_error()
+    return p
+
+
+def gn_desc(L, B, HW, Cc, G, backward, params=True, partials=False):
+    if not backward:
+        return L.GnFwdDesc(B=B, HW=HW, C=Cc, G=G, eps=1e-5, silu=1, x=P[0], ldx=Cc, gamma=P[1], beta=P[2], y=P[3], ldy=Cc, mean=P[4], rstd=P[5],
+                           workspace=P[0])
+    return L.GnBwdDesc(B=B, HW=HW, C=Cc, G=G, silu=1, x=P[0], ldx=Cc, gamma=P[1], beta=P[2], mean=P[3], rstd=P[4], dy=P[5], lddy=Cc, dx=P[0],
+                       lddx=Cc, dgamma=P[1] if params else None, dbeta=P[2] if params else None, workspace=P[3],
+                       param_partials=P[4] if partials else None)
+
+
+# (id, B, HW, C, G, backward, resident, the need worked out by hand from the layout in include/bd_hip.h)
+GN_CASES = [
+    ("gn_fwd two-stage", 2, 1024, 384, 32, 0, 0, 2 * 32 * 32 * 2 * 8),                           # S = 32: [B][S][G][2] fp64
+    ("gn_bwd two-stage", 2, 1024, 384, 32, 1, 0, 2 * 32 * 384 * 3 * 4 + 2 * 32 * 2 * 4),        # [B][S][3][C] fp32 (1152 x 256) + [B][G][2] fp32
+    ("gn_bwd two-stage S = 12", 40, 1024, 96, 8, 1, 0, 40 * 12 * 96 * 3 * 4 + 40 * 8 * 2 * 4),  # 552960 = 2160 x 256, then ds
+    # S = 102 (512 // 5), 24 channels: the statistics rows are 5 * 102 * 24 * 3 * 4 = 146880 bytes = 573.75 x 256, so ds starts at 574 x 256
+    ("gn_bwd two-stage, rounded rows", 5, 4096, 24, 6, 1, 0, 574 * 256 + 5 * 6 * 2 * 4),
+    ("gn_bwd resident", 3, 64, 128, 32, 1, 1, 3 * 128 * 2 * 4),                                   # [B][2][C] fp32: the launcher folds the sums
+]
+
+
+@pytest.mark.parametrize("name,B,HW,Cc,G,backward,resident,by_hand", GN_CASES, ids=[c[0] for c in GN_CASES])
+def test_gn_launcher_needs_what_its_plan_reports(lib, name, B, HW, Cc, G, backward, resident, by_hand):
+    L, lib = lib
+    p = gn_plan(L, lib, B, HW, Cc, G, backward)
+    assert p.resident == resident and p.workspace_bytes == by_hand > 0, (name, p.resident, p.workspace_bytes, by_hand)
+    d = gn_desc(L, B, HW, Cc, G, backward)
+    d.workspace_bytes = p.workspace_bytes - 1
+    status = (lib.bd_gn_bwd if backward else lib.bd_gn_fwd)(ctypes.byref(d), None)
+    msg = lib.bd_last_error()
+    assert status == BD_ERR_WORKSPACE, (name, status, msg)
+    m = re.search(rb"workspace (\d+) < (\d+)", msg or b"")
+    assert m, (name, msg)
+    print(name, "plan", p.workspace_bytes, "launcher was given", int(m.group(1)), "and needs", int(m.group(2)))
+    assert int(m.group(1)) == p.workspace_bytes - 1 and int(m.group(2)) == p.workspace_bytes, (name, msg)
+
+
+def test_gn_resident_needs_a_workspace_only_for_the_sums_it_owns(lib):
+    """the reported backward need is that of the largest descriptor variant: dgamma / dbeta wanted, no param_partials.  (With param_partials
+    the same call passes the workspace check at 0 bytes and would launch: not made here.)"""
+    L, lib = lib
+    B, HW, Cc, G = 3, 64, 128, 32
+    assert gn_plan(L, lib, B, HW, Cc, G, 1).workspace_bytes == B * Cc * 8
+    assert gn_plan(L, lib, B, HW, Cc, G, 0).resident == 1 and gn_plan(L, lib, B, HW, Cc, G, 0).workspace_bytes == 0
+
+
+# the shape grid of scripts/plan_step_helpers.py gnplans: every dispatch branch, and shapes the launchers turn away (skipped here)
+GN_B = (1, 2, 3, 4, 5, 40, 128, 170, 171, 256, 257, 513, 515, 2048, 65535, 65536)
+GN_HW = (16, 64, 256, 900, 1024, 2000, 4096, 4100, 65536)
+GN_CG = ((24, 6), (64, 32), (96, 8), (128, 32), (256, 2), (256, 32), (384, 32), (512, 32), (768, 32), (1024, 32), (4096, 32), (4100, 4), (130, 32),
+         (126, 6))
+
+
+def test_gn_workspace_bytes_bounds_every_shape(lib):
+    """bd_gn_workspace_bytes(B, C) >= the need of every (HW, G) the launchers take at that (B, C), in both directions"""
+    L, lib = lib
+    taken = tight = 0
+    for B in GN_B:
+        for HW in GN_HW:
+            for Cc, G in GN_CG:
+                p = L.GnPlanInfo()
+                if lib.bd_gn_plan(B, HW, Cc, G, 0, ctypes.byref(p)) != 0:
+                    continue
+                bound = lib.bd_gn_workspace_bytes(B, Cc)
+                need = max(p.workspace_bytes, gn_plan(L, lib, B, HW, Cc, G, 1).workspace_bytes)
+                assert bound >= need, (B, HW, Cc, G, bound, need)
+                taken += 1
+                tight = max(tight, need / bound)
+    print("shapes taken", taken, "of", len(GN_B) * len(GN_HW) * len(GN_CG), "largest need / bound", tight)
+    assert taken > 1000
