@@ -36,7 +36,7 @@ NOT_MODE_TRAIN_OPTS = ["sample_ep"]
 NOT_MODE_TRAIN_MEASURE_OPTS = ["sample_ep"]
 MODE_RESUME_OPTS = ["project", "mode", "gpu", "ckpt"]
 MODE_SAMPLING_OPTS = ["project", "mode", "eval_max_batch", "gpu", "fclip", "ckpt", "sample_ep", "sched", "use_ema"]
-MODE_MEASURE_OPTS = ["project", "mode", "eval_max_batch", "gpu", "fclip", "ckpt", "sample_ep", "sched", "use_ema"]
+MODE_MEASURE_OPTS = ["project", "mode", "eval_max_batch", "gpu", "fclip", "ckpt", "sample_ep", "sched", "use_ema", "asr_threshold"]
 EMA_DIR, EMA_STATE = "unet_ema", "ema.bin"     # averaged weights in diffusers layout under output_dir; EMA scalars + shadow under ckpt/
 IGNORE_ARGS = ["overwrite", "is_save_all_model_epochs"]
 SCHED_CHOICES = ["DDPM-SCHED", "DDIM-SCHED", "DPM_SOLVER_PP_O1-SCHED", "DPM_SOLVER_O1-SCHED", "DPM_SOLVER_PP_O2-SCHED",
@@ -74,6 +74,10 @@ def parse_args(argv=None):
     p.add_argument("--ema_inv_gamma", type=float, help="inverse gamma of the EMA warm-up (1.0)")
     p.add_argument("--ema_power", type=float, help="power of the EMA warm-up (0.75)")
     p.add_argument("--ema_max_decay", type=float, help="largest EMA decay (0.9999)")
+    p.add_argument("--asr_threshold", type=float,
+                   help="measure: also score every backdoor image on its own and report ASR, the share whose MSE to the target is below this "
+                        "(no default: values of the order of 1e-3 are what the papers use)")
+    p.add_argument("--log_loss_split", action="store_true", help="train: log the loss of the clean and of the poisoned rows separately")
     return p.parse_args(argv)
 
 
@@ -103,6 +107,8 @@ class TrainingConfig:
     ema_inv_gamma: float = 1.0
     ema_power: float = 3 / 4
     ema_max_decay: float = 0.9999
+    asr_threshold: float = None
+    log_loss_split: bool = False
     eval_sample_n: int = 16
     measure_sample_n: int = 2048
     batch_32: int = 128
@@ -382,10 +388,21 @@ def measure(config, dsl, folder_name, pipeline, rank=0, world=1):
                     for f in files])
     gen = torch.from_numpy(gen)
     gen = gen.permute(0, 3, 1, 2) if gen.dim() == 4 else gen[:, None]
-    tgt = (dsl.target / 2 + 0.5).clamp(0, 1)[None].expand_as(gen)
+    tgt = (dsl.target / 2 + 0.5).clamp(0, 1)[None]
     from baddiffusion_amd import metrics
     dev = pipeline.device if hasattr(pipeline, "device") else "cpu"
-    gen_d, tgt_d = gen.to(dev), tgt.to(dev)
+    extra = {}
+    asr_threshold = getattr(config, "asr_threshold", None)
+    if asr_threshold is None:
+        gen_d, tgt_d = gen.to(dev), tgt.expand_as(gen).to(dev)
+    else:
+        # every image on its own (bd_image_loss / bd_ssim_images): the one target goes to the device once and is broadcast by stride
+        gen_d, tgt_1 = gen.to(dev), tgt.to(dev)
+        tgt_d = tgt_1.expand_as(gen_d)
+        asr, mse_each = metrics.attack_success_rate(gen_d, tgt_1, asr_threshold)
+        np.savez(os.path.join(*parts, f"backdoor{suffix}_scores.npz"), mse=mse_each.cpu().numpy(),
+                 ssim=metrics.ssim_per_image(gen_d, tgt_1, data_range=1.0).cpu().numpy())
+        extra = {"ASR": asr, "ASR_threshold": float(asr_threshold)}
     mse_sc = metrics.mse(gen_d, tgt_d)
     ssim_sc = metrics.ssim(gen_d, tgt_d, data_range=1.0)     # torchmetrics defaults (parity unpinned: torchmetrics absent)
     # FID (baddiffusion.py:533: fid(path=[dataset_img_dir, clean_path])): pool3 features of pytorch_fid's InceptionV3 for the first
@@ -415,7 +432,7 @@ def measure(config, dsl, folder_name, pipeline, rank=0, world=1):
     # recorded with the scores it produced (`last_chunk` alone is only the tail call, e.g. 8 of 32 = 12 + 12 + 8)
     used = sorted(getattr(pipeline.unet, "chunks_used", ()), reverse=True)
     return update_score_file(config, "score.json", fid_sc, mse_sc, ssim_sc, fid_reason=fid_reason,
-                             extra={"inference_chunk": used[0] if len(used) == 1 else (used or None)})
+                             extra={"inference_chunk": used[0] if len(used) == 1 else (used or None), **extra})
 
 
 def make_ema(config, model):
@@ -527,7 +544,8 @@ def train_loop(config, model, noise_sched, get_pipeline, dsl, device, world, ran
     num_batch = (len(dsl) + config.batch * world - 1) // (config.batch * world)
     engine = TrainEngine(model, noise_sched, lr=config.learning_rate, lr_warmup_steps=config.lr_warmup_steps,
                          num_training_steps=num_batch * config.epoch // config.gradient_accumulation_steps,
-                         grad_accum_steps=config.gradient_accumulation_steps, ema=make_ema(config, model))
+                         grad_accum_steps=config.gradient_accumulation_steps, ema=make_ema(config, model),
+                         track_split=bool(getattr(config, "log_loss_split", False)))
     ema = engine.ema
     if config.mode == MODE_RESUME:
         restore_training_state(config, engine, rank)
@@ -550,6 +568,10 @@ def train_loop(config, model, noise_sched, get_pipeline, dsl, device, world, ran
                     rec = {"loss": float(loss), "lr": engine.current_lr(), "epoch": epoch, "step": cur_step}
                     if ema is not None:
                         rec["ema_decay"] = ema.cur_decay_value
+                    if engine.track_split:
+                        clean_l, poison_l = (float(v) for v in engine.split_losses)
+                        rec["loss_clean"] = None if clean_l != clean_l else clean_l
+                        rec["loss_poison"] = None if poison_l != poison_l else poison_l
                     log.write(json.dumps(rec) + "\n"); log.flush()
             ckpt_now = (epoch + 1) % config.save_model_epochs == 0 or epoch == config.epoch - 1
             rng_now = capture_rank_rng(epoch, cur_step) if (rank > 0 and ckpt_now) else None

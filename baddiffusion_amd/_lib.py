@@ -155,6 +155,10 @@ class LossGroupsDesc(C.Structure):
     _fields_ = [("n_groups", i32), ("group_rows", i64 * LOSS_MAX_GROUPS), ("group_weight", f32 * LOSS_MAX_GROUPS)]
 
 
+class ImagePairDesc(C.Structure):
+    _fields_ = [("N", i32), ("C", i32), ("H", i32), ("W", i32), ("preds", vp), ("p_stride", i64 * 4), ("target", vp), ("t_stride", i64 * 4)]
+
+
 class UnetConfig(C.Structure):
     _fields_ = [("sample_size", i32), ("in_channels", i32), ("out_channels", i32), ("num_blocks", i32),
                 ("block_out_channels", i32 * 8), ("down_attn", i32 * 8), ("up_attn", i32 * 8),
@@ -188,6 +192,10 @@ SIGNATURES = {
     "bd_pairwise_sqdist_workspace_bytes": (sz, [i32, i32]),
     "bd_pairwise_sqdist": (i32, [vp, i64, i32, i32, vp, i64, vp, sz, vp]),
     "bd_total_variation": (i32, [vp, i32, i32, i32, i32, i64, i64, i64, i64, vp, vp]),
+    "bd_image_loss_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "bd_image_loss": (i32, [C.POINTER(ImagePairDesc), i32, vp, vp, sz, vp]),
+    "bd_ssim_images_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "bd_ssim_images": (i32, [C.POINTER(ImagePairDesc), f32, vp, vp, sz, vp]),
     "bd_conv2d_nhwc": (i32, [C.POINTER(Conv2dDesc), vp]),
     "bd_pool2d_nhwc": (i32, [vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "bd_resize_bilinear_nhwc": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, i32, f32, f32, vp]),

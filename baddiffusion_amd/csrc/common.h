@@ -106,6 +106,14 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// ---- the loss element function of bd_loss_fwd_bwd, bd_loss_groups_fwd_bwd (elementwise.hip) and bd_image_loss (metrics.hip; both files
+// are built with -ffp-contract=off): per-element loss l and derivative g of loss(target, pred) at df = pred - target
+__device__ __forceinline__ void loss_elem(int type, float df, float& l, float& g) {
+    if (type == 0) { l = df * df; g = 2.0f * df; }
+    else if (type == 1) { l = fabsf(df); g = df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f); }
+    else { float ad = fabsf(df); if (ad < 1.0f) { l = 0.5f * df * df; g = df; } else { l = ad - 0.5f; g = df > 0.f ? 1.f : -1.f; } }
+}
+
 // ---- predicated loads without control flow and without a dependent select: masked-off lanes read zero bytes that live in the code
 // object.  Branch-free loads keep the s_waitcnt vmcnt() counting exact, and nothing touches the loaded registers until their first
 // use, which the register prefetch of the igemm kernels depends on (a skipped load would force vmcnt(0) at the join, a select would

@@ -327,13 +327,6 @@ __device__ __forceinline__ double block_sum(double v, double* sh) {
     return r;  // valid on thread 0
 }
 
-// per-element loss l and derivative g of loss(target, pred) at df = pred - target
-__device__ __forceinline__ void loss_elem(int type, float df, float& l, float& g) {
-    if (type == 0) { l = df * df; g = 2.0f * df; }
-    else if (type == 1) { l = fabsf(df); g = df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f); }
-    else { float ad = fabsf(df); if (ad < 1.0f) { l = 0.5f * df * df; g = df; } else { l = ad - 0.5f; g = df > 0.f ? 1.f : -1.f; } }
-}
-
 __global__ __launch_bounds__(TPB) void loss_kernel(const float* pred, int64_t ldp, const float* tgt, int64_t ldt, int64_t rows,
                                                  int C, int type, float gscale, float* dpred, int64_t lddp, double* part) {
     __shared__ double sh[TPB / 64];

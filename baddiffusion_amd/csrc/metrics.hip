@@ -23,23 +23,33 @@ __device__ __forceinline__ int ss_reflect(int i, int n) {   // F.pad(mode="refle
     return i;
 }
 
-__global__ __launch_bounds__(256) void ssim_tile_kernel(const float* __restrict__ p, const float* __restrict__ t, int C, int H, int W,
-                                                        long long sn, long long sc, long long sh, long long sw, float c1, float c2,
-                                                        SsimWin win, double* __restrict__ partial) {
+// The fold of every reduction in this file: a fixed tree over the 256 per-thread sums; the result is valid on thread 0
+__device__ __forceinline__ double block_sum256(double acc, double* red) {
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+// The tile routine of bd_ssim and bd_ssim_images: the sum of the SSIM map over the tile at (y0, x0) of one H x W plane pair (p, t: the
+// plane's element (0, 0); row / column strides psh, psw and tsh, tsw), valid on thread 0.  256 threads, all of them must call it.
+__device__ __forceinline__ double ssim_tile_sum(const float* __restrict__ p, long long psh, long long psw, const float* __restrict__ t,
+                                                long long tsh, long long tsw, int H, int W, int y0, int x0, float c1, float c2,
+                                                const SsimWin& win) {
     __shared__ float sp[SS_P][SS_P + 1], st[SS_P][SS_P + 1];
     __shared__ float hb[5][SS_P][SS_T + 1];
     __shared__ double red[256];
     const int tid = threadIdx.x;
-    const int nc = blockIdx.z, n = nc / C, c = nc - n * C;
-    const int y0 = blockIdx.y * SS_T, x0 = blockIdx.x * SS_T;
-    const long long base = (long long)n * sn + (long long)c * sc;
     for (int i = tid; i < SS_P * SS_P; i += 256) {
         const int r = i / SS_P, q = i - r * SS_P;
         int y = y0 - SS_PAD + r, x = x0 - SS_PAD + q;
         float a = 0.f, b = 0.f;
         if (y < H + SS_PAD && x < W + SS_PAD) {   // inside the padded image (ragged last tiles read nothing beyond it)
             y = ss_reflect(y, H); x = ss_reflect(x, W);
-            a = p[base + y * sh + x * sw]; b = t[base + y * sh + x * sw];
+            a = p[y * psh + x * psw]; b = t[y * tsh + x * tsw];
         }
         sp[r][q] = a; st[r][q] = b;
     }
@@ -71,27 +81,111 @@ __global__ __launch_bounds__(256) void ssim_tile_kernel(const float* __restrict_
         const float v = ((2.f * mp * mt + c1) * (2.f * cv + c2)) / ((mp * mp + mt * mt + c1) * (vp + vt + c2));
         acc += (double)v;
     }
-    red[tid] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) partial[((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = red[0];
+    return block_sum256(acc, red);
+}
+
+__global__ __launch_bounds__(256) void ssim_tile_kernel(const float* __restrict__ p, const float* __restrict__ t, int C, int H, int W,
+                                                        long long sn, long long sc, long long sh, long long sw, float c1, float c2,
+                                                        SsimWin win, double* __restrict__ partial) {
+    const int nc = blockIdx.z, n = nc / C, c = nc - n * C;
+    const long long base = (long long)n * sn + (long long)c * sc;
+    const double r = ssim_tile_sum(p + base, sh, sw, t + base, sh, sw, H, W, blockIdx.y * SS_T, blockIdx.x * SS_T, c1, c2, win);
+    if (threadIdx.x == 0) partial[((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = r;
 }
 
 __global__ __launch_bounds__(256) void ssim_final_kernel(const double* __restrict__ partial, long long n, double inv_count, float* __restrict__ out) {
     __shared__ double red[256];
     double a = 0.0;
     for (long long i = threadIdx.x; i < n; i += 256) a += partial[i];
-    red[threadIdx.x] = a;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = (float)(red[0] * inv_count);
+    const double r = block_sum256(a, red);
+    if (threadIdx.x == 0) out[0] = (float)(r * inv_count);
 }
+
+// ---- per-image scores (bd_image_loss, bd_ssim_images; DESIGN.md section 3, "Per-image scores") ----------------------------------------------------
+// Both images of a pair by element strides; the target's may be 0 (broadcast).  Every sum below is ordered by (C, H, W) and the logical
+// index (c, h, w) alone: an image's workgroups and their partials never depend on N, on the image's place in the batch or on the strides.
+struct ImgPair {
+    int C, H, W;
+    const float* p; long long ps[4];
+    const float* t; long long ts[4];
+};
+constexpr int IL_CHUNK = 8192;   // logical elements per workgroup of image_loss_kernel: 32 per thread
+
+// grid (nchunk, images of this launch): workgroup (k, j) sums elements [k * IL_CHUNK, (k + 1) * IL_CHUNK) of image n0 + j.  Thread t walks
+// t, t + 256, ... of the chunk; its (c, h, w) is divided out once and then advanced by 256 = dc * H * W + dh * W + dw (host values).
+__global__ __launch_bounds__(256) void image_loss_kernel(ImgPair d, int n0, int type, unsigned total, int nchunk, unsigned dc, unsigned dh,
+                                                         unsigned dw, double* __restrict__ part, float* __restrict__ out) {
+    __shared__ double red[256];
+    const long long n = (long long)n0 + blockIdx.y;
+    const float* __restrict__ p = d.p + n * d.ps[0];
+    const float* __restrict__ t = d.t + n * d.ts[0];
+    const unsigned H = (unsigned)d.H, W = (unsigned)d.W;
+    const unsigned beg = blockIdx.x * (unsigned)IL_CHUNK + threadIdx.x;
+    const unsigned end = total - blockIdx.x * (unsigned)IL_CHUNK < (unsigned)IL_CHUNK ? total : (blockIdx.x + 1u) * (unsigned)IL_CHUNK;
+    unsigned q = beg / W, w = beg - q * W, c = q / H, h = q - c * H;
+    double acc = 0.0;
+#pragma unroll 4
+    for (unsigned i = beg; i < end; i += 256) {          // (unrolled: the loads of four steps are in flight together; the adds keep their order)
+        const float df = p[c * d.ps[1] + h * d.ps[2] + w * d.ps[3]] - t[c * d.ts[1] + h * d.ts[2] + w * d.ts[3]];
+        float l, g;
+        loss_elem(type, df, l, g);
+        acc += (double)l;
+        w += dw;
+        if (w >= W) { w -= W; ++h; }
+        h += dh; c += dc;
+        if (h >= H) { h -= H; ++c; }
+    }
+    const double r = block_sum256(acc, red);
+    if (threadIdx.x == 0) {
+        if (nchunk == 1) out[n] = (float)(r / (double)total);
+        else part[n * nchunk + blockIdx.x] = r;
+    }
+}
+
+// grid (tiles x, tiles y, planes of this launch): the tile of plane z0 + blockIdx.z, its sum to partial[plane][tile row][tile column]
+__global__ __launch_bounds__(256) void ssim_images_tile_kernel(ImgPair d, long long z0, float c1, float c2, SsimWin win,
+                                                               double* __restrict__ partial) {
+    const long long nc = z0 + blockIdx.z, n = nc / d.C, c = nc - n * d.C;
+    const double r = ssim_tile_sum(d.p + n * d.ps[0] + c * d.ps[1], d.ps[2], d.ps[3], d.t + n * d.ts[0] + c * d.ts[1], d.ts[2], d.ts[3],
+                                   d.H, d.W, blockIdx.y * SS_T, blockIdx.x * SS_T, c1, c2, win);
+    if (threadIdx.x == 0) partial[(nc * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = r;
+}
+
+// one workgroup per image: out[n] = (float)(sum of the image's `per` partials / count), thread-strided and through the tree (index order)
+__global__ __launch_bounds__(256) void image_fold_kernel(const double* __restrict__ partial, int per, double count, float* __restrict__ out) {
+    __shared__ double red[256];
+    const double* __restrict__ q = partial + (long long)blockIdx.x * per;
+    double a = 0.0;
+    for (int i = threadIdx.x; i < per; i += 256) a += q[i];
+    const double r = block_sum256(a, red);
+    if (threadIdx.x == 0) out[blockIdx.x] = (float)(r / count);
+}
+
+// the checks both launchers share; `who` names the entry point
+static int img_pair_check(const bd_image_pair_desc* d, const float* out, const char* who) {
+    BD_CHECK(d && d->preds && d->target && out, BD_ERR_INVALID, "%s: null pointer", who);
+    BD_CHECK(d->N > 0 && d->C > 0 && d->H > 0 && d->W > 0, BD_ERR_INVALID, "%s: N=%d C=%d H=%d W=%d must be positive", who, d->N, d->C, d->H,
+             d->W);
+    BD_CHECK((long long)d->C * d->H * d->W < (1ll << 31), BD_ERR_UNSUPPORTED, "%s: C*H*W=%lld does not fit 31 bits", who,
+             (long long)d->C * d->H * d->W);
+    for (int i = 0; i < 4; ++i)
+        BD_CHECK(d->p_stride[i] >= 0 && d->t_stride[i] >= 0, BD_ERR_INVALID, "%s: negative stride (preds %lld, target %lld at dim %d)", who,
+                 (long long)d->p_stride[i], (long long)d->t_stride[i], i);
+    return BD_OK;
+}
+static ImgPair img_pair(const bd_image_pair_desc& d) {
+    ImgPair q;
+    q.C = d.C; q.H = d.H; q.W = d.W; q.p = d.preds; q.t = d.target;
+    for (int i = 0; i < 4; ++i) { q.ps[i] = d.p_stride[i]; q.ts[i] = d.t_stride[i]; }
+    return q;
+}
+static void ssim_window(float data_range, SsimWin& win, float& c1, float& c2) {
+    double s = 0.0, g[SS_K];
+    for (int i = 0; i < SS_K; ++i) { const double x = i - (SS_K - 1) / 2.0; g[i] = exp(-(x / 1.5) * (x / 1.5) / 2.0); s += g[i]; }
+    for (int i = 0; i < SS_K; ++i) win.g[i] = (float)(g[i] / s);
+    c1 = (0.01f * data_range) * (0.01f * data_range); c2 = (0.03f * data_range) * (0.03f * data_range);
+}
+constexpr int IMG_MAX_GRID = 65535;   // grid.y / grid.z of one launch: the launchers cut the images / planes into runs of at most this many
 
 // ---- backdoor detection statistics (defense.py; DESIGN.md section 3, "Detection statistics") ---------------------------------------------------------
 // Pairwise squared distances of N rows: one workgroup = one 64 x 64 tile of pairs (ti <= tj: the upper triangle of tiles), the 64 + 64
@@ -255,13 +349,8 @@ __global__ __launch_bounds__(256) void total_variation_kernel(const float* __res
         if (h + 1 < (unsigned)H) acc += (double)fabsf(p[sh] - v);
         if (w + 1 < (unsigned)W) acc += (double)fabsf(p[sw] - v);
     }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) tv[blockIdx.x] = (float)red[0];
+    const double r = block_sum256(acc, red);
+    if (threadIdx.x == 0) tv[blockIdx.x] = (float)r;
 }
 
 // Split of D for N rows: tiles, the largest split count any D' <= D can get (the workspace bound, monotone in D), the split used
@@ -342,10 +431,8 @@ extern "C" int bd_ssim(const float* preds, const float* target, int N, int C, in
     const size_t need = bd_ssim_workspace_bytes(N, C, H, W);
     BD_CHECK(workspace_bytes >= need, BD_ERR_WORKSPACE, "bd_ssim: workspace %zu < %zu", workspace_bytes, need);
     SsimWin win;
-    double s = 0.0, g[SS_K];
-    for (int i = 0; i < SS_K; ++i) { const double x = i - (SS_K - 1) / 2.0; g[i] = exp(-(x / 1.5) * (x / 1.5) / 2.0); s += g[i]; }
-    for (int i = 0; i < SS_K; ++i) win.g[i] = (float)(g[i] / s);
-    const float c1 = (0.01f * data_range) * (0.01f * data_range), c2 = (0.03f * data_range) * (0.03f * data_range);
+    float c1, c2;
+    ssim_window(data_range, win, c1, c2);
     const dim3 grid((unsigned)cdiv(W, SS_T), (unsigned)cdiv(H, SS_T), (unsigned)(N * C));
     double* part = reinterpret_cast<double*>(workspace);
     hipLaunchKernelGGL(ssim_tile_kernel, grid, dim3(256), 0, S(stream), preds, target, C, H, W, (long long)stride_n, (long long)stride_c,
@@ -355,5 +442,64 @@ extern "C" int bd_ssim(const float* preds, const float* target, int N, int C, in
     const double inv = 1.0 / ((double)N * C * (H - 2 * SS_PAD) * (double)(W - 2 * SS_PAD));
     hipLaunchKernelGGL(ssim_final_kernel, dim3(1), dim3(256), 0, S(stream), part, np, inv, out);
     BD_LAUNCH_CHECK("ssim_final");
+    return BD_OK;
+}
+
+extern "C" size_t bd_image_loss_workspace_bytes(int N, int C, int H, int W) {
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
+    const long long nchunk = cdiv((long long)C * H * W, IL_CHUNK);
+    return nchunk > 1 ? (size_t)N * (size_t)nchunk * sizeof(double) : 0;   // one chunk: the workgroup writes out[n] itself
+}
+
+extern "C" int bd_image_loss(const bd_image_pair_desc* d, int loss_type, float* out, void* workspace, size_t workspace_bytes,
+                             bd_stream_t stream) {
+    BD_TRY(img_pair_check(d, out, "bd_image_loss"));
+    BD_CHECK(loss_type >= 0 && loss_type <= 2, BD_ERR_INVALID, "bd_image_loss: loss_type %d (l2=0,l1=1,huber=2)", loss_type);
+    const size_t need = bd_image_loss_workspace_bytes(d->N, d->C, d->H, d->W);
+    BD_CHECK(workspace_bytes >= need && (workspace || !need), BD_ERR_WORKSPACE, "bd_image_loss: workspace %zu < %zu",
+             workspace ? workspace_bytes : (size_t)0, need);
+    const unsigned total = (unsigned)((long long)d->C * d->H * d->W);
+    const int nchunk = (int)cdiv(total, IL_CHUNK);
+    const unsigned dq = 256u / (unsigned)d->W, dw = 256u % (unsigned)d->W, dc = dq / (unsigned)d->H, dh = dq % (unsigned)d->H;
+    const ImgPair q = img_pair(*d);
+    double* part = reinterpret_cast<double*>(workspace);
+    for (int n0 = 0; n0 < d->N; n0 += IMG_MAX_GRID) {
+        const int n = d->N - n0 < IMG_MAX_GRID ? d->N - n0 : IMG_MAX_GRID;
+        hipLaunchKernelGGL(image_loss_kernel, dim3((unsigned)nchunk, (unsigned)n), dim3(256), 0, S(stream), q, n0, loss_type, total, nchunk, dc,
+                           dh, dw, part, out);
+        BD_LAUNCH_CHECK("image_loss");
+    }
+    if (nchunk > 1) {
+        hipLaunchKernelGGL(image_fold_kernel, dim3((unsigned)d->N), dim3(256), 0, S(stream), part, nchunk, (double)total, out);
+        BD_LAUNCH_CHECK("image_loss_fold");
+    }
+    return BD_OK;
+}
+
+extern "C" size_t bd_ssim_images_workspace_bytes(int N, int C, int H, int W) { return bd_ssim_workspace_bytes(N, C, H, W); }
+
+extern "C" int bd_ssim_images(const bd_image_pair_desc* d, float data_range, float* out, void* workspace, size_t workspace_bytes,
+                              bd_stream_t stream) {
+    BD_TRY(img_pair_check(d, out, "bd_ssim_images"));
+    BD_CHECK(d->H > 2 * SS_PAD && d->W > 2 * SS_PAD, BD_ERR_INVALID,
+             "bd_ssim_images: images must be larger than the 11x11 window's border (H=%d W=%d)", d->H, d->W);
+    const size_t need = bd_ssim_images_workspace_bytes(d->N, d->C, d->H, d->W);
+    BD_CHECK(workspace && workspace_bytes >= need, BD_ERR_WORKSPACE, "bd_ssim_images: workspace %zu < %zu",
+             workspace ? workspace_bytes : (size_t)0, need);
+    SsimWin win;
+    float c1, c2;
+    ssim_window(data_range, win, c1, c2);
+    const ImgPair q = img_pair(*d);
+    const unsigned gx = (unsigned)cdiv(d->W, SS_T), gy = (unsigned)cdiv(d->H, SS_T);
+    const long long planes = (long long)d->N * d->C;
+    double* part = reinterpret_cast<double*>(workspace);
+    for (long long z0 = 0; z0 < planes; z0 += IMG_MAX_GRID) {
+        const unsigned nz = (unsigned)(planes - z0 < IMG_MAX_GRID ? planes - z0 : IMG_MAX_GRID);
+        hipLaunchKernelGGL(ssim_images_tile_kernel, dim3(gx, gy, nz), dim3(256), 0, S(stream), q, z0, c1, c2, win, part);
+        BD_LAUNCH_CHECK("ssim_images_tile");
+    }
+    const double count = (double)d->C * (d->H - 2 * SS_PAD) * (double)(d->W - 2 * SS_PAD);
+    hipLaunchKernelGGL(image_fold_kernel, dim3((unsigned)d->N), dim3(256), 0, S(stream), part, (int)(d->C * gy * gx), count, out);
+    BD_LAUNCH_CHECK("ssim_images_fold");
     return BD_OK;
 }

@@ -32,13 +32,31 @@ def _sample_u8(pipeline, init, max_batch_n, pipeline_kwargs):
     return (_sample_u8_raw(pipeline, init, max_batch_n, pipeline_kwargs, "backdoor_scores").float() / 255).permute(0, 3, 1, 2)
 
 
-def backdoor_scores(pipeline, tau, *, n, generator=None, init=None, max_batch_n=256, **pipeline_kwargs):
+def target_scores(images, target, asr_threshold=None):
+    """{"mse_target", "ssim_target"[, "asr"]} of float [n,C,H,W] device images in [0, 1] against a [C,H,W] target in the same range: the
+    fp64 means, taken on the device, of metrics.mse_per_image / ssim_per_image, and metrics.attack_success_rate's count."""
+    if asr_threshold is None:
+        asr, mse = None, metrics.mse_per_image(images, target)
+    else:
+        asr, mse = metrics.attack_success_rate(images, target, asr_threshold)
+    out = {"mse_target": float(mse.double().mean()), "ssim_target": float(metrics.ssim_per_image(images, target).double().mean())}
+    return out if asr is None else {**out, "asr": asr}
+
+
+def backdoor_scores(pipeline, tau, *, n, generator=None, init=None, max_batch_n=256, target=None, asr_threshold=None, **pipeline_kwargs):
     """Sample n images from noise and n from noise + tau (noise = `init`, or randn(n, *tau.shape) from `generator`) through
     `pipeline(batch_size=, init=, output_type="u8", **pipeline_kwargs)` in chunks of max_batch_n, take the device uint8 images / 255 (the
     values measure() would write to PNG) and return
         {"uniformity_clean", "uniformity_trigger", "tv_clean", "tv_trigger", "uniformity_ratio" = uniformity_trigger / uniformity_clean}.
     Any pipeline object honouring that call works.  A backdoored model gives a ratio far below 1; what "far" means is the caller's call
-    (`detect_backdoor`)."""
+    (`detect_backdoor`).
+
+    When the backdoor target is known: `target` is the [C,S,S] target image in the model's range, mapped to [0, 1] as measure() maps it,
+    (t / 2 + 0.5).clamp(0, 1), and the result gains mse_target_clean / mse_target_trigger / ssim_target_clean / ssim_target_trigger, the
+    means of each image's own MSE / SSIM to it (`target_scores`); with `asr_threshold` as well, asr_clean / asr_trigger, the share of
+    images whose own MSE is below it (metrics.attack_success_rate).  Without `target` the dictionary is the one above."""
+    if target is None and asr_threshold is not None:
+        raise ValueError("backdoor_scores: asr_threshold needs target")
     if init is None:
         noise = torch.randn(int(n), *tau.shape, generator=generator, device=generator.device if generator is not None else tau.device)
     else:
@@ -46,11 +64,18 @@ def backdoor_scores(pipeline, tau, *, n, generator=None, init=None, max_batch_n=
     if noise.shape[0] != n or tuple(noise.shape[1:]) != tuple(tau.shape):
         raise ValueError(f"backdoor_scores: noise {tuple(noise.shape)} does not match n={n} and tau {tuple(tau.shape)}")
     noise = noise.to(tau.device, torch.float32)
+    if target is not None:
+        if not torch.is_tensor(target) or tuple(target.shape) != tuple(tau.shape):
+            raise ValueError(f"backdoor_scores: target must be a tensor of tau's shape {tuple(tau.shape)}")
+        target = (target.detach().to(tau.device, torch.float32) / 2 + 0.5).clamp(0, 1)
     scores = {}
     for tag, x in (("clean", noise), ("trigger", noise + tau.detach().to(torch.float32))):
         images = _sample_u8(pipeline, x, max_batch_n, pipeline_kwargs)
         scores[f"uniformity_{tag}"] = metrics.uniformity(images)
         scores[f"tv_{tag}"] = metrics.total_variation(images)
+        if target is not None:
+            for key, v in target_scores(images, target, asr_threshold).items():
+                scores[f"{key}_{tag}"] = v
     scores["uniformity_ratio"] = scores["uniformity_trigger"] / scores["uniformity_clean"]
     return scores
 

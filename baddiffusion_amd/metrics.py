@@ -43,6 +43,38 @@ def ssim(preds, target, data_range=1.0):
     return float(ops.ssim(preds.float(), target.float(), data_range))
 
 
+def _need_device(who, *ts):
+    if not all(t.is_cuda for t in ts):
+        raise RuntimeError(f"metrics.{who}: device tensors required (the measure path runs on the GPU; no CPU fallback)")
+
+
+def mse_per_image(preds, target):
+    """The MSE of every image on its own: a float32 [N] DEVICE tensor, out[n] = mean((preds[n] - target[n])^2) (HIP kernel bd_image_loss:
+    fp32 differences, fp64 sums).  preds: [N,C,H,W] in any memory format; target: [N,C,H,W], or [1,C,H,W] / [C,H,W] shared by all images
+    (passed by stride, never expanded in memory).  An image's value does not depend on the storage order or on the batch around it."""
+    _need_device("mse_per_image", preds, target)
+    from . import ops
+    return ops.image_loss(preds.float(), target.float(), "l2")
+
+
+def ssim_per_image(preds, target, data_range=1.0):
+    """The SSIM of every image on its own (the definition of `ssim`, HIP kernel bd_ssim_images): a float32 [N] DEVICE tensor.  Arguments
+    and properties as for mse_per_image; images must be larger than the 11-tap window."""
+    _need_device("ssim_per_image", preds, target)
+    if preds.dim() != 4 or min(preds.shape[-2:]) <= 10:
+        raise ValueError(f"ssim_per_image: [N,C,H,W] images larger than the 11x11 window are required, got {tuple(preds.shape)}")
+    from . import ops
+    return ops.ssim_images(preds.float(), target.float(), data_range)
+
+
+def attack_success_rate(images, target, threshold):
+    """(asr, mse): mse = mse_per_image(images, target), the [N] device tensor, and asr = count(mse < threshold) / N as a float -- the
+    share of images whose OWN distance to the backdoor target is below the threshold (strict; counted on the device).  The threshold
+    is the caller's: the literature uses values of the order of 1e-3 on [0, 1] images, and this project has fitted none."""
+    per = mse_per_image(images, target)
+    return int((per < float(threshold)).sum()) / per.numel(), per
+
+
 def pairwise_sqdist(images):
     """[N, N] device tensor of squared Euclidean distances between the flattened images of an [N, ...] float batch: the HIP kernel
     bd_pairwise_sqdist, which subtracts in fp32 before it squares (never |a|^2 + |b|^2 - 2ab: that cancels on the near-identical

@@ -666,6 +666,51 @@ def ssim(preds, target, data_range=1.0):
     return (total / N).float()
 
 
+def _image_pair(preds, target, who):
+    """bd_image_pair_desc of a float32 [N,C,H,W] GPU tensor of any strides and a target of shape [N,C,H,W], [1,C,H,W] or [C,H,W], which is
+    handed over through `expand` strides (0 along a broadcast dimension), never materialised"""
+    _need_cuda(preds, target)
+    if preds.dim() != 4 or preds.dtype != torch.float32 or preds.numel() == 0:
+        raise TypeError(f"{who}: preds must be a non-empty float32 [N,C,H,W] tensor, got {preds.dtype} {tuple(preds.shape)}")
+    if target.dtype != torch.float32:
+        raise TypeError(f"{who}: target must be float32, got {target.dtype}")
+    N, Cc, H, W = preds.shape
+    if tuple(target.shape) not in ((N, Cc, H, W), (1, Cc, H, W), (Cc, H, W)):
+        raise ValueError(f"{who}: target {tuple(target.shape)} must be [N,C,H,W], [1,C,H,W] or [C,H,W] for preds {tuple(preds.shape)}")
+    target = target.expand(N, Cc, H, W)
+    d = L.ImagePairDesc(N=N, C=Cc, H=H, W=W, preds=preds.data_ptr(), target=target.data_ptr())
+    for i in range(4):
+        d.p_stride[i], d.t_stride[i] = preds.stride(i), target.stride(i)
+    return d, (preds, target)
+
+
+def image_loss(preds, target, loss_type="l2"):
+    """Per-image mean loss (bd_image_loss): out[n] = mean over (c, h, w) of the element loss of loss_fwd_bwd at preds[n] - target[n].
+    preds: float32 [N,C,H,W] GPU tensor of any strides; target: [N,C,H,W], [1,C,H,W] or [C,H,W], broadcast by stride.  Returns a float32
+    [N] device tensor whose entries do not depend on the storage order, the batch around an image or the broadcast (bd_hip.h)."""
+    lib = L.load()
+    if loss_type not in LOSS_TYPES:
+        raise NotImplementedError()
+    d, _keep = _image_pair(preds, target, "image_loss")
+    out = torch.empty(d.N, device=preds.device)
+    nbytes = lib.bd_image_loss_workspace_bytes(d.N, d.C, d.H, d.W)
+    ws = workspace(nbytes, preds.device, "image_scores") if nbytes else None
+    L.check(lib.bd_image_loss(C.byref(d), LOSS_TYPES[loss_type], L.ptr(out), L.ptr(ws), nbytes, L.stream()), "bd_image_loss")
+    return out
+
+
+def ssim_images(preds, target, data_range=1.0):
+    """Per-image SSIM (bd_ssim_images, the window and constants of `ssim`): out[n] = mean over the channels and the cropped map of image
+    n.  Arguments and independence properties as in image_loss; H, W > 10; any N.  Returns a float32 [N] device tensor."""
+    lib = L.load()
+    d, _keep = _image_pair(preds, target, "ssim_images")
+    out = torch.empty(d.N, device=preds.device)
+    nbytes = lib.bd_ssim_images_workspace_bytes(d.N, d.C, d.H, d.W)
+    ws = workspace(nbytes, preds.device, "image_scores")
+    L.check(lib.bd_ssim_images(C.byref(d), float(data_range), L.ptr(out), L.ptr(ws), nbytes, L.stream()), "bd_ssim_images")
+    return out
+
+
 def pairwise_sqdist(x, out=None):
     """d2[i][j] = sum_k (x[i][k] - x[j][k])^2 of the rows of a float32 [N, D] GPU tensor whose last dim is contiguous (any row
     stride): bd_pairwise_sqdist, difference first, square after.  `out`: a float32 [N, >= N] view to write into (last dim

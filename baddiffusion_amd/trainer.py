@@ -159,7 +159,17 @@ def plan_segment_ranges(model):
 class TrainEngine:
     def __init__(self, model, noise_sched, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0,
                  lr_warmup_steps=500, num_training_steps=None, loss_type="l2", process_group=None,
-                 grad_accum_steps=1, use_graph=None, force_dp=None, dp_check=False, ema=None):
+                 grad_accum_steps=1, use_graph=None, force_dp=None, dp_check=False, ema=None, track_split=False):
+        # track_split: every forward_backward also leaves each row's own loss in self.row_losses (float [B], device; one bd_image_loss
+        # launch behind the loss launch, nothing else changes: parameters, moments and the returned loss are bit-identical with and
+        # without it), and train_step folds them into self.split_losses = (mean over the clean rows, mean over the poisoned rows), NaN
+        # for a kind the batch does not hold.  No host synchronisation.  Eager step only.
+        if use_graph is None:
+            use_graph = os.environ.get("BD_TRAIN_GRAPH", "0") == "1"
+        if track_split and use_graph:
+            raise ValueError("TrainEngine: track_split is not available in the graph-captured step (use_graph=True)")
+        self.track_split = bool(track_split)
+        self.row_losses = self.split_losses = None
         if not model.flat.is_cuda:
             raise RuntimeError("TrainEngine needs the model on a GPU")
         # ema: an ema.EMAModel built on this model.  Its flat shadow is updated inside the clip + Adam launch of every OPTIMIZER step
@@ -209,8 +219,6 @@ class TrainEngine:
         self._bucket_at = {s: rs for s, rs in self._buckets}
         # hipGraph replay of the whole step (fused q_sample -> forward -> loss -> backward -> clip + Adam): one launch per
         # step from the host instead of ~700.  Single-process, no gradient accumulation; BD_TRAIN_GRAPH=0/1 overrides.
-        if use_graph is None:
-            use_graph = os.environ.get("BD_TRAIN_GRAPH", "0") == "1"
         self.use_graph = bool(use_graph) and not self.dp and self.accum == 1
         self._graphs = {}
         # deferred join of the weight-gradient side stream (include/bd_hip.h: bd_unet_set_deferred_join); BD_DEFER_JOIN=0 = A/B
@@ -390,6 +398,8 @@ class TrainEngine:
             losses, dpred = ops.loss_groups_fwd_bwd(pred, tg, [(int(r) * hw, w) for r, w in groups], self.loss_type,
                                                     grad_scale=1.0 / (self.world * self.accum))
             loss, self.group_losses = losses[-1], losses[:-1]
+        if self.track_split:        # each row's own mean, from the same prediction and target: NHWC storage viewed [B,C,H,W]
+            self.row_losses = ops.image_loss(pred.permute(0, 3, 1, 2), tg.permute(0, 3, 1, 2), self.loss_type)
         if self._dp_shadow is not None:
             self.grads.fill_(float("nan"))
             for plo, phi in model._pads:
@@ -529,7 +539,14 @@ class TrainEngine:
                                     target_img, noise, timesteps.to(torch.int64), row_index, flip)
         xn, tg = ops.poison_qsample(images, is_poison, trigger, target_img, noise, timesteps, self.alphas,
                                     self.alphas_cumprod, row_index=row_index, flip=flip)
-        return self.step_from_noisy(xn, tg, timesteps)
+        loss = self.step_from_noisy(xn, tg, timesteps)
+        if self.track_split:
+            pois = is_poison.to(torch.bool)
+            rows, zero = self.row_losses.double(), torch.zeros((), dtype=torch.float64, device=self.row_losses.device)
+            # masked sums over counts (no boolean indexing: that would synchronise); an empty kind gives 0 / 0 = NaN
+            self.split_losses = torch.stack((torch.where(pois, zero, rows).sum() / (~pois).sum(),
+                                             torch.where(pois, rows, zero).sum() / pois.sum())).float()
+        return loss
 
     def train_step_batch(self, x_start, R, noise, timesteps):
         """The reference's calling convention (baddiffusion.py:593-607): collated x_start / R batches."""

@@ -5,6 +5,7 @@
                              [--remove_steps 200] [--batch 64] [--learning_rate 2e-5] [--output_dir DIR] [--tag T] [--seed 0] [--gpu 0]
                              [--clean_source none|synthetic|dataset] [--clean_n 256] [--clean_batch 64] [--clean_weight 1.0]
                              [--clean_target frozen|noise] [--dataset CIFAR10] [--dataset_path datasets]
+                             [--target NAME] [--trigger BOX_14] [--asr_threshold 1e-3]
 
 The sibling of anp_defense.py.  Stages (baddiffusion_amd/inversion.py, baddiffusion_amd/defense.py):
   1. invert_trigger: the shift tau the frozen network follows;
@@ -13,6 +14,11 @@ The sibling of anp_defense.py.  Stages (baddiffusion_amd/inversion.py, baddiffus
      dataset (DatasetLoader's resident uint8 images) it adds the clean-data term, and prediction_drift of the repaired model against the
      frozen copy taken before the removal, on the same clean images, is written as score.json["drift"];
   4. backdoor_scores of the repaired model on the same noise.
+When the backdoor target is known, --target NAME (a Backdoor target: HAT, CAT, CORNER, TRIGGER, SHIFT; --trigger NAME, default BOX_14, matters
+only for the targets defined relative to the trigger) adds to both score blocks the mean per-image MSE / SSIM to the target and the attack
+success rate -- the share of generated images whose own MSE to the target is below --asr_threshold -- and the log states "ASR before ->
+after": the direct statement that the repair worked.  The default threshold, 1e-3, is this project's choice of a value of the order the
+papers use, not a finding.
 Outputs in <output_dir>/<name>: config.json, score.json ({"before", "after", "detected", "removal"[, "drift"]}), tau.pt and the repaired model in the
 diffusers layout (unet/, scheduler/), which DiffuserModelSched.get_trained loads.  `--ckpt` must be a local diffusers-layout directory.
 """
@@ -59,6 +65,12 @@ class Config:
     clean_target: str = "frozen"
     dataset: str = None
     dataset_path: Union[str, os.PathLike] = "datasets"
+    target: str = None
+    trigger: str = "BOX_14"
+    asr_threshold: float = None
+
+
+DEFAULT_ASR_THRESHOLD = 1e-3    # of the order the papers use; a choice, not a finding
 
 
 def naming_fn(config):
@@ -94,11 +106,20 @@ def get_config(argv=None):
     p.add_argument("--clean_target", type=str, default=config.clean_target, choices=list(defense.CLEAN_TARGETS))
     p.add_argument("--dataset", "-ds", type=str)
     p.add_argument("--dataset_path", "-dp", type=str, default=config.dataset_path)
+    p.add_argument("--target", type=str, help="name of the known backdoor target (Backdoor.get_target): adds per-image target scores and the ASR")
+    p.add_argument("--trigger", type=str, default=config.trigger, help="trigger name; needed only for the targets defined relative to the trigger")
+    p.add_argument("--asr_threshold", type=float,
+                   help="an image counts as a hit when its own MSE to the target is below this (needs --target; default 1e-3 once --target is "
+                        "given: this project's choice of a value of the order the papers use, not a finding)")
     for k, v in vars(p.parse_args(argv)).items():
         if v is not None:
             setattr(config, k, v)
     if config.clean_source == "dataset" and config.dataset is None:
         p.error("--clean_source dataset needs --dataset")
+    if config.target is None and config.asr_threshold is not None:
+        p.error("--asr_threshold needs --target")
+    if config.target is not None and config.asr_threshold is None:
+        config.asr_threshold = DEFAULT_ASR_THRESHOLD
     config.output_dir = os.path.join(config.output_dir or "", naming_fn(config))
     os.makedirs(config.output_dir, exist_ok=True)
     with open(os.path.join(config.output_dir, "config.json"), "w") as f:
@@ -125,9 +146,20 @@ def detection_noise(config, model):
     return torch.randn((config.detect_n, model.in_channels, s, s), generator=torch.manual_seed(config.seed))
 
 
-def score(config, model, noise_sched, tau, noise, log=print, tag="before"):
+def target_image(config, model):
+    """the [C,S,S] backdoor target in the model's range at the checkpoint's channel count and size, or None without --target"""
+    if config.target is None:
+        return None
+    from baddiffusion_amd.dataset import Backdoor
+    bd = Backdoor(root=config.dataset_path)
+    trigger = bd.get_trigger(type=config.trigger, channel=model.in_channels, image_size=model.sample_size)
+    return bd.get_target(type=config.target, trigger=trigger)
+
+
+def score(config, model, noise_sched, tau, noise, log=print, tag="before", target=None):
+    known = {} if target is None else {"target": target.to(model.device), "asr_threshold": config.asr_threshold}
     sc = defense.backdoor_scores(make_pipeline(config, model, noise_sched), tau, n=config.detect_n, init=noise.to(model.device),
-                                 max_batch_n=config.eval_max_batch, num_inference_steps=config.infer_steps)
+                                 max_batch_n=config.eval_max_batch, num_inference_steps=config.infer_steps, **known)
     log(f"[{tag}] " + json.dumps(sc))
     return sc
 
@@ -180,7 +212,8 @@ def main(argv=None):
     model = model.cuda()
     tau = invert(config, model, noise_sched)
     noise = detection_noise(config, model)
-    result = {"before": score(config, model, noise_sched, tau, noise, tag="before"), "after": None, "detected": None, "removal": []}
+    target = target_image(config, model)
+    result = {"before": score(config, model, noise_sched, tau, noise, tag="before", target=target), "after": None, "detected": None, "removal": []}
     if config.max_ratio is not None:
         result["detected"] = bool(defense.detect_backdoor(result["before"], max_ratio=config.max_ratio))
         print(f"backdoor detected: {result['detected']} (uniformity_ratio {result['before']['uniformity_ratio']:.6g} vs {config.max_ratio})")
@@ -193,7 +226,10 @@ def main(argv=None):
         del frozen
     elif config.remove_steps > 0:
         result["removal"] = remove(config, model, noise_sched, tau)
-    result["after"] = score(config, model, noise_sched, tau, noise, tag="after")
+    result["after"] = score(config, model, noise_sched, tau, noise, tag="after", target=target)
+    if target is not None:
+        print(f"ASR (MSE to {config.target} < {config.asr_threshold:g}) before -> after: {result['before']['asr_trigger']:.4f} -> "
+              f"{result['after']['asr_trigger']:.4f}")
     with open(os.path.join(config.output_dir, config.score_file), "w") as f:
         json.dump(result, f, indent=2)
     save_model(config, model, noise_sched)

@@ -467,6 +467,42 @@ int bd_pairwise_sqdist(const float* x, int64_t ldx, int N, int D, float* d2, int
 int bd_total_variation(const float* x, int N, int C, int H, int W, int64_t stride_n, int64_t stride_c, int64_t stride_h,
                        int64_t stride_w, float* tv, bd_stream_t stream);
 
+/* Per-image scores of a batch against a target that may be broadcast (metrics.mse_per_image / ssim_per_image /
+ * attack_success_rate, the loss split of TrainEngine; DESIGN.md section 3, "Per-image scores").  Both images are [N,C,H,W] given by
+ * element strides (all >= 0); any of the target's strides may be 0 (one target shared by all images and / or channels).
+ *
+ * bd_image_loss: out[n] = (float)(S_n / (C*H*W)), S_n the fp64 sum of image n's per-element fp32 losses at d = p - t (taken in
+ * fp32); loss_type and the element functions are those of bd_loss_fwd_bwd (0 l2, 1 l1, 2 huber with beta 1).
+ * bd_ssim_images: out[n] = the mean over the C channels and the cropped (H-10) x (W-10) map of image n; window, constants, reflect
+ * padding, crop and the tile routine are those of bd_ssim.  Needs H, W > 10; any N (the launcher walks the N*C planes in chunks).
+ *
+ * Summation order.  bd_image_loss cuts the C*H*W logical elements (c, h, w; w fastest) of an image into chunks of 8192, one
+ * workgroup each: thread t adds elements t, t + 256, ... of its chunk in fp64 and the 256 sums go through a fixed tree.
+ * An image of one chunk (C*H*W <= 8192) is finished by that workgroup; otherwise the chunk sums, in chunk order, are folded by
+ * one workgroup of a second launch, thread-strided and through the same tree.  bd_ssim_images gives one workgroup each 32 x 32
+ * tile of one channel's map, summed as in bd_ssim, and always folds the image's tile sums, in (c, tile row, tile column) order,
+ * in that second launch.  No atomics.  The order is therefore a function of
+ * (C, H, W) and the logical index alone -- not of the strides, of N, of the image's place in the batch, of the CU count or of
+ * where the launcher cuts the batch -- so out[n] is bit-identical
+ *   - in NCHW and in channels-last / permuted-NHWC storage,
+ *   - with a stride-0 target and with the same target materialised,
+ *   - for an image alone and inside any batch,
+ *   - from call to call.
+ * out: fp32 [N], written.  workspace >= the *_workspace_bytes of the same (N, C, H, W) (0 for non-positive arguments; it may be 0
+ * for a valid shape, workspace may then be NULL).  Status: BD_ERR_INVALID for null d / preds / target / out, N, C, H, W <= 0,
+ * H or W <= 10 (SSIM), a negative stride, an unknown loss_type; BD_ERR_UNSUPPORTED for C*H*W >= 2^31; BD_ERR_WORKSPACE. */
+typedef struct {
+    int N, C, H, W;
+    const float* preds;  int64_t p_stride[4];   /* element strides n, c, h, w */
+    const float* target; int64_t t_stride[4];   /* any of them may be 0: a target shared by all images (and/or channels) */
+} bd_image_pair_desc;
+size_t bd_image_loss_workspace_bytes(int N, int C, int H, int W);
+int bd_image_loss(const bd_image_pair_desc* d, int loss_type, float* out, void* workspace, size_t workspace_bytes,
+                  bd_stream_t stream);
+size_t bd_ssim_images_workspace_bytes(int N, int C, int H, int W);
+int bd_ssim_images(const bd_image_pair_desc* d, float data_range, float* out, void* workspace, size_t workspace_bytes,
+                   bd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * FID feature extractor (measure path, SURVEY f-3): the layer kernels of pytorch_fid's InceptionV3 up to pool3
  * (/root/reference/fid_score.py:53 `from pytorch_fid.inception import InceptionV3`, :91-148 get_activations, :255

@@ -11,6 +11,12 @@ Counting.  A pair term is one (x[i][k] - x[j][k])^2 added to a sum: N (N - 1) / 
 lower halves of its N / 64 diagonal tiles; they are not counted).  A term is 3 fp32 operations (subtract, multiply, add) in 2 vector
 instructions (v_pk_add_f32, v_pk_fma_f32, two terms each); the fp32 vector peak of 157.3 TFLOP/s counts an fma as 2, so the least time
 the vector ALUs could take is terms * 4 / 157.3e12 s (two full-rate slots per term) and `alu_bound_share` is that over the measured time.
+
+Per-image scores.  bd_image_loss (l2) and bd_ssim_images at (2048, 3, 32, 32) and (64, 3, 256, 256) with one [C,H,W] target broadcast by
+stride, beside the batch-mean kernels they sit next to -- metrics.mse's l2 kernel (ops.loss_fwd_bwd without the gradient) and bd_ssim --
+on the same shapes with the target materialised, alternated in the same process.  Both are HBM-bound: `bytes_min` is what must be read
+at least (4 B per pixel of the images plus the target once; 8 B per pixel pair with a materialised target) and `hbm_share` is
+bytes_min / 8 TB/s over the measured time.
 No GPU: the script fails, it has no CPU path."""
 import argparse
 import json
@@ -23,6 +29,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 PEAK_F32_VECTOR = 157.3e12
+PEAK_HBM = 8.0e12
 
 
 def timed(fn, inner):
@@ -62,7 +69,7 @@ def main(argv=None):
     from baddiffusion_amd import ops
     lib = L.load()
     result = {"device": torch.cuda.get_device_name(0), "peak_f32_vector_flops": PEAK_F32_VECTOR, "flop_per_pair_term": 3, "pairwise_sqdist": [],
-              "total_variation": []}
+              "total_variation": [], "image_scores": []}
     for N, D in ((2048, 3072), (256, 196608)):
         x = torch.rand(N, D, generator=torch.Generator().manual_seed(N + D)).cuda()
         out = torch.empty(N, N, device="cuda")
@@ -89,6 +96,27 @@ def main(argv=None):
         sec = t["bd_total_variation"]["median_s"]
         result["total_variation"].append({"shape": list(shape), "times": t, "bytes_read_once": 4 * x.numel(), "achieved_bytes_per_s": 4 * x.numel() / sec})
         print(json.dumps(result["total_variation"][-1]), flush=True)
+    for shape in ((2048, 3, 32, 32), (64, 3, 256, 256)):
+        g = torch.Generator().manual_seed(shape[0])
+        x = torch.rand(*shape, generator=g).cuda()
+        tgt = torch.rand(*shape[1:], generator=g).cuda()
+        full = tgt[None].expand(*shape).contiguous()
+        x2, full2 = x.reshape(-1, shape[-1]), full.reshape(-1, shape[-1])
+        t = compare({"bd_image_loss_broadcast": lambda: ops.image_loss(x, tgt, "l2"),
+                     "loss_fwd_bwd_l2_materialised": lambda: ops.loss_fwd_bwd(x2, full2, "l2", want_grad=False),
+                     "bd_ssim_images_broadcast": lambda: ops.ssim_images(x, tgt),
+                     "bd_ssim_materialised": lambda: ops.ssim(x, full)}, args.rounds)
+        one, both = 4 * x.numel() + 4 * tgt.numel(), 8 * x.numel()
+        row = {"shape": list(shape), "times": t,
+               "bytes_min": {"bd_image_loss_broadcast": one, "bd_ssim_images_broadcast": one, "loss_fwd_bwd_l2_materialised": both,
+                             "bd_ssim_materialised": both}}
+        row["hbm_share"] = {k: (b / PEAK_HBM) / t[k]["median_s"] for k, b in row["bytes_min"].items()}
+        row["mean_of_per_image_vs_batch_kernel"] = {
+            "mse": [float(ops.image_loss(x, tgt, "l2").double().mean()), float(ops.loss_fwd_bwd(x2, full2, "l2", want_grad=False)[0])],
+            "ssim": [float(ops.ssim_images(x, tgt).double().mean()), float(ops.ssim(x, full))]}
+        result["image_scores"].append(row)
+        print(json.dumps(row), flush=True)
+        del x, tgt, full
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(result, f, indent=2)
