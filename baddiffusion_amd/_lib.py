@@ -40,6 +40,21 @@ class DdimStepDesc(C.Structure):
                 ("final_alpha_cumprod", f32), ("eta", f32), ("clip_sample", i32), ("clip_sample_range", f32)]
 
 
+REPAINT_UNDO_MAX = 8
+
+
+class RepaintStepDesc(C.Structure):
+    _fields_ = [("N", i32), ("C", i32), ("H", i32), ("W", i32), ("stride", i64 * 4), ("model_output", vp), ("sample", vp), ("noise", vp),
+                ("prev_sample", vp), ("pred_original", vp), ("original_image", vp), ("orig_stride", i64 * 4), ("mask", vp),
+                ("mask_stride", i64 * 4), ("shift", vp), ("shift_stride", i64 * 4), ("alphas_cumprod", vp), ("n_alphas", i32),
+                ("t", i32), ("prev_t", i32), ("final_alpha_cumprod", f32), ("eta", f32), ("clip_sample", i32), ("clip_sample_range", f32)]
+
+
+class RepaintUndoDesc(C.Structure):
+    _fields_ = [("N", i32), ("C", i32), ("H", i32), ("W", i32), ("stride", i64 * 4), ("sample", vp), ("out", vp), ("shift", vp),
+                ("shift_stride", i64 * 4), ("betas", vp), ("n_betas", i32), ("t", i32), ("k", i32)]
+
+
 class GnFwdDesc(C.Structure):
     _fields_ = [("B", i32), ("HW", i32), ("C", i32), ("G", i32), ("eps", f32), ("silu", i32),
                 ("x", vp), ("ldx", i64), ("gamma", vp), ("beta", vp), ("y", vp), ("ldy", i64),
@@ -185,6 +200,8 @@ SIGNATURES = {
     "bd_gn_fwd": (i32, [C.POINTER(GnFwdDesc), vp]),
     "bd_gn_bwd": (i32, [C.POINTER(GnBwdDesc), vp]),
     "bd_lincomb": (i32, [i32, C.POINTER(vp), C.POINTER(f32), i64, i32, f32, vp, vp]),
+    "bd_repaint_step": (i32, [C.POINTER(RepaintStepDesc), vp]),
+    "bd_repaint_undo": (i32, [C.POINTER(RepaintUndoDesc), C.POINTER(vp), vp]),
     "bd_anp_apply": (i32, [vp, i64, vp, vp, vp, i32, i64, vp, vp]),
     "bd_anp_grad": (i32, [vp, vp, vp, i32, i64, vp, vp, vp, vp, vp]),
     "bd_ssim_workspace_bytes": (sz, [i32, i32, i32, i32]),

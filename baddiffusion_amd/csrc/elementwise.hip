@@ -167,6 +167,161 @@ __global__ __launch_bounds__(TPB) void ddim_step_kernel(bd_ddim_step_desc d) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// RePaint (scheduling_repaint.py:250-293 step, :303-318 undo_step).  The dense operands share one dense layout, so the kernels walk
+// the STORAGE index i (16-byte accesses when aligned) and rebuild from it the coordinate along each dimension in storage order
+// (dimension 0 outermost); the broadcast operands (original image, mask, shift) are gathered at sum_j coord[j] * stride[j] with their
+// own strides permuted to that order by the host, 0 along a broadcast dimension.  The launchers turn away 2^31 elements and more, so
+// the coordinates are 32-bit: three 32-bit divisions per thread and pass.
+// ------------------------------------------------------------------------------------------------
+struct RpGeom {
+    int64_t n;                       // elements
+    unsigned sz[4];                  // sizes in storage order
+    int64_t os[4], ms[4], ss[4];     // strides of original image / mask / shift in storage order
+};
+struct RpCoord {
+    unsigned c[4];
+    __device__ __forceinline__ RpCoord(unsigned idx, const RpGeom& g) {
+        c[3] = idx % g.sz[3]; idx /= g.sz[3];
+        c[2] = idx % g.sz[2]; idx /= g.sz[2];
+        c[1] = idx % g.sz[1]; c[0] = idx / g.sz[1];
+    }
+    __device__ __forceinline__ void next(const RpGeom& g) {      // the coordinate of storage index + 1
+        if (++c[3] == g.sz[3]) {
+            c[3] = 0;
+            if (++c[2] == g.sz[2]) {
+                c[2] = 0;
+                if (++c[1] == g.sz[1]) { c[1] = 0; ++c[0]; }
+            }
+        }
+    }
+    __device__ __forceinline__ int64_t at(const int64_t (&s)[4]) const {
+        return (int64_t)c[0] * s[0] + (int64_t)c[1] * s[1] + (int64_t)c[2] * s[2] + (int64_t)c[3] * s[3];
+    }
+};
+
+// the scalars of one step, in the fp32 order of ddim_step_kernel (mask == 0 reproduces its bits)
+struct RpStepCoef { float sb, sa, sap, dir, sd, sbp, sh; bool var; };
+__device__ __forceinline__ RpStepCoef rp_step_coef(const bd_repaint_step_desc& d) {
+    RpStepCoef k;
+    const float a_t = d.alphas_cumprod[d.t];
+    const float a_prev = d.prev_t >= 0 ? d.alphas_cumprod[d.prev_t] : d.final_alpha_cumprod;
+    const float b_t = 1.0f - a_t, b_prev = 1.0f - a_prev;
+    k.sb = sqrtf(b_t); k.sa = sqrtf(a_t);
+    const float var = (b_prev / b_t) * (1.0f - a_t / a_prev);
+    k.sd = d.eta * sqrtf(var);
+    k.dir = sqrtf(1.0f - a_prev - k.sd * k.sd);
+    k.sap = sqrtf(a_prev);
+    k.sbp = sqrtf(b_prev);
+    k.sh = 1.0f - k.sap;
+    k.var = d.t > 0 && d.eta > 0.f;
+    return k;
+}
+__device__ __forceinline__ float rp_step_elem(const RpStepCoef& k, const bd_repaint_step_desc& d, float x, float e, float z, float o,
+                                              float m, float s, float& x0) {
+    x0 = (x - k.sb * e) / k.sa;
+    if (d.clip_sample) x0 = fminf(fmaxf(x0, -d.clip_sample_range), d.clip_sample_range);
+    float unknown = k.sap * x0 + k.dir * e;
+    if (k.var) unknown = unknown + k.sd * z;
+    float known = k.sap * o + k.sbp * z;
+    if (d.shift) known = known + k.sh * s;
+    return m * known + (1.0f - m) * unknown;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(TPB) void repaint_step_kernel(bd_repaint_step_desc d, RpGeom g) {
+    const RpStepCoef k = rp_step_coef(d);
+    const int64_t stride = (int64_t)gridDim.x * TPB;
+    if (VEC) {
+        const int64_t n4 = g.n >> 2;
+        for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n4; i += stride) {
+            const float4 xv = reinterpret_cast<const float4*>(d.sample)[i];
+            const float4 ev = reinterpret_cast<const float4*>(d.model_output)[i];
+            const float4 zv = reinterpret_cast<const float4*>(d.noise)[i];
+            const float x[4] = {xv.x, xv.y, xv.z, xv.w}, e[4] = {ev.x, ev.y, ev.z, ev.w}, z[4] = {zv.x, zv.y, zv.z, zv.w};
+            float o[4], m[4], s[4];
+            RpCoord c((unsigned)(i << 2), g);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                o[j] = d.original_image[c.at(g.os)];
+                m[j] = d.mask[c.at(g.ms)];
+                s[j] = d.shift ? d.shift[c.at(g.ss)] : 0.f;
+                c.next(g);
+            }
+            float p[4], x0[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) p[j] = rp_step_elem(k, d, x[j], e[j], z[j], o[j], m[j], s[j], x0[j]);
+            reinterpret_cast<float4*>(d.prev_sample)[i] = make_float4(p[0], p[1], p[2], p[3]);
+            if (d.pred_original) reinterpret_cast<float4*>(d.pred_original)[i] = make_float4(x0[0], x0[1], x0[2], x0[3]);
+        }
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < g.n; i += stride) {
+            const RpCoord c((unsigned)i, g);
+            const float s = d.shift ? d.shift[c.at(g.ss)] : 0.f;
+            float x0;
+            d.prev_sample[i] = rp_step_elem(k, d, d.sample[i], d.model_output[i], d.noise[i], d.original_image[c.at(g.os)],
+                                            d.mask[c.at(g.ms)], s, x0);
+            if (d.pred_original) d.pred_original[i] = x0;
+        }
+    }
+}
+
+// undo_step: x <- sqrt(1 - beta_i) x + sqrt(beta_i) z_i [+ (1 - sqrt(1 - beta_i)) shift], i = 0..k-1 in order, x in registers
+struct RpUndoArgs {
+    const float* z[BD_REPAINT_UNDO_MAX];
+    const float* x; float* out; const float* shift; const float* betas;
+    int t, k;
+};
+template <bool VEC>
+__global__ __launch_bounds__(TPB) void repaint_undo_kernel(RpUndoArgs a, RpGeom g) {
+    float ca[BD_REPAINT_UNDO_MAX], cb[BD_REPAINT_UNDO_MAX], cs[BD_REPAINT_UNDO_MAX];
+#pragma unroll
+    for (int j = 0; j < BD_REPAINT_UNDO_MAX; ++j) {
+        const float beta = j < a.k ? a.betas[a.t + j] : 0.f;
+        ca[j] = sqrtf(1.0f - beta); cb[j] = sqrtf(beta); cs[j] = 1.0f - ca[j];
+    }
+    const int64_t stride = (int64_t)gridDim.x * TPB;
+    if (VEC) {
+        const int64_t n4 = g.n >> 2;
+        for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n4; i += stride) {
+            float4 zv[BD_REPAINT_UNDO_MAX];
+#pragma unroll
+            for (int j = 0; j < BD_REPAINT_UNDO_MAX; ++j)
+                zv[j] = j < a.k ? reinterpret_cast<const float4*>(a.z[j])[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 xv = reinterpret_cast<const float4*>(a.x)[i];
+            float x[4] = {xv.x, xv.y, xv.z, xv.w}, s[4] = {0.f, 0.f, 0.f, 0.f};
+            if (a.shift) {
+                RpCoord c((unsigned)(i << 2), g);
+#pragma unroll
+                for (int l = 0; l < 4; ++l) { s[l] = a.shift[c.at(g.ss)]; c.next(g); }
+            }
+#pragma unroll
+            for (int j = 0; j < BD_REPAINT_UNDO_MAX; ++j)
+                if (j < a.k) {
+                    const float z[4] = {zv[j].x, zv[j].y, zv[j].z, zv[j].w};
+#pragma unroll
+                    for (int l = 0; l < 4; ++l) {
+                        x[l] = ca[j] * x[l] + cb[j] * z[l];
+                        if (a.shift) x[l] = x[l] + cs[j] * s[l];
+                    }
+                }
+            reinterpret_cast<float4*>(a.out)[i] = make_float4(x[0], x[1], x[2], x[3]);
+        }
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < g.n; i += stride) {
+            float x = a.x[i], s = 0.f;
+            if (a.shift) { const RpCoord c((unsigned)i, g); s = a.shift[c.at(g.ss)]; }
+#pragma unroll
+            for (int j = 0; j < BD_REPAINT_UNDO_MAX; ++j)
+                if (j < a.k) {
+                    x = ca[j] * x + cb[j] * a.z[j][i];
+                    if (a.shift) x = x + cs[j] * s;
+                }
+            a.out[i] = x;
+        }
+    }
+}
+
 // a-7: (x/2+0.5).clamp(0,1) -> NHWC float / uint8 (pipeline_ddpm.py:115-116, model.py:499)
 __global__ __launch_bounds__(TPB) void to_image_kernel(const float* x, int nhwc, int64_t ld, int B, int C, int64_t hw,
                                                      float* of, uint8_t* ou) {
@@ -625,6 +780,96 @@ extern "C" int bd_ddim_step(const bd_ddim_step_desc* d, bd_stream_t stream) {
     BD_LAUNCH_CHECK("ddim_step");
     return BD_OK;
 }
+namespace bd {
+// Storage order of a dense [N,C,H,W] layout: perm[0] outermost .. perm[3] innermost (size-1 dimensions, whose strides mean nothing,
+// go first).  False when `stride` is not dense: some stride differs from the product of the sizes inside it.
+static bool rp_storage_order(const int (&size)[4], const int64_t (&stride)[4], int (&perm)[4]) {
+    int n1 = 0, rest[4], nr = 0;
+    for (int i = 0; i < 4; ++i) {
+        if (size[i] == 1) perm[n1++] = i;
+        else rest[nr++] = i;
+    }
+    for (int a = 1; a < nr; ++a)        // descending stride
+        for (int b = a; b > 0 && stride[rest[b]] > stride[rest[b - 1]]; --b) { const int t = rest[b]; rest[b] = rest[b - 1]; rest[b - 1] = t; }
+    int64_t expect = 1;
+    for (int a = nr - 1; a >= 0; --a) {
+        if (stride[rest[a]] != expect) return false;
+        expect *= size[rest[a]];
+    }
+    for (int a = 0; a < nr; ++a) perm[n1 + a] = rest[a];
+    return true;
+}
+// the checks and the geometry both RePaint entry points share; strides of an absent broadcast operand may be NULL
+static int rp_geometry(const char* who, int N, int C, int H, int W, const int64_t (&stride)[4], const int64_t* os, const int64_t* ms,
+                       const int64_t* ss, RpGeom& g) {
+    BD_CHECK(N > 0 && C > 0 && H > 0 && W > 0, BD_ERR_INVALID, "%s: N=%d C=%d H=%d W=%d must be positive", who, N, C, H, W);
+    for (int i = 0; i < 4; ++i)
+        BD_CHECK(stride[i] >= 0 && (!os || os[i] >= 0) && (!ms || ms[i] >= 0) && (!ss || ss[i] >= 0), BD_ERR_INVALID,
+                 "%s: negative stride at dim %d", who, i);
+    const int size[4] = {N, C, H, W};
+    int perm[4];
+    BD_CHECK(rp_storage_order(size, stride, perm), BD_ERR_INVALID,
+             "%s: stride (%lld, %lld, %lld, %lld) is not a dense layout of [%d,%d,%d,%d]", who, (long long)stride[0], (long long)stride[1],
+             (long long)stride[2], (long long)stride[3], N, C, H, W);
+    g.n = (int64_t)N * C * H * W;
+    BD_CHECK(g.n < ((int64_t)1 << 31), BD_ERR_UNSUPPORTED, "%s: %lld elements (2^31 and more are not supported)", who, (long long)g.n);
+    for (int j = 0; j < 4; ++j) {
+        g.sz[j] = (unsigned)size[perm[j]];
+        g.os[j] = os ? os[perm[j]] : 0; g.ms[j] = ms ? ms[perm[j]] : 0; g.ss[j] = ss ? ss[perm[j]] : 0;
+    }
+    return BD_OK;
+}
+constexpr int64_t RP_MAX_BLOCKS = 2048;
+}  // namespace bd
+
+extern "C" int bd_repaint_step(const bd_repaint_step_desc* d, bd_stream_t stream) {
+    BD_CHECK(d, BD_ERR_INVALID, "bd_repaint_step: null descriptor");
+    BD_CHECK(d->model_output && d->sample && d->noise && d->prev_sample && d->original_image && d->mask && d->alphas_cumprod,
+             BD_ERR_INVALID, "bd_repaint_step: null pointer (model_output, sample, noise, prev_sample, original_image, mask and "
+             "alphas_cumprod are required)");
+    BD_CHECK(d->t >= 0, BD_ERR_INVALID, "bd_repaint_step: t=%d < 0", d->t);
+    BD_CHECK(d->t < d->n_alphas && d->prev_t < d->n_alphas, BD_ERR_INVALID, "bd_repaint_step: t=%d / prev_t=%d outside the table of %d",
+             d->t, d->prev_t, d->n_alphas);
+    RpGeom g;
+    BD_TRY(rp_geometry("bd_repaint_step", d->N, d->C, d->H, d->W, d->stride, d->orig_stride, d->mask_stride,
+                       d->shift ? d->shift_stride : nullptr, g));
+    const bool vec = (g.n & 3) == 0 && aligned16(d->model_output) && aligned16(d->sample) && aligned16(d->noise) &&
+                     aligned16(d->prev_sample) && aligned16(d->pred_original);
+    const dim3 grid(nblocks(vec ? g.n >> 2 : g.n, TPB, RP_MAX_BLOCKS)), block(TPB);
+    if (vec) hipLaunchKernelGGL(repaint_step_kernel<true>, grid, block, 0, S(stream), *d, g);
+    else hipLaunchKernelGGL(repaint_step_kernel<false>, grid, block, 0, S(stream), *d, g);
+    BD_LAUNCH_CHECK("repaint_step");
+    return BD_OK;
+}
+
+extern "C" int bd_repaint_undo(const bd_repaint_undo_desc* d, const float* const* noises, bd_stream_t stream) {
+    BD_CHECK(d, BD_ERR_INVALID, "bd_repaint_undo: null descriptor");
+    BD_CHECK(d->sample && d->out && d->betas && noises, BD_ERR_INVALID,
+             "bd_repaint_undo: null pointer (sample, out, betas and noises are required)");
+    BD_CHECK(d->k >= 1, BD_ERR_INVALID, "bd_repaint_undo: k=%d < 1", d->k);
+    BD_CHECK(d->t >= 0, BD_ERR_INVALID, "bd_repaint_undo: t=%d < 0", d->t);
+    BD_CHECK((int64_t)d->t + d->k <= d->n_betas, BD_ERR_INVALID, "bd_repaint_undo: t + k = %d + %d exceeds the table of %d", d->t, d->k,
+             d->n_betas);
+    RpGeom g;
+    BD_TRY(rp_geometry("bd_repaint_undo", d->N, d->C, d->H, d->W, d->stride, nullptr, nullptr, d->shift ? d->shift_stride : nullptr, g));
+    bool vec = (g.n & 3) == 0 && aligned16(d->sample) && aligned16(d->out);
+    for (int j = 0; j < d->k; ++j) {
+        BD_CHECK(noises[j], BD_ERR_INVALID, "bd_repaint_undo: noises[%d] is null", j);
+        vec = vec && aligned16(noises[j]);
+    }
+    const dim3 grid(nblocks(vec ? g.n >> 2 : g.n, TPB, RP_MAX_BLOCKS)), block(TPB);
+    for (int j0 = 0; j0 < d->k; j0 += BD_REPAINT_UNDO_MAX) {       // one path for every chunk: same kernel, same bits
+        RpUndoArgs a = {};
+        a.k = d->k - j0 < BD_REPAINT_UNDO_MAX ? d->k - j0 : BD_REPAINT_UNDO_MAX;
+        for (int j = 0; j < a.k; ++j) a.z[j] = noises[j0 + j];
+        a.x = j0 == 0 ? d->sample : d->out; a.out = d->out; a.shift = d->shift; a.betas = d->betas; a.t = d->t + j0;
+        if (vec) hipLaunchKernelGGL(repaint_undo_kernel<true>, grid, block, 0, S(stream), a, g);
+        else hipLaunchKernelGGL(repaint_undo_kernel<false>, grid, block, 0, S(stream), a, g);
+        BD_LAUNCH_CHECK("repaint_undo");
+    }
+    return BD_OK;
+}
+
 extern "C" int bd_to_image(const float* x, int src_is_nhwc, int64_t ld, int B, int C, int H, int W, float* out_f32,
                            uint8_t* out_u8, bd_stream_t stream) {
     BD_CHECK(x && (out_f32 || out_u8) && B > 0 && C > 0 && H > 0 && W > 0, BD_ERR_INVALID, "bd_to_image: bad args");

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from .pipelines import DDIMPipeline, DDPMPipeline, PNDMPipeline
-from .schedulers import DDIMScheduler, DDPMScheduler, PNDMScheduler, SchedulerConfigCarrier
+from .schedulers import DDIMScheduler, DDPMScheduler, PNDMScheduler, RePaintScheduler, SchedulerConfigCarrier
 from .unet import UNet2DModel
 
 WEIGHTS_NAME = "diffusion_pytorch_model.bin"
@@ -83,7 +83,8 @@ def save_scheduler(sched, directory):
 def load_scheduler(directory):
     with open(os.path.join(directory, SCHEDULER_CONFIG_NAME)) as f:
         cfg = json.load(f)
-    cls = {"DDPMScheduler": DDPMScheduler, "DDIMScheduler": DDIMScheduler}.get(cfg.get("_class_name", "DDPMScheduler"))
+    cls = {"DDPMScheduler": DDPMScheduler, "DDIMScheduler": DDIMScheduler,
+           "RePaintScheduler": RePaintScheduler}.get(cfg.get("_class_name", "DDPMScheduler"))
     if cls is None:
         raise NotImplementedError(f"scheduler {cfg.get('_class_name')} is not on the BadDiffusion hot path")
     return cls(**{k: v for k, v in cfg.items() if not k.startswith("_")})

@@ -152,6 +152,104 @@ def ddim_step(model_output, sample, alphas_cumprod, t, prev_t, eta=0.0, noise=No
     return (prev, x0) if want_x0 else prev
 
 
+def _is_dense(t):
+    """True when the tensor's elements fill one block of memory in some order of its dimensions"""
+    expect = 1
+    for d in sorted((d for d in range(t.dim()) if t.size(d) > 1), key=lambda d: t.stride(d)):
+        if t.stride(d) != expect:
+            return False
+        expect *= t.size(d)
+    return True
+
+
+def _repaint_dense(who, ref, *others):
+    """`ref` ([N,C,H,W] float32, made dense if it is not) and `others` brought to its strides: the dense operands of a RePaint kernel.
+    A contiguous tensor next to NHWC storage goes through bd_nchw_to_nhwc; any other mismatch is a strided copy."""
+    if ref.dim() != 4 or ref.dtype != torch.float32 or ref.numel() == 0:
+        raise TypeError(f"{who}: expected a non-empty float32 [N,C,H,W] tensor, got {ref.dtype} {tuple(ref.shape)}")
+    if not _is_dense(ref):
+        ref = ref.contiguous()
+    nhwc = ref.permute(0, 2, 3, 1).is_contiguous()
+    out = [ref]
+    for t in others:
+        if t is None:
+            out.append(None)
+            continue
+        if t.shape != ref.shape or t.dtype != torch.float32:
+            raise ValueError(f"{who}: operands must all be float32 {tuple(ref.shape)}, got {t.dtype} {tuple(t.shape)}")
+        if t.stride() != ref.stride():
+            if nhwc and t.is_contiguous():
+                t = nchw_to_nhwc(t).permute(0, 3, 1, 2)
+            if t.stride() != ref.stride():
+                t = torch.empty_like(ref).copy_(t)
+        out.append(t)
+    return out
+
+
+def _repaint_bcast(who, name, t, shape):
+    """a float32 operand broadcastable to `shape`, expanded by stride (0 along a broadcast dimension), never materialised"""
+    if t.dtype != torch.float32:
+        raise TypeError(f"{who}: {name} must be float32, got {t.dtype}")
+    if t.dim() > 4:
+        raise ValueError(f"{who}: {name} {tuple(t.shape)} does not broadcast to {tuple(shape)}")
+    try:
+        return t.reshape((1,) * (4 - t.dim()) + tuple(t.shape)).expand(*shape)
+    except RuntimeError:
+        raise ValueError(f"{who}: {name} {tuple(t.shape)} does not broadcast to {tuple(shape)}") from None
+
+
+def repaint_step(model_output, sample, noise, original_image, mask, alphas_cumprod, t, prev_t, eta=0.0, clip_sample=True,
+                 clip_sample_range=1.0, final_alpha_cumprod=1.0, shift=None, out=None, want_x0=False):
+    """One RePaint reverse step (bd_repaint_step, formulas in include/bd_hip.h).  model_output / sample / noise: float32 [N,C,H,W] GPU
+    tensors; the result has `sample`'s dense layout (NCHW, or a permuted view of NHWC storage).  original_image, mask and the optional
+    shift broadcast to [N,C,H,W] and are read through their strides.  Returns prev_sample, or (prev_sample, pred_original_sample)."""
+    lib = L.load(); _need_cuda(model_output, sample, noise, original_image, mask, alphas_cumprod, shift)
+    sample, model_output, noise = _repaint_dense("repaint_step", sample, model_output, noise)
+    N, Cc, H, W = sample.shape
+    orig = _repaint_bcast("repaint_step", "original_image", original_image, sample.shape)
+    msk = _repaint_bcast("repaint_step", "mask", mask, sample.shape)
+    shf = None if shift is None else _repaint_bcast("repaint_step", "shift", shift, sample.shape)
+    prev = torch.empty_like(sample) if out is None else out
+    x0 = torch.empty_like(sample) if want_x0 else None
+    if prev.stride() != sample.stride() or (x0 is not None and x0.stride() != sample.stride()):
+        raise ValueError("repaint_step: out must have sample's strides")
+    d = L.RepaintStepDesc(N=N, C=Cc, H=H, W=W, model_output=L.ptr(model_output), sample=L.ptr(sample), noise=L.ptr(noise),
+                          prev_sample=L.ptr(prev), pred_original=L.ptr(x0), original_image=L.ptr(orig), mask=L.ptr(msk), shift=L.ptr(shf),
+                          alphas_cumprod=L.ptr(alphas_cumprod), n_alphas=alphas_cumprod.numel(), t=int(t), prev_t=int(prev_t),
+                          final_alpha_cumprod=final_alpha_cumprod, eta=eta, clip_sample=int(bool(clip_sample)),
+                          clip_sample_range=clip_sample_range)
+    for i in range(4):
+        d.stride[i], d.orig_stride[i], d.mask_stride[i] = sample.stride(i), orig.stride(i), msk.stride(i)
+        d.shift_stride[i] = 0 if shf is None else shf.stride(i)
+    L.check(lib.bd_repaint_step(C.byref(d), L.stream()), "bd_repaint_step")
+    return (prev, x0) if want_x0 else prev
+
+
+def repaint_undo(sample, noises, betas, t, shift=None, out=None):
+    """k = len(noises) forward sub-steps of RePaint's undo_step from timestep t (bd_repaint_undo): x <- sqrt(1 - betas[t+i]) x +
+    sqrt(betas[t+i]) noises[i] [+ (1 - sqrt(1 - betas[t+i])) shift], in order.  sample and every noise: float32 [N,C,H,W] GPU tensors;
+    the result has `sample`'s dense layout.  Any k >= 1: the library cuts it into launches of REPAINT_UNDO_MAX sub-steps."""
+    lib = L.load(); _need_cuda(sample, betas, shift, *noises)
+    k = len(noises)
+    if k < 1:
+        raise ValueError("repaint_undo: at least one noise tensor")
+    sample, *noises = _repaint_dense("repaint_undo", sample, *noises)
+    N, Cc, H, W = sample.shape
+    shf = None if shift is None else _repaint_bcast("repaint_undo", "shift", shift, sample.shape)
+    if out is None:
+        out = torch.empty_like(sample)
+    elif out.stride() != sample.stride():
+        raise ValueError("repaint_undo: out must have sample's strides")
+    d = L.RepaintUndoDesc(N=N, C=Cc, H=H, W=W, sample=L.ptr(sample), out=L.ptr(out), shift=L.ptr(shf), betas=L.ptr(betas),
+                          n_betas=betas.numel(), t=int(t), k=k)
+    for i in range(4):
+        d.stride[i] = sample.stride(i)
+        d.shift_stride[i] = 0 if shf is None else shf.stride(i)
+    ptrs = (C.c_void_p * k)(*[z.data_ptr() for z in noises])
+    L.check(lib.bd_repaint_undo(C.byref(d), ptrs, L.stream()), "bd_repaint_undo")
+    return out
+
+
 def to_image(x, nhwc, shape_bchw, want_u8=False):
     """(x/2+0.5).clamp(0,1) -> NHWC float32 [B,H,W,C] (and uint8 round(255 x))."""
     lib = L.load(); _need_cuda(x)

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .schedulers import DDIMScheduler, PNDMScheduler, DDPMScheduler, randn_tensor
+from .schedulers import DDIMScheduler, PNDMScheduler, DDPMScheduler, RePaintScheduler, randn_tensor
 
 
 class ImagePipelineOutput:
@@ -239,6 +239,99 @@ class PNDMPipeline(_PipelineBase):
             images = self._to_u8(image, shape)
             return ImagePipelineOutput(images=images, movie=mov) if return_dict else (images,)
         images = self._to_numpy(image, shape)
+        if output_type == "pil":
+            images = self.numpy_to_pil(images)
+            if save_every_step:
+                mov = list(map(self.numpy_to_pil, mov))
+        if not return_dict:
+            return (images,)
+        return ImagePipelineOutput(images=images, movie=mov)
+
+
+class RePaintPipeline(_PipelineBase):
+    """pipelines/repaint/pipeline_repaint.py:73-171 for tensors: inpaint `image` where `mask_image` is 0 with an unconditional DDPM UNet.
+    Whatever scheduler it is given is converted to a RePaintScheduler from its config.  Loop body = one UNet forward + one fused
+    `bd_repaint_step` launch on the way down, one `bd_repaint_undo` call (num_train_timesteps // num_inference_steps noising sub-steps)
+    on the way back up; the running sample stays in NHWC storage and the original image and the mask are read through their strides.
+    Additions in the style of the sibling pipelines: `init=` (replaces the initial noise: how noise + trigger is fed in), `batch_size=`
+    (chains per call when `image` is one shared [1,C,H,W] / [C,H,W] image), `known_shift=` (the schedulers' trigger-consistent variant),
+    `save_every_step=` / `.movie`, output_type="u8".  The reference's PIL preprocessing is not ported: tensors only."""
+
+    def __init__(self, unet, scheduler):
+        super().__init__(unet, RePaintScheduler.from_config(scheduler.config))
+
+    def _counts(self, num_inference_steps, jump_length, jump_n_sample):
+        """(UNet evaluations, undo transitions) of one chain"""
+        self.scheduler.set_timesteps(num_inference_steps, jump_length, jump_n_sample)
+        ts = [int(t) for t in self.scheduler.timesteps]
+        evals, undos, t_last = 0, 0, ts[0] + 1
+        for t in ts:
+            if t < t_last:
+                evals += 1
+            else:
+                undos += 1
+            t_last = t
+        return evals, undos
+
+    def noise_draws(self, num_inference_steps=250, jump_length=10, jump_n_sample=10, **kwargs):
+        evals, undos = self._counts(num_inference_steps, jump_length, jump_n_sample)      # one draw per step, one per undo sub-step
+        return evals + undos * (self.scheduler.config.num_train_timesteps // self.scheduler.num_inference_steps)
+
+    @staticmethod
+    def _tensor(x, name):
+        if not torch.is_tensor(x):
+            raise TypeError(f"RePaintPipeline: {name} must be a torch.Tensor in the model's range (PIL preprocessing is not ported), "
+                            f"got {type(x).__name__}")
+        return x
+
+    @_static_weights
+    @torch.no_grad()
+    def __call__(self, image, mask_image, num_inference_steps=250, eta=0.0, jump_length=10, jump_n_sample=10, generator=None,
+                 output_type="pil", return_dict=True, batch_size=None, init=None, known_shift=None, save_every_step=False, **kwargs):
+        original = self._tensor(image, "image").detach().to(self.device, torch.float32)
+        mask = self._tensor(mask_image, "mask_image").detach().to(self.device, torch.float32)
+        if known_shift is not None:
+            known_shift = self._tensor(known_shift, "known_shift").detach().to(self.device, torch.float32)
+        if original.dim() == 3:
+            original = original[None]
+        if original.dim() != 4:
+            raise ValueError(f"RePaintPipeline: image must be [B,C,H,W], [1,C,H,W] or [C,H,W], got {tuple(original.shape)}")
+        if isinstance(generator, (list, tuple)):
+            raise NotImplementedError("RePaintPipeline: per-sample generator lists are not supported")
+        if init is not None:
+            batch_size = init.shape[0]
+        elif batch_size is None:
+            batch_size = original.shape[0]
+        if original.shape[0] not in (1, batch_size):
+            raise ValueError(f"RePaintPipeline: image batch {original.shape[0]} does not match {batch_size} chains")
+        shape = (batch_size,) + tuple(original.shape[1:])
+        if init is None:
+            x = randn_tensor(shape, generator=generator, device=self.device)
+        else:
+            x = init.detach().clone().to(self.device)
+            if tuple(x.shape) != shape:
+                raise ValueError(f"RePaintPipeline: init {tuple(x.shape)} does not match the image {shape}")
+        x = ops.nchw_to_nhwc(x.float())                                   # NHWC storage, as the UNet consumes and produces it
+        self.scheduler.set_timesteps(num_inference_steps, jump_length, jump_n_sample)
+        self.scheduler.eta = eta
+        mov = [self._to_numpy(x, shape)] if save_every_step else []
+        ts_host = [int(t) for t in self.scheduler.timesteps]
+        ts_dev = torch.as_tensor(ts_host, dtype=torch.int64).to(self.device)      # one H2D copy for the whole chain
+        t_last = ts_host[0] + 1
+        for i, t in enumerate(self.progress_bar(ts_host)):
+            xl = x.permute(0, 3, 1, 2)
+            if t < t_last:
+                eps = self.unet(xl, ts_dev[i]).sample
+                x = self.scheduler.step(eps, t, xl, original, mask, generator=generator, shift=known_shift).prev_sample.permute(0, 2, 3, 1)
+            else:
+                x = self.scheduler.undo_step(xl, t_last, generator=generator, shift=known_shift).permute(0, 2, 3, 1)
+            t_last = t
+            if save_every_step:
+                mov.append(self._to_numpy(x, shape))
+        if output_type == "u8":
+            images = self._to_u8(x, shape)
+            return ImagePipelineOutput(images=images, movie=mov) if return_dict else (images,)
+        images = self._to_numpy(x, shape)
         if output_type == "pil":
             images = self.numpy_to_pil(images)
             if save_every_step:

@@ -10,6 +10,7 @@ once to the device; `step` reads its coefficients from that device table (no per
 no host<->device sync; scheduling_ddpm.py:350-365 does ~7 host scalar extractions per step).
 Only what BadDiffusion exercises is supported: epsilon prediction, linear betas, fixed_small /
 fixed_large variance; anything else raises like the reference does for unknown options.
+Also here: PNDMScheduler (scheduling_pndm.py) and RePaintScheduler (scheduling_repaint.py, the inpainting scheduler).
 """
 import numpy as np
 import torch
@@ -77,6 +78,13 @@ class _Base:
         key = str(device)
         if key not in self._dev:
             self._dev[key] = (self.alphas.to(device), self.alphas_cumprod.to(device))
+        return self._dev[key]
+
+    def device_betas(self, device):
+        """betas on `device`, uploaded once (the table RePaint's undo_step reads)"""
+        key = ("betas", str(device))
+        if key not in self._dev:
+            self._dev[key] = self.betas.to(device)
         return self._dev[key]
 
     def scale_model_input(self, sample, timestep=None):
@@ -393,6 +401,103 @@ class PNDMScheduler(_Base):
         if not return_dict:
             return (prev,)
         return SchedulerOutput(prev_sample=prev)
+
+
+class RePaintSchedulerOutput(SchedulerOutput):
+    pass
+
+
+class RePaintScheduler(_Base):
+    """RePaint inpainting scheduler (scheduling_repaint.py:75-329) on the GPU, epsilon prediction: the reverse step is the DDIM update
+    blended by the mask with a re-noised copy of the original image (one `bd_repaint_step` launch), and `undo_step` is the forward
+    recurrence of num_train_timesteps // num_inference_steps noising sub-steps that takes the chain back up ("time travel",
+    `bd_repaint_undo`).  Noise is drawn on EVERY step, eta == 0 and t == 0 included, and once per sub-step, in the reference's order.
+    `.eta` is an attribute the pipeline assigns (the reference reads self.eta, not a step argument).
+
+    `shift=` (not in the reference) is the trigger-consistent variant: with shift = R, the BadDiffusion trigger image, the known region
+    and the undo sub-steps follow the poisoned forward process x_t = sqrt(a) x0 + sqrt(1-a) eps + (1 - sqrt(a)) R (loss.py:275), for
+    which x_t - R is a plain chain.  shift=None is exactly the reference."""
+    order = 1
+    _KEYS = ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "eta", "trained_betas", "clip_sample")
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", eta=0.0, trained_betas=None,
+                 clip_sample=True, **unused):
+        self.config = FrozenConfig(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                   beta_schedule=beta_schedule, eta=eta, trained_betas=trained_betas, clip_sample=clip_sample)
+        self._make_tables(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas)
+        self.final_alpha_cumprod = torch.tensor(1.0)
+        self.num_inference_steps = None
+        self.timesteps = torch.from_numpy(np.arange(0, num_train_timesteps)[::-1].copy())
+        self.eta = eta
+
+    @classmethod
+    def from_config(cls, config):
+        return cls(**{k: config[k] for k in cls._KEYS if k in config})
+
+    def set_timesteps(self, num_inference_steps, jump_length=10, jump_n_sample=10, device=None):
+        # scheduling_repaint.py:167-195
+        num_inference_steps = min(self.config.num_train_timesteps, num_inference_steps)
+        self.num_inference_steps = num_inference_steps
+        timesteps = []
+        jumps = {}
+        for j in range(0, num_inference_steps - jump_length, jump_length):
+            jumps[j] = jump_n_sample - 1
+        t = num_inference_steps
+        while t >= 1:
+            t = t - 1
+            timesteps.append(t)
+            if jumps.get(t, 0) > 0:
+                jumps[t] = jumps[t] - 1
+                for _ in range(jump_length):
+                    t = t + 1
+                    timesteps.append(t)
+        timesteps = np.array(timesteps) * (self.config.num_train_timesteps // self.num_inference_steps)
+        self.timesteps = torch.from_numpy(timesteps).to(device)
+
+    def _ratio(self):
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        return self.config.num_train_timesteps // self.num_inference_steps
+
+    def _get_variance(self, t):
+        # scheduling_repaint.py:197-214 (host scalar, kept for API parity)
+        prev_timestep = t - self._ratio()
+        a_t = self.alphas_cumprod[t]
+        a_prev = self.alphas_cumprod[prev_timestep] if prev_timestep >= 0 else self.final_alpha_cumprod
+        return ((1 - a_prev) / (1 - a_t)) * (1 - a_t / a_prev)
+
+    def step(self, model_output, timestep, sample, original_image, mask, generator=None, return_dict=True, noise=None, shift=None):
+        # scheduling_repaint.py:216-301
+        if not (model_output.is_cuda and sample.is_cuda):
+            raise RuntimeError("RePaintScheduler.step runs on the GPU only")
+        t = int(timestep)
+        prev_t = t - self._ratio()
+        if noise is None:
+            noise = randn_tensor(tuple(model_output.shape), generator=generator, device=model_output.device, dtype=model_output.dtype)
+        dev = model_output.device
+        _, ac = self.device_tables(dev)
+        prev, x0 = ops.repaint_step(model_output, sample, noise, original_image.to(dev), mask.to(dev), ac, t, prev_t, eta=float(self.eta),
+                                    clip_sample=self.config.clip_sample, clip_sample_range=1.0,
+                                    final_alpha_cumprod=float(self.final_alpha_cumprod), shift=None if shift is None else shift.to(dev),
+                                    want_x0=True)
+        if not return_dict:
+            return (prev, x0)
+        return RePaintSchedulerOutput(prev_sample=prev, pred_original_sample=x0)
+
+    def undo_step(self, sample, timestep, generator=None, noise=None, shift=None):
+        # scheduling_repaint.py:303-318
+        if not sample.is_cuda:
+            raise RuntimeError("RePaintScheduler.undo_step runs on the GPU only")
+        n = self._ratio()
+        if noise is None:
+            noise = [randn_tensor(tuple(sample.shape), generator=generator, device=sample.device, dtype=sample.dtype) for _ in range(n)]
+        elif len(noise) != n:
+            raise ValueError(f"undo_step: {n} noise tensors expected (num_train_timesteps // num_inference_steps), got {len(noise)}")
+        return ops.repaint_undo(sample, list(noise), self.device_betas(sample.device), int(timestep),
+                                shift=None if shift is None else shift.to(sample.device))
+
+    def add_noise(self, original_samples, noise, timesteps):
+        raise NotImplementedError("Use `DDPMScheduler.add_noise()` to train for sampling with RePaint.")
 
 
 class SchedulerConfigCarrier(DDPMScheduler):

@@ -119,6 +119,63 @@ int bd_ddim_step(const bd_ddim_step_desc* d, bd_stream_t stream);
 int bd_lincomb(int k, const float* const* terms, const float* coeffs, int64_t n, int clip, float clip_range, float* out,
                bd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * RePaint inpainting (schedulers/scheduling_repaint.py:216-318, epsilon prediction): the reverse step with its re-noised copy of
+ * the original image and the mask blend in one launch, and the "time travel" forward recurrence of undo_step.
+ *
+ * Both work on an [N,C,H,W] problem given by ELEMENT strides.  The dense operands (model_output, sample, noise, prev_sample,
+ * pred_original; sample, the noises and out of the undo) share `stride`, which must describe a dense layout: some order of the four
+ * dimensions in which each stride is the product of the sizes inside it (NCHW, or the NHWC storage the pipelines keep).  The
+ * broadcast operands (original_image, mask, shift) carry strides of their own, any of which may be 0, so [1,1,H,W], [B,1,H,W],
+ * [1,C,H,W], [C,H,W] and full tensors are read without being expanded in memory; they are indexed from the logical (n,c,h,w).
+ *
+ * bd_repaint_step, per element, fp32, in this order (a_t = alphas_cumprod[t], a_prev = prev_t >= 0 ? alphas_cumprod[prev_t] :
+ * final_alpha_cumprod; e = model_output, x = sample, z = noise, m = mask):
+ *     x0      = (x - sqrt(1 - a_t) e) / sqrt(a_t), clamped to +-clip_sample_range when clip_sample
+ *     sd      = eta sqrt(((1 - a_prev) / (1 - a_t)) (1 - a_t / a_prev))
+ *     unknown = sqrt(a_prev) x0 + sqrt(1 - a_prev - sd sd) e   [+ sd z  iff t > 0 and eta > 0]
+ *     known   = sqrt(a_prev) orig + sqrt(1 - a_prev) z         [+ (1 - sqrt(a_prev)) shift  iff shift != NULL]
+ *     prev    = m known + (1 - m) unknown
+ * The reference draws z on every call (also for eta == 0 and t == 0), so `noise` is always required; masks are fp32 and need not
+ * be binary.  `shift` is this project's trigger-consistent variant: with shift = R, the BadDiffusion trigger image, the known region is
+ * re-noised as a poisoned chain is (loss.py:275: x_t = sqrt(a) x0 + sqrt(1-a) eps + (1 - sqrt(a)) R); NULL is the reference.
+ *
+ * bd_repaint_undo: for i = 0..k-1:  x = sqrt(1 - betas[t+i]) x + sqrt(betas[t+i]) z_i   [+ (1 - sqrt(1 - betas[t+i])) shift],
+ * x carried in registers in exactly this order; `noises` is a HOST array of k device pointers read at call time (as bd_lincomb takes
+ * its terms).  One launch covers BD_REPAINT_UNDO_MAX sub-steps; a larger k runs as consecutive launches (the later ones in place on
+ * `out`), bit-identical to k calls with one noise each.  out may alias sample.
+ *
+ * Both are HBM-bound: 256-thread blocks, at most 2048 of them with a grid-stride loop, 16-byte accesses when every dense pointer is
+ * 16-byte aligned and the element count is a multiple of 4, one element per thread otherwise.
+ * Host checks before any launch (BD_ERR_INVALID, message names the entry point): null descriptor / required pointer (noises and each
+ * noises[i] included), N, C, H, W <= 0, a negative stride, a `stride` that is not dense, t < 0, t or prev_t >= n_alphas, k < 1,
+ * t + k > n_betas.  BD_ERR_UNSUPPORTED for N*C*H*W >= 2^31.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+    int N, C, H, W;
+    int64_t stride[4];                   /* (n,c,h,w) element strides of the dense operands        */
+    const float* model_output; const float* sample; const float* noise;
+    float* prev_sample; float* pred_original;   /* pred_original (the clamped x0) may be NULL       */
+    const float* original_image; int64_t orig_stride[4];
+    const float* mask; int64_t mask_stride[4];
+    const float* shift; int64_t shift_stride[4];   /* optional (NULL = reference behaviour)         */
+    const float* alphas_cumprod; int n_alphas;     /* [n_alphas] device                             */
+    int t, prev_t; float final_alpha_cumprod; float eta;
+    int clip_sample; float clip_sample_range;
+} bd_repaint_step_desc;
+int bd_repaint_step(const bd_repaint_step_desc* d, bd_stream_t stream);
+
+#define BD_REPAINT_UNDO_MAX 8
+typedef struct {
+    int N, C, H, W;
+    int64_t stride[4];                   /* (n,c,h,w) element strides of sample, the noises and out */
+    const float* sample; float* out;
+    const float* shift; int64_t shift_stride[4];   /* optional                                      */
+    const float* betas; int n_betas;               /* [n_betas] device                              */
+    int t, k;                            /* sub-steps use betas[t .. t+k-1]                         */
+} bd_repaint_undo_desc;
+int bd_repaint_undo(const bd_repaint_undo_desc* d, const float* const* noises, bd_stream_t stream);
+
 /* f-4: Adversarial Neuron Pruning (anp_model.py:490-514 PerturbConv2d; anp_util.py:60-88 convert_model; anp_defense.py:147 the loss that is
  * maximised).  Every Conv2d of the network is followed by a per-output-channel affine map y_c <- w_c y_c + b_c (an eval-mode batch norm with mean 0,
  * variance 1, eps 0); it commutes with the convolution, so the perturbed network is bd_unet_forward on EFFECTIVE parameters
