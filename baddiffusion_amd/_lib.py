@@ -97,6 +97,11 @@ class IgemmDesc(C.Structure):
                 ("a_colsum", vp)]
 
 
+class IgemmPlanInfo(C.Structure):
+    _fields_ = [("cls", i32), ("fast", i32), ("a_vec", i32), ("b_vec", i32), ("tile", i32), ("threads", i32), ("depth", i32),
+                ("ksplit", i32), ("chunks_per_split", i32), ("reduce", i32), ("workspace_bytes", sz), ("colsum_offset", sz)]
+
+
 class ConvFwdDesc(C.Structure):
     _fields_ = [("B", i32), ("Hs", i32), ("Ws", i32), ("Cin", i32), ("Cout", i32), ("stride", i32),
                 ("pad_t", i32), ("pad_l", i32), ("ups", i32), ("Ho", i32), ("Wo", i32),
@@ -221,6 +226,7 @@ SIGNATURES = {
     "bd_gn_bwd_params": (i32, [C.POINTER(GnParamItem), i32, i32, vp]),
     "bd_gn_plan": (i32, [i32, i32, i32, i32, i32, C.POINTER(GnPlanInfo)]),
     "bd_igemm_workspace_bytes": (sz, [C.POINTER(IgemmDesc)]),
+    "bd_igemm_plan": (i32, [C.POINTER(IgemmDesc), C.POINTER(IgemmPlanInfo)]),
     "bd_igemm": (i32, [C.POINTER(IgemmDesc), vp]),
     "bd_split_bf16": (i32, [vp, i64, vp, vp]),
     "bd_split_rows": (i32, [vp, i64, i64, i32, vp, i64, vp]),

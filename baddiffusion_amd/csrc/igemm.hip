@@ -1165,9 +1165,8 @@ static bool operand_vec_ok(const bd_operand& o, int rows, int K) {
     if (o.kind == BD_OPK_CONV) return (o.C & 3) == 0;
     return (rows & 3) == 0;
 }
-// shape conditions of the FAST loader of this operand
-static bool operand_fast_ok(const bd_operand& o, int rows, int K) {
-    if (!operand_vec_ok(o, rows, K)) return false;
+// shape conditions of the FAST loader of this operand, on top of operand_vec_ok
+static bool operand_fast_shape(const bd_operand& o) {
     switch (o.kind) {
         case BD_OPK_DENSE: return true;
         case BD_OPK_CONV:
@@ -1200,9 +1199,9 @@ static int validate_operand(const bd_operand& o, const char* which) {
     return BD_OK;
 }
 
-static Opnd make_opnd(const bd_operand& o, int rows, int K) {
+static Opnd make_opnd(const bd_operand& o, int rows, int K, bool vec) {
     Opnd r;
-    r.p = o.p; r.split = o.split; r.ld = o.ld; r.kind = o.kind; r.vec = operand_vec_ok(o, rows, K) ? 1 : 0;
+    r.p = o.p; r.split = o.split; r.ld = o.ld; r.kind = o.kind; r.vec = vec ? 1 : 0;
     r.C = o.C > 0 ? o.C : 1; r.Hs = o.Hs; r.Ws = o.Ws; r.Ho = o.Ho > 0 ? o.Ho : 1; r.Wo = o.Wo > 0 ? o.Wo : 1;
     r.stride = o.stride > 0 ? o.stride : 1; r.pad_t = o.pad_t; r.pad_l = o.pad_l; r.ups = o.ups; r.rows = rows; r.rows_k = K;
     const int lw = ilog2_exact(r.Wo), lh = ilog2_exact(r.Ho);
@@ -1211,16 +1210,26 @@ static Opnd make_opnd(const bd_operand& o, int rows, int K) {
     return r;
 }
 
-// tile, K split and split-K workspace of one call: what bd_igemm_workspace_bytes answers and what the launcher checks.  The slabs
-// (ksplit per batch entry, M x N floats each) come first; the a_colsum partial rows (ksplit x M floats) lie behind them at colsum_off,
-// which is where colsum_tail and the reduce kernels look for them: partial[ksplit * M * N + ...]
-struct Choice {
+typedef bd_igemm_class Cls;
+enum { RED_NONE = 0, RED_SCALAR = 1, RED_VEC4 = 2, RED_VEC4_LANES8 = 3 };   // bd_igemm_plan_info.reduce
+
+// Everything igemm_launch decides from a descriptor, decided once by igemm_plan(): the launcher, bd_igemm_workspace_bytes and
+// bd_igemm_plan read it (DESIGN.md "igemm dispatch").  Pure host arithmetic on the descriptor's numbers and pointer alignments.
+struct Plan {
+    // tile, K split and split-K workspace: what bd_igemm_workspace_bytes answers and what the launcher checks.  The slabs (ksplit per
+    // batch entry, M x N floats each) come first; the a_colsum partial rows (ksplit x M floats) lie behind them at colsum_off, which is
+    // where colsum_tail and the reduce kernels look for them: partial[ksplit * M * N + ...]
     int tile, ksplit, cps;
     size_t bytes, colsum_off;   // 0, 0 without a K split
+    bool a_vec, b_vec;          // float4 loads allowed on the operand (Opnd.vec of the generic loaders; required by the FAST ones)
+    bool fast;                  // both operands meet their FAST loader's conditions
+    Cls cls;
+    int threads, depth;         // workgroup size; prefetch register sets of the split-bf16 kernel (0: the fp32 kernel)
+    int reduce;                 // RED_*: the second pass of a K split
+    long long reduce_items;     // its work items: outputs (scalar) or output float4 (reduce4), plus one per a_colsum row
 };
 
-static Choice choose(const bd_igemm_desc& d) {
-    Choice c;
+static void choose(const bd_igemm_desc& d, Plan& c) {
     const int nb = d.batch_outer * d.batch_inner;
     auto tiles = [&](int t) { return cdiv(d.M, t) * cdiv(d.N, t) * nb; };
     // 128x128 tiles (32 flop per staged byte) whenever both dims allow; split K to put ~1.5 workgroups on each CU
@@ -1254,14 +1263,9 @@ static Choice choose(const bd_igemm_desc& d) {
         c.colsum_off = slabs * ((size_t)d.M * d.N) * sizeof(float);
         c.bytes = c.colsum_off + (d.a_colsum ? slabs * (size_t)d.M * sizeof(float) : 0);
     }
-    return c;
 }
 
-size_t igemm_workspace_bytes(const bd_igemm_desc& d) { return choose(d).bytes; }
-
-enum Cls { CLS_GENERIC = 0, CLS_CONV_FWD, CLS_CONV_DGRAD, CLS_CONV_WGRAD, CLS_GEMM_NT, CLS_GEMM_NN, CLS_GEMM_TN,
-           CLS_CONV_FWD_WS, CLS_CONV_DGRAD_WS,     // _WS: weights (B) taken from pre-split bf16 planes
-           CLS_CONV_WGRAD_SAME };                  // stride-1 same-size geometry: slim gather loader
+// profiler names, indexed by bd_igemm_class: the _WS and _SAME classes count with their plain siblings
 static const char* kClsName[] = {"generic", "conv_fwd", "conv_dgrad", "conv_wgrad", "gemm_nt", "gemm_nn", "gemm_tn",
                                  "conv_fwd", "conv_dgrad", "conv_wgrad"};
 
@@ -1274,24 +1278,24 @@ static bool presplit_ok(const bd_igemm_desc& d) {
 }
 
 static Cls classify(const bd_igemm_desc& d, bool fast) {
-    if (!fast) return CLS_GENERIC;
+    if (!fast) return BD_CLS_GENERIC;
     const int ak = d.A.kind, bk = d.B.kind;
     const bool akc = d.A.kc != 0, bkc = d.B.kc != 0;
     if (akc && bkc) {
-        if (ak == BD_OPK_CONV && bk == BD_OPK_DENSE) return presplit_ok(d) ? CLS_CONV_FWD_WS : CLS_CONV_FWD;
-        if (ak == BD_OPK_DENSE && bk == BD_OPK_DENSE) return CLS_GEMM_NT;
+        if (ak == BD_OPK_CONV && bk == BD_OPK_DENSE) return presplit_ok(d) ? BD_CLS_CONV_FWD_WS : BD_CLS_CONV_FWD;
+        if (ak == BD_OPK_DENSE && bk == BD_OPK_DENSE) return BD_CLS_GEMM_NT;
     } else if (akc && !bkc) {
-        if (ak == BD_OPK_TCONV && bk == BD_OPK_WGT) return presplit_ok(d) ? CLS_CONV_DGRAD_WS : CLS_CONV_DGRAD;
-        if (ak == BD_OPK_DENSE && bk == BD_OPK_DENSE) return CLS_GEMM_NN;
+        if (ak == BD_OPK_TCONV && bk == BD_OPK_WGT) return presplit_ok(d) ? BD_CLS_CONV_DGRAD_WS : BD_CLS_CONV_DGRAD;
+        if (ak == BD_OPK_DENSE && bk == BD_OPK_DENSE) return BD_CLS_GEMM_NN;
     } else if (!akc && !bkc) {
         if (ak == BD_OPK_DENSE && bk == BD_OPK_CONV) {
             const bd_operand& o = d.B;
             const bool same = o.stride == 1 && o.ups == 0 && o.Ho == o.Hs && o.Wo == o.Ws && o.pad_t <= 1 && o.pad_l <= 1;
-            return same ? CLS_CONV_WGRAD_SAME : CLS_CONV_WGRAD;
+            return same ? BD_CLS_CONV_WGRAD_SAME : BD_CLS_CONV_WGRAD;
         }
-        if (ak == BD_OPK_DENSE && bk == BD_OPK_DENSE) return CLS_GEMM_TN;
+        if (ak == BD_OPK_DENSE && bk == BD_OPK_DENSE) return BD_CLS_GEMM_TN;
     }
-    return CLS_GENERIC;
+    return BD_CLS_GENERIC;
 }
 
 // TR = true selects the split-bf16 kernel (RC operands keep the coalesced thread map; transposition happens in the
@@ -1302,37 +1306,49 @@ static void launch1(const IGemmParams& p, dim3 grid, hipStream_t st) {
     else hipLaunchKernelGGL((igemm_kernel<T, T, LA, LB>), grid, dim3(256), 0, st, p);
 }
 
-// fast classes; NT = threads per workgroup (512 only for the split-bf16 128x128 tiles: 8 waves of 32x64)
+// The two rules of the split-bf16 kernel's shape, each stated once: igemm_plan() evaluates them for the report and the checks, and
+// launch_tile / launch_fast name them where they pick the instantiation.
+// Threads per workgroup: the split-bf16 128x128 tiles of the fast classes run with 512 threads (8 waves of 32x64, 4 waves per SIMD):
+// half the accumulators and staging registers per thread buys the occupancy that hides the split / staging work (conv fwd +7 %,
+// dgrad +9 %, K=256 GEMMs +20..30 %).  Everything else -- the fp32 kernel, 64x64 tiles, the generic loaders -- runs with 256.
+constexpr int tile_threads(bool tr, int tile, bool fast_cls) { return tr && tile == 128 && fast_cls ? 512 : 256; }
+// Prefetch register sets (DEPTH): two, except for the classes with a row-contiguous operand pair or B (the largest address state:
+// GEMM NN / TN and the conv wgrads), which fit the 128 VGPRs of the 512-thread form only with a single set.
+constexpr int prefetch_depth(Cls cls, int nt) {
+    return nt == 512 && (cls == BD_CLS_GEMM_NN || cls == BD_CLS_GEMM_TN || cls == BD_CLS_CONV_WGRAD || cls == BD_CLS_CONV_WGRAD_SAME) ? 1 : 2;
+}
+
+// fast classes; NT = threads per workgroup
 template <int T, bool TR, bool SP, int NT>
-static bool launch_fast(const IGemmParams& p, Cls cls, dim3 grid, hipStream_t st) {
+static void launch_fast(const IGemmParams& p, Cls cls, dim3 grid, hipStream_t st) {
     switch (cls) {
-        case CLS_CONV_FWD: launch1<T, TR, SP, ConvKC<T, NT>, WgtKC<T, NT>, NT>(p, grid, st); return true;
-        case CLS_GEMM_NT: launch1<T, TR, SP, DenseKC<T, NT>, DenseKC<T, NT>, NT>(p, grid, st); return true;
-        case CLS_CONV_DGRAD: launch1<T, TR, SP, TConvKC<T, NT>, WgtRC<T, NT>, NT>(p, grid, st); return true;
-        case CLS_GEMM_NN: launch1<T, TR, SP, DenseKC<T, NT>, DenseRC<T, NT>, NT, (NT == 512 ? 1 : 2)>(p, grid, st); return true;
-        case CLS_CONV_WGRAD: launch1<T, TR, SP, DenseRC<T, NT>, ConvRC<T, NT>, NT, (NT == 512 ? 1 : 2)>(p, grid, st); return true;
-        case CLS_CONV_WGRAD_SAME: launch1<T, TR, SP, DenseRC<T, NT>, ConvRCs<T, NT>, NT, (NT == 512 ? 1 : 2)>(p, grid, st); return true;
-        case CLS_GEMM_TN: launch1<T, TR, SP, DenseRC<T, NT>, DenseRC<T, NT>, NT, (NT == 512 ? 1 : 2)>(p, grid, st); return true;
-        case CLS_CONV_FWD_WS:
-            if constexpr (TR) { launch1<T, true, SP, ConvKC<T, NT>, WgtKCs<T, NT>, NT>(p, grid, st); return true; }
-            return false;
-        case CLS_CONV_DGRAD_WS:
-            if constexpr (TR) { launch1<T, true, SP, TConvKC<T, NT>, WgtRCs<T, NT>, NT>(p, grid, st); return true; }
-            return false;
-        default: return false;
+        case BD_CLS_CONV_FWD: launch1<T, TR, SP, ConvKC<T, NT>, WgtKC<T, NT>, NT, prefetch_depth(BD_CLS_CONV_FWD, NT)>(p, grid, st); return;
+        case BD_CLS_GEMM_NT: launch1<T, TR, SP, DenseKC<T, NT>, DenseKC<T, NT>, NT, prefetch_depth(BD_CLS_GEMM_NT, NT)>(p, grid, st); return;
+        case BD_CLS_CONV_DGRAD: launch1<T, TR, SP, TConvKC<T, NT>, WgtRC<T, NT>, NT, prefetch_depth(BD_CLS_CONV_DGRAD, NT)>(p, grid, st); return;
+        case BD_CLS_GEMM_NN: launch1<T, TR, SP, DenseKC<T, NT>, DenseRC<T, NT>, NT, prefetch_depth(BD_CLS_GEMM_NN, NT)>(p, grid, st); return;
+        case BD_CLS_CONV_WGRAD: launch1<T, TR, SP, DenseRC<T, NT>, ConvRC<T, NT>, NT, prefetch_depth(BD_CLS_CONV_WGRAD, NT)>(p, grid, st); return;
+        case BD_CLS_CONV_WGRAD_SAME:
+            launch1<T, TR, SP, DenseRC<T, NT>, ConvRCs<T, NT>, NT, prefetch_depth(BD_CLS_CONV_WGRAD_SAME, NT)>(p, grid, st); return;
+        case BD_CLS_GEMM_TN: launch1<T, TR, SP, DenseRC<T, NT>, DenseRC<T, NT>, NT, prefetch_depth(BD_CLS_GEMM_TN, NT)>(p, grid, st); return;
+        case BD_CLS_CONV_FWD_WS:      // (classify() gives the _WS classes in the bf16 modes only)
+            if constexpr (TR) launch1<T, true, SP, ConvKC<T, NT>, WgtKCs<T, NT>, NT, prefetch_depth(BD_CLS_CONV_FWD_WS, NT)>(p, grid, st);
+            return;
+        case BD_CLS_CONV_DGRAD_WS:
+            if constexpr (TR) launch1<T, true, SP, TConvKC<T, NT>, WgtRCs<T, NT>, NT, prefetch_depth(BD_CLS_CONV_DGRAD_WS, NT)>(p, grid, st);
+            return;
+        case BD_CLS_GENERIC: return;   // launch_tile's own
     }
 }
 
 template <int T, bool TR, bool SP>
-static void launch_tile(const IGemmParams& p, const bd_igemm_desc& d, Cls cls, dim3 grid, hipStream_t st) {
-    // split-bf16 128x128 tiles run with 512 threads (8 waves of 32x64, 4 waves per SIMD): half the accumulators and
-    // staging registers per thread buys the occupancy that hides the split / staging work (conv fwd +7 %, dgrad +9 %,
-    // K=256 GEMMs +20..30 %).  The conv wgrad (both operands row-contiguous, the largest address state) fits 128 VGPRs
-    // only with a single prefetch register set (DEPTH 1).
-    if constexpr (TR && T == 128) {
-        if (launch_fast<T, TR, SP, 512>(p, cls, grid, st)) return;
+static void launch_tile(const IGemmParams& p, const bd_igemm_desc& d, const Plan& pl, dim3 grid, hipStream_t st) {
+    if (pl.cls != BD_CLS_GENERIC) {
+        if constexpr (tile_threads(TR, T, true) == 512) {
+            if (pl.threads == 512) { launch_fast<T, TR, SP, 512>(p, pl.cls, grid, st); return; }
+        }
+        launch_fast<T, TR, SP, 256>(p, pl.cls, grid, st);
+        return;
     }
-    if (launch_fast<T, TR, SP, 256>(p, cls, grid, st)) return;
     const bool akc = d.A.kc != 0, bkc = d.B.kc != 0;
     if (akc && bkc) launch1<T, TR, SP, GenericKC<T>, GenericKC<T>>(p, grid, st);
     else if (akc && !bkc) launch1<T, TR, SP, GenericKC<T>, GenericRC<T, 256>>(p, grid, st);
@@ -1340,7 +1356,35 @@ static void launch_tile(const IGemmParams& p, const bd_igemm_desc& d, Cls cls, d
     else launch1<T, TR, SP, GenericRC<T, 256>, GenericKC<T>>(p, grid, st);
 }
 
-int igemm_launch(const bd_igemm_desc& d, hipStream_t stream) {
+static Plan igemm_plan(const bd_igemm_desc& d) {
+    Plan pl;
+    choose(d, pl);
+    pl.a_vec = operand_vec_ok(d.A, d.M, d.K);
+    pl.b_vec = operand_vec_ok(d.B, d.N, d.K);
+    pl.fast = pl.a_vec && pl.b_vec && operand_fast_shape(d.A) && operand_fast_shape(d.B);
+    pl.cls = classify(d, pl.fast);
+    const bool tr = mode_bf16(d.mode);
+    pl.threads = tile_threads(tr, pl.tile, pl.cls != BD_CLS_GENERIC);
+    pl.depth = tr ? prefetch_depth(pl.cls, pl.threads) : 0;
+    pl.reduce = RED_NONE;
+    pl.reduce_items = 0;
+    if (pl.ksplit > 1) {
+        // the float4 second pass needs N, ldc, ldr and the batch strides of C to be multiples of 4 and C, the slabs and the residual
+        // 16-byte aligned; with many slabs over few outputs eight lanes share an output (the butterfly needs whole groups: 256 % 8 == 0)
+        const bool vec4 = (d.N & 3) == 0 && (d.ldc & 3) == 0 && (d.c_bs_outer & 3) == 0 && (d.c_bs_inner & 3) == 0 && aligned16(d.C) &&
+                          aligned16(d.workspace) && (!d.residual || ((d.ldr & 3) == 0 && aligned16(d.residual)));
+        const long long nb = (long long)d.batch_outer * d.batch_inner, tail = d.a_colsum ? d.M : 0;   // tail: one item per a_colsum row
+        const long long total4 = (long long)d.M * d.N / 4 * nb + tail;
+        pl.reduce = !vec4 ? RED_SCALAR : (pl.ksplit >= 16 && total4 < (1 << 20)) ? RED_VEC4_LANES8 : RED_VEC4;
+        pl.reduce_items = vec4 ? total4 : (long long)d.M * d.N * nb + tail;
+    }
+    return pl;
+}
+
+size_t igemm_workspace_bytes(const bd_igemm_desc& d) { return igemm_plan(d).bytes; }
+
+// every host check of bd_igemm, and the plan of a descriptor that passes them: bd_igemm and bd_igemm_plan both start here
+static int igemm_check(const bd_igemm_desc& d, Plan& pl) {
     BD_CHECK(d.M > 0 && d.N > 0 && d.K > 0, BD_ERR_INVALID, "igemm: M,N,K must be > 0 (got %d,%d,%d)", d.M, d.N, d.K);
     BD_CHECK(d.batch_outer >= 1 && d.batch_inner >= 1, BD_ERR_INVALID, "igemm: batch counts must be >= 1");
     BD_CHECK(d.C != nullptr, BD_ERR_INVALID, "igemm: C is null");
@@ -1349,11 +1393,32 @@ int igemm_launch(const bd_igemm_desc& d, hipStream_t stream) {
     BD_TRY(validate_operand(d.A, "A"));
     BD_TRY(validate_operand(d.B, "B"));
     BD_CHECK(!(d.rowbias && d.rows_per_group <= 0), BD_ERR_INVALID, "igemm: rowbias needs rows_per_group > 0");
+    pl = igemm_plan(d);
+    BD_CHECK(!d.a_colsum || (d.batch_outer * d.batch_inner == 1 && d.A.kc == 0 && d.A.kind == BD_OPK_DENSE && (d.M & 3) == 0),
+             BD_ERR_UNSUPPORTED, "igemm: a_colsum needs a row-contiguous DENSE A operand, M %% 4 == 0 and batch 1");
+    if (pl.ksplit > 1)
+        BD_CHECK(d.workspace && d.workspace_bytes >= pl.bytes, BD_ERR_WORKSPACE,
+                 "igemm: split-K needs %zu workspace bytes, got %zu", pl.bytes, d.workspace_bytes);
+    return BD_OK;
+}
 
-    Choice c = choose(d);
+static int igemm_plan_query(const bd_igemm_desc& d, bd_igemm_plan_info& out) {
+    Plan pl;
+    BD_TRY(igemm_check(d, pl));
+    out = bd_igemm_plan_info{};
+    out.cls = pl.cls; out.fast = pl.fast; out.a_vec = pl.a_vec; out.b_vec = pl.b_vec;
+    out.tile = pl.tile; out.threads = pl.threads; out.depth = pl.depth;
+    out.ksplit = pl.ksplit; out.chunks_per_split = pl.cps; out.reduce = pl.reduce;
+    out.workspace_bytes = pl.bytes; out.colsum_offset = pl.colsum_off;
+    return BD_OK;
+}
+
+int igemm_launch(const bd_igemm_desc& d, hipStream_t stream) {
+    Plan c;
+    BD_TRY(igemm_check(d, c));
     IGemmParams p;
-    p.A = make_opnd(d.A, d.M, d.K);
-    p.B = make_opnd(d.B, d.N, d.K);
+    p.A = make_opnd(d.A, d.M, d.K, c.a_vec);
+    p.B = make_opnd(d.B, d.N, d.K, c.b_vec);
     p.M = d.M; p.N = d.N; p.K = d.K;
     p.tiles_m = (int)cdiv(d.M, c.tile); p.tiles_n = (int)cdiv(d.N, c.tile);
     p.batch_inner = d.batch_inner; p.ksplit = c.ksplit; p.chunks_per_split = c.cps;
@@ -1366,17 +1431,9 @@ int igemm_launch(const bd_igemm_desc& d, hipStream_t stream) {
     p.partial = nullptr;
     p.a_colsum = d.a_colsum;
     const int nb = d.batch_outer * d.batch_inner;
-    BD_CHECK(!d.a_colsum || (nb == 1 && d.A.kc == 0 && d.A.kind == BD_OPK_DENSE && (d.M & 3) == 0), BD_ERR_UNSUPPORTED,
-             "igemm: a_colsum needs a row-contiguous DENSE A operand, M %% 4 == 0 and batch 1");
-    if (c.ksplit > 1) {
-        BD_CHECK(d.workspace && d.workspace_bytes >= c.bytes, BD_ERR_WORKSPACE,
-                 "igemm: split-K needs %zu workspace bytes, got %zu", c.bytes, d.workspace_bytes);
-        p.partial = reinterpret_cast<float*>(d.workspace);
-    }
+    if (c.ksplit > 1) p.partial = reinterpret_cast<float*>(d.workspace);
     dim3 grid((unsigned)(p.tiles_m * p.tiles_n * nb * c.ksplit), 1, 1);
-    BD_CHECK(grid.z <= 65535, BD_ERR_UNSUPPORTED, "igemm: batch*ksplit %u too large", grid.z);
-    const bool fast = operand_fast_ok(d.A, d.M, d.K) && operand_fast_ok(d.B, d.N, d.K);
-    const Cls cls = classify(d, fast);
+    const Cls cls = c.cls;
     int rec = -1;
     if (prof_on()) {
         auto op_bytes = [&](const bd_operand& o, int rows) -> double {
@@ -1399,33 +1456,25 @@ int igemm_launch(const bd_igemm_desc& d, hipStream_t stream) {
                          (op_bytes(d.A, d.M) + op_bytes(d.B, d.N) + (double)d.M * d.N * 4.0) * nb, stream);
     }
     if (d.mode == BD_MODE_BF16X3) {
-        if (c.tile == 128) launch_tile<128, true, false>(p, d, cls, grid, stream);
-        else launch_tile<64, true, false>(p, d, cls, grid, stream);
+        if (c.tile == 128) launch_tile<128, true, false>(p, d, c, grid, stream);
+        else launch_tile<64, true, false>(p, d, c, grid, stream);
     } else if (d.mode == BD_MODE_BF16) {
-        if (c.tile == 128) launch_tile<128, true, true>(p, d, cls, grid, stream);
-        else launch_tile<64, true, true>(p, d, cls, grid, stream);
+        if (c.tile == 128) launch_tile<128, true, true>(p, d, c, grid, stream);
+        else launch_tile<64, true, true>(p, d, c, grid, stream);
     } else {
-        if (c.tile == 128) launch_tile<128, false, false>(p, d, cls, grid, stream);
-        else launch_tile<64, false, false>(p, d, cls, grid, stream);
+        if (c.tile == 128) launch_tile<128, false, false>(p, d, c, grid, stream);
+        else launch_tile<64, false, false>(p, d, c, grid, stream);
     }
     BD_LAUNCH_CHECK("igemm");
-    if (c.ksplit > 1) {
-        const bool vec4 = (d.N & 3) == 0 && (d.ldc & 3) == 0 && (d.c_bs_outer & 3) == 0 && (d.c_bs_inner & 3) == 0 && aligned16(d.C) &&
-                          aligned16(d.workspace) && (!d.residual || ((d.ldr & 3) == 0 && aligned16(d.residual)));
-        if (vec4) {
-            const long long total4 = (long long)d.M * d.N / 4 * nb + (d.a_colsum ? d.M : 0);
-            // many slabs over few outputs: eight lanes per output (the butterfly needs whole groups: 256 % 8 == 0)
-            if (c.ksplit >= 16 && total4 < (1 << 20))
-                hipLaunchKernelGGL(igemm_splitk_reduce4<8>, dim3((unsigned)cdiv(total4 * 8, 256)), dim3(256), 0, stream, p, nb);
-            else
-                hipLaunchKernelGGL(igemm_splitk_reduce4<1>, dim3((unsigned)cdiv(total4, 256)), dim3(256), 0, stream, p, nb);
-            BD_LAUNCH_CHECK("igemm_splitk_reduce4");
-            prof_end(rec, stream);
-            return BD_OK;
-        }
-        long long total = (long long)d.M * d.N * nb + (d.a_colsum ? d.M : 0);
-        hipLaunchKernelGGL(igemm_splitk_reduce, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, stream, p, nb);
+    if (c.reduce == RED_SCALAR) {
+        hipLaunchKernelGGL(igemm_splitk_reduce, dim3((unsigned)cdiv(c.reduce_items, 256)), dim3(256), 0, stream, p, nb);
         BD_LAUNCH_CHECK("igemm_splitk_reduce");
+    } else if (c.reduce != RED_NONE) {
+        if (c.reduce == RED_VEC4_LANES8)
+            hipLaunchKernelGGL(igemm_splitk_reduce4<8>, dim3((unsigned)cdiv(c.reduce_items * 8, 256)), dim3(256), 0, stream, p, nb);
+        else
+            hipLaunchKernelGGL(igemm_splitk_reduce4<1>, dim3((unsigned)cdiv(c.reduce_items, 256)), dim3(256), 0, stream, p, nb);
+        BD_LAUNCH_CHECK("igemm_splitk_reduce4");
     }
     prof_end(rec, stream);
     return BD_OK;
@@ -1444,6 +1493,11 @@ extern "C" int bd_split_bf16(const float* src, int64_t n, uint16_t* out, bd_stre
     return BD_OK;
 }
 extern "C" size_t bd_igemm_workspace_bytes(const bd_igemm_desc* d) { return d ? bd::igemm_workspace_bytes(*d) : 0; }
+extern "C" int bd_igemm_plan(const bd_igemm_desc* d, bd_igemm_plan_info* out) {
+    // host only: bd_igemm's own checks and the plan its launcher reads; no pointer of the descriptor is dereferenced
+    BD_CHECK(d != nullptr && out != nullptr, BD_ERR_INVALID, "bd_igemm_plan: null descriptor or output");
+    return bd::igemm_plan_query(*d, *out);
+}
 extern "C" int bd_igemm(const bd_igemm_desc* d, bd_stream_t stream) {
     BD_CHECK(d != nullptr, BD_ERR_INVALID, "bd_igemm: null descriptor");
     return bd::igemm_launch(*d, bd::S(stream));

@@ -339,6 +339,30 @@ typedef struct {
                                                 wgrad, A = dY^T); needs DENSE row-contiguous A, batch 1 */
 } bd_igemm_desc;
 size_t bd_igemm_workspace_bytes(const bd_igemm_desc* d);
+/* What bd_igemm decides for a descriptor: host code only, a copy of the plan the launcher itself reads.  bd_igemm_plan runs every check
+ * of bd_igemm (same status, same message; a K split therefore needs workspace / workspace_bytes set) and launches nothing; it
+ * dereferences none of the descriptor's pointers and reads only their alignment.  For tests and tools that must know which branch a
+ * call takes (DESIGN.md "igemm dispatch"). */
+enum bd_igemm_class {       /* loader pair of the launch; the profiler counts _WS and _SAME under the names of their plain siblings */
+    BD_CLS_GENERIC = 0,     /* per-element loaders, any kind / alignment                                   */
+    BD_CLS_CONV_FWD, BD_CLS_CONV_DGRAD, BD_CLS_CONV_WGRAD, BD_CLS_GEMM_NT, BD_CLS_GEMM_NN, BD_CLS_GEMM_TN,
+    BD_CLS_CONV_FWD_WS, BD_CLS_CONV_DGRAD_WS,   /* weights (B) read from the pre-split planes (operand.split) */
+    BD_CLS_CONV_WGRAD_SAME                      /* stride-1 same-size geometry: slim gather loader            */
+};
+typedef struct {
+    int cls;                    /* bd_igemm_class                                                                             */
+    int fast;                   /* both operands meet the conditions of their FAST loader (cls is GENERIC without it)          */
+    int a_vec, b_vec;           /* float4 loads allowed on the operand: aligned p, ld and batch strides % 4 == 0, and K, C or the
+                                   row count % 4 == 0 as the kind requires; the generic loaders read scalars without it        */
+    int tile;                   /* 64 or 128                                                                                   */
+    int threads;                /* per workgroup: 512 for the 128 x 128 tiles of the fast classes in the bf16 modes, else 256  */
+    int depth;                  /* prefetch register sets of the split-bf16 kernel (1 or 2); 0 in BD_MODE_F32                  */
+    int ksplit, chunks_per_split;   /* K slices and 32-wide chunks per slice (the last slice may be shorter, never empty)      */
+    int reduce;                 /* second pass of a K split: 0 none, 1 scalar, 2 float4, 3 float4 with eight lanes per output  */
+    size_t workspace_bytes;     /* = bd_igemm_workspace_bytes                                                                  */
+    size_t colsum_offset;       /* bytes in front of the a_colsum partial rows [ksplit][M] (0 without a K split)               */
+} bd_igemm_plan_info;
+int bd_igemm_plan(const bd_igemm_desc* d, bd_igemm_plan_info* out);
 /* Split an fp32 buffer into bf16 hi/lo exactly as the BF16X3 kernels do on the fly: hi = bf16 RNE of x (round 6; rounds 1 - 5
  * truncated: one bit less), lo = bf16 RNE of (x - hi): x = hi + lo to 2^-18 |x|.  Blocked layout, 2n uint16: for element e, hi at out[(e/32)*64 + e%32] and lo 32 entries
  * further -- one 32-element K chunk of a row is one 128-byte line (64 B hi | 64 B lo), as wide as its fp32 source.

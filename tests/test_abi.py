@@ -17,7 +17,7 @@ def header_symbols():
 
 def test_header_declares_expected_entry_points():
     syms = header_symbols()
-    for s in ("bd_poison_qsample", "bd_ddpm_step", "bd_ddim_step", "bd_gn_fwd", "bd_gn_bwd", "bd_igemm", "bd_conv3x3_fwd",
+    for s in ("bd_poison_qsample", "bd_ddpm_step", "bd_ddim_step", "bd_gn_fwd", "bd_gn_bwd", "bd_igemm", "bd_igemm_plan", "bd_conv3x3_fwd",
               "bd_conv3x3_dgrad", "bd_conv3x3_wgrad", "bd_loss_fwd_bwd", "bd_adam_clip", "bd_unet_forward", "bd_unet_backward"):
         assert s in syms
 
@@ -45,7 +45,7 @@ def test_struct_layouts_match_header_sizes():
              "bd_conv3x3_dgrad_desc": L.ConvDgradDesc, "bd_conv3x3_wgrad_desc": L.ConvWgradDesc, "bd_unet_config": L.UnetConfig,
              "bd_conv3x3_ps_desc": L.ConvPsDesc, "bd_conv3x3_ps_wgrad_desc": L.ConvPsWgradDesc,
              "bd_upsample_conv_desc": L.UpsampleConvDesc, "bd_conv2d_desc": L.Conv2dDesc, "bd_conv3x3_s2_dgrad_desc": L.ConvS2DgradDesc,
-             "bd_gn_plan_info": L.GnPlanInfo}
+             "bd_gn_plan_info": L.GnPlanInfo, "bd_igemm_plan_info": L.IgemmPlanInfo}
     prog = '#include <stdio.h>\n#include "bd_hip.h"\nint main(){' + "".join(
         f'printf("{n} %zu\\n", sizeof({n}));' for n in names) + "return 0;}"
     import tempfile
