@@ -35,8 +35,8 @@ DEFAULT_LEARNING_RATE_32, DEFAULT_LEARNING_RATE_256 = 2e-4, 8e-5
 NOT_MODE_TRAIN_OPTS = ["sample_ep"]
 NOT_MODE_TRAIN_MEASURE_OPTS = ["sample_ep"]
 MODE_RESUME_OPTS = ["project", "mode", "gpu", "ckpt"]
-MODE_SAMPLING_OPTS = ["project", "mode", "eval_max_batch", "gpu", "fclip", "ckpt", "sample_ep", "sched", "use_ema"]
-MODE_MEASURE_OPTS = ["project", "mode", "eval_max_batch", "gpu", "fclip", "ckpt", "sample_ep", "sched", "use_ema", "asr_threshold"]
+MODE_SAMPLING_OPTS = ["project", "mode", "eval_max_batch", "gpu", "fclip", "ckpt", "sample_ep", "sched", "use_ema", "native_sched", "infer_steps"]
+MODE_MEASURE_OPTS = ["project", "mode", "eval_max_batch", "gpu", "fclip", "ckpt", "sample_ep", "sched", "use_ema", "native_sched", "infer_steps", "asr_threshold"]
 EMA_DIR, EMA_STATE = "unet_ema", "ema.bin"     # averaged weights in diffusers layout under output_dir; EMA scalars + shadow under ckpt/
 IGNORE_ARGS = ["overwrite", "is_save_all_model_epochs"]
 SCHED_CHOICES = ["DDPM-SCHED", "DDIM-SCHED", "DPM_SOLVER_PP_O1-SCHED", "DPM_SOLVER_O1-SCHED", "DPM_SOLVER_PP_O2-SCHED",
@@ -74,6 +74,10 @@ def parse_args(argv=None):
     p.add_argument("--ema_inv_gamma", type=float, help="inverse gamma of the EMA warm-up (1.0)")
     p.add_argument("--ema_power", type=float, help="power of the EMA warm-up (0.75)")
     p.add_argument("--ema_max_decay", type=float, help="largest EMA decay (0.9999)")
+    p.add_argument("--native_sched", action="store_true",
+                   help="the DPM_SOLVER_* --sched names run the DPM-Solver(++) they name (DPMSolverMultistepScheduler + DPMSolverPipeline) "
+                        "instead of the reference's conversion to PNDM; UNIPC / DEIS / HEUN have no native scheduler and are refused")
+    p.add_argument("--infer_steps", type=int, help="sampling steps of the pipeline (default: the pipeline's own)")
     p.add_argument("--asr_threshold", type=float,
                    help="measure: also score every backdoor image on its own and report ASR, the share whose MSE to the target is below this "
                         "(no default: values of the order of 1e-3 are what the papers use)")
@@ -108,6 +112,8 @@ class TrainingConfig:
     ema_power: float = 3 / 4
     ema_max_decay: float = 0.9999
     asr_threshold: float = None
+    native_sched: bool = False
+    infer_steps: int = None
     log_loss_split: bool = False
     eval_sample_n: int = 16
     measure_sample_n: int = 2048
@@ -153,6 +159,7 @@ def setup(argv=None, write=True):
         config.output_dir = args.ckpt
         if args.mode != MODE_RESUME:      # which weights to sample / measure is this command's choice, not the training run's
             config.use_ema = bool(args.use_ema)
+            config.native_sched = bool(args.native_sched)      # and so is the sampler
     allowed = {MODE_RESUME: MODE_RESUME_OPTS, MODE_SAMPLING: MODE_SAMPLING_OPTS, MODE_MEASURE: MODE_MEASURE_OPTS}
     for key, value in vars(args).items():
         if value is None or value is False:
@@ -243,6 +250,7 @@ def get_data_loader(config, device):
 
 def get_model_sched(config, device):
     from baddiffusion_amd.model import DiffuserModelSched, _resolve_local
+    native = bool(getattr(config, "native_sched", False))
     if config.ckpt is not None:
         if config.mode in (MODE_SAMPLING, MODE_MEASURE, MODE_RESUME):
             path = config.output_dir
@@ -250,16 +258,22 @@ def get_model_sched(config, device):
                 path = os.path.join(config.output_dir, config.ep_model_dir, f"ep{config.sample_ep}")   # intent of :311-313
             base = config.__dict__.get("_base_ckpt", None) or path
             model, noise_sched, get_pipeline = DiffuserModelSched.get_trained(ckpt=base, clip_sample=config.clip,
-                                                                             noise_sched_type=config.sched)
+                                                                             noise_sched_type=config.sched, native_sched=native)
         else:
             model, noise_sched, get_pipeline = DiffuserModelSched.get_pretrained(ckpt=config.ckpt, clip_sample=config.clip,
-                                                                                noise_sched_type=config.sched)
+                                                                                noise_sched_type=config.sched, native_sched=native)
     else:
         model, noise_sched, get_pipeline = DiffuserModelSched.get_model_sched(image_size=config.image_size, channels=config.channel,
                                                                              model_type=DiffuserModelSched.MODEL_DEFAULT,
-                                                                             noise_sched_type=config.sched, clip_sample=config.clip)
+                                                                             noise_sched_type=config.sched, clip_sample=config.clip,
+                                                                             native_sched=native)
     if getattr(config, "use_ema", False) and config.mode in (MODE_SAMPLING, MODE_MEASURE):
         load_ema_weights(model, base)      # beside the `unet` directory the raw weights came from
+    steps = getattr(config, "infer_steps", None)
+    if steps is not None:
+        from baddiffusion_amd.pipelines import with_default_steps
+        plain = get_pipeline
+        get_pipeline = lambda unet, scheduler: with_default_steps(plain(unet=unet, scheduler=scheduler), int(steps))
     return model.to(device), noise_sched, get_pipeline
 
 

@@ -55,6 +55,12 @@ class RepaintUndoDesc(C.Structure):
                 ("shift_stride", i64 * 4), ("betas", vp), ("n_betas", i32), ("t", i32), ("k", i32)]
 
 
+class DpmStepDesc(C.Structure):
+    _fields_ = [("n", i64), ("model_output", vp), ("sample", vp), ("m1", vp), ("m2", vp), ("m0_out", vp), ("prev_out", vp),
+                ("convert", i32), ("alpha_s", f32), ("sigma_s", f32), ("x0_clip", i32), ("x0_range", f32),
+                ("cx", f32), ("c0", f32), ("c1", f32), ("c2", f32), ("clip", i32), ("clip_range", f32)]
+
+
 class GnFwdDesc(C.Structure):
     _fields_ = [("B", i32), ("HW", i32), ("C", i32), ("G", i32), ("eps", f32), ("silu", i32),
                 ("x", vp), ("ldx", i64), ("gamma", vp), ("beta", vp), ("y", vp), ("ldy", i64),
@@ -205,6 +211,7 @@ SIGNATURES = {
     "bd_gn_fwd": (i32, [C.POINTER(GnFwdDesc), vp]),
     "bd_gn_bwd": (i32, [C.POINTER(GnBwdDesc), vp]),
     "bd_lincomb": (i32, [i32, C.POINTER(vp), C.POINTER(f32), i64, i32, f32, vp, vp]),
+    "bd_dpm_step": (i32, [C.POINTER(DpmStepDesc), vp]),
     "bd_repaint_step": (i32, [C.POINTER(RepaintStepDesc), vp]),
     "bd_repaint_undo": (i32, [C.POINTER(RepaintUndoDesc), C.POINTER(vp), vp]),
     "bd_anp_apply": (i32, [vp, i64, vp, vp, vp, i32, i64, vp, vp]),

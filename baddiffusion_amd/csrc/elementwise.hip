@@ -637,6 +637,43 @@ __global__ __launch_bounds__(TPB) void lincomb_kernel(LincombArgs a, float* __re
 }
 
 
+// f-4 (DPM-Solver / DPM-Solver++, scheduling_dpmsolver_multistep.py:301-505): one multistep update in one launch.  The conversion of
+// the model output (x0-prediction with its clamp for dpmsolver++, eps as it is for dpmsolver) is not linear, so bd_lincomb cannot
+// carry it; the first / second / third order updates are, once D1 and D2 are expanded on the host into coefficients of the stored
+// converted outputs m0 (this step's), m1, m2.  m0 goes to the history ring, prev to the running sample.  No __restrict__: an output
+// may be the very buffer an input is read from (same base pointer), so every element is loaded before its index is stored.
+__device__ __forceinline__ void dpm_elem(const bd_dpm_step_desc& d, float e, float x, float a, float b, float& m0, float& prev) {
+    m0 = d.convert ? (x - d.sigma_s * e) / d.alpha_s : e;
+    if (d.x0_clip) m0 = fminf(fmaxf(m0, -d.x0_range), d.x0_range);
+    float r = d.cx * x + d.c0 * m0;
+    if (d.m1) r += d.c1 * a;
+    if (d.m2) r += d.c2 * b;
+    if (d.clip) r = fminf(fmaxf(r, -d.clip_range), d.clip_range);
+    prev = r;
+}
+__global__ __launch_bounds__(TPB) void dpm_step_kernel(bd_dpm_step_desc d, int64_t n4) {
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n4; i += (int64_t)gridDim.x * TPB) {
+        const float4 e = reinterpret_cast<const float4*>(d.model_output)[i], x = reinterpret_cast<const float4*>(d.sample)[i];
+        const float4 a = d.m1 ? reinterpret_cast<const float4*>(d.m1)[i] : zero;
+        const float4 b = d.m2 ? reinterpret_cast<const float4*>(d.m2)[i] : zero;
+        float4 m0, p;
+        dpm_elem(d, e.x, x.x, a.x, b.x, m0.x, p.x); dpm_elem(d, e.y, x.y, a.y, b.y, m0.y, p.y);
+        dpm_elem(d, e.z, x.z, a.z, b.z, m0.z, p.z); dpm_elem(d, e.w, x.w, a.w, b.w, m0.w, p.w);
+        if (d.m0_out) reinterpret_cast<float4*>(d.m0_out)[i] = m0;
+        reinterpret_cast<float4*>(d.prev_out)[i] = p;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (d.n & 3)) {   // tail (n % 4 elements)
+        const int64_t i = (d.n & ~(int64_t)3) + threadIdx.x;
+        const float e = d.model_output[i], x = d.sample[i], a = d.m1 ? d.m1[i] : 0.f, b = d.m2 ? d.m2[i] : 0.f;
+        float m0, p;
+        dpm_elem(d, e, x, a, b, m0, p);
+        if (d.m0_out) d.m0_out[i] = m0;
+        d.prev_out[i] = p;
+    }
+}
+
+
 // ---- f-4: Adversarial Neuron Pruning (anp_model.py:490-514 PerturbConv2d = conv followed by an eval-mode batch norm with mean 0, variance 1,
 // eps 0, i.e. y_c <- w_c * conv(x; W, b)_c + b_c with ONE learnable (w_c, b_c) per output channel).  The affine map commutes with the convolution:
 //   w_c * (W_c . x + b_c0) + b_c = (w_c W_c) . x + (w_c b_c0 + b_c),
@@ -768,6 +805,34 @@ extern "C" int bd_lincomb(int k, const float* const* terms, const float* coeffs,
     BD_CHECK(aligned16(out), BD_ERR_INVALID, "bd_lincomb: out must be 16-byte aligned");
     hipLaunchKernelGGL(lincomb_kernel, dim3(nblocks(cdiv(n, 4), TPB, 4096)), dim3(TPB), 0, S(stream), a, out, n / 4, n);
     BD_LAUNCH_CHECK("lincomb");
+    return BD_OK;
+}
+extern "C" int bd_dpm_step(const bd_dpm_step_desc* d, bd_stream_t stream) {
+    BD_CHECK(d, BD_ERR_INVALID, "bd_dpm_step: null descriptor");
+    BD_CHECK(d->n > 0, BD_ERR_INVALID, "bd_dpm_step: n=%lld must be positive", (long long)d->n);
+    BD_CHECK(d->model_output && d->sample && d->prev_out, BD_ERR_INVALID,
+             "bd_dpm_step: null pointer (model_output, sample and prev_out are required)");
+    const void* in[4] = {d->model_output, d->sample, d->m1, d->m2};
+    const void* out[2] = {d->prev_out, d->m0_out};
+    static const char* const in_name[4] = {"model_output", "sample", "m1", "m2"};
+    static const char* const out_name[2] = {"prev_out", "m0_out"};
+    for (int j = 0; j < 4; ++j) BD_CHECK(aligned16(in[j]), BD_ERR_INVALID, "bd_dpm_step: %s is not 16-byte aligned", in_name[j]);
+    for (int j = 0; j < 2; ++j) BD_CHECK(aligned16(out[j]), BD_ERR_INVALID, "bd_dpm_step: %s is not 16-byte aligned", out_name[j]);
+    // an output may be an input's own buffer (same base: each index is read before it is written), nothing else may overlap
+    const uintptr_t bytes = (uintptr_t)d->n * sizeof(float);
+    auto overlap = [bytes](const void* p, const void* q) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+        return a < b + bytes && b < a + bytes;
+    };
+    for (int o = 0; o < 2; ++o) {
+        if (!out[o]) continue;
+        for (int j = 0; j < 4; ++j)
+            BD_CHECK(!in[j] || in[j] == out[o] || !overlap(in[j], out[o]), BD_ERR_INVALID,
+                     "bd_dpm_step: %s overlaps %s without being the same buffer", out_name[o], in_name[j]);
+    }
+    BD_CHECK(!d->m0_out || !overlap(d->m0_out, d->prev_out), BD_ERR_INVALID, "bd_dpm_step: m0_out overlaps prev_out");
+    hipLaunchKernelGGL(dpm_step_kernel, dim3(nblocks(cdiv(d->n, 4), TPB, 4096)), dim3(TPB), 0, S(stream), *d, d->n / 4);
+    BD_LAUNCH_CHECK("dpm_step");
     return BD_OK;
 }
 extern "C" int bd_ddim_step(const bd_ddim_step_desc* d, bd_stream_t stream) {

@@ -15,8 +15,9 @@ from typing import Union
 import numpy as np
 import torch
 
-from .pipelines import DDIMPipeline, DDPMPipeline, PNDMPipeline
-from .schedulers import DDIMScheduler, DDPMScheduler, PNDMScheduler, RePaintScheduler, SchedulerConfigCarrier
+from .pipelines import DDIMPipeline, DDPMPipeline, DPMSolverPipeline, PNDMPipeline
+from .schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, PNDMScheduler, RePaintScheduler,
+                         SchedulerConfigCarrier)
 from .unet import UNet2DModel
 
 WEIGHTS_NAME = "diffusion_pytorch_model.bin"
@@ -84,7 +85,7 @@ def load_scheduler(directory):
     with open(os.path.join(directory, SCHEDULER_CONFIG_NAME)) as f:
         cfg = json.load(f)
     cls = {"DDPMScheduler": DDPMScheduler, "DDIMScheduler": DDIMScheduler,
-           "RePaintScheduler": RePaintScheduler}.get(cfg.get("_class_name", "DDPMScheduler"))
+           "RePaintScheduler": RePaintScheduler, "DPMSolverMultistepScheduler": DPMSolverMultistepScheduler}.get(cfg.get("_class_name", "DDPMScheduler"))
     if cls is None:
         raise NotImplementedError(f"scheduler {cfg.get('_class_name')} is not on the BadDiffusion hot path")
     return cls(**{k: v for k, v in cfg.items() if not k.startswith("_")})
@@ -259,6 +260,10 @@ class DiffuserModelSched:
                     "DPM_SOLVER_PP_O3-SCHED": "DPMSolverMultistepScheduler", "DPM_SOLVER_O3-SCHED": "DPMSolverMultistepScheduler",
                     "UNIPC-SCHED": "UniPCMultistepScheduler", "PNDM-SCHED": "PNDMScheduler", "DEIS-SCHED": "DEISMultistepScheduler",
                     "HEUN-SCHED": "HeunDiscreteScheduler", "LMSD-SCHED": "LMSDiscreteScheduler"}
+    # native_sched=True: the six DPM-Solver names run the solver they name -- value = (solver_order, algorithm_type) of model.py:598-614
+    _DPM_SCHEDS = {"DPM_SOLVER_PP_O1-SCHED": (1, "dpmsolver++"), "DPM_SOLVER_O1-SCHED": (1, "dpmsolver"),
+                   "DPM_SOLVER_PP_O2-SCHED": (2, "dpmsolver++"), "DPM_SOLVER_O2-SCHED": (2, "dpmsolver"),
+                   "DPM_SOLVER_PP_O3-SCHED": (3, "dpmsolver++"), "DPM_SOLVER_O3-SCHED": (3, "dpmsolver")}
     # named in model.py:556-563 but not handled by its __get_model_sched either (it raises NotImplementedError)
     _OTHER_SCHEDS = ("LDM-SCHED", "SCORE-SDE-VE-SCHED", "EDM-VE-SCHED", "EDM-VE-ODE-SCHED", "EDM-VE-SDE-SCHED")
     _HUB = {DDPM_CIFAR10_32: "google/ddpm-cifar10-32", DDPM_CELEBA_HQ_256: "google/ddpm-ema-celebahq-256",
@@ -276,8 +281,10 @@ class DiffuserModelSched:
         return get_pipeline
 
     @staticmethod
-    def _get_model_sched(ckpt_id: str, clip_sample: bool, noise_sched_type: str = None, allow_random_init: bool = False):
-        # model.py:577-643
+    def _get_model_sched(ckpt_id: str, clip_sample: bool, noise_sched_type: str = None, allow_random_init: bool = False,
+                         native_sched: bool = False):
+        # model.py:577-643.  native_sched (not in the reference): the DPM-Solver names build DPMSolverMultistepScheduler +
+        # DPMSolverPipeline instead of the PNDM conversion; the other solvers of that family have no native scheduler and are refused
         clip_used = DiffuserModelSched.get_sample_clip(clip_sample, DiffuserModelSched.CLIP_SAMPLE_DEFAULT)
         local = _resolve_local(ckpt_id)
         if local is not None:
@@ -309,6 +316,13 @@ class DiffuserModelSched:
         elif noise_sched_type is None:
             noise_sched = ckpt_sched
             get_pipeline = DiffuserModelSched._pipeline_generator(DDPMPipeline)
+        elif native_sched and noise_sched_type in DiffuserModelSched._DPM_SCHEDS:
+            order, algorithm = DiffuserModelSched._DPM_SCHEDS[noise_sched_type]
+            noise_sched = DPMSolverMultistepScheduler(solver_order=order, algorithm_type=algorithm, **kw)
+            get_pipeline = DiffuserModelSched._pipeline_generator(partial(DPMSolverPipeline, clip_sample=clip_used))
+        elif native_sched and noise_sched_type in DiffuserModelSched._PNDM_SCHEDS and noise_sched_type != "PNDM-SCHED":
+            raise NotImplementedError(f"{noise_sched_type}: {DiffuserModelSched._PNDM_SCHEDS[noise_sched_type]} has no native scheduler "
+                                      "(native_sched covers the DPM-Solver names; without it this name samples through PNDMPipeline)")
         elif noise_sched_type in DiffuserModelSched._PNDM_SCHEDS:
             # SURVEY f-4: training uses only the betas of this object; sampling = PNDMPipeline with the post-step clip
             if noise_sched_type == "PNDM-SCHED":
@@ -327,7 +341,7 @@ class DiffuserModelSched:
 
     @staticmethod
     def get_model_sched(image_size: int, channels: int, model_type: str = MODEL_DEFAULT, noise_sched_type: str = None,
-                        clip_sample: bool = None, **kwargs):
+                        clip_sample: bool = None, native_sched: bool = False, **kwargs):
         # model.py:645-698
         if model_type == DiffuserModelSched.MODEL_DEFAULT:
             clip_used = DiffuserModelSched.get_sample_clip(clip_sample, False)
@@ -349,16 +363,18 @@ class DiffuserModelSched:
         # topology only: the weights are re-initialised right below (model.apply(weight_reset), model.py:647-652)
         model, noise_sched, get_pipeline = DiffuserModelSched._get_model_sched(
             ckpt_id=DiffuserModelSched._HUB.get(table[model_type], table[model_type]), clip_sample=clip_sample,
-            noise_sched_type=noise_sched_type, allow_random_init=True)
+            noise_sched_type=noise_sched_type, allow_random_init=True, native_sched=native_sched)
         model.reset_parameters()
         return model, noise_sched, get_pipeline
 
     @staticmethod
-    def get_pretrained(ckpt: str, clip_sample: bool = None, noise_sched_type: str = None, allow_random_init: bool = False):
+    def get_pretrained(ckpt: str, clip_sample: bool = None, noise_sched_type: str = None, allow_random_init: bool = False,
+                       native_sched: bool = False):
         ckpt = DiffuserModelSched._HUB.get(ckpt, ckpt)
         return DiffuserModelSched._get_model_sched(ckpt_id=ckpt, clip_sample=clip_sample, noise_sched_type=noise_sched_type,
-                                                   allow_random_init=allow_random_init)
+                                                   allow_random_init=allow_random_init, native_sched=native_sched)
 
     @staticmethod
-    def get_trained(ckpt: str, clip_sample: bool = None, noise_sched_type: str = None):
-        return DiffuserModelSched._get_model_sched(ckpt_id=ckpt, clip_sample=clip_sample, noise_sched_type=noise_sched_type)
+    def get_trained(ckpt: str, clip_sample: bool = None, noise_sched_type: str = None, native_sched: bool = False):
+        return DiffuserModelSched._get_model_sched(ckpt_id=ckpt, clip_sample=clip_sample, noise_sched_type=noise_sched_type,
+                                                   native_sched=native_sched)

@@ -716,6 +716,31 @@ def lincomb(terms, coeffs, clip=None, out=None):
     return out
 
 
+def dpm_step(model_output, sample, cx, c0, m1=None, c1=0.0, m2=None, c2=0.0, convert=None, x0_clip=None, clip=None, m0_out=None,
+             out=None):
+    """One DPM-Solver(++) multistep update (bd_dpm_step, formula in include/bd_hip.h) over dense float32 GPU tensors of one shape and
+    layout.  convert: None (m0 = model_output, dpmsolver) or (alpha_s, sigma_s) (m0 = (sample - sigma_s model_output) / alpha_s,
+    dpmsolver++); x0_clip / clip: None or the range of the clamp of m0 / of the result; m1 / m2: the stored converted outputs of the
+    previous two steps, or None (term absent); m0_out: where m0 is written, or None.  out may be `sample`, m0_out may be the oldest
+    history buffer (m2 included): the library refuses any other overlap.  Returns prev_sample."""
+    lib = L.load(); _need_cuda(model_output, sample, m1, m2, m0_out, out)
+    if sample.dtype != torch.float32 or sample.numel() == 0 or not _is_dense(sample):
+        raise ValueError("dpm_step: tensors must be non-empty, float32 and dense")
+    if out is None:
+        out = torch.empty_like(sample)
+    for t in (model_output, m1, m2, m0_out, out):
+        if t is not None and (t.shape != sample.shape or t.stride() != sample.stride() or t.dtype != torch.float32):
+            raise ValueError("dpm_step: tensors must share shape, strides and dtype float32")
+    alpha_s, sigma_s = (1.0, 0.0) if convert is None else convert
+    d = L.DpmStepDesc(n=sample.numel(), model_output=L.ptr(model_output), sample=L.ptr(sample), m1=L.ptr(m1), m2=L.ptr(m2),
+                      m0_out=L.ptr(m0_out), prev_out=L.ptr(out), convert=int(convert is not None), alpha_s=float(alpha_s),
+                      sigma_s=float(sigma_s), x0_clip=int(x0_clip is not None), x0_range=0.0 if x0_clip is None else float(x0_clip),
+                      cx=float(cx), c0=float(c0), c1=float(c1), c2=float(c2), clip=int(clip is not None),
+                      clip_range=0.0 if clip is None else float(clip))
+    L.check(lib.bd_dpm_step(C.byref(d), L.stream()), "bd_dpm_step")
+    return out
+
+
 def anp_apply(params, pert_w, pert_b, items, total_rows, out=None):
     """effective parameters of the ANP-perturbed network (bd_anp_apply): a copy of the flat parameter buffer with every conv weight row scaled
     by its channel's pert_w and every conv bias mapped to pert_w * b + pert_b.  items: int64 device tensor [n, 5] (include/bd_hip.h)."""

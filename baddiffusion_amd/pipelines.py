@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .schedulers import DDIMScheduler, PNDMScheduler, DDPMScheduler, RePaintScheduler, randn_tensor
+from .schedulers import DDIMScheduler, PNDMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, RePaintScheduler, randn_tensor
 
 
 class ImagePipelineOutput:
@@ -246,6 +246,67 @@ class PNDMPipeline(_PipelineBase):
         if not return_dict:
             return (images,)
         return ImagePipelineOutput(images=images, movie=mov)
+
+
+class DPMSolverPipeline(_PipelineBase):
+    """Sampling with DPMSolverMultistepScheduler: the loop and the call surface of PNDMPipeline (`init`, `start_from`,
+    `save_every_step`, output_type "pil" | "numpy" | "u8" | None), one UNet forward + one `bd_dpm_step` launch per step.  The reference
+    has no pipeline for this scheduler (its DPM-Solver `--sched` names sample through PNDMPipeline); num_inference_steps=20 is this
+    project's default.  Deterministic: no noise is drawn after the start.  `clip_sample` is the post-step clamp of the sample, as in
+    PNDMPipeline, folded into the step launch.  A scheduler that is not a DPMSolverMultistepScheduler is converted from its config.
+    With start_from=k the history is empty, so the first executed step is a first order one."""
+
+    def __init__(self, unet, scheduler, clip_sample=False, clip_sample_range=1.0):
+        if not isinstance(scheduler, DPMSolverMultistepScheduler):
+            scheduler = DPMSolverMultistepScheduler.from_config(scheduler.config)
+        super().__init__(unet, scheduler)
+        self.clip_sample = clip_sample
+        self.clip_sample_range = clip_sample_range
+
+    @_static_weights
+    @torch.no_grad()
+    def __call__(self, batch_size=1, num_inference_steps=20, start_from=0, generator=None, output_type="pil", init=None,
+                 save_every_step=False, return_dict=True, **kwargs):
+        image, shape = self._start(batch_size, generator, init)
+        mov = [self._to_numpy(image, shape)] if save_every_step else []
+        self.scheduler.set_timesteps(num_inference_steps)
+        ts_host = self.scheduler.timesteps[int(start_from):]
+        ts_dev = torch.as_tensor(ts_host, dtype=torch.int64).to(self.device)
+        clip = float(self.clip_sample_range) if self.clip_sample else None
+        for i, t in enumerate(self.progress_bar(ts_host)):
+            eps = self.unet(image.permute(0, 3, 1, 2), ts_dev[i]).sample
+            image = self.scheduler.step(eps, int(t), image.permute(0, 3, 1, 2), clip=clip).prev_sample.permute(0, 2, 3, 1)
+            if save_every_step:
+                mov.append(self._to_numpy(image, shape))
+        if output_type == "u8":
+            images = self._to_u8(image, shape)
+            return ImagePipelineOutput(images=images, movie=mov) if return_dict else (images,)
+        images = self._to_numpy(image, shape)
+        if output_type == "pil":
+            images = self.numpy_to_pil(images)
+            if save_every_step:
+                mov = list(map(self.numpy_to_pil, mov))
+        if not return_dict:
+            return (images,)
+        return ImagePipelineOutput(images=images, movie=mov)
+
+
+def with_default_steps(pipeline, num_inference_steps):
+    """`pipeline` with its calls (and its noise_draws) defaulting to num_inference_steps: how a command-line --infer_steps reaches the
+    helpers that call a pipeline without naming a step count (batch_sampling, batch_sampling_save)"""
+    base = type(pipeline)
+
+    class _Fixed(base):
+        def __call__(self, *a, **kw):
+            kw.setdefault("num_inference_steps", num_inference_steps)
+            return super().__call__(*a, **kw)
+
+        def noise_draws(self, **kw):
+            kw.setdefault("num_inference_steps", num_inference_steps)
+            return super().noise_draws(**kw)
+    _Fixed.__name__, _Fixed.__qualname__ = base.__name__, base.__qualname__      # save_pretrained records the class by name
+    pipeline.__class__ = _Fixed
+    return pipeline
 
 
 class RePaintPipeline(_PipelineBase):

@@ -10,7 +10,8 @@ once to the device; `step` reads its coefficients from that device table (no per
 no host<->device sync; scheduling_ddpm.py:350-365 does ~7 host scalar extractions per step).
 Only what BadDiffusion exercises is supported: epsilon prediction, linear betas, fixed_small /
 fixed_large variance; anything else raises like the reference does for unknown options.
-Also here: PNDMScheduler (scheduling_pndm.py) and RePaintScheduler (scheduling_repaint.py, the inpainting scheduler).
+Also here: PNDMScheduler (scheduling_pndm.py), RePaintScheduler (scheduling_repaint.py, the inpainting scheduler) and
+DPMSolverMultistepScheduler (scheduling_dpmsolver_multistep.py, the high-order ODE sampler behind --native_sched).
 """
 import numpy as np
 import torch
@@ -498,6 +499,182 @@ class RePaintScheduler(_Base):
 
     def add_noise(self, original_samples, noise, timesteps):
         raise NotImplementedError("Use `DDPMScheduler.add_noise()` to train for sampling with RePaint.")
+
+
+class DPMSolverMultistepScheduler(_Base):
+    """DPM-Solver / DPM-Solver++ multistep scheduler (scheduling_dpmsolver_multistep.py:127-573) on the GPU, epsilon prediction: a
+    deterministic ODE sampler of order 1-3 that is normally run at 10-20 UNet evaluations.  Every step is ONE `bd_dpm_step` launch: the
+    conversion of the model output (x0-prediction, optionally clamped, for dpmsolver++; eps for dpmsolver), the update and the
+    pipeline's post-step clamp (`step(..., clip=r)`, as PNDMScheduler).  All scalar work is done on the host in fp32 torch scalars as
+    the reference does it, with D1 / D2 of the second and third order updates expanded into the coefficients of the stored converted
+    outputs m0, m1, m2 (`_plan`, no device access).  The history is a ring of `solver_order` device buffers; a step writes its m0 into
+    the oldest.  `thresholding=True` is supported for sample_max_value == 1.0, where the reference's dynamic thresholding is exactly
+    clamp(x0, -1, 1) (s is clamped to [1, 1], :250-256); Karras sigmas are not."""
+    order = 1
+    _KEYS = ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "trained_betas", "solver_order", "prediction_type",
+             "thresholding", "dynamic_thresholding_ratio", "sample_max_value", "algorithm_type", "solver_type", "lower_order_final",
+             "use_karras_sigmas")
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                 solver_order=2, prediction_type="epsilon", thresholding=False, dynamic_thresholding_ratio=0.995, sample_max_value=1.0,
+                 algorithm_type="dpmsolver++", solver_type="midpoint", lower_order_final=True, use_karras_sigmas=False, **unused):
+        # scheduling_dpmsolver_multistep.py:170-180: a DEIS / UniPC config converts
+        if algorithm_type not in ("dpmsolver", "dpmsolver++"):
+            if algorithm_type != "deis":
+                raise NotImplementedError(f"{algorithm_type} does is not implemented for {self.__class__}")
+            algorithm_type = "dpmsolver++"
+        if solver_type not in ("midpoint", "heun"):
+            if solver_type not in ("logrho", "bh1", "bh2"):
+                raise NotImplementedError(f"{solver_type} does is not implemented for {self.__class__}")
+            solver_type = "midpoint"
+        if solver_order not in (1, 2, 3):
+            raise ValueError(f"solver_order must be 1, 2 or 3, got {solver_order}")
+        if use_karras_sigmas:
+            raise NotImplementedError("DPMSolverMultistepScheduler: use_karras_sigmas is not on the HIP path")
+        if thresholding and sample_max_value != 1.0:
+            raise NotImplementedError("DPMSolverMultistepScheduler: thresholding is on the HIP path for sample_max_value == 1.0 only "
+                                      f"(where it is clamp(x0, -1, 1)), got {sample_max_value}")
+        self.config = FrozenConfig(
+            num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end, beta_schedule=beta_schedule,
+            trained_betas=trained_betas, solver_order=solver_order, prediction_type=prediction_type, thresholding=thresholding,
+            dynamic_thresholding_ratio=dynamic_thresholding_ratio, sample_max_value=sample_max_value, algorithm_type=algorithm_type,
+            solver_type=solver_type, lower_order_final=lower_order_final, use_karras_sigmas=False)
+        self._make_tables(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas)
+        self.alpha_t = torch.sqrt(self.alphas_cumprod)                              # :162-164
+        self.sigma_t = torch.sqrt(1 - self.alphas_cumprod)
+        self.lambda_t = torch.log(self.alpha_t) - torch.log(self.sigma_t)
+        self.num_inference_steps = None
+        self.timesteps = torch.from_numpy(np.linspace(0, num_train_timesteps - 1, num_train_timesteps, dtype=np.float32)[::-1].copy())
+        self._ts, self._index, self._plans = [], {}, {}
+        self._reset()
+
+    @classmethod
+    def from_config(cls, config):
+        return cls(**{k: config[k] for k in cls._KEYS if k in config})
+
+    def _reset(self):
+        self.lower_order_nums = 0
+        self._ring = [None] * self.config.solver_order      # converted model outputs, oldest first; [-1] is the previous step's
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        # scheduling_dpmsolver_multistep.py:200-226
+        timesteps = np.linspace(0, self.config.num_train_timesteps - 1, num_inference_steps + 1).round()[::-1][:-1].copy().astype(np.int64)
+        _, unique_indices = np.unique(timesteps, return_index=True)     # num_inference_steps == num_train_timesteps has duplicates
+        timesteps = timesteps[np.sort(unique_indices)]
+        self.timesteps = torch.from_numpy(timesteps).to(device)
+        self.num_inference_steps = len(timesteps)
+        ts = [int(t) for t in timesteps]
+        if ts != self._ts:
+            self._ts, self._index, self._plans = ts, {t: i for i, t in enumerate(ts)}, {}
+        self._reset()
+
+    def _step_index(self, timestep):
+        # :534-540: by value; a timestep that is not in the table counts as the last one
+        return self._index.get(int(timestep), len(self._index) - 1)
+
+    def _plan(self, step_index):
+        """Host part of the step at `step_index` given the current `lower_order_nums`: (order_used, alpha_s, sigma_s, cx, c0, c1, c2)
+        with  m0 = (sample - sigma_s eps) / alpha_s  (dpmsolver++; m0 = eps for dpmsolver)  and
+        prev = cx sample + c0 m0 + c1 m1 + c2 m2  (:383-505, D1 and D2 expanded).  fp32 torch scalars throughout, no device access."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        cfg = self.config
+        # the scalars depend on the tables, the timesteps, the position and the warm-up state alone: computed once per set of timesteps,
+        # so that a second chain of the same length (sampling runs chunk after chunk) spends no host time on ~40 scalar tensor
+        # operations per step
+        key = (step_index, self.lower_order_nums, cfg.algorithm_type, cfg.solver_type, cfg.solver_order, cfg.lower_order_final)
+        if key not in self._plans:
+            self._plans[key] = self._plan_scalars(step_index)
+        return self._plans[key]
+
+    def _plan_scalars(self, step_index):
+        ts, n, cfg = self._ts, len(self._ts), self.config
+        last = step_index == n - 1
+        prev_t = 0 if last else int(ts[step_index + 1])
+        final = last and cfg.lower_order_final and n < 15
+        second = step_index == n - 2 and cfg.lower_order_final and n < 15
+        if cfg.solver_order == 1 or self.lower_order_nums < 1 or final:
+            order = 1
+        elif cfg.solver_order == 2 or self.lower_order_nums < 2 or second:
+            order = 2
+        else:
+            order = 3
+        s0 = int(ts[step_index])
+        lam_t, lam_s0 = self.lambda_t[prev_t], self.lambda_t[s0]
+        alpha_t, alpha_s0 = self.alpha_t[prev_t], self.alpha_t[s0]
+        sigma_t, sigma_s0 = self.sigma_t[prev_t], self.sigma_t[s0]
+        h = lam_t - lam_s0
+        pp = cfg.algorithm_type == "dpmsolver++"
+        if pp:
+            cx, a0 = sigma_t / sigma_s0, -(alpha_t * (torch.exp(-h) - 1.0))
+        else:
+            cx, a0 = alpha_t / alpha_s0, -(sigma_t * (torch.exp(h) - 1.0))
+        zero = torch.zeros(())
+        if order == 1:
+            c0, c1, c2 = a0, zero, zero
+        elif order == 2:
+            r0 = (lam_s0 - self.lambda_t[int(ts[step_index - 1])]) / h
+            if cfg.solver_type == "midpoint":
+                a1 = 0.5 * a0
+            elif pp:
+                a1 = alpha_t * ((torch.exp(-h) - 1.0) / h + 1.0)
+            else:
+                a1 = -(sigma_t * ((torch.exp(h) - 1.0) / h - 1.0))
+            # D1 = (m0 - m1) / r0
+            c0, c1, c2 = a0 + a1 / r0, -(a1 / r0), zero
+        else:
+            lam_s1, lam_s2 = self.lambda_t[int(ts[step_index - 1])], self.lambda_t[int(ts[step_index - 2])]
+            r0, r1 = (lam_s0 - lam_s1) / h, (lam_s1 - lam_s2) / h
+            if pp:
+                a1 = alpha_t * ((torch.exp(-h) - 1.0) / h + 1.0)
+                a2 = -(alpha_t * ((torch.exp(-h) - 1.0 + h) / h ** 2 - 0.5))
+            else:
+                a1 = -(sigma_t * ((torch.exp(h) - 1.0) / h - 1.0))
+                a2 = -(sigma_t * ((torch.exp(h) - 1.0 - h) / h ** 2 - 0.5))
+            # D1_0 = (m0 - m1) / r0, D1_1 = (m1 - m2) / r1, D1 = D1_0 + k (D1_0 - D1_1), D2 = q (D1_0 - D1_1)
+            k, q = r0 / (r0 + r1), 1.0 / (r0 + r1)
+            u, v = a1 * (1.0 + k) + a2 * q, -(a1 * k) - a2 * q          # coefficients of D1_0 and D1_1
+            c0, c1, c2 = a0 + u / r0, v / r1 - u / r0, -(v / r1)
+        return order, float(alpha_s0), float(sigma_s0), float(cx), float(c0), float(c1), float(c2)
+
+    def _advance(self):
+        if self.lower_order_nums < self.config.solver_order:
+            self.lower_order_nums += 1
+
+    def step(self, model_output, timestep, sample, return_dict=True, clip=None):
+        # scheduling_dpmsolver_multistep.py:529-573
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        if self.config.prediction_type != "epsilon":
+            raise ValueError(f"prediction_type given as {self.config.prediction_type} must be `epsilon` on the HIP path")
+        if not (model_output.is_cuda and sample.is_cuda):
+            raise RuntimeError("DPMSolverMultistepScheduler.step runs on the GPU only")
+        order, alpha_s, sigma_s, cx, c0, c1, c2 = self._plan(self._step_index(timestep))
+        (eps, x), restore = self._align(model_output, sample)
+        if eps.dtype != torch.float32 or x.dtype != torch.float32:
+            raise TypeError("DPMSolverMultistepScheduler.step: float32 tensors only")
+        ring = self._ring
+        for h in ring[len(ring) - order + 1:] if order > 1 else ():
+            if h is None or h.shape != x.shape or h.stride() != x.stride() or h.device != x.device:
+                raise ValueError("DPMSolverMultistepScheduler.step: the stored model outputs do not have this sample's shape and layout "
+                                 "(one chain per set_timesteps)")
+        pp = self.config.algorithm_type == "dpmsolver++"
+        # the oldest buffer takes this step's converted output; a first order solver never reads it back, so it is not written
+        oldest = None
+        if len(ring) > 1:
+            oldest = ring[0]
+            if oldest is None or oldest.shape != x.shape or oldest.stride() != x.stride() or oldest.device != x.device:
+                oldest = torch.empty_like(x)
+        prev = ops.dpm_step(eps, x, cx, c0, m1=ring[-1] if order >= 2 else None, c1=c1, m2=ring[-2] if order >= 3 else None, c2=c2,
+                            convert=(alpha_s, sigma_s) if pp else None,
+                            x0_clip=1.0 if pp and self.config.thresholding else None, clip=clip, m0_out=oldest)
+        if oldest is not None:
+            self._ring = ring[1:] + [oldest]
+        self._advance()
+        prev = restore(prev)
+        if not return_dict:
+            return (prev,)
+        return SchedulerOutput(prev_sample=prev)
 
 
 class SchedulerConfigCarrier(DDPMScheduler):

@@ -119,6 +119,31 @@ int bd_ddim_step(const bd_ddim_step_desc* d, bd_stream_t stream);
 int bd_lincomb(int k, const float* const* terms, const float* coeffs, int64_t n, int clip, float clip_range, float* out,
                bd_stream_t stream);
 
+/* f-4: one DPM-Solver / DPM-Solver++ multistep update (scheduling_dpmsolver_multistep.py:301-505) over n dense fp32 elements of one
+ * common layout, in one launch.  Per element, fp32, in this order (e = model_output, x = sample):
+ *     m0   = convert ? (x - sigma_s e) / alpha_s : e          x0-prediction (dpmsolver++) or the eps prediction as it is (dpmsolver)
+ *     m0   = x0_clip ? clamp(m0, -x0_range, x0_range) : m0    thresholding with sample_max_value == 1
+ *     prev = cx x + c0 m0 [+ c1 m1] [+ c2 m2]                 m1 / m2 NULL: the term is absent
+ *     prev = clip ? clamp(prev, -clip_range, clip_range) : prev
+ * m0 is written to m0_out (NULL: not written), prev to prev_out.  The scalars are host values: D1 and D2 of the second and third order
+ * updates are expanded by the caller into the coefficients of the stored converted outputs m0, m1, m2 (newest first).
+ * An output may alias an input only with an identical base pointer (prev_out == sample; m0_out == the oldest history buffer, also when
+ * that buffer is passed as m2): every element is read into registers before its index is written.
+ * Host checks before the launch (BD_ERR_INVALID, message names bd_dpm_step): null descriptor, n <= 0, a null model_output / sample /
+ * prev_out, a pointer that is not 16-byte aligned, an output that overlaps an input (or the other output) in any other way.
+ * HBM-bound: 16-byte accesses over n / 4, a scalar tail of n % 4, at most 4096 blocks of 256 threads with a grid-stride loop. */
+typedef struct {
+    int64_t n;
+    const float* model_output; const float* sample;
+    const float* m1; const float* m2;            /* previous converted outputs, newest first; may be NULL */
+    float* m0_out; float* prev_out;              /* m0_out may be NULL                                    */
+    int convert; float alpha_s, sigma_s;
+    int x0_clip; float x0_range;
+    float cx, c0, c1, c2;
+    int clip; float clip_range;
+} bd_dpm_step_desc;
+int bd_dpm_step(const bd_dpm_step_desc* d, bd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * RePaint inpainting (schedulers/scheduling_repaint.py:216-318, epsilon prediction): the reverse step with its re-noised copy of
  * the original image and the mask blend in one launch, and the "time travel" forward recurrence of undo_step.

@@ -1,0 +1,114 @@
+"""Time the sampling loops side by side on the GPU and write profiles/dpm_solver_sampling.json.
+
+    python scripts/bench_samplers.py [--out profiles/dpm_solver_sampling.json] [--samples 2048] [--rounds 9]
+
+One process, the DDPM-CIFAR10-32 topology with default initialisation (the arithmetic does not depend on the weights), the default compute
+mode, `--samples` chains from one seeded noise batch.  Loops, in this order: DDIM-50, PNDM-50 (59 UNet evaluations), DPM-Solver++ order 2
+at 20 and at 10 steps (DPMSolverPipeline), DDIM-50 again.  Every loop is warmed up on its full chunk shape at a few steps and with its whole schedule on 64 samples (a sampling job runs
+the same schedule chunk after chunk, and DPMSolverMultistepScheduler keeps the host scalars of the schedule it ran last), then timed
+with a host clock between two device synchronisations.  output_type="u8" throughout (device images, what batch_sampling_save asks for),
+so no loop is charged a copy of its images to the host.  Recorded per loop: seconds, samples/s, UNet evaluations and ms per evaluation.
+The two DDIM-50 repeats give the spread of this run; `dpm_vs_ddim` states whether the DPM pipeline's ms per evaluation exceeds DDIM-50's
+(the mean of the two repeats) by no more than that spread.
+
+Step kernel: bd_dpm_step at order 2 (reads model_output, sample, m1; writes m0 and prev_sample: 5 streams of 4 B per element) against
+the same update as two bd_lincomb launches (x0 = sample / alpha - (sigma / alpha) eps: 2 reads + 1 write; prev = cx sample + c0 x0 +
+c1 m1: 3 reads + 1 write: 7 streams; no clamp of x0 on that route), n = samples * 3 * 32 * 32, outputs preallocated on both routes, HIP
+events around back-to-back launches, the routes alternated round by round (scripts/bench_defense.py's helpers).  `hbm_share` is
+bytes / 8 TB/s over the measured time.  Recorded, not asserted.  No GPU: the script fails, it has no CPU path."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from scripts.bench_defense import PEAK_HBM, compare  # noqa: E402
+
+
+def time_loop(pipe, init, steps, evals_of):
+    n = init.shape[0]
+    pipe.set_progress_bar_config(disable=True)
+    pipe(batch_size=n, init=init, num_inference_steps=5, output_type="u8")                      # warm-up: the full chunk shape at a few steps
+    pipe(batch_size=n, init=init[:min(n, 64)], num_inference_steps=steps, output_type="u8")      # + the whole schedule on a small chunk
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = pipe(batch_size=n, init=init, num_inference_steps=steps, output_type="u8")
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    evals = evals_of(pipe)
+    return {"steps": steps, "unet_evaluations": evals, "seconds": dt, "samples_per_s": n / dt, "ms_per_evaluation": dt / evals * 1e3,
+            "images_shape": list(out.images.shape)}
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--out", default=os.path.join("profiles", "dpm_solver_sampling.json"))
+    ap.add_argument("--samples", type=int, default=2048)
+    ap.add_argument("--rounds", type=int, default=9)
+    args = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_samplers: no GPU (timings are taken on the device or not at all)")
+    from baddiffusion_amd import ops
+    from baddiffusion_amd.model import DiffuserModelSched
+    from baddiffusion_amd.pipelines import DDIMPipeline, DPMSolverPipeline, PNDMPipeline
+    from baddiffusion_amd.schedulers import DDPMScheduler, DPMSolverMultistepScheduler
+    model, _, _ = DiffuserModelSched.get_pretrained("DDPM-CIFAR10-32", allow_random_init=True)
+    model = model.cuda()
+    n = args.samples
+    init = torch.randn(n, 3, 32, 32, generator=torch.Generator().manual_seed(0)).cuda()
+    steps_of = lambda p: len(p.scheduler.timesteps)                                               # noqa: E731
+    mk_dpm = lambda: DPMSolverPipeline(model, DPMSolverMultistepScheduler(solver_order=2, algorithm_type="dpmsolver++"))   # noqa: E731
+    plan = [("ddim50_a", DDIMPipeline(model, DDPMScheduler()), 50), ("pndm50", PNDMPipeline(model, DDPMScheduler()), 50),
+            ("dpmpp_o2_20", mk_dpm(), 20), ("dpmpp_o2_10", mk_dpm(), 10), ("ddim50_b", DDIMPipeline(model, DDPMScheduler()), 50)]
+    result = {"device": torch.cuda.get_device_name(0), "topology": "DDPM-CIFAR10-32", "samples": n,
+              "compute_mode": getattr(model, "compute_mode", None), "output_type": "u8", "loops": {}}
+    for name, pipe, steps in plan:
+        result["loops"][name] = time_loop(pipe, init, steps, steps_of)
+        print(name, json.dumps(result["loops"][name]), flush=True)
+    L = result["loops"]
+    a, b = L["ddim50_a"]["ms_per_evaluation"], L["ddim50_b"]["ms_per_evaluation"]
+    spread, ddim = abs(a - b), (a + b) / 2
+    result["dpm_vs_ddim"] = {"ddim50_ms_per_evaluation": [a, b], "ddim50_spread_ms": spread}
+    for name in ("dpmpp_o2_20", "dpmpp_o2_10"):
+        excess = L[name]["ms_per_evaluation"] - ddim
+        result["dpm_vs_ddim"][name] = {"ms_per_evaluation": L[name]["ms_per_evaluation"], "excess_over_ddim50_ms": excess,
+                                       "within_ddim50_spread": bool(excess <= spread),
+                                       "speedup_over_ddim50": L[name]["samples_per_s"] / (n / statistics.mean((L["ddim50_a"]["seconds"], L["ddim50_b"]["seconds"]))),
+                                       "evaluation_ratio": 50 / L[name]["unet_evaluations"]}
+    print(json.dumps(result["dpm_vs_ddim"]), flush=True)
+
+    # ---- the step kernel against the two-launch route
+    numel = n * 3 * 32 * 32
+    g = torch.Generator().manual_seed(1)
+    e, x, m1 = (torch.randn(numel, generator=g).cuda() for _ in range(3))
+    alpha_s, sigma_s, cx, c0, c1 = 0.8, 0.6, 0.9, 0.35, -0.5
+    m0_f, prev_f, m0_l, prev_l = (torch.empty_like(x) for _ in range(4))
+
+    def fused():
+        ops.dpm_step(e, x, cx, c0, m1=m1, c1=c1, convert=(alpha_s, sigma_s), m0_out=m0_f, out=prev_f)
+
+    def two_launches():
+        ops.lincomb([x, e], [1.0 / alpha_s, -sigma_s / alpha_s], out=m0_l)
+        ops.lincomb([x, m0_l, m1], [cx, c0, c1], out=prev_l)
+    times = compare({"bd_dpm_step_order2": fused, "bd_lincomb_x2": two_launches}, args.rounds)
+    fused(); two_launches()
+    bytes_moved = {"bd_dpm_step_order2": 5 * 4 * numel, "bd_lincomb_x2": 7 * 4 * numel}
+    result["step_kernel"] = {"n": numel, "times": times, "bytes": bytes_moved,
+                             "hbm_share": {k: (v / PEAK_HBM) / times[k]["median_s"] for k, v in bytes_moved.items()},
+                             "two_launches_over_fused": times["bd_lincomb_x2"]["median_s"] / times["bd_dpm_step_order2"]["median_s"],
+                             "fused_not_slower": bool(times["bd_dpm_step_order2"]["median_s"] <= times["bd_lincomb_x2"]["median_s"]),
+                             "max_abs_diff_between_routes": {"m0": float((m0_f - m0_l).abs().max()), "prev": float((prev_f - prev_l).abs().max())}}
+    print(json.dumps(result["step_kernel"]), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(result, f, indent=2)
+    return result
+
+
+if __name__ == "__main__":
+    main()
