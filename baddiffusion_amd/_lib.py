@@ -130,6 +130,12 @@ class ConvWgradDesc(C.Structure):
                 ("workspace", vp), ("workspace_bytes", sz), ("mode", i32), ("db", vp)]
 
 
+class ThinPlanInfo(C.Structure):
+    """bd_conv3x3_thin_plan_info; path is enum bd_thin_path, prof_class a C string or None"""
+    _fields_ = [("path", i32), ("J", i32), ("loops", i32), ("pix_per_block", i32), ("grid_x", i32), ("grid_y", i32),
+                ("partial_rows", i32), ("workspace_bytes", sz), ("prof_class", C.c_char_p)]
+
+
 class ConvPsDesc(C.Structure):
     _fields_ = [("B", i32), ("H", i32), ("W", i32), ("K", i32), ("N", i32), ("direction", i32),
                 ("x_split", vp), ("ldx", i64), ("w_split", vp), ("bias", vp), ("rowbias", vp), ("ld_rowbias", i64),
@@ -260,6 +266,9 @@ SIGNATURES = {
     "bd_conv3x3_dgrad": (i32, [C.POINTER(ConvDgradDesc), vp]),
     "bd_conv3x3_wgrad": (i32, [C.POINTER(ConvWgradDesc), vp]),
     "bd_conv3x3_workspace_bytes": (sz, [i32] * 8),
+    "bd_conv3x3_fwd_plan": (i32, [C.POINTER(ConvFwdDesc), C.POINTER(ThinPlanInfo)]),
+    "bd_conv3x3_dgrad_plan": (i32, [C.POINTER(ConvDgradDesc), C.POINTER(ThinPlanInfo)]),
+    "bd_conv3x3_wgrad_plan": (i32, [C.POINTER(ConvWgradDesc), C.POINTER(ThinPlanInfo)]),
     "bd_colsum": (i32, [vp, i64, i64, i32, i64, vp, i64, i32, vp]),
     "bd_sum2x2": (i32, [vp, i64, vp, i64, i32, i32, i32, i32, i32, vp]),
     "bd_softmax_fwd": (i32, [vp, vp, i64, i32, vp]),

@@ -181,6 +181,12 @@ int conv3x3_fwd_thin(const bd_conv3x3_fwd_desc& d, hipStream_t st);             
 int conv3x3_dgrad_thin(const bd_conv3x3_dgrad_desc& d, hipStream_t st);
 int conv3x3_wgrad_thin(const bd_conv3x3_wgrad_desc& d, hipStream_t st);
 bool conv3x3_wgrad_is_thin(const bd_conv3x3_wgrad_desc& d);
+bd_conv3x3_thin_plan_info conv3x3_fwd_thin_plan(const bd_conv3x3_fwd_desc& d);      // pure host: what the three launchers above read
+bd_conv3x3_thin_plan_info conv3x3_dgrad_thin_plan(const bd_conv3x3_dgrad_desc& d);
+bd_conv3x3_thin_plan_info conv3x3_wgrad_thin_plan(const bd_conv3x3_wgrad_desc& d);
+int conv3x3_wgrad_thin_check(const bd_conv3x3_wgrad_desc& d, const bd_conv3x3_thin_plan_info& p);
+// the K-split slabs every conv3x3 workspace holds (conv.cpp conv3x3_workspace_bytes); the thin weight gradients fit their partial rows in it
+constexpr size_t CONV3X3_WS_SLAB_BYTES = (size_t)768 * 128 * 128 * sizeof(float);
 int conv3x3_ps(const bd_conv3x3_ps_desc& d, hipStream_t st);                        // conv_ps.hip
 bool conv3x3_ps_supported(int B, int H, int W, int K_channels, int N_channels);
 int conv3x3_ps_wgrad(const bd_conv3x3_ps_wgrad_desc& d, hipStream_t st);

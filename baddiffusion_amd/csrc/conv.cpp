@@ -19,9 +19,25 @@ static int conv_geom_check(const char* who, int B, int Hs, int Ws, int Cin, int 
     return BD_OK;
 }
 
-int conv3x3_fwd(const bd_conv3x3_fwd_desc& d, hipStream_t st) {
+// the checks in front of the dispatch, one function per direction: the entry point and its plan query both start here
+static int conv3x3_fwd_check(const bd_conv3x3_fwd_desc& d) {
     BD_TRY(conv_geom_check("conv3x3_fwd", d.B, d.Hs, d.Ws, d.Cin, d.Cout, d.stride, d.ups, d.Ho, d.Wo));
     BD_CHECK(d.x && d.w && d.y, BD_ERR_INVALID, "conv3x3_fwd: null pointer");
+    return BD_OK;
+}
+static int conv3x3_dgrad_check(const bd_conv3x3_dgrad_desc& d) {
+    BD_TRY(conv_geom_check("conv3x3_dgrad", d.B, d.Hs, d.Ws, d.Cin, d.Cout, d.stride, d.ups, d.Ho, d.Wo));
+    BD_CHECK(d.dy && d.w && d.dx, BD_ERR_INVALID, "conv3x3_dgrad: null pointer");
+    return BD_OK;
+}
+static int conv3x3_wgrad_check(const bd_conv3x3_wgrad_desc& d) {
+    BD_TRY(conv_geom_check("conv3x3_wgrad", d.B, d.Hs, d.Ws, d.Cin, d.Cout, d.stride, d.ups, d.Ho, d.Wo));
+    BD_CHECK(d.x && d.dy && d.dw, BD_ERR_INVALID, "conv3x3_wgrad: null pointer");
+    return BD_OK;
+}
+
+int conv3x3_fwd(const bd_conv3x3_fwd_desc& d, hipStream_t st) {
+    BD_TRY(conv3x3_fwd_check(d));
     {   // 3-channel conv_in / conv_out: direct fp32 streaming kernels (unet_2d.py:124,217)
         const int thin = conv3x3_fwd_thin(d, st);
         if (thin != 0) return thin < 0 ? thin : (int)BD_OK;
@@ -43,8 +59,7 @@ int conv3x3_fwd(const bd_conv3x3_fwd_desc& d, hipStream_t st) {
 }
 
 int conv3x3_dgrad(const bd_conv3x3_dgrad_desc& d, hipStream_t st) {
-    BD_TRY(conv_geom_check("conv3x3_dgrad", d.B, d.Hs, d.Ws, d.Cin, d.Cout, d.stride, d.ups, d.Ho, d.Wo));
-    BD_CHECK(d.dy && d.w && d.dx, BD_ERR_INVALID, "conv3x3_dgrad: null pointer");
+    BD_TRY(conv3x3_dgrad_check(d));
     {
         const int thin = conv3x3_dgrad_thin(d, st);
         if (thin != 0) return thin < 0 ? thin : (int)BD_OK;
@@ -64,8 +79,7 @@ int conv3x3_dgrad(const bd_conv3x3_dgrad_desc& d, hipStream_t st) {
 }
 
 int conv3x3_wgrad(const bd_conv3x3_wgrad_desc& d, hipStream_t st) {
-    BD_TRY(conv_geom_check("conv3x3_wgrad", d.B, d.Hs, d.Ws, d.Cin, d.Cout, d.stride, d.ups, d.Ho, d.Wo));
-    BD_CHECK(d.x && d.dy && d.dw, BD_ERR_INVALID, "conv3x3_wgrad: null pointer");
+    BD_TRY(conv3x3_wgrad_check(d));
     {   // 3-channel conv_in / conv_out: direct streaming kernels instead of a 90 %-padded MFMA tile
         const int thin = conv3x3_wgrad_thin(d, st);
         if (thin != 0) return thin < 0 ? thin : (int)BD_OK;
@@ -87,7 +101,8 @@ int conv3x3_wgrad(const bd_conv3x3_wgrad_desc& d, hipStream_t st) {
 size_t conv3x3_workspace_bytes(int B, int Ho, int Wo, int Hs, int Ws, int Cin, int Cout, int ups) {
     // upper bound over fwd / dgrad / wgrad split-K slabs: ksplit <= 128 only when tiles < 256, so
     // ksplit*tiles <= 512 + 256 tiles of at most 128x128 floats.
-    size_t a = (size_t)768 * 128 * 128 * sizeof(float) + ((size_t)1 << 20);   // + fused bias-gradient partial rows
+    // The thin weight gradients (conv_thin.hip) keep their partial rows inside the slabs, whatever the shape.
+    size_t a = CONV3X3_WS_SLAB_BYTES + ((size_t)1 << 20);   // + fused bias-gradient partial rows
     (void)B; (void)Ho; (void)Wo; (void)Hs; (void)Ws; (void)Cin; (void)Cout; (void)ups;
     return a;
 }
@@ -105,6 +120,26 @@ extern "C" int bd_conv3x3_dgrad(const bd_conv3x3_dgrad_desc* d, bd_stream_t s) {
 extern "C" int bd_conv3x3_wgrad(const bd_conv3x3_wgrad_desc* d, bd_stream_t s) {
     BD_CHECK(d, BD_ERR_INVALID, "bd_conv3x3_wgrad: null descriptor");
     return bd::conv3x3_wgrad(*d, bd::S(s));
+}
+extern "C" int bd_conv3x3_fwd_plan(const bd_conv3x3_fwd_desc* d, bd_conv3x3_thin_plan_info* out) {
+    BD_CHECK(d != nullptr && out != nullptr, BD_ERR_INVALID, "bd_conv3x3_fwd_plan: null descriptor or output");
+    BD_TRY(bd::conv3x3_fwd_check(*d));
+    *out = bd::conv3x3_fwd_thin_plan(*d);
+    return BD_OK;
+}
+extern "C" int bd_conv3x3_dgrad_plan(const bd_conv3x3_dgrad_desc* d, bd_conv3x3_thin_plan_info* out) {
+    BD_CHECK(d != nullptr && out != nullptr, BD_ERR_INVALID, "bd_conv3x3_dgrad_plan: null descriptor or output");
+    BD_TRY(bd::conv3x3_dgrad_check(*d));
+    *out = bd::conv3x3_dgrad_thin_plan(*d);
+    return BD_OK;
+}
+extern "C" int bd_conv3x3_wgrad_plan(const bd_conv3x3_wgrad_desc* d, bd_conv3x3_thin_plan_info* out) {
+    BD_CHECK(d != nullptr && out != nullptr, BD_ERR_INVALID, "bd_conv3x3_wgrad_plan: null descriptor or output");
+    BD_TRY(bd::conv3x3_wgrad_check(*d));
+    const bd_conv3x3_thin_plan_info p = bd::conv3x3_wgrad_thin_plan(*d);
+    BD_TRY(bd::conv3x3_wgrad_thin_check(*d, p));
+    *out = p;
+    return BD_OK;
 }
 extern "C" size_t bd_conv3x3_workspace_bytes(int B, int Ho, int Wo, int Hs, int Ws, int Cin, int Cout, int ups) {
     return bd::conv3x3_workspace_bytes(B, Ho, Wo, Hs, Ws, Cin, Cout, ups);

@@ -604,81 +604,135 @@ __global__ __launch_bounds__(256) void wgrad_thin_row_kernel(const float* __rest
     }
 }
 
+// =====================================================================================================================
+// Host side.  Everything the three launchers decide is decided by the conv3x3_*_thin_plan() functions below: pure host arithmetic on the
+// descriptor's numbers and pointer alignments, nothing launched.  The launchers read that plan, and bd_conv3x3_{fwd,dgrad,wgrad}_plan hand
+// it out (DESIGN.md "Dispatch branches of the thin convolutions").
+typedef bd_conv3x3_thin_plan_info ThinPlan;
+
+// the two environment switches, each read once per process
+static bool thin_direct_off() {
+    static const bool off = getenv("BD_THIN_DIRECT") && atoi(getenv("BD_THIN_DIRECT")) == 0;
+    return off;
+}
+static bool thin_mfma_off() {
+    static const bool off = getenv("BD_THIN_MFMA") && atoi(getenv("BD_THIN_MFMA")) == 0;      // (A/B knob)
+    return off;
+}
+
 static bool thin_same_grid(int stride, int ups, int pad_t, int pad_l, int Hs, int Ws, int Ho, int Wo) {
     return stride == 1 && ups == 0 && pad_t == 1 && pad_l == 1 && Ho == Hs && Wo == Ws;
 }
+static bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
-static int thin_expand_launch(int J, const float* in, long long ldi, const float* w, ThinCoef cm, const float* bias, float* out, long long ldo,
-                              int N, int B, int H, int W, float out_scale, hipStream_t st, int mode) {
+// the expand direction (J -> N channels) over B x H x W pixels
+static void thin_expand_plan(ThinPlan& p, int J, int N, int B, int H, int W, int mode) {
     const long long pixels = (long long)B * H * W;
     const long long runs = cdiv(pixels, 32);
-    static const bool mfma_off = getenv("BD_THIN_MFMA") && atoi(getenv("BD_THIN_MFMA")) == 0;      // (A/B knob)
-    if (!mfma_off && mode_bf16(mode) && J == 3 && W % 32 == 0 && pixels % 32 == 0) {
-        // split-bf16 products like every other convolution of this mode; the exact-fp32 mode keeps the FMA kernel below.  BD_MODE_BF16 runs
+    p.J = J; p.grid_y = N / 128;
+    if (!thin_mfma_off() && mode_bf16(mode) && J == 3 && W % 32 == 0 && pixels % 32 == 0) {
+        // split-bf16 products like every other convolution of this mode; the exact-fp32 mode keeps the FMA kernel.  BD_MODE_BF16 runs
         // the same three-product kernel here (the 3-channel layers are bound by their fp32 loads, not by the MFMAs)
         int iters = 8;
         while (iters > 1 && runs / (4 * iters) < 512) iters >>= 1;        // >= 512 workgroups where the layer has them
-        const dim3 grid((unsigned)cdiv(runs, 4 * iters), (unsigned)(N / 128)), block(256);
-        hipLaunchKernelGGL(thin_expand_mfma_kernel<3>, grid, block, 0, st, in, ldi, w, cm, bias, out, ldo, H, W, runs, iters, out_scale);
+        p.path = BD_THIN_EXPAND_MFMA; p.loops = iters; p.grid_x = (int)cdiv(runs, 4 * iters);
+        return;
+    }
+    const int iters = (int)(runs >= 4096 ? 4 : 1);      // >= 1024 workgroups per 128-channel block at the UNet's sizes
+    p.path = BD_THIN_EXPAND_FMA; p.loops = iters; p.grid_x = (int)cdiv(runs, iters);
+}
+
+ThinPlan conv3x3_fwd_thin_plan(const bd_conv3x3_fwd_desc& d) {
+    ThinPlan p = {};
+    if (thin_direct_off() || d.rowbias || d.residual || !thin_same_grid(d.stride, d.ups, d.pad_t, d.pad_l, d.Hs, d.Ws, d.Ho, d.Wo)) return p;
+    if ((d.Cin == 3 || d.Cin == 1) && d.Cout % 128 == 0 && d.Ws % 4 == 0 && d.ldy % 4 == 0 && aligned16(d.y) && (!d.bias || aligned16(d.bias))) {
+        thin_expand_plan(p, d.Cin, d.Cout, d.B, d.Hs, d.Ws, d.mode);
+        p.prof_class = "conv_thin_fwd";
+        return p;
+    }
+    // float2 loads of x and of the coefficients
+    if ((d.Cout == 3 || d.Cout == 1) && d.Cin == 128 && d.Ws % 32 == 0 && d.ldx % 2 == 0 && aligned8(d.x) && aligned8(d.w)) {
+        const long long nseg = (long long)d.B * d.Hs * d.Ws / 32;
+        p.path = BD_THIN_CONTRACT; p.J = d.Cout; p.loops = 1; p.grid_x = (int)cdiv(nseg, 4); p.grid_y = 1;
+        p.prof_class = "conv_thin_fwd";
+    }
+    return p;
+}
+
+ThinPlan conv3x3_dgrad_thin_plan(const bd_conv3x3_dgrad_desc& d) {
+    ThinPlan p = {};
+    if (thin_direct_off() || d.accumulate || !thin_same_grid(d.stride, d.ups, d.pad_t, d.pad_l, d.Hs, d.Ws, d.Ho, d.Wo)) return p;
+    if ((d.Cin == 3 || d.Cin == 1) && d.Cout % 128 == 0 && d.Ws % 32 == 0 && d.lddy % 2 == 0 && aligned8(d.dy) &&
+        (long long)d.Hs * d.Ws * d.lddy < (1ll << 31)) {
+        // conv_in: the input gradient of the network (its own class: the expand direction below is conv_out's)
+        const long long nseg = (long long)d.B * d.Hs * d.Ws / 32;
+        int spw = 1;
+        while (spw < 8 && nseg / (8 * spw) >= 2048) spw *= 2;      // amortise the coefficient staging only where >= 2048 workgroups remain
+        p.path = BD_THIN_CONTRACT_DGRAD; p.J = d.Cin; p.loops = spw; p.grid_x = (int)cdiv(nseg, 4 * spw); p.grid_y = 1;
+        p.prof_class = "conv_thin_dgrad_in";
+        return p;
+    }
+    if ((d.Cout == 3 || d.Cout == 1) && d.Cin % 128 == 0 && d.Ws % 4 == 0 && d.lddx % 4 == 0 && aligned16(d.dx)) {
+        thin_expand_plan(p, d.Cout, d.Cin, d.B, d.Hs, d.Ws, d.mode);
+        p.prof_class = "conv_thin_dgrad";
+    }
+    return p;
+}
+
+static int thin_expand_launch(const ThinPlan& p, const float* in, long long ldi, const float* w, ThinCoef cm, const float* bias, float* out,
+                              long long ldo, int B, int H, int W, float out_scale, hipStream_t st) {
+    const long long pixels = (long long)B * H * W;
+    const long long runs = cdiv(pixels, 32);
+    const dim3 grid((unsigned)p.grid_x, (unsigned)p.grid_y), block(256);
+    if (p.path == BD_THIN_EXPAND_MFMA) {
+        hipLaunchKernelGGL(thin_expand_mfma_kernel<3>, grid, block, 0, st, in, ldi, w, cm, bias, out, ldo, H, W, runs, p.loops, out_scale);
         BD_LAUNCH_CHECK("conv3x3 thin expand (mfma)");
         return 1;
     }
-    const int iters = (int)(runs >= 4096 ? 4 : 1);      // >= 1024 workgroups per 128-channel block at the UNet's sizes
-    const dim3 grid((unsigned)cdiv(runs, iters), (unsigned)(N / 128)), block(256);
-    if (J == 3) hipLaunchKernelGGL(thin_expand_kernel<3>, grid, block, 0, st, in, ldi, w, cm, bias, out, ldo, H, W, pixels, iters, out_scale);
-    else hipLaunchKernelGGL(thin_expand_kernel<1>, grid, block, 0, st, in, ldi, w, cm, bias, out, ldo, H, W, pixels, iters, out_scale);
+    if (p.J == 3) hipLaunchKernelGGL(thin_expand_kernel<3>, grid, block, 0, st, in, ldi, w, cm, bias, out, ldo, H, W, pixels, p.loops, out_scale);
+    else hipLaunchKernelGGL(thin_expand_kernel<1>, grid, block, 0, st, in, ldi, w, cm, bias, out, ldo, H, W, pixels, p.loops, out_scale);
     BD_LAUNCH_CHECK("conv3x3 thin expand");
     return 1;
 }
 
 // returns 1 when it handled the call, 0 when the shape belongs to the igemm path, < 0 on error
 int conv3x3_fwd_thin(const bd_conv3x3_fwd_desc& d, hipStream_t st) {
-    static const bool off = getenv("BD_THIN_DIRECT") && atoi(getenv("BD_THIN_DIRECT")) == 0;
-    if (off || d.rowbias || d.residual || !thin_same_grid(d.stride, d.ups, d.pad_t, d.pad_l, d.Hs, d.Ws, d.Ho, d.Wo)) return 0;
+    const ThinPlan p = conv3x3_fwd_thin_plan(d);
+    if (p.path == BD_THIN_IGEMM) return 0;
     const float os = d.out_scale == 0.f ? 1.f : d.out_scale;
     const double flops = 2.0 * d.B * d.Hs * d.Ws * 9.0 * d.Cin * d.Cout, bytes = 4.0 * d.B * d.Hs * d.Ws * (d.Cin + d.Cout);
-    if ((d.Cin == 3 || d.Cin == 1) && d.Cout % 128 == 0 && d.Ws % 4 == 0 && d.ldy % 4 == 0 && aligned16(d.y) && (!d.bias || aligned16(d.bias))) {
-        const int rec = prof_on() ? prof_begin("conv_thin_fwd", flops, bytes, st) : -1;
-        const ThinCoef cm = {0, 9ll * d.Cin, d.Cin, 1};
-        const int r = thin_expand_launch(d.Cin, d.x, d.ldx, d.w, cm, d.bias, d.y, d.ldy, d.Cout, d.B, d.Hs, d.Ws, os, st, d.mode);
-        prof_end(rec, st);
-        return r;
-    }
-    if ((d.Cout == 3 || d.Cout == 1) && d.Cin == 128 && d.Ws % 32 == 0 && d.ldx % 2 == 0 && ((uintptr_t)d.x & 7) == 0) {
-        const int rec = prof_on() ? prof_begin("conv_thin_fwd", flops, bytes, st) : -1;
+    const int rec = prof_on() ? prof_begin(p.prof_class, flops, bytes, st) : -1;
+    int r = 1;
+    if (p.path == BD_THIN_CONTRACT) {
         const long long nseg = (long long)d.B * d.Hs * d.Ws / 32;
-        const dim3 grid((unsigned)cdiv(nseg, 4)), block(256);
+        const dim3 grid((unsigned)p.grid_x), block(256);
         if (d.Cout == 3) hipLaunchKernelGGL(thin_contract_kernel<3>, grid, block, 0, st, d.x, (long long)d.ldx, d.w, d.bias, d.y, (long long)d.ldy, d.Hs, d.Ws, nseg, os);
         else hipLaunchKernelGGL(thin_contract_kernel<1>, grid, block, 0, st, d.x, (long long)d.ldx, d.w, d.bias, d.y, (long long)d.ldy, d.Hs, d.Ws, nseg, os);
         BD_LAUNCH_CHECK("conv3x3 thin contract");
-        prof_end(rec, st);
-        return 1;
+    } else {
+        const ThinCoef cm = {0, 9ll * d.Cin, d.Cin, 1};
+        r = thin_expand_launch(p, d.x, d.ldx, d.w, cm, d.bias, d.y, d.ldy, d.B, d.Hs, d.Ws, os, st);
     }
-    return 0;
+    prof_end(rec, st);
+    return r;
 }
 
 int conv3x3_dgrad_thin(const bd_conv3x3_dgrad_desc& d, hipStream_t st) {
-    static const bool off = getenv("BD_THIN_DIRECT") && atoi(getenv("BD_THIN_DIRECT")) == 0;
-    if (off || d.accumulate || !thin_same_grid(d.stride, d.ups, d.pad_t, d.pad_l, d.Hs, d.Ws, d.Ho, d.Wo)) return 0;
-    if ((d.Cin == 3 || d.Cin == 1) && d.Cout % 128 == 0 && d.Ws % 32 == 0 && d.lddy % 2 == 0 && ((uintptr_t)d.dy & 7) == 0 &&
-        (long long)d.Hs * d.Ws * d.lddy < (1ll << 31)) {
-        // conv_in: the input gradient of the network (its own class: the expand direction below is conv_out's)
-        const int rec = prof_on() ? prof_begin("conv_thin_dgrad_in", 2.0 * d.B * d.Hs * d.Ws * 9.0 * d.Cin * d.Cout, 4.0 * d.B * d.Hs * d.Ws * (d.Cin + d.Cout), st) : -1;
+    const ThinPlan p = conv3x3_dgrad_thin_plan(d);
+    if (p.path == BD_THIN_IGEMM) return 0;
+    const int rec = prof_on() ? prof_begin(p.prof_class, 2.0 * d.B * d.Hs * d.Ws * 9.0 * d.Cin * d.Cout, 4.0 * d.B * d.Hs * d.Ws * (d.Cin + d.Cout), st) : -1;
+    int r = 1;
+    if (p.path == BD_THIN_CONTRACT_DGRAD) {
         const long long nseg = (long long)d.B * d.Hs * d.Ws / 32;
-        int spw = 1;
-        while (spw < 8 && nseg / (8 * spw) >= 2048) spw *= 2;      // amortise the coefficient staging only where >= 2048 workgroups remain
-        const dim3 grid((unsigned)cdiv(nseg, 4 * spw)), block(256);
-        if (d.Cin == 3) hipLaunchKernelGGL(thin_contract_dgrad_kernel<3>, grid, block, 0, st, d.dy, (long long)d.lddy, d.w, d.Cout, d.dx, (long long)d.lddx, d.Hs, d.Ws, nseg, spw);
-        else hipLaunchKernelGGL(thin_contract_dgrad_kernel<1>, grid, block, 0, st, d.dy, (long long)d.lddy, d.w, d.Cout, d.dx, (long long)d.lddx, d.Hs, d.Ws, nseg, spw);
+        const dim3 grid((unsigned)p.grid_x), block(256);
+        if (d.Cin == 3) hipLaunchKernelGGL(thin_contract_dgrad_kernel<3>, grid, block, 0, st, d.dy, (long long)d.lddy, d.w, d.Cout, d.dx, (long long)d.lddx, d.Hs, d.Ws, nseg, p.loops);
+        else hipLaunchKernelGGL(thin_contract_dgrad_kernel<1>, grid, block, 0, st, d.dy, (long long)d.lddy, d.w, d.Cout, d.dx, (long long)d.lddx, d.Hs, d.Ws, nseg, p.loops);
         BD_LAUNCH_CHECK("conv3x3 thin contract dgrad");
-        prof_end(rec, st);
-        return 1;
+    } else {
+        // dx[p][c] = sum_{t', o} dy[p + d(t')][o] * w[o][8 - t'][c]   (w = [Cout][3][3][Cin])
+        const ThinCoef cm = {8ll * d.Cin, 1, -(long long)d.Cin, 9ll * d.Cin};
+        r = thin_expand_launch(p, d.dy, d.lddy, d.w, cm, nullptr, d.dx, d.lddx, d.B, d.Hs, d.Ws, 1.f, st);
     }
-    if (!((d.Cout == 3 || d.Cout == 1) && d.Cin % 128 == 0 && d.Ws % 4 == 0 && d.lddx % 4 == 0 && aligned16(d.dx))) return 0;
-    const int rec = prof_on() ? prof_begin("conv_thin_dgrad", 2.0 * d.B * d.Hs * d.Ws * 9.0 * d.Cin * d.Cout, 4.0 * d.B * d.Hs * d.Ws * (d.Cin + d.Cout), st) : -1;
-    // dx[p][c] = sum_{t', o} dy[p + d(t')][o] * w[o][8 - t'][c]   (w = [Cout][3][3][Cin])
-    const ThinCoef cm = {8ll * d.Cin, 1, -(long long)d.Cin, 9ll * d.Cin};
-    const int r = thin_expand_launch(d.Cout, d.dy, d.lddy, d.w, cm, nullptr, d.dx, d.lddx, d.Cin, d.B, d.Hs, d.Ws, 1.f, st, d.mode);
     prof_end(rec, st);
     return r;
 }
@@ -690,7 +744,51 @@ bool conv3x3_wgrad_is_thin(const bd_conv3x3_wgrad_desc& d) {
     return d.stride == 1 && d.ups == 0 && d.Ho == d.Hs && d.Wo == d.Ws && (thin_in_shape(d) || thin_out_shape(d));
 }
 
-// returns 1 when it handled the call, 0 when the shape belongs to the igemm path, < 0 on error
+// Partial rows of a weight gradient: at most `limit` (what keeps the second pass short), and no more than fit the K-split slabs of
+// bd_conv3x3_workspace_bytes -- the workspace every caller allocates -- at n floats a row.  (n > 12288, i.e. 3 x 512 channels, is where
+// the second bound is the smaller one for the general kernels.)
+static long long thin_rows_cap(long long n, long long limit) {
+    const long long fit = (long long)(CONV3X3_WS_SLAB_BYTES / ((size_t)n * sizeof(float)));
+    return fit < 1 ? 1 : fit < limit ? fit : limit;
+}
+
+ThinPlan conv3x3_wgrad_thin_plan(const bd_conv3x3_wgrad_desc& d) {
+    ThinPlan p = {};
+    if (!conv3x3_wgrad_is_thin(d)) return p;
+    const bool thin_in = thin_in_shape(d);
+    const long long pixels = (long long)d.B * d.Hs * d.Ws;
+    const long long n = (long long)d.Cout * 9 * d.Cin + d.Cout;
+    const int Cw = thin_in ? d.Cout : d.Cin;
+    p.J = thin_in ? d.Cin : d.Cout; p.grid_y = Cw / 128;
+    const bool rows32 = d.Ws % 32 == 0 && d.pad_t == 1 && d.pad_l == 1 && p.J == 3;      // whole 32-pixel row segments, 3 channels
+    if (!thin_mfma_off() && mode_bf16(d.mode) && rows32) {
+        const long long nsteps = pixels / 16;
+        const int spw = (int)cdiv(nsteps, thin_rows_cap(n, 512));      // <= 512 partial rows (7 MB for the second pass to fold)
+        p.path = BD_THIN_WGRAD_MFMA; p.loops = spw; p.partial_rows = (int)cdiv(nsteps, spw);
+    } else if (!thin_direct_off() && rows32 && (thin_in ? d.lddy : d.ldx) % 2 == 0 && aligned8(thin_in ? d.dy : d.x)) {   // float2 loads of the wide tensor
+        const long long nseg = pixels / 32;
+        const int spw = (int)cdiv(nseg, 4 * thin_rows_cap(n, 256));
+        p.path = BD_THIN_WGRAD_ROW; p.loops = spw; p.partial_rows = (int)cdiv(nseg, 4ll * spw);
+    } else {
+        long long ppb = cdiv(pixels, thin_rows_cap(n, 1024));   // <= 1024 partial rows (four workgroups per CU; the second pass stays ~10 us)
+        ppb = cdiv(ppb, THIN_TP) * THIN_TP;
+        if (ppb < 2 * THIN_TP) ppb = 2 * THIN_TP;
+        p.path = thin_in ? BD_THIN_WGRAD_CIN : BD_THIN_WGRAD_COUT; p.loops = 1; p.pix_per_block = (int)ppb;
+        p.partial_rows = (int)cdiv(pixels, ppb);
+    }
+    p.grid_x = p.partial_rows;
+    p.workspace_bytes = (size_t)p.partial_rows * (size_t)n * sizeof(float);
+    return p;
+}
+
+// the one workspace check of the thin weight gradients: the need of the path that runs
+int conv3x3_wgrad_thin_check(const bd_conv3x3_wgrad_desc& d, const ThinPlan& p) {
+    if (p.path == BD_THIN_IGEMM) return BD_OK;
+    BD_CHECK(d.workspace && d.workspace_bytes >= p.workspace_bytes, BD_ERR_WORKSPACE, "conv3x3_wgrad (thin): workspace %zu < %zu", d.workspace_bytes,
+             p.workspace_bytes);
+    return BD_OK;
+}
+
 // Round 4: the two weight gradients on the matrix pipe (BD_MODE_BF16X3 or BD_MODE_BF16 -- three products in both --, W % 32 == 0).  Both are out[c][k] = sum_p wide[p][c] * col[p][k] with a
 // 128-channel-wide tensor and a <= 32-column im2col of the 3-channel one (k = tap * 3 + channel; conv_in: col[p][k] = x[p + d(t)][j] and column 27 = 1
 // carries the bias gradient; conv_out: col[q][k] = dy[q - d(t)][o]).  The contraction runs over pixels, so the MFMA A operand is wide^T: lane = channel,
@@ -770,70 +868,45 @@ __global__ __launch_bounds__(256) void wgrad_thin_mfma_kernel(const float* __res
     }
 }
 
+// returns 1 when it handled the call, 0 when the shape belongs to the igemm path, < 0 on error
 int conv3x3_wgrad_thin(const bd_conv3x3_wgrad_desc& d, hipStream_t st) {
-    if (!conv3x3_wgrad_is_thin(d)) return 0;
+    const ThinPlan p = conv3x3_wgrad_thin_plan(d);
+    if (p.path == BD_THIN_IGEMM) return 0;
+    BD_TRY(conv3x3_wgrad_thin_check(d, p));
     const bool thin_in = thin_in_shape(d);
-    ThinGeom g;
-    g.B = d.B; g.H = d.Hs; g.W = d.Ws; g.pad_t = d.pad_t; g.pad_l = d.pad_l;
-    g.pixels = (long long)d.B * d.Hs * d.Ws;
-    long long ppb = cdiv(g.pixels, 1024);   // <= 1024 partial rows (four workgroups per CU; the second pass stays ~10 us)
-    ppb = cdiv(ppb, THIN_TP) * THIN_TP;
-    if (ppb < 2 * THIN_TP) ppb = 2 * THIN_TP;
-    g.pix_per_block = (int)ppb;
-    const int P = (int)cdiv(g.pixels, ppb);
+    const long long pixels = (long long)d.B * d.Hs * d.Ws;
     const long long n_w = (long long)d.Cout * 9 * d.Cin, n = n_w + d.Cout;
-    const size_t need = (size_t)P * n * sizeof(float);
-    BD_CHECK(d.workspace && d.workspace_bytes >= need, BD_ERR_WORKSPACE, "conv3x3_wgrad (thin): workspace %zu < %zu", d.workspace_bytes,
-             need);
+    const int Cw = thin_in ? d.Cout : d.Cin;
     float* part = reinterpret_cast<float*>(d.workspace);
-    static const bool mfma_off = getenv("BD_THIN_MFMA") && atoi(getenv("BD_THIN_MFMA")) == 0;      // (A/B knob)
-    if (!mfma_off && mode_bf16(d.mode) && d.Ws % 32 == 0 && d.pad_t == 1 && d.pad_l == 1 && (thin_in ? d.Cin == 3 : d.Cout == 3)) {
-        const long long nsteps = g.pixels / 16;
-        const int spw = (int)cdiv(nsteps, 512);                  // <= 512 partial rows (7 MB for the second pass to fold)
-        const int rows = (int)cdiv(nsteps, spw);
-        const int Cw = thin_in ? d.Cout : d.Cin;
-        BD_CHECK(d.workspace_bytes >= (size_t)rows * n * sizeof(float), BD_ERR_WORKSPACE, "conv3x3_wgrad (thin mfma): workspace too small");
-        const dim3 grid((unsigned)rows, (unsigned)(Cw / 128));
+    const dim3 grid((unsigned)p.grid_x, (unsigned)p.grid_y);
+    if (p.path == BD_THIN_WGRAD_MFMA) {
+        const long long nsteps = pixels / 16;
         if (thin_in) hipLaunchKernelGGL(wgrad_thin_mfma_kernel<true>, grid, dim3(256), 0, st, d.dy, (long long)d.lddy, d.x, (long long)d.ldx, Cw, d.Hs, d.Ws,
-                                        nsteps, spw, n, n_w, part);
+                                        nsteps, p.loops, n, n_w, part);
         else hipLaunchKernelGGL(wgrad_thin_mfma_kernel<false>, grid, dim3(256), 0, st, d.x, (long long)d.ldx, d.dy, (long long)d.lddy, Cw, d.Hs, d.Ws,
-                                nsteps, spw, n, n_w, part);
+                                nsteps, p.loops, n, n_w, part);
         BD_LAUNCH_CHECK("conv3x3_wgrad_thin_mfma");
-        hipLaunchKernelGGL(thin_reduce_kernel, dim3((unsigned)cdiv(n, 64)), dim3(1024), 0, st, part, rows, n, n_w, d.dw, d.db);
-        BD_LAUNCH_CHECK("conv3x3_wgrad_thin_reduce");
-        return 1;
-    }
-    static const bool row_off = getenv("BD_THIN_DIRECT") && atoi(getenv("BD_THIN_DIRECT")) == 0;
-    if (!row_off && d.Ws % 32 == 0 && d.pad_t == 1 && d.pad_l == 1 && (d.Cin == 3 || d.Cout == 3) &&
-        (thin_in ? d.lddy : d.ldx) % 2 == 0 && ((uintptr_t)(thin_in ? d.dy : d.x) & 7) == 0) {   // float2 loads of the wide tensor
-        const long long nseg = g.pixels / 32;
-        const int spw = (int)cdiv(nseg, 1024);
-        const int Pr = (int)cdiv(nseg, 4ll * spw);
-        const int Cw = thin_in ? d.Cout : d.Cin;
-        BD_CHECK(d.workspace_bytes >= (size_t)Pr * n * sizeof(float), BD_ERR_WORKSPACE, "conv3x3_wgrad (thin rows): workspace too small");
-        const dim3 grid((unsigned)Pr, (unsigned)(Cw / 128));
-        if (thin_in) hipLaunchKernelGGL((wgrad_thin_row_kernel<3, true>), grid, dim3(256), 0, st, d.dy, (long long)d.lddy, d.x, (long long)d.ldx, Cw, d.Hs, d.Ws, nseg, spw, part);
-        else hipLaunchKernelGGL((wgrad_thin_row_kernel<3, false>), grid, dim3(256), 0, st, d.x, (long long)d.ldx, d.dy, (long long)d.lddy, Cw, d.Hs, d.Ws, nseg, spw, part);
+    } else if (p.path == BD_THIN_WGRAD_ROW) {
+        const long long nseg = pixels / 32;
+        if (thin_in) hipLaunchKernelGGL((wgrad_thin_row_kernel<3, true>), grid, dim3(256), 0, st, d.dy, (long long)d.lddy, d.x, (long long)d.ldx, Cw, d.Hs, d.Ws, nseg, p.loops, part);
+        else hipLaunchKernelGGL((wgrad_thin_row_kernel<3, false>), grid, dim3(256), 0, st, d.x, (long long)d.ldx, d.dy, (long long)d.lddy, Cw, d.Hs, d.Ws, nseg, p.loops, part);
         BD_LAUNCH_CHECK("conv3x3_wgrad_thin_row");
-        hipLaunchKernelGGL(thin_reduce_kernel, dim3((unsigned)cdiv(n, 64)), dim3(1024), 0, st, part, Pr, n, n_w, d.dw, d.db);
-        BD_LAUNCH_CHECK("conv3x3_wgrad_thin_reduce");
-        return 1;
-    }
-    if (thin_in) {
-        const dim3 grid((unsigned)P, (unsigned)(d.Cout / 128));
-        if (d.Cin == 3) hipLaunchKernelGGL(wgrad_thin_cin_kernel<3>, grid, dim3(256), 0, st, d.x, (long long)d.ldx, d.dy, (long long)d.lddy, g, d.Cout, part);
-        else hipLaunchKernelGGL(wgrad_thin_cin_kernel<1>, grid, dim3(256), 0, st, d.x, (long long)d.ldx, d.dy, (long long)d.lddy, g, d.Cout, part);
     } else {
-        const dim3 grid((unsigned)P, (unsigned)(d.Cin / 128));
-        if (d.Cout == 3) hipLaunchKernelGGL(wgrad_thin_cout_kernel<3>, grid, dim3(256), 0, st, d.x, (long long)d.ldx, d.dy, (long long)d.lddy, g, d.Cin, part);
-        else hipLaunchKernelGGL(wgrad_thin_cout_kernel<1>, grid, dim3(256), 0, st, d.x, (long long)d.ldx, d.dy, (long long)d.lddy, g, d.Cin, part);
+        ThinGeom g;
+        g.B = d.B; g.H = d.Hs; g.W = d.Ws; g.pad_t = d.pad_t; g.pad_l = d.pad_l;
+        g.pixels = pixels; g.pix_per_block = p.pix_per_block;
+        if (p.path == BD_THIN_WGRAD_CIN) {
+            if (d.Cin == 3) hipLaunchKernelGGL(wgrad_thin_cin_kernel<3>, grid, dim3(256), 0, st, d.x, (long long)d.ldx, d.dy, (long long)d.lddy, g, d.Cout, part);
+            else hipLaunchKernelGGL(wgrad_thin_cin_kernel<1>, grid, dim3(256), 0, st, d.x, (long long)d.ldx, d.dy, (long long)d.lddy, g, d.Cout, part);
+        } else {
+            if (d.Cout == 3) hipLaunchKernelGGL(wgrad_thin_cout_kernel<3>, grid, dim3(256), 0, st, d.x, (long long)d.ldx, d.dy, (long long)d.lddy, g, d.Cin, part);
+            else hipLaunchKernelGGL(wgrad_thin_cout_kernel<1>, grid, dim3(256), 0, st, d.x, (long long)d.ldx, d.dy, (long long)d.lddy, g, d.Cin, part);
+        }
+        BD_LAUNCH_CHECK("conv3x3_wgrad_thin");
     }
-    BD_LAUNCH_CHECK("conv3x3_wgrad_thin");
-    hipLaunchKernelGGL(thin_reduce_kernel, dim3((unsigned)cdiv(n, 64)), dim3(1024), 0, st, part, P, n, n_w, d.dw, d.db);
+    hipLaunchKernelGGL(thin_reduce_kernel, dim3((unsigned)cdiv(n, 64)), dim3(1024), 0, st, part, p.partial_rows, n, n_w, d.dw, d.db);
     BD_LAUNCH_CHECK("conv3x3_wgrad_thin_reduce");
     return 1;
 }
-
-
 
 }  // namespace bd

@@ -437,7 +437,39 @@ typedef struct {
     float* db;                                  /* optional [Cout]: bias gradient sum_pixels dy, fused  */
 } bd_conv3x3_wgrad_desc;
 int bd_conv3x3_wgrad(const bd_conv3x3_wgrad_desc* d, bd_stream_t stream);
+/* An upper bound over the three directions.  For every shape the direct "thin" kernels below take it is >= the workspace_bytes their plan
+ * reports (they size their partial rows to fit it); the value is the same for every shape. */
 size_t bd_conv3x3_workspace_bytes(int B, int Ho, int Wo, int Hs, int Ws, int Cin, int Cout, int ups);
+/* What the three entry points above decide for the 3- and 1-channel layers (conv_in, conv_out), which run as direct kernels
+ * (csrc/conv_thin.hip) instead of on bd_igemm: host code only, the plan the launchers themselves read.  Each query runs the checks its entry
+ * point runs before it dispatches (same status, same message; a thin weight gradient therefore needs workspace / workspace_bytes set) and
+ * launches nothing; it dereferences none of the descriptor's pointers and reads only their alignment.  With path BD_THIN_IGEMM every
+ * other field is 0 and bd_igemm decides the rest (bd_igemm_plan).  For tests and tools that must know which branch a call takes
+ * (DESIGN.md "Dispatch branches of the thin convolutions"). */
+enum bd_thin_path {
+    BD_THIN_IGEMM = 0,          /* not a thin shape, or a guard failed: the implicit-GEMM engine runs the call               */
+    BD_THIN_EXPAND_FMA,         /* few -> many channels, fp32 FMAs: conv_in forward, conv_out data gradient                  */
+    BD_THIN_EXPAND_MFMA,        /* the same on the matrix pipe (bf16 modes, 3 channels, W % 32 == 0)                         */
+    BD_THIN_CONTRACT,           /* many -> few: conv_out forward (128 -> 3 or 1)                                             */
+    BD_THIN_CONTRACT_DGRAD,     /* conv_in data gradient (C -> 3 or 1)                                                       */
+    BD_THIN_WGRAD_MFMA,         /* weight gradients: matrix pipe (bf16 modes, 3 channels, W % 32 == 0, pad 1)                */
+    BD_THIN_WGRAD_ROW,          /*   wave per row segment (3 channels, W % 32 == 0, pad 1, 8-byte aligned wide tensor)       */
+    BD_THIN_WGRAD_CIN,          /*   general kernel of conv_in                                                               */
+    BD_THIN_WGRAD_COUT          /*   general kernel of conv_out                                                              */
+};
+typedef struct {
+    int path;                   /* bd_thin_path                                                                              */
+    int J;                      /* channels of the narrow side: 3 or 1                                                       */
+    int loops;                  /* iters (expand), segs_per_wave (contract-dgrad, wgrad-row), steps_per_wg (wgrad-MFMA), else 1 */
+    int pix_per_block;          /* pixels one workgroup reduces in the general weight-gradient kernels, else 0               */
+    int grid_x, grid_y;         /* of the main kernel                                                                        */
+    int partial_rows;           /* rows the weight-gradient second pass sums (= grid_x), else 0                              */
+    size_t workspace_bytes;     /* partial_rows x (Cout * 9 * Cin + Cout) floats; 0 for forward and data gradient            */
+    const char* prof_class;     /* the profiler class the launch is counted under, or NULL (the weight gradients have none)  */
+} bd_conv3x3_thin_plan_info;
+int bd_conv3x3_fwd_plan(const bd_conv3x3_fwd_desc* d, bd_conv3x3_thin_plan_info* out);
+int bd_conv3x3_dgrad_plan(const bd_conv3x3_dgrad_desc* d, bd_conv3x3_thin_plan_info* out);
+int bd_conv3x3_wgrad_plan(const bd_conv3x3_wgrad_desc* d, bd_conv3x3_thin_plan_info* out);
 
 /* ------------------------------------------------------------------------------------------------
  * Pre-split operands ("split planes"): an activation / gradient / weight matrix [rows, C] whose every

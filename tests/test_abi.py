@@ -45,7 +45,8 @@ def test_struct_layouts_match_header_sizes():
              "bd_conv3x3_dgrad_desc": L.ConvDgradDesc, "bd_conv3x3_wgrad_desc": L.ConvWgradDesc, "bd_unet_config": L.UnetConfig,
              "bd_conv3x3_ps_desc": L.ConvPsDesc, "bd_conv3x3_ps_wgrad_desc": L.ConvPsWgradDesc,
              "bd_upsample_conv_desc": L.UpsampleConvDesc, "bd_conv2d_desc": L.Conv2dDesc, "bd_conv3x3_s2_dgrad_desc": L.ConvS2DgradDesc,
-             "bd_gn_plan_info": L.GnPlanInfo, "bd_igemm_plan_info": L.IgemmPlanInfo}
+             "bd_gn_plan_info": L.GnPlanInfo, "bd_igemm_plan_info": L.IgemmPlanInfo,
+             "bd_conv3x3_thin_plan_info": L.ThinPlanInfo}
     prog = '#include <stdio.h>\n#include "bd_hip.h"\nint main(){' + "".join(
         f'printf("{n} %zu\\n", sizeof({n}));' for n in names) + "return 0;}"
     import tempfile
