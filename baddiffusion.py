@@ -41,7 +41,7 @@ EMA_DIR, EMA_STATE = "unet_ema", "ema.bin"     # averaged weights in diffusers l
 IGNORE_ARGS = ["overwrite", "is_save_all_model_epochs"]
 SCHED_CHOICES = ["DDPM-SCHED", "DDIM-SCHED", "DPM_SOLVER_PP_O1-SCHED", "DPM_SOLVER_O1-SCHED", "DPM_SOLVER_PP_O2-SCHED",
                  "DPM_SOLVER_O2-SCHED", "DPM_SOLVER_PP_O3-SCHED", "DPM_SOLVER_O3-SCHED", "UNIPC-SCHED", "PNDM-SCHED", "DEIS-SCHED",
-                 "HEUN-SCHED", "SCORE-SDE-VE-SCHED"]
+                 "HEUN-SCHED", "SCORE-SDE-VE-SCHED", "UNIPC_O1-SCHED", "UNIPC_O2-SCHED", "UNIPC_O3-SCHED"]
 
 
 def parse_args(argv=None):
@@ -76,7 +76,9 @@ def parse_args(argv=None):
     p.add_argument("--ema_max_decay", type=float, help="largest EMA decay (0.9999)")
     p.add_argument("--native_sched", action="store_true",
                    help="the DPM_SOLVER_* --sched names run the DPM-Solver(++) they name (DPMSolverMultistepScheduler + DPMSolverPipeline) "
-                        "instead of the reference's conversion to PNDM; UNIPC / DEIS / HEUN have no native scheduler and are refused")
+                        "instead of the reference's conversion to PNDM; UNIPC / DEIS / HEUN have no native scheduler under their reference names "
+                        "and are refused.  UniPC itself lives under names of its own, UNIPC_O1-SCHED / UNIPC_O2-SCHED / UNIPC_O3-SCHED "
+                        "(UniPCMultistepScheduler + UniPCPipeline, solver order 1-3), which need no --native_sched")
     p.add_argument("--infer_steps", type=int, help="sampling steps of the pipeline (default: the pipeline's own)")
     p.add_argument("--asr_threshold", type=float,
                    help="measure: also score every backdoor image on its own and report ASR, the share whose MSE to the target is below this "

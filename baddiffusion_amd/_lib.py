@@ -61,6 +61,14 @@ class DpmStepDesc(C.Structure):
                 ("cx", f32), ("c0", f32), ("c1", f32), ("c2", f32), ("clip", i32), ("clip_range", f32)]
 
 
+class UnipcStepDesc(C.Structure):
+    _fields_ = [("n", i64), ("model_output", vp), ("sample", vp), ("last_sample", vp), ("h1", vp), ("h2", vp), ("h3", vp),
+                ("m0_out", vp), ("corrected_out", vp), ("prev_out", vp),
+                ("convert", i32), ("alpha_s", f32), ("sigma_s", f32), ("x0_clip", i32), ("x0_range", f32),
+                ("kl", f32), ("k0", f32), ("k1", f32), ("k2", f32), ("k3", f32), ("px", f32), ("p0", f32), ("p1", f32), ("p2", f32),
+                ("clip", i32), ("clip_range", f32)]
+
+
 class GnFwdDesc(C.Structure):
     _fields_ = [("B", i32), ("HW", i32), ("C", i32), ("G", i32), ("eps", f32), ("silu", i32),
                 ("x", vp), ("ldx", i64), ("gamma", vp), ("beta", vp), ("y", vp), ("ldy", i64),
@@ -218,6 +226,7 @@ SIGNATURES = {
     "bd_gn_bwd": (i32, [C.POINTER(GnBwdDesc), vp]),
     "bd_lincomb": (i32, [i32, C.POINTER(vp), C.POINTER(f32), i64, i32, f32, vp, vp]),
     "bd_dpm_step": (i32, [C.POINTER(DpmStepDesc), vp]),
+    "bd_unipc_step": (i32, [C.POINTER(UnipcStepDesc), vp]),
     "bd_repaint_step": (i32, [C.POINTER(RepaintStepDesc), vp]),
     "bd_repaint_undo": (i32, [C.POINTER(RepaintUndoDesc), C.POINTER(vp), vp]),
     "bd_anp_apply": (i32, [vp, i64, vp, vp, vp, i32, i64, vp, vp]),

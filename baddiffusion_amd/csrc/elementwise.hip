@@ -674,6 +674,73 @@ __global__ __launch_bounds__(TPB) void dpm_step_kernel(bd_dpm_step_desc d, int64
 }
 
 
+// f-4 (UniPC, scheduling_unipc_multistep.py:257-601): one whole step in one launch -- conversion, corrector (UniC) over the history as it
+// stood before this step (h1, h2, h3, newest first) and the sample before the last predictor (l), then the predictor (UniP) from the
+// corrected sample over the shifted history (m0, h1, h2).  Both updates are linear once the host has expanded their D1 differences and
+// rho weights into coefficients, but they are chained through xc and share m0 with the conversion, so bd_dpm_step cannot carry them.
+// Whether the output is converted and which of the four optional inputs are present are template parameters (the launcher picks
+// the instance from the descriptor): the tests cost nothing, and every load stays one unconditional 16-byte access -- with run-time
+// tests the compiler sinks the loads into the branches that use them and splits them into dwords.  No __restrict__, as dpm_step_kernel: every load of an index is
+// issued before its first store.
+template <bool CV, bool L, bool H1, bool H2, bool H3>
+__device__ __forceinline__ void unipc_elem(const bd_unipc_step_desc& d, float e, float x, float l, float a, float b, float c, float& m0,
+                                           float& xc, float& prev) {
+    if constexpr (CV) m0 = (x - d.sigma_s * e) / d.alpha_s;
+    else m0 = e;
+    if (d.x0_clip) m0 = fminf(fmaxf(m0, -d.x0_range), d.x0_range);
+    xc = x;
+    if constexpr (L) {
+        float r = d.kl * l + d.k0 * m0;
+        r += d.k1 * a;
+        if constexpr (H2) r += d.k2 * b;
+        if constexpr (H3) r += d.k3 * c;
+        xc = r;
+    }
+    float r = d.px * xc + d.p0 * m0;
+    if constexpr (H1) r += d.p1 * a;
+    if constexpr (H2) r += d.p2 * b;
+    if (d.clip) r = fminf(fmaxf(r, -d.clip_range), d.clip_range);
+    prev = r;
+}
+template <bool CV, bool L, bool H1, bool H2, bool H3>
+__global__ __launch_bounds__(TPB) void unipc_step_kernel(bd_unipc_step_desc d, int64_t n4) {
+    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n4; i += (int64_t)gridDim.x * TPB) {
+        const float4 e = reinterpret_cast<const float4*>(d.model_output)[i], x = reinterpret_cast<const float4*>(d.sample)[i];
+        float4 l = make_float4(0.f, 0.f, 0.f, 0.f), a = l, b = l, c = l;
+        if constexpr (L) l = reinterpret_cast<const float4*>(d.last_sample)[i];
+        if constexpr (H1) a = reinterpret_cast<const float4*>(d.h1)[i];
+        if constexpr (H2) b = reinterpret_cast<const float4*>(d.h2)[i];
+        if constexpr (H3) c = reinterpret_cast<const float4*>(d.h3)[i];
+        float4 m0, xc, p;
+        unipc_elem<CV, L, H1, H2, H3>(d, e.x, x.x, l.x, a.x, b.x, c.x, m0.x, xc.x, p.x);
+        unipc_elem<CV, L, H1, H2, H3>(d, e.y, x.y, l.y, a.y, b.y, c.y, m0.y, xc.y, p.y);
+        unipc_elem<CV, L, H1, H2, H3>(d, e.z, x.z, l.z, a.z, b.z, c.z, m0.z, xc.z, p.z);
+        unipc_elem<CV, L, H1, H2, H3>(d, e.w, x.w, l.w, a.w, b.w, c.w, m0.w, xc.w, p.w);
+        if (d.m0_out) reinterpret_cast<float4*>(d.m0_out)[i] = m0;
+        if (d.corrected_out) reinterpret_cast<float4*>(d.corrected_out)[i] = xc;
+        reinterpret_cast<float4*>(d.prev_out)[i] = p;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (d.n & 3)) {   // tail (n % 4 elements)
+        const int64_t i = (d.n & ~(int64_t)3) + threadIdx.x;
+        const float e = d.model_output[i], x = d.sample[i];
+        float l = 0.f, a = 0.f, b = 0.f, c = 0.f;
+        if constexpr (L) l = d.last_sample[i];
+        if constexpr (H1) a = d.h1[i];
+        if constexpr (H2) b = d.h2[i];
+        if constexpr (H3) c = d.h3[i];
+        float m0, xc, p;
+        unipc_elem<CV, L, H1, H2, H3>(d, e, x, l, a, b, c, m0, xc, p);
+        if (d.m0_out) d.m0_out[i] = m0;
+        if (d.corrected_out) d.corrected_out[i] = xc;
+        d.prev_out[i] = p;
+    }
+}
+template <bool CV, bool L, bool H1, bool H2, bool H3>
+static void unipc_launch(const bd_unipc_step_desc& d, hipStream_t stream) {
+    hipLaunchKernelGGL((unipc_step_kernel<CV, L, H1, H2, H3>), dim3(nblocks(cdiv(d.n, 4), TPB, 4096)), dim3(TPB), 0, stream, d, d.n / 4);
+}
+
+
 // ---- f-4: Adversarial Neuron Pruning (anp_model.py:490-514 PerturbConv2d = conv followed by an eval-mode batch norm with mean 0, variance 1,
 // eps 0, i.e. y_c <- w_c * conv(x; W, b)_c + b_c with ONE learnable (w_c, b_c) per output channel).  The affine map commutes with the convolution:
 //   w_c * (W_c . x + b_c0) + b_c = (w_c W_c) . x + (w_c b_c0 + b_c),
@@ -833,6 +900,50 @@ extern "C" int bd_dpm_step(const bd_dpm_step_desc* d, bd_stream_t stream) {
     BD_CHECK(!d->m0_out || !overlap(d->m0_out, d->prev_out), BD_ERR_INVALID, "bd_dpm_step: m0_out overlaps prev_out");
     hipLaunchKernelGGL(dpm_step_kernel, dim3(nblocks(cdiv(d->n, 4), TPB, 4096)), dim3(TPB), 0, S(stream), *d, d->n / 4);
     BD_LAUNCH_CHECK("dpm_step");
+    return BD_OK;
+}
+extern "C" int bd_unipc_step(const bd_unipc_step_desc* d, bd_stream_t stream) {
+    BD_CHECK(d, BD_ERR_INVALID, "bd_unipc_step: null descriptor");
+    BD_CHECK(d->n > 0, BD_ERR_INVALID, "bd_unipc_step: n=%lld must be positive", (long long)d->n);
+    BD_CHECK(d->model_output && d->sample && d->prev_out, BD_ERR_INVALID,
+             "bd_unipc_step: null pointer (model_output, sample and prev_out are required)");
+    BD_CHECK(!d->last_sample || d->h1, BD_ERR_INVALID, "bd_unipc_step: last_sample without h1 (the corrector reads the previous converted output)");
+    const void* in[6] = {d->model_output, d->sample, d->last_sample, d->h1, d->h2, d->h3};
+    const void* out[3] = {d->prev_out, d->m0_out, d->corrected_out};
+    static const char* const in_name[6] = {"model_output", "sample", "last_sample", "h1", "h2", "h3"};
+    static const char* const out_name[3] = {"prev_out", "m0_out", "corrected_out"};
+    for (int j = 0; j < 6; ++j) BD_CHECK(aligned16(in[j]), BD_ERR_INVALID, "bd_unipc_step: %s is not 16-byte aligned", in_name[j]);
+    for (int j = 0; j < 3; ++j) BD_CHECK(aligned16(out[j]), BD_ERR_INVALID, "bd_unipc_step: %s is not 16-byte aligned", out_name[j]);
+    // an output may be an input's own buffer (same base: each index is read before it is written), nothing else may overlap
+    const uintptr_t bytes = (uintptr_t)d->n * sizeof(float);
+    auto overlap = [bytes](const void* p, const void* q) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+        return a < b + bytes && b < a + bytes;
+    };
+    for (int o = 0; o < 3; ++o) {
+        if (!out[o]) continue;
+        for (int p = 0; p < o; ++p)
+            BD_CHECK(!out[p] || !overlap(out[p], out[o]), BD_ERR_INVALID, "bd_unipc_step: %s overlaps %s", out_name[o], out_name[p]);
+    }
+    for (int o = 0; o < 3; ++o) {
+        if (!out[o]) continue;
+        for (int j = 0; j < 6; ++j)
+            BD_CHECK(!in[j] || in[j] == out[o] || !overlap(in[j], out[o]), BD_ERR_INVALID,
+                     "bd_unipc_step: %s overlaps %s without being the same buffer", out_name[o], in_name[j]);
+    }
+    // instance by the conversion and by which optional inputs are present: bit 4 convert, bit 3 last_sample, bits 2..0 h1, h2, h3
+    // (last_sample without h1 was refused above)
+    const int instance = (d->convert ? 16 : 0) | (d->last_sample ? 8 : 0) | (d->h1 ? 4 : 0) | (d->h2 ? 2 : 0) | (d->h3 ? 1 : 0);
+    switch (instance) {
+#define BD_UNIPC_CASE(M)                                                                                                          \
+    case M: unipc_launch<((M) & 16) != 0, ((M) & 8) != 0, ((M) & 4) != 0, ((M) & 2) != 0, ((M) & 1) != 0>(*d, S(stream)); break;  \
+    case (M) + 16: unipc_launch<true, ((M) & 8) != 0, ((M) & 4) != 0, ((M) & 2) != 0, ((M) & 1) != 0>(*d, S(stream)); break;
+        BD_UNIPC_CASE(0) BD_UNIPC_CASE(1) BD_UNIPC_CASE(2) BD_UNIPC_CASE(3) BD_UNIPC_CASE(4) BD_UNIPC_CASE(5) BD_UNIPC_CASE(6)
+        BD_UNIPC_CASE(7) BD_UNIPC_CASE(12) BD_UNIPC_CASE(13) BD_UNIPC_CASE(14) BD_UNIPC_CASE(15)
+#undef BD_UNIPC_CASE
+        default: BD_CHECK(false, BD_ERR_INVALID, "bd_unipc_step: last_sample without h1");
+    }
+    BD_LAUNCH_CHECK("unipc_step");
     return BD_OK;
 }
 extern "C" int bd_ddim_step(const bd_ddim_step_desc* d, bd_stream_t stream) {

@@ -15,9 +15,9 @@ from typing import Union
 import numpy as np
 import torch
 
-from .pipelines import DDIMPipeline, DDPMPipeline, DPMSolverPipeline, PNDMPipeline
+from .pipelines import DDIMPipeline, DDPMPipeline, DPMSolverPipeline, PNDMPipeline, UniPCPipeline
 from .schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, PNDMScheduler, RePaintScheduler,
-                         SchedulerConfigCarrier)
+                         SchedulerConfigCarrier, UniPCMultistepScheduler)
 from .unet import UNet2DModel
 
 WEIGHTS_NAME = "diffusion_pytorch_model.bin"
@@ -85,7 +85,8 @@ def load_scheduler(directory):
     with open(os.path.join(directory, SCHEDULER_CONFIG_NAME)) as f:
         cfg = json.load(f)
     cls = {"DDPMScheduler": DDPMScheduler, "DDIMScheduler": DDIMScheduler,
-           "RePaintScheduler": RePaintScheduler, "DPMSolverMultistepScheduler": DPMSolverMultistepScheduler}.get(cfg.get("_class_name", "DDPMScheduler"))
+           "RePaintScheduler": RePaintScheduler, "DPMSolverMultistepScheduler": DPMSolverMultistepScheduler,
+           "UniPCMultistepScheduler": UniPCMultistepScheduler}.get(cfg.get("_class_name", "DDPMScheduler"))
     if cls is None:
         raise NotImplementedError(f"scheduler {cfg.get('_class_name')} is not on the BadDiffusion hot path")
     return cls(**{k: v for k, v in cfg.items() if not k.startswith("_")})
@@ -264,6 +265,10 @@ class DiffuserModelSched:
     _DPM_SCHEDS = {"DPM_SOLVER_PP_O1-SCHED": (1, "dpmsolver++"), "DPM_SOLVER_O1-SCHED": (1, "dpmsolver"),
                    "DPM_SOLVER_PP_O2-SCHED": (2, "dpmsolver++"), "DPM_SOLVER_O2-SCHED": (2, "dpmsolver"),
                    "DPM_SOLVER_PP_O3-SCHED": (3, "dpmsolver++"), "DPM_SOLVER_O3-SCHED": (3, "dpmsolver")}
+    # names of this project's own (the reference's UNIPC-SCHED builds a UniPCMultistepScheduler and never steps it, and that name keeps
+    # its PNDM conversion): UniPCMultistepScheduler + UniPCPipeline with or without native_sched -- value = solver_order; the other
+    # options are the reference's defaults (bh2, predict_x0)
+    _UNIPC_SCHEDS = {"UNIPC_O1-SCHED": 1, "UNIPC_O2-SCHED": 2, "UNIPC_O3-SCHED": 3}
     # named in model.py:556-563 but not handled by its __get_model_sched either (it raises NotImplementedError)
     _OTHER_SCHEDS = ("LDM-SCHED", "SCORE-SDE-VE-SCHED", "EDM-VE-SCHED", "EDM-VE-ODE-SCHED", "EDM-VE-SDE-SCHED")
     _HUB = {DDPM_CIFAR10_32: "google/ddpm-cifar10-32", DDPM_CELEBA_HQ_256: "google/ddpm-ema-celebahq-256",
@@ -284,7 +289,8 @@ class DiffuserModelSched:
     def _get_model_sched(ckpt_id: str, clip_sample: bool, noise_sched_type: str = None, allow_random_init: bool = False,
                          native_sched: bool = False):
         # model.py:577-643.  native_sched (not in the reference): the DPM-Solver names build DPMSolverMultistepScheduler +
-        # DPMSolverPipeline instead of the PNDM conversion; the other solvers of that family have no native scheduler and are refused
+        # DPMSolverPipeline instead of the PNDM conversion; the other solvers of that family have no native scheduler and are refused.
+        # The UNIPC_O*-SCHED names (not the reference's either) always build UniPCMultistepScheduler + UniPCPipeline
         clip_used = DiffuserModelSched.get_sample_clip(clip_sample, DiffuserModelSched.CLIP_SAMPLE_DEFAULT)
         local = _resolve_local(ckpt_id)
         if local is not None:
@@ -316,6 +322,9 @@ class DiffuserModelSched:
         elif noise_sched_type is None:
             noise_sched = ckpt_sched
             get_pipeline = DiffuserModelSched._pipeline_generator(DDPMPipeline)
+        elif noise_sched_type in DiffuserModelSched._UNIPC_SCHEDS:
+            noise_sched = UniPCMultistepScheduler(solver_order=DiffuserModelSched._UNIPC_SCHEDS[noise_sched_type], **kw)
+            get_pipeline = DiffuserModelSched._pipeline_generator(partial(UniPCPipeline, clip_sample=clip_used))
         elif native_sched and noise_sched_type in DiffuserModelSched._DPM_SCHEDS:
             order, algorithm = DiffuserModelSched._DPM_SCHEDS[noise_sched_type]
             noise_sched = DPMSolverMultistepScheduler(solver_order=order, algorithm_type=algorithm, **kw)

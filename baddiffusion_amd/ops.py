@@ -741,6 +741,34 @@ def dpm_step(model_output, sample, cx, c0, m1=None, c1=0.0, m2=None, c2=0.0, con
     return out
 
 
+def unipc_step(model_output, sample, px, p0, h1=None, p1=0.0, h2=None, p2=0.0, h3=None, last_sample=None, kl=0.0, k0=0.0, k1=0.0, k2=0.0,
+               k3=0.0, convert=None, x0_clip=None, clip=None, m0_out=None, corrected_out=None, out=None):
+    """One whole UniPC step (bd_unipc_step, formula in include/bd_hip.h) over dense float32 GPU tensors of one shape and layout:
+    conversion, corrector, predictor.  convert / x0_clip / clip as in dpm_step; h1 / h2 / h3: the stored converted outputs of the
+    previous steps, newest first, or None (term absent, its coefficients ignored); last_sample: the corrected sample of the previous
+    step, or None (no corrector: the corrected sample is `sample`); m0_out / corrected_out: where m0 / the corrected sample are
+    written, or None.  out may be `sample`, corrected_out may be `last_sample`, m0_out may be the oldest history buffer (h2 or h3
+    included): the library refuses any other overlap.  Returns prev_sample."""
+    lib = L.load(); _need_cuda(model_output, sample, last_sample, h1, h2, h3, m0_out, corrected_out, out)
+    if sample.dtype != torch.float32 or sample.numel() == 0 or not _is_dense(sample):
+        raise ValueError("unipc_step: tensors must be non-empty, float32 and dense")
+    if out is None:
+        out = torch.empty_like(sample)
+    for t in (model_output, last_sample, h1, h2, h3, m0_out, corrected_out, out):
+        if t is not None and (t.shape != sample.shape or t.stride() != sample.stride() or t.dtype != torch.float32):
+            raise ValueError("unipc_step: tensors must share shape, strides and dtype float32")
+    alpha_s, sigma_s = (1.0, 0.0) if convert is None else convert
+    d = L.UnipcStepDesc(n=sample.numel(), model_output=L.ptr(model_output), sample=L.ptr(sample), last_sample=L.ptr(last_sample),
+                        h1=L.ptr(h1), h2=L.ptr(h2), h3=L.ptr(h3), m0_out=L.ptr(m0_out), corrected_out=L.ptr(corrected_out),
+                        prev_out=L.ptr(out), convert=int(convert is not None), alpha_s=float(alpha_s), sigma_s=float(sigma_s),
+                        x0_clip=int(x0_clip is not None), x0_range=0.0 if x0_clip is None else float(x0_clip),
+                        kl=float(kl), k0=float(k0), k1=float(k1), k2=float(k2), k3=float(k3),
+                        px=float(px), p0=float(p0), p1=float(p1), p2=float(p2), clip=int(clip is not None),
+                        clip_range=0.0 if clip is None else float(clip))
+    L.check(lib.bd_unipc_step(C.byref(d), L.stream()), "bd_unipc_step")
+    return out
+
+
 def anp_apply(params, pert_w, pert_b, items, total_rows, out=None):
     """effective parameters of the ANP-perturbed network (bd_anp_apply): a copy of the flat parameter buffer with every conv weight row scaled
     by its channel's pert_w and every conv bias mapped to pert_w * b + pert_b.  items: int64 device tensor [n, 5] (include/bd_hip.h)."""

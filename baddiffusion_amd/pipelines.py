@@ -15,7 +15,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .schedulers import DDIMScheduler, PNDMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, RePaintScheduler, randn_tensor
+from .schedulers import (DDIMScheduler, PNDMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, RePaintScheduler,
+                         UniPCMultistepScheduler, randn_tensor)
 
 
 class ImagePipelineOutput:
@@ -248,25 +249,22 @@ class PNDMPipeline(_PipelineBase):
         return ImagePipelineOutput(images=images, movie=mov)
 
 
-class DPMSolverPipeline(_PipelineBase):
-    """Sampling with DPMSolverMultistepScheduler: the loop and the call surface of PNDMPipeline (`init`, `start_from`,
-    `save_every_step`, output_type "pil" | "numpy" | "u8" | None), one UNet forward + one `bd_dpm_step` launch per step.  The reference
-    has no pipeline for this scheduler (its DPM-Solver `--sched` names sample through PNDMPipeline); num_inference_steps=20 is this
-    project's default.  Deterministic: no noise is drawn after the start.  `clip_sample` is the post-step clamp of the sample, as in
-    PNDMPipeline, folded into the step launch.  A scheduler that is not a DPMSolverMultistepScheduler is converted from its config.
-    With start_from=k the history is empty, so the first executed step is a first order one."""
+class _MultistepPipeline(_PipelineBase):
+    """The sampling loop of the deterministic multistep ODE solvers (DPMSolverPipeline, UniPCPipeline): the call surface of
+    PNDMPipeline (`init`, `start_from`, `save_every_step`, output_type "pil" | "numpy" | "u8" | None), one UNet forward + one fused
+    step launch per step, no noise drawn after the start.  `clip_sample` is the post-step clamp of the sample, as in PNDMPipeline,
+    folded into the step launch (`scheduler.step(..., clip=)`).  A subclass names its scheduler class; a scheduler of another class
+    is converted from its config.  With start_from=k the scheduler's history is empty, so the first executed step is first order."""
+    scheduler_class = None
 
     def __init__(self, unet, scheduler, clip_sample=False, clip_sample_range=1.0):
-        if not isinstance(scheduler, DPMSolverMultistepScheduler):
-            scheduler = DPMSolverMultistepScheduler.from_config(scheduler.config)
+        if not isinstance(scheduler, self.scheduler_class):
+            scheduler = self.scheduler_class.from_config(scheduler.config)
         super().__init__(unet, scheduler)
         self.clip_sample = clip_sample
         self.clip_sample_range = clip_sample_range
 
-    @_static_weights
-    @torch.no_grad()
-    def __call__(self, batch_size=1, num_inference_steps=20, start_from=0, generator=None, output_type="pil", init=None,
-                 save_every_step=False, return_dict=True, **kwargs):
+    def _sample(self, batch_size, num_inference_steps, start_from, generator, output_type, init, save_every_step, return_dict):
         image, shape = self._start(batch_size, generator, init)
         mov = [self._to_numpy(image, shape)] if save_every_step else []
         self.scheduler.set_timesteps(num_inference_steps)
@@ -289,6 +287,34 @@ class DPMSolverPipeline(_PipelineBase):
         if not return_dict:
             return (images,)
         return ImagePipelineOutput(images=images, movie=mov)
+
+
+class DPMSolverPipeline(_MultistepPipeline):
+    """Sampling with DPMSolverMultistepScheduler: _MultistepPipeline's loop, one UNet forward + one `bd_dpm_step` launch per step.
+    The reference has no pipeline for this scheduler (its DPM-Solver `--sched` names sample through PNDMPipeline);
+    num_inference_steps=20 is this project's default.  A scheduler that is not a DPMSolverMultistepScheduler is converted from its
+    config."""
+    scheduler_class = DPMSolverMultistepScheduler
+
+    @_static_weights
+    @torch.no_grad()
+    def __call__(self, batch_size=1, num_inference_steps=20, start_from=0, generator=None, output_type="pil", init=None,
+                 save_every_step=False, return_dict=True, **kwargs):
+        return self._sample(batch_size, num_inference_steps, start_from, generator, output_type, init, save_every_step, return_dict)
+
+
+class UniPCPipeline(_MultistepPipeline):
+    """Sampling with UniPCMultistepScheduler: _MultistepPipeline's loop, one UNet forward + one `bd_unipc_step` launch (corrector +
+    predictor) per step.  The reference has no pipeline for this scheduler either; num_inference_steps=10 is this project's default,
+    the regime UniPC is built for.  A scheduler that is not a UniPCMultistepScheduler is converted from its config.  With
+    start_from=k there is no last sample, so the first executed step has no corrector and is first order."""
+    scheduler_class = UniPCMultistepScheduler
+
+    @_static_weights
+    @torch.no_grad()
+    def __call__(self, batch_size=1, num_inference_steps=10, start_from=0, generator=None, output_type="pil", init=None,
+                 save_every_step=False, return_dict=True, **kwargs):
+        return self._sample(batch_size, num_inference_steps, start_from, generator, output_type, init, save_every_step, return_dict)
 
 
 def with_default_steps(pipeline, num_inference_steps):

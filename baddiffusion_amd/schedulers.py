@@ -10,8 +10,9 @@ once to the device; `step` reads its coefficients from that device table (no per
 no host<->device sync; scheduling_ddpm.py:350-365 does ~7 host scalar extractions per step).
 Only what BadDiffusion exercises is supported: epsilon prediction, linear betas, fixed_small /
 fixed_large variance; anything else raises like the reference does for unknown options.
-Also here: PNDMScheduler (scheduling_pndm.py), RePaintScheduler (scheduling_repaint.py, the inpainting scheduler) and
-DPMSolverMultistepScheduler (scheduling_dpmsolver_multistep.py, the high-order ODE sampler behind --native_sched).
+Also here: PNDMScheduler (scheduling_pndm.py), RePaintScheduler (scheduling_repaint.py, the inpainting scheduler),
+DPMSolverMultistepScheduler (scheduling_dpmsolver_multistep.py, the high-order ODE sampler behind --native_sched) and
+UniPCMultistepScheduler (scheduling_unipc_multistep.py, predictor + corrector, behind the UNIPC_O*-SCHED names).
 """
 import numpy as np
 import torch
@@ -671,6 +672,217 @@ class DPMSolverMultistepScheduler(_Base):
         if oldest is not None:
             self._ring = ring[1:] + [oldest]
         self._advance()
+        prev = restore(prev)
+        if not return_dict:
+            return (prev,)
+        return SchedulerOutput(prev_sample=prev)
+
+
+class UniPCMultistepScheduler(_Base):
+    """UniPC multistep scheduler (scheduling_unipc_multistep.py:126-601, B(h) version) on the GPU, epsilon prediction: a predictor
+    (UniP) of order 1-3 plus a corrector (UniC) that reuses the model output of the current step, so every step gains one order of
+    accuracy at no extra UNet evaluation.  Every step is ONE `bd_unipc_step` launch: conversion of the model output, the corrector
+    over the history as it stood before the step, the predictor from the corrected sample, and the pipeline's post-step clamp
+    (`step(..., clip=r)`).  All scalar work is done on the host in fp32 torch scalars as the reference does it (the order-3 linear
+    solves included), with the D1 differences and the rho weights of both updates expanded into coefficients of the tensors (`_plan`,
+    no device access).  State: a ring of `solver_order` device buffers of converted outputs (a step writes its own into the oldest),
+    their timesteps, and `last_sample`, the corrected sample of the previous step (on a step without a corrector that is the
+    incoming sample itself, which is kept by reference as the reference does; the scheduler never steps in place).
+    `thresholding=True` is supported for sample_max_value == 1.0, where it is exactly clamp(x0, -1, 1) (as
+    DPMSolverMultistepScheduler); `solver_p` and orders above 3 are not."""
+    order = 1
+    _KEYS = ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "trained_betas", "solver_order", "prediction_type",
+             "thresholding", "dynamic_thresholding_ratio", "sample_max_value", "predict_x0", "solver_type", "lower_order_final",
+             "disable_corrector")
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                 solver_order=2, prediction_type="epsilon", thresholding=False, dynamic_thresholding_ratio=0.995, sample_max_value=1.0,
+                 predict_x0=True, solver_type="bh2", lower_order_final=True, disable_corrector=(), solver_p=None, **unused):
+        if solver_type not in ("bh1", "bh2"):                                       # scheduling_unipc_multistep.py:169-173
+            if solver_type not in ("midpoint", "heun", "logrho"):
+                raise NotImplementedError(f"{solver_type} does is not implemented for {self.__class__}")
+            solver_type = "bh1"
+        if solver_order < 1:
+            raise ValueError(f"solver_order must be at least 1, got {solver_order}")
+        if solver_order > 3:
+            raise NotImplementedError(f"UniPCMultistepScheduler: solver_order {solver_order} is not on the HIP path (one launch carries "
+                                      "three history tensors: orders 1-3)")
+        if solver_p is not None:
+            raise NotImplementedError("UniPCMultistepScheduler: solver_p is not on the HIP path (the predictor is UniP)")
+        if thresholding and sample_max_value != 1.0:
+            raise NotImplementedError("UniPCMultistepScheduler: thresholding is on the HIP path for sample_max_value == 1.0 only "
+                                      f"(where it is clamp(x0, -1, 1)), got {sample_max_value}")
+        self.config = FrozenConfig(
+            num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end, beta_schedule=beta_schedule,
+            trained_betas=trained_betas, solver_order=solver_order, prediction_type=prediction_type, thresholding=thresholding,
+            dynamic_thresholding_ratio=dynamic_thresholding_ratio, sample_max_value=sample_max_value, predict_x0=predict_x0,
+            solver_type=solver_type, lower_order_final=lower_order_final, disable_corrector=list(disable_corrector))
+        self._make_tables(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas)
+        self.alpha_t = torch.sqrt(self.alphas_cumprod)                              # :161-164
+        self.sigma_t = torch.sqrt(1 - self.alphas_cumprod)
+        self.lambda_t = torch.log(self.alpha_t) - torch.log(self.sigma_t)
+        self.num_inference_steps = None
+        self.timesteps = torch.from_numpy(np.linspace(0, num_train_timesteps - 1, num_train_timesteps, dtype=np.float32)[::-1].copy())
+        self._ts, self._index, self._plans = [], {}, {}
+        self._reset()
+
+    @classmethod
+    def from_config(cls, config):
+        if "solver_p" in config and config["solver_p"] is not None:
+            raise NotImplementedError("UniPCMultistepScheduler: solver_p is not on the HIP path (the predictor is UniP)")
+        return cls(**{k: config[k] for k in cls._KEYS if k in config})
+
+    @property
+    def predict_x0(self):
+        return self.config.predict_x0
+
+    @property
+    def disable_corrector(self):
+        return self.config.disable_corrector
+
+    def _reset(self):
+        self.lower_order_nums = 0
+        self.this_order = 0                                   # order of the last predictor = order of the next corrector
+        self._ring = [None] * self.config.solver_order        # converted model outputs, oldest first; [-1] is the previous step's
+        self._ring_ts = [None] * self.config.solver_order     # and the timesteps they were taken at
+        self.last_sample, self._last_owned = None, False
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        # scheduling_unipc_multistep.py:188-220
+        timesteps = np.linspace(0, self.config.num_train_timesteps - 1, num_inference_steps + 1).round()[::-1][:-1].copy().astype(np.int64)
+        _, unique_indices = np.unique(timesteps, return_index=True)     # num_inference_steps == num_train_timesteps has duplicates
+        timesteps = timesteps[np.sort(unique_indices)]
+        self.timesteps = torch.from_numpy(timesteps).to(device)
+        self.num_inference_steps = len(timesteps)
+        ts = [int(t) for t in timesteps]
+        if ts != self._ts:
+            self._ts, self._index, self._plans = ts, {t: i for i, t in enumerate(ts)}, {}
+        self._reset()
+
+    def _step_index(self, timestep):
+        # :549-553: by value; a timestep that is not in the table counts as the last one
+        return self._index.get(int(timestep), len(self._index) - 1)
+
+    def _plan(self, step_index, has_last=None):
+        """Host part of the step at `step_index` given the current state (`lower_order_nums`, `this_order`, the timesteps of the
+        ring): (order, corrector_order, alpha_s, sigma_s, (kl, k0, k1, k2, k3), (px, p0, p1, p2)) for bd_unipc_step's formula
+        (include/bd_hip.h).  corrector_order is 0 when the step has no corrector: step 0, a step after one listed in
+        `disable_corrector`, or no `last_sample` (has_last, by default whether one is stored).  fp32 torch scalars throughout, no
+        device access; kept per set of timesteps, as DPMSolverMultistepScheduler._plan."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        cfg = self.config
+        if has_last is None:
+            has_last = self.last_sample is not None
+        corrector = step_index > 0 and step_index - 1 not in cfg.disable_corrector and bool(has_last)      # :555-557
+        key = (step_index, self.lower_order_nums, self.this_order if corrector else 0, tuple(self._ring_ts), cfg.predict_x0,
+               cfg.solver_type, cfg.solver_order, cfg.lower_order_final)
+        if key not in self._plans:
+            self._plans[key] = self._plan_scalars(step_index, corrector)
+        return self._plans[key]
+
+    def _bh(self, s0, t, older, order):
+        """what both updates share (:340-383 = :444-487) for the transition s0 -> t of order `order` over the timesteps `older` of the
+        history entries behind s0, newest first: (cx, A, B_h, h_phi_1, rks, R, b)"""
+        cfg, lam = self.config, self.lambda_t
+        h = lam[t] - lam[s0]
+        rks = [(lam[si] - lam[s0]) / h for si in older[:order - 1]]
+        rks_all = torch.stack(rks + [torch.ones(())])
+        hh = -h if cfg.predict_x0 else h
+        h_phi_1 = torch.expm1(hh)
+        h_phi_k = h_phi_1 / hh - 1
+        factorial_i = 1
+        if cfg.solver_type == "bh1":
+            B_h = hh
+        elif cfg.solver_type == "bh2":
+            B_h = torch.expm1(hh)
+        else:
+            raise NotImplementedError()
+        R, b = [], []
+        for i in range(1, order + 1):
+            R.append(torch.pow(rks_all, i - 1))
+            b.append(h_phi_k * factorial_i / B_h)
+            factorial_i *= i + 1
+            h_phi_k = h_phi_k / hh - 1 / factorial_i
+        if cfg.predict_x0:
+            cx, A = self.sigma_t[t] / self.sigma_t[s0], self.alpha_t[t]
+        else:
+            cx, A = self.alpha_t[t] / self.alpha_t[s0], self.sigma_t[t]
+        return cx, A, B_h, h_phi_1, rks, torch.stack(R), torch.stack(b)
+
+    def _plan_scalars(self, step_index, corrector):
+        ts, n, cfg = self._ts, len(self._ts), self.config
+        t_now = int(ts[step_index])
+        zero = torch.zeros(())
+        # corrector (UniC, :413-517) on the lists BEFORE this step's shift: from the previous step's timestep to this one, at the order
+        # the previous predictor used.  x_t = cx l - A h_phi_1 h1 - A B (sum_j rho_j (h_{j+1} - h1) / rk_j + rho_p (m0 - h1))
+        kl, k = zero, [zero] * 4
+        corr_order = self.this_order if corrector else 0
+        if corr_order:
+            older = [tt for tt in self._ring_ts[::-1]]                   # newest first: [0] is s0
+            cx, A, B_h, h_phi_1, rks, R, b = self._bh(older[0], t_now, older[1:], corr_order)
+            rhos = torch.tensor([0.5]) if corr_order == 1 else torch.linalg.solve(R, b)
+            kl = cx
+            k[0] = -(A * B_h) * rhos[-1]
+            for j, rk in enumerate(rks):
+                k[j + 2] = -(A * B_h) * rhos[j] / rk
+            k[1] = -(A * h_phi_1) - k[0] - sum(k[2:], zero)
+        # predictor (UniP, :308-411) AFTER the shift: from this step's timestep to the next one (0 at the end)
+        prev_t = 0 if step_index == n - 1 else int(ts[step_index + 1])
+        order = min(cfg.solver_order, n - step_index) if cfg.lower_order_final else cfg.solver_order      # :579-584
+        order = min(order, self.lower_order_nums + 1)
+        assert order > 0
+        cx, A, B_h, h_phi_1, rks, R, b = self._bh(t_now, prev_t, self._ring_ts[::-1], order)
+        p = [zero] * 3
+        if order > 1:
+            rhos = torch.tensor([0.5]) if order == 2 else torch.linalg.solve(R[:-1, :-1], b[:-1])
+            for j, rk in enumerate(rks):
+                p[j + 1] = -(A * B_h) * rhos[j] / rk
+        p[0] = -(A * h_phi_1) - sum(p[1:], zero)
+        return (order, corr_order, float(self.alpha_t[t_now]), float(self.sigma_t[t_now]), (float(kl),) + tuple(float(v) for v in k),
+                (float(cx),) + tuple(float(v) for v in p))
+
+    def _advance(self, step_index, order):
+        """the bookkeeping of one step: the ring's timesteps shift, the predictor's order is remembered for the next corrector"""
+        self._ring_ts = self._ring_ts[1:] + [int(self._ts[step_index])]
+        self.this_order = order
+        if self.lower_order_nums < self.config.solver_order:
+            self.lower_order_nums += 1
+
+    def step(self, model_output, timestep, sample, return_dict=True, clip=None):
+        # scheduling_unipc_multistep.py:519-601
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        if self.config.prediction_type != "epsilon":
+            raise ValueError(f"prediction_type given as {self.config.prediction_type} must be `epsilon` on the HIP path")
+        if not (model_output.is_cuda and sample.is_cuda):
+            raise RuntimeError("UniPCMultistepScheduler.step runs on the GPU only")
+        step_index = self._step_index(timestep)
+        order, corr_order, alpha_s, sigma_s, k, p = self._plan(step_index)
+        (eps, x), restore = self._align(model_output, sample)
+        if eps.dtype != torch.float32 or x.dtype != torch.float32:
+            raise TypeError("UniPCMultistepScheduler.step: float32 tensors only")
+        ring = self._ring
+        fits = lambda h: h is not None and h.shape == x.shape and h.stride() == x.stride() and h.device == x.device      # noqa: E731
+        n_hist = max(corr_order, order - 1)                  # the corrector reads h1..h_p, the predictor h1..h_{p-1}
+        hist = [ring[-1 - j] if j < n_hist else None for j in range(3)]
+        for h in hist[:n_hist] + ([self.last_sample] if corr_order else []):
+            if not fits(h):
+                raise ValueError("UniPCMultistepScheduler.step: the stored model outputs / last sample do not have this sample's "
+                                 "shape and layout (one chain per set_timesteps)")
+        oldest = ring[0] if fits(ring[0]) else torch.empty_like(x)       # takes this step's converted output
+        corrected = None
+        if corr_order:
+            corrected = self.last_sample if self._last_owned else torch.empty_like(x)
+        pp = bool(self.config.predict_x0)
+        prev = ops.unipc_step(eps, x, p[0], p[1], h1=hist[0], p1=p[2], h2=hist[1], p2=p[3], h3=hist[2],
+                              last_sample=self.last_sample if corr_order else None, kl=k[0], k0=k[1], k1=k[2], k2=k[3], k3=k[4],
+                              convert=(alpha_s, sigma_s) if pp else None, x0_clip=1.0 if pp and self.config.thresholding else None,
+                              clip=clip, m0_out=oldest, corrected_out=corrected)
+        self._ring = ring[1:] + [oldest]
+        # the sample the predictor started from: the corrected one, or the incoming one where no corrector ran
+        self.last_sample, self._last_owned = (corrected, True) if corr_order else (x, False)
+        self._advance(step_index, order)
         prev = restore(prev)
         if not return_dict:
             return (prev,)

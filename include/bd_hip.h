@@ -144,6 +144,38 @@ typedef struct {
 } bd_dpm_step_desc;
 int bd_dpm_step(const bd_dpm_step_desc* d, bd_stream_t stream);
 
+/* f-4: one whole UniPC step (scheduling_unipc_multistep.py:257-601, B(h) version, epsilon prediction) over n dense fp32 elements of one
+ * common layout, in one launch: conversion of the model output, the corrector (UniC) that turns the sample the previous predictor
+ * produced into the corrected sample, and the predictor (UniP) from there.  Per element, fp32, in this order (e = model_output,
+ * x = sample, l = last_sample, h1 / h2 / h3 = the stored converted outputs of the previous steps, newest first):
+ *     m0   = convert ? (x - sigma_s e) / alpha_s : e                          predict_x0, or the eps prediction as it is
+ *     m0   = x0_clip ? clamp(m0, -x0_range, x0_range) : m0                    thresholding with sample_max_value == 1
+ *     xc   = last_sample ? kl l + k0 m0 + k1 h1 [+ k2 h2] [+ k3 h3] : x       corrector; h2 / h3 NULL: the term is absent
+ *     prev = px xc + p0 m0 [+ p1 h1] [+ p2 h2]                                predictor; h1 / h2 NULL: the term is absent
+ *     prev = clip ? clamp(prev, -clip_range, clip_range) : prev
+ * m0 is written to m0_out, xc to corrected_out (either may be NULL: not written), prev to prev_out.  The scalars are host values: the
+ * caller expands the D1 differences and the rho weights of both updates into coefficients of the tensors; the coefficient of an absent
+ * term is ignored.  last_sample requires h1.
+ * An output may alias an input only with an identical base pointer (prev_out == sample; corrected_out == last_sample; m0_out == the
+ * oldest history buffer, also when that buffer is read as h2 or h3): every element is read into registers before its index is written.
+ * Host checks before the launch (BD_ERR_INVALID, message names bd_unipc_step): null descriptor, n <= 0, a null model_output / sample /
+ * prev_out, last_sample without h1, a pointer that is not 16-byte aligned, an output that overlaps an input or another output in any
+ * other way.
+ * HBM-bound: 16-byte accesses over n / 4, a scalar tail of n % 4, at most 4096 blocks of 256 threads with a grid-stride loop. */
+typedef struct {
+    int64_t n;
+    const float* model_output; const float* sample;
+    const float* last_sample;                    /* the corrected sample of the previous step; NULL: no corrector */
+    const float* h1; const float* h2; const float* h3;   /* previous converted outputs, newest first; may be NULL */
+    float* m0_out; float* corrected_out; float* prev_out;   /* m0_out and corrected_out may be NULL              */
+    int convert; float alpha_s, sigma_s;
+    int x0_clip; float x0_range;
+    float kl, k0, k1, k2, k3;
+    float px, p0, p1, p2;
+    int clip; float clip_range;
+} bd_unipc_step_desc;
+int bd_unipc_step(const bd_unipc_step_desc* d, bd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * RePaint inpainting (schedulers/scheduling_repaint.py:216-318, epsilon prediction): the reverse step with its re-noised copy of
  * the original image and the mask blend in one launch, and the "time travel" forward recurrence of undo_step.

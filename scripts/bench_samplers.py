@@ -1,21 +1,26 @@
-"""Time the sampling loops side by side on the GPU and write profiles/dpm_solver_sampling.json.
+"""Time the sampling loops side by side on the GPU and write profiles/unipc_sampling.json (profiles/dpm_solver_sampling.json is an
+earlier run of this script, before the UniPC rows).
 
-    python scripts/bench_samplers.py [--out profiles/dpm_solver_sampling.json] [--samples 2048] [--rounds 9]
+    python scripts/bench_samplers.py [--out profiles/unipc_sampling.json] [--samples 2048] [--rounds 9]
 
 One process, the DDPM-CIFAR10-32 topology with default initialisation (the arithmetic does not depend on the weights), the default compute
 mode, `--samples` chains from one seeded noise batch.  Loops, in this order: DDIM-50, PNDM-50 (59 UNet evaluations), DPM-Solver++ order 2
-at 20 and at 10 steps (DPMSolverPipeline), DDIM-50 again.  Every loop is warmed up on its full chunk shape at a few steps and with its whole schedule on 64 samples (a sampling job runs
+at 20 and at 10 steps (DPMSolverPipeline), UniPC order 2 at 20 and at 10 steps and order 3 at 10 (UniPCPipeline, bh2, predict_x0), DDIM-50
+again.  Every loop is warmed up on its full chunk shape at a few steps and with its whole schedule on 64 samples (a sampling job runs
 the same schedule chunk after chunk, and DPMSolverMultistepScheduler keeps the host scalars of the schedule it ran last), then timed
 with a host clock between two device synchronisations.  output_type="u8" throughout (device images, what batch_sampling_save asks for),
 so no loop is charged a copy of its images to the host.  Recorded per loop: seconds, samples/s, UNet evaluations and ms per evaluation.
 The two DDIM-50 repeats give the spread of this run; `dpm_vs_ddim` states whether the DPM pipeline's ms per evaluation exceeds DDIM-50's
-(the mean of the two repeats) by no more than that spread.
+(the mean of the two repeats) by no more than that spread; `unipc_vs_dpm` states the same for each UniPC loop against the DPM loop of the
+same step count.
 
 Step kernel: bd_dpm_step at order 2 (reads model_output, sample, m1; writes m0 and prev_sample: 5 streams of 4 B per element) against
 the same update as two bd_lincomb launches (x0 = sample / alpha - (sigma / alpha) eps: 2 reads + 1 write; prev = cx sample + c0 x0 +
 c1 m1: 3 reads + 1 write: 7 streams; no clamp of x0 on that route), n = samples * 3 * 32 * 32, outputs preallocated on both routes, HIP
 events around back-to-back launches, the routes alternated round by round (scripts/bench_defense.py's helpers).  `hbm_share` is
-bytes / 8 TB/s over the measured time.  Recorded, not asserted.  No GPU: the script fails, it has no CPU path."""
+bytes / 8 TB/s over the measured time.  bd_unipc_step at order 2 in the steady state (reads model_output, sample, last_sample, h1, h2; writes m0, the corrected sample and
+prev_sample: 8 streams) against the same step as three bd_lincomb launches (x0: 2 reads + 1 write; corrected = kl last + k0 x0 + k1 h1 +
+k2 h2: 4 + 1; prev = px corrected + p0 x0 + p1 h1: 3 + 1: 12 streams), measured the same way.  Recorded, not asserted.  No GPU: the script fails, it has no CPU path."""
 import argparse
 import json
 import os
@@ -47,7 +52,7 @@ def time_loop(pipe, init, steps, evals_of):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--out", default=os.path.join("profiles", "dpm_solver_sampling.json"))
+    ap.add_argument("--out", default=os.path.join("profiles", "unipc_sampling.json"))
     ap.add_argument("--samples", type=int, default=2048)
     ap.add_argument("--rounds", type=int, default=9)
     args = ap.parse_args(argv)
@@ -55,16 +60,18 @@ def main(argv=None):
         raise SystemExit("bench_samplers: no GPU (timings are taken on the device or not at all)")
     from baddiffusion_amd import ops
     from baddiffusion_amd.model import DiffuserModelSched
-    from baddiffusion_amd.pipelines import DDIMPipeline, DPMSolverPipeline, PNDMPipeline
-    from baddiffusion_amd.schedulers import DDPMScheduler, DPMSolverMultistepScheduler
+    from baddiffusion_amd.pipelines import DDIMPipeline, DPMSolverPipeline, PNDMPipeline, UniPCPipeline
+    from baddiffusion_amd.schedulers import DDPMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler
     model, _, _ = DiffuserModelSched.get_pretrained("DDPM-CIFAR10-32", allow_random_init=True)
     model = model.cuda()
     n = args.samples
     init = torch.randn(n, 3, 32, 32, generator=torch.Generator().manual_seed(0)).cuda()
     steps_of = lambda p: len(p.scheduler.timesteps)                                               # noqa: E731
     mk_dpm = lambda: DPMSolverPipeline(model, DPMSolverMultistepScheduler(solver_order=2, algorithm_type="dpmsolver++"))   # noqa: E731
+    mk_unipc = lambda order: UniPCPipeline(model, UniPCMultistepScheduler(solver_order=order))      # noqa: E731
     plan = [("ddim50_a", DDIMPipeline(model, DDPMScheduler()), 50), ("pndm50", PNDMPipeline(model, DDPMScheduler()), 50),
-            ("dpmpp_o2_20", mk_dpm(), 20), ("dpmpp_o2_10", mk_dpm(), 10), ("ddim50_b", DDIMPipeline(model, DDPMScheduler()), 50)]
+            ("dpmpp_o2_20", mk_dpm(), 20), ("dpmpp_o2_10", mk_dpm(), 10), ("unipc_o2_20", mk_unipc(2), 20), ("unipc_o2_10", mk_unipc(2), 10),
+            ("unipc_o3_10", mk_unipc(3), 10), ("ddim50_b", DDIMPipeline(model, DDPMScheduler()), 50)]
     result = {"device": torch.cuda.get_device_name(0), "topology": "DDPM-CIFAR10-32", "samples": n,
               "compute_mode": getattr(model, "compute_mode", None), "output_type": "u8", "loops": {}}
     for name, pipe, steps in plan:
@@ -81,6 +88,15 @@ def main(argv=None):
                                        "speedup_over_ddim50": L[name]["samples_per_s"] / (n / statistics.mean((L["ddim50_a"]["seconds"], L["ddim50_b"]["seconds"]))),
                                        "evaluation_ratio": 50 / L[name]["unet_evaluations"]}
     print(json.dumps(result["dpm_vs_ddim"]), flush=True)
+    result["unipc_vs_dpm"] = {"ddim50_spread_ms": spread}
+    for name, dpm in (("unipc_o2_20", "dpmpp_o2_20"), ("unipc_o2_10", "dpmpp_o2_10"), ("unipc_o3_10", "dpmpp_o2_10")):
+        excess = L[name]["ms_per_evaluation"] - L[dpm]["ms_per_evaluation"]
+        result["unipc_vs_dpm"][name] = {"ms_per_evaluation": L[name]["ms_per_evaluation"], "dpm_loop": dpm,
+                                        "dpm_ms_per_evaluation": L[dpm]["ms_per_evaluation"], "excess_over_dpm_ms": excess,
+                                        "within_ddim50_spread": bool(excess <= spread),
+                                        "excess_over_ddim50_ms": L[name]["ms_per_evaluation"] - ddim,
+                                        "samples_per_s": L[name]["samples_per_s"]}
+    print(json.dumps(result["unipc_vs_dpm"]), flush=True)
 
     # ---- the step kernel against the two-launch route
     numel = n * 3 * 32 * 32
@@ -104,6 +120,31 @@ def main(argv=None):
                              "fused_not_slower": bool(times["bd_dpm_step_order2"]["median_s"] <= times["bd_lincomb_x2"]["median_s"]),
                              "max_abs_diff_between_routes": {"m0": float((m0_f - m0_l).abs().max()), "prev": float((prev_f - prev_l).abs().max())}}
     print(json.dumps(result["step_kernel"]), flush=True)
+
+    # ---- the UniPC step kernel (order 2, steady state: corrector + predictor) against the three-launch route
+    last, h1, h2 = (torch.randn(numel, generator=g).cuda() for _ in range(3))
+    kl, k0, k1, k2, px, p0, p1 = 0.9, -0.25, 0.3, -0.15, 0.85, 0.35, -0.5
+    um0_f, uxc_f, uprev_f, um0_l, uxc_l, uprev_l = (torch.empty_like(x) for _ in range(6))
+
+    def unipc_fused():
+        ops.unipc_step(e, x, px, p0, h1=h1, p1=p1, h2=h2, p2=0.0, last_sample=last, kl=kl, k0=k0, k1=k1, k2=k2,
+                       convert=(alpha_s, sigma_s), m0_out=um0_f, corrected_out=uxc_f, out=uprev_f)
+
+    def three_launches():
+        ops.lincomb([x, e], [1.0 / alpha_s, -sigma_s / alpha_s], out=um0_l)
+        ops.lincomb([last, um0_l, h1, h2], [kl, k0, k1, k2], out=uxc_l)
+        ops.lincomb([uxc_l, um0_l, h1], [px, p0, p1], out=uprev_l)
+    times = compare({"bd_unipc_step_order2": unipc_fused, "bd_lincomb_x3": three_launches}, args.rounds)
+    unipc_fused(); three_launches()
+    bytes_moved = {"bd_unipc_step_order2": 8 * 4 * numel, "bd_lincomb_x3": 12 * 4 * numel}
+    result["unipc_step_kernel"] = {
+        "n": numel, "times": times, "bytes": bytes_moved,
+        "hbm_share": {k: (v / PEAK_HBM) / times[k]["median_s"] for k, v in bytes_moved.items()},
+        "three_launches_over_fused": times["bd_lincomb_x3"]["median_s"] / times["bd_unipc_step_order2"]["median_s"],
+        "fused_not_slower": bool(times["bd_unipc_step_order2"]["median_s"] <= times["bd_lincomb_x3"]["median_s"]),
+        "max_abs_diff_between_routes": {"m0": float((um0_f - um0_l).abs().max()), "corrected": float((uxc_f - uxc_l).abs().max()),
+                                        "prev": float((uprev_f - uprev_l).abs().max())}}
+    print(json.dumps(result["unipc_step_kernel"]), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(result, f, indent=2)
