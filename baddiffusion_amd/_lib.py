@@ -280,6 +280,7 @@ SIGNATURES = {
     "bd_conv3x3_wgrad_plan": (i32, [C.POINTER(ConvWgradDesc), C.POINTER(ThinPlanInfo)]),
     "bd_colsum": (i32, [vp, i64, i64, i32, i64, vp, i64, i32, vp]),
     "bd_sum2x2": (i32, [vp, i64, vp, i64, i32, i32, i32, i32, i32, vp]),
+    "bd_add": (i32, [vp, i64, vp, i64, i64, i32, f32, i32, vp]),
     "bd_softmax_fwd": (i32, [vp, vp, i64, i32, vp]),
     "bd_softmax_bwd": (i32, [vp, vp, vp, i64, i32, vp]),
     "bd_silu_fwd": (i32, [vp, vp, i64, vp]),

@@ -1049,6 +1049,7 @@ extern "C" int bd_repaint_undo(const bd_repaint_undo_desc* d, const float* const
 extern "C" int bd_to_image(const float* x, int src_is_nhwc, int64_t ld, int B, int C, int H, int W, float* out_f32,
                            uint8_t* out_u8, bd_stream_t stream) {
     BD_CHECK(x && (out_f32 || out_u8) && B > 0 && C > 0 && H > 0 && W > 0, BD_ERR_INVALID, "bd_to_image: bad args");
+    BD_CHECK(!src_is_nhwc || ld >= C, BD_ERR_INVALID, "bd_to_image: ld=%lld < C=%d", (long long)ld, C);
     hipLaunchKernelGGL(to_image_kernel, dim3(nblocks((int64_t)B * H * W)), dim3(TPB), 0, S(stream), x, src_is_nhwc, ld, B, C,
                        (int64_t)H * W, out_f32, out_u8);
     BD_LAUNCH_CHECK("to_image");
@@ -1089,6 +1090,7 @@ extern "C" int bd_softmax_bwd(const float* p, const float* dp, float* ds, int64_
 extern "C" int bd_colsum(const float* x, int64_t ldx, int64_t rows, int N, int64_t rows_per_group, float* out, int64_t ld_out,
                          int accumulate, bd_stream_t stream) {
     BD_CHECK(x && out && rows > 0 && N > 0 && rows_per_group > 0, BD_ERR_INVALID, "bd_colsum: bad args");
+    BD_CHECK(ldx >= N && ld_out >= N, BD_ERR_INVALID, "bd_colsum: ldx=%lld / ld_out=%lld < N=%d", (long long)ldx, (long long)ld_out, N);
     const int64_t groups = cdiv(rows, rows_per_group);
     BD_CHECK(groups <= 65535, BD_ERR_UNSUPPORTED, "bd_colsum: too many groups (%lld)", (long long)groups);
     hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)cdiv(N, 64), (unsigned)groups), dim3(TPB), 0, S(stream), x, ldx, rows, N,
@@ -1099,6 +1101,7 @@ extern "C" int bd_colsum(const float* x, int64_t ldx, int64_t rows, int N, int64
 extern "C" int bd_sum2x2(const float* du, int64_t ldu, float* dx, int64_t lddx, int B, int H, int W, int C, int accumulate,
                          bd_stream_t stream) {
     BD_CHECK(du && dx && B > 0 && H > 0 && W > 0 && C > 0, BD_ERR_INVALID, "bd_sum2x2: bad args");
+    BD_CHECK(ldu >= C && lddx >= C, BD_ERR_INVALID, "bd_sum2x2: ldu=%lld / lddx=%lld < C=%d", (long long)ldu, (long long)lddx, C);
     BD_CHECK((C & 3) == 0 && (ldu & 3) == 0 && (lddx & 3) == 0 && aligned16(du) && aligned16(dx), BD_ERR_UNSUPPORTED,
              "bd_sum2x2: needs C, ld multiples of 4 and 16B-aligned pointers");
     hipLaunchKernelGGL(sum2x2_kernel, dim3(nblocks((int64_t)B * H * W * (C / 4))), dim3(TPB), 0, S(stream), du, ldu, dx, lddx, B,
@@ -1110,6 +1113,7 @@ namespace bd {
 int add_launch(const float* src, int64_t lds, float* dst, int64_t ldd, int64_t rows, int C, float scale, int acc,
                hipStream_t st) {
     BD_CHECK(src && dst && rows > 0 && C > 0, BD_ERR_INVALID, "add: bad args");
+    BD_CHECK(lds >= C && ldd >= C, BD_ERR_INVALID, "add: lds=%lld / ldd=%lld < C=%d", (long long)lds, (long long)ldd, C);
     BD_CHECK((C & 3) == 0 && (lds & 3) == 0 && (ldd & 3) == 0 && aligned16(src) && aligned16(dst), BD_ERR_UNSUPPORTED,
              "add: needs C, ld multiples of 4 and 16B-aligned pointers");
     hipLaunchKernelGGL(add_kernel, dim3(nblocks(rows * (C / 4), TPB, 8192)), dim3(TPB), 0, st, src, lds, dst, ldd, rows, C, scale,
@@ -1118,6 +1122,10 @@ int add_launch(const float* src, int64_t lds, float* dst, int64_t ldd, int64_t r
     return BD_OK;
 }
 }  // namespace bd
+extern "C" int bd_add(const float* src, int64_t lds, float* dst, int64_t ldd, int64_t rows, int C, float scale, int accumulate,
+                      bd_stream_t stream) {
+    return add_launch(src, lds, dst, ldd, rows, C, scale, accumulate, S(stream));
+}
 extern "C" size_t bd_reduce_workspace_bytes(void) { return RED_BLOCKS * sizeof(double); }
 extern "C" int bd_loss_fwd_bwd(const float* pred, int64_t ldp, const float* target, int64_t ldt, int64_t rows, int C,
                                int loss_type, float grad_scale, float* loss, float* dpred, int64_t lddp, void* workspace,

@@ -250,7 +250,8 @@ int bd_anp_apply(const float* params, int64_t nparams, const float* pert_w, cons
 int bd_anp_grad(const float* params, const float* grad_eff, const int64_t* items, int n_items, int64_t total_rows, const float* pert_w,
                 float* grad_w, float* grad_b, float* row_norm, bd_stream_t stream);
 
-/* (x/2+0.5).clamp(0,1): NCHW or NHWC(ld) in -> NHWC float [B,H,W,C] and/or uint8 round(255 x). */
+/* (x/2+0.5).clamp(0,1): NCHW or NHWC(ld) in -> NHWC float [B,H,W,C] and/or uint8 round(255 x).
+ * BD_ERR_INVALID: null x, neither output, a size <= 0, or an NHWC source with ld < C (ld is not read for NCHW). */
 int bd_to_image(const float* x, int src_is_nhwc, int64_t ld, int B, int C, int H, int W,
                 float* out_f32, uint8_t* out_u8, bd_stream_t stream);
 
@@ -565,12 +566,20 @@ int bd_tune_set(const char* key, int value);
 size_t bd_conv3x3_ps_wgrad_workspace_bytes(const bd_conv3x3_ps_wgrad_desc* d);
 int bd_conv3x3_ps_wgrad(const bd_conv3x3_ps_wgrad_desc* d, bd_stream_t stream);
 
-/* out[g, n] = sum over rows m in group g of x[m, n]  (rows_per_group rows each); bias / temb grads. */
+/* out[g, n] = sum over rows m in group g of x[m, n]  (rows_per_group rows each, the last group may be shorter); bias / temb grads.
+ * BD_ERR_INVALID: null pointer, rows / N / rows_per_group <= 0, ldx or ld_out < N.  BD_ERR_UNSUPPORTED: more than 65535 groups. */
 int bd_colsum(const float* x, int64_t ldx, int64_t rows, int N, int64_t rows_per_group, float* out,
               int64_t ld_out, int accumulate, bd_stream_t stream);
-/* dx[b, y, x, c] (+)= sum of the 2x2 block of du[b, 2y.., 2x.., c]  (nearest-upsample backward). */
+/* dx[b, y, x, c] (+)= sum of the 2x2 block of du[b, 2y.., 2x.., c]  (nearest-upsample backward).
+ * BD_ERR_INVALID: null pointer, a size <= 0, ldu or lddx < C.  BD_ERR_UNSUPPORTED: C, ldu or lddx not a multiple of 4, or a pointer
+ * that is not 16-byte aligned. */
 int bd_sum2x2(const float* du, int64_t ldu, float* dx, int64_t lddx, int B, int H, int W, int C,
               int accumulate, bd_stream_t stream);
+/* dst[m, c] (+)= scale * src[m, c] over [rows, C] views with leading dimensions lds / ldd (the residual-path gradient add of the
+ * UNet plan).  BD_ERR_INVALID: null pointer, rows or C <= 0, lds or ldd < C.  BD_ERR_UNSUPPORTED: C, lds or ldd not a multiple of
+ * 4, or a pointer that is not 16-byte aligned. */
+int bd_add(const float* src, int64_t lds, float* dst, int64_t ldd, int64_t rows, int C, float scale,
+           int accumulate, bd_stream_t stream);
 
 /* Row softmax over [rows, n] (attention.py:161) and its backward dS = P * (dP - sum(dP*P)). */
 int bd_softmax_fwd(const float* s, float* p, int64_t rows, int n, bd_stream_t stream);

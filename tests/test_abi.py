@@ -100,3 +100,10 @@ def test_round2_entry_points_reject_bad_arguments_without_gpu():
     assert lib.bd_resize_bilinear_nhwc(None, 0, None, 1, 8, 8, 3, 299, 299, 2.0, -1.0, None) < 0
     assert lib.bd_global_avgpool_nhwc(None, 4, None, 1, 64, 4, None) < 0
     assert lib.bd_mfma_probe(1, 0, 1, None, None) < 0
+    # the residual-path gradient add, and the leading-dimension checks of the small ops
+    assert lib.bd_add(None, 4, None, 4, 1, 4, 1.0, 0, None) == -1 and b"add" in lib.bd_last_error()
+    p = 4096                                   # a 16-byte-aligned address that is never dereferenced: every call returns before its launch
+    assert lib.bd_add(p, 4, p, 8, 4, 8, 1.0, 0, None) == -1 and lib.bd_add(p, 8, p, 4, 4, 8, 1.0, 0, None) == -1
+    assert lib.bd_colsum(p, 7, 16, 8, 4, p, 8, 0, None) == -1 and lib.bd_colsum(p, 8, 16, 8, 4, p, 7, 0, None) == -1
+    assert lib.bd_sum2x2(p, 4, p, 8, 1, 2, 2, 8, 0, None) == -1 and lib.bd_sum2x2(p, 8, p, 4, 1, 2, 2, 8, 0, None) == -1
+    assert lib.bd_to_image(p, 1, 2, 1, 3, 4, 4, p, None, None) == -1 and b"ld" in lib.bd_last_error()
