@@ -1485,6 +1485,7 @@ extern "C" size_t bd_conv3x3_ps_wgrad_workspace_bytes(const bd_conv3x3_ps_wgrad_
 }
 extern "C" int bd_split_rows(const float* src, int64_t ld_src, int64_t rows, int C, uint16_t* dst, int64_t ld_dst, bd_stream_t stream) {
     BD_CHECK(src && dst && rows > 0 && C > 0, BD_ERR_INVALID, "bd_split_rows: bad args");
+    BD_CHECK(ld_src >= C && ld_dst >= C, BD_ERR_INVALID, "bd_split_rows: ld_src=%lld / ld_dst=%lld < C=%d", (long long)ld_src, (long long)ld_dst, C);
     BD_CHECK(C % 32 == 0 && ld_dst % 32 == 0 && (ld_src & 3) == 0 && bd::aligned16(src) && ((uintptr_t)dst & 127) == 0, BD_ERR_UNSUPPORTED,
              "bd_split_rows: C, ld_dst %% 32, ld_src %% 4, 16-byte aligned src and 128-byte aligned dst required");
     long long nb = bd::cdiv(rows * (C / 8), 256);
@@ -1496,6 +1497,8 @@ extern "C" int bd_split_rows(const float* src, int64_t ld_src, int64_t rows, int
 }
 extern "C" int bd_split_rows_ups2(const float* src, int64_t ld_src, int B, int H, int W, int C, uint16_t* dst, int64_t ld_dst, bd_stream_t stream) {
     BD_CHECK(src && dst && B > 0 && H > 0 && W > 0 && C > 0, BD_ERR_INVALID, "bd_split_rows_ups2: bad args");
+    BD_CHECK(ld_src >= C && ld_dst >= C, BD_ERR_INVALID, "bd_split_rows_ups2: ld_src=%lld / ld_dst=%lld < C=%d", (long long)ld_src, (long long)ld_dst,
+             C);
     BD_CHECK(C % 32 == 0 && ld_dst % 32 == 0 && (ld_src & 3) == 0 && bd::aligned16(src) && ((uintptr_t)dst & 127) == 0, BD_ERR_UNSUPPORTED,
              "bd_split_rows_ups2: C, ld_dst %% 32, ld_src %% 4, 16-byte aligned src and 128-byte aligned dst required");
     long long nb = bd::cdiv((long long)B * 4 * H * W * (C / 8), 256);

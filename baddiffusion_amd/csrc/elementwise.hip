@@ -609,9 +609,10 @@ __global__ __launch_bounds__(TPB) void ema_update_kernel(float* ema, const float
 // f-4 (PNDM family): out = clamp(sum_j c[j] * term[j]) over up to BD_LINCOMB_MAX dense fp32 tensors of one layout.
 // Every PRK / PLMS update of scheduling_pndm.py:236-397 is such a combination of the running sample, the stored model
 // outputs and the running accumulator, with host-computed scalar coefficients; the pipeline's post-step clip
-// (pipeline_pndm.py:108-109) rides along.
+// (pipeline_pndm.py:108-109) rides along.  No __restrict__ on out: it may be a term's own buffer (same base pointer, the ANP
+// projection clamps in place), so every term's element i is loaded before out's element i is stored.
 struct LincombArgs { const float* t[BD_LINCOMB_MAX]; float c[BD_LINCOMB_MAX]; int k; int clip; float range; };
-__global__ __launch_bounds__(TPB) void lincomb_kernel(LincombArgs a, float* __restrict__ out, int64_t n4, int64_t n) {
+__global__ __launch_bounds__(TPB) void lincomb_kernel(LincombArgs a, float* out, int64_t n4, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n4; i += (int64_t)gridDim.x * TPB) {
         float4 v[BD_LINCOMB_MAX];
 #pragma unroll
@@ -870,6 +871,12 @@ extern "C" int bd_lincomb(int k, const float* const* terms, const float* coeffs,
         a.t[j] = terms[j]; a.c[j] = coeffs[j];
     }
     BD_CHECK(aligned16(out), BD_ERR_INVALID, "bd_lincomb: out must be 16-byte aligned");
+    // out may be a term's own buffer (same base: each index is read before it is written), nothing else may overlap
+    const uintptr_t bytes = (uintptr_t)n * sizeof(float), o = reinterpret_cast<uintptr_t>(out);
+    for (int j = 0; j < k; ++j) {
+        const uintptr_t t = reinterpret_cast<uintptr_t>(terms[j]);
+        BD_CHECK(t == o || !(t < o + bytes && o < t + bytes), BD_ERR_INVALID, "bd_lincomb: out overlaps term %d without being the same buffer", j);
+    }
     hipLaunchKernelGGL(lincomb_kernel, dim3(nblocks(cdiv(n, 4), TPB, 4096)), dim3(TPB), 0, S(stream), a, out, n / 4, n);
     BD_LAUNCH_CHECK("lincomb");
     return BD_OK;
@@ -1131,6 +1138,8 @@ extern "C" int bd_loss_fwd_bwd(const float* pred, int64_t ldp, const float* targ
                                int loss_type, float grad_scale, float* loss, float* dpred, int64_t lddp, void* workspace,
                                bd_stream_t stream) {
     BD_CHECK(pred && target && loss && workspace && rows > 0 && C > 0, BD_ERR_INVALID, "bd_loss_fwd_bwd: bad args");
+    BD_CHECK(ldp >= C && ldt >= C && (!dpred || lddp >= C), BD_ERR_INVALID, "bd_loss_fwd_bwd: ldp=%lld / ldt=%lld / lddp=%lld < C=%d",
+             (long long)ldp, (long long)ldt, (long long)lddp, C);
     BD_CHECK(loss_type >= 0 && loss_type <= 2, BD_ERR_UNSUPPORTED, "bd_loss_fwd_bwd: loss_type %d (l2=0,l1=1,huber=2)", loss_type);
     const int nb = (int)nblocks(rows * C, TPB, RED_BLOCKS);
     hipLaunchKernelGGL(loss_kernel, dim3(nb), dim3(TPB), 0, S(stream), pred, ldp, target, ldt, rows, C, loss_type, grad_scale,
@@ -1148,6 +1157,8 @@ extern "C" int bd_loss_groups_fwd_bwd(const float* pred, int64_t ldp, const floa
                                       int loss_type, float grad_scale, const bd_loss_groups_desc* groups, float* losses,
                                       float* dpred, int64_t lddp, void* workspace, size_t workspace_bytes, bd_stream_t stream) {
     BD_CHECK(pred && target && groups && losses && workspace && rows > 0 && C > 0, BD_ERR_INVALID, "bd_loss_groups_fwd_bwd: bad args");
+    BD_CHECK(ldp >= C && ldt >= C && (!dpred || lddp >= C), BD_ERR_INVALID, "bd_loss_groups_fwd_bwd: ldp=%lld / ldt=%lld / lddp=%lld < C=%d",
+             (long long)ldp, (long long)ldt, (long long)lddp, C);
     BD_CHECK(loss_type >= 0 && loss_type <= 2, BD_ERR_UNSUPPORTED, "bd_loss_groups_fwd_bwd: loss_type %d (l2=0,l1=1,huber=2)", loss_type);
     BD_CHECK(groups->n_groups >= 1 && groups->n_groups <= BD_LOSS_MAX_GROUPS, BD_ERR_INVALID,
              "bd_loss_groups_fwd_bwd: n_groups %d outside 1..%d", groups->n_groups, BD_LOSS_MAX_GROUPS);

@@ -696,8 +696,9 @@ def loss_groups_fwd_bwd(pred, target, groups, loss_type="l2", grad_scale=1.0, wa
 
 
 def lincomb(terms, coeffs, clip=None, out=None):
-    """out = clamp?(sum_j coeffs[j] * terms[j]) (bd_lincomb): up to 6 dense float32 GPU tensors of one shape and layout."""
-    lib = L.load(); _need_cuda(*terms)
+    """out = clamp?(sum_j coeffs[j] * terms[j]) (bd_lincomb): up to 6 dense float32 GPU tensors of one shape and layout.  out (of the
+    terms' shape, strides and dtype) may be one of the terms; the library refuses any other overlap."""
+    lib = L.load(); _need_cuda(*terms, out)
     k = len(terms)
     if k < 1 or k > 6 or len(coeffs) != k:
         raise ValueError("lincomb: 1..6 terms with one coefficient each")
@@ -709,6 +710,8 @@ def lincomb(terms, coeffs, clip=None, out=None):
         raise ValueError("lincomb: terms must be dense")
     if out is None:
         out = torch.empty_like(t0)
+    elif out.shape != t0.shape or out.stride() != t0.stride() or out.dtype != torch.float32:
+        raise ValueError("lincomb: out must have the terms' shape, strides and dtype float32")
     ptrs = (C.c_void_p * k)(*[t.data_ptr() for t in terms])
     cs = (C.c_float * k)(*[float(c) for c in coeffs])
     L.check(lib.bd_lincomb(k, ptrs, cs, t0.numel(), 0 if clip is None else 1, 0.0 if clip is None else float(clip), L.ptr(out),

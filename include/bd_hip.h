@@ -114,7 +114,10 @@ int bd_ddim_step(const bd_ddim_step_desc* d, bd_stream_t stream);
 /* f-4: out = clamp?(sum_j coeffs[j] * terms[j]) over k <= BD_LINCOMB_MAX dense fp32 tensors of n elements (one common
  * layout; `terms` / `coeffs` are HOST arrays read at call time).  All PRK / PLMS updates of PNDMScheduler
  * (scheduling_pndm.py:236-397: running sample, stored model outputs, Runge-Kutta accumulator; formula (9) in
- * _get_prev_sample) are such combinations, and the post-step clip of pipeline_pndm.py:108-109 is the clamp. */
+ * _get_prev_sample) are such combinations, and the post-step clip of pipeline_pndm.py:108-109 is the clamp.
+ * Per element r = 0; r += coeffs[j] * terms[j][i] for j ascending, each operation rounded once in fp32.  terms and out are 16-byte
+ * aligned.  Aliasing: out may be a term's own buffer (same base pointer: every element is read before it is written; the in-place
+ * clamp of the ANP projection is k = 1, out = terms[0]); any other overlap of out with a term over n floats is BD_ERR_INVALID. */
 #define BD_LINCOMB_MAX 6
 int bd_lincomb(int k, const float* const* terms, const float* coeffs, int64_t n, int clip, float clip_range, float* out,
                bd_stream_t stream);
@@ -512,6 +515,8 @@ int bd_conv3x3_wgrad_plan(const bd_conv3x3_wgrad_desc* d, bd_conv3x3_thin_plan_i
  *     2*r*ld + (c/32)*64 + plane*32 + c%32          (ld % 32 == 0, 128-byte aligned base).
  * Same 4 bytes per element as fp32.  Producers: bd_split_rows (from fp32), bd_gn_fwd / bd_gn_bwd
  * (y_split / dx_split), bd_split_wt (transposed conv weights for the data gradient).
+ * bd_split_rows / bd_split_rows_ups2: C % 32, ld_dst % 32, ld_src % 4, 16-byte aligned src, 128-byte aligned dst (else
+ * BD_ERR_UNSUPPORTED); ld_src < C or ld_dst < C is BD_ERR_INVALID.  Columns C..ld of a row are neither read nor written.
  * bd_conv3x3_ps: stride-1 pad-1 3x3 convolution (direction +1) or its data gradient (direction -1, over
  * the transposed weight planes) with both operands streamed global -> LDS by DMA; bit-identical to
  * bd_conv3x3_fwd / bd_conv3x3_dgrad in BD_MODE_BF16X3.  Replaces aten::convolution(_backward input) of
@@ -591,7 +596,8 @@ int bd_silu_bwd(const float* x, const float* dy, float* dx, int64_t n, int accum
 
 /* a-3: loss = mean((pred - target)^2) and dpred = 2 (pred - target) / n  (loss.py:301).
  * loss_type: 0 l2, 1 l1, 2 huber(beta=1).  loss is a device scalar, written (not accumulated).
- * grad_scale multiplies dpred (1/world for DP mean).  workspace >= bd_reduce_workspace_bytes().   */
+ * grad_scale multiplies dpred (1/world for DP mean).  workspace >= bd_reduce_workspace_bytes().
+ * ldp < C, ldt < C or (with dpred) lddp < C is BD_ERR_INVALID, here and in bd_loss_groups_fwd_bwd.   */
 size_t bd_reduce_workspace_bytes(void);
 int bd_loss_fwd_bwd(const float* pred, int64_t ldp, const float* target, int64_t ldt, int64_t rows, int C,
                     int loss_type, float grad_scale, float* loss, float* dpred, int64_t lddp,
