@@ -69,6 +69,12 @@ class UnipcStepDesc(C.Structure):
                 ("clip", i32), ("clip_range", f32)]
 
 
+class SigmaStepDesc(C.Structure):
+    _fields_ = [("n", i64), ("model_output", vp), ("sample", vp), ("base", vp), ("h1", vp), ("h2", vp), ("h3", vp),
+                ("x0_out", vp), ("d_out", vp), ("prev_out", vp), ("scaled_out", vp), ("sigma_in", f32), ("average", i32),
+                ("c0", f32), ("c1", f32), ("c2", f32), ("c3", f32), ("in_div", f32), ("clip", i32), ("clip_range", f32)]
+
+
 class GnFwdDesc(C.Structure):
     _fields_ = [("B", i32), ("HW", i32), ("C", i32), ("G", i32), ("eps", f32), ("silu", i32),
                 ("x", vp), ("ldx", i64), ("gamma", vp), ("beta", vp), ("y", vp), ("ldy", i64),
@@ -227,6 +233,10 @@ SIGNATURES = {
     "bd_lincomb": (i32, [i32, C.POINTER(vp), C.POINTER(f32), i64, i32, f32, vp, vp]),
     "bd_dpm_step": (i32, [C.POINTER(DpmStepDesc), vp]),
     "bd_unipc_step": (i32, [C.POINTER(UnipcStepDesc), vp]),
+    "bd_sigma_step": (i32, [C.POINTER(SigmaStepDesc), vp]),
+    "bd_scale_input": (i32, [vp, i64, f32, f32, vp, vp]),
+    "bd_timestep_embedding_f32": (i32, [vp, i32, i32, i32, i32, f32, vp, vp]),
+    "bd_unet_forward_tf": (i32, [vp, i32, i32, vp, vp, i64, vp, i32, vp, i64, vp, sz, vp]),
     "bd_repaint_step": (i32, [C.POINTER(RepaintStepDesc), vp]),
     "bd_repaint_undo": (i32, [C.POINTER(RepaintUndoDesc), C.POINTER(vp), vp]),
     "bd_anp_apply": (i32, [vp, i64, vp, vp, vp, i32, i64, vp, vp]),

@@ -337,8 +337,11 @@ __global__ __launch_bounds__(TPB) void to_image_kernel(const float* x, int nhwc,
     }
 }
 
-// a-4a: get_timestep_embedding (embeddings.py:40-57)
-__global__ __launch_bounds__(TPB) void timestep_embedding_kernel(const int64_t* t, int t_stride, int B, int dim, int flip,
+// a-4a: get_timestep_embedding (embeddings.py:40-57).  T = int64_t (the schedulers' integer timesteps) or float (fractional timesteps:
+// the sigma-space samplers interpolate the schedule); both are `timesteps[:, None].float() * emb`, so an integral float gives the bits
+// of the integer.
+template <typename T>
+__global__ __launch_bounds__(TPB) void timestep_embedding_kernel(const T* t, int t_stride, int B, int dim, int flip,
                                                                float shift, float* out) {
     const int idx = blockIdx.x * TPB + threadIdx.x;
     const int half = dim / 2;
@@ -742,6 +745,88 @@ static void unipc_launch(const bd_unipc_step_desc& d, hipStream_t stream) {
 }
 
 
+// f-4 (sigma-space samplers: scheduling_heun_discrete.py:193-275, scheduling_lms_discrete.py:217-285, and Euler as their first order):
+// one transition in one launch -- pred_original_sample, the ODE derivative exactly as the reference rounds it ((x - x0) / sigma, not
+// the model output), Heun's average with the first stage's derivative or the linear multistep sum over the stored derivatives, the
+// update from `base` (Heun's second stage restarts from the sample of the first) and the NEXT evaluation's scale_model_input, which
+// is what makes the launch worth fusing: every UNet evaluation of these samplers reads x / sqrt(sigma^2 + 1).  The optional inputs are
+// template parameters as in unipc_step_kernel (every load one unconditional 16-byte access); NH counts the history terms of the sum
+// (AVG reads h1 for the average and has none).  No __restrict__: an output may be an input's own buffer.
+template <bool AVG, int NH>
+__device__ __forceinline__ void sigma_elem(const bd_sigma_step_desc& d, float e, float x, float b, float h1, float h2, float h3, float& x0,
+                                           float& dv, float& prev, float& sc) {
+    x0 = x - d.sigma_in * e;
+    dv = (x - x0) / d.sigma_in;
+    float dd = dv;
+    if constexpr (AVG) dd = (h1 + dv) / 2.0f;
+    float acc = d.c0 * dd;
+    if constexpr (!AVG && NH >= 1) acc += d.c1 * h1;
+    if constexpr (!AVG && NH >= 2) acc += d.c2 * h2;
+    if constexpr (!AVG && NH >= 3) acc += d.c3 * h3;
+    prev = b + acc;
+    sc = prev / d.in_div;
+    if (d.clip) {
+        sc = fminf(fmaxf(sc, -d.clip_range), d.clip_range);
+        prev = sc * d.in_div;
+    }
+}
+template <bool AVG, int NH, bool BASE>
+__global__ __launch_bounds__(TPB) void sigma_step_kernel(bd_sigma_step_desc d, int64_t n4) {
+    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n4; i += (int64_t)gridDim.x * TPB) {
+        const float4 e = reinterpret_cast<const float4*>(d.model_output)[i], x = reinterpret_cast<const float4*>(d.sample)[i];
+        float4 b = x, h1 = make_float4(0.f, 0.f, 0.f, 0.f), h2 = h1, h3 = h1;
+        if constexpr (BASE) b = reinterpret_cast<const float4*>(d.base)[i];
+        if constexpr (AVG || NH >= 1) h1 = reinterpret_cast<const float4*>(d.h1)[i];
+        if constexpr (!AVG && NH >= 2) h2 = reinterpret_cast<const float4*>(d.h2)[i];
+        if constexpr (!AVG && NH >= 3) h3 = reinterpret_cast<const float4*>(d.h3)[i];
+        float4 x0, dv, p, sc;
+        sigma_elem<AVG, NH>(d, e.x, x.x, b.x, h1.x, h2.x, h3.x, x0.x, dv.x, p.x, sc.x);
+        sigma_elem<AVG, NH>(d, e.y, x.y, b.y, h1.y, h2.y, h3.y, x0.y, dv.y, p.y, sc.y);
+        sigma_elem<AVG, NH>(d, e.z, x.z, b.z, h1.z, h2.z, h3.z, x0.z, dv.z, p.z, sc.z);
+        sigma_elem<AVG, NH>(d, e.w, x.w, b.w, h1.w, h2.w, h3.w, x0.w, dv.w, p.w, sc.w);
+        if (d.x0_out) reinterpret_cast<float4*>(d.x0_out)[i] = x0;
+        if (d.d_out) reinterpret_cast<float4*>(d.d_out)[i] = dv;
+        reinterpret_cast<float4*>(d.prev_out)[i] = p;
+        if (d.scaled_out) reinterpret_cast<float4*>(d.scaled_out)[i] = sc;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (d.n & 3)) {   // tail (n % 4 elements)
+        const int64_t i = (d.n & ~(int64_t)3) + threadIdx.x;
+        const float e = d.model_output[i], x = d.sample[i];
+        float b = x, h1 = 0.f, h2 = 0.f, h3 = 0.f;
+        if constexpr (BASE) b = d.base[i];
+        if constexpr (AVG || NH >= 1) h1 = d.h1[i];
+        if constexpr (!AVG && NH >= 2) h2 = d.h2[i];
+        if constexpr (!AVG && NH >= 3) h3 = d.h3[i];
+        float x0, dv, p, sc;
+        sigma_elem<AVG, NH>(d, e, x, b, h1, h2, h3, x0, dv, p, sc);
+        if (d.x0_out) d.x0_out[i] = x0;
+        if (d.d_out) d.d_out[i] = dv;
+        d.prev_out[i] = p;
+        if (d.scaled_out) d.scaled_out[i] = sc;
+    }
+}
+template <bool AVG, int NH>
+static void sigma_launch(const bd_sigma_step_desc& d, hipStream_t stream) {
+    const dim3 grid(nblocks(cdiv(d.n, 4), TPB, 4096));
+    if (d.base) hipLaunchKernelGGL((sigma_step_kernel<AVG, NH, true>), grid, dim3(TPB), 0, stream, d, d.n / 4);
+    else hipLaunchKernelGGL((sigma_step_kernel<AVG, NH, false>), grid, dim3(TPB), 0, stream, d, d.n / 4);
+}
+
+// out = (x * mul) / div: the start of a sigma-space chain (init * init_noise_sigma, then / sqrt(sigma_0^2 + 1)) and the public
+// scale_model_input (mul = 1: x * 1 is x).  out may be x.
+__global__ __launch_bounds__(TPB) void scale_input_kernel(const float* x, int64_t n4, int64_t n, float mul, float div, float* out) {
+    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n4; i += (int64_t)gridDim.x * TPB) {
+        float4 v = reinterpret_cast<const float4*>(x)[i];
+        v.x = (v.x * mul) / div; v.y = (v.y * mul) / div; v.z = (v.z * mul) / div; v.w = (v.w * mul) / div;
+        reinterpret_cast<float4*>(out)[i] = v;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {   // tail (n % 4 elements)
+        const int64_t i = (n & ~(int64_t)3) + threadIdx.x;
+        out[i] = (x[i] * mul) / div;
+    }
+}
+
+
 // ---- f-4: Adversarial Neuron Pruning (anp_model.py:490-514 PerturbConv2d = conv followed by an eval-mode batch norm with mean 0, variance 1,
 // eps 0, i.e. y_c <- w_c * conv(x; W, b)_c + b_c with ONE learnable (w_c, b_c) per output channel).  The affine map commutes with the convolution:
 //   w_c * (W_c . x + b_c0) + b_c = (w_c W_c) . x + (w_c b_c0 + b_c),
@@ -953,6 +1038,56 @@ extern "C" int bd_unipc_step(const bd_unipc_step_desc* d, bd_stream_t stream) {
     BD_LAUNCH_CHECK("unipc_step");
     return BD_OK;
 }
+extern "C" int bd_sigma_step(const bd_sigma_step_desc* d, bd_stream_t stream) {
+    BD_CHECK(d, BD_ERR_INVALID, "bd_sigma_step: null descriptor");
+    BD_CHECK(d->n > 0, BD_ERR_INVALID, "bd_sigma_step: n=%lld must be positive", (long long)d->n);
+    BD_CHECK(d->model_output && d->sample && d->prev_out, BD_ERR_INVALID,
+             "bd_sigma_step: null pointer (model_output, sample and prev_out are required)");
+    BD_CHECK(d->sigma_in > 0.f, BD_ERR_INVALID, "bd_sigma_step: sigma_in=%g must be positive", (double)d->sigma_in);
+    BD_CHECK(d->in_div > 0.f, BD_ERR_INVALID, "bd_sigma_step: in_div=%g must be positive", (double)d->in_div);
+    BD_CHECK(!d->average || d->h1, BD_ERR_INVALID, "bd_sigma_step: average without h1 (the first stage's derivative)");
+    BD_CHECK(!d->average || (!d->h2 && !d->h3 && d->c1 == 0.f && d->c2 == 0.f && d->c3 == 0.f), BD_ERR_INVALID,
+             "bd_sigma_step: average with history terms (h2 / h3 or a non-zero c1 / c2 / c3)");
+    BD_CHECK((d->h1 || !d->h2) && (d->h2 || !d->h3), BD_ERR_INVALID, "bd_sigma_step: history with a gap (h2 without h1, or h3 without h2)");
+    const void* in[6] = {d->model_output, d->sample, d->base, d->h1, d->h2, d->h3};
+    const void* out[4] = {d->prev_out, d->x0_out, d->d_out, d->scaled_out};
+    static const char* const in_name[6] = {"model_output", "sample", "base", "h1", "h2", "h3"};
+    static const char* const out_name[4] = {"prev_out", "x0_out", "d_out", "scaled_out"};
+    for (int j = 0; j < 6; ++j) BD_CHECK(aligned16(in[j]), BD_ERR_INVALID, "bd_sigma_step: %s is not 16-byte aligned", in_name[j]);
+    for (int j = 0; j < 4; ++j) BD_CHECK(aligned16(out[j]), BD_ERR_INVALID, "bd_sigma_step: %s is not 16-byte aligned", out_name[j]);
+    // an output may be an input's own buffer (same base: each index is read before it is written), nothing else may overlap
+    const uintptr_t bytes = (uintptr_t)d->n * sizeof(float);
+    auto overlap = [bytes](const void* p, const void* q) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+        return a < b + bytes && b < a + bytes;
+    };
+    for (int o = 0; o < 4; ++o) {
+        if (!out[o]) continue;
+        for (int p = 0; p < o; ++p)
+            BD_CHECK(!out[p] || !overlap(out[p], out[o]), BD_ERR_INVALID, "bd_sigma_step: %s overlaps %s", out_name[o], out_name[p]);
+        for (int j = 0; j < 6; ++j)
+            BD_CHECK(!in[j] || in[j] == out[o] || !overlap(in[j], out[o]), BD_ERR_INVALID,
+                     "bd_sigma_step: %s overlaps %s without being the same buffer", out_name[o], in_name[j]);
+    }
+    if (d->average) sigma_launch<true, 0>(*d, S(stream));
+    else if (d->h3) sigma_launch<false, 3>(*d, S(stream));
+    else if (d->h2) sigma_launch<false, 2>(*d, S(stream));
+    else if (d->h1) sigma_launch<false, 1>(*d, S(stream));
+    else sigma_launch<false, 0>(*d, S(stream));
+    BD_LAUNCH_CHECK("sigma_step");
+    return BD_OK;
+}
+extern "C" int bd_scale_input(const float* x, int64_t n, float mul, float div, float* out, bd_stream_t stream) {
+    BD_CHECK(x && out, BD_ERR_INVALID, "bd_scale_input: null pointer");
+    BD_CHECK(n > 0, BD_ERR_INVALID, "bd_scale_input: n=%lld must be positive", (long long)n);
+    BD_CHECK(div > 0.f, BD_ERR_INVALID, "bd_scale_input: div=%g must be positive", (double)div);
+    BD_CHECK(aligned16(x) && aligned16(out), BD_ERR_INVALID, "bd_scale_input: x and out must be 16-byte aligned");
+    const uintptr_t bytes = (uintptr_t)n * sizeof(float), a = reinterpret_cast<uintptr_t>(x), b = reinterpret_cast<uintptr_t>(out);
+    BD_CHECK(a == b || !(a < b + bytes && b < a + bytes), BD_ERR_INVALID, "bd_scale_input: out overlaps x without being the same buffer");
+    hipLaunchKernelGGL(scale_input_kernel, dim3(nblocks(cdiv(n, 4), TPB, 4096)), dim3(TPB), 0, S(stream), x, n / 4, n, mul, div, out);
+    BD_LAUNCH_CHECK("scale_input");
+    return BD_OK;
+}
 extern "C" int bd_ddim_step(const bd_ddim_step_desc* d, bd_stream_t stream) {
     BD_CHECK(d, BD_ERR_INVALID, "bd_ddim_step: null descriptor");
     BD_CHECK(d->n > 0 && d->model_output && d->sample && d->prev_sample && d->alphas_cumprod, BD_ERR_INVALID,
@@ -1065,9 +1200,17 @@ extern "C" int bd_to_image(const float* x, int src_is_nhwc, int64_t ld, int B, i
 extern "C" int bd_timestep_embedding(const int64_t* t, int t_stride, int B, int dim, int flip_sin_to_cos, float freq_shift,
                                      float* out, bd_stream_t stream) {
     BD_CHECK(t && out && B > 0 && dim >= 2, BD_ERR_INVALID, "bd_timestep_embedding: bad args");
-    hipLaunchKernelGGL(timestep_embedding_kernel, dim3(nblocks((int64_t)B * (dim / 2))), dim3(TPB), 0, S(stream), t, t_stride,
+    hipLaunchKernelGGL(timestep_embedding_kernel<int64_t>, dim3(nblocks((int64_t)B * (dim / 2))), dim3(TPB), 0, S(stream), t, t_stride,
                        B, dim, flip_sin_to_cos, freq_shift, out);
     BD_LAUNCH_CHECK("timestep_embedding");
+    return BD_OK;
+}
+extern "C" int bd_timestep_embedding_f32(const float* t, int t_stride, int B, int dim, int flip_sin_to_cos, float freq_shift,
+                                         float* out, bd_stream_t stream) {
+    BD_CHECK(t && out && B > 0 && dim >= 2, BD_ERR_INVALID, "bd_timestep_embedding_f32: bad args");
+    hipLaunchKernelGGL(timestep_embedding_kernel<float>, dim3(nblocks((int64_t)B * (dim / 2))), dim3(TPB), 0, S(stream), t, t_stride,
+                       B, dim, flip_sin_to_cos, freq_shift, out);
+    BD_LAUNCH_CHECK("timestep_embedding_f32");
     return BD_OK;
 }
 extern "C" int bd_silu_fwd(const float* x, float* y, int64_t n, bd_stream_t stream) {

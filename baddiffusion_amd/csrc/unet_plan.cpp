@@ -79,6 +79,7 @@ struct Ctx {
     hipStream_t st = nullptr;
     const float* x = nullptr; int64_t ldx = 0;
     const int64_t* t = nullptr; int t_stride = 0;
+    const float* tf = nullptr;   // fractional timesteps (bd_unet_forward_tf): exactly one of t / tf is set
     float* out = nullptr; int64_t ldo = 0;
     const float* dout = nullptr; int64_t lddo = 0;
     // backward only.  wg = false: the data-gradient-only schedule (bd_unet_backward_input with grads == NULL) -- every launch that produces
@@ -463,7 +464,9 @@ struct bd_unet {
         return c.dry ? BD_OK : bd_silu_bwd(x, dy, dx, n, 0, (bd_stream_t)c.st);
     }
     int timestep_embedding(Ctx& c, int dim, float* out) const {
-        return c.dry ? BD_OK : bd_timestep_embedding(c.t, c.t_stride, c.B, dim, cfg.flip_sin_to_cos, cfg.freq_shift, out, (bd_stream_t)c.st);
+        if (c.dry) return BD_OK;
+        if (c.tf) return bd_timestep_embedding_f32(c.tf, c.t_stride, c.B, dim, cfg.flip_sin_to_cos, cfg.freq_shift, out, (bd_stream_t)c.st);
+        return bd_timestep_embedding(c.t, c.t_stride, c.B, dim, cfg.flip_sin_to_cos, cfg.freq_shift, out, (bd_stream_t)c.st);
     }
     // bias gradient: per-sample column sums (scratch [B,N]) then a sum over the batch (fixed order)
     int bias_grad(Ctx& c, const float* dY, int64_t ld, int HW, int N, int scratch_buf, float* db) const {
@@ -1339,15 +1342,16 @@ static int unet_aux_init(bd_unet* u) {
     return BD_OK;
 }
 
-extern "C" int bd_unet_forward(bd_unet* u, int B, int training, const float* params, const float* x, int64_t ldx,
-                               const int64_t* t, int t_stride, float* out, int64_t ldo, void* workspace, size_t workspace_bytes,
-                               bd_stream_t stream) {
+// the forward of both entry points: the timesteps are int64 (t) or fp32 (tf), exactly one of the two; `who` names the entry point
+static int unet_forward(const char* who, bd_unet* u, int B, int training, const float* params, const float* x, int64_t ldx,
+                        const int64_t* t, const float* tf, int t_stride, float* out, int64_t ldo, void* workspace, size_t workspace_bytes,
+                        bd_stream_t stream) {
     Ctx c;
     BD_TRY(unet_ctx(u, c, B, training, workspace, workspace_bytes));
-    BD_CHECK(params && x && t && out, BD_ERR_INVALID, "bd_unet_forward: null pointer");
-    BD_CHECK(ldx >= u->cfg.in_channels && ldo >= u->cfg.out_channels, BD_ERR_INVALID, "bd_unet_forward: ld < channels");
-    BD_CHECK(aligned16(params), BD_ERR_INVALID, "bd_unet_forward: params must be 16-byte aligned");
-    c.params = params; c.x = x; c.ldx = ldx; c.t = t; c.t_stride = t_stride; c.out = out; c.ldo = ldo; c.st = S(stream);
+    BD_CHECK(params && x && (t || tf) && out, BD_ERR_INVALID, "%s: null pointer", who);
+    BD_CHECK(ldx >= u->cfg.in_channels && ldo >= u->cfg.out_channels, BD_ERR_INVALID, "%s: ld < channels", who);
+    BD_CHECK(aligned16(params), BD_ERR_INVALID, "%s: params must be 16-byte aligned", who);
+    c.params = params; c.x = x; c.ldx = ldx; c.t = t; c.tf = tf; c.t_stride = t_stride; c.out = out; c.ldo = ldo; c.st = S(stream);
     c.training = training != 0;
     if (training) { u->fwd_gen = bd::g_tune_gen; u->fwd_B = B; u->fwd_ws = workspace; }
     const bool prepared = u->static_weights && !training && u->prep_params == (const void*)params && u->prep_ws == workspace && u->prep_B == B;
@@ -1384,7 +1388,8 @@ extern "C" int bd_unet_forward(bd_unet* u, int B, int training, const float* par
     const int64_t hw = (int64_t)u->cfg.sample_size * u->cfg.sample_size;
     c.B = Bh;
     c2.B = B - Bh; c2.s0 = Bh; c2.st = u->aux_stream; c2.opws = c.opws2;
-    c2.x = x + (int64_t)Bh * hw * ldx; c2.t = t + (int64_t)Bh * t_stride; c2.out = out + (int64_t)Bh * hw * ldo;
+    c2.x = x + (int64_t)Bh * hw * ldx; c2.out = out + (int64_t)Bh * hw * ldo;
+    c2.t = t ? t + (int64_t)Bh * t_stride : nullptr; c2.tf = tf ? tf + (int64_t)Bh * t_stride : nullptr;
     BD_HIP_TRY(hipEventRecord(u->aux_ev_fork, c.st));
     BD_HIP_TRY(hipStreamWaitEvent(c2.st, u->aux_ev_fork, 0));
     BD_TRY(transpose_weights(c2.st));   // memory-bound, off the first pipeline's critical path
@@ -1395,6 +1400,17 @@ extern "C" int bd_unet_forward(bd_unet* u, int B, int training, const float* par
     BD_HIP_TRY(hipEventRecord(u->aux_ev_join[0], c2.st));
     BD_HIP_TRY(hipStreamWaitEvent(c.st, u->aux_ev_join[0], 0));
     return BD_OK;
+}
+
+extern "C" int bd_unet_forward(bd_unet* u, int B, int training, const float* params, const float* x, int64_t ldx,
+                               const int64_t* t, int t_stride, float* out, int64_t ldo, void* workspace, size_t workspace_bytes,
+                               bd_stream_t stream) {
+    return unet_forward("bd_unet_forward", u, B, training, params, x, ldx, t, nullptr, t_stride, out, ldo, workspace, workspace_bytes, stream);
+}
+extern "C" int bd_unet_forward_tf(bd_unet* u, int B, int training, const float* params, const float* x, int64_t ldx,
+                                  const float* t, int t_stride, float* out, int64_t ldo, void* workspace, size_t workspace_bytes,
+                                  bd_stream_t stream) {
+    return unet_forward("bd_unet_forward_tf", u, B, training, params, x, ldx, nullptr, t, t_stride, out, ldo, workspace, workspace_bytes, stream);
 }
 
 extern "C" int bd_unet_num_segments(const bd_unet* u) { return u ? (int)u->segs.size() : 0; }

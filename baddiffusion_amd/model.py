@@ -15,9 +15,9 @@ from typing import Union
 import numpy as np
 import torch
 
-from .pipelines import DDIMPipeline, DDPMPipeline, DPMSolverPipeline, PNDMPipeline, UniPCPipeline
-from .schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, PNDMScheduler, RePaintScheduler,
-                         SchedulerConfigCarrier, UniPCMultistepScheduler)
+from .pipelines import DDIMPipeline, DDPMPipeline, DPMSolverPipeline, HeunPipeline, LMSPipeline, PNDMPipeline, UniPCPipeline
+from .schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, HeunDiscreteScheduler, LMSDiscreteScheduler,
+                         PNDMScheduler, RePaintScheduler, SchedulerConfigCarrier, UniPCMultistepScheduler)
 from .unet import UNet2DModel
 
 WEIGHTS_NAME = "diffusion_pytorch_model.bin"
@@ -86,7 +86,8 @@ def load_scheduler(directory):
         cfg = json.load(f)
     cls = {"DDPMScheduler": DDPMScheduler, "DDIMScheduler": DDIMScheduler,
            "RePaintScheduler": RePaintScheduler, "DPMSolverMultistepScheduler": DPMSolverMultistepScheduler,
-           "UniPCMultistepScheduler": UniPCMultistepScheduler}.get(cfg.get("_class_name", "DDPMScheduler"))
+           "UniPCMultistepScheduler": UniPCMultistepScheduler, "HeunDiscreteScheduler": HeunDiscreteScheduler,
+           "LMSDiscreteScheduler": LMSDiscreteScheduler}.get(cfg.get("_class_name", "DDPMScheduler"))
     if cls is None:
         raise NotImplementedError(f"scheduler {cfg.get('_class_name')} is not on the BadDiffusion hot path")
     return cls(**{k: v for k, v in cfg.items() if not k.startswith("_")})
@@ -269,6 +270,12 @@ class DiffuserModelSched:
     # its PNDM conversion): UniPCMultistepScheduler + UniPCPipeline with or without native_sched -- value = solver_order; the other
     # options are the reference's defaults (bh2, predict_x0)
     _UNIPC_SCHEDS = {"UNIPC_O1-SCHED": 1, "UNIPC_O2-SCHED": 2, "UNIPC_O3-SCHED": 3}
+    # the sigma-space samplers, names of this project's own too (the reference's HEUN-SCHED / LMSD-SCHED keep their PNDM conversion):
+    # HeunDiscreteScheduler + HeunPipeline, LMSDiscreteScheduler + LMSPipeline at the named order, with or without native_sched --
+    # value = (scheduler class, order)
+    _SIGMA_SCHEDS = {"HEUN_O2-SCHED": ("HeunDiscreteScheduler", 2), "LMSD_O1-SCHED": ("LMSDiscreteScheduler", 1),
+                     "LMSD_O2-SCHED": ("LMSDiscreteScheduler", 2), "LMSD_O3-SCHED": ("LMSDiscreteScheduler", 3),
+                     "LMSD_O4-SCHED": ("LMSDiscreteScheduler", 4)}
     # named in model.py:556-563 but not handled by its __get_model_sched either (it raises NotImplementedError)
     _OTHER_SCHEDS = ("LDM-SCHED", "SCORE-SDE-VE-SCHED", "EDM-VE-SCHED", "EDM-VE-ODE-SCHED", "EDM-VE-SDE-SCHED")
     _HUB = {DDPM_CIFAR10_32: "google/ddpm-cifar10-32", DDPM_CELEBA_HQ_256: "google/ddpm-ema-celebahq-256",
@@ -325,6 +332,14 @@ class DiffuserModelSched:
         elif noise_sched_type in DiffuserModelSched._UNIPC_SCHEDS:
             noise_sched = UniPCMultistepScheduler(solver_order=DiffuserModelSched._UNIPC_SCHEDS[noise_sched_type], **kw)
             get_pipeline = DiffuserModelSched._pipeline_generator(partial(UniPCPipeline, clip_sample=clip_used))
+        elif noise_sched_type in DiffuserModelSched._SIGMA_SCHEDS:
+            cls_name, order = DiffuserModelSched._SIGMA_SCHEDS[noise_sched_type]
+            if cls_name == "HeunDiscreteScheduler":
+                noise_sched = HeunDiscreteScheduler(**kw)
+                get_pipeline = DiffuserModelSched._pipeline_generator(partial(HeunPipeline, clip_sample=clip_used))
+            else:
+                noise_sched = LMSDiscreteScheduler(**kw)
+                get_pipeline = DiffuserModelSched._pipeline_generator(partial(LMSPipeline, clip_sample=clip_used, order=order))
         elif native_sched and noise_sched_type in DiffuserModelSched._DPM_SCHEDS:
             order, algorithm = DiffuserModelSched._DPM_SCHEDS[noise_sched_type]
             noise_sched = DPMSolverMultistepScheduler(solver_order=order, algorithm_type=algorithm, **kw)

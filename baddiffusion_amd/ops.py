@@ -263,6 +263,12 @@ def to_image(x, nhwc, shape_bchw, want_u8=False):
 
 def timestep_embedding(t, dim, flip_sin_to_cos, freq_shift):
     lib = L.load(); _need_cuda(t)
+    if t.is_floating_point():       # fractional timesteps: one rounding to fp32, as the reference's .float()
+        t = t.float().contiguous()
+        out = torch.empty(t.numel(), dim, device=t.device)
+        L.check(lib.bd_timestep_embedding_f32(L.ptr(t), 1, t.numel(), dim, int(flip_sin_to_cos), float(freq_shift), L.ptr(out),
+                                              L.stream()), "bd_timestep_embedding_f32")
+        return out
     t = t.to(torch.int64).contiguous()
     out = torch.empty(t.numel(), dim, device=t.device)
     L.check(lib.bd_timestep_embedding(L.ptr(t), 1, t.numel(), dim, int(flip_sin_to_cos), float(freq_shift), L.ptr(out),
@@ -769,6 +775,44 @@ def unipc_step(model_output, sample, px, p0, h1=None, p1=0.0, h2=None, p2=0.0, h
                         px=float(px), p0=float(p0), p1=float(p1), p2=float(p2), clip=int(clip is not None),
                         clip_range=0.0 if clip is None else float(clip))
     L.check(lib.bd_unipc_step(C.byref(d), L.stream()), "bd_unipc_step")
+    return out
+
+
+def sigma_step(model_output, sample, sigma_in, c0, in_div, base=None, average=False, h1=None, c1=0.0, h2=None, c2=0.0, h3=None, c3=0.0,
+               clip=None, x0_out=None, d_out=None, scaled_out=None, out=None):
+    """One transition of a sigma-space sampler (bd_sigma_step, formula in include/bd_hip.h) over dense float32 GPU tensors of one shape
+    and layout: Euler (no history), Heun's averaging stage (average=True, h1 = the first stage's derivative, base = the sample that
+    stage started from) or a linear multistep sum over h1..h3.  in_div = sqrt(sigma_next^2 + 1) scales the result into scaled_out, the
+    next evaluation's model input; clip: None or the range of the clamp in those coordinates.  x0_out / d_out / scaled_out: where
+    pred_original_sample, the derivative and the scaled sample are written, or None.  d_out may be the oldest history buffer, out may
+    be `sample`: the library refuses any other overlap.  Returns prev_sample."""
+    lib = L.load(); _need_cuda(model_output, sample, base, h1, h2, h3, x0_out, d_out, scaled_out, out)
+    if sample.dtype != torch.float32 or sample.numel() == 0 or not _is_dense(sample):
+        raise ValueError("sigma_step: tensors must be non-empty, float32 and dense")
+    if out is None:
+        out = torch.empty_like(sample)
+    for t in (model_output, base, h1, h2, h3, x0_out, d_out, scaled_out, out):
+        if t is not None and (t.shape != sample.shape or t.stride() != sample.stride() or t.dtype != torch.float32):
+            raise ValueError("sigma_step: tensors must share shape, strides and dtype float32")
+    d = L.SigmaStepDesc(n=sample.numel(), model_output=L.ptr(model_output), sample=L.ptr(sample), base=L.ptr(base), h1=L.ptr(h1),
+                        h2=L.ptr(h2), h3=L.ptr(h3), x0_out=L.ptr(x0_out), d_out=L.ptr(d_out), prev_out=L.ptr(out),
+                        scaled_out=L.ptr(scaled_out), sigma_in=float(sigma_in), average=int(bool(average)), c0=float(c0), c1=float(c1),
+                        c2=float(c2), c3=float(c3), in_div=float(in_div), clip=int(clip is not None),
+                        clip_range=0.0 if clip is None else float(clip))
+    L.check(lib.bd_sigma_step(C.byref(d), L.stream()), "bd_sigma_step")
+    return out
+
+
+def scale_input(x, mul, div, out=None):
+    """out = (x * mul) / div (bd_scale_input) over a dense float32 GPU tensor; out may be x."""
+    lib = L.load(); _need_cuda(x, out)
+    if x.dtype != torch.float32 or x.numel() == 0 or not _is_dense(x):
+        raise ValueError("scale_input: x must be non-empty, float32 and dense")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.stride() != x.stride() or out.dtype != torch.float32:
+        raise ValueError("scale_input: out must have x's shape, strides and dtype float32")
+    L.check(lib.bd_scale_input(L.ptr(x), x.numel(), float(mul), float(div), L.ptr(out), L.stream()), "bd_scale_input")
     return out
 
 

@@ -15,8 +15,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .schedulers import (DDIMScheduler, PNDMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, RePaintScheduler,
-                         UniPCMultistepScheduler, randn_tensor)
+from .schedulers import (DDIMScheduler, PNDMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, HeunDiscreteScheduler,
+                         LMSDiscreteScheduler, RePaintScheduler, UniPCMultistepScheduler, randn_tensor)
 
 
 class ImagePipelineOutput:
@@ -313,6 +313,98 @@ class UniPCPipeline(_MultistepPipeline):
     @_static_weights
     @torch.no_grad()
     def __call__(self, batch_size=1, num_inference_steps=10, start_from=0, generator=None, output_type="pil", init=None,
+                 save_every_step=False, return_dict=True, **kwargs):
+        return self._sample(batch_size, num_inference_steps, start_from, generator, output_type, init, save_every_step, return_dict)
+
+
+class _SigmaPipeline(_MultistepPipeline):
+    """The sampling loop of the sigma-space samplers (HeunPipeline, LMSPipeline), with _MultistepPipeline's call surface.  The raw
+    state is init * init_noise_sigma -- `init` is what the sibling pipelines start from, so noise + trigger is scaled as a whole --
+    and the model never sees it: every evaluation reads the scaled buffer x / sqrt(sigma^2 + 1), which `bd_scale_input` produces at
+    the start and each `bd_sigma_step` launch afterwards, next to the raw sample.  One UNet forward at a float timestep (uploaded
+    once, fp32) + one fused launch per evaluation; no noise is drawn after the start.  `clip_sample` clamps the scaled buffer (the
+    sample in the coordinates the model sees) and rescales the raw sample to match.  `save_every_step` frames are the scaled
+    buffers -- the only ones that are images; the last frame is the final sample, at sigma = 0 where both coincide.  With
+    start_from=k the chain enters at position k of `scheduler.timesteps` with an empty history."""
+
+    def _step_kwargs(self):
+        return {}
+
+    def _check_start(self, start_from):
+        pass
+
+    def _sample(self, batch_size, num_inference_steps, start_from, generator, output_type, init, save_every_step, return_dict):
+        start_from = int(start_from)
+        self._check_start(start_from)
+        image, shape = self._start(batch_size, generator, init)
+        sched = self.scheduler
+        sched.set_timesteps(num_inference_steps, **self._step_kwargs())
+        ts_host = [float(t) for t in sched.timesteps[start_from:]]
+        ts_dev = torch.as_tensor(ts_host, dtype=torch.float64).to(torch.float32).to(self.device)    # one H2D copy for the whole chain
+        clip = float(self.clip_sample_range) if self.clip_sample else None
+        scaled = image
+        if ts_host:
+            # raw = init * init_noise_sigma; first model input = raw / sqrt(sigma_0^2 + 1), both roundings in one launch
+            scaled = ops.scale_input(image, sched.init_noise_sigma, sched._in_div[start_from])
+            image = ops.scale_input(image, sched.init_noise_sigma, 1.0, out=image)
+        mov = [self._to_numpy(scaled, shape)] if save_every_step else []
+        for i, t in enumerate(self.progress_bar(ts_host)):
+            eps = self.unet(scaled.permute(0, 3, 1, 2), ts_dev[i]).sample
+            out = sched.step(eps, t, image.permute(0, 3, 1, 2), clip=clip, scaled=True, **self._step_kwargs())
+            image, scaled = out.prev_sample.permute(0, 2, 3, 1), out.scaled_sample.permute(0, 2, 3, 1)
+            if save_every_step:
+                mov.append(self._to_numpy(scaled, shape))
+        # the last divisor is sqrt(0 + 1) = 1: the scaled buffer is the final sample (and carries the clamp when clip_sample is set)
+        image = scaled
+        if output_type == "u8":
+            images = self._to_u8(image, shape)
+            return ImagePipelineOutput(images=images, movie=mov) if return_dict else (images,)
+        images = self._to_numpy(image, shape)
+        if output_type == "pil":
+            images = self.numpy_to_pil(images)
+            if save_every_step:
+                mov = list(map(self.numpy_to_pil, mov))
+        if not return_dict:
+            return (images,)
+        return ImagePipelineOutput(images=images, movie=mov)
+
+
+class HeunPipeline(_SigmaPipeline):
+    """Sampling with HeunDiscreteScheduler: _SigmaPipeline's loop.  The reference has no pipeline for this scheduler (its HEUN-SCHED
+    samples through PNDMPipeline); num_inference_steps=10 is this project's default: 19 UNet evaluations, two per transition but
+    the last.  start_from counts positions of `scheduler.timesteps` (evaluations); an odd one is the averaging stage of a
+    transition whose first stage was not run, and is refused."""
+    scheduler_class = HeunDiscreteScheduler
+
+    def _check_start(self, start_from):
+        if start_from % 2:
+            raise ValueError(f"HeunPipeline: start_from={start_from} is the second entry of a timestep pair (the averaging stage of a "
+                             "transition whose first stage would be missing); start at an even position")
+
+    @_static_weights
+    @torch.no_grad()
+    def __call__(self, batch_size=1, num_inference_steps=10, start_from=0, generator=None, output_type="pil", init=None,
+                 save_every_step=False, return_dict=True, **kwargs):
+        return self._sample(batch_size, num_inference_steps, start_from, generator, output_type, init, save_every_step, return_dict)
+
+
+class LMSPipeline(_SigmaPipeline):
+    """Sampling with LMSDiscreteScheduler at `order` (1..4; 1 is Euler): _SigmaPipeline's loop.  The reference has no pipeline for
+    this scheduler either; num_inference_steps=20 is this project's default."""
+    scheduler_class = LMSDiscreteScheduler
+
+    def __init__(self, unet, scheduler, clip_sample=False, clip_sample_range=1.0, order=4):
+        super().__init__(unet, scheduler, clip_sample=clip_sample, clip_sample_range=clip_sample_range)
+        if not 1 <= int(order) <= LMSDiscreteScheduler.MAX_ORDER:
+            raise ValueError(f"LMSPipeline: order must be 1..{LMSDiscreteScheduler.MAX_ORDER}, got {order}")
+        self.order = int(order)
+
+    def _step_kwargs(self):
+        return {"order": self.order}
+
+    @_static_weights
+    @torch.no_grad()
+    def __call__(self, batch_size=1, num_inference_steps=20, start_from=0, generator=None, output_type="pil", init=None,
                  save_every_step=False, return_dict=True, **kwargs):
         return self._sample(batch_size, num_inference_steps, start_from, generator, output_type, init, save_every_step, return_dict)
 

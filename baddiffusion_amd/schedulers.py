@@ -12,7 +12,9 @@ Only what BadDiffusion exercises is supported: epsilon prediction, linear betas,
 fixed_large variance; anything else raises like the reference does for unknown options.
 Also here: PNDMScheduler (scheduling_pndm.py), RePaintScheduler (scheduling_repaint.py, the inpainting scheduler),
 DPMSolverMultistepScheduler (scheduling_dpmsolver_multistep.py, the high-order ODE sampler behind --native_sched) and
-UniPCMultistepScheduler (scheduling_unipc_multistep.py, predictor + corrector, behind the UNIPC_O*-SCHED names).
+UniPCMultistepScheduler (scheduling_unipc_multistep.py, predictor + corrector, behind the UNIPC_O*-SCHED names), and the two
+sigma-space samplers HeunDiscreteScheduler / LMSDiscreteScheduler (scheduling_heun_discrete.py, scheduling_lms_discrete.py; fractional
+timesteps, scaled model input and initial noise; behind HEUN_O2-SCHED and LMSD_O*-SCHED).
 """
 import numpy as np
 import torch
@@ -887,6 +889,242 @@ class UniPCMultistepScheduler(_Base):
         if not return_dict:
             return (prev,)
         return SchedulerOutput(prev_sample=prev)
+
+
+class _SigmaScheduler(_Base):
+    """What the two sigma-space (k-diffusion) schedulers share: the sample lives in the variance-exploding coordinates x = x_vp *
+    sqrt(sigma^2 + 1) with sigma = sqrt((1 - abar) / abar), the chain starts from noise * init_noise_sigma, the model sees
+    scale_model_input(x) = x / sqrt(sigma^2 + 1) at a timestep of np.linspace(0, T - 1, N) -- fractional in general, which is why
+    UNet2DModel takes float timesteps -- and every transition is ONE `bd_sigma_step` launch that also writes the next evaluation's
+    model input (`step(..., scaled=True)` returns it as `.scaled_sample`).  Host tables: `timesteps` (float64 numpy), `sigmas` (fp32
+    torch, trailing 0) and, per position, the fp32 divisor sqrt(sigma^2 + 1) computed with the reference's expression on 0-dim
+    tensors.  `step(..., clip=r)` clamps the sample in the coordinates the model sees (the clipping defence of the other pipelines
+    carried into sigma space; the reference has no clip here)."""
+    order = 1
+    _KEYS = ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "trained_betas", "prediction_type")
+
+    def _init_common(self, num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type):
+        self.config = FrozenConfig(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                   beta_schedule=beta_schedule, trained_betas=trained_betas, prediction_type=prediction_type)
+        self._make_tables(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas)
+        self.num_inference_steps = None
+        self._set_tables(num_train_timesteps)
+
+    @classmethod
+    def from_config(cls, config):
+        return cls(**{k: config[k] for k in cls._KEYS if k in config})
+
+    def _interp(self, n):
+        """(timesteps float64 [n] descending, sigmas fp32 [n + 1] with the trailing 0): scheduling_lms_discrete.py:203-206"""
+        timesteps = np.linspace(0, self.config.num_train_timesteps - 1, n, dtype=float)[::-1].copy()
+        sigmas = (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).numpy()
+        sigmas = np.interp(timesteps, np.arange(0, len(sigmas)), sigmas)
+        return timesteps, np.concatenate([sigmas, [0.0]]).astype(np.float32)
+
+    def _finish_tables(self, timesteps, sigmas):
+        self.timesteps = timesteps                                   # float64 host array
+        self.sigmas = torch.from_numpy(sigmas)                       # fp32, on the host: every scalar of a step is a host value
+        self.init_noise_sigma = float(self.sigmas.max())
+        self._in_div = [float((s ** 2 + 1) ** 0.5) for s in self.sigmas]      # (sigma**2 + 1) ** 0.5 on fp32 0-dim tensors
+        # positions by value; a device tensor of fp32 timesteps (what the pipelines hand the UNet) is found by its rounded value
+        self._index = {}
+        for i, t in enumerate(timesteps):
+            for key in {float(t), float(np.float32(t))}:
+                self._index.setdefault(key, []).append(i)
+
+    def _positions(self, timestep):
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        pos = self._index.get(float(timestep))
+        if not pos:
+            raise ValueError(f"{type(self).__name__}: timestep {float(timestep)!r} is not one of this schedule's")
+        return pos
+
+    def _check(self, model_output, sample):
+        if self.config.prediction_type != "epsilon":
+            raise ValueError(f"prediction_type given as {self.config.prediction_type} must be `epsilon` on the HIP path")
+        if not (model_output.is_cuda and sample.is_cuda):
+            raise RuntimeError(f"{type(self).__name__}.step runs on the GPU only")
+        (eps, x), restore = self._align(model_output, sample)
+        if eps.dtype != torch.float32 or x.dtype != torch.float32:
+            raise TypeError(f"{type(self).__name__}.step: float32 tensors only")
+        return eps, x, restore
+
+    @staticmethod
+    def _fits(h, x):
+        return h is not None and h.shape == x.shape and h.stride() == x.stride() and h.device == x.device
+
+    def scale_model_input(self, sample, timestep):
+        """sample / sqrt(sigma^2 + 1) at `timestep` (bd_scale_input): bit-equal to the `.scaled_sample` of the step that produced
+        `sample` (without clip; with it the step scales before it clamps)."""
+        if not sample.is_cuda:
+            raise RuntimeError(f"{type(self).__name__}.scale_model_input runs on the GPU only")
+        x, tag = self._flat(sample)
+        out = ops.scale_input(x, 1.0, self._in_div[self._step_index(timestep)])
+        return out.permute(0, 3, 1, 2) if tag == "nhwc" else out
+
+    @staticmethod
+    def _output(prev, scaled, restore, return_dict):
+        prev = restore(prev)
+        if not return_dict:
+            return (prev,)
+        out = SchedulerOutput(prev_sample=prev)
+        out.scaled_sample = None if scaled is None else restore(scaled)
+        return out
+
+
+class HeunDiscreteScheduler(_SigmaScheduler):
+    """Heun's second order sampler in sigma space (scheduling_heun_discrete.py:84-275, epsilon prediction).  A transition from
+    sigma_i to sigma_{i+1} is two calls of `step`, each after one UNet evaluation: a first order (Euler) stage that stores its
+    derivative, dt and the sample it started from, then the averaging stage from that sample.  The last transition (to sigma = 0) is a
+    plain Euler stage, so N steps cost 2N - 1 evaluations; `timesteps` has those 2N - 1 entries (each after the first twice) and
+    `sigmas` 2N.  The defaults are the reference's (beta_start=0.00085, beta_end=0.012)."""
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="linear", trained_betas=None,
+                 prediction_type="epsilon", **unused):
+        self._init_common(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type)
+
+    def _set_tables(self, n):
+        t, s = self._interp(n)
+        self._finish_tables(np.concatenate([t[:1], np.repeat(t[1:], 2)]), np.concatenate([s[:1], np.repeat(s[1:-1], 2), s[-1:]]))
+        self._reset()
+
+    def _reset(self):
+        self._stage = None          # (derivative buffer, dt, sample) of a first order stage that waits for its averaging stage
+        self._dbuf = None
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        # scheduling_heun_discrete.py:146-187 (the tables stay on the host; the pipelines upload the timesteps once)
+        self._set_tables(num_inference_steps)
+        self.num_inference_steps = num_inference_steps
+
+    @property
+    def state_in_first_order(self):
+        return self._stage is None
+
+    def _step_index(self, timestep):
+        # :115-125: a timestep is listed twice; the first order stage is the later entry, the averaging stage the earlier one
+        pos = self._positions(timestep)
+        return pos[-1] if self.state_in_first_order else pos[0]
+
+    def _plan_scalars(self, k):
+        """(sigma_in, dt or None, in_div) of the stage at position k: an even position is a first order stage sigmas[k] -> sigmas[k + 1],
+        an odd one the averaging stage, whose model output was taken at sigmas[k] (the reference's sigma_next) and whose dt is the
+        stored one"""
+        s = self.sigmas
+        return float(s[k]), (float(s[k + 1] - s[k]) if k % 2 == 0 else None), self._in_div[k + 1]
+
+    def step(self, model_output, timestep, sample, return_dict=True, clip=None, scaled=False):
+        # scheduling_heun_discrete.py:193-275
+        k = self._step_index(timestep)
+        eps, x, restore = self._check(model_output, sample)
+        first = self.state_in_first_order
+        if first != (k % 2 == 0):
+            raise ValueError(f"HeunDiscreteScheduler.step: position {k} of the schedule is "
+                             f"{'a first order' if k % 2 == 0 else 'an averaging'} stage, the scheduler is in the other state")
+        sigma_in, dt, in_div = self._plan_scalars(k)
+        sc = torch.empty_like(x) if scaled else None
+        if first:
+            last = k == len(self.timesteps) - 1
+            dbuf = None
+            if not last:
+                dbuf = self._dbuf if self._fits(self._dbuf, x) else torch.empty_like(x)
+            prev = ops.sigma_step(eps, x, sigma_in, dt, in_div, d_out=dbuf, scaled_out=sc, clip=clip)
+            if not last:
+                self._stage, self._dbuf = (dbuf, dt, x), dbuf
+        else:
+            dbuf, dt, base = self._stage
+            if not self._fits(dbuf, x) or not self._fits(base, x):
+                raise ValueError("HeunDiscreteScheduler.step: the stored first stage does not have this sample's shape and layout "
+                                 "(one chain per set_timesteps)")
+            prev = ops.sigma_step(eps, x, sigma_in, dt, in_div, base=base, average=True, h1=dbuf, scaled_out=sc, clip=clip)
+            self._stage = None
+        return self._output(prev, sc, restore, return_dict)
+
+
+class LMSDiscreteScheduler(_SigmaScheduler):
+    """Linear multistep sampler in sigma space (scheduling_lms_discrete.py:106-290, epsilon prediction): `step(..., order=4)` adds the
+    derivatives of up to `order` steps with the integrals of their Lagrange basis polynomials over [sigma, sigma_next].  The
+    coefficients are the reference's expression on the host -- fp32 0-dim tensors inside the integrand, scipy's quad at epsrel=1e-4 --
+    computed once per (num_inference_steps, order) and kept, so a sampling loop makes no quad call.  The previous derivatives live in
+    a ring of order - 1 device buffers (order <= 4: one launch carries three history terms); a step writes its own into the oldest.
+    Order 1 is Euler."""
+    MAX_ORDER = 4
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                 prediction_type="epsilon", **unused):
+        self._coeffs = {}
+        self._init_common(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type)
+
+    def _set_tables(self, n):
+        self._finish_tables(*self._interp(n))
+        self._reset()
+
+    def _reset(self):
+        self._ring = []             # previous derivatives, oldest first
+
+    def set_timesteps(self, num_inference_steps, device=None, order=None):
+        # scheduling_lms_discrete.py:191-215; order: also prepare the coefficient table of that order
+        self._set_tables(num_inference_steps)
+        self.num_inference_steps = num_inference_steps
+        if order is not None:
+            self.lms_coefficients(order)
+
+    def _step_index(self, timestep):
+        return self._positions(timestep)[0]
+
+    def get_lms_coefficient(self, order, t, current_order):
+        # scheduling_lms_discrete.py:169-189
+        from scipy import integrate
+        sigmas = self.sigmas
+
+        def lms_derivative(tau):
+            prod = 1.0
+            for k in range(order):
+                if current_order == k:
+                    continue
+                prod *= (tau - sigmas[t - k]) / (sigmas[t - current_order] - sigmas[t - k])
+            return prod
+
+        return integrate.quad(lms_derivative, sigmas[t], sigmas[t + 1], epsrel=1e-4)[0]
+
+    def lms_coefficients(self, order):
+        """[step][j]: the coefficients of the step at each position for `step(..., order=order)`, as Python floats (the reference
+        multiplies fp32 tensors by them: one rounding to fp32 at the launch)"""
+        if not 1 <= order <= self.MAX_ORDER:
+            raise ValueError(f"LMSDiscreteScheduler: order must be 1..{self.MAX_ORDER} on the HIP path, got {order}")
+        key = (len(self.timesteps), order)
+        if key not in self._coeffs:
+            self._coeffs[key] = [[float(self.get_lms_coefficient(min(i + 1, order), i, j)) for j in range(min(i + 1, order))]
+                                 for i in range(len(self.timesteps))]
+        return self._coeffs[key]
+
+    def _plan_scalars(self, k, order):
+        """(sigma_in, coefficients newest first, in_div) of the step at position k"""
+        return float(self.sigmas[k]), self.lms_coefficients(order)[k], self._in_div[k + 1]
+
+    def step(self, model_output, timestep, sample, order=4, return_dict=True, clip=None, scaled=False):
+        # scheduling_lms_discrete.py:217-285
+        k = self._step_index(timestep)
+        eps, x, restore = self._check(model_output, sample)
+        sigma_in, coeffs, in_div = self._plan_scalars(k, order)
+        ring = self._ring[-(order - 1):] if order > 1 else []
+        for h in ring:
+            if not self._fits(h, x):
+                raise ValueError("LMSDiscreteScheduler.step: the stored derivatives do not have this sample's shape and layout "
+                                 "(one chain per set_timesteps)")
+        # the reference zips the coefficients with the derivatives it has: a chain entered late uses fewer terms
+        terms = min(len(coeffs), 1 + len(ring))
+        hist = [ring[-1 - j] if j + 1 < terms else None for j in range(3)]
+        c = [coeffs[j] if j < terms else 0.0 for j in range(4)]
+        dbuf = None
+        if order > 1:       # this step's derivative goes to the oldest buffer of a full ring (it may be the last term read)
+            dbuf = ring.pop(0) if len(ring) == order - 1 else torch.empty_like(x)
+        sc = torch.empty_like(x) if scaled else None
+        prev = ops.sigma_step(eps, x, sigma_in, c[0], in_div, h1=hist[0], c1=c[1], h2=hist[1], c2=c[2], h3=hist[2], c3=c[3],
+                              d_out=dbuf, scaled_out=sc, clip=clip)
+        self._ring = ring + [dbuf] if order > 1 else []
+        return self._output(prev, sc, restore, return_dict)
 
 
 class SchedulerConfigCarrier(DDPMScheduler):

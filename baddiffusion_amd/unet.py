@@ -368,9 +368,15 @@ class UNet2DModel(nn.Module):
             raise ValueError(f"timestep must have 1 or {B} elements")
         if t.numel() == 1:
             t_stride = 0
-        L.check(self._lib.bd_unet_forward(self._plan, B, int(training), flat.data_ptr(), x_nhwc.data_ptr(), Cin,
-                                          t.data_ptr(), t_stride, out.data_ptr(), self.config.out_channels,
-                                          ws.data_ptr(), ws.numel(), L.stream()), "bd_unet_forward")
+        if t.dtype == torch.float32:
+            fwd, name = self._lib.bd_unet_forward_tf, "bd_unet_forward_tf"
+        elif t.dtype == torch.int64:
+            fwd, name = self._lib.bd_unet_forward, "bd_unet_forward"
+        else:
+            raise TypeError(f"timestep tensor must be int64 or float32 here, got {t.dtype}")
+        L.check(fwd(self._plan, B, int(training), flat.data_ptr(), x_nhwc.data_ptr(), Cin,
+                    t.data_ptr(), t_stride, out.data_ptr(), self.config.out_channels,
+                    ws.data_ptr(), ws.numel(), L.stream()), name)
         if not training:
             # stream-ordered reuse is safe: later launches on this stream run after these kernels
             self._release_ws(ws)
@@ -429,8 +435,14 @@ class UNet2DModel(nn.Module):
             x_nhwc = ops.nchw_to_nhwc(sample.float())
         if x_nhwc.dtype != torch.float32:
             x_nhwc = x_nhwc.float()
-        if not torch.is_tensor(timestep):
+        # a Python float or a floating-point tensor is a (possibly fractional) timestep: one rounding to fp32, as the reference's
+        # `timesteps[:, None].float()`, and the fp32 entry point (bd_unet_forward_tf); everything else is an integer timestep
+        if isinstance(timestep, (float, np.floating)):
+            t = torch.tensor([float(timestep)], dtype=torch.float64).to(device=sample.device, dtype=torch.float32)
+        elif not torch.is_tensor(timestep):
             t = torch.tensor([timestep], dtype=torch.int64, device=sample.device)
+        elif timestep.is_floating_point():
+            t = timestep.reshape(-1).to(device=sample.device, dtype=torch.float32)
         else:
             t = timestep.reshape(-1).to(device=sample.device, dtype=torch.int64)
         if t.numel() == 1 and B > 1:

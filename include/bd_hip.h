@@ -179,6 +179,46 @@ typedef struct {
 } bd_unipc_step_desc;
 int bd_unipc_step(const bd_unipc_step_desc* d, bd_stream_t stream);
 
+/* f-4: one transition of a sigma-space (k-diffusion) sampler -- Heun (scheduling_heun_discrete.py:193-275), linear multistep
+ * (scheduling_lms_discrete.py:217-285) and Euler as the first order of both -- over n dense fp32 elements of one common layout, in one
+ * launch, together with the NEXT evaluation's scale_model_input.  Per element, fp32, in this order (e = model_output, x = sample,
+ * h1 / h2 / h3 = the stored derivatives, newest first):
+ *     x0   = x - sigma_in e                                 pred_original_sample
+ *     d    = (x - x0) / sigma_in                            the ODE derivative as the reference rounds it (d != e bitwise)
+ *     dd   = average ? (h1 + d) / 2 : d                     Heun's second stage; h1 = the first stage's derivative, required then
+ *     acc  = c0 dd [+ c1 h1] [+ c2 h2] [+ c3 h3]            added left to right; h* NULL: the term is absent; average: no h terms
+ *     prev = (base ? base : x) + acc                        Heun's second stage restarts from the sample of the first
+ *     sc   = prev / in_div                                  in_div = sqrt(sigma_next^2 + 1), a host fp32 value; a true division
+ *     if clip: sc = clamp(sc, -clip_range, clip_range); prev = sc in_div
+ * Heun / Euler: c0 = dt = sigma_next - sigma; LMS: the integrated Lagrange coefficients.  x0 goes to x0_out, d (before the average) to
+ * d_out, prev to prev_out, sc to scaled_out; all but prev_out may be NULL (not written).  The reference has no clip for these
+ * schedulers: `clip` is this project's inference-time clipping defence, a clamp of the sample in the coordinates the model sees;
+ * with clip == 0 the arithmetic is the reference's.
+ * An output may alias an input only with an identical base pointer (d_out == the oldest history buffer, also when that buffer is read
+ * as a term; prev_out == sample): every element is read into registers before its index is written.
+ * Host checks before the launch (BD_ERR_INVALID, message names bd_sigma_step): null descriptor, n <= 0, a null model_output / sample /
+ * prev_out, sigma_in <= 0, in_div <= 0, average without h1, average with h2 / h3 or a non-zero c1 / c2 / c3, h2 without h1 or h3
+ * without h2, a pointer that is not 16-byte aligned, an output that overlaps an input or another output in any other way.
+ * HBM-bound: 16-byte accesses over n / 4, a scalar tail of n % 4, at most 4096 blocks of 256 threads with a grid-stride loop. */
+typedef struct {
+    int64_t n;
+    const float* model_output; const float* sample;
+    const float* base;                                   /* NULL: the update starts from `sample`                  */
+    const float* h1; const float* h2; const float* h3;   /* stored derivatives, newest first; may be NULL          */
+    float* x0_out; float* d_out; float* prev_out; float* scaled_out;   /* all but prev_out may be NULL             */
+    float sigma_in; int average;
+    float c0, c1, c2, c3;
+    float in_div;
+    int clip; float clip_range;
+} bd_sigma_step_desc;
+int bd_sigma_step(const bd_sigma_step_desc* d, bd_stream_t stream);
+
+/* out = (x * mul) / div over n dense fp32 elements, each operation rounded once: the start of a sigma-space chain
+ * (init * init_noise_sigma, then / sqrt(sigma_0^2 + 1)) and the schedulers' public scale_model_input (mul = 1).  Same launch shape
+ * as bd_sigma_step.  BD_ERR_INVALID: a null pointer, n <= 0, div <= 0, a pointer that is not 16-byte aligned, out overlapping x
+ * without being x. */
+int bd_scale_input(const float* x, int64_t n, float mul, float div, float* out, bd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * RePaint inpainting (schedulers/scheduling_repaint.py:216-318, epsilon prediction): the reverse step with its re-noised copy of
  * the original image and the mask blend in one launch, and the "time travel" forward recurrence of undo_step.
@@ -264,6 +304,10 @@ int bd_to_image(const float* x, int src_is_nhwc, int64_t ld, int B, int C, int H
  * ------------------------------------------------------------------------------------------------ */
 int bd_timestep_embedding(const int64_t* t, int t_stride, int B, int dim, int flip_sin_to_cos,
                           float freq_shift, float* out, bd_stream_t stream);
+/* the same for fp32 timesteps, which may be fractional (the sigma-space samplers visit np.linspace(0, T - 1, N)): the argument is
+ * t[b * t_stride] * f where the int64 entry point has (float)t[b * t_stride] * f, so integral values give identical bits. */
+int bd_timestep_embedding_f32(const float* t, int t_stride, int B, int dim, int flip_sin_to_cos,
+                              float freq_shift, float* out, bd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * GroupNorm (+ optional SiLU) over NHWC(ld).  Replaces nn.GroupNorm + F.silu at resnet.py:559,591,
@@ -765,6 +809,12 @@ size_t bd_unet_workspace_bytes(bd_unet* u, int B, int training);
 int bd_unet_forward(bd_unet* u, int B, int training, const float* params, const float* x, int64_t ldx,
                     const int64_t* t, int t_stride, float* out, int64_t ldo,
                     void* workspace, size_t workspace_bytes, bd_stream_t stream);
+/* bd_unet_forward with fp32 timesteps, which may be fractional (bd_timestep_embedding_f32); nothing else differs, and every
+ * backward entry point works unchanged after it (the time-embedding backward reads the saved sinusoid buffer).  An integral fp32
+ * timestep gives the bits of the int64 one. */
+int bd_unet_forward_tf(bd_unet* u, int B, int training, const float* params, const float* x, int64_t ldx,
+                       const float* t, int t_stride, float* out, int64_t ldo,
+                       void* workspace, size_t workspace_bytes, bd_stream_t stream);
 /* after a training forward with the same workspace and the same x: dout NHWC -> grads (flat, same offsets) */
 int bd_unet_backward(bd_unet* u, int B, const float* params, const float* x, int64_t ldx,
                      const float* dout, int64_t lddo, float* grads, void* workspace, size_t workspace_bytes,
