@@ -32,7 +32,7 @@ SOURCES = [  # (file, extra flags)
     ("prof.cpp", ["-x", "hip"]),
 ]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "splitplane.h"), os.path.join(CSRC, "ema_check.h"),
-           os.path.join(os.path.dirname(HERE), "include", "bd_hip.h")]
+           os.path.join(CSRC, "step_check.h"), os.path.join(os.path.dirname(HERE), "include", "bd_hip.h")]
 
 
 def _hipcc():

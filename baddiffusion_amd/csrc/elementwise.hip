@@ -3,7 +3,7 @@
 // ops (separate mul / add kernels, no FMA contraction) is reproduced exactly where the formula
 // order is copied (q_sample, scheduler steps).
 #include "common.h"
-#include "ema_check.h"
+#include "step_check.h"
 
 #include <cmath>
 #include <mutex>
@@ -609,43 +609,53 @@ __global__ __launch_bounds__(TPB) void ema_update_kernel(float* ema, const float
 }
 
 
+// ------------------------------------------------------------------------------------------------
+// The dense vec4 driver of the sampler steps: n floats per operand, one layout, every pointer 16-byte aligned.  An operation is a struct
+// with `template <class V> __device__ void at(int64_t i) const`, which states its loads, its per-element arithmetic and its stores once
+// for the access width V: the grid walks the n4 = n / 4 float4s, block 0 the n % 4 floats behind them.  No __restrict__ anywhere: an output
+// may be the very buffer an input is read from (same base pointer), so at() issues every load of index i before its first store.
+// ------------------------------------------------------------------------------------------------
+template <class V> __device__ __forceinline__ V ld(const float* p, int64_t i) { return reinterpret_cast<const V*>(p)[i]; }
+template <class V> __device__ __forceinline__ void st(float* p, int64_t i, const V& v) { reinterpret_cast<V*>(p)[i] = v; }
+template <class V> __device__ __forceinline__ V splat(float s);
+template <> __device__ __forceinline__ float splat<float>(float s) { return s; }
+template <> __device__ __forceinline__ float4 splat<float4>(float s) { return make_float4(s, s, s, s); }
+// f(a.x, b.x, ...), f(a.y, b.y, ...), ... over the lanes of the operands (inputs by value or outputs by reference, as f takes them)
+template <class F, class... A> __device__ __forceinline__ void lanes(F f, float& a0, A&... a) { f(a0, a...); }
+template <class F, class... A> __device__ __forceinline__ void lanes(F f, float4& a0, A&... a) {
+    f(a0.x, a.x...); f(a0.y, a.y...); f(a0.z, a.z...); f(a0.w, a.w...);
+}
+template <class Op>
+__global__ __launch_bounds__(TPB) void vec4_kernel(Op op, int64_t n4, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n4; i += (int64_t)gridDim.x * TPB) op.template at<float4>(i);
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) op.template at<float>((n & ~(int64_t)3) + threadIdx.x);   // tail (n % 4 elements)
+}
+
 // f-4 (PNDM family): out = clamp(sum_j c[j] * term[j]) over up to BD_LINCOMB_MAX dense fp32 tensors of one layout.
 // Every PRK / PLMS update of scheduling_pndm.py:236-397 is such a combination of the running sample, the stored model
 // outputs and the running accumulator, with host-computed scalar coefficients; the pipeline's post-step clip
-// (pipeline_pndm.py:108-109) rides along.  No __restrict__ on out: it may be a term's own buffer (same base pointer, the ANP
-// projection clamps in place), so every term's element i is loaded before out's element i is stored.
-struct LincombArgs { const float* t[BD_LINCOMB_MAX]; float c[BD_LINCOMB_MAX]; int k; int clip; float range; };
-__global__ __launch_bounds__(TPB) void lincomb_kernel(LincombArgs a, float* out, int64_t n4, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n4; i += (int64_t)gridDim.x * TPB) {
-        float4 v[BD_LINCOMB_MAX];
+// (pipeline_pndm.py:108-109) rides along.  out may be a term's own buffer (the ANP projection clamps in place).
+struct LincombOp {
+    const float* t[BD_LINCOMB_MAX]; float c[BD_LINCOMB_MAX]; int k; int clip; float range; float* out;
+    template <class V> __device__ __forceinline__ void at(int64_t i) const {
+        V v[BD_LINCOMB_MAX];
+#pragma unroll
+        for (int j = 0; j < BD_LINCOMB_MAX; ++j) v[j] = j < k ? ld<V>(t[j], i) : splat<V>(0.f);
+        V r = splat<V>(0.f);
 #pragma unroll
         for (int j = 0; j < BD_LINCOMB_MAX; ++j)
-            v[j] = j < a.k ? reinterpret_cast<const float4*>(a.t[j])[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-        float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int j = 0; j < BD_LINCOMB_MAX; ++j)
-            if (j < a.k) { r.x += a.c[j] * v[j].x; r.y += a.c[j] * v[j].y; r.z += a.c[j] * v[j].z; r.w += a.c[j] * v[j].w; }
-        if (a.clip) {
-            r.x = fminf(fmaxf(r.x, -a.range), a.range); r.y = fminf(fmaxf(r.y, -a.range), a.range);
-            r.z = fminf(fmaxf(r.z, -a.range), a.range); r.w = fminf(fmaxf(r.w, -a.range), a.range);
-        }
-        reinterpret_cast<float4*>(out)[i] = r;
+            if (j < k) lanes([cj = c[j]](float& r, float v) { r += cj * v; }, r, v[j]);
+        if (clip) lanes([this](float& r) { r = fminf(fmaxf(r, -range), range); }, r);
+        st<V>(out, i, r);
     }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {   // tail (n % 4 elements)
-        const int64_t i = (n & ~(int64_t)3) + threadIdx.x;
-        float r = 0.f;
-        for (int j = 0; j < a.k; ++j) r += a.c[j] * a.t[j][i];
-        if (a.clip) r = fminf(fmaxf(r, -a.range), a.range);
-        out[i] = r;
-    }
-}
+};
+constexpr auto lincomb_kernel = vec4_kernel<LincombOp>;      // the name bd_lincomb launches (the tests read its grid cap by it)
 
 
 // f-4 (DPM-Solver / DPM-Solver++, scheduling_dpmsolver_multistep.py:301-505): one multistep update in one launch.  The conversion of
 // the model output (x0-prediction with its clamp for dpmsolver++, eps as it is for dpmsolver) is not linear, so bd_lincomb cannot
 // carry it; the first / second / third order updates are, once D1 and D2 are expanded on the host into coefficients of the stored
-// converted outputs m0 (this step's), m1, m2.  m0 goes to the history ring, prev to the running sample.  No __restrict__: an output
-// may be the very buffer an input is read from (same base pointer), so every element is loaded before its index is stored.
+// converted outputs m0 (this step's), m1, m2.  m0 goes to the history ring, prev to the running sample.
 __device__ __forceinline__ void dpm_elem(const bd_dpm_step_desc& d, float e, float x, float a, float b, float& m0, float& prev) {
     m0 = d.convert ? (x - d.sigma_s * e) / d.alpha_s : e;
     if (d.x0_clip) m0 = fminf(fmaxf(m0, -d.x0_range), d.x0_range);
@@ -655,27 +665,18 @@ __device__ __forceinline__ void dpm_elem(const bd_dpm_step_desc& d, float e, flo
     if (d.clip) r = fminf(fmaxf(r, -d.clip_range), d.clip_range);
     prev = r;
 }
-__global__ __launch_bounds__(TPB) void dpm_step_kernel(bd_dpm_step_desc d, int64_t n4) {
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n4; i += (int64_t)gridDim.x * TPB) {
-        const float4 e = reinterpret_cast<const float4*>(d.model_output)[i], x = reinterpret_cast<const float4*>(d.sample)[i];
-        const float4 a = d.m1 ? reinterpret_cast<const float4*>(d.m1)[i] : zero;
-        const float4 b = d.m2 ? reinterpret_cast<const float4*>(d.m2)[i] : zero;
-        float4 m0, p;
-        dpm_elem(d, e.x, x.x, a.x, b.x, m0.x, p.x); dpm_elem(d, e.y, x.y, a.y, b.y, m0.y, p.y);
-        dpm_elem(d, e.z, x.z, a.z, b.z, m0.z, p.z); dpm_elem(d, e.w, x.w, a.w, b.w, m0.w, p.w);
-        if (d.m0_out) reinterpret_cast<float4*>(d.m0_out)[i] = m0;
-        reinterpret_cast<float4*>(d.prev_out)[i] = p;
+struct DpmOp {
+    bd_dpm_step_desc d;
+    template <class V> __device__ __forceinline__ void at(int64_t i) const {
+        V e = ld<V>(d.model_output, i), x = ld<V>(d.sample, i);
+        V a = d.m1 ? ld<V>(d.m1, i) : splat<V>(0.f);
+        V b = d.m2 ? ld<V>(d.m2, i) : splat<V>(0.f);
+        V m0, p;
+        lanes([this](float e, float x, float a, float b, float& m0, float& p) { dpm_elem(d, e, x, a, b, m0, p); }, e, x, a, b, m0, p);
+        if (d.m0_out) st<V>(d.m0_out, i, m0);
+        st<V>(d.prev_out, i, p);
     }
-    if (blockIdx.x == 0 && threadIdx.x < (d.n & 3)) {   // tail (n % 4 elements)
-        const int64_t i = (d.n & ~(int64_t)3) + threadIdx.x;
-        const float e = d.model_output[i], x = d.sample[i], a = d.m1 ? d.m1[i] : 0.f, b = d.m2 ? d.m2[i] : 0.f;
-        float m0, p;
-        dpm_elem(d, e, x, a, b, m0, p);
-        if (d.m0_out) d.m0_out[i] = m0;
-        d.prev_out[i] = p;
-    }
-}
+};
 
 
 // f-4 (UniPC, scheduling_unipc_multistep.py:257-601): one whole step in one launch -- conversion, corrector (UniC) over the history as it
@@ -684,8 +685,7 @@ __global__ __launch_bounds__(TPB) void dpm_step_kernel(bd_dpm_step_desc d, int64
 // rho weights into coefficients, but they are chained through xc and share m0 with the conversion, so bd_dpm_step cannot carry them.
 // Whether the output is converted and which of the four optional inputs are present are template parameters (the launcher picks
 // the instance from the descriptor): the tests cost nothing, and every load stays one unconditional 16-byte access -- with run-time
-// tests the compiler sinks the loads into the branches that use them and splits them into dwords.  No __restrict__, as dpm_step_kernel: every load of an index is
-// issued before its first store.
+// tests the compiler sinks the loads into the branches that use them and splits them into dwords.
 template <bool CV, bool L, bool H1, bool H2, bool H3>
 __device__ __forceinline__ void unipc_elem(const bd_unipc_step_desc& d, float e, float x, float l, float a, float b, float c, float& m0,
                                            float& xc, float& prev) {
@@ -707,41 +707,28 @@ __device__ __forceinline__ void unipc_elem(const bd_unipc_step_desc& d, float e,
     prev = r;
 }
 template <bool CV, bool L, bool H1, bool H2, bool H3>
-__global__ __launch_bounds__(TPB) void unipc_step_kernel(bd_unipc_step_desc d, int64_t n4) {
-    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n4; i += (int64_t)gridDim.x * TPB) {
-        const float4 e = reinterpret_cast<const float4*>(d.model_output)[i], x = reinterpret_cast<const float4*>(d.sample)[i];
-        float4 l = make_float4(0.f, 0.f, 0.f, 0.f), a = l, b = l, c = l;
-        if constexpr (L) l = reinterpret_cast<const float4*>(d.last_sample)[i];
-        if constexpr (H1) a = reinterpret_cast<const float4*>(d.h1)[i];
-        if constexpr (H2) b = reinterpret_cast<const float4*>(d.h2)[i];
-        if constexpr (H3) c = reinterpret_cast<const float4*>(d.h3)[i];
-        float4 m0, xc, p;
-        unipc_elem<CV, L, H1, H2, H3>(d, e.x, x.x, l.x, a.x, b.x, c.x, m0.x, xc.x, p.x);
-        unipc_elem<CV, L, H1, H2, H3>(d, e.y, x.y, l.y, a.y, b.y, c.y, m0.y, xc.y, p.y);
-        unipc_elem<CV, L, H1, H2, H3>(d, e.z, x.z, l.z, a.z, b.z, c.z, m0.z, xc.z, p.z);
-        unipc_elem<CV, L, H1, H2, H3>(d, e.w, x.w, l.w, a.w, b.w, c.w, m0.w, xc.w, p.w);
-        if (d.m0_out) reinterpret_cast<float4*>(d.m0_out)[i] = m0;
-        if (d.corrected_out) reinterpret_cast<float4*>(d.corrected_out)[i] = xc;
-        reinterpret_cast<float4*>(d.prev_out)[i] = p;
+struct UnipcOp {
+    bd_unipc_step_desc d;
+    template <class V> __device__ __forceinline__ void at(int64_t i) const {
+        V e = ld<V>(d.model_output, i), x = ld<V>(d.sample, i);
+        V l = splat<V>(0.f), a = l, b = l, c = l;
+        if constexpr (L) l = ld<V>(d.last_sample, i);
+        if constexpr (H1) a = ld<V>(d.h1, i);
+        if constexpr (H2) b = ld<V>(d.h2, i);
+        if constexpr (H3) c = ld<V>(d.h3, i);
+        V m0, xc, p;
+        lanes([this](float e, float x, float l, float a, float b, float c, float& m0, float& xc, float& p) {
+            unipc_elem<CV, L, H1, H2, H3>(d, e, x, l, a, b, c, m0, xc, p);
+        }, e, x, l, a, b, c, m0, xc, p);
+        if (d.m0_out) st<V>(d.m0_out, i, m0);
+        if (d.corrected_out) st<V>(d.corrected_out, i, xc);
+        st<V>(d.prev_out, i, p);
     }
-    if (blockIdx.x == 0 && threadIdx.x < (d.n & 3)) {   // tail (n % 4 elements)
-        const int64_t i = (d.n & ~(int64_t)3) + threadIdx.x;
-        const float e = d.model_output[i], x = d.sample[i];
-        float l = 0.f, a = 0.f, b = 0.f, c = 0.f;
-        if constexpr (L) l = d.last_sample[i];
-        if constexpr (H1) a = d.h1[i];
-        if constexpr (H2) b = d.h2[i];
-        if constexpr (H3) c = d.h3[i];
-        float m0, xc, p;
-        unipc_elem<CV, L, H1, H2, H3>(d, e, x, l, a, b, c, m0, xc, p);
-        if (d.m0_out) d.m0_out[i] = m0;
-        if (d.corrected_out) d.corrected_out[i] = xc;
-        d.prev_out[i] = p;
-    }
-}
+};
 template <bool CV, bool L, bool H1, bool H2, bool H3>
 static void unipc_launch(const bd_unipc_step_desc& d, hipStream_t stream) {
-    hipLaunchKernelGGL((unipc_step_kernel<CV, L, H1, H2, H3>), dim3(nblocks(cdiv(d.n, 4), TPB, 4096)), dim3(TPB), 0, stream, d, d.n / 4);
+    hipLaunchKernelGGL((vec4_kernel<UnipcOp<CV, L, H1, H2, H3>>), dim3(nblocks(cdiv(d.n, 4), TPB, 4096)), dim3(TPB), 0, stream,
+                       UnipcOp<CV, L, H1, H2, H3>{d}, d.n / 4, d.n);
 }
 
 
@@ -750,8 +737,8 @@ static void unipc_launch(const bd_unipc_step_desc& d, hipStream_t stream) {
 // the model output), Heun's average with the first stage's derivative or the linear multistep sum over the stored derivatives, the
 // update from `base` (Heun's second stage restarts from the sample of the first) and the NEXT evaluation's scale_model_input, which
 // is what makes the launch worth fusing: every UNet evaluation of these samplers reads x / sqrt(sigma^2 + 1).  The optional inputs are
-// template parameters as in unipc_step_kernel (every load one unconditional 16-byte access); NH counts the history terms of the sum
-// (AVG reads h1 for the average and has none).  No __restrict__: an output may be an input's own buffer.
+// template parameters as in UnipcOp (every load one unconditional 16-byte access); NH counts the history terms of the sum
+// (AVG reads h1 for the average and has none).
 template <bool AVG, int NH>
 __device__ __forceinline__ void sigma_elem(const bd_sigma_step_desc& d, float e, float x, float b, float h1, float h2, float h3, float& x0,
                                            float& dv, float& prev, float& sc) {
@@ -771,60 +758,42 @@ __device__ __forceinline__ void sigma_elem(const bd_sigma_step_desc& d, float e,
     }
 }
 template <bool AVG, int NH, bool BASE>
-__global__ __launch_bounds__(TPB) void sigma_step_kernel(bd_sigma_step_desc d, int64_t n4) {
-    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n4; i += (int64_t)gridDim.x * TPB) {
-        const float4 e = reinterpret_cast<const float4*>(d.model_output)[i], x = reinterpret_cast<const float4*>(d.sample)[i];
-        float4 b = x, h1 = make_float4(0.f, 0.f, 0.f, 0.f), h2 = h1, h3 = h1;
-        if constexpr (BASE) b = reinterpret_cast<const float4*>(d.base)[i];
-        if constexpr (AVG || NH >= 1) h1 = reinterpret_cast<const float4*>(d.h1)[i];
-        if constexpr (!AVG && NH >= 2) h2 = reinterpret_cast<const float4*>(d.h2)[i];
-        if constexpr (!AVG && NH >= 3) h3 = reinterpret_cast<const float4*>(d.h3)[i];
-        float4 x0, dv, p, sc;
-        sigma_elem<AVG, NH>(d, e.x, x.x, b.x, h1.x, h2.x, h3.x, x0.x, dv.x, p.x, sc.x);
-        sigma_elem<AVG, NH>(d, e.y, x.y, b.y, h1.y, h2.y, h3.y, x0.y, dv.y, p.y, sc.y);
-        sigma_elem<AVG, NH>(d, e.z, x.z, b.z, h1.z, h2.z, h3.z, x0.z, dv.z, p.z, sc.z);
-        sigma_elem<AVG, NH>(d, e.w, x.w, b.w, h1.w, h2.w, h3.w, x0.w, dv.w, p.w, sc.w);
-        if (d.x0_out) reinterpret_cast<float4*>(d.x0_out)[i] = x0;
-        if (d.d_out) reinterpret_cast<float4*>(d.d_out)[i] = dv;
-        reinterpret_cast<float4*>(d.prev_out)[i] = p;
-        if (d.scaled_out) reinterpret_cast<float4*>(d.scaled_out)[i] = sc;
+struct SigmaOp {
+    bd_sigma_step_desc d;
+    template <class V> __device__ __forceinline__ void at(int64_t i) const {
+        V e = ld<V>(d.model_output, i), x = ld<V>(d.sample, i);
+        V b = x, h1 = splat<V>(0.f), h2 = h1, h3 = h1;
+        if constexpr (BASE) b = ld<V>(d.base, i);
+        if constexpr (AVG || NH >= 1) h1 = ld<V>(d.h1, i);
+        if constexpr (!AVG && NH >= 2) h2 = ld<V>(d.h2, i);
+        if constexpr (!AVG && NH >= 3) h3 = ld<V>(d.h3, i);
+        V x0, dv, p, sc;
+        lanes([this](float e, float x, float b, float h1, float h2, float h3, float& x0, float& dv, float& p, float& sc) {
+            sigma_elem<AVG, NH>(d, e, x, b, h1, h2, h3, x0, dv, p, sc);
+        }, e, x, b, h1, h2, h3, x0, dv, p, sc);
+        if (d.x0_out) st<V>(d.x0_out, i, x0);
+        if (d.d_out) st<V>(d.d_out, i, dv);
+        st<V>(d.prev_out, i, p);
+        if (d.scaled_out) st<V>(d.scaled_out, i, sc);
     }
-    if (blockIdx.x == 0 && threadIdx.x < (d.n & 3)) {   // tail (n % 4 elements)
-        const int64_t i = (d.n & ~(int64_t)3) + threadIdx.x;
-        const float e = d.model_output[i], x = d.sample[i];
-        float b = x, h1 = 0.f, h2 = 0.f, h3 = 0.f;
-        if constexpr (BASE) b = d.base[i];
-        if constexpr (AVG || NH >= 1) h1 = d.h1[i];
-        if constexpr (!AVG && NH >= 2) h2 = d.h2[i];
-        if constexpr (!AVG && NH >= 3) h3 = d.h3[i];
-        float x0, dv, p, sc;
-        sigma_elem<AVG, NH>(d, e, x, b, h1, h2, h3, x0, dv, p, sc);
-        if (d.x0_out) d.x0_out[i] = x0;
-        if (d.d_out) d.d_out[i] = dv;
-        d.prev_out[i] = p;
-        if (d.scaled_out) d.scaled_out[i] = sc;
-    }
-}
+};
 template <bool AVG, int NH>
 static void sigma_launch(const bd_sigma_step_desc& d, hipStream_t stream) {
     const dim3 grid(nblocks(cdiv(d.n, 4), TPB, 4096));
-    if (d.base) hipLaunchKernelGGL((sigma_step_kernel<AVG, NH, true>), grid, dim3(TPB), 0, stream, d, d.n / 4);
-    else hipLaunchKernelGGL((sigma_step_kernel<AVG, NH, false>), grid, dim3(TPB), 0, stream, d, d.n / 4);
+    if (d.base) hipLaunchKernelGGL((vec4_kernel<SigmaOp<AVG, NH, true>>), grid, dim3(TPB), 0, stream, SigmaOp<AVG, NH, true>{d}, d.n / 4, d.n);
+    else hipLaunchKernelGGL((vec4_kernel<SigmaOp<AVG, NH, false>>), grid, dim3(TPB), 0, stream, SigmaOp<AVG, NH, false>{d}, d.n / 4, d.n);
 }
 
 // out = (x * mul) / div: the start of a sigma-space chain (init * init_noise_sigma, then / sqrt(sigma_0^2 + 1)) and the public
 // scale_model_input (mul = 1: x * 1 is x).  out may be x.
-__global__ __launch_bounds__(TPB) void scale_input_kernel(const float* x, int64_t n4, int64_t n, float mul, float div, float* out) {
-    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n4; i += (int64_t)gridDim.x * TPB) {
-        float4 v = reinterpret_cast<const float4*>(x)[i];
-        v.x = (v.x * mul) / div; v.y = (v.y * mul) / div; v.z = (v.z * mul) / div; v.w = (v.w * mul) / div;
-        reinterpret_cast<float4*>(out)[i] = v;
+struct ScaleInputOp {
+    const float* x; float mul, div; float* out;
+    template <class V> __device__ __forceinline__ void at(int64_t i) const {
+        V v = ld<V>(x, i);
+        lanes([this](float& v) { v = (v * mul) / div; }, v);
+        st<V>(out, i, v);
     }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {   // tail (n % 4 elements)
-        const int64_t i = (n & ~(int64_t)3) + threadIdx.x;
-        out[i] = (x[i] * mul) / div;
-    }
-}
+};
 
 
 // ---- f-4: Adversarial Neuron Pruning (anp_model.py:490-514 PerturbConv2d = conv followed by an eval-mode batch norm with mean 0, variance 1,
@@ -891,6 +860,15 @@ __global__ __launch_bounds__(TPB) void anp_grad_kernel(const float* __restrict__
     }
 }
 
+// step_buffers_bad (step_check.h) with the message of its first violation, for the entry points that name their operands
+static int step_buffers_check(const char* who, int64_t n, const StepBuf* in, int n_in, const StepBuf* out, int n_out) {
+    const StepViolation v = step_buffers_bad(n, in, n_in, out, n_out);
+    BD_CHECK(v.code != STEP_MISALIGNED, BD_ERR_INVALID, "%s: %s is not 16-byte aligned", who, (v.a < n_in ? in[v.a] : out[v.a - n_in]).name);
+    BD_CHECK(v.code != STEP_OUT_OUT, BD_ERR_INVALID, "%s: %s overlaps %s", who, out[v.a].name, out[v.b].name);
+    BD_CHECK(v.code != STEP_OUT_IN, BD_ERR_INVALID, "%s: %s overlaps %s without being the same buffer", who, out[v.a].name, in[v.b].name);
+    return BD_OK;
+}
+
 }  // namespace bd
 
 using namespace bd;
@@ -949,20 +927,19 @@ extern "C" int bd_ddpm_step(const bd_ddpm_step_desc* d, bd_stream_t stream) {
 extern "C" int bd_lincomb(int k, const float* const* terms, const float* coeffs, int64_t n, int clip, float clip_range, float* out,
                           bd_stream_t stream) {
     BD_CHECK(k >= 1 && k <= BD_LINCOMB_MAX && terms && coeffs && out && n > 0, BD_ERR_INVALID, "bd_lincomb: bad args (k=%d)", k);
-    LincombArgs a = {};
-    a.k = k; a.clip = clip; a.range = clip_range;
+    LincombOp a = {};
+    a.k = k; a.clip = clip; a.range = clip_range; a.out = out;
+    StepBuf in[BD_LINCOMB_MAX];
     for (int j = 0; j < k; ++j) {
         BD_CHECK(terms[j] && aligned16(terms[j]), BD_ERR_INVALID, "bd_lincomb: term %d is null or not 16-byte aligned", j);
         a.t[j] = terms[j]; a.c[j] = coeffs[j];
+        in[j] = {terms[j], "term"};
     }
-    BD_CHECK(aligned16(out), BD_ERR_INVALID, "bd_lincomb: out must be 16-byte aligned");
-    // out may be a term's own buffer (same base: each index is read before it is written), nothing else may overlap
-    const uintptr_t bytes = (uintptr_t)n * sizeof(float), o = reinterpret_cast<uintptr_t>(out);
-    for (int j = 0; j < k; ++j) {
-        const uintptr_t t = reinterpret_cast<uintptr_t>(terms[j]);
-        BD_CHECK(t == o || !(t < o + bytes && o < t + bytes), BD_ERR_INVALID, "bd_lincomb: out overlaps term %d without being the same buffer", j);
-    }
-    hipLaunchKernelGGL(lincomb_kernel, dim3(nblocks(cdiv(n, 4), TPB, 4096)), dim3(TPB), 0, S(stream), a, out, n / 4, n);
+    const StepBuf o = {out, "out"};
+    const StepViolation v = step_buffers_bad(n, in, k, &o, 1);
+    BD_CHECK(v.code != STEP_MISALIGNED, BD_ERR_INVALID, "bd_lincomb: out must be 16-byte aligned");
+    BD_CHECK(v.code == STEP_OK, BD_ERR_INVALID, "bd_lincomb: out overlaps term %d without being the same buffer", v.b);
+    hipLaunchKernelGGL(lincomb_kernel, dim3(nblocks(cdiv(n, 4), TPB, 4096)), dim3(TPB), 0, S(stream), a, n / 4, n);
     BD_LAUNCH_CHECK("lincomb");
     return BD_OK;
 }
@@ -971,26 +948,10 @@ extern "C" int bd_dpm_step(const bd_dpm_step_desc* d, bd_stream_t stream) {
     BD_CHECK(d->n > 0, BD_ERR_INVALID, "bd_dpm_step: n=%lld must be positive", (long long)d->n);
     BD_CHECK(d->model_output && d->sample && d->prev_out, BD_ERR_INVALID,
              "bd_dpm_step: null pointer (model_output, sample and prev_out are required)");
-    const void* in[4] = {d->model_output, d->sample, d->m1, d->m2};
-    const void* out[2] = {d->prev_out, d->m0_out};
-    static const char* const in_name[4] = {"model_output", "sample", "m1", "m2"};
-    static const char* const out_name[2] = {"prev_out", "m0_out"};
-    for (int j = 0; j < 4; ++j) BD_CHECK(aligned16(in[j]), BD_ERR_INVALID, "bd_dpm_step: %s is not 16-byte aligned", in_name[j]);
-    for (int j = 0; j < 2; ++j) BD_CHECK(aligned16(out[j]), BD_ERR_INVALID, "bd_dpm_step: %s is not 16-byte aligned", out_name[j]);
-    // an output may be an input's own buffer (same base: each index is read before it is written), nothing else may overlap
-    const uintptr_t bytes = (uintptr_t)d->n * sizeof(float);
-    auto overlap = [bytes](const void* p, const void* q) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-        return a < b + bytes && b < a + bytes;
-    };
-    for (int o = 0; o < 2; ++o) {
-        if (!out[o]) continue;
-        for (int j = 0; j < 4; ++j)
-            BD_CHECK(!in[j] || in[j] == out[o] || !overlap(in[j], out[o]), BD_ERR_INVALID,
-                     "bd_dpm_step: %s overlaps %s without being the same buffer", out_name[o], in_name[j]);
-    }
-    BD_CHECK(!d->m0_out || !overlap(d->m0_out, d->prev_out), BD_ERR_INVALID, "bd_dpm_step: m0_out overlaps prev_out");
-    hipLaunchKernelGGL(dpm_step_kernel, dim3(nblocks(cdiv(d->n, 4), TPB, 4096)), dim3(TPB), 0, S(stream), *d, d->n / 4);
+    const StepBuf in[4] = {{d->model_output, "model_output"}, {d->sample, "sample"}, {d->m1, "m1"}, {d->m2, "m2"}};
+    const StepBuf out[2] = {{d->prev_out, "prev_out"}, {d->m0_out, "m0_out"}};
+    BD_TRY(step_buffers_check("bd_dpm_step", d->n, in, 4, out, 2));
+    hipLaunchKernelGGL(vec4_kernel<DpmOp>, dim3(nblocks(cdiv(d->n, 4), TPB, 4096)), dim3(TPB), 0, S(stream), DpmOp{*d}, d->n / 4, d->n);
     BD_LAUNCH_CHECK("dpm_step");
     return BD_OK;
 }
@@ -1000,29 +961,10 @@ extern "C" int bd_unipc_step(const bd_unipc_step_desc* d, bd_stream_t stream) {
     BD_CHECK(d->model_output && d->sample && d->prev_out, BD_ERR_INVALID,
              "bd_unipc_step: null pointer (model_output, sample and prev_out are required)");
     BD_CHECK(!d->last_sample || d->h1, BD_ERR_INVALID, "bd_unipc_step: last_sample without h1 (the corrector reads the previous converted output)");
-    const void* in[6] = {d->model_output, d->sample, d->last_sample, d->h1, d->h2, d->h3};
-    const void* out[3] = {d->prev_out, d->m0_out, d->corrected_out};
-    static const char* const in_name[6] = {"model_output", "sample", "last_sample", "h1", "h2", "h3"};
-    static const char* const out_name[3] = {"prev_out", "m0_out", "corrected_out"};
-    for (int j = 0; j < 6; ++j) BD_CHECK(aligned16(in[j]), BD_ERR_INVALID, "bd_unipc_step: %s is not 16-byte aligned", in_name[j]);
-    for (int j = 0; j < 3; ++j) BD_CHECK(aligned16(out[j]), BD_ERR_INVALID, "bd_unipc_step: %s is not 16-byte aligned", out_name[j]);
-    // an output may be an input's own buffer (same base: each index is read before it is written), nothing else may overlap
-    const uintptr_t bytes = (uintptr_t)d->n * sizeof(float);
-    auto overlap = [bytes](const void* p, const void* q) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-        return a < b + bytes && b < a + bytes;
-    };
-    for (int o = 0; o < 3; ++o) {
-        if (!out[o]) continue;
-        for (int p = 0; p < o; ++p)
-            BD_CHECK(!out[p] || !overlap(out[p], out[o]), BD_ERR_INVALID, "bd_unipc_step: %s overlaps %s", out_name[o], out_name[p]);
-    }
-    for (int o = 0; o < 3; ++o) {
-        if (!out[o]) continue;
-        for (int j = 0; j < 6; ++j)
-            BD_CHECK(!in[j] || in[j] == out[o] || !overlap(in[j], out[o]), BD_ERR_INVALID,
-                     "bd_unipc_step: %s overlaps %s without being the same buffer", out_name[o], in_name[j]);
-    }
+    const StepBuf in[6] = {{d->model_output, "model_output"}, {d->sample, "sample"}, {d->last_sample, "last_sample"},
+                           {d->h1, "h1"}, {d->h2, "h2"}, {d->h3, "h3"}};
+    const StepBuf out[3] = {{d->prev_out, "prev_out"}, {d->m0_out, "m0_out"}, {d->corrected_out, "corrected_out"}};
+    BD_TRY(step_buffers_check("bd_unipc_step", d->n, in, 6, out, 3));
     // instance by the conversion and by which optional inputs are present: bit 4 convert, bit 3 last_sample, bits 2..0 h1, h2, h3
     // (last_sample without h1 was refused above)
     const int instance = (d->convert ? 16 : 0) | (d->last_sample ? 8 : 0) | (d->h1 ? 4 : 0) | (d->h2 ? 2 : 0) | (d->h3 ? 1 : 0);
@@ -1049,26 +991,9 @@ extern "C" int bd_sigma_step(const bd_sigma_step_desc* d, bd_stream_t stream) {
     BD_CHECK(!d->average || (!d->h2 && !d->h3 && d->c1 == 0.f && d->c2 == 0.f && d->c3 == 0.f), BD_ERR_INVALID,
              "bd_sigma_step: average with history terms (h2 / h3 or a non-zero c1 / c2 / c3)");
     BD_CHECK((d->h1 || !d->h2) && (d->h2 || !d->h3), BD_ERR_INVALID, "bd_sigma_step: history with a gap (h2 without h1, or h3 without h2)");
-    const void* in[6] = {d->model_output, d->sample, d->base, d->h1, d->h2, d->h3};
-    const void* out[4] = {d->prev_out, d->x0_out, d->d_out, d->scaled_out};
-    static const char* const in_name[6] = {"model_output", "sample", "base", "h1", "h2", "h3"};
-    static const char* const out_name[4] = {"prev_out", "x0_out", "d_out", "scaled_out"};
-    for (int j = 0; j < 6; ++j) BD_CHECK(aligned16(in[j]), BD_ERR_INVALID, "bd_sigma_step: %s is not 16-byte aligned", in_name[j]);
-    for (int j = 0; j < 4; ++j) BD_CHECK(aligned16(out[j]), BD_ERR_INVALID, "bd_sigma_step: %s is not 16-byte aligned", out_name[j]);
-    // an output may be an input's own buffer (same base: each index is read before it is written), nothing else may overlap
-    const uintptr_t bytes = (uintptr_t)d->n * sizeof(float);
-    auto overlap = [bytes](const void* p, const void* q) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-        return a < b + bytes && b < a + bytes;
-    };
-    for (int o = 0; o < 4; ++o) {
-        if (!out[o]) continue;
-        for (int p = 0; p < o; ++p)
-            BD_CHECK(!out[p] || !overlap(out[p], out[o]), BD_ERR_INVALID, "bd_sigma_step: %s overlaps %s", out_name[o], out_name[p]);
-        for (int j = 0; j < 6; ++j)
-            BD_CHECK(!in[j] || in[j] == out[o] || !overlap(in[j], out[o]), BD_ERR_INVALID,
-                     "bd_sigma_step: %s overlaps %s without being the same buffer", out_name[o], in_name[j]);
-    }
+    const StepBuf in[6] = {{d->model_output, "model_output"}, {d->sample, "sample"}, {d->base, "base"}, {d->h1, "h1"}, {d->h2, "h2"}, {d->h3, "h3"}};
+    const StepBuf out[4] = {{d->prev_out, "prev_out"}, {d->x0_out, "x0_out"}, {d->d_out, "d_out"}, {d->scaled_out, "scaled_out"}};
+    BD_TRY(step_buffers_check("bd_sigma_step", d->n, in, 6, out, 4));
     if (d->average) sigma_launch<true, 0>(*d, S(stream));
     else if (d->h3) sigma_launch<false, 3>(*d, S(stream));
     else if (d->h2) sigma_launch<false, 2>(*d, S(stream));
@@ -1081,10 +1006,12 @@ extern "C" int bd_scale_input(const float* x, int64_t n, float mul, float div, f
     BD_CHECK(x && out, BD_ERR_INVALID, "bd_scale_input: null pointer");
     BD_CHECK(n > 0, BD_ERR_INVALID, "bd_scale_input: n=%lld must be positive", (long long)n);
     BD_CHECK(div > 0.f, BD_ERR_INVALID, "bd_scale_input: div=%g must be positive", (double)div);
-    BD_CHECK(aligned16(x) && aligned16(out), BD_ERR_INVALID, "bd_scale_input: x and out must be 16-byte aligned");
-    const uintptr_t bytes = (uintptr_t)n * sizeof(float), a = reinterpret_cast<uintptr_t>(x), b = reinterpret_cast<uintptr_t>(out);
-    BD_CHECK(a == b || !(a < b + bytes && b < a + bytes), BD_ERR_INVALID, "bd_scale_input: out overlaps x without being the same buffer");
-    hipLaunchKernelGGL(scale_input_kernel, dim3(nblocks(cdiv(n, 4), TPB, 4096)), dim3(TPB), 0, S(stream), x, n / 4, n, mul, div, out);
+    const StepBuf in = {x, "x"}, o = {out, "out"};
+    const StepViolation v = step_buffers_bad(n, &in, 1, &o, 1);
+    BD_CHECK(v.code != STEP_MISALIGNED, BD_ERR_INVALID, "bd_scale_input: x and out must be 16-byte aligned");
+    BD_CHECK(v.code == STEP_OK, BD_ERR_INVALID, "bd_scale_input: out overlaps x without being the same buffer");
+    hipLaunchKernelGGL(vec4_kernel<ScaleInputOp>, dim3(nblocks(cdiv(n, 4), TPB, 4096)), dim3(TPB), 0, S(stream),
+                       ScaleInputOp{x, mul, div, out}, n / 4, n);
     BD_LAUNCH_CHECK("scale_input");
     return BD_OK;
 }

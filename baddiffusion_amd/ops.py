@@ -701,6 +701,24 @@ def loss_groups_fwd_bwd(pred, target, groups, loss_type="l2", grad_scale=1.0, wa
     return losses, dp
 
 
+def _dense_out(who, first, others, out):
+    """What the wrappers of the dense vec4 kernels open with: `first` is non-empty, float32 and dense, and every tensor of `others`
+    that is present, and `out`, has its shape, strides and dtype.  Returns out, allocated like `first` when None."""
+    if first.dtype != torch.float32 or first.numel() == 0 or not _is_dense(first):
+        raise ValueError(f"{who}: tensors must be non-empty, float32 and dense")
+    if out is None:
+        out = torch.empty_like(first)
+    for t in (*others, out):
+        if t is not None and (t.shape != first.shape or t.stride() != first.stride() or t.dtype != torch.float32):
+            raise ValueError(f"{who}: tensors must share shape, strides and dtype float32")
+    return out
+
+
+def _clip_pair(clip):
+    """None or the range of a clamp -> the descriptor's (flag, range)"""
+    return (0, 0.0) if clip is None else (1, float(clip))
+
+
 def lincomb(terms, coeffs, clip=None, out=None):
     """out = clamp?(sum_j coeffs[j] * terms[j]) (bd_lincomb): up to 6 dense float32 GPU tensors of one shape and layout.  out (of the
     terms' shape, strides and dtype) may be one of the terms; the library refuses any other overlap."""
@@ -708,20 +726,10 @@ def lincomb(terms, coeffs, clip=None, out=None):
     k = len(terms)
     if k < 1 or k > 6 or len(coeffs) != k:
         raise ValueError("lincomb: 1..6 terms with one coefficient each")
-    t0 = terms[0]
-    for t in terms:
-        if t.shape != t0.shape or t.stride() != t0.stride() or t.dtype != torch.float32:
-            raise ValueError("lincomb: terms must share shape, strides and dtype float32")
-    if not t0.permute(*sorted(range(t0.dim()), key=lambda d: -t0.stride(d))).is_contiguous():
-        raise ValueError("lincomb: terms must be dense")
-    if out is None:
-        out = torch.empty_like(t0)
-    elif out.shape != t0.shape or out.stride() != t0.stride() or out.dtype != torch.float32:
-        raise ValueError("lincomb: out must have the terms' shape, strides and dtype float32")
+    out = _dense_out("lincomb", terms[0], terms[1:], out)
     ptrs = (C.c_void_p * k)(*[t.data_ptr() for t in terms])
     cs = (C.c_float * k)(*[float(c) for c in coeffs])
-    L.check(lib.bd_lincomb(k, ptrs, cs, t0.numel(), 0 if clip is None else 1, 0.0 if clip is None else float(clip), L.ptr(out),
-                           L.stream()), "bd_lincomb")
+    L.check(lib.bd_lincomb(k, ptrs, cs, terms[0].numel(), *_clip_pair(clip), L.ptr(out), L.stream()), "bd_lincomb")
     return out
 
 
@@ -733,19 +741,13 @@ def dpm_step(model_output, sample, cx, c0, m1=None, c1=0.0, m2=None, c2=0.0, con
     previous two steps, or None (term absent); m0_out: where m0 is written, or None.  out may be `sample`, m0_out may be the oldest
     history buffer (m2 included): the library refuses any other overlap.  Returns prev_sample."""
     lib = L.load(); _need_cuda(model_output, sample, m1, m2, m0_out, out)
-    if sample.dtype != torch.float32 or sample.numel() == 0 or not _is_dense(sample):
-        raise ValueError("dpm_step: tensors must be non-empty, float32 and dense")
-    if out is None:
-        out = torch.empty_like(sample)
-    for t in (model_output, m1, m2, m0_out, out):
-        if t is not None and (t.shape != sample.shape or t.stride() != sample.stride() or t.dtype != torch.float32):
-            raise ValueError("dpm_step: tensors must share shape, strides and dtype float32")
+    out = _dense_out("dpm_step", sample, (model_output, m1, m2, m0_out), out)
     alpha_s, sigma_s = (1.0, 0.0) if convert is None else convert
+    (x0_on, x0_range), (clip_on, clip_range) = _clip_pair(x0_clip), _clip_pair(clip)
     d = L.DpmStepDesc(n=sample.numel(), model_output=L.ptr(model_output), sample=L.ptr(sample), m1=L.ptr(m1), m2=L.ptr(m2),
                       m0_out=L.ptr(m0_out), prev_out=L.ptr(out), convert=int(convert is not None), alpha_s=float(alpha_s),
-                      sigma_s=float(sigma_s), x0_clip=int(x0_clip is not None), x0_range=0.0 if x0_clip is None else float(x0_clip),
-                      cx=float(cx), c0=float(c0), c1=float(c1), c2=float(c2), clip=int(clip is not None),
-                      clip_range=0.0 if clip is None else float(clip))
+                      sigma_s=float(sigma_s), x0_clip=x0_on, x0_range=x0_range, cx=float(cx), c0=float(c0), c1=float(c1), c2=float(c2),
+                      clip=clip_on, clip_range=clip_range)
     L.check(lib.bd_dpm_step(C.byref(d), L.stream()), "bd_dpm_step")
     return out
 
@@ -759,21 +761,14 @@ def unipc_step(model_output, sample, px, p0, h1=None, p1=0.0, h2=None, p2=0.0, h
     written, or None.  out may be `sample`, corrected_out may be `last_sample`, m0_out may be the oldest history buffer (h2 or h3
     included): the library refuses any other overlap.  Returns prev_sample."""
     lib = L.load(); _need_cuda(model_output, sample, last_sample, h1, h2, h3, m0_out, corrected_out, out)
-    if sample.dtype != torch.float32 or sample.numel() == 0 or not _is_dense(sample):
-        raise ValueError("unipc_step: tensors must be non-empty, float32 and dense")
-    if out is None:
-        out = torch.empty_like(sample)
-    for t in (model_output, last_sample, h1, h2, h3, m0_out, corrected_out, out):
-        if t is not None and (t.shape != sample.shape or t.stride() != sample.stride() or t.dtype != torch.float32):
-            raise ValueError("unipc_step: tensors must share shape, strides and dtype float32")
+    out = _dense_out("unipc_step", sample, (model_output, last_sample, h1, h2, h3, m0_out, corrected_out), out)
     alpha_s, sigma_s = (1.0, 0.0) if convert is None else convert
+    (x0_on, x0_range), (clip_on, clip_range) = _clip_pair(x0_clip), _clip_pair(clip)
     d = L.UnipcStepDesc(n=sample.numel(), model_output=L.ptr(model_output), sample=L.ptr(sample), last_sample=L.ptr(last_sample),
                         h1=L.ptr(h1), h2=L.ptr(h2), h3=L.ptr(h3), m0_out=L.ptr(m0_out), corrected_out=L.ptr(corrected_out),
                         prev_out=L.ptr(out), convert=int(convert is not None), alpha_s=float(alpha_s), sigma_s=float(sigma_s),
-                        x0_clip=int(x0_clip is not None), x0_range=0.0 if x0_clip is None else float(x0_clip),
-                        kl=float(kl), k0=float(k0), k1=float(k1), k2=float(k2), k3=float(k3),
-                        px=float(px), p0=float(p0), p1=float(p1), p2=float(p2), clip=int(clip is not None),
-                        clip_range=0.0 if clip is None else float(clip))
+                        x0_clip=x0_on, x0_range=x0_range, kl=float(kl), k0=float(k0), k1=float(k1), k2=float(k2), k3=float(k3),
+                        px=float(px), p0=float(p0), p1=float(p1), p2=float(p2), clip=clip_on, clip_range=clip_range)
     L.check(lib.bd_unipc_step(C.byref(d), L.stream()), "bd_unipc_step")
     return out
 
@@ -787,18 +782,12 @@ def sigma_step(model_output, sample, sigma_in, c0, in_div, base=None, average=Fa
     pred_original_sample, the derivative and the scaled sample are written, or None.  d_out may be the oldest history buffer, out may
     be `sample`: the library refuses any other overlap.  Returns prev_sample."""
     lib = L.load(); _need_cuda(model_output, sample, base, h1, h2, h3, x0_out, d_out, scaled_out, out)
-    if sample.dtype != torch.float32 or sample.numel() == 0 or not _is_dense(sample):
-        raise ValueError("sigma_step: tensors must be non-empty, float32 and dense")
-    if out is None:
-        out = torch.empty_like(sample)
-    for t in (model_output, base, h1, h2, h3, x0_out, d_out, scaled_out, out):
-        if t is not None and (t.shape != sample.shape or t.stride() != sample.stride() or t.dtype != torch.float32):
-            raise ValueError("sigma_step: tensors must share shape, strides and dtype float32")
+    out = _dense_out("sigma_step", sample, (model_output, base, h1, h2, h3, x0_out, d_out, scaled_out), out)
+    clip_on, clip_range = _clip_pair(clip)
     d = L.SigmaStepDesc(n=sample.numel(), model_output=L.ptr(model_output), sample=L.ptr(sample), base=L.ptr(base), h1=L.ptr(h1),
                         h2=L.ptr(h2), h3=L.ptr(h3), x0_out=L.ptr(x0_out), d_out=L.ptr(d_out), prev_out=L.ptr(out),
                         scaled_out=L.ptr(scaled_out), sigma_in=float(sigma_in), average=int(bool(average)), c0=float(c0), c1=float(c1),
-                        c2=float(c2), c3=float(c3), in_div=float(in_div), clip=int(clip is not None),
-                        clip_range=0.0 if clip is None else float(clip))
+                        c2=float(c2), c3=float(c3), in_div=float(in_div), clip=clip_on, clip_range=clip_range)
     L.check(lib.bd_sigma_step(C.byref(d), L.stream()), "bd_sigma_step")
     return out
 
@@ -806,12 +795,7 @@ def sigma_step(model_output, sample, sigma_in, c0, in_div, base=None, average=Fa
 def scale_input(x, mul, div, out=None):
     """out = (x * mul) / div (bd_scale_input) over a dense float32 GPU tensor; out may be x."""
     lib = L.load(); _need_cuda(x, out)
-    if x.dtype != torch.float32 or x.numel() == 0 or not _is_dense(x):
-        raise ValueError("scale_input: x must be non-empty, float32 and dense")
-    if out is None:
-        out = torch.empty_like(x)
-    elif out.shape != x.shape or out.stride() != x.stride() or out.dtype != torch.float32:
-        raise ValueError("scale_input: out must have x's shape, strides and dtype float32")
+    out = _dense_out("scale_input", x, (), out)
     L.check(lib.bd_scale_input(L.ptr(x), x.numel(), float(mul), float(div), L.ptr(out), L.stream()), "bd_scale_input")
     return out
 

@@ -1,7 +1,7 @@
 """DDPMPipeline / DDIMPipeline -- drop-in for the two (locally modified) pipelines BadDiffusion samples with
-(/root/reference/diffusers/src/diffusers/pipelines/ddpm/pipeline_ddpm.py:46-125,
- pipelines/ddim/pipeline_ddim.py:50-142), including the repo's additions `init=`, `save_every_step=`,
-`start_from=` and the `.movie` output.
+(diffusers/src/diffusers/pipelines/ddpm/pipeline_ddpm.py:46-125, pipelines/ddim/pipeline_ddim.py:50-142 of the reference tree),
+including the repo's additions `init=`, `save_every_step=`, `start_from=` and the `.movie` output -- and the pipelines of the other
+samplers: PNDM, DPM-Solver(++), UniPC (_MultistepPipeline), Heun, LMS (_SigmaPipeline) and RePaint.
 
 Loop body = one UNet forward (bd_unet_forward) + one fused scheduler step kernel; the image never leaves the
 GPU until the final (x/2+0.5).clamp(0,1) -> NHWC conversion (bd_to_image).  With a CPU `generator` the
@@ -101,6 +101,21 @@ class _PipelineBase:
         # keep the running sample in NHWC storage (what the UNet consumes and produces)
         return ops.nchw_to_nhwc(image.float()), shape
 
+    def _finish(self, image, shape, mov, output_type, save_every_step, return_dict):
+        """What every __call__ returns: the final sample (NHWC storage) as device uint8 ("u8"), PIL images ("pil", the movie's frames
+        too) or float32 numpy (anything else), alone in a tuple or with the movie in an ImagePipelineOutput."""
+        if output_type == "u8":
+            images = self._to_u8(image, shape)
+            return ImagePipelineOutput(images=images, movie=mov) if return_dict else (images,)
+        images = self._to_numpy(image, shape)
+        if output_type == "pil":
+            images = self.numpy_to_pil(images)
+            if save_every_step:
+                mov = list(map(self.numpy_to_pil, mov))
+        if not return_dict:
+            return (images,)
+        return ImagePipelineOutput(images=images, movie=mov)
+
     def noise_draws(self, num_inference_steps=None, start_from=0, eta=0.0, **kwargs):
         """How many chunk-shaped tensors ONE call draws from its generator after the initial sample: what a rank that owns no row of a chunk
         must draw and discard to keep a shared CPU stream in the unsharded order (model.batch_sampling_save(parity=True))."""
@@ -149,17 +164,7 @@ class DDPMPipeline(_PipelineBase):
                                         ).prev_sample.permute(0, 2, 3, 1)
             if save_every_step:
                 mov.append(self._to_numpy(image, shape))
-        if output_type == "u8":
-            images = self._to_u8(image, shape)
-            return ImagePipelineOutput(images=images, movie=mov) if return_dict else (images,)
-        images = self._to_numpy(image, shape)
-        if output_type == "pil":
-            images = self.numpy_to_pil(images)
-            if save_every_step:
-                mov = list(map(self.numpy_to_pil, mov))
-        if not return_dict:
-            return (images,)
-        return ImagePipelineOutput(images=images, movie=mov)
+        return self._finish(image, shape, mov, output_type, save_every_step, return_dict)
 
 
 class DDIMPipeline(_PipelineBase):
@@ -191,71 +196,19 @@ class DDIMPipeline(_PipelineBase):
                                         generator=generator).prev_sample.permute(0, 2, 3, 1)
             if save_every_step:
                 mov.append(self._to_numpy(image, shape))
-        if output_type == "u8":
-            images = self._to_u8(image, shape)
-            return ImagePipelineOutput(images=images, movie=mov) if return_dict else (images,)
-        images = self._to_numpy(image, shape)
-        if output_type == "pil":
-            images = self.numpy_to_pil(images)
-            if save_every_step:
-                mov = list(map(self.numpy_to_pil, mov))
-        if not return_dict:
-            return (images,)
-        return ImagePipelineOutput(images=images, movie=mov)
-
-
-class PNDMPipeline(_PipelineBase):
-    """pipelines/pndm/pipeline_pndm.py:39-122 (the reference's modified copy: `clip_sample` / `clip_sample_range`, `init`,
-    `start_from`, `save_every_step`).  Whatever scheduler it is given is converted to a PNDMScheduler from its config
-    (:46) -- which is how every `--sched` other than DDPM / DDIM samples in the reference.  The post-step clamp (:108-109)
-    is folded into the scheduler's update kernel."""
-
-    def __init__(self, unet, scheduler, clip_sample=False, clip_sample_range=1.0):
-        super().__init__(unet, PNDMScheduler.from_config(scheduler.config))
-        self.clip_sample = clip_sample
-        self.clip_sample_range = clip_sample_range
-
-    def encode(self, image, *args, **kwargs):
-        return image
-
-    def decode(self, image, *args, **kwargs):
-        return image
-
-    @_static_weights
-    @torch.no_grad()
-    def __call__(self, batch_size=1, num_inference_steps=50, start_from=0, generator=None, output_type="pil", init=None,
-                 save_every_step=False, return_dict=True, **kwargs):
-        image, shape = self._start(batch_size, generator, init)
-        mov = [self._to_numpy(image, shape)] if save_every_step else []
-        self.scheduler.set_timesteps(num_inference_steps)
-        ts_host = self.scheduler.timesteps[int(start_from):]
-        ts_dev = torch.as_tensor(ts_host, dtype=torch.int64).to(self.device)
-        clip = float(self.clip_sample_range) if self.clip_sample else None
-        for i, t in enumerate(self.progress_bar(ts_host)):
-            eps = self.unet(image.permute(0, 3, 1, 2), ts_dev[i]).sample
-            image = self.scheduler.step(eps, int(t), image.permute(0, 3, 1, 2), clip=clip).prev_sample.permute(0, 2, 3, 1)
-            if save_every_step:
-                mov.append(self._to_numpy(image, shape))
-        if output_type == "u8":
-            images = self._to_u8(image, shape)
-            return ImagePipelineOutput(images=images, movie=mov) if return_dict else (images,)
-        images = self._to_numpy(image, shape)
-        if output_type == "pil":
-            images = self.numpy_to_pil(images)
-            if save_every_step:
-                mov = list(map(self.numpy_to_pil, mov))
-        if not return_dict:
-            return (images,)
-        return ImagePipelineOutput(images=images, movie=mov)
+        return self._finish(image, shape, mov, output_type, save_every_step, return_dict)
 
 
 class _MultistepPipeline(_PipelineBase):
-    """The sampling loop of the deterministic multistep ODE solvers (DPMSolverPipeline, UniPCPipeline): the call surface of
-    PNDMPipeline (`init`, `start_from`, `save_every_step`, output_type "pil" | "numpy" | "u8" | None), one UNet forward + one fused
-    step launch per step, no noise drawn after the start.  `clip_sample` is the post-step clamp of the sample, as in PNDMPipeline,
-    folded into the step launch (`scheduler.step(..., clip=)`).  A subclass names its scheduler class; a scheduler of another class
-    is converted from its config.  With start_from=k the scheduler's history is empty, so the first executed step is first order."""
+    """The sampling loop of the deterministic samplers (PNDMPipeline, DPMSolverPipeline, UniPCPipeline; _SigmaPipeline has its own
+    under the same call): the call surface of the reference's PNDM pipeline (`init`, `start_from`, `save_every_step`, output_type
+    "pil" | "numpy" | "u8" | None), one UNet forward + one fused step launch per step, no noise drawn after the start.  `clip_sample`
+    is the post-step clamp of the sample (pipeline_pndm.py:108-109), folded into the step launch (`scheduler.step(..., clip=)`).  A
+    subclass names its scheduler class and `default_steps`, the num_inference_steps of a call that gives none; a scheduler of
+    another class is converted from its config.  With start_from=k the scheduler's history is empty, so the first executed step is
+    first order."""
     scheduler_class = None
+    default_steps = None
 
     def __init__(self, unet, scheduler, clip_sample=False, clip_sample_range=1.0):
         if not isinstance(scheduler, self.scheduler_class):
@@ -263,6 +216,14 @@ class _MultistepPipeline(_PipelineBase):
         super().__init__(unet, scheduler)
         self.clip_sample = clip_sample
         self.clip_sample_range = clip_sample_range
+
+    @_static_weights
+    @torch.no_grad()
+    def __call__(self, batch_size=1, num_inference_steps=None, start_from=0, generator=None, output_type="pil", init=None,
+                 save_every_step=False, return_dict=True, **kwargs):
+        if num_inference_steps is None:
+            num_inference_steps = self.default_steps
+        return self._sample(batch_size, num_inference_steps, start_from, generator, output_type, init, save_every_step, return_dict)
 
     def _sample(self, batch_size, num_inference_steps, start_from, generator, output_type, init, save_every_step, return_dict):
         image, shape = self._start(batch_size, generator, init)
@@ -276,17 +237,25 @@ class _MultistepPipeline(_PipelineBase):
             image = self.scheduler.step(eps, int(t), image.permute(0, 3, 1, 2), clip=clip).prev_sample.permute(0, 2, 3, 1)
             if save_every_step:
                 mov.append(self._to_numpy(image, shape))
-        if output_type == "u8":
-            images = self._to_u8(image, shape)
-            return ImagePipelineOutput(images=images, movie=mov) if return_dict else (images,)
-        images = self._to_numpy(image, shape)
-        if output_type == "pil":
-            images = self.numpy_to_pil(images)
-            if save_every_step:
-                mov = list(map(self.numpy_to_pil, mov))
-        if not return_dict:
-            return (images,)
-        return ImagePipelineOutput(images=images, movie=mov)
+        return self._finish(image, shape, mov, output_type, save_every_step, return_dict)
+
+
+class PNDMPipeline(_MultistepPipeline):
+    """pipelines/pndm/pipeline_pndm.py:39-122 (the reference's modified copy: `clip_sample` / `clip_sample_range`, `init`,
+    `start_from`, `save_every_step`): _MultistepPipeline's loop.  Whatever scheduler it is given, a PNDMScheduler included, is
+    rebuilt as a PNDMScheduler from its config (:46) -- which is how every `--sched` other than DDPM / DDIM samples in the
+    reference."""
+    scheduler_class = PNDMScheduler
+    default_steps = 50
+
+    def __init__(self, unet, scheduler, clip_sample=False, clip_sample_range=1.0):
+        super().__init__(unet, PNDMScheduler.from_config(scheduler.config), clip_sample, clip_sample_range)
+
+    def encode(self, image, *args, **kwargs):
+        return image
+
+    def decode(self, image, *args, **kwargs):
+        return image
 
 
 class DPMSolverPipeline(_MultistepPipeline):
@@ -295,12 +264,7 @@ class DPMSolverPipeline(_MultistepPipeline):
     num_inference_steps=20 is this project's default.  A scheduler that is not a DPMSolverMultistepScheduler is converted from its
     config."""
     scheduler_class = DPMSolverMultistepScheduler
-
-    @_static_weights
-    @torch.no_grad()
-    def __call__(self, batch_size=1, num_inference_steps=20, start_from=0, generator=None, output_type="pil", init=None,
-                 save_every_step=False, return_dict=True, **kwargs):
-        return self._sample(batch_size, num_inference_steps, start_from, generator, output_type, init, save_every_step, return_dict)
+    default_steps = 20
 
 
 class UniPCPipeline(_MultistepPipeline):
@@ -309,12 +273,7 @@ class UniPCPipeline(_MultistepPipeline):
     the regime UniPC is built for.  A scheduler that is not a UniPCMultistepScheduler is converted from its config.  With
     start_from=k there is no last sample, so the first executed step has no corrector and is first order."""
     scheduler_class = UniPCMultistepScheduler
-
-    @_static_weights
-    @torch.no_grad()
-    def __call__(self, batch_size=1, num_inference_steps=10, start_from=0, generator=None, output_type="pil", init=None,
-                 save_every_step=False, return_dict=True, **kwargs):
-        return self._sample(batch_size, num_inference_steps, start_from, generator, output_type, init, save_every_step, return_dict)
+    default_steps = 10
 
 
 class _SigmaPipeline(_MultistepPipeline):
@@ -356,17 +315,7 @@ class _SigmaPipeline(_MultistepPipeline):
                 mov.append(self._to_numpy(scaled, shape))
         # the last divisor is sqrt(0 + 1) = 1: the scaled buffer is the final sample (and carries the clamp when clip_sample is set)
         image = scaled
-        if output_type == "u8":
-            images = self._to_u8(image, shape)
-            return ImagePipelineOutput(images=images, movie=mov) if return_dict else (images,)
-        images = self._to_numpy(image, shape)
-        if output_type == "pil":
-            images = self.numpy_to_pil(images)
-            if save_every_step:
-                mov = list(map(self.numpy_to_pil, mov))
-        if not return_dict:
-            return (images,)
-        return ImagePipelineOutput(images=images, movie=mov)
+        return self._finish(image, shape, mov, output_type, save_every_step, return_dict)
 
 
 class HeunPipeline(_SigmaPipeline):
@@ -375,23 +324,19 @@ class HeunPipeline(_SigmaPipeline):
     the last.  start_from counts positions of `scheduler.timesteps` (evaluations); an odd one is the averaging stage of a
     transition whose first stage was not run, and is refused."""
     scheduler_class = HeunDiscreteScheduler
+    default_steps = 10
 
     def _check_start(self, start_from):
         if start_from % 2:
             raise ValueError(f"HeunPipeline: start_from={start_from} is the second entry of a timestep pair (the averaging stage of a "
                              "transition whose first stage would be missing); start at an even position")
 
-    @_static_weights
-    @torch.no_grad()
-    def __call__(self, batch_size=1, num_inference_steps=10, start_from=0, generator=None, output_type="pil", init=None,
-                 save_every_step=False, return_dict=True, **kwargs):
-        return self._sample(batch_size, num_inference_steps, start_from, generator, output_type, init, save_every_step, return_dict)
-
 
 class LMSPipeline(_SigmaPipeline):
     """Sampling with LMSDiscreteScheduler at `order` (1..4; 1 is Euler): _SigmaPipeline's loop.  The reference has no pipeline for
     this scheduler either; num_inference_steps=20 is this project's default."""
     scheduler_class = LMSDiscreteScheduler
+    default_steps = 20
 
     def __init__(self, unet, scheduler, clip_sample=False, clip_sample_range=1.0, order=4):
         super().__init__(unet, scheduler, clip_sample=clip_sample, clip_sample_range=clip_sample_range)
@@ -401,12 +346,6 @@ class LMSPipeline(_SigmaPipeline):
 
     def _step_kwargs(self):
         return {"order": self.order}
-
-    @_static_weights
-    @torch.no_grad()
-    def __call__(self, batch_size=1, num_inference_steps=20, start_from=0, generator=None, output_type="pil", init=None,
-                 save_every_step=False, return_dict=True, **kwargs):
-        return self._sample(batch_size, num_inference_steps, start_from, generator, output_type, init, save_every_step, return_dict)
 
 
 def with_default_steps(pipeline, num_inference_steps):
@@ -507,14 +446,4 @@ class RePaintPipeline(_PipelineBase):
             t_last = t
             if save_every_step:
                 mov.append(self._to_numpy(x, shape))
-        if output_type == "u8":
-            images = self._to_u8(x, shape)
-            return ImagePipelineOutput(images=images, movie=mov) if return_dict else (images,)
-        images = self._to_numpy(x, shape)
-        if output_type == "pil":
-            images = self.numpy_to_pil(images)
-            if save_every_step:
-                mov = list(map(self.numpy_to_pil, mov))
-        if not return_dict:
-            return (images,)
-        return ImagePipelineOutput(images=images, movie=mov)
+        return self._finish(x, shape, mov, output_type, save_every_step, return_dict)

@@ -1,8 +1,18 @@
-"""DDPMScheduler / DDIMScheduler -- drop-in for the two diffusers schedulers BadDiffusion uses
-(/root/reference/diffusers/src/diffusers/schedulers/scheduling_ddpm.py:76-481,
- scheduling_ddim.py:79-429), with `step` / `add_noise` running as HIP kernels.
+"""The schedulers of the native path, drop-ins for diffusers' classes of the same names with `step` / `add_noise` running as HIP kernels
+(line numbers refer to diffusers/src/diffusers/schedulers/scheduling_*.py of the reference tree):
 
-Kept surface: `.betas .alphas .alphas_cumprod .timesteps .config.{num_train_timesteps,
+  DDPMScheduler, DDIMScheduler            the two BadDiffusion itself steps (scheduling_ddpm.py:76-481, scheduling_ddim.py:79-429)
+  PNDMScheduler                           every other `--sched` ends up here through PNDMPipeline (bd_lincomb)
+  RePaintScheduler                        inpainting (bd_repaint_step / bd_repaint_undo)
+  DPMSolverMultistepScheduler,            the multistep solvers in lambda, on _LambdaMultistep (bd_dpm_step, bd_unipc_step)
+  UniPCMultistepScheduler
+  HeunDiscreteScheduler,                  the sigma-space samplers, on _SigmaScheduler (bd_sigma_step, bd_scale_input)
+  LMSDiscreteScheduler
+
+_Base holds what they share: the beta tables and their device copies, `from_config` over `_KEYS`, the layout helpers `_align` /
+`_fits`, and the opening (`_begin_step`) and closing (`_output`) of a `step`.
+
+Kept surface of DDPM / DDIM: `.betas .alphas .alphas_cumprod .timesteps .config.{num_train_timesteps,
 clip_sample (assignable), variance_type, ...} .init_noise_sigma .set_timesteps() .step(...).prev_sample
 .add_noise() .previous_timestep() ._get_variance() __len__`.
 Tables are built on the host exactly as the reference does (fp32 linspace + fp32 cumprod) and mirrored
@@ -10,11 +20,8 @@ once to the device; `step` reads its coefficients from that device table (no per
 no host<->device sync; scheduling_ddpm.py:350-365 does ~7 host scalar extractions per step).
 Only what BadDiffusion exercises is supported: epsilon prediction, linear betas, fixed_small /
 fixed_large variance; anything else raises like the reference does for unknown options.
-Also here: PNDMScheduler (scheduling_pndm.py), RePaintScheduler (scheduling_repaint.py, the inpainting scheduler),
-DPMSolverMultistepScheduler (scheduling_dpmsolver_multistep.py, the high-order ODE sampler behind --native_sched) and
-UniPCMultistepScheduler (scheduling_unipc_multistep.py, predictor + corrector, behind the UNIPC_O*-SCHED names), and the two
-sigma-space samplers HeunDiscreteScheduler / LMSDiscreteScheduler (scheduling_heun_discrete.py, scheduling_lms_discrete.py; fractional
-timesteps, scaled model input and initial noise; behind HEUN_O2-SCHED and LMSD_O*-SCHED).
+DPM-Solver(++) is behind --native_sched, UniPC behind the UNIPC_O*-SCHED names, Heun and LMS (fractional timesteps, scaled model
+input and initial noise) behind HEUN_O2-SCHED and LMSD_O*-SCHED.
 """
 import numpy as np
 import torch
@@ -61,6 +68,12 @@ def randn_tensor(shape, generator=None, device=None, dtype=torch.float32):
 
 class _Base:
     order = 1
+
+    @classmethod
+    def from_config(cls, config):
+        """a scheduler of this class from any scheduler's config (pipeline_ddim.py:39-42, pipeline_pndm.py:46), for the classes that
+        name the constructor arguments a config carries over in `_KEYS`"""
+        return cls(**{k: config[k] for k in cls._KEYS if k in config})
 
     def _make_tables(self, num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas):
         if trained_betas is not None:
@@ -133,6 +146,38 @@ class _Base:
                 outs.append(t.contiguous())
         restore = (lambda y: y.permute(0, 3, 1, 2)) if tag == "nhwc" else (lambda y: y)
         return outs, restore
+
+    @staticmethod
+    def _fits(h, x):
+        """a stored buffer can stand beside the sample x in one launch: same shape, layout and device"""
+        return h is not None and h.shape == x.shape and h.stride() == x.stride() and h.device == x.device
+
+    def _begin_step(self, model_output, sample):
+        """What `step` of the multistep and sigma-space schedulers opens with: the four refusals, then (model_output, sample) in one
+        dense layout and the function that takes a result back to the caller's."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        if self.config.prediction_type != "epsilon":
+            raise ValueError(f"prediction_type given as {self.config.prediction_type} must be `epsilon` on the HIP path")
+        if not (model_output.is_cuda and sample.is_cuda):
+            raise RuntimeError(f"{type(self).__name__}.step runs on the GPU only")
+        (eps, x), restore = self._align(model_output, sample)
+        if eps.dtype != torch.float32 or x.dtype != torch.float32:
+            raise TypeError(f"{type(self).__name__}.step: float32 tensors only")
+        return eps, x, restore
+
+    @staticmethod
+    def _output(prev, restore, return_dict, pred_original_sample=None, **more):
+        """What `step` closes with: (prev_sample,) or a SchedulerOutput, every tensor back in the caller's layout; `more` become
+        further attributes of the output (a None stays None)."""
+        back = lambda v: None if v is None else restore(v)       # noqa: E731
+        prev = restore(prev)
+        if not return_dict:
+            return (prev,)
+        out = SchedulerOutput(prev_sample=prev, pred_original_sample=back(pred_original_sample))
+        for name, v in more.items():
+            setattr(out, name, back(v))
+        return out
 
 
 class DDPMScheduler(_Base):
@@ -214,13 +259,13 @@ class DDPMScheduler(_Base):
         prev, x0 = ops.ddpm_step(mo, sm, nz, ac, t, prev_t, self.variance_type, self.config.clip_sample,
                                  self.config.clip_sample_range, self.config.clip_defense, self.config.clip_defense_range,
                                  want_x0=True)
-        prev, x0 = restore(prev), restore(x0)
-        if not return_dict:
-            return (prev,)
-        return SchedulerOutput(prev_sample=prev, pred_original_sample=x0)
+        return self._output(prev, restore, return_dict, pred_original_sample=x0)
 
 
 class DDIMScheduler(_Base):
+    _KEYS = ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "trained_betas", "clip_sample", "set_alpha_to_one",
+             "steps_offset", "prediction_type", "thresholding", "dynamic_thresholding_ratio", "clip_sample_range", "sample_max_value")
+
     def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
                  trained_betas=None, clip_sample=True, set_alpha_to_one=True, steps_offset=0, prediction_type="epsilon",
                  thresholding=False, dynamic_thresholding_ratio=0.995, clip_sample_range=1.0, sample_max_value=1.0, **unused):
@@ -234,14 +279,6 @@ class DDIMScheduler(_Base):
         self.final_alpha_cumprod = torch.tensor(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
         self.num_inference_steps = None
         self.timesteps = torch.from_numpy(np.arange(0, num_train_timesteps)[::-1].copy().astype(np.int64))
-
-    @classmethod
-    def from_config(cls, config):
-        """pipeline_ddim.py:39-42 re-creates a DDIM scheduler from any scheduler's config."""
-        keys = ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "trained_betas", "clip_sample",
-                "set_alpha_to_one", "steps_offset", "prediction_type", "thresholding", "dynamic_thresholding_ratio",
-                "clip_sample_range", "sample_max_value")
-        return cls(**{k: config[k] for k in keys if k in config})
 
     def set_timesteps(self, num_inference_steps, device=None):
         # scheduling_ddim.py:237-259
@@ -285,10 +322,7 @@ class DDIMScheduler(_Base):
         prev, x0 = ops.ddim_step(mo, sm, ac, t, prev_t, eta=float(eta), noise=nz, clip_sample=self.config.clip_sample,
                                  clip_sample_range=self.config.clip_sample_range,
                                  final_alpha_cumprod=float(self.final_alpha_cumprod), want_x0=True)
-        prev, x0 = restore(prev), restore(x0)
-        if not return_dict:
-            return (prev,)
-        return SchedulerOutput(prev_sample=prev, pred_original_sample=x0)
+        return self._output(prev, restore, return_dict, pred_original_sample=x0)
 
 
 class PNDMScheduler(_Base):
@@ -315,10 +349,6 @@ class PNDMScheduler(_Base):
 
     _KEYS = ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "trained_betas", "skip_prk_steps",
              "set_alpha_to_one", "prediction_type", "steps_offset")
-
-    @classmethod
-    def from_config(cls, config):
-        return cls(**{k: config[k] for k in cls._KEYS if k in config})
 
     def _reset(self):
         self.counter, self.ets, self.cur_sample, self._acc = 0, [], None, None
@@ -401,10 +431,7 @@ class PNDMScheduler(_Base):
             sc, ec = self._coeffs(t, prev_t)
             prev = ops.lincomb([x] + terms, [sc] + [ec * wi for wi in w], clip=clip)
         self.counter += 1
-        prev = restore(prev)
-        if not return_dict:
-            return (prev,)
-        return SchedulerOutput(prev_sample=prev)
+        return self._output(prev, restore, return_dict)
 
 
 class RePaintSchedulerOutput(SchedulerOutput):
@@ -433,10 +460,6 @@ class RePaintScheduler(_Base):
         self.num_inference_steps = None
         self.timesteps = torch.from_numpy(np.arange(0, num_train_timesteps)[::-1].copy())
         self.eta = eta
-
-    @classmethod
-    def from_config(cls, config):
-        return cls(**{k: config[k] for k in cls._KEYS if k in config})
 
     def set_timesteps(self, num_inference_steps, jump_length=10, jump_n_sample=10, device=None):
         # scheduling_repaint.py:167-195
@@ -504,7 +527,58 @@ class RePaintScheduler(_Base):
         raise NotImplementedError("Use `DDPMScheduler.add_noise()` to train for sampling with RePaint.")
 
 
-class DPMSolverMultistepScheduler(_Base):
+class _LambdaMultistep(_Base):
+    """What the two multistep solvers in lambda = log(alpha / sigma) share (DPM-Solver(++), UniPC; a DEIS scheduler would start here):
+    the alpha_t / sigma_t / lambda_t tables, the timesteps and the position of one by value, the per-chain cache of the host scalars
+    of a step, the thresholding rule and the warm-up counter.  A subclass has `_plan_scalars`, the key of its cache entries, its ring
+    of device buffers (`_reset`) and the body of `step`."""
+
+    def _refuse_thresholding(self, thresholding, sample_max_value):
+        if thresholding and sample_max_value != 1.0:
+            raise NotImplementedError(f"{type(self).__name__}: thresholding is on the HIP path for sample_max_value == 1.0 only "
+                                      f"(where it is clamp(x0, -1, 1)), got {sample_max_value}")
+
+    def _make_lambda_tables(self, num_train_timesteps):
+        self.alpha_t = torch.sqrt(self.alphas_cumprod)          # scheduling_dpmsolver_multistep.py:162-164, scheduling_unipc_multistep.py:161-164
+        self.sigma_t = torch.sqrt(1 - self.alphas_cumprod)
+        self.lambda_t = torch.log(self.alpha_t) - torch.log(self.sigma_t)
+        self.num_inference_steps = None
+        self.timesteps = torch.from_numpy(np.linspace(0, num_train_timesteps - 1, num_train_timesteps, dtype=np.float32)[::-1].copy())
+        self._ts, self._index, self._plans = [], {}, {}
+        self._reset()
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        # scheduling_dpmsolver_multistep.py:200-226, scheduling_unipc_multistep.py:188-220
+        timesteps = np.linspace(0, self.config.num_train_timesteps - 1, num_inference_steps + 1).round()[::-1][:-1].copy().astype(np.int64)
+        _, unique_indices = np.unique(timesteps, return_index=True)     # num_inference_steps == num_train_timesteps has duplicates
+        timesteps = timesteps[np.sort(unique_indices)]
+        self.timesteps = torch.from_numpy(timesteps).to(device)
+        self.num_inference_steps = len(timesteps)
+        ts = [int(t) for t in timesteps]
+        if ts != self._ts:
+            self._ts, self._index, self._plans = ts, {t: i for i, t in enumerate(ts)}, {}
+        self._reset()
+
+    def _step_index(self, timestep):
+        # by value; a timestep that is not in the table counts as the last one
+        return self._index.get(int(timestep), len(self._index) - 1)
+
+    def _cached_plan(self, key, *args):
+        """_plan_scalars(*args), computed once per set of timesteps and `key`: the scalars depend on the tables, the timesteps, the
+        position and the warm-up state alone, so a second chain of the same length (sampling runs chunk after chunk) spends no host
+        time on ~40 scalar tensor operations per step"""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        if key not in self._plans:
+            self._plans[key] = self._plan_scalars(*args)
+        return self._plans[key]
+
+    def _advance(self):
+        if self.lower_order_nums < self.config.solver_order:
+            self.lower_order_nums += 1
+
+
+class DPMSolverMultistepScheduler(_LambdaMultistep):
     """DPM-Solver / DPM-Solver++ multistep scheduler (scheduling_dpmsolver_multistep.py:127-573) on the GPU, epsilon prediction: a
     deterministic ODE sampler of order 1-3 that is normally run at 10-20 UNet evaluations.  Every step is ONE `bd_dpm_step` launch: the
     conversion of the model output (x0-prediction, optionally clamped, for dpmsolver++; eps for dpmsolver), the update and the
@@ -534,61 +608,26 @@ class DPMSolverMultistepScheduler(_Base):
             raise ValueError(f"solver_order must be 1, 2 or 3, got {solver_order}")
         if use_karras_sigmas:
             raise NotImplementedError("DPMSolverMultistepScheduler: use_karras_sigmas is not on the HIP path")
-        if thresholding and sample_max_value != 1.0:
-            raise NotImplementedError("DPMSolverMultistepScheduler: thresholding is on the HIP path for sample_max_value == 1.0 only "
-                                      f"(where it is clamp(x0, -1, 1)), got {sample_max_value}")
+        self._refuse_thresholding(thresholding, sample_max_value)
         self.config = FrozenConfig(
             num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end, beta_schedule=beta_schedule,
             trained_betas=trained_betas, solver_order=solver_order, prediction_type=prediction_type, thresholding=thresholding,
             dynamic_thresholding_ratio=dynamic_thresholding_ratio, sample_max_value=sample_max_value, algorithm_type=algorithm_type,
             solver_type=solver_type, lower_order_final=lower_order_final, use_karras_sigmas=False)
         self._make_tables(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas)
-        self.alpha_t = torch.sqrt(self.alphas_cumprod)                              # :162-164
-        self.sigma_t = torch.sqrt(1 - self.alphas_cumprod)
-        self.lambda_t = torch.log(self.alpha_t) - torch.log(self.sigma_t)
-        self.num_inference_steps = None
-        self.timesteps = torch.from_numpy(np.linspace(0, num_train_timesteps - 1, num_train_timesteps, dtype=np.float32)[::-1].copy())
-        self._ts, self._index, self._plans = [], {}, {}
-        self._reset()
-
-    @classmethod
-    def from_config(cls, config):
-        return cls(**{k: config[k] for k in cls._KEYS if k in config})
+        self._make_lambda_tables(num_train_timesteps)
 
     def _reset(self):
         self.lower_order_nums = 0
         self._ring = [None] * self.config.solver_order      # converted model outputs, oldest first; [-1] is the previous step's
 
-    def set_timesteps(self, num_inference_steps, device=None):
-        # scheduling_dpmsolver_multistep.py:200-226
-        timesteps = np.linspace(0, self.config.num_train_timesteps - 1, num_inference_steps + 1).round()[::-1][:-1].copy().astype(np.int64)
-        _, unique_indices = np.unique(timesteps, return_index=True)     # num_inference_steps == num_train_timesteps has duplicates
-        timesteps = timesteps[np.sort(unique_indices)]
-        self.timesteps = torch.from_numpy(timesteps).to(device)
-        self.num_inference_steps = len(timesteps)
-        ts = [int(t) for t in timesteps]
-        if ts != self._ts:
-            self._ts, self._index, self._plans = ts, {t: i for i, t in enumerate(ts)}, {}
-        self._reset()
-
-    def _step_index(self, timestep):
-        # :534-540: by value; a timestep that is not in the table counts as the last one
-        return self._index.get(int(timestep), len(self._index) - 1)
-
     def _plan(self, step_index):
         """Host part of the step at `step_index` given the current `lower_order_nums`: (order_used, alpha_s, sigma_s, cx, c0, c1, c2)
         with  m0 = (sample - sigma_s eps) / alpha_s  (dpmsolver++; m0 = eps for dpmsolver)  and
         prev = cx sample + c0 m0 + c1 m1 + c2 m2  (:383-505, D1 and D2 expanded).  fp32 torch scalars throughout, no device access."""
-        if self.num_inference_steps is None:
-            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
         cfg = self.config
-        # the scalars depend on the tables, the timesteps, the position and the warm-up state alone: computed once per set of timesteps,
-        # so that a second chain of the same length (sampling runs chunk after chunk) spends no host time on ~40 scalar tensor
-        # operations per step
         key = (step_index, self.lower_order_nums, cfg.algorithm_type, cfg.solver_type, cfg.solver_order, cfg.lower_order_final)
-        if key not in self._plans:
-            self._plans[key] = self._plan_scalars(step_index)
-        return self._plans[key]
+        return self._cached_plan(key, step_index)
 
     def _plan_scalars(self, step_index):
         ts, n, cfg = self._ts, len(self._ts), self.config
@@ -640,47 +679,30 @@ class DPMSolverMultistepScheduler(_Base):
             c0, c1, c2 = a0 + u / r0, v / r1 - u / r0, -(v / r1)
         return order, float(alpha_s0), float(sigma_s0), float(cx), float(c0), float(c1), float(c2)
 
-    def _advance(self):
-        if self.lower_order_nums < self.config.solver_order:
-            self.lower_order_nums += 1
-
     def step(self, model_output, timestep, sample, return_dict=True, clip=None):
         # scheduling_dpmsolver_multistep.py:529-573
-        if self.num_inference_steps is None:
-            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
-        if self.config.prediction_type != "epsilon":
-            raise ValueError(f"prediction_type given as {self.config.prediction_type} must be `epsilon` on the HIP path")
-        if not (model_output.is_cuda and sample.is_cuda):
-            raise RuntimeError("DPMSolverMultistepScheduler.step runs on the GPU only")
+        eps, x, restore = self._begin_step(model_output, sample)
         order, alpha_s, sigma_s, cx, c0, c1, c2 = self._plan(self._step_index(timestep))
-        (eps, x), restore = self._align(model_output, sample)
-        if eps.dtype != torch.float32 or x.dtype != torch.float32:
-            raise TypeError("DPMSolverMultistepScheduler.step: float32 tensors only")
         ring = self._ring
         for h in ring[len(ring) - order + 1:] if order > 1 else ():
-            if h is None or h.shape != x.shape or h.stride() != x.stride() or h.device != x.device:
+            if not self._fits(h, x):
                 raise ValueError("DPMSolverMultistepScheduler.step: the stored model outputs do not have this sample's shape and layout "
                                  "(one chain per set_timesteps)")
         pp = self.config.algorithm_type == "dpmsolver++"
         # the oldest buffer takes this step's converted output; a first order solver never reads it back, so it is not written
         oldest = None
         if len(ring) > 1:
-            oldest = ring[0]
-            if oldest is None or oldest.shape != x.shape or oldest.stride() != x.stride() or oldest.device != x.device:
-                oldest = torch.empty_like(x)
+            oldest = ring[0] if self._fits(ring[0], x) else torch.empty_like(x)
         prev = ops.dpm_step(eps, x, cx, c0, m1=ring[-1] if order >= 2 else None, c1=c1, m2=ring[-2] if order >= 3 else None, c2=c2,
                             convert=(alpha_s, sigma_s) if pp else None,
                             x0_clip=1.0 if pp and self.config.thresholding else None, clip=clip, m0_out=oldest)
         if oldest is not None:
             self._ring = ring[1:] + [oldest]
         self._advance()
-        prev = restore(prev)
-        if not return_dict:
-            return (prev,)
-        return SchedulerOutput(prev_sample=prev)
+        return self._output(prev, restore, return_dict)
 
 
-class UniPCMultistepScheduler(_Base):
+class UniPCMultistepScheduler(_LambdaMultistep):
     """UniPC multistep scheduler (scheduling_unipc_multistep.py:126-601, B(h) version) on the GPU, epsilon prediction: a predictor
     (UniP) of order 1-3 plus a corrector (UniC) that reuses the model output of the current step, so every step gains one order of
     accuracy at no extra UNet evaluation.  Every step is ONE `bd_unipc_step` launch: conversion of the model output, the corrector
@@ -711,28 +733,20 @@ class UniPCMultistepScheduler(_Base):
                                       "three history tensors: orders 1-3)")
         if solver_p is not None:
             raise NotImplementedError("UniPCMultistepScheduler: solver_p is not on the HIP path (the predictor is UniP)")
-        if thresholding and sample_max_value != 1.0:
-            raise NotImplementedError("UniPCMultistepScheduler: thresholding is on the HIP path for sample_max_value == 1.0 only "
-                                      f"(where it is clamp(x0, -1, 1)), got {sample_max_value}")
+        self._refuse_thresholding(thresholding, sample_max_value)
         self.config = FrozenConfig(
             num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end, beta_schedule=beta_schedule,
             trained_betas=trained_betas, solver_order=solver_order, prediction_type=prediction_type, thresholding=thresholding,
             dynamic_thresholding_ratio=dynamic_thresholding_ratio, sample_max_value=sample_max_value, predict_x0=predict_x0,
             solver_type=solver_type, lower_order_final=lower_order_final, disable_corrector=list(disable_corrector))
         self._make_tables(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas)
-        self.alpha_t = torch.sqrt(self.alphas_cumprod)                              # :161-164
-        self.sigma_t = torch.sqrt(1 - self.alphas_cumprod)
-        self.lambda_t = torch.log(self.alpha_t) - torch.log(self.sigma_t)
-        self.num_inference_steps = None
-        self.timesteps = torch.from_numpy(np.linspace(0, num_train_timesteps - 1, num_train_timesteps, dtype=np.float32)[::-1].copy())
-        self._ts, self._index, self._plans = [], {}, {}
-        self._reset()
+        self._make_lambda_tables(num_train_timesteps)
 
     @classmethod
     def from_config(cls, config):
         if "solver_p" in config and config["solver_p"] is not None:
             raise NotImplementedError("UniPCMultistepScheduler: solver_p is not on the HIP path (the predictor is UniP)")
-        return cls(**{k: config[k] for k in cls._KEYS if k in config})
+        return super().from_config(config)
 
     @property
     def predict_x0(self):
@@ -749,39 +763,19 @@ class UniPCMultistepScheduler(_Base):
         self._ring_ts = [None] * self.config.solver_order     # and the timesteps they were taken at
         self.last_sample, self._last_owned = None, False
 
-    def set_timesteps(self, num_inference_steps, device=None):
-        # scheduling_unipc_multistep.py:188-220
-        timesteps = np.linspace(0, self.config.num_train_timesteps - 1, num_inference_steps + 1).round()[::-1][:-1].copy().astype(np.int64)
-        _, unique_indices = np.unique(timesteps, return_index=True)     # num_inference_steps == num_train_timesteps has duplicates
-        timesteps = timesteps[np.sort(unique_indices)]
-        self.timesteps = torch.from_numpy(timesteps).to(device)
-        self.num_inference_steps = len(timesteps)
-        ts = [int(t) for t in timesteps]
-        if ts != self._ts:
-            self._ts, self._index, self._plans = ts, {t: i for i, t in enumerate(ts)}, {}
-        self._reset()
-
-    def _step_index(self, timestep):
-        # :549-553: by value; a timestep that is not in the table counts as the last one
-        return self._index.get(int(timestep), len(self._index) - 1)
-
     def _plan(self, step_index, has_last=None):
         """Host part of the step at `step_index` given the current state (`lower_order_nums`, `this_order`, the timesteps of the
         ring): (order, corrector_order, alpha_s, sigma_s, (kl, k0, k1, k2, k3), (px, p0, p1, p2)) for bd_unipc_step's formula
         (include/bd_hip.h).  corrector_order is 0 when the step has no corrector: step 0, a step after one listed in
         `disable_corrector`, or no `last_sample` (has_last, by default whether one is stored).  fp32 torch scalars throughout, no
         device access; kept per set of timesteps, as DPMSolverMultistepScheduler._plan."""
-        if self.num_inference_steps is None:
-            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
         cfg = self.config
         if has_last is None:
             has_last = self.last_sample is not None
         corrector = step_index > 0 and step_index - 1 not in cfg.disable_corrector and bool(has_last)      # :555-557
         key = (step_index, self.lower_order_nums, self.this_order if corrector else 0, tuple(self._ring_ts), cfg.predict_x0,
                cfg.solver_type, cfg.solver_order, cfg.lower_order_final)
-        if key not in self._plans:
-            self._plans[key] = self._plan_scalars(step_index, corrector)
-        return self._plans[key]
+        return self._cached_plan(key, step_index, corrector)
 
     def _bh(self, s0, t, older, order):
         """what both updates share (:340-383 = :444-487) for the transition s0 -> t of order `order` over the timesteps `older` of the
@@ -848,31 +842,21 @@ class UniPCMultistepScheduler(_Base):
         """the bookkeeping of one step: the ring's timesteps shift, the predictor's order is remembered for the next corrector"""
         self._ring_ts = self._ring_ts[1:] + [int(self._ts[step_index])]
         self.this_order = order
-        if self.lower_order_nums < self.config.solver_order:
-            self.lower_order_nums += 1
+        super()._advance()
 
     def step(self, model_output, timestep, sample, return_dict=True, clip=None):
         # scheduling_unipc_multistep.py:519-601
-        if self.num_inference_steps is None:
-            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
-        if self.config.prediction_type != "epsilon":
-            raise ValueError(f"prediction_type given as {self.config.prediction_type} must be `epsilon` on the HIP path")
-        if not (model_output.is_cuda and sample.is_cuda):
-            raise RuntimeError("UniPCMultistepScheduler.step runs on the GPU only")
+        eps, x, restore = self._begin_step(model_output, sample)
         step_index = self._step_index(timestep)
         order, corr_order, alpha_s, sigma_s, k, p = self._plan(step_index)
-        (eps, x), restore = self._align(model_output, sample)
-        if eps.dtype != torch.float32 or x.dtype != torch.float32:
-            raise TypeError("UniPCMultistepScheduler.step: float32 tensors only")
         ring = self._ring
-        fits = lambda h: h is not None and h.shape == x.shape and h.stride() == x.stride() and h.device == x.device      # noqa: E731
         n_hist = max(corr_order, order - 1)                  # the corrector reads h1..h_p, the predictor h1..h_{p-1}
         hist = [ring[-1 - j] if j < n_hist else None for j in range(3)]
         for h in hist[:n_hist] + ([self.last_sample] if corr_order else []):
-            if not fits(h):
+            if not self._fits(h, x):
                 raise ValueError("UniPCMultistepScheduler.step: the stored model outputs / last sample do not have this sample's "
                                  "shape and layout (one chain per set_timesteps)")
-        oldest = ring[0] if fits(ring[0]) else torch.empty_like(x)       # takes this step's converted output
+        oldest = ring[0] if self._fits(ring[0], x) else torch.empty_like(x)       # takes this step's converted output
         corrected = None
         if corr_order:
             corrected = self.last_sample if self._last_owned else torch.empty_like(x)
@@ -885,10 +869,7 @@ class UniPCMultistepScheduler(_Base):
         # the sample the predictor started from: the corrected one, or the incoming one where no corrector ran
         self.last_sample, self._last_owned = (corrected, True) if corr_order else (x, False)
         self._advance(step_index, order)
-        prev = restore(prev)
-        if not return_dict:
-            return (prev,)
-        return SchedulerOutput(prev_sample=prev)
+        return self._output(prev, restore, return_dict)
 
 
 class _SigmaScheduler(_Base):
@@ -909,10 +890,6 @@ class _SigmaScheduler(_Base):
         self._make_tables(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas)
         self.num_inference_steps = None
         self._set_tables(num_train_timesteps)
-
-    @classmethod
-    def from_config(cls, config):
-        return cls(**{k: config[k] for k in cls._KEYS if k in config})
 
     def _interp(self, n):
         """(timesteps float64 [n] descending, sigmas fp32 [n + 1] with the trailing 0): scheduling_lms_discrete.py:203-206"""
@@ -940,20 +917,6 @@ class _SigmaScheduler(_Base):
             raise ValueError(f"{type(self).__name__}: timestep {float(timestep)!r} is not one of this schedule's")
         return pos
 
-    def _check(self, model_output, sample):
-        if self.config.prediction_type != "epsilon":
-            raise ValueError(f"prediction_type given as {self.config.prediction_type} must be `epsilon` on the HIP path")
-        if not (model_output.is_cuda and sample.is_cuda):
-            raise RuntimeError(f"{type(self).__name__}.step runs on the GPU only")
-        (eps, x), restore = self._align(model_output, sample)
-        if eps.dtype != torch.float32 or x.dtype != torch.float32:
-            raise TypeError(f"{type(self).__name__}.step: float32 tensors only")
-        return eps, x, restore
-
-    @staticmethod
-    def _fits(h, x):
-        return h is not None and h.shape == x.shape and h.stride() == x.stride() and h.device == x.device
-
     def scale_model_input(self, sample, timestep):
         """sample / sqrt(sigma^2 + 1) at `timestep` (bd_scale_input): bit-equal to the `.scaled_sample` of the step that produced
         `sample` (without clip; with it the step scales before it clamps)."""
@@ -962,15 +925,6 @@ class _SigmaScheduler(_Base):
         x, tag = self._flat(sample)
         out = ops.scale_input(x, 1.0, self._in_div[self._step_index(timestep)])
         return out.permute(0, 3, 1, 2) if tag == "nhwc" else out
-
-    @staticmethod
-    def _output(prev, scaled, restore, return_dict):
-        prev = restore(prev)
-        if not return_dict:
-            return (prev,)
-        out = SchedulerOutput(prev_sample=prev)
-        out.scaled_sample = None if scaled is None else restore(scaled)
-        return out
 
 
 class HeunDiscreteScheduler(_SigmaScheduler):
@@ -1017,7 +971,7 @@ class HeunDiscreteScheduler(_SigmaScheduler):
     def step(self, model_output, timestep, sample, return_dict=True, clip=None, scaled=False):
         # scheduling_heun_discrete.py:193-275
         k = self._step_index(timestep)
-        eps, x, restore = self._check(model_output, sample)
+        eps, x, restore = self._begin_step(model_output, sample)
         first = self.state_in_first_order
         if first != (k % 2 == 0):
             raise ValueError(f"HeunDiscreteScheduler.step: position {k} of the schedule is "
@@ -1039,7 +993,7 @@ class HeunDiscreteScheduler(_SigmaScheduler):
                                  "(one chain per set_timesteps)")
             prev = ops.sigma_step(eps, x, sigma_in, dt, in_div, base=base, average=True, h1=dbuf, scaled_out=sc, clip=clip)
             self._stage = None
-        return self._output(prev, sc, restore, return_dict)
+        return self._output(prev, restore, return_dict, scaled_sample=sc)
 
 
 class LMSDiscreteScheduler(_SigmaScheduler):
@@ -1106,7 +1060,7 @@ class LMSDiscreteScheduler(_SigmaScheduler):
     def step(self, model_output, timestep, sample, order=4, return_dict=True, clip=None, scaled=False):
         # scheduling_lms_discrete.py:217-285
         k = self._step_index(timestep)
-        eps, x, restore = self._check(model_output, sample)
+        eps, x, restore = self._begin_step(model_output, sample)
         sigma_in, coeffs, in_div = self._plan_scalars(k, order)
         ring = self._ring[-(order - 1):] if order > 1 else []
         for h in ring:
@@ -1124,7 +1078,7 @@ class LMSDiscreteScheduler(_SigmaScheduler):
         prev = ops.sigma_step(eps, x, sigma_in, c[0], in_div, h1=hist[0], c1=c[1], h2=hist[1], c2=c[2], h3=hist[2], c3=c[3],
                               d_out=dbuf, scaled_out=sc, clip=clip)
         self._ring = ring + [dbuf] if order > 1 else []
-        return self._output(prev, sc, restore, return_dict)
+        return self._output(prev, restore, return_dict, scaled_sample=sc)
 
 
 class SchedulerConfigCarrier(DDPMScheduler):

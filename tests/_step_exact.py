@@ -362,6 +362,62 @@ def lincomb_stmt(terms, coeffs, clip):
     return torch.from_numpy(r)
 
 
+# ---- the dense vec4 driver: one case per ported entry point, every optional operand present
+VEC4_OPS = ("lincomb", "dpm_step", "unipc_step", "sigma_step", "scale_input")
+VEC4_SECOND_TRIP = 4 * TPB * STEP_CAP + 5       # every thread of the capped grid takes a second trip, and a tail of one follows
+VEC4_N = (1, 3, 4, 7, VEC4_SECOND_TRIP)
+VEC4_DPM = dict(alpha_s=0.8, sigma_s=0.6, x0_range=1.5, cx=0.9, c0=0.35, c1=-0.5, c2=0.2, clip_range=2.0)
+VEC4_UNIPC = dict(alpha_s=0.8, sigma_s=0.6, x0_range=1.5, kl=0.9, k0=-0.25, k1=0.3, k2=-0.15, k3=0.1, px=0.85, p0=0.35, p1=-0.5, p2=0.2, clip_range=2.0)
+VEC4_SIGMA = dict(sigma_in=1.7, c0=-0.8, c1=0.4, c2=-0.2, c3=0.1, in_div=1.25, clip_range=2.0)
+VEC4_SCALE = (14.6, 1.9)                        # mul, div
+
+
+def vec4_inputs(n):
+    """six standard normal fp32 arrays of n elements (model_output, sample, and four more operands)"""
+    return tuple(torch.randn(n, generator=gen(900 + j)).numpy() for j in range(6))
+
+
+def dpm_stmt(k, e, x, m1, m2):
+    """bd_dpm_step (include/bd_hip.h) in the kernel's order, one fp32 rounding per operation, every option on: (m0, prev)"""
+    k = {n: f32(v) for n, v in k.items()}
+    m0 = clamp((x - k["sigma_s"] * e) / k["alpha_s"], k["x0_range"])
+    r = k["cx"] * x + k["c0"] * m0
+    r = r + k["c1"] * m1
+    r = r + k["c2"] * m2
+    return m0, clamp(r, k["clip_range"])
+
+
+def unipc_stmt(k, e, x, last, h1, h2, h3):
+    """bd_unipc_step in the kernel's order, corrector over three history terms and predictor over two: (m0, corrected, prev)"""
+    k = {n: f32(v) for n, v in k.items()}
+    m0 = clamp((x - k["sigma_s"] * e) / k["alpha_s"], k["x0_range"])
+    xc = k["kl"] * last + k["k0"] * m0
+    xc = xc + k["k1"] * h1
+    xc = xc + k["k2"] * h2
+    xc = xc + k["k3"] * h3
+    r = k["px"] * xc + k["p0"] * m0
+    r = r + k["p1"] * h1
+    r = r + k["p2"] * h2
+    return m0, xc, clamp(r, k["clip_range"])
+
+
+def sigma_stmt(k, e, x, base, h1, h2, h3):
+    """bd_sigma_step, the linear multistep form over three history terms from `base`, with the clip: (x0, d, prev, scaled)"""
+    k = {n: f32(v) for n, v in k.items()}
+    x0 = x - k["sigma_in"] * e
+    d = (x - x0) / k["sigma_in"]
+    acc = k["c0"] * d
+    acc = acc + k["c1"] * h1
+    acc = acc + k["c2"] * h2
+    acc = acc + k["c3"] * h3
+    sc = clamp((base + acc) / k["in_div"], k["clip_range"])
+    return x0, d, sc * k["in_div"], sc
+
+
+def scale_input_stmt(x, mul, div):
+    return (x * f32(mul)) / f32(div)
+
+
 # ================================================================================================ 3. clip + Adam
 ADAM_N = (1, 5, 1023, ADAM_SECOND_TRIP)
 ADAM_STEPS = (1, 2, 1000)

@@ -176,7 +176,8 @@ def test_from_config_of_a_unipc_style_config():
     import inspect
     from baddiffusion_amd.pipelines import PNDMPipeline
     sig, pndm = inspect.signature(DPMSolverPipeline.__call__), inspect.signature(PNDMPipeline.__call__)
-    assert list(sig.parameters) == list(pndm.parameters) and sig.parameters["num_inference_steps"].default == 20
+    assert list(sig.parameters) == list(pndm.parameters) and sig.parameters["num_inference_steps"].default is None
+    assert DPMSolverPipeline.default_steps == 20 and PNDMPipeline.default_steps == 50 and "__call__" not in vars(DPMSolverPipeline)
 
 
 def test_errors_are_loud():

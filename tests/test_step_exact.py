@@ -372,6 +372,66 @@ def test_ops_lincomb_refuses_mismatched_out(gpu):
         ops.lincomb([flat[:32]], [1.0], out=flat[4:36])
 
 
+# ================================================================================================ 2. the dense vec4 driver
+_VEC4 = {}
+
+
+def vec4_inputs(n):
+    """the inputs of size n, drawn once and shared by the five entry points"""
+    if n not in _VEC4:
+        _VEC4.clear()                    # (the parameters are ordered by n: one size is alive at a time)
+        _VEC4[n] = X.vec4_inputs(n)
+    return _VEC4[n]
+
+
+@pytest.mark.parametrize("op", X.VEC4_OPS)
+@pytest.mark.parametrize("n", X.VEC4_N)
+def test_vec4_driver(gpu, lib, n, op):
+    """the five entry points of the shared float4 driver with every optional operand present, tail only (1, 3), body only (4), body + tail
+    (7) and a second trip of every thread of the capped grid + tail: equal bits with the fp32 statements, the step kernels writing the
+    new sample over the old one; margins of every buffer intact, the other inputs unchanged"""
+    L, l = lib, lib.load()
+    e, x, a, b, c, d = vec4_inputs(n)
+    ins = [flat_in(v, gpu) for v in (e, x, a, b, c, d)]
+    (eb, ep), (xb, xp), (ab, ap), (bb, bp), (cb, cp), (db, dp) = ins
+    outs = {}
+
+    def out(name):
+        outs[name] = flat_out(n, gpu)
+        return outs[name][1]
+
+    if op == "lincomb":
+        coeffs = X.LINCOMB_COEFFS
+        L.check(lincomb_call(L, l, [p for _, p in ins], coeffs, n, X.LINCOMB_CLIP, out("out")), "bd_lincomb")
+        want = {"out": X.lincomb_stmt([t32(v) for v in (e, x, a, b, c, d)], coeffs, X.LINCOMB_CLIP)}
+    elif op == "dpm_step":
+        desc = L.DpmStepDesc(n=n, model_output=ep, sample=xp, m1=ap, m2=bp, m0_out=out("m0"), prev_out=xp, convert=1, x0_clip=1, clip=1, **X.VEC4_DPM)
+        L.check(l.bd_dpm_step(CT.byref(desc), L.stream()), "bd_dpm_step")
+        m0, prev = X.dpm_stmt(X.VEC4_DPM, e, x, a, b)
+        want = {"m0": m0, "sample": prev}
+    elif op == "unipc_step":
+        desc = L.UnipcStepDesc(n=n, model_output=ep, sample=xp, last_sample=ap, h1=bp, h2=cp, h3=dp, m0_out=out("m0"), corrected_out=out("xc"), prev_out=xp,
+                               convert=1, x0_clip=1, clip=1, **X.VEC4_UNIPC)
+        L.check(l.bd_unipc_step(CT.byref(desc), L.stream()), "bd_unipc_step")
+        m0, xc, prev = X.unipc_stmt(X.VEC4_UNIPC, e, x, a, b, c, d)
+        want = {"m0": m0, "xc": xc, "sample": prev}
+    elif op == "sigma_step":
+        desc = L.SigmaStepDesc(n=n, model_output=ep, sample=xp, base=ap, h1=bp, h2=cp, h3=dp, x0_out=out("x0"), d_out=out("d"), prev_out=xp,
+                               scaled_out=out("scaled"), average=0, clip=1, **X.VEC4_SIGMA)
+        L.check(l.bd_sigma_step(CT.byref(desc), L.stream()), "bd_sigma_step")
+        x0, dv, prev, sc = X.sigma_stmt(X.VEC4_SIGMA, e, x, a, b, c, d)
+        want = {"x0": x0, "d": dv, "sample": prev, "scaled": sc}
+    else:
+        L.check(l.bd_scale_input(xp, n, *X.VEC4_SCALE, out("out"), L.stream()), "bd_scale_input")
+        want = {"out": X.scale_input_stmt(x, *X.VEC4_SCALE)}
+    for name, w in want.items():
+        eq_bits(flat_result(xb if name == "sample" else outs[name][0], n), w, (op, n, name))
+    assert set(outs) == set(want) - {"sample"}
+    for j, ((buf, _), v) in enumerate(zip(ins, (e, x, a, b, c, d))):          # the inputs, read or not, are as they were
+        if not (j == 1 and "sample" in want):
+            assert X.same_bits(flat_result(buf, n), t32(v)), (op, n, j)
+
+
 # ================================================================================================ 3. clip + Adam
 def adam_call(L, l, gpu, dev_form, data, max_norm, step, want_norm, g_lead=LEAD):
     """(p, m, v, norm or None) as host tensors after one bd_adam_clip / bd_adam_clip_dev"""

@@ -329,3 +329,49 @@ def test_split_reference():
         assert torch.equal(h.view(Cin, 9, Cout), w.permute(2, 1, 0)) and not bool(l.any())
     u = X.ups2(torch.arange(2 * 3 * 5 * 1, dtype=torch.float32).view(2, 3, 5, 1))
     assert u.shape == (2, 6, 10, 1) and torch.equal(u[:, ::2, ::2], u[:, 1::2, 1::2]) and torch.equal(u[:, ::2, 1::2], u[:, 1::2, ::2])
+
+
+# ------------------------------------------------------------------------------------------------ the dense vec4 driver and its buffer check
+def test_vec4_sizes_and_statements():
+    """the sizes of test_vec4_driver follow the launchers' grid, and the fp32 statements of the DPM / UniPC / sigma steps stay within a few
+    roundings of the same formulas in fp64: every intermediate is below 32 in magnitude (clamps at 1.5 and 2, |inputs| <= 6, coefficients
+    below 1 but sigma_in), at most 12 rounded operations lie behind an output, so 12 * 32 * 2^-24 = 2.3e-5 bounds the distance"""
+    src = source("elementwise.hip")
+    assert len(re.findall(r"nblocks\(cdiv\(d(?:->|\.)n, 4\), TPB, 4096\)", src)) == 3            # dpm, unipc, sigma
+    assert len(re.findall(r"nblocks\(cdiv\(n, 4\), TPB, 4096\)", src)) == 2                      # lincomb, scale_input
+    assert X.VEC4_SECOND_TRIP == 4 * X.TPB * X.STEP_CAP + 5 and X.VEC4_N[-1] == X.VEC4_SECOND_TRIP and {1, 3, 4, 7} <= set(X.VEC4_N)
+    e, x, a, b, c, d = X.vec4_inputs(1023)
+    assert max(float(np.abs(v).max()) for v in (e, x, a, b, c, d)) <= 6.0
+    wide = [v.astype(np.float64) for v in (e, x, a, b, c, d)]
+    f64 = lambda k: {n: np.float64(f32(v)) for n, v in k.items()}
+    cl = lambda v, r: np.minimum(np.maximum(v, -r), r)
+    k = f64(X.VEC4_DPM)
+    m0 = cl((wide[1] - k["sigma_s"] * wide[0]) / k["alpha_s"], k["x0_range"])
+    prev = cl(k["cx"] * wide[1] + k["c0"] * m0 + k["c1"] * wide[2] + k["c2"] * wide[3], k["clip_range"])
+    got = X.dpm_stmt(X.VEC4_DPM, e, x, a, b)
+    worst = max(dist(got[0], m0), dist(got[1], prev))
+    k = f64(X.VEC4_UNIPC)
+    xc = k["kl"] * wide[2] + k["k0"] * m0 + k["k1"] * wide[3] + k["k2"] * wide[4] + k["k3"] * wide[5]
+    prev = cl(k["px"] * xc + k["p0"] * m0 + k["p1"] * wide[3] + k["p2"] * wide[4], k["clip_range"])
+    got = X.unipc_stmt(X.VEC4_UNIPC, e, x, a, b, c, d)
+    worst = max(worst, dist(got[0], m0), dist(got[1], xc), dist(got[2], prev))
+    k = f64(X.VEC4_SIGMA)
+    x0 = wide[1] - k["sigma_in"] * wide[0]
+    sc = cl((wide[2] + k["c0"] * wide[0] + k["c1"] * wide[3] + k["c2"] * wide[4] + k["c3"] * wide[5]) / k["in_div"], k["clip_range"])
+    got = X.sigma_stmt(X.VEC4_SIGMA, e, x, a, b, c, d)
+    worst = max(worst, dist(got[0], x0), dist(got[1], wide[0]), dist(got[2], sc * k["in_div"]), dist(got[3], sc))
+    assert all(g.dtype == f32 for g in got) and X.scale_input_stmt(x, *X.VEC4_SCALE).dtype == f32
+    print(f"fp32 statements of the dpm / unipc / sigma steps against fp64, max |d|: {worst:.3g}")
+    assert worst <= 12 * 32 * 2.0 ** -24
+
+
+def test_step_buffer_check_under_host_sanitizers(tmp_path):
+    """csrc/step_check.h (the alignment / overlap check of bd_lincomb, bd_dpm_step, bd_unipc_step, bd_sigma_step and bd_scale_input) with its
+    own main, built with -fsanitize=address,undefined and run as a stand-alone program, as tests/test_ema_host.py runs ema_check.h"""
+    import subprocess
+    csrc = os.path.join(os.path.dirname(GOLDEN), "..", "baddiffusion_amd", "csrc")
+    exe = str(tmp_path / "step_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan", "-I", csrc, os.path.join(csrc, "step_check_main.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and "step_check: ok" in r.stdout, (r.returncode, r.stdout, r.stderr)

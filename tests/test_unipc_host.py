@@ -267,7 +267,8 @@ def test_config_conversion():
     import inspect
     from baddiffusion_amd.pipelines import PNDMPipeline
     sig, pndm = inspect.signature(UniPCPipeline.__call__), inspect.signature(PNDMPipeline.__call__)
-    assert list(sig.parameters) == list(pndm.parameters) and sig.parameters["num_inference_steps"].default == 10
+    assert list(sig.parameters) == list(pndm.parameters) and sig.parameters["num_inference_steps"].default is None
+    assert UniPCPipeline.default_steps == 10 and "__call__" not in vars(UniPCPipeline)      # the call is _MultistepPipeline's
     # one loop, two thin subclasses
     assert issubclass(UniPCPipeline, _MultistepPipeline) and issubclass(DPMSolverPipeline, _MultistepPipeline)
     assert "_sample" not in vars(UniPCPipeline) and "_sample" not in vars(DPMSolverPipeline)
