@@ -42,7 +42,8 @@ IGNORE_ARGS = ["overwrite", "is_save_all_model_epochs"]
 SCHED_CHOICES = ["DDPM-SCHED", "DDIM-SCHED", "DPM_SOLVER_PP_O1-SCHED", "DPM_SOLVER_O1-SCHED", "DPM_SOLVER_PP_O2-SCHED",
                  "DPM_SOLVER_O2-SCHED", "DPM_SOLVER_PP_O3-SCHED", "DPM_SOLVER_O3-SCHED", "UNIPC-SCHED", "PNDM-SCHED", "DEIS-SCHED",
                  "HEUN-SCHED", "SCORE-SDE-VE-SCHED", "UNIPC_O1-SCHED", "UNIPC_O2-SCHED", "UNIPC_O3-SCHED",
-                 "HEUN_O2-SCHED", "LMSD_O1-SCHED", "LMSD_O2-SCHED", "LMSD_O3-SCHED", "LMSD_O4-SCHED"]
+                 "HEUN_O2-SCHED", "LMSD_O1-SCHED", "LMSD_O2-SCHED", "LMSD_O3-SCHED", "LMSD_O4-SCHED",
+                 "DEIS_O1-SCHED", "DEIS_O2-SCHED", "DEIS_O3-SCHED"]
 
 
 def parse_args(argv=None):
@@ -81,7 +82,8 @@ def parse_args(argv=None):
                         "and are refused.  UniPC itself lives under names of its own, UNIPC_O1-SCHED / UNIPC_O2-SCHED / UNIPC_O3-SCHED "
                         "(UniPCMultistepScheduler + UniPCPipeline, solver order 1-3), which need no --native_sched; so do the sigma-space "
                         "samplers, HEUN_O2-SCHED (HeunDiscreteScheduler + HeunPipeline) and LMSD_O1-SCHED ... LMSD_O4-SCHED "
-                        "(LMSDiscreteScheduler + LMSPipeline at that order).  DEIS is the one name still without a native scheduler")
+                        "(LMSDiscreteScheduler + LMSPipeline at that order), and DEIS, DEIS_O1-SCHED / DEIS_O2-SCHED / DEIS_O3-SCHED "
+                        "(DEISMultistepScheduler + DEISPipeline, solver order 1-3, the reference's coefficient arithmetic)")
     p.add_argument("--infer_steps", type=int, help="sampling steps of the pipeline (default: the pipeline's own)")
     p.add_argument("--asr_threshold", type=float,
                    help="measure: also score every backdoor image on its own and report ASR, the share whose MSE to the target is below this "

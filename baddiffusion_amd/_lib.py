@@ -69,6 +69,12 @@ class UnipcStepDesc(C.Structure):
                 ("clip", i32), ("clip_range", f32)]
 
 
+class DeisStepDesc(C.Structure):
+    _fields_ = [("n", i64), ("model_output", vp), ("sample", vp), ("m1", vp), ("m2", vp), ("m0_out", vp), ("prev_out", vp),
+                ("alpha_s", f32), ("sigma_s", f32), ("x0_clip", i32), ("x0_range", f32), ("cx", f32), ("c0", f32),
+                ("alpha_t", f32), ("k0", f32), ("k1", f32), ("k2", f32), ("clip", i32), ("clip_range", f32)]
+
+
 class SigmaStepDesc(C.Structure):
     _fields_ = [("n", i64), ("model_output", vp), ("sample", vp), ("base", vp), ("h1", vp), ("h2", vp), ("h3", vp),
                 ("x0_out", vp), ("d_out", vp), ("prev_out", vp), ("scaled_out", vp), ("sigma_in", f32), ("average", i32),
@@ -233,6 +239,7 @@ SIGNATURES = {
     "bd_lincomb": (i32, [i32, C.POINTER(vp), C.POINTER(f32), i64, i32, f32, vp, vp]),
     "bd_dpm_step": (i32, [C.POINTER(DpmStepDesc), vp]),
     "bd_unipc_step": (i32, [C.POINTER(UnipcStepDesc), vp]),
+    "bd_deis_step": (i32, [C.POINTER(DeisStepDesc), vp]),
     "bd_sigma_step": (i32, [C.POINTER(SigmaStepDesc), vp]),
     "bd_scale_input": (i32, [vp, i64, f32, f32, vp, vp]),
     "bd_timestep_embedding_f32": (i32, [vp, i32, i32, i32, i32, f32, vp, vp]),

@@ -732,6 +732,48 @@ static void unipc_launch(const bd_unipc_step_desc& d, hipStream_t stream) {
 }
 
 
+// f-4 (DEIS, scheduling_deis_multistep.py:240-473, log-rho version): one multistep update in one launch.  The conversion goes through the
+// x0-prediction and back to an eps prediction (four roundings: m0 is not e bitwise, and with the x0 clamp on a saturated element it is a
+// different value altogether), and the second / third order updates are alpha_t * (x / alpha_s + ...) with a true division, so neither
+// bd_dpm_step nor bd_lincomb can carry them bit for bit.  Which history terms are present are template parameters, as in UnipcOp.
+template <bool M1, bool M2>
+__device__ __forceinline__ void deis_elem(const bd_deis_step_desc& d, float e, float x, float a, float b, float& m0, float& prev) {
+    float x0 = (x - d.sigma_s * e) / d.alpha_s;
+    if (d.x0_clip) x0 = fminf(fmaxf(x0, -d.x0_range), d.x0_range);
+    m0 = (x - d.alpha_s * x0) / d.sigma_s;
+    float r;
+    if constexpr (M1) {
+        r = x / d.alpha_s + d.k0 * m0;
+        r += d.k1 * a;
+        if constexpr (M2) r += d.k2 * b;
+        r = d.alpha_t * r;
+    } else {
+        r = d.cx * x - d.c0 * m0;
+    }
+    if (d.clip) r = fminf(fmaxf(r, -d.clip_range), d.clip_range);
+    prev = r;
+}
+template <bool M1, bool M2>
+struct DeisOp {
+    bd_deis_step_desc d;
+    template <class V> __device__ __forceinline__ void at(int64_t i) const {
+        V e = ld<V>(d.model_output, i), x = ld<V>(d.sample, i);
+        V a = splat<V>(0.f), b = a;
+        if constexpr (M1) a = ld<V>(d.m1, i);
+        if constexpr (M2) b = ld<V>(d.m2, i);
+        V m0, p;
+        lanes([this](float e, float x, float a, float b, float& m0, float& p) { deis_elem<M1, M2>(d, e, x, a, b, m0, p); }, e, x, a, b, m0, p);
+        if (d.m0_out) st<V>(d.m0_out, i, m0);
+        st<V>(d.prev_out, i, p);
+    }
+};
+template <bool M1, bool M2>
+static void deis_launch(const bd_deis_step_desc& d, hipStream_t stream) {
+    const int64_t n4 = d.n / 4, items = n4 + (d.n % 4 != 0);          // the float4s, and one more block-0 pass for the tail
+    hipLaunchKernelGGL((vec4_kernel<DeisOp<M1, M2>>), dim3(nblocks(items, TPB, 4096)), dim3(TPB), 0, stream, DeisOp<M1, M2>{d}, n4, d.n);
+}
+
+
 // f-4 (sigma-space samplers: scheduling_heun_discrete.py:193-275, scheduling_lms_discrete.py:217-285, and Euler as their first order):
 // one transition in one launch -- pred_original_sample, the ODE derivative exactly as the reference rounds it ((x - x0) / sigma, not
 // the model output), Heun's average with the first stage's derivative or the linear multistep sum over the stored derivatives, the
@@ -978,6 +1020,23 @@ extern "C" int bd_unipc_step(const bd_unipc_step_desc* d, bd_stream_t stream) {
         default: BD_CHECK(false, BD_ERR_INVALID, "bd_unipc_step: last_sample without h1");
     }
     BD_LAUNCH_CHECK("unipc_step");
+    return BD_OK;
+}
+extern "C" int bd_deis_step(const bd_deis_step_desc* d, bd_stream_t stream) {
+    BD_CHECK(d, BD_ERR_INVALID, "bd_deis_step: null descriptor");
+    BD_CHECK(d->n > 0, BD_ERR_INVALID, "bd_deis_step: n=%lld must be positive", (long long)d->n);
+    BD_CHECK(d->model_output && d->sample && d->prev_out, BD_ERR_INVALID,
+             "bd_deis_step: null pointer (model_output, sample and prev_out are required)");
+    BD_CHECK(d->alpha_s > 0.f, BD_ERR_INVALID, "bd_deis_step: alpha_s=%g must be positive", (double)d->alpha_s);
+    BD_CHECK(d->sigma_s > 0.f, BD_ERR_INVALID, "bd_deis_step: sigma_s=%g must be positive", (double)d->sigma_s);
+    BD_CHECK(d->m1 || !d->m2, BD_ERR_INVALID, "bd_deis_step: m2 without m1 (the history has no gap)");
+    const StepBuf in[4] = {{d->model_output, "model_output"}, {d->sample, "sample"}, {d->m1, "m1"}, {d->m2, "m2"}};
+    const StepBuf out[2] = {{d->prev_out, "prev_out"}, {d->m0_out, "m0_out"}};
+    BD_TRY(step_buffers_check("bd_deis_step", d->n, in, 4, out, 2));
+    if (d->m2) deis_launch<true, true>(*d, S(stream));
+    else if (d->m1) deis_launch<true, false>(*d, S(stream));
+    else deis_launch<false, false>(*d, S(stream));
+    BD_LAUNCH_CHECK("deis_step");
     return BD_OK;
 }
 extern "C" int bd_sigma_step(const bd_sigma_step_desc* d, bd_stream_t stream) {

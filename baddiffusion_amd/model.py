@@ -15,9 +15,9 @@ from typing import Union
 import numpy as np
 import torch
 
-from .pipelines import DDIMPipeline, DDPMPipeline, DPMSolverPipeline, HeunPipeline, LMSPipeline, PNDMPipeline, UniPCPipeline
-from .schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, HeunDiscreteScheduler, LMSDiscreteScheduler,
-                         PNDMScheduler, RePaintScheduler, SchedulerConfigCarrier, UniPCMultistepScheduler)
+from .pipelines import DDIMPipeline, DDPMPipeline, DEISPipeline, DPMSolverPipeline, HeunPipeline, LMSPipeline, PNDMPipeline, UniPCPipeline
+from .schedulers import (DDIMScheduler, DDPMScheduler, DEISMultistepScheduler, DPMSolverMultistepScheduler, HeunDiscreteScheduler,
+                         LMSDiscreteScheduler, PNDMScheduler, RePaintScheduler, SchedulerConfigCarrier, UniPCMultistepScheduler)
 from .unet import UNet2DModel
 
 WEIGHTS_NAME = "diffusion_pytorch_model.bin"
@@ -87,7 +87,7 @@ def load_scheduler(directory):
     cls = {"DDPMScheduler": DDPMScheduler, "DDIMScheduler": DDIMScheduler,
            "RePaintScheduler": RePaintScheduler, "DPMSolverMultistepScheduler": DPMSolverMultistepScheduler,
            "UniPCMultistepScheduler": UniPCMultistepScheduler, "HeunDiscreteScheduler": HeunDiscreteScheduler,
-           "LMSDiscreteScheduler": LMSDiscreteScheduler}.get(cfg.get("_class_name", "DDPMScheduler"))
+           "LMSDiscreteScheduler": LMSDiscreteScheduler, "DEISMultistepScheduler": DEISMultistepScheduler}.get(cfg.get("_class_name", "DDPMScheduler"))
     if cls is None:
         raise NotImplementedError(f"scheduler {cfg.get('_class_name')} is not on the BadDiffusion hot path")
     return cls(**{k: v for k, v in cfg.items() if not k.startswith("_")})
@@ -270,6 +270,9 @@ class DiffuserModelSched:
     # its PNDM conversion): UniPCMultistepScheduler + UniPCPipeline with or without native_sched -- value = solver_order; the other
     # options are the reference's defaults (bh2, predict_x0)
     _UNIPC_SCHEDS = {"UNIPC_O1-SCHED": 1, "UNIPC_O2-SCHED": 2, "UNIPC_O3-SCHED": 3}
+    # DEIS under names of this project's own as well (the reference's DEIS-SCHED keeps its PNDM conversion): DEISMultistepScheduler +
+    # DEISPipeline with or without native_sched, in the reference's coefficient arithmetic -- value = solver_order
+    _DEIS_SCHEDS = {"DEIS_O1-SCHED": 1, "DEIS_O2-SCHED": 2, "DEIS_O3-SCHED": 3}
     # the sigma-space samplers, names of this project's own too (the reference's HEUN-SCHED / LMSD-SCHED keep their PNDM conversion):
     # HeunDiscreteScheduler + HeunPipeline, LMSDiscreteScheduler + LMSPipeline at the named order, with or without native_sched --
     # value = (scheduler class, order)
@@ -297,7 +300,8 @@ class DiffuserModelSched:
                          native_sched: bool = False):
         # model.py:577-643.  native_sched (not in the reference): the DPM-Solver names build DPMSolverMultistepScheduler +
         # DPMSolverPipeline instead of the PNDM conversion; the other solvers of that family have no native scheduler and are refused.
-        # The UNIPC_O*-SCHED names (not the reference's either) always build UniPCMultistepScheduler + UniPCPipeline
+        # The UNIPC_O*-SCHED names (not the reference's either) always build UniPCMultistepScheduler + UniPCPipeline, the DEIS_O*-SCHED
+        # names DEISMultistepScheduler + DEISPipeline
         clip_used = DiffuserModelSched.get_sample_clip(clip_sample, DiffuserModelSched.CLIP_SAMPLE_DEFAULT)
         local = _resolve_local(ckpt_id)
         if local is not None:
@@ -332,6 +336,9 @@ class DiffuserModelSched:
         elif noise_sched_type in DiffuserModelSched._UNIPC_SCHEDS:
             noise_sched = UniPCMultistepScheduler(solver_order=DiffuserModelSched._UNIPC_SCHEDS[noise_sched_type], **kw)
             get_pipeline = DiffuserModelSched._pipeline_generator(partial(UniPCPipeline, clip_sample=clip_used))
+        elif noise_sched_type in DiffuserModelSched._DEIS_SCHEDS:
+            noise_sched = DEISMultistepScheduler(solver_order=DiffuserModelSched._DEIS_SCHEDS[noise_sched_type], **kw)
+            get_pipeline = DiffuserModelSched._pipeline_generator(partial(DEISPipeline, clip_sample=clip_used))
         elif noise_sched_type in DiffuserModelSched._SIGMA_SCHEDS:
             cls_name, order = DiffuserModelSched._SIGMA_SCHEDS[noise_sched_type]
             if cls_name == "HeunDiscreteScheduler":

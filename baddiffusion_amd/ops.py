@@ -773,6 +773,25 @@ def unipc_step(model_output, sample, px, p0, h1=None, p1=0.0, h2=None, p2=0.0, h
     return out
 
 
+def deis_step(model_output, sample, alpha_s, sigma_s, cx=0.0, c0=0.0, m1=None, alpha_t=0.0, k0=0.0, k1=0.0, m2=None, k2=0.0, x0_clip=None,
+              clip=None, m0_out=None, out=None):
+    """One DEIS multistep update (bd_deis_step, formula in include/bd_hip.h) over dense float32 GPU tensors of one shape and layout.
+    (alpha_s, sigma_s): the scalars of the conversion m0 = (sample - alpha_s x0) / sigma_s, x0 = (sample - sigma_s model_output) /
+    alpha_s; x0_clip / clip: None or the range of the clamp of x0 / of the result; m1 / m2: the stored converted outputs of the
+    previous two steps, or None.  Without m1 the update is first order, cx sample - c0 m0; with it alpha_t (sample / alpha_s + k0 m0 +
+    k1 m1 [+ k2 m2]).  m0_out: where m0 is written, or None.  out may be `sample`, m0_out may be the oldest history buffer (m2
+    included): the library refuses any other overlap.  Returns prev_sample."""
+    lib = L.load(); _need_cuda(model_output, sample, m1, m2, m0_out, out)
+    out = _dense_out("deis_step", sample, (model_output, m1, m2, m0_out), out)
+    (x0_on, x0_range), (clip_on, clip_range) = _clip_pair(x0_clip), _clip_pair(clip)
+    d = L.DeisStepDesc(n=sample.numel(), model_output=L.ptr(model_output), sample=L.ptr(sample), m1=L.ptr(m1), m2=L.ptr(m2),
+                       m0_out=L.ptr(m0_out), prev_out=L.ptr(out), alpha_s=float(alpha_s), sigma_s=float(sigma_s), x0_clip=x0_on,
+                       x0_range=x0_range, cx=float(cx), c0=float(c0), alpha_t=float(alpha_t), k0=float(k0), k1=float(k1), k2=float(k2),
+                       clip=clip_on, clip_range=clip_range)
+    L.check(lib.bd_deis_step(C.byref(d), L.stream()), "bd_deis_step")
+    return out
+
+
 def sigma_step(model_output, sample, sigma_in, c0, in_div, base=None, average=False, h1=None, c1=0.0, h2=None, c2=0.0, h3=None, c3=0.0,
                clip=None, x0_out=None, d_out=None, scaled_out=None, out=None):
     """One transition of a sigma-space sampler (bd_sigma_step, formula in include/bd_hip.h) over dense float32 GPU tensors of one shape

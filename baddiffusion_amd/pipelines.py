@@ -1,7 +1,7 @@
 """DDPMPipeline / DDIMPipeline -- drop-in for the two (locally modified) pipelines BadDiffusion samples with
 (diffusers/src/diffusers/pipelines/ddpm/pipeline_ddpm.py:46-125, pipelines/ddim/pipeline_ddim.py:50-142 of the reference tree),
 including the repo's additions `init=`, `save_every_step=`, `start_from=` and the `.movie` output -- and the pipelines of the other
-samplers: PNDM, DPM-Solver(++), UniPC (_MultistepPipeline), Heun, LMS (_SigmaPipeline) and RePaint.
+samplers: PNDM, DPM-Solver(++), UniPC, DEIS (_MultistepPipeline), Heun, LMS (_SigmaPipeline) and RePaint.
 
 Loop body = one UNet forward (bd_unet_forward) + one fused scheduler step kernel; the image never leaves the
 GPU until the final (x/2+0.5).clamp(0,1) -> NHWC conversion (bd_to_image).  With a CPU `generator` the
@@ -15,8 +15,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .schedulers import (DDIMScheduler, PNDMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, HeunDiscreteScheduler,
-                         LMSDiscreteScheduler, RePaintScheduler, UniPCMultistepScheduler, randn_tensor)
+from .schedulers import (DDIMScheduler, PNDMScheduler, DDPMScheduler, DEISMultistepScheduler, DPMSolverMultistepScheduler,
+                         HeunDiscreteScheduler, LMSDiscreteScheduler, RePaintScheduler, UniPCMultistepScheduler, randn_tensor)
 
 
 class ImagePipelineOutput:
@@ -200,7 +200,7 @@ class DDIMPipeline(_PipelineBase):
 
 
 class _MultistepPipeline(_PipelineBase):
-    """The sampling loop of the deterministic samplers (PNDMPipeline, DPMSolverPipeline, UniPCPipeline; _SigmaPipeline has its own
+    """The sampling loop of the deterministic samplers (PNDMPipeline, DPMSolverPipeline, UniPCPipeline, DEISPipeline; _SigmaPipeline has its own
     under the same call): the call surface of the reference's PNDM pipeline (`init`, `start_from`, `save_every_step`, output_type
     "pil" | "numpy" | "u8" | None), one UNet forward + one fused step launch per step, no noise drawn after the start.  `clip_sample`
     is the post-step clamp of the sample (pipeline_pndm.py:108-109), folded into the step launch (`scheduler.step(..., clip=)`).  A
@@ -273,6 +273,14 @@ class UniPCPipeline(_MultistepPipeline):
     the regime UniPC is built for.  A scheduler that is not a UniPCMultistepScheduler is converted from its config.  With
     start_from=k there is no last sample, so the first executed step has no corrector and is first order."""
     scheduler_class = UniPCMultistepScheduler
+    default_steps = 10
+
+
+class DEISPipeline(_MultistepPipeline):
+    """Sampling with DEISMultistepScheduler: _MultistepPipeline's loop, one UNet forward + one `bd_deis_step` launch per step.  The
+    reference has no pipeline for this scheduler either (its DEIS-SCHED samples through PNDMPipeline); num_inference_steps=10 is this
+    project's default, the regime DEIS is built for.  A scheduler that is not a DEISMultistepScheduler is converted from its config."""
+    scheduler_class = DEISMultistepScheduler
     default_steps = 10
 
 

@@ -4,8 +4,9 @@
   DDPMScheduler, DDIMScheduler            the two BadDiffusion itself steps (scheduling_ddpm.py:76-481, scheduling_ddim.py:79-429)
   PNDMScheduler                           every other `--sched` ends up here through PNDMPipeline (bd_lincomb)
   RePaintScheduler                        inpainting (bd_repaint_step / bd_repaint_undo)
-  DPMSolverMultistepScheduler,            the multistep solvers in lambda, on _LambdaMultistep (bd_dpm_step, bd_unipc_step)
-  UniPCMultistepScheduler
+  DPMSolverMultistepScheduler,            the multistep solvers in lambda, on _LambdaMultistep (bd_dpm_step, bd_unipc_step,
+  UniPCMultistepScheduler,                bd_deis_step)
+  DEISMultistepScheduler
   HeunDiscreteScheduler,                  the sigma-space samplers, on _SigmaScheduler (bd_sigma_step, bd_scale_input)
   LMSDiscreteScheduler
 
@@ -20,7 +21,7 @@ once to the device; `step` reads its coefficients from that device table (no per
 no host<->device sync; scheduling_ddpm.py:350-365 does ~7 host scalar extractions per step).
 Only what BadDiffusion exercises is supported: epsilon prediction, linear betas, fixed_small /
 fixed_large variance; anything else raises like the reference does for unknown options.
-DPM-Solver(++) is behind --native_sched, UniPC behind the UNIPC_O*-SCHED names, Heun and LMS (fractional timesteps, scaled model
+DPM-Solver(++) is behind --native_sched, UniPC behind the UNIPC_O*-SCHED names, DEIS behind DEIS_O*-SCHED, Heun and LMS (fractional timesteps, scaled model
 input and initial noise) behind HEUN_O2-SCHED and LMSD_O*-SCHED.
 """
 import numpy as np
@@ -528,10 +529,10 @@ class RePaintScheduler(_Base):
 
 
 class _LambdaMultistep(_Base):
-    """What the two multistep solvers in lambda = log(alpha / sigma) share (DPM-Solver(++), UniPC; a DEIS scheduler would start here):
+    """What the three multistep solvers in lambda = log(alpha / sigma) share (DPM-Solver(++), UniPC, DEIS):
     the alpha_t / sigma_t / lambda_t tables, the timesteps and the position of one by value, the per-chain cache of the host scalars
     of a step, the thresholding rule and the warm-up counter.  A subclass has `_plan_scalars`, the key of its cache entries, its ring
-    of device buffers (`_reset`) and the body of `step`."""
+    of device buffers (`_reset`; `_history` serves the two that keep `solver_order` converted outputs) and the body of `step`."""
 
     def _refuse_thresholding(self, thresholding, sample_max_value):
         if thresholding and sample_max_value != 1.0:
@@ -573,7 +574,24 @@ class _LambdaMultistep(_Base):
             self._plans[key] = self._plan_scalars(*args)
         return self._plans[key]
 
-    def _advance(self):
+    def _history(self, order, x):
+        """(m1, m2, oldest) of a step of `order` on the sample x, for the solvers whose ring holds `solver_order` converted outputs, oldest
+        first: the buffers the update reads, which must fit x, and the one that takes this step's converted output -- the oldest of
+        the ring (also while it is read as m2), or None for a first order solver, which never reads it back"""
+        ring = self._ring
+        for h in ring[len(ring) - order + 1:] if order > 1 else ():
+            if not self._fits(h, x):
+                raise ValueError(f"{type(self).__name__}.step: the stored model outputs do not have this sample's shape and layout "
+                                 "(one chain per set_timesteps)")
+        oldest = None
+        if len(ring) > 1:
+            oldest = ring[0] if self._fits(ring[0], x) else torch.empty_like(x)
+        return (ring[-1] if order >= 2 else None), (ring[-2] if order >= 3 else None), oldest
+
+    def _advance(self, written=None):
+        """the bookkeeping of one step: the buffer of `_history` that the step wrote becomes the newest, the warm-up counter moves"""
+        if written is not None:
+            self._ring = self._ring[1:] + [written]
         if self.lower_order_nums < self.config.solver_order:
             self.lower_order_nums += 1
 
@@ -683,22 +701,11 @@ class DPMSolverMultistepScheduler(_LambdaMultistep):
         # scheduling_dpmsolver_multistep.py:529-573
         eps, x, restore = self._begin_step(model_output, sample)
         order, alpha_s, sigma_s, cx, c0, c1, c2 = self._plan(self._step_index(timestep))
-        ring = self._ring
-        for h in ring[len(ring) - order + 1:] if order > 1 else ():
-            if not self._fits(h, x):
-                raise ValueError("DPMSolverMultistepScheduler.step: the stored model outputs do not have this sample's shape and layout "
-                                 "(one chain per set_timesteps)")
+        m1, m2, oldest = self._history(order, x)
         pp = self.config.algorithm_type == "dpmsolver++"
-        # the oldest buffer takes this step's converted output; a first order solver never reads it back, so it is not written
-        oldest = None
-        if len(ring) > 1:
-            oldest = ring[0] if self._fits(ring[0], x) else torch.empty_like(x)
-        prev = ops.dpm_step(eps, x, cx, c0, m1=ring[-1] if order >= 2 else None, c1=c1, m2=ring[-2] if order >= 3 else None, c2=c2,
-                            convert=(alpha_s, sigma_s) if pp else None,
+        prev = ops.dpm_step(eps, x, cx, c0, m1=m1, c1=c1, m2=m2, c2=c2, convert=(alpha_s, sigma_s) if pp else None,
                             x0_clip=1.0 if pp and self.config.thresholding else None, clip=clip, m0_out=oldest)
-        if oldest is not None:
-            self._ring = ring[1:] + [oldest]
-        self._advance()
+        self._advance(oldest)
         return self._output(prev, restore, return_dict)
 
 
@@ -869,6 +876,140 @@ class UniPCMultistepScheduler(_LambdaMultistep):
         # the sample the predictor started from: the corrected one, or the incoming one where no corrector ran
         self.last_sample, self._last_owned = (corrected, True) if corr_order else (x, False)
         self._advance(step_index, order)
+        return self._output(prev, restore, return_dict)
+
+
+class DEISMultistepScheduler(_LambdaMultistep):
+    """DEIS multistep scheduler (scheduling_deis_multistep.py:61-473, log-rho version) on the GPU, epsilon prediction: an exponential
+    integrator of order 1-3 whose coefficients are the integrals of the Lagrange basis polynomials in log(rho), rho = sigma / alpha,
+    normally run at 10-20 UNet evaluations.  Every step is ONE `bd_deis_step` launch: the conversion of the model output (to the
+    x0-prediction, optionally clamped, and back to an eps prediction, :255-274), the update (:303, :345, :401) and the pipeline's
+    post-step clamp (`step(..., clip=r)`, as PNDMScheduler).  All scalar work is done on the host (`_plan`, no device access, kept
+    per set of timesteps).  The history is a ring of `solver_order` device buffers; a step writes its converted output into the
+    oldest.  `thresholding=True` is supported for sample_max_value == 1.0, where the reference's dynamic thresholding is exactly
+    clamp(x0, -1, 1); a DPM-Solver / UniPC config converts as in the reference (:155-165).
+
+    `coefficient_dtype` (this project's own, kept in the config) is the arithmetic of the host scalars:
+      "float32" (default)  the reference's: fp32 torch scalars, np.log on them, its order of operations.  Parity is the contract.
+      "float64"            the same expressions in float64 from the fp32 tables, rounded once to fp32.
+    The reference's coefficients are differences ind_fn(rho_t, ..) - ind_fn(rho_s0, ..) of nearly equal numbers, and in fp32 they
+    cancel.  Worst distance over a stand-in chain (tests/golden/make_golden_deis.py) from the same recurrence run in float64 on the
+    same fp32 tables, max |x| 16-39:
+
+      order  steps            reference (= "float32")            float64 coefficients, fp32 data
+      1      4 / 10 / 20 / 999  2.1e-5 / 1.5e-5 / 9.2e-6 / 5.6e-5  4.2e-5 / 1.9e-5 / 8.9e-6 / 5.4e-5
+      2      4 / 10 / 20        3.2e-5 / 1.9e-5 / 1.7e-5           2.3e-5 / 3.3e-5 / 7.9e-6
+      2      999                5.3e-3                             5.3e-5
+      3      10 / 20            9.7e-5 / 1.5e-4                    3.7e-5 / 1.3e-5
+      3      999                4.04                               4.7e-5
+
+    At the step counts DEIS is meant for the two agree; at 999 steps and order 3 the reference is off by a fifth of the signal, and
+    "float64" is the way out of it."""
+    order = 1
+    _KEYS = ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "trained_betas", "solver_order", "prediction_type",
+             "thresholding", "dynamic_thresholding_ratio", "sample_max_value", "algorithm_type", "solver_type", "lower_order_final",
+             "coefficient_dtype")
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                 solver_order=2, prediction_type="epsilon", thresholding=False, dynamic_thresholding_ratio=0.995, sample_max_value=1.0,
+                 algorithm_type="deis", solver_type="logrho", lower_order_final=True, coefficient_dtype="float32", **unused):
+        if algorithm_type != "deis":                                                    # scheduling_deis_multistep.py:155-165
+            if algorithm_type not in ("dpmsolver", "dpmsolver++"):
+                raise NotImplementedError(f"{algorithm_type} does is not implemented for {self.__class__}")
+            algorithm_type = "deis"
+        if solver_type != "logrho":
+            if solver_type not in ("midpoint", "heun", "bh1", "bh2"):
+                raise NotImplementedError(f"solver type {solver_type} does is not implemented for {self.__class__}")
+            solver_type = "logrho"
+        if solver_order not in (1, 2, 3):
+            raise ValueError(f"solver_order must be 1, 2 or 3, got {solver_order}")
+        if coefficient_dtype not in ("float32", "float64"):
+            raise ValueError(f"coefficient_dtype must be 'float32' (the reference's arithmetic) or 'float64', got {coefficient_dtype!r}")
+        self._refuse_thresholding(thresholding, sample_max_value)
+        self.config = FrozenConfig(
+            num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end, beta_schedule=beta_schedule,
+            trained_betas=trained_betas, solver_order=solver_order, prediction_type=prediction_type, thresholding=thresholding,
+            dynamic_thresholding_ratio=dynamic_thresholding_ratio, sample_max_value=sample_max_value, algorithm_type=algorithm_type,
+            solver_type=solver_type, lower_order_final=lower_order_final, coefficient_dtype=coefficient_dtype)
+        self._make_tables(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas)
+        self._make_lambda_tables(num_train_timesteps)
+
+    def _reset(self):
+        self.lower_order_nums = 0
+        self._ring = [None] * self.config.solver_order      # converted model outputs, oldest first; [-1] is the previous step's
+
+    def _plan(self, step_index):
+        """Host part of the step at `step_index` given the current `lower_order_nums`: (order_used, alpha_s, sigma_s, cx, c0, alpha_t,
+        k0, k1, k2) for bd_deis_step's formula (include/bd_hip.h); the scalars of the branch not taken are 0.  No device access."""
+        cfg = self.config
+        key = (step_index, self.lower_order_nums, cfg.solver_order, cfg.lower_order_final, cfg.coefficient_dtype)
+        return self._cached_plan(key, step_index)
+
+    @staticmethod
+    def _log(v):
+        """numpy's log of a 0-dim tensor, in its dtype, as a tensor: what np.log(tensor) gives the reference"""
+        return torch.as_tensor(np.log(v.numpy()))
+
+    @classmethod
+    def _ind2(cls, t, b, c):
+        """the integral of (log t - log c) / (log b - log c) (:338-340), in the reference's order of operations"""
+        lt, lb, lc = cls._log(t), cls._log(b), cls._log(c)
+        return t * (-lc + lt - 1) / (lb - lc)
+
+    @classmethod
+    def _ind3(cls, t, b, c, d):
+        """the integral of (log t - log c)(log t - log d) / ((log b - log c)(log b - log d)) (:384-395), likewise"""
+        lt, lb, lc, ld = cls._log(t), cls._log(b), cls._log(c), cls._log(d)
+        numerator = t * (lc * (ld - lt + 1) - ld * lt + ld + lt ** 2 - 2 * lt + 2)
+        return numerator / ((lb - lc) * (lb - ld))
+
+    def _plan_scalars(self, step_index):
+        ts, n, cfg = self._ts, len(self._ts), self.config
+        last = step_index == n - 1
+        prev_t = 0 if last else int(ts[step_index + 1])
+        final = last and cfg.lower_order_final and n < 15                                   # :442-447
+        second = step_index == n - 2 and cfg.lower_order_final and n < 15
+        if cfg.solver_order == 1 or self.lower_order_nums < 1 or final:
+            order = 1
+        elif cfg.solver_order == 2 or self.lower_order_nums < 2 or second:
+            order = 2
+        else:
+            order = 3
+        wide = cfg.coefficient_dtype == "float64"
+        # fp32 0-dim tensors as the reference indexes them out of its tables, or the same table entries widened
+        at = (lambda table, t: table[t].double()) if wide else (lambda table, t: table[t])
+        s0 = int(ts[step_index])
+        alpha_t, sigma_t = at(self.alpha_t, prev_t), at(self.sigma_t, prev_t)
+        alpha_s0, sigma_s0 = at(self.alpha_t, s0), at(self.sigma_t, s0)
+        zero = torch.zeros(())
+        cx = c0 = k0 = k1 = k2 = zero
+        if order == 1:
+            h = at(self.lambda_t, prev_t) - at(self.lambda_t, s0)
+            cx, c0 = alpha_t / alpha_s0, sigma_t * (torch.exp(h) - 1.0)
+        else:
+            older = [int(ts[step_index - j]) for j in range(1, order)]
+            rho_t, rho_s0 = sigma_t / alpha_t, sigma_s0 / alpha_s0
+            rho_s1 = at(self.sigma_t, older[0]) / at(self.alpha_t, older[0])
+            if order == 2:
+                k0 = self._ind2(rho_t, rho_s0, rho_s1) - self._ind2(rho_s0, rho_s0, rho_s1)
+                k1 = self._ind2(rho_t, rho_s1, rho_s0) - self._ind2(rho_s0, rho_s1, rho_s0)
+            else:
+                rho_s2 = at(self.sigma_t, older[1]) / at(self.alpha_t, older[1])
+                k0 = self._ind3(rho_t, rho_s0, rho_s1, rho_s2) - self._ind3(rho_s0, rho_s0, rho_s1, rho_s2)
+                k1 = self._ind3(rho_t, rho_s1, rho_s2, rho_s0) - self._ind3(rho_s0, rho_s1, rho_s2, rho_s0)
+                k2 = self._ind3(rho_t, rho_s2, rho_s0, rho_s1) - self._ind3(rho_s0, rho_s2, rho_s0, rho_s1)
+        f32 = lambda v: float(torch.as_tensor(v).float())       # noqa: E731  (the one rounding of a float64 scalar; a fp32 one is exact)
+        return (order, float(self.alpha_t[s0]), float(self.sigma_t[s0]), f32(cx), f32(c0), float(self.alpha_t[prev_t]) if order > 1 else 0.0,
+                f32(k0), f32(k1), f32(k2))
+
+    def step(self, model_output, timestep, sample, return_dict=True, clip=None):
+        # scheduling_deis_multistep.py:407-473
+        eps, x, restore = self._begin_step(model_output, sample)
+        order, alpha_s, sigma_s, cx, c0, alpha_t, k0, k1, k2 = self._plan(self._step_index(timestep))
+        m1, m2, oldest = self._history(order, x)
+        prev = ops.deis_step(eps, x, alpha_s, sigma_s, cx=cx, c0=c0, m1=m1, alpha_t=alpha_t, k0=k0, k1=k1, m2=m2, k2=k2,
+                             x0_clip=1.0 if self.config.thresholding else None, clip=clip, m0_out=oldest)
+        self._advance(oldest)
         return self._output(prev, restore, return_dict)
 
 

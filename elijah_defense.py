@@ -1,7 +1,7 @@
 """Elijah-style defense on the MI355X path: invert the trigger, score the checkpoint, remove the backdoor, score it again.
 
     python elijah_defense.py --ckpt <checkpoint dir> [--inv_steps 100] [--inv_batch 64] [--inv_lr 0.1] [--lam 0.5]
-                             [--detect_n 256] [--sched DDIM-SCHED|DDPM-SCHED|DPM_SOLVER_{PP_,}O{1,2,3}-SCHED|UNIPC_O{1,2,3}-SCHED|HEUN_O2-SCHED|LMSD_O{1,2,3,4}-SCHED] [--infer_steps 50] [--max_ratio R]
+                             [--detect_n 256] [--sched DDIM-SCHED|DDPM-SCHED|DPM_SOLVER_{PP_,}O{1,2,3}-SCHED|UNIPC_O{1,2,3}-SCHED|DEIS_O{1,2,3}-SCHED|HEUN_O2-SCHED|LMSD_O{1,2,3,4}-SCHED] [--infer_steps 50] [--max_ratio R]
                              [--remove_steps 200] [--batch 64] [--learning_rate 2e-5] [--output_dir DIR] [--tag T] [--seed 0] [--gpu 0]
                              [--clean_source none|synthetic|dataset] [--clean_n 256] [--clean_batch 64] [--clean_weight 1.0]
                              [--clean_target frozen|noise] [--dataset CIFAR10] [--dataset_path datasets]
@@ -33,8 +33,9 @@ import torch
 from baddiffusion_amd import defense
 from baddiffusion_amd.inversion import invert_trigger
 from baddiffusion_amd.model import DiffuserModelSched, save_scheduler, save_unet
-from baddiffusion_amd.pipelines import DDIMPipeline, DDPMPipeline, DPMSolverPipeline, HeunPipeline, LMSPipeline, UniPCPipeline
-from baddiffusion_amd.schedulers import DPMSolverMultistepScheduler, HeunDiscreteScheduler, LMSDiscreteScheduler, UniPCMultistepScheduler
+from baddiffusion_amd.pipelines import DDIMPipeline, DDPMPipeline, DEISPipeline, DPMSolverPipeline, HeunPipeline, LMSPipeline, UniPCPipeline
+from baddiffusion_amd.schedulers import (DEISMultistepScheduler, DPMSolverMultistepScheduler, HeunDiscreteScheduler, LMSDiscreteScheduler,
+                                          UniPCMultistepScheduler)
 
 
 @dataclass
@@ -72,7 +73,7 @@ class Config:
 
 
 SCHED_CHOICES = [DiffuserModelSched.DDIM_SCHED, DiffuserModelSched.DDPM_SCHED] + sorted(DiffuserModelSched._DPM_SCHEDS) + \
-    sorted(DiffuserModelSched._UNIPC_SCHEDS) + sorted(DiffuserModelSched._SIGMA_SCHEDS)
+    sorted(DiffuserModelSched._UNIPC_SCHEDS) + sorted(DiffuserModelSched._DEIS_SCHEDS) + sorted(DiffuserModelSched._SIGMA_SCHEDS)
 DEFAULT_ASR_THRESHOLD = 1e-3    # of the order the papers use; a choice, not a finding
 
 
@@ -94,7 +95,7 @@ def get_config(argv=None):
     p.add_argument("--detect_n", type=int, default=config.detect_n)
     p.add_argument("--sched", "-sc", type=str, default=config.sched, choices=SCHED_CHOICES,
                    help="sampling pipeline of the score passes; the DPM_SOLVER_* names run DPMSolverMultistepScheduler (always the native solver here), "
-                        "the UNIPC_O* names UniPCMultistepScheduler, HEUN_O2 / LMSD_O* the sigma-space samplers")
+                        "the UNIPC_O* names UniPCMultistepScheduler, the DEIS_O* names DEISMultistepScheduler, HEUN_O2 / LMSD_O* the sigma-space samplers")
     p.add_argument("--infer_steps", "-is", type=int, default=config.infer_steps)
     p.add_argument("--max_ratio", type=float)
     p.add_argument("--remove_steps", type=int, default=config.remove_steps)
@@ -140,6 +141,9 @@ def make_pipeline(config, model, noise_sched):
     if config.sched in DiffuserModelSched._UNIPC_SCHEDS:
         sched = UniPCMultistepScheduler.from_config({**noise_sched.config, "solver_order": DiffuserModelSched._UNIPC_SCHEDS[config.sched]})
         return UniPCPipeline(unet=model, scheduler=sched)
+    if config.sched in DiffuserModelSched._DEIS_SCHEDS:
+        sched = DEISMultistepScheduler.from_config({**noise_sched.config, "solver_order": DiffuserModelSched._DEIS_SCHEDS[config.sched]})
+        return DEISPipeline(unet=model, scheduler=sched)
     if config.sched in DiffuserModelSched._SIGMA_SCHEDS:
         cls_name, order = DiffuserModelSched._SIGMA_SCHEDS[config.sched]
         if cls_name == "HeunDiscreteScheduler":

@@ -179,6 +179,35 @@ typedef struct {
 } bd_unipc_step_desc;
 int bd_unipc_step(const bd_unipc_step_desc* d, bd_stream_t stream);
 
+/* f-4: one DEIS multistep update (scheduling_deis_multistep.py:240-473, log-rho version, epsilon prediction) over n dense fp32 elements of
+ * one common layout, in one launch.  Per element, fp32, in this order (e = model_output, x = sample, m1 / m2 = the stored converted
+ * outputs of the previous steps, newest first):
+ *     x0   = (x - sigma_s e) / alpha_s
+ *     x0   = x0_clip ? clamp(x0, -x0_range, x0_range) : x0        thresholding with sample_max_value == 1
+ *     m0   = (x - alpha_s x0) / sigma_s                           the eps prediction back from x0: not e bitwise, as in the reference
+ *     m1 == NULL:  prev = cx x - c0 m0                            first order: cx = alpha_t / alpha_s, c0 = sigma_t (exp(h) - 1)
+ *     else:        prev = alpha_t * (x / alpha_s + k0 m0 + k1 m1 [+ k2 m2])     summed left to right; x / alpha_s is a true division
+ *     prev = clip ? clamp(prev, -clip_range, clip_range) : prev
+ * m0 is written to m0_out (NULL: not written), prev to prev_out.  The scalars are host values; those of the branch not taken are ignored.
+ * An output may alias an input only with an identical base pointer (prev_out == sample; m0_out == the oldest history buffer, also when
+ * that buffer is read as m2): every element is read into registers before its index is written.
+ * Host checks before the launch (BD_ERR_INVALID, message names bd_deis_step): null descriptor, n <= 0, a null model_output / sample /
+ * prev_out, alpha_s <= 0, sigma_s <= 0, m2 without m1, a pointer that is not 16-byte aligned, an output that overlaps an input (or the
+ * other output) in any other way.
+ * HBM-bound: 16-byte accesses over n / 4, a scalar tail of n % 4, at most 4096 blocks of 256 threads with a grid-stride loop. */
+typedef struct {
+    int64_t n;
+    const float* model_output; const float* sample;
+    const float* m1; const float* m2;            /* previous converted outputs, newest first; may be NULL */
+    float* m0_out; float* prev_out;              /* m0_out may be NULL                                    */
+    float alpha_s, sigma_s;
+    int x0_clip; float x0_range;
+    float cx, c0;                                /* first order (m1 == NULL)                              */
+    float alpha_t, k0, k1, k2;                   /* second / third order                                  */
+    int clip; float clip_range;
+} bd_deis_step_desc;
+int bd_deis_step(const bd_deis_step_desc* d, bd_stream_t stream);
+
 /* f-4: one transition of a sigma-space (k-diffusion) sampler -- Heun (scheduling_heun_discrete.py:193-275), linear multistep
  * (scheduling_lms_discrete.py:217-285) and Euler as the first order of both -- over n dense fp32 elements of one common layout, in one
  * launch, together with the NEXT evaluation's scale_model_input.  Per element, fp32, in this order (e = model_output, x = sample,

@@ -1,19 +1,22 @@
-"""Time the sampling loops side by side on the GPU and write profiles/sigma_sampling.json (profiles/dpm_solver_sampling.json and
-profiles/unipc_sampling.json are earlier runs of this script, before the UniPC rows and before the sigma-space rows).
+"""Time the sampling loops side by side on the GPU and write profiles/deis_sampling.json (profiles/dpm_solver_sampling.json,
+profiles/unipc_sampling.json and profiles/sigma_sampling.json are earlier runs of this script, before the UniPC rows, before the
+sigma-space rows and before the DEIS rows).
 
-    python scripts/bench_samplers.py [--out profiles/sigma_sampling.json] [--samples 2048] [--rounds 9]
+    python scripts/bench_samplers.py [--out profiles/deis_sampling.json] [--samples 2048] [--rounds 9]
 
 One process, the DDPM-CIFAR10-32 topology with default initialisation (the arithmetic does not depend on the weights), the default compute
 mode, `--samples` chains from one seeded noise batch.  Loops, in this order: DDIM-50, PNDM-50 (59 UNet evaluations), DPM-Solver++ order 2
 at 20 and at 10 steps (DPMSolverPipeline), UniPC order 2 at 20 and at 10 steps and order 3 at 10 (UniPCPipeline, bh2, predict_x0), LMS
-order 4 at 20 steps (LMSPipeline) and Heun at 10 steps (HeunPipeline: 19 UNet evaluations), DDIM-50 again.  Every loop is warmed up on its full chunk shape at a few steps and with its whole schedule on 64 samples (a sampling job runs
+order 4 at 20 steps (LMSPipeline) and Heun at 10 steps (HeunPipeline: 19 UNet evaluations), DEIS order 2 at 20 steps and order 3 at 10
+(DEISPipeline, the reference's coefficient arithmetic), DDIM-50 again.  Every loop is warmed up on its full chunk shape at a few steps and with its whole schedule on 64 samples (a sampling job runs
 the same schedule chunk after chunk, and DPMSolverMultistepScheduler keeps the host scalars of the schedule it ran last), then timed
 with a host clock between two device synchronisations.  output_type="u8" throughout (device images, what batch_sampling_save asks for),
 so no loop is charged a copy of its images to the host.  Recorded per loop: seconds, samples/s, UNet evaluations and ms per evaluation.
 The two DDIM-50 repeats give the spread of this run; `dpm_vs_ddim` states whether the DPM pipeline's ms per evaluation exceeds DDIM-50's
 (the mean of the two repeats) by no more than that spread; `unipc_vs_dpm` states the same for each UniPC loop against the DPM loop of the
 same step count; `sigma_vs_dpm` states it for the two sigma-space loops against DPM-Solver++ at 20 steps, whose evaluations run the same
-UNet on the same batch -- the expectation being that throughput follows the UNet evaluations, N for LMS and 2N - 1 for Heun.
+UNet on the same batch -- the expectation being that throughput follows the UNet evaluations, N for LMS and 2N - 1 for Heun;
+`deis_vs_dpm` states it for each DEIS loop against the DPM loop of the same step count.
 
 Step kernel: bd_dpm_step at order 2 (reads model_output, sample, m1; writes m0 and prev_sample: 5 streams of 4 B per element) against
 the same update as two bd_lincomb launches (x0 = sample / alpha - (sigma / alpha) eps: 2 reads + 1 write; prev = cx sample + c0 x0 +
@@ -26,7 +29,10 @@ the steady state with its scaled output (reads model_output, sample, h1, h2, h3;
 sample: 8 streams) against the same arithmetic as three bd_lincomb launches (x0 = sample - sigma eps: 2 + 1; d = (sample - x0) / sigma:
 2 + 1; prev = sample + c0 d + c1 h1 + c2 h2 + c3 h3: 5 + 1) plus a separate bd_scale_input (1 + 1): 14 streams, and against the
 shortcut that takes the model output for the derivative (mathematically equal, not bitwise: one bd_lincomb of 5 + 1 and the
-bd_scale_input: 8 streams, but no stored derivative).  Recorded, not asserted.  No GPU: the script fails, it has no CPU path."""
+bd_scale_input: 8 streams, but no stored derivative).  bd_deis_step at order 3 (reads model_output, sample, m1, m2; writes m0 and
+prev_sample: 6 streams) against the same arithmetic as three bd_lincomb launches (x0 = sample / alpha - (sigma / alpha) eps: 2 + 1; m0 =
+sample / sigma - (alpha / sigma) x0, the conversion back: 2 + 1; prev = (alpha_t / alpha) sample + alpha_t k0 m0 + alpha_t k1 m1 +
+alpha_t k2 m2: 4 + 1: 11 streams; equal mathematically, not bitwise).  Recorded, not asserted.  No GPU: the script fails, it has no CPU path."""
 import argparse
 import json
 import os
@@ -58,7 +64,7 @@ def time_loop(pipe, init, steps, evals_of):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--out", default=os.path.join("profiles", "sigma_sampling.json"))
+    ap.add_argument("--out", default=os.path.join("profiles", "deis_sampling.json"))
     ap.add_argument("--samples", type=int, default=2048)
     ap.add_argument("--rounds", type=int, default=9)
     args = ap.parse_args(argv)
@@ -66,8 +72,8 @@ def main(argv=None):
         raise SystemExit("bench_samplers: no GPU (timings are taken on the device or not at all)")
     from baddiffusion_amd import ops
     from baddiffusion_amd.model import DiffuserModelSched
-    from baddiffusion_amd.pipelines import DDIMPipeline, DPMSolverPipeline, HeunPipeline, LMSPipeline, PNDMPipeline, UniPCPipeline
-    from baddiffusion_amd.schedulers import DDPMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler
+    from baddiffusion_amd.pipelines import DDIMPipeline, DEISPipeline, DPMSolverPipeline, HeunPipeline, LMSPipeline, PNDMPipeline, UniPCPipeline
+    from baddiffusion_amd.schedulers import DDPMScheduler, DEISMultistepScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler
     model, _, _ = DiffuserModelSched.get_pretrained("DDPM-CIFAR10-32", allow_random_init=True)
     model = model.cuda()
     n = args.samples
@@ -75,10 +81,12 @@ def main(argv=None):
     steps_of = lambda p: len(p.scheduler.timesteps)                                               # noqa: E731
     mk_dpm = lambda: DPMSolverPipeline(model, DPMSolverMultistepScheduler(solver_order=2, algorithm_type="dpmsolver++"))   # noqa: E731
     mk_unipc = lambda order: UniPCPipeline(model, UniPCMultistepScheduler(solver_order=order))      # noqa: E731
+    mk_deis = lambda order: DEISPipeline(model, DEISMultistepScheduler(solver_order=order))         # noqa: E731
     plan = [("ddim50_a", DDIMPipeline(model, DDPMScheduler()), 50), ("pndm50", PNDMPipeline(model, DDPMScheduler()), 50),
             ("dpmpp_o2_20", mk_dpm(), 20), ("dpmpp_o2_10", mk_dpm(), 10), ("unipc_o2_20", mk_unipc(2), 20), ("unipc_o2_10", mk_unipc(2), 10),
             ("unipc_o3_10", mk_unipc(3), 10), ("lms_o4_20", LMSPipeline(model, DDPMScheduler(), order=4), 20),
-            ("heun_10", HeunPipeline(model, DDPMScheduler()), 10), ("ddim50_b", DDIMPipeline(model, DDPMScheduler()), 50)]
+            ("heun_10", HeunPipeline(model, DDPMScheduler()), 10), ("deis_o2_20", mk_deis(2), 20), ("deis_o3_10", mk_deis(3), 10),
+            ("ddim50_b", DDIMPipeline(model, DDPMScheduler()), 50)]
     result = {"device": torch.cuda.get_device_name(0), "topology": "DDPM-CIFAR10-32", "samples": n,
               "compute_mode": getattr(model, "compute_mode", None), "output_type": "u8", "loops": {}}
     for name, pipe, steps in plan:
@@ -112,6 +120,14 @@ def main(argv=None):
                                         "excess_over_dpm_ms": excess, "within_ddim50_spread": bool(excess <= spread),
                                         "excess_over_ddim50_ms": L[name]["ms_per_evaluation"] - ddim, "samples_per_s": L[name]["samples_per_s"]}
     print(json.dumps(result["sigma_vs_dpm"]), flush=True)
+    result["deis_vs_dpm"] = {"ddim50_spread_ms": spread, "ddim50_ms_per_evaluation": [a, b]}
+    for name, dpm in (("deis_o2_20", "dpmpp_o2_20"), ("deis_o3_10", "dpmpp_o2_10")):
+        excess = L[name]["ms_per_evaluation"] - L[dpm]["ms_per_evaluation"]
+        result["deis_vs_dpm"][name] = {"ms_per_evaluation": L[name]["ms_per_evaluation"], "dpm_loop": dpm,
+                                       "dpm_ms_per_evaluation": L[dpm]["ms_per_evaluation"], "excess_over_dpm_ms": excess,
+                                       "within_ddim50_spread": bool(excess <= spread),
+                                       "excess_over_ddim50_ms": L[name]["ms_per_evaluation"] - ddim, "samples_per_s": L[name]["samples_per_s"]}
+    print(json.dumps(result["deis_vs_dpm"]), flush=True)
 
     # ---- the step kernel against the two-launch route
     numel = n * 3 * 32 * 32
@@ -196,6 +212,28 @@ def main(argv=None):
         "max_abs_diff_between_routes": {"derivative": float((d_f - d_l).abs().max()), "prev": float((sprev_f - sprev_l).abs().max()),
                                         "scaled": float((sc_f - sc_l).abs().max()), "prev_shortcut": float((sprev_f - sprev_s).abs().max())}}
     print(json.dumps(result["sigma_step_kernel"]), flush=True)
+
+    # ---- bd_deis_step (order 3) against three bd_lincomb launches: x0, the conversion back to eps, the update
+    alpha_t, d0, d1, d2 = 0.9, -0.5, 0.3, -0.15
+    dm0_f, dprev_f, dx0_l, dm0_l, dprev_l = (torch.empty_like(x) for _ in range(5))
+
+    def deis_fused():
+        ops.deis_step(e, x, alpha_s, sigma_s, m1=h1, alpha_t=alpha_t, k0=d0, k1=d1, m2=h2, k2=d2, m0_out=dm0_f, out=dprev_f)
+
+    def deis_three_launches():
+        ops.lincomb([x, e], [1.0 / alpha_s, -sigma_s / alpha_s], out=dx0_l)
+        ops.lincomb([x, dx0_l], [1.0 / sigma_s, -alpha_s / sigma_s], out=dm0_l)
+        ops.lincomb([x, dm0_l, h1, h2], [alpha_t / alpha_s, alpha_t * d0, alpha_t * d1, alpha_t * d2], out=dprev_l)
+    times = compare({"bd_deis_step_order3": deis_fused, "bd_lincomb_x3": deis_three_launches}, args.rounds)
+    deis_fused(); deis_three_launches()
+    bytes_moved = {"bd_deis_step_order3": 6 * 4 * numel, "bd_lincomb_x3": 11 * 4 * numel}
+    result["deis_step_kernel"] = {
+        "n": numel, "times": times, "bytes": bytes_moved,
+        "hbm_share": {k: (v / PEAK_HBM) / times[k]["median_s"] for k, v in bytes_moved.items()},
+        "three_launches_over_fused": times["bd_lincomb_x3"]["median_s"] / times["bd_deis_step_order3"]["median_s"],
+        "fused_not_slower": bool(times["bd_deis_step_order3"]["median_s"] <= times["bd_lincomb_x3"]["median_s"]),
+        "max_abs_diff_between_routes": {"m0": float((dm0_f - dm0_l).abs().max()), "prev": float((dprev_f - dprev_l).abs().max())}}
+    print(json.dumps(result["deis_step_kernel"]), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(result, f, indent=2)
