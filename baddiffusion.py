@@ -35,8 +35,10 @@ DEFAULT_LEARNING_RATE_32, DEFAULT_LEARNING_RATE_256 = 2e-4, 8e-5
 NOT_MODE_TRAIN_OPTS = ["sample_ep"]
 NOT_MODE_TRAIN_MEASURE_OPTS = ["sample_ep"]
 MODE_RESUME_OPTS = ["project", "mode", "gpu", "ckpt"]
-MODE_SAMPLING_OPTS = ["project", "mode", "eval_max_batch", "gpu", "fclip", "ckpt", "sample_ep", "sched", "use_ema", "native_sched", "infer_steps"]
-MODE_MEASURE_OPTS = ["project", "mode", "eval_max_batch", "gpu", "fclip", "ckpt", "sample_ep", "sched", "use_ema", "native_sched", "infer_steps", "asr_threshold"]
+MODE_SAMPLING_OPTS = ["project", "mode", "eval_max_batch", "gpu", "fclip", "ckpt", "sample_ep", "sched", "use_ema", "native_sched", "infer_steps", "dyn_threshold",
+                      "dyn_threshold_ratio"]
+MODE_MEASURE_OPTS = ["project", "mode", "eval_max_batch", "gpu", "fclip", "ckpt", "sample_ep", "sched", "use_ema", "native_sched", "infer_steps", "asr_threshold",
+                     "dyn_threshold", "dyn_threshold_ratio"]
 EMA_DIR, EMA_STATE = "unet_ema", "ema.bin"     # averaged weights in diffusers layout under output_dir; EMA scalars + shadow under ckpt/
 IGNORE_ARGS = ["overwrite", "is_save_all_model_epochs"]
 SCHED_CHOICES = ["DDPM-SCHED", "DDIM-SCHED", "DPM_SOLVER_PP_O1-SCHED", "DPM_SOLVER_O1-SCHED", "DPM_SOLVER_PP_O2-SCHED",
@@ -85,6 +87,11 @@ def parse_args(argv=None):
                         "(LMSDiscreteScheduler + LMSPipeline at that order), and DEIS, DEIS_O1-SCHED / DEIS_O2-SCHED / DEIS_O3-SCHED "
                         "(DEISMultistepScheduler + DEISPipeline, solver order 1-3, the reference's coefficient arithmetic)")
     p.add_argument("--infer_steps", type=int, help="sampling steps of the pipeline (default: the pipeline's own)")
+    p.add_argument("--dyn_threshold", type=float,
+                   help="sample with dynamic thresholding of the predicted x0 (Imagen) in place of --fclip's fixed clamp: per image s = the "
+                        "--dyn_threshold_ratio quantile of |x0| clamped to [1, this value], x0 = clamp(x0, -s, s) / s.  DDPM-SCHED, DDIM-SCHED "
+                        "or the checkpoint's own DDPM / DDIM scheduler only")
+    p.add_argument("--dyn_threshold_ratio", type=float, help="the quantile of --dyn_threshold (0.995)")
     p.add_argument("--asr_threshold", type=float,
                    help="measure: also score every backdoor image on its own and report ASR, the share whose MSE to the target is below this "
                         "(no default: values of the order of 1e-3 are what the papers use)")
@@ -121,6 +128,8 @@ class TrainingConfig:
     asr_threshold: float = None
     native_sched: bool = False
     infer_steps: int = None
+    dyn_threshold: float = None
+    dyn_threshold_ratio: float = 0.995
     log_loss_split: bool = False
     eval_sample_n: int = 16
     measure_sample_n: int = 2048
@@ -180,6 +189,8 @@ def setup(argv=None, write=True):
         elif key not in IGNORE_ARGS:
             raise NotImplementedError(f"Argument: {key}={value} isn't used in mode: {args.mode}")
     config.mode = args.mode
+    if args.dyn_threshold_ratio is not None and args.dyn_threshold is None:
+        raise ValueError("--dyn_threshold_ratio needs --dyn_threshold")
     if not hasattr(config, "dataset"):
         raise ValueError("--dataset is required")
     if not hasattr(config, "sched"):
@@ -258,6 +269,7 @@ def get_data_loader(config, device):
 def get_model_sched(config, device):
     from baddiffusion_amd.model import DiffuserModelSched, _resolve_local
     native = bool(getattr(config, "native_sched", False))
+    dyn = dict(dyn_threshold=getattr(config, "dyn_threshold", None), dyn_threshold_ratio=getattr(config, "dyn_threshold_ratio", 0.995))
     if config.ckpt is not None:
         if config.mode in (MODE_SAMPLING, MODE_MEASURE, MODE_RESUME):
             path = config.output_dir
@@ -265,15 +277,15 @@ def get_model_sched(config, device):
                 path = os.path.join(config.output_dir, config.ep_model_dir, f"ep{config.sample_ep}")   # intent of :311-313
             base = config.__dict__.get("_base_ckpt", None) or path
             model, noise_sched, get_pipeline = DiffuserModelSched.get_trained(ckpt=base, clip_sample=config.clip,
-                                                                             noise_sched_type=config.sched, native_sched=native)
+                                                                             noise_sched_type=config.sched, native_sched=native, **dyn)
         else:
             model, noise_sched, get_pipeline = DiffuserModelSched.get_pretrained(ckpt=config.ckpt, clip_sample=config.clip,
-                                                                                noise_sched_type=config.sched, native_sched=native)
+                                                                                noise_sched_type=config.sched, native_sched=native, **dyn)
     else:
         model, noise_sched, get_pipeline = DiffuserModelSched.get_model_sched(image_size=config.image_size, channels=config.channel,
                                                                              model_type=DiffuserModelSched.MODEL_DEFAULT,
                                                                              noise_sched_type=config.sched, clip_sample=config.clip,
-                                                                             native_sched=native)
+                                                                             native_sched=native, **dyn)
     if getattr(config, "use_ema", False) and config.mode in (MODE_SAMPLING, MODE_MEASURE):
         load_ema_weights(model, base)      # beside the `unet` directory the raw weights came from
     steps = getattr(config, "infer_steps", None)
@@ -424,6 +436,8 @@ def measure(config, dsl, folder_name, pipeline, rank=0, world=1):
         np.savez(os.path.join(*parts, f"backdoor{suffix}_scores.npz"), mse=mse_each.cpu().numpy(),
                  ssim=metrics.ssim_per_image(gen_d, tgt_1, data_range=1.0).cpu().numpy())
         extra = {"ASR": asr, "ASR_threshold": float(asr_threshold)}
+    if getattr(config, "dyn_threshold", None) is not None:       # how the x0 of these samples was clamped
+        extra.update(dyn_threshold=float(config.dyn_threshold), dyn_threshold_ratio=float(config.dyn_threshold_ratio))
     mse_sc = metrics.mse(gen_d, tgt_d)
     ssim_sc = metrics.ssim(gen_d, tgt_d, data_range=1.0)     # torchmetrics defaults (parity unpinned: torchmetrics absent)
     # FID (baddiffusion.py:533: fid(path=[dataset_img_dir, clean_path])): pool3 features of pytorch_fid's InceptionV3 for the first

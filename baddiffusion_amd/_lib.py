@@ -31,13 +31,29 @@ class QsampleDesc(C.Structure):
 class DdpmStepDesc(C.Structure):
     _fields_ = [("n", i64), ("model_output", vp), ("sample", vp), ("noise", vp), ("prev_sample", vp),
                 ("pred_original", vp), ("alphas_cumprod", vp), ("t", i32), ("prev_t", i32), ("variance_type", i32),
-                ("clip_sample", i32), ("clip_sample_range", f32), ("clip_defense", i32), ("clip_defense_range", f32)]
+                ("clip_sample", i32), ("clip_sample_range", f32), ("clip_defense", i32), ("clip_defense_range", f32),
+                ("x0_quantile", vp), ("image_elems", i64), ("sample_max_value", f32)]
 
 
 class DdimStepDesc(C.Structure):
     _fields_ = [("n", i64), ("model_output", vp), ("sample", vp), ("noise", vp), ("prev_sample", vp),
                 ("pred_original", vp), ("alphas_cumprod", vp), ("t", i32), ("prev_t", i32),
-                ("final_alpha_cumprod", f32), ("eta", f32), ("clip_sample", i32), ("clip_sample_range", f32)]
+                ("final_alpha_cumprod", f32), ("eta", f32), ("clip_sample", i32), ("clip_sample_range", f32),
+                ("x0_quantile", vp), ("image_elems", i64), ("sample_max_value", f32)]
+
+
+class AbsQuantileDesc(C.Structure):
+    _fields_ = [("B", i32), ("m", i64), ("x", vp), ("model_output", vp), ("alphas_cumprod", vp), ("n_alphas", i32), ("t", i32),
+                ("q", f32), ("out", vp), ("workspace", vp), ("workspace_bytes", sz)]
+
+
+AQ_REGISTERS, AQ_STREAM = 0, 1
+
+
+class AbsQuantilePlanInfo(C.Structure):
+    """bd_abs_quantile_plan_info; path is enum bd_abs_quantile_path"""
+    _fields_ = [("path", i32), ("workgroups", i32), ("threads", i32), ("values_per_thread", i32), ("passes", i32), ("switch_m", i64),
+                ("workspace_bytes", sz)]
 
 
 REPAINT_UNDO_MAX = 8
@@ -230,6 +246,9 @@ SIGNATURES = {
     "bd_nhwc_to_nchw": (i32, [vp, i64, vp, i32, i32, i32, i32, vp]),
     "bd_ddpm_step": (i32, [C.POINTER(DdpmStepDesc), vp]),
     "bd_ddim_step": (i32, [C.POINTER(DdimStepDesc), vp]),
+    "bd_abs_quantile_workspace_bytes": (sz, [i32, i64]),
+    "bd_abs_quantile": (i32, [C.POINTER(AbsQuantileDesc), vp]),
+    "bd_abs_quantile_plan": (i32, [i32, i64, C.POINTER(AbsQuantilePlanInfo)]),
     "bd_to_image": (i32, [vp, i32, i64, i32, i32, i32, i32, vp, vp, vp]),
     "bd_timestep_embedding": (i32, [vp, i32, i32, i32, i32, f32, vp, vp]),
     "bd_gn_workspace_bytes": (sz, [i32, i32]),

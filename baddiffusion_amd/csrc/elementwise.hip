@@ -119,12 +119,30 @@ __global__ __launch_bounds__(TPB) void nhwc_to_nchw_kernel(const float* src, int
 // a-5: DDPM reverse step (scheduling_ddpm.py:350-415).  Coefficients recomputed per thread from the
 // device table in the same fp32 order the reference uses on 0-dim CPU tensors.
 // ------------------------------------------------------------------------------------------------
+// The predicted x0 of an epsilon model, x0 = (x - sqrt(1 - a_t) e) / sqrt(a_t): ddpm_step_kernel, ddim_step_kernel and abs_quantile_kernel
+// all form it here, so the value the quantile ranks is bitwise the value the step clamps.
+struct X0Coef { float sb, sa; };
+__device__ __forceinline__ X0Coef x0_coef(const float* alphas_cumprod, int t) {
+    const float a_t = alphas_cumprod[t];
+    X0Coef k;
+    k.sb = sqrtf(1.0f - a_t); k.sa = sqrtf(a_t);
+    return k;
+}
+__device__ __forceinline__ float x0_pred(const X0Coef& k, float x, float e) { return (x - k.sb * e) / k.sa; }
+// dynamic thresholding (scheduling_ddpm.py:313-318): s = clamp(q, 1, sample_max_value), a NaN quantile staying NaN (fmaxf would drop it);
+// x0 = clamp(x0, -s, s) / s, a true division
+__device__ __forceinline__ float x0_threshold(float x0, float q, float smax) {
+    const float s = q != q ? q : fminf(fmaxf(q, 1.0f), smax);
+    return fminf(fmaxf(x0, -s), s) / s;
+}
+
+template <bool THR>
 __global__ __launch_bounds__(TPB) void ddpm_step_kernel(bd_ddpm_step_desc d) {
     const float a_t = d.alphas_cumprod[d.t];
     const float a_prev = d.prev_t >= 0 ? d.alphas_cumprod[d.prev_t] : 1.0f;
     const float b_t = 1.0f - a_t, b_prev = 1.0f - a_prev;
     const float cur_alpha = a_t / a_prev, cur_beta = 1.0f - cur_alpha;
-    const float sb = sqrtf(b_t), sa = sqrtf(a_t);
+    const X0Coef k0 = x0_coef(d.alphas_cumprod, d.t);
     const float c0 = (sqrtf(a_prev) * cur_beta) / b_t;
     const float ct = sqrtf(cur_alpha) * b_prev / b_t;
     float sd = 0.f;
@@ -136,8 +154,9 @@ __global__ __launch_bounds__(TPB) void ddpm_step_kernel(bd_ddpm_step_desc d) {
     }
     for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < d.n; i += (int64_t)gridDim.x * TPB) {
         const float x = d.sample[i], e = d.model_output[i];
-        float x0 = (x - sb * e) / sa;
-        if (d.clip_sample) x0 = fminf(fmaxf(x0, -d.clip_sample_range), d.clip_sample_range);
+        float x0 = x0_pred(k0, x, e);
+        if (THR) x0 = x0_threshold(x0, d.x0_quantile[(unsigned)i / (unsigned)d.image_elems], d.sample_max_value);   // n < 2^31 here
+        else if (d.clip_sample) x0 = fminf(fmaxf(x0, -d.clip_sample_range), d.clip_sample_range);
         float prev = c0 * x0 + ct * x;
         if (d.t > 0) prev = prev + sd * d.noise[i];
         if (d.clip_defense) prev = fminf(fmaxf(prev, -d.clip_defense_range), d.clip_defense_range);
@@ -147,23 +166,150 @@ __global__ __launch_bounds__(TPB) void ddpm_step_kernel(bd_ddpm_step_desc d) {
 }
 
 // a-6: DDIM step (scheduling_ddim.py:300-381), epsilon prediction.
+template <bool THR>
 __global__ __launch_bounds__(TPB) void ddim_step_kernel(bd_ddim_step_desc d) {
     const float a_t = d.alphas_cumprod[d.t];
     const float a_prev = d.prev_t >= 0 ? d.alphas_cumprod[d.prev_t] : d.final_alpha_cumprod;
     const float b_t = 1.0f - a_t, b_prev = 1.0f - a_prev;
-    const float sb = sqrtf(b_t), sa = sqrtf(a_t);
+    const X0Coef k0 = x0_coef(d.alphas_cumprod, d.t);
     const float var = (b_prev / b_t) * (1.0f - a_t / a_prev);
     const float sd = d.eta * sqrtf(var);
     const float dir = sqrtf(1.0f - a_prev - sd * sd);
     const float sap = sqrtf(a_prev);
     for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < d.n; i += (int64_t)gridDim.x * TPB) {
         const float x = d.sample[i], e = d.model_output[i];
-        float x0 = (x - sb * e) / sa;
-        if (d.clip_sample) x0 = fminf(fmaxf(x0, -d.clip_sample_range), d.clip_sample_range);
+        float x0 = x0_pred(k0, x, e);
+        if (THR) x0 = x0_threshold(x0, d.x0_quantile[(unsigned)i / (unsigned)d.image_elems], d.sample_max_value);   // n < 2^31 here
+        else if (d.clip_sample) x0 = fminf(fmaxf(x0, -d.clip_sample_range), d.clip_sample_range);
         float prev = sap * x0 + dir * e;
         if (d.eta > 0.f) prev = prev + sd * d.noise[i];
         d.prev_sample[i] = prev;
         if (d.pred_original) d.pred_original[i] = x0;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Dynamic thresholding's order statistic (scheduling_ddpm.py:311): out[b] = torch.quantile(|v_b|, q) per image, exact.
+// |v| as an integer (the 31 value bits) is monotone in |v|, so the two order statistics around the rank are found by a radix select on
+// those bits, most significant first, in passes of 11, 10 and 10 bits: a pass counts, in an LDS histogram, the field of every key whose
+// higher bits equal the prefix found so far, then walks the counts to the bucket that holds the rank.  After the third pass the
+// prefix IS the key, so no value is looked up again.  Two ranks (lo and ceil(rank)) are followed at once, in two histograms from the
+// pass where their prefixes part.  Integer counts do not depend on arrival order: the result is deterministic.
+// One workgroup per image.  VPT > 0: the image's keys stay in VPT registers per thread (read once); VPT == 0: every pass reads it again.
+// ------------------------------------------------------------------------------------------------
+constexpr int AQ_BUCKETS = 2048;                                  // 2^11, the widest pass
+constexpr int AQ_REG_THREADS = 256, AQ_REG_VPT = 16;              // registers path: m <= 4096
+constexpr int AQ_REG_MAX = AQ_REG_THREADS * AQ_REG_VPT;
+constexpr int AQ_STREAM_THREADS = 1024;
+constexpr unsigned AQ_NO_KEY = 0xffffffffu;                       // bit 31 set: matches no prefix in any pass
+constexpr unsigned AQ_INF = 0x7f800000u;
+
+struct AqArgs {
+    const float* x; const float* e; const float* alphas_cumprod; int t;
+    int64_t m; unsigned lo, hi; float w; float* out;
+};
+
+// exclusive prefix sum of one count per thread over the workgroup (wave scan, then the totals of the waves before)
+template <int NT>
+__device__ __forceinline__ unsigned aq_excl_scan(unsigned v, unsigned* wave_tot) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    unsigned inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned u = __shfl_up(inc, o);
+        if (lane >= o) inc += u;
+    }
+    if (lane == 63) wave_tot[wv] = inc;
+    __syncthreads();
+    unsigned base = 0;
+    for (int i = 0; i < wv; ++i) base += wave_tot[i];
+    __syncthreads();
+    return base + inc - v;
+}
+
+// the bucket of hist[0 .. nb) in which the running count first exceeds k (k < the total), and k's rank inside it: res = {bucket, rank}
+template <int NT>
+__device__ __forceinline__ void aq_select(const unsigned* hist, int nb, unsigned k, unsigned* wave_tot, unsigned* res) {
+    const int per = nb / NT, first = threadIdx.x * per;          // nb is 2048 or 1024, NT 256 or 1024
+    unsigned sum = 0;
+    for (int j = 0; j < per; ++j) sum += hist[first + j];
+    const unsigned excl = aq_excl_scan<NT>(sum, wave_tot);
+    if (k >= excl && k - excl < sum) {                           // one thread: the counts before it are <= k, with its own they exceed k
+        unsigned run = excl;
+        for (int j = 0; j < per; ++j) {
+            const unsigned c = hist[first + j];
+            if (k - run < c) { res[0] = (unsigned)(first + j); res[1] = k - run; break; }
+            run += c;
+        }
+    }
+    __syncthreads();
+}
+
+template <int NT, int VPT>
+__global__ __launch_bounds__(NT) void abs_quantile_kernel(AqArgs a) {
+    __shared__ unsigned hist[2][AQ_BUCKETS];
+    __shared__ unsigned wave_tot[NT / 64];
+    __shared__ unsigned res[2][2];
+    __shared__ unsigned has_nan;
+    const int tid = threadIdx.x;
+    const int64_t base = (int64_t)blockIdx.x * a.m;
+    const float* x = a.x + base;
+    const float* e = a.e ? a.e + base : nullptr;
+    X0Coef kf = {0.f, 1.f};
+    if (e) kf = x0_coef(a.alphas_cumprod, a.t);
+    auto key_at = [&](int64_t i) -> unsigned {
+        float v = x[i];
+        if (e) v = x0_pred(kf, v, e[i]);
+        return __float_as_uint(v) & 0x7fffffffu;                 // |v|: -0 becomes 0, a NaN stays above AQ_INF
+    };
+    unsigned key[VPT > 0 ? VPT : 1];
+    if (VPT > 0) {
+#pragma unroll
+        for (int j = 0; j < VPT; ++j) {
+            const int64_t i = tid + (int64_t)j * NT;
+            key[j] = i < a.m ? key_at(i) : AQ_NO_KEY;
+        }
+    }
+    if (tid == 0) has_nan = 0;
+    unsigned prefix[2] = {0u, 0u}, k[2] = {a.lo, a.hi};
+#pragma unroll
+    for (int pass = 0; pass < 3; ++pass) {
+        const int shift = pass == 0 ? 20 : pass == 1 ? 10 : 0;
+        const int bits = pass == 0 ? 11 : 10, nb = 1 << bits;
+        const bool same = prefix[0] == prefix[1];                // uniform over the workgroup
+        for (int i = tid; i < 2 * AQ_BUCKETS; i += NT) (&hist[0][0])[i] = 0;
+        __syncthreads();
+        bool nan = false;
+        auto count = [&](unsigned ky) {
+            if (pass == 0 && ky > AQ_INF && ky != AQ_NO_KEY) nan = true;
+            const unsigned up = ky >> (shift + bits);            // the bits above this pass's field (pass 0: bit 31, 0 for every key)
+            const unsigned b = (ky >> shift) & (unsigned)(nb - 1);
+            if (up == prefix[0]) atomicAdd(&hist[0][b], 1u);
+            if (!same && up == prefix[1]) atomicAdd(&hist[1][b], 1u);
+        };
+        if (VPT > 0) {
+#pragma unroll
+            for (int j = 0; j < VPT; ++j) count(key[j]);
+        } else {
+            for (int64_t i = tid; i < a.m; i += NT) count(key_at(i));
+        }
+        if (pass == 0 && nan) atomicOr(&has_nan, 1u);
+        __syncthreads();
+        aq_select<NT>(hist[0], nb, k[0], wave_tot, res[0]);
+        aq_select<NT>(hist[same ? 0 : 1], nb, k[1], wave_tot, res[1]);       // under one prefix the two ranks may still part here
+        const unsigned b0 = res[0][0], r0 = res[0][1], b1 = res[1][0], r1 = res[1][1];
+        __syncthreads();
+        prefix[0] = (prefix[0] << bits) | b0; k[0] = r0;
+        prefix[1] = (prefix[1] << bits) | b1; k[1] = r1;
+    }
+    if (tid == 0) {
+        float r = __uint_as_float(0x7fc00000u);
+        if (!has_nan) {
+            const float lo = __uint_as_float(prefix[0]), hi = __uint_as_float(prefix[1]);
+            const float d = hi - lo;
+            r = a.w < 0.5f ? fmaf(a.w, d, lo) : fmaf(-d, 1.0f - a.w, hi);       // at::lerp, fused as the reference's CPU kernel is
+        }
+        a.out[blockIdx.x] = r;
     }
 }
 
@@ -962,8 +1108,70 @@ extern "C" int bd_ddpm_step(const bd_ddpm_step_desc* d, bd_stream_t stream) {
     BD_CHECK(d->t == 0 || d->noise, BD_ERR_INVALID, "bd_ddpm_step: noise is required when t > 0");
     BD_CHECK(d->variance_type == 0 || d->variance_type == 1, BD_ERR_UNSUPPORTED,
              "bd_ddpm_step: variance_type must be fixed_small(0) or fixed_large(1)");
-    hipLaunchKernelGGL(ddpm_step_kernel, dim3(nblocks(d->n, TPB, 4096)), dim3(TPB), 0, S(stream), *d);
+    if (d->x0_quantile) {
+        BD_CHECK(d->image_elems > 0 && d->n % d->image_elems == 0, BD_ERR_INVALID,
+                 "bd_ddpm_step: x0_quantile with n=%lld that is no multiple of image_elems=%lld", (long long)d->n, (long long)d->image_elems);
+        BD_CHECK(d->n < ((int64_t)1 << 31), BD_ERR_INVALID, "bd_ddpm_step: x0_quantile with n=%lld >= 2^31", (long long)d->n);
+        hipLaunchKernelGGL((ddpm_step_kernel<true>), dim3(nblocks(d->n, TPB, 4096)), dim3(TPB), 0, S(stream), *d);
+    } else {
+        hipLaunchKernelGGL((ddpm_step_kernel<false>), dim3(nblocks(d->n, TPB, 4096)), dim3(TPB), 0, S(stream), *d);
+    }
     BD_LAUNCH_CHECK("ddpm_step");
+    return BD_OK;
+}
+namespace bd {
+static int aq_plan(const char* who, int B, int64_t m, bd_abs_quantile_plan_info* p) {
+    BD_CHECK(B > 0, BD_ERR_INVALID, "%s: B=%d must be positive", who, B);
+    BD_CHECK(m > 0, BD_ERR_INVALID, "%s: m=%lld must be positive", who, (long long)m);
+    BD_CHECK(m < ((int64_t)1 << 31) && (int64_t)B * m < ((int64_t)1 << 31), BD_ERR_INVALID, "%s: B * m = %d * %lld must stay below 2^31", who, B,
+             (long long)m);
+    p->path = m <= AQ_REG_MAX ? BD_AQ_REGISTERS : BD_AQ_STREAM;
+    p->workgroups = B;
+    p->threads = p->path == BD_AQ_REGISTERS ? AQ_REG_THREADS : AQ_STREAM_THREADS;
+    p->values_per_thread = p->path == BD_AQ_REGISTERS ? AQ_REG_VPT : (int)cdiv(m, (int64_t)AQ_STREAM_THREADS);
+    p->passes = 3;
+    p->switch_m = AQ_REG_MAX;
+    p->workspace_bytes = 0;
+    return BD_OK;
+}
+}  // namespace bd
+extern "C" int bd_abs_quantile_plan(int B, int64_t m, bd_abs_quantile_plan_info* out) {
+    BD_CHECK(out, BD_ERR_INVALID, "bd_abs_quantile_plan: null output");
+    return aq_plan("bd_abs_quantile_plan", B, m, out);
+}
+extern "C" size_t bd_abs_quantile_workspace_bytes(int B, int64_t m) {
+    (void)B; (void)m;
+    return 0;                                     // neither path of today keeps anything outside its workgroup
+}
+extern "C" int bd_abs_quantile(const bd_abs_quantile_desc* d, bd_stream_t stream) {
+    BD_CHECK(d, BD_ERR_INVALID, "bd_abs_quantile: null descriptor");
+    BD_CHECK(d->x && d->out, BD_ERR_INVALID, "bd_abs_quantile: null pointer (x and out are required)");
+    bd_abs_quantile_plan_info p;
+    BD_TRY(aq_plan("bd_abs_quantile", d->B, d->m, &p));
+    BD_CHECK(d->q >= 0.f && d->q <= 1.f, BD_ERR_INVALID, "bd_abs_quantile: q=%g must lie in [0, 1]", (double)d->q);     // false for a NaN
+    BD_CHECK(d->workspace_bytes >= p.workspace_bytes && (d->workspace || !p.workspace_bytes), BD_ERR_INVALID,
+             "bd_abs_quantile: workspace of %zu bytes, %zu needed", d->workspace_bytes, p.workspace_bytes);
+    if (d->model_output) {
+        BD_CHECK(d->alphas_cumprod, BD_ERR_INVALID, "bd_abs_quantile: model_output without alphas_cumprod");
+        BD_CHECK(d->t >= 0 && d->t < d->n_alphas, BD_ERR_INVALID, "bd_abs_quantile: t=%d outside the table of %d", d->t, d->n_alphas);
+    }
+    // torch.quantile's ranks, in fp32: rank = q * (m - 1), below = floor, above = ceil, weight = rank - below
+    const float last = (float)(d->m - 1);
+    const float rank = d->q * last;
+    const float below = floorf(rank);
+    AqArgs a;
+    a.x = d->x; a.e = d->model_output; a.alphas_cumprod = d->alphas_cumprod; a.t = d->t; a.m = d->m; a.out = d->out;
+    a.w = rank - below;
+    int64_t lo = (int64_t)below;
+    if (lo > d->m - 1) lo = d->m - 1;             // (float)(m - 1) may round up past m - 1 above 2^24
+    int64_t hi = lo + (a.w > 0.f ? 1 : 0);
+    if (hi > d->m - 1) hi = d->m - 1;
+    a.lo = (unsigned)lo; a.hi = (unsigned)hi;
+    if (p.path == BD_AQ_REGISTERS)
+        hipLaunchKernelGGL((abs_quantile_kernel<AQ_REG_THREADS, AQ_REG_VPT>), dim3((unsigned)d->B), dim3(AQ_REG_THREADS), 0, S(stream), a);
+    else
+        hipLaunchKernelGGL((abs_quantile_kernel<AQ_STREAM_THREADS, 0>), dim3((unsigned)d->B), dim3(AQ_STREAM_THREADS), 0, S(stream), a);
+    BD_LAUNCH_CHECK("abs_quantile");
     return BD_OK;
 }
 extern "C" int bd_lincomb(int k, const float* const* terms, const float* coeffs, int64_t n, int clip, float clip_range, float* out,
@@ -1080,7 +1288,14 @@ extern "C" int bd_ddim_step(const bd_ddim_step_desc* d, bd_stream_t stream) {
              "bd_ddim_step: bad args");
     BD_CHECK(d->t >= 0, BD_ERR_INVALID, "bd_ddim_step: t < 0");
     BD_CHECK(d->eta == 0.f || d->noise, BD_ERR_INVALID, "bd_ddim_step: noise is required when eta > 0");
-    hipLaunchKernelGGL(ddim_step_kernel, dim3(nblocks(d->n, TPB, 4096)), dim3(TPB), 0, S(stream), *d);
+    if (d->x0_quantile) {
+        BD_CHECK(d->image_elems > 0 && d->n % d->image_elems == 0, BD_ERR_INVALID,
+                 "bd_ddim_step: x0_quantile with n=%lld that is no multiple of image_elems=%lld", (long long)d->n, (long long)d->image_elems);
+        BD_CHECK(d->n < ((int64_t)1 << 31), BD_ERR_INVALID, "bd_ddim_step: x0_quantile with n=%lld >= 2^31", (long long)d->n);
+        hipLaunchKernelGGL((ddim_step_kernel<true>), dim3(nblocks(d->n, TPB, 4096)), dim3(TPB), 0, S(stream), *d);
+    } else {
+        hipLaunchKernelGGL((ddim_step_kernel<false>), dim3(nblocks(d->n, TPB, 4096)), dim3(TPB), 0, S(stream), *d);
+    }
     BD_LAUNCH_CHECK("ddim_step");
     return BD_OK;
 }

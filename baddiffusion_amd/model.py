@@ -296,8 +296,37 @@ class DiffuserModelSched:
         return get_pipeline
 
     @staticmethod
+    def _check_dyn_threshold(noise_sched_type, dyn_threshold, dyn_threshold_ratio):
+        """dyn_threshold (the sample_max_value of dynamic thresholding) goes with DDPM-SCHED, DDIM-SCHED and the checkpoint's own
+        scheduler only; its values are checked here, before anything is loaded"""
+        if dyn_threshold is None:
+            return
+        if noise_sched_type not in (DiffuserModelSched.DDPM_SCHED, DiffuserModelSched.DDIM_SCHED, None):
+            raise NotImplementedError(
+                f"dyn_threshold with {noise_sched_type}: dynamic thresholding runs in the DDPM and DDIM steps only ({DiffuserModelSched.DDPM_SCHED}, "
+                f"{DiffuserModelSched.DDIM_SCHED} or no scheduler name); the multistep schedulers take thresholding with sample_max_value == 1 alone, "
+                "where it is the plain clamp, and the other samplers have no thresholding in the reference")
+        if not float(dyn_threshold) >= 1.0:
+            raise ValueError(f"dyn_threshold={dyn_threshold} must be >= 1 (the scale is clamp(quantile, 1, dyn_threshold))")
+        if not 0.0 <= float(dyn_threshold_ratio) <= 1.0:
+            raise ValueError(f"dyn_threshold_ratio={dyn_threshold_ratio} must lie in [0, 1]")
+
+    @staticmethod
+    def _set_dyn_threshold(noise_sched, dyn_threshold, dyn_threshold_ratio):
+        if dyn_threshold is None:
+            return
+        if not isinstance(noise_sched, (DDPMScheduler, DDIMScheduler)):
+            raise NotImplementedError(f"dyn_threshold with the checkpoint's {type(noise_sched).__name__}: dynamic thresholding runs in the "
+                                      "DDPM and DDIM steps only")
+        noise_sched.config.thresholding = True
+        noise_sched.config.sample_max_value = float(dyn_threshold)
+        noise_sched.config.dynamic_thresholding_ratio = float(dyn_threshold_ratio)
+        print(f"noise_sched.config.thresholding = True (sample_max_value {float(dyn_threshold)}, ratio {float(dyn_threshold_ratio)})")
+
+    @staticmethod
     def _get_model_sched(ckpt_id: str, clip_sample: bool, noise_sched_type: str = None, allow_random_init: bool = False,
-                         native_sched: bool = False):
+                         native_sched: bool = False, dyn_threshold: float = None, dyn_threshold_ratio: float = 0.995):
+        DiffuserModelSched._check_dyn_threshold(noise_sched_type, dyn_threshold, dyn_threshold_ratio)
         # model.py:577-643.  native_sched (not in the reference): the DPM-Solver names build DPMSolverMultistepScheduler +
         # DPMSolverPipeline instead of the PNDM conversion; the other solvers of that family have no native scheduler and are refused.
         # The UNIPC_O*-SCHED names (not the reference's either) always build UniPCMultistepScheduler + UniPCPipeline, the DEIS_O*-SCHED
@@ -368,15 +397,19 @@ class DiffuserModelSched:
         if clip_used is not None:
             noise_sched.config.clip_sample = clip_used
             print(f"noise_sched.config.clip_sample = {noise_sched.config.clip_sample}")
+        DiffuserModelSched._set_dyn_threshold(noise_sched, dyn_threshold, dyn_threshold_ratio)
         return model, noise_sched, get_pipeline
 
     @staticmethod
     def get_model_sched(image_size: int, channels: int, model_type: str = MODEL_DEFAULT, noise_sched_type: str = None,
-                        clip_sample: bool = None, native_sched: bool = False, **kwargs):
+                        clip_sample: bool = None, native_sched: bool = False, dyn_threshold: float = None,
+                        dyn_threshold_ratio: float = 0.995, **kwargs):
         # model.py:645-698
         if model_type == DiffuserModelSched.MODEL_DEFAULT:
+            DiffuserModelSched._check_dyn_threshold(None, dyn_threshold, dyn_threshold_ratio)
             clip_used = DiffuserModelSched.get_sample_clip(clip_sample, False)
             noise_sched = DDPMScheduler(num_train_timesteps=1000, clip_sample=clip_used)
+            DiffuserModelSched._set_dyn_threshold(noise_sched, dyn_threshold, dyn_threshold_ratio)
             model = UNet2DModel(
                 sample_size=image_size, in_channels=channels, out_channels=channels, layers_per_block=2,
                 block_out_channels=(128, 128, 256, 256, 512, 512),
@@ -394,18 +427,22 @@ class DiffuserModelSched:
         # topology only: the weights are re-initialised right below (model.apply(weight_reset), model.py:647-652)
         model, noise_sched, get_pipeline = DiffuserModelSched._get_model_sched(
             ckpt_id=DiffuserModelSched._HUB.get(table[model_type], table[model_type]), clip_sample=clip_sample,
-            noise_sched_type=noise_sched_type, allow_random_init=True, native_sched=native_sched)
+            noise_sched_type=noise_sched_type, allow_random_init=True, native_sched=native_sched, dyn_threshold=dyn_threshold,
+            dyn_threshold_ratio=dyn_threshold_ratio)
         model.reset_parameters()
         return model, noise_sched, get_pipeline
 
     @staticmethod
     def get_pretrained(ckpt: str, clip_sample: bool = None, noise_sched_type: str = None, allow_random_init: bool = False,
-                       native_sched: bool = False):
+                       native_sched: bool = False, dyn_threshold: float = None, dyn_threshold_ratio: float = 0.995):
         ckpt = DiffuserModelSched._HUB.get(ckpt, ckpt)
         return DiffuserModelSched._get_model_sched(ckpt_id=ckpt, clip_sample=clip_sample, noise_sched_type=noise_sched_type,
-                                                   allow_random_init=allow_random_init, native_sched=native_sched)
+                                                   allow_random_init=allow_random_init, native_sched=native_sched,
+                                                   dyn_threshold=dyn_threshold, dyn_threshold_ratio=dyn_threshold_ratio)
 
     @staticmethod
-    def get_trained(ckpt: str, clip_sample: bool = None, noise_sched_type: str = None, native_sched: bool = False):
+    def get_trained(ckpt: str, clip_sample: bool = None, noise_sched_type: str = None, native_sched: bool = False,
+                    dyn_threshold: float = None, dyn_threshold_ratio: float = 0.995):
         return DiffuserModelSched._get_model_sched(ckpt_id=ckpt, clip_sample=clip_sample, noise_sched_type=noise_sched_type,
-                                                   native_sched=native_sched)
+                                                   native_sched=native_sched, dyn_threshold=dyn_threshold,
+                                                   dyn_threshold_ratio=dyn_threshold_ratio)

@@ -118,8 +118,22 @@ def nhwc_to_nchw(x):
 
 
 # ------------------------------------------------------------------------------------------------ a-5/a-6/a-7
+def _threshold_fields(who, sample, x0_quantile, sample_max_value):
+    """the three dynamic-thresholding fields of a step descriptor; x0_quantile None switches the branch off"""
+    if x0_quantile is None:
+        return dict(x0_quantile=None, image_elems=0, sample_max_value=1.0)
+    _need_cuda(x0_quantile)
+    if x0_quantile.dtype != torch.float32 or x0_quantile.dim() != 1 or not x0_quantile.is_contiguous() \
+            or x0_quantile.numel() != sample.shape[0]:
+        raise ValueError(f"{who}: x0_quantile must be a contiguous float32 [{sample.shape[0]}] tensor, one value per image")
+    return dict(x0_quantile=L.ptr(x0_quantile), image_elems=sample.numel() // sample.shape[0], sample_max_value=float(sample_max_value))
+
+
 def ddpm_step(model_output, sample, noise, alphas_cumprod, t, prev_t, variance_type="fixed_small", clip_sample=True,
-              clip_sample_range=1.0, clip_defense=False, clip_defense_range=1.0, out=None, want_x0=False):
+              clip_sample_range=1.0, clip_defense=False, clip_defense_range=1.0, out=None, want_x0=False, x0_quantile=None,
+              sample_max_value=1.0):
+    """x0_quantile ([B] raw quantiles of |x0|, from abs_quantile): dynamic thresholding of the predicted x0 in place of clip_sample;
+    the tensors' dimension 0 must then be the outermost in memory (both layouts of the schedulers are)"""
     lib = L.load(); _need_cuda(model_output, sample, noise, alphas_cumprod)
     vt = {"fixed_small": 0, "fixed_large": 1}.get(variance_type)
     if vt is None:
@@ -132,13 +146,14 @@ def ddpm_step(model_output, sample, noise, alphas_cumprod, t, prev_t, variance_t
                        noise=L.ptr(noise.contiguous()) if noise is not None else None, prev_sample=L.ptr(prev),
                        pred_original=L.ptr(x0), alphas_cumprod=L.ptr(alphas_cumprod), t=int(t), prev_t=int(prev_t),
                        variance_type=vt, clip_sample=int(bool(clip_sample)), clip_sample_range=clip_sample_range,
-                       clip_defense=int(bool(clip_defense)), clip_defense_range=clip_defense_range)
+                       clip_defense=int(bool(clip_defense)), clip_defense_range=clip_defense_range,
+                       **_threshold_fields("ddpm_step", sample, x0_quantile, sample_max_value))
     L.check(lib.bd_ddpm_step(C.byref(d), L.stream()), "bd_ddpm_step")
     return (prev, x0) if want_x0 else prev
 
 
 def ddim_step(model_output, sample, alphas_cumprod, t, prev_t, eta=0.0, noise=None, clip_sample=True,
-              clip_sample_range=1.0, final_alpha_cumprod=1.0, out=None, want_x0=False):
+              clip_sample_range=1.0, final_alpha_cumprod=1.0, out=None, want_x0=False, x0_quantile=None, sample_max_value=1.0):
     lib = L.load(); _need_cuda(model_output, sample, noise, alphas_cumprod)
     assert model_output.is_contiguous() and sample.is_contiguous()
     prev = torch.empty_like(sample) if out is None else out
@@ -147,9 +162,48 @@ def ddim_step(model_output, sample, alphas_cumprod, t, prev_t, eta=0.0, noise=No
                        noise=L.ptr(noise.contiguous()) if noise is not None else None, prev_sample=L.ptr(prev),
                        pred_original=L.ptr(x0), alphas_cumprod=L.ptr(alphas_cumprod), t=int(t), prev_t=int(prev_t),
                        final_alpha_cumprod=final_alpha_cumprod, eta=eta, clip_sample=int(bool(clip_sample)),
-                       clip_sample_range=clip_sample_range)
+                       clip_sample_range=clip_sample_range,
+                       **_threshold_fields("ddim_step", sample, x0_quantile, sample_max_value))
     L.check(lib.bd_ddim_step(C.byref(d), L.stream()), "bd_ddim_step")
     return (prev, x0) if want_x0 else prev
+
+
+def abs_quantile_plan(B, m):
+    """bd_abs_quantile_plan as a dict: which path a (B, m) takes (path 0 registers, 1 stream), with how many workgroups and threads"""
+    lib = L.load()
+    info = L.AbsQuantilePlanInfo()
+    L.check(lib.bd_abs_quantile_plan(int(B), int(m), C.byref(info)), "bd_abs_quantile_plan")
+    return {name: getattr(info, name) for name, _ in info._fields_}
+
+
+def abs_quantile(x, q, *, model_output=None, alphas_cumprod=None, t=None):
+    """[B] float32: torch.quantile(|v|.reshape(B, -1), q, dim=1) bit for bit, raw (not clamped).  v = x, or with model_output
+    (and the device table alphas_cumprod and the timestep t) the predicted x0 = (x - sqrt(1 - a_t) model_output) / sqrt(a_t), never
+    materialised.  x (and model_output, in the same layout) is float32 and dense with dimension 0 outermost in memory: contiguous, or
+    channels_last storage -- a quantile does not depend on the order inside an image."""
+    lib = L.load(); _need_cuda(x, model_output, alphas_cumprod)
+    if x.dtype != torch.float32 or x.dim() < 1 or x.numel() == 0:
+        raise TypeError(f"abs_quantile: expected a non-empty float32 tensor, got {x.dtype} {tuple(x.shape)}")
+    B = x.shape[0]
+    m = x.numel() // B
+    if not _is_dense(x) or (B > 1 and m > 1 and x.stride(0) != m):
+        raise ValueError("abs_quantile: x must be dense with dimension 0 outermost in memory")
+    if model_output is not None:
+        if alphas_cumprod is None or t is None:
+            raise ValueError("abs_quantile: model_output needs alphas_cumprod and t")
+        if model_output.shape != x.shape or model_output.stride() != x.stride() or model_output.dtype != x.dtype \
+                or model_output.device != x.device:
+            raise ValueError("abs_quantile: x and model_output must share shape, strides, dtype and device")
+        if alphas_cumprod.dtype != torch.float32 or not alphas_cumprod.is_contiguous():
+            raise ValueError("abs_quantile: alphas_cumprod must be a contiguous float32 table")
+    out = torch.empty(B, device=x.device, dtype=torch.float32)
+    need = lib.bd_abs_quantile_workspace_bytes(B, m)
+    ws = workspace(need, x.device, "abs_quantile") if need else None
+    d = L.AbsQuantileDesc(B=B, m=m, x=L.ptr(x), model_output=L.ptr(model_output), alphas_cumprod=L.ptr(alphas_cumprod),
+                          n_alphas=0 if alphas_cumprod is None else alphas_cumprod.numel(), t=0 if t is None else int(t), q=float(q),
+                          out=L.ptr(out), workspace=L.ptr(ws), workspace_bytes=0 if ws is None else ws.numel())
+    L.check(lib.bd_abs_quantile(C.byref(d), L.stream()), "bd_abs_quantile")
+    return out
 
 
 def _is_dense(t):

@@ -21,6 +21,7 @@ once to the device; `step` reads its coefficients from that device table (no per
 no host<->device sync; scheduling_ddpm.py:350-365 does ~7 host scalar extractions per step).
 Only what BadDiffusion exercises is supported: epsilon prediction, linear betas, fixed_small /
 fixed_large variance; anything else raises like the reference does for unknown options.
+Dynamic thresholding (`thresholding=True`, any `sample_max_value`) runs in DDPM and DDIM: bd_abs_quantile ahead of the step launch (`_x0_quantile`).
 DPM-Solver(++) is behind --native_sched, UniPC behind the UNIPC_O*-SCHED names, DEIS behind DEIS_O*-SCHED, Heun and LMS (fractional timesteps, scaled model
 input and initial noise) behind HEUN_O2-SCHED and LMSD_O*-SCHED.
 """
@@ -148,6 +149,27 @@ class _Base:
         restore = (lambda y: y.permute(0, 3, 1, 2)) if tag == "nhwc" else (lambda y: y)
         return outs, restore
 
+    def _x0_quantile(self, eps, x, alphas_cumprod, t):
+        """dynamic thresholding (DDPM / DDIM, scheduling_ddpm.py:381-382): per image the raw dynamic_thresholding_ratio quantile of
+        |x0|, x0 formed inside the quantile kernel exactly as the step kernel then forms it -- one launch ahead of the step's; None
+        when the config has thresholding off.  eps and x are in one of _align's layouts (dimension 0 outermost)."""
+        if not self.config.thresholding:
+            return None
+        return ops.abs_quantile(x, self.config.dynamic_thresholding_ratio, model_output=eps, alphas_cumprod=alphas_cumprod, t=t)
+
+    def _threshold_sample(self, sample):
+        """scheduling_ddpm.py:290-322 / scheduling_ddim.py:203-235 on a device tensor [B,C,H,W]: s = the per-image quantile of |sample|
+        (bd_abs_quantile) clamped to [1, sample_max_value]; clamp(sample, -s, s) / s.  `step` does not come through here (its clamp
+        and division are inside the step kernel); this is the reference's method kept for callers that threshold a tensor of their own."""
+        if not sample.is_cuda:
+            raise RuntimeError(f"{type(self).__name__}._threshold_sample runs on the GPU only")
+        dtype = sample.dtype
+        x = sample if dtype == torch.float32 else sample.float()
+        (x,), restore = self._align(x)
+        s = ops.abs_quantile(x, self.config.dynamic_thresholding_ratio).clamp(min=1, max=self.config.sample_max_value)
+        s = s.view(-1, *([1] * (x.dim() - 1)))
+        return restore(torch.clamp(x, -s, s) / s).to(dtype)
+
     @staticmethod
     def _fits(h, x):
         """a stored buffer can stand beside the sample x in one launch: same shape, layout and device"""
@@ -246,8 +268,6 @@ class DDPMScheduler(_Base):
         # scheduling_ddpm.py:324-420
         if self.config.prediction_type != "epsilon":
             raise ValueError(f"prediction_type given as {self.config.prediction_type} must be `epsilon` on the HIP path")
-        if self.config.thresholding:
-            raise NotImplementedError("dynamic thresholding is not on the BadDiffusion path")
         if not model_output.is_cuda:
             raise RuntimeError("DDPMScheduler.step runs on the GPU only")
         t = int(timestep)
@@ -259,7 +279,8 @@ class DDPMScheduler(_Base):
         _, ac = self.device_tables(model_output.device)
         prev, x0 = ops.ddpm_step(mo, sm, nz, ac, t, prev_t, self.variance_type, self.config.clip_sample,
                                  self.config.clip_sample_range, self.config.clip_defense, self.config.clip_defense_range,
-                                 want_x0=True)
+                                 want_x0=True, x0_quantile=self._x0_quantile(mo, sm, ac, t),
+                                 sample_max_value=self.config.sample_max_value)
         return self._output(prev, restore, return_dict, pred_original_sample=x0)
 
 
@@ -304,8 +325,6 @@ class DDIMScheduler(_Base):
             raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
         if self.config.prediction_type != "epsilon":
             raise ValueError(f"prediction_type given as {self.config.prediction_type} must be `epsilon` on the HIP path")
-        if self.config.thresholding:
-            raise NotImplementedError("dynamic thresholding is not on the BadDiffusion path")
         if use_clipped_model_output:
             raise NotImplementedError("use_clipped_model_output is not on the BadDiffusion path")
         if not model_output.is_cuda:
@@ -322,7 +341,8 @@ class DDIMScheduler(_Base):
         _, ac = self.device_tables(model_output.device)
         prev, x0 = ops.ddim_step(mo, sm, ac, t, prev_t, eta=float(eta), noise=nz, clip_sample=self.config.clip_sample,
                                  clip_sample_range=self.config.clip_sample_range,
-                                 final_alpha_cumprod=float(self.final_alpha_cumprod), want_x0=True)
+                                 final_alpha_cumprod=float(self.final_alpha_cumprod), want_x0=True,
+                                 x0_quantile=self._x0_quantile(mo, sm, ac, t), sample_max_value=self.config.sample_max_value)
         return self._output(prev, restore, return_dict, pred_original_sample=x0)
 
 

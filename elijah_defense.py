@@ -5,7 +5,7 @@
                              [--remove_steps 200] [--batch 64] [--learning_rate 2e-5] [--output_dir DIR] [--tag T] [--seed 0] [--gpu 0]
                              [--clean_source none|synthetic|dataset] [--clean_n 256] [--clean_batch 64] [--clean_weight 1.0]
                              [--clean_target frozen|noise] [--dataset CIFAR10] [--dataset_path datasets]
-                             [--target NAME] [--trigger BOX_14] [--asr_threshold 1e-3]
+                             [--target NAME] [--trigger BOX_14] [--asr_threshold 1e-3] [--dyn_threshold V [--dyn_threshold_ratio 0.995]]
 
 The sibling of anp_defense.py.  Stages (baddiffusion_amd/inversion.py, baddiffusion_amd/defense.py):
   1. invert_trigger: the shift tau the frozen network follows;
@@ -34,8 +34,8 @@ from baddiffusion_amd import defense
 from baddiffusion_amd.inversion import invert_trigger
 from baddiffusion_amd.model import DiffuserModelSched, save_scheduler, save_unet
 from baddiffusion_amd.pipelines import DDIMPipeline, DDPMPipeline, DEISPipeline, DPMSolverPipeline, HeunPipeline, LMSPipeline, UniPCPipeline
-from baddiffusion_amd.schedulers import (DEISMultistepScheduler, DPMSolverMultistepScheduler, HeunDiscreteScheduler, LMSDiscreteScheduler,
-                                          UniPCMultistepScheduler)
+from baddiffusion_amd.schedulers import (DDIMScheduler, DDPMScheduler, DEISMultistepScheduler, DPMSolverMultistepScheduler,
+                                          HeunDiscreteScheduler, LMSDiscreteScheduler, UniPCMultistepScheduler)
 
 
 @dataclass
@@ -70,6 +70,8 @@ class Config:
     target: str = None
     trigger: str = "BOX_14"
     asr_threshold: float = None
+    dyn_threshold: float = None
+    dyn_threshold_ratio: float = 0.995
 
 
 SCHED_CHOICES = [DiffuserModelSched.DDIM_SCHED, DiffuserModelSched.DDPM_SCHED] + sorted(DiffuserModelSched._DPM_SCHEDS) + \
@@ -117,9 +119,17 @@ def get_config(argv=None):
     p.add_argument("--asr_threshold", type=float,
                    help="an image counts as a hit when its own MSE to the target is below this (needs --target; default 1e-3 once --target is "
                         "given: this project's choice of a value of the order the papers use, not a finding)")
-    for k, v in vars(p.parse_args(argv)).items():
+    p.add_argument("--dyn_threshold", type=float,
+                   help="score passes with dynamic thresholding of the predicted x0 in place of the fixed clamp: the sample_max_value of the "
+                        "sampling scheduler (DDIM-SCHED / DDPM-SCHED only)")
+    p.add_argument("--dyn_threshold_ratio", type=float, help="the quantile of --dyn_threshold (0.995)")
+    args = p.parse_args(argv)
+    if args.dyn_threshold_ratio is not None and args.dyn_threshold is None:
+        p.error("--dyn_threshold_ratio needs --dyn_threshold")
+    for k, v in vars(args).items():
         if v is not None:
             setattr(config, k, v)
+    DiffuserModelSched._check_dyn_threshold(config.sched, config.dyn_threshold, config.dyn_threshold_ratio)
     if config.clean_source == "dataset" and config.dataset is None:
         p.error("--clean_source dataset needs --dataset")
     if config.target is None and config.asr_threshold is not None:
@@ -149,6 +159,11 @@ def make_pipeline(config, model, noise_sched):
         if cls_name == "HeunDiscreteScheduler":
             return HeunPipeline(unet=model, scheduler=HeunDiscreteScheduler.from_config(noise_sched.config))
         return LMSPipeline(unet=model, scheduler=LMSDiscreteScheduler.from_config(noise_sched.config), order=order)
+    if config.dyn_threshold is not None:
+        # a sampling scheduler of its own: the checkpoint's scheduler, which is saved back with the repaired model, keeps its config
+        cls = DDIMScheduler if config.sched == DiffuserModelSched.DDIM_SCHED else DDPMScheduler
+        noise_sched = cls(**noise_sched.config)
+        DiffuserModelSched._set_dyn_threshold(noise_sched, config.dyn_threshold, config.dyn_threshold_ratio)
     return (DDIMPipeline if config.sched == DiffuserModelSched.DDIM_SCHED else DDPMPipeline)(unet=model, scheduler=noise_sched)
 
 
@@ -251,6 +266,8 @@ def main(argv=None):
     if target is not None:
         print(f"ASR (MSE to {config.target} < {config.asr_threshold:g}) before -> after: {result['before']['asr_trigger']:.4f} -> "
               f"{result['after']['asr_trigger']:.4f}")
+    if config.dyn_threshold is not None:
+        result["dyn_threshold"], result["dyn_threshold_ratio"] = float(config.dyn_threshold), float(config.dyn_threshold_ratio)
     with open(os.path.join(config.output_dir, config.score_file), "w") as f:
         json.dump(result, f, indent=2)
     save_model(config, model, noise_sched)

@@ -98,6 +98,11 @@ typedef struct {
     int variance_type;            /* 0 fixed_small, 1 fixed_large                              */
     int clip_sample; float clip_sample_range;
     int clip_defense; float clip_defense_range;
+    /* dynamic thresholding (scheduling_ddpm.py:290-322): NULL = off, and the step is bit for bit what it was.  Set: [n / image_elems]
+     * raw quantiles of |x0| per image (bd_abs_quantile); element i belongs to image i / image_elems, s = clamp(q, 1, sample_max_value)
+     * (a NaN quantile stays NaN), x0 = clamp(x0, -s, s) / s, clip_sample is ignored (the reference's if / elif), pred_original is the
+     * thresholded value and clip_defense still applies to prev_sample.  Needs n % image_elems == 0 and n < 2^31. */
+    const float* x0_quantile; int64_t image_elems; float sample_max_value;
 } bd_ddpm_step_desc;
 int bd_ddpm_step(const bd_ddpm_step_desc* d, bd_stream_t stream);
 
@@ -108,8 +113,48 @@ typedef struct {
     const float* alphas_cumprod;
     int t, prev_t; float final_alpha_cumprod; float eta;
     int clip_sample; float clip_sample_range;
+    const float* x0_quantile; int64_t image_elems; float sample_max_value;   /* as in bd_ddpm_step_desc (scheduling_ddim.py:203-235) */
 } bd_ddim_step_desc;
 int bd_ddim_step(const bd_ddim_step_desc* d, bd_stream_t stream);
+
+/* Dynamic thresholding's order statistic: out[b] = torch.quantile(|v_b|, q, interpolation="linear") in fp32, bit for bit, over B images
+ * of m values each, image-major and dense (any order inside an image).  v is `x` as it is (model_output NULL), or the predicted
+ * x0 = (x - sqrt(1 - a_t) * model_output) / sqrt(a_t), a_t = alphas_cumprod[t], formed on the fly by the device helper the DDPM and
+ * DDIM step kernels call, so the value ranked is bitwise the value the step then clamps.
+ *   rank = q * (float)(m - 1) in fp32; lo = floor(rank), w = rank - lo; a, b = the order statistics at lo and ceil(rank);
+ *   d = b - a; out = w < 0.5 ? fmaf(w, d, a) : fmaf(-d, 1 - w, b).
+ * Exact and deterministic: a radix select over the 31 value bits of |v| in three passes (11 / 10 / 10 bits) of integer LDS histograms;
+ * one workgroup per image.  A NaN anywhere in an image gives NaN; two infinities around the rank give NaN through d; -0 ranks as 0;
+ * denormals are ordinary values.  The result is NOT yet clamped to [1, sample_max_value].  No alignment is asked of x, model_output
+ * or m.  Rejected (status < 0, bd_last_error, nothing written): null x / out, B <= 0, m <= 0, B * m >= 2^31, q outside [0, 1] or NaN,
+ * model_output without a table or t outside [0, n_alphas), workspace_bytes < bd_abs_quantile_workspace_bytes(B, m) (0 for both paths
+ * of today: workspace may then be NULL). */
+typedef struct {
+    int B; int64_t m;
+    const float* x;                 /* [B, m] values, or the sample when model_output is set                        */
+    const float* model_output;      /* [B, m] or NULL                                                               */
+    const float* alphas_cumprod; int n_alphas; int t;   /* read only with model_output                              */
+    float q;
+    float* out;                     /* [B]                                                                          */
+    void* workspace; size_t workspace_bytes;
+} bd_abs_quantile_desc;
+size_t bd_abs_quantile_workspace_bytes(int B, int64_t m);
+int bd_abs_quantile(const bd_abs_quantile_desc* d, bd_stream_t stream);
+/* Which path a (B, m) takes: host code only, the plan the launcher itself reads (same checks of B and m, same messages). */
+enum bd_abs_quantile_path {
+    BD_AQ_REGISTERS = 0,            /* m <= 4096: 256 threads hold the image in registers, the data is read once    */
+    BD_AQ_STREAM = 1                /* larger m: 1024 threads read the image again in every pass                    */
+};
+typedef struct {
+    int path;                       /* enum bd_abs_quantile_path                                                    */
+    int workgroups;                 /* = B: one per image                                                           */
+    int threads;                    /* per workgroup                                                                */
+    int values_per_thread;          /* register slots per thread (BD_AQ_REGISTERS), ceil(m / threads) loads per pass (BD_AQ_STREAM) */
+    int passes;                     /* radix passes: 3                                                              */
+    int64_t switch_m;               /* the largest m of BD_AQ_REGISTERS                                             */
+    size_t workspace_bytes;
+} bd_abs_quantile_plan_info;
+int bd_abs_quantile_plan(int B, int64_t m, bd_abs_quantile_plan_info* out);
 
 /* f-4: out = clamp?(sum_j coeffs[j] * terms[j]) over k <= BD_LINCOMB_MAX dense fp32 tensors of n elements (one common
  * layout; `terms` / `coeffs` are HOST arrays read at call time).  All PRK / PLMS updates of PNDMScheduler

@@ -84,7 +84,14 @@ def get_config(argv=None):
     p.add_argument("--output_dir", "-od", type=str)
     p.add_argument("--seed", type=int, default=config.seed)
     p.add_argument("--gpu", "-g", type=str, default=config.gpu)
-    for k, v in vars(p.parse_args(argv)).items():
+    p.add_argument("--dyn_threshold", type=float, help="refused: see --help of baddiffusion.py; RePaint has no dynamic thresholding")
+    p.add_argument("--dyn_threshold_ratio", type=float, help="refused with --dyn_threshold")
+    args = p.parse_args(argv)
+    if args.dyn_threshold is not None or args.dyn_threshold_ratio is not None:
+        # the flag of baddiffusion.py and elijah_defense.py is known here so that a shared command line fails with the reason
+        raise NotImplementedError("--dyn_threshold: inpainting samples through RePaintScheduler, which has no dynamic thresholding in the "
+                                  "reference and none here; it runs in the DDPM and DDIM steps only (--fclip's fixed clamp applies)")
+    for k, v in vars(args).items():
         if v is not None:
             setattr(config, k, v)
     if config.n < 1 or config.batch < 1:
