@@ -45,7 +45,8 @@ SCHED_CHOICES = ["DDPM-SCHED", "DDIM-SCHED", "DPM_SOLVER_PP_O1-SCHED", "DPM_SOLV
                  "DPM_SOLVER_O2-SCHED", "DPM_SOLVER_PP_O3-SCHED", "DPM_SOLVER_O3-SCHED", "UNIPC-SCHED", "PNDM-SCHED", "DEIS-SCHED",
                  "HEUN-SCHED", "SCORE-SDE-VE-SCHED", "UNIPC_O1-SCHED", "UNIPC_O2-SCHED", "UNIPC_O3-SCHED",
                  "HEUN_O2-SCHED", "LMSD_O1-SCHED", "LMSD_O2-SCHED", "LMSD_O3-SCHED", "LMSD_O4-SCHED",
-                 "DEIS_O1-SCHED", "DEIS_O2-SCHED", "DEIS_O3-SCHED"]
+                 "DEIS_O1-SCHED", "DEIS_O2-SCHED", "DEIS_O3-SCHED",
+                 "EULER_O1-SCHED", "EULER_A_O1-SCHED", "KDPM2_O2-SCHED", "KDPM2_A_O2-SCHED"]
 
 
 def parse_args(argv=None):
@@ -85,7 +86,11 @@ def parse_args(argv=None):
                         "(UniPCMultistepScheduler + UniPCPipeline, solver order 1-3), which need no --native_sched; so do the sigma-space "
                         "samplers, HEUN_O2-SCHED (HeunDiscreteScheduler + HeunPipeline) and LMSD_O1-SCHED ... LMSD_O4-SCHED "
                         "(LMSDiscreteScheduler + LMSPipeline at that order), and DEIS, DEIS_O1-SCHED / DEIS_O2-SCHED / DEIS_O3-SCHED "
-                        "(DEISMultistepScheduler + DEISPipeline, solver order 1-3, the reference's coefficient arithmetic)")
+                        "(DEISMultistepScheduler + DEISPipeline, solver order 1-3, the reference's coefficient arithmetic), and the "
+                        "stochastic sigma-space samplers with KDPM2: EULER_O1-SCHED (EulerDiscreteScheduler + EulerPipeline), "
+                        "EULER_A_O1-SCHED (EulerAncestralDiscreteScheduler + EulerAncestralPipeline), KDPM2_O2-SCHED "
+                        "(KDPM2DiscreteScheduler + KDPM2Pipeline) and KDPM2_A_O2-SCHED (KDPM2AncestralDiscreteScheduler + "
+                        "KDPM2AncestralPipeline)")
     p.add_argument("--infer_steps", type=int, help="sampling steps of the pipeline (default: the pipeline's own)")
     p.add_argument("--dyn_threshold", type=float,
                    help="sample with dynamic thresholding of the predicted x0 (Imagen) in place of --fclip's fixed clamp: per image s = the "

@@ -97,6 +97,12 @@ class SigmaStepDesc(C.Structure):
                 ("c0", f32), ("c1", f32), ("c2", f32), ("c3", f32), ("in_div", f32), ("clip", i32), ("clip_range", f32)]
 
 
+class SigmaNoiseStepDesc(C.Structure):
+    _fields_ = [("n", i64), ("model_output", vp), ("sample", vp), ("noise", vp), ("base", vp), ("x0_out", vp), ("prev_out", vp),
+                ("scaled_out", vp), ("sigma_in", f32), ("dt", f32), ("churn", i32), ("s_noise", f32), ("churn_mul", f32),
+                ("up", i32), ("sigma_up", f32), ("in_div", f32), ("clip", i32), ("clip_range", f32)]
+
+
 class GnFwdDesc(C.Structure):
     _fields_ = [("B", i32), ("HW", i32), ("C", i32), ("G", i32), ("eps", f32), ("silu", i32),
                 ("x", vp), ("ldx", i64), ("gamma", vp), ("beta", vp), ("y", vp), ("ldy", i64),
@@ -260,6 +266,7 @@ SIGNATURES = {
     "bd_unipc_step": (i32, [C.POINTER(UnipcStepDesc), vp]),
     "bd_deis_step": (i32, [C.POINTER(DeisStepDesc), vp]),
     "bd_sigma_step": (i32, [C.POINTER(SigmaStepDesc), vp]),
+    "bd_sigma_noise_step": (i32, [C.POINTER(SigmaNoiseStepDesc), vp]),
     "bd_scale_input": (i32, [vp, i64, f32, f32, vp, vp]),
     "bd_timestep_embedding_f32": (i32, [vp, i32, i32, i32, i32, f32, vp, vp]),
     "bd_unet_forward_tf": (i32, [vp, i32, i32, vp, vp, i64, vp, i32, vp, i64, vp, sz, vp]),

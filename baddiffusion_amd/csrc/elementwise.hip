@@ -927,11 +927,23 @@ static void deis_launch(const bd_deis_step_desc& d, hipStream_t stream) {
 // is what makes the launch worth fusing: every UNet evaluation of these samplers reads x / sqrt(sigma^2 + 1).  The optional inputs are
 // template parameters as in UnipcOp (every load one unconditional 16-byte access); NH counts the history terms of the sum
 // (AVG reads h1 for the average and has none).
+// the two ends every sigma-space element shares (bd_sigma_step, bd_sigma_noise_step): x0 and the derivative, and the closing scale
+// into the model's coordinates with the optional clamp there
+__device__ __forceinline__ void sigma_deriv(float sigma_in, float e, float x, float& x0, float& dv) {
+    x0 = x - sigma_in * e;
+    dv = (x - x0) / sigma_in;
+}
+__device__ __forceinline__ void sigma_scale(float in_div, int clip, float clip_range, float& prev, float& sc) {
+    sc = prev / in_div;
+    if (clip) {
+        sc = fminf(fmaxf(sc, -clip_range), clip_range);
+        prev = sc * in_div;
+    }
+}
 template <bool AVG, int NH>
 __device__ __forceinline__ void sigma_elem(const bd_sigma_step_desc& d, float e, float x, float b, float h1, float h2, float h3, float& x0,
                                            float& dv, float& prev, float& sc) {
-    x0 = x - d.sigma_in * e;
-    dv = (x - x0) / d.sigma_in;
+    sigma_deriv(d.sigma_in, e, x, x0, dv);
     float dd = dv;
     if constexpr (AVG) dd = (h1 + dv) / 2.0f;
     float acc = d.c0 * dd;
@@ -939,11 +951,7 @@ __device__ __forceinline__ void sigma_elem(const bd_sigma_step_desc& d, float e,
     if constexpr (!AVG && NH >= 2) acc += d.c2 * h2;
     if constexpr (!AVG && NH >= 3) acc += d.c3 * h3;
     prev = b + acc;
-    sc = prev / d.in_div;
-    if (d.clip) {
-        sc = fminf(fmaxf(sc, -d.clip_range), d.clip_range);
-        prev = sc * d.in_div;
-    }
+    sigma_scale(d.in_div, d.clip, d.clip_range, prev, sc);
 }
 template <bool AVG, int NH, bool BASE>
 struct SigmaOp {
@@ -970,6 +978,48 @@ static void sigma_launch(const bd_sigma_step_desc& d, hipStream_t stream) {
     const dim3 grid(nblocks(cdiv(d.n, 4), TPB, 4096));
     if (d.base) hipLaunchKernelGGL((vec4_kernel<SigmaOp<AVG, NH, true>>), grid, dim3(TPB), 0, stream, SigmaOp<AVG, NH, true>{d}, d.n / 4, d.n);
     else hipLaunchKernelGGL((vec4_kernel<SigmaOp<AVG, NH, false>>), grid, dim3(TPB), 0, stream, SigmaOp<AVG, NH, false>{d}, d.n / 4, d.n);
+}
+
+// f-4 (the stochastic sigma-space samplers: scheduling_euler_discrete.py:257-354 with churn, scheduling_euler_ancestral_discrete.py:193-281,
+// the second stage of scheduling_k_dpm_2_ancestral_discrete.py:243-329): bd_sigma_step's first order transition with a noise term in
+// front of it (Euler's churn raises the sample to sigma_hat before anything reads it) or behind it (the ancestral noise lands on the
+// updated sample before it is scaled for the next evaluation) -- neither can ride in bd_sigma_step, whose scale follows its update
+// directly.  MODE: 0 no noise term (the noise buffer is not read), 1 churn, 2 up.
+template <int MODE>
+__device__ __forceinline__ void sigma_noise_elem(const bd_sigma_noise_step_desc& d, float e, float x, float z, float b, bool has_base, float& x0,
+                                                 float& prev, float& sc) {
+    float xh = x;
+    if constexpr (MODE == 1) xh = x + (z * d.s_noise) * d.churn_mul;
+    float dv;
+    sigma_deriv(d.sigma_in, e, xh, x0, dv);
+    prev = (has_base ? b : xh) + dv * d.dt;
+    if constexpr (MODE == 2) prev = prev + z * d.sigma_up;
+    sigma_scale(d.in_div, d.clip, d.clip_range, prev, sc);
+}
+template <int MODE, bool BASE>
+struct SigmaNoiseOp {
+    bd_sigma_noise_step_desc d;
+    template <class V> __device__ __forceinline__ void at(int64_t i) const {
+        V e = ld<V>(d.model_output, i), x = ld<V>(d.sample, i);
+        V z = splat<V>(0.f), b = x;
+        if constexpr (MODE != 0) z = ld<V>(d.noise, i);
+        if constexpr (BASE) b = ld<V>(d.base, i);
+        V x0, p, sc;
+        lanes([this](float e, float x, float z, float b, float& x0, float& p, float& sc) {
+            sigma_noise_elem<MODE>(d, e, x, z, b, BASE, x0, p, sc);
+        }, e, x, z, b, x0, p, sc);
+        if (d.x0_out) st<V>(d.x0_out, i, x0);
+        st<V>(d.prev_out, i, p);
+        if (d.scaled_out) st<V>(d.scaled_out, i, sc);
+    }
+};
+// the launch shape of the vec4 driver: a thread per float4, at most 4096 blocks (the loop strides over the rest)
+static dim3 vec4_grid(int64_t elems) { return dim3(nblocks(cdiv(elems, 4), TPB, 4096)); }
+template <int MODE>
+static void sigma_noise_launch(const bd_sigma_noise_step_desc& d, hipStream_t stream) {
+    const dim3 grid = vec4_grid(d.n);
+    if (d.base) hipLaunchKernelGGL((vec4_kernel<SigmaNoiseOp<MODE, true>>), grid, dim3(TPB), 0, stream, SigmaNoiseOp<MODE, true>{d}, d.n / 4, d.n);
+    else hipLaunchKernelGGL((vec4_kernel<SigmaNoiseOp<MODE, false>>), grid, dim3(TPB), 0, stream, SigmaNoiseOp<MODE, false>{d}, d.n / 4, d.n);
 }
 
 // out = (x * mul) / div: the start of a sigma-space chain (init * init_noise_sigma, then / sqrt(sigma_0^2 + 1)) and the public
@@ -1267,6 +1317,32 @@ extern "C" int bd_sigma_step(const bd_sigma_step_desc* d, bd_stream_t stream) {
     else if (d->h1) sigma_launch<false, 1>(*d, S(stream));
     else sigma_launch<false, 0>(*d, S(stream));
     BD_LAUNCH_CHECK("sigma_step");
+    return BD_OK;
+}
+extern "C" int bd_sigma_noise_step(const bd_sigma_noise_step_desc* d, bd_stream_t stream) {
+    BD_CHECK(d, BD_ERR_INVALID, "bd_sigma_noise_step: null descriptor");
+    BD_CHECK(d->n > 0, BD_ERR_INVALID, "bd_sigma_noise_step: n=%lld must be positive", (long long)d->n);
+    BD_CHECK(d->model_output && d->sample && d->noise && d->prev_out, BD_ERR_INVALID,
+             "bd_sigma_noise_step: null pointer (model_output, sample, noise and prev_out are required)");
+    BD_CHECK(d->sigma_in > 0.f, BD_ERR_INVALID, "bd_sigma_noise_step: sigma_in=%g must be positive", (double)d->sigma_in);
+    BD_CHECK(d->in_div > 0.f, BD_ERR_INVALID, "bd_sigma_noise_step: in_div=%g must be positive", (double)d->in_div);
+    BD_CHECK(d->sigma_up >= 0.f, BD_ERR_INVALID, "bd_sigma_noise_step: sigma_up=%g must not be negative", (double)d->sigma_up);
+    BD_CHECK(!(d->churn && d->up), BD_ERR_INVALID, "bd_sigma_noise_step: churn together with up (no sampler has both noise terms)");
+    BD_CHECK(!d->churn || d->churn_mul > 0.f, BD_ERR_INVALID, "bd_sigma_noise_step: churn with churn_mul=%g, which must be positive",
+             (double)d->churn_mul);
+    const StepBuf in[4] = {{d->model_output, "model_output"}, {d->sample, "sample"}, {d->noise, "noise"}, {d->base, "base"}};
+    const StepBuf out[3] = {{d->prev_out, "prev_out"}, {d->x0_out, "x0_out"}, {d->scaled_out, "scaled_out"}};
+    // step_buffers_check lets any output be any input's own buffer; here only prev_out == sample is
+    for (int o = 0; o < 3; ++o)
+        for (int j = 0; j < 4; ++j)
+            BD_CHECK(!out[o].p || out[o].p != in[j].p || (o == 0 && out[o].p == d->sample), BD_ERR_INVALID,
+                     "bd_sigma_noise_step: %s is the buffer of %s (only prev_out may be an input's buffer, and only sample's)", out[o].name,
+                     in[j].name);
+    BD_TRY(step_buffers_check("bd_sigma_noise_step", d->n, in, 4, out, 3));
+    if (d->churn) sigma_noise_launch<1>(*d, S(stream));
+    else if (d->up) sigma_noise_launch<2>(*d, S(stream));
+    else sigma_noise_launch<0>(*d, S(stream));
+    BD_LAUNCH_CHECK("sigma_noise_step");
     return BD_OK;
 }
 extern "C" int bd_scale_input(const float* x, int64_t n, float mul, float div, float* out, bd_stream_t stream) {

@@ -15,9 +15,12 @@ from typing import Union
 import numpy as np
 import torch
 
-from .pipelines import DDIMPipeline, DDPMPipeline, DEISPipeline, DPMSolverPipeline, HeunPipeline, LMSPipeline, PNDMPipeline, UniPCPipeline
-from .schedulers import (DDIMScheduler, DDPMScheduler, DEISMultistepScheduler, DPMSolverMultistepScheduler, HeunDiscreteScheduler,
-                         LMSDiscreteScheduler, PNDMScheduler, RePaintScheduler, SchedulerConfigCarrier, UniPCMultistepScheduler)
+from .pipelines import (DDIMPipeline, DDPMPipeline, DEISPipeline, DPMSolverPipeline, EulerAncestralPipeline, EulerPipeline, HeunPipeline,
+                        KDPM2AncestralPipeline, KDPM2Pipeline, LMSPipeline, PNDMPipeline, UniPCPipeline)
+from .schedulers import (DDIMScheduler, DDPMScheduler, DEISMultistepScheduler, DPMSolverMultistepScheduler,
+                         EulerAncestralDiscreteScheduler, EulerDiscreteScheduler, HeunDiscreteScheduler, KDPM2AncestralDiscreteScheduler,
+                         KDPM2DiscreteScheduler, LMSDiscreteScheduler, PNDMScheduler, RePaintScheduler, SchedulerConfigCarrier,
+                         UniPCMultistepScheduler)
 from .unet import UNet2DModel
 
 WEIGHTS_NAME = "diffusion_pytorch_model.bin"
@@ -87,7 +90,9 @@ def load_scheduler(directory):
     cls = {"DDPMScheduler": DDPMScheduler, "DDIMScheduler": DDIMScheduler,
            "RePaintScheduler": RePaintScheduler, "DPMSolverMultistepScheduler": DPMSolverMultistepScheduler,
            "UniPCMultistepScheduler": UniPCMultistepScheduler, "HeunDiscreteScheduler": HeunDiscreteScheduler,
-           "LMSDiscreteScheduler": LMSDiscreteScheduler, "DEISMultistepScheduler": DEISMultistepScheduler}.get(cfg.get("_class_name", "DDPMScheduler"))
+           "LMSDiscreteScheduler": LMSDiscreteScheduler, "DEISMultistepScheduler": DEISMultistepScheduler,
+           "EulerDiscreteScheduler": EulerDiscreteScheduler, "EulerAncestralDiscreteScheduler": EulerAncestralDiscreteScheduler,
+           "KDPM2DiscreteScheduler": KDPM2DiscreteScheduler, "KDPM2AncestralDiscreteScheduler": KDPM2AncestralDiscreteScheduler}.get(cfg.get("_class_name", "DDPMScheduler"))
     if cls is None:
         raise NotImplementedError(f"scheduler {cfg.get('_class_name')} is not on the BadDiffusion hot path")
     return cls(**{k: v for k, v in cfg.items() if not k.startswith("_")})
@@ -279,6 +284,12 @@ class DiffuserModelSched:
     _SIGMA_SCHEDS = {"HEUN_O2-SCHED": ("HeunDiscreteScheduler", 2), "LMSD_O1-SCHED": ("LMSDiscreteScheduler", 1),
                      "LMSD_O2-SCHED": ("LMSDiscreteScheduler", 2), "LMSD_O3-SCHED": ("LMSDiscreteScheduler", 3),
                      "LMSD_O4-SCHED": ("LMSDiscreteScheduler", 4)}
+    # Euler, Euler-ancestral, KDPM2 and KDPM2-ancestral (the reference's model.py names none of them), with or without native_sched --
+    # value = (scheduler class, pipeline class)
+    _KDIFF_SCHEDS = {"EULER_O1-SCHED": ("EulerDiscreteScheduler", "EulerPipeline"),
+                     "EULER_A_O1-SCHED": ("EulerAncestralDiscreteScheduler", "EulerAncestralPipeline"),
+                     "KDPM2_O2-SCHED": ("KDPM2DiscreteScheduler", "KDPM2Pipeline"),
+                     "KDPM2_A_O2-SCHED": ("KDPM2AncestralDiscreteScheduler", "KDPM2AncestralPipeline")}
     # named in model.py:556-563 but not handled by its __get_model_sched either (it raises NotImplementedError)
     _OTHER_SCHEDS = ("LDM-SCHED", "SCORE-SDE-VE-SCHED", "EDM-VE-SCHED", "EDM-VE-ODE-SCHED", "EDM-VE-SDE-SCHED")
     _HUB = {DDPM_CIFAR10_32: "google/ddpm-cifar10-32", DDPM_CELEBA_HQ_256: "google/ddpm-ema-celebahq-256",
@@ -376,6 +387,12 @@ class DiffuserModelSched:
             else:
                 noise_sched = LMSDiscreteScheduler(**kw)
                 get_pipeline = DiffuserModelSched._pipeline_generator(partial(LMSPipeline, clip_sample=clip_used, order=order))
+        elif noise_sched_type in DiffuserModelSched._KDIFF_SCHEDS:
+            sched_cls, pipe_cls = DiffuserModelSched._KDIFF_SCHEDS[noise_sched_type]
+            noise_sched = {c.__name__: c for c in (EulerDiscreteScheduler, EulerAncestralDiscreteScheduler, KDPM2DiscreteScheduler,
+                                                   KDPM2AncestralDiscreteScheduler)}[sched_cls](**kw)
+            pipe_cls = {c.__name__: c for c in (EulerPipeline, EulerAncestralPipeline, KDPM2Pipeline, KDPM2AncestralPipeline)}[pipe_cls]
+            get_pipeline = DiffuserModelSched._pipeline_generator(partial(pipe_cls, clip_sample=clip_used))
         elif native_sched and noise_sched_type in DiffuserModelSched._DPM_SCHEDS:
             order, algorithm = DiffuserModelSched._DPM_SCHEDS[noise_sched_type]
             noise_sched = DPMSolverMultistepScheduler(solver_order=order, algorithm_type=algorithm, **kw)

@@ -865,6 +865,27 @@ def sigma_step(model_output, sample, sigma_in, c0, in_div, base=None, average=Fa
     return out
 
 
+def sigma_noise_step(model_output, sample, noise, sigma_in, dt, in_div, base=None, churn=None, sigma_up=None, clip=None, x0_out=None,
+                     scaled_out=None, out=None):
+    """One first order transition of a stochastic sigma-space sampler (bd_sigma_noise_step, formula in include/bd_hip.h) over dense
+    float32 GPU tensors of one shape and layout.  churn: None or (s_noise, churn_mul), Euler's churn -- the sample is raised by
+    (noise * s_noise) * churn_mul before anything reads it; sigma_up: None or the factor of the ancestral noise added to the updated
+    sample (0.0 is a value: the last step of a chain); at most one of the two.  base: the sample the update starts from (KDPM2's
+    second stage) or None.  in_div / clip / x0_out / scaled_out as in sigma_step.  out may be `sample`: the library refuses any other
+    overlap.  Returns prev_sample."""
+    lib = L.load(); _need_cuda(model_output, sample, noise, base, x0_out, scaled_out, out)
+    out = _dense_out("sigma_noise_step", sample, (model_output, noise, base, x0_out, scaled_out), out)
+    clip_on, clip_range = _clip_pair(clip)
+    s_noise, churn_mul = (1.0, 0.0) if churn is None else churn
+    d = L.SigmaNoiseStepDesc(n=sample.numel(), model_output=L.ptr(model_output), sample=L.ptr(sample), noise=L.ptr(noise),
+                             base=L.ptr(base), x0_out=L.ptr(x0_out), prev_out=L.ptr(out), scaled_out=L.ptr(scaled_out),
+                             sigma_in=float(sigma_in), dt=float(dt), churn=int(churn is not None), s_noise=float(s_noise),
+                             churn_mul=float(churn_mul), up=int(sigma_up is not None), sigma_up=float(sigma_up or 0.0),
+                             in_div=float(in_div), clip=clip_on, clip_range=clip_range)
+    L.check(lib.bd_sigma_noise_step(C.byref(d), L.stream()), "bd_sigma_noise_step")
+    return out
+
+
 def scale_input(x, mul, div, out=None):
     """out = (x * mul) / div (bd_scale_input) over a dense float32 GPU tensor; out may be x."""
     lib = L.load(); _need_cuda(x, out)

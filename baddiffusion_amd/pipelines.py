@@ -1,7 +1,8 @@
 """DDPMPipeline / DDIMPipeline -- drop-in for the two (locally modified) pipelines BadDiffusion samples with
 (diffusers/src/diffusers/pipelines/ddpm/pipeline_ddpm.py:46-125, pipelines/ddim/pipeline_ddim.py:50-142 of the reference tree),
 including the repo's additions `init=`, `save_every_step=`, `start_from=` and the `.movie` output -- and the pipelines of the other
-samplers: PNDM, DPM-Solver(++), UniPC, DEIS (_MultistepPipeline), Heun, LMS (_SigmaPipeline) and RePaint.
+samplers: PNDM, DPM-Solver(++), UniPC, DEIS (_MultistepPipeline), Heun, LMS, Euler, Euler-ancestral, KDPM2, KDPM2-ancestral
+(_SigmaPipeline) and RePaint.
 
 Loop body = one UNet forward (bd_unet_forward) + one fused scheduler step kernel; the image never leaves the
 GPU until the final (x/2+0.5).clamp(0,1) -> NHWC conversion (bd_to_image).  With a CPU `generator` the
@@ -16,7 +17,9 @@ import torch
 
 from . import ops
 from .schedulers import (DDIMScheduler, PNDMScheduler, DDPMScheduler, DEISMultistepScheduler, DPMSolverMultistepScheduler,
-                         HeunDiscreteScheduler, LMSDiscreteScheduler, RePaintScheduler, UniPCMultistepScheduler, randn_tensor)
+                         EulerAncestralDiscreteScheduler, EulerDiscreteScheduler, HeunDiscreteScheduler,
+                         KDPM2AncestralDiscreteScheduler, KDPM2DiscreteScheduler, LMSDiscreteScheduler, RePaintScheduler,
+                         UniPCMultistepScheduler, draw_step_noise, randn_tensor)
 
 
 class ImagePipelineOutput:
@@ -285,11 +288,13 @@ class DEISPipeline(_MultistepPipeline):
 
 
 class _SigmaPipeline(_MultistepPipeline):
-    """The sampling loop of the sigma-space samplers (HeunPipeline, LMSPipeline), with _MultistepPipeline's call surface.  The raw
+    """The sampling loop of the sigma-space samplers (HeunPipeline, LMSPipeline, EulerPipeline, EulerAncestralPipeline, KDPM2Pipeline,
+    KDPM2AncestralPipeline), with _MultistepPipeline's call surface.  The raw
     state is init * init_noise_sigma -- `init` is what the sibling pipelines start from, so noise + trigger is scaled as a whole --
     and the model never sees it: every evaluation reads the scaled buffer x / sqrt(sigma^2 + 1), which `bd_scale_input` produces at
     the start and each `bd_sigma_step` launch afterwards, next to the raw sample.  One UNet forward at a float timestep (uploaded
-    once, fp32) + one fused launch per evaluation; no noise is drawn after the start.  `clip_sample` clamps the scaled buffer (the
+    once, fp32) + one fused launch per evaluation; the deterministic samplers draw no noise after the start, the stochastic ones
+    (`_noise_used`) one tensor per position where the reference draws one.  `clip_sample` clamps the scaled buffer (the
     sample in the coordinates the model sees) and rescales the raw sample to match.  `save_every_step` frames are the scaled
     buffers -- the only ones that are images; the last frame is the final sample, at sigma = 0 where both coincide.  With
     start_from=k the chain enters at position k of `scheduler.timesteps` with an empty history."""
@@ -297,15 +302,33 @@ class _SigmaPipeline(_MultistepPipeline):
     def _step_kwargs(self):
         return {}
 
+    def _set_kwargs(self):
+        """what set_timesteps takes beside the step count: the step's own keywords, unless a subclass says otherwise"""
+        return self._step_kwargs()
+
     def _check_start(self, start_from):
         pass
+
+    def _noise_used(self, position):
+        """None: the sampler draws nothing at this position of `scheduler.timesteps`; True / False: the reference draws a tensor there
+        and the step reads it / drops it"""
+        return None
+
+    def _step_noise(self, position, shape, generator):
+        """{} or {"noise": tensor} for the step at `position`: drawn as the reference draws it (draw_step_noise) in NCHW order, then
+        taken to the NHWC storage the sample lives in, as DDPMPipeline does"""
+        used = self._noise_used(position)
+        if used is None:
+            return {}
+        noise = draw_step_noise(shape, generator, self.device, used)
+        return {} if noise is None else {"noise": ops.nchw_to_nhwc(noise).permute(0, 3, 1, 2)}
 
     def _sample(self, batch_size, num_inference_steps, start_from, generator, output_type, init, save_every_step, return_dict):
         start_from = int(start_from)
         self._check_start(start_from)
-        image, shape = self._start(batch_size, generator, init)
         sched = self.scheduler
-        sched.set_timesteps(num_inference_steps, **self._step_kwargs())
+        sched.set_timesteps(num_inference_steps, **self._set_kwargs())       # a refused step count: before anything is drawn
+        image, shape = self._start(batch_size, generator, init)
         ts_host = [float(t) for t in sched.timesteps[start_from:]]
         ts_dev = torch.as_tensor(ts_host, dtype=torch.float64).to(torch.float32).to(self.device)    # one H2D copy for the whole chain
         clip = float(self.clip_sample_range) if self.clip_sample else None
@@ -317,7 +340,8 @@ class _SigmaPipeline(_MultistepPipeline):
         mov = [self._to_numpy(scaled, shape)] if save_every_step else []
         for i, t in enumerate(self.progress_bar(ts_host)):
             eps = self.unet(scaled.permute(0, 3, 1, 2), ts_dev[i]).sample
-            out = sched.step(eps, t, image.permute(0, 3, 1, 2), clip=clip, scaled=True, **self._step_kwargs())
+            out = sched.step(eps, t, image.permute(0, 3, 1, 2), clip=clip, scaled=True, **self._step_kwargs(),
+                             **self._step_noise(start_from + i, shape, generator))
             image, scaled = out.prev_sample.permute(0, 2, 3, 1), out.scaled_sample.permute(0, 2, 3, 1)
             if save_every_step:
                 mov.append(self._to_numpy(scaled, shape))
@@ -354,6 +378,71 @@ class LMSPipeline(_SigmaPipeline):
 
     def _step_kwargs(self):
         return {"order": self.order}
+
+
+class EulerPipeline(_SigmaPipeline):
+    """Sampling with EulerDiscreteScheduler: _SigmaPipeline's loop.  s_churn / s_noise are Karras et al.'s churn, handed to every
+    `step`: with s_churn == 0 (the default) the chain is the deterministic Euler one, one `bd_sigma_step` per step; with
+    s_churn > 0 every step is one `bd_sigma_noise_step` that first raises the sample to sigma_hat.  The reference draws a noise
+    tensor in every step either way, so with a CPU generator one is drawn (and dropped when unused): the stream, and the next
+    chunk's initial noise, stay the reference's.  num_inference_steps=20 is this project's default."""
+    scheduler_class = EulerDiscreteScheduler
+    default_steps = 20
+
+    def __init__(self, unet, scheduler, clip_sample=False, clip_sample_range=1.0, s_churn=0.0, s_noise=1.0):
+        super().__init__(unet, scheduler, clip_sample=clip_sample, clip_sample_range=clip_sample_range)
+        self.s_churn, self.s_noise = float(s_churn), float(s_noise)
+
+    def _step_kwargs(self):
+        return {"s_churn": self.s_churn, "s_noise": self.s_noise}
+
+    def _set_kwargs(self):
+        return {}
+
+    def _noise_used(self, position):
+        return self.scheduler._plan_scalars(position, s_churn=self.s_churn, s_noise=self.s_noise)["churn"] is not None
+
+    def noise_draws(self, num_inference_steps=None, start_from=0, **kwargs):
+        return (num_inference_steps or self.default_steps) - int(start_from)
+
+
+class EulerAncestralPipeline(_SigmaPipeline):
+    """Sampling with EulerAncestralDiscreteScheduler: _SigmaPipeline's loop, one UNet forward + one `bd_sigma_noise_step` launch per
+    step, one noise tensor per step.  num_inference_steps=20 is this project's default."""
+    scheduler_class = EulerAncestralDiscreteScheduler
+    default_steps = 20
+
+    def _noise_used(self, position):
+        return True
+
+    def noise_draws(self, num_inference_steps=None, start_from=0, **kwargs):
+        return (num_inference_steps or self.default_steps) - int(start_from)
+
+
+class KDPM2Pipeline(_SigmaPipeline):
+    """Sampling with KDPM2DiscreteScheduler: _SigmaPipeline's loop, deterministic.  num_inference_steps=10 is this project's
+    default: 19 UNet evaluations, two per transition but the last.  start_from counts positions of `scheduler.timesteps`
+    (evaluations); an odd one is the second stage of a transition whose first stage was not run, and is refused."""
+    scheduler_class = KDPM2DiscreteScheduler
+    default_steps = 10
+
+    def _check_start(self, start_from):
+        if start_from % 2:
+            raise ValueError(f"{type(self).__name__}: start_from={start_from} is the second stage of a transition whose first stage "
+                             "would be missing; start at an even position")
+
+
+class KDPM2AncestralPipeline(KDPM2Pipeline):
+    """Sampling with KDPM2AncestralDiscreteScheduler: KDPM2Pipeline's loop with a `bd_sigma_noise_step` second stage.  The
+    reference draws a noise tensor at every position, 2N - 1 per chain, and reads the second stages'; with a CPU generator so does
+    this pipeline."""
+    scheduler_class = KDPM2AncestralDiscreteScheduler
+
+    def _noise_used(self, position):
+        return position % 2 == 1
+
+    def noise_draws(self, num_inference_steps=None, start_from=0, **kwargs):
+        return 2 * (num_inference_steps or self.default_steps) - 1 - int(start_from)
 
 
 def with_default_steps(pipeline, num_inference_steps):

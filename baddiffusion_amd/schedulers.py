@@ -9,6 +9,10 @@
   DEISMultistepScheduler
   HeunDiscreteScheduler,                  the sigma-space samplers, on _SigmaScheduler (bd_sigma_step, bd_scale_input)
   LMSDiscreteScheduler
+  EulerDiscreteScheduler,                 the stochastic sigma-space samplers and KDPM2, on _SigmaScheduler too (bd_sigma_step,
+  EulerAncestralDiscreteScheduler,        bd_sigma_noise_step)
+  KDPM2DiscreteScheduler,
+  KDPM2AncestralDiscreteScheduler
 
 _Base holds what they share: the beta tables and their device copies, `from_config` over `_KEYS`, the layout helpers `_align` /
 `_fits`, and the opening (`_begin_step`) and closing (`_output`) of a `step`.
@@ -23,7 +27,8 @@ Only what BadDiffusion exercises is supported: epsilon prediction, linear betas,
 fixed_large variance; anything else raises like the reference does for unknown options.
 Dynamic thresholding (`thresholding=True`, any `sample_max_value`) runs in DDPM and DDIM: bd_abs_quantile ahead of the step launch (`_x0_quantile`).
 DPM-Solver(++) is behind --native_sched, UniPC behind the UNIPC_O*-SCHED names, DEIS behind DEIS_O*-SCHED, Heun and LMS (fractional timesteps, scaled model
-input and initial noise) behind HEUN_O2-SCHED and LMSD_O*-SCHED.
+input and initial noise) behind HEUN_O2-SCHED and LMSD_O*-SCHED, Euler, Euler-ancestral, KDPM2 and KDPM2-ancestral behind EULER_O1-SCHED,
+EULER_A_O1-SCHED, KDPM2_O2-SCHED and KDPM2_A_O2-SCHED.
 """
 import numpy as np
 import torch
@@ -1239,6 +1244,307 @@ class LMSDiscreteScheduler(_SigmaScheduler):
         prev = ops.sigma_step(eps, x, sigma_in, c[0], in_div, h1=hist[0], c1=c[1], h2=hist[1], c2=c[2], h3=hist[2], c3=c[3],
                               d_out=dbuf, scaled_out=sc, clip=clip)
         self._ring = ring + [dbuf] if order > 1 else []
+        return self._output(prev, restore, return_dict, scaled_sample=sc)
+
+
+def _host_stream(generator):
+    """the generator is the reference's: one CPU stream that every `step` call draws from, used or not"""
+    return isinstance(generator, ShardedGenerator) or (generator is not None and generator.device.type == "cpu")
+
+
+def draw_step_noise(shape, generator, device, used):
+    """The noise tensor of one `step` call of a stochastic sigma-space sampler, or None.  The reference draws in every call of Euler,
+    Euler-ancestral and KDPM2-ancestral whether the step reads the noise or not, so with a CPU generator (or a ShardedGenerator) an
+    unused tensor is drawn on the host and dropped -- the stream stays the reference's; with generator=None or a device generator
+    only what is used is drawn, on the device."""
+    if used:
+        return randn_tensor(shape, generator=generator, device=device)
+    if _host_stream(generator):
+        randn_tensor(shape, generator=generator, device="cpu")
+    return None
+
+
+class _NoisySigmaMixin:
+    """`step(..., generator=, noise=)` of the stochastic sigma-space schedulers: the tensor `bd_sigma_noise_step` reads, given or
+    drawn (draw_step_noise), in the sample's layout"""
+
+    def _step_noise(self, noise, generator, model_output, used):
+        if noise is None:
+            noise = draw_step_noise(tuple(model_output.shape), generator, model_output.device, used)
+        if not used:
+            return None
+        if noise.dtype != torch.float32 or not noise.is_cuda:
+            raise TypeError(f"{type(self).__name__}.step: noise must be a float32 GPU tensor")
+        if self._flat(model_output)[1] == "nhwc":          # _align's layout: the model output's
+            q = noise.permute(0, 2, 3, 1)
+            return q if q.is_contiguous() else q.contiguous()
+        return noise.contiguous()
+
+
+class EulerDiscreteScheduler(_NoisySigmaMixin, _SigmaScheduler):
+    """Euler's method in sigma space with Karras et al.'s churn (scheduling_euler_discrete.py:60-354, epsilon prediction, linear sigma
+    interpolation).  gamma = min(s_churn / N, sqrt(2) - 1) inside [s_tmin, s_tmax], else 0.  gamma == 0 is one `bd_sigma_step`
+    launch; gamma > 0 one `bd_sigma_noise_step` launch that first raises the sample to sigma_hat = sigma (gamma + 1) with
+    (noise s_noise) (sigma_hat^2 - sigma^2)^0.5 and then steps from sigma_hat.  As in the reference the model was evaluated at sigma,
+    not at sigma_hat: parity with it is the contract here.  One noise tensor per `step` call on a CPU generator, used or not."""
+    _KEYS = _SigmaScheduler._KEYS + ("interpolation_type", "use_karras_sigmas")
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                 prediction_type="epsilon", interpolation_type="linear", use_karras_sigmas=False, **unused):
+        if interpolation_type != "linear":
+            raise NotImplementedError(f"EulerDiscreteScheduler: interpolation_type={interpolation_type!r} is not on the HIP path (linear only)")
+        if use_karras_sigmas:
+            raise NotImplementedError("EulerDiscreteScheduler: use_karras_sigmas is not on the HIP path")
+        self._init_common(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type)
+        self.config.interpolation_type = interpolation_type
+        self.config.use_karras_sigmas = False
+
+    def _set_tables(self, n):
+        self._finish_tables(*self._interp(n))
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        # scheduling_euler_discrete.py:182-218
+        self._set_tables(num_inference_steps)
+        self.num_inference_steps = num_inference_steps
+
+    def _step_index(self, timestep):
+        return self._positions(timestep)[0]
+
+    def _plan_scalars(self, k, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0):
+        """the scalars of the step at position k, the reference's expressions on fp32 0-dim tensors: sigma_in (= sigma_hat), dt,
+        in_div, and churn = (s_noise, (sigma_hat^2 - sigma^2)^0.5) when gamma > 0, else None"""
+        sigma = self.sigmas[k]
+        gamma = min(s_churn / (len(self.sigmas) - 1), 2 ** 0.5 - 1) if s_tmin <= sigma <= s_tmax else 0.0
+        sigma_hat = sigma * (gamma + 1)
+        churn = (float(s_noise), float((sigma_hat ** 2 - sigma ** 2) ** 0.5)) if gamma > 0 else None
+        return dict(sigma_in=float(sigma_hat), dt=float(self.sigmas[k + 1] - sigma_hat), in_div=self._in_div[k + 1], churn=churn,
+                    sigma_up=None, base=False)
+
+    def step(self, model_output, timestep, sample, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0, generator=None,
+             return_dict=True, noise=None, clip=None, scaled=False):
+        # scheduling_euler_discrete.py:257-354
+        k = self._step_index(timestep)
+        eps, x, restore = self._begin_step(model_output, sample)
+        p = self._plan_scalars(k, s_churn, s_tmin, s_tmax, s_noise)
+        z = self._step_noise(noise, generator, model_output, p["churn"] is not None)
+        sc = torch.empty_like(x) if scaled else None
+        if p["churn"] is None:
+            prev = ops.sigma_step(eps, x, p["sigma_in"], p["dt"], p["in_div"], scaled_out=sc, clip=clip)
+        else:
+            prev = ops.sigma_noise_step(eps, x, z, p["sigma_in"], p["dt"], p["in_div"], churn=p["churn"], scaled_out=sc,
+                                        clip=clip)
+        return self._output(prev, restore, return_dict, scaled_sample=sc)
+
+
+class EulerAncestralDiscreteScheduler(_NoisySigmaMixin, _SigmaScheduler):
+    """Ancestral sampling with Euler steps (scheduling_euler_ancestral_discrete.py:60-281, epsilon prediction): a deterministic Euler
+    step from sigma down to sigma_down < sigma_next, then fresh noise of standard deviation sigma_up, so that the sample lands on
+    sigma_next.  One `bd_sigma_noise_step` launch per step; sigma_up and sigma_down are the reference's expressions on fp32 0-dim
+    tensors."""
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                 prediction_type="epsilon", **unused):
+        self._init_common(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type)
+
+    def _set_tables(self, n):
+        self._finish_tables(*self._interp(n))
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        # scheduling_euler_ancestral_discrete.py:170-191
+        self._set_tables(num_inference_steps)
+        self.num_inference_steps = num_inference_steps
+
+    def _step_index(self, timestep):
+        return self._positions(timestep)[0]
+
+    def _plan_scalars(self, k):
+        """sigma_in, dt = sigma_down - sigma, in_div and sigma_up of the step at position k"""
+        sigma_from, sigma_to = self.sigmas[k], self.sigmas[k + 1]
+        sigma_up = (sigma_to ** 2 * (sigma_from ** 2 - sigma_to ** 2) / sigma_from ** 2) ** 0.5
+        sigma_down = (sigma_to ** 2 - sigma_up ** 2) ** 0.5
+        return dict(sigma_in=float(sigma_from), dt=float(sigma_down - sigma_from), in_div=self._in_div[k + 1], churn=None,
+                    sigma_up=float(sigma_up), base=False)
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict=True, noise=None, clip=None, scaled=False):
+        # scheduling_euler_ancestral_discrete.py:193-281
+        k = self._step_index(timestep)
+        eps, x, restore = self._begin_step(model_output, sample)
+        p = self._plan_scalars(k)
+        z = self._step_noise(noise, generator, model_output, True)
+        sc = torch.empty_like(x) if scaled else None
+        prev = ops.sigma_noise_step(eps, x, z, p["sigma_in"], p["dt"], p["in_div"], sigma_up=p["sigma_up"], scaled_out=sc,
+                                    clip=clip)
+        return self._output(prev, restore, return_dict, scaled_sample=sc)
+
+
+class _KDPM2Base(_SigmaScheduler):
+    """What KDPM2 and KDPM2-ancestral share (DPM-Solver-2 of Karras et al. in sigma space): a transition is two calls of `step`, a
+    first order stage from sigma to an interpolated sigma_interpol, which keeps the sample it started from, and a second stage that
+    takes the derivative there and steps from the kept sample over the whole interval.  `timesteps` has 2N - 1 entries -- the N
+    of the schedule with the fractional sigma_to_t(sigma_interpol) between them -- and the last is a first order stage to
+    sigma_interpol = 0, so a finished chain leaves its stage pending; set_timesteps resets it.  The flat tables `sigmas`,
+    `sigmas_interpol` (and the ancestral ones) have the reference's layout: the first entry once, every later one twice, the last
+    once more.  Entries of `timesteps` may be equal (KDPM2-ancestral's sigma_interpol is sigma_next to within rounding): a timestep
+    resolves to its last position in the first order state and to its first otherwise, and `step` checks the state against the
+    position's parity."""
+
+    def _init_kdpm2(self, num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type):
+        self._init_common(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type)
+
+    @staticmethod
+    def _twice(v):
+        return torch.cat([v[:1], v[1:].repeat_interleave(2), v[-1:]])
+
+    def _sigma_to_t(self, sigma, log_sigmas):
+        """the (fractional) training timestep whose sigma is `sigma`, by linear interpolation in log sigma over the training table;
+        fp32 throughout, as the reference computes it"""
+        log_sigma = sigma.log()
+        below = (log_sigma - log_sigmas[:, None]).ge(0)
+        low_idx = below.cumsum(dim=0).argmax(dim=0).clamp(max=log_sigmas.shape[0] - 2)
+        high_idx = low_idx + 1
+        low, high = log_sigmas[low_idx], log_sigmas[high_idx]
+        w = ((low - log_sigma) / (low - high)).clamp(0, 1)
+        return ((1 - w) * low_idx + w * high_idx).view(sigma.shape)
+
+    def _base_tables(self, n):
+        """(timesteps float64 tensor [n], sigmas fp32 tensor [n + 1], log of the training sigmas fp32)"""
+        timesteps, sigmas = self._interp(n)
+        train = (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).numpy()
+        return torch.from_numpy(timesteps), torch.from_numpy(sigmas), torch.from_numpy(np.log(train))
+
+    def _finish_kdpm2(self, timesteps, sigmas, sigmas_interpol, interpol_of_odd):
+        """interpol_of_odd(k): the index into the flat sigmas_interpol of the sigma the second stage at odd position k is evaluated at"""
+        self.sigmas_interpol = self._twice(sigmas_interpol)
+        self._finish_tables(timesteps.numpy(), self._twice(sigmas).numpy())
+        flat = self.sigmas_interpol
+        # the divisor of the model input per position: sigma at a first order position, sigma_interpol at a second stage one; one
+        # more entry for what follows the last position (sigma_interpol = 0 there)
+        self._in_div = [float(((self.sigmas[k] if k % 2 == 0 else flat[interpol_of_odd(k)]) ** 2 + 1) ** 0.5)
+                        for k in range(len(self.timesteps) + 1)]
+        self._reset()
+
+    def _reset(self):
+        self._stage = None          # the sample a first order stage started from, waiting for its second stage
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        self._set_tables(num_inference_steps)
+        self.num_inference_steps = num_inference_steps
+
+    @property
+    def state_in_first_order(self):
+        return self._stage is None
+
+    def _step_index(self, timestep):
+        pos = self._positions(timestep)
+        return pos[-1] if self.state_in_first_order else pos[0]
+
+    def _check_stage(self, k):
+        """the state against the parity of position k (before anything touches the GPU); True in a first order stage"""
+        first = self.state_in_first_order
+        if first != (k % 2 == 0):
+            raise ValueError(f"{type(self).__name__}.step: position {k} of the schedule is "
+                             f"{'a first order' if k % 2 == 0 else 'a second'} stage, the scheduler is in the other state")
+        return first
+
+    def _kept_sample(self, first, x):
+        """None in a first order stage, else the sample the transition started from, which must stand beside x in one launch"""
+        if first:
+            return None
+        if not self._fits(self._stage, x):
+            raise ValueError(f"{type(self).__name__}.step: the stored first stage does not have this sample's shape and layout "
+                             "(one chain per set_timesteps)")
+        return self._stage
+
+
+class KDPM2DiscreteScheduler(_KDPM2Base):
+    """KDPM2 (scheduling_k_dpm_2_discrete.py:60-310, epsilon prediction): deterministic, both stages on `bd_sigma_step`.
+    sigma_interpol is the geometric mean of sigma and sigma_next (a log-lerp with the rolled sigmas).  N steps cost 2N - 1 UNet
+    evaluations.  The defaults are the reference's (beta_start=0.00085, beta_end=0.012)."""
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="linear", trained_betas=None,
+                 prediction_type="epsilon", **unused):
+        self._init_kdpm2(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type)
+
+    def _set_tables(self, n):
+        # scheduling_k_dpm_2_discrete.py:152-203
+        timesteps, sigmas, log_sigmas = self._base_tables(n)
+        sigmas_interpol = sigmas.log().lerp(sigmas.roll(1).log(), 0.5).exp()       # [i]: between sigmas[i - 1] and sigmas[i]
+        t_interpol = self._sigma_to_t(sigmas_interpol, log_sigmas).to(timesteps.dtype)
+        pairs = torch.stack((t_interpol[1:-1, None], timesteps[1:, None]), dim=-1).flatten()
+        self._finish_kdpm2(torch.cat([timesteps[:1], pairs]), sigmas, sigmas_interpol, lambda k: k)
+
+    def _plan_scalars(self, k):
+        """sigma_in, dt, in_div of the stage at position k, and whether it starts from the kept sample"""
+        s, si = self.sigmas, self.sigmas_interpol
+        if k % 2 == 0:      # sigmas[k] -> sigma_interpol
+            return dict(sigma_in=float(s[k]), dt=float(si[k + 1] - s[k]), in_div=self._in_div[k + 1], churn=None, sigma_up=None, base=False)
+        return dict(sigma_in=float(si[k]), dt=float(s[k] - s[k - 1]), in_div=self._in_div[k + 1], churn=None, sigma_up=None, base=True)
+
+    def step(self, model_output, timestep, sample, return_dict=True, clip=None, scaled=False):
+        # scheduling_k_dpm_2_discrete.py:232-310
+        k = self._step_index(timestep)
+        first = self._check_stage(k)
+        eps, x, restore = self._begin_step(model_output, sample)
+        p = self._plan_scalars(k)
+        sc = torch.empty_like(x) if scaled else None
+        prev = ops.sigma_step(eps, x, p["sigma_in"], p["dt"], p["in_div"], base=self._kept_sample(first, x), scaled_out=sc, clip=clip)
+        self._stage = x if first else None
+        return self._output(prev, restore, return_dict, scaled_sample=sc)
+
+
+class KDPM2AncestralDiscreteScheduler(_NoisySigmaMixin, _KDPM2Base):
+    """KDPM2 with ancestral sampling (scheduling_k_dpm_2_ancestral_discrete.py:60-329, epsilon prediction): the first stage runs on
+    `bd_sigma_step` towards sigma_interpol, the geometric mean of sigma and sigma_down; the second on `bd_sigma_noise_step`, from
+    the kept sample with dt = sigma_down - sigma and noise of standard deviation sigma_up.  The reference draws a noise tensor in
+    both stages and uses the second's; with a CPU generator so does `step`.  The last entries of `sigmas_up` are NaN (0 * 0 / 0) in
+    the reference and here, and are never read.  num_inference_steps < 3 is refused: at 2 the reference's schedule holds a NaN
+    timestep and its chain fails."""
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="linear", trained_betas=None,
+                 prediction_type="epsilon", **unused):
+        self._init_kdpm2(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type)
+
+    def _set_tables(self, n):
+        # scheduling_k_dpm_2_ancestral_discrete.py:153-214
+        if n < 3:
+            raise ValueError(f"KDPM2AncestralDiscreteScheduler: num_inference_steps={n} must be at least 3 (at 2 the schedule has a NaN "
+                             "timestep, in the reference as well, and no chain runs)")
+        timesteps, sigmas, log_sigmas = self._base_tables(n)
+        sigmas_next = sigmas.roll(-1)
+        sigmas_next[-1] = 0.0
+        sigmas_up = (sigmas_next ** 2 * (sigmas ** 2 - sigmas_next ** 2) / sigmas ** 2) ** 0.5
+        sigmas_down = (sigmas_next ** 2 - sigmas_up ** 2) ** 0.5
+        sigmas_down[-1] = 0.0
+        sigmas_interpol = sigmas.log().lerp(sigmas_down.log(), 0.5).exp()
+        sigmas_interpol[-2:] = 0.0
+        self.sigmas_up, self.sigmas_down = self._twice(sigmas_up), self._twice(sigmas_down)
+        t_interpol = self._sigma_to_t(sigmas_interpol, log_sigmas).to(timesteps.dtype)
+        pairs = torch.stack((t_interpol[:-2, None], timesteps[1:, None]), dim=-1).flatten()
+        self._finish_kdpm2(torch.cat([timesteps[:1], pairs]), sigmas, sigmas_interpol, lambda k: k - 1)
+
+    def _plan_scalars(self, k):
+        """sigma_in, dt, in_div of the stage at position k; a second stage also has sigma_up and starts from the kept sample"""
+        s, si = self.sigmas, self.sigmas_interpol
+        if k % 2 == 0:      # sigmas[k] -> sigma_interpol
+            return dict(sigma_in=float(s[k]), dt=float(si[k] - s[k]), in_div=self._in_div[k + 1], churn=None, sigma_up=None, base=False)
+        return dict(sigma_in=float(si[k - 1]), dt=float(self.sigmas_down[k - 1] - s[k - 1]), in_div=self._in_div[k + 1], churn=None,
+                    sigma_up=float(self.sigmas_up[k - 1]), base=True)
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict=True, noise=None, clip=None, scaled=False):
+        # scheduling_k_dpm_2_ancestral_discrete.py:243-329
+        k = self._step_index(timestep)
+        first = self._check_stage(k)
+        eps, x, restore = self._begin_step(model_output, sample)
+        p = self._plan_scalars(k)
+        z = self._step_noise(noise, generator, model_output, not first)
+        sc = torch.empty_like(x) if scaled else None
+        if first:
+            prev = ops.sigma_step(eps, x, p["sigma_in"], p["dt"], p["in_div"], scaled_out=sc, clip=clip)
+        else:
+            prev = ops.sigma_noise_step(eps, x, z, p["sigma_in"], p["dt"], p["in_div"], base=self._kept_sample(first, x),
+                                        sigma_up=p["sigma_up"],
+                                        scaled_out=sc, clip=clip)
+        self._stage = x if first else None
         return self._output(prev, restore, return_dict, scaled_sample=sc)
 
 

@@ -1,7 +1,7 @@
 """Elijah-style defense on the MI355X path: invert the trigger, score the checkpoint, remove the backdoor, score it again.
 
     python elijah_defense.py --ckpt <checkpoint dir> [--inv_steps 100] [--inv_batch 64] [--inv_lr 0.1] [--lam 0.5]
-                             [--detect_n 256] [--sched DDIM-SCHED|DDPM-SCHED|DPM_SOLVER_{PP_,}O{1,2,3}-SCHED|UNIPC_O{1,2,3}-SCHED|DEIS_O{1,2,3}-SCHED|HEUN_O2-SCHED|LMSD_O{1,2,3,4}-SCHED] [--infer_steps 50] [--max_ratio R]
+                             [--detect_n 256] [--sched DDIM-SCHED|DDPM-SCHED|DPM_SOLVER_{PP_,}O{1,2,3}-SCHED|UNIPC_O{1,2,3}-SCHED|DEIS_O{1,2,3}-SCHED|HEUN_O2-SCHED|LMSD_O{1,2,3,4}-SCHED|EULER_{A_,}O1-SCHED|KDPM2_{A_,}O2-SCHED] [--infer_steps 50] [--max_ratio R]
                              [--remove_steps 200] [--batch 64] [--learning_rate 2e-5] [--output_dir DIR] [--tag T] [--seed 0] [--gpu 0]
                              [--clean_source none|synthetic|dataset] [--clean_n 256] [--clean_batch 64] [--clean_weight 1.0]
                              [--clean_target frozen|noise] [--dataset CIFAR10] [--dataset_path datasets]
@@ -30,7 +30,7 @@ from typing import Union
 
 import torch
 
-from baddiffusion_amd import defense
+from baddiffusion_amd import defense, pipelines
 from baddiffusion_amd.inversion import invert_trigger
 from baddiffusion_amd.model import DiffuserModelSched, save_scheduler, save_unet
 from baddiffusion_amd.pipelines import DDIMPipeline, DDPMPipeline, DEISPipeline, DPMSolverPipeline, HeunPipeline, LMSPipeline, UniPCPipeline
@@ -75,7 +75,8 @@ class Config:
 
 
 SCHED_CHOICES = [DiffuserModelSched.DDIM_SCHED, DiffuserModelSched.DDPM_SCHED] + sorted(DiffuserModelSched._DPM_SCHEDS) + \
-    sorted(DiffuserModelSched._UNIPC_SCHEDS) + sorted(DiffuserModelSched._DEIS_SCHEDS) + sorted(DiffuserModelSched._SIGMA_SCHEDS)
+    sorted(DiffuserModelSched._UNIPC_SCHEDS) + sorted(DiffuserModelSched._DEIS_SCHEDS) + sorted(DiffuserModelSched._SIGMA_SCHEDS) + \
+    sorted(DiffuserModelSched._KDIFF_SCHEDS)
 DEFAULT_ASR_THRESHOLD = 1e-3    # of the order the papers use; a choice, not a finding
 
 
@@ -97,7 +98,8 @@ def get_config(argv=None):
     p.add_argument("--detect_n", type=int, default=config.detect_n)
     p.add_argument("--sched", "-sc", type=str, default=config.sched, choices=SCHED_CHOICES,
                    help="sampling pipeline of the score passes; the DPM_SOLVER_* names run DPMSolverMultistepScheduler (always the native solver here), "
-                        "the UNIPC_O* names UniPCMultistepScheduler, the DEIS_O* names DEISMultistepScheduler, HEUN_O2 / LMSD_O* the sigma-space samplers")
+                        "the UNIPC_O* names UniPCMultistepScheduler, the DEIS_O* names DEISMultistepScheduler, HEUN_O2 / LMSD_O* the sigma-space samplers, "
+                        "EULER_O1 / EULER_A_O1 / KDPM2_O2 / KDPM2_A_O2 Euler, Euler-ancestral, KDPM2 and KDPM2-ancestral")
     p.add_argument("--infer_steps", "-is", type=int, default=config.infer_steps)
     p.add_argument("--max_ratio", type=float)
     p.add_argument("--remove_steps", type=int, default=config.remove_steps)
@@ -159,6 +161,8 @@ def make_pipeline(config, model, noise_sched):
         if cls_name == "HeunDiscreteScheduler":
             return HeunPipeline(unet=model, scheduler=HeunDiscreteScheduler.from_config(noise_sched.config))
         return LMSPipeline(unet=model, scheduler=LMSDiscreteScheduler.from_config(noise_sched.config), order=order)
+    if config.sched in DiffuserModelSched._KDIFF_SCHEDS:       # the pipeline converts the scheduler from its config
+        return getattr(pipelines, DiffuserModelSched._KDIFF_SCHEDS[config.sched][1])(unet=model, scheduler=noise_sched)
     if config.dyn_threshold is not None:
         # a sampling scheduler of its own: the checkpoint's scheduler, which is saved back with the repaired model, keeps its config
         cls = DDIMScheduler if config.sched == DiffuserModelSched.DDIM_SCHED else DDPMScheduler

@@ -287,6 +287,36 @@ typedef struct {
 } bd_sigma_step_desc;
 int bd_sigma_step(const bd_sigma_step_desc* d, bd_stream_t stream);
 
+/* f-4: one first order transition of a stochastic sigma-space sampler in one launch -- Euler with Karras churn
+ * (scheduling_euler_discrete.py:257-354), Euler-ancestral (scheduling_euler_ancestral_discrete.py:193-281) and the second stage of
+ * KDPM2-ancestral (scheduling_k_dpm_2_ancestral_discrete.py:243-329) -- with the NEXT evaluation's scale_model_input, as bd_sigma_step.
+ * Per element, fp32, each operation rounded once, in this order (e = model_output, x = sample, z = noise):
+ *     xh   = churn ? x + (z s_noise) churn_mul : x          churn_mul = (sigma_hat^2 - sigma^2) ** 0.5, a host fp32 value
+ *     x0   = xh - sigma_in e                                sigma_in = sigma_hat, or sigma_interpol in KDPM2's second stage
+ *     d    = (xh - x0) / sigma_in
+ *     prev = (base ? base : xh) + d dt
+ *     if up: prev = prev + z sigma_up                       the ancestral noise
+ *     sc   = prev / in_div;  if clip: sc = clamp(sc, -clip_range, clip_range); prev = sc in_div        exactly as bd_sigma_step
+ * x0 goes to x0_out, prev to prev_out, sc to scaled_out; x0_out and scaled_out may be NULL (not written).  With neither churn nor
+ * up the noise buffer is not read (it is still required) and the result is bd_sigma_step's first order one.
+ * prev_out may be `sample` itself (identical base pointer); no other buffer may overlap another.
+ * Host checks before the launch (BD_ERR_INVALID, message names bd_sigma_noise_step): null descriptor, n <= 0, a null model_output /
+ * sample / noise / prev_out, sigma_in <= 0, in_div <= 0, sigma_up < 0, churn together with up, churn with churn_mul <= 0, a pointer that
+ * is not 16-byte aligned, an output that is or overlaps an input or another output (but prev_out == sample).
+ * Same launch shape as bd_sigma_step. */
+typedef struct {
+    int64_t n;
+    const float* model_output; const float* sample; const float* noise;
+    const float* base;                                   /* NULL: the update starts from xh                        */
+    float* x0_out; float* prev_out; float* scaled_out;   /* all but prev_out may be NULL                           */
+    float sigma_in, dt;
+    int churn; float s_noise, churn_mul;
+    int up; float sigma_up;
+    float in_div;
+    int clip; float clip_range;
+} bd_sigma_noise_step_desc;
+int bd_sigma_noise_step(const bd_sigma_noise_step_desc* d, bd_stream_t stream);
+
 /* out = (x * mul) / div over n dense fp32 elements, each operation rounded once: the start of a sigma-space chain
  * (init * init_noise_sigma, then / sqrt(sigma_0^2 + 1)) and the schedulers' public scale_model_input (mul = 1).  Same launch shape
  * as bd_sigma_step.  BD_ERR_INVALID: a null pointer, n <= 0, div <= 0, a pointer that is not 16-byte aligned, out overlapping x
