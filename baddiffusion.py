@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from baddiffusion_amd.dataset import Backdoor, DatasetLoader
+from baddiffusion_amd.sched_names import TRAIN_CHOICES as SCHED_CHOICES
 
 MODE_TRAIN, MODE_RESUME, MODE_SAMPLING, MODE_MEASURE, MODE_TRAIN_MEASURE = "train", "resume", "sampling", "measure", "train+measure"
 
@@ -41,12 +42,6 @@ MODE_MEASURE_OPTS = ["project", "mode", "eval_max_batch", "gpu", "fclip", "ckpt"
                      "dyn_threshold", "dyn_threshold_ratio"]
 EMA_DIR, EMA_STATE = "unet_ema", "ema.bin"     # averaged weights in diffusers layout under output_dir; EMA scalars + shadow under ckpt/
 IGNORE_ARGS = ["overwrite", "is_save_all_model_epochs"]
-SCHED_CHOICES = ["DDPM-SCHED", "DDIM-SCHED", "DPM_SOLVER_PP_O1-SCHED", "DPM_SOLVER_O1-SCHED", "DPM_SOLVER_PP_O2-SCHED",
-                 "DPM_SOLVER_O2-SCHED", "DPM_SOLVER_PP_O3-SCHED", "DPM_SOLVER_O3-SCHED", "UNIPC-SCHED", "PNDM-SCHED", "DEIS-SCHED",
-                 "HEUN-SCHED", "SCORE-SDE-VE-SCHED", "UNIPC_O1-SCHED", "UNIPC_O2-SCHED", "UNIPC_O3-SCHED",
-                 "HEUN_O2-SCHED", "LMSD_O1-SCHED", "LMSD_O2-SCHED", "LMSD_O3-SCHED", "LMSD_O4-SCHED",
-                 "DEIS_O1-SCHED", "DEIS_O2-SCHED", "DEIS_O3-SCHED",
-                 "EULER_O1-SCHED", "EULER_A_O1-SCHED", "KDPM2_O2-SCHED", "KDPM2_A_O2-SCHED"]
 
 
 def parse_args(argv=None):

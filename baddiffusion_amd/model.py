@@ -15,12 +15,11 @@ from typing import Union
 import numpy as np
 import torch
 
-from .pipelines import (DDIMPipeline, DDPMPipeline, DEISPipeline, DPMSolverPipeline, EulerAncestralPipeline, EulerPipeline, HeunPipeline,
-                        KDPM2AncestralPipeline, KDPM2Pipeline, LMSPipeline, PNDMPipeline, UniPCPipeline)
+from . import sched_names
+from .pipelines import DDPMPipeline
 from .schedulers import (DDIMScheduler, DDPMScheduler, DEISMultistepScheduler, DPMSolverMultistepScheduler,
                          EulerAncestralDiscreteScheduler, EulerDiscreteScheduler, HeunDiscreteScheduler, KDPM2AncestralDiscreteScheduler,
-                         KDPM2DiscreteScheduler, LMSDiscreteScheduler, PNDMScheduler, RePaintScheduler, SchedulerConfigCarrier,
-                         UniPCMultistepScheduler)
+                         KDPM2DiscreteScheduler, LMSDiscreteScheduler, RePaintScheduler, UniPCMultistepScheduler)
 from .unet import UNet2DModel
 
 WEIGHTS_NAME = "diffusion_pytorch_model.bin"
@@ -258,40 +257,8 @@ class DiffuserModelSched:
     DDPM_CHURCH_256 = "DDPM-CHURCH-256"
     DDPM_BEDROOM_256 = "DDPM-BEDROOM-256"
     LDM_CELEBA_HQ_256 = "LDM-CELEBA-HQ-256"
-    DDPM_SCHED = "DDPM-SCHED"
-    DDIM_SCHED = "DDIM-SCHED"
-    # model.py:598-630: these build their own scheduler object but sample through PNDMPipeline, which converts it to a
-    # PNDMScheduler (pipeline_pndm.py:46) -- value = the reference class the returned config stands for
-    _PNDM_SCHEDS = {"DPM_SOLVER_PP_O1-SCHED": "DPMSolverMultistepScheduler", "DPM_SOLVER_O1-SCHED": "DPMSolverMultistepScheduler",
-                    "DPM_SOLVER_PP_O2-SCHED": "DPMSolverMultistepScheduler", "DPM_SOLVER_O2-SCHED": "DPMSolverMultistepScheduler",
-                    "DPM_SOLVER_PP_O3-SCHED": "DPMSolverMultistepScheduler", "DPM_SOLVER_O3-SCHED": "DPMSolverMultistepScheduler",
-                    "UNIPC-SCHED": "UniPCMultistepScheduler", "PNDM-SCHED": "PNDMScheduler", "DEIS-SCHED": "DEISMultistepScheduler",
-                    "HEUN-SCHED": "HeunDiscreteScheduler", "LMSD-SCHED": "LMSDiscreteScheduler"}
-    # native_sched=True: the six DPM-Solver names run the solver they name -- value = (solver_order, algorithm_type) of model.py:598-614
-    _DPM_SCHEDS = {"DPM_SOLVER_PP_O1-SCHED": (1, "dpmsolver++"), "DPM_SOLVER_O1-SCHED": (1, "dpmsolver"),
-                   "DPM_SOLVER_PP_O2-SCHED": (2, "dpmsolver++"), "DPM_SOLVER_O2-SCHED": (2, "dpmsolver"),
-                   "DPM_SOLVER_PP_O3-SCHED": (3, "dpmsolver++"), "DPM_SOLVER_O3-SCHED": (3, "dpmsolver")}
-    # names of this project's own (the reference's UNIPC-SCHED builds a UniPCMultistepScheduler and never steps it, and that name keeps
-    # its PNDM conversion): UniPCMultistepScheduler + UniPCPipeline with or without native_sched -- value = solver_order; the other
-    # options are the reference's defaults (bh2, predict_x0)
-    _UNIPC_SCHEDS = {"UNIPC_O1-SCHED": 1, "UNIPC_O2-SCHED": 2, "UNIPC_O3-SCHED": 3}
-    # DEIS under names of this project's own as well (the reference's DEIS-SCHED keeps its PNDM conversion): DEISMultistepScheduler +
-    # DEISPipeline with or without native_sched, in the reference's coefficient arithmetic -- value = solver_order
-    _DEIS_SCHEDS = {"DEIS_O1-SCHED": 1, "DEIS_O2-SCHED": 2, "DEIS_O3-SCHED": 3}
-    # the sigma-space samplers, names of this project's own too (the reference's HEUN-SCHED / LMSD-SCHED keep their PNDM conversion):
-    # HeunDiscreteScheduler + HeunPipeline, LMSDiscreteScheduler + LMSPipeline at the named order, with or without native_sched --
-    # value = (scheduler class, order)
-    _SIGMA_SCHEDS = {"HEUN_O2-SCHED": ("HeunDiscreteScheduler", 2), "LMSD_O1-SCHED": ("LMSDiscreteScheduler", 1),
-                     "LMSD_O2-SCHED": ("LMSDiscreteScheduler", 2), "LMSD_O3-SCHED": ("LMSDiscreteScheduler", 3),
-                     "LMSD_O4-SCHED": ("LMSDiscreteScheduler", 4)}
-    # Euler, Euler-ancestral, KDPM2 and KDPM2-ancestral (the reference's model.py names none of them), with or without native_sched --
-    # value = (scheduler class, pipeline class)
-    _KDIFF_SCHEDS = {"EULER_O1-SCHED": ("EulerDiscreteScheduler", "EulerPipeline"),
-                     "EULER_A_O1-SCHED": ("EulerAncestralDiscreteScheduler", "EulerAncestralPipeline"),
-                     "KDPM2_O2-SCHED": ("KDPM2DiscreteScheduler", "KDPM2Pipeline"),
-                     "KDPM2_A_O2-SCHED": ("KDPM2AncestralDiscreteScheduler", "KDPM2AncestralPipeline")}
-    # named in model.py:556-563 but not handled by its __get_model_sched either (it raises NotImplementedError)
-    _OTHER_SCHEDS = ("LDM-SCHED", "SCORE-SDE-VE-SCHED", "EDM-VE-SCHED", "EDM-VE-ODE-SCHED", "EDM-VE-SDE-SCHED")
+    DDPM_SCHED = sched_names.DDPM_SCHED
+    DDIM_SCHED = sched_names.DDIM_SCHED         # every other --sched name: the table of sched_names.py
     _HUB = {DDPM_CIFAR10_32: "google/ddpm-cifar10-32", DDPM_CELEBA_HQ_256: "google/ddpm-ema-celebahq-256",
             DDPM_CHURCH_256: "google/ddpm-ema-church-256", DDPM_BEDROOM_256: "google/ddpm-ema-bedroom-256",
             LDM_CELEBA_HQ_256: "CompVis/ldm-celebahq-256"}
@@ -312,7 +279,8 @@ class DiffuserModelSched:
         scheduler only; its values are checked here, before anything is loaded"""
         if dyn_threshold is None:
             return
-        if noise_sched_type not in (DiffuserModelSched.DDPM_SCHED, DiffuserModelSched.DDIM_SCHED, None):
+        rec = sched_names.SCHEDS.get(noise_sched_type)
+        if noise_sched_type is not None and not (rec and rec.dyn_threshold):
             raise NotImplementedError(
                 f"dyn_threshold with {noise_sched_type}: dynamic thresholding runs in the DDPM and DDIM steps only ({DiffuserModelSched.DDPM_SCHED}, "
                 f"{DiffuserModelSched.DDIM_SCHED} or no scheduler name); the multistep schedulers take thresholding with sample_max_value == 1 alone, "
@@ -339,9 +307,8 @@ class DiffuserModelSched:
                          native_sched: bool = False, dyn_threshold: float = None, dyn_threshold_ratio: float = 0.995):
         DiffuserModelSched._check_dyn_threshold(noise_sched_type, dyn_threshold, dyn_threshold_ratio)
         # model.py:577-643.  native_sched (not in the reference): the DPM-Solver names build DPMSolverMultistepScheduler +
-        # DPMSolverPipeline instead of the PNDM conversion; the other solvers of that family have no native scheduler and are refused.
-        # The UNIPC_O*-SCHED names (not the reference's either) always build UniPCMultistepScheduler + UniPCPipeline, the DEIS_O*-SCHED
-        # names DEISMultistepScheduler + DEISPipeline
+        # DPMSolverPipeline instead of the PNDM conversion; the other solvers of that family have no native scheduler and are refused
+        # (SchedName.resolve)
         clip_used = DiffuserModelSched.get_sample_clip(clip_sample, DiffuserModelSched.CLIP_SAMPLE_DEFAULT)
         local = _resolve_local(ckpt_id)
         if local is not None:
@@ -363,54 +330,21 @@ class DiffuserModelSched:
             ckpt_sched = DDPMScheduler(**KNOWN_SCHEDULERS.get(ckpt_id, {}))
         else:
             raise FileNotFoundError(f"checkpoint '{ckpt_id}' not found locally and its topology is unknown")
-        kw = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02)
-        if noise_sched_type == DiffuserModelSched.DDPM_SCHED:
-            noise_sched = DDPMScheduler(clip_sample=clip_used, **kw)
-            get_pipeline = DiffuserModelSched._pipeline_generator(DDPMPipeline)
-        elif noise_sched_type == DiffuserModelSched.DDIM_SCHED:
-            noise_sched = DDIMScheduler(clip_sample=clip_used, **kw)
-            get_pipeline = DiffuserModelSched._pipeline_generator(DDIMPipeline)
-        elif noise_sched_type is None:
-            noise_sched = ckpt_sched
-            get_pipeline = DiffuserModelSched._pipeline_generator(DDPMPipeline)
-        elif noise_sched_type in DiffuserModelSched._UNIPC_SCHEDS:
-            noise_sched = UniPCMultistepScheduler(solver_order=DiffuserModelSched._UNIPC_SCHEDS[noise_sched_type], **kw)
-            get_pipeline = DiffuserModelSched._pipeline_generator(partial(UniPCPipeline, clip_sample=clip_used))
-        elif noise_sched_type in DiffuserModelSched._DEIS_SCHEDS:
-            noise_sched = DEISMultistepScheduler(solver_order=DiffuserModelSched._DEIS_SCHEDS[noise_sched_type], **kw)
-            get_pipeline = DiffuserModelSched._pipeline_generator(partial(DEISPipeline, clip_sample=clip_used))
-        elif noise_sched_type in DiffuserModelSched._SIGMA_SCHEDS:
-            cls_name, order = DiffuserModelSched._SIGMA_SCHEDS[noise_sched_type]
-            if cls_name == "HeunDiscreteScheduler":
-                noise_sched = HeunDiscreteScheduler(**kw)
-                get_pipeline = DiffuserModelSched._pipeline_generator(partial(HeunPipeline, clip_sample=clip_used))
-            else:
-                noise_sched = LMSDiscreteScheduler(**kw)
-                get_pipeline = DiffuserModelSched._pipeline_generator(partial(LMSPipeline, clip_sample=clip_used, order=order))
-        elif noise_sched_type in DiffuserModelSched._KDIFF_SCHEDS:
-            sched_cls, pipe_cls = DiffuserModelSched._KDIFF_SCHEDS[noise_sched_type]
-            noise_sched = {c.__name__: c for c in (EulerDiscreteScheduler, EulerAncestralDiscreteScheduler, KDPM2DiscreteScheduler,
-                                                   KDPM2AncestralDiscreteScheduler)}[sched_cls](**kw)
-            pipe_cls = {c.__name__: c for c in (EulerPipeline, EulerAncestralPipeline, KDPM2Pipeline, KDPM2AncestralPipeline)}[pipe_cls]
-            get_pipeline = DiffuserModelSched._pipeline_generator(partial(pipe_cls, clip_sample=clip_used))
-        elif native_sched and noise_sched_type in DiffuserModelSched._DPM_SCHEDS:
-            order, algorithm = DiffuserModelSched._DPM_SCHEDS[noise_sched_type]
-            noise_sched = DPMSolverMultistepScheduler(solver_order=order, algorithm_type=algorithm, **kw)
-            get_pipeline = DiffuserModelSched._pipeline_generator(partial(DPMSolverPipeline, clip_sample=clip_used))
-        elif native_sched and noise_sched_type in DiffuserModelSched._PNDM_SCHEDS and noise_sched_type != "PNDM-SCHED":
-            raise NotImplementedError(f"{noise_sched_type}: {DiffuserModelSched._PNDM_SCHEDS[noise_sched_type]} has no native scheduler "
-                                      "(native_sched covers the DPM-Solver names; without it this name samples through PNDMPipeline)")
-        elif noise_sched_type in DiffuserModelSched._PNDM_SCHEDS:
-            # SURVEY f-4: training uses only the betas of this object; sampling = PNDMPipeline with the post-step clip
-            if noise_sched_type == "PNDM-SCHED":
-                noise_sched = PNDMScheduler(**kw)
-            else:
-                noise_sched = SchedulerConfigCarrier(DiffuserModelSched._PNDM_SCHEDS[noise_sched_type], **kw)
-            get_pipeline = DiffuserModelSched._pipeline_generator(partial(PNDMPipeline, clip_sample=clip_used))
-        elif noise_sched_type in DiffuserModelSched._OTHER_SCHEDS:
-            raise NotImplementedError(f"{noise_sched_type}: not handled by the reference's model.py:577-643 either")
-        else:
+        if noise_sched_type is None:
+            noise_sched, pipeline = ckpt_sched, DDPMPipeline
+        elif noise_sched_type not in sched_names.SCHEDS:
             raise NotImplementedError()
+        else:
+            rec = sched_names.SCHEDS[noise_sched_type]
+            sched_cls, sched_kw, pipeline, pipe_kw = rec.resolve(native_sched)
+            if rec.clip_in_sched:
+                sched_kw = dict(sched_kw, clip_sample=clip_used)
+            else:
+                pipe_kw = dict(pipe_kw, clip_sample=clip_used)
+            # the reference's tables for every name, Heun and KDPM2 included, whose class defaults differ
+            noise_sched = sched_cls(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, **sched_kw)
+            pipeline = partial(pipeline, **pipe_kw)
+        get_pipeline = DiffuserModelSched._pipeline_generator(pipeline)
         if clip_used is not None:
             noise_sched.config.clip_sample = clip_used
             print(f"noise_sched.config.clip_sample = {noise_sched.config.clip_sample}")

@@ -299,6 +299,9 @@ class _SigmaPipeline(_MultistepPipeline):
     buffers -- the only ones that are images; the last frame is the final sample, at sigma = 0 where both coincide.  With
     start_from=k the chain enters at position k of `scheduler.timesteps` with an empty history."""
 
+    _odd_start = None        # samplers with two evaluations per transition: what an odd start_from is, for the refusal
+    _stochastic = False      # the reference draws a noise tensor at every evaluation (`_noise_used` says which are read)
+
     def _step_kwargs(self):
         return {}
 
@@ -307,7 +310,14 @@ class _SigmaPipeline(_MultistepPipeline):
         return self._step_kwargs()
 
     def _check_start(self, start_from):
-        pass
+        if self._odd_start and start_from % 2:
+            raise ValueError(f"{type(self).__name__}: start_from={start_from} is {self._odd_start}; start at an even position")
+
+    def noise_draws(self, num_inference_steps=None, start_from=0, **kwargs):
+        if not self._stochastic:
+            return 0
+        n = num_inference_steps or self.default_steps
+        return (2 * n - 1 if self.scheduler_class._two_stage else n) - int(start_from)
 
     def _noise_used(self, position):
         """None: the sampler draws nothing at this position of `scheduler.timesteps`; True / False: the reference draws a tensor there
@@ -357,11 +367,7 @@ class HeunPipeline(_SigmaPipeline):
     transition whose first stage was not run, and is refused."""
     scheduler_class = HeunDiscreteScheduler
     default_steps = 10
-
-    def _check_start(self, start_from):
-        if start_from % 2:
-            raise ValueError(f"HeunPipeline: start_from={start_from} is the second entry of a timestep pair (the averaging stage of a "
-                             "transition whose first stage would be missing); start at an even position")
+    _odd_start = "the second entry of a timestep pair (the averaging stage of a transition whose first stage would be missing)"
 
 
 class LMSPipeline(_SigmaPipeline):
@@ -388,6 +394,7 @@ class EulerPipeline(_SigmaPipeline):
     chunk's initial noise, stay the reference's.  num_inference_steps=20 is this project's default."""
     scheduler_class = EulerDiscreteScheduler
     default_steps = 20
+    _stochastic = True
 
     def __init__(self, unet, scheduler, clip_sample=False, clip_sample_range=1.0, s_churn=0.0, s_noise=1.0):
         super().__init__(unet, scheduler, clip_sample=clip_sample, clip_sample_range=clip_sample_range)
@@ -402,21 +409,16 @@ class EulerPipeline(_SigmaPipeline):
     def _noise_used(self, position):
         return self.scheduler._plan_scalars(position, s_churn=self.s_churn, s_noise=self.s_noise)["churn"] is not None
 
-    def noise_draws(self, num_inference_steps=None, start_from=0, **kwargs):
-        return (num_inference_steps or self.default_steps) - int(start_from)
-
 
 class EulerAncestralPipeline(_SigmaPipeline):
     """Sampling with EulerAncestralDiscreteScheduler: _SigmaPipeline's loop, one UNet forward + one `bd_sigma_noise_step` launch per
     step, one noise tensor per step.  num_inference_steps=20 is this project's default."""
     scheduler_class = EulerAncestralDiscreteScheduler
     default_steps = 20
+    _stochastic = True
 
     def _noise_used(self, position):
         return True
-
-    def noise_draws(self, num_inference_steps=None, start_from=0, **kwargs):
-        return (num_inference_steps or self.default_steps) - int(start_from)
 
 
 class KDPM2Pipeline(_SigmaPipeline):
@@ -425,11 +427,7 @@ class KDPM2Pipeline(_SigmaPipeline):
     (evaluations); an odd one is the second stage of a transition whose first stage was not run, and is refused."""
     scheduler_class = KDPM2DiscreteScheduler
     default_steps = 10
-
-    def _check_start(self, start_from):
-        if start_from % 2:
-            raise ValueError(f"{type(self).__name__}: start_from={start_from} is the second stage of a transition whose first stage "
-                             "would be missing; start at an even position")
+    _odd_start = "the second stage of a transition whose first stage would be missing"
 
 
 class KDPM2AncestralPipeline(KDPM2Pipeline):
@@ -437,12 +435,10 @@ class KDPM2AncestralPipeline(KDPM2Pipeline):
     reference draws a noise tensor at every position, 2N - 1 per chain, and reads the second stages'; with a CPU generator so does
     this pipeline."""
     scheduler_class = KDPM2AncestralDiscreteScheduler
+    _stochastic = True
 
     def _noise_used(self, position):
         return position % 2 == 1
-
-    def noise_draws(self, num_inference_steps=None, start_from=0, **kwargs):
-        return 2 * (num_inference_steps or self.default_steps) - 1 - int(start_from)
 
 
 def with_default_steps(pipeline, num_inference_steps):

@@ -1039,8 +1039,9 @@ class DEISMultistepScheduler(_LambdaMultistep):
 
 
 class _SigmaScheduler(_Base):
-    """What the two sigma-space (k-diffusion) schedulers share: the sample lives in the variance-exploding coordinates x = x_vp *
-    sqrt(sigma^2 + 1) with sigma = sqrt((1 - abar) / abar), the chain starts from noise * init_noise_sigma, the model sees
+    """What the sigma-space (k-diffusion) schedulers share -- the constructor, `set_timesteps`, the resolution of a timestep to its
+    position, and for the four whose transition is a single launch the body of `step` (`_planned_step`): the sample
+    lives in the variance-exploding coordinates x = x_vp * sqrt(sigma^2 + 1) with sigma = sqrt((1 - abar) / abar), the chain starts from noise * init_noise_sigma, the model sees
     scale_model_input(x) = x / sqrt(sigma^2 + 1) at a timestep of np.linspace(0, T - 1, N) -- fractional in general, which is why
     UNet2DModel takes float timesteps -- and every transition is ONE `bd_sigma_step` launch that also writes the next evaluation's
     model input (`step(..., scaled=True)` returns it as `.scaled_sample`).  Host tables: `timesteps` (float64 numpy), `sigmas` (fp32
@@ -1049,13 +1050,35 @@ class _SigmaScheduler(_Base):
     carried into sigma space; the reference has no clip here)."""
     order = 1
     _KEYS = ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "trained_betas", "prediction_type")
+    _BETAS = (0.0001, 0.02)         # the class's default (beta_start, beta_end), the reference's
+    # a transition is two `step` calls: a first order stage that leaves something in `_stage`, then the stage that consumes it.
+    # `timesteps` then lists a timestep twice (or two equal ones side by side): it resolves to its last position in the first order
+    # state and to its first otherwise, and `_check_stage` holds the state against the position's parity
+    _two_stage = False
+    _second_stage = "a second"      # what the messages call the stage at an odd position
 
-    def _init_common(self, num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type):
+    def __init__(self, num_train_timesteps=1000, beta_start=None, beta_end=None, beta_schedule="linear", trained_betas=None,
+                 prediction_type="epsilon", **unused):
+        beta_start = self._BETAS[0] if beta_start is None else beta_start
+        beta_end = self._BETAS[1] if beta_end is None else beta_end
         self.config = FrozenConfig(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
                                    beta_schedule=beta_schedule, trained_betas=trained_betas, prediction_type=prediction_type)
         self._make_tables(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas)
         self.num_inference_steps = None
         self._set_tables(num_train_timesteps)
+        self._reset()
+
+    def _reset(self):
+        self._stage = None          # what a first order stage left for the stage that follows it
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        # the tables stay on the host; the pipelines upload the timesteps once
+        self._set_tables(num_inference_steps)
+        self._reset()
+        self.num_inference_steps = num_inference_steps
+
+    def _set_tables(self, n):
+        self._finish_tables(*self._interp(n))
 
     def _interp(self, n):
         """(timesteps float64 [n] descending, sigmas fp32 [n + 1] with the trailing 0): scheduling_lms_discrete.py:203-206"""
@@ -1083,6 +1106,65 @@ class _SigmaScheduler(_Base):
             raise ValueError(f"{type(self).__name__}: timestep {float(timestep)!r} is not one of this schedule's")
         return pos
 
+    @property
+    def state_in_first_order(self):
+        return self._stage is None
+
+    def _step_index(self, timestep):
+        pos = self._positions(timestep)
+        return pos[-1] if self._two_stage and self.state_in_first_order else pos[0]
+
+    def _check_stage(self, k):
+        """the state against the parity of position k (before anything touches the GPU); True in a first order stage"""
+        first = self.state_in_first_order
+        if first != (k % 2 == 0):
+            raise ValueError(f"{type(self).__name__}.step: position {k} of the schedule is "
+                             f"{'a first order' if k % 2 == 0 else self._second_stage} stage, the scheduler is in the other state")
+        return first
+
+    def _kept_sample(self, first, x):
+        """None in a first order stage, else the sample the transition started from, which must stand beside x in one launch"""
+        if first:
+            return None
+        if not self._fits(self._stage, x):
+            raise ValueError(f"{type(self).__name__}.step: the stored first stage does not have this sample's shape and layout "
+                             "(one chain per set_timesteps)")
+        return self._stage
+
+    def _step_noise(self, noise, generator, model_output, used):
+        """the tensor `bd_sigma_noise_step` reads, given or drawn (draw_step_noise), in the sample's layout; None when the step reads none"""
+        if noise is None:
+            noise = draw_step_noise(tuple(model_output.shape), generator, model_output.device, used)
+        if not used:
+            return None
+        if noise.dtype != torch.float32 or not noise.is_cuda:
+            raise TypeError(f"{type(self).__name__}.step: noise must be a float32 GPU tensor")
+        if self._flat(model_output)[1] == "nhwc":          # _align's layout: the model output's
+            q = noise.permute(0, 2, 3, 1)
+            return q if q.is_contiguous() else q.contiguous()
+        return noise.contiguous()
+
+    def _planned_step(self, model_output, timestep, sample, generator, noise, return_dict, clip, scaled, *plan_args):
+        """`step` of Euler, Euler-ancestral, KDPM2 and KDPM2-ancestral: one launch of what `_plan_scalars` says -- `bd_sigma_noise_step`
+        where it names a churn or a sigma_up, `bd_sigma_step` otherwise, from the kept sample where it says base.  The noise is drawn
+        as the reference draws it: with a CPU generator in every call, read or not (a deterministic class passes no generator)."""
+        k = self._step_index(timestep)
+        first = self._check_stage(k) if self._two_stage else True
+        eps, x, restore = self._begin_step(model_output, sample)
+        p = self._plan_scalars(k, *plan_args)
+        noisy = p["churn"] is not None or p["sigma_up"] is not None
+        z = self._step_noise(noise, generator, model_output, noisy)
+        sc = torch.empty_like(x) if scaled else None
+        base = self._kept_sample(first, x) if p["base"] else None
+        if noisy:
+            prev = ops.sigma_noise_step(eps, x, z, p["sigma_in"], p["dt"], p["in_div"], base=base, churn=p["churn"], sigma_up=p["sigma_up"],
+                                        scaled_out=sc, clip=clip)
+        else:
+            prev = ops.sigma_step(eps, x, p["sigma_in"], p["dt"], p["in_div"], base=base, scaled_out=sc, clip=clip)
+        if self._two_stage:
+            self._stage = x if first else None
+        return self._output(prev, restore, return_dict, scaled_sample=sc)
+
     def scale_model_input(self, sample, timestep):
         """sample / sqrt(sigma^2 + 1) at `timestep` (bd_scale_input): bit-equal to the `.scaled_sample` of the step that produced
         `sample` (without clip; with it the step scales before it clamps)."""
@@ -1099,33 +1181,18 @@ class HeunDiscreteScheduler(_SigmaScheduler):
     derivative, dt and the sample it started from, then the averaging stage from that sample.  The last transition (to sigma = 0) is a
     plain Euler stage, so N steps cost 2N - 1 evaluations; `timesteps` has those 2N - 1 entries (each after the first twice) and
     `sigmas` 2N.  The defaults are the reference's (beta_start=0.00085, beta_end=0.012)."""
-
-    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="linear", trained_betas=None,
-                 prediction_type="epsilon", **unused):
-        self._init_common(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type)
+    _BETAS = (0.00085, 0.012)
+    _two_stage = True               # scheduling_heun_discrete.py:115-125
+    _second_stage = "an averaging"
 
     def _set_tables(self, n):
+        # scheduling_heun_discrete.py:146-187
         t, s = self._interp(n)
         self._finish_tables(np.concatenate([t[:1], np.repeat(t[1:], 2)]), np.concatenate([s[:1], np.repeat(s[1:-1], 2), s[-1:]]))
-        self._reset()
 
     def _reset(self):
         self._stage = None          # (derivative buffer, dt, sample) of a first order stage that waits for its averaging stage
         self._dbuf = None
-
-    def set_timesteps(self, num_inference_steps, device=None):
-        # scheduling_heun_discrete.py:146-187 (the tables stay on the host; the pipelines upload the timesteps once)
-        self._set_tables(num_inference_steps)
-        self.num_inference_steps = num_inference_steps
-
-    @property
-    def state_in_first_order(self):
-        return self._stage is None
-
-    def _step_index(self, timestep):
-        # :115-125: a timestep is listed twice; the first order stage is the later entry, the averaging stage the earlier one
-        pos = self._positions(timestep)
-        return pos[-1] if self.state_in_first_order else pos[0]
 
     def _plan_scalars(self, k):
         """(sigma_in, dt or None, in_div) of the stage at position k: an even position is a first order stage sigmas[k] -> sigmas[k + 1],
@@ -1138,10 +1205,7 @@ class HeunDiscreteScheduler(_SigmaScheduler):
         # scheduling_heun_discrete.py:193-275
         k = self._step_index(timestep)
         eps, x, restore = self._begin_step(model_output, sample)
-        first = self.state_in_first_order
-        if first != (k % 2 == 0):
-            raise ValueError(f"HeunDiscreteScheduler.step: position {k} of the schedule is "
-                             f"{'a first order' if k % 2 == 0 else 'an averaging'} stage, the scheduler is in the other state")
+        first = self._check_stage(k)
         sigma_in, dt, in_div = self._plan_scalars(k)
         sc = torch.empty_like(x) if scaled else None
         if first:
@@ -1171,27 +1235,18 @@ class LMSDiscreteScheduler(_SigmaScheduler):
     Order 1 is Euler."""
     MAX_ORDER = 4
 
-    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
-                 prediction_type="epsilon", **unused):
-        self._coeffs = {}
-        self._init_common(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type)
-
-    def _set_tables(self, n):
-        self._finish_tables(*self._interp(n))
-        self._reset()
+    def __init__(self, *args, **kw):
+        self._coeffs = {}           # (steps, order): coefficient table; tables are a function of the step count, so it outlives set_timesteps
+        super().__init__(*args, **kw)
 
     def _reset(self):
         self._ring = []             # previous derivatives, oldest first
 
     def set_timesteps(self, num_inference_steps, device=None, order=None):
         # scheduling_lms_discrete.py:191-215; order: also prepare the coefficient table of that order
-        self._set_tables(num_inference_steps)
-        self.num_inference_steps = num_inference_steps
+        super().set_timesteps(num_inference_steps)
         if order is not None:
             self.lms_coefficients(order)
-
-    def _step_index(self, timestep):
-        return self._positions(timestep)[0]
 
     def get_lms_coefficient(self, order, t, current_order):
         # scheduling_lms_discrete.py:169-189
@@ -1264,24 +1319,7 @@ def draw_step_noise(shape, generator, device, used):
     return None
 
 
-class _NoisySigmaMixin:
-    """`step(..., generator=, noise=)` of the stochastic sigma-space schedulers: the tensor `bd_sigma_noise_step` reads, given or
-    drawn (draw_step_noise), in the sample's layout"""
-
-    def _step_noise(self, noise, generator, model_output, used):
-        if noise is None:
-            noise = draw_step_noise(tuple(model_output.shape), generator, model_output.device, used)
-        if not used:
-            return None
-        if noise.dtype != torch.float32 or not noise.is_cuda:
-            raise TypeError(f"{type(self).__name__}.step: noise must be a float32 GPU tensor")
-        if self._flat(model_output)[1] == "nhwc":          # _align's layout: the model output's
-            q = noise.permute(0, 2, 3, 1)
-            return q if q.is_contiguous() else q.contiguous()
-        return noise.contiguous()
-
-
-class EulerDiscreteScheduler(_NoisySigmaMixin, _SigmaScheduler):
+class EulerDiscreteScheduler(_SigmaScheduler):
     """Euler's method in sigma space with Karras et al.'s churn (scheduling_euler_discrete.py:60-354, epsilon prediction, linear sigma
     interpolation).  gamma = min(s_churn / N, sqrt(2) - 1) inside [s_tmin, s_tmax], else 0.  gamma == 0 is one `bd_sigma_step`
     launch; gamma > 0 one `bd_sigma_noise_step` launch that first raises the sample to sigma_hat = sigma (gamma + 1) with
@@ -1289,26 +1327,14 @@ class EulerDiscreteScheduler(_NoisySigmaMixin, _SigmaScheduler):
     not at sigma_hat: parity with it is the contract here.  One noise tensor per `step` call on a CPU generator, used or not."""
     _KEYS = _SigmaScheduler._KEYS + ("interpolation_type", "use_karras_sigmas")
 
-    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
-                 prediction_type="epsilon", interpolation_type="linear", use_karras_sigmas=False, **unused):
+    def __init__(self, *args, interpolation_type="linear", use_karras_sigmas=False, **kw):
         if interpolation_type != "linear":
             raise NotImplementedError(f"EulerDiscreteScheduler: interpolation_type={interpolation_type!r} is not on the HIP path (linear only)")
         if use_karras_sigmas:
             raise NotImplementedError("EulerDiscreteScheduler: use_karras_sigmas is not on the HIP path")
-        self._init_common(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type)
+        super().__init__(*args, **kw)
         self.config.interpolation_type = interpolation_type
         self.config.use_karras_sigmas = False
-
-    def _set_tables(self, n):
-        self._finish_tables(*self._interp(n))
-
-    def set_timesteps(self, num_inference_steps, device=None):
-        # scheduling_euler_discrete.py:182-218
-        self._set_tables(num_inference_steps)
-        self.num_inference_steps = num_inference_steps
-
-    def _step_index(self, timestep):
-        return self._positions(timestep)[0]
 
     def _plan_scalars(self, k, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0):
         """the scalars of the step at position k, the reference's expressions on fp32 0-dim tensors: sigma_in (= sigma_hat), dt,
@@ -1323,39 +1349,14 @@ class EulerDiscreteScheduler(_NoisySigmaMixin, _SigmaScheduler):
     def step(self, model_output, timestep, sample, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0, generator=None,
              return_dict=True, noise=None, clip=None, scaled=False):
         # scheduling_euler_discrete.py:257-354
-        k = self._step_index(timestep)
-        eps, x, restore = self._begin_step(model_output, sample)
-        p = self._plan_scalars(k, s_churn, s_tmin, s_tmax, s_noise)
-        z = self._step_noise(noise, generator, model_output, p["churn"] is not None)
-        sc = torch.empty_like(x) if scaled else None
-        if p["churn"] is None:
-            prev = ops.sigma_step(eps, x, p["sigma_in"], p["dt"], p["in_div"], scaled_out=sc, clip=clip)
-        else:
-            prev = ops.sigma_noise_step(eps, x, z, p["sigma_in"], p["dt"], p["in_div"], churn=p["churn"], scaled_out=sc,
-                                        clip=clip)
-        return self._output(prev, restore, return_dict, scaled_sample=sc)
+        return self._planned_step(model_output, timestep, sample, generator, noise, return_dict, clip, scaled, s_churn, s_tmin, s_tmax, s_noise)
 
 
-class EulerAncestralDiscreteScheduler(_NoisySigmaMixin, _SigmaScheduler):
+class EulerAncestralDiscreteScheduler(_SigmaScheduler):
     """Ancestral sampling with Euler steps (scheduling_euler_ancestral_discrete.py:60-281, epsilon prediction): a deterministic Euler
     step from sigma down to sigma_down < sigma_next, then fresh noise of standard deviation sigma_up, so that the sample lands on
     sigma_next.  One `bd_sigma_noise_step` launch per step; sigma_up and sigma_down are the reference's expressions on fp32 0-dim
     tensors."""
-
-    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
-                 prediction_type="epsilon", **unused):
-        self._init_common(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type)
-
-    def _set_tables(self, n):
-        self._finish_tables(*self._interp(n))
-
-    def set_timesteps(self, num_inference_steps, device=None):
-        # scheduling_euler_ancestral_discrete.py:170-191
-        self._set_tables(num_inference_steps)
-        self.num_inference_steps = num_inference_steps
-
-    def _step_index(self, timestep):
-        return self._positions(timestep)[0]
 
     def _plan_scalars(self, k):
         """sigma_in, dt = sigma_down - sigma, in_div and sigma_up of the step at position k"""
@@ -1367,14 +1368,7 @@ class EulerAncestralDiscreteScheduler(_NoisySigmaMixin, _SigmaScheduler):
 
     def step(self, model_output, timestep, sample, generator=None, return_dict=True, noise=None, clip=None, scaled=False):
         # scheduling_euler_ancestral_discrete.py:193-281
-        k = self._step_index(timestep)
-        eps, x, restore = self._begin_step(model_output, sample)
-        p = self._plan_scalars(k)
-        z = self._step_noise(noise, generator, model_output, True)
-        sc = torch.empty_like(x) if scaled else None
-        prev = ops.sigma_noise_step(eps, x, z, p["sigma_in"], p["dt"], p["in_div"], sigma_up=p["sigma_up"], scaled_out=sc,
-                                    clip=clip)
-        return self._output(prev, restore, return_dict, scaled_sample=sc)
+        return self._planned_step(model_output, timestep, sample, generator, noise, return_dict, clip, scaled)
 
 
 class _KDPM2Base(_SigmaScheduler):
@@ -1386,10 +1380,10 @@ class _KDPM2Base(_SigmaScheduler):
     `sigmas_interpol` (and the ancestral ones) have the reference's layout: the first entry once, every later one twice, the last
     once more.  Entries of `timesteps` may be equal (KDPM2-ancestral's sigma_interpol is sigma_next to within rounding): a timestep
     resolves to its last position in the first order state and to its first otherwise, and `step` checks the state against the
-    position's parity."""
-
-    def _init_kdpm2(self, num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type):
-        self._init_common(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type)
+    position's parity.  `_stage` is the sample a first order stage started from, waiting for its second stage.  The defaults are the
+    reference's (beta_start=0.00085, beta_end=0.012)."""
+    _BETAS = (0.00085, 0.012)
+    _two_stage = True
 
     @staticmethod
     def _twice(v):
@@ -1421,49 +1415,12 @@ class _KDPM2Base(_SigmaScheduler):
         # more entry for what follows the last position (sigma_interpol = 0 there)
         self._in_div = [float(((self.sigmas[k] if k % 2 == 0 else flat[interpol_of_odd(k)]) ** 2 + 1) ** 0.5)
                         for k in range(len(self.timesteps) + 1)]
-        self._reset()
-
-    def _reset(self):
-        self._stage = None          # the sample a first order stage started from, waiting for its second stage
-
-    def set_timesteps(self, num_inference_steps, device=None):
-        self._set_tables(num_inference_steps)
-        self.num_inference_steps = num_inference_steps
-
-    @property
-    def state_in_first_order(self):
-        return self._stage is None
-
-    def _step_index(self, timestep):
-        pos = self._positions(timestep)
-        return pos[-1] if self.state_in_first_order else pos[0]
-
-    def _check_stage(self, k):
-        """the state against the parity of position k (before anything touches the GPU); True in a first order stage"""
-        first = self.state_in_first_order
-        if first != (k % 2 == 0):
-            raise ValueError(f"{type(self).__name__}.step: position {k} of the schedule is "
-                             f"{'a first order' if k % 2 == 0 else 'a second'} stage, the scheduler is in the other state")
-        return first
-
-    def _kept_sample(self, first, x):
-        """None in a first order stage, else the sample the transition started from, which must stand beside x in one launch"""
-        if first:
-            return None
-        if not self._fits(self._stage, x):
-            raise ValueError(f"{type(self).__name__}.step: the stored first stage does not have this sample's shape and layout "
-                             "(one chain per set_timesteps)")
-        return self._stage
 
 
 class KDPM2DiscreteScheduler(_KDPM2Base):
     """KDPM2 (scheduling_k_dpm_2_discrete.py:60-310, epsilon prediction): deterministic, both stages on `bd_sigma_step`.
     sigma_interpol is the geometric mean of sigma and sigma_next (a log-lerp with the rolled sigmas).  N steps cost 2N - 1 UNet
-    evaluations.  The defaults are the reference's (beta_start=0.00085, beta_end=0.012)."""
-
-    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="linear", trained_betas=None,
-                 prediction_type="epsilon", **unused):
-        self._init_kdpm2(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type)
+    evaluations."""
 
     def _set_tables(self, n):
         # scheduling_k_dpm_2_discrete.py:152-203
@@ -1482,27 +1439,16 @@ class KDPM2DiscreteScheduler(_KDPM2Base):
 
     def step(self, model_output, timestep, sample, return_dict=True, clip=None, scaled=False):
         # scheduling_k_dpm_2_discrete.py:232-310
-        k = self._step_index(timestep)
-        first = self._check_stage(k)
-        eps, x, restore = self._begin_step(model_output, sample)
-        p = self._plan_scalars(k)
-        sc = torch.empty_like(x) if scaled else None
-        prev = ops.sigma_step(eps, x, p["sigma_in"], p["dt"], p["in_div"], base=self._kept_sample(first, x), scaled_out=sc, clip=clip)
-        self._stage = x if first else None
-        return self._output(prev, restore, return_dict, scaled_sample=sc)
+        return self._planned_step(model_output, timestep, sample, None, None, return_dict, clip, scaled)
 
 
-class KDPM2AncestralDiscreteScheduler(_NoisySigmaMixin, _KDPM2Base):
+class KDPM2AncestralDiscreteScheduler(_KDPM2Base):
     """KDPM2 with ancestral sampling (scheduling_k_dpm_2_ancestral_discrete.py:60-329, epsilon prediction): the first stage runs on
     `bd_sigma_step` towards sigma_interpol, the geometric mean of sigma and sigma_down; the second on `bd_sigma_noise_step`, from
     the kept sample with dt = sigma_down - sigma and noise of standard deviation sigma_up.  The reference draws a noise tensor in
     both stages and uses the second's; with a CPU generator so does `step`.  The last entries of `sigmas_up` are NaN (0 * 0 / 0) in
     the reference and here, and are never read.  num_inference_steps < 3 is refused: at 2 the reference's schedule holds a NaN
     timestep and its chain fails."""
-
-    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="linear", trained_betas=None,
-                 prediction_type="epsilon", **unused):
-        self._init_kdpm2(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type)
 
     def _set_tables(self, n):
         # scheduling_k_dpm_2_ancestral_discrete.py:153-214
@@ -1532,20 +1478,7 @@ class KDPM2AncestralDiscreteScheduler(_NoisySigmaMixin, _KDPM2Base):
 
     def step(self, model_output, timestep, sample, generator=None, return_dict=True, noise=None, clip=None, scaled=False):
         # scheduling_k_dpm_2_ancestral_discrete.py:243-329
-        k = self._step_index(timestep)
-        first = self._check_stage(k)
-        eps, x, restore = self._begin_step(model_output, sample)
-        p = self._plan_scalars(k)
-        z = self._step_noise(noise, generator, model_output, not first)
-        sc = torch.empty_like(x) if scaled else None
-        if first:
-            prev = ops.sigma_step(eps, x, p["sigma_in"], p["dt"], p["in_div"], scaled_out=sc, clip=clip)
-        else:
-            prev = ops.sigma_noise_step(eps, x, z, p["sigma_in"], p["dt"], p["in_div"], base=self._kept_sample(first, x),
-                                        sigma_up=p["sigma_up"],
-                                        scaled_out=sc, clip=clip)
-        self._stage = x if first else None
-        return self._output(prev, restore, return_dict, scaled_sample=sc)
+        return self._planned_step(model_output, timestep, sample, generator, noise, return_dict, clip, scaled)
 
 
 class SchedulerConfigCarrier(DDPMScheduler):

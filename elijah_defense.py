@@ -30,12 +30,10 @@ from typing import Union
 
 import torch
 
-from baddiffusion_amd import defense, pipelines
+from baddiffusion_amd import defense
 from baddiffusion_amd.inversion import invert_trigger
 from baddiffusion_amd.model import DiffuserModelSched, save_scheduler, save_unet
-from baddiffusion_amd.pipelines import DDIMPipeline, DDPMPipeline, DEISPipeline, DPMSolverPipeline, HeunPipeline, LMSPipeline, UniPCPipeline
-from baddiffusion_amd.schedulers import (DDIMScheduler, DDPMScheduler, DEISMultistepScheduler, DPMSolverMultistepScheduler,
-                                          HeunDiscreteScheduler, LMSDiscreteScheduler, UniPCMultistepScheduler)
+from baddiffusion_amd.sched_names import ELIJAH_CHOICES as SCHED_CHOICES, SCHEDS
 
 
 @dataclass
@@ -74,9 +72,6 @@ class Config:
     dyn_threshold_ratio: float = 0.995
 
 
-SCHED_CHOICES = [DiffuserModelSched.DDIM_SCHED, DiffuserModelSched.DDPM_SCHED] + sorted(DiffuserModelSched._DPM_SCHEDS) + \
-    sorted(DiffuserModelSched._UNIPC_SCHEDS) + sorted(DiffuserModelSched._DEIS_SCHEDS) + sorted(DiffuserModelSched._SIGMA_SCHEDS) + \
-    sorted(DiffuserModelSched._KDIFF_SCHEDS)
 DEFAULT_ASR_THRESHOLD = 1e-3    # of the order the papers use; a choice, not a finding
 
 
@@ -146,29 +141,16 @@ def get_config(argv=None):
 
 
 def make_pipeline(config, model, noise_sched):
-    if config.sched in DiffuserModelSched._DPM_SCHEDS:
-        order, algorithm = DiffuserModelSched._DPM_SCHEDS[config.sched]
-        sched = DPMSolverMultistepScheduler.from_config({**noise_sched.config, "solver_order": order, "algorithm_type": algorithm})
-        return DPMSolverPipeline(unet=model, scheduler=sched)
-    if config.sched in DiffuserModelSched._UNIPC_SCHEDS:
-        sched = UniPCMultistepScheduler.from_config({**noise_sched.config, "solver_order": DiffuserModelSched._UNIPC_SCHEDS[config.sched]})
-        return UniPCPipeline(unet=model, scheduler=sched)
-    if config.sched in DiffuserModelSched._DEIS_SCHEDS:
-        sched = DEISMultistepScheduler.from_config({**noise_sched.config, "solver_order": DiffuserModelSched._DEIS_SCHEDS[config.sched]})
-        return DEISPipeline(unet=model, scheduler=sched)
-    if config.sched in DiffuserModelSched._SIGMA_SCHEDS:
-        cls_name, order = DiffuserModelSched._SIGMA_SCHEDS[config.sched]
-        if cls_name == "HeunDiscreteScheduler":
-            return HeunPipeline(unet=model, scheduler=HeunDiscreteScheduler.from_config(noise_sched.config))
-        return LMSPipeline(unet=model, scheduler=LMSDiscreteScheduler.from_config(noise_sched.config), order=order)
-    if config.sched in DiffuserModelSched._KDIFF_SCHEDS:       # the pipeline converts the scheduler from its config
-        return getattr(pipelines, DiffuserModelSched._KDIFF_SCHEDS[config.sched][1])(unet=model, scheduler=noise_sched)
-    if config.dyn_threshold is not None:
-        # a sampling scheduler of its own: the checkpoint's scheduler, which is saved back with the repaired model, keeps its config
-        cls = DDIMScheduler if config.sched == DiffuserModelSched.DDIM_SCHED else DDPMScheduler
-        noise_sched = cls(**noise_sched.config)
+    """the sampling pipeline of config.sched over the checkpoint's scheduler config; always the native scheduler of a name that has one"""
+    rec = SCHEDS[config.sched]
+    if not rec.dyn_threshold:
+        noise_sched = rec.scheduler.from_config({**noise_sched.config, **rec.sched_kw})
+    elif config.dyn_threshold is not None:
+        # DDPM-SCHED, DDIM-SCHED: the checkpoint's scheduler as it is, unless thresholding asks for a sampling scheduler of its own --
+        # the checkpoint's, which is saved back with the repaired model, keeps its config
+        noise_sched = rec.scheduler(**noise_sched.config)
         DiffuserModelSched._set_dyn_threshold(noise_sched, config.dyn_threshold, config.dyn_threshold_ratio)
-    return (DDIMPipeline if config.sched == DiffuserModelSched.DDIM_SCHED else DDPMPipeline)(unet=model, scheduler=noise_sched)
+    return rec.pipeline(unet=model, scheduler=noise_sched, **rec.pipe_kw)
 
 
 def invert(config, model, noise_sched, log=print):

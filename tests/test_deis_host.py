@@ -297,8 +297,10 @@ def test_sched_name_wiring():
     from baddiffusion_amd.pipelines import DEISPipeline, PNDMPipeline
     from baddiffusion_amd.schedulers import DEISMultistepScheduler, PNDMScheduler, SchedulerConfigCarrier
     D = DiffuserModelSched
-    assert D._DEIS_SCHEDS == DEIS_NAMES
-    assert not set(DEIS_NAMES) & (set(D._PNDM_SCHEDS) | set(D._DPM_SCHEDS) | set(D._UNIPC_SCHEDS) | set(D._SIGMA_SCHEDS) | set(D._OTHER_SCHEDS))
+    from baddiffusion_amd.sched_names import SCHEDS
+    assert {n: r.sched_kw["solver_order"] for n, r in SCHEDS.items() if r.scheduler is DEISMultistepScheduler} == DEIS_NAMES
+    # no PNDM conversion, not native-only, not refused
+    assert all(SCHEDS[n].carrier is None and not SCHEDS[n].native_only and SCHEDS[n].refused is None for n in DEIS_NAMES)
     get = lambda name, **kw: D.get_pretrained("DDPM-CIFAR10-32", noise_sched_type=name, allow_random_init=True, **kw)      # noqa: E731
     for name, order in DEIS_NAMES.items():
         for native in (False, True):

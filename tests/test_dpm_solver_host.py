@@ -223,7 +223,9 @@ def test_native_sched_wiring():
     from baddiffusion_amd.model import DiffuserModelSched
     from baddiffusion_amd.pipelines import DDIMPipeline, DPMSolverPipeline, PNDMPipeline
     from baddiffusion_amd.schedulers import DDIMScheduler, DPMSolverMultistepScheduler, PNDMScheduler, SchedulerConfigCarrier
-    assert DiffuserModelSched._DPM_SCHEDS == DPM_NAMES
+    from baddiffusion_amd.sched_names import SCHEDS
+    assert {n: (r.sched_kw["solver_order"], r.sched_kw["algorithm_type"]) for n, r in SCHEDS.items() if r.native_only} == DPM_NAMES
+    assert all(SCHEDS[n].scheduler is DPMSolverMultistepScheduler for n in DPM_NAMES)
     get = lambda name, **kw: DiffuserModelSched.get_pretrained("DDPM-CIFAR10-32", noise_sched_type=name, allow_random_init=True, **kw)
     # without the opt-in: the reference's conversion to PNDM, as before
     m, s, gp = get("DPM_SOLVER_PP_O2-SCHED", clip_sample=True)

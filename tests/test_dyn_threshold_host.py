@@ -289,9 +289,9 @@ def test_factory_takes_dyn_threshold():
         m, s, _ = get(name)
         assert s.config.thresholding is False and s.config.sample_max_value == 1.0
         del m
-    others = sorted(set(DiffuserModelSched._PNDM_SCHEDS) | set(DiffuserModelSched._UNIPC_SCHEDS) | set(DiffuserModelSched._DEIS_SCHEDS)
-                    | set(DiffuserModelSched._SIGMA_SCHEDS) | set(DiffuserModelSched._OTHER_SCHEDS))
-    assert len(others) > 20
+    from baddiffusion_amd.sched_names import SCHEDS
+    others = sorted(set(SCHEDS) - {"DDPM-SCHED", "DDIM-SCHED"})
+    assert len(others) > 20 and not any(SCHEDS[name].dyn_threshold for name in others)
     for name in others:
         for native in (False, True):
             with pytest.raises(NotImplementedError, match=f"dyn_threshold with {name}: dynamic thresholding runs in the DDPM and DDIM steps only"):

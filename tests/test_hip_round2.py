@@ -738,8 +738,8 @@ def test_pndm_scheduler_and_pipeline_vs_reference(gpu, golden):
     and PNDMPipeline (built from a DPM-Solver config carrier, as model.py:598-630 does) on the small UNet with and without
     the post-step clip, vs the images the reference's PNDMPipeline produced."""
     from baddiffusion_amd import ops
-    from baddiffusion_amd.model import DiffuserModelSched
     from baddiffusion_amd.pipelines import PNDMPipeline
+    from baddiffusion_amd.sched_names import SCHEDS
     from baddiffusion_amd.schedulers import PNDMScheduler, SchedulerConfigCarrier
     g = golden("pndm")
     x0 = C.pndm_init()
@@ -776,7 +776,9 @@ def test_pndm_scheduler_and_pipeline_vs_reference(gpu, golden):
         ref = g[f"pipe6_{int(clip)}"]
         assert r.images.shape == ref.shape
         assert float(np.abs(r.images - ref).max()) < 2e-3, (clip, float(np.abs(r.images - ref).max()))
-    assert set(DiffuserModelSched._PNDM_SCHEDS) >= {"DPM_SOLVER_PP_O2-SCHED", "UNIPC-SCHED", "PNDM-SCHED", "HEUN-SCHED"}
+    # the names that sample through PNDMPipeline without native_sched
+    assert {n for n, r in SCHEDS.items() if r.carrier is not None or r.pipeline is PNDMPipeline} >= \
+        {"DPM_SOLVER_PP_O2-SCHED", "UNIPC-SCHED", "PNDM-SCHED", "HEUN-SCHED"}
 
 
 def test_celeba256_glasses_to_cat_poisoned_step(gpu, golden):

@@ -448,7 +448,8 @@ def test_command_line_sampling(gpu, tmp_path, monkeypatch, name):
     """baddiffusion.py --mode sampling --sched <name> --infer_steps 3 on a run directory of the small network: the pipeline it samples
     with is the sampler's own at that step count, and the grids are written"""
     import baddiffusion as cli
-    from baddiffusion_amd.model import DiffuserModelSched, save_scheduler, save_unet
+    from baddiffusion_amd.model import save_scheduler, save_unet
+    from baddiffusion_amd.sched_names import SCHEDS
     from baddiffusion_amd.schedulers import DDPMScheduler
     from baddiffusion_amd.unet import unet_from_config
     cfg = dataclasses.replace(C.SMALL_CFGS[CK.UNET_CFG], sample_size=32)
@@ -467,7 +468,7 @@ def test_command_line_sampling(gpu, tmp_path, monkeypatch, name):
         return real(cfg_, name_, pipeline, dsl)
     monkeypatch.setattr(cli, "sampling", spy)
     cli.main(["--mode", "sampling", "--ckpt", run, "--sched", name, "--infer_steps", "3"])
-    sched_cls, pipe_cls = DiffuserModelSched._KDIFF_SCHEDS[name]
+    sched_cls, pipe_cls = SCHEDS[name].scheduler.__name__, SCHEDS[name].pipeline.__name__
     draws = {"EULER_O1-SCHED": 3, "EULER_A_O1-SCHED": 3, "KDPM2_O2-SCHED": 0, "KDPM2_A_O2-SCHED": 5}[name]
     assert seen == [(pipe_cls, sched_cls, draws)]
     for folder in ("samples", "backdoor_samples"):

@@ -280,10 +280,11 @@ def test_dyn_threshold_is_refused_with_the_names():
 # ---------------------------------------------------------------------------------------------------- wiring
 def test_sched_name_wiring():
     from baddiffusion_amd.model import DiffuserModelSched
-    assert DiffuserModelSched._KDIFF_SCHEDS == KDIFF_NAMES
-    others = (DiffuserModelSched._PNDM_SCHEDS, DiffuserModelSched._DPM_SCHEDS, DiffuserModelSched._UNIPC_SCHEDS,
-              DiffuserModelSched._DEIS_SCHEDS, DiffuserModelSched._SIGMA_SCHEDS)
-    assert not any(set(KDIFF_NAMES) & set(o) for o in others)
+    from baddiffusion_amd.sched_names import SCHEDS
+    family = {classes(sampler)[0] for sampler in SAMPLER_OF}
+    assert {n: (r.scheduler.__name__, r.pipeline.__name__) for n, r in SCHEDS.items() if r.scheduler in family} == KDIFF_NAMES
+    # no PNDM conversion, with or without native_sched, and nothing refused
+    assert all(SCHEDS[n].carrier is None and not SCHEDS[n].native_only and SCHEDS[n].refused is None for n in KDIFF_NAMES)
     get = lambda name, **kw: DiffuserModelSched.get_pretrained("DDPM-CIFAR10-32", noise_sched_type=name, allow_random_init=True, **kw)
     for sampler, name in SAMPLER_OF.items():
         cls, pipe = classes(sampler)

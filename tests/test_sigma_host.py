@@ -229,9 +229,11 @@ def test_sched_name_wiring():
     from baddiffusion_amd.model import DiffuserModelSched
     from baddiffusion_amd.pipelines import HeunPipeline, LMSPipeline, PNDMPipeline
     from baddiffusion_amd.schedulers import HeunDiscreteScheduler, LMSDiscreteScheduler, PNDMScheduler, SchedulerConfigCarrier
-    assert DiffuserModelSched._SIGMA_SCHEDS == SIGMA_NAMES
-    assert not set(SIGMA_NAMES) & (set(DiffuserModelSched._PNDM_SCHEDS) | set(DiffuserModelSched._DPM_SCHEDS) |
-                                   set(DiffuserModelSched._UNIPC_SCHEDS))
+    from baddiffusion_amd.sched_names import SCHEDS
+    # Heun's order is no parameter of its record: it is what the class does
+    assert {n: (r.scheduler.__name__, r.pipe_kw.get("order", 2 if r.scheduler is HeunDiscreteScheduler else None))
+            for n, r in SCHEDS.items() if r.scheduler in (HeunDiscreteScheduler, LMSDiscreteScheduler)} == SIGMA_NAMES
+    assert all(SCHEDS[n].carrier is None and not SCHEDS[n].native_only for n in SIGMA_NAMES)     # no PNDM conversion, not native-only
     get = lambda name, **kw: DiffuserModelSched.get_pretrained("DDPM-CIFAR10-32", noise_sched_type=name, allow_random_init=True, **kw)
     for name, (cls_name, order) in SIGMA_NAMES.items():
         cls, pipe = (HeunDiscreteScheduler, HeunPipeline) if cls_name == "HeunDiscreteScheduler" else (LMSDiscreteScheduler, LMSPipeline)

@@ -312,8 +312,9 @@ def test_sched_name_wiring():
     from baddiffusion_amd.model import DiffuserModelSched
     from baddiffusion_amd.pipelines import PNDMPipeline, UniPCPipeline
     from baddiffusion_amd.schedulers import PNDMScheduler, SchedulerConfigCarrier, UniPCMultistepScheduler
-    assert DiffuserModelSched._UNIPC_SCHEDS == UNIPC_NAMES
-    assert not set(UNIPC_NAMES) & (set(DiffuserModelSched._PNDM_SCHEDS) | set(DiffuserModelSched._DPM_SCHEDS))
+    from baddiffusion_amd.sched_names import SCHEDS
+    assert {n: r.sched_kw["solver_order"] for n, r in SCHEDS.items() if r.scheduler is UniPCMultistepScheduler} == UNIPC_NAMES
+    assert all(SCHEDS[n].carrier is None and not SCHEDS[n].native_only for n in UNIPC_NAMES)     # no PNDM conversion, not native-only
     get = lambda name, **kw: DiffuserModelSched.get_pretrained("DDPM-CIFAR10-32", noise_sched_type=name, allow_random_init=True, **kw)
     for name, order in UNIPC_NAMES.items():
         for native in (False, True):
