@@ -233,6 +233,12 @@ class ImagePairDesc(C.Structure):
     _fields_ = [("N", i32), ("C", i32), ("H", i32), ("W", i32), ("preds", vp), ("p_stride", i64 * 4), ("target", vp), ("t_stride", i64 * 4)]
 
 
+class VbTermsDesc(C.Structure):
+    _fields_ = [("N", i32), ("C", i32), ("H", i32), ("W", i32), ("x0", vp), ("x0_stride", i64 * 4), ("x_t", vp), ("xt_stride", i64 * 4),
+                ("eps", vp), ("eps_stride", i64 * 4), ("t", vp), ("t_host", vp), ("alphas_cumprod", vp), ("T", i32),
+                ("term_add", vp), ("term_mul", vp), ("inv_sigma_dec", f32), ("clip_denoised", i32), ("bits", vp), ("x0_mse", vp)]
+
+
 class UnetConfig(C.Structure):
     _fields_ = [("sample_size", i32), ("in_channels", i32), ("out_channels", i32), ("num_blocks", i32),
                 ("block_out_channels", i32 * 8), ("down_attn", i32 * 8), ("up_attn", i32 * 8),
@@ -283,6 +289,8 @@ SIGNATURES = {
     "bd_image_loss": (i32, [C.POINTER(ImagePairDesc), i32, vp, vp, sz, vp]),
     "bd_ssim_images_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "bd_ssim_images": (i32, [C.POINTER(ImagePairDesc), f32, vp, vp, sz, vp]),
+    "bd_vb_terms_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "bd_vb_terms": (i32, [C.POINTER(VbTermsDesc), vp, sz, vp]),
     "bd_conv2d_nhwc": (i32, [C.POINTER(Conv2dDesc), vp]),
     "bd_pool2d_nhwc": (i32, [vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "bd_resize_bilinear_nhwc": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, i32, f32, f32, vp]),

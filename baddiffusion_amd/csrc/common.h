@@ -114,6 +114,18 @@ __device__ __forceinline__ void loss_elem(int type, float df, float& l, float& g
     else { float ad = fabsf(df); if (ad < 1.0f) { l = 0.5f * df * df; g = df; } else { l = ad - 0.5f; g = df > 0.f ? 1.f : -1.f; } }
 }
 
+// ---- the predicted x0 of an epsilon model, x0 = (x - sqrt(1 - a_t) e) / sqrt(a_t): ddpm_step_kernel, ddim_step_kernel, abs_quantile_kernel
+// (elementwise.hip) and vb_terms_kernel (metrics.hip) all form it here, so the value the quantile ranks is bitwise the value the step clamps
+// and the value the variational bound scores.
+struct X0Coef { float sb, sa; };
+__device__ __forceinline__ X0Coef x0_coef(const float* alphas_cumprod, int t) {
+    const float a_t = alphas_cumprod[t];
+    X0Coef k;
+    k.sb = sqrtf(1.0f - a_t); k.sa = sqrtf(a_t);
+    return k;
+}
+__device__ __forceinline__ float x0_pred(const X0Coef& k, float x, float e) { return (x - k.sb * e) / k.sa; }
+
 // ---- predicated loads without control flow and without a dependent select: masked-off lanes read zero bytes that live in the code
 // object.  Branch-free loads keep the s_waitcnt vmcnt() counting exact, and nothing touches the loaded registers until their first
 // use, which the register prefetch of the igemm kernels depends on (a skipped load would force vmcnt(0) at the join, a select would

@@ -119,16 +119,7 @@ __global__ __launch_bounds__(TPB) void nhwc_to_nchw_kernel(const float* src, int
 // a-5: DDPM reverse step (scheduling_ddpm.py:350-415).  Coefficients recomputed per thread from the
 // device table in the same fp32 order the reference uses on 0-dim CPU tensors.
 // ------------------------------------------------------------------------------------------------
-// The predicted x0 of an epsilon model, x0 = (x - sqrt(1 - a_t) e) / sqrt(a_t): ddpm_step_kernel, ddim_step_kernel and abs_quantile_kernel
-// all form it here, so the value the quantile ranks is bitwise the value the step clamps.
-struct X0Coef { float sb, sa; };
-__device__ __forceinline__ X0Coef x0_coef(const float* alphas_cumprod, int t) {
-    const float a_t = alphas_cumprod[t];
-    X0Coef k;
-    k.sb = sqrtf(1.0f - a_t); k.sa = sqrtf(a_t);
-    return k;
-}
-__device__ __forceinline__ float x0_pred(const X0Coef& k, float x, float e) { return (x - k.sb * e) / k.sa; }
+// (X0Coef, x0_coef, x0_pred: common.h)
 // dynamic thresholding (scheduling_ddpm.py:313-318): s = clamp(q, 1, sample_max_value), a NaN quantile staying NaN (fmaxf would drop it);
 // x0 = clamp(x0, -s, s) / s, a true division
 __device__ __forceinline__ float x0_threshold(float x0, float q, float smax) {

@@ -151,14 +151,122 @@ __global__ __launch_bounds__(256) void ssim_images_tile_kernel(ImgPair d, long l
     if (threadIdx.x == 0) partial[(nc * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = r;
 }
 
-// one workgroup per image: out[n] = (float)(sum of the image's `per` partials / count), thread-strided and through the tree (index order)
-__global__ __launch_bounds__(256) void image_fold_kernel(const double* __restrict__ partial, int per, double count, float* __restrict__ out) {
+// What bd_vb_terms makes of an image's mean m: bits = (add[t] + mul[t] * m) / ln 2, in fp64, rounded to fp32 once
+struct VbFinish { const long long* t; const float* add; const float* mul; int T; };
+__device__ __forceinline__ float vb_finish(const VbFinish& f, long long n, double mean) {
+    const long long t = f.t[n];
+    if (t < 0 || t > f.T) return __builtin_nanf("");
+    return (float)(((double)f.add[t] + (double)f.mul[t] * mean) * 1.4426950408889634074);
+}
+
+// one workgroup per image: out[n] = (float)(sum of the image's `per` partials / count), thread-strided and through the tree (index order);
+// VB: the mean goes through vb_finish instead
+template <bool VB>
+__global__ __launch_bounds__(256) void image_fold_kernel(const double* __restrict__ partial, int per, double count, float* __restrict__ out,
+                                                         VbFinish f) {
     __shared__ double red[256];
     const double* __restrict__ q = partial + (long long)blockIdx.x * per;
     double a = 0.0;
     for (int i = threadIdx.x; i < per; i += 256) a += q[i];
     const double r = block_sum256(a, red);
-    if (threadIdx.x == 0) out[blockIdx.x] = (float)(r / count);
+    if (threadIdx.x == 0) out[blockIdx.x] = VB ? vb_finish(f, blockIdx.x, r / count) : (float)(r / count);
+}
+
+// ---- variational-bound terms (bd_vb_terms; DESIGN.md section 3, "Bits per dimension") ---------------------------------------------------------------
+// The reduction of image_loss_kernel over three streams.  A workgroup belongs to one image, hence to one t: the row kind is uniform and a
+// KL or prior workgroup never enters the erfc path.  The t = 0 element is evaluated in fp64 (difference, z, erfc, log): the kernel is
+// bound by its 12 B per element, the fp64 path is taken by one row in T + 1 of a full evaluation, and it leaves the all-floor case exact.
+struct VbArgs {
+    int C, H, W, clip;
+    const float* x0; long long s0[4];
+    const float* xt; long long st[4];
+    const float* ep; long long se[4];
+    const float* ac;
+    double inv_sigma;
+    VbFinish f;
+};
+enum { VB_KL = 0, VB_DEC = 1, VB_PRIOR = 2 };
+
+// -log P of the discretised Gaussian decoder (bd_hip.h): both erfc arguments on the tail side, the floor by comparison (fmax would drop a NaN)
+__device__ __forceinline__ double vb_dec_nll(float x0, float xh, double inv_sigma) {
+    const double r2 = 0.70710678118654752440;
+    const double df = (double)x0 - (double)xh;
+    const double zp = (df + 1.0 / 255.0) * inv_sigma, zm = (df - 1.0 / 255.0) * inv_sigma;
+    const bool lo = (double)x0 < -0.999, hi = (double)x0 > 0.999, tail = zm > 0.0;
+    const double a = lo ? -zp : (hi || tail) ? zm : -zp;
+    const double b = tail ? zp : -zm;
+    const double eb = erfc(b * r2);
+    double P = 0.5 * (erfc(a * r2) - ((lo || hi) ? 0.0 : eb));
+    P = P < 1e-12 ? 1e-12 : P;
+    return -log(P);
+}
+
+// the walk of image_loss_kernel for one row kind: the workgroup's sum of the term's elements (and of (x0 - x0_hat)^2 when MSE), on thread 0
+template <int KIND, bool MSE>
+__device__ __forceinline__ void vb_walk(const VbArgs& d, long long n, int t, unsigned total, unsigned dc, unsigned dh, unsigned dw, double* red,
+                                        double& sum, double& sq) {
+    const float* __restrict__ p0 = d.x0 + n * d.s0[0];
+    const float* __restrict__ pt = KIND == VB_PRIOR ? nullptr : d.xt + n * d.st[0];
+    const float* __restrict__ pe = KIND == VB_PRIOR ? nullptr : d.ep + n * d.se[0];
+    X0Coef k = {0.f, 1.f};
+    if (KIND != VB_PRIOR) k = x0_coef(d.ac, t);
+    const unsigned H = (unsigned)d.H, W = (unsigned)d.W;
+    const unsigned beg = blockIdx.x * (unsigned)IL_CHUNK + threadIdx.x;
+    const unsigned end = total - blockIdx.x * (unsigned)IL_CHUNK < (unsigned)IL_CHUNK ? total : (blockIdx.x + 1u) * (unsigned)IL_CHUNK;
+    unsigned q = beg / W, w = beg - q * W, c = q / H, h = q - c * H;
+    double acc = 0.0, acc2 = 0.0;
+#pragma unroll 4
+    for (unsigned i = beg; i < end; i += 256) {
+        const float v = p0[c * d.s0[1] + h * d.s0[2] + w * d.s0[3]];
+        if (KIND == VB_PRIOR) {
+            acc += (double)(v * v);
+        } else {
+            float xh = x0_pred(k, pt[c * d.st[1] + h * d.st[2] + w * d.st[3]], pe[c * d.se[1] + h * d.se[2] + w * d.se[3]]);
+            if (d.clip) xh = xh < -1.0f ? -1.0f : (xh > 1.0f ? 1.0f : xh);          // comparisons: a NaN stays a NaN
+            const float df = v - xh;
+            if (KIND == VB_KL) {
+                acc += (double)(df * df);
+            } else {
+                acc += vb_dec_nll(v, xh, d.inv_sigma);
+                if (MSE) acc2 += (double)(df * df);
+            }
+        }
+        w += dw;
+        if (w >= W) { w -= W; ++h; }
+        h += dh; c += dc;
+        if (h >= H) { h -= H; ++c; }
+    }
+    sum = block_sum256(acc, red);
+    if (KIND == VB_DEC && MSE) {
+        __syncthreads();
+        sq = block_sum256(acc2, red);
+    } else {
+        sq = sum;
+    }
+}
+
+// grid (nchunk, images of this launch), as image_loss_kernel.  part: [2][N][nchunk] (term sums, squared-difference sums) when nchunk > 1.
+template <bool MSE>
+__global__ __launch_bounds__(256) void vb_terms_kernel(VbArgs d, int n0, int N, unsigned total, int nchunk, unsigned dc, unsigned dh, unsigned dw,
+                                                       double* __restrict__ part, float* __restrict__ bits, float* __restrict__ mse) {
+    __shared__ double red[256];
+    const long long n = (long long)n0 + blockIdx.y;
+    const long long tl = d.f.t[n];
+    const int t = (int)tl;
+    double sum, sq;
+    if (tl < 0 || tl > d.f.T) sum = sq = __builtin_nan("");     // the launcher checked the host copy; a device array that differs reads no table
+    else if (t == d.f.T) vb_walk<VB_PRIOR, MSE>(d, n, t, total, dc, dh, dw, red, sum, sq);
+    else if (t == 0) vb_walk<VB_DEC, MSE>(d, n, t, total, dc, dh, dw, red, sum, sq);
+    else vb_walk<VB_KL, MSE>(d, n, t, total, dc, dh, dw, red, sum, sq);
+    if (threadIdx.x == 0) {
+        if (nchunk == 1) {
+            bits[n] = vb_finish(d.f, n, sum / (double)total);
+            if (MSE) mse[n] = (float)(sq / (double)total);
+        } else {
+            part[n * nchunk + blockIdx.x] = sum;
+            if (MSE) part[((long long)N + n) * nchunk + blockIdx.x] = sq;
+        }
+    }
 }
 
 // the checks both launchers share; `who` names the entry point
@@ -470,7 +578,7 @@ extern "C" int bd_image_loss(const bd_image_pair_desc* d, int loss_type, float* 
         BD_LAUNCH_CHECK("image_loss");
     }
     if (nchunk > 1) {
-        hipLaunchKernelGGL(image_fold_kernel, dim3((unsigned)d->N), dim3(256), 0, S(stream), part, nchunk, (double)total, out);
+        hipLaunchKernelGGL(image_fold_kernel<false>, dim3((unsigned)d->N), dim3(256), 0, S(stream), part, nchunk, (double)total, out, VbFinish{});
         BD_LAUNCH_CHECK("image_loss_fold");
     }
     return BD_OK;
@@ -499,7 +607,70 @@ extern "C" int bd_ssim_images(const bd_image_pair_desc* d, float data_range, flo
         BD_LAUNCH_CHECK("ssim_images_tile");
     }
     const double count = (double)d->C * (d->H - 2 * SS_PAD) * (double)(d->W - 2 * SS_PAD);
-    hipLaunchKernelGGL(image_fold_kernel, dim3((unsigned)d->N), dim3(256), 0, S(stream), part, (int)(d->C * gy * gx), count, out);
+    hipLaunchKernelGGL(image_fold_kernel<false>, dim3((unsigned)d->N), dim3(256), 0, S(stream), part, (int)(d->C * gy * gx), count, out,
+                       VbFinish{});
     BD_LAUNCH_CHECK("ssim_images_fold");
+    return BD_OK;
+}
+
+extern "C" size_t bd_vb_terms_workspace_bytes(int N, int C, int H, int W) {
+    return 2 * bd_image_loss_workspace_bytes(N, C, H, W);                   // the term sums and the squared-difference sums
+}
+
+extern "C" int bd_vb_terms(const bd_vb_terms_desc* d, void* workspace, size_t workspace_bytes, bd_stream_t stream) {
+    BD_CHECK(d, BD_ERR_INVALID, "bd_vb_terms: null descriptor");
+    BD_CHECK(d->x0 && d->t && d->t_host && d->alphas_cumprod && d->term_add && d->term_mul && d->bits, BD_ERR_INVALID,
+             "bd_vb_terms: null pointer");
+    BD_CHECK(d->N > 0 && d->C > 0 && d->H > 0 && d->W > 0, BD_ERR_INVALID, "bd_vb_terms: N=%d C=%d H=%d W=%d must be positive", d->N, d->C,
+             d->H, d->W);
+    BD_CHECK(d->T >= 1, BD_ERR_INVALID, "bd_vb_terms: T=%d must be positive", d->T);
+    BD_CHECK(d->inv_sigma_dec > 0.f && d->inv_sigma_dec <= 3.4e38f, BD_ERR_INVALID, "bd_vb_terms: inv_sigma_dec=%g must be positive and finite",
+             (double)d->inv_sigma_dec);
+    BD_CHECK((long long)d->C * d->H * d->W < (1ll << 31), BD_ERR_UNSUPPORTED, "bd_vb_terms: C*H*W=%lld does not fit 31 bits",
+             (long long)d->C * d->H * d->W);
+    bool reads_chain = false;
+    for (int n = 0; n < d->N; ++n) {
+        const long long t = d->t_host[n];
+        BD_CHECK(t >= 0 && t <= d->T, BD_ERR_INVALID, "bd_vb_terms: t[%d]=%lld outside [0, %d]", n, t, d->T);
+        reads_chain |= t < d->T;
+    }
+    BD_CHECK(!reads_chain || (d->x_t && d->eps), BD_ERR_INVALID, "bd_vb_terms: null x_t or eps with a row at t < T");
+    for (int i = 0; i < 4; ++i)
+        BD_CHECK(d->x0_stride[i] >= 0 && d->xt_stride[i] >= 0 && d->eps_stride[i] >= 0, BD_ERR_INVALID,
+                 "bd_vb_terms: negative stride (x0 %lld, x_t %lld, eps %lld at dim %d)", (long long)d->x0_stride[i], (long long)d->xt_stride[i],
+                 (long long)d->eps_stride[i], i);
+    const size_t need = bd_vb_terms_workspace_bytes(d->N, d->C, d->H, d->W);
+    BD_CHECK(workspace_bytes >= need && (workspace || !need), BD_ERR_WORKSPACE, "bd_vb_terms: workspace %zu < %zu",
+             workspace ? workspace_bytes : (size_t)0, need);
+    const unsigned total = (unsigned)((long long)d->C * d->H * d->W);
+    const int nchunk = (int)cdiv(total, IL_CHUNK);
+    const unsigned dq = 256u / (unsigned)d->W, dw = 256u % (unsigned)d->W, dc = dq / (unsigned)d->H, dh = dq % (unsigned)d->H;
+    VbArgs a;
+    a.C = d->C; a.H = d->H; a.W = d->W; a.clip = d->clip_denoised != 0;
+    a.x0 = d->x0; a.xt = d->x_t; a.ep = d->eps; a.ac = d->alphas_cumprod;
+    for (int i = 0; i < 4; ++i) { a.s0[i] = d->x0_stride[i]; a.st[i] = d->xt_stride[i]; a.se[i] = d->eps_stride[i]; }
+    a.inv_sigma = (double)d->inv_sigma_dec;
+    a.f.t = reinterpret_cast<const long long*>(d->t); a.f.add = d->term_add; a.f.mul = d->term_mul; a.f.T = d->T;
+    double* part = reinterpret_cast<double*>(workspace);
+    for (int n0 = 0; n0 < d->N; n0 += IMG_MAX_GRID) {
+        const int n = d->N - n0 < IMG_MAX_GRID ? d->N - n0 : IMG_MAX_GRID;
+        const dim3 grid((unsigned)nchunk, (unsigned)n);
+        if (d->x0_mse)
+            hipLaunchKernelGGL(vb_terms_kernel<true>, grid, dim3(256), 0, S(stream), a, n0, d->N, total, nchunk, dc, dh, dw, part, d->bits,
+                               d->x0_mse);
+        else
+            hipLaunchKernelGGL(vb_terms_kernel<false>, grid, dim3(256), 0, S(stream), a, n0, d->N, total, nchunk, dc, dh, dw, part, d->bits,
+                               d->x0_mse);
+        BD_LAUNCH_CHECK("vb_terms");
+    }
+    if (nchunk > 1) {
+        hipLaunchKernelGGL(image_fold_kernel<true>, dim3((unsigned)d->N), dim3(256), 0, S(stream), part, nchunk, (double)total, d->bits, a.f);
+        BD_LAUNCH_CHECK("vb_terms_fold");
+        if (d->x0_mse) {
+            hipLaunchKernelGGL(image_fold_kernel<false>, dim3((unsigned)d->N), dim3(256), 0, S(stream), part + (size_t)d->N * nchunk, nchunk,
+                               (double)total, d->x0_mse, VbFinish{});
+            BD_LAUNCH_CHECK("vb_terms_fold_mse");
+        }
+    }
     return BD_OK;
 }

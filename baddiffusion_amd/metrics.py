@@ -15,6 +15,8 @@ Reference call sites: baddiffusion.py:536-547 (`nn.MSELoss`, `StructuralSimilari
 import numpy as np
 import torch
 
+from .likelihood import bits_per_dim  # noqa: F401  -- the variational bound in bits per dimension (likelihood.py, kernel bd_vb_terms)
+
 
 def mse(a, b):
     """nn.MSELoss(reduction='mean') (baddiffusion.py:545) through the fused l2-loss kernel (bd_loss_fwd_bwd): the difference

@@ -987,6 +987,46 @@ def ssim_images(preds, target, data_range=1.0):
     return out
 
 
+def vb_terms(x0, x_t, eps, t, tables, clip_denoised=True, want_x0_mse=False):
+    """Per-row terms of the variational bound in bits per dimension (bd_vb_terms; the formulas are in bd_hip.h and likelihood.py).
+    x0, x_t, eps: float32 [N,C,H,W] GPU tensors of any non-negative strides (x_t and eps may be None when every row is a prior row);
+    t: int64 [N] with values in [0, T], row n's own timestep (T = the prior term) -- a HOST tensor is uploaded, a device tensor is copied
+    back (a synchronisation), because the launcher checks the values on the host; tables: likelihood.vb_tables(...).
+    Returns bits, a float32 [N] device tensor whose entries do not depend on the storage order, the batch around a row or the other
+    rows' t; with want_x0_mse (bits, x0_mse), x0_mse[n] the row's mean (x0 - x0_hat)^2."""
+    lib = L.load(); _need_cuda(x0, x_t, eps)
+    if x0.dim() != 4 or x0.dtype != torch.float32 or x0.numel() == 0:
+        raise TypeError(f"vb_terms: x0 must be a non-empty float32 [N,C,H,W] tensor, got {x0.dtype} {tuple(x0.shape)}")
+    for name, v in (("x_t", x_t), ("eps", eps)):
+        if v is not None and (v.dtype != torch.float32 or v.shape != x0.shape):
+            raise TypeError(f"vb_terms: {name} must be float32 {tuple(x0.shape)}, got {v.dtype} {tuple(v.shape)}")
+    N, Cc, H, W = x0.shape
+    if not torch.is_tensor(t) or t.dtype != torch.int64 or tuple(t.shape) != (N,):
+        raise TypeError(f"vb_terms: t must be an int64 [{N}] tensor")
+    dev = x0.device
+    t_host = t.cpu().contiguous()
+    t_dev = t.to(dev).contiguous()
+    add, mul, ac = tables["add"], tables["mul"], tables["alphas_cumprod"]
+    _need_cuda(add, mul, ac)
+    T = int(tables["T"])
+    if add.numel() != T + 1 or mul.numel() != T + 1 or ac.numel() != T or add.dtype != torch.float32 or mul.dtype != torch.float32 \
+            or ac.dtype != torch.float32:
+        raise ValueError(f"vb_terms: tables must hold float32 add / mul of length T + 1 = {T + 1} and alphas_cumprod of length {T}")
+    bits = torch.empty(N, device=dev)
+    mse = torch.empty(N, device=dev) if want_x0_mse else None
+    d = L.VbTermsDesc(N=N, C=Cc, H=H, W=W, x0=L.ptr(x0), x_t=L.ptr(x_t), eps=L.ptr(eps), t=L.ptr(t_dev), t_host=t_host.data_ptr(),
+                      alphas_cumprod=L.ptr(ac), T=T, term_add=L.ptr(add), term_mul=L.ptr(mul), inv_sigma_dec=float(tables["inv_sigma_dec"]),
+                      clip_denoised=int(bool(clip_denoised)), bits=L.ptr(bits), x0_mse=L.ptr(mse))
+    for i in range(4):
+        d.x0_stride[i] = x0.stride(i)
+        d.xt_stride[i] = 0 if x_t is None else x_t.stride(i)
+        d.eps_stride[i] = 0 if eps is None else eps.stride(i)
+    nbytes = lib.bd_vb_terms_workspace_bytes(N, Cc, H, W)
+    ws = workspace(nbytes, dev, "image_scores") if nbytes else None
+    L.check(lib.bd_vb_terms(C.byref(d), L.ptr(ws), nbytes, L.stream()), "bd_vb_terms")
+    return (bits, mse) if want_x0_mse else bits
+
+
 def pairwise_sqdist(x, out=None):
     """d2[i][j] = sum_k (x[i][k] - x[j][k])^2 of the rows of a float32 [N, D] GPU tensor whose last dim is contiguous (any row
     stride): bd_pairwise_sqdist, difference first, square after.  `out`: a float32 [N, >= N] view to write into (last dim

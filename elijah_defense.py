@@ -6,6 +6,7 @@
                              [--clean_source none|synthetic|dataset] [--clean_n 256] [--clean_batch 64] [--clean_weight 1.0]
                              [--clean_target frozen|noise] [--dataset CIFAR10] [--dataset_path datasets]
                              [--target NAME] [--trigger BOX_14] [--asr_threshold 1e-3] [--dyn_threshold V [--dyn_threshold_ratio 0.995]]
+                             [--bpd_images N [--bpd_t_stride K]]
 
 The sibling of anp_defense.py.  Stages (baddiffusion_amd/inversion.py, baddiffusion_amd/defense.py):
   1. invert_trigger: the shift tau the frozen network follows;
@@ -19,7 +20,11 @@ only for the targets defined relative to the trigger) adds to both score blocks 
 success rate -- the share of generated images whose own MSE to the target is below --asr_threshold -- and the log states "ASR before ->
 after": the direct statement that the repair worked.  The default threshold, 1e-3, is this project's choice of a value of the order the
 papers use, not a finding.
-Outputs in <output_dir>/<name>: config.json, score.json ({"before", "after", "detected", "removal"[, "drift"]}), tau.pt and the repaired model in the
+--bpd_images N adds the utility figure that stands on its own: the variational bound in bits per dimension (likelihood.bits_per_dim) of the
+checkpoint on N clean rows -- the first N of the clean-data term's images, or of the dataset (--dataset, default CIFAR10) without one --
+before and after the removal, on the same noise, printed beside the drift and written as score.json["bpd"].  --bpd_t_stride K evaluates every
+K-th timestep only and reports likelihood.estimate_bpd, marked as an estimate.  Without the flag nothing changes.
+Outputs in <output_dir>/<name>: config.json, score.json ({"before", "after", "detected", "removal"[, "drift"][, "bpd"]}), tau.pt and the repaired model in the
 diffusers layout (unet/, scheduler/), which DiffuserModelSched.get_trained loads.  `--ckpt` must be a local diffusers-layout directory.
 """
 import argparse
@@ -70,6 +75,8 @@ class Config:
     asr_threshold: float = None
     dyn_threshold: float = None
     dyn_threshold_ratio: float = 0.995
+    bpd_images: int = None
+    bpd_t_stride: int = 1
 
 
 DEFAULT_ASR_THRESHOLD = 1e-3    # of the order the papers use; a choice, not a finding
@@ -120,7 +127,13 @@ def get_config(argv=None):
                    help="score passes with dynamic thresholding of the predicted x0 in place of the fixed clamp: the sample_max_value of the "
                         "sampling scheduler (DDIM-SCHED / DDPM-SCHED only)")
     p.add_argument("--dyn_threshold_ratio", type=float, help="the quantile of --dyn_threshold (0.995)")
+    p.add_argument("--bpd_images", type=int, help="bits per dimension (variational bound) of this many clean rows, before -> after the removal")
+    p.add_argument("--bpd_t_stride", type=int, help="with --bpd_images: evaluate every K-th timestep and report the estimate (default 1: the bound)")
     args = p.parse_args(argv)
+    if args.bpd_t_stride is not None and args.bpd_images is None:
+        p.error("--bpd_t_stride needs --bpd_images")
+    if (args.bpd_images is not None and args.bpd_images < 1) or (args.bpd_t_stride is not None and args.bpd_t_stride < 1):
+        p.error("--bpd_images and --bpd_t_stride must be positive")
     if args.dyn_threshold_ratio is not None and args.dyn_threshold is None:
         p.error("--dyn_threshold_ratio needs --dyn_threshold")
     for k, v in vars(args).items():
@@ -136,7 +149,9 @@ def get_config(argv=None):
     config.output_dir = os.path.join(config.output_dir or "", naming_fn(config))
     os.makedirs(config.output_dir, exist_ok=True)
     with open(os.path.join(config.output_dir, "config.json"), "w") as f:
-        json.dump({k: v for k, v in config.__dict__.items()}, f, indent=2, default=str)
+        # (the bpd fields appear only with --bpd_images: without the flag the file is what it was before the flag existed)
+        json.dump({k: v for k, v in config.__dict__.items() if config.bpd_images is not None or not k.startswith("bpd_")}, f, indent=2,
+                  default=str)
     return config
 
 
@@ -222,6 +237,30 @@ def drift(config, model, frozen, clean, noise_sched, log=print):
     return d
 
 
+def bpd_rows(config, model, clean, log=print):
+    """the uint8 [N, H, W, C] device rows --bpd_images scores: the first N of the clean-data term's images, else of the dataset"""
+    n = config.bpd_images
+    if clean is None:
+        from baddiffusion_amd.dataset import DatasetLoader
+        root = config.dataset_path if config.dataset_path and os.path.isdir(str(config.dataset_path)) else None
+        dsl = DatasetLoader(root=root, name=config.dataset or "CIFAR10", channel=model.in_channels, image_size=model.sample_size,
+                            seed=config.seed, device=model.device, num_images=n)
+        log(f"bits/dim data: {dsl.source}")
+        clean = dsl.device_images
+    if clean.shape[0] < n:
+        raise ValueError(f"--bpd_images {n}: only {clean.shape[0]} clean images are at hand")
+    return clean[:n]
+
+
+def bpd(config, model, noise_sched, rows):
+    """mean bits per dimension of `rows` (the estimate of likelihood.estimate_bpd with --bpd_t_stride > 1), always on the same noise"""
+    from baddiffusion_amd import likelihood
+    g = torch.Generator(device=model.device); g.manual_seed(config.seed + 4)
+    res = likelihood.bits_per_dim(model, noise_sched, rows, generator=g, max_batch_n=config.eval_max_batch,
+                                  timesteps=likelihood.strided_timesteps(noise_sched.config.num_train_timesteps, config.bpd_t_stride))
+    return float(likelihood.estimate_bpd(res["terms"], config.bpd_t_stride).mean()), bool(res["complete"])
+
+
 def save_model(config, model, noise_sched):
     save_unet(model, os.path.join(config.output_dir, "unet"))
     save_scheduler(noise_sched, os.path.join(config.output_dir, "scheduler"))
@@ -239,15 +278,24 @@ def main(argv=None):
     if config.max_ratio is not None:
         result["detected"] = bool(defense.detect_backdoor(result["before"], max_ratio=config.max_ratio))
         print(f"backdoor detected: {result['detected']} (uniformity_ratio {result['before']['uniformity_ratio']:.6g} vs {config.max_ratio})")
+    clean = clean_images(config, model, noise_sched) if config.clean_source != "none" else None
+    if config.bpd_images is not None:
+        rows = bpd_rows(config, model, clean)
+        result["bpd"] = {"n": config.bpd_images, "t_stride": config.bpd_t_stride}
+        result["bpd"]["before"], result["bpd"]["complete"] = bpd(config, model, noise_sched, rows)
     if config.clean_source != "none":
         # one frozen copy serves the removal (its targets) and the drift (the predictions before the repair)
-        clean, frozen = clean_images(config, model, noise_sched), defense.frozen_copy(model)
+        frozen = defense.frozen_copy(model)
         if config.remove_steps > 0:
             result["removal"] = remove(config, model, noise_sched, tau, clean=clean, frozen=frozen)
         result["drift"] = drift(config, model, frozen, clean, noise_sched)
         del frozen
     elif config.remove_steps > 0:
         result["removal"] = remove(config, model, noise_sched, tau)
+    if config.bpd_images is not None:
+        result["bpd"]["after"] = bpd(config, model, noise_sched, rows)[0]
+        print(f"bits/dim of {config.bpd_images} clean rows before -> after: {result['bpd']['before']:.6g} -> {result['bpd']['after']:.6g}"
+              + ("" if result["bpd"]["complete"] else f" (ESTIMATE from every {config.bpd_t_stride}-th timestep)"))
     result["after"] = score(config, model, noise_sched, tau, noise, tag="after", target=target)
     if target is not None:
         print(f"ASR (MSE to {config.target} < {config.asr_threshold:g}) before -> after: {result['before']['asr_trigger']:.4f} -> "

@@ -836,6 +836,51 @@ size_t bd_ssim_images_workspace_bytes(int N, int C, int H, int W);
 int bd_ssim_images(const bd_image_pair_desc* d, float data_range, float* out, void* workspace, size_t workspace_bytes,
                    bd_stream_t stream);
 
+/* Terms of the variational bound of a DDPM in bits per dimension (likelihood.bits_per_dim; DESIGN.md section 3, "Bits per
+ * dimension"): epsilon prediction, fixed variances.  Row n of the batch carries its own t[n] in [0, T], T = the number of training
+ * timesteps; x0, x_t and eps are fp32 [N,C,H,W] by element strides (all >= 0), as in bd_image_pair_desc.  With
+ *     x0_hat = (x_t - sqrt(1 - ac[t]) eps) / sqrt(ac[t])   in fp32, the expression of bd_ddpm_step,
+ *              clamped to [-1, 1] when clip_denoised (by comparison: a NaN stays a NaN),
+ *     m      = the mean over (c, h, w) of the row's element term e_i,
+ *     bits[n] = (float)((term_add[t] + term_mul[t] * m) / ln 2)     in fp64,
+ * the element term is
+ *     1 <= t < T   e_i = (x0_i - x0_hat_i)^2 in fp32 (the KL of two Gaussians whose means differ by c0_t (x0 - x0_hat)):
+ *                  term_add[t] = (-1 + D_t + exp(-D_t)) / 2, D_t = log(model variance / posterior variance); term_mul[t] = c0_t^2 /
+ *                  (2 model variance);
+ *     t = 0        e_i = -log max(P_i, 1e-12) in fp64, P_i the mass the Gaussian N(x0_hat_i, sigma_dec^2) puts on the bin of x0_i
+ *                  (half width 1/255; open to -inf for x0_i < -0.999 and to +inf for x0_i > 0.999), with z+- = (x0_i - x0_hat_i +-
+ *                  1/255) * inv_sigma_dec taken on the tail side: P_i = (erfc(z- / sqrt 2) - erfc(z+ / sqrt 2)) / 2 for z- > 0, else
+ *                  (erfc(-z+ / sqrt 2) - erfc(-z- / sqrt 2)) / 2; erfc(-z+ / sqrt 2) / 2 and erfc(z- / sqrt 2) / 2 in the two edge
+ *                  bins.  The exact normal CDF, not the tanh approximation of improved-DDPM.  term_add[0] = 0, term_mul[0] = 1;
+ *     t = T        e_i = x0_i^2 in fp32 (the prior term KL(q(x_T | x0) || N(0, I))); x_t and eps are not read and may be NULL when
+ *                  every row is a prior row.  term_add[T] = (-1 - log(1 - ac[T-1]) + (1 - ac[T-1])) / 2, term_mul[T] = ac[T-1] / 2.
+ * The tables term_add, term_mul (fp32 [T + 1], device) and inv_sigma_dec are the caller's (likelihood.vb_tables computes them in fp64 on
+ * the host); the kernel does no schedule arithmetic beyond x0_hat.  alphas_cumprod: fp32 [T], device.
+ * t: int64 [N] on the device; t_host: the same values on the host, which the launcher checks before anything is launched.
+ * x0_mse: optional fp32 [N], the row's mean of (x0 - x0_hat)^2 (of x0^2 in a prior row).
+ *
+ * Summation order: that of bd_image_loss (chunks of 8192 logical elements, thread-strided fp64 sums, the fixed tree, the chunk sums
+ * folded by one workgroup per image of a second launch), so bits[n] and x0_mse[n] do not depend on N, on the row's place in the batch,
+ * on the strides or on the other rows' t.  A workgroup belongs to one row, so only t = 0 rows evaluate erfc.  A NaN in a row's inputs
+ * makes that row's outputs NaN and no other's.
+ * workspace >= bd_vb_terms_workspace_bytes(N, C, H, W) (0 for C*H*W <= 8192; workspace may then be NULL).  Status: BD_ERR_INVALID for
+ * a null d / x0 / t / t_host / alphas_cumprod / table / bits, x_t or eps NULL with a row at t < T, N, C, H, W, T <= 0, t outside
+ * [0, T], a negative stride, inv_sigma_dec not positive and finite; BD_ERR_UNSUPPORTED for C*H*W >= 2^31; BD_ERR_WORKSPACE. */
+typedef struct {
+    int N, C, H, W;
+    const float* x0;  int64_t x0_stride[4];    /* element strides n, c, h, w */
+    const float* x_t; int64_t xt_stride[4];
+    const float* eps; int64_t eps_stride[4];
+    const int64_t* t;                          /* device [N] */
+    const int64_t* t_host;                     /* host   [N], the same values */
+    const float* alphas_cumprod; int T;
+    const float* term_add; const float* term_mul; float inv_sigma_dec;
+    int clip_denoised;
+    float* bits; float* x0_mse;
+} bd_vb_terms_desc;
+size_t bd_vb_terms_workspace_bytes(int N, int C, int H, int W);
+int bd_vb_terms(const bd_vb_terms_desc* d, void* workspace, size_t workspace_bytes, bd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * FID feature extractor (measure path, SURVEY f-3): the layer kernels of pytorch_fid's InceptionV3 up to pool3
  * (/root/reference/fid_score.py:53 `from pytorch_fid.inception import InceptionV3`, :91-148 get_activations, :255
