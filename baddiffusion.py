@@ -38,8 +38,9 @@ NOT_MODE_TRAIN_MEASURE_OPTS = ["sample_ep"]
 MODE_RESUME_OPTS = ["project", "mode", "gpu", "ckpt"]
 MODE_SAMPLING_OPTS = ["project", "mode", "eval_max_batch", "gpu", "fclip", "ckpt", "sample_ep", "sched", "use_ema", "native_sched", "infer_steps", "dyn_threshold",
                       "dyn_threshold_ratio"]
+QUALITY_OPTS = ["measure_prdc_k", "measure_kid", "kid_subsets", "kid_subset_size"]     # measure / train+measure only; absent from every file unless given
 MODE_MEASURE_OPTS = ["project", "mode", "eval_max_batch", "gpu", "fclip", "ckpt", "sample_ep", "sched", "use_ema", "native_sched", "infer_steps", "asr_threshold",
-                     "dyn_threshold", "dyn_threshold_ratio"]
+                     "dyn_threshold", "dyn_threshold_ratio"] + QUALITY_OPTS
 EMA_DIR, EMA_STATE = "unet_ema", "ema.bin"     # averaged weights in diffusers layout under output_dir; EMA scalars + shadow under ckpt/
 IGNORE_ARGS = ["overwrite", "is_save_all_model_epochs"]
 
@@ -96,6 +97,14 @@ def parse_args(argv=None):
                    help="measure: also score every backdoor image on its own and report ASR, the share whose MSE to the target is below this "
                         "(no default: values of the order of 1e-3 are what the papers use)")
     p.add_argument("--log_loss_split", action="store_true", help="train: log the loss of the clean and of the poisoned rows separately")
+    p.add_argument("--measure_prdc_k", type=int,
+                   help="measure: also report improved precision / recall and density / coverage of the clean samples against the FID real "
+                        "set, on the same Inception features, with k-NN radii at this k (1 ... 16; the papers use 3 and 5)")
+    p.add_argument("--measure_kid", action="store_true",
+                   help="measure: also report KID (unbiased MMD^2, cubic polynomial kernel) on the same features: mean and standard deviation "
+                        "over --kid_subsets (100) subsets of --kid_subset_size (1000) rows, capped at measure_sample_n")
+    p.add_argument("--kid_subsets", type=int, help="number of KID subsets (100); needs --measure_kid")
+    p.add_argument("--kid_subset_size", type=int, help="rows per KID subset (1000); needs --measure_kid")
     return p.parse_args(argv)
 
 
@@ -191,6 +200,14 @@ def setup(argv=None, write=True):
     config.mode = args.mode
     if args.dyn_threshold_ratio is not None and args.dyn_threshold is None:
         raise ValueError("--dyn_threshold_ratio needs --dyn_threshold")
+    if args.mode == MODE_TRAIN and any(getattr(args, k) for k in QUALITY_OPTS):
+        raise ValueError("--measure_prdc_k / --measure_kid / --kid_subsets / --kid_subset_size score samples: modes measure and train+measure only")
+    if (args.kid_subsets is not None or args.kid_subset_size is not None) and not args.measure_kid:
+        raise ValueError("--kid_subsets / --kid_subset_size need --measure_kid")
+    if args.measure_prdc_k is not None and not 1 <= args.measure_prdc_k <= 16:
+        raise ValueError(f"--measure_prdc_k {args.measure_prdc_k} must be in [1, 16]")
+    if (args.kid_subsets is not None and args.kid_subsets < 1) or (args.kid_subset_size is not None and args.kid_subset_size < 2):
+        raise ValueError("--kid_subsets must be at least 1 and --kid_subset_size at least 2")
     if not hasattr(config, "dataset"):
         raise ValueError("--dataset is required")
     if not hasattr(config, "sched"):
@@ -222,7 +239,8 @@ def setup(argv=None, write=True):
             if not config.overwrite and os.path.isdir(config.output_dir):
                 raise ValueError(f"Output directory: {config.output_dir} has already been created, please set overwrite flag --overwrite or -o")
             os.makedirs(config.output_dir, exist_ok=True)
-            _write_json(vars(args), config, "args.json")
+            # the quality flags appear only when given: without them args.json is what it was before they existed
+            _write_json({k: v for k, v in vars(args).items() if k not in QUALITY_OPTS or v not in (None, False)}, config, "args.json")
             _write_json(config.__dict__, config, "config.json")
         elif args.mode == MODE_SAMPLING:
             _write_json(config.__dict__, config, "sampling.json")
@@ -349,15 +367,46 @@ def _png_dir_u8(path, channel):
     return np.stack([np.asarray(Image.open(os.path.join(path, f)).convert("RGB"), dtype=np.uint8) for f in files])
 
 
-def fid_of_dirs(net, real_u8, gen_u8, batch=500):
+def fid_of_dirs(net, real_u8, gen_u8, batch=500, stores=None):
     """fid_score.py:233-259 on device-resident uint8 image sets: pool3 features batch by batch -> fp64 statistics on the device
-    -> Frechet distance."""
+    -> Frechet distance.  stores: a pair of metrics.FeatureStore that keep the (real, generated) features for prdc / kid."""
     from baddiffusion_amd import metrics
 
     def feats(arr):
         for s in range(0, arr.shape[0], batch):
             yield net(arr[s:s + batch])
-    return metrics.fid_from_features(feats(real_u8), feats(gen_u8))
+    return metrics.fid_from_features(feats(real_u8), feats(gen_u8), stores=stores)
+
+
+QUALITY_UNAVAILABLE = ("precision / recall / density / coverage and KID are computed on the same Inception pool3 features as FID, and the "
+                       "weights are absent (see FID_reason); quality_eval.py --features pixels scores two image folders without them")
+
+
+def quality_request(config):
+    """(prdc_k or None, kid options or None) of --measure_prdc_k / --measure_kid"""
+    prdc_k = getattr(config, "measure_prdc_k", None)
+    kid = None
+    if getattr(config, "measure_kid", False):
+        kid = {"subsets": getattr(config, "kid_subsets", None) or 100, "subset_size": getattr(config, "kid_subset_size", None) or 1000}
+    return prdc_k, kid
+
+
+def quality_extra(config, stores):
+    """score.json keys of the quality metrics that were asked for: values from the stored (real, clean-sample) features, or nulls and a
+    quality_reason when there are none (stores is None: no Inception weights).  Nothing asked for: no key."""
+    from baddiffusion_amd import metrics
+    prdc_k, kid = quality_request(config)
+    if prdc_k is None and kid is None:
+        return {}
+    if stores is None:
+        out = {k: None for k in (metrics.QUALITY_PRDC_KEYS if prdc_k is not None else ()) + (metrics.QUALITY_KID_KEYS if kid else ())}
+        if prdc_k is not None:
+            out["PRDC_k"] = int(prdc_k)
+        if kid:
+            out.update(KID_subsets=kid["subsets"], KID_subset_size=kid["subset_size"])
+        out["quality_reason"] = QUALITY_UNAVAILABLE          # a null value is never silent
+        return out
+    return metrics.quality_scores(stores[0].features(), stores[1].features(), prdc_k, kid, generator=torch.Generator().manual_seed(config.seed))
 
 
 def update_score_file(config, score_file, fid_sc, mse_sc, ssim_sc, fid_reason=None, extra=None):
@@ -444,7 +493,7 @@ def measure(config, dsl, folder_name, pipeline, rank=0, world=1):
     # measure_sample_n images of the seed-shuffled dataset and for the clean samples, on the device (baddiffusion_amd/inception.py),
     # then fp64 statistics + the Frechet distance (pinned by G8).  The weights file is a third-party asset: without it FID is null
     # and score.json says why.
-    fid_sc, fid_reason = None, FID_UNAVAILABLE
+    fid_sc, fid_reason, stores = None, FID_UNAVAILABLE, None
     from baddiffusion_amd.inception import load_fid_weights
     net = load_fid_weights(device=dev) if str(dev) != "cpu" else None
     if net is not None:
@@ -459,8 +508,11 @@ def measure(config, dsl, folder_name, pipeline, rank=0, world=1):
         if real.shape[-1] == 1:
             real = real.expand(-1, -1, -1, 3).contiguous()
         clean = torch.from_numpy(_png_dir_u8(clean_path, dsl.channel)).to(dev)
-        fid_sc = float(fid_of_dirs(net, real.to(dev), clean))
+        if any(v is not None for v in quality_request(config)):
+            stores = (metrics.FeatureStore(n_real), metrics.FeatureStore(clean.shape[0]))
+        fid_sc = float(fid_of_dirs(net, real.to(dev), clean, stores=stores))
         fid_reason = None
+    extra.update(quality_extra(config, stores))
     print(f"[{config.sample_ep}] FID: {fid_sc if fid_sc is not None else 'None (BD_FID_WEIGHTS not set: pytorch_fid Inception weights unavailable)'}, "
           f"MSE: {mse_sc}, SSIM: {ssim_sc}")
     # the inference batch decides which kernels the plan picks (fp32 summation order): EVERY batch size a forward of this measure() ran with is

@@ -233,6 +233,10 @@ class ImagePairDesc(C.Structure):
     _fields_ = [("N", i32), ("C", i32), ("H", i32), ("W", i32), ("preds", vp), ("p_stride", i64 * 4), ("target", vp), ("t_stride", i64 * 4)]
 
 
+class CrossPlanInfo(C.Structure):
+    _fields_ = [("strips", i32), ("col_tiles", i32), ("csplit", i32), ("tiles_per_split", i32), ("csplit_cap", i32)]
+
+
 class VbTermsDesc(C.Structure):
     _fields_ = [("N", i32), ("C", i32), ("H", i32), ("W", i32), ("x0", vp), ("x0_stride", i64 * 4), ("x_t", vp), ("xt_stride", i64 * 4),
                 ("eps", vp), ("eps_stride", i64 * 4), ("t", vp), ("t_host", vp), ("alphas_cumprod", vp), ("T", i32),
@@ -285,6 +289,15 @@ SIGNATURES = {
     "bd_pairwise_sqdist_workspace_bytes": (sz, [i32, i32]),
     "bd_pairwise_sqdist": (i32, [vp, i64, i32, i32, vp, i64, vp, sz, vp]),
     "bd_total_variation": (i32, [vp, i32, i32, i32, i32, i64, i64, i64, i64, vp, vp]),
+    "bd_cross_plan": (i32, [i32, i32, i32, C.POINTER(CrossPlanInfo)]),
+    "bd_knn_sqradius_workspace_bytes": (sz, [i32, i32, i32]),
+    "bd_knn_sqradius": (i32, [vp, i64, i32, i32, i32, vp, vp, sz, vp]),
+    "bd_cross_ksmallest_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "bd_cross_ksmallest": (i32, [vp, i64, i32, vp, i64, i32, i32, i32, i64, vp, vp, sz, vp]),
+    "bd_cross_count_min_workspace_bytes": (sz, [i32, i32, i32]),
+    "bd_cross_count_min": (i32, [vp, i64, i32, vp, i64, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "bd_poly3_rowsum_workspace_bytes": (sz, [i32, i32, i32]),
+    "bd_poly3_rowsum": (i32, [vp, i64, i32, vp, i64, i32, i32, i32, vp, vp, sz, vp]),
     "bd_image_loss_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "bd_image_loss": (i32, [C.POINTER(ImagePairDesc), i32, vp, vp, sz, vp]),
     "bd_ssim_images_workspace_bytes": (sz, [i32, i32, i32, i32]),

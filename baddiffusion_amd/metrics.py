@@ -166,13 +166,170 @@ def frechet_distance(mu1, sigma1, mu2, sigma2, eps=1e-6):
     return float(gap @ gap + np.trace(S[0]) + np.trace(S[1]) - 2.0 * np.trace(root))
 
 
-def fid_from_features(features_a, features_b):
-    """Frechet distance between two iterables of feature batches ([n, d] tensors)."""
+def fid_from_features(features_a, features_b, stores=None):
+    """Frechet distance between two iterables of feature batches ([n, d] tensors).  stores: a pair of FeatureStore that keep the
+    batches of the two sets for the metrics that need the rows themselves (prdc, kid)."""
     stats = []
-    for feats in (features_a, features_b):
+    for which, feats in enumerate((features_a, features_b)):
         acc = None
         for f in feats:
             acc = acc or ActivationStats(f.reshape(f.shape[0], -1).shape[1], f.device)
             acc.update(f)
+            if stores is not None:
+                stores[which].update(f)
         stats.append(acc.finalize())
     return frechet_distance(stats[0][0], stats[0][1], stats[1][0], stats[1][1])
+
+
+# ---------------------------------------------------------------------------------------------------- quality metrics on features
+# Improved precision / recall (Kynkaanniemi et al. 2019), density / coverage (Naeem et al. 2020) and KID (Binkowski et al. 2018) on
+# [N, d] feature rows (pool3 features, or anything else a caller extracts).  The pairwise work runs in the strip kernels of
+# csrc/quality.hip (direct differences, no N x M matrix); what is left here is O(N) per set.  DESIGN.md section 3.
+def _features(who, *sets):
+    out = []
+    for f in sets:
+        if not torch.is_tensor(f) or not f.is_cuda:
+            raise RuntimeError(f"metrics.{who}: device tensors required (the pairwise kernels are HIP kernels; no CPU fallback)")
+        if f.dim() < 2 or f.shape[0] < 1 or f.numel() == 0:
+            raise ValueError(f"{who}: expected non-empty [N, d] features, got {tuple(f.shape)}")
+        out.append(f.float().reshape(f.shape[0], -1).contiguous())
+    if len({f.shape[1] for f in out}) != 1:
+        raise ValueError(f"{who}: the feature dimensions differ: {[tuple(f.shape) for f in out]}")
+    return out
+
+
+def knn_sqradius(features, k):
+    """float32 [N] device tensor: the squared distance from every row of `features` ([N, d], device) to its k-th nearest OTHER row
+    (HIP kernel bd_knn_sqradius: self is left out by index, so a duplicate row has radius 0; 1 <= k <= min(16, N - 1))."""
+    (f,) = _features("knn_sqradius", features)
+    k = int(k)
+    if not 1 <= k <= min(16, f.shape[0] - 1):
+        raise ValueError(f"knn_sqradius: k={k} must be in [1, min(16, N - 1 = {f.shape[0] - 1})]")
+    from . import ops
+    return ops.knn_sqradius(f, k)
+
+
+def _prdc_counts(real, fake, k):
+    from . import ops
+    r_real, r_fake = knn_sqradius(real, k), knn_sqradius(fake, k)       # once per set
+    in_real, _ = ops.cross_count_min(fake, real, r_real)                 # per fake sample: the real balls it lies in
+    in_fake, nearest_fake = ops.cross_count_min(real, fake, r_fake)      # per real sample: the fake balls it lies in; its nearest fake
+    return r_real, in_real, in_fake, nearest_fake
+
+
+def prdc(real, fake, k=5):
+    """{"precision", "recall", "density", "coverage", "k"} of two feature sets ([N_real, d] and [N_fake, d] device tensors), Naeem et
+    al. 2020 with the manifolds of Kynkaanniemi et al. 2019.  r_X(j) is the distance from x_j to its k-th nearest other member of X:
+      precision = mean_i [ fake_i lies in some ball B(real_j, r_real(j)) ]       recall = the same with the roles exchanged
+      density   = sum_i #{ j : fake_i in B(real_j, r_real(j)) } / (k N_fake)     coverage = mean_j [ min_i d(real_j, fake_i) <= r_real(j) ]
+    Every comparison is on SQUARED distances and is `<=`.  The `prdc` package compares with strict `<`; the two differ only where a
+    distance equals a radius exactly (duplicates, integer-valued features), where `<=` counts the k-th neighbour itself as inside its
+    ball, which is what "within the k-NN radius" says.  Squared distances are bd_pairwise_sqdist's arithmetic (difference first), so
+    near-duplicate samples -- a collapsed model -- do not cancel."""
+    real, fake = _features("prdc", real, fake)
+    k = int(k)
+    r_real, in_real, in_fake, nearest_fake = _prdc_counts(real, fake, k)
+    n_real, n_fake = real.shape[0], fake.shape[0]          # integer counts from the device, one correctly rounded division each on the host
+    return {"precision": int((in_real > 0).sum()) / n_fake, "recall": int((in_fake > 0).sum()) / n_real,
+            "density": int(in_real.sum(dtype=torch.int64)) / (k * n_fake), "coverage": int((nearest_fake <= r_real).sum()) / n_real, "k": k}
+
+
+def precision_recall(real, fake, k=3):
+    """{"precision", "recall", "k"}: improved precision and recall (Kynkaanniemi et al. 2019; k = 3 is that paper's default), the
+    first two scores of `prdc` at that k."""
+    res = prdc(real, fake, k)
+    return {"precision": res["precision"], "recall": res["recall"], "k": res["k"]}
+
+
+class KidResult(tuple):
+    """(mean, std) of the per-subset MMD^2 estimates; also .mean, .std, .values (one per subset), .subsets, .subset_size and
+    .warning (None, or why subset_size is not what was asked for)"""
+
+    def __new__(cls, values, subset_size, warning):
+        self = super().__new__(cls, (float(np.mean(values)), float(np.std(values))))
+        self.values, self.subsets, self.subset_size, self.warning = list(values), len(values), int(subset_size), warning
+        return self
+
+    mean = property(lambda self: self[0])
+    std = property(lambda self: self[1])
+
+
+def kid_subset_indices(n_real, n_fake, subsets, subset_size, generator=None):
+    """the rows of every KID subset: a list of (real rows, fake rows) int64 CPU tensors, each subset_size rows drawn without
+    replacement as torch.randperm(n, generator=generator)[:subset_size], real first, subset after subset"""
+    return [(torch.randperm(n_real, generator=generator)[:subset_size], torch.randperm(n_fake, generator=generator)[:subset_size])
+            for _ in range(subsets)]
+
+
+def kid(real, fake, subsets=100, subset_size=1000, generator=None):
+    """Kernel Inception Distance (Binkowski et al. 2018): KidResult, which unpacks as (mean, std), over `subsets` draws of the
+    unbiased MMD^2 with the kernel k(x, y) = (x.y / d + 1)^3 between subset_size rows of each set (kid_subset_indices; `generator`
+    is a CPU torch.Generator):  S_xx / (m (m - 1)) + S_yy / (m (m - 1)) - 2 S_xy / m^2, the diagonal left out of S_xx and S_yy.
+    The dot products are fp32 FMA chains, the kernel values and all sums fp64 (HIP kernel bd_poly3_rowsum).  subset_size is capped at
+    the smaller set; the result's .warning says so.  std is the population standard deviation of the subset values."""
+    real, fake = _features("kid", real, fake)
+    subsets, subset_size = int(subsets), int(subset_size)
+    if subsets < 1 or subset_size < 2:
+        raise ValueError(f"kid: subsets={subsets} must be >= 1 and subset_size={subset_size} >= 2")
+    warning = None
+    smaller = min(real.shape[0], fake.shape[0])
+    if subset_size > smaller:
+        warning = f"subset_size {subset_size} capped at the smaller set's {smaller} rows"
+        subset_size = smaller
+        if subset_size < 2:
+            raise ValueError("kid: both sets need at least two rows")
+    from . import ops
+    m = subset_size
+    values = []
+    for ri, fi in kid_subset_indices(real.shape[0], fake.shape[0], subsets, m, generator):
+        x, y = real[ri.to(real.device)], fake[fi.to(fake.device)]
+        s_xx, s_yy, s_xy = (ops.poly3_rowsum(x, x, True).sum(), ops.poly3_rowsum(y, y, True).sum(), ops.poly3_rowsum(x, y, False).sum())
+        values.append(float(s_xx / (m * (m - 1)) + s_yy / (m * (m - 1)) - 2.0 * s_xy / (m * m)))
+    return KidResult(values, m, warning)
+
+
+class FeatureStore:
+    """Feature batches ([n, d] device tensors) gathered into ONE float32 device tensor, so that the k-NN and KID kernels can read what
+    ActivationStats only sums (80 MB at 10 000 x 2048).  update() appends (the buffer doubles when it is full); features() is the
+    [N, d] view of what has arrived."""
+
+    def __init__(self, capacity=0):
+        self.n, self.buf, self.capacity = 0, None, int(capacity)
+
+    def update(self, act):
+        a = act.reshape(act.shape[0], -1).float()
+        if self.buf is None:
+            self.buf = torch.empty(max(self.capacity, a.shape[0]), a.shape[1], device=a.device)
+        if a.shape[1] != self.buf.shape[1]:
+            raise ValueError(f"FeatureStore: batch of width {a.shape[1]} after width {self.buf.shape[1]}")
+        if self.n + a.shape[0] > self.buf.shape[0]:
+            grown = torch.empty(max(2 * self.buf.shape[0], self.n + a.shape[0]), self.buf.shape[1], device=self.buf.device)
+            grown[: self.n] = self.buf[: self.n]
+            self.buf = grown
+        self.buf[self.n: self.n + a.shape[0]] = a
+        self.n += a.shape[0]
+        return self
+
+    def features(self):
+        if self.buf is None:
+            raise ValueError("FeatureStore: no features yet")
+        return self.buf[: self.n]
+
+
+def quality_scores(real, fake, prdc_k=None, kid_opts=None, generator=None):
+    """the score.json / quality.json keys of the quality metrics asked for: precision / recall / density / coverage / PRDC_k with
+    prdc_k, KID_mean / KID_std / KID_subsets / KID_subset_size (/ KID_warning) with kid_opts = {"subsets", "subset_size"}"""
+    out = {}
+    if prdc_k is not None:
+        res = prdc(real, fake, prdc_k)
+        out.update({n: res[n] for n in QUALITY_PRDC_KEYS[:4]}, PRDC_k=res["k"])
+    if kid_opts is not None:
+        res = kid(real, fake, generator=generator, **kid_opts)
+        out.update(KID_mean=res.mean, KID_std=res.std, KID_subsets=res.subsets, KID_subset_size=res.subset_size)
+        if res.warning:
+            out["KID_warning"] = res.warning
+    return out
+
+
+QUALITY_PRDC_KEYS = ("precision", "recall", "density", "coverage", "PRDC_k")
+QUALITY_KID_KEYS = ("KID_mean", "KID_std", "KID_subsets", "KID_subset_size")

@@ -1045,6 +1045,80 @@ def pairwise_sqdist(x, out=None):
     return out[:, :N]
 
 
+def _rows2(who, *ts):
+    """the checks the bd_cross_* wrappers share: float32 [N, D] GPU tensors with a contiguous last dim and one D"""
+    _need_cuda(*ts)
+    for t in ts:
+        if t.dim() != 2 or t.dtype != torch.float32 or t.shape[0] < 1 or t.shape[1] < 1 or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise TypeError(f"{who}: float32 [N, D] tensors with a contiguous last dim are required, got {t.dtype} {tuple(t.shape)}")
+    if len({t.shape[1] for t in ts}) != 1:
+        raise ValueError(f"{who}: the feature dimensions differ: {[tuple(t.shape) for t in ts]}")
+
+
+def cross_plan(Na, Nb, D):
+    """bd_cross_plan: how the strip kernels cut an (Na, Nb, D) problem, as a dict (strips, col_tiles, csplit, tiles_per_split, csplit_cap)"""
+    info = L.CrossPlanInfo()
+    L.check(L.load().bd_cross_plan(int(Na), int(Nb), int(D), C.byref(info)), "bd_cross_plan")
+    return {f: getattr(info, f) for f, _ in L.CrossPlanInfo._fields_}
+
+
+def knn_sqradius(x, k):
+    """out[i] = the k-th smallest squared distance from row i of a float32 [N, D] GPU tensor to the OTHER rows (self left out by index,
+    a duplicate gives 0): bd_knn_sqradius, 1 <= k <= min(16, N - 1).  Returns a float32 [N] tensor."""
+    lib = L.load(); _rows2("knn_sqradius", x)
+    N, D = x.shape
+    out = torch.empty(N, device=x.device)
+    nbytes = lib.bd_knn_sqradius_workspace_bytes(N, D, int(k))
+    ws = workspace(nbytes, x.device, "cross") if nbytes else None
+    L.check(lib.bd_knn_sqradius(L.ptr(x), _ld(x), N, D, int(k), L.ptr(out), L.ptr(ws), nbytes, L.stream()), "bd_knn_sqradius")
+    return out
+
+
+def cross_ksmallest(a, b, k, self_col0=None):
+    """out[i] = the k smallest squared distances, ascending, from row i of a to the rows of b (float32 [Na, D] / [Nb, D] GPU tensors),
+    column i + self_col0 left out (None: no column is; 0 with a is b: the neighbour lists behind knn_sqradius); +inf where b has
+    fewer than k eligible rows: bd_cross_ksmallest, 1 <= k <= 16.  Returns float32 [Na, k]."""
+    lib = L.load(); _rows2("cross_ksmallest", a, b)
+    (Na, D), Nb = a.shape, b.shape[0]
+    out = torch.empty(Na, int(k), device=a.device)
+    nbytes = lib.bd_cross_ksmallest_workspace_bytes(Na, Nb, D, int(k))
+    ws = workspace(nbytes, a.device, "cross") if nbytes else None
+    L.check(lib.bd_cross_ksmallest(L.ptr(a), _ld(a), Na, L.ptr(b), _ld(b), Nb, D, int(k), -Na if self_col0 is None else int(self_col0),
+                                   L.ptr(out), L.ptr(ws), nbytes, L.stream()), "bd_cross_ksmallest")
+    return out
+
+
+def cross_count_min(a, b, radius2=None):
+    """(count, min_d2) per row of a: count[i] = #{j : d2(a_i, b_j) <= radius2[j]} (int32 [Na]; None without radius2, a float32 [Nb] GPU
+    tensor) and min_d2[i] = min_j d2(a_i, b_j) (float32 [Na]): bd_cross_count_min.  No pair is left out."""
+    lib = L.load(); _rows2("cross_count_min", a, b); _need_cuda(radius2)
+    (Na, D), Nb = a.shape, b.shape[0]
+    if radius2 is not None:
+        if radius2.dtype != torch.float32 or tuple(radius2.shape) != (Nb,):
+            raise TypeError(f"cross_count_min: radius2 must be float32 [{Nb}], got {radius2.dtype} {tuple(radius2.shape)}")
+        radius2 = radius2.contiguous()
+    count = torch.empty(Na, dtype=torch.int32, device=a.device) if radius2 is not None else None
+    min_d2 = torch.empty(Na, device=a.device)
+    nbytes = lib.bd_cross_count_min_workspace_bytes(Na, Nb, D)
+    ws = workspace(nbytes, a.device, "cross") if nbytes else None
+    L.check(lib.bd_cross_count_min(L.ptr(a), _ld(a), Na, L.ptr(b), _ld(b), Nb, D, L.ptr(radius2), L.ptr(count), L.ptr(min_d2), L.ptr(ws),
+                                   nbytes, L.stream()), "bd_cross_count_min")
+    return count, min_d2
+
+
+def poly3_rowsum(a, b, exclude_diag=False):
+    """rowsum[i] = sum_j (dot(a_i, b_j) / D + 1)^3, the dot product in fp32, the kernel value and the sum in fp64; exclude_diag drops
+    j == i (a and b the same set): bd_poly3_rowsum.  Returns a float64 [Na] tensor."""
+    lib = L.load(); _rows2("poly3_rowsum", a, b)
+    (Na, D), Nb = a.shape, b.shape[0]
+    out = torch.empty(Na, dtype=torch.float64, device=a.device)
+    nbytes = lib.bd_poly3_rowsum_workspace_bytes(Na, Nb, D)
+    ws = workspace(nbytes, a.device, "cross") if nbytes else None
+    L.check(lib.bd_poly3_rowsum(L.ptr(a), _ld(a), Na, L.ptr(b), _ld(b), Nb, D, int(bool(exclude_diag)), L.ptr(out), L.ptr(ws), nbytes,
+                                L.stream()), "bd_poly3_rowsum")
+    return out
+
+
 def total_variation(images):
     """tv[n] = sum of |vertical| + |horizontal| neighbour differences over all channels of a float32 [N,C,H,W] GPU tensor with any
     strides (NCHW, channels_last, a permuted NHWC buffer): bd_total_variation.  Returns a float32 [N] device tensor."""

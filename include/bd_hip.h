@@ -800,6 +800,57 @@ int bd_pairwise_sqdist(const float* x, int64_t ldx, int N, int D, float* d2, int
 int bd_total_variation(const float* x, int N, int C, int H, int W, int64_t stride_n, int64_t stride_c, int64_t stride_h,
                        int64_t stride_w, float* tv, bd_stream_t stream);
 
+/* Sample-quality metrics on feature rows (metrics.knn_sqradius / prdc / precision_recall / kid; DESIGN.md section 3, "Quality
+ * metrics on features"): pairwise work between the rows of a (fp32 [Na, D], row stride lda >= D floats) and of b ([Nb, D], ldb)
+ * reduced per row of a, without ever storing the Na x Nb matrix.  Any 4-byte aligned base and any row stride are accepted; when both
+ * bases are 16-byte aligned and both strides are multiples of 4 the rows are read with vector loads.  FINITE INPUTS ARE THE CALLER'S
+ * DUTY: a NaN or an infinity in a row makes that row's (and its partners') results unspecified; nothing checks for them.
+ *
+ * d2(a_i, b_j) = sum_k (a[i][k] - b[j][k])^2 with the arithmetic of bd_pairwise_sqdist: the difference in fp32 BEFORE the square,
+ * never the Gram identity; the sums over even and over odd k are kept apart and added at the end.  dot(a_i, b_j) is the fp32 FMA
+ * chain in the same k order.  One device function produces the value of a pair, so it has the same bits in every entry point below,
+ * with a and b exchanged, alone or inside any larger call, and from call to call.
+ *
+ * A workgroup owns 64 rows of a and walks 64-column tiles of b; D is never split.  When there are few strips of 64 rows the column
+ * tiles are cut into csplit contiguous ranges whose per-row partial results go to the workspace [csplit][Na][...] and are folded in
+ * split order by a second launch (no atomics).  bd_cross_plan reports the cut: strips = ceil(Na / 64), col_tiles = ceil(Nb / 64),
+ * csplit_cap = max(1, min(8 * CUs / strips, col_tiles)), tiles_per_split = ceil(col_tiles / csplit_cap), csplit = ceil(col_tiles /
+ * tiles_per_split).  Each *_workspace_bytes is csplit_cap * Na * (bytes per row) when csplit_cap > 1 and 0 otherwise (workspace may
+ * then be NULL); it is 0 for arguments the entry point rejects; for a fixed Na it does not decrease with Nb or with k.
+ *
+ * bd_knn_sqradius: out[i] = the k-th smallest of { d2(x_i, x_j) : j != i }, 1 <= k <= 16 and k <= N - 1 (else BD_ERR_INVALID).
+ *   Self is left out by index, not by value: a duplicate row gives 0.  The k-th smallest of a multiset depends neither on the order
+ *   in which its members arrive nor on csplit.  Bytes per row: 4 k.
+ * bd_cross_ksmallest: out[i][0 .. k-1] (fp32 [Na, k], ascending) = the k smallest of { d2(a_i, b_j) : j != i + self_col0 }, +inf
+ *   where fewer than k columns exist.  self_col0 = 0 with a == b is the neighbour list behind bd_knn_sqradius; rows a = x + r * ldx
+ *   with self_col0 = r score a slice of the rows of x; self_col0 = -Na excludes nothing.  1 <= k <= 16.  Bytes per row: 4 k.
+ * bd_cross_count_min: count[i] = #{ j : d2(a_i, b_j) <= radius2[j] } (int32) and min_d2[i] = min_j d2(a_i, b_j).  No pair is left
+ *   out.  radius2 == NULL: no count is taken and count may be NULL.  Integer sums and minima are order-independent: the bits depend
+ *   neither on csplit nor on Na.  Bytes per row: 8.
+ * bd_poly3_rowsum: rowsum[i] = sum_j (double(dot(a_i, b_j)) / D + 1)^3 in fp64, the cubic polynomial kernel of KID; exclude_diag
+ *   != 0 leaves out j == i (a and b the same set).  Columns are added in order within a quarter tile, the four quarters, the tiles and
+ *   the splits in order: bit-identical from call to call for one (Na, Nb) on one device; not across different csplit.  rowsum and
+ *   the workspace must be 8-byte aligned.  Bytes per row: 8.
+ * Status: BD_ERR_INVALID for a null pointer, Na / Nb / D < 1, a row stride < D, a base that is not 4-byte aligned, k out of range;
+ * BD_ERR_UNSUPPORTED for Na > 65535 * 64; BD_ERR_WORKSPACE.  Every check runs on the host before any launch and its message names
+ * the entry point. */
+typedef struct {
+    int strips, col_tiles, csplit, tiles_per_split, csplit_cap;
+} bd_cross_plan_info;
+int bd_cross_plan(int Na, int Nb, int D, bd_cross_plan_info* out);
+size_t bd_knn_sqradius_workspace_bytes(int N, int D, int k);
+int bd_knn_sqradius(const float* x, int64_t ldx, int N, int D, int k, float* out, void* workspace, size_t workspace_bytes,
+                    bd_stream_t stream);
+size_t bd_cross_ksmallest_workspace_bytes(int Na, int Nb, int D, int k);
+int bd_cross_ksmallest(const float* a, int64_t lda, int Na, const float* b, int64_t ldb, int Nb, int D, int k, int64_t self_col0,
+                       float* out, void* workspace, size_t workspace_bytes, bd_stream_t stream);
+size_t bd_cross_count_min_workspace_bytes(int Na, int Nb, int D);
+int bd_cross_count_min(const float* a, int64_t lda, int Na, const float* b, int64_t ldb, int Nb, int D, const float* radius2,
+                       int32_t* count, float* min_d2, void* workspace, size_t workspace_bytes, bd_stream_t stream);
+size_t bd_poly3_rowsum_workspace_bytes(int Na, int Nb, int D);
+int bd_poly3_rowsum(const float* a, int64_t lda, int Na, const float* b, int64_t ldb, int Nb, int D, int exclude_diag, double* rowsum,
+                    void* workspace, size_t workspace_bytes, bd_stream_t stream);
+
 /* Per-image scores of a batch against a target that may be broadcast (metrics.mse_per_image / ssim_per_image /
  * attack_success_rate, the loss split of TrainEngine; DESIGN.md section 3, "Per-image scores").  Both images are [N,C,H,W] given by
  * element strides (all >= 0); any of the target's strides may be 0 (one target shared by all images and / or channels).
