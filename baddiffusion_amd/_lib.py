@@ -243,6 +243,10 @@ class VbTermsDesc(C.Structure):
                 ("term_add", vp), ("term_mul", vp), ("inv_sigma_dec", f32), ("clip_denoised", i32), ("bits", vp), ("x0_mse", vp)]
 
 
+class VbTermsShiftDesc(C.Structure):
+    _fields_ = VbTermsDesc._fields_ + [("r", vp), ("r_stride", i64 * 4), ("term_shift", vp)]
+
+
 class UnetConfig(C.Structure):
     _fields_ = [("sample_size", i32), ("in_channels", i32), ("out_channels", i32), ("num_blocks", i32),
                 ("block_out_channels", i32 * 8), ("down_attn", i32 * 8), ("up_attn", i32 * 8),
@@ -304,6 +308,7 @@ SIGNATURES = {
     "bd_ssim_images": (i32, [C.POINTER(ImagePairDesc), f32, vp, vp, sz, vp]),
     "bd_vb_terms_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "bd_vb_terms": (i32, [C.POINTER(VbTermsDesc), vp, sz, vp]),
+    "bd_vb_terms_shift": (i32, [C.POINTER(VbTermsShiftDesc), vp, sz, vp]),
     "bd_conv2d_nhwc": (i32, [C.POINTER(Conv2dDesc), vp]),
     "bd_pool2d_nhwc": (i32, [vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "bd_resize_bilinear_nhwc": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, i32, f32, f32, vp]),

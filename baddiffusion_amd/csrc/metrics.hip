@@ -186,6 +186,10 @@ struct VbArgs {
     VbFinish f;
 };
 enum { VB_KL = 0, VB_DEC = 1, VB_PRIOR = 2 };
+// bd_vb_terms_shift: the fourth stream r and the table g ("The bound along the backdoored chain").  The unshifted
+// kernel's arguments are VbArgs alone, so bd_vb_terms is the code it was.
+template <bool SHIFT> struct VbArgsT : VbArgs {};
+template <> struct VbArgsT<true> : VbArgs { const float* r; long long sr[4]; const float* g; };
 
 // -log P of the discretised Gaussian decoder (bd_hip.h): both erfc arguments on the tail side, the floor by comparison (fmax would drop a NaN)
 __device__ __forceinline__ double vb_dec_nll(float x0, float xh, double inv_sigma) {
@@ -201,13 +205,20 @@ __device__ __forceinline__ double vb_dec_nll(float x0, float xh, double inv_sigm
     return -log(P);
 }
 
-// the walk of image_loss_kernel for one row kind: the workgroup's sum of the term's elements (and of (x0 - x0_hat)^2 when MSE), on thread 0
-template <int KIND, bool MSE>
-__device__ __forceinline__ void vb_walk(const VbArgs& d, long long n, int t, unsigned total, unsigned dc, unsigned dh, unsigned dw, double* red,
-                                        double& sum, double& sq) {
+// the walk of image_loss_kernel for one row kind: the workgroup's sum of the term's elements (and of (x0 - x0_hat)^2 when MSE), on thread 0.
+// SHIFT: a KL row's element is ((x0 + g[t] * r) - x0_hat)^2, a prior row's (x0 - r)^2; a t = 0 row does not read r.
+template <int KIND, bool MSE, bool SHIFT>
+__device__ __forceinline__ void vb_walk(const VbArgsT<SHIFT>& d, long long n, int t, unsigned total, unsigned dc, unsigned dh, unsigned dw,
+                                        double* red, double& sum, double& sq) {
     const float* __restrict__ p0 = d.x0 + n * d.s0[0];
     const float* __restrict__ pt = KIND == VB_PRIOR ? nullptr : d.xt + n * d.st[0];
     const float* __restrict__ pe = KIND == VB_PRIOR ? nullptr : d.ep + n * d.se[0];
+    const float* __restrict__ pr = nullptr;
+    float g = 0.f;
+    if constexpr (SHIFT) {
+        if (KIND != VB_DEC) pr = d.r + n * d.sr[0];
+        if (KIND == VB_KL) g = d.g[t];
+    }
     X0Coef k = {0.f, 1.f};
     if (KIND != VB_PRIOR) k = x0_coef(d.ac, t);
     const unsigned H = (unsigned)d.H, W = (unsigned)d.W;
@@ -217,16 +228,19 @@ __device__ __forceinline__ void vb_walk(const VbArgs& d, long long n, int t, uns
     double acc = 0.0, acc2 = 0.0;
 #pragma unroll 4
     for (unsigned i = beg; i < end; i += 256) {
-        const float v = p0[c * d.s0[1] + h * d.s0[2] + w * d.s0[3]];
+        float v = p0[c * d.s0[1] + h * d.s0[2] + w * d.s0[3]];
         if (KIND == VB_PRIOR) {
+            if constexpr (SHIFT) v = v - pr[c * d.sr[1] + h * d.sr[2] + w * d.sr[3]];
             acc += (double)(v * v);
         } else {
             float xh = x0_pred(k, pt[c * d.st[1] + h * d.st[2] + w * d.st[3]], pe[c * d.se[1] + h * d.se[2] + w * d.se[3]]);
             if (d.clip) xh = xh < -1.0f ? -1.0f : (xh > 1.0f ? 1.0f : xh);          // comparisons: a NaN stays a NaN
-            const float df = v - xh;
             if (KIND == VB_KL) {
+                if constexpr (SHIFT) v = v + g * pr[c * d.sr[1] + h * d.sr[2] + w * d.sr[3]];
+                const float df = v - xh;
                 acc += (double)(df * df);
             } else {
+                const float df = v - xh;
                 acc += vb_dec_nll(v, xh, d.inv_sigma);
                 if (MSE) acc2 += (double)(df * df);
             }
@@ -246,18 +260,19 @@ __device__ __forceinline__ void vb_walk(const VbArgs& d, long long n, int t, uns
 }
 
 // grid (nchunk, images of this launch), as image_loss_kernel.  part: [2][N][nchunk] (term sums, squared-difference sums) when nchunk > 1.
-template <bool MSE>
-__global__ __launch_bounds__(256) void vb_terms_kernel(VbArgs d, int n0, int N, unsigned total, int nchunk, unsigned dc, unsigned dh, unsigned dw,
-                                                       double* __restrict__ part, float* __restrict__ bits, float* __restrict__ mse) {
+template <bool MSE, bool SHIFT>
+__global__ __launch_bounds__(256) void vb_terms_kernel(VbArgsT<SHIFT> d, int n0, int N, unsigned total, int nchunk, unsigned dc, unsigned dh,
+                                                       unsigned dw, double* __restrict__ part, float* __restrict__ bits,
+                                                       float* __restrict__ mse) {
     __shared__ double red[256];
     const long long n = (long long)n0 + blockIdx.y;
     const long long tl = d.f.t[n];
     const int t = (int)tl;
     double sum, sq;
     if (tl < 0 || tl > d.f.T) sum = sq = __builtin_nan("");     // the launcher checked the host copy; a device array that differs reads no table
-    else if (t == d.f.T) vb_walk<VB_PRIOR, MSE>(d, n, t, total, dc, dh, dw, red, sum, sq);
-    else if (t == 0) vb_walk<VB_DEC, MSE>(d, n, t, total, dc, dh, dw, red, sum, sq);
-    else vb_walk<VB_KL, MSE>(d, n, t, total, dc, dh, dw, red, sum, sq);
+    else if (t == d.f.T) vb_walk<VB_PRIOR, MSE, SHIFT>(d, n, t, total, dc, dh, dw, red, sum, sq);
+    else if (t == 0) vb_walk<VB_DEC, MSE, SHIFT>(d, n, t, total, dc, dh, dw, red, sum, sq);
+    else vb_walk<VB_KL, MSE, SHIFT>(d, n, t, total, dc, dh, dw, red, sum, sq);
     if (threadIdx.x == 0) {
         if (nchunk == 1) {
             bits[n] = vb_finish(d.f, n, sum / (double)total);
@@ -617,35 +632,44 @@ extern "C" size_t bd_vb_terms_workspace_bytes(int N, int C, int H, int W) {
     return 2 * bd_image_loss_workspace_bytes(N, C, H, W);                   // the term sums and the squared-difference sums
 }
 
-extern "C" int bd_vb_terms(const bd_vb_terms_desc* d, void* workspace, size_t workspace_bytes, bd_stream_t stream) {
-    BD_CHECK(d, BD_ERR_INVALID, "bd_vb_terms: null descriptor");
-    BD_CHECK(d->x0 && d->t && d->t_host && d->alphas_cumprod && d->term_add && d->term_mul && d->bits, BD_ERR_INVALID,
-             "bd_vb_terms: null pointer");
-    BD_CHECK(d->N > 0 && d->C > 0 && d->H > 0 && d->W > 0, BD_ERR_INVALID, "bd_vb_terms: N=%d C=%d H=%d W=%d must be positive", d->N, d->C,
-             d->H, d->W);
-    BD_CHECK(d->T >= 1, BD_ERR_INVALID, "bd_vb_terms: T=%d must be positive", d->T);
-    BD_CHECK(d->inv_sigma_dec > 0.f && d->inv_sigma_dec <= 3.4e38f, BD_ERR_INVALID, "bd_vb_terms: inv_sigma_dec=%g must be positive and finite",
+// the checks and launches of bd_vb_terms and bd_vb_terms_shift (D: either descriptor; the shared fields carry the same names)
+template <bool SHIFT, class D>
+static int vb_terms_run(const D* d, void* workspace, size_t workspace_bytes, bd_stream_t stream, const char* who) {
+    BD_CHECK(d, BD_ERR_INVALID, "%s: null descriptor", who);
+    BD_CHECK(d->x0 && d->t && d->t_host && d->alphas_cumprod && d->term_add && d->term_mul && d->bits, BD_ERR_INVALID, "%s: null pointer", who);
+    BD_CHECK(d->N > 0 && d->C > 0 && d->H > 0 && d->W > 0, BD_ERR_INVALID, "%s: N=%d C=%d H=%d W=%d must be positive", who, d->N, d->C, d->H,
+             d->W);
+    BD_CHECK(d->T >= 1, BD_ERR_INVALID, "%s: T=%d must be positive", who, d->T);
+    BD_CHECK(d->inv_sigma_dec > 0.f && d->inv_sigma_dec <= 3.4e38f, BD_ERR_INVALID, "%s: inv_sigma_dec=%g must be positive and finite", who,
              (double)d->inv_sigma_dec);
-    BD_CHECK((long long)d->C * d->H * d->W < (1ll << 31), BD_ERR_UNSUPPORTED, "bd_vb_terms: C*H*W=%lld does not fit 31 bits",
+    BD_CHECK((long long)d->C * d->H * d->W < (1ll << 31), BD_ERR_UNSUPPORTED, "%s: C*H*W=%lld does not fit 31 bits", who,
              (long long)d->C * d->H * d->W);
     bool reads_chain = false;
     for (int n = 0; n < d->N; ++n) {
         const long long t = d->t_host[n];
-        BD_CHECK(t >= 0 && t <= d->T, BD_ERR_INVALID, "bd_vb_terms: t[%d]=%lld outside [0, %d]", n, t, d->T);
+        BD_CHECK(t >= 0 && t <= d->T, BD_ERR_INVALID, "%s: t[%d]=%lld outside [0, %d]", who, n, t, d->T);
         reads_chain |= t < d->T;
     }
-    BD_CHECK(!reads_chain || (d->x_t && d->eps), BD_ERR_INVALID, "bd_vb_terms: null x_t or eps with a row at t < T");
+    BD_CHECK(!reads_chain || (d->x_t && d->eps), BD_ERR_INVALID, "%s: null x_t or eps with a row at t < T", who);
     for (int i = 0; i < 4; ++i)
         BD_CHECK(d->x0_stride[i] >= 0 && d->xt_stride[i] >= 0 && d->eps_stride[i] >= 0, BD_ERR_INVALID,
-                 "bd_vb_terms: negative stride (x0 %lld, x_t %lld, eps %lld at dim %d)", (long long)d->x0_stride[i], (long long)d->xt_stride[i],
+                 "%s: negative stride (x0 %lld, x_t %lld, eps %lld at dim %d)", who, (long long)d->x0_stride[i], (long long)d->xt_stride[i],
                  (long long)d->eps_stride[i], i);
+    VbArgsT<SHIFT> a;
+    if constexpr (SHIFT) {
+        BD_CHECK(d->r && d->term_shift, BD_ERR_INVALID, "%s: null r or term_shift", who);
+        for (int i = 0; i < 4; ++i) {
+            BD_CHECK(d->r_stride[i] >= 0, BD_ERR_INVALID, "%s: negative stride (r %lld at dim %d)", who, (long long)d->r_stride[i], i);
+            a.sr[i] = d->r_stride[i];
+        }
+        a.r = d->r; a.g = d->term_shift;
+    }
     const size_t need = bd_vb_terms_workspace_bytes(d->N, d->C, d->H, d->W);
-    BD_CHECK(workspace_bytes >= need && (workspace || !need), BD_ERR_WORKSPACE, "bd_vb_terms: workspace %zu < %zu",
+    BD_CHECK(workspace_bytes >= need && (workspace || !need), BD_ERR_WORKSPACE, "%s: workspace %zu < %zu", who,
              workspace ? workspace_bytes : (size_t)0, need);
     const unsigned total = (unsigned)((long long)d->C * d->H * d->W);
     const int nchunk = (int)cdiv(total, IL_CHUNK);
     const unsigned dq = 256u / (unsigned)d->W, dw = 256u % (unsigned)d->W, dc = dq / (unsigned)d->H, dh = dq % (unsigned)d->H;
-    VbArgs a;
     a.C = d->C; a.H = d->H; a.W = d->W; a.clip = d->clip_denoised != 0;
     a.x0 = d->x0; a.xt = d->x_t; a.ep = d->eps; a.ac = d->alphas_cumprod;
     for (int i = 0; i < 4; ++i) { a.s0[i] = d->x0_stride[i]; a.st[i] = d->xt_stride[i]; a.se[i] = d->eps_stride[i]; }
@@ -656,21 +680,29 @@ extern "C" int bd_vb_terms(const bd_vb_terms_desc* d, void* workspace, size_t wo
         const int n = d->N - n0 < IMG_MAX_GRID ? d->N - n0 : IMG_MAX_GRID;
         const dim3 grid((unsigned)nchunk, (unsigned)n);
         if (d->x0_mse)
-            hipLaunchKernelGGL(vb_terms_kernel<true>, grid, dim3(256), 0, S(stream), a, n0, d->N, total, nchunk, dc, dh, dw, part, d->bits,
-                               d->x0_mse);
+            hipLaunchKernelGGL((vb_terms_kernel<true, SHIFT>), grid, dim3(256), 0, S(stream), a, n0, d->N, total, nchunk, dc, dh, dw, part,
+                               d->bits, d->x0_mse);
         else
-            hipLaunchKernelGGL(vb_terms_kernel<false>, grid, dim3(256), 0, S(stream), a, n0, d->N, total, nchunk, dc, dh, dw, part, d->bits,
-                               d->x0_mse);
-        BD_LAUNCH_CHECK("vb_terms");
+            hipLaunchKernelGGL((vb_terms_kernel<false, SHIFT>), grid, dim3(256), 0, S(stream), a, n0, d->N, total, nchunk, dc, dh, dw, part,
+                               d->bits, d->x0_mse);
+        BD_LAUNCH_CHECK(SHIFT ? "vb_terms_shift" : "vb_terms");
     }
     if (nchunk > 1) {
         hipLaunchKernelGGL(image_fold_kernel<true>, dim3((unsigned)d->N), dim3(256), 0, S(stream), part, nchunk, (double)total, d->bits, a.f);
-        BD_LAUNCH_CHECK("vb_terms_fold");
+        BD_LAUNCH_CHECK(SHIFT ? "vb_terms_shift_fold" : "vb_terms_fold");
         if (d->x0_mse) {
             hipLaunchKernelGGL(image_fold_kernel<false>, dim3((unsigned)d->N), dim3(256), 0, S(stream), part + (size_t)d->N * nchunk, nchunk,
                                (double)total, d->x0_mse, VbFinish{});
-            BD_LAUNCH_CHECK("vb_terms_fold_mse");
+            BD_LAUNCH_CHECK(SHIFT ? "vb_terms_shift_fold_mse" : "vb_terms_fold_mse");
         }
     }
     return BD_OK;
+}
+
+extern "C" int bd_vb_terms(const bd_vb_terms_desc* d, void* workspace, size_t workspace_bytes, bd_stream_t stream) {
+    return vb_terms_run<false>(d, workspace, workspace_bytes, stream, "bd_vb_terms");
+}
+
+extern "C" int bd_vb_terms_shift(const bd_vb_terms_shift_desc* d, void* workspace, size_t workspace_bytes, bd_stream_t stream) {
+    return vb_terms_run<true>(d, workspace, workspace_bytes, stream, "bd_vb_terms_shift");
 }

@@ -994,15 +994,35 @@ def vb_terms(x0, x_t, eps, t, tables, clip_denoised=True, want_x0_mse=False):
     back (a synchronisation), because the launcher checks the values on the host; tables: likelihood.vb_tables(...).
     Returns bits, a float32 [N] device tensor whose entries do not depend on the storage order, the batch around a row or the other
     rows' t; with want_x0_mse (bits, x0_mse), x0_mse[n] the row's mean (x0 - x0_hat)^2."""
-    lib = L.load(); _need_cuda(x0, x_t, eps)
+    return _vb_terms("vb_terms", x0, x_t, eps, None, t, tables, clip_denoised, want_x0_mse)
+
+
+def vb_terms_shift(x0, x_t, eps, r, t, tables, clip_denoised=True, want_x0_mse=False):
+    """vb_terms along the backdoored chain (bd_vb_terms_shift; bd_hip.h, likelihood.py "The backdoored chain"): a KL row's element is
+    (x0 + g_t r - x0_hat)^2, a prior row's (x0 - r)^2, a t = 0 row is vb_terms's and does not read r.
+    r: the shift image(s), a float32 GPU tensor [N,C,H,W] of any non-negative strides, or [C,H,W] / [1,C,H,W], one image every row reads
+    (by stride 0: nothing is copied); tables: likelihood.vb_tables(..., shift=True, device=...).  Everything else, the returned tensors
+    and their independence properties as in vb_terms; x0_mse[n] is the row's mean of the squared term above."""
+    return _vb_terms("vb_terms_shift", x0, x_t, eps, r, t, tables, clip_denoised, want_x0_mse)
+
+
+def _vb_terms(who, x0, x_t, eps, r, t, tables, clip_denoised, want_x0_mse):
+    """the checks and the call of vb_terms (r is None) and vb_terms_shift"""
+    shift = who == "vb_terms_shift"
+    lib = L.load(); _need_cuda(x0, x_t, eps, r)
     if x0.dim() != 4 or x0.dtype != torch.float32 or x0.numel() == 0:
-        raise TypeError(f"vb_terms: x0 must be a non-empty float32 [N,C,H,W] tensor, got {x0.dtype} {tuple(x0.shape)}")
+        raise TypeError(f"{who}: x0 must be a non-empty float32 [N,C,H,W] tensor, got {x0.dtype} {tuple(x0.shape)}")
     for name, v in (("x_t", x_t), ("eps", eps)):
         if v is not None and (v.dtype != torch.float32 or v.shape != x0.shape):
-            raise TypeError(f"vb_terms: {name} must be float32 {tuple(x0.shape)}, got {v.dtype} {tuple(v.shape)}")
+            raise TypeError(f"{who}: {name} must be float32 {tuple(x0.shape)}, got {v.dtype} {tuple(v.shape)}")
     N, Cc, H, W = x0.shape
+    if shift:
+        if not torch.is_tensor(r) or r.dtype != torch.float32 or tuple(r.shape) not in ((N, Cc, H, W), (1, Cc, H, W), (Cc, H, W)):
+            raise TypeError(f"{who}: r must be float32 {tuple(x0.shape)}, or one image {(Cc, H, W)} / {(1, Cc, H, W)}, got "
+                            f"{getattr(r, 'dtype', type(r))} {tuple(getattr(r, 'shape', ()))}")
+        r_stride = (0,) + tuple(r.stride()) if r.dim() == 3 else (r.stride(0) if r.shape[0] == N else 0,) + tuple(r.stride()[1:])
     if not torch.is_tensor(t) or t.dtype != torch.int64 or tuple(t.shape) != (N,):
-        raise TypeError(f"vb_terms: t must be an int64 [{N}] tensor")
+        raise TypeError(f"{who}: t must be an int64 [{N}] tensor")
     dev = x0.device
     t_host = t.cpu().contiguous()
     t_dev = t.to(dev).contiguous()
@@ -1011,19 +1031,28 @@ def vb_terms(x0, x_t, eps, t, tables, clip_denoised=True, want_x0_mse=False):
     T = int(tables["T"])
     if add.numel() != T + 1 or mul.numel() != T + 1 or ac.numel() != T or add.dtype != torch.float32 or mul.dtype != torch.float32 \
             or ac.dtype != torch.float32:
-        raise ValueError(f"vb_terms: tables must hold float32 add / mul of length T + 1 = {T + 1} and alphas_cumprod of length {T}")
+        raise ValueError(f"{who}: tables must hold float32 add / mul of length T + 1 = {T + 1} and alphas_cumprod of length {T}")
+    if shift:
+        g = tables.get("shift")
+        if not torch.is_tensor(g) or g.dtype != torch.float32 or g.numel() != T + 1:
+            raise ValueError(f"{who}: tables must hold a float32 shift of length T + 1 = {T + 1} (likelihood.vb_tables(..., shift=True, device=...))")
+        _need_cuda(g)
     bits = torch.empty(N, device=dev)
     mse = torch.empty(N, device=dev) if want_x0_mse else None
-    d = L.VbTermsDesc(N=N, C=Cc, H=H, W=W, x0=L.ptr(x0), x_t=L.ptr(x_t), eps=L.ptr(eps), t=L.ptr(t_dev), t_host=t_host.data_ptr(),
-                      alphas_cumprod=L.ptr(ac), T=T, term_add=L.ptr(add), term_mul=L.ptr(mul), inv_sigma_dec=float(tables["inv_sigma_dec"]),
-                      clip_denoised=int(bool(clip_denoised)), bits=L.ptr(bits), x0_mse=L.ptr(mse))
+    common = dict(N=N, C=Cc, H=H, W=W, x0=L.ptr(x0), x_t=L.ptr(x_t), eps=L.ptr(eps), t=L.ptr(t_dev), t_host=t_host.data_ptr(),
+                  alphas_cumprod=L.ptr(ac), T=T, term_add=L.ptr(add), term_mul=L.ptr(mul), inv_sigma_dec=float(tables["inv_sigma_dec"]),
+                  clip_denoised=int(bool(clip_denoised)), bits=L.ptr(bits), x0_mse=L.ptr(mse))
+    d = L.VbTermsShiftDesc(r=L.ptr(r), term_shift=L.ptr(g), **common) if shift else L.VbTermsDesc(**common)
     for i in range(4):
         d.x0_stride[i] = x0.stride(i)
         d.xt_stride[i] = 0 if x_t is None else x_t.stride(i)
         d.eps_stride[i] = 0 if eps is None else eps.stride(i)
+        if shift:
+            d.r_stride[i] = r_stride[i]
     nbytes = lib.bd_vb_terms_workspace_bytes(N, Cc, H, W)
     ws = workspace(nbytes, dev, "image_scores") if nbytes else None
-    L.check(lib.bd_vb_terms(C.byref(d), L.ptr(ws), nbytes, L.stream()), "bd_vb_terms")
+    entry = "bd_" + who
+    L.check(getattr(lib, entry)(C.byref(d), L.ptr(ws), nbytes, L.stream()), entry)
     return (bits, mse) if want_x0_mse else bits
 
 

@@ -6,7 +6,7 @@
                              [--clean_source none|synthetic|dataset] [--clean_n 256] [--clean_batch 64] [--clean_weight 1.0]
                              [--clean_target frozen|noise] [--dataset CIFAR10] [--dataset_path datasets]
                              [--target NAME] [--trigger BOX_14] [--asr_threshold 1e-3] [--dyn_threshold V [--dyn_threshold_ratio 0.995]]
-                             [--bpd_images N [--bpd_t_stride K]]
+                             [--bpd_images N [--bpd_t_stride K] [--bpd_backdoor]]
 
 The sibling of anp_defense.py.  Stages (baddiffusion_amd/inversion.py, baddiffusion_amd/defense.py):
   1. invert_trigger: the shift tau the frozen network follows;
@@ -24,6 +24,11 @@ papers use, not a finding.
 checkpoint on N clean rows -- the first N of the clean-data term's images, or of the dataset (--dataset, default CIFAR10) without one --
 before and after the removal, on the same noise, printed beside the drift and written as score.json["bpd"].  --bpd_t_stride K evaluates every
 K-th timestep only and reports likelihood.estimate_bpd, marked as an estimate.  Without the flag nothing changes.
+--bpd_backdoor (needs --bpd_images and --target) adds the figure that needs no samples: bits per dimension of the target along the chain
+triggered by --trigger (likelihood.bits_per_dim(backdoor=...), the same N rows as carriers, the clamped sampler's bound), before and after the
+removal on the same noise, printed and written as score.json["bpd"]["backdoor_before" / "backdoor_after"].  One expects a removal to RAISE
+it -- the repaired model should charge more bits for the target when the trigger is present -- but nothing here has measured that: no
+really backdoored checkpoint has been scored with it yet.
 Outputs in <output_dir>/<name>: config.json, score.json ({"before", "after", "detected", "removal"[, "drift"][, "bpd"]}), tau.pt and the repaired model in the
 diffusers layout (unet/, scheduler/), which DiffuserModelSched.get_trained loads.  `--ckpt` must be a local diffusers-layout directory.
 """
@@ -77,6 +82,7 @@ class Config:
     dyn_threshold_ratio: float = 0.995
     bpd_images: int = None
     bpd_t_stride: int = 1
+    bpd_backdoor: bool = False
 
 
 DEFAULT_ASR_THRESHOLD = 1e-3    # of the order the papers use; a choice, not a finding
@@ -129,9 +135,14 @@ def get_config(argv=None):
     p.add_argument("--dyn_threshold_ratio", type=float, help="the quantile of --dyn_threshold (0.995)")
     p.add_argument("--bpd_images", type=int, help="bits per dimension (variational bound) of this many clean rows, before -> after the removal")
     p.add_argument("--bpd_t_stride", type=int, help="with --bpd_images: evaluate every K-th timestep and report the estimate (default 1: the bound)")
+    p.add_argument("--bpd_backdoor", action="store_true",
+                   help="with --bpd_images and --target: bits per dimension of the target along the chain triggered by --trigger, before -> "
+                        "after the removal (one expects it to rise; not measured on a really backdoored checkpoint yet)")
     args = p.parse_args(argv)
     if args.bpd_t_stride is not None and args.bpd_images is None:
         p.error("--bpd_t_stride needs --bpd_images")
+    if args.bpd_backdoor and (args.bpd_images is None or args.target is None):
+        p.error("--bpd_backdoor needs --bpd_images (the carrier rows) and --target (the image the triggered chain ends in)")
     if (args.bpd_images is not None and args.bpd_images < 1) or (args.bpd_t_stride is not None and args.bpd_t_stride < 1):
         p.error("--bpd_images and --bpd_t_stride must be positive")
     if args.dyn_threshold_ratio is not None and args.dyn_threshold is None:
@@ -150,7 +161,9 @@ def get_config(argv=None):
     os.makedirs(config.output_dir, exist_ok=True)
     with open(os.path.join(config.output_dir, "config.json"), "w") as f:
         # (the bpd fields appear only with --bpd_images: without the flag the file is what it was before the flag existed)
-        json.dump({k: v for k, v in config.__dict__.items() if config.bpd_images is not None or not k.startswith("bpd_")}, f, indent=2,
+        # (and bpd_backdoor only with --bpd_backdoor)
+        json.dump({k: v for k, v in config.__dict__.items()
+                   if (config.bpd_images is not None or not k.startswith("bpd_")) and (config.bpd_backdoor or k != "bpd_backdoor")}, f, indent=2,
                   default=str)
     return config
 
@@ -252,12 +265,22 @@ def bpd_rows(config, model, clean, log=print):
     return clean[:n]
 
 
-def bpd(config, model, noise_sched, rows):
-    """mean bits per dimension of `rows` (the estimate of likelihood.estimate_bpd with --bpd_t_stride > 1), always on the same noise"""
+def backdoor_pair(config, model):
+    """(trigger, target) float32 [C, S, S] of --trigger / --target, as ops.poison_qsample takes them"""
+    from baddiffusion_amd.dataset import Backdoor
+    bd = Backdoor(root=config.dataset_path)
+    trigger = bd.get_trigger(type=config.trigger, channel=model.in_channels, image_size=model.sample_size)
+    return trigger.to(torch.float32), bd.get_target(type=config.target, trigger=trigger).to(torch.float32)
+
+
+def bpd(config, model, noise_sched, rows, backdoor=None):
+    """mean bits per dimension of `rows` (the estimate of likelihood.estimate_bpd with --bpd_t_stride > 1), always on the same noise;
+    backdoor: the (trigger, target) pair -- the rows are then the carriers of the triggered chain"""
     from baddiffusion_amd import likelihood
     g = torch.Generator(device=model.device); g.manual_seed(config.seed + 4)
     res = likelihood.bits_per_dim(model, noise_sched, rows, generator=g, max_batch_n=config.eval_max_batch,
-                                  timesteps=likelihood.strided_timesteps(noise_sched.config.num_train_timesteps, config.bpd_t_stride))
+                                  timesteps=likelihood.strided_timesteps(noise_sched.config.num_train_timesteps, config.bpd_t_stride),
+                                  **({} if backdoor is None else {"backdoor": backdoor}))
     return float(likelihood.estimate_bpd(res["terms"], config.bpd_t_stride).mean()), bool(res["complete"])
 
 
@@ -283,6 +306,9 @@ def main(argv=None):
         rows = bpd_rows(config, model, clean)
         result["bpd"] = {"n": config.bpd_images, "t_stride": config.bpd_t_stride}
         result["bpd"]["before"], result["bpd"]["complete"] = bpd(config, model, noise_sched, rows)
+        if config.bpd_backdoor:
+            pair = backdoor_pair(config, model)
+            result["bpd"]["backdoor_before"] = bpd(config, model, noise_sched, rows, backdoor=pair)[0]
     if config.clean_source != "none":
         # one frozen copy serves the removal (its targets) and the drift (the predictions before the repair)
         frozen = defense.frozen_copy(model)
@@ -296,6 +322,11 @@ def main(argv=None):
         result["bpd"]["after"] = bpd(config, model, noise_sched, rows)[0]
         print(f"bits/dim of {config.bpd_images} clean rows before -> after: {result['bpd']['before']:.6g} -> {result['bpd']['after']:.6g}"
               + ("" if result["bpd"]["complete"] else f" (ESTIMATE from every {config.bpd_t_stride}-th timestep)"))
+        if config.bpd_backdoor:
+            result["bpd"]["backdoor_after"] = bpd(config, model, noise_sched, rows, backdoor=pair)[0]
+            print(f"bits/dim of target {config.target} along the chain triggered by {config.trigger} ({config.bpd_images} carrier rows) before -> "
+                  f"after: {result['bpd']['backdoor_before']:.6g} -> {result['bpd']['backdoor_after']:.6g}"
+                  + ("" if result["bpd"]["complete"] else f" (ESTIMATE from every {config.bpd_t_stride}-th timestep)"))
     result["after"] = score(config, model, noise_sched, tau, noise, tag="after", target=target)
     if target is not None:
         print(f"ASR (MSE to {config.target} < {config.asr_threshold:g}) before -> after: {result['before']['asr_trigger']:.4f} -> "

@@ -932,6 +932,37 @@ typedef struct {
 size_t bd_vb_terms_workspace_bytes(int N, int C, int H, int W);
 int bd_vb_terms(const bd_vb_terms_desc* d, void* workspace, size_t workspace_bytes, bd_stream_t stream);
 
+/* The same terms along the BACKDOORED chain of BadDiffusion ("The bound along the backdoored chain"), whose x_t is
+ * shifted by rho_t r, rho_t = 1 - sqrt(ac[t]): the posterior mean of q'(x_{t-1} | x_t, x0) is c0_t x0 + ct_t x_t + d_t r, the model's
+ * reverse step is the unchanged one, and the two means differ by c0_t (x0 + g_t r - x0_hat), g_t = d_t / c0_t.  Everything is as in
+ * bd_vb_terms -- x0_hat, m, bits[n], the tables term_add / term_mul, the launches, the summation order and the fold -- but for a fourth
+ * stream r (fp32 [N,C,H,W] by element strides >= 0; 0 over n broadcasts one image), the table term_shift (fp32 [T + 1], device: g, with
+ * term_shift[0] = 0 and term_shift[T] = -1 by convention; likelihood.vb_tables(shift=True)) and the element terms, in fp32 and in exactly
+ * this order of operations (no contraction):
+ *     1 <= t < T   s = x0_i + term_shift[t] * r_i;   df = s - x0_hat_i;   e_i = df * df
+ *     t = 0        the decoder term of bd_vb_terms: r and term_shift are not read
+ *     t = T        df = x0_i - r_i;   e_i = df * df      (KL(q'(x_T | x0) || N(r, I)): sampling with the trigger starts from noise + r);
+ *                  term_shift[T] is not read, x_t and eps are not read and may be NULL when every row is a prior row.
+ * x0_mse: optional fp32 [N], the row's mean of that squared term ((x0 - x0_hat)^2 in a t = 0 row).
+ * With r all zeros every row equals bd_vb_terms's bit for bit; a t = 0 row does so for any r.  A NaN in a row's r makes that row's outputs
+ * NaN (t = 0 rows excepted) and no other's.  workspace: bd_vb_terms_workspace_bytes.  Status: what bd_vb_terms returns, and
+ * BD_ERR_INVALID for a null r / term_shift or a negative r stride. */
+typedef struct {
+    int N, C, H, W;
+    const float* x0;  int64_t x0_stride[4];    /* element strides n, c, h, w */
+    const float* x_t; int64_t xt_stride[4];
+    const float* eps; int64_t eps_stride[4];
+    const int64_t* t;                          /* device [N] */
+    const int64_t* t_host;                     /* host   [N], the same values */
+    const float* alphas_cumprod; int T;
+    const float* term_add; const float* term_mul; float inv_sigma_dec;
+    int clip_denoised;
+    float* bits; float* x0_mse;
+    const float* r; int64_t r_stride[4];       /* the shift image(s); r_stride[0] = 0: one image for every row */
+    const float* term_shift;                   /* device [T + 1]: g */
+} bd_vb_terms_shift_desc;
+int bd_vb_terms_shift(const bd_vb_terms_shift_desc* d, void* workspace, size_t workspace_bytes, bd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * FID feature extractor (measure path, SURVEY f-3): the layer kernels of pytorch_fid's InceptionV3 up to pool3
  * (/root/reference/fid_score.py:53 `from pytorch_fid.inception import InceptionV3`, :91-148 get_activations, :255

@@ -1,7 +1,7 @@
 """How good is a checkpoint on clean data?  The variational bound in bits per dimension, term by term, on the MI355X path.
 
     python likelihood_eval.py --ckpt <checkpoint dir> [--dataset CIFAR10] [--dataset_path datasets] [--n 16] [--batch 256] [--t_stride 1]
-                              [--variance_type fixed_small|fixed_large] [--no_clip] [--target NAME [--trigger BOX_14]]
+                              [--variance_type fixed_small|fixed_large] [--no_clip] [--target NAME [--trigger BOX_14] [--backdoor]]
                               [--output_dir DIR] [--seed 0] [--gpu 0]
 
 The sibling of inpaint_eval.py.  The first --n images of the dataset are scored by likelihood.bits_per_dim (baddiffusion_amd/likelihood.py:
@@ -14,10 +14,16 @@ that use improved-DDPM's tanh approximation).  A full evaluation is T = num_trai
   --no_clip         x0_hat is not clamped to [-1, 1]
   --target NAME     a Backdoor target (HAT, CAT, CORNER, TRIGGER, SHIFT; --trigger matters for the relative ones) quantised to uint8 and
                     scored as one more row: "target_bpd" -- does the model assign the backdoor target a better code length than the data?
+  --backdoor        (needs --target) also scores the --n rows as TRIGGERED rows along the backdoored chain of BadDiffusion
+                    (likelihood.bits_per_dim(backdoor=...): the images are the carriers of --trigger, x0 is the target, x_t is shifted by
+                    rho_t r): how many bits the model charges for the target when the trigger is present, on the same noise.  A perfectly
+                    implanted backdoor scores (close to) 0 in its KL rows under --no_clip and fixed_small; WITHOUT --no_clip the figure is
+                    the bound of the clamped sampler, under which it does not.  No really backdoored checkpoint has been scored with it yet.
 Outputs in <output_dir>/<name>: config.json, likelihood.json ({"complete", "t_stride", "timesteps", "n", "variance_type", "clip_denoised",
-"mean_bpd" (complete only), "estimate_bpd", "per_image", "prior_bpd", "l0_bpd"[, "target_bpd"]}) and likelihood_terms.npz (terms
-[len(timesteps) + 1, rows] float32 with the prior last and the target row last, timesteps).  `--ckpt` must be a local diffusers-layout
-directory.
+"mean_bpd" (complete only), "estimate_bpd", "per_image", "prior_bpd", "l0_bpd"[, "target_bpd"][, "backdoor_bpd": {"mean_bpd" (complete
+only), "estimate_bpd", "per_image", "prior_bpd", "l0_bpd", "clip_denoised"}]}) and likelihood_terms.npz (terms [len(timesteps) + 1, rows]
+float32 with the prior last and the target row last, timesteps[, backdoor_terms [len(timesteps) + 1, n]]).  Without --backdoor every file
+is what it was before the flag existed.  `--ckpt` must be a local diffusers-layout directory.
 """
 import argparse
 import json
@@ -44,6 +50,7 @@ class Config:
     clip: bool = True
     target: str = None
     trigger: str = "BOX_14"
+    backdoor: bool = False
     output_dir: Union[str, os.PathLike] = ""
     score_file: Union[str, os.PathLike] = "likelihood.json"
     terms_file: Union[str, os.PathLike] = "likelihood_terms.npz"
@@ -68,6 +75,10 @@ def get_config(argv=None):
     p.add_argument("--no_clip", action="store_true", help="do not clamp the predicted x0 to [-1, 1]")
     p.add_argument("--target", type=str, help="name of a backdoor target (Backdoor.get_target): scored as one more row")
     p.add_argument("--trigger", type=str, default=config.trigger, help="trigger name; needed only for the targets defined relative to the trigger")
+    p.add_argument("--backdoor", action="store_true",
+                   help="with --target: also score the rows as triggered rows along the backdoored chain (bits/dim of the target when the "
+                        "trigger is present); with the clamp on (no --no_clip) this is the bound of the clamped sampler, under which a "
+                        "perfect implant does not score 0")
     p.add_argument("--output_dir", "-od", type=str)
     p.add_argument("--seed", type=int, default=config.seed)
     p.add_argument("--gpu", "-g", type=str, default=config.gpu)
@@ -79,10 +90,13 @@ def get_config(argv=None):
     config.clip = not no_clip
     if config.n < 1 or config.batch < 1 or config.t_stride < 1:
         p.error("--n, --batch and --t_stride must be positive")
+    if config.backdoor and config.target is None:
+        p.error("--backdoor needs --target (the image the triggered chain ends in)")
     config.output_dir = os.path.join(config.output_dir or "", naming_fn(config))
     os.makedirs(config.output_dir, exist_ok=True)
     with open(os.path.join(config.output_dir, "config.json"), "w") as f:
-        json.dump({k: v for k, v in config.__dict__.items()}, f, indent=2, default=str)
+        # (the backdoor field appears only with --backdoor: without the flag the file is what it was before the flag existed)
+        json.dump({k: v for k, v in config.__dict__.items() if config.backdoor or k != "backdoor"}, f, indent=2, default=str)
     return config
 
 
@@ -105,6 +119,22 @@ def target_u8(config, model):
     trigger = bd.get_trigger(type=config.trigger, channel=model.in_channels, image_size=model.sample_size)
     target = bd.get_target(type=config.target, trigger=trigger).to(torch.float32)
     return ((target / 2 + 0.5).clamp(0, 1) * 255).round().to(torch.uint8).permute(1, 2, 0)[None].contiguous().to(model.device)
+
+
+def backdoor_pair(config, model):
+    """(trigger, target) float32 [C, S, S] of --trigger / --target, as ops.poison_qsample takes them"""
+    from baddiffusion_amd.dataset import Backdoor
+    bd = Backdoor(root=config.dataset_path)
+    trigger = bd.get_trigger(type=config.trigger, channel=model.in_channels, image_size=model.sample_size)
+    return trigger.to(torch.float32), bd.get_target(type=config.target, trigger=trigger).to(torch.float32)
+
+
+def summarise_backdoor(config, res):
+    """the "backdoor_bpd" block of a bits_per_dim(backdoor=...) result"""
+    out = summarise(config, res, res["terms"].shape[1])
+    out = {k: out[k] for k in ("mean_bpd", "estimate_bpd", "per_image", "prior_bpd", "l0_bpd") if k in out}
+    out["clip_denoised"] = bool(config.clip)
+    return out
 
 
 def summarise(config, res, n_clean):
@@ -136,13 +166,25 @@ def main(argv=None):
     result = summarise(config, res, n_clean)
     result["variance_type"] = config.variance_type or noise_sched.config.variance_type
     result["clip_denoised"] = bool(config.clip)
+    arrays = {"terms": res["terms"].numpy(), "timesteps": np.asarray(res["timesteps"], dtype=np.int64)}
+    if config.backdoor:
+        res_bd = likelihood.bits_per_dim(model, noise_sched, clean[:n_clean], timesteps=likelihood.strided_timesteps(T, config.t_stride),
+                                         generator=torch.manual_seed(config.seed), max_batch_n=config.batch, clip_denoised=config.clip,
+                                         variance_type=config.variance_type, backdoor=backdoor_pair(config, model))
+        result["backdoor_bpd"] = summarise_backdoor(config, res_bd)
+        arrays["backdoor_terms"] = res_bd["terms"].numpy()
     label = "bits/dim" if result["complete"] else f"bits/dim (ESTIMATE from every {config.t_stride}-th timestep)"
     print(f"{label}: {result['estimate_bpd']:.6g}  (prior {result['prior_bpd']:.3g}, L_0 {result['l0_bpd']:.6g})"
           + (f", target {config.target}: {result['target_bpd']:.6g}" if "target_bpd" in result else ""))
-    print(json.dumps({k: v for k, v in result.items() if k != "per_image"}))
+    if config.backdoor:
+        b = result["backdoor_bpd"]
+        print(f"{label} of target {config.target} along the chain triggered by {config.trigger}: {b['estimate_bpd']:.6g}  (prior "
+              f"{b['prior_bpd']:.3g}, L_0 {b['l0_bpd']:.6g}; {'clamped sampler' if config.clip else 'unclamped'})")
+    print(json.dumps({k: ({j: w for j, w in v.items() if j != "per_image"} if isinstance(v, dict) else v) for k, v in result.items()
+                      if k != "per_image"}))
     with open(os.path.join(config.output_dir, config.score_file), "w") as f:
         json.dump(result, f, indent=2)
-    np.savez(os.path.join(config.output_dir, config.terms_file), terms=res["terms"].numpy(), timesteps=np.asarray(res["timesteps"], dtype=np.int64))
+    np.savez(os.path.join(config.output_dir, config.terms_file), **arrays)
     return result
 
 

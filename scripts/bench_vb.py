@@ -1,6 +1,7 @@
 """Time the variational-bound term kernel on the GPU and write profiles/vb_terms.json.
 
     python scripts/bench_vb.py [--out profiles/vb_terms.json] [--rounds 9] [--full_images 2]
+    python scripts/bench_vb.py --shift [--out profiles/vb_shift_terms.json] [--rounds 9]
 
 bd_vb_terms at 2048 x 3 x 32 x 32 (the CIFAR evaluation batch) with mixed rows (t cycling through 0, 1, 2, 500, T-1, T) and with every row
 at t = 0 (the fp64 erfc path on all of them), and at 4 x 3 x 256 x 256 (mixed rows; 24 chunks per image and the fold launch).  HIP events
@@ -13,7 +14,16 @@ around back-to-back launches, warmed up, the routes alternated round by round (s
 `fused_not_slower` states fused <= torch on the medians; `gbytes_per_s` is the kernel's minimum traffic (12 B per element of a chain row,
 4 B of a prior row) over the fused median.  `full_evaluation` is likelihood.bits_per_dim over all T = 1000 timesteps of --full_images
 images on the CIFAR topology (default initialisation: the time does not depend on the weights) in chunks of 256 rows: UNet evaluations
-and seconds per image, and the share of it that ops.vb_terms takes.  Recorded, not asserted.  No GPU: the script fails, it has no CPU path."""
+and seconds per image, and the share of it that ops.vb_terms takes.  Recorded, not asserted.  No GPU: the script fails, it has no CPU path.
+
+--shift times bd_vb_terms_shift, the terms along the backdoored chain, instead (profiles/vb_shift_terms.json): mixed rows at
+2048 x 3 x 32 x 32 and at 4 x 3 x 256 x 256, three routes alternated round by round:
+
+  shift   ops.vb_terms_shift with one r per row
+  torch   the same result from torch ops on the device (torch_route with the shifted KL and prior elements)
+  plain   ops.vb_terms on the same rows: three streams where the shifted call reads four (16 B per element of a KL row, 8 B of a prior row)
+
+`fused_not_slower` states shift <= torch on the medians; `shift_over_plain` is recorded and nothing is expected of it."""
 import argparse
 import json
 import math
@@ -30,15 +40,19 @@ from scripts.bench_defense import compare  # noqa: E402
 MIX = (0, 1, 2, 500, 999, 1000)
 
 
-def torch_route(x0, x_t, eps, t, tab, clip=True):
-    """bits [N] of mixed rows from torch ops on the device"""
+def torch_route(x0, x_t, eps, t, tab, clip=True, r=None):
+    """bits [N] of mixed rows from torch ops on the device; r: the shift images of bd_vb_terms_shift (tab then holds "shift")"""
     T, ac = tab["T"], tab["alphas_cumprod"]
     chain = t < T
     a = ac[t.clamp(max=T - 1)].view(-1, 1, 1, 1)
     xh = (x_t - (1 - a).sqrt() * eps) / a.sqrt()
     if clip:
         xh = xh.clamp(-1, 1)
-    mean = torch.where(chain, ((x0 - xh) ** 2).flatten(1).mean(1, dtype=torch.float64), (x0 ** 2).flatten(1).mean(1, dtype=torch.float64))
+    if r is None:
+        mean = torch.where(chain, ((x0 - xh) ** 2).flatten(1).mean(1, dtype=torch.float64), (x0 ** 2).flatten(1).mean(1, dtype=torch.float64))
+    else:
+        kl = ((x0 + tab["shift"][t].view(-1, 1, 1, 1) * r - xh) ** 2).flatten(1).mean(1, dtype=torch.float64)
+        mean = torch.where(chain, kl, ((x0 - r) ** 2).flatten(1).mean(1, dtype=torch.float64))
     dec = (t == 0).nonzero().flatten()
     if dec.numel():
         v, d = x0[dec].double(), x0[dec].double() - xh[dec].double()
@@ -51,14 +65,58 @@ def torch_route(x0, x_t, eps, t, tab, clip=True):
     return ((tab["add"][t].double() + tab["mul"][t].double() * mean) / math.log(2.0)).float()
 
 
+def shift_rows(args):
+    """the --shift measurement: bd_vb_terms_shift, its torch composition and bd_vb_terms on the same mixed rows"""
+    from baddiffusion_amd import likelihood, ops
+    from baddiffusion_amd.schedulers import DDPMScheduler
+    dev = torch.device("cuda")
+    tab = likelihood.vb_tables(DDPMScheduler(), "fixed_large", device=dev, shift=True)
+    T, ac = tab["T"], tab["alphas_cumprod"]
+    result = {"device": torch.cuda.get_device_name(0), "variance_type": "fixed_large", "cases": []}
+    for name, B, S in (("mixed", 2048, 32), ("mixed_256", 4, 256)):
+        shape = (B, 3, S, S)
+        gen = torch.Generator().manual_seed(B + S + 1)
+        t_host = torch.tensor([MIX[i % len(MIX)] for i in range(B)], dtype=torch.int64)
+        t_dev = t_host.to(dev)
+        x0, r = ((torch.randint(0, 256, shape, generator=gen).float() / 255 * 2 - 1).to(dev) for _ in range(2))
+        noise, err = (torch.randn(shape, generator=gen).to(dev) for _ in range(2))
+        a = ac[t_dev.clamp(max=T - 1)].view(-1, 1, 1, 1)
+        x_t = a.sqrt() * x0 + (1 - a).sqrt() * noise + (1 - a.sqrt()) * r               # the shifted chain; the prediction is x0 + 0.01 * randn
+        eps = (x_t - a.sqrt() * (x0 + 0.01 * err)) / (1 - a).sqrt()
+        times = compare({"shift": lambda: ops.vb_terms_shift(x0, x_t, eps, r, t_host, tab),
+                         "torch": lambda: torch_route(x0, x_t, eps, t_dev, tab, r=r),
+                         "plain": lambda: ops.vb_terms(x0, x_t, eps, t_host, tab)}, args.rounds)
+        got, ref = ops.vb_terms_shift(x0, x_t, eps, r, t_host, tab).double(), torch_route(x0, x_t, eps, t_dev, tab, r=r).double()
+        n_kl, n_dec, n_prior = (int(m.sum()) for m in ((t_host > 0) & (t_host < T), t_host == 0, t_host == T))
+        nbytes = 4 * 3 * S * S * (4 * n_kl + 3 * n_dec + 2 * n_prior)
+        f, c, p = (times[k]["median_s"] for k in ("shift", "torch", "plain"))
+        row = {"case": name, "shape": list(shape), "t": list(MIX), "seconds": times, "shift_s": f, "torch_s": c, "plain_s": p,
+               "torch_over_shift": c / f, "shift_over_plain": f / p, "fused_not_slower": bool(f <= c), "bytes_min": nbytes,
+               "gbytes_per_s": nbytes / f / 1e9, "max_rel_difference_to_torch": float(((got - ref).abs() / ref.abs()).max())}
+        result["cases"].append(row)
+        print(json.dumps({k: v for k, v in row.items() if k != "seconds"}), flush=True)
+    result["fused_not_slower"] = all(r["fused_not_slower"] for r in result["cases"])
+    return result
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--out", default=os.path.join("profiles", "vb_terms.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--full_images", type=int, default=2)
+    ap.add_argument("--shift", action="store_true", help="time bd_vb_terms_shift instead (default --out: profiles/vb_shift_terms.json)")
     args = ap.parse_args(argv)
+    if args.out is None:
+        args.out = os.path.join("profiles", "vb_shift_terms.json" if args.shift else "vb_terms.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_vb: no GPU (timings are taken on the device or not at all)")
+    if args.shift:
+        result = shift_rows(args)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(result, f, indent=1)
+        print(f"wrote {args.out}")
+        return
     from baddiffusion_amd import likelihood, ops
     from baddiffusion_amd.model import DiffuserModelSched
     from baddiffusion_amd.schedulers import DDPMScheduler
