@@ -41,6 +41,8 @@ MODE_SAMPLING_OPTS = ["project", "mode", "eval_max_batch", "gpu", "fclip", "ckpt
 QUALITY_OPTS = ["measure_prdc_k", "measure_kid", "kid_subsets", "kid_subset_size"]     # measure / train+measure only; absent from every file unless given
 MODE_MEASURE_OPTS = ["project", "mode", "eval_max_batch", "gpu", "fclip", "ckpt", "sample_ep", "sched", "use_ema", "native_sched", "infer_steps", "asr_threshold",
                      "dyn_threshold", "dyn_threshold_ratio"] + QUALITY_OPTS
+# the training target's correction table (train / train+measure; resume reads it back); absent from every file unless given
+CORRECTION_OPTS = ["correction", "correction_zeta", "correction_steps", "correction_eta"]
 EMA_DIR, EMA_STATE = "unet_ema", "ema.bin"     # averaged weights in diffusers layout under output_dir; EMA scalars + shadow under ckpt/
 IGNORE_ARGS = ["overwrite", "is_save_all_model_epochs"]
 
@@ -105,6 +107,15 @@ def parse_args(argv=None):
                         "over --kid_subsets (100) subsets of --kid_subset_size (1000) rows, capped at measure_sample_n")
     p.add_argument("--kid_subsets", type=int, help="number of KID subsets (100); needs --measure_kid")
     p.add_argument("--kid_subset_size", type=int, help="rows per KID subset (1000); needs --measure_kid")
+    p.add_argument("--correction", type=str, choices=["ddpm", "ode", "sde", "ddim"],
+                   help="train: the coefficient c_t of the poisoned rows' target eps + c_t R, matched to the sampler the backdoor is to fire "
+                        "under (baddiffusion_amd/correction.py): ddpm = the reference's rho_t (the default, the DDPM ancestral sampler), "
+                        "ode = sqrt(1 - ac_t) (every deterministic sampler: DDIM eta 0, PNDM, DPM-Solver, UniPC, DEIS, Heun, LMS, Euler, "
+                        "KDPM2), sde = sqrt(1 - ac_t) / (1 + zeta^2) with --correction_zeta, ddim = the exact coefficient of a DDIM "
+                        "chain of --correction_steps steps at --correction_eta")
+    p.add_argument("--correction_zeta", type=float, help="noise level of --correction sde (0 = ode, 1 = the ancestral sampler's limit)")
+    p.add_argument("--correction_steps", type=int, help="steps of the DDIM chain --correction ddim is exact for")
+    p.add_argument("--correction_eta", type=float, help="eta of that chain (0)")
     return p.parse_args(argv)
 
 
@@ -208,6 +219,11 @@ def setup(argv=None, write=True):
         raise ValueError(f"--measure_prdc_k {args.measure_prdc_k} must be in [1, 16]")
     if (args.kid_subsets is not None and args.kid_subsets < 1) or (args.kid_subset_size is not None and args.kid_subset_size < 2):
         raise ValueError("--kid_subsets must be at least 1 and --kid_subset_size at least 2")
+    if any(getattr(args, k) is not None for k in CORRECTION_OPTS[1:]) and args.correction is None:
+        raise ValueError("--correction_zeta / --correction_steps / --correction_eta need --correction")
+    if args.correction is not None:
+        from baddiffusion_amd.correction import check_options
+        check_options(args.correction, zeta=args.correction_zeta, steps=args.correction_steps, eta=args.correction_eta)
     if not hasattr(config, "dataset"):
         raise ValueError("--dataset is required")
     if not hasattr(config, "sched"):
@@ -240,7 +256,8 @@ def setup(argv=None, write=True):
                 raise ValueError(f"Output directory: {config.output_dir} has already been created, please set overwrite flag --overwrite or -o")
             os.makedirs(config.output_dir, exist_ok=True)
             # the quality flags appear only when given: without them args.json is what it was before they existed
-            _write_json({k: v for k, v in vars(args).items() if k not in QUALITY_OPTS or v not in (None, False)}, config, "args.json")
+            _write_json({k: v for k, v in vars(args).items() if k not in QUALITY_OPTS + CORRECTION_OPTS or v not in (None, False)},
+                        config, "args.json")
             _write_json(config.__dict__, config, "config.json")
         elif args.mode == MODE_SAMPLING:
             _write_json(config.__dict__, config, "sampling.json")
@@ -522,6 +539,16 @@ def measure(config, dsl, folder_name, pipeline, rank=0, world=1):
                              extra={"inference_chunk": used[0] if len(used) == 1 else (used or None), **extra})
 
 
+def make_correction(config, noise_sched, device):
+    """the table of --correction (baddiffusion_amd/correction.py), or None: the reference's in-kernel rho_t"""
+    kind = getattr(config, "correction", None)
+    if kind is None:
+        return None
+    from baddiffusion_amd.correction import make_table
+    return make_table(kind, noise_sched, zeta=getattr(config, "correction_zeta", None), steps=getattr(config, "correction_steps", None),
+                      eta=getattr(config, "correction_eta", None), device=device)
+
+
 def make_ema(config, model):
     """the EMAModel of --use_ema (train_unconditional.py:465-473), or None"""
     if not getattr(config, "use_ema", False):
@@ -632,7 +659,8 @@ def train_loop(config, model, noise_sched, get_pipeline, dsl, device, world, ran
     engine = TrainEngine(model, noise_sched, lr=config.learning_rate, lr_warmup_steps=config.lr_warmup_steps,
                          num_training_steps=num_batch * config.epoch // config.gradient_accumulation_steps,
                          grad_accum_steps=config.gradient_accumulation_steps, ema=make_ema(config, model),
-                         track_split=bool(getattr(config, "log_loss_split", False)))
+                         track_split=bool(getattr(config, "log_loss_split", False)),
+                         correction=make_correction(config, noise_sched, device))
     ema = engine.ema
     if config.mode == MODE_RESUME:
         restore_training_state(config, engine, rank)

@@ -28,6 +28,14 @@ class QsampleDesc(C.Structure):
                 ("x_noisy", vp), ("ld_noisy", i64), ("target", vp), ("ld_target", i64)]
 
 
+class PoisonQsampleCorrDesc(C.Structure):
+    _fields_ = PoisonQsampleDesc._fields_ + [("corr", vp)]
+
+
+class QsampleCorrDesc(C.Structure):
+    _fields_ = QsampleDesc._fields_ + [("corr", vp)]
+
+
 class DdpmStepDesc(C.Structure):
     _fields_ = [("n", i64), ("model_output", vp), ("sample", vp), ("noise", vp), ("prev_sample", vp),
                 ("pred_original", vp), ("alphas_cumprod", vp), ("t", i32), ("prev_t", i32), ("variance_type", i32),
@@ -262,6 +270,8 @@ SIGNATURES = {
     "bd_version": (i32, []),
     "bd_poison_qsample": (i32, [C.POINTER(PoisonQsampleDesc), vp]),
     "bd_qsample": (i32, [C.POINTER(QsampleDesc), vp]),
+    "bd_poison_qsample_corr": (i32, [C.POINTER(PoisonQsampleCorrDesc), vp]),
+    "bd_qsample_corr": (i32, [C.POINTER(QsampleCorrDesc), vp]),
     "bd_nchw_to_nhwc": (i32, [vp, vp, i32, i32, i32, i32, i64, vp]),
     "bd_nhwc_to_nchw": (i32, [vp, i64, vp, i32, i32, i32, i32, vp]),
     "bd_ddpm_step": (i32, [C.POINTER(DdpmStepDesc), vp]),

@@ -33,17 +33,31 @@ static inline unsigned nblocks(int64_t n, int per = TPB, int64_t cap = 1 << 20) 
 // a-1 + a-2: trigger blend + BadDiffusion q_sample.  One thread per (b, pixel); loops channels.
 // dataset.py:275-276, :288-315 ; util.py:111 ; loss.py:264-285 ; scheduling_ddpm.py:429-442
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(TPB) void poison_qsample_kernel(bd_poison_qsample_desc d) {
+// The coefficient of R in the training target.  TABLE = false: the reference's rho_t (loss.py:270), from alphas[t] and s = sqrt(1 - ac_t).
+// TABLE = true (the *_corr descriptors): the caller's table corr[t], DESIGN.md section 3 "Sampler-matched correction terms"; alphas is
+// not read.  Everything else of the two kernel bodies below is common to both, so x_noisy and the optional outputs cannot differ.
+template <bool TABLE, class D>
+__device__ __forceinline__ float target_coef(const D& d, int64_t t, float s) {
+    if constexpr (TABLE) {
+        return d.corr[t];
+    } else {
+        const float al = d.alphas[t];
+        return (1.0f - sqrtf(al)) * s / (1.0f - al);
+    }
+}
+
+template <bool TABLE, class D>
+__device__ __forceinline__ void poison_qsample_body(const D& d) {
     const int64_t hw = (int64_t)d.H * d.W;
     const int64_t idx = (int64_t)blockIdx.x * TPB + threadIdx.x;
     if (idx >= (int64_t)d.B * hw) return;
     const int b = (int)(idx / hw);
     const int64_t pix = idx - (int64_t)b * hw;
     const int64_t t = d.timesteps[b];
-    const float ac = d.alphas_cumprod[t], al = d.alphas[t];
+    const float ac = d.alphas_cumprod[t];
     const float a = sqrtf(ac);                       // alphas_cumprod[t] ** 0.5
     const float s = sqrtf(1.0f - ac);                // (1 - alphas_cumprod[t]) ** 0.5
-    const float rho = (1.0f - sqrtf(al)) * s / (1.0f - al);   // loss.py:270
+    const float rho = target_coef<TABLE>(d, t, s);
     const bool poison = d.is_poison[b] != 0;
     // fused DataLoader gather + RandomHorizontalFlip (dataset.py:127-128): batch row b reads image row_index[b] of the
     // resident array, mirrored along W when flip[b]
@@ -81,16 +95,20 @@ __global__ __launch_bounds__(TPB) void poison_qsample_kernel(bd_poison_qsample_d
     }
 }
 
-__global__ __launch_bounds__(TPB) void qsample_kernel(bd_qsample_desc d) {
+__global__ __launch_bounds__(TPB) void poison_qsample_kernel(bd_poison_qsample_desc d) { poison_qsample_body<false>(d); }
+__global__ __launch_bounds__(TPB) void poison_qsample_corr_kernel(bd_poison_qsample_corr_desc d) { poison_qsample_body<true>(d); }
+
+template <bool TABLE, class D>
+__device__ __forceinline__ void qsample_body(const D& d) {
     const int64_t hw = (int64_t)d.H * d.W;
     const int64_t idx = (int64_t)blockIdx.x * TPB + threadIdx.x;
     if (idx >= (int64_t)d.B * hw) return;
     const int b = (int)(idx / hw);
     const int64_t pix = idx - (int64_t)b * hw;
     const int64_t t = d.timesteps[b];
-    const float ac = d.alphas_cumprod[t], al = d.alphas[t];
+    const float ac = d.alphas_cumprod[t];
     const float a = sqrtf(ac), s = sqrtf(1.0f - ac);
-    const float rho = (1.0f - sqrtf(al)) * s / (1.0f - al);
+    const float rho = target_coef<TABLE>(d, t, s);
     for (int c = 0; c < d.C; ++c) {
         const int64_t src = (int64_t)b * d.C * hw + (int64_t)c * hw + pix;
         const float x0 = d.x0[src], R = d.R[src], eps = d.noise[src];
@@ -99,6 +117,8 @@ __global__ __launch_bounds__(TPB) void qsample_kernel(bd_qsample_desc d) {
         d.target[idx * d.ld_target + c] = rho * R + eps;
     }
 }
+__global__ __launch_bounds__(TPB) void qsample_kernel(bd_qsample_desc d) { qsample_body<false>(d); }
+__global__ __launch_bounds__(TPB) void qsample_corr_kernel(bd_qsample_corr_desc d) { qsample_body<true>(d); }
 
 __global__ __launch_bounds__(TPB) void nchw_to_nhwc_kernel(const float* src, float* dst, int B, int C, int64_t hw, int64_t ld) {
     const int64_t idx = (int64_t)blockIdx.x * TPB + threadIdx.x;
@@ -1105,26 +1125,55 @@ using namespace bd;
 extern "C" const char* bd_last_error(void) { return g_err.c_str(); }
 extern "C" int bd_version(void) { return 1; }
 
+// the host checks of the two fused q_sample entry points; `coef` is the table the kernel reads the target's coefficient from
+// (alphas, or corr for the *_corr entry points, which do not read alphas)
+template <class D>
+static int poison_qsample_check(const char* who, const D* d, const float* coef) {
+    BD_CHECK(d->B > 0 && d->C > 0 && d->H > 0 && d->W > 0, BD_ERR_INVALID, "%s: bad shape", who);
+    BD_CHECK((d->images_f32 != nullptr) != (d->images_u8 != nullptr), BD_ERR_INVALID,
+             "%s: exactly one of images_f32 / images_u8 must be given", who);
+    BD_CHECK(d->is_poison && d->trigger && d->target_img && d->noise && d->timesteps && coef && d->alphas_cumprod &&
+                 d->x_noisy && d->target, BD_ERR_INVALID, "%s: null pointer", who);
+    BD_CHECK(d->ld_noisy >= d->C && d->ld_target >= d->C, BD_ERR_INVALID, "%s: ld < C", who);
+    return BD_OK;
+}
+template <class D>
+static int qsample_check(const char* who, const D* d, const float* coef) {
+    BD_CHECK(d->B > 0 && d->C > 0 && d->H > 0 && d->W > 0, BD_ERR_INVALID, "%s: bad shape", who);
+    BD_CHECK(d->x0 && d->R && d->noise && d->timesteps && coef && d->alphas_cumprod && d->x_noisy && d->target,
+             BD_ERR_INVALID, "%s: null pointer", who);
+    BD_CHECK(d->ld_noisy >= d->C && d->ld_target >= d->C, BD_ERR_INVALID, "%s: ld < C", who);
+    return BD_OK;
+}
+
 extern "C" int bd_poison_qsample(const bd_poison_qsample_desc* d, bd_stream_t stream) {
     BD_CHECK(d, BD_ERR_INVALID, "bd_poison_qsample: null descriptor");
-    BD_CHECK(d->B > 0 && d->C > 0 && d->H > 0 && d->W > 0, BD_ERR_INVALID, "bd_poison_qsample: bad shape");
-    BD_CHECK((d->images_f32 != nullptr) != (d->images_u8 != nullptr), BD_ERR_INVALID,
-             "bd_poison_qsample: exactly one of images_f32 / images_u8 must be given");
-    BD_CHECK(d->is_poison && d->trigger && d->target_img && d->noise && d->timesteps && d->alphas && d->alphas_cumprod &&
-                 d->x_noisy && d->target, BD_ERR_INVALID, "bd_poison_qsample: null pointer");
-    BD_CHECK(d->ld_noisy >= d->C && d->ld_target >= d->C, BD_ERR_INVALID, "bd_poison_qsample: ld < C");
+    if (int st = poison_qsample_check("bd_poison_qsample", d, d->alphas)) return st;
     hipLaunchKernelGGL(poison_qsample_kernel, dim3(nblocks((int64_t)d->B * d->H * d->W)), dim3(TPB), 0, S(stream), *d);
     BD_LAUNCH_CHECK("poison_qsample");
     return BD_OK;
 }
+extern "C" int bd_poison_qsample_corr(const bd_poison_qsample_corr_desc* d, bd_stream_t stream) {
+    BD_CHECK(d, BD_ERR_INVALID, "bd_poison_qsample_corr: null descriptor");
+    BD_CHECK(d->corr, BD_ERR_INVALID, "bd_poison_qsample_corr: null corr table");
+    if (int st = poison_qsample_check("bd_poison_qsample_corr", d, d->corr)) return st;
+    hipLaunchKernelGGL(poison_qsample_corr_kernel, dim3(nblocks((int64_t)d->B * d->H * d->W)), dim3(TPB), 0, S(stream), *d);
+    BD_LAUNCH_CHECK("poison_qsample_corr");
+    return BD_OK;
+}
 extern "C" int bd_qsample(const bd_qsample_desc* d, bd_stream_t stream) {
     BD_CHECK(d, BD_ERR_INVALID, "bd_qsample: null descriptor");
-    BD_CHECK(d->B > 0 && d->C > 0 && d->H > 0 && d->W > 0, BD_ERR_INVALID, "bd_qsample: bad shape");
-    BD_CHECK(d->x0 && d->R && d->noise && d->timesteps && d->alphas && d->alphas_cumprod && d->x_noisy && d->target,
-             BD_ERR_INVALID, "bd_qsample: null pointer");
-    BD_CHECK(d->ld_noisy >= d->C && d->ld_target >= d->C, BD_ERR_INVALID, "bd_qsample: ld < C");
+    if (int st = qsample_check("bd_qsample", d, d->alphas)) return st;
     hipLaunchKernelGGL(qsample_kernel, dim3(nblocks((int64_t)d->B * d->H * d->W)), dim3(TPB), 0, S(stream), *d);
     BD_LAUNCH_CHECK("qsample");
+    return BD_OK;
+}
+extern "C" int bd_qsample_corr(const bd_qsample_corr_desc* d, bd_stream_t stream) {
+    BD_CHECK(d, BD_ERR_INVALID, "bd_qsample_corr: null descriptor");
+    BD_CHECK(d->corr, BD_ERR_INVALID, "bd_qsample_corr: null corr table");
+    if (int st = qsample_check("bd_qsample_corr", d, d->corr)) return st;
+    hipLaunchKernelGGL(qsample_corr_kernel, dim3(nblocks((int64_t)d->B * d->H * d->W)), dim3(TPB), 0, S(stream), *d);
+    BD_LAUNCH_CHECK("qsample_corr");
     return BD_OK;
 }
 extern "C" int bd_nchw_to_nhwc(const float* src, float* dst, int B, int C, int H, int W, int64_t ld, bd_stream_t stream) {

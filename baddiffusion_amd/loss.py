@@ -16,14 +16,15 @@ def _tables(noise_sched, device):
             noise_sched.alphas_cumprod.to(device=device, dtype=torch.float32))
 
 
-def q_sample_diffuser(noise_sched, x_start, R, timesteps, noise=None):
-    """loss.py:257-285 -> (x_noisy, target), logical [B,C,H,W] (NHWC storage, i.e. channels_last views)."""
+def q_sample_diffuser(noise_sched, x_start, R, timesteps, noise=None, R_coef=None):
+    """loss.py:257-285 -> (x_noisy, target), logical [B,C,H,W] (NHWC storage, i.e. channels_last views).
+    R_coef: None, or a float32 device table [T] (correction.make_table): target = R_coef[t] R + eps in place of the reference's rho_t."""
     if noise is None:
         noise = torch.randn_like(x_start)
     if not x_start.is_cuda:
         raise RuntimeError("q_sample_diffuser runs on the GPU only (libbd_hip.so); no CPU fallback on the hot path")
     a, ac = _tables(noise_sched, x_start.device)
-    xn, tg = ops.qsample(x_start, R.to(x_start.device), noise.to(x_start.device), timesteps.to(x_start.device), a, ac)
+    xn, tg = ops.qsample(x_start, R.to(x_start.device), noise.to(x_start.device), timesteps.to(x_start.device), a, ac, corr=R_coef)
     return xn.permute(0, 3, 1, 2), tg.permute(0, 3, 1, 2)
 
 
@@ -43,14 +44,14 @@ class _LossFn(torch.autograd.Function):
         return (dpred * g).reshape(ctx.shape), None, None
 
 
-def p_losses_diffuser(noise_sched, model, x_start, R, timesteps, noise=None, loss_type="l2"):
-    """loss.py:287-307."""
+def p_losses_diffuser(noise_sched, model, x_start, R, timesteps, noise=None, loss_type="l2", R_coef=None):
+    """loss.py:287-307.  R_coef: as in q_sample_diffuser."""
     if len(x_start) == 0:
         return 0
     if loss_type not in ops.LOSS_TYPES:
         raise NotImplementedError()
     if noise is None:
         noise = torch.randn_like(x_start)
-    x_noisy, target = q_sample_diffuser(noise_sched=noise_sched, x_start=x_start, R=R, timesteps=timesteps, noise=noise)
+    x_noisy, target = q_sample_diffuser(noise_sched=noise_sched, x_start=x_start, R=R, timesteps=timesteps, noise=noise, R_coef=R_coef)
     predicted_noise = model(x_noisy, timesteps.contiguous(), return_dict=False)[0]
     return _LossFn.apply(predicted_noise.permute(0, 2, 3, 1), target.permute(0, 2, 3, 1), loss_type)

@@ -37,11 +37,13 @@ def _ld(t):
 
 # ------------------------------------------------------------------------------------------------ a-1/a-2
 def poison_qsample(images, is_poison, trigger, target_img, noise, timesteps, alphas, alphas_cumprod,
-                   vmin=-1.0, want_batch=False, want_mask=False, want_image=False, row_index=None, flip=None):
+                   vmin=-1.0, want_batch=False, want_mask=False, want_image=False, row_index=None, flip=None, corr=None):
     """Fused blend + q_sample.  images: float [B,C,H,W] (normalised) or uint8 [B,H,W,C].
     row_index (int64 [B]): batch row b reads images[row_index[b]] (images is then the whole resident array);
     flip (bool/uint8 [B]): mirror that image along W.  Both optional: the shuffled gather and
     RandomHorizontalFlip of the reference's DataLoader, fused into the kernel.
+    corr (float32 [T], device): target = corr[t] R + eps (bd_poison_qsample_corr; correction.make_table) in place of the in-kernel
+    rho_t; None is bd_poison_qsample.
     Returns (x_noisy NHWC [B,H,W,C], target NHWC [B,H,W,C][, R NCHW, x0 NCHW][, mask int64 [C,H,W]])."""
     lib = L.load()
     _need_cuda(images, is_poison, trigger, target_img, noise, timesteps, alphas, alphas_cumprod, row_index, flip)
@@ -66,14 +68,20 @@ def poison_qsample(images, is_poison, trigger, target_img, noise, timesteps, alp
     x0 = torch.empty(B, Cc, H, W, device=dev) if want_batch else None
     mask = torch.empty(Cc, H, W, dtype=torch.int64, device=dev) if want_mask else None
     image = torch.empty(B, Cc, H, W, device=dev) if want_image else None
-    d = L.PoisonQsampleDesc(B=B, C=Cc, H=H, W=W, images_f32=None if u8 else L.ptr(images),
-                            images_u8=L.ptr(images) if u8 else None, is_poison=L.ptr(is_poison),
-                            trigger=L.ptr(trigger), target_img=L.ptr(target_img), noise=L.ptr(noise),
-                            timesteps=L.ptr(timesteps), alphas=L.ptr(alphas), alphas_cumprod=L.ptr(alphas_cumprod),
-                            vmin=vmin, x_noisy=L.ptr(xn), ld_noisy=Cc, target=L.ptr(tg), ld_target=Cc,
-                            R_out=L.ptr(R), x0_out=L.ptr(x0), mask_out=L.ptr(mask), image_out=L.ptr(image),
-                            row_index=L.ptr(row_index), flip=L.ptr(flip))
-    L.check(lib.bd_poison_qsample(C.byref(d), L.stream()), "bd_poison_qsample")
+    kw = dict(B=B, C=Cc, H=H, W=W, images_f32=None if u8 else L.ptr(images),
+              images_u8=L.ptr(images) if u8 else None, is_poison=L.ptr(is_poison),
+              trigger=L.ptr(trigger), target_img=L.ptr(target_img), noise=L.ptr(noise),
+              timesteps=L.ptr(timesteps), alphas=L.ptr(alphas), alphas_cumprod=L.ptr(alphas_cumprod),
+              vmin=vmin, x_noisy=L.ptr(xn), ld_noisy=Cc, target=L.ptr(tg), ld_target=Cc,
+              R_out=L.ptr(R), x0_out=L.ptr(x0), mask_out=L.ptr(mask), image_out=L.ptr(image),
+              row_index=L.ptr(row_index), flip=L.ptr(flip))
+    if corr is None:
+        d = L.PoisonQsampleDesc(**kw)
+        L.check(lib.bd_poison_qsample(C.byref(d), L.stream()), "bd_poison_qsample")
+    else:
+        corr = _corr_table(corr, alphas_cumprod)
+        d = L.PoisonQsampleCorrDesc(corr=L.ptr(corr), **kw)
+        L.check(lib.bd_poison_qsample_corr(C.byref(d), L.stream()), "bd_poison_qsample_corr")
     out = [xn, tg]
     if want_batch:
         out += [R, x0]
@@ -84,18 +92,32 @@ def poison_qsample(images, is_poison, trigger, target_img, noise, timesteps, alp
     return tuple(out)
 
 
-def qsample(x0, R, noise, timesteps, alphas, alphas_cumprod):
-    """loss.py:257-285 on NCHW inputs -> (x_noisy, target) NHWC [B,H,W,C]."""
+def _corr_table(corr, alphas_cumprod):
+    """the target-coefficient table of the *_corr entry points: float32, contiguous, on the GPU, one entry per timestep"""
+    _need_cuda(corr)
+    if corr.dtype != torch.float32 or corr.dim() != 1 or corr.numel() != alphas_cumprod.numel():
+        raise ValueError(f"corr must be a float32 [T = {alphas_cumprod.numel()}] table, got {corr.dtype} {tuple(corr.shape)}")
+    return corr.contiguous()
+
+
+def qsample(x0, R, noise, timesteps, alphas, alphas_cumprod, corr=None):
+    """loss.py:257-285 on NCHW inputs -> (x_noisy, target) NHWC [B,H,W,C].  corr: as in poison_qsample (bd_qsample_corr)."""
     lib = L.load()
     _need_cuda(x0, R, noise, timesteps, alphas, alphas_cumprod)
     B, Cc, H, W = x0.shape
     x0 = x0.contiguous().float(); R = R.contiguous().float(); noise = noise.contiguous().float()
     timesteps = timesteps.to(torch.int64).contiguous()
     xn = torch.empty(B, H, W, Cc, device=x0.device); tg = torch.empty(B, H, W, Cc, device=x0.device)
-    d = L.QsampleDesc(B=B, C=Cc, H=H, W=W, x0=L.ptr(x0), R=L.ptr(R), noise=L.ptr(noise), timesteps=L.ptr(timesteps),
-                      alphas=L.ptr(alphas), alphas_cumprod=L.ptr(alphas_cumprod), x_noisy=L.ptr(xn), ld_noisy=Cc,
-                      target=L.ptr(tg), ld_target=Cc)
-    L.check(lib.bd_qsample(C.byref(d), L.stream()), "bd_qsample")
+    kw = dict(B=B, C=Cc, H=H, W=W, x0=L.ptr(x0), R=L.ptr(R), noise=L.ptr(noise), timesteps=L.ptr(timesteps),
+              alphas=L.ptr(alphas), alphas_cumprod=L.ptr(alphas_cumprod), x_noisy=L.ptr(xn), ld_noisy=Cc,
+              target=L.ptr(tg), ld_target=Cc)
+    if corr is None:
+        d = L.QsampleDesc(**kw)
+        L.check(lib.bd_qsample(C.byref(d), L.stream()), "bd_qsample")
+    else:
+        corr = _corr_table(corr, alphas_cumprod)
+        d = L.QsampleCorrDesc(corr=L.ptr(corr), **kw)
+        L.check(lib.bd_qsample_corr(C.byref(d), L.stream()), "bd_qsample_corr")
     return xn, tg
 
 

@@ -159,7 +159,11 @@ def plan_segment_ranges(model):
 class TrainEngine:
     def __init__(self, model, noise_sched, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0,
                  lr_warmup_steps=500, num_training_steps=None, loss_type="l2", process_group=None,
-                 grad_accum_steps=1, use_graph=None, force_dp=None, dp_check=False, ema=None, track_split=False):
+                 grad_accum_steps=1, use_graph=None, force_dp=None, dp_check=False, ema=None, track_split=False,
+                 correction=None):
+        # correction: None, or a float32 device table [T] (correction.make_table): poisoned rows train against eps + correction[t] R
+        # (bd_poison_qsample_corr / bd_qsample_corr) in place of the reference's rho_t.  None is the step as it always was, launch for
+        # launch.  The table's storage is read by every step (and by the captured graph): it is this engine's own copy.
         # track_split: every forward_backward also leaves each row's own loss in self.row_losses (float [B], device; one bd_image_loss
         # launch behind the loss launch, nothing else changes: parameters, moments and the returned loss are bit-identical with and
         # without it), and train_step folds them into self.split_losses = (mean over the clean rows, mean over the poisoned rows), NaN
@@ -247,6 +251,12 @@ class TrainEngine:
         self.time_buckets = False
         self._bucket_events = []
         self.alphas, self.alphas_cumprod = noise_sched.device_tables(dev)
+        if correction is not None:
+            if correction.dim() != 1 or correction.numel() != self.alphas_cumprod.numel():
+                raise ValueError(f"TrainEngine: correction must be a [T = {self.alphas_cumprod.numel()}] table, "
+                                 f"got {tuple(correction.shape)}")
+            correction = correction.to(device=dev, dtype=torch.float32).clone()
+        self.correction = correction
         self.sync_state()
 
     def _open_rccl(self, dev):
@@ -477,7 +487,8 @@ class TrainEngine:
 
             def body():
                 xn, tg = ops.poison_qsample(st["images"], st["is_poison"], st["trigger"], st["target"], st["noise"], st["t"],
-                                            self.alphas, self.alphas_cumprod, row_index=st["rows"], flip=st["flip"])
+                                            self.alphas, self.alphas_cumprod, row_index=st["rows"], flip=st["flip"],
+                                            corr=self.correction)
                 loss = self.forward_backward(xn, tg, st["t"])
                 ops.sumsq(self.grads, out=self.sumsq)
                 b1, b2 = self.betas
@@ -538,7 +549,7 @@ class TrainEngine:
             return self._graph_step(images, is_poison.to(torch.uint8) if is_poison.dtype == torch.bool else is_poison, trigger,
                                     target_img, noise, timesteps.to(torch.int64), row_index, flip)
         xn, tg = ops.poison_qsample(images, is_poison, trigger, target_img, noise, timesteps, self.alphas,
-                                    self.alphas_cumprod, row_index=row_index, flip=flip)
+                                    self.alphas_cumprod, row_index=row_index, flip=flip, corr=self.correction)
         loss = self.step_from_noisy(xn, tg, timesteps)
         if self.track_split:
             pois = is_poison.to(torch.bool)
@@ -550,7 +561,7 @@ class TrainEngine:
 
     def train_step_batch(self, x_start, R, noise, timesteps):
         """The reference's calling convention (baddiffusion.py:593-607): collated x_start / R batches."""
-        xn, tg = ops.qsample(x_start, R, noise, timesteps, self.alphas, self.alphas_cumprod)
+        xn, tg = ops.qsample(x_start, R, noise, timesteps, self.alphas, self.alphas_cumprod, corr=self.correction)
         return self.step_from_noisy(xn, tg, timesteps)
 
     def step_from_noisy(self, xn, tg, timesteps, groups=None):

@@ -7,6 +7,7 @@
                              [--clean_target frozen|noise] [--dataset CIFAR10] [--dataset_path datasets]
                              [--target NAME] [--trigger BOX_14] [--asr_threshold 1e-3] [--dyn_threshold V [--dyn_threshold_ratio 0.995]]
                              [--bpd_images N [--bpd_t_stride K] [--bpd_backdoor]]
+                             [--correction ode|sde|ddim|ddpm [--correction_zeta Z] [--correction_steps N --correction_eta E]]
 
 The sibling of anp_defense.py.  Stages (baddiffusion_amd/inversion.py, baddiffusion_amd/defense.py):
   1. invert_trigger: the shift tau the frozen network follows;
@@ -29,6 +30,9 @@ triggered by --trigger (likelihood.bits_per_dim(backdoor=...), the same N rows a
 removal on the same noise, printed and written as score.json["bpd"]["backdoor_before" / "backdoor_after"].  One expects a removal to RAISE
 it -- the repaired model should charge more bits for the target when the trigger is present -- but nothing here has measured that: no
 really backdoored checkpoint has been scored with it yet.
+--correction KIND names the correction table the checkpoint was trained with (baddiffusion.py --correction, baddiffusion_amd/correction.py): the
+inversion models mean eps_hat = c_T-1 * tau, so --lam then defaults to that table's entry at the last timestep (0.99998 for ode; the
+reference's rho_T-1 is 0.5025, which the standing default 0.5 approximates).  An explicit --lam wins; without --correction nothing changes.
 Outputs in <output_dir>/<name>: config.json, score.json ({"before", "after", "detected", "removal"[, "drift"][, "bpd"]}), tau.pt and the repaired model in the
 diffusers layout (unet/, scheduler/), which DiffuserModelSched.get_trained loads.  `--ckpt` must be a local diffusers-layout directory.
 """
@@ -88,6 +92,21 @@ class Config:
 DEFAULT_ASR_THRESHOLD = 1e-3    # of the order the papers use; a choice, not a finding
 
 
+def correction_lam(args):
+    """--lam under --correction: the table's entry at the last timestep, on the tables of the checkpoint's own scheduler (a checkpoint
+    named by its hub id has no scheduler folder to read here: the google/ddpm-* checkpoints this project knows all carry DDPMScheduler's
+    default tables, which stand in)"""
+    from baddiffusion_amd import correction
+    from baddiffusion_amd.model import load_scheduler
+    from baddiffusion_amd.schedulers import DDPMScheduler
+    d = os.path.join(str(args.ckpt), "scheduler")
+    sched = load_scheduler(d) if os.path.isdir(d) else DDPMScheduler()
+    if args.correction == "ddpm":
+        return float(correction.reference_rho(sched.alphas, sched.alphas_cumprod)[-1])
+    return float(correction.table_values(args.correction, sched, zeta=args.correction_zeta, steps=args.correction_steps,
+                                         eta=args.correction_eta)[-1])
+
+
 def naming_fn(config):
     add_on = f"_{config.tag}" if config.tag is not None else ""
     return (f"res_elijah_inv{config.inv_steps}_lam{config.lam}_rm{config.remove_steps}_lr{config.learning_rate}{add_on}_"
@@ -102,7 +121,9 @@ def get_config(argv=None):
     p.add_argument("--inv_steps", type=int, default=config.inv_steps)
     p.add_argument("--inv_batch", type=int, default=config.inv_batch)
     p.add_argument("--inv_lr", type=float, default=config.inv_lr)
-    p.add_argument("--lam", type=float, default=config.lam)
+    p.add_argument("--lam", type=float,
+                   help=f"the inversion models mean eps_hat = lam * tau at the last timestep ({config.lam}: the reference's rho_T-1 = 0.5025, "
+                        "rounded; with --correction: that table's entry at the last timestep)")
     p.add_argument("--detect_n", type=int, default=config.detect_n)
     p.add_argument("--sched", "-sc", type=str, default=config.sched, choices=SCHED_CHOICES,
                    help="sampling pipeline of the score passes; the DPM_SOLVER_* names run DPMSolverMultistepScheduler (always the native solver here), "
@@ -138,7 +159,18 @@ def get_config(argv=None):
     p.add_argument("--bpd_backdoor", action="store_true",
                    help="with --bpd_images and --target: bits per dimension of the target along the chain triggered by --trigger, before -> "
                         "after the removal (one expects it to rise; not measured on a really backdoored checkpoint yet)")
+    p.add_argument("--correction", type=str, choices=["ode", "sde", "ddim", "ddpm"],
+                   help="the correction table the checkpoint was trained with (baddiffusion.py --correction): --lam then defaults to its "
+                        "entry at the last timestep, c_T-1 (0.99998 for ode), since a model trained against eps + c_t R answers a shifted "
+                        "input with mean eps_hat = c_T-1 * tau.  An explicit --lam wins")
+    p.add_argument("--correction_zeta", type=float, help="zeta of --correction sde")
+    p.add_argument("--correction_steps", type=int, help="steps of --correction ddim")
+    p.add_argument("--correction_eta", type=float, help="eta of --correction ddim (0)")
     args = p.parse_args(argv)
+    if args.correction is None and any(v is not None for v in (args.correction_zeta, args.correction_steps, args.correction_eta)):
+        p.error("--correction_zeta / --correction_steps / --correction_eta need --correction")
+    if args.correction is not None and args.lam is None:
+        args.lam = correction_lam(args)
     if args.bpd_t_stride is not None and args.bpd_images is None:
         p.error("--bpd_t_stride needs --bpd_images")
     if args.bpd_backdoor and (args.bpd_images is None or args.target is None):

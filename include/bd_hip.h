@@ -80,6 +80,49 @@ typedef struct {
 } bd_qsample_desc;
 int bd_qsample(const bd_qsample_desc* d, bd_stream_t stream);
 
+/* The same two kernels with the target's coefficient read from a table: target = corr[t] R + eps, x_noisy as above (its shift
+ * (1 - sqrt(ac_t)) R belongs to the forward chain and does not depend on the sampler).  rho_t above is the coefficient for which the
+ * DDPM ancestral step maps the shifted chain onto itself; a deterministic sampler needs another one (DESIGN.md section 3,
+ * "Sampler-matched correction terms"; baddiffusion_amd/correction.py builds the tables).  The descriptors are the ones above, field for
+ * field, plus
+ *     corr   fp32 [T], device, indexed by timesteps[b] like alphas_cumprod.
+ * `alphas` is not read and may be NULL.  The kernel bodies are shared with bd_poison_qsample / bd_qsample: every output but `target` is
+ * theirs bit for bit, and with corr[t] = their rho_t so is `target`; a clean row's target is eps itself.  Status: as above, and
+ * BD_ERR_INVALID for a null corr (checked on the host, before any launch). */
+typedef struct {
+    int B, C, H, W;
+    const float* images_f32;
+    const uint8_t* images_u8;
+    const uint8_t* is_poison;
+    const float* trigger;
+    const float* target_img;
+    const float* noise;
+    const int64_t* timesteps;
+    const float* alphas;          /* not read, may be NULL */
+    const float* alphas_cumprod;
+    float vmin;
+    float* x_noisy; int64_t ld_noisy;
+    float* target;  int64_t ld_target;
+    float* R_out;
+    float* x0_out;
+    int64_t* mask_out;
+    float* image_out;
+    const int64_t* row_index;
+    const uint8_t* flip;
+    const float* corr;            /* [T] coefficient of R in the target */
+} bd_poison_qsample_corr_desc;
+int bd_poison_qsample_corr(const bd_poison_qsample_corr_desc* d, bd_stream_t stream);
+
+typedef struct {
+    int B, C, H, W;
+    const float* x0; const float* R; const float* noise;   /* NCHW */
+    const int64_t* timesteps; const float* alphas; const float* alphas_cumprod;   /* alphas: not read, may be NULL */
+    float* x_noisy; int64_t ld_noisy;   /* NHWC */
+    float* target;  int64_t ld_target;  /* NHWC */
+    const float* corr;                  /* [T] coefficient of R in the target */
+} bd_qsample_corr_desc;
+int bd_qsample_corr(const bd_qsample_corr_desc* d, bd_stream_t stream);
+
 /* NCHW <-> NHWC(ld) conversion for the 3-channel boundary tensors. */
 int bd_nchw_to_nhwc(const float* src, float* dst, int B, int C, int H, int W, int64_t ld, bd_stream_t stream);
 int bd_nhwc_to_nchw(const float* src, int64_t ld, float* dst, int B, int C, int H, int W, bd_stream_t stream);
