@@ -1227,6 +1227,11 @@ int conv3x3_ps(const bd_conv3x3_ps_desc& d, hipStream_t st) {
              "conv3x3_ps: split planes need ld %% 32 == 0 and 128-byte aligned bases");
     BD_CHECK(d.direction == 1 || d.direction == -1, BD_ERR_INVALID, "conv3x3_ps: direction must be +1 or -1");
     BD_CHECK(sp_mode_valid(d.mode), BD_ERR_INVALID, "conv3x3_ps: unknown compute mode %d", d.mode);
+    // a row of a buffer holds at least the channels the kernels read or write in it (the contract of bd_split_rows and the loss launchers)
+    BD_CHECK(d.ldx >= d.K && d.ldy >= d.N, BD_ERR_INVALID, "conv3x3_ps: ldx=%lld < K=%d or ldy=%lld < N=%d", (long long)d.ldx, d.K,
+             (long long)d.ldy, d.N);
+    BD_CHECK(!d.residual || d.ldr >= d.N, BD_ERR_INVALID, "conv3x3_ps: ldr=%lld < N=%d", (long long)d.ldr, d.N);
+    BD_CHECK(!d.rowbias || d.ld_rowbias >= d.N, BD_ERR_INVALID, "conv3x3_ps: ld_rowbias=%lld < N=%d", (long long)d.ld_rowbias, d.N);
     const bool sp = d.mode == BD_MODE_BF16;   // single pass: hi*hi only
     // the epilogues and the split-K second pass move float4: every fp32 operand needs 16-byte rows
     BD_CHECK(d.ldy % 4 == 0 && ((uintptr_t)d.y & 15) == 0, BD_ERR_UNSUPPORTED, "conv3x3_ps: y needs ldy %% 4 == 0 and a 16-byte aligned base");
@@ -1366,6 +1371,8 @@ int conv3x3_ps_wgrad(const bd_conv3x3_ps_wgrad_desc& d, hipStream_t st) {
     BD_CHECK(d.ldx % 32 == 0 && d.lddy % 32 == 0 && ((uintptr_t)d.x_split & 127) == 0 && ((uintptr_t)d.dy_split & 127) == 0,
              BD_ERR_UNSUPPORTED, "conv3x3_ps_wgrad: split planes need ld %% 32 == 0 and 128-byte aligned bases");
     BD_CHECK(sp_mode_valid(d.mode), BD_ERR_INVALID, "conv3x3_ps_wgrad: unknown compute mode %d", d.mode);
+    BD_CHECK(d.ldx >= d.Cin && d.lddy >= d.Cout, BD_ERR_INVALID, "conv3x3_ps_wgrad: ldx=%lld < Cin=%d or lddy=%lld < Cout=%d", (long long)d.ldx,
+             d.Cin, (long long)d.lddy, d.Cout);
     const bool sp = d.mode == BD_MODE_BF16;
     PsWgParams p = {};
     p.dy = reinterpret_cast<const char*>(d.dy_split); p.x = reinterpret_cast<const char*>(d.x_split);

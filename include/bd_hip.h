@@ -739,6 +739,8 @@ typedef struct {
     int mode;                       /* bd_compute_mode of the products: BD_MODE_BF16X3 (or 0, the zero-initialised default: these
                                        kernels have no f32 form) = hi*hi + hi*lo + lo*hi, BD_MODE_BF16 = hi*hi; other values BD_ERR_INVALID */
 } bd_conv3x3_ps_desc;
+/* BD_ERR_INVALID before any launch: a leading dimension below the channel count of its buffer -- ldx < K, ldy < N, ldr < N (residual given),
+ * ld_rowbias < N (rowbias given); bd_conv3x3_ps_wgrad: ldx < Cin, lddy < Cout. */
 size_t bd_conv3x3_ps_workspace_bytes(const bd_conv3x3_ps_desc* d);
 int bd_conv3x3_ps_gn_splits(int B, int H, int W, int K, int N, int groups);   /* 0: this call cannot write GroupNorm partials */
 int bd_conv3x3_ps(const bd_conv3x3_ps_desc* d, bd_stream_t stream);

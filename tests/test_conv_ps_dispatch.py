@@ -210,17 +210,24 @@ def bracketed(fn):
     return res, counts
 
 
-def describe(got, ref):
-    """where a result differs from the reference: the pattern names the rows, columns (taps / K slices show as value patterns) at fault"""
+def describe(got, ref, grid=None):
+    """where a result differs from the reference: the pattern names the rows, columns (taps / K slices show as value patterns) at fault.
+    grid = (H, W) of the image the rows are pixels of: also the (b, y, x) of the first wrong rows and the x columns that hold one, so that an
+    error at a strip seam or on a strip's first row reads as such"""
     got = got.double().cpu().reshape(-1, got.shape[-1]); ref = ref.reshape(-1, ref.shape[-1])
     bad = ~(got == ref)
     if not bool(bad.any()):
         return "equal"
     rows = bad.any(dim=1).nonzero().flatten(); cols = bad.any(dim=0).nonzero().flatten()
     d = (got - ref)[bad]
+    where = ""
+    if grid is not None:
+        H, W = grid
+        bxy = [(r // (H * W), r // W % H, r % W) for r in rows[:8].tolist()]
+        where = f"; (b, y, x) of the first rows {bxy}; x of all wrong rows {sorted(set((rows % W).tolist()))[:16]}, y {sorted(set((rows // W % H).tolist()))[:16]}"
     return (f"{int(bad.sum())} of {bad.numel()} elements differ ({int(torch.isnan(got[bad]).sum())} NaN); rows {int(rows[0])}..{int(rows[-1])} "
             f"({rows.numel()} rows, first {rows[:8].tolist()}), columns {int(cols[0])}..{int(cols[-1])} ({cols.numel()}); "
-            f"max |diff| {float(d.abs().nan_to_num().max()):.6g}")
+            f"max |diff| {float(d.abs().nan_to_num().max()):.6g}{where}")
 
 
 @gpu
