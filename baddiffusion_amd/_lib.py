@@ -199,6 +199,23 @@ class ConvPsWgradDesc(C.Structure):
                 ("mode", i32)]
 
 
+PS_256, PS_256_SHARED_TAP, PS_128 = 0, 1, 2                    # enum bd_ps_kernel
+PS_WGRAD, PS_WGRAD_SHARED_TAP, PS_WGRAD_PHASE = 0, 1, 2        # enum bd_ps_wgrad_kernel
+
+
+class ConvPsPlanInfo(C.Structure):
+    """bd_conv3x3_ps_plan_info; kernel is enum bd_ps_kernel, prof_class a C string"""
+    _fields_ = [("kernel", i32), ("tiles_m", i32), ("tiles_n", i32), ("ksplit", i32), ("chunks_per_split", i32), ("stages", i32),
+                ("reduce", i32), ("grid", i32), ("gn_splits", i32), ("workspace_bytes", sz), ("prof_class", C.c_char_p)]
+
+
+class ConvPsWgradPlanInfo(C.Structure):
+    """bd_conv3x3_ps_wgrad_plan_info; kernel is enum bd_ps_wgrad_kernel, prof_class a C string"""
+    _fields_ = [("kernel", i32), ("ntaps", i32), ("tiles_m", i32), ("tiles_n", i32), ("slots", i32), ("ksplit", i32),
+                ("chunks_per_split", i32), ("reduce", i32), ("grid", i32), ("bias_rows", i32), ("slab_floats", sz),
+                ("workspace_bytes", sz), ("de_offset", sz), ("prof_class", C.c_char_p)]
+
+
 class UpsampleConvDesc(C.Structure):
     _fields_ = [("B", i32), ("H", i32), ("W", i32), ("Cin", i32), ("Cout", i32), ("x_split", vp), ("ldx", i64), ("dy_split", vp),
                 ("lddy", i64), ("e_split", vp), ("et_split", vp), ("bias", vp), ("y", vp), ("ldy", i64), ("dx", vp), ("lddx", i64),
@@ -336,12 +353,15 @@ SIGNATURES = {
     "bd_conv3x3_ps": (i32, [C.POINTER(ConvPsDesc), vp]),
     "bd_conv3x3_ps_workspace_bytes": (sz, [C.POINTER(ConvPsDesc)]),
     "bd_conv3x3_ps_gn_splits": (i32, [i32, i32, i32, i32, i32, i32]),
+    "bd_conv3x3_ps_plan": (i32, [C.POINTER(ConvPsDesc), C.POINTER(ConvPsPlanInfo)]),
     "bd_upsample_weights": (i32, [vp, i32, i32, vp, vp, vp]),
     "bd_upsample_conv_fwd": (i32, [C.POINTER(UpsampleConvDesc), vp]),
     "bd_upsample_conv_dgrad": (i32, [C.POINTER(UpsampleConvDesc), vp]),
     "bd_upsample_conv_wgrad": (i32, [C.POINTER(UpsampleConvDesc), vp]),
     "bd_upsample_conv_wgrad_workspace_bytes": (sz, [C.POINTER(UpsampleConvDesc)]),
     "bd_upsample_conv_dgrad_workspace_bytes": (sz, [C.POINTER(UpsampleConvDesc)]),
+    "bd_upsample_conv_wgrad_plan": (i32, [C.POINTER(UpsampleConvDesc), C.POINTER(ConvPsWgradPlanInfo)]),
+    "bd_upsample_conv_dgrad_tap_groups": (i32, [C.POINTER(UpsampleConvDesc)]),
     "bd_conv3x3_s2_dgrad_ps": (i32, [C.POINTER(ConvS2DgradDesc), vp]),
     "bd_gemm_sp_workspace_bytes": (sz, [C.POINTER(GemmSpDesc)]),
     "bd_gemm_sp": (i32, [C.POINTER(GemmSpDesc), vp]),
@@ -350,6 +370,7 @@ SIGNATURES = {
     "bd_attn_sp_bwd": (i32, [C.POINTER(AttnSpDesc), vp]),
     "bd_conv3x3_ps_wgrad": (i32, [C.POINTER(ConvPsWgradDesc), vp]),
     "bd_conv3x3_ps_wgrad_workspace_bytes": (sz, [C.POINTER(ConvPsWgradDesc)]),
+    "bd_conv3x3_ps_wgrad_plan": (i32, [C.POINTER(ConvPsWgradDesc), C.POINTER(ConvPsWgradPlanInfo)]),
     "bd_conv3x3_fwd": (i32, [C.POINTER(ConvFwdDesc), vp]),
     "bd_conv3x3_dgrad": (i32, [C.POINTER(ConvDgradDesc), vp]),
     "bd_conv3x3_wgrad": (i32, [C.POINTER(ConvWgradDesc), vp]),

@@ -211,6 +211,7 @@ int upsample_weights(const float* w, int Cin, int Cout, uint16_t* e_split, uint1
 int upsample_conv_fwd(const bd_upsample_conv_desc& d, hipStream_t st);
 int upsample_conv_dgrad(const bd_upsample_conv_desc& d, hipStream_t st);
 size_t upsample_conv_dgrad_workspace_bytes(const bd_upsample_conv_desc& d);
+int upsample_conv_dgrad_tap_groups(int B, int H, int W, int Cin);                   // 4 or 1: the launcher's rule, also the network plan's path choice
 bool upsample_conv_ps_supported(int B, int H, int W, int Cin, int Cout);
 int conv3x3_s2_dgrad_ps(const bd_conv3x3_s2_dgrad_desc& d, hipStream_t st);
 int ups_dweff_combine(const float* de, int Cin, int Cout, float* dw, hipStream_t st);

@@ -317,13 +317,13 @@ static int ph_launch(PhParams& p, bool sp, hipStream_t st, const char* what) {
     }
     return BD_OK;
 }
-// tiles of a one-class launch on this device's CUs: below half a wave of workgroups the 16 taps are dealt to 4 groups
-static int ph_tap_groups(long long M, int N) {
-    return cdiv(M, PH_BM) * (N / PH_BN) * 2 <= device_cus() ? 4 : 1;
+// tiles of the upsample data gradient's one-class launch on this device's CUs: below half a wave of workgroups the 16 taps are dealt to 4
+// groups.  The launcher, its workspace size, the network plan's path choice (unet_plan.cpp) and bd_upsample_conv_dgrad_tap_groups read this.
+int upsample_conv_dgrad_tap_groups(int B, int H, int W, int Cin) {
+    return cdiv((long long)B * H * W, PH_BM) * (Cin / PH_BN) * 2 <= device_cus() ? 4 : 1;
 }
 size_t upsample_conv_dgrad_workspace_bytes(const bd_upsample_conv_desc& d) {
-    const long long M = (long long)d.B * d.H * d.W;
-    return ph_tap_groups(M, d.Cin) > 1 ? (size_t)4 * M * d.Cin * sizeof(float) : 0;
+    return upsample_conv_dgrad_tap_groups(d.B, d.H, d.W, d.Cin) > 1 ? (size_t)4 * d.B * d.H * d.W * d.Cin * sizeof(float) : 0;
 }
 
 static int ph_common(PhParams& p, int B, int H, int W, int C, int N, const void* a, long long lda, const void* w, float* y, long long ldy,
@@ -379,7 +379,7 @@ int upsample_conv_dgrad(const bd_upsample_conv_desc& d, hipStream_t st) {
     PhClass& k = p.cls[0];
     k.p = k.q = 0; k.ntaps = 16;
     for (int t = 0; t < 16; ++t) { k.oy[t] = t / 4 - 1; k.ox[t] = t % 4 - 1; k.wt[t] = t; }
-    if (ph_tap_groups(p.M, p.N) > 1) {     // few tiles: four workgroups per tile, four taps each, + a fixed-order fold
+    if (upsample_conv_dgrad_tap_groups(d.B, d.H, d.W, d.Cin) > 1) {     // few tiles: four workgroups per tile, four taps each, + a fixed-order fold
         const size_t need = upsample_conv_dgrad_workspace_bytes(d);
         BD_CHECK(d.workspace && d.workspace_bytes >= need, BD_ERR_WORKSPACE, "bd_upsample_conv_dgrad: workspace %zu < %zu", d.workspace_bytes, need);
         p.tsplit = 4; p.partial = reinterpret_cast<float*>(d.workspace);
@@ -434,6 +434,9 @@ extern "C" int bd_upsample_conv_fwd(const bd_upsample_conv_desc* d, bd_stream_t 
 }
 extern "C" size_t bd_upsample_conv_dgrad_workspace_bytes(const bd_upsample_conv_desc* d) {
     return d ? bd::upsample_conv_dgrad_workspace_bytes(*d) : 0;
+}
+extern "C" int bd_upsample_conv_dgrad_tap_groups(const bd_upsample_conv_desc* d) {
+    return d ? bd::upsample_conv_dgrad_tap_groups(d->B, d->H, d->W, d->Cin) : 0;
 }
 extern "C" int bd_upsample_conv_dgrad(const bd_upsample_conv_desc* d, bd_stream_t s) {
     BD_CHECK(d, BD_ERR_INVALID, "bd_upsample_conv_dgrad: null descriptor");

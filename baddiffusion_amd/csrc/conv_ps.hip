@@ -1181,49 +1181,67 @@ int split_wt_batched(const float* params, uint16_t* out, const long long* off, c
 // shapes the LDS-DMA convolution handles: power-of-two images, whole 32-channel blocks, 128-wide output tiles.
 // Large layers (>= 96 tiles of 256 x 128) run the three-stage 256 x 128 kernel, one workgroup per CU and no K split;
 // small ones (8x8 / 4x4 images at CIFAR batch sizes) the 128 x 128 split-K variant.
-bool conv3x3_ps_supported(int B, int H, int W, int K_channels, int N_channels) {
-    return B > 0 && ilog2_exact(H) >= 0 && ilog2_exact(W) >= 0 && K_channels % 32 == 0 && N_channels % PS_BN == 0 && K_channels >= 32;
-}
-static bool ps_large(long long M, int N) { return cdiv(M, PS_BM) * (N / PS_BN) >= 96; }
-// K split and slab bytes of one call: what bd_conv3x3_ps_workspace_bytes answers and what the launcher checks and hands the kernel.
-// Large layers (and shapes the launcher refuses) take no workspace.
-struct PsWs { int ksplit, cps; size_t bytes; };
-static PsWs ps_ws(const bd_conv3x3_ps_desc& d) {
-    PsWs s = {1, 0, 0};
-    const long long M = (long long)d.B * d.H * d.W;
-    if (d.N % PS_BN || ps_large(M, d.N)) return s;
-    const long long tiles = cdiv(M, 128) * (d.N / 128);
-    const int nchunks = 9 * (d.K / 32);
-    // one slot per CU (2 x CUs measured 0.1-0.2 ms/step slower: twice the slab traffic for the 4x4 / 8x8 layers), >= 4 chunks per split
-    split_k(device_cus(), tiles, nchunks, 4, s.ksplit, s.cps);
-    if (s.ksplit > 1) s.bytes = (size_t)s.ksplit * (size_t)M * d.N * sizeof(float);
-    return s;
-}
-size_t conv3x3_ps_workspace_bytes(const bd_conv3x3_ps_desc& d) { return ps_ws(d).bytes; }
+static bool ps_grid_ok(int B, int H, int W) { return B > 0 && ilog2_exact(H) >= 0 && ilog2_exact(W) >= 0; }
+static bool ps_channels_ok(int K, int N) { return K > 0 && K % 32 == 0 && N > 0 && N % PS_BN == 0; }
+bool conv3x3_ps_supported(int B, int H, int W, int K_channels, int N_channels) { return ps_grid_ok(B, H, W) && ps_channels_ok(K_channels, N_channels); }
+// the VIRTUAL image width of the vertical-tap sharing kernels: images wider than 32 pixels are walked strip by strip (ps_v2r)
+static int ps_vw(int W) { return W < 32 ? W : 32; }
+static int ps_epi(const bd_conv3x3_ps_desc& d) { return (d.residual ? 1 : 0) | (d.rowbias ? 2 : 0) | (d.accumulate ? 4 : 0); }
 
-// does this call run on conv_ps3_kernel (256 x 128 tiles, whole tiles only)?
-static bool ps_takes_v3(int B, int H, int W, int N) {
+// Everything bd_conv3x3_ps decides from a descriptor's numbers, decided once: the launcher, bd_conv3x3_ps_workspace_bytes,
+// bd_conv3x3_ps_gn_splits and bd_conv3x3_ps_plan read it.  Pure host arithmetic.  `ok` false, nothing else set: a shape ps_check refuses.
+struct PsPlan : bd_conv3x3_ps_plan_info { bool ok, large; long long M; };
+static PsPlan ps_plan(const bd_conv3x3_ps_desc& d) {
     static const bool v3_off = getenv("BD_PS_V3") && atoi(getenv("BD_PS_V3")) == 0;
     // round 4: any W >= 16 -- images wider than 32 pixels are walked strip by strip (virtual pixel order, ps_v2r)
     static const int v3_maxw = getenv("BD_PS_V3_MAXW") ? atoi(getenv("BD_PS_V3_MAXW")) : (1 << 30);     // (A/B knob: 32 = round 3's gate)
-    const long long M = (long long)B * H * W;
-    const int vw = W < 32 ? W : 32;
-    return ps_large(M, N) && !v3_off && W >= 16 && W <= v3_maxw && ((long long)H * vw) % PS_BM == 0 && M % PS_BM == 0;
+    static const char* kName[2][2][2] = {{{"conv_ps128_dgrad", "conv_ps_dgrad"}, {"conv_ps128_fwd", "conv_ps_fwd"}},
+                                         {{"conv_ps128_dgrad_bf16", "conv_ps_dgrad_bf16"}, {"conv_ps128_fwd_bf16", "conv_ps_fwd_bf16"}}};
+    PsPlan p = {};
+    if (!(p.ok = conv3x3_ps_supported(d.B, d.H, d.W, d.K, d.N))) return p;
+    p.M = (long long)d.B * d.H * d.W;
+    p.large = cdiv(p.M, PS_BM) * (d.N / PS_BN) >= 96;
+    const int nchunks = 9 * (d.K / 32);
+    p.tiles_m = (int)cdiv(p.M, p.large ? PS_BM : 128); p.tiles_n = d.N / PS_BN;
+    p.ksplit = 1; p.chunks_per_split = nchunks; p.stages = PS_STAGES;
+    p.prof_class = kName[d.mode == BD_MODE_BF16][d.direction > 0][p.large];
+    if (p.large) {
+        // vertical-tap sharing variant (conv_ps3_kernel): image rows of 16 or 32 pixels, whole images per tile row block, whole tiles only
+        const bool v3 = !v3_off && d.W >= 16 && d.W <= v3_maxw && ((long long)d.H * ps_vw(d.W)) % PS_BM == 0 && p.M % PS_BM == 0;
+        p.kernel = v3 ? BD_PS_256_SHARED_TAP : BD_PS_256;
+        // Round 4: pixel splits of the GroupNorm partials a forward call can write from its epilogue (0: it cannot).  One split per 256-pixel tile.
+        const int lc = d.gn_groups > 0 && d.N % d.gn_groups == 0 ? ilog2_exact(d.N / d.gn_groups) : -1;
+        if (v3 && lc >= 2 && lc <= 5 && (d.H * d.W) % PS_BM == 0) p.gn_splits = d.H * d.W / PS_BM;
+    } else {
+        p.kernel = BD_PS_128;
+        // one slot per CU (2 x CUs measured 0.1-0.2 ms/step slower: twice the slab traffic for the 4x4 / 8x8 layers), >= 4 chunks per split
+        split_k(device_cus(), (long long)p.tiles_m * p.tiles_n, nchunks, 4, p.ksplit, p.chunks_per_split);
+        // round 6: short K slices (the 4 x 4 level) take the four-stage form (three chunks in flight, one workgroup per CU).  9: the 4 x 4
+        // level only, -0.05 ms per step; two stages everywhere or the 8 x 8 level too measured slower (profiles/r06_ab_ps128_deep.txt)
+        constexpr int deep_maxcps = 9;
+        p.stages = p.ksplit > 1 && p.chunks_per_split <= deep_maxcps ? 4 : 2;
+        p.reduce = p.ksplit > 1;      // K-split slabs [ksplit][M][N]; conv_ps128_reduce folds them and applies the epilogue
+        if (p.reduce) p.workspace_bytes = (size_t)p.ksplit * (size_t)p.M * d.N * sizeof(float);
+    }
+    p.grid = p.tiles_m * p.tiles_n * p.ksplit;
+    return p;
 }
-// Round 4: pixel splits of the GroupNorm partials a forward call can write from its epilogue (0: it cannot).  One split per 256-pixel tile.
+size_t conv3x3_ps_workspace_bytes(const bd_conv3x3_ps_desc& d) { return ps_plan(d).workspace_bytes; }
 int conv3x3_ps_gn_splits(int B, int H, int W, int K, int N, int groups) {
-    if (B <= 0 || ilog2_exact(H) < 0 || ilog2_exact(W) < 0 || K <= 0 || K % 32 || N <= 0 || N % PS_BN || groups <= 0 || N % groups) return 0;
-    const int lc = ilog2_exact(N / groups);
-    if (lc < 2 || lc > 5 || (H * W) % PS_BM) return 0;
-    return ps_takes_v3(B, H, W, N) ? H * W / PS_BM : 0;
+    bd_conv3x3_ps_desc d = {};
+    d.B = B; d.H = H; d.W = W; d.K = K; d.N = N; d.direction = 1; d.gn_groups = groups;
+    return ps_plan(d).gn_splits;
 }
 
-int conv3x3_ps(const bd_conv3x3_ps_desc& d, hipStream_t st) {
-    BD_CHECK(d.x_split && d.w_split && d.y, BD_ERR_INVALID, "conv3x3_ps: null pointer");
-    BD_CHECK(d.B > 0 && ilog2_exact(d.H) >= 0 && ilog2_exact(d.W) >= 0, BD_ERR_UNSUPPORTED, "conv3x3_ps: H, W must be powers of two");
-    BD_CHECK(d.K > 0 && d.K % 32 == 0 && d.N > 0 && d.N % PS_BN == 0, BD_ERR_UNSUPPORTED,
-             "conv3x3_ps: K channels %% 32 and N channels %% %d must be 0 (got %d, %d)", PS_BN, d.K, d.N);
-    BD_CHECK(d.ldx % 32 == 0 && ((uintptr_t)d.x_split & 127) == 0 && ((uintptr_t)d.w_split & 127) == 0, BD_ERR_UNSUPPORTED,
+// Every host check of bd_conv3x3_ps, in the order the entry point has always reported them (the pointer checks sit between the checks of
+// the numbers, so one list keeps the order).  `launch` false -- bd_conv3x3_ps_plan -- skips the null-pointer, base-alignment and workspace
+// checks: the launcher's own.
+static int ps_check(const bd_conv3x3_ps_desc& d, const PsPlan& pl, bool launch) {
+    const auto al = [launch](const void* p, uintptr_t mask) { return !launch || ((uintptr_t)p & mask) == 0; };
+    BD_CHECK(!launch || (d.x_split && d.w_split && d.y), BD_ERR_INVALID, "conv3x3_ps: null pointer");
+    BD_CHECK(ps_grid_ok(d.B, d.H, d.W), BD_ERR_UNSUPPORTED, "conv3x3_ps: H, W must be powers of two");
+    BD_CHECK(ps_channels_ok(d.K, d.N), BD_ERR_UNSUPPORTED, "conv3x3_ps: K channels %% 32 and N channels %% %d must be 0 (got %d, %d)", PS_BN, d.K, d.N);
+    BD_CHECK(d.ldx % 32 == 0 && al(d.x_split, 127) && al(d.w_split, 127), BD_ERR_UNSUPPORTED,
              "conv3x3_ps: split planes need ld %% 32 == 0 and 128-byte aligned bases");
     BD_CHECK(d.direction == 1 || d.direction == -1, BD_ERR_INVALID, "conv3x3_ps: direction must be +1 or -1");
     BD_CHECK(sp_mode_valid(d.mode), BD_ERR_INVALID, "conv3x3_ps: unknown compute mode %d", d.mode);
@@ -1232,122 +1250,100 @@ int conv3x3_ps(const bd_conv3x3_ps_desc& d, hipStream_t st) {
              (long long)d.ldy, d.N);
     BD_CHECK(!d.residual || d.ldr >= d.N, BD_ERR_INVALID, "conv3x3_ps: ldr=%lld < N=%d", (long long)d.ldr, d.N);
     BD_CHECK(!d.rowbias || d.ld_rowbias >= d.N, BD_ERR_INVALID, "conv3x3_ps: ld_rowbias=%lld < N=%d", (long long)d.ld_rowbias, d.N);
-    const bool sp = d.mode == BD_MODE_BF16;   // single pass: hi*hi only
     // the epilogues and the split-K second pass move float4: every fp32 operand needs 16-byte rows
-    BD_CHECK(d.ldy % 4 == 0 && ((uintptr_t)d.y & 15) == 0, BD_ERR_UNSUPPORTED, "conv3x3_ps: y needs ldy %% 4 == 0 and a 16-byte aligned base");
-    BD_CHECK(!d.residual || (d.ldr % 4 == 0 && ((uintptr_t)d.residual & 15) == 0), BD_ERR_UNSUPPORTED,
+    BD_CHECK(d.ldy % 4 == 0 && al(d.y, 15), BD_ERR_UNSUPPORTED, "conv3x3_ps: y needs ldy %% 4 == 0 and a 16-byte aligned base");
+    BD_CHECK(!d.residual || (d.ldr % 4 == 0 && al(d.residual, 15)), BD_ERR_UNSUPPORTED,
              "conv3x3_ps: residual needs ldr %% 4 == 0 and a 16-byte aligned base");
-    BD_CHECK(!d.rowbias || (d.ld_rowbias % 4 == 0 && ((uintptr_t)d.rowbias & 15) == 0), BD_ERR_UNSUPPORTED,
+    BD_CHECK(!d.rowbias || (d.ld_rowbias % 4 == 0 && al(d.rowbias, 15)), BD_ERR_UNSUPPORTED,
              "conv3x3_ps: rowbias needs ld_rowbias %% 4 == 0 and a 16-byte aligned base");
-    BD_CHECK(!d.bias || ((uintptr_t)d.bias & 15) == 0, BD_ERR_UNSUPPORTED, "conv3x3_ps: bias needs a 16-byte aligned base");
-    const long long M = (long long)d.B * d.H * d.W;
-    BD_CHECK(M < (1ll << 31), BD_ERR_UNSUPPORTED, "conv3x3_ps: pixel count overflows int32");
+    BD_CHECK(!d.bias || al(d.bias, 15), BD_ERR_UNSUPPORTED, "conv3x3_ps: bias needs a 16-byte aligned base");
+    BD_CHECK(pl.M < (1ll << 31), BD_ERR_UNSUPPORTED, "conv3x3_ps: pixel count overflows int32");
     BD_CHECK((long long)(d.W + 1) * d.ldx * 4 < (1ll << 31), BD_ERR_UNSUPPORTED, "conv3x3_ps: row pitch too large");
-    PsParams p = {};
+    const int epi = ps_epi(d);
+    BD_CHECK(!d.gn_part || !pl.large || (d.direction == 1 && (epi == 1 || epi == 2) && pl.gn_splits > 0), BD_ERR_UNSUPPORTED,
+             "conv3x3_ps: gn_part needs a forward call with exactly one of rowbias / residual and bd_conv3x3_ps_gn_splits() > 0");
+    BD_CHECK(!d.gn_part || pl.large, BD_ERR_UNSUPPORTED, "conv3x3_ps: gn_part on a small layer (bd_conv3x3_ps_gn_splits() == 0)");
+    BD_CHECK(!launch || !pl.reduce || (d.workspace && d.workspace_bytes >= pl.workspace_bytes), BD_ERR_WORKSPACE,
+             "conv3x3_ps: split-K needs %zu workspace bytes, got %zu", pl.workspace_bytes, d.workspace_bytes);
+    return BD_OK;
+}
+
+// run-time kernel choice and epilogue bits -> the instantiation: every epilogue combination has its own (the epilogue's addends are
+// compile-time); the four-stage form of conv_ps128_kernel exists for EPI 0 only (it always runs split, the reduce applies the epilogue)
+template <bool SP, int... EPI>
+static void ps_launch(const PsPlan& pl, int epi, const PsSmallParams& pp, hipStream_t st) {
+    static constexpr void (*general[])(PsParams) = {conv_ps_kernel<EPI, SP>...}, (*shared_tap[])(PsParams) = {conv_ps3_kernel<EPI, SP>...};
+    static constexpr void (*small[])(PsSmallParams) = {conv_ps128_kernel<EPI, SP, 2>...}, (*small_deep)(PsSmallParams) = conv_ps128_kernel<0, SP, 4>;
+    const dim3 grid((unsigned)pl.grid), block(PS_NT);
+    if (pl.kernel == BD_PS_128) {
+        const auto kernel = pl.stages == 4 ? small_deep : small[epi];
+        hipLaunchKernelGGL(kernel, grid, block, 0, st, pp);
+    } else {
+        const auto kernel = pl.kernel == BD_PS_256_SHARED_TAP ? shared_tap[epi] : general[epi];
+        hipLaunchKernelGGL(kernel, grid, block, 0, st, pp.q);
+    }
+}
+
+int conv3x3_ps(const bd_conv3x3_ps_desc& d, hipStream_t st) {
+    const PsPlan pl = ps_plan(d);
+    BD_TRY(ps_check(d, pl, true));
+    PsSmallParams pp = {};
+    PsParams& p = pp.q;
     p.a = reinterpret_cast<const char*>(d.x_split); p.w = reinterpret_cast<const char*>(d.w_split);
     p.y = d.y; p.bias = d.bias; p.rowbias = d.rowbias; p.residual = d.residual;
     p.lda = d.ldx; p.ldy = d.ldy; p.ldr = d.ldr; p.ld_rowbias = d.ld_rowbias;
     p.C = d.K; p.H = d.H; p.W = d.W; p.lw = ilog2_exact(d.W); p.lhw = ilog2_exact(d.W) + ilog2_exact(d.H);
-    p.sign = d.direction; p.M = (int)M; p.N = d.N;
+    p.sign = d.direction; p.M = (int)pl.M; p.N = d.N; p.tiles_m = pl.tiles_m; p.tiles_n = pl.tiles_n;
     p.out_scale = d.out_scale == 0.f ? 1.f : d.out_scale; p.accumulate = d.accumulate;
-    const bool large = ps_large(M, d.N);
-    int rec = -1;
-    if (prof_on()) {
-        static const char* kName[2][2][2] = {{{"conv_ps128_dgrad", "conv_ps_dgrad"}, {"conv_ps128_fwd", "conv_ps_fwd"}},
-                                             {{"conv_ps128_dgrad_bf16", "conv_ps_dgrad_bf16"}, {"conv_ps128_fwd_bf16", "conv_ps_fwd_bf16"}}};
-        rec = prof_begin(kName[sp][d.direction > 0][large],
-                         2.0 * (double)M * d.N * 9.0 * d.K, ((double)M * d.K + 9.0 * d.K * d.N + (double)M * d.N) * 4.0, st);
-    }
-    const int epi = (d.residual ? 1 : 0) | (d.rowbias ? 2 : 0) | (d.accumulate ? 4 : 0);
-    if (large) {
-        p.tiles_m = (int)cdiv(M, PS_BM); p.tiles_n = d.N / PS_BN;
-        const dim3 grid((unsigned)(p.tiles_m * p.tiles_n)), block(PS_NT);
-        // vertical-tap sharing variant (conv_ps3_kernel): image rows of 16 or 32 pixels, whole images per tile row block
-        const int vw = d.W < 32 ? d.W : 32;
-        const bool v3 = ps_takes_v3(d.B, d.H, d.W, d.N);
-        p.lvw = ilog2_exact(vw);
-        if (d.gn_part) {
-            BD_CHECK(d.direction == 1 && (epi == 1 || epi == 2) && conv3x3_ps_gn_splits(d.B, d.H, d.W, d.K, d.N, d.gn_groups) > 0, BD_ERR_UNSUPPORTED,
-                     "conv3x3_ps: gn_part needs a forward call with exactly one of rowbias / residual and bd_conv3x3_ps_gn_splits() > 0");
-            p.gn_part = d.gn_part; p.gn_G = d.gn_groups; p.gn_lcpg = ilog2_exact(d.N / d.gn_groups);
-        }
-#define PS_LAUNCH(E) do { if (v3) { if (sp) hipLaunchKernelGGL((conv_ps3_kernel<E, true>), grid, block, 0, st, p); \
-                                    else hipLaunchKernelGGL((conv_ps3_kernel<E, false>), grid, block, 0, st, p); } \
-                          else if (sp) hipLaunchKernelGGL((conv_ps_kernel<E, true>), grid, block, 0, st, p); \
-                          else hipLaunchKernelGGL((conv_ps_kernel<E, false>), grid, block, 0, st, p); } while (0)
-        switch (epi) {          // every combination has its own instantiation: the epilogue's addends are compile-time
-            case 0: PS_LAUNCH(0); break;
-            case 1: PS_LAUNCH(1); break;
-            case 2: PS_LAUNCH(2); break;
-            case 3: PS_LAUNCH(3); break;
-            case 4: PS_LAUNCH(4); break;
-            case 5: PS_LAUNCH(5); break;
-            case 6: PS_LAUNCH(6); break;
-            default: PS_LAUNCH(7); break;
-        }
-#undef PS_LAUNCH
-        BD_LAUNCH_CHECK("conv_ps");
-    } else {
-        BD_CHECK(!d.gn_part, BD_ERR_UNSUPPORTED, "conv3x3_ps: gn_part on a small layer (bd_conv3x3_ps_gn_splits() == 0)");
-        PsSmallParams pp = {};
-        p.tiles_m = (int)cdiv(M, 128); p.tiles_n = d.N / 128;
-        pp.q = p;
-        const PsWs ws = ps_ws(d);
-        pp.ksplit = ws.ksplit; pp.cps = ws.cps;
-        if (pp.ksplit > 1) {
-            BD_CHECK(d.workspace && d.workspace_bytes >= ws.bytes, BD_ERR_WORKSPACE, "conv3x3_ps: split-K needs %zu workspace bytes, got %zu", ws.bytes,
-                     d.workspace_bytes);
-            pp.partial = reinterpret_cast<float*>(d.workspace);
-        }
-        const dim3 grid((unsigned)(p.tiles_m * p.tiles_n * pp.ksplit)), block(512);
-        // round 6: short K slices (the 4 x 4 level) take the four-stage form (three chunks in flight, one workgroup per CU).  9: the 4 x 4
-        // level only, -0.05 ms per step; two stages everywhere or the 8 x 8 level too measured slower (profiles/r06_ab_ps128_deep.txt)
-        constexpr int deep_maxcps = 9;
-#define PS128_LAUNCH(E, ...) do { if (sp) hipLaunchKernelGGL((conv_ps128_kernel<E, true, ##__VA_ARGS__>), grid, block, 0, st, pp); \
-                                      else hipLaunchKernelGGL((conv_ps128_kernel<E, false, ##__VA_ARGS__>), grid, block, 0, st, pp); } while (0)
-        if (pp.ksplit > 1 && pp.cps <= deep_maxcps) {
-            PS128_LAUNCH(0, 4);
-        } else
-        switch (pp.ksplit > 1 ? 0 : epi) {
-            case 0: PS128_LAUNCH(0); break;
-            case 1: PS128_LAUNCH(1); break;
-            case 2: PS128_LAUNCH(2); break;
-            case 3: PS128_LAUNCH(3); break;
-            case 4: PS128_LAUNCH(4); break;
-            case 5: PS128_LAUNCH(5); break;
-            case 6: PS128_LAUNCH(6); break;
-            default: PS128_LAUNCH(7); break;
-        }
-#undef PS128_LAUNCH
-        BD_LAUNCH_CHECK("conv_ps128");
-        if (pp.ksplit > 1) {
-            hipLaunchKernelGGL(conv_ps128_reduce, dim3((unsigned)cdiv(M * (d.N / 4), 256)), dim3(256), 0, st, pp);
-            BD_LAUNCH_CHECK("conv_ps128_reduce");
-        }
+    if (pl.large) p.lvw = ilog2_exact(ps_vw(d.W));
+    if (d.gn_part) { p.gn_part = d.gn_part; p.gn_G = d.gn_groups; p.gn_lcpg = ilog2_exact(d.N / d.gn_groups); }
+    pp.ksplit = pl.ksplit; pp.cps = pl.chunks_per_split;
+    if (pl.reduce) pp.partial = reinterpret_cast<float*>(d.workspace);
+    const int rec = prof_on() ? prof_begin(pl.prof_class, 2.0 * (double)pl.M * d.N * 9.0 * d.K,
+                                           ((double)pl.M * d.K + 9.0 * d.K * d.N + (double)pl.M * d.N) * 4.0, st) : -1;
+    const int epi = pl.reduce ? 0 : ps_epi(d);
+    if (d.mode == BD_MODE_BF16) ps_launch<true, 0, 1, 2, 3, 4, 5, 6, 7>(pl, epi, pp, st);   // single pass: hi*hi only
+    else ps_launch<false, 0, 1, 2, 3, 4, 5, 6, 7>(pl, epi, pp, st);
+    BD_LAUNCH_CHECK(pl.large ? "conv_ps" : "conv_ps128");
+    if (pl.reduce) {
+        hipLaunchKernelGGL(conv_ps128_reduce, dim3((unsigned)cdiv(pl.M * (d.N / 4), 256)), dim3(256), 0, st, pp);
+        BD_LAUNCH_CHECK("conv_ps128_reduce");
     }
     prof_end(rec, st);
     return BD_OK;
 }
 
-bool conv3x3_ps_wgrad_supported(int B, int H, int W, int Cin, int Cout) {
-    return B > 0 && ilog2_exact(H) >= 0 && ilog2_exact(W) >= 0 && Cin % WG_BN == 0 && Cout % WG_BM == 0;
+// ---- the weight gradients: bd_conv3x3_ps_wgrad (nine taps) and its PHASE form bd_upsample_conv_wgrad (the 16 entries of E, conv_ph.hip) share
+// one plan, one list of checks and one launcher.  The nine-tap descriptor is read through the fields it shares with the phase form's.
+static bd_upsample_conv_desc ps_wgrad_desc(const bd_conv3x3_ps_wgrad_desc& d) {
+    bd_upsample_conv_desc u = {};
+    u.B = d.B; u.H = d.H; u.W = d.W; u.Cin = d.Cin; u.Cout = d.Cout; u.x_split = d.x_split; u.ldx = d.ldx; u.dy_split = d.dy_split; u.lddy = d.lddy;
+    u.dw = d.dw; u.db = d.db; u.workspace = d.workspace; u.workspace_bytes = d.workspace_bytes; u.mode = d.mode;
+    return u;
 }
-// vertical-tap sharing form (conv_ps_wgrad3_kernel): image rows of 16 or 32 pixels, whole 32-pixel chunks
-static bool ps_wgrad_v3(const bd_conv3x3_ps_wgrad_desc& d) {
-    static const bool off = getenv("BD_PS_WG3") && atoi(getenv("BD_PS_WG3")) == 0;
-    static const int maxw = getenv("BD_PS_WG3_MAXW") ? atoi(getenv("BD_PS_WG3_MAXW")) : (1 << 30);        // (A/B knob: 32 = round 3's gate)
-    // round 4: any W >= 16 -- wider images are walked strip by strip (virtual pixel order, ps_v2r): a chunk = one 32-pixel strip row
-    return !off && d.W >= 16 && d.W <= maxw && ((long long)d.B * d.H * d.W) % 32 == 0;
+bool conv3x3_ps_wgrad_supported(int B, int H, int W, int Cin, int Cout) {
+    return ps_grid_ok(B, H, W) && Cin > 0 && Cin % WG_BN == 0 && Cout > 0 && Cout % WG_BM == 0;
 }
 static int g_wg3_slots_override = 0;     // 0: environment / default (set by bd_tune_set)
-// K split and slab bytes (Cout * 9 * Cin gradient + Cout bias-gradient floats per split) of one call: what
-// bd_conv3x3_ps_wgrad_workspace_bytes answers and what the launcher checks and hands the kernel
-struct PsWgWs { int ksplit, cps; size_t bytes; };
-static PsWgWs ps_wgrad_ws(const bd_conv3x3_ps_wgrad_desc& d) {
-    PsWgWs s = {1, 0, 0};
-    const bool v3 = ps_wgrad_v3(d);
-    const long long tiles = (long long)(d.Cout / WG_BM) * ((v3 ? 3 : 9) * d.Cin / WG_BN);
-    const int nchunks = (int)cdiv((long long)d.B * d.H * d.W, 32);
+// Everything the two entry points decide from a descriptor's numbers: kernel, tiles, K split and the layout of the slabs (Cout * ntaps * Cin
+// gradient + bias_rows * Cout bias-gradient floats per split; behind them dE in the phase form).  The launcher, the two *_workspace_bytes and
+// the two plan queries read it.  grid 0, nothing else set: a shape ps_wgrad_check refuses.
+typedef bd_conv3x3_ps_wgrad_plan_info PsWgPlan;
+static PsWgPlan ps_wgrad_plan(const bd_upsample_conv_desc& d, bool phase) {
+    static const bool v3_off = getenv("BD_PS_WG3") && atoi(getenv("BD_PS_WG3")) == 0;
+    static const int v3_maxw = getenv("BD_PS_WG3_MAXW") ? atoi(getenv("BD_PS_WG3_MAXW")) : (1 << 30);        // (A/B knob: 32 = round 3's gate)
+    static const int slots3_getenv = getenv("BD_PS_WG3_SLOTS") ? atoi(getenv("BD_PS_WG3_SLOTS")) : 0;
+    static const char* kName[3][2] = {{"conv_ps_wgrad", "conv_ps_wgrad_bf16"}, {"conv_ps_wgrad3", "conv_ps_wgrad3_bf16"},      // (round 6: the large layers' kernel is its own class)
+                                      {"conv_ph_ups_wgrad", "conv_ph_ups_wgrad_bf16"}};
+    PsWgPlan p = {};
+    if (!conv3x3_ps_wgrad_supported(d.B, d.H, d.W, d.Cin, d.Cout)) return p;
+    const long long P = (long long)d.B * d.H * d.W;
+    // vertical-tap sharing form (conv_ps_wgrad3_kernel): image rows of 16 or 32 pixels, whole 32-pixel chunks
+    // round 4: any W >= 16 -- wider images are walked strip by strip (virtual pixel order, ps_v2r): a chunk = one 32-pixel strip row
+    const bool v3 = !phase && !v3_off && d.W >= 16 && d.W <= v3_maxw && P % 32 == 0;
+    p.kernel = phase ? BD_PS_WGRAD_PHASE : v3 ? BD_PS_WGRAD_SHARED_TAP : BD_PS_WGRAD;
+    p.ntaps = phase ? 16 : 9; p.bias_rows = phase ? 4 : 1;      // (phase form: one bias row per pixel class of the fine grid)
+    p.tiles_m = d.Cout / WG_BM; p.tiles_n = (v3 ? 3 : p.ntaps) * d.Cin / WG_BN;
     const int slots = 2 * device_cus();   // two 64-KB workgroups per CU (two LDS stages each): the pair de-phases, 141 vs 189 us
     // 96 KB of LDS: one workgroup per CU -- and three quarters of the CUs (round 4, late: 192 of 256).  The kernel never runs alone: the data-gradient
     // chain shares the chip with it, so the CUs it leaves are not idle, and a quarter fewer slabs are a quarter less slab traffic: CIFAR step
@@ -1355,110 +1351,73 @@ static PsWgWs ps_wgrad_ws(const bd_conv3x3_ps_wgrad_desc& d) {
     // Images walked strip by strip (W > 32: the 256 x 256 network at B = 4, whose main stream carries the three-pass GroupNorm and 2 048-tile data
     // gradients): HALF the CUs -- 27.14 -> 26.69 ms per step (144 / 160 / 176 slots: 27.52 / 27.51 / 27.74; 112 / 96 / 64: 27.21 / 28.16 / 32.9), while the
     // CIFAR step wants its 192 (128: 18.08 against 17.89).
-    static const int slots3_getenv = getenv("BD_PS_WG3_SLOTS") ? atoi(getenv("BD_PS_WG3_SLOTS")) : 0;
     const int slots3_env = g_wg3_slots_override > 0 ? g_wg3_slots_override : slots3_getenv;      // bd_tune_set("ps_wg3_slots", n) wins over the environment
-    const int slots3 = slots3_env > 0 ? slots3_env : (d.W > 32 ? slots / 4 : slots * 3 / 8);
+    p.slots = !v3 ? slots : slots3_env > 0 ? slots3_env : (d.W > 32 ? slots / 4 : slots * 3 / 8);
     // chunks per split at least 8 (4x4 layers: 8 slabs instead of 14; 4 / 16 measured +0.2 / +0.1 ms)
-    split_k(v3 ? slots3 : slots, tiles, nchunks, 8, s.ksplit, s.cps);
-    if (s.ksplit > 1) s.bytes = (size_t)s.ksplit * ((size_t)d.Cout * 9 * d.Cin + d.Cout) * sizeof(float);
-    return s;
+    split_k(p.slots, (long long)p.tiles_m * p.tiles_n, (int)cdiv(P, 32), 8, p.ksplit, p.chunks_per_split);
+    p.reduce = phase || p.ksplit > 1;
+    p.grid = p.tiles_m * p.tiles_n * p.ksplit;
+    const size_t mn = (size_t)d.Cout * p.ntaps * d.Cin;
+    p.slab_floats = mn + (size_t)p.bias_rows * d.Cout;
+    if (p.reduce) p.workspace_bytes = (size_t)p.ksplit * p.slab_floats * sizeof(float);
+    if (phase) { p.de_offset = p.workspace_bytes; p.workspace_bytes += mn * sizeof(float); }       // K-split slabs + dE
+    p.prof_class = kName[p.kernel][d.mode == BD_MODE_BF16];
+    return p;
 }
-size_t conv3x3_ps_wgrad_workspace_bytes(const bd_conv3x3_ps_wgrad_desc& d) { return ps_wgrad_ws(d).bytes; }
-int conv3x3_ps_wgrad(const bd_conv3x3_ps_wgrad_desc& d, hipStream_t st) {
-    BD_CHECK(d.x_split && d.dy_split && d.dw, BD_ERR_INVALID, "conv3x3_ps_wgrad: null pointer");
-    BD_CHECK(d.B > 0 && conv3x3_ps_wgrad_supported(d.B, d.H, d.W, d.Cin, d.Cout), BD_ERR_UNSUPPORTED,
-             "conv3x3_ps_wgrad: needs power-of-two H, W, Cin and Cout multiples of 128");
-    BD_CHECK(d.ldx % 32 == 0 && d.lddy % 32 == 0 && ((uintptr_t)d.x_split & 127) == 0 && ((uintptr_t)d.dy_split & 127) == 0,
-             BD_ERR_UNSUPPORTED, "conv3x3_ps_wgrad: split planes need ld %% 32 == 0 and 128-byte aligned bases");
-    BD_CHECK(sp_mode_valid(d.mode), BD_ERR_INVALID, "conv3x3_ps_wgrad: unknown compute mode %d", d.mode);
-    BD_CHECK(d.ldx >= d.Cin && d.lddy >= d.Cout, BD_ERR_INVALID, "conv3x3_ps_wgrad: ldx=%lld < Cin=%d or lddy=%lld < Cout=%d", (long long)d.ldx,
+size_t conv3x3_ps_wgrad_workspace_bytes(const bd_conv3x3_ps_wgrad_desc& d) { return ps_wgrad_plan(ps_wgrad_desc(d), false).workspace_bytes; }
+size_t upsample_conv_wgrad_workspace_bytes(const bd_upsample_conv_desc& d) { return ps_wgrad_plan(d, true).workspace_bytes; }
+
+// The checks of the weight-gradient entry point `who`, in the order it has always reported them, and -- `p` given: the launcher -- the kernel
+// arguments.  Without `p` (the plan queries) the null-pointer, base-alignment and workspace checks, the launcher's own, are skipped.
+static int ps_wgrad_check(const char* who, const bd_upsample_conv_desc& d, bool phase, const PsWgPlan& pl, PsWgParams* p) {
+    BD_CHECK(!p || (d.x_split && d.dy_split && d.dw), BD_ERR_INVALID, "%s: null pointer", who);
+    BD_CHECK(pl.grid > 0, BD_ERR_UNSUPPORTED, "%s: needs power-of-two H, W, Cin and Cout multiples of 128", who);
+    BD_CHECK(d.ldx % 32 == 0 && d.lddy % 32 == 0 && (!p || (((uintptr_t)d.x_split | (uintptr_t)d.dy_split) & 127) == 0), BD_ERR_UNSUPPORTED,
+             "%s: split planes need ld %% 32 == 0 and 128-byte aligned bases", who);
+    BD_CHECK(!phase || (long long)d.B * d.H * d.W * 4 < (1ll << 31), BD_ERR_UNSUPPORTED, "%s: pixel count overflows int32", who);
+    BD_CHECK(sp_mode_valid(d.mode), BD_ERR_INVALID, "%s: unknown compute mode %d", who, d.mode);
+    BD_CHECK(phase || (d.ldx >= d.Cin && d.lddy >= d.Cout), BD_ERR_INVALID, "%s: ldx=%lld < Cin=%d or lddy=%lld < Cout=%d", who, (long long)d.ldx,
              d.Cin, (long long)d.lddy, d.Cout);
-    const bool sp = d.mode == BD_MODE_BF16;
-    PsWgParams p = {};
-    p.dy = reinterpret_cast<const char*>(d.dy_split); p.x = reinterpret_cast<const char*>(d.x_split);
-    p.lddy = d.lddy; p.ldx = d.ldx; p.Cin = d.Cin; p.Cout = d.Cout; p.H = d.H; p.W = d.W; p.lw = ilog2_exact(d.W);
-    p.lh = ilog2_exact(d.H); p.lvw = ilog2_exact(d.W < 32 ? d.W : 32);
-    p.P = d.B * d.H * d.W;
-    const bool v3 = ps_wgrad_v3(d);
-    p.tiles_m = d.Cout / WG_BM; p.tiles_n = (v3 ? 3 : 9) * d.Cin / WG_BN; p.ntaps = 9;
-    const PsWgWs ws = ps_wgrad_ws(d);
-    p.ksplit = ws.ksplit; p.cps = ws.cps;
-    p.want_db = d.db != nullptr;
-    const long long mn = (long long)d.Cout * 9 * d.Cin;
-    if (p.ksplit > 1) {
-        BD_CHECK(d.workspace && d.workspace_bytes >= ws.bytes, BD_ERR_WORKSPACE, "conv3x3_ps_wgrad: workspace %zu < %zu", d.workspace_bytes, ws.bytes);
-        p.out = reinterpret_cast<float*>(d.workspace);
-    } else {
-        p.out = d.dw; p.db = d.db;
-    }
-    int rec = -1;
-    if (prof_on())
-        rec = prof_begin(v3 ? (sp ? "conv_ps_wgrad3_bf16" : "conv_ps_wgrad3") : (sp ? "conv_ps_wgrad_bf16" : "conv_ps_wgrad"), 2.0 * (double)p.P * d.Cout * 9.0 * d.Cin,   // (round 6: the large layers' kernel is its own class)
-                         ((double)p.P * (d.Cin + d.Cout) + 9.0 * d.Cin * d.Cout) * 4.0, st);
-    const dim3 grid((unsigned)(p.tiles_m * p.tiles_n * p.ksplit));
-    if (v3 && sp) hipLaunchKernelGGL(conv_ps_wgrad3_kernel<true>, grid, dim3(512), 0, st, p);
-    else if (v3) hipLaunchKernelGGL(conv_ps_wgrad3_kernel<false>, grid, dim3(512), 0, st, p);
-    else if (sp) hipLaunchKernelGGL((conv_ps_wgrad_kernel<2, 8, true>), grid, dim3(512), 0, st, p);
-    else hipLaunchKernelGGL((conv_ps_wgrad_kernel<2, 8, false>), grid, dim3(512), 0, st, p);
-    BD_LAUNCH_CHECK("conv_ps_wgrad");
-    if (p.ksplit > 1) {
-        const long long total = mn / 4 + (d.db ? d.Cout : 0);
-        if (v3) hipLaunchKernelGGL(conv_ps_wgrad_reduce<true>, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, st, p.out, p.ksplit, mn, d.Cout, d.dw, d.db, p.ksplit);
-        else hipLaunchKernelGGL(conv_ps_wgrad_reduce<false>, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, st, p.out, p.ksplit, mn, d.Cout, d.dw, d.db, p.ksplit);
-        BD_LAUNCH_CHECK("conv_ps_wgrad_reduce");
-    }
-    prof_end(rec, st);
+    if (!p) return BD_OK;
+    BD_CHECK(!pl.reduce || (d.workspace && d.workspace_bytes >= pl.workspace_bytes), BD_ERR_WORKSPACE, "%s: workspace %zu < %zu", who,
+             d.workspace_bytes, pl.workspace_bytes);
+    p->dy = reinterpret_cast<const char*>(d.dy_split); p->x = reinterpret_cast<const char*>(d.x_split);
+    p->lddy = d.lddy; p->ldx = d.ldx; p->Cin = d.Cin; p->Cout = d.Cout; p->H = d.H; p->W = d.W; p->lw = ilog2_exact(d.W);
+    if (!phase) { p->lh = ilog2_exact(d.H); p->lvw = ilog2_exact(ps_vw(d.W)); }
+    p->P = d.B * d.H * d.W;
+    p->tiles_m = pl.tiles_m; p->tiles_n = pl.tiles_n; p->ntaps = pl.ntaps; p->ksplit = pl.ksplit; p->cps = pl.chunks_per_split;
+    p->want_db = d.db != nullptr;
+    if (pl.reduce) p->out = reinterpret_cast<float*>(d.workspace);      // slabs; the second pass writes dw (phase form: dE) and db
+    else { p->out = d.dw; p->db = d.db; }
     return BD_OK;
 }
 
-// ---- PHASE form of the weight gradient: the upsample convolution (conv_ph.hip) ---------------------------------------------------
-static void ups_wgrad_split(const bd_upsample_conv_desc& d, int& ksplit, int& cps) {
-    const long long tiles = (long long)(d.Cout / WG_BM) * (16 * d.Cin / WG_BN);
-    const int nchunks = (int)cdiv((long long)d.B * d.H * d.W, 32);
-    split_k(2 * device_cus(), tiles, nchunks, 8, ksplit, cps);
-}
-size_t upsample_conv_wgrad_workspace_bytes(const bd_upsample_conv_desc& d) {
-    int ks, cps;
-    ups_wgrad_split(d, ks, cps);
-    const size_t mn = (size_t)d.Cout * 16 * d.Cin;
-    return ((size_t)ks * (mn + 4 * (size_t)d.Cout) + mn) * sizeof(float);       // K-split slabs (+ 4 bias rows each) + dE
-}
-// dw [Cout,3,3,Cin] (+ db) of y = conv3x3(nearest_up2(x)) from x (split planes, SOURCE grid) and dY (split planes, fine grid)
-int upsample_conv_wgrad(const bd_upsample_conv_desc& d, hipStream_t st) {
-    BD_CHECK(d.x_split && d.dy_split && d.dw, BD_ERR_INVALID, "bd_upsample_conv_wgrad: null pointer");
-    BD_CHECK(d.B > 0 && conv3x3_ps_wgrad_supported(d.B, d.H, d.W, d.Cin, d.Cout), BD_ERR_UNSUPPORTED,
-             "bd_upsample_conv_wgrad: needs power-of-two H, W, Cin and Cout multiples of 128");
-    BD_CHECK(d.ldx % 32 == 0 && d.lddy % 32 == 0 && ((uintptr_t)d.x_split & 127) == 0 && ((uintptr_t)d.dy_split & 127) == 0,
-             BD_ERR_UNSUPPORTED, "bd_upsample_conv_wgrad: split planes need ld %% 32 == 0 and 128-byte aligned bases");
-    BD_CHECK((long long)d.B * d.H * d.W * 4 < (1ll << 31), BD_ERR_UNSUPPORTED, "bd_upsample_conv_wgrad: pixel count overflows int32");
-    BD_CHECK(sp_mode_valid(d.mode), BD_ERR_INVALID, "bd_upsample_conv_wgrad: unknown compute mode %d", d.mode);
-    const size_t need = upsample_conv_wgrad_workspace_bytes(d);
-    BD_CHECK(d.workspace && d.workspace_bytes >= need, BD_ERR_WORKSPACE, "bd_upsample_conv_wgrad: workspace %zu < %zu", d.workspace_bytes, need);
+static int ps_wgrad_launch(const char* who, const bd_upsample_conv_desc& d, bool phase, hipStream_t st) {
+    static constexpr void (*kernels[3][2])(PsWgParams) = {{conv_ps_wgrad_kernel<2, 8, false>, conv_ps_wgrad_kernel<2, 8, true>},
+                                                          {conv_ps_wgrad3_kernel<false>, conv_ps_wgrad3_kernel<true>},
+                                                          {conv_ps_wgrad_kernel<2, 8, false, true>, conv_ps_wgrad_kernel<2, 8, true, true>}};
+    const PsWgPlan pl = ps_wgrad_plan(d, phase);
     PsWgParams p = {};
-    p.dy = reinterpret_cast<const char*>(d.dy_split); p.x = reinterpret_cast<const char*>(d.x_split);
-    p.lddy = d.lddy; p.ldx = d.ldx; p.Cin = d.Cin; p.Cout = d.Cout; p.H = d.H; p.W = d.W; p.lw = ilog2_exact(d.W);
-    p.P = d.B * d.H * d.W;
-    p.tiles_m = d.Cout / WG_BM; p.tiles_n = 16 * d.Cin / WG_BN; p.ntaps = 16;
-    ups_wgrad_split(d, p.ksplit, p.cps);
-    p.want_db = d.db != nullptr;
-    const long long mn = (long long)d.Cout * 16 * d.Cin;
-    p.out = reinterpret_cast<float*>(d.workspace);
-    float* de = p.out + (size_t)p.ksplit * ((size_t)mn + 4 * (size_t)d.Cout);
-    int rec = -1;
-    if (prof_on())
-        rec = prof_begin(d.mode == BD_MODE_BF16 ? "conv_ph_ups_wgrad_bf16" : "conv_ph_ups_wgrad", 2.0 * (double)p.P * 4.0 * d.Cout * 9.0 * d.Cin,
-                         ((double)p.P * (d.Cin + 4.0 * d.Cout) + 9.0 * d.Cin * d.Cout) * 4.0, st);
-    const dim3 grid((unsigned)(p.tiles_m * p.tiles_n * p.ksplit));
-    if (d.mode == BD_MODE_BF16) hipLaunchKernelGGL((conv_ps_wgrad_kernel<2, 8, true, true>), grid, dim3(512), 0, st, p);
-    else hipLaunchKernelGGL((conv_ps_wgrad_kernel<2, 8, false, true>), grid, dim3(512), 0, st, p);
-    BD_LAUNCH_CHECK("conv_ps_wgrad (phase)");
-    const long long total = mn / 4 + (d.db ? d.Cout : 0);
-    hipLaunchKernelGGL(conv_ps_wgrad_reduce<false>, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, st, p.out, p.ksplit, mn, d.Cout, de, d.db, 4 * p.ksplit);
-    BD_LAUNCH_CHECK("conv_ps_wgrad_reduce (phase)");
-    BD_TRY(ups_dweff_combine(de, d.Cin, d.Cout, d.dw, st));
+    BD_TRY(ps_wgrad_check(who, d, phase, pl, &p));
+    const double fine = phase ? 4.0 : 1.0;       // phase form: dY lives on the fine grid, four pixels per source pixel
+    const int rec = prof_on() ? prof_begin(pl.prof_class, 2.0 * (double)p.P * fine * d.Cout * 9.0 * d.Cin,
+                                           ((double)p.P * (d.Cin + fine * d.Cout) + 9.0 * d.Cin * d.Cout) * 4.0, st) : -1;
+    hipLaunchKernelGGL(kernels[pl.kernel][d.mode == BD_MODE_BF16], dim3((unsigned)pl.grid), dim3(512), 0, st, p);
+    BD_LAUNCH_CHECK(phase ? "conv_ps_wgrad (phase)" : "conv_ps_wgrad");
+    if (pl.reduce) {
+        const long long mn = (long long)d.Cout * pl.ntaps * d.Cin, total = mn / 4 + (d.db ? d.Cout : 0);
+        float* dst = phase ? reinterpret_cast<float*>(static_cast<char*>(d.workspace) + pl.de_offset) : d.dw;
+        const auto reduce = pl.kernel == BD_PS_WGRAD_SHARED_TAP ? conv_ps_wgrad_reduce<true> : conv_ps_wgrad_reduce<false>;
+        hipLaunchKernelGGL(reduce, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, st, p.out, p.ksplit, mn, d.Cout, dst, d.db, pl.bias_rows * p.ksplit);
+        BD_LAUNCH_CHECK(phase ? "conv_ps_wgrad_reduce (phase)" : "conv_ps_wgrad_reduce");
+        if (phase) BD_TRY(ups_dweff_combine(dst, d.Cin, d.Cout, d.dw, st));      // dE -> dw [Cout,3,3,Cin]
+    }
     prof_end(rec, st);
     return BD_OK;
 }
+int conv3x3_ps_wgrad(const bd_conv3x3_ps_wgrad_desc& d, hipStream_t st) { return ps_wgrad_launch("conv3x3_ps_wgrad", ps_wgrad_desc(d), false, st); }
+// dw [Cout,3,3,Cin] (+ db) of y = conv3x3(nearest_up2(x)) from x (split planes, SOURCE grid) and dY (split planes, fine grid)
+int upsample_conv_wgrad(const bd_upsample_conv_desc& d, hipStream_t st) { return ps_wgrad_launch("bd_upsample_conv_wgrad", d, true, st); }
 
 int g_tune_gen = 0;
 int tune_set(const char* key, int value) {
@@ -1483,12 +1442,31 @@ extern "C" int bd_conv3x3_ps(const bd_conv3x3_ps_desc* d, bd_stream_t s) {
     BD_CHECK(d, BD_ERR_INVALID, "bd_conv3x3_ps: null descriptor");
     return bd::conv3x3_ps(*d, bd::S(s));
 }
+extern "C" int bd_conv3x3_ps_plan(const bd_conv3x3_ps_desc* d, bd_conv3x3_ps_plan_info* out) {
+    BD_CHECK(d != nullptr && out != nullptr, BD_ERR_INVALID, "bd_conv3x3_ps_plan: null descriptor or output");
+    const bd::PsPlan p = bd::ps_plan(*d);
+    BD_TRY(bd::ps_check(*d, p, false));
+    *out = p;
+    return BD_OK;
+}
 extern "C" int bd_conv3x3_ps_wgrad(const bd_conv3x3_ps_wgrad_desc* d, bd_stream_t s) {
     BD_CHECK(d, BD_ERR_INVALID, "bd_conv3x3_ps_wgrad: null descriptor");
     return bd::conv3x3_ps_wgrad(*d, bd::S(s));
 }
 extern "C" size_t bd_conv3x3_ps_wgrad_workspace_bytes(const bd_conv3x3_ps_wgrad_desc* d) {
     return d ? bd::conv3x3_ps_wgrad_workspace_bytes(*d) : 0;
+}
+static int ps_wgrad_plan_query(const char* who, const bd_upsample_conv_desc& d, bool phase, bd_conv3x3_ps_wgrad_plan_info* out) {
+    *out = bd::ps_wgrad_plan(d, phase);
+    return bd::ps_wgrad_check(who, d, phase, *out, nullptr);
+}
+extern "C" int bd_conv3x3_ps_wgrad_plan(const bd_conv3x3_ps_wgrad_desc* d, bd_conv3x3_ps_wgrad_plan_info* out) {
+    BD_CHECK(d != nullptr && out != nullptr, BD_ERR_INVALID, "bd_conv3x3_ps_wgrad_plan: null descriptor or output");
+    return ps_wgrad_plan_query("conv3x3_ps_wgrad", bd::ps_wgrad_desc(*d), false, out);
+}
+extern "C" int bd_upsample_conv_wgrad_plan(const bd_upsample_conv_desc* d, bd_conv3x3_ps_wgrad_plan_info* out) {
+    BD_CHECK(d != nullptr && out != nullptr, BD_ERR_INVALID, "bd_upsample_conv_wgrad_plan: null descriptor or output");
+    return ps_wgrad_plan_query("bd_upsample_conv_wgrad", *d, true, out);
 }
 extern "C" int bd_split_rows(const float* src, int64_t ld_src, int64_t rows, int C, uint16_t* dst, int64_t ld_dst, bd_stream_t stream) {
     BD_CHECK(src && dst && rows > 0 && C > 0, BD_ERR_INVALID, "bd_split_rows: bad args");

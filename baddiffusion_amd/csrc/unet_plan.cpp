@@ -545,11 +545,9 @@ struct bd_unet {
     }
     // the upsample convolution's data gradient as ONE class of 16 taps on dY sampled at stride 2 (else: the fine-grid form + 2x2 sums): with
     // >= 128 tiles of its own, or >= 32 where the launch deals the taps of a tile to four workgroups, as it does while the tiles fill at most half
-    // the chip.  KEEP IN STEP with ph_tap_groups of conv_ph.hip (256 x 128 = its PH_BM x PH_BN tile): that function takes the launcher's
-    // decision, this line restates it as the plan's path choice.  (phase_ups_dgrad sizes the workspace by the launcher's own function.)
+    // the chip: the launcher's own decision (upsample_conv_dgrad_tap_groups, conv_ph.hip), read here as the plan's path choice.
     bool phase_dgrad_shape(int B, int H, int W, int C) const {
-        const bool deals_taps = cdiv((int64_t)B * H * W, 256) * (C / 128) * 2 <= device_cus();
-        return phase_shape(B, H, W, C, C, deals_taps ? 4 : 1);
+        return phase_shape(B, H, W, C, C, upsample_conv_dgrad_tap_groups(B, H, W, C));
     }
     // the plane kernel in either direction: +1 forward (W planes of the per-step split copy), -1 data gradient (transposed planes)
     int conv3_planes(Ctx& c, const Conv3& k, int direction, const Opnd& x, float* y, int64_t ldy, int acc, const Conv3Epi& e) const {

@@ -480,6 +480,36 @@ def conv3x3_ps(x_split, w_split, B, H, W, K, N, direction=1, bias=None, rowbias=
     return y if part is None else (y, part)
 
 
+def _plan_dict(info):
+    return {name: v.decode() if isinstance(v, bytes) else v for name, v in ((n, getattr(info, n)) for n, _ in info._fields_)}
+
+
+def conv3x3_ps_plan(B, H, W, K, N, direction=1, gn_groups=0, mode=0, epi=0):
+    """bd_conv3x3_ps_plan of a dense call (ldx = K, ldy = N) as a dict: kernel (L.PS_*), tiles, K split, ring depth, grid, workspace bytes,
+    profiler class, GroupNorm splits for gn_groups.  epi: bit 1 = residual, 2 = row bias, 4 = accumulate.  Host only, nothing is launched;
+    raises what bd_conv3x3_ps would answer for a shape it refuses."""
+    lib = L.load()
+    d = L.ConvPsDesc(B=B, H=H, W=W, K=K, N=N, direction=direction, ldx=K, ldy=N, residual=16 if epi & 1 else None, ldr=N,
+                     rowbias=16 if epi & 2 else None, ld_rowbias=N, accumulate=int(bool(epi & 4)), gn_groups=gn_groups, mode=mode)
+    info = L.ConvPsPlanInfo()
+    L.check(lib.bd_conv3x3_ps_plan(C.byref(d), C.byref(info)), "bd_conv3x3_ps_plan")
+    return _plan_dict(info)
+
+
+def conv3x3_ps_wgrad_plan(B, H, W, Cin, Cout, mode=0, phase=False):
+    """bd_conv3x3_ps_wgrad_plan (phase: bd_upsample_conv_wgrad_plan, H x W the SOURCE grid) of a dense call as a dict: kernel (L.PS_WGRAD*),
+    taps, tiles, slots, K split, slab layout, workspace bytes, profiler class.  Host only, nothing is launched."""
+    lib = L.load()
+    info = L.ConvPsWgradPlanInfo()
+    if phase:
+        d = L.UpsampleConvDesc(B=B, H=H, W=W, Cin=Cin, Cout=Cout, ldx=Cin, lddy=Cout, mode=mode)
+        L.check(lib.bd_upsample_conv_wgrad_plan(C.byref(d), C.byref(info)), "bd_upsample_conv_wgrad_plan")
+    else:
+        d = L.ConvPsWgradDesc(B=B, H=H, W=W, Cin=Cin, Cout=Cout, ldx=Cin, lddy=Cout, mode=mode)
+        L.check(lib.bd_conv3x3_ps_wgrad_plan(C.byref(d), C.byref(info)), "bd_conv3x3_ps_wgrad_plan")
+    return _plan_dict(info)
+
+
 def conv3x3_ps_wgrad(x_split, dy_split, B, H, W, Cin, Cout, with_db=False, mode=0):
     """dw [Cout,3,3,Cin] (and db [Cout]) of the stride-1 pad-1 conv from split-plane operands."""
     lib = L.load(); _need_cuda(x_split, dy_split)

@@ -744,6 +744,29 @@ typedef struct {
 size_t bd_conv3x3_ps_workspace_bytes(const bd_conv3x3_ps_desc* d);
 int bd_conv3x3_ps_gn_splits(int B, int H, int W, int K, int N, int groups);   /* 0: this call cannot write GroupNorm partials */
 int bd_conv3x3_ps(const bd_conv3x3_ps_desc* d, bd_stream_t stream);
+/* What bd_conv3x3_ps decides for a descriptor: host code only, a copy of the plan the launcher, bd_conv3x3_ps_workspace_bytes and
+ * bd_conv3x3_ps_gn_splits themselves read.  bd_conv3x3_ps_plan runs the checks of bd_conv3x3_ps on the descriptor's numbers (shape,
+ * direction, mode, leading dimensions: same status, same message) and launches nothing; it reads none of the descriptor's pointers beyond
+ * whether residual / rowbias are set, and neither needs nor checks a workspace.  For tests and tools that must know which branch a call
+ * takes (DESIGN.md "Dispatch branches of the split-plane convolutions"). */
+enum bd_ps_kernel {
+    BD_PS_256 = 0,              /* conv_ps_kernel: 256 x 128 tiles, three LDS stages, no K split (>= 96 tiles)                  */
+    BD_PS_256_SHARED_TAP,       /* conv_ps3_kernel: the same tiles with the vertical taps shared (W >= 16, whole tiles per image) */
+    BD_PS_128                   /* conv_ps128_kernel: 128 x 128 tiles, K split over the CUs (fewer than 96 tiles of 256 x 128)    */
+};
+typedef struct {
+    int kernel;                 /* bd_ps_kernel                                                                                   */
+    int tiles_m, tiles_n;       /* output tiles (256 x 128 or 128 x 128)                                                          */
+    int ksplit, chunks_per_split;   /* K slices and (tap, 32-channel) chunks per slice (the last slice may be shorter, never empty) */
+    int stages;                 /* LDS ring depth: 3 (256-row kernels), 2 or 4 (BD_PS_128; 4: split slices of at most 9 chunks)   */
+    int reduce;                 /* 1: conv_ps128_reduce folds the slabs and applies the epilogue (ksplit > 1)                     */
+    int grid;                   /* workgroups of the main kernel = tiles_m * tiles_n * ksplit                                     */
+    int gn_splits;              /* 256-pixel tiles per image whose GroupNorm partials the epilogue can write for the descriptor's
+                                   gn_groups (= bd_conv3x3_ps_gn_splits), else 0; 0 groups: not asked                             */
+    size_t workspace_bytes;     /* = bd_conv3x3_ps_workspace_bytes                                                                */
+    const char* prof_class;     /* the profiler class the launch is counted under                                                */
+} bd_conv3x3_ps_plan_info;
+int bd_conv3x3_ps_plan(const bd_conv3x3_ps_desc* d, bd_conv3x3_ps_plan_info* out);
 /* weight (and bias) gradient of the same convolution, both operands as split planes:
  *   dw[Cout][3][3][Cin] = sum_p dy[p][co] x[p + tap][ci],  db[Cout] = sum_p dy[p][co] (optional, same launch).
  * Cin, Cout % 128 == 0; K (pixels) is split over workgroups with a fixed-order second pass (deterministic);
@@ -763,6 +786,30 @@ typedef struct {
 int bd_tune_set(const char* key, int value);
 size_t bd_conv3x3_ps_wgrad_workspace_bytes(const bd_conv3x3_ps_wgrad_desc* d);
 int bd_conv3x3_ps_wgrad(const bd_conv3x3_ps_wgrad_desc* d, bd_stream_t stream);
+/* What bd_conv3x3_ps_wgrad and bd_upsample_conv_wgrad (below) decide for a descriptor: host code only, a copy of the one plan both
+ * launchers and their *_workspace_bytes read.  The queries run their entry point's checks on the descriptor's numbers (same status, same
+ * message), read no pointer, neither need nor check a workspace, and launch nothing. */
+enum bd_ps_wgrad_kernel {
+    BD_PS_WGRAD = 0,            /* conv_ps_wgrad_kernel: one tile per (tap, 128 ci), 9 taps                                       */
+    BD_PS_WGRAD_SHARED_TAP,     /* conv_ps_wgrad3_kernel: one tile per (kx, 128 ci), the three ky share the X ring (W >= 16, pixels % 32 == 0) */
+    BD_PS_WGRAD_PHASE           /* conv_ps_wgrad_kernel in its phase form: the 16 entries of E (bd_upsample_conv_wgrad)           */
+};
+typedef struct {
+    int kernel;                 /* bd_ps_wgrad_kernel                                                                             */
+    int ntaps;                  /* 9, or 16 in the phase form                                                                     */
+    int tiles_m, tiles_n;       /* 128 x 128 output tiles: Cout / 128 and (3, 9 or 16) * Cin / 128                                */
+    int slots;                  /* workgroup slots the K split fills (two per CU; the shared-tap form: 3/4 or 1/2 of a CU each, or
+                                   the "ps_wg3_slots" knob)                                                                       */
+    int ksplit, chunks_per_split;   /* K slices and 32-pixel chunks per slice (the last slice may be shorter, never empty)        */
+    int reduce;                 /* 1: conv_ps_wgrad_reduce folds the slabs (ksplit > 1, and always in the phase form)             */
+    int grid;                   /* workgroups of the main kernel = tiles_m * tiles_n * ksplit                                     */
+    int bias_rows;              /* bias-gradient rows of Cout floats per K slice: 1, or 4 in the phase form (one per pixel class) */
+    size_t slab_floats;         /* floats per K slice: ntaps * Cin * Cout + bias_rows * Cout                                      */
+    size_t workspace_bytes;     /* = the entry point's *_workspace_bytes: ksplit slabs where reduce is set, and dE in the phase form */
+    size_t de_offset;           /* phase form: bytes in front of dE [Cout][16][Cin] (behind the slabs), else 0                    */
+    const char* prof_class;     /* the profiler class the launch is counted under                                                */
+} bd_conv3x3_ps_wgrad_plan_info;
+int bd_conv3x3_ps_wgrad_plan(const bd_conv3x3_ps_wgrad_desc* d, bd_conv3x3_ps_wgrad_plan_info* out);
 
 /* out[g, n] = sum over rows m in group g of x[m, n]  (rows_per_group rows each, the last group may be shorter); bias / temb grads.
  * BD_ERR_INVALID: null pointer, rows / N / rows_per_group <= 0, ldx or ld_out < N.  BD_ERR_UNSUPPORTED: more than 65535 groups. */
@@ -1180,6 +1227,11 @@ int bd_upsample_conv_dgrad(const bd_upsample_conv_desc* d, bd_stream_t stream);
 int bd_upsample_conv_wgrad(const bd_upsample_conv_desc* d, bd_stream_t stream);
 size_t bd_upsample_conv_wgrad_workspace_bytes(const bd_upsample_conv_desc* d);
 size_t bd_upsample_conv_dgrad_workspace_bytes(const bd_upsample_conv_desc* d);   /* 0 unless the grid is small (taps dealt to 4 workgroups per tile) */
+/* host-only queries: the plan of bd_upsample_conv_wgrad (bd_conv3x3_ps_wgrad_plan_info above), and the workgroups per tile of
+ * bd_upsample_conv_dgrad: 4 (the 16 taps dealt to four groups + a fixed-order fold, while the tiles fill at most half the chip) or 1 --
+ * what bd_upsample_conv_dgrad_workspace_bytes follows; 0 for a null descriptor */
+int bd_upsample_conv_wgrad_plan(const bd_upsample_conv_desc* d, bd_conv3x3_ps_wgrad_plan_info* out);
+int bd_upsample_conv_dgrad_tap_groups(const bd_upsample_conv_desc* d);
 
 typedef struct {
     int B, Ho, Wo, Cin, Cout, pad;              /* stride-2 conv: input grid 2Ho x 2Wo; pad 0 = F.pad(0,1,0,1) + padding 0, 1 = padding 1 */

@@ -46,7 +46,8 @@ def test_struct_layouts_match_header_sizes():
              "bd_conv3x3_ps_desc": L.ConvPsDesc, "bd_conv3x3_ps_wgrad_desc": L.ConvPsWgradDesc,
              "bd_upsample_conv_desc": L.UpsampleConvDesc, "bd_conv2d_desc": L.Conv2dDesc, "bd_conv3x3_s2_dgrad_desc": L.ConvS2DgradDesc,
              "bd_gn_plan_info": L.GnPlanInfo, "bd_igemm_plan_info": L.IgemmPlanInfo,
-             "bd_conv3x3_thin_plan_info": L.ThinPlanInfo}
+             "bd_conv3x3_thin_plan_info": L.ThinPlanInfo, "bd_conv3x3_ps_plan_info": L.ConvPsPlanInfo,
+             "bd_conv3x3_ps_wgrad_plan_info": L.ConvPsWgradPlanInfo}
     prog = '#include <stdio.h>\n#include "bd_hip.h"\nint main(){' + "".join(
         f'printf("{n} %zu\\n", sizeof({n}));' for n in names) + "return 0;}"
     import tempfile

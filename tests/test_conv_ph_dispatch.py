@@ -31,7 +31,7 @@ The two modes' references differ (asserted), so equality in BD_MODE_BF16 also sh
 Outputs go into NaN-filled buffers with a 256-row guard band; the strided variants give the output a leading dimension of N + 32 (the pad
 columns must stay NaN) and the input planes a leading dimension of C + 32 whose pad block holds a bf16 NaN pattern.
 
-The case table holds for 256 CUs; on another device the GPU tests skip.  Whoever retunes ph_tap_groups or ups_wgrad_split moves the cases with
+The case table holds for 256 CUs; on another device the GPU tests skip.  Whoever retunes upsample_conv_dgrad_tap_groups or ps_wgrad_plan moves the cases with
 it (DESIGN.md, "Dispatch branches of the phase-decomposed convolutions").
 
 Observed on MI355X (256 CUs): equality held on every case, mode, operand set and epilogue of the four entry points, on the planes of

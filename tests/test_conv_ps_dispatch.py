@@ -2,7 +2,7 @@
 
 The host code of the two entry points picks one of five kernels, a K-split count and a two- or four-stage ring from the batch, the image
 size, the channel counts and the CU count.  Each case below pins ONE of those branches -- the test asserts the (profiling class, ksplit) it
-expects, from the ABI's own queries, before it looks at a number -- and compares the result with an fp64 F.conv2d on the CPU for EQUALITY.
+expects, from the ABI's plan queries (bd_conv3x3_ps_plan, bd_conv3x3_ps_wgrad_plan), before it looks at a number -- and compares the result with an fp64 F.conv2d on the CPU for EQUALITY.
 
 Equality is possible because the operands lie on grids for which every product and every partial sum, in any order, is an fp32 number:
   * a WIDE operand is an integer in (-2048, 2048) over 2048 (about 69 % of them have a nonzero bf16 lo part, and that lo is exact in bf16);
@@ -17,8 +17,8 @@ test_operand_grids_keep_every_sum_exact (no GPU) proves the precondition for eve
 The outputs are written into a NaN-filled buffer with a guard band behind the last row: a row the ragged-tile masks forget stays NaN, a
 store past M lands in the band.
 
-The branch tables hold for 256 CUs; on another device the GPU tests skip rather than assert a stale table.  Whoever retunes ps_large,
-ps_ws or ps_wgrad_ws moves the cases with it ("Dispatch branches of the split-plane convolutions").
+The branch tables hold for 256 CUs; on another device the GPU tests skip rather than assert a stale table.  Whoever retunes ps_plan or
+ps_wgrad_plan moves the cases with it ("Dispatch branches of the split-plane convolutions").
 
 Observed on MI355X (256 CUs): equality holds on the anchor cases the older tests already cover (P10, W6) and on every other case, both modes,
 both operand sets, every epilogue -- the bf16 MFMA's fp32 accumulation is exact when every partial sum is representable, so the tests assert
@@ -239,13 +239,14 @@ def test_conv_ps_branch_is_exact(ops, cid, direction, opset):
     lib = L.load()
     B, H, W, K, N, _, large, kernel, ksplit, _ = FWD_CASES[cid]
     M = B * H * W
-    # ---- the branch, before anything is launched
+    # ---- the branch, before anything is launched: what the launcher's own plan says
+    plan = ops.conv3x3_ps_plan(B, H, W, K, N, direction, mode=BF16X3)
     d = L.ConvPsDesc(B=B, H=H, W=W, K=K, N=N, direction=direction, mode=BF16X3)
-    wsb = lib.bd_conv3x3_ps_workspace_bytes(ctypes.byref(d))
-    assert wsb % (4 * M * N) == 0 and (wsb // (4 * M * N) or 1) == ksplit, (cid, wsb, ksplit)
-    shared_tap = W >= 16 and (H * min(W, 32)) % 256 == 0 and M % 256 == 0     # the dispatch rule of conv_ps3_kernel among the large layers
-    assert kernel == ("conv_ps128" if not large else "conv_ps3" if shared_tap else "conv_ps")
+    assert plan["ksplit"] == ksplit and plan["workspace_bytes"] == lib.bd_conv3x3_ps_workspace_bytes(ctypes.byref(d)), (cid, plan)
+    assert kernel == {L.PS_128: "conv_ps128", L.PS_256_SHARED_TAP: "conv_ps3", L.PS_256: "conv_ps"}[plan["kernel"]], (cid, plan)
+    assert large == (plan["kernel"] != L.PS_128), (cid, plan)
     cls = ("conv_ps" if large else "conv_ps128") + ("_fwd" if direction > 0 else "_dgrad")
+    assert plan["prof_class"] == cls, (cid, plan)
 
     o = fwd_operands(cid, direction, opset)
     dev = {k: v.cuda() for k, v in o.items()}
@@ -283,12 +284,12 @@ def test_conv_ps_wgrad_branch_is_exact(ops, cid, opset):
     from baddiffusion_amd import _lib as L
     lib = L.load()
     B, H, W, Cin, Cout, strip, ksplit, _ = WGRAD_CASES[cid]
+    plan = ops.conv3x3_ps_wgrad_plan(B, H, W, Cin, Cout, mode=BF16X3)              # the branch, before anything is launched
     d = L.ConvPsWgradDesc(B=B, H=H, W=W, Cin=Cin, Cout=Cout, mode=BF16X3)
-    wsb = lib.bd_conv3x3_ps_wgrad_workspace_bytes(ctypes.byref(d))
-    slab = 4 * (9 * Cin * Cout + Cout)
-    assert wsb % slab == 0 and (wsb // slab or 1) == ksplit, (cid, wsb, ksplit)
-    assert strip == (W >= 16 and (B * H * W) % 32 == 0)                         # the dispatch rule of conv_ps_wgrad3_kernel
+    assert plan["ksplit"] == ksplit and plan["workspace_bytes"] == lib.bd_conv3x3_ps_wgrad_workspace_bytes(ctypes.byref(d)), (cid, plan)
+    assert strip == (plan["kernel"] == L.PS_WGRAD_SHARED_TAP), (cid, plan)
     cls = "conv_ps_wgrad3" if strip else "conv_ps_wgrad"
+    assert plan["prof_class"] == cls, (cid, plan)
 
     o = wgrad_operands(cid, opset)
     xs, dys = ops.split_rows(o["x"].cuda()), ops.split_rows(o["dy"].cuda())

@@ -26,12 +26,12 @@ P(nonzero) = 3/8, bias and row bias integers in [-2, 2], residual a multiple of 
 (row bias form) or 1/8 (residual form), and test_gn_data_keeps_every_partial_exact proves sum |y| / u < 2^24 and sum (y / u)^2 < 2^24 per
 (sample, tile, group) -- every term of the second sum is non-negative, so the total bounds every partial sum.
 
-The branch of every case is asserted from the ABI's own queries before anything is launched: bd_conv3x3_ps_workspace_bytes (the K split)
-and bd_conv3x3_ps_gn_splits(B, H, W, K, N, N / 4) == H W / 256, the one query that answers "does conv_ps3_kernel take this shape"; for the
-weight gradient bd_conv3x3_ps_wgrad_workspace_bytes and the profiling class (conv_ps_wgrad3 against conv_ps_wgrad).  The tables are
-derived by hand from ps_large, ps_takes_v3, ps_ws, ps_wgrad_ws and split_k at 256 CUs (K-split slots of the strip-order weight gradient:
-192 for W <= 32, 128 for W > 32; at least 8 chunks per slice; tiles = Cout/128 * 3 Cin/128); on another device the GPU tests skip.  Whoever
-retunes those functions moves the cases with them ("Dispatch branches of the split-plane convolutions").
+The branch of every case is asserted from the ABI's plan queries before anything is launched: bd_conv3x3_ps_plan (kernel, K split, and
+gn_splits, which bd_conv3x3_ps_gn_splits repeats) and bd_conv3x3_ps_wgrad_plan (kernel, K split, chunks per slice); the profiling class
+behind the launch shows that the launcher ran what the plan said.  The tables are derived by hand from ps_plan, ps_wgrad_plan and split_k
+at 256 CUs (K-split slots of the strip-order weight gradient: 192 for W <= 32, 128 for W > 32; at least 8 chunks per slice; tiles =
+Cout/128 * 3 Cin/128); on another device the GPU tests skip.  Whoever retunes those functions moves the cases with them (DESIGN.md,
+"Dispatch branches of the split-plane convolutions").
 
 Observed on MI355X (256 CUs): see DESIGN.md, same paragraph."""
 import ctypes
@@ -53,8 +53,8 @@ GUARD = PH.GUARD
 OK, ERR_INVALID, ERR_UNSUPPORTED = 0, -1, -2
 cdiv = lambda a, b: -(-a // b)
 
-# id: (B, H, W, K, N, directions, kernel, ksplit, what the case is there for).  V1 .. S4: M = 24576 is the smallest that makes ps_large
-# true (96 tiles of 256 x 128)
+# id: (B, H, W, K, N, directions, kernel, ksplit, what the case is there for).  V1 .. S4: M = 24576 is the smallest large layer
+# (96 tiles of 256 x 128)
 FWD_CASES = {
     "V1": (24, 32, 32, 32, 128, (1, -1), "conv_ps3", 1, "W = 32: the 320-row window; 3 groups: the loop leaves after its first half; 4 tiles per image: top, two interior, bottom"),
     "V2": (8, 32, 32, 96, 384, (1,), "conv_ps3", 1, "9 groups (odd, more than one trip); three N tiles in the XCD order"),
@@ -175,38 +175,37 @@ def tile_sums(y, G):
 
 
 # ------------------------------------------------------------------------------------------------ the tables, from the ABI (no GPU)
-def fwd_branch(lib, L, shape):
-    """(ksplit, strip-order tiles per image or 0) of a forward / data-gradient shape from bd_conv3x3_ps_workspace_bytes and
-    bd_conv3x3_ps_gn_splits at 4 channels per group"""
+def plan_of(lib, L, fn, d, info):
+    L.check(getattr(lib, fn)(ctypes.byref(d), ctypes.byref(info)), fn)
+    return info
+
+
+def fwd_plan(lib, L, shape, gn_groups=0):
+    """bd_conv3x3_ps_plan of a dense forward call of the shape"""
     B, H, W, K, N = shape
-    M = B * H * W
-    d = L.ConvPsDesc(B=B, H=H, W=W, K=K, N=N, direction=1, mode=BF16X3)
-    wsb = lib.bd_conv3x3_ps_workspace_bytes(ctypes.byref(d))
-    assert wsb % (4 * M * N) == 0, (shape, wsb)
-    return wsb // (4 * M * N) or 1, lib.bd_conv3x3_ps_gn_splits(B, H, W, K, N, N // 4)
+    return plan_of(lib, L, "bd_conv3x3_ps_plan", L.ConvPsDesc(B=B, H=H, W=W, K=K, N=N, direction=1, ldx=K, ldy=N, gn_groups=gn_groups, mode=BF16X3),
+                   L.ConvPsPlanInfo())
 
 
 def assert_fwd_branch(lib, L, cid):
     B, H, W, K, N, _, kernel, ksplit, _ = FWD_CASES[cid]
-    ks, v3_tiles = fwd_branch(lib, L, (B, H, W, K, N))
-    assert ks == ksplit, (cid, ks)
-    assert v3_tiles == (H * W // 256 if kernel == "conv_ps3" else 0), (cid, v3_tiles)
-    large = cdiv(B * H * W, 256) * (N // 128) >= 96                      # ps_large, restated; the profiling class confirms it at the launch
-    assert (kernel != "conv_ps128") == large, cid
-    return ("conv_ps" if large else "conv_ps128")
+    p = fwd_plan(lib, L, (B, H, W, K, N), gn_groups=N // 4)
+    assert p.ksplit == ksplit, (cid, p.ksplit)
+    assert kernel == {L.PS_128: "conv_ps128", L.PS_256_SHARED_TAP: "conv_ps3", L.PS_256: "conv_ps"}[p.kernel], (cid, p.kernel)
+    # the GroupNorm partials at 4 channels per group: one split per virtual tile exactly where conv_ps3_kernel runs; the older query repeats it
+    assert p.gn_splits == lib.bd_conv3x3_ps_gn_splits(B, H, W, K, N, N // 4) == (H * W // 256 if kernel == "conv_ps3" else 0), (cid, p.gn_splits)
+    cls = "conv_ps128" if p.kernel == L.PS_128 else "conv_ps"                # the profiling class confirms it at the launch
+    assert p.prof_class.decode() == cls + "_fwd", (cid, p.prof_class)
+    return cls
 
 
 def wgrad_split(lib, L, shape):
-    """(ksplit, chunks per slice, chunks of the last slice) from bd_conv3x3_ps_wgrad_workspace_bytes: slabs of 9 Cin Cout + Cout floats"""
+    """(ksplit, chunks per slice, chunks of the last slice) from bd_conv3x3_ps_wgrad_plan; the kernel must be conv_ps_wgrad3_kernel"""
     B, H, W, Cin, Cout = shape
-    d = L.ConvPsWgradDesc(B=B, H=H, W=W, Cin=Cin, Cout=Cout, mode=BF16X3)
-    wsb = lib.bd_conv3x3_ps_wgrad_workspace_bytes(ctypes.byref(d))
-    slab = 4 * (9 * Cin * Cout + Cout)
-    assert wsb % slab == 0, (shape, wsb)
-    ks = wsb // slab or 1
-    nch = cdiv(B * H * W, 32)
-    cps = cdiv(nch, ks)
-    return ks, cps, nch - (ks - 1) * cps
+    p = plan_of(lib, L, "bd_conv3x3_ps_wgrad_plan", L.ConvPsWgradDesc(B=B, H=H, W=W, Cin=Cin, Cout=Cout, ldx=Cin, lddy=Cout, mode=BF16X3),
+                L.ConvPsWgradPlanInfo())
+    assert p.kernel == L.PS_WGRAD_SHARED_TAP and p.prof_class == b"conv_ps_wgrad3", (shape, p.kernel, p.prof_class)
+    return p.ksplit, p.chunks_per_split, cdiv(B * H * W, 32) - (p.ksplit - 1) * p.chunks_per_split
 
 
 def test_case_tables_follow_the_dispatch_rules():
@@ -221,9 +220,7 @@ def test_case_tables_follow_the_dispatch_rules():
     assert (18, 5) == (9 * FWD_CASES["O1"][3] // 32, cdiv(18, 4))                 # O1: 5 + 5 + 5 + 3 chunks, <= 9 per slice: the four-stage ring
     assert FWD_CASES["O2"][1] * 32 % 256 != 0
     for cid, c in WGRAD_CASES.items():
-        B, H, W = c[:3]
-        assert wgrad_split(lib, L, c[:5]) == c[5:8], (cid, wgrad_split(lib, L, c[:5]))
-        assert W >= 16 and (B * H * W) % 32 == 0, cid                               # the dispatch rule of conv_ps_wgrad3_kernel
+        assert wgrad_split(lib, L, c[:5]) == c[5:8], (cid, wgrad_split(lib, L, c[:5]))   # (on conv_ps_wgrad3_kernel: wgrad_split asserts it)
     # the GroupNorm partials: one split per virtual tile where conv_ps3_kernel runs and the group is 4 .. 32 channels, else none
     q = lib.bd_conv3x3_ps_gn_splits
     for cid, (B, H, W, K, N, groups) in GN_CASES.items():
