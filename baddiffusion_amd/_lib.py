@@ -235,6 +235,13 @@ class GemmSpDesc(C.Structure):
                 ("mode", i32)]
 
 
+class GemmSpPlanInfo(C.Structure):
+    """bd_gemm_sp_plan_info; form is 2 * a_kmajor + b_kmajor, prof_class a C string"""
+    _fields_ = [("form", i32), ("tiles_m", i32), ("tiles_n", i32), ("batch", i32), ("ksplit", i32), ("chunks_per_split", i32),
+                ("reduce", i32), ("colsum_reduce", i32), ("grid", i64), ("workspace_bytes", sz), ("colsum_offset", sz),
+                ("prof_class", C.c_char_p)]
+
+
 class AttnSpDesc(C.Structure):
     _fields_ = [("B", i32), ("heads", i32), ("N", i32), ("dh", i32), ("qkv_split", vp), ("ld", i64), ("scale", f32), ("o_split", vp),
                 ("ldo", i64), ("pt_split", vp), ("do_split", vp), ("lddo", i64), ("dst_split", vp), ("dqkv_split", vp), ("lddqkv", i64),
@@ -365,6 +372,7 @@ SIGNATURES = {
     "bd_conv3x3_s2_dgrad_ps": (i32, [C.POINTER(ConvS2DgradDesc), vp]),
     "bd_gemm_sp_workspace_bytes": (sz, [C.POINTER(GemmSpDesc)]),
     "bd_gemm_sp": (i32, [C.POINTER(GemmSpDesc), vp]),
+    "bd_gemm_sp_plan": (i32, [C.POINTER(GemmSpDesc), C.POINTER(GemmSpPlanInfo)]),
     "bd_attn_sp_supported": (i32, [i32, i32]),
     "bd_attn_sp_fwd": (i32, [C.POINTER(AttnSpDesc), vp]),
     "bd_attn_sp_bwd": (i32, [C.POINTER(AttnSpDesc), vp]),

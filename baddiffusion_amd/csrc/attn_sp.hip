@@ -562,34 +562,46 @@ bool attn_sp_supported(int N, int dh) {
     return !off && N == AS_N && dh == 256;
 }
 
+// what is wrong with split planes of `cols` columns (the [N, N] matrices have no stride of their own): each entry point reports these in its own order
+enum { AS_NULL = 1, AS_LD = 2, AS_ALIGN = 4 };
+static int as_bad(const void* base, int64_t ld = 0, int cols = 0) {
+    return (base ? 0 : AS_NULL) | (ld >= cols && ld % 32 == 0 ? 0 : AS_LD) | (((uintptr_t)base & 127) == 0 ? 0 : AS_ALIGN);
+}
+
 static int attn_sp_common(const bd_attn_sp_desc& d, const char* who, AsParams& p) {
     BD_CHECK(d.B > 0 && d.heads > 0 && attn_sp_supported(d.N, d.dh), BD_ERR_UNSUPPORTED, "%s: needs N == 256 and head dim 256 (got N %d, dh %d)", who,
              d.N, d.dh);
-    const int C = d.heads * d.dh;
-    BD_CHECK(d.qkv_split && d.ld >= 3 * C && d.ld % 32 == 0 && ((uintptr_t)d.qkv_split & 127) == 0, BD_ERR_INVALID,
-             "%s: qkv planes must be 128-byte aligned with a row stride >= 3C, multiple of 32", who);
-    BD_CHECK(sp_mode_valid(d.mode), BD_ERR_INVALID, "%s: unknown compute mode %d", who, d.mode);
     p = {};
-    p.qkv = reinterpret_cast<const char*>(d.qkv_split); p.ld = d.ld * 4;
-    p.C = C; p.dh = d.dh; p.heads = d.heads; p.scale = d.scale;
+    p.C = d.heads * d.dh; p.dh = d.dh; p.heads = d.heads; p.scale = d.scale;
+    BD_CHECK(!as_bad(d.qkv_split, d.ld, 3 * p.C), BD_ERR_INVALID, "%s: qkv planes must be 128-byte aligned with a row stride >= 3C, multiple of 32", who);
+    BD_CHECK(sp_mode_valid(d.mode), BD_ERR_INVALID, "%s: unknown compute mode %d", who, d.mode);
+    p.qkv = reinterpret_cast<const char*>(d.qkv_split); p.ld = d.ld * 4; p.pt = reinterpret_cast<char*>(d.pt_split);
     return BD_OK;
+}
+
+// One of the three launches, opened in the profiler (the record to close, or -1).  bench.py roofline: each takes two [N, N] x dh products per head
+// (4 B N^2 dh flop) and moves four [N, dh] blocks and its [N, N] plane matrices -- forward: q, k, v in, o (+ P^T for training) out; A (dP = dO V^T,
+// dQ = dS K): k, v, dO, P^T in, dq, dS^T out; B (dV = P^T dO, dK = dS^T Q): P^T, dS^T, dO, q in, dk, dv out
+enum { AS_FWD, AS_BWD_A, AS_BWD_B };
+static int as_launch(int which, const bd_attn_sp_desc& d, const AsParams& p, hipStream_t st) {
+    static constexpr void (*fwd[2][2])(AsParams) = {{attn_sp_fwd_kernel<false, false>, attn_sp_fwd_kernel<false, true>},      // [write P^T][single pass]
+                                                    {attn_sp_fwd_kernel<true, false>, attn_sp_fwd_kernel<true, true>}};
+    static constexpr void (*bwd[2][2])(AsParams) = {{attn_sp_bwd_a_kernel<false>, attn_sp_bwd_a_kernel<true>}, {attn_sp_bwd_b_kernel<false>, attn_sp_bwd_b_kernel<true>}};
+    static const char* kClass[3][2] = {{"attn_sp_fwd", "attn_sp_fwd_bf16"}, {"attn_sp_bwd_a", "attn_sp_bwd_a_bf16"}, {"attn_sp_bwd_b", "attn_sp_bwd_b_bf16"}};
+    const bool sp = d.mode == BD_MODE_BF16, write_p = d.pt_split != nullptr;
+    const double bh = (double)d.B * d.heads, nn = (double)d.N * d.N, nd = (double)d.N * d.dh, matrices = which != AS_FWD ? 2.0 : write_p ? 1.0 : 0.0;
+    const int rec = prof_on() ? prof_begin(kClass[which][sp], 4.0 * bh * nn * d.dh, 4.0 * bh * (4.0 * nd + matrices * nn), st) : -1;
+    hipLaunchKernelGGL(which == AS_FWD ? fwd[write_p][sp] : bwd[which - AS_BWD_A][sp], dim3((unsigned)(d.B * d.heads * 2)), dim3(AS_NT), 0, st, p);
+    return rec;
 }
 
 int attn_sp_fwd(const bd_attn_sp_desc& d, hipStream_t st) {
     AsParams p;
     BD_TRY(attn_sp_common(d, "bd_attn_sp_fwd", p));
-    BD_CHECK(d.o_split && d.ldo >= p.C && d.ldo % 32 == 0 && ((uintptr_t)d.o_split & 127) == 0, BD_ERR_INVALID, "bd_attn_sp_fwd: bad output planes");
-    BD_CHECK(((uintptr_t)d.pt_split & 127) == 0, BD_ERR_INVALID, "bd_attn_sp_fwd: P^T planes must be 128-byte aligned");
-    p.o = reinterpret_cast<char*>(d.o_split); p.ldo = d.ldo * 4; p.pt = reinterpret_cast<char*>(d.pt_split);
-    const dim3 grid((unsigned)(d.B * d.heads * 2));
-    // bench.py roofline: S = Q K^T and O = P V (4 B N^2 dh flop per head); bytes = q, k, v in, o (+ P^T for training) out
-    const double bh = (double)d.B * d.heads, nn = (double)d.N * d.N, nd = (double)d.N * d.dh;
-    const bool sp = d.mode == BD_MODE_BF16;
-    const int rec = prof_on() ? prof_begin(sp ? "attn_sp_fwd_bf16" : "attn_sp_fwd", 4.0 * bh * nn * d.dh, 4.0 * bh * (4.0 * nd + (d.pt_split ? nn : 0.0)), st) : -1;
-    if (d.pt_split && sp) hipLaunchKernelGGL((attn_sp_fwd_kernel<true, true>), grid, dim3(AS_NT), 0, st, p);
-    else if (d.pt_split) hipLaunchKernelGGL((attn_sp_fwd_kernel<true, false>), grid, dim3(AS_NT), 0, st, p);
-    else if (sp) hipLaunchKernelGGL((attn_sp_fwd_kernel<false, true>), grid, dim3(AS_NT), 0, st, p);
-    else hipLaunchKernelGGL((attn_sp_fwd_kernel<false, false>), grid, dim3(AS_NT), 0, st, p);
+    BD_CHECK(!as_bad(d.o_split, d.ldo, p.C), BD_ERR_INVALID, "bd_attn_sp_fwd: bad output planes");
+    BD_CHECK(!(as_bad(d.pt_split) & AS_ALIGN), BD_ERR_INVALID, "bd_attn_sp_fwd: P^T planes must be 128-byte aligned");
+    p.o = reinterpret_cast<char*>(d.o_split); p.ldo = d.ldo * 4;
+    const int rec = as_launch(AS_FWD, d, p, st);
     BD_LAUNCH_CHECK("attn_sp_fwd");
     prof_end(rec, st);
     return BD_OK;
@@ -598,27 +610,14 @@ int attn_sp_fwd(const bd_attn_sp_desc& d, hipStream_t st) {
 int attn_sp_bwd(const bd_attn_sp_desc& d, hipStream_t st) {
     AsParams p;
     BD_TRY(attn_sp_common(d, "bd_attn_sp_bwd", p));
-    BD_CHECK(d.pt_split && d.do_split && d.dst_split && d.dqkv_split, BD_ERR_INVALID, "bd_attn_sp_bwd: null pointer");
-    BD_CHECK(d.lddo >= p.C && d.lddo % 32 == 0 && d.lddqkv >= 3 * p.C && d.lddqkv % 32 == 0, BD_ERR_INVALID, "bd_attn_sp_bwd: bad row strides");
-    BD_CHECK((((uintptr_t)d.pt_split | (uintptr_t)d.do_split | (uintptr_t)d.dst_split | (uintptr_t)d.dqkv_split) & 127) == 0, BD_ERR_INVALID,
-             "bd_attn_sp_bwd: planes must be 128-byte aligned");
-    p.pt = reinterpret_cast<char*>(const_cast<uint16_t*>(d.pt_split));
-    p.dO = reinterpret_cast<const char*>(d.do_split); p.lddo = d.lddo * 4;
-    p.dst = reinterpret_cast<char*>(d.dst_split);
+    const int bad = as_bad(d.pt_split) | as_bad(d.do_split, d.lddo, p.C) | as_bad(d.dst_split) | as_bad(d.dqkv_split, d.lddqkv, 3 * p.C);
+    BD_CHECK(!(bad & AS_NULL), BD_ERR_INVALID, "bd_attn_sp_bwd: null pointer");
+    BD_CHECK(!(bad & AS_LD), BD_ERR_INVALID, "bd_attn_sp_bwd: bad row strides");
+    BD_CHECK(!(bad & AS_ALIGN), BD_ERR_INVALID, "bd_attn_sp_bwd: planes must be 128-byte aligned");
+    p.dO = reinterpret_cast<const char*>(d.do_split); p.lddo = d.lddo * 4; p.dst = reinterpret_cast<char*>(d.dst_split);
     p.dqkv = reinterpret_cast<char*>(d.dqkv_split); p.lddqkv = d.lddqkv * 4;
-    const dim3 grid((unsigned)(d.B * d.heads * 2));
-    // bench.py roofline.  A: dP = dO V^T, dQ = dS K (4 B N^2 dh flop per head; reads k, v, dO, P^T; writes dq, dS^T).
-    // B: dV = P^T dO, dK = dS^T Q (same flops; reads P^T, dS^T, dO, q; writes dk, dv).
-    const double bh = (double)d.B * d.heads, nn = (double)d.N * d.N, nd = (double)d.N * d.dh;
-    const bool sp = d.mode == BD_MODE_BF16;
-    int rec = prof_on() ? prof_begin(sp ? "attn_sp_bwd_a_bf16" : "attn_sp_bwd_a", 4.0 * bh * nn * d.dh, 4.0 * bh * (4.0 * nd + 2.0 * nn), st) : -1;
-    if (sp) hipLaunchKernelGGL(attn_sp_bwd_a_kernel<true>, grid, dim3(AS_NT), 0, st, p);
-    else hipLaunchKernelGGL(attn_sp_bwd_a_kernel<false>, grid, dim3(AS_NT), 0, st, p);
-    prof_end(rec, st);
-    rec = prof_on() ? prof_begin(sp ? "attn_sp_bwd_b_bf16" : "attn_sp_bwd_b", 4.0 * bh * nn * d.dh, 4.0 * bh * (4.0 * nd + 2.0 * nn), st) : -1;
-    if (sp) hipLaunchKernelGGL(attn_sp_bwd_b_kernel<true>, grid, dim3(AS_NT), 0, st, p);
-    else hipLaunchKernelGGL(attn_sp_bwd_b_kernel<false>, grid, dim3(AS_NT), 0, st, p);
-    prof_end(rec, st);
+    prof_end(as_launch(AS_BWD_A, d, p, st), st);
+    prof_end(as_launch(AS_BWD_B, d, p, st), st);
     BD_LAUNCH_CHECK("attn_sp_bwd");
     return BD_OK;
 }

@@ -370,52 +370,75 @@ __global__ __launch_bounds__(64) void gemm_sp_colsum_reduce(const float* __restr
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------
-// K split and workspace of one supported call (gemm_sp_supported): what bd_gemm_sp_workspace_bytes answers and what the launcher checks
-// and hands the kernels.  ksplit slabs of M x N floats, then at colsum_off the ksplit partial rows of the a_colsum bias gradient
-struct SpWs { int ksplit, cps; size_t bytes, colsum_off; };
-static SpWs sp_ws(const bd_gemm_sp_desc& d) {
-    SpWs s = {1, 0, 0, 0};
-    const int nch = d.K / 32;
-    const long long tiles = (long long)(d.M / SP_T) * (d.N / SP_T) * (d.batch > 0 ? d.batch : 1);
-    if (d.batch <= 1 && tiles < device_cus() && nch >= 32) {   // one workgroup per CU: the slabs are written and read once more each
-        s.ksplit = (int)cdiv(device_cus(), tiles);
-        if (s.ksplit > nch / 8) s.ksplit = nch / 8;
-    }
-    if (s.ksplit < 1) s.ksplit = 1;
-    s.cps = (int)cdiv(nch, s.ksplit);
-    s.ksplit = (int)cdiv(nch, s.cps);
-    if (s.ksplit > 1) {
-        s.colsum_off = (size_t)s.ksplit * ((size_t)d.M * d.N) * sizeof(float);
-        s.bytes = s.colsum_off + (size_t)s.ksplit * d.M * sizeof(float);
-    }
-    return s;
-}
-
+static bool sp_shape_ok(int M, int N, int K) { return M > 0 && N > 0 && K > 0 && M % SP_T == 0 && N % SP_T == 0 && K % 32 == 0; }
 bool gemm_sp_supported(int M, int N, int K) {
     static const bool off = getenv("BD_GEMM_SP") && atoi(getenv("BD_GEMM_SP")) == 0;
-    return !off && M > 0 && N > 0 && K > 0 && M % SP_T == 0 && N % SP_T == 0 && K % 32 == 0;
+    return !off && sp_shape_ok(M, N, K);
 }
 
-size_t gemm_sp_workspace_bytes(const bd_gemm_sp_desc& d) { return gemm_sp_supported(d.M, d.N, d.K) ? sp_ws(d).bytes : 0; }
+// Everything bd_gemm_sp decides from a descriptor's numbers, decided once: the launcher, bd_gemm_sp_workspace_bytes and bd_gemm_sp_plan read
+// it.  Pure host arithmetic.  grid 0, nothing else set: a shape sp_check refuses.  The workspace of a split call: ksplit slabs of M x N
+// floats, then at colsum_offset the ksplit partial rows of the a_colsum bias gradient.
+typedef bd_gemm_sp_plan_info SpPlan;
+static SpPlan sp_plan(const bd_gemm_sp_desc& d) {
+    static const char* kName[2][4] = {{"gemm_sp_nt", "gemm_sp_nn", "gemm_sp_tn_a", "gemm_sp_tn"},
+                                      {"gemm_sp_nt_bf16", "gemm_sp_nn_bf16", "gemm_sp_tn_a_bf16", "gemm_sp_tn_bf16"}};
+    SpPlan p = {};
+    if (!sp_shape_ok(d.M, d.N, d.K)) return p;
+    p.form = (d.a_kmajor ? 2 : 0) + (d.b_kmajor ? 1 : 0);
+    p.prof_class = kName[d.mode == BD_MODE_BF16][p.form];
+    p.tiles_m = d.M / SP_T; p.tiles_n = d.N / SP_T; p.batch = d.batch > 0 ? d.batch : 1;
+    const int nch = d.K / 32;
+    const long long tiles = (long long)p.tiles_m * p.tiles_n * p.batch;
+    p.ksplit = 1;
+    // one workgroup per CU: the slabs are written and read once more each.  CUs / tiles rounded UP (split_k of common.h rounds down)
+    if (d.batch <= 1 && tiles < device_cus() && nch >= 32) {
+        p.ksplit = (int)cdiv(device_cus(), tiles);
+        if (p.ksplit > nch / 8) p.ksplit = nch / 8;
+    }
+    p.chunks_per_split = (int)cdiv(nch, p.ksplit);
+    p.ksplit = (int)cdiv(nch, p.chunks_per_split);      // no empty slice
+    p.grid = tiles * p.ksplit;
+    p.reduce = p.ksplit > 1; p.colsum_reduce = p.reduce && d.a_colsum;
+    if (p.reduce) {
+        p.colsum_offset = (size_t)p.ksplit * ((size_t)d.M * d.N) * sizeof(float);
+        p.workspace_bytes = p.colsum_offset + (size_t)p.ksplit * d.M * sizeof(float);
+    }
+    return p;
+}
+size_t gemm_sp_workspace_bytes(const bd_gemm_sp_desc& d) { return gemm_sp_supported(d.M, d.N, d.K) ? sp_plan(d).workspace_bytes : 0; }
 
-int gemm_sp(const bd_gemm_sp_desc& d, hipStream_t st) {
-    BD_CHECK(d.a && d.b && (d.c || d.c_split), BD_ERR_INVALID, "bd_gemm_sp: null pointer");
+// Every host check of bd_gemm_sp, in the order the entry point has always reported them (the pointer checks sit between the checks of the
+// numbers, so one list keeps the order).  `launch` false -- bd_gemm_sp_plan -- skips the null-pointer, base-alignment and workspace checks:
+// the launcher's own.
+static int sp_check(const bd_gemm_sp_desc& d, const SpPlan& pl, bool launch) {
+    const auto al = [launch](const void* p) { return !launch || ((uintptr_t)p & 127) == 0; };
+    BD_CHECK(!launch || (d.a && d.b && (d.c || d.c_split)), BD_ERR_INVALID, "bd_gemm_sp: null pointer");
     BD_CHECK(sp_mode_valid(d.mode), BD_ERR_INVALID, "bd_gemm_sp: unknown compute mode %d", d.mode);
-    const bool sp = d.mode == BD_MODE_BF16;   // single pass: hi*hi only
-    BD_CHECK(d.M > 0 && d.N > 0 && d.K > 0 && d.M % SP_T == 0 && d.N % SP_T == 0 && d.K % 32 == 0, BD_ERR_UNSUPPORTED,
-             "bd_gemm_sp: needs M, N %% 128 == 0 and K %% 32 == 0 (M=%d N=%d K=%d)", d.M, d.N, d.K);
-    const int batch = d.batch > 0 ? d.batch : 1;
-    BD_CHECK(((uintptr_t)d.a & 127) == 0 && ((uintptr_t)d.b & 127) == 0 && d.lda % 32 == 0 && d.ldb % 32 == 0 && d.a_bs % 32 == 0 &&
-                 d.b_bs % 32 == 0,
-             BD_ERR_UNSUPPORTED, "bd_gemm_sp: operand planes must be 128-byte aligned with row / batch strides multiples of 32");
+    BD_CHECK(sp_shape_ok(d.M, d.N, d.K), BD_ERR_UNSUPPORTED, "bd_gemm_sp: needs M, N %% 128 == 0 and K %% 32 == 0 (M=%d N=%d K=%d)", d.M, d.N, d.K);
+    BD_CHECK(al(d.a) && al(d.b) && d.lda % 32 == 0 && d.ldb % 32 == 0 && d.a_bs % 32 == 0 && d.b_bs % 32 == 0, BD_ERR_UNSUPPORTED,
+             "bd_gemm_sp: operand planes must be 128-byte aligned with row / batch strides multiples of 32");
     BD_CHECK(d.lda >= (d.a_kmajor ? d.M : d.K) && d.ldb >= (d.b_kmajor ? d.N : d.K), BD_ERR_INVALID, "bd_gemm_sp: row stride below the row length");
-    BD_CHECK(!d.c_split || (((uintptr_t)d.c_split & 127) == 0 && d.ldcs % 32 == 0 && d.cs_bs % 32 == 0 && d.ldcs >= d.N), BD_ERR_UNSUPPORTED,
+    BD_CHECK(!d.c_split || (al(d.c_split) && d.ldcs % 32 == 0 && d.cs_bs % 32 == 0 && d.ldcs >= d.N), BD_ERR_UNSUPPORTED,
              "bd_gemm_sp: split output must be 128-byte aligned with strides multiples of 32");
     BD_CHECK(!d.c || d.ldc >= d.N, BD_ERR_INVALID, "bd_gemm_sp: ldc < N");
     BD_CHECK(!d.accumulate || d.c, BD_ERR_INVALID, "bd_gemm_sp: accumulate needs the fp32 output");
     BD_CHECK(!d.residual || d.ldr >= d.N, BD_ERR_INVALID, "bd_gemm_sp: ldr < N");
-    BD_CHECK(!d.a_colsum || (d.a_kmajor && d.b_kmajor && batch == 1), BD_ERR_UNSUPPORTED,
+    BD_CHECK(!d.a_colsum || (d.a_kmajor && d.b_kmajor && pl.batch == 1), BD_ERR_UNSUPPORTED,
              "bd_gemm_sp: a_colsum needs both operands K-major and no batch");
+    BD_CHECK(!launch || !pl.reduce || (d.workspace && d.workspace_bytes >= pl.workspace_bytes), BD_ERR_WORKSPACE,
+             "bd_gemm_sp: workspace %zu < %zu", d.workspace_bytes, pl.workspace_bytes);
+    BD_CHECK(pl.grid < (1ll << 31), BD_ERR_UNSUPPORTED, "bd_gemm_sp: grid too large");
+    return BD_OK;
+}
+
+int gemm_sp(const bd_gemm_sp_desc& d, hipStream_t st) {
+    // [mode == BD_MODE_BF16 (single pass: hi*hi only)][a_kmajor][b_kmajor]
+    static constexpr void (*kernels[2][2][2])(SpParams) = {
+        {{gemm_sp_kernel<false, false, false>, gemm_sp_kernel<false, true, false>}, {gemm_sp_kernel<true, false, false>, gemm_sp_kernel<true, true, false>}},
+        {{gemm_sp_kernel<false, false, true>, gemm_sp_kernel<false, true, true>}, {gemm_sp_kernel<true, false, true>, gemm_sp_kernel<true, true, true>}}};
+    const SpPlan pl = sp_plan(d);
+    BD_TRY(sp_check(d, pl, true));
     SpParams p = {};
     p.a = reinterpret_cast<const char*>(d.a); p.b = reinterpret_cast<const char*>(d.b);
     p.lda = d.lda * 4; p.ldb = d.ldb * 4; p.a_bs = d.a_bs * 4; p.b_bs = d.b_bs * 4;
@@ -423,44 +446,23 @@ int gemm_sp(const bd_gemm_sp_desc& d, hipStream_t st) {
     p.cs = reinterpret_cast<char*>(d.c_split); p.ldcs = d.ldcs * 4; p.cs_bs = d.cs_bs * 4;
     p.bias = d.bias; p.res = d.residual; p.ldr = d.ldr; p.r_bs = d.r_bs;
     p.alpha = d.alpha; p.out_scale = d.out_scale; p.accumulate = d.accumulate;
-    p.M = d.M; p.N = d.N; p.K = d.K; p.tiles_m = d.M / SP_T; p.tiles_n = d.N / SP_T; p.batch = batch;
+    p.M = d.M; p.N = d.N; p.K = d.K; p.tiles_m = pl.tiles_m; p.tiles_n = pl.tiles_n; p.batch = pl.batch;
     p.colsum = d.a_colsum; p.want_colsum = d.a_colsum != nullptr;
-    const SpWs ws = sp_ws(d);
-    p.ksplit = ws.ksplit; p.cps = ws.cps;
-    if (p.ksplit > 1) {
-        BD_CHECK(d.workspace && d.workspace_bytes >= ws.bytes, BD_ERR_WORKSPACE, "bd_gemm_sp: workspace %zu < %zu", d.workspace_bytes, ws.bytes);
-        p.partial = reinterpret_cast<float*>(d.workspace);
-    }
-    const long long grid = (long long)p.tiles_m * p.tiles_n * batch * p.ksplit;
-    BD_CHECK(grid < (1ll << 31), BD_ERR_UNSUPPORTED, "bd_gemm_sp: grid too large");
-    const dim3 g((unsigned)grid), b(SP_NT);
+    p.ksplit = pl.ksplit; p.cps = pl.chunks_per_split;
+    if (pl.reduce) p.partial = reinterpret_cast<float*>(d.workspace);
     int rec = -1;
     if (prof_on()) {   // bench.py roofline: algorithmic flops, unique operand + output bytes (planes are 4 B per element like fp32)
-        const double nb = batch;
+        const double nb = pl.batch;
         const double outs = (d.c ? 1.0 : 0.0) + (d.c_split ? 1.0 : 0.0) + (d.residual ? 1.0 : 0.0) + (d.accumulate ? 1.0 : 0.0);
-        static const char* kName[2][4] = {{"gemm_sp_nt", "gemm_sp_nn", "gemm_sp_tn_a", "gemm_sp_tn"},
-                                          {"gemm_sp_nt_bf16", "gemm_sp_nn_bf16", "gemm_sp_tn_a_bf16", "gemm_sp_tn_bf16"}};
-        rec = prof_begin(kName[sp][(d.a_kmajor ? 2 : 0) + (d.b_kmajor ? 1 : 0)],
-                         2.0 * d.M * d.N * (double)d.K * nb, 4.0 * nb * ((double)d.M * d.K + (double)d.N * d.K + outs * d.M * d.N), st);
+        rec = prof_begin(pl.prof_class, 2.0 * d.M * d.N * (double)d.K * nb, 4.0 * nb * ((double)d.M * d.K + (double)d.N * d.K + outs * d.M * d.N), st);
     }
-    if (sp) {
-        if (d.a_kmajor && d.b_kmajor) hipLaunchKernelGGL((gemm_sp_kernel<true, true, true>), g, b, 0, st, p);
-        else if (d.a_kmajor) hipLaunchKernelGGL((gemm_sp_kernel<true, false, true>), g, b, 0, st, p);
-        else if (d.b_kmajor) hipLaunchKernelGGL((gemm_sp_kernel<false, true, true>), g, b, 0, st, p);
-        else hipLaunchKernelGGL((gemm_sp_kernel<false, false, true>), g, b, 0, st, p);
-    } else {
-        if (d.a_kmajor && d.b_kmajor) hipLaunchKernelGGL((gemm_sp_kernel<true, true, false>), g, b, 0, st, p);
-        else if (d.a_kmajor) hipLaunchKernelGGL((gemm_sp_kernel<true, false, false>), g, b, 0, st, p);
-        else if (d.b_kmajor) hipLaunchKernelGGL((gemm_sp_kernel<false, true, false>), g, b, 0, st, p);
-        else hipLaunchKernelGGL((gemm_sp_kernel<false, false, false>), g, b, 0, st, p);
-    }
+    hipLaunchKernelGGL(kernels[d.mode == BD_MODE_BF16][d.a_kmajor != 0][d.b_kmajor != 0], dim3((unsigned)pl.grid), dim3(SP_NT), 0, st, p);
     BD_LAUNCH_CHECK("gemm_sp");
-    if (p.ksplit > 1) {
-        const long long work = (long long)d.M * (d.N / 8);
-        hipLaunchKernelGGL(gemm_sp_reduce, dim3((unsigned)cdiv(work, 256)), dim3(256), 0, st, p);
-        if (p.want_colsum)
-            hipLaunchKernelGGL(gemm_sp_colsum_reduce, dim3((unsigned)cdiv(d.M, 64)), dim3(64), 0, st,
-                               p.partial + ws.colsum_off / sizeof(float), p.ksplit, d.M, d.a_colsum);
+    if (pl.reduce) {
+        hipLaunchKernelGGL(gemm_sp_reduce, dim3((unsigned)cdiv((long long)d.M * (d.N / 8), 256)), dim3(256), 0, st, p);
+        if (pl.colsum_reduce)
+            hipLaunchKernelGGL(gemm_sp_colsum_reduce, dim3((unsigned)cdiv(d.M, 64)), dim3(64), 0, st, p.partial + pl.colsum_offset / sizeof(float),
+                               pl.ksplit, d.M, d.a_colsum);
         BD_LAUNCH_CHECK("gemm_sp_reduce");
     }
     prof_end(rec, st);
@@ -473,4 +475,9 @@ extern "C" size_t bd_gemm_sp_workspace_bytes(const bd_gemm_sp_desc* d) { return 
 extern "C" int bd_gemm_sp(const bd_gemm_sp_desc* d, bd_stream_t s) {
     BD_CHECK(d, BD_ERR_INVALID, "bd_gemm_sp: null descriptor");
     return bd::gemm_sp(*d, bd::S(s));
+}
+extern "C" int bd_gemm_sp_plan(const bd_gemm_sp_desc* d, bd_gemm_sp_plan_info* out) {
+    BD_CHECK(d != nullptr && out != nullptr, BD_ERR_INVALID, "bd_gemm_sp_plan: null descriptor or output");
+    *out = bd::sp_plan(*d);
+    return bd::sp_check(*d, *out, false);
 }

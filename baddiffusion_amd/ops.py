@@ -682,6 +682,20 @@ def gemm_sp(a_split, b_split, M, N, K, a_kmajor=False, b_kmajor=False, batch=1, 
     return (c, cs, colsum_t) if want_colsum else (c, cs)
 
 
+def gemm_sp_plan(M, N, K, batch=1, a_kmajor=False, b_kmajor=False, a_colsum=False, mode=0):
+    """bd_gemm_sp_plan of a dense call with an fp32 output as a dict: operand form (2 * a_kmajor + b_kmajor), tiles, batch, K split, grid,
+    second passes, workspace bytes, offset of the column-sum rows, profiler class.  Host only, nothing is launched; raises what bd_gemm_sp
+    would answer for a shape it refuses."""
+    lib = L.load()
+    ar, ac = (K, M) if a_kmajor else (M, K)
+    br, bc = (K, N) if b_kmajor else (N, K)
+    d = L.GemmSpDesc(M=M, N=N, K=K, batch=batch, lda=ac, a_bs=ar * ac, a_kmajor=int(a_kmajor), ldb=bc, b_bs=br * bc, b_kmajor=int(b_kmajor),
+                     c=16, ldc=N, c_bs=M * N, alpha=1.0, out_scale=1.0, a_colsum=16 if a_colsum else None, mode=mode)
+    info = L.GemmSpPlanInfo()
+    L.check(lib.bd_gemm_sp_plan(C.byref(d), C.byref(info)), "bd_gemm_sp_plan")
+    return _plan_dict(info)
+
+
 # ------------------------------------------------------------------------------------------------ small ops
 def colsum(x, rows_per_group):
     lib = L.load(); _need_cuda(x)

@@ -1268,6 +1268,25 @@ typedef struct {
 } bd_gemm_sp_desc;
 size_t bd_gemm_sp_workspace_bytes(const bd_gemm_sp_desc* d);
 int bd_gemm_sp(const bd_gemm_sp_desc* d, bd_stream_t stream);
+/* What bd_gemm_sp decides for a descriptor: host code only, a copy of the plan the launcher and bd_gemm_sp_workspace_bytes themselves
+ * read.  bd_gemm_sp_plan runs the checks of bd_gemm_sp on the descriptor's numbers (mode, shape, strides, accumulate / a_colsum rules:
+ * same status, same message) and launches nothing; it reads none of the descriptor's pointers beyond whether c, c_split, residual, bias
+ * and a_colsum are set, and neither needs nor checks a workspace.  For tests and tools that must know which branch a call takes
+ * (DESIGN.md "K split of the split-plane GEMM"). */
+typedef struct {
+    int form;                   /* operand form, 2 * a_kmajor + b_kmajor: 0 both K-contiguous ("nt"), 1 B K-major ("nn"), 2 A K-major
+                                   ("tn_a"), 3 both K-major ("tn") -- the kernel instantiation, with the descriptor's mode            */
+    int tiles_m, tiles_n;       /* 128 x 128 output tiles: M / 128, N / 128                                                       */
+    int batch;                  /* products: max(batch, 1)                                                                        */
+    int ksplit, chunks_per_split;   /* K slices and 32-element chunks per slice (the last slice may be shorter, never empty)      */
+    int reduce;                 /* 1: gemm_sp_reduce folds the slabs and applies the epilogue (ksplit > 1)                        */
+    int colsum_reduce;          /* 1: gemm_sp_colsum_reduce folds the partial rows of a_colsum (reduce, and a_colsum is set)      */
+    int64_t grid;               /* workgroups of the main kernel = tiles_m * tiles_n * batch * ksplit                             */
+    size_t workspace_bytes;     /* = bd_gemm_sp_workspace_bytes (with BD_GEMM_SP unset): ksplit * (M N + M) floats where reduce is set */
+    size_t colsum_offset;       /* bytes in front of the ksplit partial rows of a_colsum [ksplit][M] (behind the slabs), else 0   */
+    const char* prof_class;     /* the profiler class the launch is counted under                                                */
+} bd_gemm_sp_plan_info;
+int bd_gemm_sp_plan(const bd_gemm_sp_desc* d, bd_gemm_sp_plan_info* out);
 
 /* Attention core on split planes (attention.py:148-162 and its backward), N = 256 tokens, head dim 256:
  *   forward : o = softmax(scale * q k^T) v                         [+ pt_split = P^T planes, needed by the backward]

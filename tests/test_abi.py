@@ -17,7 +17,7 @@ def header_symbols():
 
 def test_header_declares_expected_entry_points():
     syms = header_symbols()
-    for s in ("bd_poison_qsample", "bd_ddpm_step", "bd_ddim_step", "bd_gn_fwd", "bd_gn_bwd", "bd_igemm", "bd_igemm_plan", "bd_conv3x3_fwd",
+    for s in ("bd_poison_qsample", "bd_ddpm_step", "bd_ddim_step", "bd_gn_fwd", "bd_gn_bwd", "bd_igemm", "bd_igemm_plan", "bd_gemm_sp", "bd_gemm_sp_plan", "bd_conv3x3_fwd",
               "bd_conv3x3_dgrad", "bd_conv3x3_wgrad", "bd_loss_fwd_bwd", "bd_adam_clip", "bd_unet_forward", "bd_unet_backward"):
         assert s in syms
 
@@ -47,7 +47,7 @@ def test_struct_layouts_match_header_sizes():
              "bd_upsample_conv_desc": L.UpsampleConvDesc, "bd_conv2d_desc": L.Conv2dDesc, "bd_conv3x3_s2_dgrad_desc": L.ConvS2DgradDesc,
              "bd_gn_plan_info": L.GnPlanInfo, "bd_igemm_plan_info": L.IgemmPlanInfo,
              "bd_conv3x3_thin_plan_info": L.ThinPlanInfo, "bd_conv3x3_ps_plan_info": L.ConvPsPlanInfo,
-             "bd_conv3x3_ps_wgrad_plan_info": L.ConvPsWgradPlanInfo}
+             "bd_conv3x3_ps_wgrad_plan_info": L.ConvPsWgradPlanInfo, "bd_gemm_sp_desc": L.GemmSpDesc, "bd_gemm_sp_plan_info": L.GemmSpPlanInfo}
     prog = '#include <stdio.h>\n#include "bd_hip.h"\nint main(){' + "".join(
         f'printf("{n} %zu\\n", sizeof({n}));' for n in names) + "return 0;}"
     import tempfile

@@ -214,6 +214,72 @@ def test_large_logits_are_exact_and_wide(B, heads):
     assert float(logits.max()) > 88.7 and float(logits.min()) < -88.7
 
 
+# ------------------------------------------------------------------------------------------------ refusals (no GPU)
+ERR_INVALID, ERR_UNSUPPORTED = -1, -2
+FAKE = [0x40000000 * (i + 1) for i in range(6)]      # 128-byte aligned addresses, never dereferenced: every call below is turned away
+SHAPE_TEXT = b"%s: needs N == 256 and head dim 256 (got N %d, dh %d)"
+QKV_TEXT = b"%s: qkv planes must be 128-byte aligned with a row stride >= 3C, multiple of 32"
+FWD, BWD = b"bd_attn_sp_fwd", b"bd_attn_sp_bwd"
+# (entry points, fields changed on a good descriptor of B = 2, heads = 2: C = 512, status, message with the entry point's name left out)
+ATTN_REFUSALS = [
+    ((FWD, BWD), dict(N=128), ERR_UNSUPPORTED, SHAPE_TEXT.replace(b"%d, dh %d", b"128, dh 256")),
+    ((FWD, BWD), dict(dh=64), ERR_UNSUPPORTED, SHAPE_TEXT.replace(b"%d, dh %d", b"256, dh 64")),
+    ((FWD, BWD), dict(B=0), ERR_UNSUPPORTED, SHAPE_TEXT.replace(b"%d, dh %d", b"256, dh 256")),
+    ((FWD, BWD), dict(heads=0), ERR_UNSUPPORTED, SHAPE_TEXT.replace(b"%d, dh %d", b"256, dh 256")),
+    ((FWD, BWD), dict(qkv_split=None), ERR_INVALID, QKV_TEXT),
+    ((FWD, BWD), dict(ld=1024), ERR_INVALID, QKV_TEXT),                      # below 3C = 1536
+    ((FWD, BWD), dict(ld=1552), ERR_INVALID, QKV_TEXT),                      # no multiple of 32
+    ((FWD, BWD), dict(qkv_split=FAKE[0] + 64), ERR_INVALID, QKV_TEXT),
+    ((FWD, BWD), dict(mode=3), ERR_INVALID, b"%s: unknown compute mode 3"),
+    ((FWD,), dict(o_split=None), ERR_INVALID, b"%s: bad output planes"),
+    ((FWD,), dict(ldo=256), ERR_INVALID, b"%s: bad output planes"),
+    ((FWD,), dict(ldo=528), ERR_INVALID, b"%s: bad output planes"),
+    ((FWD,), dict(o_split=FAKE[1] + 64), ERR_INVALID, b"%s: bad output planes"),
+    ((FWD,), dict(pt_split=FAKE[2] + 2), ERR_INVALID, b"%s: P^T planes must be 128-byte aligned"),
+    ((BWD,), dict(pt_split=None), ERR_INVALID, b"%s: null pointer"),
+    ((BWD,), dict(do_split=None), ERR_INVALID, b"%s: null pointer"),
+    ((BWD,), dict(dst_split=None), ERR_INVALID, b"%s: null pointer"),
+    ((BWD,), dict(dqkv_split=None), ERR_INVALID, b"%s: null pointer"),
+    ((BWD,), dict(lddo=256), ERR_INVALID, b"%s: bad row strides"),
+    ((BWD,), dict(lddo=528), ERR_INVALID, b"%s: bad row strides"),
+    ((BWD,), dict(lddqkv=1024), ERR_INVALID, b"%s: bad row strides"),
+    ((BWD,), dict(lddqkv=1552), ERR_INVALID, b"%s: bad row strides"),
+    ((BWD,), dict(pt_split=FAKE[2] + 64), ERR_INVALID, b"%s: planes must be 128-byte aligned"),
+    ((BWD,), dict(do_split=FAKE[3] + 2), ERR_INVALID, b"%s: planes must be 128-byte aligned"),
+    ((BWD,), dict(dst_split=FAKE[4] + 32), ERR_INVALID, b"%s: planes must be 128-byte aligned"),
+    ((BWD,), dict(dqkv_split=FAKE[5] + 64), ERR_INVALID, b"%s: planes must be 128-byte aligned"),
+    # two faults at once: the first of the entry point's order is the one reported
+    ((FWD, BWD), dict(N=128, mode=3), ERR_UNSUPPORTED, SHAPE_TEXT.replace(b"%d, dh %d", b"128, dh 256")),
+    ((FWD, BWD), dict(ld=1024, mode=3), ERR_INVALID, QKV_TEXT),
+    ((FWD, BWD), dict(mode=3, o_split=None, do_split=None), ERR_INVALID, b"%s: unknown compute mode 3"),
+    ((FWD,), dict(ldo=256, pt_split=FAKE[2] + 2), ERR_INVALID, b"%s: bad output planes"),
+    ((BWD,), dict(dst_split=None, lddo=256), ERR_INVALID, b"%s: null pointer"),
+    ((BWD,), dict(dqkv_split=None, pt_split=FAKE[2] + 64), ERR_INVALID, b"%s: null pointer"),
+    ((BWD,), dict(lddqkv=1024, do_split=FAKE[3] + 2), ERR_INVALID, b"%s: bad row strides"),
+]
+
+
+@pytest.mark.parametrize("who,kw,status,text", ATTN_REFUSALS, ids=[f"{i}-{'-'.join(r[1])}" for i, r in enumerate(ATTN_REFUSALS)])
+def test_refusals_keep_their_status_message_and_order(who, kw, status, text):
+    """bad N / dh, bad mode, missing or misaligned planes and short or odd row strides: the host checks of both entry points, in the order
+    they have always been reported (the backward: null pointers, then strides, then alignment).  No descriptor here reaches a launch."""
+    import os
+    assert "BD_ATTN_SP" not in os.environ, "BD_ATTN_SP=0 turns every call away at the first check"
+    from baddiffusion_amd.build import build_lib
+    build_lib(force=False, verbose=False)
+    from baddiffusion_amd import _lib as L
+    lib = L.load()
+    good = dict(B=2, heads=2, N=N, dh=DH, qkv_split=FAKE[0], ld=1536, scale=SCALE, o_split=FAKE[1], ldo=512, pt_split=FAKE[2], do_split=FAKE[3],
+                lddo=512, dst_split=FAKE[4], dqkv_split=FAKE[5], lddqkv=1536, mode=BF16X3)
+    d = L.AttnSpDesc(**{**good, **kw})
+    for name in who:
+        fn = lib.bd_attn_sp_fwd if name == FWD else lib.bd_attn_sp_bwd
+        assert fn(ctypes.byref(d), None) == status and lib.bd_last_error() == text.replace(b"%s", name), (name, kw, lib.bd_last_error())
+    assert lib.bd_attn_sp_fwd(None, None) == ERR_INVALID and lib.bd_last_error() == b"bd_attn_sp_fwd: null descriptor"
+    assert lib.bd_attn_sp_bwd(None, None) == ERR_INVALID and lib.bd_last_error() == b"bd_attn_sp_bwd: null descriptor"
+    assert (lib.bd_attn_sp_supported(256, 256), lib.bd_attn_sp_supported(128, 256), lib.bd_attn_sp_supported(256, 512)) == (1, 0, 0)
+
+
 # ------------------------------------------------------------------------------------------------ GPU
 @pytest.fixture(scope="module")
 def dev():

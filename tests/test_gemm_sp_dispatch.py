@@ -1,10 +1,11 @@
 """Exact-value tests for the K-split branches, the operand forms, the outputs and the strides of the split-plane GEMM (bd_gemm_sp:
 csrc/gemm_sp.hip), in the manner of tests/test_conv_ps_dispatch.py.
 
-sp_ws() splits K over workgroups when batch <= 1, tiles < CUs and K / 32 >= 32:
+sp_plan() splits K over workgroups when batch <= 1, tiles < CUs and K / 32 >= 32:
     ksplit = min(ceil(CUs / tiles), nch / 8),  cps = ceil(nch / ksplit),  ksplit = ceil(nch / cps)        (nch = K / 32)
-Each case below pins one shape of that rule (test_case_table_follows_the_split_rule restates it; the GPU tests assert the workspace the ABI
-asks for -- ksplit * (M N + M) * 4 bytes, or 0 -- before they launch anything): a single chunk (stage 0 of the ring only), an odd chunk count, an
+Each case below pins one shape of that rule (test_case_table_follows_the_split_rule restates it; the GPU tests assert what bd_gemm_sp_plan
+reports -- ksplit, chunks per slice, profiler class -- and the workspace the ABI asks for -- ksplit * (M N + M) * 4 bytes, or 0 -- before they
+launch anything; tests/test_gemm_sp_plan_host.py checks the table, the rule's boundaries and the refusals without a device): a single chunk (stage 0 of the ring only), an odd chunk count, an
 odd cps with a ragged last slice, nine slices (the column-sum fold's group of eight plus its tail loop), a last slice of one chunk, and a long K
 under a batch, which must not split.  Every case runs in the four operand forms (K-contiguous / K-major A and B), both compute modes, both
 operand sets, with fp32, fp32 + plane and plane-only outputs (c == NULL: what the QKV projection and its data gradient ask for), without and
@@ -21,7 +22,7 @@ fp32 outputs are written into NaN-filled buffers, plane outputs into buffers pre
 behind the last one; the strided variant places operands and outputs as column blocks of wider buffers (ld > row length, a 32-aligned column
 offset, batch strides beyond M * ld) and requires every byte outside the [M, N] windows to be unchanged.
 
-The case table holds for 256 CUs; on another device the GPU tests skip.  Whoever retunes sp_ws() moves the cases with it (DESIGN.md,
+The case table holds for 256 CUs; on another device the GPU tests skip.  Whoever retunes sp_plan() moves the cases with it (DESIGN.md,
 "K split of the split-plane GEMM").
 
 Observed on MI355X (256 CUs): every case, form, mode, set, output and epilogue combination is equal to the reference, bit for bit; no case
@@ -58,7 +59,7 @@ STRIDED_PARAMS = [pytest.param(cid, akm, bkm, id=f"{cid}-{form_id(akm, bkm)}") f
 
 
 def split_rule(M, N, K, batch, cus=EXPECTED_CUS):
-    """sp_ws() of gemm_sp.hip -> (ksplit, chunks per slice, chunks of the last slice)"""
+    """the K split of sp_plan() of gemm_sp.hip, restated -> (ksplit, chunks per slice, chunks of the last slice)"""
     nch = K // 32
     tiles = (M // 128) * (N // 128) * max(batch, 1)
     ksplit = 1
@@ -209,9 +210,9 @@ class Buf:
         return describe(bits(chk), bits(self.init).double().cpu())
 
 
-def launch(dev, M, N, K, batch, a, akm, b, bkm, mode, expect_ws, c=None, cs=None, bias=None, res=None, alpha=1.0, out_scale=1.0, accumulate=False,
-           colsum=None):
+def launch(dev, cid, a, akm, b, bkm, mode, c=None, cs=None, bias=None, res=None, alpha=1.0, out_scale=1.0, accumulate=False, colsum=None):
     lib, L = dev
+    M, N, K, batch, ksplit, cps = CASES[cid][:6]
     d = L.GemmSpDesc(M=M, N=N, K=K, batch=batch, a=a.ptr, lda=a.ld, a_bs=a.bs, a_kmajor=int(akm), b=b.ptr, ldb=b.ld, b_bs=b.bs, b_kmajor=int(bkm),
                      alpha=alpha, out_scale=out_scale, accumulate=int(accumulate), bias=L.ptr(bias), a_colsum=L.ptr(colsum), mode=mode)
     if c is not None:
@@ -220,8 +221,12 @@ def launch(dev, M, N, K, batch, a, akm, b, bkm, mode, expect_ws, c=None, cs=None
         d.c_split, d.ldcs, d.cs_bs = cs.ptr, cs.ld, cs.bs
     if res is not None:
         d.residual, d.ldr, d.r_bs = res.ptr, res.ld, res.bs
+    info = L.GemmSpPlanInfo()                                                # the branch, before anything is launched
+    L.check(lib.bd_gemm_sp_plan(ctypes.byref(d), ctypes.byref(info)), "bd_gemm_sp_plan")
+    want_class = PROF_CLASS[(akm, bkm)] + ("_bf16" if mode == BF16 else "")
+    assert (info.ksplit, info.chunks_per_split, info.prof_class.decode()) == (ksplit, cps, want_class), ("plan", cid, info.ksplit, info.chunks_per_split, info.prof_class)
     need = lib.bd_gemm_sp_workspace_bytes(ctypes.byref(d))
-    assert need == expect_ws, ("workspace", need, expect_ws)                 # the branch, before anything is launched
+    assert need == workspace_bytes(cid) == info.workspace_bytes, ("workspace", need, workspace_bytes(cid), info.workspace_bytes)
     ws = torch.empty(max(need, 256), dtype=torch.uint8, device="cuda")
     d.workspace, d.workspace_bytes = (ws.data_ptr(), need) if need else (None, 0)
     L.check(lib.bd_gemm_sp(ctypes.byref(d), L.stream()), "bd_gemm_sp")
@@ -230,7 +235,6 @@ def launch(dev, M, N, K, batch, a, akm, b, bkm, mode, expect_ws, c=None, cs=None
 def check_case(dev, cid, akm, bkm, opset, lay, combos, profile):
     """run the case in both modes; combos: (outputs in {"f32", "both", "planes"}, epilogue?, accumulate?)"""
     M, N, K, batch = CASES[cid][:4]
-    expect_ws = workspace_bytes(cid)
     o = operands(cid, opset)
     refs = {}
     for shared in ((False, True) if batch > 1 else (False,)):
@@ -250,8 +254,8 @@ def check_case(dev, cid, akm, bkm, opset, lay, combos, profile):
                 ref = epilogue64(prod, o, epi, acc)
                 c = Buf(False, batch, M, N, lay, o["prev"] if acc else None) if outs != "planes" else None
                 cs = Buf(True, batch, M, N, lay) if outs != "f32" else None
-                run = lambda: launch(dev, M, N, K, batch, a, akm, b, bkm, mode, expect_ws, c=c, cs=cs, bias=bias if epi else None,
-                                     res=res if epi else None, alpha=ALPHA if epi else 1.0, out_scale=OUT_SCALE if epi else 1.0, accumulate=acc)
+                run = lambda: launch(dev, cid, a, akm, b, bkm, mode, c=c, cs=cs, bias=bias if epi else None, res=res if epi else None,
+                                     alpha=ALPHA if epi else 1.0, out_scale=OUT_SCALE if epi else 1.0, accumulate=acc)
                 if profile and n_run == 0 and not shared:
                     _, counts = bracketed(run)
                     want = PROF_CLASS[(akm, bkm)] + ("_bf16" if mode == BF16 else "")
@@ -301,8 +305,8 @@ def test_gemm_sp_column_sums_are_exact(dev, cid, opset):
         ref = product64(prep(o["a"]), prep(o["b"]), False)
         c0, c1 = Buf(False, 1, M, N, DENSE), Buf(False, 1, M, N, DENSE)
         colsum = torch.full((M + 64,), float("nan"), device="cuda")
-        launch(dev, M, N, K, 1, a, True, b, True, mode, workspace_bytes(cid), c=c0)
-        launch(dev, M, N, K, 1, a, True, b, True, mode, workspace_bytes(cid), c=c1, colsum=colsum)
+        launch(dev, cid, a, True, b, True, mode, c=c0)
+        launch(dev, cid, a, True, b, True, mode, c=c1, colsum=colsum)
         got = colsum[:M].double().cpu()
         assert torch.equal(got, sum_ref), (cid, opset, mode, "a_colsum", describe(got[None], sum_ref[None]))
         assert bool(torch.isnan(colsum[M:]).all()), (cid, opset, mode, "a_colsum store past M")
